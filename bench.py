@@ -18,6 +18,10 @@ Workloads (synthetic seeded triangle soups, lists built by
     lambert_4k   3840x2160, 1M triangles (edge 0.004), as lambert_1m
     lambert_10m_4k  3840x2160, 10M triangles (edge 0.0013), as lambert_1m (BASELINE config 5 on one GPU)
 One JSON line on stdout (rank 0); progress goes to stderr.
+
+--dump-outputs DIR: after the timed frames, rank 0 writes the last timed frame's three planes (what RaytraceAll hands its caller)
+as DIR/out_r.npy, out_g.npy, out_b.npy in float32 (u16 values, exact), shape (H, W).  Above DUMP_BYTES_MAX a fixed seeded sample of
+pixels is written instead, the same for every plane, with their row-major pixel indices in DIR/pixel_index.npy (float64).
 """
 import argparse
 import json
@@ -39,6 +43,8 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0  # ... and the measured float4-copy ceiling (report both fractions)
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20240607
 
 
 def log(*a):
@@ -52,6 +58,24 @@ def algorithmic_bytes(stats: dict, lights: int) -> float:
     + boxMin (4112 B) and lights (60 B each) once per frame."""
     return (20.0 * stats["primarySamples"] + 68.0 * stats["primaryCandidates"] + 8.0 * stats["gridCells"] + 68.0 * stats["gridCandidates"]
             + 124.0 * stats["shadedHits"] + 40.0 * stats["texelFetches"] + 4112.0 + 60.0 * lights)
+
+
+def dump_outputs(out_dir: str, planes: np.ndarray) -> None:
+    """planes: (3, H, W) u16, the frame as the caller receives it.  Whole planes when they fit DUMP_BYTES_MAX, otherwise the same
+    seeded pixel sample of every plane (sorted row-major indices), so that two builds dump the same pixels."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = ("out_r", "out_g", "out_b")
+    pixels = planes.shape[1] * planes.shape[2]
+    if 3 * 4 * pixels + 4096 <= DUMP_BYTES_MAX:
+        for name, p in zip(names, planes):
+            np.save(os.path.join(out_dir, name + ".npy"), p.astype(np.float32))
+        return
+    n = (DUMP_BYTES_MAX - 4096) // (3 * 4 + 8)  # three float32 values and one float64 index per sampled pixel
+    idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(pixels, n, replace=False))
+    flat = planes.reshape(3, -1)
+    for name, p in zip(names, flat):
+        np.save(os.path.join(out_dir, name + ".npy"), p[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
 
 
 def make_scene(name: str, samples: int):
@@ -79,7 +103,11 @@ def main():
     ap.add_argument("--workload", default="lambert_1m", choices=sorted(WORKLOADS))
     ap.add_argument("--samples", type=int, default=1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame's planes as DIR/<name>.npy (float32; a seeded sample above 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -330,6 +358,8 @@ def main():
     rehearsal_bad = 0
     if rank == 0:
         got = planes.cpu().numpy().view(np.uint16).reshape(3, H, W)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got)
         ms_per_step = 1e3 * elapsed / args.steps
         primary_rays = float(P) * S
         total_rays = primary_rays + total_stats["gridRays"]

@@ -13,6 +13,8 @@ scene inputs in the ABI layouts and the expected u16 planes / function results.
   scene_<name>.npz   inputs (grid start stored sparsely as non-empty cell ids + counts) and planes R,G,B
   kat.npz            function-level known answers (randF, GetSpherePoint, positive_modf, RayIntersectsTriangle,
                      GetPointToLineSqLen, GetBoxAddress, BindInCube)
+  ref_fresh_scenes.npz  planes R,G,B ("<seed>_r", "_g", "_b") of scenarios.fresh_soup(seed) for scenarios.FRESH_SEEDS
+                     (inputs not stored: the test regenerates them from the seed)
 """
 import ctypes as C
 import os
@@ -133,10 +135,20 @@ def make_kat(path):
     np.savez_compressed(path, **kat)
 
 
+def make_fresh(path):
+    planes = {}
+    for seed in scenarios.FRESH_SEEDS:
+        sc = scenarios.fresh_soup(seed)
+        R.build_lists(sc)
+        for c, p in zip("rgb", O.ref_render(sc)):
+            planes[f"{seed}_{c}"] = p
+    np.savez_compressed(path, **planes)
+
+
 def main():
     if not O.have_ref():
         sys.exit("oracle/_ref/libref_kernel.so missing: run `make -C oracle` where /root/reference exists")
-    only = set(sys.argv[1:])  # optional: names of the fixtures to (re)write, "kat" for kat.npz; default = everything
+    only = set(sys.argv[1:])  # optional: names of the fixtures to (re)write, "kat" / "fresh" for kat.npz / ref_fresh_scenes.npz; default = everything
     for f in scenarios.ALL:
         if only and f.__name__ not in only:
             continue
@@ -149,6 +161,9 @@ def main():
     if not only or "kat" in only:
         make_kat(os.path.join(HERE, "kat.npz"))
         print("kat.npz written")
+    if not only or "fresh" in only:
+        make_fresh(os.path.join(HERE, "ref_fresh_scenes.npz"))
+        print("ref_fresh_scenes.npz written")
 
 
 if __name__ == "__main__":

@@ -125,6 +125,22 @@ def odd_size_multi_tile():
 ALL = [lambert_distant, primary_only, all_light_types, spot_finite_range, no_material, mixed_materials_textured,
        mirror_hall, degenerate_and_outside, sparse_many_samples, odd_size_multi_tile]
 
+FRESH_SEEDS = (101, 202, 303)
+
+
+def fresh_soup(seed):
+    """Random materials (every channel, bump maps), random lights of types 0..9 and a smooth-normal soup, drawn from the seed
+    alone: scenes nobody picked, beside the curated ones above.  The reference's planes for FRESH_SEEDS are stored in
+    tests/golden/ref_fresh_scenes.npz."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    mats = [dict(color=tuple(rng.integers(0, 256, 3)), reflection=tuple(rng.integers(0, 200, 3)),
+                 transparency=tuple(rng.integers(0, 200, 3)), bump=rng.integers(0, 256, (5, 5, 3)),
+                 luminance=tuple(rng.integers(0, 60, 3))) for _ in range(3)]
+    lights = [dict(type=int(rng.integers(0, 10)), pos=tuple(rng.uniform(-1, 1, 3)), dir=tuple(rng.uniform(-1, 1, 3)),
+                   col=tuple(rng.uniform(0, 1, 3)), radius=float(rng.uniform(0, 1)), half_att=float(rng.choice([np.inf, 1.5])))
+              for _ in range(3)]
+    return S.make_soup(40, 32, 500, 0.3, seed=seed, samples=2, materials=mats, lights=lights, random_uv=True, smooth_normals=True)
+
 
 def by_name(name):
     for f in ALL:

@@ -1,6 +1,6 @@
 """CPU tests: the oracle (C restatement) against the golden fixtures minted from the reference kernel, against the
-function-level known answers, and -- where oracle/_ref exists (the build container) -- against the reference kernel
-itself on freshly generated scenes."""
+function-level known answers, and against the reference kernel's stored planes of seeded random scenes (where
+oracle/_ref exists, against the reference kernel itself as well)."""
 import ctypes as C
 import os
 
@@ -104,21 +104,19 @@ def test_kat_box_address_and_bind(kat):
         assert got.tobytes() == kat["bind_res"][i].tobytes(), i
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference; build container only)")
-@pytest.mark.parametrize("seed", [101, 202, 303])
+@pytest.mark.parametrize("seed", scenarios.FRESH_SEEDS)
 def test_oracle_matches_reference_kernel_on_fresh_scenes(seed):
-    """Fresh seeds, not the committed fixtures: restatement == reference kernel, plane for plane."""
-    from opencl_render_amd import raytrace as R, scene as S
-    rng = np.random.Generator(np.random.PCG64(seed))
-    mats = [dict(color=tuple(rng.integers(0, 256, 3)), reflection=tuple(rng.integers(0, 200, 3)),
-                 transparency=tuple(rng.integers(0, 200, 3)), bump=rng.integers(0, 256, (5, 5, 3)),
-                 luminance=tuple(rng.integers(0, 60, 3))) for _ in range(3)]
-    lights = [dict(type=int(rng.integers(0, 10)), pos=tuple(rng.uniform(-1, 1, 3)), dir=tuple(rng.uniform(-1, 1, 3)),
-                   col=tuple(rng.uniform(0, 1, 3)), radius=float(rng.uniform(0, 1)), half_att=float(rng.choice([np.inf, 1.5])))
-              for _ in range(3)]
-    sc = S.make_soup(40, 32, 500, 0.3, seed=seed, samples=2, materials=mats, lights=lights, random_uv=True, smooth_normals=True)
+    """Seeded random scenes, not the curated ones: restatement == reference kernel, plane for plane.  The reference's planes
+    are stored (tests/golden/ref_fresh_scenes.npz, minted by make_golden.py); where oracle/_ref exists the reference kernel
+    is run as well and must still give the stored planes."""
+    from opencl_render_amd import raytrace as R
+    sc = scenarios.fresh_soup(seed)
     R.build_lists(sc)
+    stored = np.load(os.path.join(GOLDEN, "ref_fresh_scenes.npz"))
+    want = [stored[f"{seed}_{c}"] for c in "rgb"]
     a = O.oracle_render(sc)
-    b = O.ref_render(sc)
-    for x, y in zip(a, b):
-        assert np.array_equal(x, y)
+    for ch, x, y in zip("RGB", a, want):
+        assert np.array_equal(x, y), f"seed {seed}: plane {ch} differs from the reference's in {(x != y).sum()} pixels"
+    if O.have_ref():
+        for ch, x, y in zip("RGB", O.ref_render(sc), want):
+            assert np.array_equal(x, y), f"seed {seed}: the reference kernel no longer gives the stored plane {ch}"
