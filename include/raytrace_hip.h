@@ -428,7 +428,8 @@ int rtHipDeviceKat(int device, int op, cl_uint count, const void *in, cl_uint in
  * down, make them redo themselves or fail); every tuning value and every fault injector of the tests is set here, process-wide,
  * and applies to scenes built afterwards.  Keys (rt_api.cpp, struct Tuning): "reset" (all defaults), "stage_mb", "extra_factor",
  * "state_mb", "groups", "lookahead", "seg0".."seg4", "seg_rays0".."seg_rays3", "fast_quotient", "spin_limit", "append_rays", "ordered_first", "extra_factor",
- * "slice_rays", "small_slices", "group_rays", "blocking", "batch_plan", "pipeline", "timing", "cache", and the test hooks "plan_rounds",
+ * "slice_rays", "small_slices", "group_rays", "blocking", "batch_plan", "pipeline", "timing", "cache", "logic_class" (0: every scene's
+ * paths run on the general logic kernel; 1, the default: on the kernel of the scene's path class), and the test hooks "plan_rounds",
  * "plan_grid_tiny", "virtual_devices".  Returns 0, -1 for an unknown key. */
 int rtHipTune(const char *key, double value);
 
@@ -440,6 +441,14 @@ int rtHipTestCachePointers(const void *out[6]);
 /* TEST-ONLY: the content hash RaytraceAll's scene cache compares per input array (rt_api.cpp, hash_chunk), on the host.  Two byte
  * strings that differ must hash differently for the cache to notice an edit; tests/test_abi.py probes the tail handling. */
 uint64_t rtHipTestHashBytes(const void *bytes, uint64_t count);
+
+/* The path class a scene description falls in, on the host (no device needed): 1 = opaque-diffuse (every material's reflection,
+ * transparency and luminance absent or one black texel, every height map absent or one texel, at most one light), 0 = general.  The
+ * arrays must be host memory.  Returns -1 on an invalid description. */
+int rtHipScenePathClass(const rtHipSceneDesc *desc);
+
+/* TEST-ONLY: the path class a resident scene's logic kernels run (0 when "logic_class" was 0 at its build).  -1 for NULL. */
+int rtHipTestPathClass(const rtHipScene *scene);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,7 @@ struct Tuning {
     uint32_t virtualDevices = 0;    // test hook: the all-GPUs id deals the tiles over this many instances on the devices that are there
     uint32_t cache = 1;             // 0: RaytraceAll builds and frees per call, like the reference
     uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
+    uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
 };
 Tuning g_tune;
 std::mutex g_tuneMutex;
@@ -227,6 +228,7 @@ struct rtHipScene {
     uint32_t gridListSizeHint = 0;  // scene description with device arrays: scenePixelTriangleListStart[256^3], fetched by scene_build
     bool haveGridListSize = false;
     bool wfMultiLight = false;     // what the path-state buffers were sized for
+    bool classMaterials = false, classLights = false; // the materials part / the lights part admit the opaque-diffuse path class
     uint64_t bytes = 0;
     std::vector<cl_uint> tileIds;
     uint32_t width = 0, height = 0, tilesX = 0;
@@ -510,6 +512,27 @@ int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
     return 0;
 }
 
+// The path class (RtDevScene::pathClass) is decided per part: the materials (every reflection, transparency and luminance channel absent or one
+// black texel, every height map absent or one texel; the colour channel is free) and the lights (at most one, of any type).
+bool materials_admit_opaque_diffuse(const rtHipSceneDesc *d)
+{
+    for (uint32_t m = 0; m < d->materialCount; ++m)
+        for (int c = 1; c < 5; ++c) { // reflection, transparency, bump, luminance (raytrace_opencl.h:14-22)
+            const uint32_t w = d->matSize[5 * m + c].s[0], h = d->matSize[5 * m + c].s[1];
+            if (w == 0u) continue; // absent (matRec descriptor 0)
+            if (w != 1u || h != 1u) return false; // an image
+            if (c == 3) continue; // a one-texel height map: any texel
+            const cl_uchar *px = d->textures[d->matStart[5 * m + c]].s;
+            if (px[0] | px[1] | px[2]) return false; // only 0x80000000, black, reads as 0
+        }
+    return true;
+}
+bool lights_admit_opaque_diffuse(const rtHipSceneDesc *d) { return d->lightCount <= 1u; }
+void derive_path_class(rtHipScene *sc)
+{
+    sc->dev.pathClass = (sc->tune.logicClass && sc->classMaterials && sc->classLights) ? RT_PATH_CLASS_OPAQUE_DIFFUSE : RT_PATH_CLASS_GENERAL;
+}
+
 int build_materials(rtHipScene *sc, const rtHipSceneDesc *d)
 {
     sc->release_part(PART_MATERIALS);
@@ -539,6 +562,8 @@ int build_materials(rtHipScene *sc, const rtHipSceneDesc *d)
             }
         if (sc->upload(rec.data(), rec.size(), &D.matRec, "matRec")) return -1;
     }
+    sc->classMaterials = materials_admit_opaque_diffuse(d); // (the channel starts were checked above)
+    derive_path_class(sc);
     HIP_OK(sc->stager.drain());
     return 0;
 }
@@ -566,6 +591,8 @@ int build_lights(rtHipScene *sc, const rtHipSceneDesc *d)
     if (sc->upload(d->lightRadius, d->lightCount, &D.lightRadius, "lightRadius")) return -1;
     if (sc->upload(d->lightHalfAtt, d->lightCount, &D.lightHalfAtt, "lightHalfAttenuationDistance")) return -1;
     if (sc->upload(spread.data(), d->lightCount, &D.lightSpread, "lightSpread")) return -1;
+    sc->classLights = lights_admit_opaque_diffuse(d);
+    derive_path_class(sc);
     HIP_OK(sc->stager.drain());
     return 0;
 }
@@ -713,9 +740,15 @@ int clone_part(rtHipScene *dst, const rtHipScene *src, int part)
         D.planesTame = S.planesTame; D.cellCount = S.cellCount;
         RT_MOVE(boxMin); RT_MOVE(cellLut); RT_MOVE(gridStart); RT_MOVE(gridList); RT_MOVE(gridBits); RT_MOVE(gridBlockSparse); RT_MOVE(pairRec);
     }
-    if (part == PART_MATERIALS) { D.materialCount = S.materialCount; D.texelCount = S.texelCount; RT_MOVE(matSize); RT_MOVE(matStart); RT_MOVE(textures); RT_MOVE(matRec); }
+    if (part == PART_MATERIALS) {
+        D.materialCount = S.materialCount; D.texelCount = S.texelCount; RT_MOVE(matSize); RT_MOVE(matStart); RT_MOVE(textures); RT_MOVE(matRec);
+        dst->classMaterials = src->classMaterials;
+        derive_path_class(dst);
+    }
     if (part == PART_LIGHTS) {
         D.lightCount = S.lightCount;
+        dst->classLights = src->classLights;
+        derive_path_class(dst);
         RT_MOVE(lightType); RT_MOVE(lightPos); RT_MOVE(lightDir); RT_MOVE(lightCol); RT_MOVE(lightRadius); RT_MOVE(lightHalfAtt); RT_MOVE(lightSpread);
     }
 #undef RT_MOVE
@@ -1477,6 +1510,7 @@ int rtHipTune(const char *key, double value)
         { "fast_quotient", &T.fastQuotient }, { "spin_limit", &T.spinLimit }, { "append_rays", &T.appendRays }, { "ordered_first", &T.orderedFirst }, { "slice_rays", &T.sliceRays },
         { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
+        { "logic_class", &T.logicClass },
     };
     if (k == "state_mb") { T.stateMb = (uint64_t)(value < 0 ? 0 : value); return 0; }
     for (auto &e : table)
@@ -1492,6 +1526,23 @@ int rtHipTestCachePointers(const void *out[6])
     const RtDevScene &D = g_cache.scenes[0]->dev;
     out[0] = D.triRec; out[1] = D.triShade; out[2] = D.pairRec; out[3] = D.matRec; out[4] = D.textures; out[5] = D.camList;
     return 0;
+}
+
+int rtHipTestPathClass(const rtHipScene *scene)
+{
+    if (!scene) return -1;
+    return (int)scene->dev.pathClass;
+}
+
+int rtHipScenePathClass(const rtHipSceneDesc *desc)
+{
+    if (!desc) return fail("rtHipScenePathClass: null scene description");
+    if (desc->arraysOnDevice) return fail("rtHipScenePathClass: the description's arrays are device memory");
+    if (desc->materialCount && (!desc->matSize || !desc->matStart || !desc->textures)) return fail("rtHipScenePathClass: null material array");
+    for (uint32_t i = 0; i < desc->materialCount * 5; ++i)
+        if (desc->matSize[i].s[0] == 1u && desc->matSize[i].s[1] == 1u && ((int64_t)desc->matStart[i] < 0 || (uint64_t)desc->matStart[i] >= desc->texturesSize))
+            return fail("rtHipScenePathClass: material channel %u starts outside the atlas", i);
+    return (materials_admit_opaque_diffuse(desc) && lights_admit_opaque_diffuse(desc)) ? RT_PATH_CLASS_OPAQUE_DIFFUSE : RT_PATH_CLASS_GENERAL;
 }
 
 uint64_t rtHipTestHashBytes(const void *bytes, uint64_t count) { return hash_chunk((const unsigned char *)bytes, (size_t)count); }

@@ -324,7 +324,8 @@ __device__ __forceinline__ float tame_quotient(float n, float d, float r1)
 }
 
 // ---- shading normal (raytrace_opencl.c:195-263) -----------------------------------------------------------------
-template <bool COUNT>
+// ONE_TEXEL_BUMP: the caller knows the height map is absent or one texel (the opaque-diffuse path class): the image look-ups are not compiled.
+template <bool COUNT, bool ONE_TEXEL_BUMP = false>
 __device__ V3 shading_normal(const RtDevScene &S, const Shared &sh, V3 where, V3 ray_o, V3 ray_d, uint32_t tri, float l1, float l2,
                              const float *shade, int m, Counters &cn, const MatRec *mat = nullptr, const float4 *firstVertex = nullptr)
 {
@@ -344,20 +345,20 @@ __device__ V3 shading_normal(const RtDevScene &S, const Shared &sh, V3 where, V3
 
     if (0 <= m) {
         const bool oneTexel = mat && (mat->desc[CH_BUMP] & 0x80000000u); // the height map is one texel, held in the descriptor
-        const uint32_t bw = oneTexel ? 1u : ((mat && mat->desc[CH_BUMP] == 0u) ? 0u : S.matSize[2 * (CH_COUNT * m + CH_BUMP)]);
+        const uint32_t bw = oneTexel ? 1u : ((ONE_TEXEL_BUMP || (mat && mat->desc[CH_BUMP] == 0u)) ? 0u : S.matSize[2 * (CH_COUNT * m + CH_BUMP)]);
         if (0 < bw) {
             const uint32_t bh = oneTexel ? 1u : S.matSize[2 * (CH_COUNT * m + CH_BUMP) + 1];
             const int bstart = oneTexel ? 0 : S.matStart[CH_COUNT * m + CH_BUMP];
             const float *uv = shade + 15;
             const V3 tb = ld3(S.tb), lr = ld3(S.lr);
-            uint32_t h0, hs, he;
+            uint32_t h0 = 0u, hs = 0u, he = 0u;
             float t, p1 = 0.f, p2 = 0.f;
             if (oneTexel) { // three fetches of the same texel
                 h0 = hs = he = mat->desc[CH_BUMP] & 255u;
                 if (COUNT) cn.v[ST_TEXELS] += 3;
-            } else
+            } else if (!ONE_TEXEL_BUMP)
             (void)texel<COUNT>(S, sh, bstart, bw, bh, uv, l1, l2, h0, cn);
-            if (oneTexel) {
+            if (oneTexel || ONE_TEXEL_BUMP) {
             } else if (bw == 1u && bh == 1u) { // one-texel height map: the neighbour samples are the same texel, wherever they land
                 (void)texel<COUNT>(S, sh, bstart, bw, bh, uv, 0.f, 0.f, hs, cn);
                 (void)texel<COUNT>(S, sh, bstart, bw, bh, uv, 0.f, 0.f, he, cn);

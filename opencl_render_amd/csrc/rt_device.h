@@ -23,6 +23,7 @@
 //  boxMin   [3][257]        split planes, one array per axis (staged into LDS by every workgroup)
 //  camStart/camEnd          per pixel of this scene's tiles, TILE-MAJOR: index = slot*128*128 + ly*128 + lx
 //  tileBuf  [slot][3][128*128] u16 planes R,G,B
+enum { RT_PATH_CLASS_GENERAL = 0, RT_PATH_CLASS_OPAQUE_DIFFUSE = 1 };
 struct RtDevScene {
     // camera (raytrace.h:61-66)
     float eye[3], topLeft[3], lr[3], tb[3];
@@ -86,6 +87,9 @@ struct RtDevScene {
     const float *lightPos, *lightDir, *lightCol; // 4 floats each
     const float *lightRadius, *lightHalfAtt;
     const float *lightSpread; // per light: (float)(sin((r/2)*PI_F/180) * sqrt(|dir|^2)), host libm (raytrace_opencl.c:594)
+    // which logic kernel runs the paths (rt_api.cpp, path_class_of): RT_PATH_CLASS_GENERAL, or RT_PATH_CLASS_OPAQUE_DIFFUSE when no material
+    // has a reflection, transparency or luminance other than absent or one black texel, no height map is an image, and lightCount <= 1
+    uint32_t pathClass;
     // outputs
     uint16_t *tileBuf;
     unsigned long long *stats; // 7 counters, only touched by the counted kernel variant

@@ -438,6 +438,12 @@ __device__ __forceinline__ bool cut_at(float ta, float te, uint32_t k, uint32_t 
 #ifndef RT_WF_LOGIC_WAVES_FIRST_ORDERED
 #define RT_WF_LOGIC_WAVES_FIRST_ORDERED 3
 #endif
+#ifndef RT_WF_LOGIC_WAVES_LEAN_FIRST
+#define RT_WF_LOGIC_WAVES_LEAN_FIRST 4
+#endif
+#ifndef RT_WF_LOGIC_WAVES_LEAN
+#define RT_WF_LOGIC_WAVES_LEAN 4
+#endif
 #define RT_WF_LIGHTS_LDS 64
 #ifdef RT_DIAG_LOGIC // diagnostic build: where a wave is at which time, round RT_DIAG_LOGIC (no waits added; scripts/diag_logic.py)
 #define DG(i) dg[i] = diag_stamp()
@@ -462,8 +468,11 @@ __device__ __forceinline__ void load_tri_row(const RtDevScene &S, uint32_t tri, 
 // ORDERED = the round this launch spawns is an ordered one (next.ordered): its entries are planned and classed here; the other
 // instantiation carries none of that code (its registers are the state machine's).
 // slicesIn = queue slices per kind of THIS round (what logic(round - 1) was told), next = how the round this launch spawns is laid out.
-template <bool FIRST, bool ORDERED>
-__global__ __launch_bounds__(256, FIRST ? (ORDERED ? RT_WF_LOGIC_WAVES_FIRST_ORDERED : RT_WF_LOGIC_WAVES_FIRST) : RT_WF_LOGIC_WAVES) void wf_logic_kernel(const RtDevScene S, const RtWavefront W, const uint32_t round,
+// LEAN = the scene is in the opaque-diffuse path class (RtDevScene::pathClass, rt_api.cpp): the path is written out as its fixed shape
+// instead of the general state machine below, in fewer registers.
+template <bool FIRST, bool ORDERED, bool LEAN>
+__global__ __launch_bounds__(256, LEAN ? (FIRST ? RT_WF_LOGIC_WAVES_LEAN_FIRST : RT_WF_LOGIC_WAVES_LEAN)
+                                       : (FIRST ? (ORDERED ? RT_WF_LOGIC_WAVES_FIRST_ORDERED : RT_WF_LOGIC_WAVES_FIRST) : RT_WF_LOGIC_WAVES)) void wf_logic_kernel(const RtDevScene S, const RtWavefront W, const uint32_t round,
                                                                                                              const uint32_t slicesIn, const RtRoundMode next)
 {
     __shared__ Shared sh; // the texel/255 table and the split planes (for the entries of the rays spawned here)
@@ -557,7 +566,234 @@ __global__ __launch_bounds__(256, FIRST ? (ORDERED ? RT_WF_LOGIC_WAVES_FIRST_ORD
         float rtmin = 0.f, rtmax = 0.f, latmin = 0.f;
         uint32_t rexcl = RT_NONE, laexcl = RT_NONE, a = 0;
 
-        if (live) {
+        if (LEAN && live) {
+            // ---- the opaque-diffuse path class (rt_api.cpp, path_class_of): every material's reflection, transparency and luminance are
+            // absent or one black texel, the height map is absent or one texel, and there is at most one light.  Then a path is: the camera
+            // ray's hit, shaded, spawning at most one diffuse bounce (bounces = 0, fromCamera = 0), light 0's shadow ray; the bounce's hit,
+            // shaded with no spawn, light 0's shadow ray.  At most one ring entry after the camera's, no camera-type ray after the primary,
+            // no second light.  Every operation the general machine performs on that path is performed here, in the same order; only
+            // branches that cannot be taken are left out (each says why).  Entry states: round 0's camera hit, a shadow answer, a ray answer.
+            const V3 zero = mk(0.f, 0.f, 0.f); // what the absent / black reflection, transparency and luminance channels read as
+            uint32_t res_tri = RT_NONE;
+            float res_t = 0.f, res_l1 = 0.f, res_l2 = 0.f;
+            unsigned long long key = ~0ull, laKeyEarly = ~0ull;
+            if (FIRST) {
+                a = q;
+                const uint4 r = W.res[q];
+                res_tri = r.x; res_t = __uint_as_float(r.y); res_l1 = __uint_as_float(r.z); res_l2 = __uint_as_float(r.w);
+            } else {
+                const uint2 who = W.pathOf[in][q];
+                a = who.x;
+                key = W.hitKey[in][q];
+                if (who.y != 0xffffffffu) laKeyEarly = W.hitKey[in][who.y];
+            }
+            float4 *ringA = W.ring + (size_t)a * (RT_RING * 3);
+            uint64_t rng = W.rng[a];
+            const uint4 meta = FIRST ? make_uint4(0u, 0u, 0u | (1u << 4) | ((uint32_t)WS_RAY << 8), res_tri) : W.meta[a];
+            V3 out = mk(0.f, 0.f, 0.f);
+            float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0, c2 = c0;
+            TriRow row;
+            row.tri = RT_NONE;
+            if (FIRST) {
+                c0 = pack4(ld3(S.eye), 0.f); c1 = ringA[1]; c2 = make_float4(1.f, 1.f, 1.f, __uint_as_float((12u << 1) | 1u));
+                load_tri_row(S, res_tri, row);
+            } else out = xyz(W.outc[a]);
+            uint32_t hit_tri = meta.w;
+            int head = (int)(meta.z & 15u), tail = (int)((meta.z >> 4) & 15u);
+            const uint32_t stage = (meta.z >> 8) & 1u;
+            uint32_t laState = (meta.z >> 10) & 3u;
+            int laIndex = (int)((meta.z >> 12) & 15u);
+            bool laFetched = false;
+            unsigned long long laKey = ~0ull;
+            if (laState == 1u) { laKey = laKeyEarly; laState = 2u; laFetched = true; }
+            else if (laState == 2u) laKey = W.laKey[a];
+
+            V3 cur_o = mk(0, 0, 0), cur_d = mk(0, 0, 0), cur_w = mk(0, 0, 0);
+            float cur_tmin = 0.f;
+            uint32_t cur_excl = RT_NONE;
+            int cur_bounces = 0;
+            V3 n = mk(0, 0, 0), where = mk(0, 0, 0), P = mk(0, 0, 0), face = mk(0, 0, 0), toL = mk(0, 0, 0);
+            float ndl = 0.f, lmin = 0.f, lmax = 0.f;
+            bool front = false, finished = false, rngDirty = false, outDirty = false, shade = false;
+            uint32_t emitStage = WS_RAY;
+            int firstSpawnSlot = -1;
+            float4 firstSpawn0 = make_float4(0.f, 0.f, 0.f, 0.f), firstSpawn1 = firstSpawn0;
+
+            auto take_ray = [&](float4 e0, float4 e1, float4 e2) {
+                cur_o = xyz(e0); cur_tmin = e0.w; cur_d = xyz(e1); cur_excl = __float_as_uint(e1.w); cur_w = xyz(e2);
+                cur_bounces = (int)(__float_as_uint(e2.w) >> 1); // (fromCamera is set on the camera ray only: see-through rays are never spawned)
+            };
+            // PC_NEXT_RAY (:509): false when the ring is empty (the path is finished)
+            auto next_ray = [&]() -> bool {
+                head = (head + 1) % RT_RING;
+                if (head == tail) { finished = true; return false; }
+                take_ray(ringA[head * 3 + 0], ringA[head * 3 + 1], ringA[head * 3 + 2]);
+                return true;
+            };
+            auto emit_ray = [&]() { emit = true; emitStage = WS_RAY; ro = cur_o; rd = cur_d; rtmin = cur_tmin; rtmax = RT_INF; rexcl = cur_excl; };
+            // PC_LIGHT_ACCUM (:628-636) for light 0
+            auto light_accum = [&](V3 atten) {
+                const float mag = __builtin_fabsf(ndl);
+                const float4 lc = light_col_half(0);
+                const float x = lmax / lc.w;
+                const float e = mag * half_falloff(x);
+                if ((0.f <= ndl) == front) {
+                    face.x += (1.f - face.x) * atten.x * e * lc.x;
+                    face.y += (1.f - face.y) * atten.y * e * lc.y;
+                    face.z += (1.f - face.z) * atten.z * e * lc.z;
+                }
+            };
+            // PC_SHADE_END (:647-651)
+            auto shade_end = [&]() {
+                out.x += P.x * face.x;
+                out.y += P.y * face.y;
+                out.z += P.z * face.z;
+                outDirty = true;
+            };
+
+            bool advance = false; // the hit in hand is done: on to the next ring entry
+            if (FIRST) {
+                take_ray(c0, c1, c2);
+                shade = res_tri != RT_NONE;
+                advance = !shade;
+            } else if (stage == WS_SHADOW) { // PC_SHADOW_RESULT (:612-626) of light 0
+                const float4 sp = W.shP[a], sf = W.shFace[a];
+                P = xyz(sp); ndl = sp.w; face = xyz(sf); front = (sf.w != 0.f);
+                const float4 *e = reinterpret_cast<const float4 *>(W.ent[in]) + 4 * (size_t)q;
+                const float4 e1 = e[1], e2 = e[2], e3 = e[3];
+                where = xyz(e2); lmin = e1.w; toL = xyz(e3); lmax = e2.w;
+                res_tri = resolve_hit(S, key, where, toL, lmin, lmax, hit_tri, res_t, res_l1, res_l2);
+                V3 atten = mk(1.f, 1.f, 1.f);
+                // an occluder's transparency is absent or black in this class: atten becomes 0, so the shadow ray is never sent on (:621-625)
+                if (res_tri != RT_NONE) { atten.x *= zero.x; atten.y *= zero.y; atten.z *= zero.z; }
+                light_accum(atten);
+                shade_end(); // (no light after light 0)
+                advance = true;
+            } else { // a ray's answer: the ray is the ring entry at head
+                take_ray(ringA[head * 3 + 0], ringA[head * 3 + 1], ringA[head * 3 + 2]);
+                res_tri = resolve_hit(S, key, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
+                shade = res_tri != RT_NONE;
+                advance = !shade;
+            }
+            if (advance && next_ray()) {
+                if (laState == 2u && laIndex == head) { // traced ahead of time: the answer is already here
+                    res_tri = resolve_hit(S, laKey, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
+                    laState = 0u;
+                    shade = res_tri != RT_NONE;
+                    if (!shade && next_ray()) emit_ray(); // (the ring holds no further entry: this finishes the path)
+                } else emit_ray();
+            }
+            if (shade) { // SHADE_BEGIN (:532-561), the hit's one spawn, light 0
+                hit_tri = res_tri;
+                const float *shadeRow = FIRST ? row.v : S.triShade + 24 * (size_t)res_tri; // (round 0 shades the camera hit only)
+                const int m = __float_as_int(shadeRow[21]);
+                const float *uv = shadeRow + 15;
+                where = along(cur_o, res_t, cur_d);
+                MatRec mat;
+                mat.desc[0] = mat.desc[1] = mat.desc[2] = mat.desc[3] = mat.desc[4] = 0u; mat.m = m;
+                if (0 <= m) mat = load_mat(S, m);
+                n = shading_normal<false, true>(S, sh, where, cur_o, cur_d, hit_tri, res_l1, res_l2, shadeRow, m, cn, &mat, FIRST ? &row.a : nullptr);
+                V3 tex = mk(0, 0, 0);
+                const V3 transp = zero, refl = zero, lum = zero;
+                if (0 <= m && mat.desc[CH_COLOR]) {
+                    uint32_t raw;
+                    tex = texel_rec<false>(S, sh, mat, CH_COLOR, uv, res_l1, res_l2, raw, cn);
+                }
+                out.x += (1.f - out.x) * lum.x * cur_w.x;
+                out.y += (1.f - out.y) * lum.y * cur_w.y;
+                out.z += (1.f - out.z) * lum.z * cur_w.z;
+                outDirty = true;
+                front = (dot3(n, cur_d) <= 0.f);
+                P.x = (1.f - out.x) * cur_w.x * (1.f - transp.x) * tex.x;
+                P.y = (1.f - out.y) * cur_w.y * (1.f - transp.y) * tex.y;
+                P.z = (1.f - out.z) * cur_w.z * (1.f - transp.z) * tex.z;
+                face = mk(0.1f, 0.1f, 0.1f);
+                // light 0's GetSpherePoint comes before the bounce's draws (:573,:595 then :671)
+                const int type = S.lightCount != 0u ? light_type(0) : 0;
+                SphereRaw raw0;
+                raw0.p = mk(0, 0, 0); raw0.len = 1.f; raw0.sq = 0.f;
+                if (S.lightCount != 0u && type >= 1 && type <= 9) raw0 = sphere_raw(rng);
+                rngDirty = true;
+                if (cur_bounces > 0) {
+                    const int frontI = front ? 1 : 0;
+                    const float total_rt = RT_MAX2(RT_MAX2(refl.x + transp.x, refl.y + transp.y), refl.z + transp.z);
+                    const float dif = (total_rt < 1.f) ? 1.f - total_rt : 0.f;
+                    const V3 w = mk(cur_w.x * tex.x * dif, cur_w.y * tex.y * dif, cur_w.z * tex.z * dif);
+                    if (3.f / 256.f <= w.x + w.y + w.z) { // diffuse bounce (:664-683)
+                        V3 nd = sphere_scaled(sphere_raw(rng), 1.f);
+                        if (frontI != ((0 <= dot3(nd, n)) ? 1 : 0)) { nd.x = -nd.x; nd.y = -nd.y; nd.z = -nd.z; }
+                        const float4 s0 = pack4(where, 0.f), s1 = pack4(nd, __uint_as_float(hit_tri));
+                        ringA[tail * 3 + 0] = s0; ringA[tail * 3 + 1] = s1; ringA[tail * 3 + 2] = pack4(w, __uint_as_float(0u));
+                        if (FIRST) { firstSpawnSlot = tail; firstSpawn0 = s0; firstSpawn1 = s1; }
+                        tail = (tail + 1) % RT_RING;
+                    }
+                    // mirror (:686-705) and see-through (:707-722): their weights are cur_w * tex * 0, i.e. +-0 or NaN, and 3/256 <= a sum of
+                    // those is false -- never spawned
+                }
+                // PC_LIGHT_SETUP (:563-607) of light 0 (the draws above); no light 1
+                if (S.lightCount != 0u) {
+                    toL = mk(0.f, 0.f, 0.f);
+                    lmin = 0.f; lmax = 0.f;
+                    if (type >= 1 && type <= 9) {
+                        if (type >= 3 && type <= 6) {
+                            const float4 ld = light_dir_spread(0);
+                            toL = sphere_scaled(raw0, ld.w);
+                            toL.x -= ld.x; toL.y -= ld.y; toL.z -= ld.z;
+                            const float inv = 1.f / sqrt_rn(dot3(toL, toL));
+                            toL.x *= inv; toL.y *= inv; toL.z *= inv;
+                            lmax = RT_INF;
+                        } else {
+                            const float4 lp = light_pos_radius(0);
+                            const V3 rp = sphere_scaled(raw0, lp.w);
+                            toL.x = rp.x + lp.x - where.x;
+                            toL.y = rp.y + lp.y - where.y;
+                            toL.z = rp.z + lp.z - where.z;
+                            lmax = sqrt_rn(dot3(toL, toL));
+                            const float inv = 1.f / lmax;
+                            toL.x *= inv; toL.y *= inv; toL.z *= inv;
+                        }
+                    }
+                    ndl = dot3(n, toL);
+                    if (lmin < lmax) { emit = true; emitStage = WS_SHADOW; ro = where; rd = toL; rtmin = lmin; rtmax = lmax; rexcl = hit_tri; }
+                    else light_accum(mk(1.f, 1.f, 1.f));
+                }
+                if (!emit) {
+                    shade_end();
+                    // (a look-ahead answer is only ever outstanding while a shadow ray is: it was taken above)
+                    if (next_ray()) emit_ray();
+                }
+            }
+
+            // Leaving with a request and no look-ahead outstanding: start the next ring entry's grid walk as well (every entry is a grid ray)
+            if (!finished && laState == 0u && W.lookAhead) {
+                const int nx = (head + 1) % RT_RING;
+                if (nx != tail) {
+                    float4 n0 = firstSpawn0, n1 = firstSpawn1;
+                    if (!FIRST || nx != firstSpawnSlot) { n0 = ringA[nx * 3 + 0]; n1 = ringA[nx * 3 + 1]; }
+                    emitLa = true; lo3 = xyz(n0); latmin = n0.w; ld3v = xyz(n1); laexcl = __float_as_uint(n1.w);
+                    laState = 1u; laIndex = nx;
+                }
+            }
+
+            if (finished) {
+                const uint2 where2 = FIRST ? *reinterpret_cast<const uint2 *>(W.meta + a) : make_uint2(meta.x, meta.y); // {output slot, pixel}
+                if (S.sampleCount == 1u) store_single_sample(S, where2.y, out);
+                else W.sampleOut[where2.x] = pack4(out, 0.f);
+            } else {
+                asm volatile("" : "+v"(a));
+                if (rngDirty) W.rng[a] = rng;
+                if (outDirty) W.outc[a] = pack4(out, 0.f);
+                // (a shadow ray leaves with atten = 1, never stored; the next light index is always 0)
+                const uint32_t flags = (uint32_t)head | ((uint32_t)tail << 4) | (emitStage << 8) | (laState << 10) | ((uint32_t)laIndex << 12);
+                if (FIRST) reinterpret_cast<uint2 *>(W.meta + a)[1] = make_uint2(flags, hit_tri);
+                else W.meta[a] = make_uint4(meta.x, meta.y, flags, hit_tri);
+                if (laState == 2u && laFetched) W.laKey[a] = laKey;
+                if (emitStage == WS_SHADOW) {
+                    W.shP[a] = pack4(P, ndl);
+                    W.shFace[a] = pack4(face, front ? 1.f : 0.f);
+                }
+            }
+        } else if (live) {
             // Round 0 issues its loads in as few dependent batches as the data allows -- a wave runs one chunk and has two
             // neighbours on its SIMD, so the chunk lasts as long as its chain of memory round trips (measured: ~8 of them at
             // 2-4 us each before the first shading instruction when every load sat next to its use).  Batch one: the primary hit,
@@ -1759,10 +1995,17 @@ extern "C" hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefron
 {
     if (blocks % (RT_WF_SHARDS / 4) != 0) return hipErrorInvalidValue; // a whole number of waves per queue slice (wf_logic_kernel)
     if (!mode_ok(*next) || slicesIn < next->slices || slicesIn > RT_WF_SHARDS || (slicesIn & (slicesIn - 1u)) != 0u) return hipErrorInvalidValue;
-    if (round == 0u && next->ordered) hipLaunchKernelGGL((wf_logic_kernel<true, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
-    else if (round == 0u) hipLaunchKernelGGL((wf_logic_kernel<true, false>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
-    else if (next->ordered) hipLaunchKernelGGL((wf_logic_kernel<false, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
-    else hipLaunchKernelGGL((wf_logic_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+    if (scene->pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE) {
+        if (round == 0u && next->ordered) hipLaunchKernelGGL((wf_logic_kernel<true, true, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+        else if (round == 0u) hipLaunchKernelGGL((wf_logic_kernel<true, false, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+        else if (next->ordered) hipLaunchKernelGGL((wf_logic_kernel<false, true, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+        else hipLaunchKernelGGL((wf_logic_kernel<false, false, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+    } else if (scene->pathClass == RT_PATH_CLASS_GENERAL) {
+        if (round == 0u && next->ordered) hipLaunchKernelGGL((wf_logic_kernel<true, true, false>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+        else if (round == 0u) hipLaunchKernelGGL((wf_logic_kernel<true, false, false>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+        else if (next->ordered) hipLaunchKernelGGL((wf_logic_kernel<false, true, false>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+        else hipLaunchKernelGGL((wf_logic_kernel<false, false, false>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
+    } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -67,7 +67,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
-    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes",
+    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
@@ -157,6 +157,8 @@ def lib() -> C.CDLL:
     L.rtHipTune.argtypes = [C.c_char_p, C.c_double]
     L.rtHipTestHashBytes.restype = u64
     L.rtHipTestHashBytes.argtypes = [vp, u64]
+    L.rtHipScenePathClass.argtypes = [C.POINTER(SceneDesc)]
+    L.rtHipTestPathClass.argtypes = [vp]
     L.rtHipFree.argtypes = [vp]
     L.rtHipFree.restype = None
     _lib = L
@@ -171,6 +173,7 @@ _ENV_KEYS = {
     "RT_WF_APPEND_RAYS": "append_rays", "RT_WF_ORDERED_FIRST": "ordered_first", "RT_WF_EXTRA_FACTOR": "extra_factor", "RT_WF_SLICE_RAYS": "slice_rays", "RT_WF_SMALL_SLICES": "small_slices", "RT_WF_GROUP_RAYS": "group_rays",
     "RT_WF_BLOCKING": "blocking", "RT_WF_BATCH_PLAN": "batch_plan", "RT_WF_PLAN_ROUNDS": "plan_rounds", "RT_HIP_PIPELINE": "pipeline",
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
+    "RT_WF_LOGIC_CLASS": "logic_class",
 }
 
 
@@ -357,6 +360,22 @@ def scene_desc(sc: Scene) -> SceneDesc:
     return d
 
 
+PATH_CLASS_GENERAL, PATH_CLASS_OPAQUE_DIFFUSE = 0, 1
+
+
+def path_class(sc: Scene) -> int:
+    """The logic kernel a scene's paths run on (rtHipScenePathClass), decided on the host: PATH_CLASS_OPAQUE_DIFFUSE when no material
+    reflects, lets light through or glows, no height map is an image and there is at most one light; PATH_CLASS_GENERAL otherwise."""
+    d = SceneDesc()  # (only the materials and the lights are looked at: the lists need not be built)
+    d.materialCount, d.matSize, d.matStart = sc.material_count, _ptr(sc.mat_size), _ptr(sc.mat_start)
+    d.texturesSize, d.textures = len(sc.textures), _ptr(sc.textures)
+    d.lightCount, d.lightType = sc.light_count, _ptr(sc.light_type)
+    c = lib().rtHipScenePathClass(C.byref(d))
+    if c < 0:
+        raise ValueError(last_error())
+    return c
+
+
 def tile_count(width: int, height: int) -> int:
     return ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
 
@@ -390,6 +409,10 @@ class ResidentScene:
             self.handle = None
 
     __del__ = close
+
+    def path_class(self) -> int:
+        """The path class this scene's logic kernels run (rtHipTestPathClass: 0 when it was built with logic_class = 0)."""
+        return lib().rtHipTestPathClass(self.handle)
 
     def _check(self, rc, what):
         if rc != 0:
