@@ -429,8 +429,9 @@ int rtHipDeviceKat(int device, int op, cl_uint count, const void *in, cl_uint in
  * and applies to scenes built afterwards.  Keys (rt_api.cpp, struct Tuning): "reset" (all defaults), "stage_mb", "extra_factor",
  * "state_mb", "groups", "lookahead", "seg0".."seg4", "seg_rays0".."seg_rays3", "fast_quotient", "spin_limit", "append_rays", "ordered_first", "extra_factor",
  * "slice_rays", "small_slices", "group_rays", "blocking", "batch_plan", "pipeline", "timing", "cache", "logic_class" (0: every scene's
- * paths run on the general logic kernel; 1, the default: on the kernel of the scene's path class), and the test hooks "plan_rounds",
- * "plan_grid_tiny", "virtual_devices".  Returns 0, -1 for an unknown key. */
+ * paths run on the general logic kernel; 1, the default: on the kernel of the scene's path class), "dead_shadow" (0: trace every
+ * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), and the test hooks
+ * "plan_rounds", "plan_grid_tiny", "virtual_devices".  Returns 0, -1 for an unknown key. */
 int rtHipTune(const char *key, double value);
 
 /* TEST-ONLY: device addresses held by the first scene of RaytraceAll's cache -- triangle records, shading rows, the grid's pair
@@ -449,6 +450,12 @@ int rtHipScenePathClass(const rtHipSceneDesc *desc);
 
 /* TEST-ONLY: the path class a resident scene's logic kernels run (0 when "logic_class" was 0 at its build).  -1 for NULL. */
 int rtHipTestPathClass(const rtHipScene *scene);
+
+/* TEST-ONLY: the rays of each round of the scene's last wavefront frame, summed over its tile groups (round 0: the paths the primary
+ * rays made; round r > 0: the rays logic round r - 1 sent to the grid), for rounds [0, n); rounds the frame did not issue read 0.  Call
+ * after the frame was synchronised; with several sample batches the figures are the last batch's.  Returns the frame's round count,
+ * -1 for invalid arguments. */
+int rtHipTestRoundLog(const rtHipScene *scene, cl_uint *rays, cl_uint n);
 
 #ifdef __cplusplus
 }

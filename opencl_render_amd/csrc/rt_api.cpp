@@ -95,6 +95,7 @@ struct Tuning {
     uint32_t cache = 1;             // 0: RaytraceAll builds and frees per call, like the reference
     uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
     uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
+    uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
 };
 Tuning g_tune;
 std::mutex g_tuneMutex;
@@ -660,6 +661,7 @@ int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
         Wf.capacity = (uint32_t)cap;
         Wf.shardCap = (uint32_t)shardCap;
         Wf.lookAhead = T.lookAhead ? 1u : 0u;
+        Wf.deadShadow = T.deadShadow ? 1u : 0u;
         const uint64_t qcap = 2 * cap; // queue entries: up to two rays in flight per path
         const uint64_t extraCap = (uint64_t)extraFactor * cap; // room for the further segments of cut rays (a wave that finds it full leaves its rays whole)
         const uint64_t ecap = qcap + extraCap;
@@ -1510,7 +1512,7 @@ int rtHipTune(const char *key, double value)
         { "fast_quotient", &T.fastQuotient }, { "spin_limit", &T.spinLimit }, { "append_rays", &T.appendRays }, { "ordered_first", &T.orderedFirst }, { "slice_rays", &T.sliceRays },
         { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
-        { "logic_class", &T.logicClass },
+        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow },
     };
     if (k == "state_mb") { T.stateMb = (uint64_t)(value < 0 ? 0 : value); return 0; }
     for (auto &e : table)
@@ -1532,6 +1534,19 @@ int rtHipTestPathClass(const rtHipScene *scene)
 {
     if (!scene) return -1;
     return (int)scene->dev.pathClass;
+}
+
+int rtHipTestRoundLog(const rtHipScene *scene, uint32_t *rays, uint32_t n)
+{
+    if (!scene || (n && !rays)) return -1;
+    const uint32_t rounds = (uint32_t)std::min<uint64_t>(scene->roundsLast, RT_WF_ROUND_LOG);
+    for (uint32_t r = 0; r < n; ++r) {
+        uint64_t sum = 0;
+        if (r < rounds)
+            for (const auto &G : scene->groups) sum += G.hostLog[r].x; // (mapped host memory, written by the logic kernels)
+        rays[r] = (uint32_t)std::min<uint64_t>(sum, 0xffffffffu);
+    }
+    return (int)scene->roundsLast;
 }
 
 int rtHipScenePathClass(const rtHipSceneDesc *desc)

@@ -156,6 +156,7 @@ struct RtWavefront {
     uint32_t sampleBase;     // samples sampleBase+1 .. sampleBase+samplesInBatch are in flight (1-based ids, raytrace.c:612-653)
     uint32_t samplesInBatch;
     uint32_t lookAhead;      // 1: a path traces its next ring entry while the current hit's shadow ray is in flight
+    uint32_t deadShadow;     // 1: no shadow ray for a light on the side of the normal whose face[] entry :647 will not read (its answer is dead)
     uint32_t fastQuotient;   // 1: waves whose rays all have tame exponents skip the scaling / fix-up instructions of the quotients
     uint32_t spinLimit;      // walk phases a wave of wf_trace_kernel may run before it gives up and raises RT_WF_ERR_SPIN (default 16384)
     uint32_t *hostStatus;    // pinned HOST words mapped into the device (RT_WF_STATUS_*): written by kernels, read by the host after a sync

@@ -573,6 +573,7 @@ __global__ __launch_bounds__(256, LEAN ? (FIRST ? RT_WF_LOGIC_WAVES_LEAN_FIRST :
             // shaded with no spawn, light 0's shadow ray.  At most one ring entry after the camera's, no camera-type ray after the primary,
             // no second light.  Every operation the general machine performs on that path is performed here, in the same order; only
             // branches that cannot be taken are left out (each says why).  Entry states: round 0's camera hit, a shadow answer, a ray answer.
+            // A hit whose shadow ray is dead (W.deadShadow) goes on at once: the bounce becomes the main ray of round 1, or the path ends.
             const V3 zero = mk(0.f, 0.f, 0.f); // what the absent / black reflection, transparency and luminance channels read as
             uint32_t res_tri = RT_NONE;
             float res_t = 0.f, res_l1 = 0.f, res_l2 = 0.f;
@@ -754,13 +755,21 @@ __global__ __launch_bounds__(256, LEAN ? (FIRST ? RT_WF_LOGIC_WAVES_LEAN_FIRST :
                         }
                     }
                     ndl = dot3(n, toL);
-                    if (lmin < lmax) { emit = true; emitStage = WS_SHADOW; ro = where; rd = toL; rtmin = lmin; rtmax = lmax; rexcl = hit_tri; }
+                    // a dead shadow ray (light on the side whose face entry :647 does not read) is not traced: light_accum is a no-op for it
+                    const bool dead = W.deadShadow && ((0.f <= ndl) != front);
+                    if (lmin < lmax && !dead) { emit = true; emitStage = WS_SHADOW; ro = where; rd = toL; rtmin = lmin; rtmax = lmax; rexcl = hit_tri; }
                     else light_accum(mk(1.f, 1.f, 1.f));
                 }
                 if (!emit) {
                     shade_end();
                     // (a look-ahead answer is only ever outstanding while a shadow ray is: it was taken above)
-                    if (next_ray()) emit_ray();
+                    if (FIRST && firstSpawnSlot >= 0) {
+                        // the camera hit's bounce is the next ring entry and becomes the main ray: from the registers it was spawned from
+                        // (PC_NEXT_RAY + take_ray + emit_ray without reading back the ring slot just stored)
+                        head = firstSpawnSlot;
+                        emit = true; emitStage = WS_RAY; ro = xyz(firstSpawn0); rtmin = firstSpawn0.w; rd = xyz(firstSpawn1); rtmax = RT_INF;
+                        rexcl = __float_as_uint(firstSpawn1.w);
+                    } else if (next_ray()) emit_ray();
                 }
             }
 
@@ -1010,7 +1019,11 @@ __global__ __launch_bounds__(256, LEAN ? (FIRST ? RT_WF_LOGIC_WAVES_LEAN_FIRST :
                         }
                     }
                     ndl = dot3(n, toL);
-                    if (lmin < lmax) { // shadow ray (:608-611): leave the machine until the grid has answered
+                    // shadow ray (:608-611): leave the machine until the grid has answered -- unless it is dead: a light on the side whose face
+                    // entry :647 will not read (W.deadShadow).  Its answer, any walk through transparent occluders and the attenuation feed only
+                    // that entry, and no draw depends on them; PC_LIGHT_ACCUM is a no-op on `face` for it.
+                    const bool dead = W.deadShadow && ((0.f <= ndl) != front);
+                    if (lmin < lmax && !dead) {
                         emit = true; emitStage = WS_SHADOW; ro = where; rd = toL; rtmin = lmin; rtmax = lmax; rexcl = hit_tri;
                         pc = PC_EXIT;
                     } else pc = PC_LIGHT_ACCUM;

@@ -67,7 +67,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
-    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass",
+    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
@@ -159,6 +159,7 @@ def lib() -> C.CDLL:
     L.rtHipTestHashBytes.argtypes = [vp, u64]
     L.rtHipScenePathClass.argtypes = [C.POINTER(SceneDesc)]
     L.rtHipTestPathClass.argtypes = [vp]
+    L.rtHipTestRoundLog.argtypes = [vp, C.POINTER(u32), u32]
     L.rtHipFree.argtypes = [vp]
     L.rtHipFree.restype = None
     _lib = L
@@ -173,7 +174,7 @@ _ENV_KEYS = {
     "RT_WF_APPEND_RAYS": "append_rays", "RT_WF_ORDERED_FIRST": "ordered_first", "RT_WF_EXTRA_FACTOR": "extra_factor", "RT_WF_SLICE_RAYS": "slice_rays", "RT_WF_SMALL_SLICES": "small_slices", "RT_WF_GROUP_RAYS": "group_rays",
     "RT_WF_BLOCKING": "blocking", "RT_WF_BATCH_PLAN": "batch_plan", "RT_WF_PLAN_ROUNDS": "plan_rounds", "RT_HIP_PIPELINE": "pipeline",
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
-    "RT_WF_LOGIC_CLASS": "logic_class",
+    "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow",
 }
 
 
@@ -413,6 +414,14 @@ class ResidentScene:
     def path_class(self) -> int:
         """The path class this scene's logic kernels run (rtHipTestPathClass: 0 when it was built with logic_class = 0)."""
         return lib().rtHipTestPathClass(self.handle)
+
+    def round_rays(self, n: int = 8) -> list:
+        """Rays per round of the last frame (rtHipTestRoundLog; call after a synchronisation): round 0 = the paths, round r > 0 = the
+        rays logic round r - 1 sent to the grid.  Rounds the frame did not issue read 0."""
+        rays = (C.c_uint32 * n)()
+        if lib().rtHipTestRoundLog(self.handle, rays, n) < 0:
+            raise RuntimeError("rtHipTestRoundLog failed")
+        return [int(v) for v in rays]
 
     def _check(self, rc, what):
         if rc != 0:
