@@ -15,10 +15,14 @@ scene inputs in the ABI layouts and the expected u16 planes / function results.
                      GetPointToLineSqLen, GetBoxAddress, BindInCube)
   ref_fresh_scenes.npz  planes R,G,B ("<seed>_r", "_g", "_b") of scenarios.fresh_soup(seed) for scenarios.FRESH_SEEDS
                      (inputs not stored: the test regenerates them from the seed)
+  ref_class_scenes.npz  planes R,G,B ("<name>_r", "_g", "_b") of every opaque-diffuse scenario in scenarios.CLASS (inputs not
+                     stored: the tests regenerate them from the code and R.build_lists); written byte for byte the same on every run
 """
 import ctypes as C
+import io
 import os
 import sys
+import zipfile
 
 import numpy as np
 
@@ -145,10 +149,36 @@ def make_fresh(path):
     np.savez_compressed(path, **planes)
 
 
+def save_npz_stable(path, arrays):
+    """np.savez_compressed without the wall-clock time stamps: entries in key order, each dated 1980-01-01, so that the same
+    planes give the same bytes."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for key in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o600 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def make_class(path):
+    planes = {}
+    for f in scenarios.CLASS:
+        sc = f()
+        R.build_lists(sc)
+        if R.path_class(sc) != R.PATH_CLASS_OPAQUE_DIFFUSE:
+            sys.exit(f"{f.__name__} is not in the opaque-diffuse class")
+        for c, p in zip("rgb", O.ref_render(sc)):
+            planes[f"{f.__name__}_{c}"] = p
+    save_npz_stable(path, planes)
+
+
 def main():
     if not O.have_ref():
         sys.exit("oracle/_ref/libref_kernel.so missing: run `make -C oracle` where /root/reference exists")
-    only = set(sys.argv[1:])  # optional: names of the fixtures to (re)write, "kat" / "fresh" for kat.npz / ref_fresh_scenes.npz; default = everything
+    only = set(sys.argv[1:])  # optional: names of the fixtures to (re)write, "kat" / "fresh" / "class" for kat.npz / ref_fresh_scenes.npz /
+    # ref_class_scenes.npz; default = everything
     for f in scenarios.ALL:
         if only and f.__name__ not in only:
             continue
@@ -164,6 +194,9 @@ def main():
     if not only or "fresh" in only:
         make_fresh(os.path.join(HERE, "ref_fresh_scenes.npz"))
         print("ref_fresh_scenes.npz written")
+    if not only or "class" in only:
+        make_class(os.path.join(HERE, "ref_class_scenes.npz"))
+        print("ref_class_scenes.npz written")
 
 
 if __name__ == "__main__":

@@ -142,6 +142,156 @@ def fresh_soup(seed):
     return S.make_soup(40, 32, 500, 0.3, seed=seed, samples=2, materials=mats, lights=lights, random_uv=True, smooth_normals=True)
 
 
+# ---- the opaque-diffuse path class ---------------------------------------------------------------------------------------------
+# Scenes the host puts in the opaque-diffuse class (rt_api.cpp materials_admit_opaque_diffuse / lights_admit_opaque_diffuse: every
+# reflection, transparency and luminance absent or one black texel, every height map absent or one texel, at most one light), so
+# that the GPU renders them with wf_logic_kernel<.., LEAN=true>.  Each aims at one family of that kernel's branches.  The reference's
+# planes are stored in tests/golden/ref_class_scenes.npz; tests/test_path_class.py fails if one of them drifts out of the class.
+
+def _img(seed, w, h, lo=0, hi=256):
+    """A w x h colour image ([h, w, 3] bytes: mat_size records (w, h))."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return rng.integers(lo, hi, (h, w, 3)).astype(np.uint8)
+
+
+BLACK = (0, 0, 0)
+
+
+def class_no_light():
+    """No light (:563 loop runs zero times): no shadow ray, the face stays at the ambient 0.1 (:647), and a camera hit's bounce still
+    goes out.  White and image colours (bouncing) beside a colour too dark to bounce."""
+    mats = [_lambert(), _lambert(color=_img(31, 6, 4)), _lambert(color=(1, 1, 0))]
+    return S.make_soup(64, 48, 1500, 0.14, seed=31, samples=2, materials=mats, lights=[], random_uv=True, name="class_no_light")
+
+
+# One light per scene.  Positional types (1, 2, 7, 8, 9) draw their sphere point before the bounce's (:573 then :671), have a finite
+# shadow range and a finite half-attenuation (pow(0.5, d/h) :631); types 1, 7 and 9 sit inside the soup (z 2..4), so N.L changes sign
+# across the frame and shadow rays end mid-grid.  Directional types (3-6) draw a point on a spread sphere; type 0 and an unknown type
+# draw nothing and leave lmin == lmax == 0 (no shadow ray, :628-636 with N.L = 0).
+_CLASS_LIGHTS = {
+    0: dict(type=S.LIGHT_OMNI, pos=(0.1, 0.0, 3.0), col=(0.9, 0.8, 0.7)),
+    1: dict(type=S.LIGHT_SPOT, pos=(0.1, -0.05, 3.0), col=(0.9, 0.8, 0.7), radius=0.15, half_att=1.5),
+    2: dict(type=S.LIGHT_SPOTRECT, pos=(-0.4, 0.3, 1.2), col=(0.6, 0.9, 0.5), radius=0.3, half_att=1.5),
+    3: dict(type=S.LIGHT_DISTANT, dir=(-0.6, 0.2, 0.75), col=(0.8, 0.9, 1.0), radius=12.0),
+    4: dict(type=S.LIGHT_PARALLEL, dir=(0.1, 0.9, -0.4), col=(1.0, 0.7, 0.5), radius=0.0),
+    5: dict(type=S.LIGHT_PARSPOT, dir=(0.7, -0.1, 0.7), col=(0.5, 0.6, 0.9), radius=40.0),
+    6: dict(type=S.LIGHT_PARSPOTRECT, dir=(0.0, 0.0, 1.0), col=(0.7, 0.7, 0.7), radius=3.0),
+    7: dict(type=S.LIGHT_TUBE, pos=(-0.2, 0.1, 2.6), col=(1.2, 1.0, 0.8), radius=0.05, half_att=1.5),
+    8: dict(type=S.LIGHT_AREA, pos=(0.3, -0.2, 1.0), col=(0.9, 1.0, 0.6), radius=0.4, half_att=1.5),
+    9: dict(type=S.LIGHT_PHOTOMETRIC, pos=(0.0, 0.2, 3.4), col=(0.8, 0.6, 1.1), radius=0.25, half_att=1.5),
+    42: dict(type=42, pos=(0.1, 0.0, 3.0), dir=(0.3, -0.8, 0.5), col=(0.9, 0.8, 0.7), radius=0.3, half_att=1.5),
+}
+
+
+def _class_light(t):
+    def make():
+        mats = [_lambert(), _lambert(color=_img(40 + t, 5, 5, 40, 256))]
+        return S.make_soup(64, 48, 2000, 0.14, seed=40 + t, samples=2, materials=mats, lights=[_CLASS_LIGHTS[t]], random_uv=True,
+                           name=f"class_light_type_{t}")
+    make.__name__ = f"class_light_type_{t}"
+    make.__doc__ = f"One light of type {t} ({_CLASS_LIGHTS[t]})."
+    return make
+
+
+def class_textured_bumped():
+    """Image colours of 1x7, 7x1, 5x5 and 8x3 texels and an absent colour (:550, black); one-texel height maps of several values
+    (shading_normal's one-texel branch, :231-261); absent and one-black-texel reflection, transparency and luminance side by side;
+    smooth normals, wrapping UVs and material -1 on about a fifth of the triangles."""
+    mats = [
+        dict(color=_img(51, 1, 7), reflection=None, transparency=BLACK, bump=(255, 255, 255), luminance=None),
+        dict(color=_img(52, 7, 1), reflection=BLACK, transparency=None, bump=(17, 200, 3), luminance=BLACK),
+        dict(color=_img(53, 5, 5), reflection=None, transparency=None, bump=None, luminance=None),
+        dict(color=_img(54, 8, 3), reflection=BLACK, transparency=BLACK, bump=(128, 0, 0), luminance=BLACK),
+        dict(color=None, reflection=BLACK, transparency=None, bump=(60, 61, 62), luminance=None),
+        dict(color=(255, 255, 255), reflection=None, transparency=BLACK, bump=(0, 0, 255), luminance=BLACK),
+    ]
+    sc = S.make_soup(64, 48, 2500, 0.13, seed=55, samples=2, materials=mats, random_uv=True, smooth_normals=True,
+                     lights=[dict(type=S.LIGHT_TUBE, pos=(0.05, 0.05, 2.8), col=(1.1, 0.9, 0.8), radius=0.1, half_att=1.5)],
+                     name="class_textured_bumped")
+    rng = np.random.Generator(np.random.PCG64(56))
+    sc.tri_material[rng.random(sc.triangle_count) < 0.2] = -1
+    return sc
+
+
+def class_degenerate_outside():
+    """Triangles collapsed to points and segments (NaN barycentrics meet one-texel colour and height descriptors), the camera
+    outside the bounding box, one light bright enough to saturate (:726-741), S=3."""
+    mats = [_lambert(), _lambert(color=_img(61, 4, 4), bump=(90, 10, 200))]
+    sc = S.make_soup(56, 40, 900, 0.12, seed=61, samples=3, materials=mats, random_uv=True,
+                     lights=[dict(type=S.LIGHT_DISTANT, dir=(-0.5, -0.5, 0.2), col=(3.0, 2.0, 40.0))],
+                     name="class_degenerate_outside")
+    v = sc.vertex.reshape(-1, 3, 4)
+    v[::7, 1] = v[::7, 0]
+    v[::7, 2] = v[::7, 0]
+    v[::11, 2] = v[::11, 1]
+    return sc
+
+
+def class_dark_and_bright():
+    """Colours on both sides of the bounce threshold 3/256 <= w.x + w.y + w.z (:664): (1,1,1) bounces, (1,1,0) and (2,0,0) do not,
+    so paths of both shapes share waves; one positional light with a negative colour channel."""
+    mats = [_lambert(color=(1, 1, 1)), _lambert(color=(1, 1, 0)), _lambert(color=(2, 0, 0)), _lambert(),
+            _lambert(color=_img(71, 3, 3, 0, 3))]
+    return S.make_soup(64, 48, 2000, 0.13, seed=71, samples=2, materials=mats, random_uv=True,
+                       lights=[dict(type=S.LIGHT_AREA, pos=(0.2, 0.1, 2.9), col=(-0.4, 0.7, 1.5), radius=0.2, half_att=2.5)],
+                       name="class_dark_and_bright")
+
+
+CLASS = [class_no_light] + [_class_light(t) for t in list(range(10)) + [42]] + [class_textured_bumped, class_degenerate_outside,
+                                                                                  class_dark_and_bright]
+
+
+def class_by_name(name):
+    for f in CLASS:
+        if f.__name__ == name:
+            return f
+    raise KeyError(name)
+
+
+# ---- fuzz scenes (tests/test_fuzz_parity_gpu.py, tests/fuzz_parity.py) --------------------------------------------------------
+
+def fuzz_scene(seed):
+    """A random soup drawn from the seed alone.  Even seeds draw an opaque-diffuse class scene: zero or one light of any type,
+    reflection, transparency and luminance absent or black, a height map absent or one texel of any value, material -1 on some
+    triangles.  Odd seeds draw a general scene: textures, bump maps, mirrors, transparency, glow and up to four lights."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    nm = int(rng.integers(1, 6))
+
+    def image():
+        return rng.integers(0, 256, (int(rng.integers(1, 9)), int(rng.integers(1, 9)), 3))
+
+    if seed % 2 == 0:
+        def absent_or_black():
+            return None if rng.integers(0, 2) else BLACK
+        mats = []
+        for _ in range(nm):
+            colour = (None, tuple(rng.integers(0, 256, 3)), image())[int(rng.integers(0, 3))]
+            bump = None if rng.integers(0, 2) else tuple(rng.integers(0, 256, 3))
+            mats.append(dict(color=colour, reflection=absent_or_black(), transparency=absent_or_black(), bump=bump,
+                             luminance=absent_or_black()))
+        nl = int(rng.integers(0, 4) > 0)  # (one light three times in four)
+    else:
+        mats = [dict(color=image(), reflection=tuple(rng.integers(0, 200, 3)), transparency=tuple(rng.integers(0, 200, 3)), bump=image(),
+                     luminance=tuple(rng.integers(0, 60, 3))) for _ in range(nm)]
+        nl = int(rng.integers(0, 5))
+    lights = [dict(type=int(t), pos=tuple(rng.uniform(-1, 1, 3) + [0, 0, 2]), dir=tuple(rng.uniform(-1, 1, 3)), col=tuple(rng.uniform(0, 1, 3)),
+                   radius=float(rng.uniform(0, 1)), half_att=float(rng.choice([np.inf, 2.5, 0.7]))) for t in rng.integers(0, 11, nl)]
+    w, h = int(rng.integers(60, 321)), int(rng.integers(40, 241))
+    tris, edge = int(rng.integers(200, 20001)), float(rng.choice([0.01, 0.03, 0.08, 0.2]))
+    sc = S.make_soup(w, h, tris, edge, seed=seed, samples=int(rng.integers(1, 5)), materials=mats, lights=lights, random_uv=True,
+                     smooth_normals=bool(rng.integers(0, 2)), name=f"fuzz_{seed}")
+    if seed % 2 == 0 and rng.integers(0, 2):
+        sc.tri_material[rng.random(sc.triangle_count) < 0.15] = -1
+    sc.meta.update(materials=nm, lights=[int(t) for t in sc.light_type], path_class="opaque-diffuse" if seed % 2 == 0 else "general")
+    return sc
+
+
+def fuzz_summary(sc):
+    m = sc.meta
+    return (f"seed {m['seed']}: {sc.width}x{sc.height}, {sc.triangle_count} triangles (edge {m['edge']}), {m['materials']} materials, "
+            f"light types {m['lights']}, S={sc.sample_count}, drawn as {m['path_class']}")
+
+
 def by_name(name):
     for f in ALL:
         if f.__name__ == name:

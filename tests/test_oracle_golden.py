@@ -120,3 +120,20 @@ def test_oracle_matches_reference_kernel_on_fresh_scenes(seed):
     if O.have_ref():
         for ch, x, y in zip("RGB", O.ref_render(sc), want):
             assert np.array_equal(x, y), f"seed {seed}: the reference kernel no longer gives the stored plane {ch}"
+
+
+@pytest.mark.parametrize("name", [f.__name__ for f in scenarios.CLASS])
+def test_oracle_matches_reference_kernel_on_class_scenes(name):
+    """The opaque-diffuse scenarios (scenarios.CLASS): restatement == the reference's stored planes
+    (tests/golden/ref_class_scenes.npz); where oracle/_ref exists the reference kernel must still give them."""
+    from opencl_render_amd import raytrace as R
+    sc = scenarios.class_by_name(name)()
+    R.build_lists(sc)
+    stored = np.load(os.path.join(GOLDEN, "ref_class_scenes.npz"))
+    want = [stored[f"{name}_{c}"] for c in "rgb"]
+    for ch, x, y in zip("RGB", O.oracle_render(sc), want):
+        assert np.array_equal(x, y), f"{name}: plane {ch} differs from the reference's in {(x != y).sum()} pixels"
+    if O.have_ref():
+        for ch, x, y in zip("RGB", O.ref_render(sc), want):
+            assert np.array_equal(x, y), f"{name}: the reference kernel no longer gives the stored plane {ch}"
+    assert set(stored.files) == {f"{f.__name__}_{c}" for f in scenarios.CLASS for c in "rgb"}

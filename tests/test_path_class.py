@@ -4,6 +4,7 @@ most one light) or the general one.  No GPU needed."""
 import copy
 
 import numpy as np
+import pytest
 
 import scenarios as SC
 from opencl_render_amd import raytrace as R, scene as S
@@ -52,3 +53,15 @@ def test_general_scenes():
     assert R.path_class(_with_lights(_soup(), two)) == R.PATH_CLASS_GENERAL
     for ch in ("reflection", "transparency", "luminance"):  # one texel that is not black
         assert R.path_class(_with_materials(_soup(), [dict(LAMBERT, **{ch: (0, 0, 1)})])) == R.PATH_CLASS_GENERAL, ch
+
+
+@pytest.mark.parametrize("name", [f.__name__ for f in SC.CLASS])
+def test_class_scenarios_stay_in_the_class(name):
+    """Every scenario the class tests pin (scenarios.CLASS) must run the opaque-diffuse kernel: one that drifted out of the class would
+    quietly test the general kernel instead."""
+    assert R.path_class(SC.class_by_name(name)()) == R.PATH_CLASS_OPAQUE_DIFFUSE
+
+
+def test_even_fuzz_seeds_draw_class_scenes():
+    for seed in range(0, 64, 2):
+        assert R.path_class(SC.fuzz_scene(seed)) == R.PATH_CLASS_OPAQUE_DIFFUSE, SC.fuzz_summary(SC.fuzz_scene(seed))
