@@ -282,7 +282,8 @@ int rtHipBuildCameraList(cl_uint width, cl_uint height, const cl_float eye[4], c
 /* The same camera lists built on a HIP device (rt_build_device.hip): identical membership (the arithmetic is one shared
  * header compiled for both), every pixel's entries ascending, and the reference's neighbour de-duplication (:580-613: equal
  * neighbouring lists share storage) applied, so Start, End and the list equal rtHipBuildCameraList's.  Fails (no CPU
- * fallback) when the device is missing.
+ * fallback) when the device is missing.  Returns -3, before the list is allocated, when it would hold more than 2^32 - 1 entries
+ * (the host builder's limit; "build_list_limit" of rtHipTune lowers it).
  * *deviceMs (optional) = device time of the build without the transfers. */
 int rtHipBuildCameraListDevice(int device, cl_uint width, cl_uint height, const cl_float eye[4], const cl_float eyeToTopLeft[4],
                                const cl_float leftToRight[4], const cl_float topToBottom[4], cl_float pixelSizeInv,
@@ -295,7 +296,8 @@ int rtHipBuildSceneGrid(cl_uint vertexCount, cl_uint triangleCount, const cl_flo
 
 /* The same grid built on a HIP device (rt_build_device.hip): split planes from radix-sorted coordinates, the flood fill of
  * every triangle with the shared membership test (small triangles one thread each, big ones one workgroup each), pairs
- * radix-sorted on cell << 32 | triangle.  Same planes, starts and lists as rtHipBuildSceneGrid.  No CPU fallback. */
+ * radix-sorted on cell << 32 | triangle.  Same planes, starts and lists as rtHipBuildSceneGrid.  No CPU fallback.  Returns -3
+ * for more than 2^32 - 1 pairs (lowered by "build_list_limit"), -7 when a single fill outgrows its workgroup queue. */
 int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uint triangleCount, const cl_float3 *vertex, const cl_int3 *triIndex,
                               cl_float3 outBoxMin[257], cl_uint **outStart, cl_uint **outList, uint64_t *outListSize, double *deviceMs);
 
@@ -431,7 +433,9 @@ int rtHipDeviceKat(int device, int op, cl_uint count, const void *in, cl_uint in
  * "slice_rays", "small_slices", "group_rays", "blocking", "batch_plan", "pipeline", "timing", "cache", "logic_class" (0: every scene's
  * paths run on the general logic kernel; 1, the default: on the kernel of the scene's path class), "dead_shadow" (0: trace every
  * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), and the test hooks
- * "plan_rounds", "plan_grid_tiny", "virtual_devices".  Returns 0, -1 for an unknown key. */
+ * "plan_rounds", "plan_grid_tiny", "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
+ * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
+ * and most 2^32 - 1; above it they return -3).  Returns 0, -1 for an unknown key. */
 int rtHipTune(const char *key, double value);
 
 /* TEST-ONLY: device addresses held by the first scene of RaytraceAll's cache -- triangle records, shading rows, the grid's pair
@@ -456,6 +460,18 @@ int rtHipTestPathClass(const rtHipScene *scene);
  * after the frame was synchronised; with several sample batches the figures are the last batch's.  Returns the frame's round count,
  * -1 for invalid arguments. */
 int rtHipTestRoundLog(const rtHipScene *scene, cl_uint *rays, cl_uint n);
+
+/* TEST-ONLY: what the calling thread's last device list builds did (rtHipBuildCameraListDevice, rtHipBuildSceneGridDevice; each
+ * clears and fills its own fields), so that tests can prove which paths ran.  out[i] for i < n in the order of RT_BUILD_LOG_*:
+ * camera triangles rasterised by one thread / by a workgroup (clipped rectangle above 1024 pixels), camera list entries before the
+ * de-duplication; grid triangles filled by one thread / handed to workgroups, workgroup batches, first and final key capacity,
+ * 1 when the key buffer grew for the big triangles, fill attempts (2 after the first fill overflowed), (cell, triangle) pairs.  The
+ * grid's per-attempt fields are the last attempt's.  Fields past RT_BUILD_LOG_FIELDS read 0.  Returns RT_BUILD_LOG_FIELDS, -1 for
+ * invalid arguments. */
+enum { RT_BUILD_LOG_CAM_THREAD = 0, RT_BUILD_LOG_CAM_GROUP, RT_BUILD_LOG_CAM_ENTRIES, RT_BUILD_LOG_GRID_THREAD, RT_BUILD_LOG_GRID_GROUP,
+       RT_BUILD_LOG_GRID_BATCHES, RT_BUILD_LOG_KEY_CAP_FIRST, RT_BUILD_LOG_KEY_CAP_FINAL, RT_BUILD_LOG_GREW, RT_BUILD_LOG_ATTEMPTS,
+       RT_BUILD_LOG_PAIRS, RT_BUILD_LOG_FIELDS };
+int rtHipTestBuildLog(uint64_t *out, cl_uint n);
 
 #ifdef __cplusplus
 }

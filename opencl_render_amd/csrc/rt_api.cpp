@@ -6,6 +6,7 @@
 // There is no CPU fallback: without a HIP device every entry point that would compute fails with an error text.
 #include "raytrace_hip.h"
 #include "rt_device.h"
+#include "rt_build_shared.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -96,10 +97,24 @@ struct Tuning {
     uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
     uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
     uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
+    uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
+    uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
 };
 Tuning g_tune;
 std::mutex g_tuneMutex;
 Tuning tuning() { std::lock_guard<std::mutex> lock(g_tuneMutex); return g_tune; }
+
+} // namespace
+
+// The device builders' test hooks (rt_build_shared.h).
+void rtbuild::device_build_tuning(uint64_t *keyCap, uint64_t *listLimit)
+{
+    const Tuning t = tuning();
+    *keyCap = t.buildKeyCap;
+    *listLimit = t.buildListLimit;
+}
+
+namespace {
 
 // Device scratch of a scene build: freed when the scope ends, whichever way it ends.
 struct DevScratch {
@@ -1515,6 +1530,8 @@ int rtHipTune(const char *key, double value)
         { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow },
     };
     if (k == "state_mb") { T.stateMb = (uint64_t)(value < 0 ? 0 : value); return 0; }
+    if (k == "build_key_cap") { T.buildKeyCap = (uint64_t)(value < 0 ? 0 : std::min(value, 1e18)); return 0; }
+    if (k == "build_list_limit") { T.buildListLimit = u; return 0; }
     for (auto &e : table)
         if (k == e.name) { *e.field = u; return 0; }
     return fail("rtHipTune: unknown key '%s'", key);

@@ -10,6 +10,7 @@
 //   cam_rasterize    one thread per triangle (COUNT or FILL pass): triangles whose clipped rectangle has more than
 //                    RT_BIG_RECT pixels are put on a list instead ...
 //   cam_rasterize_big ... and rasterized by one workgroup each, the pixels of the rectangle dealt to its threads
+//   cam_total        the number of entries in 64 bits, checked against the list limit before the list is allocated
 //   cam_sort_pixels  one thread per pixel: insertion sort of its (short) list
 //   cam_dedup_*      the reference's neighbour de-duplication (:580-613: a pixel whose list equals its left, else its upper
 //                    neighbour's shares that neighbour's storage), so Start/End/list equal the host builder's arrays
@@ -89,6 +90,16 @@ __global__ __launch_bounds__(256) void cam_rasterize_big(uint32_t W, uint32_t H,
             if (rtbuild::rect_pixel_test(s, x, y)) emit_pixel<FILL>((uint64_t)x + (uint64_t)y * (uint64_t)W, t, count, start, list);
         }
     }
+}
+
+// Sum of the per-pixel counts in 64 bits: the exclusive scan that gives the starts runs in 32 bits and would wrap unnoticed.
+__global__ __launch_bounds__(256) void cam_total(uint64_t P, const uint32_t *__restrict__ count, unsigned long long *total)
+{
+    unsigned long long sum = 0;
+    for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (uint64_t)gridDim.x * 256) sum += count[p];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
 }
 
 __global__ __launch_bounds__(256) void cam_sort_pixels(uint64_t P, const uint32_t *__restrict__ start, const uint32_t *__restrict__ count, uint32_t *list,
@@ -174,16 +185,29 @@ struct Buffers { // frees what it holds
 
 #define BUILD_OK(expr) do { if ((expr) != hipSuccess) return -4; } while (0)
 
+// What the calling thread's last device builds did (rtHipTestBuildLog, RT_BUILD_LOG_* order): each builder clears and fills its own fields.
+thread_local uint64_t t_buildLog[RT_BUILD_LOG_FIELDS];
+
 } // namespace
+
+extern "C" int rtHipTestBuildLog(uint64_t *out, cl_uint n)
+{
+    if (n && !out) return -1;
+    for (cl_uint i = 0; i < n; ++i) out[i] = i < RT_BUILD_LOG_FIELDS ? t_buildLog[i] : 0;
+    return RT_BUILD_LOG_FIELDS;
+}
 
 extern "C" int rtHipBuildCameraListDevice(int device, cl_uint W, cl_uint H, const cl_float eye[4], const cl_float eyeToTopLeft[4],
                                           const cl_float leftToRight[4], const cl_float topToBottom[4], cl_float pixelSizeInv,
                                           cl_uint vertexCount, cl_uint triangleCount, const cl_float3 *vertex, const cl_int3 *triIndex,
                                           cl_uint **outStart, cl_uint **outEnd, cl_uint **outList, uint64_t *outListSize, double *deviceMs)
 {
+    for (int i = RT_BUILD_LOG_CAM_THREAD; i <= RT_BUILD_LOG_CAM_ENTRIES; ++i) t_buildLog[i] = 0;
     if (!outStart || !outEnd || !outList || !outListSize || W == 0 || H == 0) return -1;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || device < 0 || device >= nDev) return -5; // no CPU fallback: use rtHipBuildCameraList for that
+    uint64_t tunedKeyCap = 0, listLimit = 0;
+    rtbuild::device_build_tuning(&tunedKeyCap, &listLimit);
     BUILD_OK(hipSetDevice(device));
     const uint64_t P = (uint64_t)W * H;
     const uint32_t T = triangleCount;
@@ -195,9 +219,10 @@ extern "C" int rtHipBuildCameraListDevice(int device, cl_uint W, cl_uint H, cons
     Buffers buf;
     float4 *dVertex = nullptr; int4 *dIndex = nullptr; F2 *dPos = nullptr;
     uint32_t *dCount = nullptr, *dStart = nullptr, *dEnd = nullptr, *dList = nullptr, *dBigList = nullptr, *dBigCount = nullptr;
+    unsigned long long *dTotal = nullptr;
     BUILD_OK(buf.alloc(&dVertex, vertexCount)); BUILD_OK(buf.alloc(&dIndex, T)); BUILD_OK(buf.alloc(&dPos, (size_t)3 * T));
     BUILD_OK(buf.alloc(&dCount, P)); BUILD_OK(buf.alloc(&dStart, P + 1)); BUILD_OK(buf.alloc(&dEnd, P));
-    BUILD_OK(buf.alloc(&dBigList, T)); BUILD_OK(buf.alloc(&dBigCount, 1));
+    BUILD_OK(buf.alloc(&dBigList, T)); BUILD_OK(buf.alloc(&dBigCount, 1)); BUILD_OK(buf.alloc(&dTotal, 1));
     BUILD_OK(hipMemcpy(dVertex, vertex, (size_t)vertexCount * 16, hipMemcpyHostToDevice));
     BUILD_OK(hipMemcpy(dIndex, triIndex, (size_t)T * 16, hipMemcpyHostToDevice));
     hipEvent_t e0, e1;
@@ -206,27 +231,32 @@ extern "C" int rtHipBuildCameraListDevice(int device, cl_uint W, cl_uint H, cons
     const uint32_t tBlocks = (T + 255) / 256, bigBlocks = 1024;
     BUILD_OK(hipMemsetAsync(dCount, 0, P * 4, nullptr));
     BUILD_OK(hipMemsetAsync(dBigCount, 0, 4, nullptr));
+    BUILD_OK(hipMemsetAsync(dTotal, 0, 8, nullptr));
     if (T) {
         hipLaunchKernelGGL(cam_project, dim3(tBlocks), dim3(256), 0, nullptr, cam, T, dVertex, dIndex, dPos);
         hipLaunchKernelGGL(cam_rasterize<false>, dim3(tBlocks), dim3(256), 0, nullptr, W, H, T, dPos, dCount, dStart, dList, dBigList, dBigCount);
         hipLaunchKernelGGL(cam_rasterize_big<false>, dim3(bigBlocks), dim3(256), 0, nullptr, W, H, dPos, dCount, dStart, dList, dBigList, dBigCount);
     }
-    // exclusive scan of the counts -> start; the total is start[P-1] + count[P-1]
+    // the total in 64 bits, checked before anything is sized by it: above 2^32 - 1 the 32-bit starts below would have wrapped
+    const uint32_t pBlocks = (uint32_t)((P + 255) / 256);
+    hipLaunchKernelGGL(cam_total, dim3(std::min<uint32_t>(pBlocks, 1024u)), dim3(256), 0, nullptr, P, dCount, dTotal);
+    unsigned long long total = 0;
+    uint32_t bigTotal = 0;
+    BUILD_OK(hipMemcpy(&total, dTotal, 8, hipMemcpyDeviceToHost));
+    BUILD_OK(hipMemcpy(&bigTotal, dBigCount, 4, hipMemcpyDeviceToHost));
+    t_buildLog[RT_BUILD_LOG_CAM_THREAD] = T - bigTotal; t_buildLog[RT_BUILD_LOG_CAM_GROUP] = bigTotal; t_buildLog[RT_BUILD_LOG_CAM_ENTRIES] = total;
+    if (total > listLimit) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return -3; } // (like the host builder)
+    // exclusive scan of the counts -> start
     void *tmp = nullptr; size_t tmpBytes = 0;
     BUILD_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, dCount, dStart, (int)P, nullptr));
     BUILD_OK(buf.alloc((char **)&tmp, tmpBytes));
     BUILD_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmpBytes, dCount, dStart, (int)P, nullptr));
-    uint32_t lastStart = 0, lastCount = 0;
-    BUILD_OK(hipMemcpy(&lastStart, dStart + (P - 1), 4, hipMemcpyDeviceToHost));
-    BUILD_OK(hipMemcpy(&lastCount, dCount + (P - 1), 4, hipMemcpyDeviceToHost));
-    const uint64_t total = (uint64_t)lastStart + lastCount; // (a sum above 2^32 has wrapped: checked below through the counts)
     BUILD_OK(buf.alloc(&dList, total));
     BUILD_OK(hipMemsetAsync(dCount, 0, P * 4, nullptr));
     if (T) {
         hipLaunchKernelGGL(cam_rasterize<true>, dim3(tBlocks), dim3(256), 0, nullptr, W, H, T, dPos, dCount, dStart, dList, dBigList, dBigCount);
         hipLaunchKernelGGL(cam_rasterize_big<true>, dim3(bigBlocks), dim3(256), 0, nullptr, W, H, dPos, dCount, dStart, dList, dBigList, dBigCount);
     }
-    const uint32_t pBlocks = (uint32_t)((P + 255) / 256);
     hipLaunchKernelGGL(cam_sort_pixels, dim3(pBlocks), dim3(256), 0, nullptr, P, dStart, dCount, dList, dEnd);
     // neighbour de-duplication: parents, sizes kept, new starts of the roots, roots of everybody, compacted storage
     uint32_t *dParent = nullptr, *dKeep = nullptr, *dNewStart = nullptr, *dOutList = nullptr, *dOutStart = nullptr;
@@ -523,9 +553,12 @@ __global__ __launch_bounds__(256) void grid_write_list(unsigned long long n, con
 extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uint triangleCount, const cl_float3 *vertex, const cl_int3 *triIndex,
                                          cl_float3 outBoxMin[257], cl_uint **outStart, cl_uint **outList, uint64_t *outListSize, double *deviceMs)
 {
+    for (int i = RT_BUILD_LOG_GRID_THREAD; i < RT_BUILD_LOG_FIELDS; ++i) t_buildLog[i] = 0;
     if (!outBoxMin || !outStart || !outList || !outListSize) return -1;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || device < 0 || device >= nDev) return -5; // no CPU fallback: rtHipBuildSceneGrid is the host builder
+    uint64_t tunedKeyCap = 0, listLimit = 0;
+    rtbuild::device_build_tuning(&tunedKeyCap, &listLimit);
     BUILD_OK(hipSetDevice(device));
     const uint32_t V = vertexCount, T = triangleCount;
     for (uint32_t t = 0; t < T; ++t)
@@ -536,7 +569,9 @@ extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uin
     float *dVals = nullptr, *dSorted = nullptr, *dBm = nullptr;
     unsigned long long *dKeys = nullptr, *dKeysSorted = nullptr, *dCursor = nullptr;
     uint32_t *dBigList = nullptr, *dBigCount = nullptr, *dOverflow = nullptr, *dBitmaps = nullptr, *dQueues = nullptr, *dStart = nullptr, *dCount = nullptr;
-    const unsigned long long keyCap = std::max<unsigned long long>(32ull * T, 1ull << 22);
+    const unsigned long long keyCap = tunedKeyCap ? tunedKeyCap : std::max<unsigned long long>(32ull * T, 1ull << 22);
+    uint64_t *log = t_buildLog;
+    log[RT_BUILD_LOG_KEY_CAP_FIRST] = keyCap;
     BUILD_OK(buf.alloc(&dVertex, V)); BUILD_OK(buf.alloc(&dIndex, T));
     BUILD_OK(buf.alloc(&dVals, (size_t)3 * V)); BUILD_OK(buf.alloc(&dSorted, (size_t)3 * V)); BUILD_OK(buf.alloc(&dBm, 4 * (rtbuild::DIV + 1)));
     BUILD_OK(buf.alloc(&dKeys, keyCap)); BUILD_OK(buf.alloc(&dKeysSorted, keyCap)); BUILD_OK(buf.alloc(&dCursor, 1));
@@ -559,10 +594,10 @@ extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uin
     if (V) {
         hipLaunchKernelGGL(grid_axis_values, dim3((V + 255) / 256), dim3(256), 0, nullptr, V, dVertex, dVals);
         void *tmp = nullptr; size_t tmpBytes = 0;
-        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, dVals, dSorted, (int)V, 0, 32, nullptr));
+        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, dVals, dSorted, (size_t)V, 0, 32, nullptr));
         BUILD_OK(buf3.alloc((char **)&tmp, tmpBytes));
         for (int w = 0; w < 3; ++w)
-            BUILD_OK(hipcub::DeviceRadixSort::SortKeys(tmp, tmpBytes, dVals + (size_t)w * V, dSorted + (size_t)w * V, (int)V, 0, 32, nullptr));
+            BUILD_OK(hipcub::DeviceRadixSort::SortKeys(tmp, tmpBytes, dVals + (size_t)w * V, dSorted + (size_t)w * V, (size_t)V, 0, 32, nullptr));
         hipLaunchKernelGGL(grid_planes, dim3(3), dim3(320), 0, nullptr, V, dSorted, dBm);
     }
     unsigned long long n = 0;
@@ -574,6 +609,7 @@ extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uin
     BUILD_OK(buf3.alloc(&dPassmaps, (size_t)RT_FILL_GROUPS * (GRID_CELLS / 32))); BUILD_OK(buf3.alloc(&dBound, 1));
     BUILD_OK(hipMemsetAsync(dPassmaps, 0, (size_t)RT_FILL_GROUPS * (GRID_CELLS / 32) * 4, nullptr));
     for (int attempt = 0; attempt < 2; ++attempt) {
+        log[RT_BUILD_LOG_ATTEMPTS] = attempt + 1;
         if (T) {
             hipLaunchKernelGGL(grid_fill_small, dim3((T + 255) / 256), dim3(256), 0, nullptr, T, dVertex, dIndex, dBm, dKeys, dCursor, cap, dBigList,
                                dBigCount, dOverflow);
@@ -588,11 +624,15 @@ extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uin
                 BUILD_OK(bufRetry.alloc(&bigger, (size_t)(small + bound))); BUILD_OK(bufRetry.alloc(&biggerSorted, (size_t)(small + bound)));
                 if (small) BUILD_OK(hipMemcpy(bigger, dKeys, (size_t)small * 8, hipMemcpyDeviceToDevice));
                 dKeys = bigger; dKeysSorted = biggerSorted; cap = small + bound;
+                log[RT_BUILD_LOG_GREW] = 1;
             }
             uint32_t bigTotal = 0;
             BUILD_OK(hipMemcpy(&bigTotal, dBigCount, 4, hipMemcpyDeviceToHost));
+            log[RT_BUILD_LOG_GRID_THREAD] = T - bigTotal; log[RT_BUILD_LOG_GRID_GROUP] = bigTotal;
+            log[RT_BUILD_LOG_GRID_BATCHES] = 0;
             for (uint32_t base = 0; base < bigTotal; base += RT_FILL_GROUPS) { // RT_FILL_GROUPS bitmaps: that many big triangles at a time
                 const uint32_t batch = std::min<uint32_t>(RT_FILL_GROUPS, bigTotal - base);
+                ++log[RT_BUILD_LOG_GRID_BATCHES];
                 hipLaunchKernelGGL(grid_test_big, dim3(128, batch), dim3(256), 0, nullptr, dVertex, dIndex, dBm, dBigList, base, dPassmaps);
                 hipLaunchKernelGGL(grid_fill_big, dim3(batch), dim3(256), 0, nullptr, dVertex, dIndex, dBm, dKeys, dCursor, cap, dBigList, base,
                                    dBitmaps, dPassmaps, dQueues, dOverflow);
@@ -603,22 +643,24 @@ extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uin
         if (overflow != 1u || attempt == 1) break;
         // More pairs than the key buffer holds after all (very many mid-sized triangles).  The cursor has counted them all, like
         // the reference's own overflow pass (trianglelist.cpp:696-706): fill again into a buffer of exactly that size.
-        if (n > 0xffffffffull) return -3;
+        if (n > listLimit) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return -3; }
         cap = n;
         BUILD_OK(bufRetry.alloc(&dKeys, (size_t)cap)); BUILD_OK(bufRetry.alloc(&dKeysSorted, (size_t)cap));
         BUILD_OK(hipMemsetAsync(dCursor, 0, 8, nullptr));
         BUILD_OK(hipMemsetAsync(dBigCount, 0, 4, nullptr));
         BUILD_OK(hipMemsetAsync(dOverflow, 0, 4, nullptr));
     }
-    if (overflow || n > cap) return -7; // a single fill larger than the workgroup queue (2^22 cells), or a second overflow
-    if (n > 0xffffffffull) return -3;
+    log[RT_BUILD_LOG_KEY_CAP_FINAL] = cap; log[RT_BUILD_LOG_PAIRS] = n;
+    if (overflow || n > cap) return -7; // a single fill larger than the workgroup queue (RT_FILL_QUEUE = 2^24 cells), or a second overflow
+    if (n > listLimit) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return -3; }
     uint32_t *dList = nullptr;
     BUILD_OK(buf3.alloc(&dList, (size_t)n));
     if (n) {
         void *tmp = nullptr; size_t tmpBytes = 0;
-        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, dKeys, dKeysSorted, (int)n, 0, 56, nullptr));
+        // (64-bit item counts: an int would turn 2^31 .. 2^32 - 1 pairs, which the list limit admits, negative)
+        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, dKeys, dKeysSorted, (size_t)n, 0, 56, nullptr));
         BUILD_OK(buf3.alloc((char **)&tmp, tmpBytes));
-        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(tmp, tmpBytes, dKeys, dKeysSorted, (int)n, 0, 56, nullptr));
+        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(tmp, tmpBytes, dKeys, dKeysSorted, (size_t)n, 0, 56, nullptr));
         hipLaunchKernelGGL(grid_count_cells, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr, n, dKeysSorted, dCount);
     }
     {

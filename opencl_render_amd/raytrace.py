@@ -67,7 +67,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
-    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog",
+    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
@@ -160,6 +160,7 @@ def lib() -> C.CDLL:
     L.rtHipScenePathClass.argtypes = [C.POINTER(SceneDesc)]
     L.rtHipTestPathClass.argtypes = [vp]
     L.rtHipTestRoundLog.argtypes = [vp, C.POINTER(u32), u32]
+    L.rtHipTestBuildLog.argtypes = [C.POINTER(u64), u32]
     L.rtHipFree.argtypes = [vp]
     L.rtHipFree.restype = None
     _lib = L
@@ -175,6 +176,7 @@ _ENV_KEYS = {
     "RT_WF_BLOCKING": "blocking", "RT_WF_BATCH_PLAN": "batch_plan", "RT_WF_PLAN_ROUNDS": "plan_rounds", "RT_HIP_PIPELINE": "pipeline",
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
     "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow",
+    "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit",
 }
 
 
@@ -285,6 +287,21 @@ def build_scene_grid_device(sc: Scene, device: int = 0) -> float:
     sc.grid_start = _take(ps, GRID_DIV ** 3 + 1, np.uint32)
     sc.grid_list = _take(pl, n.value, np.uint32)
     return ms.value
+
+
+# rtHipTestBuildLog's fields, in the order of RT_BUILD_LOG_* (include/raytrace_hip.h)
+BUILD_LOG_FIELDS = ("cam_thread", "cam_group", "cam_entries", "grid_thread", "grid_group", "grid_batches", "key_cap_first", "key_cap_final",
+                    "grew", "attempts", "pairs")
+
+
+def build_log() -> dict:
+    """What this thread's last device builds did (rtHipTestBuildLog): camera triangles rasterised by one thread / a workgroup and
+    the entries before de-duplication; grid triangles filled by one thread / workgroups, workgroup batches, first and final key
+    capacity, whether the key buffer grew, fill attempts and pairs."""
+    out = (C.c_uint64 * len(BUILD_LOG_FIELDS))()
+    if lib().rtHipTestBuildLog(out, len(BUILD_LOG_FIELDS)) != len(BUILD_LOG_FIELDS):
+        raise RuntimeError("rtHipTestBuildLog: the library logs a different set of fields")
+    return dict(zip(BUILD_LOG_FIELDS, (int(v) for v in out)))
 
 
 def build_lists(sc: Scene, threads: int = 0) -> Scene:

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import builder_cases as BC
 import oracle_lib as O
 from opencl_render_amd import raytrace as R, scene as S
 
@@ -99,40 +100,60 @@ def test_empty_scene_builds():
 # rt_build_shared.h.  Still "parity unpinned" against the reference itself (trianglelist.cpp cannot be compiled here), but no
 # longer a comparison of the product with its own twin.
 
-def _builder_cases():
-    rng = np.random.Generator(np.random.PCG64(4))
-    cases = [
-        S.make_soup(72, 56, 1200, 0.12, seed=77),
-        S.make_soup(200, 150, 2500, 0.08, seed=20),                     # several tiles, ragged edges
-        S.make_soup(64, 48, 300, 1.4, seed=8),                          # triangles larger than the image, many off-screen vertices
-        S.make_soup(97, 61, 900, 0.3, seed=9, depth=(0.2, 6.0)),        # near triangles: huge projections, some straddle the image border
-    ]
-    deg = S.make_soup(56, 40, 900, 0.12, seed=18)                      # zero-area and axis-parallel triangles
-    v = deg.vertex.reshape(-1, 3, 4)
-    v[::7, 1] = v[::7, 0]; v[::7, 2] = v[::7, 0]
-    v[::11, 2] = v[::11, 1]
-    v[::5, 1, 1] = v[::5, 0, 1]                                         # horizontal edge ab (slope division by zero, :143-150)
-    v[::3, 2, 0] = v[::3, 1, 0]                                         # vertical edge bc
-    cases.append(deg)
-    snap = S.make_soup(80, 60, 600, 0.2, seed=10)                       # vertices exactly on pixel corners / split planes
-    snap.vertex[:, :3] = np.round(snap.vertex[:, :3] * 16) / 16 + np.float32(0)  # (+0 turns -0.0 into +0.0: where equal keys land is the sort's business, in the reference too)
-    cases.append(snap)
-    del rng
-    return cases
-
-
-@pytest.mark.parametrize("idx", range(6))
+@pytest.mark.parametrize("idx", range(len(BC.NAMES)))
 def test_host_builders_equal_independent_oracle(idx):
-    sc = _builder_cases()[idx]
+    name = BC.NAMES[idx]
+    sc = BC.make(name)
     R.build_lists(sc, threads=4)
     ostart, oend, olist = O.oracle_camera_list(sc)
-    assert np.array_equal(sc.cam_start, ostart), "camera Start (incl. the neighbour aliasing of :580-613)"
-    assert np.array_equal(sc.cam_end, oend), "camera End"
-    assert np.array_equal(sc.cam_list, olist), "camera list (membership, ascending order, de-duplicated storage)"
+    assert np.array_equal(sc.cam_start, ostart), f"{name}: camera Start (incl. the neighbour aliasing of :580-613)"
+    assert np.array_equal(sc.cam_end, oend), f"{name}: camera End"
+    assert np.array_equal(sc.cam_list, olist), f"{name}: camera list (membership, ascending order, de-duplicated storage)"
     obox, ogstart, oglist = O.oracle_scene_grid(sc)
-    assert sc.box_min.tobytes() == obox.tobytes(), "split planes"
-    assert np.array_equal(sc.grid_start, ogstart), "grid Start"
-    assert np.array_equal(sc.grid_list, oglist), "grid list"
+    assert_same_planes(sc, obox, name)
+    assert np.array_equal(sc.grid_start, ogstart), f"{name}: grid Start"
+    assert np.array_equal(sc.grid_list, oglist), f"{name}: grid list"
+
+
+def assert_same_planes(sc, want, label):
+    """Split planes equal byte for byte -- except in a scene with coordinates of both zero signs, where a plane taken at a run of
+    zeros may carry either sign (the sorts order -0.0 and +0.0, which compare equal, each their own way): there by value, and the
+    bytes may differ only where both planes are zero."""
+    if not sc.meta.get("signed_zeros"):
+        assert sc.box_min.tobytes() == want.tobytes(), f"{label}: split planes"
+        return
+    assert np.array_equal(sc.box_min, want), f"{label}: split planes (by value, -0 == +0)"
+    differ = sc.box_min.view(np.uint32) != want.view(np.uint32)
+    assert (sc.box_min[differ] == 0).all(), f"{label}: split planes differ in more than the sign of a zero"
+
+
+def test_builder_cases_reach_their_edges():
+    """The families are what they claim to be."""
+    L = O.oracle()
+    fp = C.POINTER(C.c_float)
+    sc = BC.make("boundary")
+    for t, want in enumerate(sc.meta["rect_area"]):  # the clipped rectangle (rt_build_shared.h rect_setup) of the projected vertices
+        xy = np.zeros((3, 2), np.float32)
+        for k in range(3):
+            v = np.ascontiguousarray(sc.vertex[sc.tri_index[t, k], :3])
+            L.rt_oracle_camera_position(O._f3p(sc.eye), O._f3p(sc.eye_to_top_left), O._f3p(sc.left_to_right), O._f3p(sc.top_to_bottom),
+                                        sc.pixel_size_inv, v.ctypes.data_as(fp), xy[k].ctypes.data_as(fp))
+        x0, x1 = int(max(0.0, min(xy[:, 0].min(), sc.width - 1))), int(min(sc.width - 1, max(xy[:, 0].max(), 0.0)))
+        y0, y1 = int(max(0.0, min(xy[:, 1].min(), sc.height - 1))), int(min(sc.height - 1, max(xy[:, 1].max(), 0.0)))
+        assert (x1 - x0 + 1) * (y1 - y0 + 1) == want, (t, xy)
+    assert sorted(set(sc.meta["rect_area"])) == [BC.BIG_RECT, BC.BIG_RECT + 1]
+    sz = BC.make("signed_zeros")
+    assert (np.signbit(sz.vertex[:, :3]) & (sz.vertex[:, :3] == 0)).sum() > 20 and (~np.signbit(sz.vertex[:, :3]) & (sz.vertex[:, :3] == 0)).sum() > 20
+    whole = R.build_lists(BC.make("whole_image"), threads=2)
+    assert len(whole.cam_list) == 1 and (whole.cam_start == 0).all() and (whole.cam_end == 1).all()
+    stacked = R.build_lists(BC.make("stacked"), threads=2)
+    assert (stacked.cam_end - stacked.cam_start).max() > 1000
+    behind = BC.make("behind_the_eye")
+    z = behind.vertex[behind.tri_index[:, :3], 2]
+    assert (z.max(axis=1) < 0).sum() > 50 and ((z.min(axis=1) < 0) & (z.max(axis=1) > 0)).sum() > 10
+    assert BC.make("nothing").vertex_count == 0 and BC.make("no_triangles").vertex_count > 0 and BC.make("no_triangles").triangle_count == 0
+    room, obj = BC.make("room"), BC.make("obj")
+    assert room.triangle_count == 146 and obj.triangle_count == 19
 
 
 def test_builder_oracle_function_level():

@@ -1,6 +1,7 @@
 """GPU end-to-end case for the front-end and the sinks (run with -m gpu): mesh scene -> both lists built ON THE DEVICE ->
 frame through the drop-in RaytraceAll on the GPU -> BMP/PPM bytes, compared with the bytes the same sinks produce from the CPU
 oracle's planes of the same scene (bit-exact planes => identical files)."""
+import copy
 import os
 
 import numpy as np
@@ -17,11 +18,14 @@ def test_mesh_to_image_file_on_the_gpu(tmp_path, hip_lib):
     if hip_lib.rtHipDeviceCount() < 1:
         pytest.fail("no HIP device (the product has no CPU fallback)")
     sc = FC.room_scene(200, 150, samples=3)
+    host = R.build_lists(copy.copy(sc))  # the host builders equal the independent builder oracle (tests/test_builders.py)
     R.build_camera_list_device(sc, 0)
     R.build_scene_grid_device(sc, 0)
+    for k in ("cam_start", "cam_end", "cam_list", "box_min", "grid_start", "grid_list"):
+        assert np.array_equal(getattr(sc, k), getattr(host, k)), f"device-built {k} differs from the host builder's"
     ok, r, g, b = R.raytrace_all(1, sc)
     assert ok, R.last_error()
-    want = O.oracle_render(sc, threads=os.cpu_count() or 1)
+    want = O.oracle_render(host, threads=os.cpu_count() or 1)  # on the host-built lists: a cell the device grid lost would show
     for ch, got, exp in zip("RGB", (r, g, b), want):
         assert np.array_equal(got, exp), f"plane {ch}: {(got != exp).sum()} values differ from the oracle"
     assert (r > 0).mean() > 0.95 and len(np.unique(r >> 8)) > 50  # a picture, not a blank or saturated frame
