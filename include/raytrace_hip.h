@@ -264,6 +264,24 @@ int rtHipReadback(rtHipScene *scene, cl_ushort *outR, cl_ushort *outG, cl_ushort
 /* Waits for `stream` (NULL = scene stream). */
 int rtHipSync(rtHipScene *scene, void *stream);
 
+/* Render passes next to the beauty image (opt-in per scene, wavefront pipeline only).  For pixel p and its samples s = 1..S, from the
+ * primary rays the frame traces anyway:
+ *   ALPHA     u16  hits * 65535 / S (64-bit integer arithmetic, truncated); hits = samples whose primary ray hit a triangle
+ *   DEPTH     f32  sample 1's eye-to-hit distance t * sqrt((dx*dx + dy*dy) + dz*dz) (its direction is not normalised); +inf on a miss
+ *   TRIANGLE  u32  the triangle sample 1's primary ray hit; 0xffffffff on a miss
+ * rtHipScenePasses allocates the pass buffer on first use (or frees it: mask 0) and takes effect from the next frame; it fails on a
+ * scene on the megakernel pipeline, and rtHipSetPipeline(MEGAKERNEL) fails while passes are on.  The buffer is laid out like the tile
+ * buffer: [slot][hits u32 | depth f32 | triangle u32][128*128].  rtHipReadbackPasses synchronises and finishes the frame like
+ * rtHipReadback, then STORES the pixels of the scene's own tiles into row-major width x height host arrays (every other pixel keeps
+ * its value, so instances with disjoint tile sets compose one image); NULL = not wanted, asking for a pass that is off is an error. */
+#define RT_HIP_PASS_ALPHA    1u
+#define RT_HIP_PASS_DEPTH    2u
+#define RT_HIP_PASS_TRIANGLE 4u
+int      rtHipScenePasses(rtHipScene *scene, cl_uint mask);
+void    *rtHipPassBuffer(rtHipScene *scene);
+uint64_t rtHipPassBufferBytes(const rtHipScene *scene);
+int      rtHipReadbackPasses(rtHipScene *scene, cl_ushort *alpha, cl_float *depth, cl_uint *triangle);
+
 /* Average device time in milliseconds of one rtHipRenderTiles frame (all its kernels) over the frames recorded since
  * the last call (HIP events on the launch stream), and the number of frames.  Returns 0 on success. */
 int rtHipKernelTime(rtHipScene *scene, double *avgMs, uint64_t *launches);
@@ -414,6 +432,12 @@ int rtHipWriteBmp(const char *path, cl_uint width, cl_uint height, const cl_usho
 
 /* Binary PPM (P6, maxval 255) of the same 8-bit image, top row first. */
 int rtHipWritePpm(const char *path, cl_uint width, cl_uint height, const cl_ushort *red, const cl_ushort *green, const cl_ushort *blue);
+
+/* Sinks of the render passes (rtHipReadbackPasses): an 8-bit binary PGM (P5, maxval 255, top row first) of a u16 plane, value >> 8
+ * like the colour sinks; a PFM greyscale image (Pf, scale -1.0 = little-endian floats, bottom row first) of an f32 plane.
+ * Returns 0, -1 bad argument, -4 I/O error. */
+int rtHipWritePgm(const char *path, cl_uint width, cl_uint height, const cl_ushort *plane);
+int rtHipWritePfm(const char *path, cl_uint width, cl_uint height, const cl_float *plane);
 
 /* ------------------------------------------------------------------------------------------------------------
  * TEST-ONLY: device-side known-answer runner (rt_kat.hip).  Runs the kernels' own building blocks -- the restatements

@@ -4,6 +4,10 @@ The counterpart of the plugin's dialog fields (image size, samples per pixel, de
 and of the tail of ``parseAndRender`` (``render.cpp:1311-1397``): build a scene through the front-end, build both lists on the
 GPU, render through the drop-in ``RaytraceAll`` and write the image the way the reference does (BMP in ``writebmp3s``'s layout,
 or PPM).  Needs an MI355X: there is no CPU fallback.
+
+``--passes PREFIX`` renders through the resident layer instead (one instance per GPU over a tile deal for the all-GPUs device) and
+also writes the render passes: PREFIX_alpha.pgm (coverage), PREFIX_depth.pfm (eye-to-hit distance of sample 1) and PREFIX_ids.npz
+(triangle, material and mesh ids of sample 1's hit; -1 -- 0xffffffff for the triangle -- where it missed).
 """
 import argparse
 import sys
@@ -12,7 +16,7 @@ import time
 import numpy as np
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(prog="python -m opencl_render_amd", description=__doc__.splitlines()[0])
     ap.add_argument("--scene", choices=["room", "soup"], default="room", help="demo room (meshes through the front-end) or a seeded triangle soup")
     ap.add_argument("--obj", help="render this Wavefront OBJ (its MTL libraries and PPM / BMP textures are read too) instead of a demo scene")
@@ -27,7 +31,39 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=1, help="computationType: 1..N = HIP device, N+1 = all GPUs (tiled)")
     ap.add_argument("--out", default="img.bmp", help=".bmp or .ppm")
     ap.add_argument("--low-byte-compat", action="store_true", help="BMP only: keep the low byte of every u16 like the reference's writebmp3s")
-    args = ap.parse_args(argv)
+    ap.add_argument("--passes", metavar="PREFIX", help="also write PREFIX_alpha.pgm, PREFIX_depth.pfm and PREFIX_ids.npz (render passes)")
+    return ap
+
+
+def render_passes(sc, device: int, gpus: int):
+    """The frame through ResidentScene with every pass on: computation type `device` (1..gpus = one GPU, gpus + 1 = all of them, one
+    instance per GPU over raytrace.tiles_of_rank).  Returns the R, G, B planes and readback_passes' dict."""
+    from . import raytrace
+    world = gpus if device == gpus + 1 else 1
+    instances = []
+    try:
+        for rank in range(world):
+            tiles = raytrace.tiles_of_rank(sc.width, sc.height, rank, world) if world > 1 else None
+            rs = raytrace.ResidentScene(sc, rank if world > 1 else device - 1, tiles, like=instances[0] if instances else None)
+            instances.append(rs)
+            rs.set_passes(alpha=True, depth=True, triangle=True)
+        for rs in instances:
+            rs.render()
+        planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
+        passes = None
+        for rs in instances:  # disjoint tiles: the planes add up, the passes are stored tile by tile
+            rs.readback(planes)
+            passes = rs.readback_passes(passes)
+    finally:
+        for rs in instances:
+            rs.close()
+    if "mesh" not in passes:  # a scene not made of front-end meshes: all of it counts as mesh 0
+        passes["mesh"] = np.where(passes["triangle"] != 0xFFFFFFFF, 0, -1).astype(np.int32)
+    return [p.reshape(sc.height, sc.width) for p in planes], passes
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
 
     from . import demo, frontend, raytrace, scene
     if raytrace.lib().rtHipDeviceCount() < 1:
@@ -52,10 +88,18 @@ def main(argv=None):
     cam_ms = raytrace.build_camera_list_device(sc, 0)
     grid_ms = raytrace.build_scene_grid_device(sc, 0)
     t2 = time.perf_counter()
-    ok, r, g, b = raytrace.raytrace_all(args.device, sc)
+    if args.passes:
+        (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount())
+        ok = True
+    else:
+        ok, r, g, b = raytrace.raytrace_all(args.device, sc)
     t3 = time.perf_counter()
     if not ok:
         sys.exit("RaytraceAll failed: " + raytrace.last_error())
+    if args.passes:
+        frontend.write_pgm(args.passes + "_alpha.pgm", passes["alpha"])
+        frontend.write_pfm(args.passes + "_depth.pfm", passes["depth"])
+        np.savez(args.passes + "_ids.npz", triangle=passes["triangle"], material=passes["material"], mesh=passes["mesh"])
     if args.out.lower().endswith(".ppm"):
         frontend.write_ppm(args.out, r, g, b)
     else:
@@ -63,7 +107,7 @@ def main(argv=None):
     rays = args.width * args.height * args.samples
     print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel -> {args.out}\n"
           f"  scene {1e3 * (t1 - t0):.0f} ms, lists on the device {1e3 * (t2 - t1):.0f} ms (kernels {cam_ms:.1f} + {grid_ms:.1f} ms), "
-          f"RaytraceAll {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
+          f"{'resident render + passes' if args.passes else 'RaytraceAll'} {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
     return 0
 
 

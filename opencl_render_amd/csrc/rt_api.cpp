@@ -40,6 +40,7 @@ extern "C" hipError_t rtp_dense_grid(const uint32_t *gridStart, const uint32_t *
                                      uint32_t *pairCount, void *scratch, size_t *scratchBytes, hipStream_t stream);
 
 extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefront *wf, hipStream_t stream);
+extern "C" hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const RtWavefront *wf, uint32_t *passBuf, hipStream_t stream);
 extern "C" hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next, hipStream_t stream);
 extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
 extern "C" hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
@@ -293,6 +294,10 @@ struct rtHipScene {
     size_t stageEventsUsed = 0;
     bool stageTiming = false;
     uint64_t roundsLast = 0;
+    // render passes (rtHipScenePasses): RT_HIP_PASS_* bits, and the pass buffer [slot][RT_PASS_WORDS][128*128] (rt_device.h) while any is on
+    uint32_t passMask = 0;
+    uint32_t *passBuf = nullptr;
+    uint64_t passBytes = 0;
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -988,7 +993,20 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
             if (!G.ctlClean) HIP_OK(hipMemsetAsync(G.wf.ctl, 0, sizeof(uint32_t) * (size_t)3 * RT_WF_CTL_WORDS, on));
             G.ctlClean = false;
             if (!planned) memset(G.hostLog, 0, sizeof(uint4) * RT_WF_ROUND_LOG); // (nothing of this group is in flight: the batch before was waited for)
-            HIP_OK(stage(0, on, [&] { return rtw_launch_primary(&G.dev, &G.wf, on); }));
+            if (sc->passBuf) {
+                // passes on: with several samples per pixel the group's hit counters (one 64 KiB plane per slot) start at zero in every
+                // frame -- in-stream, so planned and redone frames alike; a one-sample frame's kernel stores them, and sample 1 rewrites
+                // every depth and triangle word
+                uint32_t *pass = sc->passBuf + (size_t)G.slot0 * RT_PASS_WORDS * RT_TILE_PIXELS;
+                HIP_OK(stage(0, on, [&] {
+                    if (base == 0 && sampleCount > 1) {
+                        const hipError_t er = hipMemset2DAsync(pass + RT_PASS_HITS * RT_TILE_PIXELS, (size_t)RT_PASS_WORDS * RT_TILE_PIXELS * 4, 0,
+                                                               (size_t)RT_TILE_PIXELS * 4, G.slot1 - G.slot0, on);
+                        if (er != hipSuccess) return er;
+                    }
+                    return rtw_launch_primary_passes(&G.dev, &G.wf, pass, on);
+                }));
+            } else HIP_OK(stage(0, on, [&] { return rtw_launch_primary(&G.dev, &G.wf, on); }));
             if (planned) {
                 while (G.rounds < planRounds)
                     if (issue_round(G, on) != 0) return -1;
@@ -1152,6 +1170,7 @@ void rtHipSceneDestroy(rtHipScene *sc)
         if (G.done) (void)hipEventDestroy(G.done);
     }
     if (sc->forkEvent) (void)hipEventDestroy(sc->forkEvent);
+    if (sc->passBuf) (void)hipFree(sc->passBuf);
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
     sc->stager.destroy();
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
@@ -1186,9 +1205,41 @@ int rtHipSetPipeline(rtHipScene *sc, int pipeline)
 {
     if (!sc) return fail("null scene");
     if (pipeline != RT_HIP_PIPELINE_MEGAKERNEL && pipeline != RT_HIP_PIPELINE_WAVEFRONT) return fail("unknown pipeline %d", pipeline);
+    if (pipeline == RT_HIP_PIPELINE_MEGAKERNEL && sc->passMask)
+        return fail("render passes are on: the megakernel pipeline does not produce them (rtHipScenePasses(scene, 0) first)");
     sc->pipeline = pipeline;
     return 0;
 }
+
+int rtHipScenePasses(rtHipScene *sc, cl_uint mask)
+{
+    if (!sc) return fail("null scene");
+    if (mask & ~(cl_uint)(RT_HIP_PASS_ALPHA | RT_HIP_PASS_DEPTH | RT_HIP_PASS_TRIANGLE)) return fail("unknown render pass bits 0x%x", mask);
+    if (mask && sc->pipeline == RT_HIP_PIPELINE_MEGAKERNEL) return fail("render passes need the wavefront pipeline (the scene is on the megakernel)");
+    HIP_OK(hipSetDevice(sc->device));
+    if (mask == 0) {
+        if (sc->passBuf) {
+            HIP_OK(hipDeviceSynchronize()); // (frames in flight may still write it)
+            HIP_OK(hipFree(sc->passBuf));
+            sc->bytes -= sc->passBytes;
+        }
+        sc->passBuf = nullptr;
+        sc->passBytes = 0;
+    } else if (!sc->passBuf) {
+        const uint64_t n = (uint64_t)sc->tileIds.size() * RT_PASS_WORDS * RT_TILE_PIXELS * 4;
+        void *p = nullptr;
+        HIP_OK(hipMalloc(&p, n ? n : 4));
+        HIP_OK(hipMemset(p, 0, n ? n : 4));
+        sc->passBuf = (uint32_t *)p;
+        sc->passBytes = n ? n : 4;
+        sc->bytes += sc->passBytes;
+    }
+    sc->passMask = mask;
+    return 0;
+}
+
+void *rtHipPassBuffer(rtHipScene *sc) { return sc ? (void *)sc->passBuf : nullptr; }
+uint64_t rtHipPassBufferBytes(const rtHipScene *sc) { return sc && sc->passBuf ? (uint64_t)sc->tileIds.size() * RT_PASS_WORDS * RT_TILE_PIXELS * 4 : 0; }
 
 // Diagnostic: raw copy of the 8 device-side debug counters (work counters of the counted kernel, or the cycle sums of
 // an RT_DIAG_STAMPS build).  clear != 0 zeroes them afterwards.
@@ -1323,6 +1374,39 @@ int rtHipReadback(rtHipScene *sc, cl_ushort *outR, cl_ushort *outG, cl_ushort *o
                     dst[i] = (cl_ushort)(v > 0xFFFFu ? 0xFFFFu : v);
                 }
             }
+    }
+    return 0;
+}
+
+int rtHipReadbackPasses(rtHipScene *sc, cl_ushort *alpha, cl_float *depth, cl_uint *triangle)
+{
+    if (!sc) return fail("null scene");
+    const struct { const void *out; cl_uint bit; const char *name; } want[3] = {
+        { alpha, RT_HIP_PASS_ALPHA, "alpha" }, { depth, RT_HIP_PASS_DEPTH, "depth" }, { triangle, RT_HIP_PASS_TRIANGLE, "triangle" } };
+    for (const auto &w : want)
+        if (w.out && !(sc->passMask & w.bit)) return fail("the %s pass is not on for this scene (rtHipScenePasses)", w.name);
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    if (!alpha && !depth && !triangle) return 0;
+    const size_t nt = sc->tileIds.size();
+    std::vector<uint32_t> host(nt * RT_PASS_WORDS * RT_TILE_PIXELS);
+    HIP_OK(hipMemcpy(host.data(), sc->passBuf, host.size() * 4, hipMemcpyDeviceToHost));
+    const uint64_t S = sc->dev.sampleCount;
+    for (size_t s = 0; s < nt; ++s) {
+        const uint32_t tx = sc->tileIds[s] % sc->tilesX, ty = sc->tileIds[s] / sc->tilesX;
+        const uint32_t n = std::min<uint32_t>(RT_TILE, sc->width - tx * RT_TILE);
+        for (uint32_t ly = 0; ly < RT_TILE; ++ly) {
+            const uint32_t gy = ty * RT_TILE + ly;
+            if (gy >= sc->height) break;
+            const uint32_t *src = host.data() + s * RT_PASS_WORDS * RT_TILE_PIXELS + ly * RT_TILE;
+            const size_t at = (size_t)gy * sc->width + tx * RT_TILE;
+            for (uint32_t i = 0; i < n; ++i) {
+                if (alpha) alpha[at + i] = (cl_ushort)((uint64_t)src[RT_PASS_HITS * RT_TILE_PIXELS + i] * 65535u / S);
+                if (depth) memcpy(&depth[at + i], &src[RT_PASS_DEPTH * RT_TILE_PIXELS + i], 4);
+                if (triangle) triangle[at + i] = src[RT_PASS_TRIANGLE * RT_TILE_PIXELS + i];
+            }
+        }
     }
     return 0;
 }

@@ -23,6 +23,13 @@
 //  boxMin   [3][257]        split planes, one array per axis (staged into LDS by every workgroup)
 //  camStart/camEnd          per pixel of this scene's tiles, TILE-MAJOR: index = slot*128*128 + ly*128 + lx
 //  tileBuf  [slot][3][128*128] u16 planes R,G,B
+//  passBuf  [slot][RT_PASS_WORDS][128*128] 32-bit words (only when render passes are on; not part of RtDevScene): per pixel the
+//           number of samples whose primary ray hit (u32), sample 1's eye-to-hit distance (f32, +inf on a miss) and its triangle
+//           (u32, 0xffffffff on a miss)
+#define RT_PASS_HITS 0
+#define RT_PASS_DEPTH 1
+#define RT_PASS_TRIANGLE 2
+#define RT_PASS_WORDS 3
 enum { RT_PATH_CLASS_GENERAL = 0, RT_PATH_CLASS_OPAQUE_DIFFUSE = 1 };
 struct RtDevScene {
     // camera (raytrace.h:61-66)

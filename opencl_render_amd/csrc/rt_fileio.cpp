@@ -1,5 +1,6 @@
 // rt_fileio.cpp -- file input of the headless front-end (include/raytrace_hip.h, section 3): Wavefront OBJ / MTL meshes and
 // PPM / BMP images, and the projected UVs of the reference's ShdProjectPoint.
+// It also holds the sinks of the render passes (PGM of the alpha pass, PFM of the depth pass).
 //
 // The reference takes its geometry from Cinema 4D's object tree (source/render.cpp:707-1003) and its textures from C4D bitmaps
 // (render.cpp:1136-1309); neither exists without the SDK.  What a host without Cinema 4D has is files: this reader turns an OBJ
@@ -367,6 +368,43 @@ int rtHipProjectUv(int projection, const cl_float point[3], const cl_float norma
     uv[0] = (cl_float)u; uv[1] = (cl_float)v; // (cl_float) casts of render.cpp:940-941
     if (tile) return 1;
     return (u >= 0.0 && u <= 1.0 && v >= 0.0 && v <= 1.0) ? 1 : 0;
+}
+
+
+// ---- render pass sinks (rtHipReadbackPasses' planes) ----------------------------------------------------------------------------
+// PGM: one u16 plane as 8 bits, value >> 8 like the colour sinks, top row first.
+int rtHipWritePgm(const char *path, cl_uint width, cl_uint height, const cl_ushort *plane)
+{
+    if (!path || !plane || width == 0 || height == 0) return -1;
+    std::vector<cl_uchar> bytes((size_t)width * height);
+    for (size_t i = 0; i < bytes.size(); ++i) bytes[i] = (cl_uchar)(plane[i] >> 8);
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return -4;
+    bool ok = std::fprintf(f, "P5\n%u %u\n255\n", width, height) > 0;
+    ok = ok && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? 0 : -4;
+}
+
+// PFM: one f32 plane, greyscale ("Pf"), scale -1.0 = little-endian, rows bottom-up as the format has them.  Bytes are laid out
+// explicitly, so the file is the same on any host.
+int rtHipWritePfm(const char *path, cl_uint width, cl_uint height, const cl_float *plane)
+{
+    if (!path || !plane || width == 0 || height == 0) return -1;
+    std::vector<cl_uchar> bytes((size_t)width * height * 4);
+    size_t at = 0;
+    for (cl_uint row = height; row-- > 0;)
+        for (cl_uint x = 0; x < width; ++x) {
+            uint32_t v;
+            std::memcpy(&v, &plane[(size_t)row * width + x], 4);
+            for (int k = 0; k < 4; ++k) bytes[at++] = (cl_uchar)(v >> (8 * k));
+        }
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return -4;
+    bool ok = std::fprintf(f, "Pf\n%u %u\n-1.0\n", width, height) > 0;
+    ok = ok && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? 0 : -4;
 }
 
 } // extern "C"

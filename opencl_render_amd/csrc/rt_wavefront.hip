@@ -218,7 +218,11 @@ __device__ __forceinline__ V3 sphere_scaled(const SphereRaw &r, float radius)
 
 // ---- stage 1: primary rays ---------------------------------------------------------------------------------------
 // grid = (tileCount*64, samplesInBatch); workgroup = 16x16 pixel patch, wave = 8x8 quadrant.
-__global__ __launch_bounds__(256) void wf_primary_kernel(const RtDevScene S, const RtWavefront W)
+// PASSES (rtHipScenePasses): the primary hit also feeds the render passes, laid out like tileBuf ([slot][RT_PASS_*][128*128] 32-bit
+// words): every hitting sample adds 1 to its pixel's hit counter (zeroed by the host before the frame's first batch; a one-sample frame
+// stores it instead), and sample 1 writes the eye-to-hit distance and the triangle.  Without PASSES the body is the plain primary stage.
+template <bool PASSES>
+__device__ __forceinline__ void wf_primary_body(const RtDevScene &S, const RtWavefront &W, uint32_t *passBuf)
 {
     const uint32_t slot = blockIdx.x >> 6, patch = blockIdx.x & 63;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -264,6 +268,24 @@ __global__ __launch_bounds__(256) void wf_primary_kernel(const RtDevScene S, con
         W.ring[(size_t)a * (RT_RING * 3) + 1] = pack4(dir, __uint_as_float(RT_NONE));
         W.res[a] = make_uint4(hit_tri, __float_as_uint(hit_t), __float_as_uint(hit_l1), __float_as_uint(hit_l2));
     }
+    if (PASSES && valid) {
+        uint32_t *pass = passBuf + (size_t)slot * RT_PASS_WORDS * RT_TILE_PIXELS + ly * RT_TILE + lx;
+        // one sample per pixel: this thread is the pixel's only sample and stores its count (no zeroing, no atomic); otherwise the
+        // samples of a pixel sit in different workgroups and batches and add into the counter the host zeroed
+        if (S.sampleCount == 1u) pass[RT_PASS_HITS * RT_TILE_PIXELS] = born ? 1u : 0u;
+        else if (born) __hip_atomic_fetch_add(pass + RT_PASS_HITS * RT_TILE_PIXELS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (result unused: no-return atomic)
+        if (W.sampleBase + sb == 0u) {
+            const float depth = born ? hit_t * sqrt_rn(dot3(dir, dir)) : RT_INF; // dir is not normalised: t * |dir| is the distance
+            pass[RT_PASS_DEPTH * RT_TILE_PIXELS] = __float_as_uint(depth);
+            pass[RT_PASS_TRIANGLE * RT_TILE_PIXELS] = hit_tri;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void wf_primary_kernel(const RtDevScene S, const RtWavefront W) { wf_primary_body<false>(S, W, nullptr); }
+__global__ __launch_bounds__(256) void wf_primary_passes_kernel(const RtDevScene S, const RtWavefront W, uint32_t *passBuf)
+{
+    wf_primary_body<true>(S, W, passBuf);
 }
 
 // ---- trace entries: the DDA start state of a ray, and exact segments ------------------------------------------------
@@ -1995,6 +2017,14 @@ extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefr
 {
     if (scene->tileCount == 0) return hipSuccess;
     hipLaunchKernelGGL(wf_primary_kernel, dim3(scene->tileCount * 64, wf->samplesInBatch), dim3(256), 0, stream, *scene, *wf);
+    return hipGetLastError();
+}
+
+// passBuf: this tile group's slice of the pass buffer (rt_device.h, RT_PASS_*), its hit counters zeroed before the frame's first batch
+extern "C" hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const RtWavefront *wf, uint32_t *passBuf, hipStream_t stream)
+{
+    if (scene->tileCount == 0) return hipSuccess;
+    hipLaunchKernelGGL(wf_primary_passes_kernel, dim3(scene->tileCount * 64, wf->samplesInBatch), dim3(256), 0, stream, *scene, *wf, passBuf);
     return hipGetLastError();
 }
 

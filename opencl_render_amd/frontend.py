@@ -61,6 +61,8 @@ def _lib():
         L.rtHipPlanesToRgb8.argtypes = [u32, u32, vp, vp, vp, vp, C.c_int]
         L.rtHipWriteBmp.argtypes = [C.c_char_p, u32, u32, vp, vp, vp, C.c_int]
         L.rtHipWritePpm.argtypes = [C.c_char_p, u32, u32, vp, vp, vp]
+        L.rtHipWritePgm.argtypes = [C.c_char_p, u32, u32, vp]
+        L.rtHipWritePfm.argtypes = [C.c_char_p, u32, u32, vp]
         L.rtHipObjRead.argtypes = [C.c_char_p, C.POINTER(_ObjData)]
         L.rtHipObjFree.restype = None
         L.rtHipObjFree.argtypes = [C.POINTER(_ObjData)]
@@ -199,7 +201,17 @@ def scene_from_meshes(meshes: Sequence[Mesh], materials: Sequence[dict], lights:
     return Scene(width=width, height=height, eye=eye, eye_to_top_left=tl, left_to_right=lr, top_to_bottom=tb, pixel_size_inv=inv,
                  sample_count=samples, vertex=vertex, tri_index=tri_index, tri_material=tri_material, tri_uv=tri_uv, tri_normal=tri_normal,
                  mat_size=mat_size, mat_start=mat_start, textures=textures, light_type=ltype, light_pos=lpos, light_dir=ldir,
-                 light_col=lcol, light_radius=lrad, light_half_att=lhalf, name=name)
+                 light_col=lcol, light_radius=lrad, light_half_att=lhalf, name=name, tri_mesh=triangle_meshes(meshes))
+
+
+def triangle_meshes(meshes: Sequence[Mesh]) -> np.ndarray:
+    """Index of the mesh each triangle of mesh_arrays comes from: meshes in order, one triangle per triangle polygon (c == d) and two
+    per quad (render.cpp:736)."""
+    per = []
+    for m in meshes:
+        pol = np.asarray(m.polygons).reshape(-1, 4)
+        per.append(int(np.where(pol[:, 2] != pol[:, 3], 2, 1).sum()))
+    return np.repeat(np.arange(len(meshes), dtype=np.int32), np.asarray(per, np.int64))
 
 
 PROJ_SPHERICAL, PROJ_CYLINDRICAL, PROJ_FLAT, PROJ_CUBIC, PROJ_FRONTAL, PROJ_SPATIAL, PROJ_UVW, PROJ_SHRINKWRAP, PROJ_VOLUMESHADER = 0, 1, 2, 3, 4, 5, 6, 7, 10
@@ -286,6 +298,24 @@ def write_bmp(path: str, r, g, b, low_byte_compat: bool = False) -> None:
     rc = _lib().rtHipWriteBmp(path.encode(), w, h, _p(planes[0]), _p(planes[1]), _p(planes[2]), 1 if low_byte_compat else 0)
     if rc != 0:
         raise OSError(f"rtHipWriteBmp({path}) failed ({rc})")
+
+
+def write_pgm(path: str, alpha) -> None:
+    """[H,W] u16 plane (the alpha pass) -> 8-bit binary PGM, value >> 8, top row first."""
+    h, w = alpha.shape
+    plane = np.ascontiguousarray(alpha, np.uint16)
+    rc = _lib().rtHipWritePgm(path.encode(), w, h, _p(plane))
+    if rc != 0:
+        raise OSError(f"rtHipWritePgm({path}) failed ({rc})")
+
+
+def write_pfm(path: str, depth) -> None:
+    """[H,W] f32 plane (the depth pass) -> greyscale PFM, little-endian (scale -1.0), bottom row first."""
+    h, w = depth.shape
+    plane = np.ascontiguousarray(depth, np.float32)
+    rc = _lib().rtHipWritePfm(path.encode(), w, h, _p(plane))
+    if rc != 0:
+        raise OSError(f"rtHipWritePfm({path}) failed ({rc})")
 
 
 def write_ppm(path: str, r, g, b) -> None:

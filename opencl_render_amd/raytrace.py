@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RT_HIP_LIB") or os.path.join(_HERE, "libraytrace_hip.so")
 TILE = 128
 PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT = 0, 1
+PASS_ALPHA, PASS_DEPTH, PASS_TRIANGLE = 1, 2, 4  # RT_HIP_PASS_*
 
 
 class Float3(C.Structure):  # cl_float3 == cl_float4: 16 bytes, passed as two SSE eightbytes on SysV
@@ -66,9 +67,10 @@ RESIDENT_SYMBOLS = [
     "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipRenderTiles", "rtHipFrameFinish",
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
+    "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
-    "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm",
+    "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
 
@@ -146,6 +148,12 @@ def lib() -> C.CDLL:
     L.rtHipDeviceFree.argtypes = [C.c_int, vp]
     L.rtHipDeviceCopy.argtypes = [C.c_int, vp, vp, u64, C.c_int]
     L.rtHipSync.argtypes = [vp, vp]
+    L.rtHipScenePasses.argtypes = [vp, u32]
+    L.rtHipPassBuffer.restype = vp
+    L.rtHipPassBuffer.argtypes = [vp]
+    L.rtHipPassBufferBytes.restype = u64
+    L.rtHipPassBufferBytes.argtypes = [vp]
+    L.rtHipReadbackPasses.argtypes = [vp, vp, vp, vp]
     L.rtHipKernelTime.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
     L.rtHipBuildCameraList.argtypes = [u32, u32, vp, vp, vp, vp, f32, u32, vp, vp, C.c_int,
                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
@@ -496,6 +504,47 @@ class ResidentScene:
             planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
         self._check(lib().rtHipReadback(self.handle, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2])), "rtHipReadback")
         return planes
+
+    def set_passes(self, alpha: bool = False, depth: bool = False, triangle: bool = False):
+        """Render passes from the next frame on (rtHipScenePasses); all off frees the pass buffer."""
+        mask = (PASS_ALPHA if alpha else 0) | (PASS_DEPTH if depth else 0) | (PASS_TRIANGLE if triangle else 0)
+        self._check(lib().rtHipScenePasses(self.handle, mask), "rtHipScenePasses")
+        self.passes = mask
+
+    def pass_buffer(self):
+        return lib().rtHipPassBuffer(self.handle), lib().rtHipPassBufferBytes(self.handle)
+
+    def readback_passes(self, out: Optional[dict] = None) -> dict:
+        """The passes that are on, as [H, W] arrays: alpha u16, depth f32, triangle u32, and with triangle also material i32
+        (-1 on a miss) and -- for a scene made by frontend.scene_from_meshes -- mesh i32 (-1 on a miss).  `out`: arrays of an earlier
+        call (another instance's tiles) to store this instance's tiles into; pixels of other tiles keep their values."""
+        sc = self.scene
+        mask = getattr(self, "passes", 0)
+        shape = (sc.height, sc.width)
+        if out is None:
+            out = {}
+        if mask & PASS_ALPHA:
+            out.setdefault("alpha", np.zeros(shape, np.uint16))
+        if mask & PASS_DEPTH:
+            out.setdefault("depth", np.full(shape, np.inf, np.float32))
+        if mask & PASS_TRIANGLE:
+            out.setdefault("triangle", np.full(shape, 0xFFFFFFFF, np.uint32))
+        for k, dt in (("alpha", np.uint16), ("depth", np.float32), ("triangle", np.uint32)):
+            if k in out and (out[k].dtype != dt or out[k].shape != shape or not out[k].flags.c_contiguous):
+                raise ValueError(f"readback_passes: out[{k!r}] must be a C-contiguous {shape} {np.dtype(dt).name} array")
+        self._check(lib().rtHipReadbackPasses(self.handle, _ptr(out.get("alpha")), _ptr(out.get("depth")), _ptr(out.get("triangle"))),
+                    "rtHipReadbackPasses")
+        if "triangle" in out:
+            tri = out["triangle"]
+            hit = tri != 0xFFFFFFFF
+            idx = np.where(hit, tri, 0).astype(np.int64)
+            mat = np.asarray(sc.tri_material, np.int32)
+            out["material"] = np.where(hit, mat[idx] if len(mat) else -1, -1).astype(np.int32)
+            tri_mesh = getattr(sc, "tri_mesh", None)
+            if tri_mesh is not None:
+                tm = np.asarray(tri_mesh, np.int32)
+                out["mesh"] = np.where(hit, tm[idx] if len(tm) else -1, -1).astype(np.int32)
+        return out
 
 
 def render_resident(sc: Scene, device: int = 0):

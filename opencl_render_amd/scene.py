@@ -58,6 +58,8 @@ class Scene:
     grid_list: Optional[np.ndarray] = None   # [n] u32
     name: str = ""
     meta: dict = field(default_factory=dict)
+    # host only (never sent to the device): index of the front-end Mesh each triangle came from (frontend.scene_from_meshes)
+    tri_mesh: Optional[np.ndarray] = None   # [T] i32
 
     @property
     def pixels(self) -> int:
