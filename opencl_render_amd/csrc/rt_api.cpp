@@ -101,19 +101,14 @@ struct Tuning {
     uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
     uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
 };
+// Read at the entry points only (scene create, RaytraceAll, the two public device builders): a build works from one snapshot.
 Tuning g_tune;
 std::mutex g_tuneMutex;
 Tuning tuning() { std::lock_guard<std::mutex> lock(g_tuneMutex); return g_tune; }
 
 } // namespace
 
-// The device builders' test hooks (rt_build_shared.h).
-void rtbuild::device_build_tuning(uint64_t *keyCap, uint64_t *listLimit)
-{
-    const Tuning t = tuning();
-    *keyCap = t.buildKeyCap;
-    *listLimit = t.buildListLimit;
-}
+rtbuild::DeviceBuildTuning rtbuild::device_build_tuning() { const Tuning t = tuning(); return { t.buildKeyCap, t.buildListLimit }; }
 
 namespace {
 
@@ -164,10 +159,10 @@ struct Stager {
         }
     };
     static Pool &pool() { static Pool *p = new Pool(); return *p; } // (never destroyed: buffers may come back during process exit)
-    int init(hipStream_t st)
+    int init(hipStream_t st, const Tuning &T)
     {
         stream = st;
-        size = (size_t)std::min<uint32_t>(std::max<uint32_t>(tuning().stageMb, 1u), 4096u) << 20;
+        size = (size_t)std::min<uint32_t>(std::max<uint32_t>(T.stageMb, 1u), 4096u) << 20;
         for (int i = 0; i < 2; ++i) HIP_OK(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
         return 0;
     }
@@ -778,8 +773,9 @@ int clone_part(rtHipScene *dst, const rtHipScene *src, int part)
     return 0;
 }
 
-// `like`: an instance of the same scene (same inputs) on this or another device whose shared parts are copied instead of built
-int scene_build(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds, cl_uint tileCount, const rtHipScene *like = nullptr)
+// `like`: an instance of the same scene (same inputs) on this or another device whose shared parts are copied instead of built;
+// `tune`: the caller's one snapshot of the tuning values, kept as sc->tune for the scene's later part rebuilds and frames
+int scene_build(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds, cl_uint tileCount, const rtHipScene *like, const Tuning &tune)
 {
     if (!d) return fail("null scene description");
     if (d->width == 0 || d->height == 0) return fail("empty image %ux%u", d->width, d->height);
@@ -788,11 +784,11 @@ int scene_build(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds,
     if ((uint64_t)d->width * d->height > 0xffffffffull) return fail("image too large");
     HIP_OK(hipSetDevice(sc->device));
     HIP_OK(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
-    sc->tune = tuning();
-    sc->pipeline = sc->tune.pipeline == RT_HIP_PIPELINE_MEGAKERNEL ? RT_HIP_PIPELINE_MEGAKERNEL : RT_HIP_PIPELINE_WAVEFRONT;
-    if (sc->stager.init(sc->stream) != 0) return -1;
+    sc->tune = tune;
+    sc->pipeline = tune.pipeline == RT_HIP_PIPELINE_MEGAKERNEL ? RT_HIP_PIPELINE_MEGAKERNEL : RT_HIP_PIPELINE_WAVEFRONT;
+    if (sc->stager.init(sc->stream, tune) != 0) return -1;
     // Tuning::timing: where the time of a scene upload goes (stderr)
-    const bool timing = sc->tune.timing != 0;
+    const bool timing = tune.timing != 0;
     auto tLast = std::chrono::steady_clock::now();
     auto mark = [&](const char *what) {
         if (!timing) return;
@@ -1120,6 +1116,21 @@ int frame_finish(rtHipScene *sc, hipStream_t st, int *redone)
     return 0;
 }
 
+rtHipScene *scene_create(int device, const rtHipSceneDesc *desc, const cl_uint *tileIds, cl_uint tileCount, const rtHipScene *like, const Tuning &tune)
+{
+    g_error.clear();
+    const int n = rtHipDeviceCount();
+    if (n <= 0) { fail("no HIP device available: libraytrace_hip has no CPU fallback"); return nullptr; }
+    if (device < 0 || device >= n) { fail("device %d out of range (%d HIP devices)", device, n); return nullptr; }
+    rtHipScene *sc = new rtHipScene();
+    sc->device = device;
+    if (scene_build(sc, desc, tileIds, tileCount, like, tune) == 0) return sc;
+    const std::string keep = g_error;
+    rtHipSceneDestroy(sc);
+    g_error = keep;
+    return nullptr;
+}
+
 } // namespace
 
 extern "C" {
@@ -1140,19 +1151,7 @@ rtHipScene *rtHipSceneCreate(int device, const rtHipSceneDesc *desc, const cl_ui
 
 rtHipScene *rtHipSceneCreateLike(int device, const rtHipSceneDesc *desc, const cl_uint *tileIds, cl_uint tileCount, const rtHipScene *like)
 {
-    g_error.clear();
-    const int n = rtHipDeviceCount();
-    if (n <= 0) { fail("no HIP device available: libraytrace_hip has no CPU fallback"); return nullptr; }
-    if (device < 0 || device >= n) { fail("device %d out of range (%d HIP devices)", device, n); return nullptr; }
-    rtHipScene *sc = new rtHipScene();
-    sc->device = device;
-    if (scene_build(sc, desc, tileIds, tileCount, like) != 0) {
-        std::string keep = g_error;
-        rtHipSceneDestroy(sc);
-        g_error = keep;
-        return nullptr;
-    }
-    return sc;
+    return scene_create(device, desc, tileIds, tileCount, like, tuning());
 }
 
 void rtHipSceneDestroy(rtHipScene *sc)
@@ -1602,9 +1601,9 @@ int rtHipTune(const char *key, double value)
     std::lock_guard<std::mutex> lock(g_tuneMutex);
     Tuning &T = g_tune;
     const std::string k = key;
-    const uint32_t u = value < 0 ? 0u : (value > 4294967295.0 ? 0xffffffffu : (uint32_t)value);
     if (k == "reset") { T = Tuning(); return 0; }
-    struct { const char *name; uint32_t *field; } table[] = {
+    // every key's field, 32 or 64 bits wide, and the most it takes: negative values become 0, larger ones saturate at `most`
+    struct Key { const char *name; uint32_t *f32; uint64_t *f64 = nullptr; double most = 4294967295.0; } table[] = {
         { "stage_mb", &T.stageMb }, { "extra_factor", &T.extraFactor }, { "groups", &T.groups }, { "lookahead", &T.lookAhead },
         { "seg0", &T.segLen[0] }, { "seg1", &T.segLen[1] }, { "seg2", &T.segLen[2] }, { "seg3", &T.segLen[3] }, { "seg4", &T.segLen[4] },
         { "seg_rays0", &T.segRays[0] }, { "seg_rays1", &T.segRays[1] }, { "seg_rays2", &T.segRays[2] }, { "seg_rays3", &T.segRays[3] },
@@ -1612,12 +1611,14 @@ int rtHipTune(const char *key, double value)
         { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
         { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow },
+        { "state_mb", nullptr, &T.stateMb, HUGE_VAL }, { "build_key_cap", nullptr, &T.buildKeyCap, 1e18 }, { "build_list_limit", nullptr, &T.buildListLimit },
     };
-    if (k == "state_mb") { T.stateMb = (uint64_t)(value < 0 ? 0 : value); return 0; }
-    if (k == "build_key_cap") { T.buildKeyCap = (uint64_t)(value < 0 ? 0 : std::min(value, 1e18)); return 0; }
-    if (k == "build_list_limit") { T.buildListLimit = u; return 0; }
-    for (auto &e : table)
-        if (k == e.name) { *e.field = u; return 0; }
+    for (const Key &e : table) {
+        if (k != e.name) continue;
+        const double v = value < 0 ? 0 : std::min(value, e.most);
+        if (e.f64) *e.f64 = (uint64_t)v; else *e.f32 = (uint32_t)v;
+        return 0;
+    }
     return fail("rtHipTune: unknown key '%s'", key);
 }
 
@@ -1793,7 +1794,7 @@ cl_bool RaytraceAll(cl_uint computationType, cl_uint2 cameraImageDimension, cl_f
         bool ok = true;
         const rtHipScene *root = g > 0 ? C.scenes[0] : nullptr;
         if (!C.scenes[g]) {
-            C.scenes[g] = rtHipSceneCreateLike((first + g) % n, &d, C.tiles[g].empty() ? nullptr : C.tiles[g].data(), (cl_uint)C.tiles[g].size(), root);
+            C.scenes[g] = scene_create((first + g) % n, &d, C.tiles[g].empty() ? nullptr : C.tiles[g].data(), (cl_uint)C.tiles[g].size(), root, tune);
             ok = C.scenes[g] != nullptr;
         } else {
             rtHipScene *sc = C.scenes[g];

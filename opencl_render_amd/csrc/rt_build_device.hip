@@ -206,8 +206,7 @@ extern "C" int rtHipBuildCameraListDevice(int device, cl_uint W, cl_uint H, cons
     if (!outStart || !outEnd || !outList || !outListSize || W == 0 || H == 0) return -1;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || device < 0 || device >= nDev) return -5; // no CPU fallback: use rtHipBuildCameraList for that
-    uint64_t tunedKeyCap = 0, listLimit = 0;
-    rtbuild::device_build_tuning(&tunedKeyCap, &listLimit);
+    const uint64_t listLimit = rtbuild::device_build_tuning().listLimit;
     BUILD_OK(hipSetDevice(device));
     const uint64_t P = (uint64_t)W * H;
     const uint32_t T = triangleCount;
@@ -557,8 +556,7 @@ extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uin
     if (!outBoxMin || !outStart || !outList || !outListSize) return -1;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || device < 0 || device >= nDev) return -5; // no CPU fallback: rtHipBuildSceneGrid is the host builder
-    uint64_t tunedKeyCap = 0, listLimit = 0;
-    rtbuild::device_build_tuning(&tunedKeyCap, &listLimit);
+    const auto [tunedKeyCap, listLimit] = rtbuild::device_build_tuning();
     BUILD_OK(hipSetDevice(device));
     const uint32_t V = vertexCount, T = triangleCount;
     for (uint32_t t = 0; t < T; ++t)

@@ -168,9 +168,10 @@ RT_HD inline void box_address(const float (*bm)[4], F3 p, int cell[3])
     cell[0] = cx; cell[1] = cy; cell[2] = cz;
 }
 
-// Test hooks of the device builders, set through rtHipTune (rt_api.cpp): the first key capacity of the grid build (0 = its
-// default) and the most entries a device-built list may hold (2^32 - 1 unless a test lowers it).  Host code only.
-void device_build_tuning(uint64_t *keyCap, uint64_t *listLimit);
+// Test hooks of the device builders, set through rtHipTune (rt_api.cpp): the grid build's first key capacity (0 = its default) and the
+// most entries a device-built list may hold (2^32 - 1 unless a test lowers it).  Host code, read once at entry by the two public builders.
+struct DeviceBuildTuning { uint64_t keyCap, listLimit; };
+DeviceBuildTuning device_build_tuning();
 
 } // namespace rtbuild
 

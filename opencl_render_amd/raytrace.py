@@ -186,6 +186,8 @@ _ENV_KEYS = {
     "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow",
     "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit",
 }
+# comma-separated lists: RT_WF_SEG=a,b,.. sets seg0, seg1, .. (at most 5 values), RT_WF_SEG_RAYS sets seg_rays0.. (at most 4)
+_ENV_LISTS = (("RT_WF_SEG", "seg", 5), ("RT_WF_SEG_RAYS", "seg_rays", 4))
 
 
 def tune(key: str, value: float) -> None:
@@ -199,7 +201,7 @@ def apply_env_tuning() -> None:
     for var, key in _ENV_KEYS.items():
         if var in os.environ:
             tune(key, float(os.environ[var]))
-    for var, key, n in (("RT_WF_SEG", "seg", 5), ("RT_WF_SEG_RAYS", "seg_rays", 4)):
+    for var, key, n in _ENV_LISTS:
         for i, v in enumerate([x for x in os.environ.get(var, "").split(",") if x][:n]):
             tune(f"{key}{i}", float(v))
     if os.environ.get("RT_WF_PLAN_GRID") == "tiny":
