@@ -187,14 +187,18 @@ void rt_oracle_box_address(int axes_div, const float *box_min, const float p[3],
     box_address(axes_div, box_min, ld3(p), out);
 }
 
-/* raytrace_opencl.c:265-322: six sequential face clamps along the ray; early 'false' returns */
-static int bind_in_cube(v3 *p, v3 d, v3 lo, v3 hi)
+/* raytrace_opencl.c:265-322: six sequential face clamps along the ray; early 'false' returns.  zero_outside (may be NULL) counts the
+ * faces the point lies beyond while the direction's component on that axis is +-0: there the '<= 0' / '0 <=' tests decide alone. */
+static int bind_in_cube(v3 *p, v3 d, v3 lo, v3 hi, uint64_t *zero_outside)
 {
     float t;
+    if (zero_outside) *zero_outside += (uint64_t)((p->x < lo.x || hi.x < p->x) && d.x == 0.f);
     if (p->x < lo.x) { if (d.x <= 0) return 0; t = (lo.x - p->x) / d.x; p->x += t * d.x; p->y += t * d.y; p->z += t * d.z; }
     if (hi.x < p->x) { if (0 <= d.x) return 0; t = (hi.x - p->x) / d.x; p->x += t * d.x; p->y += t * d.y; p->z += t * d.z; }
+    if (zero_outside) *zero_outside += (uint64_t)((p->y < lo.y || hi.y < p->y) && d.y == 0.f);
     if (p->y < lo.y) { if (d.y <= 0) return 0; t = (lo.y - p->y) / d.y; p->x += t * d.x; p->y += t * d.y; p->z += t * d.z; }
     if (hi.y < p->y) { if (0 <= d.y) return 0; t = (hi.y - p->y) / d.y; p->x += t * d.x; p->y += t * d.y; p->z += t * d.z; }
+    if (zero_outside) *zero_outside += (uint64_t)((p->z < lo.z || hi.z < p->z) && d.z == 0.f);
     if (p->z < lo.z) { if (d.z <= 0) return 0; t = (lo.z - p->z) / d.z; p->x += t * d.x; p->y += t * d.y; p->z += t * d.z; }
     if (hi.z < p->z) { if (0 <= d.z) return 0; t = (hi.z - p->z) / d.z; p->x += t * d.x; p->y += t * d.y; p->z += t * d.z; }
     return 1;
@@ -203,7 +207,7 @@ static int bind_in_cube(v3 *p, v3 d, v3 lo, v3 hi)
 int rt_oracle_bind_in_cube(float p[3], const float d[3], const float lo[3], const float hi[3])
 {
     v3 q = ld3(p);
-    int ok = bind_in_cube(&q, ld3(d), ld3(lo), ld3(hi));
+    int ok = bind_in_cube(&q, ld3(d), ld3(lo), ld3(hi), 0);
     p[0] = q.x; p[1] = q.y; p[2] = q.z;
     return ok;
 }
@@ -239,9 +243,44 @@ static inline v3 tri_vertex(const rt_oracle_scene *sc, uint32_t tri, int corner)
     return ld3(sc->vertex + 4 * (ptrdiff_t)sc->tri_index[4 * (ptrdiff_t)tri + corner]);
 }
 
+/* ---- walk census (rt_oracle_render_census): only reads what the walk computes ---------------------- */
+
+/* 1 if v equals one of the ascending planes bm[0..div] of axis a (binary search) */
+static int on_plane(const float *bm, int div, int a, float v)
+{
+    int lo = 0, hi = div;
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (bm[4 * mid + a] < v) lo = mid + 1; else hi = mid;
+    }
+    return bm[4 * lo + a] == v;
+}
+
+static void census_start(rt_oracle_census *cs, const float *bm, int div, v3 o, v3 d, const int cell[3], float tmax)
+{
+    const float oc[3] = { o.x, o.y, o.z }, dc[3] = { d.x, d.y, d.z };
+    int a;
+    cs->grid_rays++;
+    cs->finite_rays += (uint64_t)(tmax < INFINITY);
+    for (a = 0; a < 3; ++a) {
+        const float m = (float)fabs((double)dc[a]);
+        /* the head the first step compares (:383-385), formed as the walk forms it */
+        const float head = (bm[4 * (cell[a] + (0 <= dc[a])) + a] - oc[a]) / dc[a];
+        if (dc[a] == 0.f) { if (signbit(dc[a])) cs->dir_neg_zero++; else cs->dir_pos_zero++; }
+        else if (!(m >= 0x1p-40f && m <= 0x1p40f)) cs->dir_untame++;
+        cs->dir_subnormal += (uint64_t)(dc[a] != 0.f && m < 0x1p-126f);
+        cs->origin_on_plane += (uint64_t)on_plane(bm, div, a, oc[a]);
+        if (head != head) cs->head_nan++;
+        else if (head == -INFINITY) cs->head_neg_inf++;
+        else if (head == INFINITY) cs->head_pos_inf++;
+    }
+    cs->zero_width_start += (uint64_t)(bm[4 * (cell[0] + 1) + 0] == bm[4 * cell[0] + 0] || bm[4 * (cell[1] + 1) + 1] == bm[4 * cell[1] + 1] ||
+                                       bm[4 * (cell[2] + 1) + 2] == bm[4 * cell[2] + 2]);
+}
+
 /* ---- secondary rays: 3-D DDA over the non-uniform grid (raytrace_opencl.c:324-401) ------------------ */
 static uint32_t grid_trace(const rt_oracle_scene *sc, v3 o, v3 d, float tmin, float tmax, uint32_t excluded,
-                           float *t_out, float *ab_out, float *ac_out, rt_oracle_stats *st)
+                           float *t_out, float *ab_out, float *ac_out, rt_oracle_stats *st, rt_oracle_census *cs)
 {
     const int div = sc->axes_div;
     const float *bm = sc->box_min;
@@ -249,14 +288,15 @@ static uint32_t grid_trace(const rt_oracle_scene *sc, v3 o, v3 d, float tmin, fl
     uint32_t best = 0xffffffffu;
     int cell[3], last[3] = { -1, -1, -1 };
     v3 from = along(o, tmin, d);
-    bind_in_cube(&from, d, lo, hi); /* result ignored (:354) */
+    bind_in_cube(&from, d, lo, hi, cs ? &cs->bind_zero_outside : 0); /* result ignored (:354) */
     box_address(div, bm, from, cell);
     if (tmax < INFINITY) {
         v3 to = along(o, tmax, d);
-        bind_in_cube(&to, d, lo, hi); /* result ignored (:360) */
+        bind_in_cube(&to, d, lo, hi, cs ? &cs->bind_zero_outside : 0); /* result ignored (:360) */
         box_address(div, bm, to, last);
     }
     if (st) st->grid_rays++;
+    if (cs) census_start(cs, bm, div, o, d, cell, tmax);
     for (;;) {
         uint32_t id = (uint32_t)(cell[0] + div * cell[1] + div * div * cell[2]);
         uint32_t i;
@@ -276,21 +316,27 @@ static uint32_t grid_trace(const rt_oracle_scene *sc, v3 o, v3 d, float tmin, fl
             }
         }
         /* stop at the first cell that produced any hit, or at the end cell (:380-381) */
-        if (best != 0xffffffffu || (cell[0] == last[0] && cell[1] == last[1] && cell[2] == last[2])) break;
+        if (best != 0xffffffffu || (cell[0] == last[0] && cell[1] == last[1] && cell[2] == last[2])) {
+            if (cs) { if (best != 0xffffffffu) cs->end_hit++; else cs->end_last_cell++; }
+            break;
+        }
         {
             /* distances measured from the ray origin, not from the clamped start (:383-385) */
             float dx = (bm[4 * (cell[0] + (0 <= d.x)) + 0] - o.x) / d.x;
             float dy = (bm[4 * (cell[1] + (0 <= d.y)) + 1] - o.y) / d.y;
             float dz = (bm[4 * (cell[2] + (0 <= d.z)) + 2] - o.z) / d.z;
             if ((dx < dy) & (dx < dz)) {
+                if (cs) cs->zero_axis_steps += (uint64_t)(d.x == 0.f);
                 cell[0] += (0 <= d.x) ? 1 : -1;
-                if (cell[0] < 0 || div <= cell[0]) break;
+                if (cell[0] < 0 || div <= cell[0]) { if (cs) cs->end_left_grid++; break; }
             } else if (dy < dz) {
+                if (cs) cs->zero_axis_steps += (uint64_t)(d.y == 0.f);
                 cell[1] += (0 <= d.y) ? 1 : -1;
-                if (cell[1] < 0 || div <= cell[1]) break;
+                if (cell[1] < 0 || div <= cell[1]) { if (cs) cs->end_left_grid++; break; }
             } else {
+                if (cs) cs->zero_axis_steps += (uint64_t)(d.z == 0.f);
                 cell[2] += (0 <= d.z) ? 1 : -1;
-                if (cell[2] < 0 || div <= cell[2]) break;
+                if (cell[2] < 0 || div <= cell[2]) { if (cs) cs->end_left_grid++; break; }
             }
         }
     }
@@ -300,7 +346,7 @@ static uint32_t grid_trace(const rt_oracle_scene *sc, v3 o, v3 d, float tmin, fl
 uint32_t rt_oracle_grid_trace(const rt_oracle_scene *sc, const float o[3], const float d[3], float tmin, float tmax,
                               uint32_t excluded, float *t, float *ab_l, float *ac_l)
 {
-    return grid_trace(sc, ld3(o), ld3(d), tmin, tmax, excluded, t, ab_l, ac_l, 0);
+    return grid_trace(sc, ld3(o), ld3(d), tmin, tmax, excluded, t, ab_l, ac_l, 0, 0);
 }
 
 /* ---- shading normal: Phong interpolation + bump (raytrace_opencl.c:195-263) ------------------------ */
@@ -359,7 +405,7 @@ typedef struct {
 #define MAX2(a, b) (((a) > (b)) ? (a) : (b)) /* raytrace.h:30 (NaN in a falls through to b) */
 
 /* One sample of one pixel: raytrace_opencl.c:470-741, seeded as the C path does (:477-482). */
-static void trace_sample(const rt_oracle_scene *sc, uint32_t pixel, uint32_t sample_id, rt_oracle_stats *st)
+static void trace_sample(const rt_oracle_scene *sc, uint32_t pixel, uint32_t sample_id, rt_oracle_stats *st, rt_oracle_census *cs)
 {
     queued_ray ring[RING];
     int head = 0, tail;
@@ -406,7 +452,7 @@ static void trace_sample(const rt_oracle_scene *sc, uint32_t pixel, uint32_t sam
                 }
             }
         } else {
-            hit_tri = grid_trace(sc, cur.o, cur.d, cur.tmin, cur.tmax, cur.excluded, &hit_t, &hit_ab, &hit_ac, st);
+            hit_tri = grid_trace(sc, cur.o, cur.d, cur.tmin, cur.tmax, cur.excluded, &hit_t, &hit_ab, &hit_ac, st, cs);
         }
         if (hit_tri == 0xffffffffu) continue;
 
@@ -470,7 +516,7 @@ static void trace_sample(const rt_oracle_scene *sc, uint32_t pixel, uint32_t sam
                 if (lmin < lmax) { /* shadow ray through transparent occluders (:608-627) */
                     for (;;) {
                         float t, l1, l2;
-                        uint32_t occ = grid_trace(sc, where, to_light, lmin, lmax, hit_tri, &t, &l1, &l2, st);
+                        uint32_t occ = grid_trace(sc, where, to_light, lmin, lmax, hit_tri, &t, &l1, &l2, st, cs);
                         v3 tr = { 0.f, 0.f, 0.f };
                         int om;
                         if (occ == 0xffffffffu) break;
@@ -594,26 +640,52 @@ static void add_stats(rt_oracle_stats *dst, const rt_oracle_stats *src)
     dst->texel_fetches += src->texel_fetches;
 }
 
+static void add_census(rt_oracle_census *dst, const rt_oracle_census *src)
+{
+    uint64_t *d = (uint64_t *)dst;
+    const uint64_t *s = (const uint64_t *)src;
+    size_t i;
+    for (i = 0; i < sizeof *dst / sizeof(uint64_t); ++i) d[i] += s[i];
+}
+
 /* raytrace.c:612-653: for each pixel, samples 1..S in order */
-int rt_oracle_render(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count, int threads, rt_oracle_stats *stats)
+static void render_range(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count, int threads, rt_oracle_stats *stats,
+                         rt_oracle_census *census)
 {
     const int64_t n = (int64_t)pixel_count;
     if (stats) memset(stats, 0, sizeof *stats);
+    if (census) memset(census, 0, sizeof *census);
     if (threads < 1) threads = 1;
 #pragma omp parallel num_threads(threads)
     {
         rt_oracle_stats local;
+        rt_oracle_census local_census;
         int64_t i;
         memset(&local, 0, sizeof local);
+        memset(&local_census, 0, sizeof local_census);
 #pragma omp for schedule(dynamic, 256)
         for (i = 0; i < n; ++i) {
             uint32_t pixel = first_pixel + (uint32_t)i, s;
-            for (s = 1; s <= sc->sample_count; ++s) trace_sample(sc, pixel, s, stats ? &local : 0);
+            for (s = 1; s <= sc->sample_count; ++s) trace_sample(sc, pixel, s, stats ? &local : 0, census ? &local_census : 0);
         }
-        if (stats) {
+        if (stats || census) {
 #pragma omp critical
-            add_stats(stats, &local);
+            {
+                if (stats) add_stats(stats, &local);
+                if (census) add_census(census, &local_census);
+            }
         }
     }
+}
+
+int rt_oracle_render(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count, int threads, rt_oracle_stats *stats)
+{
+    render_range(sc, first_pixel, pixel_count, threads, stats, 0);
+    return 1;
+}
+
+int rt_oracle_render_census(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count, int threads, rt_oracle_census *census)
+{
+    render_range(sc, first_pixel, pixel_count, threads, 0, census);
     return 1;
 }

@@ -66,11 +66,35 @@ typedef struct rt_oracle_stats {
     uint64_t texel_fetches;
 } rt_oracle_stats;
 
+/* What the grid walks of a frame met (rt_oracle_render_census): the inputs on which a DDA goes wrong.  Per grid ray, unless noted. */
+typedef struct rt_oracle_census {
+    uint64_t grid_rays;         /* calls of the grid traversal */
+    uint64_t finite_rays;       /* ... with tmax < inf (positional lights' shadow rays) */
+    uint64_t dir_pos_zero;      /* direction components equal to +0 */
+    uint64_t dir_neg_zero;      /* direction components equal to -0 */
+    uint64_t dir_untame;        /* non-zero direction components outside [2^-40, 2^40] (no fast quotient) */
+    uint64_t dir_subnormal;     /* non-zero direction components below 2^-126 */
+    uint64_t origin_on_plane;   /* origin components equal to a split plane of their axis */
+    uint64_t head_nan;          /* initial heads (plane - o) / d, per component, that are NaN */
+    uint64_t head_neg_inf;      /* ... -inf */
+    uint64_t head_pos_inf;      /* ... +inf */
+    uint64_t zero_axis_steps;   /* steps along an axis whose direction component is +-0 */
+    uint64_t end_left_grid;     /* walks that end by leaving the grid */
+    uint64_t end_last_cell;     /* ... at the end cell without a hit */
+    uint64_t end_hit;           /* ... at a cell with a hit */
+    uint64_t zero_width_start;  /* start cells of zero width on some axis */
+    uint64_t bind_zero_outside; /* BindInCube faces the start or end point lies beyond while that axis' component is +-0 */
+} rt_oracle_census;
+
 /* Renders pixels [first_pixel, first_pixel+pixel_count) with all samples, in pixel order
  * (raytrace.c:612-653).  threads<=1: the reference's single-thread order.  threads>1 splits the pixel
  * range over OpenMP threads (pixels are independent, so the planes are identical).  stats may be NULL. */
 int rt_oracle_render(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count,
                      int threads, rt_oracle_stats *stats);
+
+/* rt_oracle_render with the walk census instead of the work counters: the same planes, the counting only reads. */
+int rt_oracle_render_census(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count,
+                            int threads, rt_oracle_census *census);
 
 /* Function-level entry points for known-answer tests (same maths as the reference helpers). */
 float rt_oracle_randf(uint64_t *state, float lo, float hi);                     /* :12-23  */

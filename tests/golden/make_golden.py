@@ -17,6 +17,8 @@ scene inputs in the ABI layouts and the expected u16 planes / function results.
                      (inputs not stored: the test regenerates them from the seed)
   ref_class_scenes.npz  planes R,G,B ("<name>_r", "_g", "_b") of every opaque-diffuse scenario in scenarios.CLASS (inputs not
                      stored: the tests regenerate them from the code and R.build_lists); written byte for byte the same on every run
+  ref_axis_scenes.npz   planes R,G,B ("<name>_r", "_g", "_b") of every grid-walk edge scenario in scenarios.AXIS (inputs not stored,
+                     as for ref_class_scenes.npz); written byte for byte the same on every run
 """
 import ctypes as C
 import io
@@ -174,11 +176,20 @@ def make_class(path):
     save_npz_stable(path, planes)
 
 
+def make_axis(path):
+    planes = {}
+    for f in scenarios.AXIS:
+        sc = f()  # (builds its lists and asserts its edge)
+        for c, p in zip("rgb", O.ref_render(sc)):
+            planes[f"{f.__name__}_{c}"] = p
+    save_npz_stable(path, planes)
+
+
 def main():
     if not O.have_ref():
         sys.exit("oracle/_ref/libref_kernel.so missing: run `make -C oracle` where /root/reference exists")
-    only = set(sys.argv[1:])  # optional: names of the fixtures to (re)write, "kat" / "fresh" / "class" for kat.npz / ref_fresh_scenes.npz /
-    # ref_class_scenes.npz; default = everything
+    only = set(sys.argv[1:])  # optional: names of the fixtures to (re)write, "kat" / "fresh" / "class" / "axis" for kat.npz /
+    # ref_fresh_scenes.npz / ref_class_scenes.npz / ref_axis_scenes.npz; default = everything
     for f in scenarios.ALL:
         if only and f.__name__ not in only:
             continue
@@ -197,6 +208,9 @@ def main():
     if not only or "class" in only:
         make_class(os.path.join(HERE, "ref_class_scenes.npz"))
         print("ref_class_scenes.npz written")
+    if not only or "axis" in only:
+        make_axis(os.path.join(HERE, "ref_axis_scenes.npz"))
+        print("ref_axis_scenes.npz written")
 
 
 if __name__ == "__main__":

@@ -45,6 +45,18 @@ class OracleStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+CENSUS_FIELDS = ("grid_rays", "finite_rays", "dir_pos_zero", "dir_neg_zero", "dir_untame", "dir_subnormal", "origin_on_plane", "head_nan",
+                 "head_neg_inf", "head_pos_inf", "zero_axis_steps", "end_left_grid", "end_last_cell", "end_hit", "zero_width_start",
+                 "bind_zero_outside")
+
+
+class OracleCensus(C.Structure):  # rt_oracle_census (oracle/rt_oracle.h)
+    _fields_ = [(n, C.c_uint64) for n in CENSUS_FIELDS]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in CENSUS_FIELDS}
+
+
 class Float3(C.Structure):
     _fields_ = [("s", C.c_float * 4)]
 
@@ -64,6 +76,7 @@ def oracle() -> C.CDLL:
             build_oracle()
         L = C.CDLL(ORACLE_SO)
         L.rt_oracle_render.argtypes = [C.POINTER(OracleScene), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(OracleStats)]
+        L.rt_oracle_render_census.argtypes = [C.POINTER(OracleScene), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(OracleCensus)]
         L.rt_oracle_randf.restype = C.c_float
         L.rt_oracle_randf.argtypes = [C.POINTER(C.c_uint64), C.c_float, C.c_float]
         L.rt_oracle_sphere_point.argtypes = [C.POINTER(C.c_uint64), C.c_float, C.POINTER(C.c_float)]
@@ -153,6 +166,15 @@ def oracle_render(sc, threads: int = 1, with_stats: bool = False, first_pixel: i
     oracle().rt_oracle_render(C.byref(o), first_pixel, n, threads, C.byref(st) if with_stats else None)
     out = [p.reshape(sc.height, sc.width) for p in planes]
     return (out, st.as_dict()) if with_stats else out
+
+
+def oracle_census(sc, threads: int = 1):
+    """The planes and the walk census of the C restatement over the whole scene (rt_oracle_render_census)."""
+    planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
+    o = oracle_scene(sc, planes)
+    cs = OracleCensus()
+    oracle().rt_oracle_render_census(C.byref(o), 0, sc.pixels, threads, C.byref(cs))
+    return [p.reshape(sc.height, sc.width) for p in planes], cs.as_dict()
 
 
 def ref_render(sc, first_pixel: int = 0, pixel_count: int = None):

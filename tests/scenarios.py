@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from opencl_render_amd import scene as S
+from opencl_render_amd import raytrace as R, scene as S
 
 
 def _tex(seed, side, lo=0, hi=256):
@@ -297,3 +297,258 @@ def by_name(name):
         if f.__name__ == name:
             return f
     raise KeyError(name)
+
+
+# ---- AXIS: grid walks with zero and extreme direction components --------------------------------------------------------------
+# Mesh rooms of axis-aligned quads at exactly representable coordinates (many vertices share a coordinate: repeated split planes,
+# zero-width cells, hits exactly on a plane), lit by lights along or next to an axis with radius 0.  A directional light's shadow
+# direction is GetSpherePoint(r = 0) - dir (:589-606): every zero component of dir comes out +0 or -0 by the sign of that hit's
+# random draw, so the walk meets 0 <= -0.0, heads of -inf and NaN (0/0 on a plane) and steps along a zero axis (:383-395).
+# The reference's planes are stored in tests/golden/ref_axis_scenes.npz; tests/test_walk_edges.py checks with the oracle's walk
+# census (rt_oracle_render_census) that every scene still meets the edge it is named for.
+
+from opencl_render_amd import demo as _demo, frontend as _F  # noqa: E402  (the AXIS scenes are mesh scenes)
+
+TAME_LO, TAME_HI = 2.0 ** -60, 2.0 ** 39  # rt_api.cpp: a plane coordinate is tame when it is 0 or in [2^-60, 2^39]
+
+
+def planes_tame(box_min):
+    m = np.abs(np.asarray(box_min, np.float32)[:, :3])
+    return bool(np.all((m == 0) | ((m >= np.float32(TAME_LO)) & (m <= np.float32(TAME_HI)))))
+
+
+def repeated_planes(box_min):
+    """Split planes equal to the one before them, over the three axes (each is a cell of zero width)."""
+    b = np.asarray(box_min, np.float32)[:, :3]
+    return int((b[1:] == b[:-1]).sum())
+
+
+def _panel(axis, value, lo, hi, step, material):
+    """An axis-aligned rectangle at coordinate `value` of `axis`, spanning lo..hi (the other two axes in order) in square quads of
+    side `step`: every vertex at an exact multiple of step."""
+    u = np.arange(lo[0], hi[0] + step / 2, step, dtype=np.float64)
+    v = np.arange(lo[1], hi[1] + step / 2, step, dtype=np.float64)
+    others = [a for a in range(3) if a != axis]
+    pts = np.zeros((len(v), len(u), 3))
+    pts[..., axis] = value
+    pts[..., others[0]] = u[None, :]
+    pts[..., others[1]] = v[:, None]
+    nu = len(u)
+    quads = [[j * nu + i, j * nu + i + 1, (j + 1) * nu + i + 1, (j + 1) * nu + i] for j in range(len(v) - 1) for i in range(nu - 1)]
+    quads = np.array(quads, np.int32)
+    uv = np.tile(np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32), (len(quads), 1, 1))
+    return _F.Mesh(points=pts.reshape(-1, 3).astype(np.float32), polygons=quads, corner_uv=uv,
+                   polygon_material=np.full(len(quads), material, np.int32))
+
+
+ROOM_LO, ROOM_HI = (-2.0, 0.0, 0.5), (2.0, 2.5, 5.0)
+
+
+def _room_meshes(floor=0, walls=0, ceiling=False, props=1, step=0.25):
+    """Floor, back wall, left and right walls (and a ceiling) of the box ROOM_LO..ROOM_HI, open towards the camera, plus two boxes and
+    a pyramid standing on the floor (material `props`)."""
+    (x0, y0, z0), (x1, y1, z1) = ROOM_LO, ROOM_HI
+    m = [_panel(1, y0, (x0, z0), (x1, z1), step, floor), _panel(2, z1, (x0, y0), (x1, y1), 2 * step, walls),
+         _panel(0, x0, (y0, z0), (y1, z1), 2 * step, walls), _panel(0, x1, (y0, z0), (y1, z1), 2 * step, walls)]
+    if ceiling:
+        m.append(_panel(1, y1, (x0, z0), (x1, z1), 4 * step, walls))
+    m += [_demo.quad_box((-1.25, 0.0, 2.0), (-0.5, 0.75, 2.75), props), _demo.quad_box((0.5, 0.0, 3.0), (1.25, 1.5, 3.5), props),
+          _demo.pyramid([(0.0, 0.0, 1.5), (0.5, 0.0, 1.5), (0.5, 0.0, 2.0), (0.0, 0.0, 2.0)], (0.25, 0.5, 1.75), props)]
+    return m
+
+
+def _axis_scene(name, lights, width=96, height=72, samples=2, materials=None, meshes=None, scale=1.0, extra=None):
+    """A room scene through the front-end, then the lights packed as given (radius and direction bits untouched: rtHipLightFill would
+    normalise the direction and set the radius to 0.52) and the host builders' lists."""
+    meshes = _room_meshes() if meshes is None else meshes
+    if scale != 1.0:
+        meshes = [_F.Mesh(points=(np.asarray(mm.points, np.float64) * scale).astype(np.float32), polygons=mm.polygons,
+                          corner_uv=mm.corner_uv, polygon_material=mm.polygon_material) for mm in meshes]
+    meshes = meshes + (extra or [])
+    mats = materials or [dict(rgb=(0.8, 0.8, 0.75)), dict(rgb=(0.9, 0.5, 0.3))]
+    sc = _F.scene_from_meshes(meshes, mats, [], position=(0.25 * scale, 1.25 * scale, -2.0 * scale), look_at=(0.0, 0.75 * scale, 3.0 * scale),
+                              up=(0, 1, 0), fov=np.radians(60.0), width=width, height=height, samples=samples, name=name)
+    sc.light_type, sc.light_pos, sc.light_dir, sc.light_col, sc.light_radius, sc.light_half_att = S.pack_lights(lights)
+    R.build_lists(sc)
+    return sc
+
+
+def _check(sc, tame=True, min_repeated=100):
+    assert planes_tame(sc.box_min) == tame, f"{sc.name}: planes tame = {planes_tame(sc.box_min)}"
+    assert repeated_planes(sc.box_min) >= min_repeated, f"{sc.name}: {repeated_planes(sc.box_min)} repeated planes"
+    return sc
+
+
+def _sun(t, d, col=0.3, radius=0.0):
+    return dict(type=t, dir=d, col=(col, col, col), radius=radius)
+
+
+AXES = [(1.0, 0.0, 0.0), (-1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, -1.0, 0.0), (0.0, 0.0, 1.0), (0.0, 0.0, -1.0)]
+
+
+def _axis_suns(t):
+    def make():
+        sc = _check(_axis_scene(f"axis_suns_type_{t}", [_sun(t, d, 0.18) for d in AXES]))
+        zeros = sc.light_dir[:, :3] == 0
+        assert zeros.sum() == 12 and not np.signbit(sc.light_dir[:, :3][zeros]).any() and (sc.light_radius == 0).all()
+        return sc
+    make.__name__ = f"axis_suns_type_{t}"
+    make.__doc__ = f"Six radius-0 lights of type {t}, along +x, -x, +y, -y, +z and -z: every shadow direction has two +-0 components."
+    return make
+
+
+def axis_sun_negative_zero_dir():
+    """A sun straight overhead written (-0.0, -1, -0.0): (+-0) - (-0) = +0, so every zero of its shadow direction is +0 (a branch the
+    +0 spelling does not take), beside a sun along +x written (1, +0, +0) and one written (1, -0.0, -0.0)."""
+    sc = _check(_axis_scene("axis_sun_negative_zero_dir", [_sun(3, (-0.0, -1.0, -0.0), 0.4), _sun(4, (1.0, 0.0, 0.0), 0.3),
+                                                            _sun(4, (1.0, -0.0, -0.0), 0.3)]))
+    assert np.signbit(sc.light_dir[0, [0, 2]]).all() and not np.signbit(sc.light_dir[1, 1:3]).any() and np.signbit(sc.light_dir[2, 1:3]).all()
+    return sc
+
+
+def axis_planes_fine():
+    """Floor and walls in quads of 1/8: hundreds of repeated planes, hits that land exactly on them (0/0 heads), a ceiling, lit by a
+    sun along -y (blocked by the ceiling: the walks end at a hit) and a sun along -z through the open front."""
+    sc = _axis_scene("axis_planes_fine", [_sun(4, (0.0, -1.0, 0.0), 0.4), _sun(3, (0.0, 0.0, 1.0), 0.4)],
+                     meshes=_room_meshes(ceiling=True, step=0.125))
+    return _check(sc, min_repeated=400)
+
+
+NEAR_AXIS = (2.0 ** -40, 1e-13, 1e-40, 2.0 ** -149)
+
+
+def axis_near_axis_lights():
+    """Suns whose directions have one component of 2^-40 (the fast quotient's bound), 1e-13, 1e-40 (subnormal) and 2^-149 (the smallest
+    subnormal) next to an axis: finite, non-zero, but not tame, so no wave takes the short quotient."""
+    lights = [_sun(3, (e, -1.0, 0.0), 0.2) for e in NEAR_AXIS] + [_sun(4, (0.0, -e, 1.0), 0.2) for e in NEAR_AXIS[::-1]]
+    sc = _check(_axis_scene("axis_near_axis_lights", lights))
+    assert sc.light_dir[3, 0] == np.float32(2.0 ** -149) and sc.light_dir[2, 0] < np.finfo(np.float32).tiny
+    return sc
+
+
+def axis_near_axis_mixed():
+    """The near-axis suns beside ordinary lights in the same frame (tame and non-tame shadow rays share waves), 200x150: more than one
+    128x128 tile."""
+    lights = [_sun(3, (0.3, -0.8, 0.5), 0.3, radius=2.0), _sun(4, (2.0 ** -40, -1.0, -1e-40), 0.3), _sun(5, (1e-13, 2.0 ** -149, 1.0), 0.3),
+              dict(type=S.LIGHT_SPOT, pos=(0.3, 2.0, 1.5), col=(0.4, 0.4, 0.4), radius=0.1)]
+    return _check(_axis_scene("axis_near_axis_mixed", lights, width=200, height=150))
+
+
+def _far_triangle(c):
+    return _F.Mesh(points=np.array([[c, 0, c], [c + 1, 0, c], [c, 1, c]], np.float32), polygons=np.array([[0, 1, 2, 2]], np.int32))
+
+
+def _specks(size, at=(0.0, 0.0, 0.0), n=64):
+    """n tiny triangles of side `size` at `at`: their vertex coordinates become split planes."""
+    pts, pol = [], []
+    for k in range(n):
+        o = np.asarray(at, np.float64) + size * k
+        pts += [o, o + (size, 0, 0), o + (0, size, size)]
+        pol.append([3 * k, 3 * k + 1, 3 * k + 2, 3 * k + 2])
+    return [_F.Mesh(points=np.array(pts, np.float32), polygons=np.array(pol, np.int32))]
+
+
+def axis_untame_far():
+    """The room with one far triangle at 1e12 (beyond 2^39): planesTame == 0, every wave divides the long way."""
+    sc = _axis_scene("axis_untame_far", [_sun(4, (0.0, -1.0, 0.0), 0.4), _sun(3, (1.0, 0.0, 0.0), 0.3)], extra=[_far_triangle(1e12)])
+    return _check(sc, tame=False)
+
+
+def axis_untame_tiny():
+    """The room with 64 specks of 2^-70 at the origin (plane coordinates non-zero below 2^-60): planesTame == 0."""
+    sc = _axis_scene("axis_untame_tiny", [_sun(4, (0.0, -1.0, 0.0), 0.4), _sun(6, (0.0, 0.0, 1.0), 0.3)], extra=_specks(2.0 ** -70))
+    return _check(sc, tame=False)
+
+
+def axis_untame_scaled():
+    """The room scaled by 2^30 (its triangle test still far from overflow) with a speck of side 2^-40 at its origin: planes span
+    2^-40 .. 2^32.3 and are not tame."""
+    sc = _axis_scene("axis_untame_scaled", [_sun(4, (0.0, -1.0, 0.0), 0.4), _sun(5, (-1.0, 0.0, 0.0), 0.3)], scale=2.0 ** 30,
+                     extra=_specks(2.0 ** -64))
+    return _check(sc, tame=False)
+
+
+def axis_tame_bounds():
+    """Plane coordinates exactly at the tame bounds: 64 point triangles at (2^-60, 2^-60, 2^-60) and a far triangle at 2^39 (its other
+    corners 2^39 + 1 round back to 2^39): still tame."""
+    sc = _axis_scene("axis_tame_bounds", [_sun(4, (0.0, -1.0, 0.0), 0.4), _sun(3, (0.0, 0.0, -1.0), 0.3)],
+                     extra=_specks(0.0, at=(2.0 ** -60, 2.0 ** -60, 2.0 ** -60)) + [_far_triangle(2.0 ** 39)])
+    m = np.abs(sc.box_min[:, :3])
+    assert m.max() == np.float32(2.0 ** 39) and m[m > 0].min() == np.float32(2.0 ** -60)
+    return _check(sc, tame=True)
+
+
+def axis_point_lights():
+    """Point-type lights (1, 2, 7, 8, 9) of radius 0: on the left wall's plane, at the grid's corner, outside the box along an axis
+    (above, behind the back wall, beside the right wall).  Finite shadow rays whose end point lies on a plane or outside the box meet
+    BindInCube's '<= 0' tests with zero components."""
+    (x0, y0, z0), (x1, y1, z1) = ROOM_LO, ROOM_HI
+    lights = [dict(type=1, pos=(x0, 1.25, 2.5), col=(0.3, 0.3, 0.3), radius=0.0, half_att=3.0),
+              dict(type=2, pos=(x0, y0, z0), col=(0.3, 0.3, 0.3), radius=0.0),
+              dict(type=7, pos=(0.25, 6.0, 2.5), col=(0.3, 0.3, 0.3), radius=0.0),
+              dict(type=8, pos=(0.25, 1.25, 9.0), col=(0.3, 0.3, 0.3), radius=0.0, half_att=5.0),
+              dict(type=9, pos=(7.0, 0.75, 3.0), col=(0.3, 0.3, 0.3), radius=0.0)]
+    return _check(_axis_scene("axis_point_lights", lights))
+
+
+def axis_mirror_glass():
+    """A mirror floor and a glass box in the axis room: bounce and see-through rays cross the same planes, S=3."""
+    mats = [dict(rgb=(0.7, 0.7, 0.7), reflection=np.full((1, 1, 3), 200, np.uint8)), dict(rgb=(0.8, 0.8, 0.75)),
+            dict(rgb=(0.8, 0.9, 1.0), transparency=np.full((1, 1, 3), 170, np.uint8))]
+    sc = _axis_scene("axis_mirror_glass", [_sun(4, (0.0, -1.0, 0.0), 0.4), _sun(3, (-1.0, 0.0, 0.0), 0.3)], samples=3, materials=mats,
+                     meshes=_room_meshes(floor=0, walls=1, props=2))
+    return _check(sc)
+
+
+def axis_class_sun():
+    """One radius-0 sun along -y over a white room: the opaque-diffuse class (wf_logic_kernel<.., LEAN=true>), 160x120."""
+    sc = _axis_scene("axis_class_sun", [_sun(4, (0.0, -1.0, 0.0), 0.8)], width=160, height=120,
+                     materials=[dict(rgb=(0.8, 0.8, 0.75)), dict(rgb=(0.6, 0.7, 0.9))])
+    assert R.path_class(sc) == R.PATH_CLASS_OPAQUE_DIFFUSE
+    return _check(sc)
+
+
+AXIS = [_axis_suns(t) for t in (3, 4, 5, 6)] + [axis_sun_negative_zero_dir, axis_planes_fine, axis_near_axis_lights, axis_near_axis_mixed,
+                                                 axis_untame_far, axis_untame_tiny, axis_untame_scaled, axis_tame_bounds, axis_point_lights,
+                                                 axis_mirror_glass, axis_class_sun]
+
+
+def axis_by_name(name):
+    for f in AXIS:
+        if f.__name__ == name:
+            return f
+    raise KeyError(name)
+
+
+def axis_fuzz_scene(seed):
+    """A random axis room drawn from the seed alone: boxes on a quarter grid, floor quads of 1/4 or 1/8, with or without a ceiling,
+    1-3 lights along an axis or next to one (zero components written +0 or -0, near-axis components from NEAR_AXIS), radius 0 or not,
+    one point light in one seed of two, S 1-3, up to 160x120."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    meshes = _room_meshes(ceiling=bool(rng.integers(0, 2)), step=float(rng.choice([0.25, 0.125])))[:-3]  # random boxes for the props
+    for _ in range(int(rng.integers(1, 6))):
+        lo = np.array([rng.integers(-7, 6) / 4, 0.0, rng.integers(4, 18) / 4])
+        hi = lo + np.array([rng.integers(1, 5) / 4, rng.integers(1, 9) / 4, rng.integers(1, 5) / 4])
+        meshes.append(_demo.quad_box(tuple(lo), tuple(hi), int(rng.integers(0, 3))))
+    lights = []
+    for _ in range(int(rng.integers(1, 4))):
+        d = np.array(AXES[int(rng.integers(0, 6))])
+        a = int(np.nonzero(d)[0][0])
+        for k in range(3):
+            if k != a:
+                d[k] = (-0.0 if rng.integers(0, 2) else 0.0) if rng.integers(0, 3) else float(rng.choice(NEAR_AXIS)) * rng.choice([-1, 1])
+        lights.append(_sun(int(rng.integers(3, 7)), tuple(d), 0.3, radius=float(rng.choice([0.0, 0.0, 1.5]))))
+    if seed % 2:
+        lights.append(dict(type=int(rng.choice([1, 2, 7, 8, 9])), pos=(rng.integers(-8, 9) / 4, rng.integers(0, 11) / 4, rng.integers(2, 21) / 4),
+                           col=(0.3, 0.3, 0.3), radius=0.0))
+    mats = [dict(rgb=(0.8, 0.8, 0.75)), dict(rgb=(0.9, 0.5, 0.3)),
+            dict(rgb=(0.8, 0.9, 1.0), transparency=np.full((1, 1, 3), int(rng.integers(0, 200)), np.uint8),
+                 reflection=np.full((1, 1, 3), int(rng.integers(0, 120)), np.uint8))]
+    w, h = int(rng.integers(48, 161)), int(rng.integers(36, 121))
+    sc = _axis_scene(f"axis_fuzz_{seed}", lights, width=w, height=h, samples=int(rng.integers(1, 4)), materials=mats, meshes=meshes)
+    sc.meta.update(seed=seed, lights=[(int(t), tuple(float(v) for v in d[:3])) for t, d in zip(sc.light_type, sc.light_dir)])
+    return sc
+
+
+def axis_fuzz_summary(sc):
+    return f"seed {sc.meta['seed']}: {sc.width}x{sc.height}, {sc.triangle_count} triangles, S={sc.sample_count}, lights {sc.meta['lights']}"
