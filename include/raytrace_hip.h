@@ -447,8 +447,18 @@ int rtHipWritePfm(const char *path, cl_uint width, cl_uint height, const cl_floa
  * are documented at the top of rt_kat.hip.  `table` is only read by RT_KAT_BOX (split planes, 3 x 257 floats, one
  * array per axis).  Returns 0, -1 bad arguments, -2 no such device (there is no CPU stand-in), -3 HIP failure.
  * ---------------------------------------------------------------------------------------------------------- */
-enum { RT_KAT_RANDF = 0, RT_KAT_SPHERE, RT_KAT_PMODF, RT_KAT_TRI, RT_KAT_PLINE, RT_KAT_BOX, RT_KAT_BIND, RT_KAT_POW, RT_KAT_QUOTIENT, RT_KAT_OPS };
+enum { RT_KAT_RANDF = 0, RT_KAT_SPHERE, RT_KAT_PMODF, RT_KAT_TRI, RT_KAT_PLINE, RT_KAT_BOX, RT_KAT_BIND, RT_KAT_POW, RT_KAT_QUOTIENT,
+       RT_KAT_SPHERE_SPLIT, RT_KAT_ACCUM, RT_KAT_OPS };
 int rtHipDeviceKat(int device, int op, cl_uint count, const void *in, cl_uint inStride, void *out, cl_uint outStride, const float *table);
+
+/* TEST-ONLY: the shading building blocks -- the texel look-up (Get2dTableValue3, raytrace_opencl.c:103-122) on every route
+ * texel_rec / texel take, and the shading normal (GetTriangleNormal, :195-263) in all three instantiations the kernels use -- run on
+ * a RESIDENT scene's own device records (triangle records, shading rows, material descriptors, atlas, bump tables), `count` items
+ * of 40 (RT_SHADE_KAT_TEXEL) or 48 (RT_SHADE_KAT_NORMAL) bytes in, 64 or 96 bytes out; layouts at the top of rt_kat.hip.
+ * Returns 0, -1 bad arguments (an unknown op, a material, channel or triangle the scene does not have, an empty atlas),
+ * -3 HIP failure. */
+enum { RT_SHADE_KAT_TEXEL = 0, RT_SHADE_KAT_NORMAL = 1 };
+int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void *in, void *out);
 
 /* TEST / TUNING ONLY.  The library reads no environment variables (a plugin host's environment must not be able to slow frames
  * down, make them redo themselves or fail); every tuning value and every fault injector of the tests is set here, process-wide,

@@ -1638,6 +1638,26 @@ int rtHipTestPathClass(const rtHipScene *scene)
     return (int)scene->dev.pathClass;
 }
 
+int rt_shade_kat_run(const RtDevScene *scene, int op, uint32_t count, const void *in, void *out); // rt_kat.hip
+
+int rtHipTestShadeKat(const rtHipScene *scene, int op, uint32_t count, const void *in, void *out)
+{
+    if (!scene || (count && (!in || !out))) return -1;
+    const RtDevScene &D = scene->dev;
+    // every index the kernel reads through is checked here: the kernel trusts its items
+    for (uint32_t i = 0; i < count; ++i) {
+        if (op == RT_SHADE_KAT_TEXEL) {
+            const int32_t *item = reinterpret_cast<const int32_t *>(in) + 10 * (size_t)i;
+            if (D.texelCount == 0u || item[0] < 0 || (uint32_t)item[0] >= D.materialCount || item[1] < 0 || item[1] >= 5) return -1;
+        } else if (op == RT_SHADE_KAT_NORMAL) {
+            if (reinterpret_cast<const uint32_t *>(in)[12 * (size_t)i] >= D.triangleCount) return -1;
+        } else return -1;
+    }
+    if (op == RT_SHADE_KAT_NORMAL && count && D.texelCount == 0u && D.materialCount) return -1; // (a height map fetch needs an atlas)
+    if (hipSetDevice(scene->device) != hipSuccess || hipStreamSynchronize(scene->stream) != hipSuccess) return -3;
+    return rt_shade_kat_run(&D, op, count, in, out);
+}
+
 int rtHipTestRoundLog(const rtHipScene *scene, uint32_t *rays, uint32_t n)
 {
     if (!scene || (n && !rays)) return -1;

@@ -89,6 +89,28 @@ __device__ V3 sphere_point(uint64_t &s, float radius)
     return mk(scale * p.x, scale * p.y, scale * p.z);
 }
 
+// GetSpherePoint (raytrace_opencl.c:30-45) split in two: the draws, and the scaling by the sphere's radius.  The number of
+// draws does not depend on the radius, so a hit's light samples can be drawn before the radius is looked at.
+struct SphereRaw { V3 p; float len, sq; };
+// (forced inline: left to the inliner it became a call in the round-0 kernels once they grew, with the generator state in scratch)
+__device__ __forceinline__ SphereRaw sphere_raw(uint64_t &s)
+{
+    SphereRaw r;
+    do {
+        r.p.x = rand11(s);
+        r.p.y = rand11(s);
+        r.p.z = rand11(s);
+        r.len = sqrt_rn(dot3(r.p, r.p));
+    } while (r.len <= 0.f);
+    r.sq = sqrt_rn(rand01(s));
+    return r;
+}
+__device__ __forceinline__ V3 sphere_scaled(const SphereRaw &r, float radius)
+{
+    const float scale = r.sq * radius / r.len; // :40
+    return mk(scale * r.p.x, scale * r.p.y, scale * r.p.z);
+}
+
 // raytrace_opencl.c:25-28.  Must stay in double: frac + 1.0 needs up to 53 bits (a tiny negative frac gives
 // 1 - 2^-k, which survives the second modf and only then rounds to 1.0f).
 __device__ __forceinline__ float pos_modf(float v)

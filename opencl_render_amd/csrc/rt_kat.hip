@@ -12,6 +12,19 @@
 //   RT_KAT_BIND       p3 d3 lo3 hi3                                   p3 after the clamps                                                     (:265-322)
 //   RT_KAT_POW        f32 x                                           (float)pow(0.5f, x), NaN -> 1                                           (:631-632)
 //   RT_KAT_QUOTIENT   f32 plane, o, d                                 f32 (plane-o)/d as the compiler divides, f32 the walk's short sequence, u32 tame (:383-385)
+//   RT_KAT_SPHERE_SPLIT  u64 seed, f32 radius, pad                    as RT_KAT_SPHERE, through sphere_raw + sphere_scaled (the wavefront kernels' form)
+//   RT_KAT_ACCUM      i32 plane, f32 colour, f32 scale                i32 sat_add_u16(plane, colour, scale), i32 trunc_x86(colour * scale)  (:726-741)
+//
+// rtHipTestShadeKat runs the shading building blocks on a RESIDENT scene (its RtDevScene: triRec, triShade, matRec, matSize,
+// matStart, the atlas and the bump tables exactly as the upload built them), with the Shared set-up of the kernels:
+//   op                      in (per item, 40 / 48 bytes)                    out (per item, 64 / 96 bytes)
+//   RT_SHADE_KAT_TEXEL      i32 material, i32 channel, uv[6], l1, l2        {x,y,z,raw} of texel_rec (zero when the descriptor is 0), of
+//                           (Get2dTableValue3, :103-122)                   texel<false> and of texel<true> on matStart/matSize, then the
+//                                                                           descriptor word and the texel count of the counted variant
+//   RT_SHADE_KAT_NORMAL     u32 triangle, where3, ray o3, ray d3, l1, l2    {x,y,z,ran} of shading_normal<false> with the MatRec,
+//                           (GetTriangleNormal, :195-263)                  <true> without one (the megakernel's) and <false, true> (the
+//                                                                           opaque-diffuse class form; ran = 0 where the material's height
+//                                                                           map is an image), each without and with firstVertex
 #include "rt_devfuncs.h"
 #include "raytrace_hip.h"
 
@@ -107,16 +120,120 @@ __global__ __launch_bounds__(256) void rt_kat_kernel(int op, uint32_t count, con
         reinterpret_cast<uint32_t *>(fo)[2] = (tame_origin(plane) && tame_origin(o) && tame_direction(d)) ? 1u : 0u;
         break;
     }
+    case RT_KAT_SPHERE_SPLIT: {
+        uint64_t s = *reinterpret_cast<const uint64_t *>(fi);
+        const V3 p = sphere_scaled(sphere_raw(s), fi[2]);
+        fo[0] = p.x; fo[1] = p.y; fo[2] = p.z; fo[3] = 0.f;
+        *reinterpret_cast<uint64_t *>(fo + 4) = s;
+        break;
+    }
+    case RT_KAT_ACCUM: {
+        const int *ii = reinterpret_cast<const int *>(fi);
+        int *io = reinterpret_cast<int *>(fo);
+        io[0] = sat_add_u16(ii[0], fi[1], fi[2]);
+        io[1] = trunc_x86(fi[1] * fi[2]);
+        break;
+    }
     default:
         break;
     }
 }
 
+__device__ __forceinline__ void put4(float *o, V3 v, uint32_t w)
+{
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; reinterpret_cast<uint32_t *>(o)[3] = w;
+}
+
+__global__ __launch_bounds__(256) void rt_shade_kat_kernel(const RtDevScene S, int op, uint32_t count, const unsigned char *__restrict__ in,
+                                                           unsigned char *__restrict__ out)
+{
+    __shared__ Shared sh; // as every kernel that shades sets it up
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) (&sh.planes[0][0])[i] = S.boxMin[i];
+    sh.unit255[threadIdx.x] = (float)threadIdx.x / 255.f;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    if (op == RT_SHADE_KAT_TEXEL) {
+        const int *ii = reinterpret_cast<const int *>(in + (size_t)i * 40);
+        const float *fi = reinterpret_cast<const float *>(ii);
+        float *fo = reinterpret_cast<float *>(out + (size_t)i * 64);
+        const int m = ii[0], ch = ii[1];
+        const float *uv = fi + 2;
+        const float l1 = fi[8], l2 = fi[9];
+        const MatRec M = load_mat(S, m);
+        const int at = CH_COUNT * m + ch;
+        Counters cn;
+        for (int k = 0; k < ST_COUNT; ++k) cn.v[k] = 0;
+        uint32_t raw = 0u;
+        V3 v = mk(0.f, 0.f, 0.f);
+        if (M.desc[ch]) v = texel_rec<false>(S, sh, M, ch, uv, l1, l2, raw, cn);
+        put4(fo, v, raw);
+        raw = 0u;
+        v = texel<false>(S, sh, S.matStart[at], S.matSize[2 * at], S.matSize[2 * at + 1], uv, l1, l2, raw, cn);
+        put4(fo + 4, v, raw);
+        raw = 0u;
+        v = texel<true>(S, sh, S.matStart[at], S.matSize[2 * at], S.matSize[2 * at + 1], uv, l1, l2, raw, cn);
+        put4(fo + 8, v, raw);
+        reinterpret_cast<uint32_t *>(fo)[12] = M.desc[ch];
+        reinterpret_cast<uint32_t *>(fo)[13] = cn.v[ST_TEXELS];
+        return;
+    }
+    // RT_SHADE_KAT_NORMAL
+    const float *fi = reinterpret_cast<const float *>(in + (size_t)i * 48);
+    float *fo = reinterpret_cast<float *>(out + (size_t)i * 96);
+    const uint32_t tri = reinterpret_cast<const uint32_t *>(fi)[0];
+    const V3 where = ld3(fi + 1), o = ld3(fi + 4), d = ld3(fi + 7);
+    const float l1 = fi[10], l2 = fi[11];
+    const float *shade = S.triShade + 24 * (size_t)tri;
+    const int m = __float_as_int(shade[21]);
+    const float4 first = reinterpret_cast<const float4 *>(S.triRec)[4 * (size_t)tri]; // the round-0 row's copy (rt_wavefront.hip, TriRow)
+    MatRec mat;
+    mat.desc[0] = mat.desc[1] = mat.desc[2] = mat.desc[3] = mat.desc[4] = 0u; mat.m = m;
+    if (0 <= m) mat = load_mat(S, m);
+    Counters cn;
+    for (int k = 0; k < ST_COUNT; ++k) cn.v[k] = 0;
+    put4(fo + 0, shading_normal<false>(S, sh, where, o, d, tri, l1, l2, shade, m, cn, &mat), 1u);
+    put4(fo + 4, shading_normal<false>(S, sh, where, o, d, tri, l1, l2, shade, m, cn, &mat, &first), 1u);
+    put4(fo + 8, shading_normal<true>(S, sh, where, o, d, tri, l1, l2, shade, m, cn), 1u);
+    put4(fo + 12, shading_normal<true>(S, sh, where, o, d, tri, l1, l2, shade, m, cn, nullptr, &first), 1u);
+    const uint32_t bump = mat.desc[CH_BUMP];
+    if (m < 0 || bump == 0u || (bump & 0x80000000u)) { // what the class kernel admits: no height map, or one of one texel
+        put4(fo + 16, shading_normal<false, true>(S, sh, where, o, d, tri, l1, l2, shade, m, cn, &mat), 1u);
+        put4(fo + 20, shading_normal<false, true>(S, sh, where, o, d, tri, l1, l2, shade, m, cn, &mat, &first), 1u);
+    } else {
+        put4(fo + 16, mk(0.f, 0.f, 0.f), 0u);
+        put4(fo + 20, mk(0.f, 0.f, 0.f), 0u);
+    }
+}
+
 } // namespace
+
+// rtHipTestShadeKat's device part (rt_api.cpp holds the scene): synchronous, on the current device.  0, -1 bad op, -3 HIP failure.
+extern "C" __attribute__((visibility("hidden"))) int rt_shade_kat_run(const RtDevScene *scene, int op, uint32_t count, const void *in, void *out)
+{
+    const RtDevScene &S = *scene;
+    if (op != RT_SHADE_KAT_TEXEL && op != RT_SHADE_KAT_NORMAL) return -1;
+    if (count == 0) return 0;
+    const size_t inStride = op == RT_SHADE_KAT_TEXEL ? 40 : 48, outStride = op == RT_SHADE_KAT_TEXEL ? 64 : 96;
+    unsigned char *dIn = nullptr, *dOut = nullptr;
+    int rc = -3;
+    do {
+        if (hipMalloc((void **)&dIn, count * inStride) != hipSuccess) break;
+        if (hipMalloc((void **)&dOut, count * outStride) != hipSuccess) break;
+        if (hipMemcpy(dIn, in, count * inStride, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemset(dOut, 0, count * outStride) != hipSuccess) break;
+        hipLaunchKernelGGL(rt_shade_kat_kernel, dim3((count + 255) / 256), dim3(256), 0, 0, S, op, count, dIn, dOut);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(out, dOut, count * outStride, hipMemcpyDeviceToHost) != hipSuccess) break;
+        rc = 0;
+    } while (0);
+    (void)hipFree(dIn); (void)hipFree(dOut);
+    return rc;
+}
 
 extern "C" int rtHipDeviceKat(int device, int op, cl_uint count, const void *in, cl_uint inStride, void *out, cl_uint outStride, const float *table)
 {
-    static const uint32_t inNeed[RT_KAT_OPS] = { 8, 16, 4, 68, 36, 12, 48, 4, 12 }, outNeed[RT_KAT_OPS] = { 192, 24, 4, 20, 4, 12, 12, 4, 12 };
+    static const uint32_t inNeed[RT_KAT_OPS] = { 8, 16, 4, 68, 36, 12, 48, 4, 12, 16, 12 }, outNeed[RT_KAT_OPS] = { 192, 24, 4, 20, 4, 12, 12, 4, 12, 24, 8 };
     if (op < 0 || op >= RT_KAT_OPS || !in || !out || inStride < inNeed[op] || outStride < outNeed[op] || (inStride & 3u) || (outStride & 3u)) return -1;
     if (op == RT_KAT_BOX && !table) return -1;
     if (count == 0) return 0;

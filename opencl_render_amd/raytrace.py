@@ -70,6 +70,7 @@ RESIDENT_SYMBOLS = [
     "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
+    "rtHipTestShadeKat",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
@@ -169,6 +170,7 @@ def lib() -> C.CDLL:
     L.rtHipTestPathClass.argtypes = [vp]
     L.rtHipTestRoundLog.argtypes = [vp, C.POINTER(u32), u32]
     L.rtHipTestBuildLog.argtypes = [C.POINTER(u64), u32]
+    L.rtHipTestShadeKat.argtypes = [vp, C.c_int, u32, vp, vp]
     L.rtHipFree.argtypes = [vp]
     L.rtHipFree.restype = None
     _lib = L
@@ -449,6 +451,15 @@ class ResidentScene:
         if lib().rtHipTestRoundLog(self.handle, rays, n) < 0:
             raise RuntimeError("rtHipTestRoundLog failed")
         return [int(v) for v in rays]
+
+    def shade_kat(self, op: int, inp: np.ndarray) -> np.ndarray:
+        """rtHipTestShadeKat on this scene: `inp` holds one 40-byte (RT_SHADE_KAT_TEXEL) or 48-byte (RT_SHADE_KAT_NORMAL) row per item;
+        returns the 64- or 96-byte rows as uint8."""
+        inp = np.ascontiguousarray(inp)
+        n = inp.shape[0]
+        out = np.zeros((n, 64 if op == 0 else 96), np.uint8)
+        self._check(lib().rtHipTestShadeKat(self.handle, op, n, _ptr(inp), _ptr(out)), "rtHipTestShadeKat")
+        return out
 
     def _check(self, rc, what):
         if rc != 0:

@@ -393,6 +393,13 @@ static v3 shading_normal(const rt_oracle_scene *sc, v3 where, v3 ray_o, v3 ray_d
     return n;
 }
 
+void rt_oracle_shading_normal(const rt_oracle_scene *sc, const float where[3], const float ray_o[3], const float ray_d[3], uint32_t tri,
+                              float ab_l, float ac_l, float out[3])
+{
+    v3 n = shading_normal(sc, ld3(where), ld3(ray_o), ld3(ray_d), tri, ab_l, ac_l, 0);
+    out[0] = n.x; out[1] = n.y; out[2] = n.z;
+}
+
 /* One queued ray (raytrace_opencl.c:461-468). */
 typedef struct {
     int bounces_left;

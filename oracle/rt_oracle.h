@@ -111,6 +111,10 @@ uint32_t rt_oracle_grid_trace(const rt_oracle_scene *sc, const float o[3], const
                               float *t, float *ab_l, float *ac_l);              /* :324-401 */
 void  rt_oracle_texel(const uint8_t *table, uint32_t w, uint32_t h, const float uv[6],
                       float ab_l, float ac_l, float out[3]);                    /* :103-122 */
+/* GetTriangleNormal on the scene's triangle `tri` (camera vectors and pixelSizeInv from the scene); a bump probe that misses the
+ * plane leaves abL/acL at 0 (the deviation noted at the top of rt_oracle.c). */
+void  rt_oracle_shading_normal(const rt_oracle_scene *sc, const float where[3], const float ray_o[3], const float ray_d[3],
+                               uint32_t tri, float ab_l, float ac_l, float out[3]); /* :195-263 */
 
 #ifdef __cplusplus
 }

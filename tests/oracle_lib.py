@@ -127,8 +127,49 @@ def ref() -> C.CDLL:
         L.GetBoxAddress.argtypes = [C.c_int32, vp, Float3]
         L.BindInCube.restype = u32
         L.BindInCube.argtypes = [C.POINTER(Float3), Float3, Float3, Float3]
+        L.Get2dTableValue3.restype = Float3
+        L.Get2dTableValue3.argtypes = [vp, _U2, _F2, _F2, _F2, f32, f32]
+        if hasattr(L, "ref_triangle_normal"):  # (a library built from an older oracle/ref_glue.c lacks it)
+            L.ref_triangle_normal.argtypes = [vp, vp, vp, u32, f32, f32] + [vp] * 8 + [vp, vp, f32, f32, vp]
         _ref = L
     return _ref
+
+
+# OpenCL vectors passed by value to Get2dTableValue3: members spelled out one by one, so that ctypes classifies the structures as the
+# C compiler does (two floats in one SSE register, two uints in one integer register)
+class _F2(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float)]
+
+
+class _U2(C.Structure):
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32)]
+
+
+def ref_texel(table, w, h, uv, ab_l, ac_l):
+    """The reference's Get2dTableValue3 (raytrace_opencl.c:103-122) on the w x h table at `table` ([n, 4] u8), uv = {aU, aV, bU, bV,
+    cU, cV}.  Returns the three floats."""
+    r = ref().Get2dTableValue3(table.ctypes.data_as(C.c_void_p), _U2(w, h), _F2(float(uv[0]), float(uv[1])), _F2(float(uv[2]), float(uv[3])),
+                               _F2(float(uv[4]), float(uv[5])), float(ab_l), float(ac_l))
+    return np.array(r.s[:3], np.float32)
+
+
+def have_ref_zeroed() -> bool:
+    """oracle/_ref's library carries ref_glue.c's ref_triangle_normal (one built from an older ref_glue.c does not)."""
+    return have_ref() and hasattr(ref(), "ref_triangle_normal")
+
+
+def ref_triangle_normal_zeroed(sc, where, o, d, tri, ab_l, ac_l, stack_fill=0.0):
+    """The reference's GetTriangleNormal (raytrace_opencl.c:195-263) on triangle `tri` of the scene, through oracle/ref_glue.c's
+    ref_triangle_normal: the stack its frame will occupy is first filled with `stack_fill`, so that the barycentrics a missed bump
+    probe leaves unwritten (:244,:249) read that value (0: the rule of the restatement and the kernels)."""
+    # the reference reads materialImageSize[5 * m + 3] before it tests m >= 0 (:226): two entries in front for material -1
+    msz = np.concatenate([np.zeros((4, 2), np.uint32), sc.mat_size]).astype(np.uint32)
+    out = np.zeros(3, np.float32)
+    w, ro, rd = (np.ascontiguousarray(v, np.float32) for v in (where, o, d))
+    ref().ref_triangle_normal(_ptr(w), _ptr(ro), _ptr(rd), int(tri), float(ab_l), float(ac_l), _ptr(sc.tri_index), _ptr(sc.tri_normal),
+                              _ptr(sc.tri_material), _ptr(sc.tri_uv), _ptr(sc.vertex), _ptr(msz[4:]), _ptr(sc.mat_start), _ptr(sc.textures),
+                              _ptr(sc.top_to_bottom), _ptr(sc.left_to_right), float(sc.pixel_size_inv), float(stack_fill), _ptr(out))
+    return out
 
 
 def _ptr(a):

@@ -552,3 +552,95 @@ def axis_fuzz_scene(seed):
 
 def axis_fuzz_summary(sc):
     return f"seed {sc.meta['seed']}: {sc.width}x{sc.height}, {sc.triangle_count} triangles, S={sc.sample_count}, lights {sc.meta['lights']}"
+
+
+# ---- shading known answers (tests/golden/kat_shading.npz, tests/test_shading_kat.py, tests/test_shading_kat_gpu.py) ------------------
+# The texel look-up (raytrace_opencl.c:103-122) and the shading normal (:195-263) on resident scenes.  The tables are generated from a
+# formula (bytes of an integer hash of the texel index), so that the fixture stores only the queries and the reference's answers.
+
+def hash_texels(n, salt):
+    """n texels [n, 4] u8 (the 4th byte 0): the low three bytes of splitmix64(index + salt * golden ratio)."""
+    x = np.arange(n, dtype=np.uint64) + np.uint64((salt * 0x9E3779B97F4A7C15) & (2 ** 64 - 1))
+    x ^= x >> np.uint64(30)
+    x *= np.uint64(0xBF58476D1CE4E5B9)
+    x ^= x >> np.uint64(27)
+    x *= np.uint64(0x94D049BB133111EB)
+    x ^= x >> np.uint64(31)
+    out = np.zeros((n, 4), np.uint8)
+    out[:, :3] = x.view(np.uint8).reshape(n, 8)[:, :3]
+    return out
+
+
+# (w, h) of the texel scene's tables, in atlas order: the small shapes, then a 4096 x 4096 table, so that the last table starts above
+# 2^24 texels.  Table i is channel i % 5 of material i (the other channels absent).
+TEXEL_TABLES = [(1, 1), (1, 7), (7, 1), (2, 2), (5, 3), (64, 48), (1024, 1), (1, 1024), (4096, 4096), (37, 29)]
+
+
+def shade_texel_scene():
+    """A few triangles whose materials carry TEXEL_TABLES (the triangles themselves are not queried)."""
+    m = len(TEXEL_TABLES)
+    sc = S.make_soup(32, 24, 40, 0.2, seed=81, samples=1, materials=[_lambert()] * m, name="shade_texel_scene")
+    sizes = np.zeros((S.CH_COUNT * m, 2), np.uint32)
+    starts = np.zeros(S.CH_COUNT * m + 1, np.int32)
+    cursor = 0
+    for i, (w, h) in enumerate(TEXEL_TABLES):
+        for c in range(S.CH_COUNT):
+            starts[S.CH_COUNT * i + c] = cursor
+            if c == i % S.CH_COUNT:
+                sizes[S.CH_COUNT * i + c] = (w, h)
+                cursor += w * h
+    starts[-1] = cursor
+    sc.mat_size, sc.mat_start = sizes, starts
+    sc.textures = np.concatenate([hash_texels(w * h, 1000 + i) for i, (w, h) in enumerate(TEXEL_TABLES)])
+    return sc
+
+
+# Materials of the normal scenes: none (-1 is assigned on top), no height map, one-texel height maps of several values, and image
+# height maps of 1x7, 7x1, 5x5 and 64x48 texels.  NORMAL_BUMPS[i] is material i's height map.
+NORMAL_BUMPS = [None, (255, 0, 0), (17, 3, 9), (128, 128, 128), (0, 0, 0), (1, 7), (7, 1), (5, 5), (64, 48)]
+
+
+def _bump_image(w, h, salt):
+    return hash_texels(w * h, salt)[:, :3].reshape(h, w, 3)
+
+
+def shade_normal_scene(zoom=1):
+    """A soup with smooth, flat and non-unit vertex normals and some collapsed triangles, UVs spread wide so that neighbouring pixels
+    land on different texels of the height maps; every tenth triangle lies in the plane z = 3 (the camera's tb and lr have no z, so
+    probe rays with d.z = 0 are parallel to it).  zoom = 1: a 60-pixel-wide camera (pixelSizeInv 60); zoom = 50: the same view
+    magnified 50 times (pixelSizeInv 3000, tb and lr 50 times shorter)."""
+    mats = []
+    for i, b in enumerate(NORMAL_BUMPS):
+        bump = None if b is None else (_bump_image(b[0], b[1], 2000 + i) if i >= 5 else b)
+        mats.append(dict(color=(200, 200, 200), bump=bump))
+    t = 360
+    sc = S.make_soup(60, 44, t, 0.35, seed=91, samples=1, materials=mats, random_uv=True, smooth_normals=True,
+                     material_ids=(np.arange(t) % (len(mats) + 1) - 1).astype(np.int32), name=f"shade_normal_scene_{zoom}")
+    rng = np.random.Generator(np.random.PCG64(92))
+    sc.tri_uv *= np.float32(9.0)
+    nrm = sc.tri_normal.reshape(t, 3, 4)
+    v = sc.vertex.reshape(t, 3, 4)
+    flat = np.arange(t) % 3 == 1
+    nrm[flat, 1:] = nrm[flat, :1]
+    scaled = np.arange(t) % 3 == 2
+    nrm[scaled, :, :3] *= rng.uniform(0.2, 5.0, (int(scaled.sum()), 3, 1)).astype(np.float32)
+    planar = np.arange(t) % 10 == 4
+    v[planar, :, 2] = np.float32(3.0)
+    a = v[planar, 0, :3]
+    n = np.cross(v[planar, 1, :3] - a, v[planar, 2, :3] - a)
+    nrm[planar, :, :3] = np.where(n[:, 2:3] < 0, np.float32(-1), np.float32(1))[:, None, :] * np.array([0, 0, 1], np.float32)
+    v[np.arange(t) % 23 == 7, 2] = v[np.arange(t) % 23 == 7, 1]           # segments
+    v[np.arange(t) % 29 == 11, 1:] = v[np.arange(t) % 29 == 11, :1]      # points
+    if zoom != 1:
+        z = np.float32(zoom)
+        sc.left_to_right = (sc.left_to_right / z).astype(np.float32)
+        sc.top_to_bottom = (sc.top_to_bottom / z).astype(np.float32)
+        sc.eye_to_top_left = (sc.eye_to_top_left * np.array([1 / z, 1 / z, 1, 0], np.float32)).astype(np.float32)
+        sc.pixel_size_inv = float(np.float32(sc.pixel_size_inv) * z)
+    return sc
+
+
+# light spreads the host computes for sun radii 0, 0.5, 90 and 360 degrees (rt_api.cpp, raytrace_opencl.c:594) are minted with these
+# light directions
+SPREAD_RADII = (0.0, 0.5, 90.0, 360.0)
+SPREAD_DIRS = ((0.3, -0.8, 0.5), (0.0, 0.0, 2.0))
