@@ -282,6 +282,39 @@ void    *rtHipPassBuffer(rtHipScene *scene);
 uint64_t rtHipPassBufferBytes(const rtHipScene *scene);
 int      rtHipReadbackPasses(rtHipScene *scene, cl_ushort *alpha, cl_float *depth, cl_uint *triangle);
 
+/* RAY QUERIES: what does a ray of the caller's hit in a resident scene?  The answer is the reference's grid walk,
+ * RayIntersectsTriangles (raytrace_opencl.c:324-401), the routine every secondary and shadow ray of a render goes through, on the
+ * scene's own grid -- bit for bit what rt_oracle_grid_trace (oracle/rt_oracle.h) returns.
+ *
+ * Inputs per ray: origin o and direction d (not normalised: t is measured in units of d), tmin and tmax, and an excluded triangle id
+ * (0xffffffff = none; excluded == NULL: none for every ray).  Answer per ray:
+ *   triangle  the triangle hit, 0xffffffff on a miss;
+ *   t         on a hit the hit's t; on a miss tmax (the walk resets its running maximum to tmax in every cell);
+ *   abL, acL  on a hit the hit's barycentric coordinates along ab and ac; on a miss both 0 (the reference leaves them unwritten).
+ * This is the reference's walk, NOT a geometric nearest hit.  The walk visits cells from the one holding o + tmin*d (clamped into the
+ * grid's box) in DDA order and ends at the first cell that holds a candidate passing the test (tmin < t < running maximum, inside the
+ * triangle, not the excluded one); in that cell it keeps the smallest t, on equal t the earliest candidate in the cell's list.  A
+ * triangle that spans several cells can therefore win with a hit that lies beyond that cell, over a nearer triangle of a later cell:
+ * the price of agreeing with the image the renderer produces.  The walk also ends at the cell of o + tmax*d (finite tmax) and where it
+ * would leave the grid.
+ * Every bit pattern of the inputs has a defined answer -- NaN, +-inf, +-0, subnormals, tmin > tmax, o + tmin*d overflowing, d = 0,
+ * excluded ids >= the triangle count -- and no input makes the kernel read outside the grid arrays: a point's cell is a binary search
+ * over the split planes (always in [0, 255]), and each step moves one axis one cell in a direction fixed per ray, so a walk ends within
+ * 3 x 256 steps.
+ * Queries read only the geometry and the grid: they may be interleaved with frames on the scene's stream and change nothing those frames
+ * produce.  They work on every instance (rtHipSceneCreateLike peers, partial tile sets, passes on, either pipeline). */
+typedef struct rtHipRay { cl_float o[3]; cl_float tmin; cl_float d[3]; cl_float tmax; } rtHipRay; /* 32 bytes */
+typedef struct rtHipHit { cl_float t; cl_uint triangle; cl_float abL; cl_float acL; } rtHipHit;     /* 16 bytes */
+/* HOST arrays, synchronous.  The rays go through a staging chunk the scene owns (allocated on first use -- device and pinned host memory,
+ * 52 bytes per ray of a chunk, counted by rtHipSceneBytes -- freed with the scene), one kernel launch per chunk on the scene's stream.
+ * count == 0 returns 0; a NULL scene, or NULL rays / hits with count > 0, returns -1. */
+int rtHipSceneIntersect(rtHipScene *scene, const rtHipRay *rays, const cl_uint *excluded, cl_uint count, rtHipHit *hits);
+/* DEVICE arrays of the scene's device (rays and hits 16-byte aligned), asynchronous on `stream` (a hipStream_t as void*; NULL = the
+ * scene's stream): one kernel launch, no allocation, no synchronisation.  Every pointer is checked first (hipPointerGetAttributes: device
+ * memory of the scene's device, the whole range inside one allocation); anything else returns -1 with the last-error text set and
+ * launches nothing.  count == 0 returns 0 and launches nothing. */
+int rtHipSceneIntersectDevice(rtHipScene *scene, const void *rays, const void *excluded, cl_uint count, void *hits, void *stream);
+
 /* Average device time in milliseconds of one rtHipRenderTiles frame (all its kernels) over the frames recorded since
  * the last call (HIP events on the launch stream), and the number of frames.  Returns 0 on success. */
 int rtHipKernelTime(rtHipScene *scene, double *avgMs, uint64_t *launches);
@@ -469,7 +502,8 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
  * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), and the test hooks
  * "plan_rounds", "plan_grid_tiny", "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
  * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
- * and most 2^32 - 1; above it they return -3).  Returns 0, -1 for an unknown key. */
+ * and most 2^32 - 1; above it they return -3), and "query_rays" (rays per staging chunk of rtHipSceneIntersect, default 2^20).  Returns 0, -1 for
+ * an unknown key. */
 int rtHipTune(const char *key, double value);
 
 /* TEST-ONLY: device addresses held by the first scene of RaytraceAll's cache -- triangle records, shading rows, the grid's pair

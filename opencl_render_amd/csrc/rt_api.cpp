@@ -46,6 +46,8 @@ extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, 
 extern "C" hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
 extern "C" hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, hipStream_t stream);
 extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefront *wf, int first, hipStream_t stream);
+extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
+                                       uint32_t fastQuotient, hipStream_t stream);
 
 namespace {
 
@@ -100,6 +102,7 @@ struct Tuning {
     uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
     uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
     uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
+    uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
 };
 // Read at the entry points only (scene create, RaytraceAll, the two public device builders): a build works from one snapshot.
 Tuning g_tune;
@@ -293,6 +296,11 @@ struct rtHipScene {
     uint32_t passMask = 0;
     uint32_t *passBuf = nullptr;
     uint64_t passBytes = 0;
+    // ray queries through host arrays (rtHipSceneIntersect): one chunk of hits | rays | excluded ids on the device and a pinned host buffer
+    // of the same layout from the staging pool, both made on first use
+    uint32_t queryRays = 0;
+    char *queryDev = nullptr, *queryHost = nullptr;
+    uint64_t queryBytes = 0;
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -1170,6 +1178,8 @@ void rtHipSceneDestroy(rtHipScene *sc)
     }
     if (sc->forkEvent) (void)hipEventDestroy(sc->forkEvent);
     if (sc->passBuf) (void)hipFree(sc->passBuf);
+    if (sc->queryDev) (void)hipFree(sc->queryDev);
+    if (sc->queryHost) Stager::pool().give(sc->queryHost, sc->queryBytes);
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
     sc->stager.destroy();
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
@@ -1410,6 +1420,75 @@ int rtHipReadbackPasses(rtHipScene *sc, cl_ushort *alpha, cl_float *depth, cl_ui
     return 0;
 }
 
+// A device pointer the query kernel may read or write `bytes` from: device memory of the scene's device, 16-byte aligned where the kernel
+// loads 16 bytes at a time, and inside one allocation.  A host pointer must never reach the kernel: its fault takes the whole GPU down.
+static int query_pointer_ok(const rtHipScene *sc, const void *p, uint64_t bytes, uint64_t align, const char *what)
+{
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("%s %p is not device memory", what, p); }
+    if (at.type != hipMemoryTypeDevice) return fail("%s %p is not device memory (memory type %d)", what, p, (int)at.type);
+    if (at.device != sc->device) return fail("%s %p is memory of device %d, the scene is on device %d", what, p, at.device, sc->device);
+    if ((uintptr_t)p % align) return fail("%s %p is not %llu-byte aligned", what, p, (unsigned long long)align);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return fail("%s %p: no allocation found", what, p); }
+    if ((uint64_t)((const char *)p - (const char *)base) + bytes > (uint64_t)size)
+        return fail("%s %p: %llu bytes reach past the end of its allocation", what, p, (unsigned long long)bytes);
+    return 0;
+}
+
+int rtHipSceneIntersectDevice(rtHipScene *sc, const void *rays, const void *excluded, cl_uint count, void *hits, void *stream)
+{
+    if (!sc) return fail("null scene");
+    if (count == 0) return 0;
+    if (!rays || !hits) return fail("null rays or hits with %u rays", count);
+    HIP_OK(hipSetDevice(sc->device));
+    if (query_pointer_ok(sc, rays, (uint64_t)count * sizeof(rtHipRay), 16, "rays") != 0) return -1;
+    if (excluded && query_pointer_ok(sc, excluded, (uint64_t)count * 4, 4, "excluded") != 0) return -1;
+    if (query_pointer_ok(sc, hits, (uint64_t)count * sizeof(rtHipHit), 16, "hits") != 0) return -1;
+    HIP_OK(rtw_launch_query(&sc->dev, rays, (const uint32_t *)excluded, count, hits, sc->tune.fastQuotient ? 1u : 0u,
+                            stream ? (hipStream_t)stream : sc->stream));
+    return 0;
+}
+
+int rtHipSceneIntersect(rtHipScene *sc, const rtHipRay *rays, const cl_uint *excluded, cl_uint count, rtHipHit *hits)
+{
+    if (!sc) return fail("null scene");
+    if (count == 0) return 0;
+    if (!rays || !hits) return fail("null rays or hits with %u rays", count);
+    HIP_OK(hipSetDevice(sc->device));
+    if (!sc->queryDev) {
+        const uint32_t chunk = std::max<uint32_t>(sc->tune.queryRays, 1u);
+        const uint64_t bytes = (uint64_t)chunk * (sizeof(rtHipRay) + 4 + sizeof(rtHipHit));
+        char *host = Stager::pool().take(bytes);
+        if (!host) return fail("rtHipSceneIntersect: no pinned staging buffer of %llu bytes", (unsigned long long)bytes);
+        void *dev = nullptr;
+        const hipError_t e = hipMalloc(&dev, bytes);
+        if (e != hipSuccess) { Stager::pool().give(host, bytes); return fail("rtHipSceneIntersect: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e)); }
+        sc->queryRays = chunk; sc->queryHost = host; sc->queryDev = (char *)dev; sc->queryBytes = bytes;
+        sc->bytes += bytes;
+    }
+    const uint64_t chunk = sc->queryRays;
+    // hits | rays | excluded ids: the two 16-byte records stay 16-byte aligned whatever the chunk
+    char *hostHits = sc->queryHost, *hostRays = hostHits + chunk * sizeof(rtHipHit), *hostExcl = hostRays + chunk * sizeof(rtHipRay);
+    char *devHits = sc->queryDev, *devRays = devHits + chunk * sizeof(rtHipHit), *devExcl = devRays + chunk * sizeof(rtHipRay);
+    for (uint64_t off = 0; off < count; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - off);
+        memcpy(hostRays, rays + off, (size_t)n * sizeof(rtHipRay));
+        HIP_OK(hipMemcpyAsync(devRays, hostRays, (size_t)n * sizeof(rtHipRay), hipMemcpyHostToDevice, sc->stream));
+        if (excluded) {
+            memcpy(hostExcl, excluded + off, (size_t)n * 4);
+            HIP_OK(hipMemcpyAsync(devExcl, hostExcl, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+        }
+        HIP_OK(rtw_launch_query(&sc->dev, devRays, excluded ? (const uint32_t *)devExcl : nullptr, n, devHits, sc->tune.fastQuotient ? 1u : 0u, sc->stream));
+        HIP_OK(hipMemcpyAsync(hostHits, devHits, (size_t)n * sizeof(rtHipHit), hipMemcpyDeviceToHost, sc->stream));
+        HIP_OK(hipStreamSynchronize(sc->stream));
+        memcpy(hits + off, hostHits, (size_t)n * sizeof(rtHipHit));
+    }
+    return 0;
+}
+
 int rtHipKernelTime(rtHipScene *sc, double *avgMs, uint64_t *launches)
 {
     if (!sc || !avgMs || !launches) return fail("null argument");
@@ -1610,7 +1689,7 @@ int rtHipTune(const char *key, double value)
         { "fast_quotient", &T.fastQuotient }, { "spin_limit", &T.spinLimit }, { "append_rays", &T.appendRays }, { "ordered_first", &T.orderedFirst }, { "slice_rays", &T.sliceRays },
         { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
-        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow },
+        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
         { "state_mb", nullptr, &T.stateMb, HUGE_VAL }, { "build_key_cap", nullptr, &T.buildKeyCap, 1e18 }, { "build_list_limit", nullptr, &T.buildListLimit },
     };
     for (const Key &e : table) {

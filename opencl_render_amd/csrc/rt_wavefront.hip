@@ -1990,7 +1990,135 @@ __global__ __launch_bounds__(256) void wf_status_kernel(const RtWavefront W, con
     for (uint32_t i = threadIdx.x; i < 3u * RT_WF_CTL_WORDS; i += 256u) W.ctl[i] = 0u;
 }
 
+// ---- ray queries (rtHipSceneIntersect*): caller-supplied rays against the resident grid -------------------------------------
+// One lane per ray: RayIntersectsTriangles (raytrace_opencl.c:324-401) over the dense view wf_trace_kernel reads (rt_device.h,
+// gridBlockSparse / pairRec): one block-table look-up per 4x4x4 block the walk enters, one 64-byte gather per occupied cell (its
+// first candidate and its count), the further candidates at `rest` in list order.  The running maximum is reset per cell (:366), a
+// candidate replaces it only with a strictly smaller t (ties keep the earlier candidate), and the walk ends at the first cell with a
+// hit, at the end cell, or where a step would leave the grid (:380-398).  Rays are {o.xyz, tmin} {d.xyz, tmax}; hits {t, triangle,
+// abL, acL}, abL = acL = 0 and t = tmax on a miss.  Every input has a bounded walk that reads inside the grid arrays: cell_of is a
+// binary search (coordinates in [0, 255] whatever the point, NaN included), and each step moves one axis one cell in the direction
+// fixed by the sign of d, so a walk leaves the grid after at most 3 x 255 steps -- the loop bound only states that.
+template <bool FAST>
+__device__ __forceinline__ uint32_t query_walk(const RtDevScene &S, const float *planes, V3 o, V3 d, float tmin, float tmax, uint32_t excluded,
+                                               float &hitT, float &hitL1, float &hitL2)
+{
+    const V3 lo = mk(planes[0], planes[RT_GRID_DIV + 1], planes[2 * (RT_GRID_DIV + 1)]);
+    const V3 hi = mk(planes[RT_GRID_DIV], planes[2 * RT_GRID_DIV + 1], planes[3 * RT_GRID_DIV + 2]);
+    V3 from = along(o, tmin, d);
+    bind_in_cube(from, d, lo, hi);
+    uint32_t cell = cell_of(planes, from), endCell = 0xffffffffu;
+    if (tmax < RT_INF) {
+        V3 to = along(o, tmax, d);
+        bind_in_cube(to, d, lo, hi);
+        endCell = cell_of(planes, to);
+    }
+    const bool px = (0.f <= d.x), py = (0.f <= d.y), pz = (0.f <= d.z);
+    const float *planesY = planes + (RT_GRID_DIV + 1), *planesZ = planes + 2 * (RT_GRID_DIV + 1);
+    uint32_t cx = cell & 255u, cy = (cell >> 8) & 255u, cz = cell >> 16;
+    // distances from the ray ORIGIN to the next plane of each axis (:383-385); a step re-divides only the axis it moved
+    float dx = (planes[cx + (px ? 1 : 0)] - o.x) / d.x;
+    float dy = (planesY[cy + (py ? 1 : 0)] - o.y) / d.y;
+    float dz = (planesZ[cz + (pz ? 1 : 0)] - o.z) / d.z;
+    const float rx = FAST ? refined_rcp(d.x) : 0.f, ry = FAST ? refined_rcp(d.y) : 0.f, rz = FAST ? refined_rcp(d.z) : 0.f;
+    const char *__restrict__ blockTable = reinterpret_cast<const char *>(S.gridBlockSparse);
+    const float4 *__restrict__ recs = reinterpret_cast<const float4 *>(S.pairRec);
+    uint32_t wordKey = 0xffffffffu, wordLo = 0, wordHi = 0, wordRank = 0;
+    uint32_t best = RT_NONE;
+    hitT = tmax;
+#pragma unroll 1
+    for (uint32_t visit = 0; visit < 3u * RT_GRID_DIV; ++visit) {
+        cell = cx | (cy << 8) | (cz << 16);
+        const uint32_t key = cell & 0xFCFCFCu;
+        if (key != wordKey) {
+            const uint3 w = *reinterpret_cast<const uint3 *>(blockTable + (size_t)key * 3u);
+            wordKey = key; wordLo = w.x; wordHi = w.y; wordRank = w.z;
+        }
+        const uint32_t bit = (cx & 3u) | ((cy & 3u) << 2) | ((cz & 3u) << 4);
+        const uint32_t below = (1u << (bit & 31u)) - 1u;
+        const uint32_t half = (bit & 32u) ? wordHi : wordLo;
+        if ((half >> (bit & 31u)) & 1u) {
+            const uint32_t dense = wordRank + ((bit & 32u) ? __popc(wordLo) + __popc(wordHi & below) : __popc(wordLo & below));
+            float tbest = tmax; // reset per cell (:366)
+            const float4 *rec = recs + 4 * (size_t)dense;
+            float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+            const uint32_t info = __float_as_uint(r1.w);
+            float t, l1, l2;
+            if (pair_test_flat(r0, r1, r2, r3, o, d, tmin, tbest, excluded, t, l1, l2)) {
+                best = __float_as_uint(r0.w); tbest = t; hitL1 = l1; hitL2 = l2;
+            }
+            uint32_t n = info & 15u;
+            if (n > 1u) {
+                rec = recs + 4 * (size_t)(info >> 4);
+                r0 = rec[0]; r1 = rec[1]; r2 = rec[2]; r3 = rec[3];
+                if (n == RT_PAIR_MANY) n = __float_as_uint(r1.w); // (the first further record has the exact count)
+#pragma unroll 1
+                for (uint32_t i = 1;;) {
+                    if (pair_test_flat(r0, r1, r2, r3, o, d, tmin, tbest, excluded, t, l1, l2)) {
+                        best = __float_as_uint(r0.w); tbest = t; hitL1 = l1; hitL2 = l2;
+                    }
+                    if (++i >= n) break;
+                    rec += 4;
+                    r0 = rec[0]; r1 = rec[1]; r2 = rec[2]; r3 = rec[3];
+                }
+            }
+            hitT = tbest;
+            if (best != RT_NONE) break;
+        }
+        if (cell == endCell) break;
+        // axis choice (:387-398): x only if strictly smallest, else y if smaller than z, else z; a step off the grid ends the walk
+        if ((dx < dy) & (dx < dz)) {
+            if (cx == (px ? 255u : 0u)) break;
+            cx = px ? cx + 1u : cx - 1u;
+            const float num = planes[cx + (px ? 1 : 0)] - o.x;
+            dx = FAST ? tame_quotient(num, d.x, rx) : num / d.x;
+        } else if (dy < dz) {
+            if (cy == (py ? 255u : 0u)) break;
+            cy = py ? cy + 1u : cy - 1u;
+            const float num = planesY[cy + (py ? 1 : 0)] - o.y;
+            dy = FAST ? tame_quotient(num, d.y, ry) : num / d.y;
+        } else {
+            if (cz == (pz ? 255u : 0u)) break;
+            cz = pz ? cz + 1u : cz - 1u;
+            const float num = planesZ[cz + (pz ? 1 : 0)] - o.z;
+            dz = FAST ? tame_quotient(num, d.z, rz) : num / d.z;
+        }
+    }
+    return best;
+}
+
+// rays [count][2] float4, excluded [count] (nullptr: none), hits [count] float4.  fastQuotient: the walk's quotient without scaling
+// and fix-up for waves whose rays are all tame, under the same guard as wf_trace_kernel.
+__global__ __launch_bounds__(256) void rt_query_kernel(const RtDevScene S, const float4 *__restrict__ rays, const uint32_t *__restrict__ excludedIds,
+                                                       const uint32_t count, float4 *__restrict__ hits, const uint32_t fastQuotient)
+{
+    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
+    __syncthreads();
+    const size_t at = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (at >= count) return;
+    const float4 a = rays[2 * at], b = rays[2 * at + 1];
+    const uint32_t excluded = excludedIds ? excludedIds[at] : RT_NONE;
+    const V3 o = xyz(a), d = xyz(b);
+    float t, l1 = 0.f, l2 = 0.f;
+    uint32_t tri;
+    const bool tame = tame_origin(o.x) && tame_origin(o.y) && tame_origin(o.z) && tame_direction(d.x) && tame_direction(d.y) && tame_direction(d.z);
+    if (S.planesTame && fastQuotient && __ballot(!tame) == 0ull) tri = query_walk<true>(S, planes, o, d, a.w, b.w, excluded, t, l1, l2);
+    else tri = query_walk<false>(S, planes, o, d, a.w, b.w, excluded, t, l1, l2);
+    if (tri == RT_NONE) { l1 = 0.f; l2 = 0.f; }
+    hits[at] = make_float4(t, __uint_as_float(tri), l1, l2);
+}
+
 // ---- launch wrappers ------------------------------------------------------------------------------------------------
+extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
+                                       uint32_t fastQuotient, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_query_kernel, dim3((uint32_t)(((uint64_t)count + 255u) / 256u)), dim3(256), 0, stream, *scene,
+                       reinterpret_cast<const float4 *>(rays), excluded, count, reinterpret_cast<float4 *>(hits), fastQuotient);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefront *wf, hipStream_t stream)
 {
     if (scene->tileCount == 0) return hipSuccess;

@@ -50,6 +50,14 @@ class SceneDesc(C.Structure):  # rtHipSceneDesc
     ]
 
 
+class Ray(C.Structure):  # rtHipRay: 32 bytes
+    _fields_ = [("o", C.c_float * 3), ("tmin", C.c_float), ("d", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class Hit(C.Structure):  # rtHipHit: 16 bytes
+    _fields_ = [("t", C.c_float), ("triangle", C.c_uint32), ("abL", C.c_float), ("acL", C.c_float)]
+
+
 class Stats(C.Structure):  # rtHipStats
     _fields_ = [(n, C.c_uint64) for n in ("primarySamples", "primaryCandidates", "gridRays", "gridCells", "gridCandidates", "shadedHits", "texelFetches")]
 
@@ -68,6 +76,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
+    "rtHipSceneIntersect", "rtHipSceneIntersectDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat",
@@ -155,6 +164,8 @@ def lib() -> C.CDLL:
     L.rtHipPassBufferBytes.restype = u64
     L.rtHipPassBufferBytes.argtypes = [vp]
     L.rtHipReadbackPasses.argtypes = [vp, vp, vp, vp]
+    L.rtHipSceneIntersect.argtypes = [vp, vp, vp, u32, vp]
+    L.rtHipSceneIntersectDevice.argtypes = [vp, vp, vp, u32, vp, vp]
     L.rtHipKernelTime.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
     L.rtHipBuildCameraList.argtypes = [u32, u32, vp, vp, vp, vp, f32, u32, vp, vp, C.c_int,
                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
@@ -186,7 +197,7 @@ _ENV_KEYS = {
     "RT_WF_BLOCKING": "blocking", "RT_WF_BATCH_PLAN": "batch_plan", "RT_WF_PLAN_ROUNDS": "plan_rounds", "RT_HIP_PIPELINE": "pipeline",
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
     "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow",
-    "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit",
+    "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit", "RT_HIP_QUERY_RAYS": "query_rays",
 }
 # comma-separated lists: RT_WF_SEG=a,b,.. sets seg0, seg1, .. (at most 5 values), RT_WF_SEG_RAYS sets seg_rays0.. (at most 4)
 _ENV_LISTS = (("RT_WF_SEG", "seg", 5), ("RT_WF_SEG_RAYS", "seg_rays", 4))
@@ -559,6 +570,132 @@ class ResidentScene:
                 out["mesh"] = np.where(hit, tm[idx] if len(tm) else -1, -1).astype(np.int32)
         return out
 
+    def intersect(self, origins, directions, tmin=0.0, tmax=np.inf, exclude=None, stream: int = 0) -> dict:
+        """What rays hit in this scene: the reference's grid walk, RayIntersectsTriangles (raytrace_opencl.c:324-401), bit for bit
+        (contract in include/raytrace_hip.h, rtHipSceneIntersect).  origins, directions: [N, 3] float32; tmin, tmax, exclude
+        (triangle ids, 0xffffffff = none): scalars or [N].  Returns t, triangle (u32, 0xffffffff on a miss), ab, ac (0 on a miss), hit,
+        position (o + t*d in float32) and material (i32, -1 on a miss) -- and mesh for a scene made by frontend.scene_from_meshes.
+        numpy inputs go through the host entry point.  torch tensors on this scene's device never leave it: the rays are packed on the
+        device, the query runs on torch's current stream (or `stream`), and the results are tensors on that device."""
+        if hasattr(origins, "data_ptr") or hasattr(directions, "data_ptr"):
+            return self._intersect_torch(origins, directions, tmin, tmax, exclude, stream)
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(directions, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"intersect: origins and directions must both be [N, 3] (got {o.shape} and {d.shape})")
+        n = o.shape[0]
+        if n >= 1 << 32:
+            raise ValueError("intersect: at most 2^32 - 1 rays per call")
+        rays = np.empty((n, 8), np.float32)
+        rays[:, 0:3] = o
+        rays[:, 4:7] = d
+        try:
+            rays[:, 3] = np.broadcast_to(np.asarray(tmin, np.float32), (n,))
+            rays[:, 7] = np.broadcast_to(np.asarray(tmax, np.float32), (n,))
+            excl = None if exclude is None else np.ascontiguousarray(np.broadcast_to(np.asarray(exclude).astype(np.uint32), (n,)))
+        except ValueError as e:
+            raise ValueError(f"intersect: tmin, tmax and exclude must be scalars or [{n}] arrays ({e})") from None
+        hits = np.zeros((n, 4), np.float32)
+        self._check(lib().rtHipSceneIntersect(self.handle, _ptr(rays), _ptr(excl), n, _ptr(hits)), "rtHipSceneIntersect")
+        t = hits[:, 0].copy()
+        tri = hits[:, 1].copy().view(np.uint32)
+        hit = tri != 0xFFFFFFFF
+        idx = np.where(hit, tri, 0).astype(np.int64)
+        out = dict(t=t, triangle=tri, ab=hits[:, 2].copy(), ac=hits[:, 3].copy(), hit=hit, position=o + t[:, None] * d)
+        for key, table in (("material", self.scene.tri_material), ("mesh", getattr(self.scene, "tri_mesh", None))):
+            if key == "mesh" and table is None:
+                continue
+            table = np.asarray(table, np.int32)
+            out[key] = np.where(hit, table[idx] if len(table) else -1, -1).astype(np.int32)
+        return out
+
+    def _intersect_torch(self, origins, directions, tmin, tmax, exclude, stream):
+        import torch
+
+        dev = torch.device("cuda", self.device)
+
+        def on_device(name, v):
+            if not isinstance(v, torch.Tensor) or v.device != dev:
+                where = v.device if isinstance(v, torch.Tensor) else type(v).__name__
+                raise ValueError(f"intersect: {name} must be a tensor on {dev} (the scene's device), not {where}")
+            return v
+
+        o = on_device("origins", origins).to(torch.float32)
+        d = on_device("directions", directions).to(torch.float32)
+        if o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"intersect: origins and directions must both be [N, 3] (got {tuple(o.shape)} and {tuple(d.shape)})")
+        n = o.shape[0]
+        if n >= 1 << 32:
+            raise ValueError("intersect: at most 2^32 - 1 rays per call")
+
+        def per_ray(name, v, dtype):
+            """A [n] tensor on the device, or a Python scalar (filled in on the device: no host-to-device copy)."""
+            if not isinstance(v, torch.Tensor) and np.ndim(v) == 0:
+                return np.asarray(v, np.float32 if dtype == torch.float32 else np.int64).item()
+            v = on_device(name, v) if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v), device=dev)
+            if v.dim() > 1 or (v.dim() == 1 and v.shape[0] != n):
+                raise ValueError(f"intersect: {name} must be a scalar or a [{n}] tensor (got {tuple(v.shape)})")
+            return v.to(dtype).expand(n)
+
+        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        rays[:, 0:3] = o
+        rays[:, 4:7] = d
+        rays[:, 3] = per_ray("tmin", tmin, torch.float32)
+        rays[:, 7] = per_ray("tmax", tmax, torch.float32)
+        excl = None
+        if exclude is not None:
+            e = per_ray("exclude", exclude, torch.int64)
+            if isinstance(e, int):
+                e &= 0xFFFFFFFF
+                excl = torch.full((n,), e - (1 << 32) if e >= 1 << 31 else e, dtype=torch.int32, device=dev)
+            else:
+                e = e & 0xFFFFFFFF
+                excl = torch.where(e >= 1 << 31, e - (1 << 32), e).to(torch.int32).contiguous()  # the u32 bits in an int32 tensor
+        hits = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        # The query runs on `run`: torch's current stream, or the caller's `stream`, or -- when the current stream is the null stream, which
+        # the library would take for "the scene's own stream" -- a side stream of this scene.  A stream other than the current one is ordered
+        # after the packing above and before everything enqueued on the current stream afterwards (events, no host synchronisation), and
+        # the buffers are recorded on it so that the caching allocator does not hand them out while the query may still use them.
+        cur = torch.cuda.current_stream(dev)
+        if stream and stream != cur.cuda_stream:
+            run = torch.cuda.ExternalStream(stream, device=dev)
+        elif cur.cuda_stream:
+            run = cur
+        else:
+            if getattr(self, "_side_stream", None) is None:
+                self._side_stream = torch.cuda.Stream(dev)
+            run = self._side_stream
+        if run is not cur:
+            run.wait_stream(cur)
+        self._check(lib().rtHipSceneIntersectDevice(self.handle, C.c_void_p(rays.data_ptr()), None if excl is None else C.c_void_p(excl.data_ptr()),
+                                                    n, C.c_void_p(hits.data_ptr()), C.c_void_p(run.cuda_stream)), "rtHipSceneIntersectDevice")
+        if run is not cur:
+            cur.wait_stream(run)
+            for buf in (rays, excl, hits):
+                if buf is not None:
+                    buf.record_stream(run)
+        bits = hits.view(torch.int32)
+        t = hits[:, 0].contiguous()
+        tri32 = bits[:, 1].contiguous()
+        hit = tri32 != -1
+        idx = torch.where(hit, tri32.to(torch.int64) & 0xFFFFFFFF, 0)
+        out = dict(t=t, triangle=tri32.view(torch.uint32), ab=hits[:, 2].contiguous(), ac=hits[:, 3].contiguous(), hit=hit,
+                   position=o + t[:, None] * d)
+        for key, table in self._device_id_tables(dev).items():
+            none = torch.full_like(tri32, -1)
+            out[key] = torch.where(hit, table[idx], none) if table.numel() else none
+        return out
+
+    def _device_id_tables(self, dev) -> dict:
+        """The scene's per-triangle material (and mesh) ids as int32 tensors on `dev`, uploaded once per scene."""
+        tables = getattr(self, "_id_tables", None)
+        if tables is None:
+            import torch
+            tables = {"material": torch.as_tensor(np.asarray(self.scene.tri_material, np.int32), device=dev)}
+            if getattr(self.scene, "tri_mesh", None) is not None:
+                tables["mesh"] = torch.as_tensor(np.asarray(self.scene.tri_mesh, np.int32), device=dev)
+            self._id_tables = tables
+        return tables
 
 def render_resident(sc: Scene, device: int = 0):
     """Upload, render every tile once, read back: returns [H,W] uint16 R,G,B."""
