@@ -282,6 +282,25 @@ void    *rtHipPassBuffer(rtHipScene *scene);
 uint64_t rtHipPassBufferBytes(const rtHipScene *scene);
 int      rtHipReadbackPasses(rtHipScene *scene, cl_ushort *alpha, cl_float *depth, cl_uint *triangle);
 
+/* Surface passes, the auxiliary images a denoiser takes next to the beauty: MEANS over all S samples of a pixel (anti-aliased like the
+ * beauty), 3 x f32 per pixel, row-major and interleaved (xyz / rgb).  Sample s = 1..S of pixel p = y*W + x is the primary ray the renderer
+ * traces: seed p*S + s, LR jitter first, then TB, the pixel's camera list scanned in order with a running closest hit (ties keep the
+ * earlier candidate).  On a hit (tri, t, abL, acL), with where = eye + t*dir per component in fp32:
+ *   NORMAL  n_s = GetTriangleNormal(where, eye, dir, tri, abL, acL) (raytrace_opencl.c:195-263, called at :548), the vector the
+ *           renderer shades with: Phong-interpolated, NOT normalised unless a bump map applies, not flipped toward the viewer
+ *   ALBEDO  a_s = the material's colour-channel texel at (abL, acL) (Get2dTableValue3, :554); (0,0,0) for material -1 or no colour channel
+ * A miss gives n_s = a_s = (0,0,0).  Per component, in fp32:  acc = +0.0f; for s = 1..S in order: acc = acc + v_s;  pass = acc / (float)S.
+ * The ALPHA pass tells where a mean mixes hits and misses.
+ * The surface buffer is separate from the pass buffer: [slot][nx ny nz ar ag ab][128*128] f32 holding the SUMS (not the means).  The
+ * pass buffer is used exactly while ALPHA, DEPTH or TRIANGLE is on, the surface buffer exactly while NORMAL or ALBEDO is on; each is
+ * made on first need, freed when its bits go off, and counted in rtHipSceneBytes.  rtHipReadbackSurfacePasses has the contract of
+ * rtHipReadbackPasses (W x H x 3 host arrays, only the scene's own tiles are stored) and divides by S on the host. */
+#define RT_HIP_PASS_NORMAL   8u
+#define RT_HIP_PASS_ALBEDO   16u
+void    *rtHipSurfaceBuffer(rtHipScene *scene);
+uint64_t rtHipSurfaceBufferBytes(const rtHipScene *scene);
+int      rtHipReadbackSurfacePasses(rtHipScene *scene, cl_float *normal, cl_float *albedo);
+
 /* RAY QUERIES: what does a ray of the caller's hit in a resident scene?  The answer is the reference's grid walk,
  * RayIntersectsTriangles (raytrace_opencl.c:324-401), the routine every secondary and shadow ray of a render goes through, on the
  * scene's own grid -- bit for bit what rt_oracle_grid_trace (oracle/rt_oracle.h) returns.
@@ -471,6 +490,9 @@ int rtHipWritePpm(const char *path, cl_uint width, cl_uint height, const cl_usho
  * Returns 0, -1 bad argument, -4 I/O error. */
 int rtHipWritePgm(const char *path, cl_uint width, cl_uint height, const cl_ushort *plane);
 int rtHipWritePfm(const char *path, cl_uint width, cl_uint height, const cl_float *plane);
+/* Sink of the surface passes (rtHipReadbackSurfacePasses): a colour PFM (PF, scale -1.0 = little-endian floats, bottom row first) of a
+ * row-major width x height x 3 f32 image.  Returns 0, -1 bad argument, -4 I/O error. */
+int rtHipWritePfmRgb(const char *path, cl_uint width, cl_uint height, const cl_float *rgb);
 
 /* ------------------------------------------------------------------------------------------------------------
  * TEST-ONLY: device-side known-answer runner (rt_kat.hip).  Runs the kernels' own building blocks -- the restatements

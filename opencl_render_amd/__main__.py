@@ -7,7 +7,9 @@ or PPM).  Needs an MI355X: there is no CPU fallback.
 
 ``--passes PREFIX`` renders through the resident layer instead (one instance per GPU over a tile deal for the all-GPUs device) and
 also writes the render passes: PREFIX_alpha.pgm (coverage), PREFIX_depth.pfm (eye-to-hit distance of sample 1) and PREFIX_ids.npz
-(triangle, material and mesh ids of sample 1's hit; -1 -- 0xffffffff for the triangle -- where it missed).
+(triangle, material and mesh ids of sample 1's hit; -1 -- 0xffffffff for the triangle -- where it missed).  With
+``--surface-passes`` it also writes PREFIX_normal.pfm and PREFIX_albedo.pfm (colour PFMs of the shading normal and the albedo at the
+primary hit, means over the pixel's samples: a denoiser's auxiliary images).
 """
 import argparse
 import sys
@@ -32,12 +34,22 @@ def parser():
     ap.add_argument("--out", default="img.bmp", help=".bmp or .ppm")
     ap.add_argument("--low-byte-compat", action="store_true", help="BMP only: keep the low byte of every u16 like the reference's writebmp3s")
     ap.add_argument("--passes", metavar="PREFIX", help="also write PREFIX_alpha.pgm, PREFIX_depth.pfm and PREFIX_ids.npz (render passes)")
+    ap.add_argument("--surface-passes", action="store_true", help="with --passes: also write PREFIX_normal.pfm and PREFIX_albedo.pfm")
     return ap
 
 
-def render_passes(sc, device: int, gpus: int):
-    """The frame through ResidentScene with every pass on: computation type `device` (1..gpus = one GPU, gpus + 1 = all of them, one
-    instance per GPU over raytrace.tiles_of_rank).  Returns the R, G, B planes and readback_passes' dict."""
+def parse_args(argv=None):
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.surface_passes and not args.passes:
+        ap.error("--surface-passes needs --passes PREFIX")
+    return args
+
+
+def render_passes(sc, device: int, gpus: int, surface: bool = False):
+    """The frame through ResidentScene with the alpha, depth and triangle passes on (and normal and albedo with `surface`): computation
+    type `device` (1..gpus = one GPU, gpus + 1 = all of them, one instance per GPU over raytrace.tiles_of_rank).  Returns the R, G, B
+    planes and readback_passes' dict."""
     from . import raytrace
     world = gpus if device == gpus + 1 else 1
     instances = []
@@ -46,7 +58,7 @@ def render_passes(sc, device: int, gpus: int):
             tiles = raytrace.tiles_of_rank(sc.width, sc.height, rank, world) if world > 1 else None
             rs = raytrace.ResidentScene(sc, rank if world > 1 else device - 1, tiles, like=instances[0] if instances else None)
             instances.append(rs)
-            rs.set_passes(alpha=True, depth=True, triangle=True)
+            rs.set_passes(alpha=True, depth=True, triangle=True, normal=surface, albedo=surface)
         for rs in instances:
             rs.render()
         planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
@@ -63,7 +75,7 @@ def render_passes(sc, device: int, gpus: int):
 
 
 def main(argv=None):
-    args = parser().parse_args(argv)
+    args = parse_args(argv)
 
     from . import demo, frontend, raytrace, scene
     if raytrace.lib().rtHipDeviceCount() < 1:
@@ -89,7 +101,7 @@ def main(argv=None):
     grid_ms = raytrace.build_scene_grid_device(sc, 0)
     t2 = time.perf_counter()
     if args.passes:
-        (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount())
+        (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount(), surface=args.surface_passes)
         ok = True
     else:
         ok, r, g, b = raytrace.raytrace_all(args.device, sc)
@@ -100,6 +112,9 @@ def main(argv=None):
         frontend.write_pgm(args.passes + "_alpha.pgm", passes["alpha"])
         frontend.write_pfm(args.passes + "_depth.pfm", passes["depth"])
         np.savez(args.passes + "_ids.npz", triangle=passes["triangle"], material=passes["material"], mesh=passes["mesh"])
+        if args.surface_passes:
+            frontend.write_pfm_rgb(args.passes + "_normal.pfm", passes["normal"])
+            frontend.write_pfm_rgb(args.passes + "_albedo.pfm", passes["albedo"])
     if args.out.lower().endswith(".ppm"):
         frontend.write_ppm(args.out, r, g, b)
     else:

@@ -41,6 +41,7 @@ extern "C" hipError_t rtp_dense_grid(const uint32_t *gridStart, const uint32_t *
 
 extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefront *wf, hipStream_t stream);
 extern "C" hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const RtWavefront *wf, uint32_t *passBuf, hipStream_t stream);
+extern "C" hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const RtWavefront *wf, float *surfBuf, hipStream_t stream);
 extern "C" hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next, hipStream_t stream);
 extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
 extern "C" hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
@@ -292,10 +293,13 @@ struct rtHipScene {
     size_t stageEventsUsed = 0;
     bool stageTiming = false;
     uint64_t roundsLast = 0;
-    // render passes (rtHipScenePasses): RT_HIP_PASS_* bits, and the pass buffer [slot][RT_PASS_WORDS][128*128] (rt_device.h) while any is on
+    // render passes (rtHipScenePasses): RT_HIP_PASS_* bits, the pass buffer [slot][RT_PASS_WORDS][128*128] (rt_device.h) while ALPHA,
+    // DEPTH or TRIANGLE is on, and the surface buffer [slot][RT_SURF_WORDS][128*128] while NORMAL or ALBEDO is on
     uint32_t passMask = 0;
     uint32_t *passBuf = nullptr;
     uint64_t passBytes = 0;
+    float *surfBuf = nullptr;
+    uint64_t surfBytes = 0;
     // ray queries through host arrays (rtHipSceneIntersect): one chunk of hits | rays | excluded ids on the device and a pinned host buffer
     // of the same layout from the staging pool, both made on first use
     uint32_t queryRays = 0;
@@ -982,6 +986,11 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
         }
         return 0;
     };
+    // NORMAL / ALBEDO on: the batch's samples are summed per pixel in the primary stage's bracket (the batch with sampleBase 0 starts
+    // the sums from zero, so planned and redone frames need no memset)
+    auto launch_surface = [&](rtHipScene::Group &G, hipStream_t on) {
+        return rtw_launch_surface_passes(&G.dev, &G.wf, sc->surfBuf + (size_t)G.slot0 * RT_SURF_WORDS * RT_TILE_PIXELS, on);
+    };
     uint64_t rounds = 0;
     bool anyPlannedBatch = false;
     const uint32_t sampleCount = sc->dev.sampleCount;
@@ -1008,9 +1017,13 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
                                                                (size_t)RT_TILE_PIXELS * 4, G.slot1 - G.slot0, on);
                         if (er != hipSuccess) return er;
                     }
-                    return rtw_launch_primary_passes(&G.dev, &G.wf, pass, on);
+                    const hipError_t er = rtw_launch_primary_passes(&G.dev, &G.wf, pass, on);
+                    return (er != hipSuccess || !sc->surfBuf) ? er : launch_surface(G, on);
                 }));
-            } else HIP_OK(stage(0, on, [&] { return rtw_launch_primary(&G.dev, &G.wf, on); }));
+            } else HIP_OK(stage(0, on, [&] {
+                const hipError_t er = rtw_launch_primary(&G.dev, &G.wf, on);
+                return (er != hipSuccess || !sc->surfBuf) ? er : launch_surface(G, on);
+            }));
             if (planned) {
                 while (G.rounds < planRounds)
                     if (issue_round(G, on) != 0) return -1;
@@ -1178,6 +1191,7 @@ void rtHipSceneDestroy(rtHipScene *sc)
     }
     if (sc->forkEvent) (void)hipEventDestroy(sc->forkEvent);
     if (sc->passBuf) (void)hipFree(sc->passBuf);
+    if (sc->surfBuf) (void)hipFree(sc->surfBuf);
     if (sc->queryDev) (void)hipFree(sc->queryDev);
     if (sc->queryHost) Stager::pool().give(sc->queryHost, sc->queryBytes);
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
@@ -1220,35 +1234,48 @@ int rtHipSetPipeline(rtHipScene *sc, int pipeline)
     return 0;
 }
 
-int rtHipScenePasses(rtHipScene *sc, cl_uint mask)
+// Which render pass bits need which buffer
+#define RT_PASS_BUF_BITS (RT_HIP_PASS_ALPHA | RT_HIP_PASS_DEPTH | RT_HIP_PASS_TRIANGLE)
+#define RT_SURF_BUF_BITS (RT_HIP_PASS_NORMAL | RT_HIP_PASS_ALBEDO)
+
+// One of the two pass buffers: made (zeroed) when `want` and absent, freed when not `want` -- after a sync, frames in flight may still
+// write it.  Counted in rtHipSceneBytes.
+static int keep_pass_buffer(rtHipScene *sc, bool want, void **buf, uint64_t &bytes, uint32_t words)
 {
-    if (!sc) return fail("null scene");
-    if (mask & ~(cl_uint)(RT_HIP_PASS_ALPHA | RT_HIP_PASS_DEPTH | RT_HIP_PASS_TRIANGLE)) return fail("unknown render pass bits 0x%x", mask);
-    if (mask && sc->pipeline == RT_HIP_PIPELINE_MEGAKERNEL) return fail("render passes need the wavefront pipeline (the scene is on the megakernel)");
-    HIP_OK(hipSetDevice(sc->device));
-    if (mask == 0) {
-        if (sc->passBuf) {
-            HIP_OK(hipDeviceSynchronize()); // (frames in flight may still write it)
-            HIP_OK(hipFree(sc->passBuf));
-            sc->bytes -= sc->passBytes;
-        }
-        sc->passBuf = nullptr;
-        sc->passBytes = 0;
-    } else if (!sc->passBuf) {
-        const uint64_t n = (uint64_t)sc->tileIds.size() * RT_PASS_WORDS * RT_TILE_PIXELS * 4;
+    if (!want && *buf) {
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipFree(*buf));
+        sc->bytes -= bytes;
+        *buf = nullptr;
+        bytes = 0;
+    } else if (want && !*buf) {
+        const uint64_t n = (uint64_t)sc->tileIds.size() * words * RT_TILE_PIXELS * 4;
         void *p = nullptr;
         HIP_OK(hipMalloc(&p, n ? n : 4));
         HIP_OK(hipMemset(p, 0, n ? n : 4));
-        sc->passBuf = (uint32_t *)p;
-        sc->passBytes = n ? n : 4;
-        sc->bytes += sc->passBytes;
+        *buf = p;
+        bytes = n ? n : 4;
+        sc->bytes += bytes;
     }
+    return 0;
+}
+
+int rtHipScenePasses(rtHipScene *sc, cl_uint mask)
+{
+    if (!sc) return fail("null scene");
+    if (mask & ~(cl_uint)(RT_PASS_BUF_BITS | RT_SURF_BUF_BITS)) return fail("unknown render pass bits 0x%x", mask);
+    if (mask && sc->pipeline == RT_HIP_PIPELINE_MEGAKERNEL) return fail("render passes need the wavefront pipeline (the scene is on the megakernel)");
+    HIP_OK(hipSetDevice(sc->device));
+    if (keep_pass_buffer(sc, (mask & RT_PASS_BUF_BITS) != 0, (void **)&sc->passBuf, sc->passBytes, RT_PASS_WORDS) != 0) return -1;
+    if (keep_pass_buffer(sc, (mask & RT_SURF_BUF_BITS) != 0, (void **)&sc->surfBuf, sc->surfBytes, RT_SURF_WORDS) != 0) return -1;
     sc->passMask = mask;
     return 0;
 }
 
 void *rtHipPassBuffer(rtHipScene *sc) { return sc ? (void *)sc->passBuf : nullptr; }
 uint64_t rtHipPassBufferBytes(const rtHipScene *sc) { return sc && sc->passBuf ? (uint64_t)sc->tileIds.size() * RT_PASS_WORDS * RT_TILE_PIXELS * 4 : 0; }
+void *rtHipSurfaceBuffer(rtHipScene *sc) { return sc ? (void *)sc->surfBuf : nullptr; }
+uint64_t rtHipSurfaceBufferBytes(const rtHipScene *sc) { return sc && sc->surfBuf ? (uint64_t)sc->tileIds.size() * RT_SURF_WORDS * RT_TILE_PIXELS * 4 : 0; }
 
 // Diagnostic: raw copy of the 8 device-side debug counters (work counters of the counted kernel, or the cycle sums of
 // an RT_DIAG_STAMPS build).  clear != 0 zeroes them afterwards.
@@ -1415,6 +1442,37 @@ int rtHipReadbackPasses(rtHipScene *sc, cl_ushort *alpha, cl_float *depth, cl_ui
                 if (depth) memcpy(&depth[at + i], &src[RT_PASS_DEPTH * RT_TILE_PIXELS + i], 4);
                 if (triangle) triangle[at + i] = src[RT_PASS_TRIANGLE * RT_TILE_PIXELS + i];
             }
+        }
+    }
+    return 0;
+}
+
+int rtHipReadbackSurfacePasses(rtHipScene *sc, cl_float *normal, cl_float *albedo)
+{
+    if (!sc) return fail("null scene");
+    if (normal && !(sc->passMask & RT_HIP_PASS_NORMAL)) return fail("the normal pass is not on for this scene (rtHipScenePasses)");
+    if (albedo && !(sc->passMask & RT_HIP_PASS_ALBEDO)) return fail("the albedo pass is not on for this scene (rtHipScenePasses)");
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    if (!normal && !albedo) return 0;
+    const size_t nt = sc->tileIds.size();
+    std::vector<float> host(nt * RT_SURF_WORDS * RT_TILE_PIXELS);
+    HIP_OK(hipMemcpy(host.data(), sc->surfBuf, host.size() * 4, hipMemcpyDeviceToHost));
+    const float S = (float)sc->dev.sampleCount; // the buffer holds sums in sample order; the means are taken here, in fp32
+    for (size_t s = 0; s < nt; ++s) {
+        const uint32_t tx = sc->tileIds[s] % sc->tilesX, ty = sc->tileIds[s] / sc->tilesX;
+        const uint32_t n = std::min<uint32_t>(RT_TILE, sc->width - tx * RT_TILE);
+        for (uint32_t ly = 0; ly < RT_TILE; ++ly) {
+            const uint32_t gy = ty * RT_TILE + ly;
+            if (gy >= sc->height) break;
+            const float *src = host.data() + s * RT_SURF_WORDS * RT_TILE_PIXELS + ly * RT_TILE;
+            const size_t at = (size_t)gy * sc->width + tx * RT_TILE;
+            for (uint32_t i = 0; i < n; ++i)
+                for (int c = 0; c < 3; ++c) {
+                    if (normal) normal[3 * (at + i) + c] = src[(RT_SURF_NORMAL + c) * RT_TILE_PIXELS + i] / S;
+                    if (albedo) albedo[3 * (at + i) + c] = src[(RT_SURF_ALBEDO + c) * RT_TILE_PIXELS + i] / S;
+                }
         }
     }
     return 0;

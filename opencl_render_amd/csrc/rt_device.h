@@ -30,6 +30,11 @@
 #define RT_PASS_DEPTH 1
 #define RT_PASS_TRIANGLE 2
 #define RT_PASS_WORDS 3
+//  surfBuf  [slot][RT_SURF_WORDS][128*128] f32 (only when the NORMAL or ALBEDO pass is on; not part of RtDevScene): per pixel the
+//           running sums over its samples, in sample order, of the primary hit's shading normal (x, y, z) and albedo (r, g, b)
+#define RT_SURF_NORMAL 0
+#define RT_SURF_ALBEDO 3
+#define RT_SURF_WORDS 6
 enum { RT_PATH_CLASS_GENERAL = 0, RT_PATH_CLASS_OPAQUE_DIFFUSE = 1 };
 struct RtDevScene {
     // camera (raytrace.h:61-66)

@@ -1,6 +1,6 @@
 // rt_fileio.cpp -- file input of the headless front-end (include/raytrace_hip.h, section 3): Wavefront OBJ / MTL meshes and
 // PPM / BMP images, and the projected UVs of the reference's ShdProjectPoint.
-// It also holds the sinks of the render passes (PGM of the alpha pass, PFM of the depth pass).
+// It also holds the sinks of the render passes (PGM of the alpha pass, PFM of the depth pass, colour PFM of the normal and albedo passes).
 //
 // The reference takes its geometry from Cinema 4D's object tree (source/render.cpp:707-1003) and its textures from C4D bitmaps
 // (render.cpp:1136-1309); neither exists without the SDK.  What a host without Cinema 4D has is files: this reader turns an OBJ
@@ -402,6 +402,26 @@ int rtHipWritePfm(const char *path, cl_uint width, cl_uint height, const cl_floa
     FILE *f = std::fopen(path, "wb");
     if (!f) return -4;
     bool ok = std::fprintf(f, "Pf\n%u %u\n-1.0\n", width, height) > 0;
+    ok = ok && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? 0 : -4;
+}
+
+// PFM: a width x height x 3 f32 image, colour ("PF"), the same byte layout with three floats per pixel (the surface passes).
+int rtHipWritePfmRgb(const char *path, cl_uint width, cl_uint height, const cl_float *rgb)
+{
+    if (!path || !rgb || width == 0 || height == 0) return -1;
+    std::vector<cl_uchar> bytes((size_t)width * height * 12);
+    size_t at = 0;
+    for (cl_uint row = height; row-- > 0;)
+        for (size_t i = (size_t)row * width * 3; i < ((size_t)row + 1) * width * 3; ++i) {
+            uint32_t v;
+            std::memcpy(&v, &rgb[i], 4);
+            for (int k = 0; k < 4; ++k) bytes[at++] = (cl_uchar)(v >> (8 * k));
+        }
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return -4;
+    bool ok = std::fprintf(f, "PF\n%u %u\n-1.0\n", width, height) > 0;
     ok = ok && std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
     ok = (std::fclose(f) == 0) && ok;
     return ok ? 0 : -4;

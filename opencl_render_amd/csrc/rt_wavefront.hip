@@ -266,6 +266,65 @@ __global__ __launch_bounds__(256) void wf_primary_passes_kernel(const RtDevScene
     wf_primary_body<true>(S, W, passBuf);
 }
 
+// ---- surface passes: shading normal and albedo, summed over a pixel's samples (RT_HIP_PASS_NORMAL | RT_HIP_PASS_ALBEDO) -------------
+// grid = tileCount*64; workgroup = 16x16 pixel patch, wave = 8x8 quadrant, as wf_primary -- but ONE thread per pixel, which walks the
+// batch's samples in order.  Each sample's primary hit is derived again (generator, direction and camera scan of wf_primary_body) and
+// shaded as SHADE_BEGIN shades it (raytrace_opencl.c:548, :554): n = shading_normal, albedo = the colour channel's texel, both zero on a
+// miss or for material -1.  They are added into the pixel's six f32 sums (rt_device.h, surfBuf).  The batch with sampleBase 0 starts
+// from +0 instead of reading the buffer; later batches of the frame follow on the same stream, so every sum is taken in sample order
+// s = 1..S without atomics.  (The samples of a pixel sit in different workgroups of wf_primary and in different paths of the logic
+// kernel: summing them in order there would need per-sample staging.)
+__global__ __launch_bounds__(256) void wf_surface_passes_kernel(const RtDevScene S, const RtWavefront W, float *surfBuf)
+{
+    __shared__ Shared sh; // as every kernel that shades sets it up
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) (&sh.planes[0][0])[i] = S.boxMin[i];
+    sh.unit255[threadIdx.x] = (float)threadIdx.x / 255.f;
+    __syncthreads();
+    const uint32_t slot = blockIdx.x >> 6, patch = blockIdx.x & 63;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lx = (patch & 7) * RT_PATCH + (wave & 1) * 8 + (lane & 7);
+    const uint32_t ly = (patch >> 3) * RT_PATCH + (wave >> 1) * 8 + (lane >> 3);
+    const uint32_t tile = S.tileIds[slot];
+    const uint32_t gx = (tile % S.tilesX) * RT_TILE + lx;
+    const uint32_t gy = (tile / S.tilesX) * RT_TILE + ly;
+    if (gx >= S.width || gy >= S.height) return;
+
+    const uint32_t localPixel = slot * RT_TILE_PIXELS + ly * RT_TILE + lx;
+    float *sums = surfBuf + (size_t)slot * RT_SURF_WORDS * RT_TILE_PIXELS + ly * RT_TILE + lx;
+    float acc[RT_SURF_WORDS];
+#pragma unroll
+    for (int k = 0; k < RT_SURF_WORDS; ++k) acc[k] = W.sampleBase == 0u ? 0.f : sums[k * RT_TILE_PIXELS];
+    const uint32_t pixel = gy * S.width + gx;
+    const V3 eye = ld3(S.eye), lr = ld3(S.lr), tb = ld3(S.tb), topLeft = ld3(S.topLeft);
+    Counters cn; // unused (COUNT=false)
+    for (uint32_t sb = 0; sb < W.samplesInBatch; ++sb) {
+        uint64_t rng = (uint64_t)pixel * (uint64_t)S.sampleCount + (uint64_t)(W.sampleBase + sb + 1); // :481
+        V3 dir = topLeft;
+        float k = (float)gx + rand01(rng); // LR jitter first, then TB (:496-503)
+        dir.x += lr.x * k; dir.y += lr.y * k; dir.z += lr.z * k;
+        k = (float)gy + rand01(rng);
+        dir.x += tb.x * k; dir.y += tb.y * k; dir.z += tb.z * k;
+        float hit_t = 0.f, hit_l1 = 0.f, hit_l2 = 0.f;
+        const uint32_t hit_tri = camera_scan(S, localPixel, eye, dir, 0.f, RT_INF, RT_NONE, hit_t, hit_l1, hit_l2);
+        V3 n = mk(0.f, 0.f, 0.f), albedo = mk(0.f, 0.f, 0.f);
+        if (hit_tri != RT_NONE) {
+            const float *shade = S.triShade + 24 * (size_t)hit_tri;
+            const int m = __float_as_int(shade[21]);
+            const V3 where = along(eye, hit_t, dir);
+            MatRec mat;
+            mat.desc[0] = mat.desc[1] = mat.desc[2] = mat.desc[3] = mat.desc[4] = 0u; mat.m = m;
+            if (0 <= m) mat = load_mat(S, m);
+            n = shading_normal<false>(S, sh, where, eye, dir, hit_tri, hit_l1, hit_l2, shade, m, cn, &mat);
+            uint32_t raw;
+            if (0 <= m && mat.desc[CH_COLOR]) albedo = texel_rec<false>(S, sh, mat, CH_COLOR, shade + 15, hit_l1, hit_l2, raw, cn);
+        }
+        acc[RT_SURF_NORMAL + 0] += n.x; acc[RT_SURF_NORMAL + 1] += n.y; acc[RT_SURF_NORMAL + 2] += n.z;
+        acc[RT_SURF_ALBEDO + 0] += albedo.x; acc[RT_SURF_ALBEDO + 1] += albedo.y; acc[RT_SURF_ALBEDO + 2] += albedo.z;
+    }
+#pragma unroll
+    for (int k = 0; k < RT_SURF_WORDS; ++k) sums[k * RT_TILE_PIXELS] = acc[k];
+}
+
 // ---- trace entries: the DDA start state of a ray, and exact segments ------------------------------------------------
 // A round lasts as long as its longest dependent chain: a ray that crosses the whole grid makes 766 cell visits one after
 // the other, and measured round times are ~0.4 ms + 0.32 ms per million rays -- the constant is that chain.  The walk is a
@@ -2131,6 +2190,14 @@ extern "C" hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const R
 {
     if (scene->tileCount == 0) return hipSuccess;
     hipLaunchKernelGGL(wf_primary_passes_kernel, dim3(scene->tileCount * 64, wf->samplesInBatch), dim3(256), 0, stream, *scene, *wf, passBuf);
+    return hipGetLastError();
+}
+
+// surfBuf: this tile group's slice of the surface buffer (rt_device.h, RT_SURF_*); the batch with sampleBase 0 overwrites it
+extern "C" hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const RtWavefront *wf, float *surfBuf, hipStream_t stream)
+{
+    if (scene->tileCount == 0) return hipSuccess;
+    hipLaunchKernelGGL(wf_surface_passes_kernel, dim3(scene->tileCount * 64), dim3(256), 0, stream, *scene, *wf, surfBuf);
     return hipGetLastError();
 }
 

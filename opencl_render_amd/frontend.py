@@ -63,6 +63,7 @@ def _lib():
         L.rtHipWritePpm.argtypes = [C.c_char_p, u32, u32, vp, vp, vp]
         L.rtHipWritePgm.argtypes = [C.c_char_p, u32, u32, vp]
         L.rtHipWritePfm.argtypes = [C.c_char_p, u32, u32, vp]
+        L.rtHipWritePfmRgb.argtypes = [C.c_char_p, u32, u32, vp]
         L.rtHipObjRead.argtypes = [C.c_char_p, C.POINTER(_ObjData)]
         L.rtHipObjFree.restype = None
         L.rtHipObjFree.argtypes = [C.POINTER(_ObjData)]
@@ -316,6 +317,17 @@ def write_pfm(path: str, depth) -> None:
     rc = _lib().rtHipWritePfm(path.encode(), w, h, _p(plane))
     if rc != 0:
         raise OSError(f"rtHipWritePfm({path}) failed ({rc})")
+
+
+def write_pfm_rgb(path: str, image) -> None:
+    """[H,W,3] f32 image (the normal or albedo pass) -> colour PFM, little-endian (scale -1.0), bottom row first."""
+    h, w, c = image.shape
+    if c != 3:
+        raise ValueError(f"write_pfm_rgb: expected an [H, W, 3] image, got {image.shape}")
+    rgb = np.ascontiguousarray(image, np.float32)
+    rc = _lib().rtHipWritePfmRgb(path.encode(), w, h, _p(rgb))
+    if rc != 0:
+        raise OSError(f"rtHipWritePfmRgb({path}) failed ({rc})")
 
 
 def write_ppm(path: str, r, g, b) -> None:

@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RT_HIP_LIB") or os.path.join(_HERE, "libraytrace_hip.so")
 TILE = 128
 PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT = 0, 1
-PASS_ALPHA, PASS_DEPTH, PASS_TRIANGLE = 1, 2, 4  # RT_HIP_PASS_*
+PASS_ALPHA, PASS_DEPTH, PASS_TRIANGLE, PASS_NORMAL, PASS_ALBEDO = 1, 2, 4, 8, 16  # RT_HIP_PASS_*
 
 
 class Float3(C.Structure):  # cl_float3 == cl_float4: 16 bytes, passed as two SSE eightbytes on SysV
@@ -76,11 +76,12 @@ RESIDENT_SYMBOLS = [
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
+    "rtHipSurfaceBuffer", "rtHipSurfaceBufferBytes", "rtHipReadbackSurfacePasses",
     "rtHipSceneIntersect", "rtHipSceneIntersectDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat",
-    "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm",
+    "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm", "rtHipWritePfmRgb",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
 
@@ -164,6 +165,11 @@ def lib() -> C.CDLL:
     L.rtHipPassBufferBytes.restype = u64
     L.rtHipPassBufferBytes.argtypes = [vp]
     L.rtHipReadbackPasses.argtypes = [vp, vp, vp, vp]
+    L.rtHipSurfaceBuffer.restype = vp
+    L.rtHipSurfaceBuffer.argtypes = [vp]
+    L.rtHipSurfaceBufferBytes.restype = u64
+    L.rtHipSurfaceBufferBytes.argtypes = [vp]
+    L.rtHipReadbackSurfacePasses.argtypes = [vp, vp, vp]
     L.rtHipSceneIntersect.argtypes = [vp, vp, vp, u32, vp]
     L.rtHipSceneIntersectDevice.argtypes = [vp, vp, vp, u32, vp, vp]
     L.rtHipKernelTime.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
@@ -529,18 +535,24 @@ class ResidentScene:
         self._check(lib().rtHipReadback(self.handle, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2])), "rtHipReadback")
         return planes
 
-    def set_passes(self, alpha: bool = False, depth: bool = False, triangle: bool = False):
-        """Render passes from the next frame on (rtHipScenePasses); all off frees the pass buffer."""
+    def set_passes(self, alpha: bool = False, depth: bool = False, triangle: bool = False, normal: bool = False, albedo: bool = False):
+        """Render passes from the next frame on (rtHipScenePasses); a buffer whose passes are all off is freed."""
         mask = (PASS_ALPHA if alpha else 0) | (PASS_DEPTH if depth else 0) | (PASS_TRIANGLE if triangle else 0)
+        mask |= (PASS_NORMAL if normal else 0) | (PASS_ALBEDO if albedo else 0)
         self._check(lib().rtHipScenePasses(self.handle, mask), "rtHipScenePasses")
         self.passes = mask
 
     def pass_buffer(self):
         return lib().rtHipPassBuffer(self.handle), lib().rtHipPassBufferBytes(self.handle)
 
+    def surface_buffer(self):
+        """The NORMAL / ALBEDO sums on the device ([slot][nx ny nz ar ag ab][128*128] f32), and their size; (None, 0) while both are off."""
+        return lib().rtHipSurfaceBuffer(self.handle), lib().rtHipSurfaceBufferBytes(self.handle)
+
     def readback_passes(self, out: Optional[dict] = None) -> dict:
         """The passes that are on, as [H, W] arrays: alpha u16, depth f32, triangle u32, and with triangle also material i32
-        (-1 on a miss) and -- for a scene made by frontend.scene_from_meshes -- mesh i32 (-1 on a miss).  `out`: arrays of an earlier
+        (-1 on a miss) and -- for a scene made by frontend.scene_from_meshes -- mesh i32 (-1 on a miss); normal and albedo as [H, W, 3]
+        f32, the means over the pixel's samples.  `out`: arrays of an earlier
         call (another instance's tiles) to store this instance's tiles into; pixels of other tiles keep their values."""
         sc = self.scene
         mask = getattr(self, "passes", 0)
@@ -553,11 +565,19 @@ class ResidentScene:
             out.setdefault("depth", np.full(shape, np.inf, np.float32))
         if mask & PASS_TRIANGLE:
             out.setdefault("triangle", np.full(shape, 0xFFFFFFFF, np.uint32))
-        for k, dt in (("alpha", np.uint16), ("depth", np.float32), ("triangle", np.uint32)):
-            if k in out and (out[k].dtype != dt or out[k].shape != shape or not out[k].flags.c_contiguous):
-                raise ValueError(f"readback_passes: out[{k!r}] must be a C-contiguous {shape} {np.dtype(dt).name} array")
+        if mask & PASS_NORMAL:
+            out.setdefault("normal", np.zeros(shape + (3,), np.float32))
+        if mask & PASS_ALBEDO:
+            out.setdefault("albedo", np.zeros(shape + (3,), np.float32))
+        for k, dt, shp in (("alpha", np.uint16, shape), ("depth", np.float32, shape), ("triangle", np.uint32, shape),
+                           ("normal", np.float32, shape + (3,)), ("albedo", np.float32, shape + (3,))):
+            if k in out and (out[k].dtype != dt or out[k].shape != shp or not out[k].flags.c_contiguous):
+                raise ValueError(f"readback_passes: out[{k!r}] must be a C-contiguous {shp} {np.dtype(dt).name} array")
         self._check(lib().rtHipReadbackPasses(self.handle, _ptr(out.get("alpha")), _ptr(out.get("depth")), _ptr(out.get("triangle"))),
                     "rtHipReadbackPasses")
+        if mask & (PASS_NORMAL | PASS_ALBEDO):
+            self._check(lib().rtHipReadbackSurfacePasses(self.handle, _ptr(out.get("normal")), _ptr(out.get("albedo"))),
+                        "rtHipReadbackSurfacePasses")
         if "triangle" in out:
             tri = out["triangle"]
             hit = tri != 0xFFFFFFFF

@@ -1,0 +1,80 @@
+"""Do two source trees compile to the same GPU code?  Compiles every .hip file of opencl_render_amd/csrc in both trees for gfx950 (device
+code only, the Makefile's DEVFLAGS), disassembles the code objects with llvm-objdump and compares them symbol by symbol (kernels and the device functions not inlined).  The address
+comments llvm-objdump prints are dropped; the instruction text, relative branch offsets included, is compared.  Needs no GPU.
+
+    python scripts/kernel_disasm_diff.py --base /path/to/parent/checkout [--new .] [--keep DIR]
+
+Prints per source file the symbols that are identical, changed, removed and added, and exits 1 if any existing symbol changed or went.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCES = ("rt_kernels", "rt_wavefront", "rt_build_device", "rt_kat", "rt_scene_prep")
+
+
+def devflags(tree):
+    text = open(os.path.join(tree, "opencl_render_amd", "csrc", "Makefile")).read().replace("\\\n", " ")
+    m = re.search(r"^DEVFLAGS\s*:=(.*)$", text, re.M)
+    return m.group(1).replace("$(ARCH)", "gfx950").split()
+
+
+def disassemble(tree, out, rocm):
+    csrc = os.path.join(tree, "opencl_render_amd", "csrc")
+    kernels = {}
+    for name in SOURCES:
+        co = os.path.join(out, name + ".co")
+        subprocess.run([os.path.join(rocm, "bin", "hipcc")] + devflags(tree) + ["-I" + os.path.join(tree, "include"), "-I" + csrc,
+                       "--cuda-device-only", "--no-gpu-bundle-output", "-c", os.path.join(csrc, name + ".hip"), "-o", co], check=True)
+        dis = subprocess.run([os.path.join(rocm, "llvm", "bin", "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr", co],
+                             check=True, capture_output=True, text=True).stdout
+        body, cur = {}, None
+        for line in dis.splitlines():
+            m = re.match(r"^<(.+)>:$", line.strip())
+            if m:
+                cur = m.group(1)
+                body[cur] = []
+            elif cur is not None and line.strip():
+                body[cur].append(re.sub(r"\s*//.*$", "", line).strip())
+        kernels[name] = body
+    return kernels
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--base", required=True, help="root of the tree to compare against (e.g. a checkout of the parent commit)")
+    ap.add_argument("--new", default=ROOT, help="root of the tree under review (default: this one)")
+    ap.add_argument("--keep", help="keep the code objects here (default: a temporary directory)")
+    ap.add_argument("--rocm", default=os.environ.get("ROCM_PATH", "/opt/rocm"))
+    args = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        keep = args.keep or tmp
+        os.makedirs(os.path.join(keep, "base"), exist_ok=True)
+        os.makedirs(os.path.join(keep, "new"), exist_ok=True)
+        a = disassemble(args.base, os.path.join(keep, "base"), args.rocm)
+        b = disassemble(args.new, os.path.join(keep, "new"), args.rocm)
+    bad = False
+    for name in SOURCES:
+        ka, kb = a[name], b[name]
+        same = [k for k in ka if k in kb and ka[k] == kb[k]]
+        changed = [k for k in ka if k in kb and ka[k] != kb[k]]
+        gone = [k for k in ka if k not in kb]
+        added = [k for k in kb if k not in ka]
+        print(f"{name}.hip: {len(ka)} symbols before, {len(kb)} after: {len(same)} identical, {len(changed)} changed, {len(gone)} removed, "
+              f"{len(added)} added")
+        for k in changed:
+            print(f"  changed  {k} ({len(ka[k])} -> {len(kb[k])} instructions)")
+        for k in gone:
+            print(f"  removed  {k}")
+        for k in added:
+            print(f"  added    {k} ({len(kb[k])} instructions)")
+        bad = bad or bool(changed or gone)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
