@@ -334,6 +334,59 @@ int rtHipSceneIntersect(rtHipScene *scene, const rtHipRay *rays, const cl_uint *
  * launches nothing.  count == 0 returns 0 and launches nothing. */
 int rtHipSceneIntersectDevice(rtHipScene *scene, const void *rays, const void *excluded, cl_uint count, void *hits, void *stream);
 
+/* DENOISER: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the normal and albedo passes.  K iterations of a
+ * 5x5 B3-spline stencil dilated by h = 2^i; a tap's weight falls off across normal, albedo and colour edges.  The arithmetic is IEEE fp32
+ * + - * /, sqrt and compares only (no transcendental, no FMA, divisions and square roots correctly rounded): tests/denoise_oracle.py
+ * restates it in numpy and the device output equals it bit for bit.
+ *
+ * Inputs: W x H pixels, row-major, 3 x f32 interleaved per pixel: colour c, normal n, albedo a.
+ * Parameters: iterations K in 0..12, colourInvSigma2 ic and albedoInvSigma2 ia finite and >= 0, normalPowerLog2 E in 0..10; also
+ * ic * 4^(K-1) (computed as below) must be finite.  Anything else returns -1 before anything is launched.
+ * Guides, once per call, per pixel: m = (nx*nx + ny*ny) + nz*nz; if m > 0: r = sqrt(m), n^ = (nx/r, ny/r, nz/r), z = false; otherwise
+ * (zero, underflow, NaN) n^ = (0,0,0), z = true.
+ * Iteration i = 0..K-1 reads C^i (C^0 = c) and writes C^(i+1); h = 2^i; ic_i = ic multiplied by 4.0f i times in fp32;
+ * B = {1/16, 1/4, 3/8, 1/4, 1/16}.  For pixel p = (x, y), taps j = 0..4 (rows, outer) and k = 0..4 (columns, inner) at
+ * q = (x + (k-2)h, y + (j-2)h); taps outside the image are skipped.  Per tap, in this order:
+ *   dc = (dr*dr + dg*dg) + db*db with d = C^i_p - C^i_q;  da = the same on the albedo;
+ *   wn = 1 if z_p and z_q, else d = (n^p.x*n^q.x + n^p.y*n^q.y) + n^p.z*n^q.z, d = (d > 0 ? d : 0), d = d*d repeated E times, wn = d;
+ *   w = ((B[j]*B[k]) * wn) / ((1 + dc*ic_i) * (1 + da*ia));
+ *   sw += w;  s_c += w * C^i_q per component (the sums start at +0.0f and add in tap order).
+ * C^(i+1)_p = s_c / sw if sw > 0, else C^i_p.  The output is C^K (K = 0 copies the colour bit for bit).
+ * Non-finite inputs give unspecified values but never an access out of range. */
+typedef struct rtHipDenoiseParams {
+    cl_uint  iterations;      /* K */
+    cl_float colourInvSigma2; /* ic */
+    cl_float albedoInvSigma2; /* ia */
+    cl_uint  normalPowerLog2; /* E: the normal weight is max(dot, 0)^(2^E) */
+} rtHipDenoiseParams;
+/* K = 4, ic = 4, ia = 100, E = 7 ("Denoiser", says why). */
+void     rtHipDenoiseDefaults(rtHipDenoiseParams *params);
+/* Device scratch rtHipDenoiseDevice needs for a W x H image (16-byte aligned): two float4 colour buffers and the packed guides, 64 B per
+ * pixel.  0 for a size rtHipDenoiseDevice refuses. */
+uint64_t rtHipDenoiseScratchBytes(cl_uint width, cl_uint height);
+/* DEVICE arrays of `device`, asynchronous on `stream` (a hipStream_t of `device` as void*; NULL = the null stream): no allocation, no
+ * synchronisation.  colour, normal, albedo and out hold W x H x 3 f32 (4-byte aligned), scratch at least rtHipDenoiseScratchBytes
+ * (16-byte aligned).  Every pointer is checked first like rtHipSceneIntersectDevice's (device memory of `device`, the whole range inside
+ * one allocation); a non-NULL stream must belong to `device` (hipStreamGetDevice); out and scratch must not overlap each other nor any
+ * input; W, H >= 1 and W*H <= 2^27.  Anything else returns -1 with
+ * the last-error text set and launches nothing. */
+int rtHipDenoiseDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *normal, const void *albedo, void *out,
+                       void *scratch, uint64_t scratchBytes, const rtHipDenoiseParams *params, void *stream);
+/* HOST arrays, synchronous; device memory is allocated and freed per call.  Same checks and results as rtHipDenoiseDevice. */
+int rtHipDenoise(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *normal, const cl_float *albedo,
+                 cl_float *out, const rtHipDenoiseParams *params);
+/* The scene's last frame, denoised on its device without a host round trip: colour = (float)u16 / 65535.0f of the beauty planes, normal
+ * and albedo = sum / (float)S, exactly what rtHipReadback and rtHipReadbackSurfacePasses give.  Needs RT_HIP_PASS_NORMAL |
+ * RT_HIP_PASS_ALBEDO on and a tile set that holds every tile of the image once; otherwise -1.  Synchronises and finishes the frame like
+ * rtHipReadback.  Outputs (each may be NULL, host arrays): outRgb W x H x 3 f32 = C^K, and u16 planes R, G, B with v = C * 65535.0f,
+ * u = !(v > 0) ? 0 : (v >= 65534.5f ? 65535 : (u16)(v + 0.5f)).  The scratch belongs to the scene: made on first use, counted in
+ * rtHipSceneBytes, freed with the scene or when the surface passes go off.  The tile and surface buffers are not changed. */
+int rtHipSceneDenoise(rtHipScene *scene, const rtHipDenoiseParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG,
+                      cl_ushort *outB);
+/* Device time in milliseconds of the scene's last rtHipSceneDenoise call, from HIP events on the scene's stream: ms[0] the gather, ms[1] the
+ * guide prologue, ms[2] the K iterations and the output kernel.  All 0 before the first call.  Returns 0, or -1 for a NULL argument. */
+int rtHipSceneDenoiseTimes(const rtHipScene *scene, cl_float *ms);
+
 /* Average device time in milliseconds of one rtHipRenderTiles frame (all its kernels) over the frames recorded since
  * the last call (HIP events on the launch stream), and the number of frames.  Returns 0 on success. */
 int rtHipKernelTime(rtHipScene *scene, double *avgMs, uint64_t *launches);

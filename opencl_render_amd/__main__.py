@@ -10,6 +10,11 @@ also writes the render passes: PREFIX_alpha.pgm (coverage), PREFIX_depth.pfm (ey
 (triangle, material and mesh ids of sample 1's hit; -1 -- 0xffffffff for the triangle -- where it missed).  With
 ``--surface-passes`` it also writes PREFIX_normal.pfm and PREFIX_albedo.pfm (colour PFMs of the shading normal and the albedo at the
 primary hit, means over the pixel's samples: a denoiser's auxiliary images).
+
+``--denoise PATH`` renders through the resident layer with the normal and albedo passes on and writes the frame denoised by the
+built-in edge-aware filter (include/raytrace_hip.h, "DENOISER", default parameters) to PATH: .bmp / .ppm (u16 planes) or .pfm (the
+f32 colour).  ``--out`` is still the noisy beauty.  For the all-GPUs device the instances' read-backs are composed on the host and
+denoised with rtHipDenoise on device 0.
 """
 import argparse
 import sys
@@ -35,6 +40,7 @@ def parser():
     ap.add_argument("--low-byte-compat", action="store_true", help="BMP only: keep the low byte of every u16 like the reference's writebmp3s")
     ap.add_argument("--passes", metavar="PREFIX", help="also write PREFIX_alpha.pgm, PREFIX_depth.pfm and PREFIX_ids.npz (render passes)")
     ap.add_argument("--surface-passes", action="store_true", help="with --passes: also write PREFIX_normal.pfm and PREFIX_albedo.pfm")
+    ap.add_argument("--denoise", metavar="PATH", help="also write the denoised frame to PATH (.bmp, .ppm or .pfm)")
     return ap
 
 
@@ -43,13 +49,17 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.surface_passes and not args.passes:
         ap.error("--surface-passes needs --passes PREFIX")
+    if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
+        ap.error("--denoise PATH must end in .bmp, .ppm or .pfm")
     return args
 
 
-def render_passes(sc, device: int, gpus: int, surface: bool = False):
-    """The frame through ResidentScene with the alpha, depth and triangle passes on (and normal and albedo with `surface`): computation
-    type `device` (1..gpus = one GPU, gpus + 1 = all of them, one instance per GPU over raytrace.tiles_of_rank).  Returns the R, G, B
-    planes and readback_passes' dict."""
+def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool = True, denoise: bool = False):
+    """The frame through ResidentScene with the alpha, depth and triangle passes on (with `basic`) and normal and albedo (with `surface`
+    or `denoise`): computation type `device` (1..gpus = one GPU, gpus + 1 = all of them, one instance per GPU over
+    raytrace.tiles_of_rank).  Returns the R, G, B planes and readback_passes' dict; with `denoise` the dict also holds "denoised", what
+    ResidentScene.denoise returns (default parameters) -- for several instances their read-backs composed and run through
+    raytrace.denoise on device 0."""
     from . import raytrace
     world = gpus if device == gpus + 1 else 1
     instances = []
@@ -58,7 +68,7 @@ def render_passes(sc, device: int, gpus: int, surface: bool = False):
             tiles = raytrace.tiles_of_rank(sc.width, sc.height, rank, world) if world > 1 else None
             rs = raytrace.ResidentScene(sc, rank if world > 1 else device - 1, tiles, like=instances[0] if instances else None)
             instances.append(rs)
-            rs.set_passes(alpha=True, depth=True, triangle=True, normal=surface, albedo=surface)
+            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface or denoise, albedo=surface or denoise)
         for rs in instances:
             rs.render()
         planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
@@ -66,10 +76,16 @@ def render_passes(sc, device: int, gpus: int, surface: bool = False):
         for rs in instances:  # disjoint tiles: the planes add up, the passes are stored tile by tile
             rs.readback(planes)
             passes = rs.readback_passes(passes)
+        if denoise and world == 1:
+            passes["denoised"] = instances[0].denoise()
     finally:
         for rs in instances:
             rs.close()
-    if "mesh" not in passes:  # a scene not made of front-end meshes: all of it counts as mesh 0
+    if denoise and world > 1:
+        colour = np.stack(planes, -1).reshape(sc.height, sc.width, 3).astype(np.float32) / np.float32(65535.0)
+        out = raytrace.denoise(colour, passes["normal"], passes["albedo"], device=0)
+        passes["denoised"] = {"colour": out, "planes": raytrace.quantise(out)}
+    if "triangle" in passes and "mesh" not in passes:  # a scene not made of front-end meshes: all of it counts as mesh 0
         passes["mesh"] = np.where(passes["triangle"] != 0xFFFFFFFF, 0, -1).astype(np.int32)
     return [p.reshape(sc.height, sc.width) for p in planes], passes
 
@@ -100,8 +116,9 @@ def main(argv=None):
     cam_ms = raytrace.build_camera_list_device(sc, 0)
     grid_ms = raytrace.build_scene_grid_device(sc, 0)
     t2 = time.perf_counter()
-    if args.passes:
-        (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount(), surface=args.surface_passes)
+    if args.passes or args.denoise:
+        (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount(), surface=args.surface_passes,
+                                          basic=bool(args.passes), denoise=bool(args.denoise))
         ok = True
     else:
         ok, r, g, b = raytrace.raytrace_all(args.device, sc)
@@ -115,6 +132,14 @@ def main(argv=None):
         if args.surface_passes:
             frontend.write_pfm_rgb(args.passes + "_normal.pfm", passes["normal"])
             frontend.write_pfm_rgb(args.passes + "_albedo.pfm", passes["albedo"])
+    if args.denoise:
+        den = passes["denoised"]
+        if args.denoise.lower().endswith(".pfm"):
+            frontend.write_pfm_rgb(args.denoise, den["colour"])
+        elif args.denoise.lower().endswith(".ppm"):
+            frontend.write_ppm(args.denoise, *den["planes"])
+        else:
+            frontend.write_bmp(args.denoise, *den["planes"], low_byte_compat=args.low_byte_compat)
     if args.out.lower().endswith(".ppm"):
         frontend.write_ppm(args.out, r, g, b)
     else:
@@ -122,7 +147,7 @@ def main(argv=None):
     rays = args.width * args.height * args.samples
     print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel -> {args.out}\n"
           f"  scene {1e3 * (t1 - t0):.0f} ms, lists on the device {1e3 * (t2 - t1):.0f} ms (kernels {cam_ms:.1f} + {grid_ms:.1f} ms), "
-          f"{'resident render + passes' if args.passes else 'RaytraceAll'} {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
+          f"{'resident render + passes' if args.passes or args.denoise else 'RaytraceAll'} {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
     return 0
 
 

@@ -50,6 +50,14 @@ extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefron
 extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
                                        uint32_t fastQuotient, hipStream_t stream);
 
+extern "C" hipError_t rtd_launch_guides(uint32_t n, const float *colour, const float *normal, const float *albedo, void *c0, void *g0, void *g1,
+                                        hipStream_t stream);
+extern "C" hipError_t rtd_launch_iteration(uint32_t W, uint32_t H, int h, float ic, float ia, uint32_t E, const void *cin, const void *g0,
+                                           const void *g1, void *cout, hipStream_t stream);
+extern "C" hipError_t rtd_launch_output(uint32_t n, const void *c, float *out, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
+extern "C" hipError_t rtd_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount, const uint16_t *tileBuf,
+                                        const float *surf, float S, float *colour, float *normal, float *albedo, hipStream_t stream);
+
 namespace {
 
 thread_local std::string g_error;
@@ -305,6 +313,12 @@ struct rtHipScene {
     uint32_t queryRays = 0;
     char *queryDev = nullptr, *queryHost = nullptr;
     uint64_t queryBytes = 0;
+    // denoiser scratch of rtHipSceneDenoise (gathered inputs, filter scratch, outputs), made on first use while NORMAL and ALBEDO are on
+    char *denoiseBuf = nullptr;
+    uint64_t denoiseBytes = 0;
+    // device time of the last rtHipSceneDenoise: events before the gather, after it, after the guides and after the output
+    hipEvent_t denoiseEv[4] = {};
+    float denoiseMs[3] = {};
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -1192,6 +1206,9 @@ void rtHipSceneDestroy(rtHipScene *sc)
     if (sc->forkEvent) (void)hipEventDestroy(sc->forkEvent);
     if (sc->passBuf) (void)hipFree(sc->passBuf);
     if (sc->surfBuf) (void)hipFree(sc->surfBuf);
+    if (sc->denoiseBuf) (void)hipFree(sc->denoiseBuf);
+    for (hipEvent_t e : sc->denoiseEv)
+        if (e) (void)hipEventDestroy(e);
     if (sc->queryDev) (void)hipFree(sc->queryDev);
     if (sc->queryHost) Stager::pool().give(sc->queryHost, sc->queryBytes);
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
@@ -1268,6 +1285,13 @@ int rtHipScenePasses(rtHipScene *sc, cl_uint mask)
     HIP_OK(hipSetDevice(sc->device));
     if (keep_pass_buffer(sc, (mask & RT_PASS_BUF_BITS) != 0, (void **)&sc->passBuf, sc->passBytes, RT_PASS_WORDS) != 0) return -1;
     if (keep_pass_buffer(sc, (mask & RT_SURF_BUF_BITS) != 0, (void **)&sc->surfBuf, sc->surfBytes, RT_SURF_WORDS) != 0) return -1;
+    if ((mask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS && sc->denoiseBuf) { // the denoiser needs both surface passes
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipFree(sc->denoiseBuf));
+        sc->bytes -= sc->denoiseBytes;
+        sc->denoiseBuf = nullptr;
+        sc->denoiseBytes = 0;
+    }
     sc->passMask = mask;
     return 0;
 }
@@ -1478,15 +1502,16 @@ int rtHipReadbackSurfacePasses(rtHipScene *sc, cl_float *normal, cl_float *albed
     return 0;
 }
 
-// A device pointer the query kernel may read or write `bytes` from: device memory of the scene's device, 16-byte aligned where the kernel
-// loads 16 bytes at a time, and inside one allocation.  A host pointer must never reach the kernel: its fault takes the whole GPU down.
-static int query_pointer_ok(const rtHipScene *sc, const void *p, uint64_t bytes, uint64_t align, const char *what)
+// A device pointer a kernel may read or write `bytes` from: device memory of `device`, 16-byte aligned where the kernel loads 16 bytes at
+// a time, and inside one allocation.  A host pointer must never reach a kernel: its fault takes the whole GPU down.
+// `whose` names what lives on `device` in the error text ("the scene").
+static int query_pointer_ok(int device, const char *whose, const void *p, uint64_t bytes, uint64_t align, const char *what)
 {
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof at);
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("%s %p is not device memory", what, p); }
     if (at.type != hipMemoryTypeDevice) return fail("%s %p is not device memory (memory type %d)", what, p, (int)at.type);
-    if (at.device != sc->device) return fail("%s %p is memory of device %d, the scene is on device %d", what, p, at.device, sc->device);
+    if (at.device != device) return fail("%s %p is memory of device %d, %s is on device %d", what, p, at.device, whose, device);
     if ((uintptr_t)p % align) return fail("%s %p is not %llu-byte aligned", what, p, (unsigned long long)align);
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
@@ -1502,9 +1527,9 @@ int rtHipSceneIntersectDevice(rtHipScene *sc, const void *rays, const void *excl
     if (count == 0) return 0;
     if (!rays || !hits) return fail("null rays or hits with %u rays", count);
     HIP_OK(hipSetDevice(sc->device));
-    if (query_pointer_ok(sc, rays, (uint64_t)count * sizeof(rtHipRay), 16, "rays") != 0) return -1;
-    if (excluded && query_pointer_ok(sc, excluded, (uint64_t)count * 4, 4, "excluded") != 0) return -1;
-    if (query_pointer_ok(sc, hits, (uint64_t)count * sizeof(rtHipHit), 16, "hits") != 0) return -1;
+    if (query_pointer_ok(sc->device, "the scene", rays, (uint64_t)count * sizeof(rtHipRay), 16, "rays") != 0) return -1;
+    if (excluded && query_pointer_ok(sc->device, "the scene", excluded, (uint64_t)count * 4, 4, "excluded") != 0) return -1;
+    if (query_pointer_ok(sc->device, "the scene", hits, (uint64_t)count * sizeof(rtHipHit), 16, "hits") != 0) return -1;
     HIP_OK(rtw_launch_query(&sc->dev, rays, (const uint32_t *)excluded, count, hits, sc->tune.fastQuotient ? 1u : 0u,
                             stream ? (hipStream_t)stream : sc->stream));
     return 0;
@@ -1544,6 +1569,178 @@ int rtHipSceneIntersect(rtHipScene *sc, const rtHipRay *rays, const cl_uint *exc
         HIP_OK(hipStreamSynchronize(sc->stream));
         memcpy(hits + off, hostHits, (size_t)n * sizeof(rtHipHit));
     }
+    return 0;
+}
+
+// ---- denoiser (include/raytrace_hip.h, "DENOISER"; kernels in rt_denoise.hip) ------------------------------------------------
+// Filter scratch of a W x H image: C^i and C^(i+1) as float4 (ping-pong), then the guides G0 = (n^, z) and G1 = (albedo, 0) as float4.
+#define RT_DENOISE_MAX_PIXELS (1ull << 27)
+#define RT_DENOISE_SCRATCH_PER_PIXEL 64ull
+
+void rtHipDenoiseDefaults(rtHipDenoiseParams *p)
+{
+    if (!p) return;
+    p->iterations = 4;
+    p->colourInvSigma2 = 4.0f;
+    p->albedoInvSigma2 = 100.0f;
+    p->normalPowerLog2 = 7;
+}
+
+static int denoise_params_ok(const rtHipDenoiseParams *p)
+{
+    if (!p) return fail("denoise: null parameters");
+    if (p->iterations > 12) return fail("denoise: iterations %u is not in 0..12", p->iterations);
+    if (!(std::isfinite(p->colourInvSigma2) && p->colourInvSigma2 >= 0.f))
+        return fail("denoise: colourInvSigma2 %g is not finite and >= 0", (double)p->colourInvSigma2);
+    if (!(std::isfinite(p->albedoInvSigma2) && p->albedoInvSigma2 >= 0.f))
+        return fail("denoise: albedoInvSigma2 %g is not finite and >= 0", (double)p->albedoInvSigma2);
+    if (p->normalPowerLog2 > 10) return fail("denoise: normalPowerLog2 %u is not in 0..10", p->normalPowerLog2);
+    float ic = p->colourInvSigma2; // what the last iteration uses: ic multiplied by 4.0f K-1 times in fp32
+    for (uint32_t i = 1; i < p->iterations; ++i) ic = ic * 4.0f;
+    if (!std::isfinite(ic)) return fail("denoise: colourInvSigma2 * 4^(iterations-1) overflows fp32");
+    return 0;
+}
+
+static int denoise_size_ok(uint32_t W, uint32_t H)
+{
+    if (W == 0 || H == 0 || (uint64_t)W * H > RT_DENOISE_MAX_PIXELS) return fail("denoise: a %u x %u image is not 1..2^27 pixels", W, H);
+    return 0;
+}
+
+uint64_t rtHipDenoiseScratchBytes(cl_uint width, cl_uint height)
+{
+    if (width == 0 || height == 0 || (uint64_t)width * height > RT_DENOISE_MAX_PIXELS) return 0;
+    return (uint64_t)width * height * RT_DENOISE_SCRATCH_PER_PIXEL;
+}
+
+// Issues the filter on `st`: guides, K iterations, output (planes: all three or none), and `afterGuides` (if any) between the guides and
+// the first iteration.  Arguments were checked by the caller.
+static int denoise_issue(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo, float *out, uint16_t *planeR,
+                         uint16_t *planeG, uint16_t *planeB, char *scratch, const rtHipDenoiseParams *p, hipStream_t st,
+                         hipEvent_t afterGuides = nullptr)
+{
+    const size_t n = (size_t)W * H;
+    char *c[2] = { scratch, scratch + 16 * n };
+    char *g0 = scratch + 32 * n, *g1 = scratch + 48 * n;
+    HIP_OK(rtd_launch_guides((uint32_t)n, colour, normal, albedo, c[0], g0, g1, st));
+    if (afterGuides) HIP_OK(hipEventRecord(afterGuides, st));
+    float ic = p->colourInvSigma2;
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        HIP_OK(rtd_launch_iteration(W, H, 1 << i, ic, p->albedoInvSigma2, p->normalPowerLog2, c[i & 1], g0, g1, c[(i + 1) & 1], st));
+        ic = ic * 4.0f;
+    }
+    HIP_OK(rtd_launch_output((uint32_t)n, c[p->iterations & 1], out, planeR, planeG, planeB, st));
+    return 0;
+}
+
+static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+int rtHipDenoiseDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *normal, const void *albedo, void *out,
+                       void *scratch, uint64_t scratchBytes, const rtHipDenoiseParams *params, void *stream)
+{
+    if (denoise_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
+    if (!colour || !normal || !albedo || !out || !scratch) return fail("denoise: null array");
+    const uint64_t img = (uint64_t)width * height * 12, need = rtHipDenoiseScratchBytes(width, height);
+    if (scratchBytes < need) return fail("denoise: scratch of %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)need);
+    const struct { const void *p; uint64_t bytes, align; const char *what; } arr[5] = {
+        { colour, img, 4, "colour" }, { normal, img, 4, "normal" }, { albedo, img, 4, "albedo" }, { out, img, 4, "out" }, { scratch, need, 16, "scratch" } };
+    for (int i = 0; i < 5; ++i) // out and scratch are written: neither may overlap anything else
+        for (int k = 3; k < 5; ++k)
+            if (i != k && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
+                return fail("denoise: %s overlaps %s", arr[k].what, arr[i].what);
+    HIP_OK(hipSetDevice(device));
+    if (stream) { // (the null stream is the current device's, set above)
+        hipDevice_t sd = -1;
+        if (hipStreamGetDevice((hipStream_t)stream, &sd) != hipSuccess) { (void)hipGetLastError(); return fail("denoise: stream %p is not a stream", stream); }
+        if (sd != device) return fail("denoise: stream %p belongs to device %d, the call is for device %d", stream, (int)sd, device);
+    }
+    for (const auto &a : arr)
+        if (query_pointer_ok(device, "the call", a.p, a.bytes, a.align, a.what) != 0) return -1;
+    return denoise_issue(width, height, (const float *)colour, (const float *)normal, (const float *)albedo, (float *)out, nullptr, nullptr,
+                         nullptr, (char *)scratch, params, (hipStream_t)stream);
+}
+
+int rtHipDenoise(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *normal, const cl_float *albedo,
+                 cl_float *out, const rtHipDenoiseParams *params)
+{
+    if (denoise_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
+    if (!colour || !normal || !albedo || !out) return fail("denoise: null array");
+    HIP_OK(hipSetDevice(device));
+    const size_t img = (size_t)width * height * 12;
+    DevScratch mem;
+    char *in = nullptr, *dout = nullptr, *scratch = nullptr;
+    HIP_OK(mem.get((void **)&in, 3 * img));
+    HIP_OK(mem.get((void **)&dout, img));
+    HIP_OK(mem.get((void **)&scratch, rtHipDenoiseScratchBytes(width, height)));
+    HIP_OK(hipMemcpy(in, colour, img, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(in + img, normal, img, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(in + 2 * img, albedo, img, hipMemcpyHostToDevice));
+    if (denoise_issue(width, height, (const float *)in, (const float *)(in + img), (const float *)(in + 2 * img), (float *)dout, nullptr,
+                      nullptr, nullptr, scratch, params, nullptr) != 0)
+        return -1;
+    HIP_OK(hipMemcpy(out, dout, img, hipMemcpyDeviceToHost));
+    HIP_OK(hipDeviceSynchronize());
+    return 0;
+}
+
+int rtHipSceneDenoise(rtHipScene *sc, const rtHipDenoiseParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG, cl_ushort *outB)
+{
+    if (!sc) return fail("null scene");
+    if (denoise_params_ok(params) != 0 || denoise_size_ok(sc->width, sc->height) != 0) return -1;
+    if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
+        return fail("denoise needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
+    const uint32_t tiles = sc->tilesX * ((sc->height + RT_TILE - 1) / RT_TILE);
+    std::vector<char> seen(tiles, 0);
+    for (cl_uint t : sc->tileIds)
+        if (t >= tiles || seen[t]++) return fail("denoise needs a tile set that holds every tile of the image once (tile %u)", t);
+    if (sc->tileIds.size() != tiles) return fail("denoise needs a tile set that holds every tile of the image (%zu of %u)", sc->tileIds.size(), tiles);
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    // [colour | normal | albedo | out] W x H x 3 f32, [R | G | B] u16, filter scratch; every part 256-byte aligned
+    const uint32_t W = sc->width, H = sc->height;
+    const size_t n = (size_t)W * H, img = (n * 12 + 255) & ~(size_t)255, plane = (n * 2 + 255) & ~(size_t)255;
+    const uint64_t bytes = 4 * img + 3 * plane + rtHipDenoiseScratchBytes(W, H);
+    if (!sc->denoiseBuf) {
+        void *p = nullptr;
+        HIP_OK(hipMalloc(&p, bytes));
+        sc->denoiseBuf = (char *)p;
+        sc->denoiseBytes = bytes;
+        sc->bytes += bytes;
+    }
+    for (hipEvent_t &e : sc->denoiseEv)
+        if (!e) HIP_OK(hipEventCreate(&e));
+    char *b = sc->denoiseBuf;
+    float *colour = (float *)b, *normal = (float *)(b + img), *albedo = (float *)(b + 2 * img), *out = (float *)(b + 3 * img);
+    uint16_t *planes[3] = { (uint16_t *)(b + 4 * img), (uint16_t *)(b + 4 * img + plane), (uint16_t *)(b + 4 * img + 2 * plane) };
+    const bool wantPlanes = outR || outG || outB;
+    hipStream_t st = sc->stream;
+    hipEvent_t *ev = sc->denoiseEv;
+    HIP_OK(hipEventRecord(ev[0], st));
+    HIP_OK(rtd_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->surfBuf,
+                             (float)sc->dev.sampleCount, colour, normal, albedo, st));
+    HIP_OK(hipEventRecord(ev[1], st));
+    if (denoise_issue(W, H, colour, normal, albedo, outRgb ? out : nullptr, wantPlanes ? planes[0] : nullptr, wantPlanes ? planes[1] : nullptr,
+                      wantPlanes ? planes[2] : nullptr, b + 4 * img + 3 * plane, params, st, ev[2]) != 0)
+        return -1;
+    HIP_OK(hipEventRecord(ev[3], st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(&sc->denoiseMs[i], ev[i], ev[i + 1]));
+    if (outRgb) HIP_OK(hipMemcpy(outRgb, out, n * 12, hipMemcpyDeviceToHost));
+    cl_ushort *dst[3] = { outR, outG, outB };
+    for (int c = 0; c < 3; ++c)
+        if (dst[c]) HIP_OK(hipMemcpy(dst[c], planes[c], n * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rtHipSceneDenoiseTimes(const rtHipScene *sc, cl_float *ms)
+{
+    if (!sc || !ms) return fail("null argument");
+    for (int i = 0; i < 3; ++i) ms[i] = sc->denoiseMs[i];
     return 0;
 }
 

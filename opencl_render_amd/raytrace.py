@@ -58,6 +58,14 @@ class Hit(C.Structure):  # rtHipHit: 16 bytes
     _fields_ = [("t", C.c_float), ("triangle", C.c_uint32), ("abL", C.c_float), ("acL", C.c_float)]
 
 
+class DenoiseParams(C.Structure):  # rtHipDenoiseParams
+    _fields_ = [("iterations", C.c_uint32), ("colourInvSigma2", C.c_float), ("albedoInvSigma2", C.c_float), ("normalPowerLog2", C.c_uint32)]
+
+
+# rtHipDenoiseDefaults (include/raytrace_hip.h, "DENOISER"; DESIGN.md says why these values)
+DENOISE_DEFAULTS = dict(iterations=4, colour_inv_sigma2=4.0, albedo_inv_sigma2=100.0, normal_power_log2=7)
+
+
 class Stats(C.Structure):  # rtHipStats
     _fields_ = [(n, C.c_uint64) for n in ("primarySamples", "primaryCandidates", "gridRays", "gridCells", "gridCandidates", "shadedHits", "texelFetches")]
 
@@ -78,6 +86,7 @@ RESIDENT_SYMBOLS = [
     "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
     "rtHipSurfaceBuffer", "rtHipSurfaceBufferBytes", "rtHipReadbackSurfacePasses",
     "rtHipSceneIntersect", "rtHipSceneIntersectDevice",
+    "rtHipDenoiseDefaults", "rtHipDenoiseScratchBytes", "rtHipDenoiseDevice", "rtHipDenoise", "rtHipSceneDenoise", "rtHipSceneDenoiseTimes",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat",
@@ -172,6 +181,14 @@ def lib() -> C.CDLL:
     L.rtHipReadbackSurfacePasses.argtypes = [vp, vp, vp]
     L.rtHipSceneIntersect.argtypes = [vp, vp, vp, u32, vp]
     L.rtHipSceneIntersectDevice.argtypes = [vp, vp, vp, u32, vp, vp]
+    L.rtHipDenoiseDefaults.restype = None
+    L.rtHipDenoiseDefaults.argtypes = [C.POINTER(DenoiseParams)]
+    L.rtHipDenoiseScratchBytes.restype = u64
+    L.rtHipDenoiseScratchBytes.argtypes = [u32, u32]
+    L.rtHipDenoiseDevice.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, vp, u64, C.POINTER(DenoiseParams), vp]
+    L.rtHipDenoise.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, C.POINTER(DenoiseParams)]
+    L.rtHipSceneDenoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp]
+    L.rtHipSceneDenoiseTimes.argtypes = [vp, C.POINTER(C.c_float)]
     L.rtHipKernelTime.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
     L.rtHipBuildCameraList.argtypes = [u32, u32, vp, vp, vp, vp, f32, u32, vp, vp, C.c_int,
                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
@@ -362,6 +379,77 @@ def raytrace_all(computation_type: int, sc: Scene):
         _ptr(r), _ptr(g), _ptr(b))
     shape = (sc.height, sc.width)
     return bool(ok), r.reshape(shape), g.reshape(shape), b.reshape(shape)
+
+
+def denoise_params(iterations=DENOISE_DEFAULTS["iterations"], colour_inv_sigma2=DENOISE_DEFAULTS["colour_inv_sigma2"],
+                   albedo_inv_sigma2=DENOISE_DEFAULTS["albedo_inv_sigma2"], normal_power_log2=DENOISE_DEFAULTS["normal_power_log2"]) -> DenoiseParams:
+    """rtHipDenoiseParams from the Python keywords (the library checks the values)."""
+    if not all(0 <= int(v) <= 0xFFFFFFFF for v in (iterations, normal_power_log2)):  # (ctypes would wrap them into the uint32 fields)
+        raise ValueError(f"denoise: iterations and normal_power_log2 must be in 0..2^32-1 (got {iterations}, {normal_power_log2})")
+    return DenoiseParams(int(iterations), float(colour_inv_sigma2), float(albedo_inv_sigma2), int(normal_power_log2))
+
+
+def quantise(colour: np.ndarray) -> list:
+    """[H, W, 3] f32 -> u16 planes R, G, B as rtHipSceneDenoise writes them: v = c * 65535, 0 unless v > 0, 65535 from v >= 65534.5,
+    else (u16)(v + 0.5)."""
+    v = np.asarray(colour, np.float32) * np.float32(65535.0)
+    with np.errstate(invalid="ignore"):
+        u = np.where(~(v > 0), np.float32(0), np.where(v >= np.float32(65534.5), np.float32(65535), np.floor(v + np.float32(0.5))))
+    u = u.astype(np.uint16)
+    return [np.ascontiguousarray(u[..., c]) for c in range(3)]
+
+
+def denoise(colour, normal, albedo, iterations=DENOISE_DEFAULTS["iterations"], colour_inv_sigma2=DENOISE_DEFAULTS["colour_inv_sigma2"],
+            albedo_inv_sigma2=DENOISE_DEFAULTS["albedo_inv_sigma2"], normal_power_log2=DENOISE_DEFAULTS["normal_power_log2"], device: int = 0,
+            stream: int = 0):
+    """The denoiser of include/raytrace_hip.h ("DENOISER") on [H, W, 3] float32 colour, normal and albedo images; returns C^K as
+    [H, W, 3] float32.  numpy arrays go through rtHipDenoise (host arrays, synchronous).  torch tensors on cuda:`device` go through
+    rtHipDenoiseDevice on torch's current stream (or `stream`) with a torch scratch tensor; the result is a tensor on that device."""
+    p = denoise_params(iterations, colour_inv_sigma2, albedo_inv_sigma2, normal_power_log2)
+    if any(hasattr(a, "data_ptr") for a in (colour, normal, albedo)):
+        return _denoise_torch(colour, normal, albedo, p, device, stream)
+    c, n, a = (np.ascontiguousarray(v, np.float32) for v in (colour, normal, albedo))
+    if c.ndim != 3 or c.shape[2] != 3 or n.shape != c.shape or a.shape != c.shape:
+        raise ValueError(f"denoise: colour, normal and albedo must all be [H, W, 3] (got {c.shape}, {n.shape}, {a.shape})")
+    out = np.empty_like(c)
+    if lib().rtHipDenoise(device, c.shape[1], c.shape[0], _ptr(c), _ptr(n), _ptr(a), _ptr(out), C.byref(p)) != 0:
+        raise RuntimeError("rtHipDenoise failed: " + last_error())
+    return out
+
+
+def _denoise_torch(colour, normal, albedo, p, device, stream):
+    import torch
+
+    dev = torch.device("cuda", device)
+    ins = []
+    for name, v in (("colour", colour), ("normal", normal), ("albedo", albedo)):
+        if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype != torch.float32:
+            where = f"{v.dtype} on {v.device}" if isinstance(v, torch.Tensor) else type(v).__name__
+            raise ValueError(f"denoise: {name} must be a float32 tensor on {dev}, not {where}")
+        ins.append(v.contiguous())
+    c, n, a = ins
+    if c.dim() != 3 or c.shape[2] != 3 or n.shape != c.shape or a.shape != c.shape:
+        raise ValueError(f"denoise: colour, normal and albedo must all be [H, W, 3] (got {tuple(c.shape)}, {tuple(n.shape)}, {tuple(a.shape)})")
+    H, W = int(c.shape[0]), int(c.shape[1])
+    nbytes = lib().rtHipDenoiseScratchBytes(W, H)
+    if nbytes == 0:
+        raise ValueError(f"denoise: a {W} x {H} image is not 1..2^27 pixels")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty_like(c)
+    cur = torch.cuda.current_stream(dev)
+    run = torch.cuda.ExternalStream(stream, device=dev) if stream and stream != cur.cuda_stream else cur
+    if run is not cur:
+        run.wait_stream(cur)
+    rc = lib().rtHipDenoiseDevice(device, W, H, C.c_void_p(c.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(a.data_ptr()),
+                                  C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes, C.byref(p),
+                                  C.c_void_p(run.cuda_stream) if run.cuda_stream else None)
+    if rc != 0:
+        raise RuntimeError("rtHipDenoiseDevice failed: " + last_error())
+    if run is not cur:
+        cur.wait_stream(run)
+        for buf in (c, n, a, out, scratch):
+            buf.record_stream(run)
+    return out
 
 
 def computation_type_names() -> list:
@@ -589,6 +677,23 @@ class ResidentScene:
                 tm = np.asarray(tri_mesh, np.int32)
                 out["mesh"] = np.where(hit, tm[idx] if len(tm) else -1, -1).astype(np.int32)
         return out
+
+    def denoise(self, **params) -> dict:
+        """The last frame denoised on the device (rtHipSceneDenoise; keywords as for raytrace.denoise): {"colour": [H, W, 3] f32 C^K,
+        "planes": [r, g, b] [H, W] u16}.  Needs set_passes(normal=True, albedo=True) and every tile of the image in this instance."""
+        p = denoise_params(**params)
+        sc = self.scene
+        colour = np.empty((sc.height, sc.width, 3), np.float32)
+        planes = [np.empty((sc.height, sc.width), np.uint16) for _ in range(3)]
+        self._check(lib().rtHipSceneDenoise(self.handle, C.byref(p), _ptr(colour), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2])),
+                    "rtHipSceneDenoise")
+        return {"colour": colour, "planes": planes}
+
+    def denoise_times_ms(self) -> dict:
+        """Device time of the last denoise() (rtHipSceneDenoiseTimes): gather, prologue (guides), filter (iterations and output)."""
+        ms = (C.c_float * 3)()
+        self._check(lib().rtHipSceneDenoiseTimes(self.handle, ms), "rtHipSceneDenoiseTimes")
+        return dict(gather=ms[0], prologue=ms[1], filter=ms[2])
 
     def intersect(self, origins, directions, tmin=0.0, tmax=np.inf, exclude=None, stream: int = 0) -> dict:
         """What rays hit in this scene: the reference's grid walk, RayIntersectsTriangles (raytrace_opencl.c:324-401), bit for bit

@@ -8,5 +8,8 @@ make -s
 mkdir -p build ../variants
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-gpu-rdc \
     -I../../include -I. "$@" -c rt_wavefront.hip -o build/wf_$tag.o
-/opt/rocm/bin/hipcc -shared -fPIC -o ../variants/lib_$tag.so build/rt_kernels.o build/wf_$tag.o build/rt_build_device.o build/rt_kat.o build/rt_scene_prep.o build/rt_api.o build/rt_builders.o build/rt_mathabi.o build/rt_frontend.o build/rt_fileio.o -pthread
+# the Makefile's own object list, rt_wavefront.o replaced by the variant (so the two lists cannot drift apart)
+objs=$(make -s objs | sed "s#/build/rt_wavefront\.o#/build/wf_$tag.o#")
+case "$objs" in *"/build/wf_$tag.o"*) ;; *) echo "build_variant.sh: rt_wavefront.o is not in the Makefile's OBJS" >&2; exit 1 ;; esac
+/opt/rocm/bin/hipcc -shared -fPIC -o ../variants/lib_$tag.so $objs -pthread
 echo built opencl_render_amd/variants/lib_$tag.so
