@@ -387,6 +387,48 @@ int rtHipSceneDenoise(rtHipScene *scene, const rtHipDenoiseParams *params, cl_fl
  * guide prologue, ms[2] the K iterations and the output kernel.  All 0 before the first call.  Returns 0, or -1 for a NULL argument. */
 int rtHipSceneDenoiseTimes(const rtHipScene *scene, cl_float *ms);
 
+/* AMBIENT OCCLUSION: per pixel, the fraction of cosine-weighted hemisphere rays from the primary hit that reach `radius` unoccluded,
+ * traced against a resident scene with the renderer's own grid walk (the answer rtHipSceneIntersect gives for each ray).  It needs the
+ * camera, geometry and grid only: no frame has to be rendered, and a call changes nothing a later frame, read-back, pass or denoise
+ * produces.  The arithmetic is IEEE fp32 + - * /, sqrt and compares (no FMA, division and square root correctly rounded) plus a 64-bit
+ * integer hash: tests/ao_oracle.py restates it in numpy and, with rt_oracle_grid_trace for the walks, the device output equals it bit
+ * for bit.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2; cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0).
+ *
+ * Parameters: raysPerHit R in 1..256, pixelSamples Sp in 1..64, radius > 0 (+inf allowed, NaN not), seed any u32.
+ * Random numbers, mod 2^64: mix(z) = splitmix64's finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ * z *= 0x94D049BB133111EB; z ^= z >> 31); S0 = mix(seed); h(c) = mix(S0 + (c + 1) * 0x9E3779B97F4A7C15); U(c) = (float)(h(c) >> 40) *
+ * 2^-24.  (Seed 0: h(0), h(1), h(2) = 0xE220A8397B1DCDAF, 0x6E789E6AA1B965F4, 0x06C45D188009454F, splitmix64's outputs from state 0.)
+ * Counter c = (((p*Sp + j)*(R + 1) + slot)*32 + draw): pixel p = y*W + x, pixel sample j, slot 0 the jitter and slot 1 + r AO ray r.
+ * Pixel sample (x, y, j): u = v = 0.5 if Sp = 1, else u = U(slot 0, draw 0), v = U(slot 0, draw 1); the ray o = eye,
+ * d = (topLeft + lr*((float)x + u)) + tb*((float)y + v) per component, tmin = 0, tmax = +inf, nothing excluded.  A miss counts R
+ * unoccluded rays.  A hit (triangle tri, t): P = o + t*d per component; n = cross(ac, ab) (ab = b - a, ac = c - a from the vertices);
+ * n = -n if dot(n, d) > 0; m = dot(n, n); if !(m > 0) the sample counts R unoccluded rays, else n^ = n / sqrt(m) (three divisions).
+ * Frame (Duff et al. 2017): s = (n^z >= 0) ? 1 : -1, a = -1 / (s + n^z), b = (n^x*n^y)*a, t1 = (1 + ((s*n^x)*n^x)*a, s*b, -(s*n^x)),
+ * t2 = (b, s + (n^y*n^y)*a, -n^y).  AO ray r (Malley): for k = 0..15, xd = 2*U(slot 1+r, draw 2k) - 1, yd = 2*U(slot 1+r, draw 2k+1) - 1,
+ * r2 = xd*xd + yd*yd; the first k with r2 < 1 is taken, none gives xd = yd = r2 = 0.  z = sqrt(1 - r2), dir_c = (xd*t1_c + yd*t2_c) +
+ * z*n^_c; the ray o = P, d = dir, tmin = 0, tmax = radius, excluding tri, is occluded iff the walk returns a triangle.
+ * Output: U = unoccluded rays over the pixel's Sp samples, value = (float)U / (float)(Sp*R), in [0, 1].  Only the pixels of the scene's
+ * own tiles are written; every other pixel keeps its value, so instances over a tile deal compose one image.  Every input bit pattern
+ * has a defined answer (NaN directions, degenerate triangles, the eye outside the grid's box): the walk has one.
+ * The scratch (the pixel counters and one chunk of primary hits, 32 bytes per pixel sample; "ao_samples" of rtHipTune) belongs to the
+ * scene: made on first use, counted in rtHipSceneBytes, freed with the scene.  Calls on different streams are ordered by an event.
+ * Both calls refuse, with -1, the last-error text set and nothing launched: a NULL argument, a parameter out of range, an image of
+ * 2^32 pixels or more. */
+typedef struct rtHipAoParams {
+    cl_uint  raysPerHit;   /* R */
+    cl_uint  pixelSamples; /* Sp */
+    cl_float radius;       /* tmax of the AO rays */
+    cl_uint  seed;
+} rtHipAoParams;
+/* R = 16, Sp = 1, radius = +inf, seed = 0. */
+void rtHipAoDefaults(rtHipAoParams *params);
+/* HOST W x H f32, row-major; synchronous, on the scene's stream. */
+int  rtHipSceneAmbientOcclusion(rtHipScene *scene, const rtHipAoParams *params, cl_float *out);
+/* DEVICE W x H f32 of the scene's device (4-byte aligned), asynchronous on `stream` (a hipStream_t as void*; NULL = the scene's stream):
+ * no synchronisation.  out is checked like rtHipSceneIntersectDevice's pointers (device memory of the scene's device, the whole range
+ * inside one allocation); a host pointer returns -1. */
+int  rtHipSceneAmbientOcclusionDevice(rtHipScene *scene, const rtHipAoParams *params, void *out, void *stream);
+
 /* Average device time in milliseconds of one rtHipRenderTiles frame (all its kernels) over the frames recorded since
  * the last call (HIP events on the launch stream), and the number of frames.  Returns 0 on success. */
 int rtHipKernelTime(rtHipScene *scene, double *avgMs, uint64_t *launches);
@@ -577,8 +619,8 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
  * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), and the test hooks
  * "plan_rounds", "plan_grid_tiny", "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
  * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
- * and most 2^32 - 1; above it they return -3), and "query_rays" (rays per staging chunk of rtHipSceneIntersect, default 2^20).  Returns 0, -1 for
- * an unknown key. */
+ * and most 2^32 - 1; above it they return -3), "query_rays" (rays per staging chunk of rtHipSceneIntersect, default 2^20), and
+ * "ao_samples" (pixel samples per chunk of the ambient occlusion calls, default 2^20, at most 2^24).  Returns 0, -1 for an unknown key. */
 int rtHipTune(const char *key, double value);
 
 /* TEST-ONLY: device addresses held by the first scene of RaytraceAll's cache -- triangle records, shading rows, the grid's pair

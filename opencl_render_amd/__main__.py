@@ -15,6 +15,10 @@ primary hit, means over the pixel's samples: a denoiser's auxiliary images).
 built-in edge-aware filter (include/raytrace_hip.h, "DENOISER", default parameters) to PATH: .bmp / .ppm (u16 planes) or .pfm (the
 f32 colour).  ``--out`` is still the noisy beauty.  For the all-GPUs device the instances' read-backs are composed on the host and
 denoised with rtHipDenoise on device 0.
+
+``--ao PATH`` also writes the scene's ambient occlusion (include/raytrace_hip.h, "AMBIENT OCCLUSION"), traced on the device from the
+scene's camera, to PATH: .pfm (f32) or .pgm (u16 quantised like the denoiser's output, written as 8 bits).  ``--ao-rays``,
+``--ao-radius``, ``--ao-samples`` and ``--ao-seed`` set its parameters.  For the all-GPUs device it runs on device 0.
 """
 import argparse
 import sys
@@ -41,6 +45,11 @@ def parser():
     ap.add_argument("--passes", metavar="PREFIX", help="also write PREFIX_alpha.pgm, PREFIX_depth.pfm and PREFIX_ids.npz (render passes)")
     ap.add_argument("--surface-passes", action="store_true", help="with --passes: also write PREFIX_normal.pfm and PREFIX_albedo.pfm")
     ap.add_argument("--denoise", metavar="PATH", help="also write the denoised frame to PATH (.bmp, .ppm or .pfm)")
+    ap.add_argument("--ao", metavar="PATH", help="also write the ambient occlusion image to PATH (.pfm or .pgm)")
+    ap.add_argument("--ao-rays", type=int, default=16, help="--ao: hemisphere rays per pixel sample (1..256)")
+    ap.add_argument("--ao-radius", type=float, default=float("inf"), help="--ao: how far an occluder counts (scene units; default: any distance)")
+    ap.add_argument("--ao-samples", type=int, default=1, help="--ao: jittered primary samples per pixel (1..64)")
+    ap.add_argument("--ao-seed", type=int, default=0, help="--ao: seed of the ray directions (u32)")
     return ap
 
 
@@ -51,7 +60,25 @@ def parse_args(argv=None):
         ap.error("--surface-passes needs --passes PREFIX")
     if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
         ap.error("--denoise PATH must end in .bmp, .ppm or .pfm")
+    if args.ao and not args.ao.lower().endswith((".pfm", ".pgm")):
+        ap.error("--ao PATH must end in .pfm or .pgm")
     return args
+
+
+def write_ao(sc, path: str, device: int, rays: int, radius: float, samples: int, seed: int) -> np.ndarray:
+    """ResidentScene.ambient_occlusion on HIP device `device` -> PATH (.pfm: f32; .pgm: u16 quantised like raytrace.quantise).  Returns
+    the [H, W] f32 image."""
+    from . import frontend, raytrace
+    rs = raytrace.ResidentScene(sc, device)
+    try:
+        ao = rs.ambient_occlusion(rays=rays, radius=radius, pixel_samples=samples, seed=seed)
+    finally:
+        rs.close()
+    if path.lower().endswith(".pfm"):
+        frontend.write_pfm(path, ao)
+    else:
+        frontend.write_pgm(path, raytrace.quantise(ao[..., None].repeat(3, -1))[0])
+    return ao
 
 
 def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool = True, denoise: bool = False):
@@ -140,6 +167,9 @@ def main(argv=None):
             frontend.write_ppm(args.denoise, *den["planes"])
         else:
             frontend.write_bmp(args.denoise, *den["planes"], low_byte_compat=args.low_byte_compat)
+    if args.ao:
+        gpus = raytrace.lib().rtHipDeviceCount()
+        write_ao(sc, args.ao, 0 if args.device == gpus + 1 else args.device - 1, args.ao_rays, args.ao_radius, args.ao_samples, args.ao_seed)
     if args.out.lower().endswith(".ppm"):
         frontend.write_ppm(args.out, r, g, b)
     else:

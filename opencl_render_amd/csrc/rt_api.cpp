@@ -49,6 +49,9 @@ extern "C" hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, h
 extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefront *wf, int first, hipStream_t stream);
 extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
                                        uint32_t fastQuotient, hipStream_t stream);
+extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream);
+extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
+                                           hipStream_t stream);
 
 extern "C" hipError_t rtd_launch_guides(uint32_t n, const float *colour, const float *normal, const float *albedo, void *c0, void *g0, void *g1,
                                         hipStream_t stream);
@@ -112,6 +115,7 @@ struct Tuning {
     uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
     uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
     uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
+    uint32_t aoSamples = 1u << 20;  // pixel samples per chunk of the ambient occlusion calls (32 bytes each of scene-owned scratch)
 };
 // Read at the entry points only (scene create, RaytraceAll, the two public device builders): a build works from one snapshot.
 Tuning g_tune;
@@ -319,6 +323,12 @@ struct rtHipScene {
     // device time of the last rtHipSceneDenoise: events before the gather, after it, after the guides and after the output
     hipEvent_t denoiseEv[4] = {};
     float denoiseMs[3] = {};
+    // ambient occlusion scratch (rtHipSceneAmbientOcclusion*), made on first use: the pixel counters, then one chunk of primary hits; the
+    // event marks the end of the last call that used it, so that a call on another stream waits for it on the device
+    char *aoBuf = nullptr;
+    uint64_t aoBytes = 0;
+    uint32_t aoChunk = 0;
+    hipEvent_t aoDone = nullptr;
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -1211,6 +1221,8 @@ void rtHipSceneDestroy(rtHipScene *sc)
         if (e) (void)hipEventDestroy(e);
     if (sc->queryDev) (void)hipFree(sc->queryDev);
     if (sc->queryHost) Stager::pool().give(sc->queryHost, sc->queryBytes);
+    if (sc->aoBuf) (void)hipFree(sc->aoBuf);
+    if (sc->aoDone) (void)hipEventDestroy(sc->aoDone);
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
     sc->stager.destroy();
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
@@ -1568,6 +1580,85 @@ int rtHipSceneIntersect(rtHipScene *sc, const rtHipRay *rays, const cl_uint *exc
         HIP_OK(hipMemcpyAsync(hostHits, devHits, (size_t)n * sizeof(rtHipHit), hipMemcpyDeviceToHost, sc->stream));
         HIP_OK(hipStreamSynchronize(sc->stream));
         memcpy(hits + off, hostHits, (size_t)n * sizeof(rtHipHit));
+    }
+    return 0;
+}
+
+// ---- ambient occlusion (include/raytrace_hip.h, "AMBIENT OCCLUSION"; kernels in rt_wavefront.hip, rt_ao_*) ------------------------
+void rtHipAoDefaults(rtHipAoParams *p)
+{
+    if (!p) return;
+    p->raysPerHit = 16;
+    p->pixelSamples = 1;
+    p->radius = HUGE_VALF;
+    p->seed = 0;
+}
+
+static int ao_check(const rtHipScene *sc, const rtHipAoParams *p, const void *out)
+{
+    if (!sc || !p || !out) return fail("ambient occlusion: null scene, parameters or output");
+    if (p->raysPerHit < 1 || p->raysPerHit > 256) return fail("ambient occlusion: raysPerHit %u is not in 1..256", p->raysPerHit);
+    if (p->pixelSamples < 1 || p->pixelSamples > 64) return fail("ambient occlusion: pixelSamples %u is not in 1..64", p->pixelSamples);
+    if (!(p->radius > 0.f)) return fail("ambient occlusion: radius %g is not > 0", (double)p->radius);
+    if ((uint64_t)sc->width * sc->height >= (1ull << 32)) return fail("ambient occlusion: %u x %u is 2^32 pixels or more", sc->width, sc->height);
+    return 0;
+}
+
+// Enqueues the whole pass on `st`: counters zeroed, the chunks' primary and AO launches, the finish kernel into `out` (row-major W x H), or --
+// rowMajor false -- over the counters themselves, in AO order.
+static int ao_run(rtHipScene *sc, const rtHipAoParams *p, float *out, bool rowMajor, hipStream_t st)
+{
+    const uint64_t pixels = (uint64_t)sc->tileIds.size() * RT_TILE_PIXELS, counterBytes = (pixels * 4 + 255) & ~255ull;
+    if (!sc->aoBuf) {
+        const uint32_t chunk = std::max<uint32_t>(sc->tune.aoSamples, 1u);
+        const uint64_t bytes = counterBytes + 256 + (uint64_t)chunk * 32; // counters | hit list length | hit list
+        void *buf = nullptr;
+        const hipError_t e = hipMalloc(&buf, bytes);
+        if (e != hipSuccess) return fail("ambient occlusion: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        const hipError_t ee = hipEventCreateWithFlags(&sc->aoDone, hipEventDisableTiming);
+        if (ee != hipSuccess) { (void)hipFree(buf); sc->aoDone = nullptr; return fail("ambient occlusion: hipEventCreate failed: %s", hipGetErrorString(ee)); }
+        sc->aoBuf = (char *)buf; sc->aoBytes = bytes; sc->aoChunk = chunk;
+        sc->bytes += bytes;
+    } else HIP_OK(hipStreamWaitEvent(st, sc->aoDone, 0)); // the last call's use of the scratch, on whatever stream it ran
+    uint32_t *counter = (uint32_t *)sc->aoBuf;
+    HIP_OK(hipMemsetAsync(counter, 0, pixels * 4, st));
+    RtAoArgs A;
+    A.raysPerHit = p->raysPerHit; A.pixelSamples = p->pixelSamples; A.seed = p->seed; A.fastQuotient = sc->tune.fastQuotient ? 1u : 0u;
+    A.radius = p->radius; A.hits = (uint32_t *)(sc->aoBuf + counterBytes); A.rec = (float4 *)(sc->aoBuf + counterBytes + 256); A.counter = counter;
+    const uint64_t total = pixels * p->pixelSamples;
+    for (uint64_t base = 0; base < total; base += sc->aoChunk) {
+        A.base = base;
+        A.count = (uint32_t)std::min<uint64_t>(sc->aoChunk, total - base);
+        HIP_OK(hipMemsetAsync(A.hits, 0, 4, st));
+        HIP_OK(rtw_launch_ao(&sc->dev, &A, st));
+    }
+    HIP_OK(rtw_launch_ao_finish(&sc->dev, counter, p->pixelSamples * p->raysPerHit, rowMajor ? out : (float *)counter, rowMajor ? 1u : 0u, st));
+    HIP_OK(hipEventRecord(sc->aoDone, st));
+    return 0;
+}
+
+int rtHipSceneAmbientOcclusionDevice(rtHipScene *sc, const rtHipAoParams *p, void *out, void *stream)
+{
+    if (ao_check(sc, p, out) != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    if (query_pointer_ok(sc->device, "the scene", out, (uint64_t)sc->width * sc->height * 4, 4, "out") != 0) return -1;
+    return ao_run(sc, p, (float *)out, true, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtHipSceneAmbientOcclusion(rtHipScene *sc, const rtHipAoParams *p, cl_float *out)
+{
+    if (ao_check(sc, p, out) != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    // the finished values overwrite the counters in AO order; the host stores the scene's pixels
+    if (ao_run(sc, p, nullptr, false, sc->stream) != 0) return -1;
+    const size_t n = sc->tileIds.size() * (size_t)RT_TILE_PIXELS;
+    std::vector<float> host(n);
+    HIP_OK(hipMemcpyAsync(host.data(), sc->aoBuf, n * 4, hipMemcpyDeviceToHost, sc->stream));
+    HIP_OK(hipStreamSynchronize(sc->stream));
+    for (size_t lp = 0; lp < n; ++lp) {
+        const uint32_t tile = sc->tileIds[lp >> 14], q = (uint32_t)(lp & (RT_TILE_PIXELS - 1)), blk = q >> 6, in = q & 63u;
+        const uint32_t gx = (tile % sc->tilesX) * RT_TILE + (blk & 15u) * 8u + (in & 7u), gy = (tile / sc->tilesX) * RT_TILE + (blk >> 4) * 8u + (in >> 3);
+        if (gx < sc->width && gy < sc->height) out[(size_t)gy * sc->width + gx] = host[lp];
     }
     return 0;
 }
@@ -1945,6 +2036,7 @@ int rtHipTune(const char *key, double value)
         { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
         { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
+        { "ao_samples", &T.aoSamples, nullptr, 1u << 22 },
         { "state_mb", nullptr, &T.stateMb, HUGE_VAL }, { "build_key_cap", nullptr, &T.buildKeyCap, 1e18 }, { "build_list_limit", nullptr, &T.buildListLimit },
     };
     for (const Key &e : table) {

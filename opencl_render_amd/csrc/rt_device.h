@@ -212,4 +212,20 @@ struct RtWavefront {
     float4 *sampleOut;         // [capacity] finished colour per output slot
 };
 
+// ---- ambient occlusion (rt_wavefront.hip, rt_ao_*; definition in include/raytrace_hip.h, "AMBIENT OCCLUSION") -----------------------
+// Pixel samples are numbered g = lp*Sp + j over the scene's pixels in AO order: lp = slot*128*128 + q, q walking its tile in 8x8 blocks,
+// 16 blocks per block row (a wave of 64 samples at Sp = 1 is one 8x8 block of the screen).  One launch pair per chunk of `count` samples
+// from g = base: the primary kernel adds R to counter[lp] for a miss or a normal of length 0 and appends every other sample to the hit
+// list, rec[*hits++] = {P.xyz, tri} {n^.xyz, g - base}; the AO kernel traces R rays per listed sample and adds each pixel's unoccluded
+// rays into counter[lp].
+struct RtAoArgs {
+    uint32_t raysPerHit, pixelSamples, seed, fastQuotient;
+    float radius;
+    uint32_t count;
+    uint64_t base;
+    float4 *rec;       // [count][2] the hit list
+    uint32_t *hits;    // its length, zeroed before the chunk's primary launch
+    uint32_t *counter; // [tileCount * 128*128], zeroed before the first chunk
+};
+
 #endif

@@ -2256,3 +2256,166 @@ extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefron
     hipLaunchKernelGGL(wf_accum_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *scene, *wf, first);
     return hipGetLastError();
 }
+
+// ---- ambient occlusion (rtHipSceneAmbientOcclusion*; include/raytrace_hip.h, "AMBIENT OCCLUSION"; buffers in rt_device.h, RtAoArgs) -------
+// Both walks are query_walk, under rt_query_kernel's tame guard: each ray gets exactly the answer rtHipSceneIntersect gives it.
+__device__ __forceinline__ uint64_t ao_mix(uint64_t z)
+{
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// U(c) for base state s0 = mix(seed): the top 24 bits of h(c), exact in fp32
+__device__ __forceinline__ float ao_uniform(uint64_t s0, uint64_t c)
+{
+    return (float)(uint32_t)(ao_mix(s0 + (c + 1ull) * 0x9E3779B97F4A7C15ull) >> 40) * 0x1p-24f;
+}
+// the image pixel of AO-order index lp (may lie outside the image in a tile at its right or bottom edge)
+__device__ __forceinline__ void ao_pixel(const RtDevScene &S, uint32_t lp, uint32_t &gx, uint32_t &gy)
+{
+    const uint32_t tile = S.tileIds[lp >> 14], q = lp & (RT_TILE_PIXELS - 1u), blk = q >> 6, in = q & 63u;
+    gx = (tile % S.tilesX) * RT_TILE + (blk & 15u) * 8u + (in & 7u);
+    gy = (tile / S.tilesX) * RT_TILE + (blk >> 4) * 8u + (in >> 3);
+}
+__device__ __forceinline__ uint32_t ao_walk(const RtDevScene &S, const float *planes, uint32_t fastQuotient, V3 o, V3 d, float tmax, uint32_t excluded,
+                                            float &t)
+{
+    float l1, l2;
+    const bool tame = tame_origin(o.x) && tame_origin(o.y) && tame_origin(o.z) && tame_direction(d.x) && tame_direction(d.y) && tame_direction(d.z);
+    if (S.planesTame && fastQuotient && __ballot(!tame) == 0ull) return query_walk<true>(S, planes, o, d, 0.f, tmax, excluded, t, l1, l2);
+    return query_walk<false>(S, planes, o, d, 0.f, tmax, excluded, t, l1, l2);
+}
+
+// One lane per pixel sample: the primary ray, its walk, the hit point and the oriented unit normal.  A sample with something to trace is
+// appended to the chunk's hit list (one atomic per wave); a miss or a normal of length 0 adds its R open rays to the pixel at once, so the
+// AO kernel's waves hold only rays that are traced.
+__global__ __launch_bounds__(256) void rt_ao_primary_kernel(const RtDevScene S, const RtAoArgs A)
+{
+    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
+    __syncthreads();
+    const uint32_t at = blockIdx.x * 256u + threadIdx.x;
+    if (at >= A.count) return;
+    const uint64_t g = A.base + at;
+    const uint32_t Sp = A.pixelSamples, lp = (uint32_t)(g / Sp), j = (uint32_t)(g - (uint64_t)lp * Sp);
+    uint32_t gx, gy;
+    ao_pixel(S, lp, gx, gy);
+    if (gx >= S.width || gy >= S.height) return; // (its counter is never read)
+    const uint32_t p = gy * S.width + gx;
+    float u = 0.5f, v = 0.5f;
+    if (Sp > 1u) {
+        const uint64_t s0 = ao_mix(A.seed), c = ((uint64_t)p * Sp + j) * (A.raysPerHit + 1u) * 32ull;
+        u = ao_uniform(s0, c);
+        v = ao_uniform(s0, c + 1u);
+    }
+    const float fx = (float)gx + u, fy = (float)gy + v;
+    const V3 o = mk(S.eye[0], S.eye[1], S.eye[2]);
+    const V3 d = mk((S.topLeft[0] + S.lr[0] * fx) + S.tb[0] * fy, (S.topLeft[1] + S.lr[1] * fx) + S.tb[1] * fy,
+                    (S.topLeft[2] + S.lr[2] * fx) + S.tb[2] * fy);
+    float t;
+    const uint32_t tri = ao_walk(S, planes, A.fastQuotient, o, d, RT_INF, RT_NONE, t);
+    V3 P = mk(0.f, 0.f, 0.f), n = P;
+    bool trace = false;
+    if (tri != RT_NONE) {
+        P = along(o, t, d);
+        const float4 r2 = reinterpret_cast<const float4 *>(S.triRec)[4 * (size_t)tri + 2]; // {ac.z, n = cross(ac, ab)}
+        n = mk(r2.y, r2.z, r2.w);
+        if (dot3(n, d) > 0.f) n = mk(-n.x, -n.y, -n.z);
+        const float m = dot3(n, n);
+        if (m > 0.f) {
+            const float r = sqrt_rn(m);
+            n = mk(n.x / r, n.y / r, n.z / r);
+            trace = true;
+        }
+    }
+    const uint32_t slot = wave_append(A.hits, trace);
+    if (trace) {
+        A.rec[2 * (size_t)slot] = make_float4(P.x, P.y, P.z, __uint_as_float(tri));
+        A.rec[2 * (size_t)slot + 1] = make_float4(n.x, n.y, n.z, __uint_as_float(at));
+    } else atomicAdd(A.counter + lp, A.raysPerHit);
+}
+
+// One lane per AO ray of the chunk's hit list, the R rays of a pixel sample on consecutive lanes (the grid is sized for every sample of
+// the chunk hitting; workgroups past the list exit at once).  The unoccluded rays of a wave are counted per pixel with a ballot: each
+// pixel's lanes are one run of the wave, its first lane adds the run's popcount to the pixel's counter (integer sums: the result does
+// not depend on the order of the atomics, nor on the order of the hit list).
+__global__ __launch_bounds__(256) void rt_ao_kernel(const RtDevScene S, const RtAoArgs A)
+{
+    const uint32_t R = A.raysPerHit, Sp = A.pixelSamples, listed = *A.hits;
+    if ((uint64_t)blockIdx.x * 256u >= (uint64_t)listed * R) return;
+    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
+    __syncthreads();
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x, s = k / R, r = k - s * R;
+    const bool live = s < listed;
+    bool open = false;
+    uint32_t lp = 0xffffffffu;
+    if (live) {
+        const float4 a = A.rec[2 * (size_t)s], b = A.rec[2 * (size_t)s + 1];
+        const uint64_t g = A.base + __float_as_uint(b.w);
+        lp = (uint32_t)(g / Sp);
+        const uint32_t j = (uint32_t)(g - (uint64_t)lp * Sp), tri = __float_as_uint(a.w);
+        uint32_t gx, gy;
+        ao_pixel(S, lp, gx, gy);
+        const V3 n = xyz(b);
+        const float sg = (n.z >= 0.f) ? 1.f : -1.f, fa = -1.f / (sg + n.z), fb = (n.x * n.y) * fa;
+        const V3 t1 = mk(1.f + ((sg * n.x) * n.x) * fa, sg * fb, -(sg * n.x));
+        const V3 t2 = mk(fb, sg + (n.y * n.y) * fa, -n.y);
+        const uint64_t s0 = ao_mix(A.seed), c = (((uint64_t)(gy * S.width + gx) * Sp + j) * (R + 1u) + 1u + r) * 32ull;
+        float xd = 0.f, yd = 0.f, r2 = 0.f;
+#pragma unroll 1
+        for (uint32_t att = 0; att < 16u; ++att) {
+            const float x = 2.f * ao_uniform(s0, c + 2u * att) - 1.f, y = 2.f * ao_uniform(s0, c + 2u * att + 1u) - 1.f;
+            const float q = x * x + y * y;
+            if (q < 1.f) { xd = x; yd = y; r2 = q; break; }
+        }
+        const float z = sqrt_rn(1.f - r2);
+        const V3 d = mk((xd * t1.x + yd * t2.x) + z * n.x, (xd * t1.y + yd * t2.y) + z * n.y, (xd * t1.z + yd * t2.z) + z * n.z);
+        float t;
+        open = ao_walk(S, planes, A.fastQuotient, xyz(a), d, A.radius, tri, t) == RT_NONE;
+    }
+    const uint64_t openMask = __ballot(open);
+    const uint32_t lane = __lane_id();
+    const uint32_t before = __shfl_up(lp, 1, 64);
+    const bool first = live && (lane == 0u || before != lp);
+    const uint64_t firsts = __ballot(first);
+    if (first) {
+        const uint64_t later = firsts & ~((2ull << lane) - 1ull);           // first lanes of the runs after this one
+        const uint64_t run = (later ? (later & (0ull - later)) - 1ull : ~0ull) & ~((1ull << lane) - 1ull);
+        const uint32_t n = (uint32_t)__popcll(openMask & run);
+        if (n) atomicAdd(A.counter + lp, n);
+    }
+}
+
+// One lane per pixel of the scene's tiles: value = (float)U / (float)(Sp*R) into row-major W x H `out` (rowMajor) or at index lp
+// (the host entry point's staging, de-tiled on the host; `out` may then be `counter` itself).
+__global__ __launch_bounds__(256) void rt_ao_finish_kernel(const RtDevScene S, const uint32_t *counter, float den, float *out, uint32_t rowMajor)
+{
+    const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
+    if (lp >= S.tileCount * RT_TILE_PIXELS) return;
+    uint32_t gx, gy;
+    ao_pixel(S, lp, gx, gy);
+    if (gx >= S.width || gy >= S.height) return;
+    const float v = (float)counter[lp] / den;
+    if (rowMajor) out[(size_t)gy * S.width + gx] = v;
+    else out[lp] = v;
+}
+
+extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream)
+{
+    if (args->count == 0) return hipSuccess;
+    const uint64_t rays = (uint64_t)args->count * args->raysPerHit;
+    if (rays > (1ull << 31)) return hipErrorInvalidValue; // (the AO kernel's lane index is 32-bit)
+    hipLaunchKernelGGL(rt_ao_primary_kernel, dim3((args->count + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
+    hipLaunchKernelGGL(rt_ao_kernel, dim3((uint32_t)((rays + 255u) / 256u)), dim3(256), 0, stream, *scene, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
+                                           hipStream_t stream)
+{
+    const uint32_t n = scene->tileCount * RT_TILE_PIXELS;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_ao_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, *scene, counter, (float)samplesTimesRays, out, rowMajor);
+    return hipGetLastError();
+}

@@ -66,6 +66,14 @@ class DenoiseParams(C.Structure):  # rtHipDenoiseParams
 DENOISE_DEFAULTS = dict(iterations=4, colour_inv_sigma2=4.0, albedo_inv_sigma2=100.0, normal_power_log2=7)
 
 
+class AoParams(C.Structure):  # rtHipAoParams
+    _fields_ = [("raysPerHit", C.c_uint32), ("pixelSamples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
+
+
+# rtHipAoDefaults (include/raytrace_hip.h, "AMBIENT OCCLUSION")
+AO_DEFAULTS = dict(rays=16, radius=float("inf"), pixel_samples=1, seed=0)
+
+
 class Stats(C.Structure):  # rtHipStats
     _fields_ = [(n, C.c_uint64) for n in ("primarySamples", "primaryCandidates", "gridRays", "gridCells", "gridCandidates", "shadedHits", "texelFetches")]
 
@@ -87,6 +95,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSurfaceBuffer", "rtHipSurfaceBufferBytes", "rtHipReadbackSurfacePasses",
     "rtHipSceneIntersect", "rtHipSceneIntersectDevice",
     "rtHipDenoiseDefaults", "rtHipDenoiseScratchBytes", "rtHipDenoiseDevice", "rtHipDenoise", "rtHipSceneDenoise", "rtHipSceneDenoiseTimes",
+    "rtHipAoDefaults", "rtHipSceneAmbientOcclusion", "rtHipSceneAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat",
@@ -189,6 +198,10 @@ def lib() -> C.CDLL:
     L.rtHipDenoise.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, C.POINTER(DenoiseParams)]
     L.rtHipSceneDenoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp]
     L.rtHipSceneDenoiseTimes.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rtHipAoDefaults.restype = None
+    L.rtHipAoDefaults.argtypes = [C.POINTER(AoParams)]
+    L.rtHipSceneAmbientOcclusion.argtypes = [vp, C.POINTER(AoParams), vp]
+    L.rtHipSceneAmbientOcclusionDevice.argtypes = [vp, C.POINTER(AoParams), vp, vp]
     L.rtHipKernelTime.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
     L.rtHipBuildCameraList.argtypes = [u32, u32, vp, vp, vp, vp, f32, u32, vp, vp, C.c_int,
                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
@@ -387,6 +400,14 @@ def denoise_params(iterations=DENOISE_DEFAULTS["iterations"], colour_inv_sigma2=
     if not all(0 <= int(v) <= 0xFFFFFFFF for v in (iterations, normal_power_log2)):  # (ctypes would wrap them into the uint32 fields)
         raise ValueError(f"denoise: iterations and normal_power_log2 must be in 0..2^32-1 (got {iterations}, {normal_power_log2})")
     return DenoiseParams(int(iterations), float(colour_inv_sigma2), float(albedo_inv_sigma2), int(normal_power_log2))
+
+
+def ao_params(rays=AO_DEFAULTS["rays"], radius=AO_DEFAULTS["radius"], pixel_samples=AO_DEFAULTS["pixel_samples"],
+              seed=AO_DEFAULTS["seed"]) -> AoParams:
+    """rtHipAoParams from the Python keywords (the library checks the ranges)."""
+    if not all(0 <= int(v) <= 0xFFFFFFFF for v in (rays, pixel_samples, seed)):  # (ctypes would wrap them into the uint32 fields)
+        raise ValueError(f"ambient_occlusion: rays, pixel_samples and seed must be in 0..2^32-1 (got {rays}, {pixel_samples}, {seed})")
+    return AoParams(int(rays), int(pixel_samples), float(radius), int(seed))
 
 
 def quantise(colour: np.ndarray) -> list:
@@ -694,6 +715,47 @@ class ResidentScene:
         ms = (C.c_float * 3)()
         self._check(lib().rtHipSceneDenoiseTimes(self.handle, ms), "rtHipSceneDenoiseTimes")
         return dict(gather=ms[0], prologue=ms[1], filter=ms[2])
+
+    def ambient_occlusion(self, rays=AO_DEFAULTS["rays"], radius=AO_DEFAULTS["radius"], pixel_samples=AO_DEFAULTS["pixel_samples"],
+                          seed=AO_DEFAULTS["seed"], out=None, stream: int = 0):
+        """Ambient occlusion from the scene's camera (include/raytrace_hip.h, "AMBIENT OCCLUSION"): per pixel the fraction of `rays`
+        cosine-weighted hemisphere rays per pixel sample that travel `radius` unoccluded, over `pixel_samples` jittered samples.  Returns
+        [H, W] float32: a numpy array (rtHipSceneAmbientOcclusion) -- `out` if given, else a new one of zeros -- or, when `out` is a
+        float32 [H, W] tensor on this scene's device, that tensor, filled by rtHipSceneAmbientOcclusionDevice on torch's current stream
+        (or `stream`).  Only the pixels of this instance's tiles are written."""
+        p = ao_params(rays, radius, pixel_samples, seed)
+        sc = self.scene
+        shape = (sc.height, sc.width)
+        if hasattr(out, "data_ptr"):
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != shape \
+                    or not out.is_contiguous():
+                raise ValueError(f"ambient_occlusion: out must be a contiguous float32 {shape} tensor on {dev}")
+            cur = torch.cuda.current_stream(dev)
+            if stream and stream != cur.cuda_stream:
+                run = torch.cuda.ExternalStream(stream, device=dev)
+            elif cur.cuda_stream:
+                run = cur
+            else:  # the null stream would mean "the scene's own stream" to the library (see _intersect_torch)
+                if getattr(self, "_side_stream", None) is None:
+                    self._side_stream = torch.cuda.Stream(dev)
+                run = self._side_stream
+            if run is not cur:
+                run.wait_stream(cur)
+            self._check(lib().rtHipSceneAmbientOcclusionDevice(self.handle, C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(run.cuda_stream)),
+                        "rtHipSceneAmbientOcclusionDevice")
+            if run is not cur:
+                cur.wait_stream(run)
+                out.record_stream(run)
+            return out
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags.c_contiguous):
+            raise ValueError(f"ambient_occlusion: out must be a C-contiguous float32 {shape} array")
+        self._check(lib().rtHipSceneAmbientOcclusion(self.handle, C.byref(p), _ptr(out)), "rtHipSceneAmbientOcclusion")
+        return out
 
     def intersect(self, origins, directions, tmin=0.0, tmax=np.inf, exclude=None, stream: int = 0) -> dict:
         """What rays hit in this scene: the reference's grid walk, RayIntersectsTriangles (raytrace_opencl.c:324-401), bit for bit

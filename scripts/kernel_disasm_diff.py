@@ -1,6 +1,7 @@
 """Do two source trees compile to the same GPU code?  Compiles every .hip file of opencl_render_amd/csrc in both trees for gfx950 (device
 code only, the Makefile's DEVFLAGS), disassembles the code objects with llvm-objdump and compares them symbol by symbol (kernels and the device functions not inlined).  The address
-comments llvm-objdump prints are dropped; the instruction text, relative branch offsets included, is compared.  Needs no GPU.
+comments llvm-objdump prints are dropped, and so is the padding (s_nop, zero bytes) after a kernel's s_endpgm (it depends on where the next symbol
+starts); the instruction text, relative branch offsets included, is compared.  Needs no GPU.
 
     python scripts/kernel_disasm_diff.py --base /path/to/parent/checkout [--new .] [--keep DIR]
 
@@ -40,6 +41,9 @@ def disassemble(tree, out, rocm):
                 body[cur] = []
             elif cur is not None and line.strip():
                 body[cur].append(re.sub(r"\s*//.*$", "", line).strip())
+        for insns in body.values():  # the padding up to the next symbol's alignment (s_nop, zero bytes: "...") is not the function's code
+            while insns and insns[-1] in ("s_nop 0", "...") and "s_endpgm" in insns:
+                insns.pop()
         kernels[name] = body
     return kernels
 
