@@ -429,6 +429,56 @@ int  rtHipSceneAmbientOcclusion(rtHipScene *scene, const rtHipAoParams *params, 
  * inside one allocation); a host pointer returns -1. */
 int  rtHipSceneAmbientOcclusionDevice(rtHipScene *scene, const rtHipAoParams *params, void *out, void *stream);
 
+/* AMBIENT OCCLUSION BAKE: a W x H texture of ambient occlusion over the scene's UV layout.  Each texel centre is mapped to the surface
+ * point of the triangle whose UV triangle covers it, and the AO rays of the block above are traced from there with the same walk.  It
+ * needs geometry, UVs, corner normals and the grid only: it works on every instance (whatever its tiles, passes or pipeline), ignores
+ * the tile set, and changes nothing a later frame, read-back, pass, denoise or AO call produces.  The arithmetic is IEEE fp32 + - * /,
+ * sqrt and compares (no FMA, division and square root correctly rounded) plus the AO block's hash; dot and cross as defined there.
+ * tests/bake_oracle.py restates it in numpy and the device output equals it bit for bit.
+ *
+ * Parameters: W, H >= 1 with W*H <= 2^26; raysPerTexel R in 1..256; radius > 0 (+inf allowed, NaN not); seed any u32; dilate G in 0..64;
+ * the triangles firstTriangle .. firstTriangle + triangleCount - 1 are selected (first + count <= T; triangleCount = 0xffffffff selects
+ * first .. T - 1, first <= T), and of those, when matchMaterial is non-zero, only the ones whose material id equals `material` (-1 is an id).
+ * Texel (x, y), index t = y*W + x, row 0 at v near 0 (the top row, as the renderer's textures are read): cu = ((float)x + 0.5f) / (float)W,
+ * cv = ((float)y + 0.5f) / (float)H.  A selected triangle with corner UVs uvA, uvB, uvC (its triangleUv[3i .. 3i+2]) covers it iff
+ * l1 >= 0 && l2 >= 0 && l1 + l2 <= 1, with e1 = uvB - uvA, e2 = uvC - uvA, q = (cu, cv) - uvA per component,
+ * den = e1.x*e2.y - e1.y*e2.x, l1 = (q.x*e2.y - q.y*e2.x) / den, l2 = (e1.x*q.y - e1.y*q.x) / den.  NaN compares false: a triangle
+ * with den = 0 or a NaN UV covers nothing.  UVs are not wrapped (the renderer's look-up wraps them; the bake clips to [0,1]^2).  Of
+ * several covering triangles the smallest id wins.  Every bit pattern of the UVs has a defined answer.
+ * A covered texel, winner tri: P = (a + l1*ab) + l2*ac per component (a, ab, ac = b - a, c - a from the vertices; l1 weighs b, l2 c);
+ * n = cross(ac, ab); s = (nA + nB) + nC from the corner normals; n = -n if dot(n, s) < 0; m = dot(n, n); if !(m > 0) the texel counts
+ * R open rays, else n^ = n / sqrt(m) (three divisions) and AO ray r (0 <= r < R) is the AO block's ray around n^ with counter
+ * c = ((t*(R + 1) + 1 + r)*32 + draw) (the AO counter at p = t, Sp = 1, j = 0): o = P, tmin = 0, tmax = radius, excluding tri, occluded
+ * iff the walk returns a triangle.  Value: (float)U / (float)R for a covered texel with U open rays, 0 for an uncovered one.  Triangle
+ * map: the winner, 0xffffffff where nothing covers the texel.
+ * Dilation (a gutter fill): G Jacobi passes.  A texel is valid at the start iff it is covered.  In a pass, an invalid texel sums the
+ * values of its valid neighbours inside the map, rows dy = -1..1 outer, dx = -1..1 inner, itself skipped, in that order from +0.0f; if
+ * k > 0 of them are valid it takes sum / (float)k and is valid from the next pass on.  The triangle map is not dilated.
+ * Out of scope: one sample per texel (no super-sampling), no conservative coverage of UV slivers, and the renderer's texture look-up
+ * (floor(u*(w-1))) sees a baked map shifted by up to one texel.
+ * The scratch (winners, counters and values, 12 bytes per texel; one chunk of texels, 32 bytes each, "bake_texels" of rtHipTune; a list
+ * of 4 bytes per triangle) belongs to the scene: made on first use, grown for a larger map, counted in rtHipSceneBytes, freed with the
+ * scene.  Calls on different streams are ordered by an event.  Both calls refuse, with -1, the last-error text set and nothing launched:
+ * a NULL scene, params or ao, a parameter out of range, a triangle range past T. */
+typedef struct rtHipBakeParams {
+    cl_uint  width, height;   /* W, H */
+    cl_uint  raysPerTexel;    /* R */
+    cl_float radius;          /* tmax of the AO rays */
+    cl_uint  seed;
+    cl_uint  dilate;          /* G */
+    cl_uint  firstTriangle, triangleCount;
+    cl_int   material;        /* the material filter, used when matchMaterial != 0 */
+    cl_uint  matchMaterial;
+} rtHipBakeParams;
+/* R = 16, radius = +inf, seed = 0, G = 2, every triangle (first 0, count 0xffffffff), no material filter; width and height are set to 0,
+ * which the calls refuse: the caller sets them. */
+void rtHipBakeDefaults(rtHipBakeParams *params);
+/* HOST W x H arrays, row-major: ao f32, triangle u32 (may be NULL); synchronous, on the scene's stream. */
+int  rtHipSceneBakeAmbientOcclusion(rtHipScene *scene, const rtHipBakeParams *params, cl_float *ao, cl_uint *triangle);
+/* DEVICE W x H arrays of the scene's device (4-byte aligned; triangle may be NULL), asynchronous on `stream` (a hipStream_t as void*;
+ * NULL = the scene's stream).  Checked like rtHipSceneIntersectDevice's pointers; a host pointer returns -1. */
+int  rtHipSceneBakeAmbientOcclusionDevice(rtHipScene *scene, const rtHipBakeParams *params, void *ao, void *triangle, void *stream);
+
 /* Average device time in milliseconds of one rtHipRenderTiles frame (all its kernels) over the frames recorded since
  * the last call (HIP events on the launch stream), and the number of frames.  Returns 0 on success. */
 int rtHipKernelTime(rtHipScene *scene, double *avgMs, uint64_t *launches);
@@ -620,7 +670,8 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
  * "plan_rounds", "plan_grid_tiny", "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
  * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
  * and most 2^32 - 1; above it they return -3), "query_rays" (rays per staging chunk of rtHipSceneIntersect, default 2^20), and
- * "ao_samples" (pixel samples per chunk of the ambient occlusion calls, default 2^20, at most 2^24).  Returns 0, -1 for an unknown key. */
+ * "ao_samples" (pixel samples per chunk of the ambient occlusion calls, default 2^20, at most 2^24), and "bake_texels" (texels per chunk
+ * of the ambient occlusion bake, default 2^20, at most 2^24; a call uses at most 2^31 / R).  Returns 0, -1 for an unknown key. */
 int rtHipTune(const char *key, double value);
 
 /* TEST-ONLY: device addresses held by the first scene of RaytraceAll's cache -- triangle records, shading rows, the grid's pair

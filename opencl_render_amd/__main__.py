@@ -19,6 +19,12 @@ denoised with rtHipDenoise on device 0.
 ``--ao PATH`` also writes the scene's ambient occlusion (include/raytrace_hip.h, "AMBIENT OCCLUSION"), traced on the device from the
 scene's camera, to PATH: .pfm (f32) or .pgm (u16 quantised like the denoiser's output, written as 8 bits).  ``--ao-rays``,
 ``--ao-radius``, ``--ao-samples`` and ``--ao-seed`` set its parameters.  For the all-GPUs device it runs on device 0.
+
+``--bake-ao PATH`` also bakes ambient occlusion into a texture over the scene's UVs (include/raytrace_hip.h, "AMBIENT OCCLUSION
+BAKE") and writes it to PATH like ``--ao``: .pfm (f32) or .pgm (8 bits).  ``--bake-size W H`` (default 512 512), ``--bake-rays``,
+``--bake-radius``, ``--bake-seed`` and ``--bake-dilate`` set its parameters; ``--bake-material M`` or ``--bake-triangles FIRST COUNT``
+selects what is baked; ``--bake-atlas`` bakes over a grid atlas (scene.grid_atlas_uv) instead of the scene's own UVs.  For the
+all-GPUs device it runs on device 0.
 """
 import argparse
 import sys
@@ -50,6 +56,16 @@ def parser():
     ap.add_argument("--ao-radius", type=float, default=float("inf"), help="--ao: how far an occluder counts (scene units; default: any distance)")
     ap.add_argument("--ao-samples", type=int, default=1, help="--ao: jittered primary samples per pixel (1..64)")
     ap.add_argument("--ao-seed", type=int, default=0, help="--ao: seed of the ray directions (u32)")
+    ap.add_argument("--bake-ao", metavar="PATH", help="also bake ambient occlusion over the UVs into PATH (.pfm or .pgm)")
+    ap.add_argument("--bake-size", type=int, nargs=2, metavar=("W", "H"), default=(512, 512), help="--bake-ao: texture size")
+    ap.add_argument("--bake-rays", type=int, default=16, help="--bake-ao: hemisphere rays per texel (1..256)")
+    ap.add_argument("--bake-radius", type=float, default=float("inf"), help="--bake-ao: how far an occluder counts (default: any distance)")
+    ap.add_argument("--bake-seed", type=int, default=0, help="--bake-ao: seed of the ray directions (u32)")
+    ap.add_argument("--bake-dilate", type=int, default=2, help="--bake-ao: gutter-fill passes (0..64)")
+    sel = ap.add_mutually_exclusive_group()
+    sel.add_argument("--bake-material", type=int, metavar="M", help="--bake-ao: bake only the triangles of material M")
+    sel.add_argument("--bake-triangles", type=int, nargs=2, metavar=("FIRST", "COUNT"), help="--bake-ao: bake only these triangles")
+    ap.add_argument("--bake-atlas", action="store_true", help="--bake-ao: bake over a grid atlas, one cell per triangle, not the scene's UVs")
     return ap
 
 
@@ -62,6 +78,8 @@ def parse_args(argv=None):
         ap.error("--denoise PATH must end in .bmp, .ppm or .pfm")
     if args.ao and not args.ao.lower().endswith((".pfm", ".pgm")):
         ap.error("--ao PATH must end in .pfm or .pgm")
+    if args.bake_ao and not args.bake_ao.lower().endswith((".pfm", ".pgm")):
+        ap.error("--bake-ao PATH must end in .pfm or .pgm")
     return args
 
 
@@ -79,6 +97,28 @@ def write_ao(sc, path: str, device: int, rays: int, radius: float, samples: int,
     else:
         frontend.write_pgm(path, raytrace.quantise(ao[..., None].repeat(3, -1))[0])
     return ao
+
+
+def write_bake_ao(sc, path: str, device: int, size, rays: int, radius: float, seed: int, dilate: int, triangles=None, material=None,
+                  atlas: bool = False) -> dict:
+    """ResidentScene.bake_ambient_occlusion on HIP device `device` -> PATH (.pfm: f32; .pgm: u16 quantised like raytrace.quantise, 8
+    bits written); atlas: over scene.grid_atlas_uv instead of the scene's UVs.  Returns the bake's {"ao", "triangle"}."""
+    import dataclasses
+
+    from . import frontend, raytrace, scene
+    W, H = (int(v) for v in size)
+    if atlas:
+        sc = dataclasses.replace(sc, tri_uv=scene.grid_atlas_uv(sc.triangle_count, max(W, H)))
+    rs = raytrace.ResidentScene(sc, device)
+    try:
+        res = rs.bake_ambient_occlusion(W, H, rays=rays, radius=radius, seed=seed, dilate=dilate, triangles=triangles, material=material)
+    finally:
+        rs.close()
+    if path.lower().endswith(".pfm"):
+        frontend.write_pfm(path, res["ao"])
+    else:
+        frontend.write_pgm(path, raytrace.quantise(res["ao"][..., None].repeat(3, -1))[0])
+    return res
 
 
 def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool = True, denoise: bool = False):
@@ -170,6 +210,10 @@ def main(argv=None):
     if args.ao:
         gpus = raytrace.lib().rtHipDeviceCount()
         write_ao(sc, args.ao, 0 if args.device == gpus + 1 else args.device - 1, args.ao_rays, args.ao_radius, args.ao_samples, args.ao_seed)
+    if args.bake_ao:
+        gpus = raytrace.lib().rtHipDeviceCount()
+        write_bake_ao(sc, args.bake_ao, 0 if args.device == gpus + 1 else args.device - 1, args.bake_size, args.bake_rays, args.bake_radius,
+                      args.bake_seed, args.bake_dilate, triangles=args.bake_triangles, material=args.bake_material, atlas=args.bake_atlas)
     if args.out.lower().endswith(".ppm"):
         frontend.write_ppm(args.out, r, g, b)
     else:

@@ -52,6 +52,12 @@ extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays
 extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream);
 extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
                                            hipStream_t stream);
+extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
+extern "C" hipError_t rtw_launch_bake_points(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
+extern "C" hipError_t rtw_launch_bake_ao(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
+extern "C" hipError_t rtw_launch_bake_finish(uint32_t texels, const uint32_t *win, const uint32_t *counter, uint32_t rays, float fill, float *out,
+                                             uint32_t *tri, hipStream_t stream);
+extern "C" hipError_t rtw_launch_bake_dilate(uint32_t W, uint32_t H, const float *src, float *dst, uint32_t last, hipStream_t stream);
 
 extern "C" hipError_t rtd_launch_guides(uint32_t n, const float *colour, const float *normal, const float *albedo, void *c0, void *g0, void *g1,
                                         hipStream_t stream);
@@ -116,6 +122,7 @@ struct Tuning {
     uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
     uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
     uint32_t aoSamples = 1u << 20;  // pixel samples per chunk of the ambient occlusion calls (32 bytes each of scene-owned scratch)
+    uint32_t bakeTexels = 1u << 20; // texels per chunk of the ambient occlusion bake (32 bytes each of scene-owned scratch)
 };
 // Read at the entry points only (scene create, RaytraceAll, the two public device builders): a build works from one snapshot.
 Tuning g_tune;
@@ -329,6 +336,12 @@ struct rtHipScene {
     uint64_t aoBytes = 0;
     uint32_t aoChunk = 0;
     hipEvent_t aoDone = nullptr;
+    // ambient occlusion bake scratch (rtHipSceneBakeAmbientOcclusion*), made on first use and grown for a larger map: winners, counters
+    // and a second value plane for W*H texels, the big list, one chunk of texels; the event as above
+    char *bakeBuf = nullptr;
+    uint64_t bakeBytes = 0, bakeTexels = 0;
+    uint32_t bakeChunk = 0;
+    hipEvent_t bakeDone = nullptr;
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -1223,6 +1236,8 @@ void rtHipSceneDestroy(rtHipScene *sc)
     if (sc->queryHost) Stager::pool().give(sc->queryHost, sc->queryBytes);
     if (sc->aoBuf) (void)hipFree(sc->aoBuf);
     if (sc->aoDone) (void)hipEventDestroy(sc->aoDone);
+    if (sc->bakeBuf) (void)hipFree(sc->bakeBuf);
+    if (sc->bakeDone) (void)hipEventDestroy(sc->bakeDone);
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
     sc->stager.destroy();
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
@@ -1663,6 +1678,116 @@ int rtHipSceneAmbientOcclusion(rtHipScene *sc, const rtHipAoParams *p, cl_float 
     return 0;
 }
 
+// ---- ambient occlusion bake (include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE"; kernels in rt_wavefront.hip, rt_bake_*) -------------
+void rtHipBakeDefaults(rtHipBakeParams *p)
+{
+    if (!p) return;
+    p->width = 0; p->height = 0;
+    p->raysPerTexel = 16;
+    p->radius = HUGE_VALF;
+    p->seed = 0;
+    p->dilate = 2;
+    p->firstTriangle = 0; p->triangleCount = 0xffffffffu;
+    p->material = 0; p->matchMaterial = 0;
+}
+
+static int bake_check(const rtHipScene *sc, const rtHipBakeParams *p, const void *ao)
+{
+    if (!sc || !p || !ao) return fail("ambient occlusion bake: null scene, parameters or ao");
+    if (p->width < 1 || p->height < 1 || (uint64_t)p->width * p->height > (1ull << 26))
+        return fail("ambient occlusion bake: a %u x %u map is not 1 .. 2^26 texels", p->width, p->height);
+    if (p->raysPerTexel < 1 || p->raysPerTexel > 256) return fail("ambient occlusion bake: raysPerTexel %u is not in 1..256", p->raysPerTexel);
+    if (!(p->radius > 0.f)) return fail("ambient occlusion bake: radius %g is not > 0", (double)p->radius);
+    if (p->dilate > 64) return fail("ambient occlusion bake: dilate %u is not in 0..64", p->dilate);
+    const uint64_t T = sc->dev.triangleCount;
+    if (p->triangleCount == 0xffffffffu ? p->firstTriangle > T : (uint64_t)p->firstTriangle + p->triangleCount > T)
+        return fail("ambient occlusion bake: triangles %u + %u reach past the scene's %llu", p->firstTriangle, p->triangleCount, (unsigned long long)T);
+    return 0;
+}
+
+// Enqueues the whole bake on `st`: rasterise, the chunks' points and AO launches, finish and dilation.  The values go to `ao` and the
+// winners to `tri` (may be null), both row-major W x H device arrays; null `ao` = into the scratch, whose value plane bake_run returns
+// in `result` (the host entry point reads it and the winners from there).
+static int bake_run(rtHipScene *sc, const rtHipBakeParams *p, float *ao, uint32_t *tri, hipStream_t st, const char **result = nullptr)
+{
+    const uint64_t texels = (uint64_t)p->width * p->height;
+    const uint32_t T = sc->dev.triangleCount, chunkWant = std::min<uint32_t>(std::max<uint32_t>(sc->tune.bakeTexels, 1u), 1u << 24);
+    const uint64_t bigBytes = ((uint64_t)T * 4 + 255) & ~255ull;
+    if (!sc->bakeBuf || texels > sc->bakeTexels || chunkWant != sc->bakeChunk) {
+        const uint64_t cap = std::max<uint64_t>(texels, sc->bakeTexels), capPlane = (cap * 4 + 255) & ~255ull;
+        if (sc->bakeBuf) { // a larger map: the last call's use of the old scratch ends first
+            HIP_OK(hipEventSynchronize(sc->bakeDone));
+            (void)hipFree(sc->bakeBuf);
+            sc->bytes -= sc->bakeBytes;
+            sc->bakeBuf = nullptr; sc->bakeBytes = 0; sc->bakeTexels = 0;
+        }
+        const uint64_t bytes = 3 * capPlane + bigBytes + 256 + (uint64_t)chunkWant * 32; // win | counter | values | big list | lengths | hit list
+        void *buf = nullptr;
+        const hipError_t e = hipMalloc(&buf, bytes);
+        if (e != hipSuccess) return fail("ambient occlusion bake: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        if (!sc->bakeDone) {
+            const hipError_t ee = hipEventCreateWithFlags(&sc->bakeDone, hipEventDisableTiming);
+            if (ee != hipSuccess) { (void)hipFree(buf); sc->bakeDone = nullptr; return fail("ambient occlusion bake: hipEventCreate failed: %s", hipGetErrorString(ee)); }
+        }
+        sc->bakeBuf = (char *)buf; sc->bakeBytes = bytes; sc->bakeTexels = cap; sc->bakeChunk = chunkWant;
+        sc->bytes += bytes;
+    } else HIP_OK(hipStreamWaitEvent(st, sc->bakeDone, 0)); // the last call's use of the scratch, on whatever stream it ran
+    const uint64_t capPlane = (sc->bakeTexels * 4 + 255) & ~255ull;
+    uint32_t *win = (uint32_t *)sc->bakeBuf, *counter = (uint32_t *)(sc->bakeBuf + capPlane);
+    float *values = (float *)(sc->bakeBuf + 2 * capPlane);
+    char *tail = sc->bakeBuf + 3 * capPlane;
+    RtBakeArgs A;
+    A.width = p->width; A.height = p->height; A.raysPerTexel = p->raysPerTexel; A.seed = p->seed; A.fastQuotient = sc->tune.fastQuotient ? 1u : 0u;
+    A.radius = p->radius; A.material = p->material; A.matchMaterial = p->matchMaterial ? 1u : 0u;
+    A.win = win; A.counter = counter; A.bigList = (uint32_t *)tail; A.bigCount = (uint32_t *)(tail + bigBytes); A.hits = A.bigCount + 1;
+    A.rec = (float4 *)(tail + bigBytes + 256);
+    HIP_OK(hipMemsetAsync(win, 0xff, texels * 4, st));
+    HIP_OK(hipMemsetAsync(A.bigCount, 0, 4, st));
+    A.first = p->firstTriangle; A.count = p->triangleCount == 0xffffffffu ? T - p->firstTriangle : p->triangleCount; A.base = 0;
+    HIP_OK(rtw_launch_bake_raster(&sc->dev, &A, st));
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(sc->bakeChunk, (1ull << 31) / p->raysPerTexel); // (chunk x R <= 2^31)
+    for (uint64_t base = 0; base < texels; base += chunk) {
+        A.base = base;
+        A.count = (uint32_t)std::min<uint64_t>(chunk, texels - base);
+        HIP_OK(hipMemsetAsync(A.hits, 0, 4, st));
+        HIP_OK(rtw_launch_bake_points(&sc->dev, &A, st));
+        HIP_OK(rtw_launch_bake_ao(&sc->dev, &A, st));
+    }
+    // values: counter's plane (in place) and `values` in turn, the last pass into `ao` -- or, for the host, the plane it would read next
+    float *planes[2] = { (float *)counter, values };
+    const uint32_t G = p->dilate;
+    float *dst = ao ? ao : planes[G & 1u];
+    HIP_OK(rtw_launch_bake_finish((uint32_t)texels, win, counter, p->raysPerTexel, G ? -1.f : 0.f, G ? planes[0] : dst, tri, st));
+    for (uint32_t g = 1; g <= G; ++g)
+        HIP_OK(rtw_launch_bake_dilate(p->width, p->height, planes[(g - 1) & 1u], g == G ? dst : planes[g & 1u], g == G ? 1u : 0u, st));
+    HIP_OK(hipEventRecord(sc->bakeDone, st));
+    if (result) *result = (const char *)dst;
+    return 0;
+}
+
+int rtHipSceneBakeAmbientOcclusionDevice(rtHipScene *sc, const rtHipBakeParams *p, void *ao, void *triangle, void *stream)
+{
+    if (bake_check(sc, p, ao) != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    const uint64_t bytes = (uint64_t)p->width * p->height * 4;
+    if (query_pointer_ok(sc->device, "the scene", ao, bytes, 4, "ao") != 0) return -1;
+    if (triangle && query_pointer_ok(sc->device, "the scene", triangle, bytes, 4, "triangle") != 0) return -1;
+    return bake_run(sc, p, (float *)ao, (uint32_t *)triangle, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtHipSceneBakeAmbientOcclusion(rtHipScene *sc, const rtHipBakeParams *p, cl_float *ao, cl_uint *triangle)
+{
+    if (bake_check(sc, p, ao) != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    const char *values = nullptr;
+    if (bake_run(sc, p, nullptr, nullptr, sc->stream, &values) != 0) return -1;
+    const size_t bytes = (size_t)p->width * p->height * 4;
+    HIP_OK(hipMemcpyAsync(ao, values, bytes, hipMemcpyDeviceToHost, sc->stream));
+    if (triangle) HIP_OK(hipMemcpyAsync(triangle, sc->bakeBuf, bytes, hipMemcpyDeviceToHost, sc->stream)); // (the winners' plane)
+    HIP_OK(hipStreamSynchronize(sc->stream));
+    return 0;
+}
+
 // ---- denoiser (include/raytrace_hip.h, "DENOISER"; kernels in rt_denoise.hip) ------------------------------------------------
 // Filter scratch of a W x H image: C^i and C^(i+1) as float4 (ping-pong), then the guides G0 = (n^, z) and G1 = (albedo, 0) as float4.
 #define RT_DENOISE_MAX_PIXELS (1ull << 27)
@@ -2036,7 +2161,7 @@ int rtHipTune(const char *key, double value)
         { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
         { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
-        { "ao_samples", &T.aoSamples, nullptr, 1u << 22 },
+        { "ao_samples", &T.aoSamples, nullptr, 1u << 22 }, { "bake_texels", &T.bakeTexels, nullptr, 1u << 24 },
         { "state_mb", nullptr, &T.stateMb, HUGE_VAL }, { "build_key_cap", nullptr, &T.buildKeyCap, 1e18 }, { "build_list_limit", nullptr, &T.buildListLimit },
     };
     for (const Key &e : table) {

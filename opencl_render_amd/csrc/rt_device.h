@@ -228,4 +228,23 @@ struct RtAoArgs {
     uint32_t *counter; // [tileCount * 128*128], zeroed before the first chunk
 };
 
+// ---- ambient occlusion bake (rt_wavefront.hip, rt_bake_*; definition in include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE") -----------
+// Texels t = y*W + x.  The rasterise kernels atomicMin the selected triangles into win[t] (all ones before).  Then per chunk of `count`
+// texels from t = base: the points kernel settles uncovered and zero-normal texels in counter[t] and appends the others to the hit list,
+// rec[*hits++] = {P.xyz, tri} {n^.xyz, t - base}; the AO kernel traces R rays per listed texel and adds its open rays into counter[t].
+struct RtBakeArgs {
+    uint32_t width, height, raysPerTexel, seed, fastQuotient;
+    float radius;
+    uint32_t first, count;  // rasterise: the triangle range; chunk kernels: texels base .. base + count - 1
+    int32_t material;
+    uint32_t matchMaterial;
+    uint64_t base;
+    uint32_t *win;      // [W*H] winning triangle per texel
+    uint32_t *counter;  // [W*H] open rays per texel
+    uint32_t *bigList;  // [triangles] triangles whose texel rectangle is rasterised by a workgroup each
+    uint32_t *bigCount; // its length
+    float4 *rec;        // [chunk][2] the hit list
+    uint32_t *hits;     // its length, zeroed before the chunk's points launch
+};
+
 #endif

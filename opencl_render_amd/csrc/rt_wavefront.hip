@@ -2419,3 +2419,252 @@ extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32
     hipLaunchKernelGGL(rt_ao_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, *scene, counter, (float)samplesTimesRays, out, rowMajor);
     return hipGetLastError();
 }
+
+// ---- ambient occlusion bake (rtHipSceneBakeAmbientOcclusion*; include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE"; buffers in rt_device.h,
+// RtBakeArgs) ------------------------------------------------------------------------------------------------------------------------
+// The AO rays are the AO block's (ao_mix, ao_uniform, ao_walk): each gets exactly the answer rtHipSceneIntersect gives it.
+#define RT_BAKE_BIG_RECT 1024u // texel rectangles larger than this are rasterised by every workgroup of rt_bake_raster_big_kernel
+#define RT_BAKE_BIG_BLOCKS 1024u
+
+// The coverage test of texel centre (cu, cv) against UV corners uv[0..5] = uvA, uvB, uvC, and its barycentrics (l1 weighs b, l2 c).
+__device__ __forceinline__ bool bake_cover(const float *uv, float cu, float cv, float &l1, float &l2)
+{
+    const float e1x = uv[2] - uv[0], e1y = uv[3] - uv[1], e2x = uv[4] - uv[0], e2y = uv[5] - uv[1], qx = cu - uv[0], qy = cv - uv[1];
+    const float den = e1x * e2y - e1y * e2x;
+    l1 = (qx * e2y - qy * e2x) / den;
+    l2 = (e1x * qy - e1y * qx) / den;
+    return l1 >= 0.f && l2 >= 0.f && l1 + l2 <= 1.f;
+}
+__device__ __forceinline__ float bake_centre(uint32_t i, uint32_t n) { return ((float)i + 0.5f) / (float)n; }
+
+// The texel rectangle outside which bake_cover provably fails for UV corners uv[0..5]; false if no texel can pass.  A den that is 0 or
+// NaN (a NaN UV gives one) covers nothing.  Otherwise the UV bounding box is grown by a bound on the test's rounding (in double):
+// with E the largest |e| component, Q = 1 + max|uvA|, u = 2^-24, the computed den is within 8uE^2 of the exact D of the rounded edges,
+// and a texel that passes has exact barycentrics within delta = 4(u + 8u(QE + 2E^2)/D) of [0, 1], so its centre lies within 6 delta E
+// (+ 4uQ for the centre's own rounding) of the box, plus one texel.  An infinite UV, or D <= 32uE^2 (den may be rounding noise), gets
+// the whole map.
+__device__ __forceinline__ bool bake_rect(const float *uv, uint32_t W, uint32_t H, uint32_t &x0, uint32_t &x1, uint32_t &y0, uint32_t &y1)
+{
+    const float e1x = uv[2] - uv[0], e1y = uv[3] - uv[1], e2x = uv[4] - uv[0], e2y = uv[5] - uv[1];
+    const float den = e1x * e2y - e1y * e2x;
+    if (den == 0.f || den != den) return false;
+    x0 = 0; x1 = W - 1; y0 = 0; y1 = H - 1;
+    bool finite = fabsf(den) < RT_INF;
+    for (int k = 0; k < 6; ++k) finite = finite && fabsf(uv[k]) < RT_INF;
+    if (!finite) return true;
+    const double u = 0x1p-24, E = fmax(fmax(fabs((double)e1x), fabs((double)e1y)), fmax(fabs((double)e2x), fabs((double)e2y)));
+    const double D = fabs((double)e1x * (double)e2y - (double)e1y * (double)e2x);
+    if (!(D > 32.0 * u * E * E)) return true;
+    const double Q = 1.0 + fmax(fabs((double)uv[0]), fabs((double)uv[1]));
+    const double delta = 4.0 * (u + 8.0 * u * (Q * E + 2.0 * E * E) / D), m = 6.0 * delta * E + 4.0 * u * Q;
+    const double umin = fmin(fmin((double)uv[0], (double)uv[2]), (double)uv[4]) - m, umax = fmax(fmax((double)uv[0], (double)uv[2]), (double)uv[4]) + m;
+    const double vmin = fmin(fmin((double)uv[1], (double)uv[3]), (double)uv[5]) - m, vmax = fmax(fmax((double)uv[1], (double)uv[3]), (double)uv[5]) + m;
+    const double lx = floor(umin * W - 0.5) - 1.0, hx = ceil(umax * W - 0.5) + 1.0, ly = floor(vmin * H - 0.5) - 1.0, hy = ceil(vmax * H - 0.5) + 1.0;
+    if (hx < 0.0 || hy < 0.0 || lx > (double)(W - 1) || ly > (double)(H - 1)) return false;
+    x0 = lx > 0.0 ? (uint32_t)lx : 0u; y0 = ly > 0.0 ? (uint32_t)ly : 0u;
+    x1 = hx < (double)(W - 1) ? (uint32_t)hx : W - 1; y1 = hy < (double)(H - 1) ? (uint32_t)hy : H - 1;
+    return true;
+}
+__device__ __forceinline__ void bake_texel(const float *uv, uint32_t W, uint32_t H, uint32_t x, uint32_t y, uint32_t tri, uint32_t *win)
+{
+    float l1, l2;
+    if (bake_cover(uv, bake_centre(x, W), bake_centre(y, H), l1, l2)) atomicMin(win + (size_t)y * W + x, tri);
+}
+
+// One thread per triangle of the range A.first .. A.first + A.count - 1 that passes the material filter: the texels of its rectangle,
+// or -- a rectangle of more than RT_BAKE_BIG_RECT texels -- an entry of the big list.  atomicMin: the smallest covering id wins
+// whatever the order.
+__global__ __launch_bounds__(256) void rt_bake_raster_kernel(const RtDevScene S, const RtBakeArgs A)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.count) return;
+    const uint32_t tri = A.first + i;
+    const float *sh = S.triShade + 24 * (size_t)tri;
+    if (A.matchMaterial && __float_as_int(sh[21]) != A.material) return;
+    float uv[6];
+    for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
+    uint32_t x0, x1, y0, y1;
+    if (!bake_rect(uv, A.width, A.height, x0, x1, y0, y1)) return;
+    if ((uint64_t)(x1 - x0 + 1) * (uint64_t)(y1 - y0 + 1) > RT_BAKE_BIG_RECT) {
+        A.bigList[atomicAdd(A.bigCount, 1u)] = tri;
+        return;
+    }
+    for (uint32_t y = y0; y <= y1; ++y)
+        for (uint32_t x = x0; x <= x1; ++x) bake_texel(uv, A.width, A.height, x, y, tri, A.win);
+}
+
+// The big list's triangles in turn, the texels of each one's rectangle dealt over every thread of the launch (one quad can cover the
+// whole map: a workgroup per triangle would leave the chip idle).
+__global__ __launch_bounds__(256) void rt_bake_raster_big_kernel(const RtDevScene S, const RtBakeArgs A)
+{
+    const uint32_t n = *A.bigCount;
+    const uint32_t stride = gridDim.x * 256u;
+    for (uint32_t b = 0; b < n; ++b) {
+        const uint32_t tri = A.bigList[b];
+        const float *sh = S.triShade + 24 * (size_t)tri;
+        float uv[6];
+        for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
+        uint32_t x0, x1, y0, y1;
+        bake_rect(uv, A.width, A.height, x0, x1, y0, y1); // (true: it was listed)
+        const uint32_t w = x1 - x0 + 1, area = w * (y1 - y0 + 1); // (at most W*H <= 2^26)
+        for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < area; k += stride) {
+            const uint32_t ky = k / w;
+            bake_texel(uv, A.width, A.height, x0 + (k - ky * w), y0 + ky, tri, A.win);
+        }
+    }
+}
+
+// One lane per texel of the chunk: its winner, the surface point and the oriented unit normal.  An uncovered texel's counter is set to
+// 0 and a zero-normal texel's to R here; the others' to 0, and they are appended to the hit list (one atomic per wave).
+__global__ __launch_bounds__(256) void rt_bake_points_kernel(const RtDevScene S, const RtBakeArgs A)
+{
+    const uint32_t at = blockIdx.x * 256u + threadIdx.x;
+    if (at >= A.count) return;
+    const uint32_t t = (uint32_t)(A.base + at), tri = A.win[t];
+    V3 P = mk(0.f, 0.f, 0.f), n = P;
+    bool trace = false;
+    uint32_t open = 0;
+    if (tri != RT_NONE) {
+        const float *sh = S.triShade + 24 * (size_t)tri;
+        float uv[6];
+        for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
+        const uint32_t y = t / A.width, x = t - y * A.width;
+        float l1, l2;
+        bake_cover(uv, bake_centre(x, A.width), bake_centre(y, A.height), l1, l2); // (true: it won)
+        const float4 *rec = reinterpret_cast<const float4 *>(S.triRec) + 4 * (size_t)tri;
+        const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2]; // a.xyz ab.x | ab.yz ac.xy | ac.z n.xyz
+        P = mk((r0.x + l1 * r0.w) + l2 * r1.z, (r0.y + l1 * r1.x) + l2 * r1.w, (r0.z + l1 * r1.y) + l2 * r2.x);
+        n = mk(r2.y, r2.z, r2.w);
+        const V3 s = mk((sh[6] + sh[9]) + sh[12], (sh[7] + sh[10]) + sh[13], (sh[8] + sh[11]) + sh[14]);
+        if (dot3(n, s) < 0.f) n = mk(-n.x, -n.y, -n.z);
+        const float m = dot3(n, n);
+        if (m > 0.f) {
+            const float r = sqrt_rn(m);
+            n = mk(n.x / r, n.y / r, n.z / r);
+            trace = true;
+        } else open = A.raysPerTexel;
+    }
+    A.counter[t] = open;
+    const uint32_t slot = wave_append(A.hits, trace);
+    if (trace) {
+        A.rec[2 * (size_t)slot] = make_float4(P.x, P.y, P.z, __uint_as_float(tri));
+        A.rec[2 * (size_t)slot + 1] = make_float4(n.x, n.y, n.z, __uint_as_float(at));
+    }
+}
+
+// One lane per AO ray of the chunk's hit list, a texel's R rays on consecutive lanes; open rays are counted per texel with
+// rt_ao_kernel's ballot and one atomic per run of a wave.
+__global__ __launch_bounds__(256) void rt_bake_ao_kernel(const RtDevScene S, const RtBakeArgs A)
+{
+    const uint32_t R = A.raysPerTexel, listed = *A.hits;
+    if ((uint64_t)blockIdx.x * 256u >= (uint64_t)listed * R) return;
+    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
+    __syncthreads();
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x, s = k / R, r = k - s * R;
+    const bool live = s < listed;
+    bool open = false;
+    uint32_t t = 0xffffffffu;
+    if (live) {
+        const float4 a = A.rec[2 * (size_t)s], b = A.rec[2 * (size_t)s + 1];
+        t = (uint32_t)(A.base + __float_as_uint(b.w));
+        const uint32_t tri = __float_as_uint(a.w);
+        const V3 n = xyz(b);
+        const float sg = (n.z >= 0.f) ? 1.f : -1.f, fa = -1.f / (sg + n.z), fb = (n.x * n.y) * fa;
+        const V3 t1 = mk(1.f + ((sg * n.x) * n.x) * fa, sg * fb, -(sg * n.x));
+        const V3 t2 = mk(fb, sg + (n.y * n.y) * fa, -n.y);
+        const uint64_t s0 = ao_mix(A.seed), c = ((uint64_t)t * (R + 1u) + 1u + r) * 32ull;
+        float xd = 0.f, yd = 0.f, r2 = 0.f;
+#pragma unroll 1
+        for (uint32_t att = 0; att < 16u; ++att) {
+            const float x = 2.f * ao_uniform(s0, c + 2u * att) - 1.f, y = 2.f * ao_uniform(s0, c + 2u * att + 1u) - 1.f;
+            const float q = x * x + y * y;
+            if (q < 1.f) { xd = x; yd = y; r2 = q; break; }
+        }
+        const float z = sqrt_rn(1.f - r2);
+        const V3 d = mk((xd * t1.x + yd * t2.x) + z * n.x, (xd * t1.y + yd * t2.y) + z * n.y, (xd * t1.z + yd * t2.z) + z * n.z);
+        float th;
+        open = ao_walk(S, planes, A.fastQuotient, xyz(a), d, A.radius, tri, th) == RT_NONE;
+    }
+    const uint64_t openMask = __ballot(open);
+    const uint32_t lane = __lane_id();
+    const uint32_t before = __shfl_up(t, 1, 64);
+    const bool first = live && (lane == 0u || before != t);
+    const uint64_t firsts = __ballot(first);
+    if (first) {
+        const uint64_t later = firsts & ~((2ull << lane) - 1ull);
+        const uint64_t run = (later ? (later & (0ull - later)) - 1ull : ~0ull) & ~((1ull << lane) - 1ull);
+        const uint32_t cnt = (uint32_t)__popcll(openMask & run);
+        if (cnt) atomicAdd(A.counter + t, cnt);
+    }
+}
+
+// One lane per texel: the value (float)U / (float)R, or `fill` where nothing covers the texel (0, or -1 = invalid when dilation
+// follows), into `out` (which may be `counter` itself), and the winner into `tri` (if not null).
+__global__ __launch_bounds__(256) void rt_bake_finish_kernel(uint32_t texels, const uint32_t *win, const uint32_t *counter, float rays, float fill,
+                                                             float *out, uint32_t *tri)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= texels) return;
+    const uint32_t w = win[t];
+    const float v = (w == RT_NONE) ? fill : (float)counter[t] / rays;
+    out[t] = v;
+    if (tri) tri[t] = w;
+}
+
+// One dilation pass (Jacobi): values >= 0 are valid, -1 is not.  `last`: a texel still invalid is written as 0.
+__global__ __launch_bounds__(256) void rt_bake_dilate_kernel(uint32_t W, uint32_t H, const float *src, float *dst, uint32_t last)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= W * H) return;
+    const float v = src[t];
+    if (v >= 0.f) { dst[t] = v; return; }
+    const int y = (int)(t / W), x = (int)(t - (uint32_t)y * W);
+    float sum = 0.f;
+    uint32_t k = 0;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int nx = x + dx, ny = y + dy;
+            if ((dx == 0 && dy == 0) || nx < 0 || ny < 0 || nx >= (int)W || ny >= (int)H) continue;
+            const float w = src[(size_t)ny * W + nx];
+            if (w >= 0.f) { sum += w; ++k; }
+        }
+    dst[t] = k ? sum / (float)k : (last ? 0.f : -1.f);
+}
+
+extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream)
+{
+    if (args->count == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_bake_raster_kernel, dim3((args->count + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
+    hipLaunchKernelGGL(rt_bake_raster_big_kernel, dim3(RT_BAKE_BIG_BLOCKS), dim3(256), 0, stream, *scene, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtw_launch_bake_points(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream)
+{
+    if (args->count == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_bake_points_kernel, dim3((args->count + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtw_launch_bake_ao(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream)
+{
+    if (args->count == 0) return hipSuccess;
+    const uint64_t rays = (uint64_t)args->count * args->raysPerTexel;
+    if (rays > (1ull << 31)) return hipErrorInvalidValue; // (the AO kernel's lane index is 32-bit)
+    hipLaunchKernelGGL(rt_bake_ao_kernel, dim3((uint32_t)((rays + 255u) / 256u)), dim3(256), 0, stream, *scene, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtw_launch_bake_finish(uint32_t texels, const uint32_t *win, const uint32_t *counter, uint32_t rays, float fill, float *out,
+                                             uint32_t *tri, hipStream_t stream)
+{
+    hipLaunchKernelGGL(rt_bake_finish_kernel, dim3((texels + 255u) / 256u), dim3(256), 0, stream, texels, win, counter, (float)rays, fill, out, tri);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtw_launch_bake_dilate(uint32_t W, uint32_t H, const float *src, float *dst, uint32_t last, hipStream_t stream)
+{
+    hipLaunchKernelGGL(rt_bake_dilate_kernel, dim3((W * H + 255u) / 256u), dim3(256), 0, stream, W, H, src, dst, last);
+    return hipGetLastError();
+}

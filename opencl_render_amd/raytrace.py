@@ -74,6 +74,17 @@ class AoParams(C.Structure):  # rtHipAoParams
 AO_DEFAULTS = dict(rays=16, radius=float("inf"), pixel_samples=1, seed=0)
 
 
+class BakeParams(C.Structure):  # rtHipBakeParams
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raysPerTexel", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32),
+                ("dilate", C.c_uint32), ("firstTriangle", C.c_uint32), ("triangleCount", C.c_uint32), ("material", C.c_int32),
+                ("matchMaterial", C.c_uint32)]
+
+
+# rtHipBakeDefaults (include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE"); triangleCount ALL_TRIANGLES = first .. T - 1
+BAKE_DEFAULTS = dict(rays=16, radius=float("inf"), seed=0, dilate=2)
+ALL_TRIANGLES = 0xFFFFFFFF
+
+
 class Stats(C.Structure):  # rtHipStats
     _fields_ = [(n, C.c_uint64) for n in ("primarySamples", "primaryCandidates", "gridRays", "gridCells", "gridCandidates", "shadedHits", "texelFetches")]
 
@@ -96,6 +107,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSceneIntersect", "rtHipSceneIntersectDevice",
     "rtHipDenoiseDefaults", "rtHipDenoiseScratchBytes", "rtHipDenoiseDevice", "rtHipDenoise", "rtHipSceneDenoise", "rtHipSceneDenoiseTimes",
     "rtHipAoDefaults", "rtHipSceneAmbientOcclusion", "rtHipSceneAmbientOcclusionDevice",
+    "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat",
@@ -202,6 +214,10 @@ def lib() -> C.CDLL:
     L.rtHipAoDefaults.argtypes = [C.POINTER(AoParams)]
     L.rtHipSceneAmbientOcclusion.argtypes = [vp, C.POINTER(AoParams), vp]
     L.rtHipSceneAmbientOcclusionDevice.argtypes = [vp, C.POINTER(AoParams), vp, vp]
+    L.rtHipBakeDefaults.restype = None
+    L.rtHipBakeDefaults.argtypes = [C.POINTER(BakeParams)]
+    L.rtHipSceneBakeAmbientOcclusion.argtypes = [vp, C.POINTER(BakeParams), vp, vp]
+    L.rtHipSceneBakeAmbientOcclusionDevice.argtypes = [vp, C.POINTER(BakeParams), vp, vp, vp]
     L.rtHipKernelTime.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
     L.rtHipBuildCameraList.argtypes = [u32, u32, vp, vp, vp, vp, f32, u32, vp, vp, C.c_int,
                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
@@ -408,6 +424,27 @@ def ao_params(rays=AO_DEFAULTS["rays"], radius=AO_DEFAULTS["radius"], pixel_samp
     if not all(0 <= int(v) <= 0xFFFFFFFF for v in (rays, pixel_samples, seed)):  # (ctypes would wrap them into the uint32 fields)
         raise ValueError(f"ambient_occlusion: rays, pixel_samples and seed must be in 0..2^32-1 (got {rays}, {pixel_samples}, {seed})")
     return AoParams(int(rays), int(pixel_samples), float(radius), int(seed))
+
+
+def bake_params(width, height, rays=BAKE_DEFAULTS["rays"], radius=BAKE_DEFAULTS["radius"], seed=BAKE_DEFAULTS["seed"],
+                dilate=BAKE_DEFAULTS["dilate"], triangles=None, material=None) -> BakeParams:
+    """rtHipBakeParams from the Python keywords (the library checks the ranges).  triangles: None (all), a range with step 1 or
+    (first, count); material: None (no filter) or a material id."""
+    if triangles is None:
+        first, count = 0, ALL_TRIANGLES
+    elif isinstance(triangles, range):
+        if triangles.step != 1:
+            raise ValueError("bake_ambient_occlusion: triangles must be a range with step 1")
+        first, count = triangles.start, max(len(triangles), 0)
+    else:
+        first, count = (int(v) for v in triangles)
+    vals = (width, height, rays, seed, dilate, first, count)
+    if not all(0 <= int(v) <= 0xFFFFFFFF for v in vals):  # (ctypes would wrap them into the uint32 fields)
+        raise ValueError(f"bake_ambient_occlusion: width, height, rays, seed, dilate and the triangle range must be in 0..2^32-1 (got {vals})")
+    if material is not None and not -(1 << 31) <= int(material) < (1 << 31):
+        raise ValueError(f"bake_ambient_occlusion: material {material} is not an int32")
+    return BakeParams(int(width), int(height), int(rays), float(radius), int(seed), int(dilate), int(first), int(count),
+                      0 if material is None else int(material), 0 if material is None else 1)
 
 
 def quantise(colour: np.ndarray) -> list:
@@ -733,22 +770,8 @@ class ResidentScene:
             if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != shape \
                     or not out.is_contiguous():
                 raise ValueError(f"ambient_occlusion: out must be a contiguous float32 {shape} tensor on {dev}")
-            cur = torch.cuda.current_stream(dev)
-            if stream and stream != cur.cuda_stream:
-                run = torch.cuda.ExternalStream(stream, device=dev)
-            elif cur.cuda_stream:
-                run = cur
-            else:  # the null stream would mean "the scene's own stream" to the library (see _intersect_torch)
-                if getattr(self, "_side_stream", None) is None:
-                    self._side_stream = torch.cuda.Stream(dev)
-                run = self._side_stream
-            if run is not cur:
-                run.wait_stream(cur)
-            self._check(lib().rtHipSceneAmbientOcclusionDevice(self.handle, C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(run.cuda_stream)),
-                        "rtHipSceneAmbientOcclusionDevice")
-            if run is not cur:
-                cur.wait_stream(run)
-                out.record_stream(run)
+            self._on_torch_stream(stream, [out], lambda run: self._check(lib().rtHipSceneAmbientOcclusionDevice(
+                self.handle, C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(run)), "rtHipSceneAmbientOcclusionDevice"))
             return out
         if out is None:
             out = np.zeros(shape, np.float32)
@@ -756,6 +779,66 @@ class ResidentScene:
             raise ValueError(f"ambient_occlusion: out must be a C-contiguous float32 {shape} array")
         self._check(lib().rtHipSceneAmbientOcclusion(self.handle, C.byref(p), _ptr(out)), "rtHipSceneAmbientOcclusion")
         return out
+
+    def _on_torch_stream(self, stream, tensors, call):
+        """call(hipStream_t as int) on torch's current stream of this scene's device, or on `stream`, ordered after the current stream's
+        work and before its later work; `tensors` are recorded on a stream other than the current one."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(dev)
+        if stream and stream != cur.cuda_stream:
+            run = torch.cuda.ExternalStream(stream, device=dev)
+        elif cur.cuda_stream:
+            run = cur
+        else:  # the null stream would mean "the scene's own stream" to the library (see _intersect_torch)
+            if getattr(self, "_side_stream", None) is None:
+                self._side_stream = torch.cuda.Stream(dev)
+            run = self._side_stream
+        if run is not cur:
+            run.wait_stream(cur)
+        call(run.cuda_stream)
+        if run is not cur:
+            cur.wait_stream(run)
+            for t in tensors:
+                t.record_stream(run)
+
+    def bake_ambient_occlusion(self, width, height, rays=BAKE_DEFAULTS["rays"], radius=BAKE_DEFAULTS["radius"], seed=BAKE_DEFAULTS["seed"],
+                               dilate=BAKE_DEFAULTS["dilate"], triangles=None, material=None, out=None, triangle_out=None, stream: int = 0) -> dict:
+        """Ambient occlusion baked into a width x height texture over the scene's UVs (include/raytrace_hip.h, "AMBIENT OCCLUSION
+        BAKE"): per texel the fraction of `rays` cosine-weighted hemisphere rays from the covering triangle's surface point that travel
+        `radius` unoccluded, then `dilate` gutter-fill passes.  triangles: None (all), a range or (first, count); material: None or the
+        only material id baked.  Returns {"ao": [H, W] f32, "triangle": [H, W] winner ids (0xffffffff: uncovered)}: numpy arrays
+        (rtHipSceneBakeAmbientOcclusion; `out` / `triangle_out` if given, u32) or, when `out` is a float32 [H, W] tensor on this scene's
+        device, tensors filled by rtHipSceneBakeAmbientOcclusionDevice on torch's current stream (or `stream`): `triangle_out` an int32
+        [H, W] tensor there (the ids' bits), or a new one."""
+        p = bake_params(width, height, rays, radius, seed, dilate, triangles, material)
+        shape = (int(height), int(width))
+        if hasattr(out, "data_ptr"):
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            for t, dt, name in ((out, torch.float32, "out"), (triangle_out, torch.int32, "triangle_out")):
+                if t is not None and (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != shape
+                                      or not t.is_contiguous()):
+                    raise ValueError(f"bake_ambient_occlusion: {name} must be a contiguous {dt} {shape} tensor on {dev}")
+            if triangle_out is None:
+                triangle_out = torch.empty(shape, dtype=torch.int32, device=dev)
+            self._on_torch_stream(stream, [out, triangle_out], lambda run: self._check(lib().rtHipSceneBakeAmbientOcclusionDevice(
+                self.handle, C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(triangle_out.data_ptr()), C.c_void_p(run)),
+                "rtHipSceneBakeAmbientOcclusionDevice"))
+            return dict(ao=out, triangle=triangle_out)
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags.c_contiguous):
+            raise ValueError(f"bake_ambient_occlusion: out must be a C-contiguous float32 {shape} array")
+        if triangle_out is None:
+            triangle_out = np.zeros(shape, np.uint32)
+        elif not (isinstance(triangle_out, np.ndarray) and triangle_out.dtype == np.uint32 and triangle_out.shape == shape
+                  and triangle_out.flags.c_contiguous):
+            raise ValueError(f"bake_ambient_occlusion: triangle_out must be a C-contiguous uint32 {shape} array")
+        self._check(lib().rtHipSceneBakeAmbientOcclusion(self.handle, C.byref(p), _ptr(out), _ptr(triangle_out)), "rtHipSceneBakeAmbientOcclusion")
+        return dict(ao=out, triangle=triangle_out)
 
     def intersect(self, origins, directions, tmin=0.0, tmax=np.inf, exclude=None, stream: int = 0) -> dict:
         """What rays hit in this scene: the reference's grid walk, RayIntersectsTriangles (raytrace_opencl.c:324-401), bit for bit

@@ -223,3 +223,26 @@ def primary_only_material(texture_side: int = 0, seed: int = 7) -> dict:
     else:
         lum = (255, 255, 255)
     return dict(color=(0, 0, 0), reflection=(0, 0, 0), transparency=(0, 0, 0), bump=(0, 0, 0), luminance=lum)
+
+
+def grid_atlas_uv(triangle_count: int, size: int, margin_texels: float = 1) -> np.ndarray:
+    """[3T, 2] float32 corner UVs that give every triangle a cell of its own in a square grid atlas: n = ceil(sqrt(T)) cells a side,
+    triangle i in column i % n, row i // n, a right triangle (corners a, b = a + (w, 0), c = a + (0, w)) inset by `margin_texels`
+    texels of a `size` x `size` map (at most a quarter of the cell).  For baking a scene whose own UVs overlap (the demo meshes give
+    every quad the whole of [0, 1]^2)."""
+    T = int(triangle_count)
+    if T <= 0:
+        return np.zeros((0, 2), np.float32)
+    n = int(np.ceil(np.sqrt(T)))
+    while n * n < T:  # (sqrt rounding)
+        n += 1
+    cell = 1.0 / n
+    m = min(float(margin_texels) / float(size), cell / 4)
+    i = np.arange(T)
+    x0, y0 = (i % n) * cell + m, (i // n) * cell + m
+    w = cell - 2 * m
+    uv = np.empty((T, 3, 2), np.float64)
+    uv[:, 0, 0], uv[:, 0, 1] = x0, y0
+    uv[:, 1, 0], uv[:, 1, 1] = x0 + w, y0
+    uv[:, 2, 0], uv[:, 2, 1] = x0, y0 + w
+    return np.ascontiguousarray(uv.reshape(3 * T, 2).astype(np.float32))
