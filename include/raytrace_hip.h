@@ -188,7 +188,14 @@ const char *rtHipLastError(void);
 
 /* Uploads a scene to `device` and builds the device-side layout (pre-resolved triangle records etc.).
  * tileCount/tileIds select the 128x128 tiles this scene instance will render (row-major tile ids); NULL/0 = all.
- * Only those tiles' slices of the camera lists are uploaded.  Returns NULL on failure. */
+ * Only those tiles' slices of the camera lists are uploaded.  Returns NULL on failure.
+ * Every id the kernels will index with is checked on the device before anything gathers through it, and a scene that fails is refused
+ * with "scene rejected (0x<bits>): ..." in rtHipLastError(): a vertex id outside [0, vertexCount) in lanes x, y, z of a triangle (lane w
+ * is never read), a material id >= materialCount (any negative id is legal and means "no material"), a camera or grid list entry >=
+ * triangleCount, a pixel range that ends past cameraPixelTriangleListSize (End < Start is legal and reads as empty), and grid starts
+ * that descend (equal starts are an empty cell).  The pixel ranges are read -- and therefore checked -- only for the pixels of THIS
+ * instance's tiles: a bad range in a tile the instance does not own is not refused here, on purpose (the instance that owns the tile
+ * refuses it); the camera LIST is uploaded whole and every entry of it is checked, also one that no pixel's range covers. */
 rtHipScene *rtHipSceneCreate(int device, const rtHipSceneDesc *desc, const cl_uint *tileIds, cl_uint tileCount);
 /* The same for a further instance of a scene that is already resident somewhere (`like`, built from the same description, on this or
  * another device): geometry, grid, materials and lights are copied from it device to device (hipMemcpyPeerAsync: xGMI between
@@ -708,6 +715,25 @@ enum { RT_BUILD_LOG_CAM_THREAD = 0, RT_BUILD_LOG_CAM_GROUP, RT_BUILD_LOG_CAM_ENT
        RT_BUILD_LOG_GRID_BATCHES, RT_BUILD_LOG_KEY_CAP_FIRST, RT_BUILD_LOG_KEY_CAP_FINAL, RT_BUILD_LOG_GREW, RT_BUILD_LOG_ATTEMPTS,
        RT_BUILD_LOG_PAIRS, RT_BUILD_LOG_FIELDS };
 int rtHipTestBuildLog(uint64_t *out, cl_uint n);
+
+/* TEST-ONLY: copies elements [firstElement, firstElement + count) of one of a resident scene's device arrays -- what the scene upload
+ * (rt_scene_prep.hip, rt_prepare_triangles, rt_gather_pair_records) left for the kernels -- to host memory, after synchronising the
+ * scene's stream.  `what` and the element of each array:
+ *   RT_SCENE_VIEW_HEADER     cl_uint: planesTame, tileCount, tilesX, triangleCount, pair count (5 elements)
+ *   RT_SCENE_VIEW_CAM_START  cl_uint: tile-major range starts, index slot*128*128 + ly*128 + lx (tileCount*128*128 elements)
+ *   RT_SCENE_VIEW_CAM_END    cl_uint: the range ends, same index
+ *   RT_SCENE_VIEW_TRI_REC    16 floats (64 bytes): a triangle's intersection record (triangleCount elements)
+ *   RT_SCENE_VIEW_TRI_SHADE  24 floats (96 bytes): a triangle's shading row
+ *   RT_SCENE_VIEW_GRID_BITS  uint64_t: the occupancy word of a 4x4x4 block, block (cx>>2) + 64*(cy>>2) + 4096*(cz>>2) (64^3 elements)
+ *   RT_SCENE_VIEW_BLOCK_SPARSE cl_uint: the block table {word lo, word hi, rank}, entry 3*((cx>>2) | (cy>>2)<<8 | (cz>>2)<<16)
+ *                            (3 * ((63<<16 | 63<<8 | 63) + 1) elements)
+ *   RT_SCENE_VIEW_PAIR_REC   16 32-bit words (64 bytes): a (cell, triangle) pair record (pair count elements)
+ *   RT_SCENE_VIEW_CELL_LUT   one byte: the cell estimate table [3][256]
+ * With out == NULL it returns the array's element count (firstElement and count are ignored); otherwise 0, or -1 with a
+ * rtHipLastError() text for a NULL scene, an unknown `what`, a range that reaches past the array's end or a HIP failure. */
+enum { RT_SCENE_VIEW_HEADER = 0, RT_SCENE_VIEW_CAM_START, RT_SCENE_VIEW_CAM_END, RT_SCENE_VIEW_TRI_REC, RT_SCENE_VIEW_TRI_SHADE,
+       RT_SCENE_VIEW_GRID_BITS, RT_SCENE_VIEW_BLOCK_SPARSE, RT_SCENE_VIEW_PAIR_REC, RT_SCENE_VIEW_CELL_LUT, RT_SCENE_VIEWS };
+int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement, uint64_t count, void *out);
 
 #ifdef __cplusplus
 }

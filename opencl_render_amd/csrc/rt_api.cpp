@@ -260,6 +260,7 @@ struct rtHipScene {
     Stager stager;
     uint32_t *prepErr = nullptr;   // device word: RT_PREP_ERR_* bits raised by the validation kernels
     uint64_t camListSize = 0;
+    uint64_t gridListSize = 0;      // entries of the grid list = pair records of the dense view
     uint32_t gridListSizeHint = 0;  // scene description with device arrays: scenePixelTriangleListStart[256^3], fetched by scene_build
     bool haveGridListSize = false;
     bool wfMultiLight = false;     // what the path-state buffers were sized for
@@ -572,6 +573,7 @@ int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
     if (sc->alloc<float>((uint64_t)listSize * 16, &pairRec)) return -1;
     HIP_OK(rtk_launch_gather_pairs((uint32_t)listSize, pairOrder, pairCount, D.triRec, pairRec, sc->stream));
     D.gridBits = words; D.gridBlockSparse = sparse; D.pairRec = pairRec;
+    sc->gridListSize = listSize;
     D.cellCount = 0; // informational; the kernels find a cell's records through the block table
     HIP_OK(hipStreamSynchronize(sc->stream));
     return 0;
@@ -803,7 +805,7 @@ int clone_part(rtHipScene *dst, const rtHipScene *src, int part)
 #define RT_MOVE(field) D.field = (decltype(D.field))at(S.field)
     if (part == PART_GEOMETRY) { D.triangleCount = S.triangleCount; RT_MOVE(triRec); RT_MOVE(triShade); }
     if (part == PART_GRID) {
-        D.planesTame = S.planesTame; D.cellCount = S.cellCount;
+        D.planesTame = S.planesTame; D.cellCount = S.cellCount; dst->gridListSize = src->gridListSize;
         RT_MOVE(boxMin); RT_MOVE(cellLut); RT_MOVE(gridStart); RT_MOVE(gridList); RT_MOVE(gridBits); RT_MOVE(gridBlockSparse); RT_MOVE(pairRec);
     }
     if (part == PART_MATERIALS) {
@@ -2220,6 +2222,39 @@ int rtHipTestRoundLog(const rtHipScene *scene, uint32_t *rays, uint32_t n)
         rays[r] = (uint32_t)std::min<uint64_t>(sum, 0xffffffffu);
     }
     return (int)scene->roundsLast;
+}
+
+int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement, uint64_t count, void *out)
+{
+    if (!scene) return fail("rtHipTestSceneView: null scene");
+    const RtDevScene &D = scene->dev;
+    const uint32_t header[5] = { D.planesTame, D.tileCount, D.tilesX, D.triangleCount, (uint32_t)scene->gridListSize };
+    const uint64_t tilePixels = (uint64_t)D.tileCount * RT_TILE_PIXELS, blocks = (uint64_t)(RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * (RT_GRID_DIV / 4);
+    struct View { const void *ptr; uint64_t elements, elementBytes; bool host; } v;
+    switch (what) {
+    case RT_SCENE_VIEW_HEADER: v = { header, 5, 4, true }; break;
+    case RT_SCENE_VIEW_CAM_START: v = { D.camStart, tilePixels, 4, false }; break;
+    case RT_SCENE_VIEW_CAM_END: v = { D.camEnd, tilePixels, 4, false }; break;
+    case RT_SCENE_VIEW_TRI_REC: v = { D.triRec, D.triangleCount, 64, false }; break;
+    case RT_SCENE_VIEW_TRI_SHADE: v = { D.triShade, D.triangleCount, 96, false }; break;
+    case RT_SCENE_VIEW_GRID_BITS: v = { D.gridBits, blocks, 8, false }; break;
+    case RT_SCENE_VIEW_BLOCK_SPARSE: v = { D.gridBlockSparse, (uint64_t)3 * ((63u << 16 | 63u << 8 | 63u) + 1u), 4, false }; break;
+    case RT_SCENE_VIEW_PAIR_REC: v = { D.pairRec, scene->gridListSize, 64, false }; break;
+    case RT_SCENE_VIEW_CELL_LUT: v = { D.cellLut, 3 * 256, 1, false }; break;
+    default: return fail("rtHipTestSceneView: unknown array %d", what);
+    }
+    if (v.elements > 0x7fffffffull) return fail("rtHipTestSceneView: array %d has %llu elements", what, (unsigned long long)v.elements);
+    if (!out) return (int)v.elements;
+    if (firstElement > v.elements || count > v.elements - firstElement)
+        return fail("rtHipTestSceneView: elements %llu + %llu reach past the %llu of array %d", (unsigned long long)firstElement,
+                    (unsigned long long)count, (unsigned long long)v.elements, what);
+    if (!count) return 0;
+    if (v.host) { memcpy(out, (const char *)v.ptr + firstElement * v.elementBytes, count * v.elementBytes); return 0; }
+    if (!v.ptr) return fail("rtHipTestSceneView: the scene does not hold array %d", what);
+    HIP_OK(hipSetDevice(scene->device));
+    HIP_OK(hipStreamSynchronize(scene->stream));
+    HIP_OK(hipMemcpy(out, (const char *)v.ptr + firstElement * v.elementBytes, count * v.elementBytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int rtHipScenePathClass(const rtHipSceneDesc *desc)

@@ -110,7 +110,7 @@ RESIDENT_SYMBOLS = [
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
-    "rtHipTestShadeKat",
+    "rtHipTestShadeKat", "rtHipTestSceneView",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm", "rtHipWritePfmRgb",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
@@ -234,6 +234,7 @@ def lib() -> C.CDLL:
     L.rtHipTestRoundLog.argtypes = [vp, C.POINTER(u32), u32]
     L.rtHipTestBuildLog.argtypes = [C.POINTER(u64), u32]
     L.rtHipTestShadeKat.argtypes = [vp, C.c_int, u32, vp, vp]
+    L.rtHipTestSceneView.argtypes = [vp, C.c_int, u64, u64, vp]
     L.rtHipFree.argtypes = [vp]
     L.rtHipFree.restype = None
     _lib = L
@@ -555,6 +556,14 @@ def scene_desc(sc: Scene) -> SceneDesc:
 
 PATH_CLASS_GENERAL, PATH_CLASS_OPAQUE_DIFFUSE = 0, 1
 
+# rtHipTestSceneView: name -> (RT_SCENE_VIEW_*, dtype of a word, words per element)
+SCENE_VIEWS = {
+    "header": (0, np.uint32, 1), "cam_start": (1, np.uint32, 1), "cam_end": (2, np.uint32, 1), "tri_rec": (3, np.float32, 16),
+    "tri_shade": (4, np.float32, 24), "grid_bits": (5, np.uint64, 1), "block_sparse": (6, np.uint32, 1), "pair_rec": (7, np.uint32, 16),
+    "cell_lut": (8, np.uint8, 1),
+}
+SCENE_VIEW_HEADER = ("planes_tame", "tile_count", "tiles_x", "triangle_count", "pair_count")
+
 
 def path_class(sc: Scene) -> int:
     """The logic kernel a scene's paths run on (rtHipScenePathClass), decided on the host: PATH_CLASS_OPAQUE_DIFFUSE when no material
@@ -623,6 +632,23 @@ class ResidentScene:
         out = np.zeros((n, 64 if op == 0 else 96), np.uint8)
         self._check(lib().rtHipTestShadeKat(self.handle, op, n, _ptr(inp), _ptr(out)), "rtHipTestShadeKat")
         return out
+
+    def scene_view(self, name: str, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Elements [first, first + count) (default: to the end) of one of the scene's device arrays (rtHipTestSceneView; names in
+        SCENE_VIEWS): cam_start / cam_end tile-major u32, tri_rec [n, 16] f32, tri_shade [n, 24] f32, grid_bits u64, block_sparse u32
+        words, pair_rec [n, 16] u32 words (floats as their bits), cell_lut u8, header u32 (SCENE_VIEW_HEADER)."""
+        what, dtype, words = SCENE_VIEWS[name]
+        total = lib().rtHipTestSceneView(self.handle, what, 0, 0, None)
+        if total < 0:
+            raise RuntimeError("rtHipTestSceneView failed: " + last_error())
+        if count is None:
+            count = max(total - first, 0)
+        out = np.zeros((count, words) if words > 1 else count, dtype)
+        self._check(lib().rtHipTestSceneView(self.handle, what, first, count, _ptr(out)), "rtHipTestSceneView")
+        return out
+
+    def scene_header(self) -> dict:
+        return dict(zip(SCENE_VIEW_HEADER, (int(v) for v in self.scene_view("header"))))
 
     def _check(self, rc, what):
         if rc != 0:
