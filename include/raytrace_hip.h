@@ -206,6 +206,50 @@ void        rtHipSceneDestroy(rtHipScene *scene);
 /* Bytes of HBM held by the scene. */
 uint64_t rtHipSceneBytes(const rtHipScene *scene);
 
+/* The camera of a resident scene, moved on the device.  rtHipSceneGetCamera gives the five fields in effect (after creation: the
+ * description's; lane 3 of the vectors reads 0).  rtHipSceneSetCamera replaces them and rebuilds the per-pixel candidate lists of the
+ * instance's tiles for the new view from the triangles the scene already holds (rt_camera_move.hip), so that a second view of a scene
+ * costs a list build instead of a new scene.
+ *   Equivalence.  After it returns 0 the scene is, for everything the public API shows, the scene rtHipSceneCreate would have made from
+ *   the same description with the five camera fields replaced and camStart / camEnd / camList = what rtHipBuildCameraList returns for
+ *   that camera (same image size, tile set and sample count): every later frame (both pipelines), rtHipReadbackPasses,
+ *   rtHipReadbackSurfacePasses, rtHipSceneDenoise and rtHipSceneAmbientOcclusion result is bit-identical to that scene's.  Ray queries
+ *   and the ambient occlusion bake do not read the camera and are unchanged.  "The same lists" are the same CONTENTS: every pixel of
+ *   the instance's tiles reads the triangles the host builder gives it, in ascending order (one shared header decides membership for
+ *   both).  The range numbers differ: the moved scene's ranges do not share storage between neighbouring pixels, its list is the
+ *   concatenation of the pixels' lists in tile-major order, and pixels of a tile that lie outside the image read nothing.
+ *   Only this instance's tiles.  An instance over a tile subset builds ranges for its own tiles; pixels of other tiles are dropped
+ *   before their membership test.  Peers made with rtHipSceneCreateLike are moved one by one by the caller, and instances over a
+ *   disjoint deal of the tiles still compose the full image.
+ *   Everything stays on the device.  No vertex, index, range or list array crosses the bus in either direction; the host sends the
+ *   camera and receives 16 bytes (the 64-bit entry total and the number of large triangles).  Geometry, grid, materials, lights, path
+ *   state and the pass / surface / denoise / AO / bake scratch keep their allocations and addresses.
+ *   Ordering.  The call is synchronous on the scene's own stream: it waits for the work already issued there (a frame in flight reads
+ *   the old lists; planned frames are verified as by rtHipFrameFinish first) and on return the new camera is in effect for everything
+ *   issued afterwards.  A caller that rendered on a stream of its own synchronises that stream first, as for rtHipReadback.  The launch
+ *   plan of the old view is dropped: the next frame is a watched one.
+ *   Transactional.  The new view is built into storage the frames do not read and takes the old one's place at the very end; on any
+ *   failure the scene keeps its old camera and lists and renders what it rendered before.  Returns -1 for a NULL argument, -3 when the
+ *   view's lists hold more than 2^32 - 1 entries or more than rtHipTune("build_list_limit", n) (decided from the 64-bit total before the
+ *   list is sized, like rtHipBuildCameraListDevice), -4 when device memory could not be had, -2 for any other HIP failure; each with a
+ *   text in rtHipLastError().
+ *   Every bit pattern of the camera has a defined answer -- NaN, infinities, pixelSizeInv 0, an eye inside a triangle: the lists are
+ *   those rtHipBuildCameraList gives for the same values.  Nothing is refused for its value and nothing indexes out of range.
+ *   Memory.  The first move makes the build storage: 24 bytes per triangle of projected vertices, 4 per triangle for the list of large
+ *   triangles, 4 per tile pixel of counts, the tile slot tables and the scan's temporaries in one block, and TWO sets of ranges (8 bytes
+ *   per tile pixel each).  A move builds into the set that is not in use; the lists the scene was created with are freed after the first
+ *   move.  A list buffer that is too small for a view is replaced by one of entries + entries / 8 (at least 1024) entries and never
+ *   shrinks, and after a move the other set's list is made as large, so that a later move to a view of no more entries allocates
+ *   nothing.  All of it is counted in rtHipSceneBytes and freed with the scene.
+ *   Tuning.  The call reads "build_list_limit" once at entry, so a rtHipTune call made after the scene was created is seen by the next
+ *   move; the scene's other tuning values stay those it was built with. */
+typedef struct rtHipCamera {
+    cl_float eye[4], eyeToTopLeft[4], leftToRight[4], topToBottom[4]; /* lane 3 is never read */
+    cl_float pixelSizeInv;
+} rtHipCamera;
+int rtHipSceneGetCamera(const rtHipScene *scene, rtHipCamera *out);
+int rtHipSceneSetCamera(rtHipScene *scene, const rtHipCamera *camera);
+
 /* Renders all samples of the scene's tiles into its device-resident tile buffer
  * ([tile][plane R,G,B][128*128] u16, tiles in the order given at creation).  Asynchronous on `stream`
  * (a hipStream_t passed as void*; NULL = the scene's own stream).  Returns 0 on success. */
@@ -734,6 +778,19 @@ int rtHipTestBuildLog(uint64_t *out, cl_uint n);
 enum { RT_SCENE_VIEW_HEADER = 0, RT_SCENE_VIEW_CAM_START, RT_SCENE_VIEW_CAM_END, RT_SCENE_VIEW_TRI_REC, RT_SCENE_VIEW_TRI_SHADE,
        RT_SCENE_VIEW_GRID_BITS, RT_SCENE_VIEW_BLOCK_SPARSE, RT_SCENE_VIEW_PAIR_REC, RT_SCENE_VIEW_CELL_LUT, RT_SCENE_VIEWS };
 int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement, uint64_t count, void *out);
+
+/* TEST-ONLY, for rtHipSceneSetCamera.  rtHipTestSceneCameraList copies entries [first, first + count) of the scene's device camera list
+ * (the one its ranges, RT_SCENE_VIEW_CAM_START / _END, index) after synchronising the scene's stream; with out == NULL it returns the
+ * entry count.  rtHipTestScenePointers gives the device addresses of triRec, triShade, gridBlockSparse, pairRec, matRec and lightPos, so
+ * that a test can show a move leaves them where they were.  rtHipTestSceneCameraLog gives, for the scene's last successful move:
+ * triangles rasterised by one thread, triangles handed to workgroups (clipped rectangle above 1024 pixels), list entries (zeros before
+ * the first move; a move does not write rtHipTestBuildLog's fields).  rtHipTestSceneCameraTimes gives that move's device time in
+ * milliseconds: [0] projection, count pass and total, [1] scan, fill pass and per-pixel order (HIP events on the scene's stream; the
+ * host's look at the total lies between the two).  Each returns 0, or -1 with a rtHipLastError() text. */
+int rtHipTestSceneCameraList(const rtHipScene *scene, uint64_t first, uint64_t count, cl_uint *out);
+int rtHipTestScenePointers(const rtHipScene *scene, const void *out[6]);
+int rtHipTestSceneCameraLog(const rtHipScene *scene, uint64_t out[3]);
+int rtHipTestSceneCameraTimes(const rtHipScene *scene, double out[2]);
 
 #ifdef __cplusplus
 }

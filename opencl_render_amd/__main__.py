@@ -66,12 +66,24 @@ def parser():
     sel.add_argument("--bake-material", type=int, metavar="M", help="--bake-ao: bake only the triangles of material M")
     sel.add_argument("--bake-triangles", type=int, nargs=2, metavar=("FIRST", "COUNT"), help="--bake-ao: bake only these triangles")
     ap.add_argument("--bake-atlas", action="store_true", help="--bake-ao: bake over a grid atlas, one cell per triangle, not the scene's UVs")
+    ap.add_argument("--orbit", type=int, default=1, metavar="N",
+                    help="N views of the one resident scene on a circle about the vertical axis through the look-at point, same height and "
+                         "distance, each after the first through ResidentScene.look_at (the camera lists are rebuilt on the device, nothing is "
+                         "uploaded again); --out img.bmp becomes img_000.bmp .. img_{N-1}.bmp, and --passes, --denoise and --ao are numbered "
+                         "the same way.  One GPU only.  Face normals the front-end made for a mesh WITHOUT normals were oriented toward the "
+                         "first eye and are not re-oriented by a move; a scene whose normals come from the file is unaffected.  For the "
+                         "built-in scenes every view, the first included, is set through --eye / --look-at / --fov (defaults: the origin and "
+                         "(0, 0, 3))")
     return ap
 
 
 def parse_args(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
+    if args.orbit < 1:
+        ap.error("--orbit N needs N >= 1")
+    if args.orbit > 1 and args.bake_ao:
+        ap.error("--orbit does not go with --bake-ao (a bake does not read the camera)")
     if args.surface_passes and not args.passes:
         ap.error("--surface-passes needs --passes PREFIX")
     if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
@@ -157,6 +169,70 @@ def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool
     return [p.reshape(sc.height, sc.width) for p in planes], passes
 
 
+def orbit_outputs(args, index: int) -> dict:
+    """The files view `index` of an orbit writes: every given path numbered like --out (img.bmp -> img_007.bmp)."""
+    from . import raytrace
+    return dict(out=raytrace.orbit_path(args.out, index), passes=f"{args.passes}_{index:03d}" if args.passes else None,
+                denoise=raytrace.orbit_path(args.denoise, index) if args.denoise else None,
+                ao=raytrace.orbit_path(args.ao, index) if args.ao else None)
+
+
+def write_view(args, paths: dict, planes, passes, denoised, ao) -> None:
+    from . import frontend, raytrace
+    r, g, b = planes
+    if paths["passes"]:
+        frontend.write_pgm(paths["passes"] + "_alpha.pgm", passes["alpha"])
+        frontend.write_pfm(paths["passes"] + "_depth.pfm", passes["depth"])
+        np.savez(paths["passes"] + "_ids.npz", triangle=passes["triangle"], material=passes["material"], mesh=passes["mesh"])
+        if args.surface_passes:
+            frontend.write_pfm_rgb(paths["passes"] + "_normal.pfm", passes["normal"])
+            frontend.write_pfm_rgb(paths["passes"] + "_albedo.pfm", passes["albedo"])
+    if paths["denoise"]:
+        if paths["denoise"].lower().endswith(".pfm"):
+            frontend.write_pfm_rgb(paths["denoise"], denoised["colour"])
+        elif paths["denoise"].lower().endswith(".ppm"):
+            frontend.write_ppm(paths["denoise"], *denoised["planes"])
+        else:
+            frontend.write_bmp(paths["denoise"], *denoised["planes"], low_byte_compat=args.low_byte_compat)
+    if paths["ao"]:
+        if paths["ao"].lower().endswith(".pfm"):
+            frontend.write_pfm(paths["ao"], ao)
+        else:
+            frontend.write_pgm(paths["ao"], raytrace.quantise(ao[..., None].repeat(3, -1))[0])
+    if paths["out"].lower().endswith(".ppm"):
+        frontend.write_ppm(paths["out"], r, g, b)
+    else:
+        frontend.write_bmp(paths["out"], r, g, b, low_byte_compat=args.low_byte_compat)
+
+
+def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
+    """--orbit: args.orbit views of one ResidentScene on HIP device `device`, the camera moved on the device between them.  Returns
+    the seconds the moves, frames and read-backs took."""
+    from . import raytrace
+    rs = raytrace.ResidentScene(sc, device)
+    try:
+        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise)
+        if basic or surface:
+            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        spent = 0.0
+        for i, position in enumerate(raytrace.orbit_positions(eye, centre, args.orbit)):
+            t = time.perf_counter()
+            if i or move_first:
+                rs.look_at(position, centre, (0, 1, 0), np.radians(args.fov))
+            rs.render()
+            planes = [p.reshape(sc.height, sc.width) for p in rs.readback()]
+            spent += time.perf_counter() - t
+            passes = rs.readback_passes() if basic or surface else None
+            if passes is not None and "triangle" in passes and "mesh" not in passes:
+                passes["mesh"] = np.where(passes["triangle"] != 0xFFFFFFFF, 0, -1).astype(np.int32)
+            denoised = rs.denoise() if args.denoise else None
+            ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
+            write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+    finally:
+        rs.close()
+    return spent
+
+
 def main(argv=None):
     args = parse_args(argv)
 
@@ -183,6 +259,16 @@ def main(argv=None):
     cam_ms = raytrace.build_camera_list_device(sc, 0)
     grid_ms = raytrace.build_scene_grid_device(sc, 0)
     t2 = time.perf_counter()
+    if args.orbit > 1:
+        if args.device == raytrace.lib().rtHipDeviceCount() + 1:
+            sys.exit("--orbit renders on one GPU: choose --device 1..%d" % raytrace.lib().rtHipDeviceCount())
+        if not args.obj:
+            eye = np.asarray(args.eye, np.float32) if args.eye else np.zeros(3, np.float32)
+            look_at = np.asarray(args.look_at, np.float32) if args.look_at else np.float32([0, 0, 3])
+        spent = render_orbit(sc, args, args.device - 1, eye, look_at, move_first=not args.obj)
+        print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel, "
+              f"{args.orbit} views -> {raytrace.orbit_path(args.out, 0)} ..\n  moves + frames + read-backs {1e3 * spent:.0f} ms = {args.orbit / spent:.1f} views/s")
+        return 0
     if args.passes or args.denoise:
         (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount(), surface=args.surface_passes,
                                           basic=bool(args.passes), denoise=bool(args.denoise))

@@ -6,6 +6,7 @@
 // There is no CPU fallback: without a HIP device every entry point that would compute fails with an error text.
 #include "raytrace_hip.h"
 #include "rt_device.h"
+#include "rt_camera_move.h"
 #include "rt_build_shared.h"
 
 #include <hip/hip_runtime_api.h>
@@ -39,6 +40,9 @@ extern "C" hipError_t rtp_camera_ranges(uint32_t W, uint32_t H, uint32_t tilesX,
 extern "C" hipError_t rtp_dense_grid(const uint32_t *gridStart, const uint32_t *gridList, unsigned long long *words, uint32_t *sparse, uint32_t *pairOrder,
                                      uint32_t *pairCount, void *scratch, size_t *scratchBytes, hipStream_t stream);
 
+extern "C" hipError_t rtc_scan_bytes(uint32_t n, size_t *bytes);
+extern "C" hipError_t rtc_launch_count(const RtCamMoveArgs *args, hipStream_t stream);
+extern "C" hipError_t rtc_launch_fill(const RtCamMoveArgs *args, hipStream_t stream);
 extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefront *wf, hipStream_t stream);
 extern "C" hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const RtWavefront *wf, uint32_t *passBuf, hipStream_t stream);
 extern "C" hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const RtWavefront *wf, float *surfBuf, hipStream_t stream);
@@ -343,6 +347,21 @@ struct rtHipScene {
     uint64_t bakeBytes = 0, bakeTexels = 0;
     uint32_t bakeChunk = 0;
     hipEvent_t bakeDone = nullptr;
+    // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
+    // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
+    // and the sets change places at its end.  listCap: entries each list holds.  log: triangles per thread, per workgroup, entries of the
+    // last move; ms: device time of its count stage and of its fill stage.
+    struct CamMove {
+        char *scratch = nullptr;
+        uint64_t scratchBytes = 0;
+        uint32_t *start[2] = {}, *end[2] = {}, *list[2] = {};
+        uint64_t listCap[2] = {};
+        int live = -1; // the set in use; -1 while the scene still renders from the lists it was created with
+        RtCamMoveArgs args{};
+        hipEvent_t ev[4] = {};
+        uint64_t log[3] = {};
+        double ms[2] = {};
+    } cam;
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -1240,6 +1259,14 @@ void rtHipSceneDestroy(rtHipScene *sc)
     if (sc->aoDone) (void)hipEventDestroy(sc->aoDone);
     if (sc->bakeBuf) (void)hipFree(sc->bakeBuf);
     if (sc->bakeDone) (void)hipEventDestroy(sc->bakeDone);
+    if (sc->cam.scratch) (void)hipFree(sc->cam.scratch);
+    for (int i = 0; i < 2; ++i) {
+        if (sc->cam.start[i]) (void)hipFree(sc->cam.start[i]);
+        if (sc->cam.end[i]) (void)hipFree(sc->cam.end[i]);
+        if (sc->cam.list[i]) (void)hipFree(sc->cam.list[i]);
+    }
+    for (hipEvent_t e : sc->cam.ev)
+        if (e) (void)hipEventDestroy(e);
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
     sc->stager.destroy();
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
@@ -1247,6 +1274,177 @@ void rtHipSceneDestroy(rtHipScene *sc)
 }
 
 uint64_t rtHipSceneBytes(const rtHipScene *sc) { return sc ? sc->bytes : 0; }
+
+int rtHipSceneGetCamera(const rtHipScene *sc, rtHipCamera *out)
+{
+    if (!sc || !out) return fail("rtHipSceneGetCamera: null argument");
+    const RtDevScene &D = sc->dev;
+    memset(out, 0, sizeof *out);
+    for (int i = 0; i < 3; ++i) { out->eye[i] = D.eye[i]; out->eyeToTopLeft[i] = D.topLeft[i]; out->leftToRight[i] = D.lr[i]; out->topToBottom[i] = D.tb[i]; }
+    out->pixelSizeInv = D.pixelSizeInv;
+    return 0;
+}
+
+// The scene-owned storage of camera moves, made by the first move: one scratch block and both sets of ranges.  The lists are sized by
+// the move itself.  On failure nothing is kept.
+static int cam_move_init(rtHipScene *sc)
+{
+    rtHipScene::CamMove &C = sc->cam;
+    if (C.scratch) return 0;
+    const RtDevScene &D = sc->dev;
+    const uint32_t tilesX = sc->tilesX, tilesY = (sc->height + RT_TILE - 1) / RT_TILE, nt = (uint32_t)sc->tileIds.size();
+    const uint64_t pixels = (uint64_t)nt * RT_TILE_PIXELS, T = D.triangleCount;
+    if (pixels > 0x7fffffffull) { fail("rtHipSceneSetCamera: %llu tile pixels are more than the range scan takes", (unsigned long long)pixels); return -2; }
+    std::vector<uint32_t> tables((size_t)tilesX * tilesY + nt, RTC_NO_SLOT);
+    uint32_t *slotOf = tables.data(), *firstSlot = slotOf + (size_t)tilesX * tilesY;
+    bool repeats = false;
+    for (uint32_t i = 0; i < nt; ++i) {
+        uint32_t &slot = slotOf[sc->tileIds[i]];
+        if (slot == RTC_NO_SLOT) slot = i; else repeats = true;
+        firstSlot[i] = slot;
+    }
+    size_t scanBytes = 0;
+    if (const hipError_t e = rtc_scan_bytes((uint32_t)pixels, &scanBytes); e != hipSuccess) { fail("rtHipSceneSetCamera: sizing the scan failed: %s", hipGetErrorString(e)); return -2; }
+    auto up = [](uint64_t v) { return (v + 255) & ~(uint64_t)255; };
+    const uint64_t oTables = 0, oCtl = up(tables.size() * 4), oPos = oCtl + 256, oCount = oPos + up(T * 24), oBig = oCount + up(pixels * 4),
+                   oScan = oBig + up(T * 4), total = oScan + up(scanBytes ? scanBytes : 1);
+    char *block = nullptr;
+    uint32_t *r[4] = {};
+    const uint64_t rangeBytes = pixels ? pixels * 4 : 4;
+    bool ok = hipMalloc((void **)&block, total) == hipSuccess;
+    for (int i = 0; ok && i < 4; ++i) ok = hipMalloc((void **)&r[i], rangeBytes) == hipSuccess;
+    if (ok) ok = hipMemcpy(block + oTables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    for (int i = 0; ok && i < 4; ++i) ok = hipEventCreate(&C.ev[i]) == hipSuccess;
+    if (!ok) {
+        const hipError_t e = hipGetLastError();
+        fail("rtHipSceneSetCamera: the build storage (%llu bytes) could not be made: %s", (unsigned long long)(total + 4 * rangeBytes), hipGetErrorString(e));
+        if (block) (void)hipFree(block);
+        for (uint32_t *p : r) if (p) (void)hipFree(p);
+        for (hipEvent_t &e2 : C.ev) { if (e2) (void)hipEventDestroy(e2); e2 = nullptr; }
+        return -4;
+    }
+    C.scratch = block; C.scratchBytes = total;
+    C.start[0] = r[0]; C.end[0] = r[1]; C.start[1] = r[2]; C.end[1] = r[3];
+    sc->bytes += total + 4 * rangeBytes;
+    RtCamMoveArgs &A = C.args;
+    A.width = sc->width; A.height = sc->height; A.tilesX = tilesX; A.triangleCount = D.triangleCount; A.pixels = (uint32_t)pixels;
+    A.triRec = D.triRec; A.triShade = D.triShade;
+    A.slotOf = (const uint32_t *)(block + oTables);
+    A.firstSlot = repeats ? A.slotOf + (size_t)tilesX * tilesY : nullptr;
+    A.ctl = (RtCamMoveCtl *)(block + oCtl); A.pos = block + oPos; A.count = (uint32_t *)(block + oCount); A.bigList = (uint32_t *)(block + oBig);
+    A.scanTmp = block + oScan; A.scanBytes = scanBytes;
+    return 0;
+}
+
+// One of the two lists made to hold `entries` entries (an eighth more than asked for, at least 1024, at most 2^32 - 1); an existing
+// buffer is only ever replaced by a larger one; `exact`: of just `entries` entries (the other set's capacity).  The caller has made sure no work reads set `i`.
+static bool cam_move_list(rtHipScene *sc, int i, uint64_t entries, bool exact = false)
+{
+    rtHipScene::CamMove &C = sc->cam;
+    if (C.listCap[i] >= entries && C.list[i]) return true;
+    const uint64_t cap = exact ? entries : std::min<uint64_t>(std::max<uint64_t>(entries + entries / 8, 1024), 0xffffffffull);
+    uint32_t *p = nullptr;
+    if (hipMalloc((void **)&p, cap * 4) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (C.list[i]) { (void)hipFree(C.list[i]); sc->bytes -= C.listCap[i] * 4; }
+    C.list[i] = p; C.listCap[i] = cap;
+    sc->bytes += cap * 4;
+    return true;
+}
+
+int rtHipSceneSetCamera(rtHipScene *sc, const rtHipCamera *cam)
+{
+    if (!sc || !cam) return fail("rtHipSceneSetCamera: null argument");
+    const uint64_t listLimit = std::min<uint64_t>(tuning().buildListLimit, 0xffffffffull); // this entry point's one look at the tuning values
+#define CAM_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { fail("rtHipSceneSetCamera: %s failed: %s", #expr, hipGetErrorString(e_)); return -2; } } while (0)
+    CAM_HIP(hipSetDevice(sc->device));
+    // work already issued reads the old lists: planned frames are verified (and redone, watched, if their plan was short) while the old
+    // camera is still in effect, then the stream is idle
+    if (sc->unverified && frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -2;
+    CAM_HIP(hipStreamSynchronize(sc->stream));
+    if (const int rc = cam_move_init(sc)) return rc;
+    rtHipScene::CamMove &C = sc->cam;
+    const int target = C.live == 0 ? 1 : 0;
+    RtCamMoveArgs A = C.args;
+    for (int i = 0; i < 3; ++i) { A.eye[i] = cam->eye[i]; A.topLeft[i] = cam->eyeToTopLeft[i]; A.lr[i] = cam->leftToRight[i]; A.tb[i] = cam->topToBottom[i]; }
+    A.pixelSizeInv = cam->pixelSizeInv;
+    A.start = C.start[target]; A.end = C.end[target]; A.list = nullptr;
+    CAM_HIP(hipEventRecord(C.ev[0], sc->stream));
+    CAM_HIP(rtc_launch_count(&A, sc->stream));
+    CAM_HIP(hipEventRecord(C.ev[1], sc->stream));
+    RtCamMoveCtl ctl{};
+    CAM_HIP(hipMemcpyAsync(&ctl, A.ctl, sizeof ctl, hipMemcpyDeviceToHost, sc->stream)); // the only words that come back: 16 bytes
+    CAM_HIP(hipStreamSynchronize(sc->stream));
+    if (ctl.total > listLimit) {
+        fail("rtHipSceneSetCamera: the view's lists hold %llu entries, more than the limit of %llu", ctl.total, (unsigned long long)listLimit);
+        return -3;
+    }
+    if (!cam_move_list(sc, target, ctl.total)) {
+        fail("rtHipSceneSetCamera: no memory for a list of %llu entries", ctl.total);
+        return -4;
+    }
+    A.list = C.list[target];
+    CAM_HIP(hipEventRecord(C.ev[2], sc->stream));
+    CAM_HIP(rtc_launch_fill(&A, sc->stream));
+    CAM_HIP(hipEventRecord(C.ev[3], sc->stream));
+    CAM_HIP(hipStreamSynchronize(sc->stream));
+    float ms0 = 0.f, ms1 = 0.f;
+    CAM_HIP(hipEventElapsedTime(&ms0, C.ev[0], C.ev[1]));
+    CAM_HIP(hipEventElapsedTime(&ms1, C.ev[2], C.ev[3]));
+#undef CAM_HIP
+    // the new view is complete: it takes the old one's place
+    RtDevScene &D = sc->dev;
+    for (int i = 0; i < 3; ++i) { D.eye[i] = cam->eye[i]; D.topLeft[i] = cam->eyeToTopLeft[i]; D.lr[i] = cam->leftToRight[i]; D.tb[i] = cam->topToBottom[i]; }
+    D.pixelSizeInv = cam->pixelSizeInv;
+    D.camStart = C.start[target]; D.camEnd = C.end[target]; D.camList = C.list[target];
+    sc->camListSize = ctl.total;
+    C.live = target;
+    C.log[0] = D.triangleCount - ctl.bigCount; C.log[1] = ctl.bigCount; C.log[2] = ctl.total;
+    C.ms[0] = ms0; C.ms[1] = ms1;
+    sc->planRounds = 0; // other rays: the next frame watches its queue again
+    refresh_views(sc);
+    sc->release_part(PART_CAMERA); // the lists the scene was created with (the first move only)
+    // the other list is made as large as this one now, so that the next move to a view of no more entries allocates nothing; if that
+    // fails the move has succeeded all the same and the next one tries again
+    (void)cam_move_list(sc, target ^ 1, C.listCap[target], true);
+    return 0;
+}
+
+int rtHipTestSceneCameraList(const rtHipScene *sc, uint64_t first, uint64_t count, cl_uint *out)
+{
+    if (!sc) return fail("rtHipTestSceneCameraList: null scene");
+    if (sc->camListSize > 0x7fffffffull) return fail("rtHipTestSceneCameraList: the list has %llu entries", (unsigned long long)sc->camListSize);
+    if (!out) return (int)sc->camListSize;
+    if (first > sc->camListSize || count > sc->camListSize - first)
+        return fail("rtHipTestSceneCameraList: entries %llu + %llu reach past the %llu of the list", (unsigned long long)first, (unsigned long long)count,
+                    (unsigned long long)sc->camListSize);
+    if (!count) return 0;
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipStreamSynchronize(sc->stream));
+    HIP_OK(hipMemcpy(out, sc->dev.camList + first, count * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rtHipTestScenePointers(const rtHipScene *sc, const void *out[6])
+{
+    if (!sc || !out) return fail("rtHipTestScenePointers: null argument");
+    const RtDevScene &D = sc->dev;
+    out[0] = D.triRec; out[1] = D.triShade; out[2] = D.gridBlockSparse; out[3] = D.pairRec; out[4] = D.matRec; out[5] = D.lightPos;
+    return 0;
+}
+
+int rtHipTestSceneCameraLog(const rtHipScene *sc, uint64_t out[3])
+{
+    if (!sc || !out) return fail("rtHipTestSceneCameraLog: null argument");
+    for (int i = 0; i < 3; ++i) out[i] = sc->cam.log[i];
+    return 0;
+}
+
+int rtHipTestSceneCameraTimes(const rtHipScene *sc, double out[2])
+{
+    if (!sc || !out) return fail("rtHipTestSceneCameraTimes: null argument");
+    out[0] = sc->cam.ms[0]; out[1] = sc->cam.ms[1];
+    return 0;
+}
 
 int rtHipRenderTiles(rtHipScene *sc, void *stream)
 {

@@ -85,6 +85,11 @@ BAKE_DEFAULTS = dict(rays=16, radius=float("inf"), seed=0, dilate=2)
 ALL_TRIANGLES = 0xFFFFFFFF
 
 
+class Camera(C.Structure):  # rtHipCamera
+    _fields_ = [("eye", C.c_float * 4), ("eyeToTopLeft", C.c_float * 4), ("leftToRight", C.c_float * 4), ("topToBottom", C.c_float * 4),
+                ("pixelSizeInv", C.c_float)]
+
+
 class Stats(C.Structure):  # rtHipStats
     _fields_ = [(n, C.c_uint64) for n in ("primarySamples", "primaryCandidates", "gridRays", "gridCells", "gridCandidates", "shadedHits", "texelFetches")]
 
@@ -99,7 +104,7 @@ DROPIN_SYMBOLS = [
     "dot", "cross", "normalize", "vector", "bindf", "GetPointToLineSqLen", "RayIntersectsTriangle", "GetBoxAddress",
 ]
 RESIDENT_SYMBOLS = [
-    "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipRenderTiles", "rtHipFrameFinish",
+    "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipSceneGetCamera", "rtHipSceneSetCamera", "rtHipRenderTiles", "rtHipFrameFinish",
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
@@ -110,7 +115,7 @@ RESIDENT_SYMBOLS = [
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
-    "rtHipTestShadeKat", "rtHipTestSceneView",
+    "rtHipTestShadeKat", "rtHipTestSceneView", "rtHipTestSceneCameraList", "rtHipTestScenePointers", "rtHipTestSceneCameraLog", "rtHipTestSceneCameraTimes",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm", "rtHipWritePfmRgb",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
@@ -169,6 +174,12 @@ def lib() -> C.CDLL:
     L.rtHipSceneDestroy.restype = None
     L.rtHipSceneBytes.restype = u64
     L.rtHipSceneBytes.argtypes = [vp]
+    L.rtHipSceneGetCamera.argtypes = [vp, C.POINTER(Camera)]
+    L.rtHipSceneSetCamera.argtypes = [vp, C.POINTER(Camera)]
+    L.rtHipTestSceneCameraList.argtypes = [vp, u64, u64, vp]
+    L.rtHipTestScenePointers.argtypes = [vp, C.POINTER(vp * 6)]
+    L.rtHipTestSceneCameraLog.argtypes = [vp, C.POINTER(u64 * 3)]
+    L.rtHipTestSceneCameraTimes.argtypes = [vp, C.POINTER(C.c_double * 2)]
     L.rtHipRenderTiles.argtypes = [vp, vp]
     L.rtHipFrameFinish.argtypes = [vp, C.POINTER(C.c_int)]
     L.rtHipRenderTilesCounted.argtypes = [vp, C.POINTER(Stats)]
@@ -587,6 +598,31 @@ def tiles_of_rank(width: int, height: int, rank: int, world: int) -> np.ndarray:
     return np.arange(rank, tile_count(width, height), world, dtype=np.uint32)
 
 
+def look_at_vectors(position, look_at, up, fov: float, width: int, height: int):
+    """(eye_to_top_left, left_to_right, top_to_bottom, pixel_size_inv) of a camera at `position` looking at `look_at`: frontend.set_camera."""
+    from . import frontend
+    return frontend.set_camera(position, look_at, up, fov, width, height)
+
+
+def orbit_positions(position, look_at, count: int) -> list:
+    """`count` eye positions on the circle through `position` about the vertical (y) axis through `look_at`: pose i is `position` turned by
+    i * 360 / count degrees, so every pose keeps the first one's height and its distance to the axis (float64 arithmetic)."""
+    p, c = np.asarray(position, np.float64)[:3], np.asarray(look_at, np.float64)[:3]
+    dx, dz = p[0] - c[0], p[2] - c[2]
+    out = []
+    for i in range(count):
+        a = 2.0 * np.pi * i / count
+        out.append(np.array([c[0] + dx * np.cos(a) + dz * np.sin(a), p[1], c[2] - dx * np.sin(a) + dz * np.cos(a)], np.float64))
+    return out
+
+
+def orbit_path(path: str, index: int) -> str:
+    """img.bmp -> img_007.bmp: the file an orbit's view `index` is written to."""
+    import os
+    root, ext = os.path.splitext(path)
+    return f"{root}_{index:03d}{ext}"
+
+
 class ResidentScene:
     """A scene resident in one GPU's HBM (rtHipScene)."""
 
@@ -611,6 +647,64 @@ class ResidentScene:
             self.handle = None
 
     __del__ = close
+
+    def try_set_camera(self, eye, eye_to_top_left, left_to_right, top_to_bottom, pixel_size_inv) -> int:
+        """rtHipSceneSetCamera's return code (0, or a negative code with last_error() set): the scene's camera becomes the five fields and
+        the candidate lists of its tiles are rebuilt on the device.  On failure the scene keeps its old view."""
+        cam = Camera()
+        for dst, src in ((cam.eye, eye), (cam.eyeToTopLeft, eye_to_top_left), (cam.leftToRight, left_to_right), (cam.topToBottom, top_to_bottom)):
+            v = np.asarray(src, np.float32).reshape(-1)
+            for i in range(3):
+                dst[i] = v[i]
+        cam.pixelSizeInv = np.float32(pixel_size_inv)
+        return int(lib().rtHipSceneSetCamera(self.handle, C.byref(cam)))
+
+    def set_camera(self, eye, eye_to_top_left, left_to_right, top_to_bottom, pixel_size_inv) -> None:
+        """Moves the resident scene's camera (rtHipSceneSetCamera); raises RuntimeError when the move is refused."""
+        rc = self.try_set_camera(eye, eye_to_top_left, left_to_right, top_to_bottom, pixel_size_inv)
+        if rc != 0:
+            raise RuntimeError(f"rtHipSceneSetCamera failed ({rc}): {last_error()}")
+
+    def look_at(self, position, look_at, up, fov: float) -> None:
+        """Moves the camera to `position`, looking at `look_at`: the vectors frontend.set_camera gives for the scene's image size."""
+        self.set_camera(position, *look_at_vectors(position, look_at, up, fov, self.scene.width, self.scene.height))
+
+    def camera(self) -> dict:
+        """The camera in effect (rtHipSceneGetCamera): eye, eye_to_top_left, left_to_right, top_to_bottom ([4] float32), pixel_size_inv."""
+        cam = Camera()
+        self._check(lib().rtHipSceneGetCamera(self.handle, C.byref(cam)), "rtHipSceneGetCamera")
+        return dict(eye=np.array(cam.eye, np.float32), eye_to_top_left=np.array(cam.eyeToTopLeft, np.float32),
+                    left_to_right=np.array(cam.leftToRight, np.float32), top_to_bottom=np.array(cam.topToBottom, np.float32),
+                    pixel_size_inv=float(cam.pixelSizeInv))
+
+    def camera_list(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Entries of the device camera list the scene's ranges index (rtHipTestSceneCameraList)."""
+        total = lib().rtHipTestSceneCameraList(self.handle, 0, 0, None)
+        if total < 0:
+            raise RuntimeError("rtHipTestSceneCameraList failed: " + last_error())
+        if count is None:
+            count = max(total - first, 0)
+        out = np.zeros(count, np.uint32)
+        self._check(lib().rtHipTestSceneCameraList(self.handle, first, count, _ptr(out)), "rtHipTestSceneCameraList")
+        return out
+
+    def pointers(self) -> tuple:
+        """Device addresses of triRec, triShade, gridBlockSparse, pairRec, matRec, lightPos (rtHipTestScenePointers)."""
+        out = (C.c_void_p * 6)()
+        self._check(lib().rtHipTestScenePointers(self.handle, C.byref(out)), "rtHipTestScenePointers")
+        return tuple(int(v or 0) for v in out)
+
+    def camera_log(self) -> dict:
+        """The last move: triangles rasterised by one thread, by a workgroup, list entries (rtHipTestSceneCameraLog)."""
+        out = (C.c_uint64 * 3)()
+        self._check(lib().rtHipTestSceneCameraLog(self.handle, C.byref(out)), "rtHipTestSceneCameraLog")
+        return dict(thread=int(out[0]), group=int(out[1]), entries=int(out[2]))
+
+    def camera_times_ms(self) -> dict:
+        """Device time of the last move's two stages (rtHipTestSceneCameraTimes)."""
+        out = (C.c_double * 2)()
+        self._check(lib().rtHipTestSceneCameraTimes(self.handle, C.byref(out)), "rtHipTestSceneCameraTimes")
+        return dict(count=out[0], fill=out[1])
 
     def path_class(self) -> int:
         """The path class this scene's logic kernels run (rtHipTestPathClass: 0 when it was built with logic_class = 0)."""
