@@ -250,6 +250,61 @@ typedef struct rtHipCamera {
 int rtHipSceneGetCamera(const rtHipScene *scene, rtHipCamera *out);
 int rtHipSceneSetCamera(rtHipScene *scene, const rtHipCamera *camera);
 
+/* The SHAPE of a resident scene, changed on the device.  rtHipSceneSetGeometry replaces the vertex array (and, where given, the index array
+ * and the corner normals) of a resident scene and rebuilds everything that depends on them where the data lives: triangle records, the
+ * 256^3 grid, its dense view and pair records, and the per-pixel candidate lists of the camera in effect.  The triangle count never changes.
+ *   Equivalence.  After it returns 0 the scene is, for everything the public API shows, the scene rtHipSceneCreate would have made from
+ *   the same description with vertexCount, vertex (and triIndex, triNormal where given) replaced, boxMin / gridStart / gridList = what
+ *   rtHipBuildSceneGrid returns for the new arrays, the camera in effect (after any rtHipSceneSetCamera) and camStart / camEnd / camList =
+ *   what rtHipBuildCameraList returns for it: every later frame on both pipelines, pass, surface pass, denoise, AO image, AO bake and ray
+ *   query is bit-identical to that scene's.  The per-pixel lists have the same CONTENTS as the host builder's, as after a camera move
+ *   (range numbers may differ, see there).  UVs, material ids, materials, lights, tile set, sample count, pipeline and pass mask are
+ *   untouched.
+ *   Stages, all on the scene's stream: host arrays are staged to the device (device pointers are checked like rtHipSceneIntersectDevice's);
+ *   every index is checked on the device before anything gathers through it (a retained index array too: V may have shrunk); new triangle
+ *   records (rt_prepare_triangles' operations; UV, material and -- without triNormal -- normal words are carried over from the rows the
+ *   scene holds); the grid from the device-resident arrays by the kernels of rtHipBuildSceneGridDevice; the dense view and the pair
+ *   records; the camera lists through the resident camera build of rtHipSceneSetCamera; the swap.
+ *   Everything stays on the device.  No array whose size grows with V, T, the pair count or the list entries crosses the bus from device
+ *   to host, and host to device only the caller's own host arrays (and 4 KB of planes and cell table).  What the host reads: the error
+ *   word, the fill's counters (24 bytes, up to four times), the 257 x 16 bytes of split planes, the camera build's 16 bytes.  Materials,
+ *   lights, path state and the pass / surface / denoise / AO / bake scratch keep their allocations and addresses.
+ *   Transactional.  The new records, grid and lists are built into storage the frames do not read and take the old ones' place at the
+ *   very end; on any failure the scene keeps its old shape, camera lists, retained index array and launch plan and renders what it
+ *   rendered before.  Returns -1 for a NULL argument, a NULL vertex with vertexCount > 0, triIndex == NULL when nothing is retained (a
+ *   scene drops the index array it was created with: the first update brings one), or a bad device pointer; -5 with the text
+ *   "scene rejected (0x..): ..." for an index outside [0, vertexCount); -3 when the grid holds 2^28 pairs or more (the trace kernel's record
+ *   limit) or more than rtHipTune("build_list_limit"), or the camera lists exceed that limit; -7 as rtHipBuildSceneGridDevice; -4 when device
+ *   memory could not be had; -2 for any other HIP failure; each with a text in rtHipLastError().
+ *   Ordering.  Synchronous on the scene's own stream like rtHipSceneSetCamera: it waits for what was issued there, planned frames are
+ *   verified first, and on return the new shape is in effect for everything issued afterwards; the launch plan is dropped, the next frame
+ *   is a watched one.  With arraysOnDevice == 1 the CALLER has synchronised the stream that produced the arrays before the call (there is
+ *   no stream argument), and the arrays are not needed after it returns.
+ *   Vertices that are not finite: no promise beyond "the grid rtHipBuildSceneGridDevice gives for the same arrays".  Degenerate triangles
+ *   (zero area, repeated corners) are handled like everywhere else.
+ *   Peers.  Instances made with rtHipSceneCreateLike and instances over tile subsets are updated one by one by the caller; each builds
+ *   its own grid.  A scene that was updated can be the `like` of a new instance.
+ *   Memory.  The first update makes a SECOND set of everything the kernels read of the shape (64 + 96 bytes per triangle, 64 MB of grid
+ *   starts, 50 MB of block table, 2 MB of occupancy words, 4 + 64 bytes per pair) -- updates build into the set that is not in use, and
+ *   the parts the scene was created with are freed after the first one -- and the build scratch, which stays: the grid build's storage
+ *   (two key buffers of max(32 T, 2^22) x 8 bytes, 24 bytes per vertex, 64 MB of cell counts, sort temporaries; when a triangle is too
+ *   large for one thread also 8 fill queues of 64 MB and 16 maps of 2 MB), staging for host vertices and normals (made by the first update
+ *   from host arrays, the normals' whether it brings normals or not), two index arrays of 16 bytes per triangle (the retained one and
+ *   the one being checked), 4 bytes per triangle of stand-in material ids, 8 bytes per pair
+ *   of pair order, and the camera move's storage.  A buffer too small for an update is replaced by one of needed + needed / 8 and never
+ *   shrinks, and after an update the other set is made as large, so that a later update needing no more pairs and list entries
+ *   allocates nothing.  All of it is counted in rtHipSceneBytes and freed with the scene.  A scene that is never updated holds none of it.
+ *   Tuning.  The call reads "build_list_limit" and "build_key_cap" once at entry. */
+typedef struct rtHipGeometryUpdate {
+    cl_uint          vertexCount;     /* V of the new vertex array */
+    const cl_float3 *vertex;          /* V x 16 bytes, required */
+    const cl_int3   *triIndex;        /* T x 16 bytes (T = the scene's triangle count, which never changes); NULL = the index array the
+                                         scene retained from its previous successful update */
+    const cl_float3 *triNormal;       /* 3T x 16 bytes of corner normals; NULL = keep the normals the scene holds */
+    cl_int           arraysOnDevice;  /* as in rtHipSceneDesc: 0 host arrays, 1 device arrays of the scene's device (16-byte aligned) */
+} rtHipGeometryUpdate;
+int rtHipSceneSetGeometry(rtHipScene *scene, const rtHipGeometryUpdate *update);
+
 /* Renders all samples of the scene's tiles into its device-resident tile buffer
  * ([tile][plane R,G,B][128*128] u16, tiles in the order given at creation).  Asynchronous on `stream`
  * (a hipStream_t passed as void*; NULL = the scene's own stream).  Returns 0 on success. */
@@ -791,6 +846,15 @@ int rtHipTestSceneCameraList(const rtHipScene *scene, uint64_t first, uint64_t c
 int rtHipTestScenePointers(const rtHipScene *scene, const void *out[6]);
 int rtHipTestSceneCameraLog(const rtHipScene *scene, uint64_t out[3]);
 int rtHipTestSceneCameraTimes(const rtHipScene *scene, double out[2]);
+
+/* TEST-ONLY, for rtHipSceneSetGeometry.  rtHipTestSceneGeometryLog gives, for the scene's last successful update, out[i] for i < n:
+ * triangles whose cells one thread filled, triangles handed to workgroups, fill attempts (2 after the first fill overflowed its key
+ * buffer), (cell, triangle) pairs, camera list entries, and 1 when any device buffer was allocated or replaced by that update (zeros
+ * before the first update; fields past the sixth read 0); it returns 6.  rtHipTestSceneGeometryTimes gives that update's time on the
+ * scene's stream in milliseconds, from HIP events: [0] index check and records, [1] grid, [2] dense view and pair gather, [3] camera
+ * lists; the host's looks at counters lie inside the stages.  -1 with a rtHipLastError() text for a NULL argument. */
+int rtHipTestSceneGeometryLog(const rtHipScene *scene, uint64_t *out, cl_uint n);
+int rtHipTestSceneGeometryTimes(const rtHipScene *scene, double ms[4]);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,12 @@ def parser():
                          "first eye and are not re-oriented by a move; a scene whose normals come from the file is unaffected.  For the "
                          "built-in scenes every view, the first included, is set through --eye / --look-at / --fov (defaults: the origin and "
                          "(0, 0, 3))")
+    ap.add_argument("--spin", type=int, default=1, metavar="N",
+                    help="N frames of the one resident scene with the meshes turned by i * 360 / N degrees about the vertical axis through the "
+                         "look-at point (vertices and corner normals turned, lights and camera fixed), each after the first through "
+                         "ResidentScene.set_vertices (grid and camera lists are rebuilt on the device); outputs are numbered like --orbit's.  "
+                         "For the built-in scenes the camera is set through --eye / --look-at / --fov as for --orbit (defaults: the origin "
+                         "and (0, 0, 3)).  One GPU only; not together with --orbit or --bake-ao")
     return ap
 
 
@@ -84,6 +90,10 @@ def parse_args(argv=None):
         ap.error("--orbit N needs N >= 1")
     if args.orbit > 1 and args.bake_ao:
         ap.error("--orbit does not go with --bake-ao (a bake does not read the camera)")
+    if args.spin < 1:
+        ap.error("--spin N needs N >= 1")
+    if args.spin > 1 and (args.orbit > 1 or args.bake_ao):
+        ap.error("--spin does not go with --orbit or --bake-ao")
     if args.surface_passes and not args.passes:
         ap.error("--surface-passes needs --passes PREFIX")
     if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
@@ -233,6 +243,39 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
     return spent
 
 
+def render_spin(sc, args, device: int, centre, eye=None) -> float:
+    """--spin: args.spin frames of one ResidentScene on HIP device `device`, the meshes turned on the device between them.  `eye`: the
+    camera is set through look_at first (the built-in scenes, as --orbit does).  Returns the seconds the updates, frames and read-backs
+    took."""
+    from . import raytrace
+    rs = raytrace.ResidentScene(sc, device)
+    try:
+        if eye is not None:
+            rs.look_at(eye, centre, (0, 1, 0), np.radians(args.fov))
+        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise)
+        if basic or surface:
+            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        vertex, index, normal = sc.vertex, sc.tri_index, sc.tri_normal
+        spent = 0.0
+        for i in range(args.spin):
+            t = time.perf_counter()
+            if i:
+                rs.set_vertices(raytrace.spin_vertices(vertex, centre, i, args.spin), index if i == 1 else None,
+                                raytrace.spin_directions(normal, i, args.spin))
+            rs.render()
+            planes = [p.reshape(sc.height, sc.width) for p in rs.readback()]
+            spent += time.perf_counter() - t
+            passes = rs.readback_passes() if basic or surface else None
+            if passes is not None and "triangle" in passes and "mesh" not in passes:
+                passes["mesh"] = np.where(passes["triangle"] != 0xFFFFFFFF, 0, -1).astype(np.int32)
+            denoised = rs.denoise() if args.denoise else None
+            ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
+            write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+    finally:
+        rs.close()
+    return spent
+
+
 def main(argv=None):
     args = parse_args(argv)
 
@@ -259,6 +302,15 @@ def main(argv=None):
     cam_ms = raytrace.build_camera_list_device(sc, 0)
     grid_ms = raytrace.build_scene_grid_device(sc, 0)
     t2 = time.perf_counter()
+    if args.spin > 1:
+        if args.device == raytrace.lib().rtHipDeviceCount() + 1:
+            sys.exit("--spin renders on one GPU: choose --device 1..%d" % raytrace.lib().rtHipDeviceCount())
+        centre = look_at if args.obj else (np.asarray(args.look_at, np.float32) if args.look_at else np.float32([0, 0, 3]))
+        first_eye = None if args.obj else (np.asarray(args.eye, np.float32) if args.eye else np.zeros(3, np.float32))
+        spent = render_spin(sc, args, args.device - 1, centre, first_eye)
+        print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel, "
+              f"{args.spin} poses -> {raytrace.orbit_path(args.out, 0)} ..\n  updates + frames + read-backs {1e3 * spent:.0f} ms = {args.spin / spent:.1f} frames/s")
+        return 0
     if args.orbit > 1:
         if args.device == raytrace.lib().rtHipDeviceCount() + 1:
             sys.exit("--orbit renders on one GPU: choose --device 1..%d" % raytrace.lib().rtHipDeviceCount())

@@ -7,6 +7,7 @@
 #include "raytrace_hip.h"
 #include "rt_device.h"
 #include "rt_camera_move.h"
+#include "rt_geometry_move.h"
 #include "rt_build_shared.h"
 
 #include <hip/hip_runtime_api.h>
@@ -362,6 +363,28 @@ struct rtHipScene {
         uint64_t log[3] = {};
         double ms[2] = {};
     } cam;
+    // geometry updates (rtHipSceneSetGeometry), made by the first update: TWO sets of everything the kernels read of the shape (triangle
+    // records, shading rows, planes, cell table, grid starts and list, occupancy words, block table, pair records) -- an update builds into
+    // the set the frames do not read and the sets change places at its end; the parts the scene was created with are freed after the
+    // first update.  pairCap: entries the set's list and pair records hold.  The rest is build scratch that stays: the grid build's space,
+    // staging for host arrays, two index arrays (the retained one and the one being checked), the pair order.
+    struct GeoMove {
+        struct Set {
+            float *triRec = nullptr, *triShade = nullptr, *boxMin = nullptr, *pairRec = nullptr;
+            uint8_t *cellLut = nullptr;
+            uint32_t *gridStart = nullptr, *gridList = nullptr, *sparse = nullptr;
+            unsigned long long *gridBits = nullptr;
+            uint64_t listCap = 0, pairCap = 0; // in bytes
+        } set[2];
+        int live = -1;      // the set in use; -1 while the scene still renders from the parts it was created with
+        RtGridSpace space{};
+        char *vertexBuf = nullptr, *normalBuf = nullptr, *index[2] = {}, *material = nullptr, *pairOrder = nullptr, *pairInfo = nullptr, *denseTmp = nullptr;
+        uint64_t vertexCap = 0, normalCap = 0, indexCap[2] = {}, materialCap = 0, orderCap = 0, infoCap = 0, denseCap = 0; // in bytes
+        int retained = -1;  // which index array the last successful update left; -1: none (creation drops the index array)
+        hipEvent_t ev[5] = {};
+        uint64_t log[6] = {}; // per thread, per workgroup, attempts, pairs, camera entries, allocated
+        double ms[4] = {};
+    } geo;
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -533,6 +556,27 @@ int build_geometry(rtHipScene *sc, const rtHipSceneDesc *d)
     return 0;
 }
 
+// What the host derives from the split planes ([3][257], one array per axis): the cell estimate table of rt_device.h (cellLut, [3][256])
+// and planesTame.  One arithmetic for a scene build and a geometry update.
+void grid_tables(const float *planes, uint8_t *lut, uint32_t *tame)
+{
+    for (int w = 0; w < 3; ++w) {
+        const float *pw = planes + w * (RT_GRID_DIV + 1);
+        const float lo = pw[0], step = (pw[RT_GRID_DIV] - pw[0]) / 256.f;
+        int c = 0;
+        for (int i = 0; i < 256; ++i) {
+            const float x = lo + ((float)i + 0.5f) * step;
+            while (c < RT_GRID_DIV - 1 && pw[c + 1] < x) ++c; // (planes ascend: the cell index only ever grows with i)
+            lut[w * 256 + i] = (uint8_t)c;
+        }
+    }
+    *tame = 1u;
+    for (int i = 0; i < 3 * (RT_GRID_DIV + 1); ++i) {
+        const float m = std::fabs(planes[i]);
+        if (!(m == 0.f || (m >= 0x1p-60f && m <= 0x1p39f))) *tame = 0u;
+    }
+}
+
 // the grid as the ABI hands it over, plus its dense view for the wavefront trace kernel, built on the device
 int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
 {
@@ -544,25 +588,9 @@ int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
     for (int w = 0; w < 3; ++w)
         for (int i = 0; i <= RT_GRID_DIV; ++i) planes[w * (RT_GRID_DIV + 1) + i] = d->boxMin[i].s[w];
     if (sc->upload(planes.data(), planes.size(), &D.boxMin, "boxMin")) return -1;
-    { // the cell estimate table of rt_device.h (cellLut)
-        std::vector<uint8_t> lut(3 * 256);
-        for (int w = 0; w < 3; ++w) {
-            const float *pw = planes.data() + w * (RT_GRID_DIV + 1);
-            const float lo = pw[0], step = (pw[RT_GRID_DIV] - pw[0]) / 256.f;
-            int c = 0;
-            for (int i = 0; i < 256; ++i) {
-                const float x = lo + ((float)i + 0.5f) * step;
-                while (c < RT_GRID_DIV - 1 && pw[c + 1] < x) ++c; // (planes ascend: the cell index only ever grows with i)
-                lut[w * 256 + i] = (uint8_t)c;
-            }
-        }
-        if (sc->upload(lut.data(), lut.size(), &D.cellLut, "cellLut")) return -1;
-    }
-    D.planesTame = 1u;
-    for (float pl : planes) {
-        const float m = std::fabs(pl);
-        if (!(m == 0.f || (m >= 0x1p-60f && m <= 0x1p39f))) D.planesTame = 0u;
-    }
+    std::vector<uint8_t> lut(3 * 256);
+    grid_tables(planes.data(), lut.data(), &D.planesTame);
+    if (sc->upload(lut.data(), lut.size(), &D.cellLut, "cellLut")) return -1;
     const uint64_t cells = (uint64_t)RT_GRID_DIV * RT_GRID_DIV * RT_GRID_DIV;
     if (!d->gridStart) return fail("null scenePixelTriangleListStart");
     const uint64_t listSize = sc->haveGridListSize ? sc->gridListSizeHint : d->gridStart[cells]; // (the last start = the list's length; read from the device by scene_build when the array lives there)
@@ -800,6 +828,11 @@ void refresh_views(rtHipScene *sc)
     }
 }
 
+// bytes of the fixed-size arrays of a grid (rtHipScene::GeoMove::Set)
+constexpr uint64_t GEO_PLANE_BYTES = 3 * (RT_GRID_DIV + 1) * 4, GEO_LUT_BYTES = 3 * 256, GEO_START_BYTES = ((uint64_t)RT_GRID_DIV * RT_GRID_DIV * RT_GRID_DIV + 1) * 4,
+                   GEO_BITS_BYTES = (uint64_t)(RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * 8,
+                   GEO_SPARSE_BYTES = (uint64_t)3 * ((63u << 16 | 63u << 8 | 63u) + 1u) * 4;
+
 // One of the parts every instance of a scene holds alike (geometry, grid, materials, lights), copied from an instance that has it --
 // device to device, over xGMI between GPUs -- instead of uploaded and reshaped once more: the "all GPUs" mode builds the scene once
 // ("upload once via root then broadcast").  The source's work on the part must be complete (its builders synchronise).
@@ -808,12 +841,23 @@ int clone_part(rtHipScene *dst, const rtHipScene *src, int part)
     dst->release_part(part);
     dst->curPart = part;
     std::vector<std::pair<const char *, char *>> moved; // (source block, copy)
-    for (size_t i = 0; i < src->partAllocs[part].size(); ++i) {
+    std::vector<void *> blocks = src->partAllocs[part];
+    std::vector<uint64_t> sizes = src->partSizes[part];
+    if (src->geo.live >= 0 && (part == PART_GEOMETRY || part == PART_GRID)) { // a source whose shape was updated holds it in a set of its own
+        const rtHipScene::GeoMove::Set &L = src->geo.set[src->geo.live];
+        const uint64_t T = src->dev.triangleCount ? src->dev.triangleCount : 1, n = src->gridListSize ? src->gridListSize : 1;
+        if (part == PART_GEOMETRY) { blocks = { L.triRec, L.triShade }; sizes = { T * 64, T * 96 }; }
+        else {
+            blocks = { L.boxMin, L.cellLut, L.gridStart, L.gridList, L.gridBits, L.sparse, L.pairRec };
+            sizes = { GEO_PLANE_BYTES, GEO_LUT_BYTES, GEO_START_BYTES, n * 4, GEO_BITS_BYTES, GEO_SPARSE_BYTES, n * 64 };
+        }
+    }
+    for (size_t i = 0; i < blocks.size(); ++i) {
         char *p = nullptr;
-        const uint64_t n = src->partSizes[part][i];
+        const uint64_t n = sizes[i];
         if (dst->alloc<char>(n, &p)) return -1;
-        HIP_OK(hipMemcpyPeerAsync(p, dst->device, src->partAllocs[part][i], src->device, n, dst->stream));
-        moved.emplace_back((const char *)src->partAllocs[part][i], p);
+        HIP_OK(hipMemcpyPeerAsync(p, dst->device, blocks[i], src->device, n, dst->stream));
+        moved.emplace_back((const char *)blocks[i], p);
     }
     auto at = [&](const void *old) -> const void * { // the copy of the block `old` points to (the builders hand out block starts only)
         for (auto &m : moved) if (m.first == (const char *)old) return m.second;
@@ -1267,6 +1311,19 @@ void rtHipSceneDestroy(rtHipScene *sc)
     }
     for (hipEvent_t e : sc->cam.ev)
         if (e) (void)hipEventDestroy(e);
+    {
+        rtHipScene::GeoMove &G = sc->geo;
+        for (auto &L : G.set)
+            for (void *p : { (void *)L.triRec, (void *)L.triShade, (void *)L.boxMin, (void *)L.pairRec, (void *)L.cellLut, (void *)L.gridStart, (void *)L.gridList,
+                             (void *)L.sparse, (void *)L.gridBits })
+                if (p) (void)hipFree(p);
+        for (void *p : { (void *)G.vertexBuf, (void *)G.normalBuf, (void *)G.index[0], (void *)G.index[1], (void *)G.material, (void *)G.pairOrder, (void *)G.pairInfo,
+                         (void *)G.denseTmp })
+            if (p) (void)hipFree(p);
+        rt_grid_space_free(&G.space);
+        for (hipEvent_t e : G.ev)
+            if (e) (void)hipEventDestroy(e);
+    }
     for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
     sc->stager.destroy();
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
@@ -1351,6 +1408,62 @@ static bool cam_move_list(rtHipScene *sc, int i, uint64_t entries, bool exact = 
     return true;
 }
 
+// The lists of camera `cam` over the triangles in triRec / triShade, built into the set the frames do not read (*target) on the idle
+// stream of the scene and complete on return; nothing the scene renders from changes.  `who` names the entry point in error texts.
+static int cam_move_build(rtHipScene *sc, const rtHipCamera *cam, const float *triRec, const float *triShade, uint64_t listLimit, const char *who,
+                          int *target, RtCamMoveCtl *ctl, float ms[2])
+{
+#define CAM_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); return -2; } } while (0)
+    if (const int rc = cam_move_init(sc)) return rc;
+    rtHipScene::CamMove &C = sc->cam;
+    *target = C.live == 0 ? 1 : 0;
+    RtCamMoveArgs A = C.args;
+    A.triRec = triRec; A.triShade = triShade;
+    for (int i = 0; i < 3; ++i) { A.eye[i] = cam->eye[i]; A.topLeft[i] = cam->eyeToTopLeft[i]; A.lr[i] = cam->leftToRight[i]; A.tb[i] = cam->topToBottom[i]; }
+    A.pixelSizeInv = cam->pixelSizeInv;
+    A.start = C.start[*target]; A.end = C.end[*target]; A.list = nullptr;
+    CAM_HIP(hipEventRecord(C.ev[0], sc->stream));
+    CAM_HIP(rtc_launch_count(&A, sc->stream));
+    CAM_HIP(hipEventRecord(C.ev[1], sc->stream));
+    CAM_HIP(hipMemcpyAsync(ctl, A.ctl, sizeof *ctl, hipMemcpyDeviceToHost, sc->stream)); // the only words that come back: 16 bytes
+    CAM_HIP(hipStreamSynchronize(sc->stream));
+    if (ctl->total > listLimit) {
+        fail("%s: the view's lists hold %llu entries, more than the limit of %llu", who, ctl->total, (unsigned long long)listLimit);
+        return -3;
+    }
+    if (!cam_move_list(sc, *target, ctl->total)) {
+        fail("%s: no memory for a list of %llu entries", who, ctl->total);
+        return -4;
+    }
+    A.list = C.list[*target];
+    CAM_HIP(hipEventRecord(C.ev[2], sc->stream));
+    CAM_HIP(rtc_launch_fill(&A, sc->stream));
+    CAM_HIP(hipEventRecord(C.ev[3], sc->stream));
+    CAM_HIP(hipStreamSynchronize(sc->stream));
+    CAM_HIP(hipEventElapsedTime(&ms[0], C.ev[0], C.ev[1]));
+    CAM_HIP(hipEventElapsedTime(&ms[1], C.ev[2], C.ev[3]));
+#undef CAM_HIP
+    return 0;
+}
+
+// The view cam_move_build made takes the old one's place.
+static void cam_move_commit(rtHipScene *sc, const rtHipCamera *cam, int target, const RtCamMoveCtl &ctl)
+{
+    rtHipScene::CamMove &C = sc->cam;
+    RtDevScene &D = sc->dev;
+    for (int i = 0; i < 3; ++i) { D.eye[i] = cam->eye[i]; D.topLeft[i] = cam->eyeToTopLeft[i]; D.lr[i] = cam->leftToRight[i]; D.tb[i] = cam->topToBottom[i]; }
+    D.pixelSizeInv = cam->pixelSizeInv;
+    D.camStart = C.start[target]; D.camEnd = C.end[target]; D.camList = C.list[target];
+    sc->camListSize = ctl.total;
+    C.live = target;
+    sc->planRounds = 0; // other rays: the next frame watches its queue again
+    refresh_views(sc);
+    sc->release_part(PART_CAMERA); // the lists the scene was created with (the first move only)
+    // the other list is made as large as this one now, so that the next move to a view of no more entries allocates nothing; if that
+    // fails the move has succeeded all the same and the next one tries again
+    (void)cam_move_list(sc, target ^ 1, C.listCap[target], true);
+}
+
 int rtHipSceneSetCamera(rtHipScene *sc, const rtHipCamera *cam)
 {
     if (!sc || !cam) return fail("rtHipSceneSetCamera: null argument");
@@ -1361,51 +1474,16 @@ int rtHipSceneSetCamera(rtHipScene *sc, const rtHipCamera *cam)
     // camera is still in effect, then the stream is idle
     if (sc->unverified && frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -2;
     CAM_HIP(hipStreamSynchronize(sc->stream));
-    if (const int rc = cam_move_init(sc)) return rc;
-    rtHipScene::CamMove &C = sc->cam;
-    const int target = C.live == 0 ? 1 : 0;
-    RtCamMoveArgs A = C.args;
-    for (int i = 0; i < 3; ++i) { A.eye[i] = cam->eye[i]; A.topLeft[i] = cam->eyeToTopLeft[i]; A.lr[i] = cam->leftToRight[i]; A.tb[i] = cam->topToBottom[i]; }
-    A.pixelSizeInv = cam->pixelSizeInv;
-    A.start = C.start[target]; A.end = C.end[target]; A.list = nullptr;
-    CAM_HIP(hipEventRecord(C.ev[0], sc->stream));
-    CAM_HIP(rtc_launch_count(&A, sc->stream));
-    CAM_HIP(hipEventRecord(C.ev[1], sc->stream));
-    RtCamMoveCtl ctl{};
-    CAM_HIP(hipMemcpyAsync(&ctl, A.ctl, sizeof ctl, hipMemcpyDeviceToHost, sc->stream)); // the only words that come back: 16 bytes
-    CAM_HIP(hipStreamSynchronize(sc->stream));
-    if (ctl.total > listLimit) {
-        fail("rtHipSceneSetCamera: the view's lists hold %llu entries, more than the limit of %llu", ctl.total, (unsigned long long)listLimit);
-        return -3;
-    }
-    if (!cam_move_list(sc, target, ctl.total)) {
-        fail("rtHipSceneSetCamera: no memory for a list of %llu entries", ctl.total);
-        return -4;
-    }
-    A.list = C.list[target];
-    CAM_HIP(hipEventRecord(C.ev[2], sc->stream));
-    CAM_HIP(rtc_launch_fill(&A, sc->stream));
-    CAM_HIP(hipEventRecord(C.ev[3], sc->stream));
-    CAM_HIP(hipStreamSynchronize(sc->stream));
-    float ms0 = 0.f, ms1 = 0.f;
-    CAM_HIP(hipEventElapsedTime(&ms0, C.ev[0], C.ev[1]));
-    CAM_HIP(hipEventElapsedTime(&ms1, C.ev[2], C.ev[3]));
 #undef CAM_HIP
+    int target = 0;
+    RtCamMoveCtl ctl{};
+    float ms[2] = { 0.f, 0.f };
+    if (const int rc = cam_move_build(sc, cam, sc->dev.triRec, sc->dev.triShade, listLimit, "rtHipSceneSetCamera", &target, &ctl, ms)) return rc;
     // the new view is complete: it takes the old one's place
-    RtDevScene &D = sc->dev;
-    for (int i = 0; i < 3; ++i) { D.eye[i] = cam->eye[i]; D.topLeft[i] = cam->eyeToTopLeft[i]; D.lr[i] = cam->leftToRight[i]; D.tb[i] = cam->topToBottom[i]; }
-    D.pixelSizeInv = cam->pixelSizeInv;
-    D.camStart = C.start[target]; D.camEnd = C.end[target]; D.camList = C.list[target];
-    sc->camListSize = ctl.total;
-    C.live = target;
-    C.log[0] = D.triangleCount - ctl.bigCount; C.log[1] = ctl.bigCount; C.log[2] = ctl.total;
-    C.ms[0] = ms0; C.ms[1] = ms1;
-    sc->planRounds = 0; // other rays: the next frame watches its queue again
-    refresh_views(sc);
-    sc->release_part(PART_CAMERA); // the lists the scene was created with (the first move only)
-    // the other list is made as large as this one now, so that the next move to a view of no more entries allocates nothing; if that
-    // fails the move has succeeded all the same and the next one tries again
-    (void)cam_move_list(sc, target ^ 1, C.listCap[target], true);
+    cam_move_commit(sc, cam, target, ctl);
+    rtHipScene::CamMove &C = sc->cam;
+    C.log[0] = sc->dev.triangleCount - ctl.bigCount; C.log[1] = ctl.bigCount; C.log[2] = ctl.total;
+    C.ms[0] = ms[0]; C.ms[1] = ms[1];
     return 0;
 }
 
@@ -2157,6 +2235,190 @@ int rtHipSceneDenoiseTimes(const rtHipScene *sc, cl_float *ms)
 {
     if (!sc || !ms) return fail("null argument");
     for (int i = 0; i < 3; ++i) ms[i] = sc->denoiseMs[i];
+    return 0;
+}
+
+// ---- geometry updates ------------------------------------------------------------------------------------------------------------
+// A scene-owned device buffer of at least `need` bytes: kept when it is large enough, otherwise replaced by one of need + need / 8 bytes
+// (`exact`: of just `need`); contents are not carried over.  The caller has made sure no work reads it.
+static bool geo_fit(rtHipScene *sc, void *bufp, uint64_t *cap, uint64_t need, bool exact, bool *allocated)
+{
+    void **buf = (void **)bufp;
+    if (*buf && *cap >= need) return true;
+    const uint64_t want = std::max<uint64_t>(exact ? need : need + need / 8, 64);
+    void *q = nullptr;
+    if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (*buf) { (void)hipFree(*buf); sc->bytes -= *cap; }
+    *buf = q; *cap = want;
+    sc->bytes += want;
+    if (allocated) *allocated = true;
+    return true;
+}
+
+// the arrays of set `i` whose size only depends on the triangle count and, with `lists`, its list and pair records for `listBytes` / `pairBytes`
+static bool geo_set_fit(rtHipScene *sc, int i, bool lists, uint64_t listBytes, uint64_t pairBytes, bool exact, bool *allocated)
+{
+    rtHipScene::GeoMove::Set &L = sc->geo.set[i];
+    const uint64_t T = sc->dev.triangleCount;
+    uint64_t cRec = L.triRec ? T * 64 : 0, cShade = L.triShade ? T * 96 : 0, cPlane = L.boxMin ? GEO_PLANE_BYTES : 0, cLut = L.cellLut ? GEO_LUT_BYTES : 0,
+             cStart = L.gridStart ? GEO_START_BYTES : 0, cBits = L.gridBits ? GEO_BITS_BYTES : 0, cSparse = L.sparse ? GEO_SPARSE_BYTES : 0;
+    return geo_fit(sc, &L.triRec, &cRec, T * 64, true, allocated) && geo_fit(sc, &L.triShade, &cShade, T * 96, true, allocated) &&
+           geo_fit(sc, &L.boxMin, &cPlane, GEO_PLANE_BYTES, true, allocated) && geo_fit(sc, &L.cellLut, &cLut, GEO_LUT_BYTES, true, allocated) &&
+           geo_fit(sc, &L.gridStart, &cStart, GEO_START_BYTES, true, allocated) && geo_fit(sc, &L.gridBits, &cBits, GEO_BITS_BYTES, true, allocated) &&
+           geo_fit(sc, &L.sparse, &cSparse, GEO_SPARSE_BYTES, true, allocated) &&
+           (!lists || (geo_fit(sc, &L.gridList, &L.listCap, listBytes, exact, allocated) && geo_fit(sc, &L.pairRec, &L.pairCap, pairBytes, exact, allocated)));
+}
+
+int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
+{
+    static const char who[] = "rtHipSceneSetGeometry";
+    if (!sc || !up) return fail("%s: null argument", who);
+    rtHipScene::GeoMove &G = sc->geo;
+    const uint64_t V = up->vertexCount, T = sc->dev.triangleCount;
+    if (V && !up->vertex) return fail("%s: null vertex array with %llu vertices", who, (unsigned long long)V);
+    if (!up->triIndex && G.retained < 0) return fail("%s: no index array given and none retained (a scene drops the one it was created with)", who);
+    const Tuning tune = tuning(); // this entry point's one look at the tuning values
+    const uint64_t listLimit = std::min<uint64_t>(tune.buildListLimit, 0xffffffffull);
+#define GEO_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); return -2; } } while (0)
+#define GEO_MEM(expr, what) do { if (!(expr)) { fail("%s: no device memory for %s", who, what); return -4; } } while (0)
+    GEO_HIP(hipSetDevice(sc->device));
+    if (up->arraysOnDevice) {
+        if (V && query_pointer_ok(sc->device, "the scene", up->vertex, V * 16, 16, "vertex") != 0) return -1;
+        if (up->triIndex && T && query_pointer_ok(sc->device, "the scene", up->triIndex, T * 16, 16, "triIndex") != 0) return -1;
+        if (up->triNormal && T && query_pointer_ok(sc->device, "the scene", up->triNormal, T * 48, 16, "triNormal") != 0) return -1;
+    }
+    // work already issued reads the old shape: planned frames are verified while it is still in effect, then the stream is idle
+    if (sc->unverified && frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -2;
+    GEO_HIP(hipStreamSynchronize(sc->stream));
+    hipStream_t st = sc->stream;
+    bool allocated = false;
+    const uint64_t camCapBefore[2] = { sc->cam.listCap[0], sc->cam.listCap[1] };
+    const bool camMade = sc->cam.scratch == nullptr;
+    for (hipEvent_t &e : G.ev)
+        if (!e) GEO_HIP(hipEventCreate(&e));
+    if (!G.space.fillGroups) { G.space.fillGroups = 8; G.space.headroom = 1; }
+    const int target = G.live == 0 ? 1 : 0, spareIndex = G.retained == 0 ? 1 : 0;
+    rtHipScene::GeoMove::Set &N = G.set[target];
+    GEO_MEM(geo_set_fit(sc, target, false, 0, 0, true, &allocated), "the spare set of records and grid arrays");
+    GEO_MEM(geo_fit(sc, &G.material, &G.materialCap, T * 4, true, &allocated), "the build scratch");
+    if (allocated) GEO_HIP(hipMemsetAsync(G.material, 0xff, (size_t)G.materialCap, st)); // every id -1: rtp_validate reads a material per triangle
+
+    // 1. the caller's arrays on the device
+    const void *dVertex = up->vertex, *dIndex = up->triIndex, *dNormal = up->triNormal;
+    if (!up->arraysOnDevice) {
+        GEO_MEM(geo_fit(sc, &G.vertexBuf, &G.vertexCap, V * 16, false, &allocated), "the vertices");
+        GEO_HIP(sc->stager.copy(G.vertexBuf, up->vertex, V * 16));
+        dVertex = G.vertexBuf;
+        // (the normals' staging is made with the vertices', whether this update brings normals or not: a later one that does allocates nothing)
+        GEO_MEM(geo_fit(sc, &G.normalBuf, &G.normalCap, T * 48, true, &allocated), "the corner normals");
+        if (up->triNormal) {
+            GEO_HIP(sc->stager.copy(G.normalBuf, up->triNormal, T * 48));
+            dNormal = G.normalBuf;
+        }
+    }
+    // both index arrays are made by the first update: the retained one and the one a later update is checked in
+    GEO_MEM(geo_fit(sc, &G.index[0], &G.indexCap[0], T * 16, true, &allocated) && geo_fit(sc, &G.index[1], &G.indexCap[1], T * 16, true, &allocated), "the index arrays");
+    if (up->triIndex) { // host or device: the scene keeps a copy of its own
+        GEO_HIP(sc->stager.copy(G.index[spareIndex], up->triIndex, T * 16));
+        dIndex = G.index[spareIndex];
+    } else dIndex = G.index[G.retained];
+    GEO_HIP(sc->stager.drain());
+    GEO_HIP(hipEventRecord(G.ev[0], st));
+
+    // 2. ids are checked before anything gathers through them (the retained array too: V may have shrunk)
+    GEO_HIP(rtp_validate((uint32_t)T, (uint32_t)V, 0x7fffffffu, dIndex, (const int *)G.material, 0, nullptr, nullptr, 0, nullptr, sc->prepErr, st));
+    GEO_HIP(hipStreamSynchronize(st));
+    if (sc->check_prep() != 0) return -5;
+
+    // 3. records
+    GEO_HIP(rtg_launch_records((uint32_t)T, dVertex, dIndex, dNormal, sc->dev.triShade, N.triRec, N.triShade, st));
+    GEO_HIP(hipEventRecord(G.ev[1], st));
+
+    // 4. the grid, device arrays in, device arrays out
+    uint64_t pairs = 0, glog[RT_BUILD_LOG_FIELDS] = {};
+    G.space.allocated = 0;
+    const uint64_t spaceBefore = G.space.bytes;
+    const int grc = rt_grid_core_fill(&G.space, (uint32_t)V, (uint32_t)T, dVertex, dIndex, tune.buildKeyCap, listLimit, st, &pairs, glog);
+    sc->bytes += G.space.bytes - spaceBefore;
+    allocated = allocated || G.space.allocated;
+    if (grc == -3) { fail("%s: the grid holds %llu pairs, more than the limit of %llu", who, (unsigned long long)glog[RT_BUILD_LOG_PAIRS], (unsigned long long)listLimit); return -3; }
+    if (grc == -7) { fail("%s: a single triangle's fill outgrew its workgroup queue, or the second fill overflowed", who); return -7; }
+    if (grc == -4) { fail("%s: no device memory for the grid build", who); return -4; }
+    if (grc) { fail("%s: the grid build failed on the device", who); return -2; }
+    if (pairs >= RT_PAIR_LIMIT) { fail("%s: the grid holds 2^28 pairs or more: pair indices would not fit the trace kernel's records", who); return -3; }
+    GEO_MEM(geo_set_fit(sc, target, true, pairs * 4, pairs * 64, false, &allocated), "the grid list and pair records");
+    GEO_MEM(geo_fit(sc, &G.pairOrder, &G.orderCap, pairs * 4, false, &allocated) && geo_fit(sc, &G.pairInfo, &G.infoCap, pairs * 4, false, &allocated), "the pair order");
+    if (rt_grid_core_lists(&G.space, pairs, N.gridStart, N.gridList, st) != 0) { fail("%s: sorting the grid's pairs failed on the device", who); return -2; }
+    float bm[4 * (RT_GRID_DIV + 1)];
+    GEO_HIP(hipMemcpyAsync(bm, G.space.bm, sizeof bm, hipMemcpyDeviceToHost, st)); // 4 KB: the planes, for the tables the host derives
+    GEO_HIP(hipStreamSynchronize(st));
+    float planes[3 * (RT_GRID_DIV + 1)];
+    uint8_t lut[3 * 256];
+    uint32_t tame = 0;
+    for (int w = 0; w < 3; ++w)
+        for (int i = 0; i <= RT_GRID_DIV; ++i) planes[w * (RT_GRID_DIV + 1) + i] = bm[4 * i + w];
+    grid_tables(planes, lut, &tame);
+    GEO_HIP(hipMemcpyAsync(N.boxMin, planes, sizeof planes, hipMemcpyHostToDevice, st));
+    GEO_HIP(hipMemcpyAsync(N.cellLut, lut, sizeof lut, hipMemcpyHostToDevice, st));
+    GEO_HIP(hipEventRecord(G.ev[2], st));
+
+    // 5. the dense view and the pair records
+    size_t denseBytes = 0;
+    GEO_HIP(rtp_dense_grid(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &denseBytes, st));
+    GEO_MEM(geo_fit(sc, &G.denseTmp, &G.denseCap, denseBytes, true, &allocated), "the dense view's scratch");
+    denseBytes = (size_t)G.denseCap;
+    GEO_HIP(hipMemsetAsync(N.sparse, 0, GEO_SPARSE_BYTES, st));
+    GEO_HIP(rtp_dense_grid(N.gridStart, N.gridList, N.gridBits, N.sparse, (uint32_t *)G.pairOrder, (uint32_t *)G.pairInfo, G.denseTmp, &denseBytes, st));
+    GEO_HIP(rtk_launch_gather_pairs((uint32_t)pairs, (const uint32_t *)G.pairOrder, (const uint32_t *)G.pairInfo, N.triRec, N.pairRec, st));
+    GEO_HIP(hipEventRecord(G.ev[3], st));
+
+    // 6. the camera lists of the camera in effect, over the new records
+    rtHipCamera cam;
+    (void)rtHipSceneGetCamera(sc, &cam);
+    int camTarget = 0;
+    RtCamMoveCtl ctl{};
+    float camMs[2] = { 0.f, 0.f };
+    if (const int rc = cam_move_build(sc, &cam, N.triRec, N.triShade, listLimit, who, &camTarget, &ctl, camMs)) return rc;
+    GEO_HIP(hipEventRecord(G.ev[4], st));
+    GEO_HIP(hipStreamSynchronize(st));
+    float ms[4] = {};
+    for (int i = 0; i < 4; ++i) GEO_HIP(hipEventElapsedTime(&ms[i], G.ev[i], G.ev[i + 1]));
+#undef GEO_HIP
+#undef GEO_MEM
+
+    // 7. everything is complete: the new shape takes the old one's place
+    RtDevScene &D = sc->dev;
+    D.triRec = N.triRec; D.triShade = N.triShade;
+    D.boxMin = N.boxMin; D.cellLut = N.cellLut; D.planesTame = tame;
+    D.gridStart = N.gridStart; D.gridList = N.gridList; D.gridBits = N.gridBits; D.gridBlockSparse = N.sparse; D.pairRec = N.pairRec;
+    sc->gridListSize = pairs;
+    G.live = target;
+    if (up->triIndex) G.retained = spareIndex;
+    sc->cam.args.triRec = N.triRec; sc->cam.args.triShade = N.triShade;
+    cam_move_commit(sc, &cam, camTarget, ctl); // (refreshes the groups' views and drops the launch plan)
+    sc->release_part(PART_GEOMETRY); // what the scene was created with (the first update only)
+    sc->release_part(PART_GRID);
+    // the other set is made as large as this one now, so that the next update to a shape of no more pairs allocates nothing; if that fails
+    // the update has succeeded all the same and the next one tries again
+    (void)geo_set_fit(sc, target ^ 1, true, N.listCap, N.pairCap, true, &allocated);
+    allocated = allocated || camMade || camCapBefore[0] != sc->cam.listCap[0] || camCapBefore[1] != sc->cam.listCap[1];
+    G.log[0] = glog[RT_BUILD_LOG_GRID_THREAD]; G.log[1] = glog[RT_BUILD_LOG_GRID_GROUP]; G.log[2] = glog[RT_BUILD_LOG_ATTEMPTS];
+    G.log[3] = pairs; G.log[4] = ctl.total; G.log[5] = allocated ? 1 : 0;
+    for (int i = 0; i < 4; ++i) G.ms[i] = ms[i];
+    return 0;
+}
+
+int rtHipTestSceneGeometryLog(const rtHipScene *sc, uint64_t *out, cl_uint n)
+{
+    if (!sc || (n && !out)) return fail("rtHipTestSceneGeometryLog: null argument");
+    for (cl_uint i = 0; i < n; ++i) out[i] = i < 6 ? sc->geo.log[i] : 0;
+    return 6;
+}
+
+int rtHipTestSceneGeometryTimes(const rtHipScene *sc, double ms[4])
+{
+    if (!sc || !ms) return fail("rtHipTestSceneGeometryTimes: null argument");
+    for (int i = 0; i < 4; ++i) ms[i] = sc->geo.ms[i];
     return 0;
 }
 

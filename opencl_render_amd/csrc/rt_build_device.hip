@@ -19,6 +19,7 @@
 
 #include "raytrace_hip.h"
 #include "rt_build_shared.h"
+#include "rt_geometry_move.h"
 
 #include <chrono>
 #include <algorithm>
@@ -549,6 +550,219 @@ __global__ __launch_bounds__(256) void grid_write_list(unsigned long long n, con
 
 } // namespace
 
+// ---- the core: device arrays in, planes, starts and list left on the device (rt_geometry_move.h) -----------------------------
+// rtHipBuildSceneGridDevice below is a caller of it (upload, core, download), and so is rtHipSceneSetGeometry (rt_api.cpp), whose
+// space belongs to the scene and is kept between updates.
+namespace {
+
+#define CORE_HIP(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return -2; } } while (0)
+
+// a buffer of at least `need` elements: kept when it is large enough, otherwise replaced (its contents are not carried over)
+template <class T> int space_fit(RtGridSpace &S, T **buf, uint64_t *cap, uint64_t need)
+{
+    if (*buf && *cap >= need) return 0;
+    const uint64_t want = std::max<uint64_t>(S.headroom ? need + need / 8 : need, 1);
+    void *q = nullptr;
+    if (hipMalloc(&q, want * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return -4; }
+    if (*buf) { (void)hipFree(*buf); S.bytes -= *cap * sizeof(T); }
+    *buf = (T *)q; *cap = want;
+    S.bytes += want * sizeof(T);
+    S.allocated = 1;
+    return 0;
+}
+int space_fit_bytes(RtGridSpace &S, void **buf, size_t *have, size_t need)
+{
+    uint64_t cap = *have;
+    char *p = (char *)*buf;
+    const int rc = space_fit(S, &p, &cap, (uint64_t)need);
+    *buf = p; *have = (size_t)cap;
+    return rc;
+}
+
+// the key buffers for `need` keys and the temporary storage of their sort; on failure the space holds no key buffers
+int space_keys(RtGridSpace &S, uint64_t need)
+{
+    if (S.keys && S.keysSorted && S.keyCap >= need) return 0;
+    uint64_t capA = S.keyCap, capB = S.keyCap;
+    int rc = space_fit(S, &S.keys, &capA, need);
+    if (!rc) rc = space_fit(S, &S.keysSorted, &capB, capA);
+    size_t tmpBytes = 0;
+    if (!rc && hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, S.keys, S.keysSorted, (size_t)capA, 0, 56, nullptr) != hipSuccess) rc = -2;
+    if (!rc) rc = space_fit_bytes(S, &S.kSortTmp, &S.kSortBytes, tmpBytes);
+    if (rc) {
+        if (S.keys) { (void)hipFree(S.keys); S.bytes -= capA * 8; S.keys = nullptr; }
+        if (S.keysSorted) { (void)hipFree(S.keysSorted); S.bytes -= capB * 8; S.keysSorted = nullptr; }
+        S.keyCap = 0;
+        return rc;
+    }
+    S.keyCap = capA;
+    return 0;
+}
+
+constexpr size_t CTL_CURSOR = 0, CTL_BOUND = 8, CTL_BIG = 16, CTL_OVERFLOW = 20, CTL_BYTES = 32;
+constexpr size_t MAP_WORDS = GRID_CELLS / 32;
+
+} // namespace
+
+void rt_grid_space_free(RtGridSpace *space)
+{
+    RtGridSpace &S = *space;
+    void *all[] = { S.bm, S.ctl, S.count, S.scanTmp, S.bitmaps, S.passmaps, S.queues, S.vals, S.sorted, S.vSortTmp, S.bigList, S.keys, S.keysSorted, S.kSortTmp };
+    for (void *p : all)
+        if (p) (void)hipFree(p);
+    const uint32_t groups = S.fillGroups;
+    const int headroom = S.headroom;
+    S = RtGridSpace{};
+    S.fillGroups = groups; S.headroom = headroom;
+}
+
+int rt_grid_space_reserve(RtGridSpace *space, uint32_t V, uint32_t T, uint64_t tunedKeyCap)
+{
+    RtGridSpace &S = *space;
+    if (S.fillGroups < 1u || S.fillGroups > RT_FILL_GROUPS) S.fillGroups = RT_FILL_GROUPS;
+    const unsigned long long keyCap = tunedKeyCap ? tunedKeyCap : std::max<unsigned long long>(32ull * T, 1ull << 22);
+    uint64_t one = S.bm ? 4 * (rtbuild::DIV + 1) : 0, ctl = S.ctl ? CTL_BYTES : 0, cells = S.count ? GRID_CELLS : 0;
+    int rc = space_fit(S, &S.bm, &one, (uint64_t)4 * (rtbuild::DIV + 1));
+    if (!rc) rc = space_fit(S, &S.ctl, &ctl, (uint64_t)CTL_BYTES);
+    if (!rc) rc = space_fit(S, &S.count, &cells, (uint64_t)GRID_CELLS);
+    if (!rc && !S.scanTmp) {
+        size_t scanBytes = 0;
+        CORE_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, S.count, S.count, (int)GRID_CELLS, nullptr));
+        rc = space_fit_bytes(S, &S.scanTmp, &S.scanBytes, scanBytes);
+    }
+    if (!rc && (!S.vals || !S.sorted || S.vCap < (uint64_t)3 * V)) { // vCap: floats each of the two holds
+        uint64_t capA = S.vals ? S.vCap : 0, capB = S.sorted ? S.vCap : 0;
+        rc = space_fit(S, &S.vals, &capA, (uint64_t)3 * V);
+        if (!rc) rc = space_fit(S, &S.sorted, &capB, capA);
+        S.vCap = std::min(capA, capB);
+        size_t tmpBytes = 0;
+        if (!rc) CORE_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, S.vals, S.sorted, (size_t)std::max<uint64_t>(S.vCap / 3, 1), 0, 32, nullptr));
+        if (!rc) rc = space_fit_bytes(S, &S.vSortTmp, &S.vSortBytes, tmpBytes);
+    }
+    if (!rc) rc = space_fit(S, &S.bigList, &S.tCap, (uint64_t)T);
+    if (!rc) rc = space_keys(S, keyCap);
+    return rc;
+}
+
+int rt_grid_core_fill(RtGridSpace *space, uint32_t V, uint32_t T, const void *vertexDevice, const void *indexDevice, uint64_t tunedKeyCap,
+                      uint64_t listLimit, hipStream_t stream, uint64_t *pairs, uint64_t *log)
+{
+    RtGridSpace &S = *space;
+    if (const int rc = rt_grid_space_reserve(space, V, T, tunedKeyCap)) return rc;
+    const float4 *dVertex = (const float4 *)vertexDevice;
+    const int4 *dIndex = (const int4 *)indexDevice;
+    const unsigned long long keyCap = tunedKeyCap ? tunedKeyCap : std::max<unsigned long long>(32ull * T, 1ull << 22);
+    log[RT_BUILD_LOG_KEY_CAP_FIRST] = keyCap;
+    unsigned long long *dCursor = (unsigned long long *)(S.ctl + CTL_CURSOR), *dBound = (unsigned long long *)(S.ctl + CTL_BOUND);
+    uint32_t *dBigCount = (uint32_t *)(S.ctl + CTL_BIG), *dOverflow = (uint32_t *)(S.ctl + CTL_OVERFLOW);
+    float *dBm = S.bm;
+    if (S.mapsDirty) {
+        if (S.bitmaps) CORE_HIP(hipMemsetAsync(S.bitmaps, 0, (size_t)S.bitmapCap * 4, stream));
+        if (S.passmaps) CORE_HIP(hipMemsetAsync(S.passmaps, 0, (size_t)S.passmapCap * 4, stream));
+    }
+    S.mapsDirty = 1; // until this build is through
+    CORE_HIP(hipMemsetAsync(dBm, 0, sizeof(float) * 4 * (rtbuild::DIV + 1), stream));
+    CORE_HIP(hipMemsetAsync(S.ctl, 0, CTL_BYTES, stream));
+    CORE_HIP(hipMemsetAsync(S.count, 0, (size_t)GRID_CELLS * 4, stream));
+    if (V) {
+        hipLaunchKernelGGL(grid_axis_values, dim3((V + 255) / 256), dim3(256), 0, stream, V, dVertex, S.vals);
+        for (int w = 0; w < 3; ++w) {
+            size_t tmpBytes = S.vSortBytes;
+            CORE_HIP(hipcub::DeviceRadixSort::SortKeys(S.vSortTmp, tmpBytes, S.vals + (size_t)w * V, S.sorted + (size_t)w * V, (size_t)V, 0, 32, stream));
+        }
+        hipLaunchKernelGGL(grid_planes, dim3(3), dim3(320), 0, stream, V, S.sorted, dBm);
+    }
+    auto look = [&](void *dst, const void *src, size_t bytes) -> hipError_t { // the host's look at a few device words
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(stream);
+    };
+    unsigned long long n = 0;
+    uint32_t overflow = 0;
+    unsigned long long cap = keyCap;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        log[RT_BUILD_LOG_ATTEMPTS] = attempt + 1;
+        if (T) {
+            hipLaunchKernelGGL(grid_fill_small, dim3((T + 255) / 256), dim3(256), 0, stream, T, dVertex, dIndex, dBm, S.keys, dCursor, cap, S.bigList,
+                               dBigCount, dOverflow);
+            // the big triangles' cells are bounded by their overlap boxes: make room for them before they are filled
+            CORE_HIP(hipMemsetAsync(dBound, 0, 8, stream));
+            hipLaunchKernelGGL(grid_big_bound, dim3(64), dim3(256), 0, stream, dVertex, dIndex, dBm, S.bigList, dBigCount, dBound);
+            unsigned long long head[3] = { 0, 0, 0 }; // cursor, bound, big count | overflow
+            CORE_HIP(look(head, S.ctl, 24));
+            const unsigned long long small = head[0], bound = head[1];
+            const uint32_t bigTotal = (uint32_t)head[2];
+            if (small <= cap && small + bound > cap && small + bound <= (1ull << 31)) {
+                if (S.keyCap < small + bound) { // a larger pair of buffers; the small triangles' keys move over
+                    unsigned long long *old = S.keys, *oldSorted = S.keysSorted;
+                    const uint64_t oldCap = S.keyCap;
+                    S.keys = nullptr; S.keysSorted = nullptr; S.keyCap = 0;
+                    int rc = space_keys(S, small + bound);
+                    if (!rc && small && hipMemcpyAsync(S.keys, old, (size_t)small * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess) rc = -2;
+                    if (!rc && hipStreamSynchronize(stream) != hipSuccess) rc = -2;
+                    (void)hipFree(old); (void)hipFree(oldSorted);
+                    S.bytes -= 2 * oldCap * 8;
+                    if (rc) return rc;
+                }
+                cap = small + bound;
+                log[RT_BUILD_LOG_GREW] = 1;
+            }
+            log[RT_BUILD_LOG_GRID_THREAD] = T - bigTotal; log[RT_BUILD_LOG_GRID_GROUP] = bigTotal;
+            log[RT_BUILD_LOG_GRID_BATCHES] = 0;
+            if (bigTotal && !(S.bitmaps && S.passmaps && S.queues)) { // the workgroup fill's bitmaps, test maps and queues
+                int rc = space_fit(S, &S.bitmaps, &S.bitmapCap, (uint64_t)S.fillGroups * MAP_WORDS);
+                if (!rc) rc = space_fit(S, &S.passmaps, &S.passmapCap, (uint64_t)S.fillGroups * MAP_WORDS);
+                if (!rc) { const int keep = S.headroom; S.headroom = 0; rc = space_fit(S, &S.queues, &S.queueCap, (uint64_t)S.fillGroups * RT_FILL_QUEUE); S.headroom = keep; }
+                if (rc) return rc;
+                CORE_HIP(hipMemsetAsync(S.bitmaps, 0, (size_t)S.bitmapCap * 4, stream));
+                CORE_HIP(hipMemsetAsync(S.passmaps, 0, (size_t)S.passmapCap * 4, stream));
+            }
+            for (uint32_t base = 0; base < bigTotal; base += S.fillGroups) { // that many bitmaps: that many big triangles at a time
+                const uint32_t batch = std::min<uint32_t>(S.fillGroups, bigTotal - base);
+                ++log[RT_BUILD_LOG_GRID_BATCHES];
+                hipLaunchKernelGGL(grid_test_big, dim3(128, batch), dim3(256), 0, stream, dVertex, dIndex, dBm, S.bigList, base, S.passmaps);
+                hipLaunchKernelGGL(grid_fill_big, dim3(batch), dim3(256), 0, stream, dVertex, dIndex, dBm, S.keys, dCursor, cap, S.bigList, base,
+                                   S.bitmaps, S.passmaps, S.queues, dOverflow);
+            }
+        }
+        unsigned long long tail[3] = { 0, 0, 0 };
+        CORE_HIP(look(tail, S.ctl, 24));
+        n = tail[0]; overflow = (uint32_t)(tail[2] >> 32);
+        if (overflow != 1u || attempt == 1) break;
+        // More pairs than the key buffer holds after all (very many mid-sized triangles).  The cursor has counted them all, like
+        // the reference's own overflow pass (trianglelist.cpp:696-706): fill again into a buffer of that size.
+        if (n > listLimit) { log[RT_BUILD_LOG_PAIRS] = n; S.mapsDirty = 0; return -3; }
+        cap = n;
+        if (const int rc = space_keys(S, cap)) return rc;
+        CORE_HIP(hipMemsetAsync(S.ctl, 0, CTL_BYTES, stream));
+    }
+    log[RT_BUILD_LOG_KEY_CAP_FINAL] = cap; log[RT_BUILD_LOG_PAIRS] = n;
+    CORE_HIP(hipGetLastError());
+    if (overflow || n > cap) return -7; // a single fill larger than the workgroup queue (RT_FILL_QUEUE = 2^24 cells), or a second overflow
+    S.mapsDirty = 0;
+    if (n > listLimit) return -3;
+    *pairs = n;
+    return 0;
+}
+
+int rt_grid_core_lists(RtGridSpace *space, uint64_t pairs, uint32_t *dStart, uint32_t *dList, hipStream_t stream)
+{
+    RtGridSpace &S = *space;
+    const unsigned long long n = pairs;
+    if (n) {
+        // (64-bit item counts: an int would turn 2^31 .. 2^32 - 1 pairs, which the list limit admits, negative)
+        size_t tmpBytes = S.kSortBytes;
+        CORE_HIP(hipcub::DeviceRadixSort::SortKeys(S.kSortTmp, tmpBytes, S.keys, S.keysSorted, (size_t)n, 0, 56, stream));
+        hipLaunchKernelGGL(grid_count_cells, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, n, S.keysSorted, S.count);
+    }
+    size_t scanBytes = S.scanBytes;
+    CORE_HIP(hipcub::DeviceScan::ExclusiveSum(S.scanTmp, scanBytes, S.count, dStart, (int)GRID_CELLS, stream));
+    hipLaunchKernelGGL(grid_write_list, dim3((uint32_t)((std::max<unsigned long long>(n, 1) + 255) / 256)), dim3(256), 0, stream, n, S.keysSorted, dList, dStart);
+    CORE_HIP(hipGetLastError());
+    return 0;
+}
+
+#undef CORE_HIP
+
 extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uint triangleCount, const cl_float3 *vertex, const cl_int3 *triIndex,
                                          cl_float3 outBoxMin[257], cl_uint **outStart, cl_uint **outList, uint64_t *outListSize, double *deviceMs)
 {
@@ -562,123 +776,31 @@ extern "C" int rtHipBuildSceneGridDevice(int device, cl_uint vertexCount, cl_uin
     for (uint32_t t = 0; t < T; ++t)
         for (int k = 0; k < 3; ++k)
             if ((uint32_t)triIndex[t].s[k] >= V) return -6;
+    // upload, core, download
     Buffers buf;
     float4 *dVertex = nullptr; int4 *dIndex = nullptr;
-    float *dVals = nullptr, *dSorted = nullptr, *dBm = nullptr;
-    unsigned long long *dKeys = nullptr, *dKeysSorted = nullptr, *dCursor = nullptr;
-    uint32_t *dBigList = nullptr, *dBigCount = nullptr, *dOverflow = nullptr, *dBitmaps = nullptr, *dQueues = nullptr, *dStart = nullptr, *dCount = nullptr;
-    const unsigned long long keyCap = tunedKeyCap ? tunedKeyCap : std::max<unsigned long long>(32ull * T, 1ull << 22);
-    uint64_t *log = t_buildLog;
-    log[RT_BUILD_LOG_KEY_CAP_FIRST] = keyCap;
-    BUILD_OK(buf.alloc(&dVertex, V)); BUILD_OK(buf.alloc(&dIndex, T));
-    BUILD_OK(buf.alloc(&dVals, (size_t)3 * V)); BUILD_OK(buf.alloc(&dSorted, (size_t)3 * V)); BUILD_OK(buf.alloc(&dBm, 4 * (rtbuild::DIV + 1)));
-    BUILD_OK(buf.alloc(&dKeys, keyCap)); BUILD_OK(buf.alloc(&dKeysSorted, keyCap)); BUILD_OK(buf.alloc(&dCursor, 1));
+    uint32_t *dStart = nullptr, *dList = nullptr;
+    BUILD_OK(buf.alloc(&dVertex, V)); BUILD_OK(buf.alloc(&dIndex, T)); BUILD_OK(buf.alloc(&dStart, (size_t)GRID_CELLS + 1));
     BUILD_OK(hipMemcpy(dVertex, vertex, (size_t)V * 16, hipMemcpyHostToDevice));
     BUILD_OK(hipMemcpy(dIndex, triIndex, (size_t)T * 16, hipMemcpyHostToDevice));
-    Buffers buf2; // (Buffers holds ten pointers)
-    BUILD_OK(buf2.alloc(&dBigList, T)); BUILD_OK(buf2.alloc(&dBigCount, 1)); BUILD_OK(buf2.alloc(&dOverflow, 1));
-    BUILD_OK(buf2.alloc(&dBitmaps, (size_t)RT_FILL_GROUPS * (GRID_CELLS / 32))); BUILD_OK(buf2.alloc(&dQueues, (size_t)RT_FILL_GROUPS * RT_FILL_QUEUE));
-    BUILD_OK(buf2.alloc(&dStart, (size_t)GRID_CELLS + 1)); BUILD_OK(buf2.alloc(&dCount, (size_t)GRID_CELLS));
-    BUILD_OK(hipMemset(dBitmaps, 0, (size_t)RT_FILL_GROUPS * (GRID_CELLS / 32) * 4));
-    hipEvent_t e0, e1;
-    BUILD_OK(hipEventCreate(&e0)); BUILD_OK(hipEventCreate(&e1));
-    BUILD_OK(hipEventRecord(e0, nullptr));
-    BUILD_OK(hipMemsetAsync(dBm, 0, sizeof(float) * 4 * (rtbuild::DIV + 1), nullptr));
-    BUILD_OK(hipMemsetAsync(dCursor, 0, 8, nullptr));
-    BUILD_OK(hipMemsetAsync(dBigCount, 0, 4, nullptr));
-    BUILD_OK(hipMemsetAsync(dOverflow, 0, 4, nullptr));
-    BUILD_OK(hipMemsetAsync(dCount, 0, (size_t)GRID_CELLS * 4, nullptr));
-    Buffers buf3;
-    if (V) {
-        hipLaunchKernelGGL(grid_axis_values, dim3((V + 255) / 256), dim3(256), 0, nullptr, V, dVertex, dVals);
-        void *tmp = nullptr; size_t tmpBytes = 0;
-        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, dVals, dSorted, (size_t)V, 0, 32, nullptr));
-        BUILD_OK(buf3.alloc((char **)&tmp, tmpBytes));
-        for (int w = 0; w < 3; ++w)
-            BUILD_OK(hipcub::DeviceRadixSort::SortKeys(tmp, tmpBytes, dVals + (size_t)w * V, dSorted + (size_t)w * V, (size_t)V, 0, 32, nullptr));
-        hipLaunchKernelGGL(grid_planes, dim3(3), dim3(320), 0, nullptr, V, dSorted, dBm);
-    }
-    unsigned long long n = 0;
-    uint32_t overflow = 0;
-    Buffers bufRetry;
-    unsigned long long cap = keyCap;
-    uint32_t *dPassmaps = nullptr;
-    unsigned long long *dBound = nullptr;
-    BUILD_OK(buf3.alloc(&dPassmaps, (size_t)RT_FILL_GROUPS * (GRID_CELLS / 32))); BUILD_OK(buf3.alloc(&dBound, 1));
-    BUILD_OK(hipMemsetAsync(dPassmaps, 0, (size_t)RT_FILL_GROUPS * (GRID_CELLS / 32) * 4, nullptr));
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        log[RT_BUILD_LOG_ATTEMPTS] = attempt + 1;
-        if (T) {
-            hipLaunchKernelGGL(grid_fill_small, dim3((T + 255) / 256), dim3(256), 0, nullptr, T, dVertex, dIndex, dBm, dKeys, dCursor, cap, dBigList,
-                               dBigCount, dOverflow);
-            // the big triangles' cells are bounded by their overlap boxes: make room for them before they are filled
-            BUILD_OK(hipMemsetAsync(dBound, 0, 8, nullptr));
-            hipLaunchKernelGGL(grid_big_bound, dim3(64), dim3(256), 0, nullptr, dVertex, dIndex, dBm, dBigList, dBigCount, dBound);
-            unsigned long long small = 0, bound = 0;
-            BUILD_OK(hipMemcpy(&small, dCursor, 8, hipMemcpyDeviceToHost));
-            BUILD_OK(hipMemcpy(&bound, dBound, 8, hipMemcpyDeviceToHost));
-            if (small <= cap && small + bound > cap && small + bound <= (1ull << 31)) {
-                unsigned long long *bigger = nullptr, *biggerSorted = nullptr;
-                BUILD_OK(bufRetry.alloc(&bigger, (size_t)(small + bound))); BUILD_OK(bufRetry.alloc(&biggerSorted, (size_t)(small + bound)));
-                if (small) BUILD_OK(hipMemcpy(bigger, dKeys, (size_t)small * 8, hipMemcpyDeviceToDevice));
-                dKeys = bigger; dKeysSorted = biggerSorted; cap = small + bound;
-                log[RT_BUILD_LOG_GREW] = 1;
-            }
-            uint32_t bigTotal = 0;
-            BUILD_OK(hipMemcpy(&bigTotal, dBigCount, 4, hipMemcpyDeviceToHost));
-            log[RT_BUILD_LOG_GRID_THREAD] = T - bigTotal; log[RT_BUILD_LOG_GRID_GROUP] = bigTotal;
-            log[RT_BUILD_LOG_GRID_BATCHES] = 0;
-            for (uint32_t base = 0; base < bigTotal; base += RT_FILL_GROUPS) { // RT_FILL_GROUPS bitmaps: that many big triangles at a time
-                const uint32_t batch = std::min<uint32_t>(RT_FILL_GROUPS, bigTotal - base);
-                ++log[RT_BUILD_LOG_GRID_BATCHES];
-                hipLaunchKernelGGL(grid_test_big, dim3(128, batch), dim3(256), 0, nullptr, dVertex, dIndex, dBm, dBigList, base, dPassmaps);
-                hipLaunchKernelGGL(grid_fill_big, dim3(batch), dim3(256), 0, nullptr, dVertex, dIndex, dBm, dKeys, dCursor, cap, dBigList, base,
-                                   dBitmaps, dPassmaps, dQueues, dOverflow);
-            }
-        }
-        BUILD_OK(hipMemcpy(&n, dCursor, 8, hipMemcpyDeviceToHost));
-        BUILD_OK(hipMemcpy(&overflow, dOverflow, 4, hipMemcpyDeviceToHost));
-        if (overflow != 1u || attempt == 1) break;
-        // More pairs than the key buffer holds after all (very many mid-sized triangles).  The cursor has counted them all, like
-        // the reference's own overflow pass (trianglelist.cpp:696-706): fill again into a buffer of exactly that size.
-        if (n > listLimit) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return -3; }
-        cap = n;
-        BUILD_OK(bufRetry.alloc(&dKeys, (size_t)cap)); BUILD_OK(bufRetry.alloc(&dKeysSorted, (size_t)cap));
-        BUILD_OK(hipMemsetAsync(dCursor, 0, 8, nullptr));
-        BUILD_OK(hipMemsetAsync(dBigCount, 0, 4, nullptr));
-        BUILD_OK(hipMemsetAsync(dOverflow, 0, 4, nullptr));
-    }
-    log[RT_BUILD_LOG_KEY_CAP_FINAL] = cap; log[RT_BUILD_LOG_PAIRS] = n;
-    if (overflow || n > cap) return -7; // a single fill larger than the workgroup queue (RT_FILL_QUEUE = 2^24 cells), or a second overflow
-    if (n > listLimit) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return -3; }
-    uint32_t *dList = nullptr;
-    BUILD_OK(buf3.alloc(&dList, (size_t)n));
-    if (n) {
-        void *tmp = nullptr; size_t tmpBytes = 0;
-        // (64-bit item counts: an int would turn 2^31 .. 2^32 - 1 pairs, which the list limit admits, negative)
-        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, dKeys, dKeysSorted, (size_t)n, 0, 56, nullptr));
-        BUILD_OK(buf3.alloc((char **)&tmp, tmpBytes));
-        BUILD_OK(hipcub::DeviceRadixSort::SortKeys(tmp, tmpBytes, dKeys, dKeysSorted, (size_t)n, 0, 56, nullptr));
-        hipLaunchKernelGGL(grid_count_cells, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr, n, dKeysSorted, dCount);
-    }
-    {
-        void *tmp = nullptr; size_t tmpBytes = 0;
-        BUILD_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, dCount, dStart, (int)GRID_CELLS, nullptr));
-        BUILD_OK(buf3.alloc((char **)&tmp, tmpBytes));
-        BUILD_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmpBytes, dCount, dStart, (int)GRID_CELLS, nullptr));
-    }
-    hipLaunchKernelGGL(grid_write_list, dim3((uint32_t)((std::max<unsigned long long>(n, 1) + 255) / 256)), dim3(256), 0, nullptr, n, dKeysSorted, dList, dStart);
-    BUILD_OK(hipGetLastError());
-    BUILD_OK(hipEventRecord(e1, nullptr));
-    BUILD_OK(hipEventSynchronize(e1));
+    struct Space : RtGridSpace { Space() : RtGridSpace{} { fillGroups = RT_FILL_GROUPS; } ~Space() { rt_grid_space_free(this); } } space;
+    struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
+    BUILD_OK(hipEventCreate(&ev.a)); BUILD_OK(hipEventCreate(&ev.b));
+    if (const int rc = rt_grid_space_reserve(&space, V, T, tunedKeyCap)) return rc == -2 ? -4 : rc;
+    BUILD_OK(hipEventRecord(ev.a, nullptr));
+    uint64_t n = 0;
+    if (const int rc = rt_grid_core_fill(&space, V, T, dVertex, dIndex, tunedKeyCap, listLimit, nullptr, &n, t_buildLog)) return rc == -2 ? -4 : rc;
+    BUILD_OK(buf.alloc(&dList, (size_t)n));
+    if (rt_grid_core_lists(&space, n, dStart, dList, nullptr) != 0) return -4;
+    BUILD_OK(hipEventRecord(ev.b, nullptr));
+    BUILD_OK(hipEventSynchronize(ev.b));
     float ms = 0.f;
-    BUILD_OK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    BUILD_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
     if (deviceMs) *deviceMs = ms;
 
     cl_uint *start = (cl_uint *)std::malloc(((size_t)GRID_CELLS + 1) * 4), *list = (cl_uint *)std::malloc((size_t)(n ? n : 1) * 4);
     if (!start || !list) { std::free(start); std::free(list); return -2; }
-    if (hipMemcpy(outBoxMin, dBm, sizeof(float) * 4 * (rtbuild::DIV + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+    if (hipMemcpy(outBoxMin, space.bm, sizeof(float) * 4 * (rtbuild::DIV + 1), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(start, dStart, ((size_t)GRID_CELLS + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         (n && hipMemcpy(list, dList, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
         std::free(start); std::free(list);

@@ -90,6 +90,10 @@ class Camera(C.Structure):  # rtHipCamera
                 ("pixelSizeInv", C.c_float)]
 
 
+class GeometryUpdate(C.Structure):  # rtHipGeometryUpdate
+    _fields_ = [("vertexCount", C.c_uint32), ("vertex", C.c_void_p), ("triIndex", C.c_void_p), ("triNormal", C.c_void_p), ("arraysOnDevice", C.c_int32)]
+
+
 class Stats(C.Structure):  # rtHipStats
     _fields_ = [(n, C.c_uint64) for n in ("primarySamples", "primaryCandidates", "gridRays", "gridCells", "gridCandidates", "shadedHits", "texelFetches")]
 
@@ -104,7 +108,7 @@ DROPIN_SYMBOLS = [
     "dot", "cross", "normalize", "vector", "bindf", "GetPointToLineSqLen", "RayIntersectsTriangle", "GetBoxAddress",
 ]
 RESIDENT_SYMBOLS = [
-    "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipSceneGetCamera", "rtHipSceneSetCamera", "rtHipRenderTiles", "rtHipFrameFinish",
+    "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipSceneGetCamera", "rtHipSceneSetCamera", "rtHipSceneSetGeometry", "rtHipRenderTiles", "rtHipFrameFinish",
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
@@ -116,6 +120,7 @@ RESIDENT_SYMBOLS = [
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat", "rtHipTestSceneView", "rtHipTestSceneCameraList", "rtHipTestScenePointers", "rtHipTestSceneCameraLog", "rtHipTestSceneCameraTimes",
+    "rtHipTestSceneGeometryLog", "rtHipTestSceneGeometryTimes",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm", "rtHipWritePfmRgb",
     "rtHipObjRead", "rtHipObjFree", "rtHipImageRead", "rtHipProjectUv",
 ]
@@ -180,6 +185,9 @@ def lib() -> C.CDLL:
     L.rtHipTestScenePointers.argtypes = [vp, C.POINTER(vp * 6)]
     L.rtHipTestSceneCameraLog.argtypes = [vp, C.POINTER(u64 * 3)]
     L.rtHipTestSceneCameraTimes.argtypes = [vp, C.POINTER(C.c_double * 2)]
+    L.rtHipSceneSetGeometry.argtypes = [vp, C.POINTER(GeometryUpdate)]
+    L.rtHipTestSceneGeometryLog.argtypes = [vp, C.POINTER(u64 * 6), u32]
+    L.rtHipTestSceneGeometryTimes.argtypes = [vp, C.POINTER(C.c_double * 4)]
     L.rtHipRenderTiles.argtypes = [vp, vp]
     L.rtHipFrameFinish.argtypes = [vp, C.POINTER(C.c_int)]
     L.rtHipRenderTilesCounted.argtypes = [vp, C.POINTER(Stats)]
@@ -623,6 +631,89 @@ def orbit_path(path: str, index: int) -> str:
     return f"{root}_{index:03d}{ext}"
 
 
+def spin_vertices(points, centre, index: int, count: int) -> np.ndarray:
+    """`points` ([n, 3] or [n, 4] float32 positions) turned by index * 360 / count degrees about the vertical axis through `centre`, the
+    turn orbit_positions gives the eye: x and z in fp64 and rounded to fp32, heights (and lane 3) copied.  Pose 0 is the input, bit for bit."""
+    src = np.asarray(points, np.float32)
+    out = src.copy()
+    if index % count == 0:
+        return out
+    c = np.asarray(centre, np.float64)
+    a = 2.0 * np.pi * index / count
+    dx, dz = src[:, 0].astype(np.float64) - c[0], src[:, 2].astype(np.float64) - c[2]
+    out[:, 0] = c[0] + dx * np.cos(a) + dz * np.sin(a)
+    out[:, 2] = c[2] - dx * np.sin(a) + dz * np.cos(a)
+    return out
+
+
+def spin_directions(normals, index: int, count: int) -> np.ndarray:
+    """Direction vectors (corner normals) under the same turn: spin_vertices about the origin."""
+    return spin_vertices(normals, (0.0, 0.0, 0.0), index, count)
+
+
+def _padded_rows(name: str, a, dtype, rows: Optional[int] = None):
+    """A [n, 3] or [n, 4] array (numpy, or a torch tensor on a GPU) as contiguous [n, 4] rows of `dtype`, lane 3 zero where it is added:
+    the library's 16-byte cl_float3 / cl_int3.  Returns (array, on_device)."""
+    if hasattr(a, "data_ptr"):
+        import torch
+
+        want = torch.float32 if dtype == np.float32 else torch.int32
+        if a.dtype != want:
+            raise TypeError(f"{name}: dtype {a.dtype}, expected {want}")
+        if a.dim() != 2 or a.shape[1] not in (3, 4) or (rows is not None and a.shape[0] != rows):
+            raise ValueError(f"{name}: shape {tuple(a.shape)}, expected [{rows if rows is not None else 'n'}, 3 or 4]")
+        if not a.is_cuda:
+            raise ValueError(f"{name}: a torch tensor must live on the scene's GPU (pass numpy arrays for host memory)")
+        if a.shape[1] == 3:
+            a = torch.nn.functional.pad(a, (0, 1))
+        return a.contiguous(), True
+    a = np.asarray(a)
+    if a.dtype != dtype:
+        raise TypeError(f"{name}: dtype {a.dtype}, expected {np.dtype(dtype)}")
+    if a.ndim != 2 or a.shape[1] not in (3, 4) or (rows is not None and a.shape[0] != rows):
+        raise ValueError(f"{name}: shape {a.shape}, expected [{rows if rows is not None else 'n'}, 3 or 4]")
+    if a.shape[1] == 3:
+        out = np.zeros((a.shape[0], 4), dtype)
+        out[:, :3] = a
+        return out, False
+    return np.ascontiguousarray(a), False
+
+
+class _ResidentView:
+    """Mixed into the Scene class of ResidentScene.scene after a geometry update (see ResidentScene._describe_geometry)."""
+
+
+def _resident_view_class(base):
+    def array(name):
+        def get(self):
+            v = self.__dict__.get(name)
+            if hasattr(v, "data_ptr"):  # handed over as a tensor: downloaded on first read
+                v = self.__dict__[name] = v.cpu().numpy()
+            return v
+
+        def put(self, value):
+            self.__dict__[name] = value
+        return property(get, put)
+
+    def built(name, kind):
+        def get(self):
+            stale = self.__dict__.get("_stale", set())
+            if kind in stale:
+                stale.discard(kind)  # (first: the builders read and write these attributes themselves)
+                (build_scene_grid if kind == "grid" else build_camera_list)(self)
+            return self.__dict__.get(name)
+
+        def put(self, value):
+            self.__dict__[name] = value
+        return property(get, put)
+    members = {n: array(n) for n in ("vertex", "tri_index", "tri_normal")}
+    members.update({n: built(n, "grid") for n in ("box_min", "grid_start", "grid_list")})
+    members.update({n: built(n, "camera") for n in ("cam_start", "cam_end", "cam_list")})
+    members["triangle_count"] = property(lambda self: int(self.__dict__["tri_index"].shape[0]))  # (the counts do not download anything)
+    members["vertex_count"] = property(lambda self: int(self.__dict__["vertex"].shape[0]))
+    return type("Resident" + base.__name__, (base, _ResidentView), members)
+
+
 class ResidentScene:
     """A scene resident in one GPU's HBM (rtHipScene)."""
 
@@ -676,6 +767,81 @@ class ResidentScene:
         return dict(eye=np.array(cam.eye, np.float32), eye_to_top_left=np.array(cam.eyeToTopLeft, np.float32),
                     left_to_right=np.array(cam.leftToRight, np.float32), top_to_bottom=np.array(cam.topToBottom, np.float32),
                     pixel_size_inv=float(cam.pixelSizeInv))
+
+    def try_set_vertices(self, vertex, tri_index=None, tri_normal=None) -> int:
+        """rtHipSceneSetGeometry's return code (0, or a negative code with last_error() set).  vertex [V, 3] or [V, 4] float32, tri_index
+        [T, 3] or [T, 4] int32 (None: the index array the scene retained from its last update), tri_normal [3T, 3] or [3T, 4] float32
+        (None: the normals stay): numpy arrays, or torch tensors on the scene's GPU (all of one kind), which are handed over as device
+        pointers once torch's current stream has been synchronised; nothing of them comes to the host.  On success self.scene is replaced by a
+        copy that describes what is resident (_describe_geometry says how, lazily); on failure nothing changes."""
+        T = self.scene.triangle_count
+        v, dev = _padded_rows("vertex", vertex, np.float32)
+        arrays = [v]
+        idx = nrm = None
+        if tri_index is not None:
+            idx, d = _padded_rows("tri_index", tri_index, np.int32, T)
+            arrays.append(idx)
+            if d != dev:
+                raise ValueError("tri_index: numpy arrays and torch tensors cannot be mixed in one update")
+        if tri_normal is not None:
+            nrm, d = _padded_rows("tri_normal", tri_normal, np.float32, 3 * T)
+            arrays.append(nrm)
+            if d != dev:
+                raise ValueError("tri_normal: numpy arrays and torch tensors cannot be mixed in one update")
+        if dev:
+            import torch
+
+            for a in arrays:
+                if a.device.index != self.device:
+                    raise ValueError(f"a tensor lives on {a.device}, the scene on GPU {self.device}")
+            torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()  # the call has no stream argument
+        rc = self._set_geometry(v, idx, nrm, dev)
+        if rc == 0:
+            self._describe_geometry(v, idx, nrm, dev)
+        return rc
+
+    def _set_geometry(self, vertex, tri_index, tri_normal, on_device: bool) -> int:
+        up = GeometryUpdate(int(vertex.shape[0]), _ptr(vertex), _ptr(tri_index), _ptr(tri_normal), 1 if on_device else 0)
+        return int(lib().rtHipSceneSetGeometry(self.handle, C.byref(up)))
+
+    def _describe_geometry(self, vertex, tri_index, tri_normal, on_device: bool) -> None:
+        """self.scene becomes a copy that describes what is resident, without moving anything: arrays that were handed over as tensors stay
+        on the GPU and come to the host when (and if) the copy's vertex / tri_index / tri_normal is first read; its camera is the one in
+        effect; box_min / grid_* / cam_* are rebuilt by the host builders -- whose results the resident arrays equal -- when first read."""
+        import copy
+
+        sc = copy.copy(self.scene)
+        if not isinstance(sc, _ResidentView):
+            sc.__class__ = _resident_view_class(type(sc))
+        for name, a in (("vertex", vertex), ("tri_index", tri_index), ("tri_normal", tri_normal)):
+            if a is not None:
+                setattr(sc, name, a)  # (a tensor is kept as it is: _ResidentView downloads it on first read)
+        if self.handle:
+            cam = self.camera()
+            sc.eye, sc.eye_to_top_left, sc.left_to_right, sc.top_to_bottom = (cam[k] for k in ("eye", "eye_to_top_left", "left_to_right", "top_to_bottom"))
+            sc.pixel_size_inv = cam["pixel_size_inv"]
+        sc.__dict__["_stale"] = {"grid", "camera"}
+        self.scene = sc
+
+    def set_vertices(self, vertex, tri_index=None, tri_normal=None) -> None:
+        """Changes the resident scene's shape (rtHipSceneSetGeometry); raises RuntimeError when the update is refused."""
+        rc = self.try_set_vertices(vertex, tri_index, tri_normal)
+        if rc != 0:
+            raise RuntimeError(f"rtHipSceneSetGeometry failed ({rc}): {last_error()}")
+
+    def geometry_log(self) -> dict:
+        """The last update: triangles filled by one thread, by workgroups, fill attempts, pairs, camera list entries, and whether it
+        allocated anything (rtHipTestSceneGeometryLog)."""
+        out = (C.c_uint64 * 6)()
+        if lib().rtHipTestSceneGeometryLog(self.handle, C.byref(out), 6) != 6:
+            raise RuntimeError("rtHipTestSceneGeometryLog failed: " + last_error())
+        return dict(thread=int(out[0]), group=int(out[1]), attempts=int(out[2]), pairs=int(out[3]), entries=int(out[4]), allocated=int(out[5]))
+
+    def geometry_times_ms(self) -> dict:
+        """Stream time of the last update's stages (rtHipTestSceneGeometryTimes)."""
+        out = (C.c_double * 4)()
+        self._check(lib().rtHipTestSceneGeometryTimes(self.handle, C.byref(out)), "rtHipTestSceneGeometryTimes")
+        return dict(records=out[0], grid=out[1], dense=out[2], camera=out[3])
 
     def camera_list(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """Entries of the device camera list the scene's ranges index (rtHipTestSceneCameraList)."""
