@@ -535,6 +535,53 @@ int  rtHipSceneAmbientOcclusion(rtHipScene *scene, const rtHipAoParams *params, 
  * inside one allocation); a host pointer returns -1. */
 int  rtHipSceneAmbientOcclusionDevice(rtHipScene *scene, const rtHipAoParams *params, void *out, void *stream);
 
+/* MOTION VECTORS: per pixel, where on the PREVIOUS frame's screen the surface point now seen through the pixel's centre was, and what a
+ * consumer needs to reject stale history.  "Previous" is the reference state recorded by rtHipSceneMotionMark; the pass is the flow
+ * input of a temporal filter (history buffers, resampling and blending are the consumer's).  It reads the camera, the triangle
+ * records, the grid and the reference: no frame has to be rendered, it works on either pipeline, and a call changes nothing a later
+ * frame, read-back, pass, denoise, AO, bake or query produces.  The arithmetic is IEEE fp32 + - * / and compares only (no FMA, division
+ * correctly rounded); dot and cross as the AMBIENT OCCLUSION block defines them.  tests/motion_oracle.py restates it in numpy and,
+ * with rt_oracle_grid_trace for the walks, the device output equals it bit for bit (up to the payload of a NaN).
+ *
+ * Reference state: rtHipSceneMotionMark records the camera in effect (five fields) and, per triangle, a, ab = b - a, ac = c - a (per
+ * component) -- exactly the fp32 values the scene's triangle records hold at that moment.  A later rtHipSceneSetCamera or
+ * rtHipSceneSetGeometry does not touch the reference; a new mark replaces it.  The triangle count of a scene never changes, so triangle
+ * i now is triangle i then, also after an update that re-indexes the vertices.  The reference lives in storage of its own (it does not
+ * point into the geometry update's two sets): made by the first mark, 48 bytes per triangle, counted in rtHipSceneBytes from then on and
+ * freed with the scene; a scene that never marks holds none of it.  The mark is one copy kernel on the scene's stream: nothing crosses
+ * the bus.  Instances made by rtHipSceneCreateLike mark for themselves.
+ *
+ * Pixel (x, y) of the scene's own tiles: the primary ray of the AO block at Sp = 1, o = eye, d = (topLeft + lr*((float)x + 0.5f)) +
+ * tb*((float)y + 0.5f) per component, tmin = 0, tmax = +inf, nothing excluded, traced with the renderer's grid walk (the answer
+ * rtHipSceneIntersect gives: tri, t, abL, acL).  Primes denote the reference: E', TL', lr', tb' and a', ab', ac' of triangle tri.
+ *   hit:   P' = (a' + abL*ab') + acL*ac' per component;  w = P' - E' per component.
+ *   miss:  w = d (the background is a point at infinity: a rotation of the camera moves it, a translation does not).
+ *   n = cross(lr', tb');  den = dot(w, n);  px = dot(TL', cross(w, tb')) / den;  py = dot(TL', cross(lr', w)) / den
+ *   (Cramer's rule for TL' + lr'*px + tb'*py parallel to w).
+ * Outputs: motion = (px - ((float)x + 0.5f), py - ((float)y + 0.5f)), from the pixel to the previous position, in pixels;
+ *   t = the hit's t, +inf on a miss;
+ *   prevT = den / dot(TL', n) on a hit, +inf on a miss: the parameter at which the reference camera's ray through (px, py) reaches P'
+ *   (<= 0: the point was behind that camera);
+ *   triangle = tri, 0xffffffff on a miss.
+ * No special cases: den = 0, NaN cameras, degenerate triangles and points behind the eye give what the operations give (infinities,
+ * NaN); every bit pattern has a defined answer up to the payload of a NaN, and nothing indexes out of range.
+ * Validating history: a consumer keeps last frame's t and triangle maps, looks them up at (x + 0.5 + motion.x, y + 0.5 + motion.y) and
+ * compares them with prevT and triangle ("Motion vectors (reprojection)").
+ * Only the pixels of the scene's own tiles are written; every other pixel keeps its value, so instances over a tile deal compose one
+ * image.  Both rtHipSceneMotion calls refuse, with -1, the last-error text set and nothing launched: a NULL scene, every output NULL,
+ * no mark yet ("no motion reference"), an image of 2^32 pixels or more, a bad device pointer. */
+/* Records the scene's camera and triangles as the reference.  Asynchronous, on the scene's stream.  Returns 0, -1 on failure. */
+int  rtHipSceneMotionMark(rtHipScene *scene);
+/* The camera the last mark recorded; -1 before the first mark. */
+int  rtHipSceneMotionReferenceCamera(const rtHipScene *scene, rtHipCamera *out);
+/* HOST row-major W x H arrays: motion 2 x f32 interleaved, t f32, prevT f32, triangle u32; each may be NULL, not all.  Synchronous, on
+ * the scene's stream.  Its staging (20 bytes per pixel of the scene's tiles) is made on first use and counted in rtHipSceneBytes. */
+int  rtHipSceneMotion(rtHipScene *scene, cl_float *motion, cl_float *t, cl_float *prevT, cl_uint *triangle);
+/* DEVICE arrays of the scene's device (4-byte aligned), asynchronous on `stream` (a hipStream_t as void*; NULL = the scene's stream): no
+ * allocation, no synchronisation.  The pointers are checked like rtHipSceneIntersectDevice's; the call is ordered after the mark, and a
+ * later mark after it, by events. */
+int  rtHipSceneMotionDevice(rtHipScene *scene, void *motion, void *t, void *prevT, void *triangle, void *stream);
+
 /* AMBIENT OCCLUSION BAKE: a W x H texture of ambient occlusion over the scene's UV layout.  Each texel centre is mapped to the surface
  * point of the triangle whose UV triangle covers it, and the AO rays of the block above are traced from there with the same walk.  It
  * needs geometry, UVs, corner normals and the grid only: it works on every instance (whatever its tiles, passes or pipeline), ignores

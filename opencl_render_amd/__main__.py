@@ -20,6 +20,9 @@ denoised with rtHipDenoise on device 0.
 scene's camera, to PATH: .pfm (f32) or .pgm (u16 quantised like the denoiser's output, written as 8 bits).  ``--ao-rays``,
 ``--ao-radius``, ``--ao-samples`` and ``--ao-seed`` set its parameters.  For the all-GPUs device it runs on device 0.
 
+``--motion PREFIX`` (with ``--orbit N`` or ``--spin N``) also writes every frame's motion vectors (include/raytrace_hip.h, "MOTION
+VECTORS") against the frame before it to PREFIX_000.npz .. PREFIX_{N-1}.npz.
+
 ``--bake-ao PATH`` also bakes ambient occlusion into a texture over the scene's UVs (include/raytrace_hip.h, "AMBIENT OCCLUSION
 BAKE") and writes it to PATH like ``--ao``: .pfm (f32) or .pgm (8 bits).  ``--bake-size W H`` (default 512 512), ``--bake-rays``,
 ``--bake-radius``, ``--bake-seed`` and ``--bake-dilate`` set its parameters; ``--bake-material M`` or ``--bake-triangles FIRST COUNT``
@@ -66,6 +69,10 @@ def parser():
     sel.add_argument("--bake-material", type=int, metavar="M", help="--bake-ao: bake only the triangles of material M")
     sel.add_argument("--bake-triangles", type=int, nargs=2, metavar=("FIRST", "COUNT"), help="--bake-ao: bake only these triangles")
     ap.add_argument("--bake-atlas", action="store_true", help="--bake-ao: bake over a grid atlas, one cell per triangle, not the scene's UVs")
+    ap.add_argument("--motion", metavar="PREFIX",
+                    help="with --orbit N or --spin N: also write every frame's motion vectors (include/raytrace_hip.h, \"MOTION VECTORS\") to "
+                         "PREFIX_000.npz .. PREFIX_{N-1}.npz with the arrays motion [H, W, 2], t, prev_t and triangle [H, W].  Each frame is "
+                         "measured against the state of the frame before it (frame 0 against itself): the scene is marked after each frame's outputs")
     ap.add_argument("--orbit", type=int, default=1, metavar="N",
                     help="N views of the one resident scene on a circle about the vertical axis through the look-at point, same height and "
                          "distance, each after the first through ResidentScene.look_at (the camera lists are rebuilt on the device, nothing is "
@@ -94,6 +101,8 @@ def parse_args(argv=None):
         ap.error("--spin N needs N >= 1")
     if args.spin > 1 and (args.orbit > 1 or args.bake_ao):
         ap.error("--spin does not go with --orbit or --bake-ao")
+    if args.motion and args.orbit < 2 and args.spin < 2:
+        ap.error("--motion PREFIX needs --orbit N or --spin N with N >= 2 (the frames it is measured between)")
     if args.surface_passes and not args.passes:
         ap.error("--surface-passes needs --passes PREFIX")
     if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
@@ -215,6 +224,17 @@ def write_view(args, paths: dict, planes, passes, denoised, ao) -> None:
         frontend.write_bmp(paths["out"], r, g, b, low_byte_compat=args.low_byte_compat)
 
 
+def write_motion(rs, args, index: int) -> None:
+    """--motion: frame `index`'s motion vectors against the marked state (frame 0: against itself) -> PREFIX_index.npz; then the scene is
+    marked for the next frame."""
+    if not args.motion:
+        return
+    if index == 0:
+        rs.mark_motion()
+    np.savez(f"{args.motion}_{index:03d}.npz", **rs.motion())
+    rs.mark_motion()
+
+
 def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
     """--orbit: args.orbit views of one ResidentScene on HIP device `device`, the camera moved on the device between them.  Returns
     the seconds the moves, frames and read-backs took."""
@@ -238,6 +258,7 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_motion(rs, args, i)
     finally:
         rs.close()
     return spent
@@ -271,6 +292,7 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_motion(rs, args, i)
     finally:
         rs.close()
     return spent

@@ -55,6 +55,8 @@ extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefron
 extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
                                        uint32_t fastQuotient, hipStream_t stream);
 extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream);
+extern "C" hipError_t rtw_launch_motion_mark(const float *triRec, void *ref, uint32_t triangles, hipStream_t stream);
+extern "C" hipError_t rtw_launch_motion(const RtDevScene *scene, const RtMotionArgs *args, hipStream_t stream);
 extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
                                            hipStream_t stream);
 extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
@@ -348,6 +350,20 @@ struct rtHipScene {
     uint64_t bakeBytes = 0, bakeTexels = 0;
     uint32_t bakeChunk = 0;
     hipEvent_t bakeDone = nullptr;
+    // motion vectors (rtHipSceneMotion*): the reference of the last rtHipSceneMotionMark -- its camera, and a, ab, ac of every triangle in
+    // storage of its own (RT_MOTION_REF_ROWS float4 per triangle), made by the first mark -- and the host entry point's staging (tile-major
+    // motion | t | prevT | triangle, 20 bytes per tile pixel), made on its first use.  marked: the end of the last mark on the scene's
+    // stream; done: the end of the last call that read the reference or used the staging, on whatever stream it ran.
+    struct Motion {
+        bool have = false;
+        rtHipCamera cam{};
+        uint32_t triangles = 0;
+        char *ref = nullptr;
+        uint64_t refBytes = 0;
+        char *stage = nullptr;
+        uint64_t stageBytes = 0;
+        hipEvent_t marked = nullptr, done = nullptr;
+    } motion;
     // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
     // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
     // and the sets change places at its end.  listCap: entries each list holds.  log: triangles per thread, per workgroup, entries of the
@@ -1303,6 +1319,10 @@ void rtHipSceneDestroy(rtHipScene *sc)
     if (sc->aoDone) (void)hipEventDestroy(sc->aoDone);
     if (sc->bakeBuf) (void)hipFree(sc->bakeBuf);
     if (sc->bakeDone) (void)hipEventDestroy(sc->bakeDone);
+    if (sc->motion.ref) (void)hipFree(sc->motion.ref);
+    if (sc->motion.stage) (void)hipFree(sc->motion.stage);
+    if (sc->motion.marked) (void)hipEventDestroy(sc->motion.marked);
+    if (sc->motion.done) (void)hipEventDestroy(sc->motion.done);
     if (sc->cam.scratch) (void)hipFree(sc->cam.scratch);
     for (int i = 0; i < 2; ++i) {
         if (sc->cam.start[i]) (void)hipFree(sc->cam.start[i]);
@@ -1952,6 +1972,124 @@ int rtHipSceneAmbientOcclusion(rtHipScene *sc, const rtHipAoParams *p, cl_float 
         const uint32_t tile = sc->tileIds[lp >> 14], q = (uint32_t)(lp & (RT_TILE_PIXELS - 1)), blk = q >> 6, in = q & 63u;
         const uint32_t gx = (tile % sc->tilesX) * RT_TILE + (blk & 15u) * 8u + (in & 7u), gy = (tile / sc->tilesX) * RT_TILE + (blk >> 4) * 8u + (in >> 3);
         if (gx < sc->width && gy < sc->height) out[(size_t)gy * sc->width + gx] = host[lp];
+    }
+    return 0;
+}
+
+// ---- motion vectors (include/raytrace_hip.h, "MOTION VECTORS"; kernels in rt_wavefront.hip, rt_motion_*) ---------------------------
+int rtHipSceneMotionMark(rtHipScene *sc)
+{
+    if (!sc) return fail("rtHipSceneMotionMark: null scene");
+    rtHipScene::Motion &M = sc->motion;
+    HIP_OK(hipSetDevice(sc->device));
+    const uint32_t T = sc->dev.triangleCount;
+    if (!M.ref) {
+        const uint64_t bytes = std::max<uint64_t>((uint64_t)T * RT_MOTION_REF_ROWS * 16, 16);
+        hipEvent_t ev[2] = { nullptr, nullptr };
+        void *buf = nullptr;
+        const hipError_t e = hipMalloc(&buf, bytes);
+        if (e != hipSuccess) return fail("rtHipSceneMotionMark: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        for (hipEvent_t &v : ev) {
+            const hipError_t ee = hipEventCreateWithFlags(&v, hipEventDisableTiming);
+            if (ee != hipSuccess) {
+                (void)hipFree(buf);
+                if (ev[0]) (void)hipEventDestroy(ev[0]);
+                return fail("rtHipSceneMotionMark: hipEventCreate failed: %s", hipGetErrorString(ee));
+            }
+        }
+        M.ref = (char *)buf; M.refBytes = bytes; M.triangles = T; M.marked = ev[0]; M.done = ev[1];
+        sc->bytes += bytes;
+    } else {
+        if (T != M.triangles) return fail("rtHipSceneMotionMark: the scene has %u triangles, the reference was made for %u", T, M.triangles);
+        HIP_OK(hipStreamWaitEvent(sc->stream, M.done, 0)); // calls on other streams that still read the old reference
+    }
+    HIP_OK(rtw_launch_motion_mark(sc->dev.triRec, M.ref, T, sc->stream));
+    HIP_OK(hipEventRecord(M.marked, sc->stream));
+    rtHipSceneGetCamera(sc, &M.cam);
+    M.have = true;
+    return 0;
+}
+
+int rtHipSceneMotionReferenceCamera(const rtHipScene *sc, rtHipCamera *out)
+{
+    if (!sc || !out) return fail("rtHipSceneMotionReferenceCamera: null argument");
+    if (!sc->motion.have) return fail("rtHipSceneMotionReferenceCamera: no motion reference (rtHipSceneMotionMark)");
+    *out = sc->motion.cam;
+    return 0;
+}
+
+static int motion_check(const rtHipScene *sc, const void *motion, const void *t, const void *prevT, const void *triangle)
+{
+    if (!sc) return fail("motion vectors: null scene");
+    if (!motion && !t && !prevT && !triangle) return fail("motion vectors: every output is null");
+    if (!sc->motion.have) return fail("motion vectors: no motion reference (rtHipSceneMotionMark)");
+    if (sc->dev.triangleCount != sc->motion.triangles)
+        return fail("motion vectors: the scene has %u triangles, the reference was made for %u", sc->dev.triangleCount, sc->motion.triangles);
+    if ((uint64_t)sc->width * sc->height >= (1ull << 32)) return fail("motion vectors: %u x %u is 2^32 pixels or more", sc->width, sc->height);
+    return 0;
+}
+
+// Enqueues the pass on `st`, after the mark and after the last call's use of the reference and the staging.
+static int motion_run(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, bool rowMajor, hipStream_t st)
+{
+    rtHipScene::Motion &M = sc->motion;
+    RtMotionArgs A;
+    for (int i = 0; i < 3; ++i) { A.eye[i] = M.cam.eye[i]; A.topLeft[i] = M.cam.eyeToTopLeft[i]; A.lr[i] = M.cam.leftToRight[i]; A.tb[i] = M.cam.topToBottom[i]; }
+    A.ref = (const float4 *)M.ref;
+    A.motion = (float *)motion; A.t = (float *)t; A.prevT = (float *)prevT; A.triangle = (uint32_t *)triangle;
+    A.rowMajor = rowMajor ? 1u : 0u; A.fastQuotient = sc->tune.fastQuotient ? 1u : 0u;
+    if (st != sc->stream) HIP_OK(hipStreamWaitEvent(st, M.marked, 0));
+    if (!rowMajor) HIP_OK(hipStreamWaitEvent(st, M.done, 0)); // (the staging)
+    HIP_OK(rtw_launch_motion(&sc->dev, &A, st));
+    HIP_OK(hipEventRecord(M.done, st));
+    return 0;
+}
+
+int rtHipSceneMotionDevice(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, void *stream)
+{
+    if (motion_check(sc, motion, t, prevT, triangle) != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    const uint64_t pixels = (uint64_t)sc->width * sc->height;
+    if (motion && query_pointer_ok(sc->device, "the scene", motion, pixels * 8, 4, "motion") != 0) return -1;
+    if (t && query_pointer_ok(sc->device, "the scene", t, pixels * 4, 4, "t") != 0) return -1;
+    if (prevT && query_pointer_ok(sc->device, "the scene", prevT, pixels * 4, 4, "prevT") != 0) return -1;
+    if (triangle && query_pointer_ok(sc->device, "the scene", triangle, pixels * 4, 4, "triangle") != 0) return -1;
+    return motion_run(sc, motion, t, prevT, triangle, true, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtHipSceneMotion(rtHipScene *sc, cl_float *motion, cl_float *t, cl_float *prevT, cl_uint *triangle)
+{
+    if (motion_check(sc, motion, t, prevT, triangle) != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    rtHipScene::Motion &M = sc->motion;
+    const size_t n = sc->tileIds.size() * (size_t)RT_TILE_PIXELS;
+    if (!M.stage) {
+        const uint64_t bytes = std::max<uint64_t>((uint64_t)n * 20, 16);
+        void *buf = nullptr;
+        const hipError_t e = hipMalloc(&buf, bytes);
+        if (e != hipSuccess) return fail("motion vectors: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        M.stage = (char *)buf; M.stageBytes = bytes;
+        sc->bytes += bytes;
+    }
+    // tile-major planes in AO order: motion | t | prevT | triangle; the host stores the scene's pixels
+    char *dMotion = M.stage, *dT = M.stage + n * 8, *dPrev = M.stage + n * 12, *dTri = M.stage + n * 16;
+    if (motion_run(sc, motion ? dMotion : nullptr, t ? dT : nullptr, prevT ? dPrev : nullptr, triangle ? dTri : nullptr, false, sc->stream) != 0) return -1;
+    std::vector<uint32_t> host(n * 5);
+    uint32_t *hMotion = host.data(), *hT = hMotion + n * 2, *hPrev = hT + n, *hTri = hPrev + n;
+    if (motion) HIP_OK(hipMemcpyAsync(hMotion, dMotion, n * 8, hipMemcpyDeviceToHost, sc->stream));
+    if (t) HIP_OK(hipMemcpyAsync(hT, dT, n * 4, hipMemcpyDeviceToHost, sc->stream));
+    if (prevT) HIP_OK(hipMemcpyAsync(hPrev, dPrev, n * 4, hipMemcpyDeviceToHost, sc->stream));
+    if (triangle) HIP_OK(hipMemcpyAsync(hTri, dTri, n * 4, hipMemcpyDeviceToHost, sc->stream));
+    HIP_OK(hipStreamSynchronize(sc->stream));
+    for (size_t lp = 0; lp < n; ++lp) {
+        const uint32_t tile = sc->tileIds[lp >> 14], q = (uint32_t)(lp & (RT_TILE_PIXELS - 1)), blk = q >> 6, in = q & 63u;
+        const uint32_t gx = (tile % sc->tilesX) * RT_TILE + (blk & 15u) * 8u + (in & 7u), gy = (tile / sc->tilesX) * RT_TILE + (blk >> 4) * 8u + (in >> 3);
+        if (gx >= sc->width || gy >= sc->height) continue;
+        const size_t at = (size_t)gy * sc->width + gx;
+        if (motion) memcpy(motion + 2 * at, hMotion + 2 * lp, 8);
+        if (t) memcpy(t + at, hT + lp, 4);
+        if (prevT) memcpy(prevT + at, hPrev + lp, 4);
+        if (triangle) triangle[at] = hTri[lp];
     }
     return 0;
 }

@@ -247,4 +247,18 @@ struct RtBakeArgs {
     uint32_t *hits;     // its length, zeroed before the chunk's points launch
 };
 
+// ---- motion vectors (rt_wavefront.hip, rt_motion_*; definition in include/raytrace_hip.h, "MOTION VECTORS") -------------------------
+// The reference record of triangle i is three float4: {a.xyz, ab.x} {ab.yz, ac.xy} {ac.z, 0, 0, 0}, the first 9 floats of its triRec row at
+// the mark (48 B per triangle).  The motion kernel runs one lane per pixel of the scene's tiles in AO order (lp, see RtAoArgs) and stores
+// the wanted outputs (a null array is skipped) at the pixel's row-major index (rowMajor) or at lp (the host entry point's staging).
+#define RT_MOTION_REF_ROWS 3
+struct RtMotionArgs {
+    float eye[3], topLeft[3], lr[3], tb[3]; // the reference camera
+    const float4 *ref;                      // [triangleCount][RT_MOTION_REF_ROWS]
+    float *motion;                          // 2 per pixel
+    float *t, *prevT;
+    uint32_t *triangle;
+    uint32_t rowMajor, fastQuotient;
+};
+
 #endif

@@ -2420,6 +2420,81 @@ extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32
     return hipGetLastError();
 }
 
+// ---- motion vectors (rtHipSceneMotion*; include/raytrace_hip.h, "MOTION VECTORS"; buffers in rt_device.h, RtMotionArgs) -------------------
+// One lane per triangle: the rows of its triRec line that hold a, ab, ac become its reference record (16-byte loads and stores).
+__global__ __launch_bounds__(256) void rt_motion_mark_kernel(const float4 *__restrict__ triRec, float4 *__restrict__ ref, const uint32_t triangles)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= triangles) return;
+    const float4 *src = triRec + 4 * (size_t)i;
+    const float4 r0 = src[0], r1 = src[1], r2 = src[2];
+    float4 *dst = ref + RT_MOTION_REF_ROWS * (size_t)i;
+    dst[0] = r0;
+    dst[1] = r1;
+    dst[2] = make_float4(r2.x, 0.f, 0.f, 0.f); // (the rest of the row is the normal)
+}
+
+// One lane per pixel of the scene's tiles in AO order (a wave is one 8x8 block of the screen): the centre ray, its walk -- query_walk
+// under rt_query_kernel's tame guard, the answer rtHipSceneIntersect gives --, one gather of the hit triangle's reference record, the
+// projection through the reference camera and up to four stores.
+__global__ __launch_bounds__(256) void rt_motion_kernel(const RtDevScene S, const RtMotionArgs A)
+{
+    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
+    __syncthreads();
+    const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
+    if (lp >= S.tileCount * RT_TILE_PIXELS) return;
+    uint32_t gx, gy;
+    ao_pixel(S, lp, gx, gy);
+    if (gx >= S.width || gy >= S.height) return;
+    const float fx = (float)gx + 0.5f, fy = (float)gy + 0.5f;
+    const V3 o = mk(S.eye[0], S.eye[1], S.eye[2]);
+    const V3 d = mk((S.topLeft[0] + S.lr[0] * fx) + S.tb[0] * fy, (S.topLeft[1] + S.lr[1] * fx) + S.tb[1] * fy,
+                    (S.topLeft[2] + S.lr[2] * fx) + S.tb[2] * fy);
+    float t, l1 = 0.f, l2 = 0.f;
+    uint32_t tri;
+    const bool tame = tame_origin(o.x) && tame_origin(o.y) && tame_origin(o.z) && tame_direction(d.x) && tame_direction(d.y) && tame_direction(d.z);
+    if (S.planesTame && A.fastQuotient && __ballot(!tame) == 0ull) tri = query_walk<true>(S, planes, o, d, 0.f, RT_INF, RT_NONE, t, l1, l2);
+    else tri = query_walk<false>(S, planes, o, d, 0.f, RT_INF, RT_NONE, t, l1, l2);
+    const bool hit = tri != RT_NONE;
+    const V3 E = mk(A.eye[0], A.eye[1], A.eye[2]), TL = mk(A.topLeft[0], A.topLeft[1], A.topLeft[2]);
+    const V3 lr = mk(A.lr[0], A.lr[1], A.lr[2]), tb = mk(A.tb[0], A.tb[1], A.tb[2]);
+    V3 w = d; // a miss: the background is a point at infinity
+    if (hit) {
+        const float4 *rec = A.ref + RT_MOTION_REF_ROWS * (size_t)tri;
+        const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+        const V3 P = mk((r0.x + l1 * r0.w) + l2 * r1.z, (r0.y + l1 * r1.x) + l2 * r1.w, (r0.z + l1 * r1.y) + l2 * r2.x);
+        w = sub3(P, E);
+    }
+    const V3 n = cross3(lr, tb);
+    const float den = dot3(w, n);
+    const size_t at = A.rowMajor ? (size_t)gy * S.width + gx : (size_t)lp;
+    if (A.motion) {
+        const float px = dot3(TL, cross3(w, tb)) / den, py = dot3(TL, cross3(lr, w)) / den;
+        A.motion[2 * at] = px - fx; // (two 4-byte stores: the caller's array need not be 8-byte aligned)
+        A.motion[2 * at + 1] = py - fy;
+    }
+    if (A.t) A.t[at] = hit ? t : RT_INF;
+    if (A.prevT) A.prevT[at] = hit ? den / dot3(TL, n) : RT_INF;
+    if (A.triangle) A.triangle[at] = tri;
+}
+
+extern "C" hipError_t rtw_launch_motion_mark(const float *triRec, void *ref, uint32_t triangles, hipStream_t stream)
+{
+    if (triangles == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_motion_mark_kernel, dim3((triangles + 255u) / 256u), dim3(256), 0, stream, reinterpret_cast<const float4 *>(triRec),
+                       reinterpret_cast<float4 *>(ref), triangles);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtw_launch_motion(const RtDevScene *scene, const RtMotionArgs *args, hipStream_t stream)
+{
+    const uint32_t n = scene->tileCount * RT_TILE_PIXELS;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_motion_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
+    return hipGetLastError();
+}
+
 // ---- ambient occlusion bake (rtHipSceneBakeAmbientOcclusion*; include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE"; buffers in rt_device.h,
 // RtBakeArgs) ------------------------------------------------------------------------------------------------------------------------
 // The AO rays are the AO block's (ao_mix, ao_uniform, ao_walk): each gets exactly the answer rtHipSceneIntersect gives it.

@@ -116,6 +116,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSceneIntersect", "rtHipSceneIntersectDevice",
     "rtHipDenoiseDefaults", "rtHipDenoiseScratchBytes", "rtHipDenoiseDevice", "rtHipDenoise", "rtHipSceneDenoise", "rtHipSceneDenoiseTimes",
     "rtHipAoDefaults", "rtHipSceneAmbientOcclusion", "rtHipSceneAmbientOcclusionDevice",
+    "rtHipSceneMotionMark", "rtHipSceneMotionReferenceCamera", "rtHipSceneMotion", "rtHipSceneMotionDevice",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
@@ -233,6 +234,10 @@ def lib() -> C.CDLL:
     L.rtHipAoDefaults.argtypes = [C.POINTER(AoParams)]
     L.rtHipSceneAmbientOcclusion.argtypes = [vp, C.POINTER(AoParams), vp]
     L.rtHipSceneAmbientOcclusionDevice.argtypes = [vp, C.POINTER(AoParams), vp, vp]
+    L.rtHipSceneMotionMark.argtypes = [vp]
+    L.rtHipSceneMotionReferenceCamera.argtypes = [vp, C.POINTER(Camera)]
+    L.rtHipSceneMotion.argtypes = [vp, vp, vp, vp, vp]
+    L.rtHipSceneMotionDevice.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rtHipBakeDefaults.restype = None
     L.rtHipBakeDefaults.argtypes = [C.POINTER(BakeParams)]
     L.rtHipSceneBakeAmbientOcclusion.argtypes = [vp, C.POINTER(BakeParams), vp, vp]
@@ -1064,6 +1069,52 @@ class ResidentScene:
         elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags.c_contiguous):
             raise ValueError(f"ambient_occlusion: out must be a C-contiguous float32 {shape} array")
         self._check(lib().rtHipSceneAmbientOcclusion(self.handle, C.byref(p), _ptr(out)), "rtHipSceneAmbientOcclusion")
+        return out
+
+    def mark_motion(self) -> None:
+        """Records the camera and the triangles now resident as the reference of motion() (rtHipSceneMotionMark): "the previous frame"."""
+        self._check(lib().rtHipSceneMotionMark(self.handle), "rtHipSceneMotionMark")
+
+    def motion_reference_camera(self) -> dict:
+        """The camera the last mark_motion() recorded (rtHipSceneMotionReferenceCamera), in camera()'s form; raises before the first mark."""
+        cam = Camera()
+        self._check(lib().rtHipSceneMotionReferenceCamera(self.handle, C.byref(cam)), "rtHipSceneMotionReferenceCamera")
+        return dict(eye=np.array(cam.eye, np.float32), eye_to_top_left=np.array(cam.eyeToTopLeft, np.float32),
+                    left_to_right=np.array(cam.leftToRight, np.float32), top_to_bottom=np.array(cam.topToBottom, np.float32),
+                    pixel_size_inv=float(cam.pixelSizeInv))
+
+    def motion(self, out: Optional[dict] = None, stream: int = 0) -> dict:
+        """Motion vectors against the marked reference (include/raytrace_hip.h, "MOTION VECTORS"): {"motion": [H, W, 2] f32 (from the
+        pixel to where its surface point was, in pixels), "t": [H, W] f32, "prev_t": [H, W] f32, "triangle": [H, W] u32 (0xffffffff: a
+        miss)} as numpy arrays (rtHipSceneMotion; zeros where this instance's tiles do not reach).  `out`: a dict with any subset of the
+        keys; numpy arrays of those shapes are filled and returned with the missing keys left out, and torch tensors on this scene's
+        device (float32; triangle uint32 or int32, the ids' bits) are filled by rtHipSceneMotionDevice on torch's current stream (or
+        `stream`) and returned as they are."""
+        sc = self.scene
+        shapes = dict(motion=(sc.height, sc.width, 2), t=(sc.height, sc.width), prev_t=(sc.height, sc.width), triangle=(sc.height, sc.width))
+        keys = ("motion", "t", "prev_t", "triangle")
+        if out is None:
+            out = {k: np.zeros(shapes[k], np.uint32 if k == "triangle" else np.float32) for k in keys}
+        unknown = [k for k in out if k not in keys]
+        if unknown or not out:
+            raise ValueError(f"motion: out takes a non-empty subset of {keys} (got {sorted(out)})")
+        if any(hasattr(v, "data_ptr") for v in out.values()):
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            for k, v in out.items():
+                kinds = (torch.uint32, torch.int32) if k == "triangle" else (torch.float32,)
+                if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype not in kinds or tuple(v.shape) != shapes[k] or not v.is_contiguous():
+                    raise ValueError(f"motion: out[{k!r}] must be a contiguous {kinds[0]} {shapes[k]} tensor on {dev}")
+            ptrs = [C.c_void_p(out[k].data_ptr()) if k in out else None for k in keys]
+            self._on_torch_stream(stream, list(out.values()), lambda run: self._check(lib().rtHipSceneMotionDevice(
+                self.handle, *ptrs, C.c_void_p(run)), "rtHipSceneMotionDevice"))
+            return out
+        for k, v in out.items():
+            kind = np.uint32 if k == "triangle" else np.float32
+            if not (isinstance(v, np.ndarray) and v.dtype == kind and v.shape == shapes[k] and v.flags.c_contiguous):
+                raise ValueError(f"motion: out[{k!r}] must be a C-contiguous {np.dtype(kind).name} {shapes[k]} array")
+        self._check(lib().rtHipSceneMotion(self.handle, *[_ptr(out.get(k)) for k in keys]), "rtHipSceneMotion")
         return out
 
     def _on_torch_stream(self, stream, tensors, call):
