@@ -537,7 +537,7 @@ int  rtHipSceneAmbientOcclusionDevice(rtHipScene *scene, const rtHipAoParams *pa
 
 /* MOTION VECTORS: per pixel, where on the PREVIOUS frame's screen the surface point now seen through the pixel's centre was, and what a
  * consumer needs to reject stale history.  "Previous" is the reference state recorded by rtHipSceneMotionMark; the pass is the flow
- * input of a temporal filter (history buffers, resampling and blending are the consumer's).  It reads the camera, the triangle
+ * input of a temporal filter (history buffers, resampling and blending: TEMPORAL ACCUMULATION below, or the consumer's own).  It reads the camera, the triangle
  * records, the grid and the reference: no frame has to be rendered, it works on either pipeline, and a call changes nothing a later
  * frame, read-back, pass, denoise, AO, bake or query produces.  The arithmetic is IEEE fp32 + - * / and compares only (no FMA, division
  * correctly rounded); dot and cross as the AMBIENT OCCLUSION block defines them.  tests/motion_oracle.py restates it in numpy and,
@@ -581,6 +581,84 @@ int  rtHipSceneMotion(rtHipScene *scene, cl_float *motion, cl_float *t, cl_float
  * allocation, no synchronisation.  The pointers are checked like rtHipSceneIntersectDevice's; the call is ordered after the mark, and a
  * later mark after it, by events. */
 int  rtHipSceneMotionDevice(rtHipScene *scene, void *motion, void *t, void *prevT, void *triangle, void *stream);
+
+/* TEMPORAL ACCUMULATION: the consumer of the motion vectors.  The previous call's output (the history) is fetched bilinearly where the
+ * flow says each pixel's surface point was, every tap validated against the triangle id and prevT, and blended with the new frame as a
+ * running mean of at most maxHistory frames; a pixel without valid history starts again from the frame itself.  The arithmetic is IEEE
+ * fp32 + - * /, floorf, fabsf and compares in a fixed order (no FMA, divisions correctly rounded): tests/temporal_oracle.py restates it
+ * in numpy and the device output equals it bit for bit (up to the payload of a NaN).
+ *
+ * All arrays are W x H, row-major; W, H >= 1, W, H <= 16384 (so (float)W and the pixel coordinates are exact) and W*H <= 2^27.
+ * Current frame: colour 3 x f32, motion 2 x f32, prevT f32, triangle u32 -- the last three exactly what rtHipSceneMotion writes.
+ * History (the previous call's outputs and guides): histColour 3 x f32, histCount f32 (the history length; 0 = none), histT f32 (the
+ * previous frame's t map), histTriangle u32.  Outputs: outColour 3 x f32, outCount f32.
+ * Parameters: maxHistory finite in [1, 65536], depthTolerance finite and >= 0; anything else returns -1 before anything is launched.
+ * Per pixel p = (x, y):
+ *   gx = (((float)x + 0.5f) + motion.x) - 0.5f;  gy likewise with y
+ *   ok = prevT > 0 && gx >= -1.0f && gx < (float)W && gy >= -1.0f && gy < (float)H            (a NaN compares false)
+ *   if ok: x0f = floorf(gx), y0f = floorf(gy), ax = gx - x0f, ay = gy - y0f, x0 = (int)x0f, y0 = (int)y0f (converted only after the
+ *     range test: x0 in [-1, W-1]); sw = sr = sg = sb = sn = +0.0f; for j = 0..1 (rows, outer), k = 0..1 (columns, inner):
+ *       q = (x0 + k, y0 + j); a tap outside the image is skipped;
+ *       b = (k ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+ *       accepted iff histCount_q >= 1.0f && histTriangle_q == triangle_p
+ *                    && (histT_q == prevT || fabsf(histT_q - prevT) <= depthTolerance * prevT);
+ *       accepted: sw += b;  sr += b * histColour_q.r (g, b alike);  sn += b * histCount_q
+ *   if ok && sw > 0: hc = (sr/sw, sg/sw, sb/sw), hn = sn/sw;  n = hn + 1.0f;  if (n > maxHistory) n = maxHistory;  a = 1.0f / n;
+ *     outColour = hc + (colour - hc) * a per component (a subtract, a multiply, an add), but colour itself if n == 1.0f;  outCount = n
+ *     (n == 1 happens only with maxHistory = 1, which so returns the frame bit for bit: hc + (colour - hc) rounds twice and need not)
+ *   else: outColour = colour;  outCount = 1.0f
+ * The == arm lets a missed pixel (prevT = +inf, triangle 0xffffffff) accept a missed history pixel (t = +inf): the background accumulates
+ * under a pure rotation and starts again wherever the flow points at geometry.  Every bit pattern of the inputs has a defined answer up to
+ * the payload of a NaN, and no index is formed before its range test.  The outputs must not overlap any input nor each other: a history
+ * tap belongs to a neighbour, so the filter cannot run in place. */
+typedef struct rtHipTemporalParams {
+    cl_float maxHistory;     /* the running mean's longest length, in frames */
+    cl_float depthTolerance; /* relative: |histT - prevT| <= depthTolerance * prevT */
+} rtHipTemporalParams;
+/* maxHistory = 32, depthTolerance = 0.05 ("a few per cent: the stored value belongs to the nearest pixel centre"); defaults of a
+ * parameter, not measurements. */
+void rtHipTemporalDefaults(rtHipTemporalParams *params);
+/* DEVICE arrays of `device`, asynchronous on `stream` (a hipStream_t of `device` as void*; NULL = the null stream): one launch, no
+ * allocation, no synchronisation.  outCount may be NULL.  Every pointer is checked first like rtHipDenoiseDevice's (device memory of
+ * `device`, the whole range inside one allocation, 4-byte aligned); a non-NULL stream must belong to `device`; outColour and outCount must
+ * overlap nothing.  Anything else returns -1 with the last-error text set and launches nothing. */
+int  rtHipTemporalDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                         const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
+                         void *outColour, void *outCount, const rtHipTemporalParams *params, void *stream);
+/* HOST arrays, synchronous; device memory is allocated and freed per call.  outCount may be NULL.  Same results as rtHipTemporalDevice. */
+int  rtHipTemporal(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                   const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                   const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params);
+/* The scene's last frame, accumulated on its device against the history the scene keeps.  The caller's loop is: rtHipSceneSetCamera and
+ * / or rtHipSceneSetGeometry, render, rtHipSceneTemporal.  The call needs a tile set that holds every tile of the image once (as
+ * rtHipSceneDenoise does), synchronises and finishes the frame like rtHipReadback, and then, on the scene's stream: marks the scene if
+ * it has no motion reference yet; runs the motion pass into storage of its own; gathers the colour ((float)u16 / 65535.0f of the beauty
+ * planes, what rtHipReadback gives); accumulates against the history; makes outColour, outCount and this frame's t and triangle maps the
+ * new history; and marks the scene again, so that the reference becomes the state this frame was rendered from.  THE CALL OWNS THE
+ * MARK: a later rtHipSceneMotion of the caller measures against this frame, and a mark of the caller between two calls changes what
+ * the next call reprojects against.
+ * denoise non-NULL (temporal, then spatial): needs RT_HIP_PASS_NORMAL | RT_HIP_PASS_ALBEDO on; the accumulated colour goes through the
+ * DENOISER with the gathered normal and albedo (exactly rtHipSceneDenoise's) before it is output, in the scratch rtHipSceneDenoise uses.
+ * The history keeps the unfiltered accumulation.
+ * Outputs (each may be NULL, host arrays): outRgb W x H x 3 f32, the u16 planes R, G, B quantised as rtHipSceneDenoise's, outCount W x H
+ * f32 (the history length each pixel now has).
+ * Storage, made on first use in one block, counted in rtHipSceneBytes from then on and freed with the scene (a scene that never calls
+ * holds none of it), with n = W*H and every part rounded up to 256 bytes: two history sets of colour 12n, count 4n, t 4n and triangle 4n
+ * (24 B per pixel each); motion 8n and prevT 4n (this frame's t and triangle are written straight into the new history set, so the pass
+ * keeps 12 B per pixel of its own); the gathered colour 12n; and the u16 output planes 3 x 2n.  A call with denoise non-NULL also
+ * needs the scene's denoiser scratch (rtHipSceneDenoise's: 4 images of 12n, 3 planes of 2n, each rounded up to 256 bytes, plus
+ * rtHipDenoiseScratchBytes): if no rtHipSceneDenoise has made it yet, that call makes it, and rtHipSceneBytes grows by it as well.
+ * If a step fails after the accumulation was issued, the history is dropped: the next call starts again, as after a reset.
+ * Refused with -1, the last-error text set and nothing launched: a NULL scene or params, parameters out of range, an image wider or
+ * higher than 16384 or of more than 2^27 pixels, a tile subset, denoise without both surface passes. */
+int  rtHipSceneTemporal(rtHipScene *scene, const rtHipTemporalParams *params, const rtHipDenoiseParams *denoise, cl_float *outRgb,
+                        cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount);
+/* Sets the scene's history to "none": the next rtHipSceneTemporal outputs the frame itself with count 1.  Returns 0, -1 for NULL. */
+int  rtHipSceneTemporalReset(rtHipScene *scene);
+/* Device time in milliseconds of the scene's last rtHipSceneTemporal call, from HIP events on the scene's stream: ms[0] the motion pass,
+ * ms[1] the colour gather (with denoise: the gather of colour, normal and albedo), ms[2] the accumulation, ms[3] the filter (if any) and
+ * the output kernel.  All 0 before the first call.  Returns 0, or -1 for a NULL argument. */
+int  rtHipSceneTemporalTimes(const rtHipScene *scene, cl_float ms[4]);
 
 /* AMBIENT OCCLUSION BAKE: a W x H texture of ambient occlusion over the scene's UV layout.  Each texel centre is mapped to the surface
  * point of the triangle whose UV triangle covers it, and the AO rays of the block above are traced from there with the same walk.  It

@@ -23,6 +23,10 @@ scene's camera, to PATH: .pfm (f32) or .pgm (u16 quantised like the denoiser's o
 ``--motion PREFIX`` (with ``--orbit N`` or ``--spin N``) also writes every frame's motion vectors (include/raytrace_hip.h, "MOTION
 VECTORS") against the frame before it to PREFIX_000.npz .. PREFIX_{N-1}.npz.
 
+``--temporal PATH`` (with ``--orbit N`` or ``--spin N``) also writes every frame accumulated over the frames before it (include/raytrace_hip.h,
+"TEMPORAL ACCUMULATION"; ResidentScene.temporal) to PATH_000 .. PATH_{N-1}: .bmp, .ppm or .pfm.  With ``--denoise`` the denoiser runs on
+the accumulation before it is written.
+
 ``--bake-ao PATH`` also bakes ambient occlusion into a texture over the scene's UVs (include/raytrace_hip.h, "AMBIENT OCCLUSION
 BAKE") and writes it to PATH like ``--ao``: .pfm (f32) or .pgm (8 bits).  ``--bake-size W H`` (default 512 512), ``--bake-rays``,
 ``--bake-radius``, ``--bake-seed`` and ``--bake-dilate`` set its parameters; ``--bake-material M`` or ``--bake-triangles FIRST COUNT``
@@ -73,6 +77,10 @@ def parser():
                     help="with --orbit N or --spin N: also write every frame's motion vectors (include/raytrace_hip.h, \"MOTION VECTORS\") to "
                          "PREFIX_000.npz .. PREFIX_{N-1}.npz with the arrays motion [H, W, 2], t, prev_t and triangle [H, W].  Each frame is "
                          "measured against the state of the frame before it (frame 0 against itself): the scene is marked after each frame's outputs")
+    ap.add_argument("--temporal", metavar="PATH",
+                    help="with --orbit N or --spin N: also write every frame accumulated over the frames before it (ResidentScene.temporal: "
+                         "the history reprojected along the motion vectors, default parameters) to PATH numbered like --out: .bmp, .ppm or "
+                         ".pfm.  With --denoise the denoiser runs on the accumulation before it is written (the history stays unfiltered)")
     ap.add_argument("--orbit", type=int, default=1, metavar="N",
                     help="N views of the one resident scene on a circle about the vertical axis through the look-at point, same height and "
                          "distance, each after the first through ResidentScene.look_at (the camera lists are rebuilt on the device, nothing is "
@@ -103,6 +111,10 @@ def parse_args(argv=None):
         ap.error("--spin does not go with --orbit or --bake-ao")
     if args.motion and args.orbit < 2 and args.spin < 2:
         ap.error("--motion PREFIX needs --orbit N or --spin N with N >= 2 (the frames it is measured between)")
+    if args.temporal and args.orbit < 2 and args.spin < 2:
+        ap.error("--temporal PATH needs --orbit N or --spin N with N >= 2 (the frames it accumulates)")
+    if args.temporal and not args.temporal.lower().endswith((".bmp", ".ppm", ".pfm")):
+        ap.error("--temporal PATH must end in .bmp, .ppm or .pfm")
     if args.surface_passes and not args.passes:
         ap.error("--surface-passes needs --passes PREFIX")
     if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
@@ -226,13 +238,29 @@ def write_view(args, paths: dict, planes, passes, denoised, ao) -> None:
 
 def write_motion(rs, args, index: int) -> None:
     """--motion: frame `index`'s motion vectors against the marked state (frame 0: against itself) -> PREFIX_index.npz; then the scene is
-    marked for the next frame."""
+    marked for the next frame (with --temporal by write_temporal, which follows: ResidentScene.temporal owns the mark)."""
     if not args.motion:
         return
     if index == 0:
         rs.mark_motion()
     np.savez(f"{args.motion}_{index:03d}.npz", **rs.motion())
-    rs.mark_motion()
+    if not args.temporal:
+        rs.mark_motion()
+
+
+def write_temporal(rs, args, index: int) -> None:
+    """--temporal: frame `index` accumulated over the frames before it -> PATH numbered like --out; with --denoise, filtered."""
+    if not args.temporal:
+        return
+    from . import frontend, raytrace
+    res = rs.temporal(denoise={} if args.denoise else None)
+    path = raytrace.orbit_path(args.temporal, index)
+    if path.lower().endswith(".pfm"):
+        frontend.write_pfm_rgb(path, res["colour"])
+    elif path.lower().endswith(".ppm"):
+        frontend.write_ppm(path, *res["planes"])
+    else:
+        frontend.write_bmp(path, *res["planes"], low_byte_compat=args.low_byte_compat)
 
 
 def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
@@ -259,6 +287,7 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
             write_motion(rs, args, i)
+            write_temporal(rs, args, i)
     finally:
         rs.close()
     return spent
@@ -293,6 +322,7 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
             write_motion(rs, args, i)
+            write_temporal(rs, args, i)
     finally:
         rs.close()
     return spent

@@ -57,6 +57,13 @@ extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays
 extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream);
 extern "C" hipError_t rtw_launch_motion_mark(const float *triRec, void *ref, uint32_t triangles, hipStream_t stream);
 extern "C" hipError_t rtw_launch_motion(const RtDevScene *scene, const RtMotionArgs *args, hipStream_t stream);
+extern "C" hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
+                                            const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
+                                            const uint32_t *histTriangle, float *outColour, float *outCount, float maxHistory,
+                                            float depthTolerance, hipStream_t stream);
+extern "C" hipError_t rtt_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount,
+                                        const uint16_t *tileBuf, float *colour, hipStream_t stream);
+extern "C" hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
 extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
                                            hipStream_t stream);
 extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
@@ -364,6 +371,17 @@ struct rtHipScene {
         uint64_t stageBytes = 0;
         hipEvent_t marked = nullptr, done = nullptr;
     } motion;
+    // temporal accumulation (rtHipSceneTemporal), made on its first call in one block: two history sets (colour | count | t | triangle;
+    // `cur` is the one the next call reads), this frame's motion and prevT, the gathered colour and the u16 output planes.  valid: the
+    // history set `cur` holds a frame (false after a reset: the next call clears its counts first).
+    struct Temporal {
+        char *buf = nullptr;
+        uint64_t bytes = 0;
+        int cur = 0;
+        bool valid = false;
+        hipEvent_t ev[5] = {};
+        float ms[4] = {};
+    } temporal;
     // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
     // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
     // and the sets change places at its end.  listCap: entries each list holds.  log: triangles per thread, per workgroup, entries of the
@@ -1323,6 +1341,9 @@ void rtHipSceneDestroy(rtHipScene *sc)
     if (sc->motion.stage) (void)hipFree(sc->motion.stage);
     if (sc->motion.marked) (void)hipEventDestroy(sc->motion.marked);
     if (sc->motion.done) (void)hipEventDestroy(sc->motion.done);
+    if (sc->temporal.buf) (void)hipFree(sc->temporal.buf);
+    for (hipEvent_t e : sc->temporal.ev)
+        if (e) (void)hipEventDestroy(e);
     if (sc->cam.scratch) (void)hipFree(sc->cam.scratch);
     for (int i = 0; i < 2; ++i) {
         if (sc->cam.start[i]) (void)hipFree(sc->cam.start[i]);
@@ -2319,21 +2340,27 @@ int rtHipDenoise(int device, cl_uint width, cl_uint height, const cl_float *colo
     return 0;
 }
 
-int rtHipSceneDenoise(rtHipScene *sc, const rtHipDenoiseParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG, cl_ushort *outB)
+// `who` needs every tile of the image once in the instance's tile set (it works on the whole row-major image).
+static int whole_image_tiles(const rtHipScene *sc, const char *who)
 {
-    if (!sc) return fail("null scene");
-    if (denoise_params_ok(params) != 0 || denoise_size_ok(sc->width, sc->height) != 0) return -1;
-    if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
-        return fail("denoise needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
     const uint32_t tiles = sc->tilesX * ((sc->height + RT_TILE - 1) / RT_TILE);
     std::vector<char> seen(tiles, 0);
     for (cl_uint t : sc->tileIds)
-        if (t >= tiles || seen[t]++) return fail("denoise needs a tile set that holds every tile of the image once (tile %u)", t);
-    if (sc->tileIds.size() != tiles) return fail("denoise needs a tile set that holds every tile of the image (%zu of %u)", sc->tileIds.size(), tiles);
-    HIP_OK(hipSetDevice(sc->device));
-    HIP_OK(hipDeviceSynchronize());
-    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
-    // [colour | normal | albedo | out] W x H x 3 f32, [R | G | B] u16, filter scratch; every part 256-byte aligned
+        if (t >= tiles || seen[t]++) return fail("%s needs a tile set that holds every tile of the image once (tile %u)", who, t);
+    if (sc->tileIds.size() != tiles) return fail("%s needs a tile set that holds every tile of the image (%zu of %u)", who, sc->tileIds.size(), tiles);
+    return 0;
+}
+
+// The scene's denoiser scratch, made on first use: [colour | normal | albedo | out] W x H x 3 f32, [R | G | B] u16, filter scratch; every
+// part 256-byte aligned.
+struct DenoiseBuffer {
+    size_t n;
+    float *colour, *normal, *albedo, *out;
+    uint16_t *planes[3];
+    char *scratch;
+};
+static int denoise_buffer(rtHipScene *sc, DenoiseBuffer &D)
+{
     const uint32_t W = sc->width, H = sc->height;
     const size_t n = (size_t)W * H, img = (n * 12 + 255) & ~(size_t)255, plane = (n * 2 + 255) & ~(size_t)255;
     const uint64_t bytes = 4 * img + 3 * plane + rtHipDenoiseScratchBytes(W, H);
@@ -2344,28 +2371,46 @@ int rtHipSceneDenoise(rtHipScene *sc, const rtHipDenoiseParams *params, cl_float
         sc->denoiseBytes = bytes;
         sc->bytes += bytes;
     }
+    char *b = sc->denoiseBuf;
+    D.n = n;
+    D.colour = (float *)b; D.normal = (float *)(b + img); D.albedo = (float *)(b + 2 * img); D.out = (float *)(b + 3 * img);
+    for (int c = 0; c < 3; ++c) D.planes[c] = (uint16_t *)(b + 4 * img + c * plane);
+    D.scratch = b + 4 * img + 3 * plane;
+    return 0;
+}
+
+int rtHipSceneDenoise(rtHipScene *sc, const rtHipDenoiseParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG, cl_ushort *outB)
+{
+    if (!sc) return fail("null scene");
+    if (denoise_params_ok(params) != 0 || denoise_size_ok(sc->width, sc->height) != 0) return -1;
+    if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
+        return fail("denoise needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
+    if (whole_image_tiles(sc, "denoise") != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    const uint32_t W = sc->width, H = sc->height;
+    DenoiseBuffer D;
+    if (denoise_buffer(sc, D) != 0) return -1;
     for (hipEvent_t &e : sc->denoiseEv)
         if (!e) HIP_OK(hipEventCreate(&e));
-    char *b = sc->denoiseBuf;
-    float *colour = (float *)b, *normal = (float *)(b + img), *albedo = (float *)(b + 2 * img), *out = (float *)(b + 3 * img);
-    uint16_t *planes[3] = { (uint16_t *)(b + 4 * img), (uint16_t *)(b + 4 * img + plane), (uint16_t *)(b + 4 * img + 2 * plane) };
     const bool wantPlanes = outR || outG || outB;
     hipStream_t st = sc->stream;
     hipEvent_t *ev = sc->denoiseEv;
     HIP_OK(hipEventRecord(ev[0], st));
     HIP_OK(rtd_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->surfBuf,
-                             (float)sc->dev.sampleCount, colour, normal, albedo, st));
+                             (float)sc->dev.sampleCount, D.colour, D.normal, D.albedo, st));
     HIP_OK(hipEventRecord(ev[1], st));
-    if (denoise_issue(W, H, colour, normal, albedo, outRgb ? out : nullptr, wantPlanes ? planes[0] : nullptr, wantPlanes ? planes[1] : nullptr,
-                      wantPlanes ? planes[2] : nullptr, b + 4 * img + 3 * plane, params, st, ev[2]) != 0)
+    if (denoise_issue(W, H, D.colour, D.normal, D.albedo, outRgb ? D.out : nullptr, wantPlanes ? D.planes[0] : nullptr,
+                      wantPlanes ? D.planes[1] : nullptr, wantPlanes ? D.planes[2] : nullptr, D.scratch, params, st, ev[2]) != 0)
         return -1;
     HIP_OK(hipEventRecord(ev[3], st));
     HIP_OK(hipStreamSynchronize(st));
     for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(&sc->denoiseMs[i], ev[i], ev[i + 1]));
-    if (outRgb) HIP_OK(hipMemcpy(outRgb, out, n * 12, hipMemcpyDeviceToHost));
+    if (outRgb) HIP_OK(hipMemcpy(outRgb, D.out, D.n * 12, hipMemcpyDeviceToHost));
     cl_ushort *dst[3] = { outR, outG, outB };
     for (int c = 0; c < 3; ++c)
-        if (dst[c]) HIP_OK(hipMemcpy(dst[c], planes[c], n * 2, hipMemcpyDeviceToHost));
+        if (dst[c]) HIP_OK(hipMemcpy(dst[c], D.planes[c], D.n * 2, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2373,6 +2418,195 @@ int rtHipSceneDenoiseTimes(const rtHipScene *sc, cl_float *ms)
 {
     if (!sc || !ms) return fail("null argument");
     for (int i = 0; i < 3; ++i) ms[i] = sc->denoiseMs[i];
+    return 0;
+}
+
+// ---- temporal accumulation (include/raytrace_hip.h, "TEMPORAL ACCUMULATION"; kernels in rt_temporal.hip) ---------------------------
+#define RT_TEMPORAL_MAX_SIDE 16384u
+
+void rtHipTemporalDefaults(rtHipTemporalParams *p)
+{
+    if (!p) return;
+    p->maxHistory = 32.0f;
+    p->depthTolerance = 0.05f;
+}
+
+static int temporal_params_ok(const rtHipTemporalParams *p)
+{
+    if (!p) return fail("temporal: null parameters");
+    if (!(std::isfinite(p->maxHistory) && p->maxHistory >= 1.0f && p->maxHistory <= 65536.0f))
+        return fail("temporal: maxHistory %g is not finite and in 1..65536", (double)p->maxHistory);
+    if (!(std::isfinite(p->depthTolerance) && p->depthTolerance >= 0.f))
+        return fail("temporal: depthTolerance %g is not finite and >= 0", (double)p->depthTolerance);
+    return 0;
+}
+
+static int temporal_size_ok(uint32_t W, uint32_t H)
+{
+    if (W == 0 || H == 0 || W > RT_TEMPORAL_MAX_SIDE || H > RT_TEMPORAL_MAX_SIDE || (uint64_t)W * H > RT_DENOISE_MAX_PIXELS)
+        return fail("temporal: a %u x %u image is not 1..16384 pixels wide and high and 1..2^27 pixels", W, H);
+    return 0;
+}
+
+int rtHipTemporalDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                        const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
+                        void *outColour, void *outCount, const rtHipTemporalParams *params, void *stream)
+{
+    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
+    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !outColour)
+        return fail("temporal: null array");
+    const uint64_t n = (uint64_t)width * height;
+    const struct { const void *p; uint64_t bytes; const char *what; } arr[10] = {
+        { colour, n * 12, "colour" }, { motion, n * 8, "motion" }, { prevT, n * 4, "prevT" }, { triangle, n * 4, "triangle" },
+        { histColour, n * 12, "histColour" }, { histCount, n * 4, "histCount" }, { histT, n * 4, "histT" }, { histTriangle, n * 4, "histTriangle" },
+        { outColour, n * 12, "outColour" }, { outCount, n * 4, "outCount" } };
+    const int count = outCount ? 10 : 9;
+    for (int i = 0; i < count; ++i) // the outputs are written: neither may overlap anything else
+        for (int k = 8; k < count; ++k)
+            if (i != k && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
+                return fail("temporal: %s overlaps %s", arr[k].what, arr[i].what);
+    HIP_OK(hipSetDevice(device));
+    if (stream) { // (the null stream is the current device's, set above)
+        hipDevice_t sd = -1;
+        if (hipStreamGetDevice((hipStream_t)stream, &sd) != hipSuccess) { (void)hipGetLastError(); return fail("temporal: stream %p is not a stream", stream); }
+        if (sd != device) return fail("temporal: stream %p belongs to device %d, the call is for device %d", stream, (int)sd, device);
+    }
+    for (int i = 0; i < count; ++i)
+        if (query_pointer_ok(device, "the call", arr[i].p, arr[i].bytes, 4, arr[i].what) != 0) return -1;
+    HIP_OK(rtt_launch_accumulate(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
+                                 (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle,
+                                 (float *)outColour, (float *)outCount, params->maxHistory, params->depthTolerance, (hipStream_t)stream));
+    return 0;
+}
+
+int rtHipTemporal(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                  const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                  const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params)
+{
+    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
+    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !outColour)
+        return fail("temporal: null array");
+    HIP_OK(hipSetDevice(device));
+    const size_t n = (size_t)width * height;
+    const struct { const void *host; size_t bytes; } in[8] = { { colour, n * 12 }, { motion, n * 8 }, { prevT, n * 4 }, { triangle, n * 4 },
+                                                               { histColour, n * 12 }, { histCount, n * 4 }, { histT, n * 4 }, { histTriangle, n * 4 } };
+    DevScratch mem;
+    char *d[8], *dColour = nullptr, *dCount = nullptr;
+    for (int i = 0; i < 8; ++i) {
+        HIP_OK(mem.get((void **)&d[i], in[i].bytes));
+        HIP_OK(hipMemcpy(d[i], in[i].host, in[i].bytes, hipMemcpyHostToDevice));
+    }
+    HIP_OK(mem.get((void **)&dColour, n * 12));
+    if (outCount) HIP_OK(mem.get((void **)&dCount, n * 4));
+    HIP_OK(rtt_launch_accumulate(width, height, (const float *)d[0], (const float *)d[1], (const float *)d[2], (const uint32_t *)d[3],
+                                 (const float *)d[4], (const float *)d[5], (const float *)d[6], (const uint32_t *)d[7], (float *)dColour,
+                                 (float *)dCount, params->maxHistory, params->depthTolerance, nullptr));
+    HIP_OK(hipMemcpy(outColour, dColour, n * 12, hipMemcpyDeviceToHost));
+    if (outCount) HIP_OK(hipMemcpy(outCount, dCount, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipDeviceSynchronize());
+    return 0;
+}
+
+int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipDenoiseParams *denoise, cl_float *outRgb,
+                       cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount)
+{
+    if (!sc) return fail("temporal: null scene");
+    if (temporal_params_ok(params) != 0 || temporal_size_ok(sc->width, sc->height) != 0) return -1;
+    if (denoise) {
+        if (denoise_params_ok(denoise) != 0) return -1;
+        if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
+            return fail("temporal: denoise needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
+    }
+    if (whole_image_tiles(sc, "temporal accumulation") != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    if (!sc->motion.have && rtHipSceneMotionMark(sc) != 0) return -1;
+    if (sc->dev.triangleCount != sc->motion.triangles)
+        return fail("temporal: the scene has %u triangles, the motion reference was made for %u", sc->dev.triangleCount, sc->motion.triangles);
+    rtHipScene::Temporal &T = sc->temporal;
+    const uint32_t W = sc->width, H = sc->height;
+    const size_t n = (size_t)W * H;
+    const auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t set = part(n * 12) + 3 * part(n * 4); // a history set: colour | count | t | triangle
+    if (!T.buf) {
+        const uint64_t bytes = 2 * set + part(n * 8) + part(n * 4) + part(n * 12) + 3 * part(n * 2);
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) return fail("temporal: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        T.buf = (char *)p; T.bytes = bytes; T.cur = 0; T.valid = false;
+        sc->bytes += bytes;
+    }
+    for (hipEvent_t &e : T.ev)
+        if (!e) HIP_OK(hipEventCreate(&e));
+    struct Set { float *colour, *count, *t; uint32_t *triangle; } hs[2];
+    for (int i = 0; i < 2; ++i) {
+        char *b = T.buf + i * set;
+        hs[i].colour = (float *)b; hs[i].count = (float *)(b + part(n * 12)); hs[i].t = (float *)(b + part(n * 12) + part(n * 4));
+        hs[i].triangle = (uint32_t *)(b + part(n * 12) + 2 * part(n * 4));
+    }
+    char *rest = T.buf + 2 * set;
+    float *motion = (float *)rest, *prevT = (float *)(rest + part(n * 8)), *colour = (float *)(rest + part(n * 8) + part(n * 4));
+    uint16_t *planes[3];
+    for (int c = 0; c < 3; ++c) planes[c] = (uint16_t *)(rest + part(n * 8) + part(n * 4) + part(n * 12) + c * part(n * 2));
+    const Set &hist = hs[T.cur], &next = hs[T.cur ^ 1];
+    DenoiseBuffer D{};
+    if (denoise && denoise_buffer(sc, D) != 0) return -1;
+    hipStream_t st = sc->stream;
+    if (!T.valid) HIP_OK(hipMemsetAsync(hist.count, 0, n * 4, st)); // no history: every tap is refused, whatever the rest of the set holds
+    HIP_OK(hipEventRecord(T.ev[0], st));
+    if (motion_run(sc, motion, next.t, prevT, next.triangle, true, st) != 0) return -1; // this frame's guides are the next call's history
+    HIP_OK(hipEventRecord(T.ev[1], st));
+    if (denoise) {
+        HIP_OK(rtd_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->surfBuf,
+                                 (float)sc->dev.sampleCount, D.colour, D.normal, D.albedo, st));
+        colour = D.colour;
+    } else {
+        HIP_OK(rtt_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, colour, st));
+    }
+    HIP_OK(hipEventRecord(T.ev[2], st));
+    HIP_OK(rtt_launch_accumulate(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle, next.colour,
+                                 next.count, params->maxHistory, params->depthTolerance, st));
+    HIP_OK(hipEventRecord(T.ev[3], st));
+    // From here until the new mark stands, a failure leaves the scene without history: set `next` is half a step ahead of the reference.
+    T.valid = false;
+    const bool wantPlanes = outR || outG || outB;
+    const float *result = next.colour;
+    uint16_t **resultPlanes = planes;
+    if (denoise) { // temporal, then spatial; the history keeps the unfiltered accumulation
+        if (denoise_issue(W, H, next.colour, D.normal, D.albedo, outRgb ? D.out : nullptr, wantPlanes ? D.planes[0] : nullptr,
+                          wantPlanes ? D.planes[1] : nullptr, wantPlanes ? D.planes[2] : nullptr, D.scratch, denoise, st) != 0)
+            return -1;
+        result = D.out;
+        resultPlanes = D.planes;
+    } else if (wantPlanes) {
+        HIP_OK(rtt_launch_quantise((uint32_t)n, next.colour, planes[0], planes[1], planes[2], st));
+    }
+    HIP_OK(hipEventRecord(T.ev[4], st));
+    if (rtHipSceneMotionMark(sc) != 0) return -1; // the reference becomes the state this frame was rendered from
+    HIP_OK(hipStreamSynchronize(st));
+    T.cur ^= 1; // the sets change places only now: history and reference advance together
+    T.valid = true;
+    for (int i = 0; i < 4; ++i) HIP_OK(hipEventElapsedTime(&T.ms[i], T.ev[i], T.ev[i + 1]));
+    if (outRgb) HIP_OK(hipMemcpy(outRgb, result, n * 12, hipMemcpyDeviceToHost));
+    cl_ushort *dst[3] = { outR, outG, outB };
+    for (int c = 0; c < 3; ++c)
+        if (dst[c]) HIP_OK(hipMemcpy(dst[c], resultPlanes[c], n * 2, hipMemcpyDeviceToHost));
+    if (outCount) HIP_OK(hipMemcpy(outCount, next.count, n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rtHipSceneTemporalReset(rtHipScene *sc)
+{
+    if (!sc) return fail("temporal: null scene");
+    sc->temporal.valid = false;
+    return 0;
+}
+
+int rtHipSceneTemporalTimes(const rtHipScene *sc, cl_float *ms)
+{
+    if (!sc || !ms) return fail("null argument");
+    for (int i = 0; i < 4; ++i) ms[i] = sc->temporal.ms[i];
     return 0;
 }
 

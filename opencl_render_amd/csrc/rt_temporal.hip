@@ -1,0 +1,90 @@
+// rt_temporal.hip -- the temporal accumulation of include/raytrace_hip.h ("TEMPORAL ACCUMULATION"): the history of the previous frame is
+// fetched bilinearly where the motion vectors point, tap by tap validated against the triangle id and prevT, and blended with the new
+// frame, in the exact fp32 arithmetic the header fixes (tests/temporal_oracle.py is the same definition in numpy).
+//
+// Kernels (rt_api.cpp issues them on one stream):
+//   rtt_gather_kernel      scene path only: the [slot][R,G,B][128*128] u16 tile buffer -> row-major W x H x 3 f32 colour (u16 / 65535);
+//                          rtd_gather_kernel without the surface sums, for scenes that have no surface passes on
+//   rtt_accumulate_kernel  one lane per pixel, a wave is one 8x8 block of the screen (a workgroup is four of them side by side), so under
+//                          a smooth flow the four taps of neighbouring lanes fall into the same cache lines; no LDS: the flow is arbitrary
+//   rtt_quantise_kernel    scene path only: W x H x 3 f32 -> the quantised u16 planes, as rtd_output_kernel writes them
+// Nothing here may change a bit: no fast math, no reciprocal-multiply, no contraction (the Makefile's exactness flags apply).
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "rt_temporal_pixel.h"
+
+namespace {
+
+__global__ __launch_bounds__(256) void rtt_accumulate_kernel(const RttArgs A)
+{
+    const uint32_t bx = blockIdx.x % A.blocksX, by = blockIdx.x / A.blocksX;
+    const uint32_t wave = threadIdx.x >> 6, in = threadIdx.x & 63u;
+    const uint32_t x = bx * 32u + wave * 8u + (in & 7u), y = by * 8u + (in >> 3);
+    if (x >= A.W || y >= A.H) return;
+    rtt_pixel(A, x, y);
+}
+
+// One thread per pixel slot of the instance's tiles (tile-major, like tileBuf); slots past the image's edge write nothing.  tileIds were
+// checked against the tile count when the scene was built.
+__global__ __launch_bounds__(256) void rtt_gather_kernel(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *__restrict__ tileIds,
+                                                         const uint16_t *__restrict__ tileBuf, float *__restrict__ colour)
+{
+    const uint32_t slot = blockIdx.x / 64u, l = (blockIdx.x % 64u) * 256u + threadIdx.x;
+    const uint32_t t = tileIds[slot];
+    const uint32_t gx = (t % tilesX) * 128u + (l % 128u), gy = (t / tilesX) * 128u + (l / 128u);
+    if (gx >= W || gy >= H) return;
+    const size_t o = ((size_t)gy * W + gx) * 3;
+    const uint16_t *tb = tileBuf + (size_t)slot * 3 * 16384u + l;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) colour[o + c] = (float)tb[c * 16384u] / 65535.0f;
+}
+
+__global__ __launch_bounds__(256) void rtt_quantise_kernel(uint32_t n, const float *__restrict__ colour, uint16_t *__restrict__ outR,
+                                                           uint16_t *__restrict__ outG, uint16_t *__restrict__ outB)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const size_t b = (size_t)i * 3;
+    const float s[3] = { colour[b] * 65535.0f, colour[b + 1] * 65535.0f, colour[b + 2] * 65535.0f };
+    uint16_t u[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        u[ch] = !(s[ch] > 0.f) ? (uint16_t)0 : (s[ch] >= 65534.5f ? (uint16_t)65535 : (uint16_t)(s[ch] + 0.5f));
+    outR[i] = u[0];
+    outG[i] = u[1];
+    outB[i] = u[2];
+}
+
+} // namespace
+
+// The arrays were checked by the caller (rt_api.cpp): W x H each, W, H in 1..16384, W*H <= 2^27, the outputs overlap nothing.
+extern "C" hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
+                                            const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
+                                            const uint32_t *histTriangle, float *outColour, float *outCount, float maxHistory,
+                                            float depthTolerance, hipStream_t stream)
+{
+    RttArgs A;
+    A.W = W; A.H = H; A.blocksX = (W + 31u) / 32u;
+    A.maxHistory = maxHistory; A.depthTolerance = depthTolerance;
+    A.colour = colour; A.motion = motion; A.prevT = prevT; A.triangle = triangle;
+    A.histColour = histColour; A.histCount = histCount; A.histT = histT; A.histTriangle = histTriangle;
+    A.outColour = outColour; A.outCount = outCount;
+    hipLaunchKernelGGL(rtt_accumulate_kernel, dim3(A.blocksX * ((H + 7u) / 8u)), dim3(256), 0, stream, A);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtt_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount,
+                                        const uint16_t *tileBuf, float *colour, hipStream_t stream)
+{
+    if (tileCount == 0) return hipSuccess;
+    hipLaunchKernelGGL(rtt_gather_kernel, dim3(tileCount * 64u), dim3(256), 0, stream, W, H, tilesX, tileIds, tileBuf, colour);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream)
+{
+    hipLaunchKernelGGL(rtt_quantise_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, n, colour, outR, outG, outB);
+    return hipGetLastError();
+}

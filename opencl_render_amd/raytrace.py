@@ -66,6 +66,14 @@ class DenoiseParams(C.Structure):  # rtHipDenoiseParams
 DENOISE_DEFAULTS = dict(iterations=4, colour_inv_sigma2=4.0, albedo_inv_sigma2=100.0, normal_power_log2=7)
 
 
+class TemporalParams(C.Structure):  # rtHipTemporalParams
+    _fields_ = [("maxHistory", C.c_float), ("depthTolerance", C.c_float)]
+
+
+# rtHipTemporalDefaults (include/raytrace_hip.h, "TEMPORAL ACCUMULATION")
+TEMPORAL_DEFAULTS = dict(max_history=32.0, depth_tolerance=0.05)
+
+
 class AoParams(C.Structure):  # rtHipAoParams
     _fields_ = [("raysPerHit", C.c_uint32), ("pixelSamples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -117,6 +125,7 @@ RESIDENT_SYMBOLS = [
     "rtHipDenoiseDefaults", "rtHipDenoiseScratchBytes", "rtHipDenoiseDevice", "rtHipDenoise", "rtHipSceneDenoise", "rtHipSceneDenoiseTimes",
     "rtHipAoDefaults", "rtHipSceneAmbientOcclusion", "rtHipSceneAmbientOcclusionDevice",
     "rtHipSceneMotionMark", "rtHipSceneMotionReferenceCamera", "rtHipSceneMotion", "rtHipSceneMotionDevice",
+    "rtHipTemporalDefaults", "rtHipTemporalDevice", "rtHipTemporal", "rtHipSceneTemporal", "rtHipSceneTemporalReset", "rtHipSceneTemporalTimes",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
@@ -238,6 +247,13 @@ def lib() -> C.CDLL:
     L.rtHipSceneMotionReferenceCamera.argtypes = [vp, C.POINTER(Camera)]
     L.rtHipSceneMotion.argtypes = [vp, vp, vp, vp, vp]
     L.rtHipSceneMotionDevice.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rtHipTemporalDefaults.restype = None
+    L.rtHipTemporalDefaults.argtypes = [C.POINTER(TemporalParams)]
+    L.rtHipTemporalDevice.argtypes = [C.c_int, u32, u32] + [vp] * 10 + [C.POINTER(TemporalParams), vp]
+    L.rtHipTemporal.argtypes = [C.c_int, u32, u32] + [vp] * 10 + [C.POINTER(TemporalParams)]
+    L.rtHipSceneTemporal.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
+    L.rtHipSceneTemporalReset.argtypes = [vp]
+    L.rtHipSceneTemporalTimes.argtypes = [vp, C.POINTER(C.c_float)]
     L.rtHipBakeDefaults.restype = None
     L.rtHipBakeDefaults.argtypes = [C.POINTER(BakeParams)]
     L.rtHipSceneBakeAmbientOcclusion.argtypes = [vp, C.POINTER(BakeParams), vp, vp]
@@ -533,6 +549,77 @@ def _denoise_torch(colour, normal, albedo, p, device, stream):
         for buf in (c, n, a, out, scratch):
             buf.record_stream(run)
     return out
+
+
+def temporal_params(max_history=TEMPORAL_DEFAULTS["max_history"], depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"]) -> TemporalParams:
+    """rtHipTemporalParams from the Python keywords (the library checks the values)."""
+    return TemporalParams(float(max_history), float(depth_tolerance))
+
+
+_TEMPORAL_INPUTS = (("colour", 3, False), ("motion", 2, False), ("prev_t", 1, False), ("triangle", 1, True))
+_TEMPORAL_HISTORY = (("colour", 3, False), ("count", 1, False), ("t", 1, False), ("triangle", 1, True))
+
+
+def temporal(colour, motion, prev_t, triangle, history, max_history=TEMPORAL_DEFAULTS["max_history"],
+             depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"], out: Optional[dict] = None, device: int = 0, stream: int = 0) -> dict:
+    """The temporal accumulation of include/raytrace_hip.h ("TEMPORAL ACCUMULATION"): the frame `colour` [H, W, 3] f32 with its flow --
+    `motion` [H, W, 2] f32, `prev_t` [H, W] f32, `triangle` [H, W] u32, what ResidentScene.motion() gives -- against `history`, a dict
+    with "colour" [H, W, 3] f32, "count" [H, W] f32 (0: none), "t" [H, W] f32 and "triangle" [H, W] u32: the previous call's outputs and
+    the previous frame's t and triangle maps.  Returns {"colour": [H, W, 3] f32, "count": [H, W] f32}.  numpy arrays go through
+    rtHipTemporal (host arrays, synchronous); torch tensors on cuda:`device` (triangle ids uint32 or int32, their bits) stay there and go
+    through rtHipTemporalDevice on torch's current stream (or `stream`).  `out`: a dict with "colour" and, optionally, "count" to fill
+    instead of new arrays (they must not overlap an input); without "count" the counts are not written."""
+    p = temporal_params(max_history, depth_tolerance)
+    missing = [k for k, _, _ in _TEMPORAL_HISTORY if k not in history]
+    if missing:
+        raise ValueError(f"temporal: history lacks {missing}")
+    given = [("", name, v, ch, ids) for (name, ch, ids), v in zip(_TEMPORAL_INPUTS, (colour, motion, prev_t, triangle))]
+    given += [("history ", name, history[name], ch, ids) for name, ch, ids in _TEMPORAL_HISTORY]
+    if out is not None and ("colour" not in out or any(k not in ("colour", "count") for k in out)):
+        raise ValueError(f"temporal: out takes 'colour' and optionally 'count' (got {sorted(out)})")
+    on_gpu = any(hasattr(v, "data_ptr") for _, _, v, _, _ in given)
+    shape = tuple(colour.shape[:2])
+    if len(colour.shape) != 3 or colour.shape[2] != 3:
+        raise ValueError(f"temporal: colour must be [H, W, 3] (got {tuple(colour.shape)})")
+    H, W = int(shape[0]), int(shape[1])
+    if on_gpu:
+        import torch
+
+        dev = torch.device("cuda", device)
+        f32, ids32, new = (torch.float32,), (torch.uint32, torch.int32), lambda sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        good = lambda v, sh, kinds: isinstance(v, torch.Tensor) and v.device == dev and v.dtype in kinds and tuple(v.shape) == sh and v.is_contiguous()
+        address = lambda v: C.c_void_p(v.data_ptr())
+    else:
+        f32, ids32, new = (np.dtype(np.float32),), (np.dtype(np.uint32),), lambda sh: np.empty(sh, np.float32)
+        good = lambda v, sh, kinds: isinstance(v, np.ndarray) and v.dtype in kinds and v.shape == sh and v.flags.c_contiguous
+        address = _ptr
+    for prefix, name, v, ch, ids in given:
+        want = shape + (ch,) if ch > 1 else shape
+        if not good(v, want, ids32 if ids else f32):
+            raise ValueError(f"temporal: {prefix}{name} must be a contiguous {'uint32' if ids else 'float32'} {want} "
+                             f"{'tensor on ' + str(dev) if on_gpu else 'array'}")
+    res = dict(out) if out is not None else {"colour": new(shape + (3,)), "count": new(shape)}
+    for name, v in res.items():
+        want = shape + (3,) if name == "colour" else shape
+        if not good(v, want, f32):
+            raise ValueError(f"temporal: out[{name!r}] must be a contiguous float32 {want} {'tensor on ' + str(dev) if on_gpu else 'array'}")
+    ptrs = [address(v) for _, _, v, _, _ in given] + [address(res["colour"]), address(res["count"]) if "count" in res else None]
+    if not on_gpu:
+        if lib().rtHipTemporal(device, W, H, *ptrs, C.byref(p)) != 0:
+            raise RuntimeError("rtHipTemporal failed: " + last_error())
+        return res
+    cur = torch.cuda.current_stream(dev)
+    run = torch.cuda.ExternalStream(stream, device=dev) if stream and stream != cur.cuda_stream else cur
+    if run is not cur:
+        run.wait_stream(cur)
+    rc = lib().rtHipTemporalDevice(device, W, H, *ptrs, C.byref(p), C.c_void_p(run.cuda_stream) if run.cuda_stream else None)
+    if rc != 0:
+        raise RuntimeError("rtHipTemporalDevice failed: " + last_error())
+    if run is not cur:
+        cur.wait_stream(run)
+        for buf in [v for _, _, v, _, _ in given] + list(res.values()):
+            buf.record_stream(run)
+    return res
 
 
 def computation_type_names() -> list:
@@ -1043,6 +1130,34 @@ class ResidentScene:
         ms = (C.c_float * 3)()
         self._check(lib().rtHipSceneDenoiseTimes(self.handle, ms), "rtHipSceneDenoiseTimes")
         return dict(gather=ms[0], prologue=ms[1], filter=ms[2])
+
+    def temporal(self, denoise: Optional[dict] = None, **params) -> dict:
+        """The last frame accumulated over the frames before it on the device (rtHipSceneTemporal; keywords max_history and
+        depth_tolerance as for raytrace.temporal): {"colour": [H, W, 3] f32, "planes": [r, g, b] [H, W] u16, "count": [H, W] f32, the
+        history length of each pixel}.  The loop is set_camera / set_vertices, render(), temporal(); the call marks the scene (mark_motion)
+        after itself, so a later motion() measures against this frame.  `denoise`: a dict of raytrace.denoise's keywords ({} for the
+        defaults) runs the denoiser on the accumulation before it is returned (needs set_passes(normal=True, albedo=True)); the history
+        keeps the unfiltered colour.  Needs every tile of the image in this instance."""
+        p = temporal_params(**params)
+        d = denoise_params(**denoise) if denoise is not None else None
+        sc = self.scene
+        colour = np.empty((sc.height, sc.width, 3), np.float32)
+        planes = [np.empty((sc.height, sc.width), np.uint16) for _ in range(3)]
+        count = np.empty((sc.height, sc.width), np.float32)
+        self._check(lib().rtHipSceneTemporal(self.handle, C.byref(p), C.byref(d) if d is not None else None, _ptr(colour), _ptr(planes[0]),
+                                             _ptr(planes[1]), _ptr(planes[2]), _ptr(count)), "rtHipSceneTemporal")
+        return {"colour": colour, "planes": planes, "count": count}
+
+    def reset_temporal(self) -> None:
+        """Forgets the history of temporal() (rtHipSceneTemporalReset): the next call returns the frame itself with count 1."""
+        self._check(lib().rtHipSceneTemporalReset(self.handle), "rtHipSceneTemporalReset")
+
+    def temporal_times_ms(self) -> dict:
+        """Device time of the last temporal() (rtHipSceneTemporalTimes): motion pass, gather, accumulate, filter (denoiser, if any, and
+        output)."""
+        ms = (C.c_float * 4)()
+        self._check(lib().rtHipSceneTemporalTimes(self.handle, ms), "rtHipSceneTemporalTimes")
+        return dict(motion=ms[0], gather=ms[1], accumulate=ms[2], filter=ms[3])
 
     def ambient_occlusion(self, rays=AO_DEFAULTS["rays"], radius=AO_DEFAULTS["radius"], pixel_samples=AO_DEFAULTS["pixel_samples"],
                           seed=AO_DEFAULTS["seed"], out=None, stream: int = 0):
