@@ -1,0 +1,41 @@
+"""Resident scenes under sequences of operations on the MI355X (run with -m gpu): every sequence of tests/session_cases.py -- the
+Eulerian circuits over the operation kinds, cut into sequences of at most 40 steps, the random walks and the named regressions -- is
+played on a fresh scene, and after every step the device's answer is compared with the oracle's answer for the model's state (frames as
+integers, lists and device arrays, motion and temporal accumulation as float bits, passes, denoise, AO and the bake against a twin
+created fresh from the model's Scene, refusals by code and text).  A test stops at the first mismatch and names the scene, the seed,
+the step, every step so far and the array that differed; nothing is tried again.  tests/test_session.py shows without a GPU that the
+sequences are not vacuous and that the model is right; tests/session_replay.py plays one sequence by hand.
+
+Sizing, measured on the MI355X in one run of this file with tests/test_temporal_gpu.py: the temporal suite's slowest test (the camera
+chain on axis_class_sun) takes 1.85 s, so a sequence may take 5.55 s.  The slowest sequence takes 3.19 s (axis_near_axis_mixed, 25
+steps); every mirror_hall sequence of 40 steps and both walks of 60 stay below 1.3 s.  The module's fixture takes 61 s: it makes the
+oracles' products once -- the grids of the larger scene's six shapes at 7 s each, prep_oracle's records and dense views, and the planes
+and walks of every visited state -- so that a sequence's time is the device's and the comparisons'.  On the larger scene (12.6 million
+grid pairs) the check of the device arrays after an update takes 1.2 s; a sequence there holds at most two updates and 25 steps."""
+import pytest
+import torch  # noqa: F401  (before the library loads its HIP runtime: the order bench.py uses)
+
+import motion_cases as MC
+import session_cases as SC
+from opencl_render_amd import raytrace as R
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def need_gpu(hip_lib):
+    if hip_lib.rtHipDeviceCount() < 1:
+        pytest.fail("no HIP device: the session tests cannot run (and the product has no CPU fallback)")
+    MC.use_grid_builder(lambda sc: R.build_scene_grid_device(sc, 0))
+    for name, spec in SC.SCENES.items():  # the oracles' products of every shape and visited state, once for the module
+        for shape in spec["shapes"]:
+            SC.world(name).shape_scene(shape)
+        SC.world(name).warm(SC.visited(name))
+    yield
+    MC.use_grid_builder(R.build_scene_grid)
+    R.tune("build_list_limit", 0xFFFFFFFF)
+
+
+@pytest.mark.parametrize("name, seed, part", SC.all_parts())
+def test_sequence(name, seed, part):
+    assert SC.play(name, seed, part) >= 2
