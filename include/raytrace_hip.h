@@ -660,6 +660,105 @@ int  rtHipSceneTemporalReset(rtHipScene *scene);
  * the output kernel.  All 0 before the first call.  Returns 0, or -1 for a NULL argument. */
 int  rtHipSceneTemporalTimes(const rtHipScene *scene, cl_float ms[4]);
 
+/* VARIANCE-GUIDED FILTER: the denoising chain's knowledge of how noisy each pixel still is (Schied et al. 2017, "SVGF").  (a) The first
+ * two moments of the luminance are accumulated along TEMPORAL ACCUMULATION's reprojection; (b) a per-pixel variance is estimated from
+ * them, spatially where the history is too short to tell; (c) an a-trous filter like the DENOISER runs with a luminance edge-stop scaled
+ * by the local variance, and carries the variance through its iterations.  The arithmetic is IEEE fp32 + - * /, floorf, fabsf, sqrt
+ * (guides only) and compares in a fixed order (no FMA, divisions correctly rounded): tests/variance_oracle.py restates it in numpy and the
+ * device output equals it bit for bit (up to the payload of a NaN).
+ *
+ * lum(c) = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b.  The guides n^ and z, the normal weight wn (with E) and the albedo distance da are
+ * exactly the DENOISER block's; B = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ *
+ * (a) Moments accumulation.  Inputs and per-pixel work as TEMPORAL ACCUMULATION, unchanged: outColour and outCount are bit-identical to
+ * rtHipTemporal's for the same inputs.  In addition histMoments and outMoments, 2 x f32 per pixel (the means of lum and of lum*lum), and
+ * outVariance f32:
+ *   l = lum(colour_p), l2 = l*l;  s1 = s2 = +0.0f;  in the tap loop, for an accepted tap: s1 += b * histMoments_q[0];  s2 += b * histMoments_q[1]
+ *   if ok && sw > 0: h1 = s1/sw, h2 = s2/sw;  if n != 1.0f: m1 = h1 + (l - h1)*a, m2 = h2 + (l2 - h2)*a;  if n == 1.0f: m1 = l, m2 = l2
+ *   else: m1 = l, m2 = l2
+ *   outMoments = (m1, m2);  v = m2 - m1*m1;  outVariance = (v > 0 ? v : 0)                       (a NaN gives 0)
+ *
+ * (b) Variance estimate V^0, from moments 2 x f32 and count f32 (the history length).  With both NULL: moments = (lum(c), lum(c)*lum(c))
+ * and count = 1 in every pixel, the single-frame use.
+ *   if count_p >= spatialBelow: V^0 = (v > 0 ? v : 0) with v = m2 - m1*m1
+ *   otherwise (a NaN count too): a 7x7 window at spacing 1, dy = -3..3 (rows, outer), dx = -3..3 (columns, inner), q = (x + dx, y + dy);
+ *     taps outside the image are skipped; sw = s1 = s2 = +0.0f;  per tap: w = wn / (1 + da*ia);  sw += w;  s1 += w*m1_q;  s2 += w*m2_q
+ *     if sw > 0: M1 = s1/sw, M2 = s2/sw, v = M2 - M1*M1, v = (v > 0 ? v : 0), V^0 = v * (count_p >= 1.0f ? 4.0f/count_p : 4.0f)
+ *     else: V^0 = 0
+ *
+ * (c) Iteration i = 0..K-1 reads the state (C^i, V^i) (C^0 = c) and writes (C^(i+1), V^(i+1)); h = 2^i.  Per pixel p = (x, y):
+ *   G = {1/4, 1/2, 1/4};  gs = gw = +0.0f;  for j = 0..2 (rows, outer), k = 0..2 (columns, inner), q = (x + k-1, y + j-1), taps outside
+ *     the image skipped: gs += (G[j]*G[k]) * V^i_q;  gw += G[j]*G[k]
+ *   g = gs/gw;  il = 1.0f / (ls*g + floor)
+ *   the 25 taps of the DENOISER block at spacing h, same order, same skipping; sw = s_c = sv = +0.0f; per tap:
+ *     dl = lum(C^i_p) - lum(C^i_q)
+ *     w = ((B[j]*B[k]) * wn) / ((1 + (dl*dl)*il) * (1 + da*ia))
+ *     sw += w;  s_c += w * C^i_q per component;  sv += (w*w) * V^i_q
+ *   if sw > 0: C^(i+1)_p = s_c/sw, V^(i+1)_p = sv / (sw*sw);  otherwise both are kept.
+ * There is no sigma schedule: the variance shrinks by itself, and the edge-stop with it.  Outputs: C^K and, optionally, V^K.
+ *
+ * Parameters: iterations K in 0..12; luminanceSigma2 ls finite and >= 0; varianceFloor finite and >= 2^-100; albedoInvSigma2 ia and
+ * normalPowerLog2 E as the DENOISER block's; spatialBelow finite and in [0, 65537].  Anything else returns -1 before anything is
+ * launched.  Every bit pattern of the inputs has a defined answer up to the payload of a NaN (an infinite variance next to a zero weight
+ * is a NaN by 0 * inf, and spreads), and nothing indexes out of range.
+ *
+ * One limit: the renderer seeds every frame alike (the reference's seeding), so under a still camera and still geometry successive
+ * frames are identical and the temporal variance is 0: the filter then does not smooth at all beyond what the floor allows.  For such
+ * sequences set spatialBelow above maxHistory, which forces the spatial estimate in every pixel. */
+typedef struct rtHipVarianceParams {
+    cl_uint  iterations;      /* K */
+    cl_float luminanceSigma2; /* ls: the luminance edge-stop is (dl*dl) / (ls * variance + floor) */
+    cl_float varianceFloor;   /* floor */
+    cl_float albedoInvSigma2; /* ia */
+    cl_uint  normalPowerLog2; /* E */
+    cl_float spatialBelow;    /* pixels whose history is shorter than this take the 7x7 spatial estimate */
+} rtHipVarianceParams;
+/* K = 4, ls = 4, floor = 1e-8f, ia = 100, E = 7, spatialBelow = 4 ("Variance-guided filter", says why). */
+void     rtHipVarianceDefaults(rtHipVarianceParams *params);
+/* (a) on DEVICE arrays: rtHipTemporalDevice plus histMoments (input), outMoments and outVariance (outputs; outCount and outVariance may
+ * be NULL).  Same checks: every pointer, overlap (no output may overlap anything else), stream and size as rtHipTemporalDevice; a
+ * refusal launches nothing.  One launch. */
+int  rtHipTemporalMomentsDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                                const void *triangle, const void *histColour, const void *histCount, const void *histT,
+                                const void *histTriangle, const void *histMoments, void *outColour, void *outCount, void *outMoments,
+                                void *outVariance, const rtHipTemporalParams *params, void *stream);
+/* HOST arrays, synchronous; outCount and outVariance may be NULL.  Same results as rtHipTemporalMomentsDevice. */
+int  rtHipTemporalMoments(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                          const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                          const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour, cl_float *outCount,
+                          cl_float *outMoments, cl_float *outVariance, const rtHipTemporalParams *params);
+/* Device scratch rtHipDenoiseVarianceDevice needs for a W x H image (16-byte aligned): two float4 states, the packed guides and il,
+ * 68 B per pixel.  0 for a size it refuses. */
+uint64_t rtHipVarianceScratchBytes(cl_uint width, cl_uint height);
+/* (b) and (c) on DEVICE arrays of `device`, asynchronous on `stream`: no allocation, no synchronisation.  colour, normal, albedo and out
+ * W x H x 3 f32, moments W x H x 2 f32 and count W x H f32 (both NULL or both given), outVariance W x H f32 (V^K; may be NULL), scratch at
+ * least rtHipVarianceScratchBytes.  Checked exactly as rtHipDenoiseDevice checks: pointers, alignment (4 bytes, scratch 16), stream, W*H
+ * <= 2^27; out, outVariance and scratch must overlap nothing.  Anything else returns -1 with the last-error text set and launches
+ * nothing. */
+int  rtHipDenoiseVarianceDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *normal, const void *albedo,
+                                const void *moments, const void *count, void *out, void *outVariance, void *scratch, uint64_t scratchBytes,
+                                const rtHipVarianceParams *params, void *stream);
+/* HOST arrays, synchronous; device memory is allocated and freed per call.  Same checks and results as rtHipDenoiseVarianceDevice. */
+int  rtHipDenoiseVariance(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *normal, const cl_float *albedo,
+                          const cl_float *moments, const cl_float *count, cl_float *out, cl_float *outVariance,
+                          const rtHipVarianceParams *params);
+/* rtHipSceneTemporal with the moments carried along: the same sequence, the same ownership of the mark, the same outputs and the same
+ * four timing slots of rtHipSceneTemporalTimes (the estimate and the filter go into ms[3]), with (a) in place of the accumulation.
+ * variance NULL: no filter; outRgb and the planes are the accumulation and outVariance is (a)'s variance.  variance non-NULL: needs
+ * RT_HIP_PASS_NORMAL | RT_HIP_PASS_ALBEDO on; the accumulated colour, the new moments and the new counts go through (b) and (c) with the
+ * gathered normal and albedo, in the scratch rtHipSceneDenoise uses (made by this call if need be, and counted then); outRgb and the
+ * planes are C^K and outVariance is V^K.  The history keeps the unfiltered accumulation and its moments.  outVariance W x H f32, host,
+ * may be NULL like every other output.
+ * Storage: the moments history shares colour, count, t and triangle with rtHipSceneTemporal's; it adds, in one block made on the first
+ * call, counted in rtHipSceneBytes from then on and freed with the scene, with n = W*H and every part rounded up to 256 bytes: two sets
+ * of moments 8n, the variance plane 4n and the filter's il plane 4n.
+ * Mixing: rtHipSceneTemporal does not write moments, so a call to it leaves them stale.  An rtHipSceneTemporalVariance that finds a live
+ * history with stale moments starts the history again, as after rtHipSceneTemporalReset; rtHipSceneTemporal after this call goes on
+ * with the history this call left.  Refusals as rtHipSceneTemporal's, with the variance parameters and "a filter without both surface
+ * passes" in place of the denoiser's. */
+int  rtHipSceneTemporalVariance(rtHipScene *scene, const rtHipTemporalParams *params, const rtHipVarianceParams *variance, cl_float *outRgb,
+                                cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount, cl_float *outVariance);
+
 /* AMBIENT OCCLUSION BAKE: a W x H texture of ambient occlusion over the scene's UV layout.  Each texel centre is mapped to the surface
  * point of the triangle whose UV triangle covers it, and the AO rays of the block above are traced from there with the same walk.  It
  * needs geometry, UVs, corner normals and the grid only: it works on every instance (whatever its tiles, passes or pipeline), ignores

@@ -25,7 +25,9 @@ VECTORS") against the frame before it to PREFIX_000.npz .. PREFIX_{N-1}.npz.
 
 ``--temporal PATH`` (with ``--orbit N`` or ``--spin N``) also writes every frame accumulated over the frames before it (include/raytrace_hip.h,
 "TEMPORAL ACCUMULATION"; ResidentScene.temporal) to PATH_000 .. PATH_{N-1}: .bmp, .ppm or .pfm.  With ``--denoise`` the denoiser runs on
-the accumulation before it is written.
+the accumulation before it is written.  ``--variance-guided`` (beside ``--temporal PATH``) carries the luminance moments along and
+runs the variance-guided filter (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER"; ResidentScene.temporal_variance) on the accumulation
+in the denoiser's place; ``--variance PATH`` also writes each frame's variance (V^K with the filter) as .pfm, numbered the same way.
 
 ``--bake-ao PATH`` also bakes ambient occlusion into a texture over the scene's UVs (include/raytrace_hip.h, "AMBIENT OCCLUSION
 BAKE") and writes it to PATH like ``--ao``: .pfm (f32) or .pgm (8 bits).  ``--bake-size W H`` (default 512 512), ``--bake-rays``,
@@ -81,6 +83,12 @@ def parser():
                     help="with --orbit N or --spin N: also write every frame accumulated over the frames before it (ResidentScene.temporal: "
                          "the history reprojected along the motion vectors, default parameters) to PATH numbered like --out: .bmp, .ppm or "
                          ".pfm.  With --denoise the denoiser runs on the accumulation before it is written (the history stays unfiltered)")
+    ap.add_argument("--variance-guided", action="store_true",
+                    help="with --temporal PATH: accumulate the luminance moments too and run the variance-guided filter (default parameters) "
+                         "on the accumulation before it is written (ResidentScene.temporal_variance); not together with --denoise")
+    ap.add_argument("--variance", metavar="PATH",
+                    help="with --temporal PATH: also write every frame's variance as .pfm, numbered like --out: V^K of the variance-guided "
+                         "filter with --variance-guided, the temporal variance of the luminance without")
     ap.add_argument("--orbit", type=int, default=1, metavar="N",
                     help="N views of the one resident scene on a circle about the vertical axis through the look-at point, same height and "
                          "distance, each after the first through ResidentScene.look_at (the camera lists are rebuilt on the device, nothing is "
@@ -115,6 +123,12 @@ def parse_args(argv=None):
         ap.error("--temporal PATH needs --orbit N or --spin N with N >= 2 (the frames it accumulates)")
     if args.temporal and not args.temporal.lower().endswith((".bmp", ".ppm", ".pfm")):
         ap.error("--temporal PATH must end in .bmp, .ppm or .pfm")
+    if (args.variance_guided or args.variance) and not args.temporal:
+        ap.error("--variance-guided and --variance PATH need --temporal PATH")
+    if args.variance_guided and args.denoise:
+        ap.error("--variance-guided does not go with --denoise (one filter runs on the accumulation)")
+    if args.variance and not args.variance.lower().endswith(".pfm"):
+        ap.error("--variance PATH must end in .pfm")
     if args.surface_passes and not args.passes:
         ap.error("--surface-passes needs --passes PREFIX")
     if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
@@ -249,11 +263,17 @@ def write_motion(rs, args, index: int) -> None:
 
 
 def write_temporal(rs, args, index: int) -> None:
-    """--temporal: frame `index` accumulated over the frames before it -> PATH numbered like --out; with --denoise, filtered."""
+    """--temporal: frame `index` accumulated over the frames before it -> PATH numbered like --out; with --denoise or --variance-guided,
+    filtered; --variance: its variance too."""
     if not args.temporal:
         return
     from . import frontend, raytrace
-    res = rs.temporal(denoise={} if args.denoise else None)
+    if args.variance_guided or args.variance:
+        res = rs.temporal_variance(filter={} if args.variance_guided else None)
+        if args.variance:
+            frontend.write_pfm(raytrace.orbit_path(args.variance, index), res["variance"])
+    else:
+        res = rs.temporal(denoise={} if args.denoise else None)
     path = raytrace.orbit_path(args.temporal, index)
     if path.lower().endswith(".pfm"):
         frontend.write_pfm_rgb(path, res["colour"])
@@ -269,7 +289,7 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
     from . import raytrace
     rs = raytrace.ResidentScene(sc, device)
     try:
-        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise)
+        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
         if basic or surface:
             rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
         spent = 0.0
@@ -302,7 +322,7 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
     try:
         if eye is not None:
             rs.look_at(eye, centre, (0, 1, 0), np.radians(args.fov))
-        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise)
+        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
         if basic or surface:
             rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
         vertex, index, normal = sc.vertex, sc.tri_index, sc.tri_normal

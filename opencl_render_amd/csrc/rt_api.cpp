@@ -64,6 +64,18 @@ extern "C" hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float 
 extern "C" hipError_t rtt_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount,
                                         const uint16_t *tileBuf, float *colour, hipStream_t stream);
 extern "C" hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
+// rt_variance.hip
+extern "C" hipError_t rtv_launch_moments(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
+                                         const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
+                                         const uint32_t *histTriangle, const float *histMoments, float *outColour, float *outCount,
+                                         float *outMoments, float *outVariance, float maxHistory, float depthTolerance, hipStream_t stream);
+extern "C" hipError_t rtv_launch_estimate(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo,
+                                          const float *moments, const float *count, float spatialBelow, float ia, uint32_t E, void *s0,
+                                          void *g0, void *g1, hipStream_t stream);
+extern "C" hipError_t rtv_launch_iteration(uint32_t W, uint32_t H, int h, float ls, float floor_, float ia, uint32_t E, const void *sin,
+                                           void *il, const void *g0, const void *g1, void *sout, hipStream_t stream);
+extern "C" hipError_t rtv_launch_output(uint32_t n, const void *s, float *out, float *outVariance, uint16_t *outR, uint16_t *outG,
+                                        uint16_t *outB, hipStream_t stream);
 extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
                                            hipStream_t stream);
 extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
@@ -374,11 +386,17 @@ struct rtHipScene {
     // temporal accumulation (rtHipSceneTemporal), made on its first call in one block: two history sets (colour | count | t | triangle;
     // `cur` is the one the next call reads), this frame's motion and prevT, the gathered colour and the u16 output planes.  valid: the
     // history set `cur` holds a frame (false after a reset: the next call clears its counts first).
+    // rtHipSceneTemporalVariance adds a block of its own on its first call: two sets of moments (they change places with the history
+    // sets), the variance plane and the filter's il plane.  momentsValid: the moments set `cur` belongs to the history set `cur` (false
+    // after an rtHipSceneTemporal, which does not write them).
     struct Temporal {
         char *buf = nullptr;
         uint64_t bytes = 0;
         int cur = 0;
         bool valid = false;
+        char *momentsBuf = nullptr;
+        uint64_t momentsBytes = 0;
+        bool momentsValid = false;
         hipEvent_t ev[5] = {};
         float ms[4] = {};
     } temporal;
@@ -1342,6 +1360,7 @@ void rtHipSceneDestroy(rtHipScene *sc)
     if (sc->motion.marked) (void)hipEventDestroy(sc->motion.marked);
     if (sc->motion.done) (void)hipEventDestroy(sc->motion.done);
     if (sc->temporal.buf) (void)hipFree(sc->temporal.buf);
+    if (sc->temporal.momentsBuf) (void)hipFree(sc->temporal.momentsBuf);
     for (hipEvent_t e : sc->temporal.ev)
         if (e) (void)hipEventDestroy(e);
     if (sc->cam.scratch) (void)hipFree(sc->cam.scratch);
@@ -2507,8 +2526,16 @@ int rtHipTemporal(int device, cl_uint width, cl_uint height, const cl_float *col
     return 0;
 }
 
-int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipDenoiseParams *denoise, cl_float *outRgb,
-                       cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount)
+static int variance_params_ok(const rtHipVarianceParams *p);
+static int variance_issue(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo, const float *moments,
+                          const float *count, float *out, float *outVariance, uint16_t *planeR, uint16_t *planeG, uint16_t *planeB, char *scratch,
+                          char *il, const rtHipVarianceParams *p, hipStream_t st);
+
+// rtHipSceneTemporal (withMoments false: `denoise` or no filter) and rtHipSceneTemporalVariance (withMoments true: `variance` or no filter)
+// are one sequence; the second carries the moments along and has a variance to output.
+static int scene_temporal(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipDenoiseParams *denoise, bool withMoments,
+                          const rtHipVarianceParams *variance, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG, cl_ushort *outB,
+                          cl_float *outCount, cl_float *outVariance)
 {
     if (!sc) return fail("temporal: null scene");
     if (temporal_params_ok(params) != 0 || temporal_size_ok(sc->width, sc->height) != 0) return -1;
@@ -2516,6 +2543,11 @@ int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const 
         if (denoise_params_ok(denoise) != 0) return -1;
         if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
             return fail("temporal: denoise needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
+    }
+    if (variance) {
+        if (variance_params_ok(variance) != 0) return -1;
+        if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
+            return fail("temporal: the variance-guided filter needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
     }
     if (whole_image_tiles(sc, "temporal accumulation") != 0) return -1;
     HIP_OK(hipSetDevice(sc->device));
@@ -2537,6 +2569,15 @@ int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const 
         T.buf = (char *)p; T.bytes = bytes; T.cur = 0; T.valid = false;
         sc->bytes += bytes;
     }
+    if (withMoments && !T.momentsBuf) { // two sets of moments | the variance | the filter's il
+        const uint64_t bytes = 2 * part(n * 8) + 2 * part(n * 4);
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) return fail("temporal: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        T.momentsBuf = (char *)p; T.momentsBytes = bytes; T.momentsValid = false;
+        sc->bytes += bytes;
+    }
+    if (withMoments && !T.momentsValid) T.valid = false; // a live history whose moments are stale starts again, as after a reset
     for (hipEvent_t &e : T.ev)
         if (!e) HIP_OK(hipEventCreate(&e));
     struct Set { float *colour, *count, *t; uint32_t *triangle; } hs[2];
@@ -2550,14 +2591,22 @@ int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const 
     uint16_t *planes[3];
     for (int c = 0; c < 3; ++c) planes[c] = (uint16_t *)(rest + part(n * 8) + part(n * 4) + part(n * 12) + c * part(n * 2));
     const Set &hist = hs[T.cur], &next = hs[T.cur ^ 1];
+    float *moments[2] = {}, *varianceOut = nullptr;
+    char *il = nullptr;
+    if (withMoments) {
+        moments[0] = (float *)T.momentsBuf; moments[1] = (float *)(T.momentsBuf + part(n * 8));
+        varianceOut = (float *)(T.momentsBuf + 2 * part(n * 8));
+        il = T.momentsBuf + 2 * part(n * 8) + part(n * 4);
+    }
+    const bool surfaces = denoise || variance; // the filters take the gathered normal and albedo
     DenoiseBuffer D{};
-    if (denoise && denoise_buffer(sc, D) != 0) return -1;
+    if (surfaces && denoise_buffer(sc, D) != 0) return -1;
     hipStream_t st = sc->stream;
     if (!T.valid) HIP_OK(hipMemsetAsync(hist.count, 0, n * 4, st)); // no history: every tap is refused, whatever the rest of the set holds
     HIP_OK(hipEventRecord(T.ev[0], st));
     if (motion_run(sc, motion, next.t, prevT, next.triangle, true, st) != 0) return -1; // this frame's guides are the next call's history
     HIP_OK(hipEventRecord(T.ev[1], st));
-    if (denoise) {
+    if (surfaces) {
         HIP_OK(rtd_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->surfBuf,
                                  (float)sc->dev.sampleCount, D.colour, D.normal, D.albedo, st));
         colour = D.colour;
@@ -2565,15 +2614,28 @@ int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const 
         HIP_OK(rtt_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, colour, st));
     }
     HIP_OK(hipEventRecord(T.ev[2], st));
-    HIP_OK(rtt_launch_accumulate(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle, next.colour,
-                                 next.count, params->maxHistory, params->depthTolerance, st));
+    if (withMoments)
+        HIP_OK(rtv_launch_moments(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle, moments[T.cur],
+                                  next.colour, next.count, moments[T.cur ^ 1], variance ? nullptr : varianceOut, params->maxHistory,
+                                  params->depthTolerance, st));
+    else
+        HIP_OK(rtt_launch_accumulate(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle, next.colour,
+                                     next.count, params->maxHistory, params->depthTolerance, st));
     HIP_OK(hipEventRecord(T.ev[3], st));
     // From here until the new mark stands, a failure leaves the scene without history: set `next` is half a step ahead of the reference.
     T.valid = false;
+    T.momentsValid = false;
     const bool wantPlanes = outR || outG || outB;
     const float *result = next.colour;
     uint16_t **resultPlanes = planes;
-    if (denoise) { // temporal, then spatial; the history keeps the unfiltered accumulation
+    if (variance) { // temporal, then spatial with the moments' variance; the history keeps the unfiltered accumulation
+        if (variance_issue(W, H, next.colour, D.normal, D.albedo, moments[T.cur ^ 1], next.count, outRgb ? D.out : nullptr, varianceOut,
+                           wantPlanes ? D.planes[0] : nullptr, wantPlanes ? D.planes[1] : nullptr, wantPlanes ? D.planes[2] : nullptr,
+                           D.scratch, il, variance, st) != 0)
+            return -1;
+        result = D.out;
+        resultPlanes = D.planes;
+    } else if (denoise) { // temporal, then spatial; the history keeps the unfiltered accumulation
         if (denoise_issue(W, H, next.colour, D.normal, D.albedo, outRgb ? D.out : nullptr, wantPlanes ? D.planes[0] : nullptr,
                           wantPlanes ? D.planes[1] : nullptr, wantPlanes ? D.planes[2] : nullptr, D.scratch, denoise, st) != 0)
             return -1;
@@ -2587,13 +2649,21 @@ int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const 
     HIP_OK(hipStreamSynchronize(st));
     T.cur ^= 1; // the sets change places only now: history and reference advance together
     T.valid = true;
+    T.momentsValid = withMoments;
     for (int i = 0; i < 4; ++i) HIP_OK(hipEventElapsedTime(&T.ms[i], T.ev[i], T.ev[i + 1]));
     if (outRgb) HIP_OK(hipMemcpy(outRgb, result, n * 12, hipMemcpyDeviceToHost));
     cl_ushort *dst[3] = { outR, outG, outB };
     for (int c = 0; c < 3; ++c)
         if (dst[c]) HIP_OK(hipMemcpy(dst[c], resultPlanes[c], n * 2, hipMemcpyDeviceToHost));
     if (outCount) HIP_OK(hipMemcpy(outCount, next.count, n * 4, hipMemcpyDeviceToHost));
+    if (outVariance) HIP_OK(hipMemcpy(outVariance, varianceOut, n * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipDenoiseParams *denoise, cl_float *outRgb,
+                       cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount)
+{
+    return scene_temporal(sc, params, denoise, false, nullptr, outRgb, outR, outG, outB, outCount, nullptr);
 }
 
 int rtHipSceneTemporalReset(rtHipScene *sc)
@@ -2608,6 +2678,200 @@ int rtHipSceneTemporalTimes(const rtHipScene *sc, cl_float *ms)
     if (!sc || !ms) return fail("null argument");
     for (int i = 0; i < 4; ++i) ms[i] = sc->temporal.ms[i];
     return 0;
+}
+
+// ---- variance-guided filter (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER"; kernels in rt_variance.hip) ------------------------
+// Filter scratch of a W x H image: the states S^i and S^(i+1) = (C.rgb, V) as float4 (ping-pong), the guides G0 and G1 as float4 (the
+// denoiser's 64 B per pixel), then il as f32.
+#define RT_VARIANCE_SCRATCH_PER_PIXEL 68ull
+
+void rtHipVarianceDefaults(rtHipVarianceParams *p)
+{
+    if (!p) return;
+    p->iterations = 4;
+    p->luminanceSigma2 = 4.0f;
+    p->varianceFloor = 1e-8f;
+    p->albedoInvSigma2 = 100.0f;
+    p->normalPowerLog2 = 7;
+    p->spatialBelow = 4.0f;
+}
+
+static int variance_params_ok(const rtHipVarianceParams *p)
+{
+    if (!p) return fail("variance: null parameters");
+    if (p->iterations > 12) return fail("variance: iterations %u is not in 0..12", p->iterations);
+    if (!(std::isfinite(p->luminanceSigma2) && p->luminanceSigma2 >= 0.f))
+        return fail("variance: luminanceSigma2 %g is not finite and >= 0", (double)p->luminanceSigma2);
+    if (!(std::isfinite(p->varianceFloor) && p->varianceFloor >= 0x1p-100f))
+        return fail("variance: varianceFloor %g is not finite and >= 2^-100", (double)p->varianceFloor);
+    if (!(std::isfinite(p->albedoInvSigma2) && p->albedoInvSigma2 >= 0.f))
+        return fail("variance: albedoInvSigma2 %g is not finite and >= 0", (double)p->albedoInvSigma2);
+    if (p->normalPowerLog2 > 10) return fail("variance: normalPowerLog2 %u is not in 0..10", p->normalPowerLog2);
+    if (!(std::isfinite(p->spatialBelow) && p->spatialBelow >= 0.f && p->spatialBelow <= 65537.0f))
+        return fail("variance: spatialBelow %g is not finite and in 0..65537", (double)p->spatialBelow);
+    return 0;
+}
+
+uint64_t rtHipVarianceScratchBytes(cl_uint width, cl_uint height)
+{
+    if (width == 0 || height == 0 || (uint64_t)width * height > RT_DENOISE_MAX_PIXELS) return 0;
+    return (uint64_t)width * height * RT_VARIANCE_SCRATCH_PER_PIXEL;
+}
+
+// Issues the filter on `st`: guides and estimate, K iterations, output (planes: all three or none).  scratch: the first 64 B per pixel of
+// the layout above; il: n f32.  Arguments were checked by the caller.
+static int variance_issue(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo, const float *moments,
+                          const float *count, float *out, float *outVariance, uint16_t *planeR, uint16_t *planeG, uint16_t *planeB, char *scratch,
+                          char *il, const rtHipVarianceParams *p, hipStream_t st)
+{
+    const size_t n = (size_t)W * H;
+    char *s[2] = { scratch, scratch + 16 * n };
+    char *g0 = scratch + 32 * n, *g1 = scratch + 48 * n;
+    HIP_OK(rtv_launch_estimate(W, H, colour, normal, albedo, moments, count, p->spatialBelow, p->albedoInvSigma2, p->normalPowerLog2, s[0], g0,
+                               g1, st));
+    for (uint32_t i = 0; i < p->iterations; ++i)
+        HIP_OK(rtv_launch_iteration(W, H, 1 << i, p->luminanceSigma2, p->varianceFloor, p->albedoInvSigma2, p->normalPowerLog2, s[i & 1], il,
+                                    g0, g1, s[(i + 1) & 1], st));
+    HIP_OK(rtv_launch_output((uint32_t)n, s[p->iterations & 1], out, outVariance, planeR, planeG, planeB, st));
+    return 0;
+}
+
+static int stream_of_device_ok(const char *who, int device, void *stream)
+{
+    if (!stream) return 0; // (the null stream is the current device's, set by the caller)
+    hipDevice_t sd = -1;
+    if (hipStreamGetDevice((hipStream_t)stream, &sd) != hipSuccess) { (void)hipGetLastError(); return fail("%s: stream %p is not a stream", who, stream); }
+    if (sd != device) return fail("%s: stream %p belongs to device %d, the call is for device %d", who, stream, (int)sd, device);
+    return 0;
+}
+
+int rtHipDenoiseVarianceDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *normal, const void *albedo,
+                               const void *moments, const void *count, void *out, void *outVariance, void *scratch, uint64_t scratchBytes,
+                               const rtHipVarianceParams *params, void *stream)
+{
+    if (variance_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
+    if (!colour || !normal || !albedo || !out || !scratch) return fail("variance: null array");
+    if ((moments == nullptr) != (count == nullptr)) return fail("variance: moments and count are both NULL or both given");
+    const uint64_t n = (uint64_t)width * height, img = n * 12, need = rtHipVarianceScratchBytes(width, height);
+    if (scratchBytes < need) return fail("variance: scratch of %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)need);
+    const struct { const void *p; uint64_t bytes, align; const char *what; } arr[8] = {
+        { colour, img, 4, "colour" }, { normal, img, 4, "normal" }, { albedo, img, 4, "albedo" }, { moments, n * 8, 4, "moments" },
+        { count, n * 4, 4, "count" }, { out, img, 4, "out" }, { scratch, need, 16, "scratch" }, { outVariance, n * 4, 4, "outVariance" } };
+    for (int i = 0; i < 8; ++i) // out, scratch and outVariance are written: none may overlap anything else
+        for (int k = 5; k < 8; ++k)
+            if (i != k && arr[i].p && arr[k].p && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
+                return fail("variance: %s overlaps %s", arr[k].what, arr[i].what);
+    HIP_OK(hipSetDevice(device));
+    if (stream_of_device_ok("variance", device, stream) != 0) return -1;
+    for (const auto &a : arr)
+        if (a.p && query_pointer_ok(device, "the call", a.p, a.bytes, a.align, a.what) != 0) return -1;
+    return variance_issue(width, height, (const float *)colour, (const float *)normal, (const float *)albedo, (const float *)moments,
+                          (const float *)count, (float *)out, (float *)outVariance, nullptr, nullptr, nullptr, (char *)scratch,
+                          (char *)scratch + 64 * n, params, (hipStream_t)stream);
+}
+
+int rtHipDenoiseVariance(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *normal, const cl_float *albedo,
+                         const cl_float *moments, const cl_float *count, cl_float *out, cl_float *outVariance, const rtHipVarianceParams *params)
+{
+    if (variance_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
+    if (!colour || !normal || !albedo || !out) return fail("variance: null array");
+    if ((moments == nullptr) != (count == nullptr)) return fail("variance: moments and count are both NULL or both given");
+    HIP_OK(hipSetDevice(device));
+    const size_t n = (size_t)width * height, img = n * 12;
+    DevScratch mem;
+    char *in = nullptr, *dm = nullptr, *dn = nullptr, *dout = nullptr, *dvar = nullptr, *scratch = nullptr;
+    HIP_OK(mem.get((void **)&in, 3 * img));
+    HIP_OK(mem.get((void **)&dout, img));
+    HIP_OK(mem.get((void **)&dvar, n * 4));
+    HIP_OK(mem.get((void **)&scratch, rtHipVarianceScratchBytes(width, height)));
+    HIP_OK(hipMemcpy(in, colour, img, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(in + img, normal, img, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(in + 2 * img, albedo, img, hipMemcpyHostToDevice));
+    if (moments) {
+        HIP_OK(mem.get((void **)&dm, n * 8));
+        HIP_OK(mem.get((void **)&dn, n * 4));
+        HIP_OK(hipMemcpy(dm, moments, n * 8, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dn, count, n * 4, hipMemcpyHostToDevice));
+    }
+    if (variance_issue(width, height, (const float *)in, (const float *)(in + img), (const float *)(in + 2 * img), (const float *)dm,
+                       (const float *)dn, (float *)dout, (float *)dvar, nullptr, nullptr, nullptr, scratch, scratch + 64 * n, params, nullptr) != 0)
+        return -1;
+    HIP_OK(hipMemcpy(out, dout, img, hipMemcpyDeviceToHost));
+    if (outVariance) HIP_OK(hipMemcpy(outVariance, dvar, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipDeviceSynchronize());
+    return 0;
+}
+
+int rtHipTemporalMomentsDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                               const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
+                               const void *histMoments, void *outColour, void *outCount, void *outMoments, void *outVariance,
+                               const rtHipTemporalParams *params, void *stream)
+{
+    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
+    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !histMoments || !outColour ||
+        !outMoments)
+        return fail("temporal: null array");
+    const uint64_t n = (uint64_t)width * height;
+    const struct { const void *p; uint64_t bytes; const char *what; } arr[13] = {
+        { colour, n * 12, "colour" }, { motion, n * 8, "motion" }, { prevT, n * 4, "prevT" }, { triangle, n * 4, "triangle" },
+        { histColour, n * 12, "histColour" }, { histCount, n * 4, "histCount" }, { histT, n * 4, "histT" }, { histTriangle, n * 4, "histTriangle" },
+        { histMoments, n * 8, "histMoments" }, { outColour, n * 12, "outColour" }, { outMoments, n * 8, "outMoments" },
+        { outCount, n * 4, "outCount" }, { outVariance, n * 4, "outVariance" } };
+    for (int i = 0; i < 13; ++i) // the outputs are written: none may overlap anything else
+        for (int k = 9; k < 13; ++k)
+            if (i != k && arr[i].p && arr[k].p && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
+                return fail("temporal: %s overlaps %s", arr[k].what, arr[i].what);
+    HIP_OK(hipSetDevice(device));
+    if (stream_of_device_ok("temporal", device, stream) != 0) return -1;
+    for (const auto &a : arr)
+        if (a.p && query_pointer_ok(device, "the call", a.p, a.bytes, 4, a.what) != 0) return -1;
+    HIP_OK(rtv_launch_moments(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
+                              (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle,
+                              (const float *)histMoments, (float *)outColour, (float *)outCount, (float *)outMoments, (float *)outVariance,
+                              params->maxHistory, params->depthTolerance, (hipStream_t)stream));
+    return 0;
+}
+
+int rtHipTemporalMoments(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                         const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                         const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour, cl_float *outCount, cl_float *outMoments,
+                         cl_float *outVariance, const rtHipTemporalParams *params)
+{
+    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
+    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !histMoments || !outColour ||
+        !outMoments)
+        return fail("temporal: null array");
+    HIP_OK(hipSetDevice(device));
+    const size_t n = (size_t)width * height;
+    const struct { const void *host; size_t bytes; } in[9] = { { colour, n * 12 }, { motion, n * 8 }, { prevT, n * 4 }, { triangle, n * 4 },
+                                                               { histColour, n * 12 }, { histCount, n * 4 }, { histT, n * 4 }, { histTriangle, n * 4 },
+                                                               { histMoments, n * 8 } };
+    DevScratch mem;
+    char *d[9], *dColour = nullptr, *dCount = nullptr, *dMoments = nullptr, *dVariance = nullptr;
+    for (int i = 0; i < 9; ++i) {
+        HIP_OK(mem.get((void **)&d[i], in[i].bytes));
+        HIP_OK(hipMemcpy(d[i], in[i].host, in[i].bytes, hipMemcpyHostToDevice));
+    }
+    HIP_OK(mem.get((void **)&dColour, n * 12));
+    HIP_OK(mem.get((void **)&dMoments, n * 8));
+    if (outCount) HIP_OK(mem.get((void **)&dCount, n * 4));
+    if (outVariance) HIP_OK(mem.get((void **)&dVariance, n * 4));
+    HIP_OK(rtv_launch_moments(width, height, (const float *)d[0], (const float *)d[1], (const float *)d[2], (const uint32_t *)d[3],
+                              (const float *)d[4], (const float *)d[5], (const float *)d[6], (const uint32_t *)d[7], (const float *)d[8],
+                              (float *)dColour, (float *)dCount, (float *)dMoments, (float *)dVariance, params->maxHistory,
+                              params->depthTolerance, nullptr));
+    HIP_OK(hipMemcpy(outColour, dColour, n * 12, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(outMoments, dMoments, n * 8, hipMemcpyDeviceToHost));
+    if (outCount) HIP_OK(hipMemcpy(outCount, dCount, n * 4, hipMemcpyDeviceToHost));
+    if (outVariance) HIP_OK(hipMemcpy(outVariance, dVariance, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipDeviceSynchronize());
+    return 0;
+}
+
+int rtHipSceneTemporalVariance(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipVarianceParams *variance, cl_float *outRgb,
+                               cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount, cl_float *outVariance)
+{
+    return scene_temporal(sc, params, nullptr, true, variance, outRgb, outR, outG, outB, outCount, outVariance);
 }
 
 // ---- geometry updates ------------------------------------------------------------------------------------------------------------

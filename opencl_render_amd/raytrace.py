@@ -74,6 +74,16 @@ class TemporalParams(C.Structure):  # rtHipTemporalParams
 TEMPORAL_DEFAULTS = dict(max_history=32.0, depth_tolerance=0.05)
 
 
+class VarianceParams(C.Structure):  # rtHipVarianceParams
+    _fields_ = [("iterations", C.c_uint32), ("luminanceSigma2", C.c_float), ("varianceFloor", C.c_float), ("albedoInvSigma2", C.c_float),
+                ("normalPowerLog2", C.c_uint32), ("spatialBelow", C.c_float)]
+
+
+# rtHipVarianceDefaults (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER"; DESIGN.md says why these values)
+VARIANCE_DEFAULTS = dict(iterations=4, luminance_sigma2=4.0, variance_floor=1e-8, albedo_inv_sigma2=100.0, normal_power_log2=7,
+                         spatial_below=4.0)
+
+
 class AoParams(C.Structure):  # rtHipAoParams
     _fields_ = [("raysPerHit", C.c_uint32), ("pixelSamples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -126,6 +136,8 @@ RESIDENT_SYMBOLS = [
     "rtHipAoDefaults", "rtHipSceneAmbientOcclusion", "rtHipSceneAmbientOcclusionDevice",
     "rtHipSceneMotionMark", "rtHipSceneMotionReferenceCamera", "rtHipSceneMotion", "rtHipSceneMotionDevice",
     "rtHipTemporalDefaults", "rtHipTemporalDevice", "rtHipTemporal", "rtHipSceneTemporal", "rtHipSceneTemporalReset", "rtHipSceneTemporalTimes",
+    "rtHipVarianceDefaults", "rtHipTemporalMomentsDevice", "rtHipTemporalMoments", "rtHipVarianceScratchBytes", "rtHipDenoiseVarianceDevice",
+    "rtHipDenoiseVariance", "rtHipSceneTemporalVariance",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
@@ -254,6 +266,15 @@ def lib() -> C.CDLL:
     L.rtHipSceneTemporal.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
     L.rtHipSceneTemporalReset.argtypes = [vp]
     L.rtHipSceneTemporalTimes.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rtHipVarianceDefaults.restype = None
+    L.rtHipVarianceDefaults.argtypes = [C.POINTER(VarianceParams)]
+    L.rtHipTemporalMomentsDevice.argtypes = [C.c_int, u32, u32] + [vp] * 13 + [C.POINTER(TemporalParams), vp]
+    L.rtHipTemporalMoments.argtypes = [C.c_int, u32, u32] + [vp] * 13 + [C.POINTER(TemporalParams)]
+    L.rtHipVarianceScratchBytes.restype = C.c_uint64
+    L.rtHipVarianceScratchBytes.argtypes = [u32, u32]
+    L.rtHipDenoiseVarianceDevice.argtypes = [C.c_int, u32, u32] + [vp] * 8 + [C.c_uint64, C.POINTER(VarianceParams), vp]
+    L.rtHipDenoiseVariance.argtypes = [C.c_int, u32, u32] + [vp] * 7 + [C.POINTER(VarianceParams)]
+    L.rtHipSceneTemporalVariance.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(VarianceParams), vp, vp, vp, vp, vp, vp]
     L.rtHipBakeDefaults.restype = None
     L.rtHipBakeDefaults.argtypes = [C.POINTER(BakeParams)]
     L.rtHipSceneBakeAmbientOcclusion.argtypes = [vp, C.POINTER(BakeParams), vp, vp]
@@ -619,6 +640,131 @@ def temporal(colour, motion, prev_t, triangle, history, max_history=TEMPORAL_DEF
         cur.wait_stream(run)
         for buf in [v for _, _, v, _, _ in given] + list(res.values()):
             buf.record_stream(run)
+    return res
+
+
+def variance_params(iterations=VARIANCE_DEFAULTS["iterations"], luminance_sigma2=VARIANCE_DEFAULTS["luminance_sigma2"],
+                    variance_floor=VARIANCE_DEFAULTS["variance_floor"], albedo_inv_sigma2=VARIANCE_DEFAULTS["albedo_inv_sigma2"],
+                    normal_power_log2=VARIANCE_DEFAULTS["normal_power_log2"], spatial_below=VARIANCE_DEFAULTS["spatial_below"]) -> VarianceParams:
+    """rtHipVarianceParams from the Python keywords (the library checks the ranges)."""
+    if not (0 <= int(iterations) <= 0xFFFFFFFF and 0 <= int(normal_power_log2) <= 0xFFFFFFFF):  # (ctypes would wrap them into the uint32 fields)
+        raise ValueError(f"variance: iterations and normal_power_log2 must be in 0..2^32-1 (got {iterations}, {normal_power_log2})")
+    return VarianceParams(int(iterations), float(luminance_sigma2), float(variance_floor), float(albedo_inv_sigma2), int(normal_power_log2),
+                          float(spatial_below))
+
+
+class _Arrays:
+    """What temporal_moments and denoise_variance need of their arrays, for numpy (host entry point) or torch on cuda:`device` (device
+    entry point on torch's current stream or `stream`)."""
+
+    def __init__(self, who, on_gpu, device, stream):
+        self.who, self.on_gpu, self.device = who, on_gpu, device
+        if on_gpu:
+            import torch
+
+            self.torch, self.dev = torch, torch.device("cuda", device)
+            self.cur = torch.cuda.current_stream(self.dev)
+            self.run = torch.cuda.ExternalStream(stream, device=self.dev) if stream and stream != self.cur.cuda_stream else self.cur
+
+    def check(self, name, v, shape, ids=False):
+        if self.on_gpu:
+            kinds = (self.torch.uint32, self.torch.int32) if ids else (self.torch.float32,)
+            ok = isinstance(v, self.torch.Tensor) and v.device == self.dev and v.dtype in kinds and tuple(v.shape) == shape and v.is_contiguous()
+        else:
+            ok = isinstance(v, np.ndarray) and v.dtype == (np.uint32 if ids else np.float32) and v.shape == shape and v.flags.c_contiguous
+        if not ok:
+            raise ValueError(f"{self.who}: {name} must be a contiguous {'uint32' if ids else 'float32'} {shape} "
+                             f"{'tensor on ' + str(self.dev) if self.on_gpu else 'array'}")
+        return v
+
+    def new(self, shape, dtype=np.float32):
+        if self.on_gpu:
+            return self.torch.empty(shape, dtype=self.torch.uint8 if dtype == np.uint8 else self.torch.float32, device=self.dev)
+        return np.empty(shape, dtype)
+
+    def address(self, v):
+        if v is None:
+            return None
+        return C.c_void_p(v.data_ptr()) if self.on_gpu else _ptr(v)
+
+    def stream_arg(self):
+        if self.run is not self.cur:
+            self.run.wait_stream(self.cur)
+        return C.c_void_p(self.run.cuda_stream) if self.run.cuda_stream else None
+
+    def done(self, buffers):
+        if self.run is not self.cur:
+            self.cur.wait_stream(self.run)
+            for buf in buffers:
+                if buf is not None:
+                    buf.record_stream(self.run)
+
+
+_MOMENTS_HISTORY = _TEMPORAL_HISTORY + (("moments", 2, False),)
+
+
+def temporal_moments(colour, motion, prev_t, triangle, history, max_history=TEMPORAL_DEFAULTS["max_history"],
+                     depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"], device: int = 0, stream: int = 0) -> dict:
+    """raytrace.temporal with the luminance moments carried along (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER", (a)): `history` also
+    holds "moments" [H, W, 2] f32.  Returns {"colour", "count", "moments" [H, W, 2] f32, "variance" [H, W] f32}; colour and count equal
+    raytrace.temporal's.  numpy arrays go through rtHipTemporalMoments; torch tensors on cuda:`device` stay there and go through
+    rtHipTemporalMomentsDevice on torch's current stream (or `stream`)."""
+    p = temporal_params(max_history, depth_tolerance)
+    missing = [k for k, _, _ in _MOMENTS_HISTORY if k not in history]
+    if missing:
+        raise ValueError(f"temporal_moments: history lacks {missing}")
+    given = [(name, v, ch, ids) for (name, ch, ids), v in zip(_TEMPORAL_INPUTS, (colour, motion, prev_t, triangle))]
+    given += [("history " + name, history[name], ch, ids) for name, ch, ids in _MOMENTS_HISTORY]
+    if len(colour.shape) != 3 or colour.shape[2] != 3:
+        raise ValueError(f"temporal_moments: colour must be [H, W, 3] (got {tuple(colour.shape)})")
+    shape = (int(colour.shape[0]), int(colour.shape[1]))
+    A = _Arrays("temporal_moments", any(hasattr(v, "data_ptr") for _, v, _, _ in given), device, stream)
+    for name, v, ch, ids in given:
+        A.check(name, v, shape + (ch,) if ch > 1 else shape, ids)
+    res = {"colour": A.new(shape + (3,)), "count": A.new(shape), "moments": A.new(shape + (2,)), "variance": A.new(shape)}
+    ptrs = [A.address(v) for _, v, _, _ in given] + [A.address(res[k]) for k in ("colour", "count", "moments", "variance")]
+    if not A.on_gpu:
+        if lib().rtHipTemporalMoments(device, shape[1], shape[0], *ptrs, C.byref(p)) != 0:
+            raise RuntimeError("rtHipTemporalMoments failed: " + last_error())
+        return res
+    if lib().rtHipTemporalMomentsDevice(device, shape[1], shape[0], *ptrs, C.byref(p), A.stream_arg()) != 0:
+        raise RuntimeError("rtHipTemporalMomentsDevice failed: " + last_error())
+    A.done([v for _, v, _, _ in given] + list(res.values()))
+    return res
+
+
+def denoise_variance(colour, normal, albedo, moments=None, count=None, device: int = 0, stream: int = 0, **params) -> dict:
+    """The variance-guided filter of include/raytrace_hip.h ("VARIANCE-GUIDED FILTER", (b) and (c)) on [H, W, 3] float32 colour, normal
+    and albedo images, with the `moments` [H, W, 2] f32 and `count` [H, W] f32 that temporal_moments returns (both None: the single-frame
+    use).  Keywords as VARIANCE_DEFAULTS.  Returns {"colour": C^K [H, W, 3] f32, "variance": V^K [H, W] f32}.  numpy arrays go through
+    rtHipDenoiseVariance; torch tensors on cuda:`device` go through rtHipDenoiseVarianceDevice on torch's current stream (or `stream`)
+    with a torch scratch tensor."""
+    p = variance_params(**params)
+    if (moments is None) != (count is None):
+        raise ValueError("denoise_variance: moments and count are both None or both given")
+    if len(colour.shape) != 3 or colour.shape[2] != 3:
+        raise ValueError(f"denoise_variance: colour must be [H, W, 3] (got {tuple(colour.shape)})")
+    shape = (int(colour.shape[0]), int(colour.shape[1]))
+    given = [("colour", colour, 3), ("normal", normal, 3), ("albedo", albedo, 3)]
+    if moments is not None:
+        given += [("moments", moments, 2), ("count", count, 1)]
+    A = _Arrays("denoise_variance", any(hasattr(v, "data_ptr") for _, v, _ in given), device, stream)
+    for name, v, ch in given:
+        A.check(name, v, shape + (ch,) if ch > 1 else shape)
+    res = {"colour": A.new(shape + (3,)), "variance": A.new(shape)}
+    ptrs = [A.address(v) for v in (colour, normal, albedo, moments, count, res["colour"], res["variance"])]
+    H, W = shape
+    if not A.on_gpu:
+        if lib().rtHipDenoiseVariance(device, W, H, *ptrs, C.byref(p)) != 0:
+            raise RuntimeError("rtHipDenoiseVariance failed: " + last_error())
+        return res
+    nbytes = lib().rtHipVarianceScratchBytes(W, H)
+    if nbytes == 0:
+        raise ValueError(f"denoise_variance: a {W} x {H} image is not 1..2^27 pixels")
+    scratch = A.new(nbytes, np.uint8)
+    if lib().rtHipDenoiseVarianceDevice(device, W, H, *ptrs, A.address(scratch), nbytes, C.byref(p), A.stream_arg()) != 0:
+        raise RuntimeError("rtHipDenoiseVarianceDevice failed: " + last_error())
+    A.done([v for _, v, _ in given] + list(res.values()) + [scratch])
     return res
 
 
@@ -1147,6 +1293,23 @@ class ResidentScene:
         self._check(lib().rtHipSceneTemporal(self.handle, C.byref(p), C.byref(d) if d is not None else None, _ptr(colour), _ptr(planes[0]),
                                              _ptr(planes[1]), _ptr(planes[2]), _ptr(count)), "rtHipSceneTemporal")
         return {"colour": colour, "planes": planes, "count": count}
+
+    def temporal_variance(self, filter: Optional[dict] = None, **params) -> dict:
+        """temporal() with the luminance moments carried along (rtHipSceneTemporalVariance): also returns "variance" [H, W] f32.
+        `filter`: a dict of raytrace.denoise_variance's keywords ({} for the defaults) runs the variance-guided filter on the accumulation
+        (needs set_passes(normal=True, albedo=True)); "colour" and "planes" are then C^K and "variance" is V^K, otherwise the accumulation
+        and its temporal variance.  The history keeps the unfiltered colour; a temporal() between two calls makes the next one start again."""
+        p = temporal_params(**params)
+        v = variance_params(**filter) if filter is not None else None
+        sc = self.scene
+        colour = np.empty((sc.height, sc.width, 3), np.float32)
+        planes = [np.empty((sc.height, sc.width), np.uint16) for _ in range(3)]
+        count = np.empty((sc.height, sc.width), np.float32)
+        variance = np.empty((sc.height, sc.width), np.float32)
+        self._check(lib().rtHipSceneTemporalVariance(self.handle, C.byref(p), C.byref(v) if v is not None else None, _ptr(colour),
+                                                     _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), _ptr(count), _ptr(variance)),
+                    "rtHipSceneTemporalVariance")
+        return {"colour": colour, "planes": planes, "count": count, "variance": variance}
 
     def reset_temporal(self) -> None:
         """Forgets the history of temporal() (rtHipSceneTemporalReset): the next call returns the frame itself with count 1."""
