@@ -992,7 +992,7 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
 
 /* TEST / TUNING ONLY.  The library reads no environment variables (a plugin host's environment must not be able to slow frames
  * down, make them redo themselves or fail); every tuning value and every fault injector of the tests is set here, process-wide,
- * and applies to scenes built afterwards.  Keys (rt_api.cpp, struct Tuning): "reset" (all defaults), "stage_mb", "extra_factor",
+ * and applies to scenes built afterwards.  Keys (rt_host.h, struct Tuning): "reset" (all defaults), "stage_mb", "extra_factor",
  * "state_mb", "groups", "lookahead", "seg0".."seg4", "seg_rays0".."seg_rays3", "fast_quotient", "spin_limit", "append_rays", "ordered_first", "extra_factor",
  * "slice_rays", "small_slices", "group_rays", "blocking", "batch_plan", "pipeline", "timing", "cache", "logic_class" (0: every scene's
  * paths run on the general logic kernel; 1, the default: on the kernel of the scene's path class), "dead_shadow" (0: trace every

@@ -4,27 +4,17 @@
 // recompiles the kernel and enqueues tiles x samples NDRanges per call (raytrace.c:330-556), this one uploads the
 // scene once into HBM, reshapes it on the device (rt_prepare_triangles) and issues ONE launch per frame and GPU.
 // There is no CPU fallback: without a HIP device every entry point that would compute fails with an error text.
-#include "raytrace_hip.h"
-#include "rt_device.h"
-#include "rt_camera_move.h"
-#include "rt_geometry_move.h"
+#include "rt_host.h"
 #include "rt_build_shared.h"
 
-#include <hip/hip_runtime_api.h>
-
-#include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <unordered_map>
 #include <chrono>
-#include <vector>
+
+using namespace rthost;
 
 extern "C" hipError_t rtk_launch_trace(const RtDevScene *scene, int counted, hipStream_t stream);
 extern "C" hipError_t rtk_launch_prepare(uint32_t triangleCount, const void *vertex, const void *triIndex, const void *triMaterial,
@@ -57,25 +47,6 @@ extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays
 extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream);
 extern "C" hipError_t rtw_launch_motion_mark(const float *triRec, void *ref, uint32_t triangles, hipStream_t stream);
 extern "C" hipError_t rtw_launch_motion(const RtDevScene *scene, const RtMotionArgs *args, hipStream_t stream);
-extern "C" hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
-                                            const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
-                                            const uint32_t *histTriangle, float *outColour, float *outCount, float maxHistory,
-                                            float depthTolerance, hipStream_t stream);
-extern "C" hipError_t rtt_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount,
-                                        const uint16_t *tileBuf, float *colour, hipStream_t stream);
-extern "C" hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
-// rt_variance.hip
-extern "C" hipError_t rtv_launch_moments(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
-                                         const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
-                                         const uint32_t *histTriangle, const float *histMoments, float *outColour, float *outCount,
-                                         float *outMoments, float *outVariance, float maxHistory, float depthTolerance, hipStream_t stream);
-extern "C" hipError_t rtv_launch_estimate(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo,
-                                          const float *moments, const float *count, float spatialBelow, float ia, uint32_t E, void *s0,
-                                          void *g0, void *g1, hipStream_t stream);
-extern "C" hipError_t rtv_launch_iteration(uint32_t W, uint32_t H, int h, float ls, float floor_, float ia, uint32_t E, const void *sin,
-                                           void *il, const void *g0, const void *g1, void *sout, hipStream_t stream);
-extern "C" hipError_t rtv_launch_output(uint32_t n, const void *s, float *out, float *outVariance, uint16_t *outR, uint16_t *outG,
-                                        uint16_t *outB, hipStream_t stream);
 extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
                                            hipStream_t stream);
 extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
@@ -85,19 +56,11 @@ extern "C" hipError_t rtw_launch_bake_finish(uint32_t texels, const uint32_t *wi
                                              uint32_t *tri, hipStream_t stream);
 extern "C" hipError_t rtw_launch_bake_dilate(uint32_t W, uint32_t H, const float *src, float *dst, uint32_t last, hipStream_t stream);
 
-extern "C" hipError_t rtd_launch_guides(uint32_t n, const float *colour, const float *normal, const float *albedo, void *c0, void *g0, void *g1,
-                                        hipStream_t stream);
-extern "C" hipError_t rtd_launch_iteration(uint32_t W, uint32_t H, int h, float ic, float ia, uint32_t E, const void *cin, const void *g0,
-                                           const void *g1, void *cout, hipStream_t stream);
-extern "C" hipError_t rtd_launch_output(uint32_t n, const void *c, float *out, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
-extern "C" hipError_t rtd_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount, const uint16_t *tileBuf,
-                                        const float *surf, float S, float *colour, float *normal, float *albedo, hipStream_t stream);
-
 namespace {
-
 thread_local std::string g_error;
+}
 
-int fail(const char *fmt, ...)
+int rthost::fail(const char *fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -108,48 +71,8 @@ int fail(const char *fmt, ...)
     return -1;
 }
 
-#define HIP_OK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail("%s failed: %s", #expr, hipGetErrorString(e_));              \
-    } while (0)
+namespace {
 
-// Tuning values and test hooks.  The library reads NO environment variables: a plugin host's environment must not be able to
-// make frames slower, redo themselves or fail.  Everything here is set through rtHipTune() (include/raytrace_hip.h, test / tuning
-// entry point; the Python stub maps RT_* variables of ITS process onto it for the sweep scripts) and applies to scenes built
-// afterwards.
-struct Tuning {
-    uint32_t stageMb = 32;          // size of each of the two pinned staging buffers of an upload
-    uint32_t extraFactor = 6;       // region B of the entry arrays (further segments of cut rays), in units of the path capacity
-    uint64_t stateMb = 0;           // path-state budget per sample batch (0 = 24 GB, never more than a third of free memory); tests force several batches
-    uint32_t groups = 1;            // concurrent tile groups per instance (measured: no gain once rays are cut into segments)
-    uint32_t lookAhead = 1;         // 0: one ray in flight per path
-    uint32_t segLen[5] = { 4096u, 384u, 96u, 64u, 16u }; // aimed-at cell visits per segment for rounds with >= segRays[0] | [1] | [2] | [3] | fewer rays
-    uint32_t segRays[4] = { 700000u, 300000u, 100000u, 30000u };
-    uint32_t fastQuotient = 1;
-    uint32_t spinLimit = 16384;     // a ray makes at most 766 cell visits = 154 walk phases; lowered by the test of the guard's error path
-    uint32_t appendRays = 300000;   // later rounds with fewer rays are not ordered: the trace kernel plans and cuts their rays itself (RtRoundMode)
-    uint32_t orderedFirst = 1;      // 0: round 1 follows the same rule (tests: the trace kernel's planning on dense rounds)
-    uint32_t sliceRays = 0;         // rounds with fewer rays use smallSlices queue slices per kind instead of RT_WF_SHARDS (off: a round's appends want
-                                    // many counters -- 16 slices cost the logic kernel of a 58 k-ray round 17 us -- and the trace kernel packs its pieces anyway)
-    uint32_t smallSlices = 16;
-    uint32_t groupRays = 0;         // rays per workgroup of the trace kernel in rounds that are not ordered (0 = by segment length)
-    uint32_t blocking = 0;          // 1: every frame watches its queue (no launch plan)
-    uint32_t planRounds = 0;        // test hook: planned frames issue at most this many rounds, so that the too-short-plan path runs
-    uint32_t planGridTiny = 0;      // test hook: planned trace grids of one workgroup, so that the too-small-grid path runs
-    uint32_t pipeline = RT_HIP_PIPELINE_WAVEFRONT;
-    uint32_t timing = 0;            // 1: where the time of a scene build / a RaytraceAll call goes (stderr)
-    uint32_t virtualDevices = 0;    // test hook: the all-GPUs id deals the tiles over this many instances on the devices that are there
-    uint32_t cache = 1;             // 0: RaytraceAll builds and frees per call, like the reference
-    uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
-    uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
-    uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
-    uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
-    uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
-    uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
-    uint32_t aoSamples = 1u << 20;  // pixel samples per chunk of the ambient occlusion calls (32 bytes each of scene-owned scratch)
-    uint32_t bakeTexels = 1u << 20; // texels per chunk of the ambient occlusion bake (32 bytes each of scene-owned scratch)
-};
 // Read at the entry points only (scene create, RaytraceAll, the two public device builders): a build works from one snapshot.
 Tuning g_tune;
 std::mutex g_tuneMutex;
@@ -158,340 +81,6 @@ Tuning tuning() { std::lock_guard<std::mutex> lock(g_tuneMutex); return g_tune; 
 } // namespace
 
 rtbuild::DeviceBuildTuning rtbuild::device_build_tuning() { const Tuning t = tuning(); return { t.buildKeyCap, t.buildListLimit }; }
-
-namespace {
-
-// Device scratch of a scene build: freed when the scope ends, whichever way it ends.
-struct DevScratch {
-    std::vector<void *> blocks;
-    ~DevScratch() { for (void *p : blocks) (void)hipFree(p); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) blocks.push_back(*out);
-        return e;
-    }
-};
-
-// Host-to-device copies go through two pinned buffers (hipHostMalloc once per scene, RT_HIP_STAGE_MB each, default 32): the
-// caller's arrays are pageable (new[] in render.cpp:1089-1123), and a pageable hipMemcpy is a synchronous bounce through the
-// runtime's own small staging area.  Here the CPU fills one buffer (several threads for big pieces) while the DMA engine
-// drains the other; copy() returns when the source has been read completely, so callers may free it at once.
-struct Stager {
-    hipStream_t stream = nullptr;
-    char *buf[2] = { nullptr, nullptr };
-    hipEvent_t done[2] = { nullptr, nullptr };
-    bool used[2] = { false, false };
-    size_t size = 0;
-    int next = 0;
-    // Pinning 2 x 32 MB costs 15-25 ms, more than the rest of an instance's build when its shared parts are copied from another
-    // instance: the buffers are taken when the first host array needs them and go back to a process-wide pool, not to the driver.
-    struct Pool {
-        std::mutex lock;
-        std::vector<std::pair<char *, size_t>> idle;
-        char *take(size_t bytes)
-        {
-            {
-                std::lock_guard<std::mutex> g(lock);
-                for (size_t i = 0; i < idle.size(); ++i)
-                    if (idle[i].second == bytes) { char *p = idle[i].first; idle.erase(idle.begin() + i); return p; }
-            }
-            char *p = nullptr;
-            if (hipHostMalloc((void **)&p, bytes, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            return p;
-        }
-        void give(char *p, size_t bytes)
-        {
-            std::lock_guard<std::mutex> g(lock);
-            if (idle.size() < 8) idle.emplace_back(p, bytes);
-            else (void)hipHostFree(p);
-        }
-    };
-    static Pool &pool() { static Pool *p = new Pool(); return *p; } // (never destroyed: buffers may come back during process exit)
-    int init(hipStream_t st, const Tuning &T)
-    {
-        stream = st;
-        size = (size_t)std::min<uint32_t>(std::max<uint32_t>(T.stageMb, 1u), 4096u) << 20;
-        for (int i = 0; i < 2; ++i) HIP_OK(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
-        return 0;
-    }
-    static void fill(char *dst, const char *src, size_t n)
-    {
-        const size_t piece = (size_t)4 << 20;
-        if (n < 2 * piece) { memcpy(dst, src, n); return; }
-        const size_t parts = std::min<size_t>(8, n / piece);
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < parts; ++t) pool.emplace_back([=] { memcpy(dst + n * t / parts, src + n * t / parts, n * (t + 1) / parts - n * t / parts); });
-        memcpy(dst, src, n / parts);
-        for (auto &th : pool) th.join();
-    }
-    // is `p` device memory (a scene description may hand over arrays that are already on the GPU)?
-    static bool on_device(const void *p)
-    {
-        hipPointerAttribute_t at;
-        memset(&at, 0, sizeof at);
-        if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; } // (plain host memory: "invalid value")
-        return at.type == hipMemoryTypeDevice;
-    }
-    hipError_t copy(void *dst, const void *src, size_t bytes)
-    {
-        if (bytes && on_device(src)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream); // no staging: HBM to HBM
-        for (size_t off = 0; off < bytes;) {
-            const size_t n = std::min(size, bytes - off);
-            const int i = next;
-            next ^= 1;
-            if (used[i]) { const hipError_t e = hipEventSynchronize(done[i]); if (e != hipSuccess) return e; }
-            if (!buf[i] && !(buf[i] = pool().take(size))) return hipErrorOutOfMemory;
-            fill(buf[i], (const char *)src + off, n);
-            hipError_t e = hipMemcpyAsync((char *)dst + off, buf[i], n, hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess) return e;
-            e = hipEventRecord(done[i], stream);
-            if (e != hipSuccess) return e;
-            used[i] = true;
-            off += n;
-        }
-        return hipSuccess;
-    }
-    hipError_t drain() // every copy so far has left its staging buffer; the buffers go back to the pool (the next instance's build takes them)
-    {
-        for (int i = 0; i < 2; ++i) {
-            if (used[i]) { const hipError_t e = hipEventSynchronize(done[i]); if (e != hipSuccess) return e; used[i] = false; }
-            if (buf[i]) { pool().give(buf[i], size); buf[i] = nullptr; }
-        }
-        return hipSuccess;
-    }
-    void destroy()
-    {
-        for (int i = 0; i < 2; ++i) {
-            if (done[i]) { if (used[i]) (void)hipEventSynchronize(done[i]); (void)hipEventDestroy(done[i]); done[i] = nullptr; }
-            if (buf[i]) { pool().give(buf[i], size); buf[i] = nullptr; }
-        }
-    }
-};
-
-enum { PART_FIXED = 0, PART_CAMERA, PART_GEOMETRY, PART_GRID, PART_MATERIALS, PART_LIGHTS, PART_WAVEFRONT, PART_COUNT };
-
-} // namespace
-
-struct rtHipScene {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    RtDevScene dev{};
-    // Device allocations by PART (tiles + outputs | camera lists | geometry | grid | materials | lights | path state): the drop-in
-    // layer's cache replaces the parts whose inputs changed between two RaytraceAll calls and keeps the others in HBM.
-    std::vector<void *> partAllocs[PART_COUNT];
-    std::vector<uint64_t> partSizes[PART_COUNT]; // bytes of every allocation (a peer instance copies the shared parts device to device)
-    uint64_t partBytes[PART_COUNT] = { 0 };
-    int curPart = PART_FIXED;
-    Stager stager;
-    uint32_t *prepErr = nullptr;   // device word: RT_PREP_ERR_* bits raised by the validation kernels
-    uint64_t camListSize = 0;
-    uint64_t gridListSize = 0;      // entries of the grid list = pair records of the dense view
-    uint32_t gridListSizeHint = 0;  // scene description with device arrays: scenePixelTriangleListStart[256^3], fetched by scene_build
-    bool haveGridListSize = false;
-    bool wfMultiLight = false;     // what the path-state buffers were sized for
-    bool classMaterials = false, classLights = false; // the materials part / the lights part admit the opaque-diffuse path class
-    uint64_t bytes = 0;
-    std::vector<cl_uint> tileIds;
-    uint32_t width = 0, height = 0, tilesX = 0;
-    // kernel timing: one event pair per launch since the last rtHipKernelTime
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    size_t eventsUsed = 0;
-    // wavefront pipeline (rt_wavefront.hip)
-    int pipeline = RT_HIP_PIPELINE_WAVEFRONT;
-    // The instance's tile slots are cut into contiguous GROUPS, each a view of `dev` (its own slice of tileIds, camStart/End,
-    // tileBuf) with its own path state and stream.  A frame runs the groups concurrently: while one group is in a phase that
-    // cannot fill the GPU (a round with few rays, a host read-back), the others' kernels do.  Per pixel nothing changes.
-    struct Group {
-        RtDevScene dev{};
-        RtWavefront wf{};
-        hipStream_t stream = nullptr;   // groups 1.. ; group 0 runs on the caller's stream
-        hipEvent_t done = nullptr;
-        uint32_t logicBlocks = 1, traceBlocks = 1, queueBlocks = 1;
-        uint32_t *hostCount = nullptr;  // pinned: queue length read back between round chunks
-        uint32_t *hostStatus = nullptr; // pinned + mapped: RT_WF_STATUS_* words the kernels write (rt_device.h)
-        bool ctlClean = false;          // the batch before was a planned one: wf_status_kernel left the control words zeroed
-        uint32_t rounds = 0;
-        uint32_t slot0 = 0, slot1 = 0;  // this group's range of the instance's tile slots
-        // launch plan (render_wavefront): what the last discovery frame needed
-        uint32_t roundsNeeded = 0;
-        // per round: rays (entries in region A), the longest queue slice, entries in region B -- the maximum over the watched batches
-        // rays of the round, and -- an ordered round -- the further segments of its cut rays under the cut it was logged with
-        struct RoundPlan { uint32_t rays = 0, extra = 0, extraSegLen = 0; };
-        uint4 *hostLog = nullptr;       // pinned + mapped: RtWavefront::roundLog, written by the kernels, read by the host after a sync
-        RoundPlan plan[RT_WF_ROUND_LOG], planNext[RT_WF_ROUND_LOG];
-        std::vector<RtRoundMode> modes; // how the rounds of the batch being issued are laid out (modes[r] is decided when logic(r-1) is launched)
-        uint64_t guessRays = 0;         // watched batches: what the next round is assumed to hold
-    };
-    std::vector<Group> groups;
-    hipEvent_t forkEvent = nullptr;
-    uint32_t samplesPerBatch = 1;
-    uint32_t planRounds = 0;   // rounds a planned frame issues per batch; 0 = no plan yet (the next frame is a discovery frame)
-    bool blocking = false;     // every frame watches the queue (no plan)
-    Tuning tune;               // the tuning values this scene was built with (rtHipTune)
-    bool unverified = false;   // planned frames were issued since the last frame_finish()
-    hipStream_t lastStream = nullptr; // where the last frame was issued
-    std::atomic<float> *progress = nullptr; // drop-in layer: where finished sample batches are reported (GetProgress, raytrace.c:566-587)
-    float progressBase = 0.f, progressSpan = 0.f;
-    // per-stage device time of the frames since the last query: [primary, logic, trace, accum, sort]
-    struct StageEvent { int stage; hipEvent_t a, b; };
-    std::vector<StageEvent> stageEvents;
-    size_t stageEventsUsed = 0;
-    bool stageTiming = false;
-    uint64_t roundsLast = 0;
-    // render passes (rtHipScenePasses): RT_HIP_PASS_* bits, the pass buffer [slot][RT_PASS_WORDS][128*128] (rt_device.h) while ALPHA,
-    // DEPTH or TRIANGLE is on, and the surface buffer [slot][RT_SURF_WORDS][128*128] while NORMAL or ALBEDO is on
-    uint32_t passMask = 0;
-    uint32_t *passBuf = nullptr;
-    uint64_t passBytes = 0;
-    float *surfBuf = nullptr;
-    uint64_t surfBytes = 0;
-    // ray queries through host arrays (rtHipSceneIntersect): one chunk of hits | rays | excluded ids on the device and a pinned host buffer
-    // of the same layout from the staging pool, both made on first use
-    uint32_t queryRays = 0;
-    char *queryDev = nullptr, *queryHost = nullptr;
-    uint64_t queryBytes = 0;
-    // denoiser scratch of rtHipSceneDenoise (gathered inputs, filter scratch, outputs), made on first use while NORMAL and ALBEDO are on
-    char *denoiseBuf = nullptr;
-    uint64_t denoiseBytes = 0;
-    // device time of the last rtHipSceneDenoise: events before the gather, after it, after the guides and after the output
-    hipEvent_t denoiseEv[4] = {};
-    float denoiseMs[3] = {};
-    // ambient occlusion scratch (rtHipSceneAmbientOcclusion*), made on first use: the pixel counters, then one chunk of primary hits; the
-    // event marks the end of the last call that used it, so that a call on another stream waits for it on the device
-    char *aoBuf = nullptr;
-    uint64_t aoBytes = 0;
-    uint32_t aoChunk = 0;
-    hipEvent_t aoDone = nullptr;
-    // ambient occlusion bake scratch (rtHipSceneBakeAmbientOcclusion*), made on first use and grown for a larger map: winners, counters
-    // and a second value plane for W*H texels, the big list, one chunk of texels; the event as above
-    char *bakeBuf = nullptr;
-    uint64_t bakeBytes = 0, bakeTexels = 0;
-    uint32_t bakeChunk = 0;
-    hipEvent_t bakeDone = nullptr;
-    // motion vectors (rtHipSceneMotion*): the reference of the last rtHipSceneMotionMark -- its camera, and a, ab, ac of every triangle in
-    // storage of its own (RT_MOTION_REF_ROWS float4 per triangle), made by the first mark -- and the host entry point's staging (tile-major
-    // motion | t | prevT | triangle, 20 bytes per tile pixel), made on its first use.  marked: the end of the last mark on the scene's
-    // stream; done: the end of the last call that read the reference or used the staging, on whatever stream it ran.
-    struct Motion {
-        bool have = false;
-        rtHipCamera cam{};
-        uint32_t triangles = 0;
-        char *ref = nullptr;
-        uint64_t refBytes = 0;
-        char *stage = nullptr;
-        uint64_t stageBytes = 0;
-        hipEvent_t marked = nullptr, done = nullptr;
-    } motion;
-    // temporal accumulation (rtHipSceneTemporal), made on its first call in one block: two history sets (colour | count | t | triangle;
-    // `cur` is the one the next call reads), this frame's motion and prevT, the gathered colour and the u16 output planes.  valid: the
-    // history set `cur` holds a frame (false after a reset: the next call clears its counts first).
-    // rtHipSceneTemporalVariance adds a block of its own on its first call: two sets of moments (they change places with the history
-    // sets), the variance plane and the filter's il plane.  momentsValid: the moments set `cur` belongs to the history set `cur` (false
-    // after an rtHipSceneTemporal, which does not write them).
-    struct Temporal {
-        char *buf = nullptr;
-        uint64_t bytes = 0;
-        int cur = 0;
-        bool valid = false;
-        char *momentsBuf = nullptr;
-        uint64_t momentsBytes = 0;
-        bool momentsValid = false;
-        hipEvent_t ev[5] = {};
-        float ms[4] = {};
-    } temporal;
-    // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
-    // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
-    // and the sets change places at its end.  listCap: entries each list holds.  log: triangles per thread, per workgroup, entries of the
-    // last move; ms: device time of its count stage and of its fill stage.
-    struct CamMove {
-        char *scratch = nullptr;
-        uint64_t scratchBytes = 0;
-        uint32_t *start[2] = {}, *end[2] = {}, *list[2] = {};
-        uint64_t listCap[2] = {};
-        int live = -1; // the set in use; -1 while the scene still renders from the lists it was created with
-        RtCamMoveArgs args{};
-        hipEvent_t ev[4] = {};
-        uint64_t log[3] = {};
-        double ms[2] = {};
-    } cam;
-    // geometry updates (rtHipSceneSetGeometry), made by the first update: TWO sets of everything the kernels read of the shape (triangle
-    // records, shading rows, planes, cell table, grid starts and list, occupancy words, block table, pair records) -- an update builds into
-    // the set the frames do not read and the sets change places at its end; the parts the scene was created with are freed after the
-    // first update.  pairCap: entries the set's list and pair records hold.  The rest is build scratch that stays: the grid build's space,
-    // staging for host arrays, two index arrays (the retained one and the one being checked), the pair order.
-    struct GeoMove {
-        struct Set {
-            float *triRec = nullptr, *triShade = nullptr, *boxMin = nullptr, *pairRec = nullptr;
-            uint8_t *cellLut = nullptr;
-            uint32_t *gridStart = nullptr, *gridList = nullptr, *sparse = nullptr;
-            unsigned long long *gridBits = nullptr;
-            uint64_t listCap = 0, pairCap = 0; // in bytes
-        } set[2];
-        int live = -1;      // the set in use; -1 while the scene still renders from the parts it was created with
-        RtGridSpace space{};
-        char *vertexBuf = nullptr, *normalBuf = nullptr, *index[2] = {}, *material = nullptr, *pairOrder = nullptr, *pairInfo = nullptr, *denseTmp = nullptr;
-        uint64_t vertexCap = 0, normalCap = 0, indexCap[2] = {}, materialCap = 0, orderCap = 0, infoCap = 0, denseCap = 0; // in bytes
-        int retained = -1;  // which index array the last successful update left; -1: none (creation drops the index array)
-        hipEvent_t ev[5] = {};
-        uint64_t log[6] = {}; // per thread, per workgroup, attempts, pairs, camera entries, allocated
-        double ms[4] = {};
-    } geo;
-
-    template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
-    {
-        void *p = nullptr;
-        const uint64_t n = count ? count : 1;
-        HIP_OK(hipMalloc(&p, n * sizeof(T)));
-        partAllocs[curPart].push_back(p);
-        partSizes[curPart].push_back(n * sizeof(T));
-        partBytes[curPart] += n * sizeof(T);
-        bytes += n * sizeof(T);
-        if (count) {
-            if (!src) return fail("%s: null pointer with %llu elements", what, (unsigned long long)count);
-            HIP_OK(stager.copy(p, src, count * sizeof(T)));
-        }
-        *dst = (const T *)p;
-        return 0;
-    }
-    template <class T> int alloc(uint64_t count, T **dst)
-    {
-        void *p = nullptr;
-        const uint64_t n = count ? count : 1;
-        HIP_OK(hipMalloc(&p, n * sizeof(T)));
-        partAllocs[curPart].push_back(p);
-        partSizes[curPart].push_back(n * sizeof(T));
-        partBytes[curPart] += n * sizeof(T);
-        bytes += n * sizeof(T);
-        *dst = (T *)p;
-        return 0;
-    }
-    void release_part(int part)
-    {
-        if (partAllocs[part].empty()) return;
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void *p : partAllocs[part]) (void)hipFree(p);
-        partAllocs[part].clear();
-        partSizes[part].clear();
-        bytes -= partBytes[part];
-        partBytes[part] = 0;
-    }
-    // looks at the device-side validation word (after the caller's stream synchronisation)
-    int check_prep()
-    {
-        uint32_t err = 0;
-        HIP_OK(hipMemcpy(&err, prepErr, 4, hipMemcpyDeviceToHost));
-        if (!err) return 0;
-        HIP_OK(hipMemset(prepErr, 0, 4));
-        return fail("scene rejected (0x%x):%s%s%s%s%s%s", err,
-                    (err & RT_PREP_ERR_TRI_INDEX) ? " a triangle references a vertex that does not exist;" : "",
-                    (err & RT_PREP_ERR_TRI_MATERIAL) ? " a triangle uses a material >= materialCount;" : "",
-                    (err & RT_PREP_ERR_CAM_ENTRY) ? " a camera list entry is not a triangle;" : "",
-                    (err & RT_PREP_ERR_CAM_RANGE) ? " a camera list range exceeds the list size;" : "",
-                    (err & RT_PREP_ERR_GRID_MONOTONE) ? " scenePixelTriangleListStart is not monotone;" : "",
-                    (err & RT_PREP_ERR_GRID_ENTRY) ? " a grid list entry is not a triangle;" : "");
-    }
-};
 
 namespace {
 
@@ -1259,10 +848,12 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
     return 0;
 }
 
+} // namespace
+
 // After the caller's synchronisation of `st`: were the planned frames since the last call complete?  If not, the LAST frame
 // is rendered again with the queue watched (earlier incomplete frames were overwritten by it anyway).  *redone (optional)
 // = 1 when that happened: whatever was enqueued behind the incomplete frame saw unfinished tiles.
-int frame_finish(rtHipScene *sc, hipStream_t st, int *redone)
+int rthost::frame_finish(rtHipScene *sc, hipStream_t st, int *redone)
 {
     if (redone) *redone = 0;
     if (!sc->unverified) return 0;
@@ -1290,6 +881,44 @@ int frame_finish(rtHipScene *sc, hipStream_t st, int *redone)
     HIP_OK(hipStreamSynchronize(st));
     return 0;
 }
+
+// A device pointer a kernel may read or write `bytes` from: device memory of `device`, 16-byte aligned where the kernel loads 16 bytes at
+// a time, and inside one allocation.  A host pointer must never reach a kernel: its fault takes the whole GPU down.
+// `whose` names what lives on `device` in the error text ("the scene").  Declared in rt_host.h: the filters (rt_filters.cpp) call it too.
+int rthost::query_pointer_ok(int device, const char *whose, const void *p, uint64_t bytes, uint64_t align, const char *what)
+{
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("%s %p is not device memory", what, p); }
+    if (at.type != hipMemoryTypeDevice) return fail("%s %p is not device memory (memory type %d)", what, p, (int)at.type);
+    if (at.device != device) return fail("%s %p is memory of device %d, %s is on device %d", what, p, at.device, whose, device);
+    if ((uintptr_t)p % align) return fail("%s %p is not %llu-byte aligned", what, p, (unsigned long long)align);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return fail("%s %p: no allocation found", what, p); }
+    if ((uint64_t)((const char *)p - (const char *)base) + bytes > (uint64_t)size)
+        return fail("%s %p: %llu bytes reach past the end of its allocation", what, p, (unsigned long long)bytes);
+    return 0;
+}
+
+// Enqueues the motion pass (rtHipSceneMotion*) on `st`, after the mark and after the last call's use of the reference and the staging.  Declared in rt_host.h: the temporal
+// calls of rt_filters.cpp run it too.
+int rthost::motion_run(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, bool rowMajor, hipStream_t st)
+{
+    rtHipScene::Motion &M = sc->motion;
+    RtMotionArgs A;
+    for (int i = 0; i < 3; ++i) { A.eye[i] = M.cam.eye[i]; A.topLeft[i] = M.cam.eyeToTopLeft[i]; A.lr[i] = M.cam.leftToRight[i]; A.tb[i] = M.cam.topToBottom[i]; }
+    A.ref = (const float4 *)M.ref;
+    A.motion = (float *)motion; A.t = (float *)t; A.prevT = (float *)prevT; A.triangle = (uint32_t *)triangle;
+    A.rowMajor = rowMajor ? 1u : 0u; A.fastQuotient = sc->tune.fastQuotient ? 1u : 0u;
+    if (st != sc->stream) HIP_OK(hipStreamWaitEvent(st, M.marked, 0));
+    if (!rowMajor) HIP_OK(hipStreamWaitEvent(st, M.done, 0)); // (the staging)
+    HIP_OK(rtw_launch_motion(&sc->dev, &A, st));
+    HIP_OK(hipEventRecord(M.done, st));
+    return 0;
+}
+
+namespace {
 
 rtHipScene *scene_create(int device, const rtHipSceneDesc *desc, const cl_uint *tileIds, cl_uint tileCount, const rtHipScene *like, const Tuning &tune)
 {
@@ -1616,9 +1245,8 @@ int rtHipSetPipeline(rtHipScene *sc, int pipeline)
     return 0;
 }
 
-// Which render pass bits need which buffer
+// Which render pass bits need the pass buffer (RT_SURF_BUF_BITS: rt_host.h)
 #define RT_PASS_BUF_BITS (RT_HIP_PASS_ALPHA | RT_HIP_PASS_DEPTH | RT_HIP_PASS_TRIANGLE)
-#define RT_SURF_BUF_BITS (RT_HIP_PASS_NORMAL | RT_HIP_PASS_ALBEDO)
 
 // One of the two pass buffers: made (zeroed) when `want` and absent, freed when not `want` -- after a sync, frames in flight may still
 // write it.  Counted in rtHipSceneBytes.
@@ -1867,25 +1495,6 @@ int rtHipReadbackSurfacePasses(rtHipScene *sc, cl_float *normal, cl_float *albed
     return 0;
 }
 
-// A device pointer a kernel may read or write `bytes` from: device memory of `device`, 16-byte aligned where the kernel loads 16 bytes at
-// a time, and inside one allocation.  A host pointer must never reach a kernel: its fault takes the whole GPU down.
-// `whose` names what lives on `device` in the error text ("the scene").
-static int query_pointer_ok(int device, const char *whose, const void *p, uint64_t bytes, uint64_t align, const char *what)
-{
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("%s %p is not device memory", what, p); }
-    if (at.type != hipMemoryTypeDevice) return fail("%s %p is not device memory (memory type %d)", what, p, (int)at.type);
-    if (at.device != device) return fail("%s %p is memory of device %d, %s is on device %d", what, p, at.device, whose, device);
-    if ((uintptr_t)p % align) return fail("%s %p is not %llu-byte aligned", what, p, (unsigned long long)align);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return fail("%s %p: no allocation found", what, p); }
-    if ((uint64_t)((const char *)p - (const char *)base) + bytes > (uint64_t)size)
-        return fail("%s %p: %llu bytes reach past the end of its allocation", what, p, (unsigned long long)bytes);
-    return 0;
-}
-
 int rtHipSceneIntersectDevice(rtHipScene *sc, const void *rays, const void *excluded, cl_uint count, void *hits, void *stream)
 {
     if (!sc) return fail("null scene");
@@ -2069,22 +1678,6 @@ static int motion_check(const rtHipScene *sc, const void *motion, const void *t,
     return 0;
 }
 
-// Enqueues the pass on `st`, after the mark and after the last call's use of the reference and the staging.
-static int motion_run(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, bool rowMajor, hipStream_t st)
-{
-    rtHipScene::Motion &M = sc->motion;
-    RtMotionArgs A;
-    for (int i = 0; i < 3; ++i) { A.eye[i] = M.cam.eye[i]; A.topLeft[i] = M.cam.eyeToTopLeft[i]; A.lr[i] = M.cam.leftToRight[i]; A.tb[i] = M.cam.topToBottom[i]; }
-    A.ref = (const float4 *)M.ref;
-    A.motion = (float *)motion; A.t = (float *)t; A.prevT = (float *)prevT; A.triangle = (uint32_t *)triangle;
-    A.rowMajor = rowMajor ? 1u : 0u; A.fastQuotient = sc->tune.fastQuotient ? 1u : 0u;
-    if (st != sc->stream) HIP_OK(hipStreamWaitEvent(st, M.marked, 0));
-    if (!rowMajor) HIP_OK(hipStreamWaitEvent(st, M.done, 0)); // (the staging)
-    HIP_OK(rtw_launch_motion(&sc->dev, &A, st));
-    HIP_OK(hipEventRecord(M.done, st));
-    return 0;
-}
-
 int rtHipSceneMotionDevice(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, void *stream)
 {
     if (motion_check(sc, motion, t, prevT, triangle) != 0) return -1;
@@ -2242,636 +1835,6 @@ int rtHipSceneBakeAmbientOcclusion(rtHipScene *sc, const rtHipBakeParams *p, cl_
     if (triangle) HIP_OK(hipMemcpyAsync(triangle, sc->bakeBuf, bytes, hipMemcpyDeviceToHost, sc->stream)); // (the winners' plane)
     HIP_OK(hipStreamSynchronize(sc->stream));
     return 0;
-}
-
-// ---- denoiser (include/raytrace_hip.h, "DENOISER"; kernels in rt_denoise.hip) ------------------------------------------------
-// Filter scratch of a W x H image: C^i and C^(i+1) as float4 (ping-pong), then the guides G0 = (n^, z) and G1 = (albedo, 0) as float4.
-#define RT_DENOISE_MAX_PIXELS (1ull << 27)
-#define RT_DENOISE_SCRATCH_PER_PIXEL 64ull
-
-void rtHipDenoiseDefaults(rtHipDenoiseParams *p)
-{
-    if (!p) return;
-    p->iterations = 4;
-    p->colourInvSigma2 = 4.0f;
-    p->albedoInvSigma2 = 100.0f;
-    p->normalPowerLog2 = 7;
-}
-
-static int denoise_params_ok(const rtHipDenoiseParams *p)
-{
-    if (!p) return fail("denoise: null parameters");
-    if (p->iterations > 12) return fail("denoise: iterations %u is not in 0..12", p->iterations);
-    if (!(std::isfinite(p->colourInvSigma2) && p->colourInvSigma2 >= 0.f))
-        return fail("denoise: colourInvSigma2 %g is not finite and >= 0", (double)p->colourInvSigma2);
-    if (!(std::isfinite(p->albedoInvSigma2) && p->albedoInvSigma2 >= 0.f))
-        return fail("denoise: albedoInvSigma2 %g is not finite and >= 0", (double)p->albedoInvSigma2);
-    if (p->normalPowerLog2 > 10) return fail("denoise: normalPowerLog2 %u is not in 0..10", p->normalPowerLog2);
-    float ic = p->colourInvSigma2; // what the last iteration uses: ic multiplied by 4.0f K-1 times in fp32
-    for (uint32_t i = 1; i < p->iterations; ++i) ic = ic * 4.0f;
-    if (!std::isfinite(ic)) return fail("denoise: colourInvSigma2 * 4^(iterations-1) overflows fp32");
-    return 0;
-}
-
-static int denoise_size_ok(uint32_t W, uint32_t H)
-{
-    if (W == 0 || H == 0 || (uint64_t)W * H > RT_DENOISE_MAX_PIXELS) return fail("denoise: a %u x %u image is not 1..2^27 pixels", W, H);
-    return 0;
-}
-
-uint64_t rtHipDenoiseScratchBytes(cl_uint width, cl_uint height)
-{
-    if (width == 0 || height == 0 || (uint64_t)width * height > RT_DENOISE_MAX_PIXELS) return 0;
-    return (uint64_t)width * height * RT_DENOISE_SCRATCH_PER_PIXEL;
-}
-
-// Issues the filter on `st`: guides, K iterations, output (planes: all three or none), and `afterGuides` (if any) between the guides and
-// the first iteration.  Arguments were checked by the caller.
-static int denoise_issue(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo, float *out, uint16_t *planeR,
-                         uint16_t *planeG, uint16_t *planeB, char *scratch, const rtHipDenoiseParams *p, hipStream_t st,
-                         hipEvent_t afterGuides = nullptr)
-{
-    const size_t n = (size_t)W * H;
-    char *c[2] = { scratch, scratch + 16 * n };
-    char *g0 = scratch + 32 * n, *g1 = scratch + 48 * n;
-    HIP_OK(rtd_launch_guides((uint32_t)n, colour, normal, albedo, c[0], g0, g1, st));
-    if (afterGuides) HIP_OK(hipEventRecord(afterGuides, st));
-    float ic = p->colourInvSigma2;
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        HIP_OK(rtd_launch_iteration(W, H, 1 << i, ic, p->albedoInvSigma2, p->normalPowerLog2, c[i & 1], g0, g1, c[(i + 1) & 1], st));
-        ic = ic * 4.0f;
-    }
-    HIP_OK(rtd_launch_output((uint32_t)n, c[p->iterations & 1], out, planeR, planeG, planeB, st));
-    return 0;
-}
-
-static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-int rtHipDenoiseDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *normal, const void *albedo, void *out,
-                       void *scratch, uint64_t scratchBytes, const rtHipDenoiseParams *params, void *stream)
-{
-    if (denoise_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
-    if (!colour || !normal || !albedo || !out || !scratch) return fail("denoise: null array");
-    const uint64_t img = (uint64_t)width * height * 12, need = rtHipDenoiseScratchBytes(width, height);
-    if (scratchBytes < need) return fail("denoise: scratch of %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)need);
-    const struct { const void *p; uint64_t bytes, align; const char *what; } arr[5] = {
-        { colour, img, 4, "colour" }, { normal, img, 4, "normal" }, { albedo, img, 4, "albedo" }, { out, img, 4, "out" }, { scratch, need, 16, "scratch" } };
-    for (int i = 0; i < 5; ++i) // out and scratch are written: neither may overlap anything else
-        for (int k = 3; k < 5; ++k)
-            if (i != k && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
-                return fail("denoise: %s overlaps %s", arr[k].what, arr[i].what);
-    HIP_OK(hipSetDevice(device));
-    if (stream) { // (the null stream is the current device's, set above)
-        hipDevice_t sd = -1;
-        if (hipStreamGetDevice((hipStream_t)stream, &sd) != hipSuccess) { (void)hipGetLastError(); return fail("denoise: stream %p is not a stream", stream); }
-        if (sd != device) return fail("denoise: stream %p belongs to device %d, the call is for device %d", stream, (int)sd, device);
-    }
-    for (const auto &a : arr)
-        if (query_pointer_ok(device, "the call", a.p, a.bytes, a.align, a.what) != 0) return -1;
-    return denoise_issue(width, height, (const float *)colour, (const float *)normal, (const float *)albedo, (float *)out, nullptr, nullptr,
-                         nullptr, (char *)scratch, params, (hipStream_t)stream);
-}
-
-int rtHipDenoise(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *normal, const cl_float *albedo,
-                 cl_float *out, const rtHipDenoiseParams *params)
-{
-    if (denoise_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
-    if (!colour || !normal || !albedo || !out) return fail("denoise: null array");
-    HIP_OK(hipSetDevice(device));
-    const size_t img = (size_t)width * height * 12;
-    DevScratch mem;
-    char *in = nullptr, *dout = nullptr, *scratch = nullptr;
-    HIP_OK(mem.get((void **)&in, 3 * img));
-    HIP_OK(mem.get((void **)&dout, img));
-    HIP_OK(mem.get((void **)&scratch, rtHipDenoiseScratchBytes(width, height)));
-    HIP_OK(hipMemcpy(in, colour, img, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(in + img, normal, img, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(in + 2 * img, albedo, img, hipMemcpyHostToDevice));
-    if (denoise_issue(width, height, (const float *)in, (const float *)(in + img), (const float *)(in + 2 * img), (float *)dout, nullptr,
-                      nullptr, nullptr, scratch, params, nullptr) != 0)
-        return -1;
-    HIP_OK(hipMemcpy(out, dout, img, hipMemcpyDeviceToHost));
-    HIP_OK(hipDeviceSynchronize());
-    return 0;
-}
-
-// `who` needs every tile of the image once in the instance's tile set (it works on the whole row-major image).
-static int whole_image_tiles(const rtHipScene *sc, const char *who)
-{
-    const uint32_t tiles = sc->tilesX * ((sc->height + RT_TILE - 1) / RT_TILE);
-    std::vector<char> seen(tiles, 0);
-    for (cl_uint t : sc->tileIds)
-        if (t >= tiles || seen[t]++) return fail("%s needs a tile set that holds every tile of the image once (tile %u)", who, t);
-    if (sc->tileIds.size() != tiles) return fail("%s needs a tile set that holds every tile of the image (%zu of %u)", who, sc->tileIds.size(), tiles);
-    return 0;
-}
-
-// The scene's denoiser scratch, made on first use: [colour | normal | albedo | out] W x H x 3 f32, [R | G | B] u16, filter scratch; every
-// part 256-byte aligned.
-struct DenoiseBuffer {
-    size_t n;
-    float *colour, *normal, *albedo, *out;
-    uint16_t *planes[3];
-    char *scratch;
-};
-static int denoise_buffer(rtHipScene *sc, DenoiseBuffer &D)
-{
-    const uint32_t W = sc->width, H = sc->height;
-    const size_t n = (size_t)W * H, img = (n * 12 + 255) & ~(size_t)255, plane = (n * 2 + 255) & ~(size_t)255;
-    const uint64_t bytes = 4 * img + 3 * plane + rtHipDenoiseScratchBytes(W, H);
-    if (!sc->denoiseBuf) {
-        void *p = nullptr;
-        HIP_OK(hipMalloc(&p, bytes));
-        sc->denoiseBuf = (char *)p;
-        sc->denoiseBytes = bytes;
-        sc->bytes += bytes;
-    }
-    char *b = sc->denoiseBuf;
-    D.n = n;
-    D.colour = (float *)b; D.normal = (float *)(b + img); D.albedo = (float *)(b + 2 * img); D.out = (float *)(b + 3 * img);
-    for (int c = 0; c < 3; ++c) D.planes[c] = (uint16_t *)(b + 4 * img + c * plane);
-    D.scratch = b + 4 * img + 3 * plane;
-    return 0;
-}
-
-int rtHipSceneDenoise(rtHipScene *sc, const rtHipDenoiseParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG, cl_ushort *outB)
-{
-    if (!sc) return fail("null scene");
-    if (denoise_params_ok(params) != 0 || denoise_size_ok(sc->width, sc->height) != 0) return -1;
-    if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
-        return fail("denoise needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
-    if (whole_image_tiles(sc, "denoise") != 0) return -1;
-    HIP_OK(hipSetDevice(sc->device));
-    HIP_OK(hipDeviceSynchronize());
-    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
-    const uint32_t W = sc->width, H = sc->height;
-    DenoiseBuffer D;
-    if (denoise_buffer(sc, D) != 0) return -1;
-    for (hipEvent_t &e : sc->denoiseEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    const bool wantPlanes = outR || outG || outB;
-    hipStream_t st = sc->stream;
-    hipEvent_t *ev = sc->denoiseEv;
-    HIP_OK(hipEventRecord(ev[0], st));
-    HIP_OK(rtd_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->surfBuf,
-                             (float)sc->dev.sampleCount, D.colour, D.normal, D.albedo, st));
-    HIP_OK(hipEventRecord(ev[1], st));
-    if (denoise_issue(W, H, D.colour, D.normal, D.albedo, outRgb ? D.out : nullptr, wantPlanes ? D.planes[0] : nullptr,
-                      wantPlanes ? D.planes[1] : nullptr, wantPlanes ? D.planes[2] : nullptr, D.scratch, params, st, ev[2]) != 0)
-        return -1;
-    HIP_OK(hipEventRecord(ev[3], st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(&sc->denoiseMs[i], ev[i], ev[i + 1]));
-    if (outRgb) HIP_OK(hipMemcpy(outRgb, D.out, D.n * 12, hipMemcpyDeviceToHost));
-    cl_ushort *dst[3] = { outR, outG, outB };
-    for (int c = 0; c < 3; ++c)
-        if (dst[c]) HIP_OK(hipMemcpy(dst[c], D.planes[c], D.n * 2, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int rtHipSceneDenoiseTimes(const rtHipScene *sc, cl_float *ms)
-{
-    if (!sc || !ms) return fail("null argument");
-    for (int i = 0; i < 3; ++i) ms[i] = sc->denoiseMs[i];
-    return 0;
-}
-
-// ---- temporal accumulation (include/raytrace_hip.h, "TEMPORAL ACCUMULATION"; kernels in rt_temporal.hip) ---------------------------
-#define RT_TEMPORAL_MAX_SIDE 16384u
-
-void rtHipTemporalDefaults(rtHipTemporalParams *p)
-{
-    if (!p) return;
-    p->maxHistory = 32.0f;
-    p->depthTolerance = 0.05f;
-}
-
-static int temporal_params_ok(const rtHipTemporalParams *p)
-{
-    if (!p) return fail("temporal: null parameters");
-    if (!(std::isfinite(p->maxHistory) && p->maxHistory >= 1.0f && p->maxHistory <= 65536.0f))
-        return fail("temporal: maxHistory %g is not finite and in 1..65536", (double)p->maxHistory);
-    if (!(std::isfinite(p->depthTolerance) && p->depthTolerance >= 0.f))
-        return fail("temporal: depthTolerance %g is not finite and >= 0", (double)p->depthTolerance);
-    return 0;
-}
-
-static int temporal_size_ok(uint32_t W, uint32_t H)
-{
-    if (W == 0 || H == 0 || W > RT_TEMPORAL_MAX_SIDE || H > RT_TEMPORAL_MAX_SIDE || (uint64_t)W * H > RT_DENOISE_MAX_PIXELS)
-        return fail("temporal: a %u x %u image is not 1..16384 pixels wide and high and 1..2^27 pixels", W, H);
-    return 0;
-}
-
-int rtHipTemporalDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
-                        const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
-                        void *outColour, void *outCount, const rtHipTemporalParams *params, void *stream)
-{
-    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
-    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !outColour)
-        return fail("temporal: null array");
-    const uint64_t n = (uint64_t)width * height;
-    const struct { const void *p; uint64_t bytes; const char *what; } arr[10] = {
-        { colour, n * 12, "colour" }, { motion, n * 8, "motion" }, { prevT, n * 4, "prevT" }, { triangle, n * 4, "triangle" },
-        { histColour, n * 12, "histColour" }, { histCount, n * 4, "histCount" }, { histT, n * 4, "histT" }, { histTriangle, n * 4, "histTriangle" },
-        { outColour, n * 12, "outColour" }, { outCount, n * 4, "outCount" } };
-    const int count = outCount ? 10 : 9;
-    for (int i = 0; i < count; ++i) // the outputs are written: neither may overlap anything else
-        for (int k = 8; k < count; ++k)
-            if (i != k && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
-                return fail("temporal: %s overlaps %s", arr[k].what, arr[i].what);
-    HIP_OK(hipSetDevice(device));
-    if (stream) { // (the null stream is the current device's, set above)
-        hipDevice_t sd = -1;
-        if (hipStreamGetDevice((hipStream_t)stream, &sd) != hipSuccess) { (void)hipGetLastError(); return fail("temporal: stream %p is not a stream", stream); }
-        if (sd != device) return fail("temporal: stream %p belongs to device %d, the call is for device %d", stream, (int)sd, device);
-    }
-    for (int i = 0; i < count; ++i)
-        if (query_pointer_ok(device, "the call", arr[i].p, arr[i].bytes, 4, arr[i].what) != 0) return -1;
-    HIP_OK(rtt_launch_accumulate(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
-                                 (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle,
-                                 (float *)outColour, (float *)outCount, params->maxHistory, params->depthTolerance, (hipStream_t)stream));
-    return 0;
-}
-
-int rtHipTemporal(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
-                  const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
-                  const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params)
-{
-    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
-    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !outColour)
-        return fail("temporal: null array");
-    HIP_OK(hipSetDevice(device));
-    const size_t n = (size_t)width * height;
-    const struct { const void *host; size_t bytes; } in[8] = { { colour, n * 12 }, { motion, n * 8 }, { prevT, n * 4 }, { triangle, n * 4 },
-                                                               { histColour, n * 12 }, { histCount, n * 4 }, { histT, n * 4 }, { histTriangle, n * 4 } };
-    DevScratch mem;
-    char *d[8], *dColour = nullptr, *dCount = nullptr;
-    for (int i = 0; i < 8; ++i) {
-        HIP_OK(mem.get((void **)&d[i], in[i].bytes));
-        HIP_OK(hipMemcpy(d[i], in[i].host, in[i].bytes, hipMemcpyHostToDevice));
-    }
-    HIP_OK(mem.get((void **)&dColour, n * 12));
-    if (outCount) HIP_OK(mem.get((void **)&dCount, n * 4));
-    HIP_OK(rtt_launch_accumulate(width, height, (const float *)d[0], (const float *)d[1], (const float *)d[2], (const uint32_t *)d[3],
-                                 (const float *)d[4], (const float *)d[5], (const float *)d[6], (const uint32_t *)d[7], (float *)dColour,
-                                 (float *)dCount, params->maxHistory, params->depthTolerance, nullptr));
-    HIP_OK(hipMemcpy(outColour, dColour, n * 12, hipMemcpyDeviceToHost));
-    if (outCount) HIP_OK(hipMemcpy(outCount, dCount, n * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipDeviceSynchronize());
-    return 0;
-}
-
-static int variance_params_ok(const rtHipVarianceParams *p);
-static int variance_issue(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo, const float *moments,
-                          const float *count, float *out, float *outVariance, uint16_t *planeR, uint16_t *planeG, uint16_t *planeB, char *scratch,
-                          char *il, const rtHipVarianceParams *p, hipStream_t st);
-
-// rtHipSceneTemporal (withMoments false: `denoise` or no filter) and rtHipSceneTemporalVariance (withMoments true: `variance` or no filter)
-// are one sequence; the second carries the moments along and has a variance to output.
-static int scene_temporal(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipDenoiseParams *denoise, bool withMoments,
-                          const rtHipVarianceParams *variance, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG, cl_ushort *outB,
-                          cl_float *outCount, cl_float *outVariance)
-{
-    if (!sc) return fail("temporal: null scene");
-    if (temporal_params_ok(params) != 0 || temporal_size_ok(sc->width, sc->height) != 0) return -1;
-    if (denoise) {
-        if (denoise_params_ok(denoise) != 0) return -1;
-        if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
-            return fail("temporal: denoise needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
-    }
-    if (variance) {
-        if (variance_params_ok(variance) != 0) return -1;
-        if ((sc->passMask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS)
-            return fail("temporal: the variance-guided filter needs the normal and the albedo pass on for this scene (rtHipScenePasses)");
-    }
-    if (whole_image_tiles(sc, "temporal accumulation") != 0) return -1;
-    HIP_OK(hipSetDevice(sc->device));
-    HIP_OK(hipDeviceSynchronize());
-    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
-    if (!sc->motion.have && rtHipSceneMotionMark(sc) != 0) return -1;
-    if (sc->dev.triangleCount != sc->motion.triangles)
-        return fail("temporal: the scene has %u triangles, the motion reference was made for %u", sc->dev.triangleCount, sc->motion.triangles);
-    rtHipScene::Temporal &T = sc->temporal;
-    const uint32_t W = sc->width, H = sc->height;
-    const size_t n = (size_t)W * H;
-    const auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-    const size_t set = part(n * 12) + 3 * part(n * 4); // a history set: colour | count | t | triangle
-    if (!T.buf) {
-        const uint64_t bytes = 2 * set + part(n * 8) + part(n * 4) + part(n * 12) + 3 * part(n * 2);
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return fail("temporal: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        T.buf = (char *)p; T.bytes = bytes; T.cur = 0; T.valid = false;
-        sc->bytes += bytes;
-    }
-    if (withMoments && !T.momentsBuf) { // two sets of moments | the variance | the filter's il
-        const uint64_t bytes = 2 * part(n * 8) + 2 * part(n * 4);
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return fail("temporal: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        T.momentsBuf = (char *)p; T.momentsBytes = bytes; T.momentsValid = false;
-        sc->bytes += bytes;
-    }
-    if (withMoments && !T.momentsValid) T.valid = false; // a live history whose moments are stale starts again, as after a reset
-    for (hipEvent_t &e : T.ev)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    struct Set { float *colour, *count, *t; uint32_t *triangle; } hs[2];
-    for (int i = 0; i < 2; ++i) {
-        char *b = T.buf + i * set;
-        hs[i].colour = (float *)b; hs[i].count = (float *)(b + part(n * 12)); hs[i].t = (float *)(b + part(n * 12) + part(n * 4));
-        hs[i].triangle = (uint32_t *)(b + part(n * 12) + 2 * part(n * 4));
-    }
-    char *rest = T.buf + 2 * set;
-    float *motion = (float *)rest, *prevT = (float *)(rest + part(n * 8)), *colour = (float *)(rest + part(n * 8) + part(n * 4));
-    uint16_t *planes[3];
-    for (int c = 0; c < 3; ++c) planes[c] = (uint16_t *)(rest + part(n * 8) + part(n * 4) + part(n * 12) + c * part(n * 2));
-    const Set &hist = hs[T.cur], &next = hs[T.cur ^ 1];
-    float *moments[2] = {}, *varianceOut = nullptr;
-    char *il = nullptr;
-    if (withMoments) {
-        moments[0] = (float *)T.momentsBuf; moments[1] = (float *)(T.momentsBuf + part(n * 8));
-        varianceOut = (float *)(T.momentsBuf + 2 * part(n * 8));
-        il = T.momentsBuf + 2 * part(n * 8) + part(n * 4);
-    }
-    const bool surfaces = denoise || variance; // the filters take the gathered normal and albedo
-    DenoiseBuffer D{};
-    if (surfaces && denoise_buffer(sc, D) != 0) return -1;
-    hipStream_t st = sc->stream;
-    if (!T.valid) HIP_OK(hipMemsetAsync(hist.count, 0, n * 4, st)); // no history: every tap is refused, whatever the rest of the set holds
-    HIP_OK(hipEventRecord(T.ev[0], st));
-    if (motion_run(sc, motion, next.t, prevT, next.triangle, true, st) != 0) return -1; // this frame's guides are the next call's history
-    HIP_OK(hipEventRecord(T.ev[1], st));
-    if (surfaces) {
-        HIP_OK(rtd_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->surfBuf,
-                                 (float)sc->dev.sampleCount, D.colour, D.normal, D.albedo, st));
-        colour = D.colour;
-    } else {
-        HIP_OK(rtt_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, colour, st));
-    }
-    HIP_OK(hipEventRecord(T.ev[2], st));
-    if (withMoments)
-        HIP_OK(rtv_launch_moments(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle, moments[T.cur],
-                                  next.colour, next.count, moments[T.cur ^ 1], variance ? nullptr : varianceOut, params->maxHistory,
-                                  params->depthTolerance, st));
-    else
-        HIP_OK(rtt_launch_accumulate(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle, next.colour,
-                                     next.count, params->maxHistory, params->depthTolerance, st));
-    HIP_OK(hipEventRecord(T.ev[3], st));
-    // From here until the new mark stands, a failure leaves the scene without history: set `next` is half a step ahead of the reference.
-    T.valid = false;
-    T.momentsValid = false;
-    const bool wantPlanes = outR || outG || outB;
-    const float *result = next.colour;
-    uint16_t **resultPlanes = planes;
-    if (variance) { // temporal, then spatial with the moments' variance; the history keeps the unfiltered accumulation
-        if (variance_issue(W, H, next.colour, D.normal, D.albedo, moments[T.cur ^ 1], next.count, outRgb ? D.out : nullptr, varianceOut,
-                           wantPlanes ? D.planes[0] : nullptr, wantPlanes ? D.planes[1] : nullptr, wantPlanes ? D.planes[2] : nullptr,
-                           D.scratch, il, variance, st) != 0)
-            return -1;
-        result = D.out;
-        resultPlanes = D.planes;
-    } else if (denoise) { // temporal, then spatial; the history keeps the unfiltered accumulation
-        if (denoise_issue(W, H, next.colour, D.normal, D.albedo, outRgb ? D.out : nullptr, wantPlanes ? D.planes[0] : nullptr,
-                          wantPlanes ? D.planes[1] : nullptr, wantPlanes ? D.planes[2] : nullptr, D.scratch, denoise, st) != 0)
-            return -1;
-        result = D.out;
-        resultPlanes = D.planes;
-    } else if (wantPlanes) {
-        HIP_OK(rtt_launch_quantise((uint32_t)n, next.colour, planes[0], planes[1], planes[2], st));
-    }
-    HIP_OK(hipEventRecord(T.ev[4], st));
-    if (rtHipSceneMotionMark(sc) != 0) return -1; // the reference becomes the state this frame was rendered from
-    HIP_OK(hipStreamSynchronize(st));
-    T.cur ^= 1; // the sets change places only now: history and reference advance together
-    T.valid = true;
-    T.momentsValid = withMoments;
-    for (int i = 0; i < 4; ++i) HIP_OK(hipEventElapsedTime(&T.ms[i], T.ev[i], T.ev[i + 1]));
-    if (outRgb) HIP_OK(hipMemcpy(outRgb, result, n * 12, hipMemcpyDeviceToHost));
-    cl_ushort *dst[3] = { outR, outG, outB };
-    for (int c = 0; c < 3; ++c)
-        if (dst[c]) HIP_OK(hipMemcpy(dst[c], resultPlanes[c], n * 2, hipMemcpyDeviceToHost));
-    if (outCount) HIP_OK(hipMemcpy(outCount, next.count, n * 4, hipMemcpyDeviceToHost));
-    if (outVariance) HIP_OK(hipMemcpy(outVariance, varianceOut, n * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int rtHipSceneTemporal(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipDenoiseParams *denoise, cl_float *outRgb,
-                       cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount)
-{
-    return scene_temporal(sc, params, denoise, false, nullptr, outRgb, outR, outG, outB, outCount, nullptr);
-}
-
-int rtHipSceneTemporalReset(rtHipScene *sc)
-{
-    if (!sc) return fail("temporal: null scene");
-    sc->temporal.valid = false;
-    return 0;
-}
-
-int rtHipSceneTemporalTimes(const rtHipScene *sc, cl_float *ms)
-{
-    if (!sc || !ms) return fail("null argument");
-    for (int i = 0; i < 4; ++i) ms[i] = sc->temporal.ms[i];
-    return 0;
-}
-
-// ---- variance-guided filter (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER"; kernels in rt_variance.hip) ------------------------
-// Filter scratch of a W x H image: the states S^i and S^(i+1) = (C.rgb, V) as float4 (ping-pong), the guides G0 and G1 as float4 (the
-// denoiser's 64 B per pixel), then il as f32.
-#define RT_VARIANCE_SCRATCH_PER_PIXEL 68ull
-
-void rtHipVarianceDefaults(rtHipVarianceParams *p)
-{
-    if (!p) return;
-    p->iterations = 4;
-    p->luminanceSigma2 = 4.0f;
-    p->varianceFloor = 1e-8f;
-    p->albedoInvSigma2 = 100.0f;
-    p->normalPowerLog2 = 7;
-    p->spatialBelow = 4.0f;
-}
-
-static int variance_params_ok(const rtHipVarianceParams *p)
-{
-    if (!p) return fail("variance: null parameters");
-    if (p->iterations > 12) return fail("variance: iterations %u is not in 0..12", p->iterations);
-    if (!(std::isfinite(p->luminanceSigma2) && p->luminanceSigma2 >= 0.f))
-        return fail("variance: luminanceSigma2 %g is not finite and >= 0", (double)p->luminanceSigma2);
-    if (!(std::isfinite(p->varianceFloor) && p->varianceFloor >= 0x1p-100f))
-        return fail("variance: varianceFloor %g is not finite and >= 2^-100", (double)p->varianceFloor);
-    if (!(std::isfinite(p->albedoInvSigma2) && p->albedoInvSigma2 >= 0.f))
-        return fail("variance: albedoInvSigma2 %g is not finite and >= 0", (double)p->albedoInvSigma2);
-    if (p->normalPowerLog2 > 10) return fail("variance: normalPowerLog2 %u is not in 0..10", p->normalPowerLog2);
-    if (!(std::isfinite(p->spatialBelow) && p->spatialBelow >= 0.f && p->spatialBelow <= 65537.0f))
-        return fail("variance: spatialBelow %g is not finite and in 0..65537", (double)p->spatialBelow);
-    return 0;
-}
-
-uint64_t rtHipVarianceScratchBytes(cl_uint width, cl_uint height)
-{
-    if (width == 0 || height == 0 || (uint64_t)width * height > RT_DENOISE_MAX_PIXELS) return 0;
-    return (uint64_t)width * height * RT_VARIANCE_SCRATCH_PER_PIXEL;
-}
-
-// Issues the filter on `st`: guides and estimate, K iterations, output (planes: all three or none).  scratch: the first 64 B per pixel of
-// the layout above; il: n f32.  Arguments were checked by the caller.
-static int variance_issue(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo, const float *moments,
-                          const float *count, float *out, float *outVariance, uint16_t *planeR, uint16_t *planeG, uint16_t *planeB, char *scratch,
-                          char *il, const rtHipVarianceParams *p, hipStream_t st)
-{
-    const size_t n = (size_t)W * H;
-    char *s[2] = { scratch, scratch + 16 * n };
-    char *g0 = scratch + 32 * n, *g1 = scratch + 48 * n;
-    HIP_OK(rtv_launch_estimate(W, H, colour, normal, albedo, moments, count, p->spatialBelow, p->albedoInvSigma2, p->normalPowerLog2, s[0], g0,
-                               g1, st));
-    for (uint32_t i = 0; i < p->iterations; ++i)
-        HIP_OK(rtv_launch_iteration(W, H, 1 << i, p->luminanceSigma2, p->varianceFloor, p->albedoInvSigma2, p->normalPowerLog2, s[i & 1], il,
-                                    g0, g1, s[(i + 1) & 1], st));
-    HIP_OK(rtv_launch_output((uint32_t)n, s[p->iterations & 1], out, outVariance, planeR, planeG, planeB, st));
-    return 0;
-}
-
-static int stream_of_device_ok(const char *who, int device, void *stream)
-{
-    if (!stream) return 0; // (the null stream is the current device's, set by the caller)
-    hipDevice_t sd = -1;
-    if (hipStreamGetDevice((hipStream_t)stream, &sd) != hipSuccess) { (void)hipGetLastError(); return fail("%s: stream %p is not a stream", who, stream); }
-    if (sd != device) return fail("%s: stream %p belongs to device %d, the call is for device %d", who, stream, (int)sd, device);
-    return 0;
-}
-
-int rtHipDenoiseVarianceDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *normal, const void *albedo,
-                               const void *moments, const void *count, void *out, void *outVariance, void *scratch, uint64_t scratchBytes,
-                               const rtHipVarianceParams *params, void *stream)
-{
-    if (variance_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
-    if (!colour || !normal || !albedo || !out || !scratch) return fail("variance: null array");
-    if ((moments == nullptr) != (count == nullptr)) return fail("variance: moments and count are both NULL or both given");
-    const uint64_t n = (uint64_t)width * height, img = n * 12, need = rtHipVarianceScratchBytes(width, height);
-    if (scratchBytes < need) return fail("variance: scratch of %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)need);
-    const struct { const void *p; uint64_t bytes, align; const char *what; } arr[8] = {
-        { colour, img, 4, "colour" }, { normal, img, 4, "normal" }, { albedo, img, 4, "albedo" }, { moments, n * 8, 4, "moments" },
-        { count, n * 4, 4, "count" }, { out, img, 4, "out" }, { scratch, need, 16, "scratch" }, { outVariance, n * 4, 4, "outVariance" } };
-    for (int i = 0; i < 8; ++i) // out, scratch and outVariance are written: none may overlap anything else
-        for (int k = 5; k < 8; ++k)
-            if (i != k && arr[i].p && arr[k].p && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
-                return fail("variance: %s overlaps %s", arr[k].what, arr[i].what);
-    HIP_OK(hipSetDevice(device));
-    if (stream_of_device_ok("variance", device, stream) != 0) return -1;
-    for (const auto &a : arr)
-        if (a.p && query_pointer_ok(device, "the call", a.p, a.bytes, a.align, a.what) != 0) return -1;
-    return variance_issue(width, height, (const float *)colour, (const float *)normal, (const float *)albedo, (const float *)moments,
-                          (const float *)count, (float *)out, (float *)outVariance, nullptr, nullptr, nullptr, (char *)scratch,
-                          (char *)scratch + 64 * n, params, (hipStream_t)stream);
-}
-
-int rtHipDenoiseVariance(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *normal, const cl_float *albedo,
-                         const cl_float *moments, const cl_float *count, cl_float *out, cl_float *outVariance, const rtHipVarianceParams *params)
-{
-    if (variance_params_ok(params) != 0 || denoise_size_ok(width, height) != 0) return -1;
-    if (!colour || !normal || !albedo || !out) return fail("variance: null array");
-    if ((moments == nullptr) != (count == nullptr)) return fail("variance: moments and count are both NULL or both given");
-    HIP_OK(hipSetDevice(device));
-    const size_t n = (size_t)width * height, img = n * 12;
-    DevScratch mem;
-    char *in = nullptr, *dm = nullptr, *dn = nullptr, *dout = nullptr, *dvar = nullptr, *scratch = nullptr;
-    HIP_OK(mem.get((void **)&in, 3 * img));
-    HIP_OK(mem.get((void **)&dout, img));
-    HIP_OK(mem.get((void **)&dvar, n * 4));
-    HIP_OK(mem.get((void **)&scratch, rtHipVarianceScratchBytes(width, height)));
-    HIP_OK(hipMemcpy(in, colour, img, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(in + img, normal, img, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(in + 2 * img, albedo, img, hipMemcpyHostToDevice));
-    if (moments) {
-        HIP_OK(mem.get((void **)&dm, n * 8));
-        HIP_OK(mem.get((void **)&dn, n * 4));
-        HIP_OK(hipMemcpy(dm, moments, n * 8, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dn, count, n * 4, hipMemcpyHostToDevice));
-    }
-    if (variance_issue(width, height, (const float *)in, (const float *)(in + img), (const float *)(in + 2 * img), (const float *)dm,
-                       (const float *)dn, (float *)dout, (float *)dvar, nullptr, nullptr, nullptr, scratch, scratch + 64 * n, params, nullptr) != 0)
-        return -1;
-    HIP_OK(hipMemcpy(out, dout, img, hipMemcpyDeviceToHost));
-    if (outVariance) HIP_OK(hipMemcpy(outVariance, dvar, n * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipDeviceSynchronize());
-    return 0;
-}
-
-int rtHipTemporalMomentsDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
-                               const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
-                               const void *histMoments, void *outColour, void *outCount, void *outMoments, void *outVariance,
-                               const rtHipTemporalParams *params, void *stream)
-{
-    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
-    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !histMoments || !outColour ||
-        !outMoments)
-        return fail("temporal: null array");
-    const uint64_t n = (uint64_t)width * height;
-    const struct { const void *p; uint64_t bytes; const char *what; } arr[13] = {
-        { colour, n * 12, "colour" }, { motion, n * 8, "motion" }, { prevT, n * 4, "prevT" }, { triangle, n * 4, "triangle" },
-        { histColour, n * 12, "histColour" }, { histCount, n * 4, "histCount" }, { histT, n * 4, "histT" }, { histTriangle, n * 4, "histTriangle" },
-        { histMoments, n * 8, "histMoments" }, { outColour, n * 12, "outColour" }, { outMoments, n * 8, "outMoments" },
-        { outCount, n * 4, "outCount" }, { outVariance, n * 4, "outVariance" } };
-    for (int i = 0; i < 13; ++i) // the outputs are written: none may overlap anything else
-        for (int k = 9; k < 13; ++k)
-            if (i != k && arr[i].p && arr[k].p && ranges_overlap(arr[i].p, arr[i].bytes, arr[k].p, arr[k].bytes))
-                return fail("temporal: %s overlaps %s", arr[k].what, arr[i].what);
-    HIP_OK(hipSetDevice(device));
-    if (stream_of_device_ok("temporal", device, stream) != 0) return -1;
-    for (const auto &a : arr)
-        if (a.p && query_pointer_ok(device, "the call", a.p, a.bytes, 4, a.what) != 0) return -1;
-    HIP_OK(rtv_launch_moments(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
-                              (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle,
-                              (const float *)histMoments, (float *)outColour, (float *)outCount, (float *)outMoments, (float *)outVariance,
-                              params->maxHistory, params->depthTolerance, (hipStream_t)stream));
-    return 0;
-}
-
-int rtHipTemporalMoments(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
-                         const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
-                         const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour, cl_float *outCount, cl_float *outMoments,
-                         cl_float *outVariance, const rtHipTemporalParams *params)
-{
-    if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
-    if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !histMoments || !outColour ||
-        !outMoments)
-        return fail("temporal: null array");
-    HIP_OK(hipSetDevice(device));
-    const size_t n = (size_t)width * height;
-    const struct { const void *host; size_t bytes; } in[9] = { { colour, n * 12 }, { motion, n * 8 }, { prevT, n * 4 }, { triangle, n * 4 },
-                                                               { histColour, n * 12 }, { histCount, n * 4 }, { histT, n * 4 }, { histTriangle, n * 4 },
-                                                               { histMoments, n * 8 } };
-    DevScratch mem;
-    char *d[9], *dColour = nullptr, *dCount = nullptr, *dMoments = nullptr, *dVariance = nullptr;
-    for (int i = 0; i < 9; ++i) {
-        HIP_OK(mem.get((void **)&d[i], in[i].bytes));
-        HIP_OK(hipMemcpy(d[i], in[i].host, in[i].bytes, hipMemcpyHostToDevice));
-    }
-    HIP_OK(mem.get((void **)&dColour, n * 12));
-    HIP_OK(mem.get((void **)&dMoments, n * 8));
-    if (outCount) HIP_OK(mem.get((void **)&dCount, n * 4));
-    if (outVariance) HIP_OK(mem.get((void **)&dVariance, n * 4));
-    HIP_OK(rtv_launch_moments(width, height, (const float *)d[0], (const float *)d[1], (const float *)d[2], (const uint32_t *)d[3],
-                              (const float *)d[4], (const float *)d[5], (const float *)d[6], (const uint32_t *)d[7], (const float *)d[8],
-                              (float *)dColour, (float *)dCount, (float *)dMoments, (float *)dVariance, params->maxHistory,
-                              params->depthTolerance, nullptr));
-    HIP_OK(hipMemcpy(outColour, dColour, n * 12, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(outMoments, dMoments, n * 8, hipMemcpyDeviceToHost));
-    if (outCount) HIP_OK(hipMemcpy(outCount, dCount, n * 4, hipMemcpyDeviceToHost));
-    if (outVariance) HIP_OK(hipMemcpy(outVariance, dVariance, n * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipDeviceSynchronize());
-    return 0;
-}
-
-int rtHipSceneTemporalVariance(rtHipScene *sc, const rtHipTemporalParams *params, const rtHipVarianceParams *variance, cl_float *outRgb,
-                               cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount, cl_float *outVariance)
-{
-    return scene_temporal(sc, params, nullptr, true, variance, outRgb, outR, outG, outB, outCount, outVariance);
 }
 
 // ---- geometry updates ------------------------------------------------------------------------------------------------------------

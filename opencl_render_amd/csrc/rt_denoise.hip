@@ -1,7 +1,7 @@
 // rt_denoise.hip -- the denoiser of include/raytrace_hip.h ("DENOISER"): an edge-avoiding a-trous wavelet filter guided by the normal
 // and albedo passes, in the exact fp32 arithmetic the header fixes (tests/denoise_oracle.py is the same definition in numpy).
 //
-// Kernels, in launch order (rt_api.cpp issues them on one stream):
+// Kernels, in launch order (rt_filters.cpp issues them on one stream):
 //   rtd_gather_kernel    scene path only: the [slot][R,G,B][128*128] u16 tile buffer and the [slot][nx ny nz ar ag ab][128*128] surface
 //                        sums -> row-major W x H x 3 f32 colour (u16 / 65535), normal and albedo (sum / S)
 //   rtd_guide_kernel     row-major inputs -> C^0 as float4 (padded, so every later colour load is one 16-byte load) and the packed

@@ -1,0 +1,413 @@
+// rt_host.h -- what the host translation units of libraytrace_hip.so share (rt_api.cpp: scenes, frames, queries; rt_filters.cpp: the
+// image-space filters): the error text, the tuning values, device scratch and staging, and the resident scene itself.  Internal: nothing
+// here is part of the C ABI of include/raytrace_hip.h.
+#pragma once
+#include "raytrace_hip.h"
+#include "rt_device.h"
+#include "rt_camera_move.h"
+#include "rt_geometry_move.h"
+
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+// Which render pass bits need the surface buffer
+#define RT_SURF_BUF_BITS (RT_HIP_PASS_NORMAL | RT_HIP_PASS_ALBEDO)
+
+namespace rthost {
+
+// Internal functions are kept out of the library's exported symbols.
+#define RT_INTERNAL __attribute__((visibility("hidden")))
+
+// Sets this thread's error text (rtHipLastError) and returns -1.
+RT_INTERNAL int fail(const char *fmt, ...);
+
+#define HIP_OK(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) return rthost::fail("%s failed: %s", #expr, hipGetErrorString(e_));      \
+    } while (0)
+
+// Tuning values and test hooks.  The library reads NO environment variables: a plugin host's environment must not be able to
+// make frames slower, redo themselves or fail.  Everything here is set through rtHipTune() (include/raytrace_hip.h, test / tuning
+// entry point; the Python stub maps RT_* variables of ITS process onto it for the sweep scripts) and applies to scenes built
+// afterwards.
+struct Tuning {
+    uint32_t stageMb = 32;          // size of each of the two pinned staging buffers of an upload
+    uint32_t extraFactor = 6;       // region B of the entry arrays (further segments of cut rays), in units of the path capacity
+    uint64_t stateMb = 0;           // path-state budget per sample batch (0 = 24 GB, never more than a third of free memory); tests force several batches
+    uint32_t groups = 1;            // concurrent tile groups per instance (measured: no gain once rays are cut into segments)
+    uint32_t lookAhead = 1;         // 0: one ray in flight per path
+    uint32_t segLen[5] = { 4096u, 384u, 96u, 64u, 16u }; // aimed-at cell visits per segment for rounds with >= segRays[0] | [1] | [2] | [3] | fewer rays
+    uint32_t segRays[4] = { 700000u, 300000u, 100000u, 30000u };
+    uint32_t fastQuotient = 1;
+    uint32_t spinLimit = 16384;     // a ray makes at most 766 cell visits = 154 walk phases; lowered by the test of the guard's error path
+    uint32_t appendRays = 300000;   // later rounds with fewer rays are not ordered: the trace kernel plans and cuts their rays itself (RtRoundMode)
+    uint32_t orderedFirst = 1;      // 0: round 1 follows the same rule (tests: the trace kernel's planning on dense rounds)
+    uint32_t sliceRays = 0;         // rounds with fewer rays use smallSlices queue slices per kind instead of RT_WF_SHARDS (off: a round's appends want
+                                    // many counters -- 16 slices cost the logic kernel of a 58 k-ray round 17 us -- and the trace kernel packs its pieces anyway)
+    uint32_t smallSlices = 16;
+    uint32_t groupRays = 0;         // rays per workgroup of the trace kernel in rounds that are not ordered (0 = by segment length)
+    uint32_t blocking = 0;          // 1: every frame watches its queue (no launch plan)
+    uint32_t planRounds = 0;        // test hook: planned frames issue at most this many rounds, so that the too-short-plan path runs
+    uint32_t planGridTiny = 0;      // test hook: planned trace grids of one workgroup, so that the too-small-grid path runs
+    uint32_t pipeline = RT_HIP_PIPELINE_WAVEFRONT;
+    uint32_t timing = 0;            // 1: where the time of a scene build / a RaytraceAll call goes (stderr)
+    uint32_t virtualDevices = 0;    // test hook: the all-GPUs id deals the tiles over this many instances on the devices that are there
+    uint32_t cache = 1;             // 0: RaytraceAll builds and frees per call, like the reference
+    uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
+    uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
+    uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
+    uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
+    uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
+    uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
+    uint32_t aoSamples = 1u << 20;  // pixel samples per chunk of the ambient occlusion calls (32 bytes each of scene-owned scratch)
+    uint32_t bakeTexels = 1u << 20; // texels per chunk of the ambient occlusion bake (32 bytes each of scene-owned scratch)
+};
+
+// Device scratch of a scene build: freed when the scope ends, whichever way it ends.
+struct DevScratch {
+    std::vector<void *> blocks;
+    ~DevScratch() { for (void *p : blocks) (void)hipFree(p); }
+    hipError_t get(void **out, size_t bytes)
+    {
+        const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+        if (e == hipSuccess) blocks.push_back(*out);
+        return e;
+    }
+};
+
+// Host-to-device copies go through two pinned buffers (hipHostMalloc once per scene, RT_HIP_STAGE_MB each, default 32): the
+// caller's arrays are pageable (new[] in render.cpp:1089-1123), and a pageable hipMemcpy is a synchronous bounce through the
+// runtime's own small staging area.  Here the CPU fills one buffer (several threads for big pieces) while the DMA engine
+// drains the other; copy() returns when the source has been read completely, so callers may free it at once.
+struct Stager {
+    hipStream_t stream = nullptr;
+    char *buf[2] = { nullptr, nullptr };
+    hipEvent_t done[2] = { nullptr, nullptr };
+    bool used[2] = { false, false };
+    size_t size = 0;
+    int next = 0;
+    // Pinning 2 x 32 MB costs 15-25 ms, more than the rest of an instance's build when its shared parts are copied from another
+    // instance: the buffers are taken when the first host array needs them and go back to a process-wide pool, not to the driver.
+    struct Pool {
+        std::mutex lock;
+        std::vector<std::pair<char *, size_t>> idle;
+        char *take(size_t bytes)
+        {
+            {
+                std::lock_guard<std::mutex> g(lock);
+                for (size_t i = 0; i < idle.size(); ++i)
+                    if (idle[i].second == bytes) { char *p = idle[i].first; idle.erase(idle.begin() + i); return p; }
+            }
+            char *p = nullptr;
+            if (hipHostMalloc((void **)&p, bytes, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            return p;
+        }
+        void give(char *p, size_t bytes)
+        {
+            std::lock_guard<std::mutex> g(lock);
+            if (idle.size() < 8) idle.emplace_back(p, bytes);
+            else (void)hipHostFree(p);
+        }
+    };
+    static Pool &pool() { static Pool *p = new Pool(); return *p; } // (never destroyed: buffers may come back during process exit)
+    int init(hipStream_t st, const Tuning &T)
+    {
+        stream = st;
+        size = (size_t)std::min<uint32_t>(std::max<uint32_t>(T.stageMb, 1u), 4096u) << 20;
+        for (int i = 0; i < 2; ++i) HIP_OK(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
+        return 0;
+    }
+    static void fill(char *dst, const char *src, size_t n)
+    {
+        const size_t piece = (size_t)4 << 20;
+        if (n < 2 * piece) { memcpy(dst, src, n); return; }
+        const size_t parts = std::min<size_t>(8, n / piece);
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < parts; ++t) pool.emplace_back([=] { memcpy(dst + n * t / parts, src + n * t / parts, n * (t + 1) / parts - n * t / parts); });
+        memcpy(dst, src, n / parts);
+        for (auto &th : pool) th.join();
+    }
+    // is `p` device memory (a scene description may hand over arrays that are already on the GPU)?
+    static bool on_device(const void *p)
+    {
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof at);
+        if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; } // (plain host memory: "invalid value")
+        return at.type == hipMemoryTypeDevice;
+    }
+    hipError_t copy(void *dst, const void *src, size_t bytes)
+    {
+        if (bytes && on_device(src)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream); // no staging: HBM to HBM
+        for (size_t off = 0; off < bytes;) {
+            const size_t n = std::min(size, bytes - off);
+            const int i = next;
+            next ^= 1;
+            if (used[i]) { const hipError_t e = hipEventSynchronize(done[i]); if (e != hipSuccess) return e; }
+            if (!buf[i] && !(buf[i] = pool().take(size))) return hipErrorOutOfMemory;
+            fill(buf[i], (const char *)src + off, n);
+            hipError_t e = hipMemcpyAsync((char *)dst + off, buf[i], n, hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess) return e;
+            e = hipEventRecord(done[i], stream);
+            if (e != hipSuccess) return e;
+            used[i] = true;
+            off += n;
+        }
+        return hipSuccess;
+    }
+    hipError_t drain() // every copy so far has left its staging buffer; the buffers go back to the pool (the next instance's build takes them)
+    {
+        for (int i = 0; i < 2; ++i) {
+            if (used[i]) { const hipError_t e = hipEventSynchronize(done[i]); if (e != hipSuccess) return e; used[i] = false; }
+            if (buf[i]) { pool().give(buf[i], size); buf[i] = nullptr; }
+        }
+        return hipSuccess;
+    }
+    void destroy()
+    {
+        for (int i = 0; i < 2; ++i) {
+            if (done[i]) { if (used[i]) (void)hipEventSynchronize(done[i]); (void)hipEventDestroy(done[i]); done[i] = nullptr; }
+            if (buf[i]) { pool().give(buf[i], size); buf[i] = nullptr; }
+        }
+    }
+};
+
+} // namespace rthost
+
+enum { PART_FIXED = 0, PART_CAMERA, PART_GEOMETRY, PART_GRID, PART_MATERIALS, PART_LIGHTS, PART_WAVEFRONT, PART_COUNT };
+
+struct rtHipScene {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    RtDevScene dev{};
+    // Device allocations by PART (tiles + outputs | camera lists | geometry | grid | materials | lights | path state): the drop-in
+    // layer's cache replaces the parts whose inputs changed between two RaytraceAll calls and keeps the others in HBM.
+    std::vector<void *> partAllocs[PART_COUNT];
+    std::vector<uint64_t> partSizes[PART_COUNT]; // bytes of every allocation (a peer instance copies the shared parts device to device)
+    uint64_t partBytes[PART_COUNT] = { 0 };
+    int curPart = PART_FIXED;
+    rthost::Stager stager;
+    uint32_t *prepErr = nullptr;   // device word: RT_PREP_ERR_* bits raised by the validation kernels
+    uint64_t camListSize = 0;
+    uint64_t gridListSize = 0;      // entries of the grid list = pair records of the dense view
+    uint32_t gridListSizeHint = 0;  // scene description with device arrays: scenePixelTriangleListStart[256^3], fetched by scene_build
+    bool haveGridListSize = false;
+    bool wfMultiLight = false;     // what the path-state buffers were sized for
+    bool classMaterials = false, classLights = false; // the materials part / the lights part admit the opaque-diffuse path class
+    uint64_t bytes = 0;
+    std::vector<cl_uint> tileIds;
+    uint32_t width = 0, height = 0, tilesX = 0;
+    // kernel timing: one event pair per launch since the last rtHipKernelTime
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    size_t eventsUsed = 0;
+    // wavefront pipeline (rt_wavefront.hip)
+    int pipeline = RT_HIP_PIPELINE_WAVEFRONT;
+    // The instance's tile slots are cut into contiguous GROUPS, each a view of `dev` (its own slice of tileIds, camStart/End,
+    // tileBuf) with its own path state and stream.  A frame runs the groups concurrently: while one group is in a phase that
+    // cannot fill the GPU (a round with few rays, a host read-back), the others' kernels do.  Per pixel nothing changes.
+    struct Group {
+        RtDevScene dev{};
+        RtWavefront wf{};
+        hipStream_t stream = nullptr;   // groups 1.. ; group 0 runs on the caller's stream
+        hipEvent_t done = nullptr;
+        uint32_t logicBlocks = 1, traceBlocks = 1, queueBlocks = 1;
+        uint32_t *hostCount = nullptr;  // pinned: queue length read back between round chunks
+        uint32_t *hostStatus = nullptr; // pinned + mapped: RT_WF_STATUS_* words the kernels write (rt_device.h)
+        bool ctlClean = false;          // the batch before was a planned one: wf_status_kernel left the control words zeroed
+        uint32_t rounds = 0;
+        uint32_t slot0 = 0, slot1 = 0;  // this group's range of the instance's tile slots
+        // launch plan (render_wavefront): what the last discovery frame needed
+        uint32_t roundsNeeded = 0;
+        // per round: rays (entries in region A), the longest queue slice, entries in region B -- the maximum over the watched batches
+        // rays of the round, and -- an ordered round -- the further segments of its cut rays under the cut it was logged with
+        struct RoundPlan { uint32_t rays = 0, extra = 0, extraSegLen = 0; };
+        uint4 *hostLog = nullptr;       // pinned + mapped: RtWavefront::roundLog, written by the kernels, read by the host after a sync
+        RoundPlan plan[RT_WF_ROUND_LOG], planNext[RT_WF_ROUND_LOG];
+        std::vector<RtRoundMode> modes; // how the rounds of the batch being issued are laid out (modes[r] is decided when logic(r-1) is launched)
+        uint64_t guessRays = 0;         // watched batches: what the next round is assumed to hold
+    };
+    std::vector<Group> groups;
+    hipEvent_t forkEvent = nullptr;
+    uint32_t samplesPerBatch = 1;
+    uint32_t planRounds = 0;   // rounds a planned frame issues per batch; 0 = no plan yet (the next frame is a discovery frame)
+    bool blocking = false;     // every frame watches the queue (no plan)
+    rthost::Tuning tune;       // the tuning values this scene was built with (rtHipTune)
+    bool unverified = false;   // planned frames were issued since the last frame_finish()
+    hipStream_t lastStream = nullptr; // where the last frame was issued
+    std::atomic<float> *progress = nullptr; // drop-in layer: where finished sample batches are reported (GetProgress, raytrace.c:566-587)
+    float progressBase = 0.f, progressSpan = 0.f;
+    // per-stage device time of the frames since the last query: [primary, logic, trace, accum, sort]
+    struct StageEvent { int stage; hipEvent_t a, b; };
+    std::vector<StageEvent> stageEvents;
+    size_t stageEventsUsed = 0;
+    bool stageTiming = false;
+    uint64_t roundsLast = 0;
+    // render passes (rtHipScenePasses): RT_HIP_PASS_* bits, the pass buffer [slot][RT_PASS_WORDS][128*128] (rt_device.h) while ALPHA,
+    // DEPTH or TRIANGLE is on, and the surface buffer [slot][RT_SURF_WORDS][128*128] while NORMAL or ALBEDO is on
+    uint32_t passMask = 0;
+    uint32_t *passBuf = nullptr;
+    uint64_t passBytes = 0;
+    float *surfBuf = nullptr;
+    uint64_t surfBytes = 0;
+    // ray queries through host arrays (rtHipSceneIntersect): one chunk of hits | rays | excluded ids on the device and a pinned host buffer
+    // of the same layout from the staging pool, both made on first use
+    uint32_t queryRays = 0;
+    char *queryDev = nullptr, *queryHost = nullptr;
+    uint64_t queryBytes = 0;
+    // denoiser scratch of rtHipSceneDenoise (gathered inputs, filter scratch, outputs), made on first use while NORMAL and ALBEDO are on
+    char *denoiseBuf = nullptr;
+    uint64_t denoiseBytes = 0;
+    // device time of the last rtHipSceneDenoise: events before the gather, after it, after the guides and after the output
+    hipEvent_t denoiseEv[4] = {};
+    float denoiseMs[3] = {};
+    // ambient occlusion scratch (rtHipSceneAmbientOcclusion*), made on first use: the pixel counters, then one chunk of primary hits; the
+    // event marks the end of the last call that used it, so that a call on another stream waits for it on the device
+    char *aoBuf = nullptr;
+    uint64_t aoBytes = 0;
+    uint32_t aoChunk = 0;
+    hipEvent_t aoDone = nullptr;
+    // ambient occlusion bake scratch (rtHipSceneBakeAmbientOcclusion*), made on first use and grown for a larger map: winners, counters
+    // and a second value plane for W*H texels, the big list, one chunk of texels; the event as above
+    char *bakeBuf = nullptr;
+    uint64_t bakeBytes = 0, bakeTexels = 0;
+    uint32_t bakeChunk = 0;
+    hipEvent_t bakeDone = nullptr;
+    // motion vectors (rtHipSceneMotion*): the reference of the last rtHipSceneMotionMark -- its camera, and a, ab, ac of every triangle in
+    // storage of its own (RT_MOTION_REF_ROWS float4 per triangle), made by the first mark -- and the host entry point's staging (tile-major
+    // motion | t | prevT | triangle, 20 bytes per tile pixel), made on its first use.  marked: the end of the last mark on the scene's
+    // stream; done: the end of the last call that read the reference or used the staging, on whatever stream it ran.
+    struct Motion {
+        bool have = false;
+        rtHipCamera cam{};
+        uint32_t triangles = 0;
+        char *ref = nullptr;
+        uint64_t refBytes = 0;
+        char *stage = nullptr;
+        uint64_t stageBytes = 0;
+        hipEvent_t marked = nullptr, done = nullptr;
+    } motion;
+    // temporal accumulation (rtHipSceneTemporal), made on its first call in one block: two history sets (colour | count | t | triangle;
+    // `cur` is the one the next call reads), this frame's motion and prevT, the gathered colour and the u16 output planes.  valid: the
+    // history set `cur` holds a frame (false after a reset: the next call clears its counts first).
+    // rtHipSceneTemporalVariance adds a block of its own on its first call: two sets of moments (they change places with the history
+    // sets), the variance plane and the filter's il plane.  momentsValid: the moments set `cur` belongs to the history set `cur` (false
+    // after an rtHipSceneTemporal, which does not write them).
+    struct Temporal {
+        char *buf = nullptr;
+        uint64_t bytes = 0;
+        int cur = 0;
+        bool valid = false;
+        char *momentsBuf = nullptr;
+        uint64_t momentsBytes = 0;
+        bool momentsValid = false;
+        hipEvent_t ev[5] = {};
+        float ms[4] = {};
+    } temporal;
+    // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
+    // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
+    // and the sets change places at its end.  listCap: entries each list holds.  log: triangles per thread, per workgroup, entries of the
+    // last move; ms: device time of its count stage and of its fill stage.
+    struct CamMove {
+        char *scratch = nullptr;
+        uint64_t scratchBytes = 0;
+        uint32_t *start[2] = {}, *end[2] = {}, *list[2] = {};
+        uint64_t listCap[2] = {};
+        int live = -1; // the set in use; -1 while the scene still renders from the lists it was created with
+        RtCamMoveArgs args{};
+        hipEvent_t ev[4] = {};
+        uint64_t log[3] = {};
+        double ms[2] = {};
+    } cam;
+    // geometry updates (rtHipSceneSetGeometry), made by the first update: TWO sets of everything the kernels read of the shape (triangle
+    // records, shading rows, planes, cell table, grid starts and list, occupancy words, block table, pair records) -- an update builds into
+    // the set the frames do not read and the sets change places at its end; the parts the scene was created with are freed after the
+    // first update.  pairCap: entries the set's list and pair records hold.  The rest is build scratch that stays: the grid build's space,
+    // staging for host arrays, two index arrays (the retained one and the one being checked), the pair order.
+    struct GeoMove {
+        struct Set {
+            float *triRec = nullptr, *triShade = nullptr, *boxMin = nullptr, *pairRec = nullptr;
+            uint8_t *cellLut = nullptr;
+            uint32_t *gridStart = nullptr, *gridList = nullptr, *sparse = nullptr;
+            unsigned long long *gridBits = nullptr;
+            uint64_t listCap = 0, pairCap = 0; // in bytes
+        } set[2];
+        int live = -1;      // the set in use; -1 while the scene still renders from the parts it was created with
+        RtGridSpace space{};
+        char *vertexBuf = nullptr, *normalBuf = nullptr, *index[2] = {}, *material = nullptr, *pairOrder = nullptr, *pairInfo = nullptr, *denseTmp = nullptr;
+        uint64_t vertexCap = 0, normalCap = 0, indexCap[2] = {}, materialCap = 0, orderCap = 0, infoCap = 0, denseCap = 0; // in bytes
+        int retained = -1;  // which index array the last successful update left; -1: none (creation drops the index array)
+        hipEvent_t ev[5] = {};
+        uint64_t log[6] = {}; // per thread, per workgroup, attempts, pairs, camera entries, allocated
+        double ms[4] = {};
+    } geo;
+
+    template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
+    {
+        void *p = nullptr;
+        const uint64_t n = count ? count : 1;
+        HIP_OK(hipMalloc(&p, n * sizeof(T)));
+        partAllocs[curPart].push_back(p);
+        partSizes[curPart].push_back(n * sizeof(T));
+        partBytes[curPart] += n * sizeof(T);
+        bytes += n * sizeof(T);
+        if (count) {
+            if (!src) return rthost::fail("%s: null pointer with %llu elements", what, (unsigned long long)count);
+            HIP_OK(stager.copy(p, src, count * sizeof(T)));
+        }
+        *dst = (const T *)p;
+        return 0;
+    }
+    template <class T> int alloc(uint64_t count, T **dst)
+    {
+        void *p = nullptr;
+        const uint64_t n = count ? count : 1;
+        HIP_OK(hipMalloc(&p, n * sizeof(T)));
+        partAllocs[curPart].push_back(p);
+        partSizes[curPart].push_back(n * sizeof(T));
+        partBytes[curPart] += n * sizeof(T);
+        bytes += n * sizeof(T);
+        *dst = (T *)p;
+        return 0;
+    }
+    void release_part(int part)
+    {
+        if (partAllocs[part].empty()) return;
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void *p : partAllocs[part]) (void)hipFree(p);
+        partAllocs[part].clear();
+        partSizes[part].clear();
+        bytes -= partBytes[part];
+        partBytes[part] = 0;
+    }
+    // looks at the device-side validation word (after the caller's stream synchronisation)
+    int check_prep()
+    {
+        uint32_t err = 0;
+        HIP_OK(hipMemcpy(&err, prepErr, 4, hipMemcpyDeviceToHost));
+        if (!err) return 0;
+        HIP_OK(hipMemset(prepErr, 0, 4));
+        return rthost::fail("scene rejected (0x%x):%s%s%s%s%s%s", err,
+                    (err & RT_PREP_ERR_TRI_INDEX) ? " a triangle references a vertex that does not exist;" : "",
+                    (err & RT_PREP_ERR_TRI_MATERIAL) ? " a triangle uses a material >= materialCount;" : "",
+                    (err & RT_PREP_ERR_CAM_ENTRY) ? " a camera list entry is not a triangle;" : "",
+                    (err & RT_PREP_ERR_CAM_RANGE) ? " a camera list range exceeds the list size;" : "",
+                    (err & RT_PREP_ERR_GRID_MONOTONE) ? " scenePixelTriangleListStart is not monotone;" : "",
+                    (err & RT_PREP_ERR_GRID_ENTRY) ? " a grid list entry is not a triangle;" : "");
+    }
+};
+
+namespace rthost {
+
+// rt_api.cpp
+RT_INTERNAL int frame_finish(rtHipScene *sc, hipStream_t st, int *redone);
+RT_INTERNAL int query_pointer_ok(int device, const char *whose, const void *p, uint64_t bytes, uint64_t align, const char *what);
+RT_INTERNAL int motion_run(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, bool rowMajor, hipStream_t st);
+
+} // namespace rthost

@@ -2,7 +2,7 @@
 // fetched bilinearly where the motion vectors point, tap by tap validated against the triangle id and prevT, and blended with the new
 // frame, in the exact fp32 arithmetic the header fixes (tests/temporal_oracle.py is the same definition in numpy).
 //
-// Kernels (rt_api.cpp issues them on one stream):
+// Kernels (rt_filters.cpp issues them on one stream):
 //   rtt_gather_kernel      scene path only: the [slot][R,G,B][128*128] u16 tile buffer -> row-major W x H x 3 f32 colour (u16 / 65535);
 //                          rtd_gather_kernel without the surface sums, for scenes that have no surface passes on
 //   rtt_accumulate_kernel  one lane per pixel, a wave is one 8x8 block of the screen (a workgroup is four of them side by side), so under
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void rtt_quantise_kernel(uint32_t n, const flo
 
 } // namespace
 
-// The arrays were checked by the caller (rt_api.cpp): W x H each, W, H in 1..16384, W*H <= 2^27, the outputs overlap nothing.
+// The arrays were checked by the caller (rt_filters.cpp): W x H each, W, H in 1..16384, W*H <= 2^27, the outputs overlap nothing.
 extern "C" hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
                                             const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
                                             const uint32_t *histTriangle, float *outColour, float *outCount, float maxHistory,

@@ -3,7 +3,7 @@
 // local variance and which carries the variance through its iterations (Schied et al. 2017), in the exact fp32 arithmetic the header
 // fixes (tests/variance_oracle.py is the same definition in numpy).  The per-pixel arithmetic is rt_variance_pixel.h's.
 //
-// Kernels, in launch order (rt_api.cpp issues them on one stream):
+// Kernels, in launch order (rt_filters.cpp issues them on one stream):
 //   rtv_moments_kernel    rtt_accumulate_kernel's layout (a wave is one 8x8 block of the screen), with the two moments on the same taps
 //   rtv_guide_kernel      row-major normal and albedo -> the packed guides G0 = (n^.xyz, z ? 1 : 0), G1 = (albedo.rgb, 0)
 //   rtv_estimate_kernel   colour, moments, count and guides -> the state S^0 = (C^0.rgb, V^0) as float4.  A 16x16 workgroup stages the 22x22
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void rtv_output_kernel(uint32_t n, const float
 
 } // namespace
 
-// The arrays were checked by the caller (rt_api.cpp): W x H each, W, H in 1..16384, W*H <= 2^27, the outputs overlap nothing.
+// The arrays were checked by the caller (rt_filters.cpp): W x H each, W, H in 1..16384, W*H <= 2^27, the outputs overlap nothing.
 extern "C" hipError_t rtv_launch_moments(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
                                          const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
                                          const uint32_t *histTriangle, const float *histMoments, float *outColour, float *outCount,

@@ -526,49 +526,28 @@ def denoise(colour, normal, albedo, iterations=DENOISE_DEFAULTS["iterations"], c
     [H, W, 3] float32.  numpy arrays go through rtHipDenoise (host arrays, synchronous).  torch tensors on cuda:`device` go through
     rtHipDenoiseDevice on torch's current stream (or `stream`) with a torch scratch tensor; the result is a tensor on that device."""
     p = denoise_params(iterations, colour_inv_sigma2, albedo_inv_sigma2, normal_power_log2)
-    if any(hasattr(a, "data_ptr") for a in (colour, normal, albedo)):
-        return _denoise_torch(colour, normal, albedo, p, device, stream)
-    c, n, a = (np.ascontiguousarray(v, np.float32) for v in (colour, normal, albedo))
-    if c.ndim != 3 or c.shape[2] != 3 or n.shape != c.shape or a.shape != c.shape:
-        raise ValueError(f"denoise: colour, normal and albedo must all be [H, W, 3] (got {c.shape}, {n.shape}, {a.shape})")
-    out = np.empty_like(c)
-    if lib().rtHipDenoise(device, c.shape[1], c.shape[0], _ptr(c), _ptr(n), _ptr(a), _ptr(out), C.byref(p)) != 0:
-        raise RuntimeError("rtHipDenoise failed: " + last_error())
-    return out
-
-
-def _denoise_torch(colour, normal, albedo, p, device, stream):
-    import torch
-
-    dev = torch.device("cuda", device)
-    ins = []
-    for name, v in (("colour", colour), ("normal", normal), ("albedo", albedo)):
-        if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype != torch.float32:
-            where = f"{v.dtype} on {v.device}" if isinstance(v, torch.Tensor) else type(v).__name__
-            raise ValueError(f"denoise: {name} must be a float32 tensor on {dev}, not {where}")
-        ins.append(v.contiguous())
-    c, n, a = ins
-    if c.dim() != 3 or c.shape[2] != 3 or n.shape != c.shape or a.shape != c.shape:
-        raise ValueError(f"denoise: colour, normal and albedo must all be [H, W, 3] (got {tuple(c.shape)}, {tuple(n.shape)}, {tuple(a.shape)})")
-    H, W = int(c.shape[0]), int(c.shape[1])
+    A = _Arrays("denoise", any(hasattr(v, "data_ptr") for v in (colour, normal, albedo)), device, stream)
+    if A.on_gpu:
+        c, n, a = (v.contiguous() if isinstance(v, A.torch.Tensor) else v for v in (colour, normal, albedo))
+    else:
+        c, n, a = (np.ascontiguousarray(v, np.float32) for v in (colour, normal, albedo))
+    shape, *others = (tuple(getattr(v, "shape", ())) for v in (c, n, a))
+    if len(shape) != 3 or shape[2] != 3 or any(sh != shape for sh in others):
+        raise ValueError(f"denoise: colour, normal and albedo must all be [H, W, 3] (got {shape}, {others[0]}, {others[1]})")
+    for name, v in (("colour", c), ("normal", n), ("albedo", a)):
+        A.check(name, v, shape)
+    (H, W), out = shape[:2], A.new(shape)
+    if not A.on_gpu:
+        if lib().rtHipDenoise(device, W, H, _ptr(c), _ptr(n), _ptr(a), _ptr(out), C.byref(p)) != 0:
+            raise RuntimeError("rtHipDenoise failed: " + last_error())
+        return out
     nbytes = lib().rtHipDenoiseScratchBytes(W, H)
     if nbytes == 0:
         raise ValueError(f"denoise: a {W} x {H} image is not 1..2^27 pixels")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    out = torch.empty_like(c)
-    cur = torch.cuda.current_stream(dev)
-    run = torch.cuda.ExternalStream(stream, device=dev) if stream and stream != cur.cuda_stream else cur
-    if run is not cur:
-        run.wait_stream(cur)
-    rc = lib().rtHipDenoiseDevice(device, W, H, C.c_void_p(c.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(a.data_ptr()),
-                                  C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes, C.byref(p),
-                                  C.c_void_p(run.cuda_stream) if run.cuda_stream else None)
-    if rc != 0:
+    scratch = A.new(nbytes, np.uint8)
+    if lib().rtHipDenoiseDevice(device, W, H, *[A.address(v) for v in (c, n, a, out, scratch)], nbytes, C.byref(p), A.stream_arg()) != 0:
         raise RuntimeError("rtHipDenoiseDevice failed: " + last_error())
-    if run is not cur:
-        cur.wait_stream(run)
-        for buf in (c, n, a, out, scratch):
-            buf.record_stream(run)
+    A.done([c, n, a, out, scratch])
     return out
 
 
@@ -594,52 +573,27 @@ def temporal(colour, motion, prev_t, triangle, history, max_history=TEMPORAL_DEF
     missing = [k for k, _, _ in _TEMPORAL_HISTORY if k not in history]
     if missing:
         raise ValueError(f"temporal: history lacks {missing}")
-    given = [("", name, v, ch, ids) for (name, ch, ids), v in zip(_TEMPORAL_INPUTS, (colour, motion, prev_t, triangle))]
-    given += [("history ", name, history[name], ch, ids) for name, ch, ids in _TEMPORAL_HISTORY]
+    given = [(name, v, ch, ids) for (name, ch, ids), v in zip(_TEMPORAL_INPUTS, (colour, motion, prev_t, triangle))]
+    given += [("history " + name, history[name], ch, ids) for name, ch, ids in _TEMPORAL_HISTORY]
     if out is not None and ("colour" not in out or any(k not in ("colour", "count") for k in out)):
         raise ValueError(f"temporal: out takes 'colour' and optionally 'count' (got {sorted(out)})")
-    on_gpu = any(hasattr(v, "data_ptr") for _, _, v, _, _ in given)
-    shape = tuple(colour.shape[:2])
     if len(colour.shape) != 3 or colour.shape[2] != 3:
         raise ValueError(f"temporal: colour must be [H, W, 3] (got {tuple(colour.shape)})")
-    H, W = int(shape[0]), int(shape[1])
-    if on_gpu:
-        import torch
-
-        dev = torch.device("cuda", device)
-        f32, ids32, new = (torch.float32,), (torch.uint32, torch.int32), lambda sh: torch.empty(sh, dtype=torch.float32, device=dev)
-        good = lambda v, sh, kinds: isinstance(v, torch.Tensor) and v.device == dev and v.dtype in kinds and tuple(v.shape) == sh and v.is_contiguous()
-        address = lambda v: C.c_void_p(v.data_ptr())
-    else:
-        f32, ids32, new = (np.dtype(np.float32),), (np.dtype(np.uint32),), lambda sh: np.empty(sh, np.float32)
-        good = lambda v, sh, kinds: isinstance(v, np.ndarray) and v.dtype in kinds and v.shape == sh and v.flags.c_contiguous
-        address = _ptr
-    for prefix, name, v, ch, ids in given:
-        want = shape + (ch,) if ch > 1 else shape
-        if not good(v, want, ids32 if ids else f32):
-            raise ValueError(f"temporal: {prefix}{name} must be a contiguous {'uint32' if ids else 'float32'} {want} "
-                             f"{'tensor on ' + str(dev) if on_gpu else 'array'}")
-    res = dict(out) if out is not None else {"colour": new(shape + (3,)), "count": new(shape)}
+    shape = (int(colour.shape[0]), int(colour.shape[1]))
+    A = _Arrays("temporal", any(hasattr(v, "data_ptr") for _, v, _, _ in given), device, stream)
+    for name, v, ch, ids in given:
+        A.check(name, v, shape + (ch,) if ch > 1 else shape, ids)
+    res = dict(out) if out is not None else {"colour": A.new(shape + (3,)), "count": A.new(shape)}
     for name, v in res.items():
-        want = shape + (3,) if name == "colour" else shape
-        if not good(v, want, f32):
-            raise ValueError(f"temporal: out[{name!r}] must be a contiguous float32 {want} {'tensor on ' + str(dev) if on_gpu else 'array'}")
-    ptrs = [address(v) for _, _, v, _, _ in given] + [address(res["colour"]), address(res["count"]) if "count" in res else None]
-    if not on_gpu:
-        if lib().rtHipTemporal(device, W, H, *ptrs, C.byref(p)) != 0:
+        A.check(f"out[{name!r}]", v, shape + (3,) if name == "colour" else shape)
+    ptrs = [A.address(v) for _, v, _, _ in given] + [A.address(res["colour"]), A.address(res.get("count"))]
+    if not A.on_gpu:
+        if lib().rtHipTemporal(device, shape[1], shape[0], *ptrs, C.byref(p)) != 0:
             raise RuntimeError("rtHipTemporal failed: " + last_error())
         return res
-    cur = torch.cuda.current_stream(dev)
-    run = torch.cuda.ExternalStream(stream, device=dev) if stream and stream != cur.cuda_stream else cur
-    if run is not cur:
-        run.wait_stream(cur)
-    rc = lib().rtHipTemporalDevice(device, W, H, *ptrs, C.byref(p), C.c_void_p(run.cuda_stream) if run.cuda_stream else None)
-    if rc != 0:
+    if lib().rtHipTemporalDevice(device, shape[1], shape[0], *ptrs, C.byref(p), A.stream_arg()) != 0:
         raise RuntimeError("rtHipTemporalDevice failed: " + last_error())
-    if run is not cur:
-        cur.wait_stream(run)
-        for buf in [v for _, _, v, _, _ in given] + list(res.values()):
-            buf.record_stream(run)
+    A.done([v for _, v, _, _ in given] + list(res.values()))
     return res
 
 
@@ -654,8 +608,8 @@ def variance_params(iterations=VARIANCE_DEFAULTS["iterations"], luminance_sigma2
 
 
 class _Arrays:
-    """What temporal_moments and denoise_variance need of their arrays, for numpy (host entry point) or torch on cuda:`device` (device
-    entry point on torch's current stream or `stream`)."""
+    """What denoise, temporal, temporal_moments and denoise_variance need of their arrays, for numpy (host entry point) or torch on
+    cuda:`device` (device entry point on torch's current stream or `stream`)."""
 
     def __init__(self, who, on_gpu, device, stream):
         self.who, self.on_gpu, self.device = who, on_gpu, device

@@ -15,8 +15,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("rt_kernels", "rt_wavefront", "rt_build_device", "rt_kat", "rt_scene_prep", "rt_denoise", "rt_temporal", "rt_camera_move",
-           "rt_geometry_move")
+SOURCES = ("rt_kernels", "rt_wavefront", "rt_build_device", "rt_kat", "rt_scene_prep", "rt_denoise", "rt_temporal", "rt_variance",
+           "rt_camera_move", "rt_geometry_move")
 
 
 def devflags(tree):
