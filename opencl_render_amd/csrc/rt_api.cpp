@@ -355,13 +355,8 @@ int build_lights(rtHipScene *sc, const rtHipSceneDesc *d)
 // wavefront pipeline buffers: worst case every pixel of every sample in a batch becomes a path
 int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
 {
-    for (auto &G : sc->groups) {
-        if (G.hostCount) (void)hipHostFree(G.hostCount);
-        if (G.hostStatus) (void)hipHostFree(G.hostStatus);
-        if (G.hostLog) (void)hipHostFree(G.hostLog);
-        if (G.stream) { (void)hipStreamSynchronize(G.stream); (void)hipStreamDestroy(G.stream); }
-        if (G.done) (void)hipEventDestroy(G.done);
-    }
+    for (auto &G : sc->groups)
+        if (G.stream) (void)hipStreamSynchronize(G.stream);
     sc->groups.clear();
     sc->release_part(PART_WAVEFRONT);
     sc->curPart = PART_WAVEFRONT;
@@ -397,14 +392,14 @@ int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
     if (groupCount > nt) groupCount = nt ? (uint32_t)nt : 1u;
     const bool multiLight = D.lightCount > 1;
     sc->wfMultiLight = multiLight;
-    if (!sc->forkEvent) HIP_OK(hipEventCreateWithFlags(&sc->forkEvent, hipEventDisableTiming));
+    HIP_OK(sc->forkEvent.make(hipEventDisableTiming));
     sc->groups.resize(groupCount);
     for (uint32_t g = 0; g < groupCount; ++g) {
         rtHipScene::Group &G = sc->groups[g];
         const uint32_t slot0 = (uint32_t)((uint64_t)nt * g / groupCount), slot1 = (uint32_t)((uint64_t)nt * (g + 1) / groupCount);
         G.slot0 = slot0; G.slot1 = slot1;
-        if (g > 0) HIP_OK(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
+        if (g > 0) HIP_OK(G.stream.make(hipStreamNonBlocking));
+        HIP_OK(G.done.make(hipEventDisableTiming));
         // queue slices: the primary kernel's workgroups are dealt to the shards round-robin, 256 paths each at most
         const uint64_t gpix = (uint64_t)(slot1 - slot0) * RT_TILE_PIXELS;
         const uint64_t primaryBlocks = (uint64_t)(slot1 - slot0) * 64 * sb;
@@ -433,11 +428,11 @@ int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
             sc->alloc<uint32_t>((uint64_t)3 * RT_WF_CTL_WORDS, &Wf.ctl))
             return -1;
         HIP_OK(hipMemsetAsync(Wf.ctl, 0, sizeof(uint32_t) * 3 * RT_WF_CTL_WORDS, sc->stream));
-        HIP_OK(hipHostMalloc((void **)&G.hostLog, sizeof(uint4) * RT_WF_ROUND_LOG, hipHostMallocMapped));
+        HIP_OK(G.hostLog.make(sizeof(uint4) * RT_WF_ROUND_LOG, hipHostMallocMapped));
         memset(G.hostLog, 0, sizeof(uint4) * RT_WF_ROUND_LOG);
         HIP_OK(hipHostGetDevicePointer((void **)&Wf.roundLog, G.hostLog, 0));
-        HIP_OK(hipHostMalloc((void **)&G.hostCount, sizeof(uint32_t) * RT_WF_SHARDS, hipHostMallocDefault));
-        HIP_OK(hipHostMalloc((void **)&G.hostStatus, sizeof(uint32_t) * RT_WF_STATUS_WORDS, hipHostMallocMapped));
+        HIP_OK(G.hostCount.make(sizeof(uint32_t) * RT_WF_SHARDS, hipHostMallocDefault));
+        HIP_OK(G.hostStatus.make(sizeof(uint32_t) * RT_WF_STATUS_WORDS, hipHostMallocMapped));
         memset(G.hostStatus, 0, sizeof(uint32_t) * RT_WF_STATUS_WORDS);
         HIP_OK(hipHostGetDevicePointer((void **)&Wf.hostStatus, G.hostStatus, 0));
         Wf.spinLimit = T.spinLimit ? T.spinLimit : 16384u;
@@ -538,7 +533,7 @@ int scene_build(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds,
     if (d->axesDiv != RT_GRID_DIV) return fail("axesDivCount %d unsupported (the reference builds %d, trianglelist.h:110)", d->axesDiv, RT_GRID_DIV);
     if ((uint64_t)d->width * d->height > 0xffffffffull) return fail("image too large");
     HIP_OK(hipSetDevice(sc->device));
-    HIP_OK(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
+    HIP_OK(sc->stream.make(hipStreamNonBlocking));
     sc->tune = tune;
     sc->pipeline = tune.pipeline == RT_HIP_PIPELINE_MEGAKERNEL ? RT_HIP_PIPELINE_MEGAKERNEL : RT_HIP_PIPELINE_WAVEFRONT;
     if (sc->stager.init(sc->stream, tune) != 0) return -1;
@@ -652,11 +647,11 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
         if (!sc->stageTiming) return launch();
         if (sc->stageEventsUsed == sc->stageEvents.size()) {
             rtHipScene::StageEvent e{};
-            hipError_t er = hipEventCreate(&e.a);
+            hipError_t er = e.a.make();
             if (er != hipSuccess) return er;
-            er = hipEventCreate(&e.b);
+            er = e.b.make();
             if (er != hipSuccess) return er;
-            sc->stageEvents.push_back(e);
+            sc->stageEvents.push_back(std::move(e));
         }
         rtHipScene::StageEvent &e = sc->stageEvents[sc->stageEventsUsed++];
         e.stage = which;
@@ -908,7 +903,7 @@ int rthost::motion_run(rtHipScene *sc, void *motion, void *t, void *prevT, void 
     rtHipScene::Motion &M = sc->motion;
     RtMotionArgs A;
     for (int i = 0; i < 3; ++i) { A.eye[i] = M.cam.eye[i]; A.topLeft[i] = M.cam.eyeToTopLeft[i]; A.lr[i] = M.cam.leftToRight[i]; A.tb[i] = M.cam.topToBottom[i]; }
-    A.ref = (const float4 *)M.ref;
+    A.ref = M.ref;
     A.motion = (float *)motion; A.t = (float *)t; A.prevT = (float *)prevT; A.triangle = (uint32_t *)triangle;
     A.rowMajor = rowMajor ? 1u : 0u; A.fastQuotient = sc->tune.fastQuotient ? 1u : 0u;
     if (st != sc->stream) HIP_OK(hipStreamWaitEvent(st, M.marked, 0));
@@ -960,63 +955,7 @@ rtHipScene *rtHipSceneCreateLike(int device, const rtHipSceneDesc *desc, const c
 
 void rtHipSceneDestroy(rtHipScene *sc)
 {
-    if (!sc) return;
-    if (sc->device >= 0) (void)hipSetDevice(sc->device);
-    if (sc->stream) (void)hipStreamSynchronize(sc->stream);
-    for (auto &e : sc->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto &e : sc->stageEvents) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (auto &G : sc->groups) {
-        if (G.hostCount) (void)hipHostFree(G.hostCount);
-        if (G.hostStatus) (void)hipHostFree(G.hostStatus);
-        if (G.hostLog) (void)hipHostFree(G.hostLog);
-        if (G.stream) { (void)hipStreamSynchronize(G.stream); (void)hipStreamDestroy(G.stream); }
-        if (G.done) (void)hipEventDestroy(G.done);
-    }
-    if (sc->forkEvent) (void)hipEventDestroy(sc->forkEvent);
-    if (sc->passBuf) (void)hipFree(sc->passBuf);
-    if (sc->surfBuf) (void)hipFree(sc->surfBuf);
-    if (sc->denoiseBuf) (void)hipFree(sc->denoiseBuf);
-    for (hipEvent_t e : sc->denoiseEv)
-        if (e) (void)hipEventDestroy(e);
-    if (sc->queryDev) (void)hipFree(sc->queryDev);
-    if (sc->queryHost) Stager::pool().give(sc->queryHost, sc->queryBytes);
-    if (sc->aoBuf) (void)hipFree(sc->aoBuf);
-    if (sc->aoDone) (void)hipEventDestroy(sc->aoDone);
-    if (sc->bakeBuf) (void)hipFree(sc->bakeBuf);
-    if (sc->bakeDone) (void)hipEventDestroy(sc->bakeDone);
-    if (sc->motion.ref) (void)hipFree(sc->motion.ref);
-    if (sc->motion.stage) (void)hipFree(sc->motion.stage);
-    if (sc->motion.marked) (void)hipEventDestroy(sc->motion.marked);
-    if (sc->motion.done) (void)hipEventDestroy(sc->motion.done);
-    if (sc->temporal.buf) (void)hipFree(sc->temporal.buf);
-    if (sc->temporal.momentsBuf) (void)hipFree(sc->temporal.momentsBuf);
-    for (hipEvent_t e : sc->temporal.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (sc->cam.scratch) (void)hipFree(sc->cam.scratch);
-    for (int i = 0; i < 2; ++i) {
-        if (sc->cam.start[i]) (void)hipFree(sc->cam.start[i]);
-        if (sc->cam.end[i]) (void)hipFree(sc->cam.end[i]);
-        if (sc->cam.list[i]) (void)hipFree(sc->cam.list[i]);
-    }
-    for (hipEvent_t e : sc->cam.ev)
-        if (e) (void)hipEventDestroy(e);
-    {
-        rtHipScene::GeoMove &G = sc->geo;
-        for (auto &L : G.set)
-            for (void *p : { (void *)L.triRec, (void *)L.triShade, (void *)L.boxMin, (void *)L.pairRec, (void *)L.cellLut, (void *)L.gridStart, (void *)L.gridList,
-                             (void *)L.sparse, (void *)L.gridBits })
-                if (p) (void)hipFree(p);
-        for (void *p : { (void *)G.vertexBuf, (void *)G.normalBuf, (void *)G.index[0], (void *)G.index[1], (void *)G.material, (void *)G.pairOrder, (void *)G.pairInfo,
-                         (void *)G.denseTmp })
-            if (p) (void)hipFree(p);
-        rt_grid_space_free(&G.space);
-        for (hipEvent_t e : G.ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (int part = 0; part < PART_COUNT; ++part) sc->release_part(part);
-    sc->stager.destroy();
-    if (sc->stream) (void)hipStreamDestroy(sc->stream);
-    delete sc;
+    if (sc) delete sc;
 }
 
 uint64_t rtHipSceneBytes(const rtHipScene *sc) { return sc ? sc->bytes : 0; }
@@ -1054,24 +993,21 @@ static int cam_move_init(rtHipScene *sc)
     auto up = [](uint64_t v) { return (v + 255) & ~(uint64_t)255; };
     const uint64_t oTables = 0, oCtl = up(tables.size() * 4), oPos = oCtl + 256, oCount = oPos + up(T * 24), oBig = oCount + up(pixels * 4),
                    oScan = oBig + up(T * 4), total = oScan + up(scanBytes ? scanBytes : 1);
-    char *block = nullptr;
-    uint32_t *r[4] = {};
+    // made here and handed to the scene -- and counted -- when all of it is there
+    Dev<> block;
+    Dev<uint32_t> r[4];
+    Event ev[4];
+    uint64_t uncounted = 0;
     const uint64_t rangeBytes = pixels ? pixels * 4 : 4;
-    bool ok = hipMalloc((void **)&block, total) == hipSuccess;
-    for (int i = 0; ok && i < 4; ++i) ok = hipMalloc((void **)&r[i], rangeBytes) == hipSuccess;
-    if (ok) ok = hipMemcpy(block + oTables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    for (int i = 0; ok && i < 4; ++i) ok = hipEventCreate(&C.ev[i]) == hipSuccess;
-    if (!ok) {
-        const hipError_t e = hipGetLastError();
+    hipError_t e = block.make(total, uncounted);
+    for (int i = 0; e == hipSuccess && i < 4; ++i) e = r[i].make(rangeBytes, uncounted);
+    if (e == hipSuccess) e = hipMemcpy(block + oTables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice);
+    for (int i = 0; e == hipSuccess && i < 4; ++i) e = ev[i].make();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
         fail("rtHipSceneSetCamera: the build storage (%llu bytes) could not be made: %s", (unsigned long long)(total + 4 * rangeBytes), hipGetErrorString(e));
-        if (block) (void)hipFree(block);
-        for (uint32_t *p : r) if (p) (void)hipFree(p);
-        for (hipEvent_t &e2 : C.ev) { if (e2) (void)hipEventDestroy(e2); e2 = nullptr; }
         return -4;
     }
-    C.scratch = block; C.scratchBytes = total;
-    C.start[0] = r[0]; C.end[0] = r[1]; C.start[1] = r[2]; C.end[1] = r[3];
-    sc->bytes += total + 4 * rangeBytes;
     RtCamMoveArgs &A = C.args;
     A.width = sc->width; A.height = sc->height; A.tilesX = tilesX; A.triangleCount = D.triangleCount; A.pixels = (uint32_t)pixels;
     A.triRec = D.triRec; A.triShade = D.triShade;
@@ -1079,6 +1015,12 @@ static int cam_move_init(rtHipScene *sc)
     A.firstSlot = repeats ? A.slotOf + (size_t)tilesX * tilesY : nullptr;
     A.ctl = (RtCamMoveCtl *)(block + oCtl); A.pos = block + oPos; A.count = (uint32_t *)(block + oCount); A.bigList = (uint32_t *)(block + oBig);
     A.scanTmp = block + oScan; A.scanBytes = scanBytes;
+    C.scratch.adopt(std::move(block), sc->bytes);
+    for (int i = 0; i < 2; ++i) {
+        C.start[i].adopt(std::move(r[2 * i]), sc->bytes);
+        C.end[i].adopt(std::move(r[2 * i + 1]), sc->bytes);
+    }
+    for (int i = 0; i < 4; ++i) C.ev[i] = std::move(ev[i]);
     return 0;
 }
 
@@ -1086,15 +1028,8 @@ static int cam_move_init(rtHipScene *sc)
 // buffer is only ever replaced by a larger one; `exact`: of just `entries` entries (the other set's capacity).  The caller has made sure no work reads set `i`.
 static bool cam_move_list(rtHipScene *sc, int i, uint64_t entries, bool exact = false)
 {
-    rtHipScene::CamMove &C = sc->cam;
-    if (C.listCap[i] >= entries && C.list[i]) return true;
     const uint64_t cap = exact ? entries : std::min<uint64_t>(std::max<uint64_t>(entries + entries / 8, 1024), 0xffffffffull);
-    uint32_t *p = nullptr;
-    if (hipMalloc((void **)&p, cap * 4) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (C.list[i]) { (void)hipFree(C.list[i]); sc->bytes -= C.listCap[i] * 4; }
-    C.list[i] = p; C.listCap[i] = cap;
-    sc->bytes += cap * 4;
-    return true;
+    return sc->cam.list[i].fit(entries * 4, cap * 4, sc->bytes) == hipSuccess;
 }
 
 // The lists of camera `cam` over the triangles in triRec / triShade, built into the set the frames do not read (*target) on the idle
@@ -1150,7 +1085,7 @@ static void cam_move_commit(rtHipScene *sc, const rtHipCamera *cam, int target, 
     sc->release_part(PART_CAMERA); // the lists the scene was created with (the first move only)
     // the other list is made as large as this one now, so that the next move to a view of no more entries allocates nothing; if that
     // fails the move has succeeded all the same and the next one tries again
-    (void)cam_move_list(sc, target ^ 1, C.listCap[target], true);
+    (void)cam_move_list(sc, target ^ 1, C.list[target].size / 4, true);
 }
 
 int rtHipSceneSetCamera(rtHipScene *sc, const rtHipCamera *cam)
@@ -1220,9 +1155,9 @@ int rtHipRenderTiles(rtHipScene *sc, void *stream)
     hipStream_t st = stream ? (hipStream_t)stream : sc->stream;
     sc->lastStream = st;
     if (sc->eventsUsed == sc->events.size()) {
-        hipEvent_t a, b;
-        HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b));
-        sc->events.emplace_back(a, b);
+        Event a, b;
+        HIP_OK(a.make()); HIP_OK(b.make());
+        sc->events.emplace_back(std::move(a), std::move(b));
     }
     auto &ev = sc->events[sc->eventsUsed++];
     HIP_OK(hipEventRecord(ev.first, st));
@@ -1250,22 +1185,15 @@ int rtHipSetPipeline(rtHipScene *sc, int pipeline)
 
 // One of the two pass buffers: made (zeroed) when `want` and absent, freed when not `want` -- after a sync, frames in flight may still
 // write it.  Counted in rtHipSceneBytes.
-static int keep_pass_buffer(rtHipScene *sc, bool want, void **buf, uint64_t &bytes, uint32_t words)
+static int keep_pass_buffer(rtHipScene *sc, bool want, DevBlock &buf, uint32_t words)
 {
-    if (!want && *buf) {
+    if (!want && buf.p) {
         HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipFree(*buf));
-        sc->bytes -= bytes;
-        *buf = nullptr;
-        bytes = 0;
-    } else if (want && !*buf) {
-        const uint64_t n = (uint64_t)sc->tileIds.size() * words * RT_TILE_PIXELS * 4;
-        void *p = nullptr;
-        HIP_OK(hipMalloc(&p, n ? n : 4));
-        HIP_OK(hipMemset(p, 0, n ? n : 4));
-        *buf = p;
-        bytes = n ? n : 4;
-        sc->bytes += bytes;
+        buf.drop(sc->bytes);
+    } else if (want && !buf.p) {
+        const uint64_t n = std::max<uint64_t>((uint64_t)sc->tileIds.size() * words * RT_TILE_PIXELS * 4, 4);
+        HIP_OK(buf.make(n, sc->bytes));
+        HIP_OK(hipMemset(buf.p, 0, n));
     }
     return 0;
 }
@@ -1276,22 +1204,19 @@ int rtHipScenePasses(rtHipScene *sc, cl_uint mask)
     if (mask & ~(cl_uint)(RT_PASS_BUF_BITS | RT_SURF_BUF_BITS)) return fail("unknown render pass bits 0x%x", mask);
     if (mask && sc->pipeline == RT_HIP_PIPELINE_MEGAKERNEL) return fail("render passes need the wavefront pipeline (the scene is on the megakernel)");
     HIP_OK(hipSetDevice(sc->device));
-    if (keep_pass_buffer(sc, (mask & RT_PASS_BUF_BITS) != 0, (void **)&sc->passBuf, sc->passBytes, RT_PASS_WORDS) != 0) return -1;
-    if (keep_pass_buffer(sc, (mask & RT_SURF_BUF_BITS) != 0, (void **)&sc->surfBuf, sc->surfBytes, RT_SURF_WORDS) != 0) return -1;
+    if (keep_pass_buffer(sc, (mask & RT_PASS_BUF_BITS) != 0, sc->passBuf, RT_PASS_WORDS) != 0) return -1;
+    if (keep_pass_buffer(sc, (mask & RT_SURF_BUF_BITS) != 0, sc->surfBuf, RT_SURF_WORDS) != 0) return -1;
     if ((mask & RT_SURF_BUF_BITS) != RT_SURF_BUF_BITS && sc->denoiseBuf) { // the denoiser needs both surface passes
         HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipFree(sc->denoiseBuf));
-        sc->bytes -= sc->denoiseBytes;
-        sc->denoiseBuf = nullptr;
-        sc->denoiseBytes = 0;
+        sc->denoiseBuf.drop(sc->bytes);
     }
     sc->passMask = mask;
     return 0;
 }
 
-void *rtHipPassBuffer(rtHipScene *sc) { return sc ? (void *)sc->passBuf : nullptr; }
+void *rtHipPassBuffer(rtHipScene *sc) { return sc ? sc->passBuf.p : nullptr; }
 uint64_t rtHipPassBufferBytes(const rtHipScene *sc) { return sc && sc->passBuf ? (uint64_t)sc->tileIds.size() * RT_PASS_WORDS * RT_TILE_PIXELS * 4 : 0; }
-void *rtHipSurfaceBuffer(rtHipScene *sc) { return sc ? (void *)sc->surfBuf : nullptr; }
+void *rtHipSurfaceBuffer(rtHipScene *sc) { return sc ? sc->surfBuf.p : nullptr; }
 uint64_t rtHipSurfaceBufferBytes(const rtHipScene *sc) { return sc && sc->surfBuf ? (uint64_t)sc->tileIds.size() * RT_SURF_WORDS * RT_TILE_PIXELS * 4 : 0; }
 
 // Diagnostic: raw copy of the 8 device-side debug counters (work counters of the counted kernel, or the cycle sums of
@@ -1520,11 +1445,8 @@ int rtHipSceneIntersect(rtHipScene *sc, const rtHipRay *rays, const cl_uint *exc
         const uint64_t bytes = (uint64_t)chunk * (sizeof(rtHipRay) + 4 + sizeof(rtHipHit));
         char *host = Stager::pool().take(bytes);
         if (!host) return fail("rtHipSceneIntersect: no pinned staging buffer of %llu bytes", (unsigned long long)bytes);
-        void *dev = nullptr;
-        const hipError_t e = hipMalloc(&dev, bytes);
-        if (e != hipSuccess) { Stager::pool().give(host, bytes); return fail("rtHipSceneIntersect: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e)); }
-        sc->queryRays = chunk; sc->queryHost = host; sc->queryDev = (char *)dev; sc->queryBytes = bytes;
-        sc->bytes += bytes;
+        if (scene_block(sc, sc->queryDev, bytes, "rtHipSceneIntersect") != 0) { Stager::pool().give(host, bytes); return -1; }
+        sc->queryRays = chunk; sc->queryHost = host;
     }
     const uint64_t chunk = sc->queryRays;
     // hits | rays | excluded ids: the two 16-byte records stay 16-byte aligned whatever the chunk
@@ -1574,15 +1496,11 @@ static int ao_run(rtHipScene *sc, const rtHipAoParams *p, float *out, bool rowMa
     if (!sc->aoBuf) {
         const uint32_t chunk = std::max<uint32_t>(sc->tune.aoSamples, 1u);
         const uint64_t bytes = counterBytes + 256 + (uint64_t)chunk * 32; // counters | hit list length | hit list
-        void *buf = nullptr;
-        const hipError_t e = hipMalloc(&buf, bytes);
-        if (e != hipSuccess) return fail("ambient occlusion: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        const hipError_t ee = hipEventCreateWithFlags(&sc->aoDone, hipEventDisableTiming);
-        if (ee != hipSuccess) { (void)hipFree(buf); sc->aoDone = nullptr; return fail("ambient occlusion: hipEventCreate failed: %s", hipGetErrorString(ee)); }
-        sc->aoBuf = (char *)buf; sc->aoBytes = bytes; sc->aoChunk = chunk;
-        sc->bytes += bytes;
+        // (the event first: one that is left without its scratch is harmless and is found again by the next call)
+        if (scene_event(sc->aoDone, hipEventDisableTiming, "ambient occlusion") != 0 || scene_block(sc, sc->aoBuf, bytes, "ambient occlusion") != 0) return -1;
+        sc->aoChunk = chunk;
     } else HIP_OK(hipStreamWaitEvent(st, sc->aoDone, 0)); // the last call's use of the scratch, on whatever stream it ran
-    uint32_t *counter = (uint32_t *)sc->aoBuf;
+    uint32_t *counter = sc->aoBuf.as<uint32_t>();
     HIP_OK(hipMemsetAsync(counter, 0, pixels * 4, st));
     RtAoArgs A;
     A.raysPerHit = p->raysPerHit; A.pixelSamples = p->pixelSamples; A.seed = p->seed; A.fastQuotient = sc->tune.fastQuotient ? 1u : 0u;
@@ -1634,20 +1552,10 @@ int rtHipSceneMotionMark(rtHipScene *sc)
     const uint32_t T = sc->dev.triangleCount;
     if (!M.ref) {
         const uint64_t bytes = std::max<uint64_t>((uint64_t)T * RT_MOTION_REF_ROWS * 16, 16);
-        hipEvent_t ev[2] = { nullptr, nullptr };
-        void *buf = nullptr;
-        const hipError_t e = hipMalloc(&buf, bytes);
-        if (e != hipSuccess) return fail("rtHipSceneMotionMark: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        for (hipEvent_t &v : ev) {
-            const hipError_t ee = hipEventCreateWithFlags(&v, hipEventDisableTiming);
-            if (ee != hipSuccess) {
-                (void)hipFree(buf);
-                if (ev[0]) (void)hipEventDestroy(ev[0]);
-                return fail("rtHipSceneMotionMark: hipEventCreate failed: %s", hipGetErrorString(ee));
-            }
-        }
-        M.ref = (char *)buf; M.refBytes = bytes; M.triangles = T; M.marked = ev[0]; M.done = ev[1];
-        sc->bytes += bytes;
+        static const char who[] = "rtHipSceneMotionMark"; // (the events first, as in ao_run)
+        if (scene_event(M.marked, hipEventDisableTiming, who) != 0 || scene_event(M.done, hipEventDisableTiming, who) != 0 || scene_block(sc, M.ref, bytes, who) != 0)
+            return -1;
+        M.triangles = T;
     } else {
         if (T != M.triangles) return fail("rtHipSceneMotionMark: the scene has %u triangles, the reference was made for %u", T, M.triangles);
         HIP_OK(hipStreamWaitEvent(sc->stream, M.done, 0)); // calls on other streams that still read the old reference
@@ -1698,11 +1606,7 @@ int rtHipSceneMotion(rtHipScene *sc, cl_float *motion, cl_float *t, cl_float *pr
     const size_t n = sc->tileIds.size() * (size_t)RT_TILE_PIXELS;
     if (!M.stage) {
         const uint64_t bytes = std::max<uint64_t>((uint64_t)n * 20, 16);
-        void *buf = nullptr;
-        const hipError_t e = hipMalloc(&buf, bytes);
-        if (e != hipSuccess) return fail("motion vectors: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        M.stage = (char *)buf; M.stageBytes = bytes;
-        sc->bytes += bytes;
+        if (scene_block(sc, M.stage, bytes, "motion vectors") != 0) return -1;
     }
     // tile-major planes in AO order: motion | t | prevT | triangle; the host stores the scene's pixels
     char *dMotion = M.stage, *dT = M.stage + n * 8, *dPrev = M.stage + n * 12, *dTri = M.stage + n * 16;
@@ -1764,25 +1668,18 @@ static int bake_run(rtHipScene *sc, const rtHipBakeParams *p, float *ao, uint32_
     const uint64_t bigBytes = ((uint64_t)T * 4 + 255) & ~255ull;
     if (!sc->bakeBuf || texels > sc->bakeTexels || chunkWant != sc->bakeChunk) {
         const uint64_t cap = std::max<uint64_t>(texels, sc->bakeTexels), capPlane = (cap * 4 + 255) & ~255ull;
-        if (sc->bakeBuf) { // a larger map: the last call's use of the old scratch ends first
+        if (sc->bakeBuf) { // a larger map: the last call's use of the old scratch ends first, and the scratch goes before the larger one is made
             HIP_OK(hipEventSynchronize(sc->bakeDone));
-            (void)hipFree(sc->bakeBuf);
-            sc->bytes -= sc->bakeBytes;
-            sc->bakeBuf = nullptr; sc->bakeBytes = 0; sc->bakeTexels = 0;
+            sc->bakeBuf.drop(sc->bytes);
+            sc->bakeTexels = 0;
         }
         const uint64_t bytes = 3 * capPlane + bigBytes + 256 + (uint64_t)chunkWant * 32; // win | counter | values | big list | lengths | hit list
-        void *buf = nullptr;
-        const hipError_t e = hipMalloc(&buf, bytes);
-        if (e != hipSuccess) return fail("ambient occlusion bake: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        if (!sc->bakeDone) {
-            const hipError_t ee = hipEventCreateWithFlags(&sc->bakeDone, hipEventDisableTiming);
-            if (ee != hipSuccess) { (void)hipFree(buf); sc->bakeDone = nullptr; return fail("ambient occlusion bake: hipEventCreate failed: %s", hipGetErrorString(ee)); }
-        }
-        sc->bakeBuf = (char *)buf; sc->bakeBytes = bytes; sc->bakeTexels = cap; sc->bakeChunk = chunkWant;
-        sc->bytes += bytes;
+        static const char who[] = "ambient occlusion bake"; // (the event first, as in ao_run)
+        if (scene_event(sc->bakeDone, hipEventDisableTiming, who) != 0 || scene_block(sc, sc->bakeBuf, bytes, who) != 0) return -1;
+        sc->bakeTexels = cap; sc->bakeChunk = chunkWant;
     } else HIP_OK(hipStreamWaitEvent(st, sc->bakeDone, 0)); // the last call's use of the scratch, on whatever stream it ran
     const uint64_t capPlane = (sc->bakeTexels * 4 + 255) & ~255ull;
-    uint32_t *win = (uint32_t *)sc->bakeBuf, *counter = (uint32_t *)(sc->bakeBuf + capPlane);
+    uint32_t *win = sc->bakeBuf.as<uint32_t>(), *counter = (uint32_t *)(sc->bakeBuf + capPlane);
     float *values = (float *)(sc->bakeBuf + 2 * capPlane);
     char *tail = sc->bakeBuf + 3 * capPlane;
     RtBakeArgs A;
@@ -1840,17 +1737,11 @@ int rtHipSceneBakeAmbientOcclusion(rtHipScene *sc, const rtHipBakeParams *p, cl_
 // ---- geometry updates ------------------------------------------------------------------------------------------------------------
 // A scene-owned device buffer of at least `need` bytes: kept when it is large enough, otherwise replaced by one of need + need / 8 bytes
 // (`exact`: of just `need`); contents are not carried over.  The caller has made sure no work reads it.
-static bool geo_fit(rtHipScene *sc, void *bufp, uint64_t *cap, uint64_t need, bool exact, bool *allocated)
+static bool geo_fit(rtHipScene *sc, DevBlock &buf, uint64_t need, bool exact, bool *allocated)
 {
-    void **buf = (void **)bufp;
-    if (*buf && *cap >= need) return true;
-    const uint64_t want = std::max<uint64_t>(exact ? need : need + need / 8, 64);
-    void *q = nullptr;
-    if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (*buf) { (void)hipFree(*buf); sc->bytes -= *cap; }
-    *buf = q; *cap = want;
-    sc->bytes += want;
-    if (allocated) *allocated = true;
+    const void *before = buf.p;
+    if (buf.fit(need, std::max<uint64_t>(exact ? need : need + need / 8, 64), sc->bytes) != hipSuccess) return false;
+    if (allocated && buf.p != before) *allocated = true;
     return true;
 }
 
@@ -1859,13 +1750,11 @@ static bool geo_set_fit(rtHipScene *sc, int i, bool lists, uint64_t listBytes, u
 {
     rtHipScene::GeoMove::Set &L = sc->geo.set[i];
     const uint64_t T = sc->dev.triangleCount;
-    uint64_t cRec = L.triRec ? T * 64 : 0, cShade = L.triShade ? T * 96 : 0, cPlane = L.boxMin ? GEO_PLANE_BYTES : 0, cLut = L.cellLut ? GEO_LUT_BYTES : 0,
-             cStart = L.gridStart ? GEO_START_BYTES : 0, cBits = L.gridBits ? GEO_BITS_BYTES : 0, cSparse = L.sparse ? GEO_SPARSE_BYTES : 0;
-    return geo_fit(sc, &L.triRec, &cRec, T * 64, true, allocated) && geo_fit(sc, &L.triShade, &cShade, T * 96, true, allocated) &&
-           geo_fit(sc, &L.boxMin, &cPlane, GEO_PLANE_BYTES, true, allocated) && geo_fit(sc, &L.cellLut, &cLut, GEO_LUT_BYTES, true, allocated) &&
-           geo_fit(sc, &L.gridStart, &cStart, GEO_START_BYTES, true, allocated) && geo_fit(sc, &L.gridBits, &cBits, GEO_BITS_BYTES, true, allocated) &&
-           geo_fit(sc, &L.sparse, &cSparse, GEO_SPARSE_BYTES, true, allocated) &&
-           (!lists || (geo_fit(sc, &L.gridList, &L.listCap, listBytes, exact, allocated) && geo_fit(sc, &L.pairRec, &L.pairCap, pairBytes, exact, allocated)));
+    return geo_fit(sc, L.triRec, T * 64, true, allocated) && geo_fit(sc, L.triShade, T * 96, true, allocated) &&
+           geo_fit(sc, L.boxMin, GEO_PLANE_BYTES, true, allocated) && geo_fit(sc, L.cellLut, GEO_LUT_BYTES, true, allocated) &&
+           geo_fit(sc, L.gridStart, GEO_START_BYTES, true, allocated) && geo_fit(sc, L.gridBits, GEO_BITS_BYTES, true, allocated) &&
+           geo_fit(sc, L.sparse, GEO_SPARSE_BYTES, true, allocated) &&
+           (!lists || (geo_fit(sc, L.gridList, listBytes, exact, allocated) && geo_fit(sc, L.pairRec, pairBytes, exact, allocated)));
 }
 
 int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
@@ -1891,32 +1780,31 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     GEO_HIP(hipStreamSynchronize(sc->stream));
     hipStream_t st = sc->stream;
     bool allocated = false;
-    const uint64_t camCapBefore[2] = { sc->cam.listCap[0], sc->cam.listCap[1] };
-    const bool camMade = sc->cam.scratch == nullptr;
-    for (hipEvent_t &e : G.ev)
-        if (!e) GEO_HIP(hipEventCreate(&e));
+    const uint64_t camCapBefore[2] = { sc->cam.list[0].size, sc->cam.list[1].size };
+    const bool camMade = !sc->cam.scratch;
+    for (Event &e : G.ev) GEO_HIP(e.make());
     if (!G.space.fillGroups) { G.space.fillGroups = 8; G.space.headroom = 1; }
     const int target = G.live == 0 ? 1 : 0, spareIndex = G.retained == 0 ? 1 : 0;
     rtHipScene::GeoMove::Set &N = G.set[target];
     GEO_MEM(geo_set_fit(sc, target, false, 0, 0, true, &allocated), "the spare set of records and grid arrays");
-    GEO_MEM(geo_fit(sc, &G.material, &G.materialCap, T * 4, true, &allocated), "the build scratch");
-    if (allocated) GEO_HIP(hipMemsetAsync(G.material, 0xff, (size_t)G.materialCap, st)); // every id -1: rtp_validate reads a material per triangle
+    GEO_MEM(geo_fit(sc, G.material, T * 4, true, &allocated), "the build scratch");
+    if (allocated) GEO_HIP(hipMemsetAsync(G.material, 0xff, (size_t)G.material.size, st)); // every id -1: rtp_validate reads a material per triangle
 
     // 1. the caller's arrays on the device
     const void *dVertex = up->vertex, *dIndex = up->triIndex, *dNormal = up->triNormal;
     if (!up->arraysOnDevice) {
-        GEO_MEM(geo_fit(sc, &G.vertexBuf, &G.vertexCap, V * 16, false, &allocated), "the vertices");
+        GEO_MEM(geo_fit(sc, G.vertexBuf, V * 16, false, &allocated), "the vertices");
         GEO_HIP(sc->stager.copy(G.vertexBuf, up->vertex, V * 16));
         dVertex = G.vertexBuf;
         // (the normals' staging is made with the vertices', whether this update brings normals or not: a later one that does allocates nothing)
-        GEO_MEM(geo_fit(sc, &G.normalBuf, &G.normalCap, T * 48, true, &allocated), "the corner normals");
+        GEO_MEM(geo_fit(sc, G.normalBuf, T * 48, true, &allocated), "the corner normals");
         if (up->triNormal) {
             GEO_HIP(sc->stager.copy(G.normalBuf, up->triNormal, T * 48));
             dNormal = G.normalBuf;
         }
     }
     // both index arrays are made by the first update: the retained one and the one a later update is checked in
-    GEO_MEM(geo_fit(sc, &G.index[0], &G.indexCap[0], T * 16, true, &allocated) && geo_fit(sc, &G.index[1], &G.indexCap[1], T * 16, true, &allocated), "the index arrays");
+    GEO_MEM(geo_fit(sc, G.index[0], T * 16, true, &allocated) && geo_fit(sc, G.index[1], T * 16, true, &allocated), "the index arrays");
     if (up->triIndex) { // host or device: the scene keeps a copy of its own
         GEO_HIP(sc->stager.copy(G.index[spareIndex], up->triIndex, T * 16));
         dIndex = G.index[spareIndex];
@@ -1925,7 +1813,7 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     GEO_HIP(hipEventRecord(G.ev[0], st));
 
     // 2. ids are checked before anything gathers through them (the retained array too: V may have shrunk)
-    GEO_HIP(rtp_validate((uint32_t)T, (uint32_t)V, 0x7fffffffu, dIndex, (const int *)G.material, 0, nullptr, nullptr, 0, nullptr, sc->prepErr, st));
+    GEO_HIP(rtp_validate((uint32_t)T, (uint32_t)V, 0x7fffffffu, dIndex, G.material, 0, nullptr, nullptr, 0, nullptr, sc->prepErr, st));
     GEO_HIP(hipStreamSynchronize(st));
     if (sc->check_prep() != 0) return -5;
 
@@ -1946,7 +1834,7 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     if (grc) { fail("%s: the grid build failed on the device", who); return -2; }
     if (pairs >= RT_PAIR_LIMIT) { fail("%s: the grid holds 2^28 pairs or more: pair indices would not fit the trace kernel's records", who); return -3; }
     GEO_MEM(geo_set_fit(sc, target, true, pairs * 4, pairs * 64, false, &allocated), "the grid list and pair records");
-    GEO_MEM(geo_fit(sc, &G.pairOrder, &G.orderCap, pairs * 4, false, &allocated) && geo_fit(sc, &G.pairInfo, &G.infoCap, pairs * 4, false, &allocated), "the pair order");
+    GEO_MEM(geo_fit(sc, G.pairOrder, pairs * 4, false, &allocated) && geo_fit(sc, G.pairInfo, pairs * 4, false, &allocated), "the pair order");
     if (rt_grid_core_lists(&G.space, pairs, N.gridStart, N.gridList, st) != 0) { fail("%s: sorting the grid's pairs failed on the device", who); return -2; }
     float bm[4 * (RT_GRID_DIV + 1)];
     GEO_HIP(hipMemcpyAsync(bm, G.space.bm, sizeof bm, hipMemcpyDeviceToHost, st)); // 4 KB: the planes, for the tables the host derives
@@ -1964,11 +1852,11 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     // 5. the dense view and the pair records
     size_t denseBytes = 0;
     GEO_HIP(rtp_dense_grid(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &denseBytes, st));
-    GEO_MEM(geo_fit(sc, &G.denseTmp, &G.denseCap, denseBytes, true, &allocated), "the dense view's scratch");
-    denseBytes = (size_t)G.denseCap;
+    GEO_MEM(geo_fit(sc, G.denseTmp, denseBytes, true, &allocated), "the dense view's scratch");
+    denseBytes = (size_t)G.denseTmp.size;
     GEO_HIP(hipMemsetAsync(N.sparse, 0, GEO_SPARSE_BYTES, st));
-    GEO_HIP(rtp_dense_grid(N.gridStart, N.gridList, N.gridBits, N.sparse, (uint32_t *)G.pairOrder, (uint32_t *)G.pairInfo, G.denseTmp, &denseBytes, st));
-    GEO_HIP(rtk_launch_gather_pairs((uint32_t)pairs, (const uint32_t *)G.pairOrder, (const uint32_t *)G.pairInfo, N.triRec, N.pairRec, st));
+    GEO_HIP(rtp_dense_grid(N.gridStart, N.gridList, N.gridBits, N.sparse, G.pairOrder, G.pairInfo, G.denseTmp, &denseBytes, st));
+    GEO_HIP(rtk_launch_gather_pairs((uint32_t)pairs, G.pairOrder, G.pairInfo, N.triRec, N.pairRec, st));
     GEO_HIP(hipEventRecord(G.ev[3], st));
 
     // 6. the camera lists of the camera in effect, over the new records
@@ -1999,8 +1887,8 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     sc->release_part(PART_GRID);
     // the other set is made as large as this one now, so that the next update to a shape of no more pairs allocates nothing; if that fails
     // the update has succeeded all the same and the next one tries again
-    (void)geo_set_fit(sc, target ^ 1, true, N.listCap, N.pairCap, true, &allocated);
-    allocated = allocated || camMade || camCapBefore[0] != sc->cam.listCap[0] || camCapBefore[1] != sc->cam.listCap[1];
+    (void)geo_set_fit(sc, target ^ 1, true, N.gridList.size, N.pairRec.size, true, &allocated);
+    allocated = allocated || camMade || camCapBefore[0] != sc->cam.list[0].size || camCapBefore[1] != sc->cam.list[1].size;
     G.log[0] = glog[RT_BUILD_LOG_GRID_THREAD]; G.log[1] = glog[RT_BUILD_LOG_GRID_GROUP]; G.log[2] = glog[RT_BUILD_LOG_ATTEMPTS];
     G.log[3] = pairs; G.log[4] = ctl.total; G.log[5] = allocated ? 1 : 0;
     for (int i = 0; i < 4; ++i) G.ms[i] = ms[i];
@@ -2181,9 +2069,9 @@ struct SceneCache {
     uint64_t hash[5] = { 0 };
     bool valid = false;
     // gather root (device `first`): row-major planes and, for several scenes, the peers' tile buffers
-    uint16_t *planes = nullptr;
-    uint16_t *gather = nullptr;
-    uint32_t *gatherIds = nullptr;
+    Dev<uint16_t> planes, gather;
+    Dev<uint32_t> gatherIds;
+    uint64_t bytes = 0; // (of these three; no scene counts them)
     size_t gatherTiles = 0;
     void clear()
     {
@@ -2191,15 +2079,13 @@ struct SceneCache {
         scenes.clear(); tiles.clear();
         if (valid || planes || gather || gatherIds) {
             if (devices > 0) (void)hipSetDevice(first % devices);
-            if (planes) (void)hipFree(planes);
-            if (gather) (void)hipFree(gather);
-            if (gatherIds) (void)hipFree(gatherIds);
+            planes.drop(bytes); gather.drop(bytes); gatherIds.drop(bytes);
         }
-        planes = nullptr; gather = nullptr; gatherIds = nullptr; gatherTiles = 0;
+        gatherTiles = 0;
         valid = false;
     }
 };
-SceneCache g_cache;
+SceneCache &g_cache = *new SceneCache(); // (never destroyed: nothing is freed on the device during process exit)
 std::mutex g_cacheMutex;
 
 } // namespace
@@ -2525,7 +2411,7 @@ cl_bool RaytraceAll(cl_uint computationType, cl_uint2 cameraImageDimension, cl_f
             for (rtHipScene *s : C.scenes) if (s) { root = s; break; }
             if (!root) return fail("RaytraceAll: nothing to render");
             HIP_OK(hipSetDevice(root->device));
-            if (!C.planes) HIP_OK(hipMalloc((void **)&C.planes, 3 * P * sizeof(uint16_t)));
+            if (!C.planes) HIP_OK(C.planes.make(3 * P * sizeof(uint16_t), C.bytes));
             // (the ABI's planes are zeroed first, raytrace.c:476,481,486, and every pixel belongs to exactly one tile of the deal:
             // the de-tiling launch simply writes them)
             const void *tileBuf = root->dev.tileBuf;
@@ -2536,11 +2422,9 @@ cl_bool RaytraceAll(cl_uint computationType, cl_uint2 cameraImageDimension, cl_f
                 size_t total = 0;
                 for (rtHipScene *s : C.scenes) if (s) total += s->tileIds.size();
                 if (C.gatherTiles != total) {
-                    if (C.gather) HIP_OK(hipFree(C.gather));
-                    if (C.gatherIds) HIP_OK(hipFree(C.gatherIds));
-                    C.gather = nullptr; C.gatherIds = nullptr;
-                    HIP_OK(hipMalloc((void **)&C.gather, total * 3 * RT_TILE_PIXELS * sizeof(uint16_t)));
-                    HIP_OK(hipMalloc((void **)&C.gatherIds, total * sizeof(uint32_t)));
+                    C.gather.drop(C.bytes); C.gatherIds.drop(C.bytes);
+                    HIP_OK(C.gather.make(total * 3 * RT_TILE_PIXELS * sizeof(uint16_t), C.bytes));
+                    HIP_OK(C.gatherIds.make(total * sizeof(uint32_t), C.bytes));
                     std::vector<uint32_t> allIds;
                     for (rtHipScene *s : C.scenes) if (s) allIds.insert(allIds.end(), s->tileIds.begin(), s->tileIds.end());
                     HIP_OK(hipMemcpy(C.gatherIds, allIds.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -2550,7 +2434,7 @@ cl_bool RaytraceAll(cl_uint computationType, cl_uint2 cameraImageDimension, cl_f
                 for (rtHipScene *s : C.scenes) {
                     if (!s) continue;
                     const size_t bytes = s->tileIds.size() * 3 * RT_TILE_PIXELS * sizeof(uint16_t);
-                    HIP_OK(hipMemcpyPeerAsync((char *)C.gather + at, root->device, s->dev.tileBuf, s->device, bytes, root->stream)); // (the scenes were synchronised above)
+                    HIP_OK(hipMemcpyPeerAsync(C.gather.as<char>() + at, root->device, s->dev.tileBuf, s->device, bytes, root->stream)); // (the scenes were synchronised above)
                     at += bytes;
                 }
                 tileBuf = C.gather; ids = C.gatherIds; tiles = total;

@@ -205,13 +205,7 @@ static int denoise_buffer(rtHipScene *sc, DenoiseBuffer &D)
     const uint32_t W = sc->width, H = sc->height;
     const size_t n = (size_t)W * H, img = (n * 12 + 255) & ~(size_t)255, plane = (n * 2 + 255) & ~(size_t)255;
     const uint64_t bytes = 4 * img + 3 * plane + rtHipDenoiseScratchBytes(W, H);
-    if (!sc->denoiseBuf) {
-        void *p = nullptr;
-        HIP_OK(hipMalloc(&p, bytes));
-        sc->denoiseBuf = (char *)p;
-        sc->denoiseBytes = bytes;
-        sc->bytes += bytes;
-    }
+    if (!sc->denoiseBuf) HIP_OK(sc->denoiseBuf.make(bytes, sc->bytes));
     char *b = sc->denoiseBuf;
     D.n = n;
     D.colour = (float *)b; D.normal = (float *)(b + img); D.albedo = (float *)(b + 2 * img); D.out = (float *)(b + 3 * img);
@@ -233,11 +227,10 @@ int rtHipSceneDenoise(rtHipScene *sc, const rtHipDenoiseParams *params, cl_float
     const uint32_t W = sc->width, H = sc->height;
     DenoiseBuffer D;
     if (denoise_buffer(sc, D) != 0) return -1;
-    for (hipEvent_t &e : sc->denoiseEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
+    for (Event &e : sc->denoiseEv) HIP_OK(e.make());
     const bool wantPlanes = outR || outG || outB;
     hipStream_t st = sc->stream;
-    hipEvent_t *ev = sc->denoiseEv;
+    Event *ev = sc->denoiseEv;
     HIP_OK(hipEventRecord(ev[0], st));
     HIP_OK(rtd_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->surfBuf,
                              (float)sc->dev.sampleCount, D.colour, D.normal, D.albedo, st));
@@ -509,23 +502,16 @@ static int scene_temporal(rtHipScene *sc, const rtHipTemporalParams *params, con
     const size_t set = part(n * 12) + 3 * part(n * 4); // a history set: colour | count | t | triangle
     if (!T.buf) {
         const uint64_t bytes = 2 * set + part(n * 8) + part(n * 4) + part(n * 12) + 3 * part(n * 2);
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return fail("temporal: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        T.buf = (char *)p; T.bytes = bytes; T.cur = 0; T.valid = false;
-        sc->bytes += bytes;
+        if (scene_block(sc, T.buf, bytes, "temporal") != 0) return -1;
+        T.cur = 0; T.valid = false;
     }
     if (withMoments && !T.momentsBuf) { // two sets of moments | the variance | the filter's il
         const uint64_t bytes = 2 * part(n * 8) + 2 * part(n * 4);
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return fail("temporal: hipMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        T.momentsBuf = (char *)p; T.momentsBytes = bytes; T.momentsValid = false;
-        sc->bytes += bytes;
+        if (scene_block(sc, T.momentsBuf, bytes, "temporal") != 0) return -1;
+        T.momentsValid = false;
     }
     if (withMoments && !T.momentsValid) T.valid = false; // a live history whose moments are stale starts again, as after a reset
-    for (hipEvent_t &e : T.ev)
-        if (!e) HIP_OK(hipEventCreate(&e));
+    for (Event &e : T.ev) HIP_OK(e.make());
     struct Set { float *colour, *count, *t; uint32_t *triangle; } hs[2];
     for (int i = 0; i < 2; ++i) {
         char *b = T.buf + i * set;
@@ -540,7 +526,7 @@ static int scene_temporal(rtHipScene *sc, const rtHipTemporalParams *params, con
     float *moments[2] = {}, *varianceOut = nullptr;
     char *il = nullptr;
     if (withMoments) {
-        moments[0] = (float *)T.momentsBuf; moments[1] = (float *)(T.momentsBuf + part(n * 8));
+        moments[0] = T.momentsBuf.as<float>(); moments[1] = (float *)(T.momentsBuf + part(n * 8));
         varianceOut = (float *)(T.momentsBuf + 2 * part(n * 8));
         il = T.momentsBuf + 2 * part(n * 8) + part(n * 4);
     }

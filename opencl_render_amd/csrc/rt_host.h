@@ -6,6 +6,7 @@
 #include "rt_device.h"
 #include "rt_camera_move.h"
 #include "rt_geometry_move.h"
+#include "rt_owned.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -185,7 +186,7 @@ enum { PART_FIXED = 0, PART_CAMERA, PART_GEOMETRY, PART_GRID, PART_MATERIALS, PA
 
 struct rtHipScene {
     int device = -1;
-    hipStream_t stream = nullptr;
+    rthost::Stream stream; // (declared before everything issued on it: destroyed last)
     RtDevScene dev{};
     // Device allocations by PART (tiles + outputs | camera lists | geometry | grid | materials | lights | path state): the drop-in
     // layer's cache replaces the parts whose inputs changed between two RaytraceAll calls and keeps the others in HBM.
@@ -205,7 +206,7 @@ struct rtHipScene {
     std::vector<cl_uint> tileIds;
     uint32_t width = 0, height = 0, tilesX = 0;
     // kernel timing: one event pair per launch since the last rtHipKernelTime
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    std::vector<std::pair<rthost::Event, rthost::Event>> events;
     size_t eventsUsed = 0;
     // wavefront pipeline (rt_wavefront.hip)
     int pipeline = RT_HIP_PIPELINE_WAVEFRONT;
@@ -215,11 +216,11 @@ struct rtHipScene {
     struct Group {
         RtDevScene dev{};
         RtWavefront wf{};
-        hipStream_t stream = nullptr;   // groups 1.. ; group 0 runs on the caller's stream
-        hipEvent_t done = nullptr;
+        rthost::Stream stream;          // groups 1.. ; group 0 runs on the caller's stream
+        rthost::Event done;
         uint32_t logicBlocks = 1, traceBlocks = 1, queueBlocks = 1;
-        uint32_t *hostCount = nullptr;  // pinned: queue length read back between round chunks
-        uint32_t *hostStatus = nullptr; // pinned + mapped: RT_WF_STATUS_* words the kernels write (rt_device.h)
+        rthost::Pinned<uint32_t> hostCount;  // pinned: queue length read back between round chunks
+        rthost::Pinned<uint32_t> hostStatus; // pinned + mapped: RT_WF_STATUS_* words the kernels write (rt_device.h)
         bool ctlClean = false;          // the batch before was a planned one: wf_status_kernel left the control words zeroed
         uint32_t rounds = 0;
         uint32_t slot0 = 0, slot1 = 0;  // this group's range of the instance's tile slots
@@ -228,13 +229,13 @@ struct rtHipScene {
         // per round: rays (entries in region A), the longest queue slice, entries in region B -- the maximum over the watched batches
         // rays of the round, and -- an ordered round -- the further segments of its cut rays under the cut it was logged with
         struct RoundPlan { uint32_t rays = 0, extra = 0, extraSegLen = 0; };
-        uint4 *hostLog = nullptr;       // pinned + mapped: RtWavefront::roundLog, written by the kernels, read by the host after a sync
+        rthost::Pinned<uint4> hostLog;  // pinned + mapped: RtWavefront::roundLog, written by the kernels, read by the host after a sync
         RoundPlan plan[RT_WF_ROUND_LOG], planNext[RT_WF_ROUND_LOG];
         std::vector<RtRoundMode> modes; // how the rounds of the batch being issued are laid out (modes[r] is decided when logic(r-1) is launched)
         uint64_t guessRays = 0;         // watched batches: what the next round is assumed to hold
     };
     std::vector<Group> groups;
-    hipEvent_t forkEvent = nullptr;
+    rthost::Event forkEvent;
     uint32_t samplesPerBatch = 1;
     uint32_t planRounds = 0;   // rounds a planned frame issues per batch; 0 = no plan yet (the next frame is a discovery frame)
     bool blocking = false;     // every frame watches the queue (no plan)
@@ -244,7 +245,7 @@ struct rtHipScene {
     std::atomic<float> *progress = nullptr; // drop-in layer: where finished sample batches are reported (GetProgress, raytrace.c:566-587)
     float progressBase = 0.f, progressSpan = 0.f;
     // per-stage device time of the frames since the last query: [primary, logic, trace, accum, sort]
-    struct StageEvent { int stage; hipEvent_t a, b; };
+    struct StageEvent { int stage; rthost::Event a, b; };
     std::vector<StageEvent> stageEvents;
     size_t stageEventsUsed = 0;
     bool stageTiming = false;
@@ -252,33 +253,29 @@ struct rtHipScene {
     // render passes (rtHipScenePasses): RT_HIP_PASS_* bits, the pass buffer [slot][RT_PASS_WORDS][128*128] (rt_device.h) while ALPHA,
     // DEPTH or TRIANGLE is on, and the surface buffer [slot][RT_SURF_WORDS][128*128] while NORMAL or ALBEDO is on
     uint32_t passMask = 0;
-    uint32_t *passBuf = nullptr;
-    uint64_t passBytes = 0;
-    float *surfBuf = nullptr;
-    uint64_t surfBytes = 0;
+    rthost::Dev<uint32_t> passBuf;
+    rthost::Dev<float> surfBuf;
     // ray queries through host arrays (rtHipSceneIntersect): one chunk of hits | rays | excluded ids on the device and a pinned host buffer
     // of the same layout from the staging pool, both made on first use
     uint32_t queryRays = 0;
-    char *queryDev = nullptr, *queryHost = nullptr;
-    uint64_t queryBytes = 0;
+    rthost::Dev<> queryDev;
+    char *queryHost = nullptr; // (queryDev.size bytes; goes back to the pool)
     // denoiser scratch of rtHipSceneDenoise (gathered inputs, filter scratch, outputs), made on first use while NORMAL and ALBEDO are on
-    char *denoiseBuf = nullptr;
-    uint64_t denoiseBytes = 0;
+    rthost::Dev<> denoiseBuf;
     // device time of the last rtHipSceneDenoise: events before the gather, after it, after the guides and after the output
-    hipEvent_t denoiseEv[4] = {};
+    rthost::Event denoiseEv[4];
     float denoiseMs[3] = {};
     // ambient occlusion scratch (rtHipSceneAmbientOcclusion*), made on first use: the pixel counters, then one chunk of primary hits; the
     // event marks the end of the last call that used it, so that a call on another stream waits for it on the device
-    char *aoBuf = nullptr;
-    uint64_t aoBytes = 0;
+    rthost::Dev<> aoBuf;
     uint32_t aoChunk = 0;
-    hipEvent_t aoDone = nullptr;
+    rthost::Event aoDone;
     // ambient occlusion bake scratch (rtHipSceneBakeAmbientOcclusion*), made on first use and grown for a larger map: winners, counters
     // and a second value plane for W*H texels, the big list, one chunk of texels; the event as above
-    char *bakeBuf = nullptr;
-    uint64_t bakeBytes = 0, bakeTexels = 0;
+    rthost::Dev<> bakeBuf;
+    uint64_t bakeTexels = 0;
     uint32_t bakeChunk = 0;
-    hipEvent_t bakeDone = nullptr;
+    rthost::Event bakeDone;
     // motion vectors (rtHipSceneMotion*): the reference of the last rtHipSceneMotionMark -- its camera, and a, ab, ac of every triangle in
     // storage of its own (RT_MOTION_REF_ROWS float4 per triangle), made by the first mark -- and the host entry point's staging (tile-major
     // motion | t | prevT | triangle, 20 bytes per tile pixel), made on its first use.  marked: the end of the last mark on the scene's
@@ -287,11 +284,9 @@ struct rtHipScene {
         bool have = false;
         rtHipCamera cam{};
         uint32_t triangles = 0;
-        char *ref = nullptr;
-        uint64_t refBytes = 0;
-        char *stage = nullptr;
-        uint64_t stageBytes = 0;
-        hipEvent_t marked = nullptr, done = nullptr;
+        rthost::Dev<float4> ref;
+        rthost::Dev<> stage;
+        rthost::Event marked, done;
     } motion;
     // temporal accumulation (rtHipSceneTemporal), made on its first call in one block: two history sets (colour | count | t | triangle;
     // `cur` is the one the next call reads), this frame's motion and prevT, the gathered colour and the u16 output planes.  valid: the
@@ -300,53 +295,61 @@ struct rtHipScene {
     // sets), the variance plane and the filter's il plane.  momentsValid: the moments set `cur` belongs to the history set `cur` (false
     // after an rtHipSceneTemporal, which does not write them).
     struct Temporal {
-        char *buf = nullptr;
-        uint64_t bytes = 0;
+        rthost::Dev<> buf, momentsBuf;
         int cur = 0;
-        bool valid = false;
-        char *momentsBuf = nullptr;
-        uint64_t momentsBytes = 0;
-        bool momentsValid = false;
-        hipEvent_t ev[5] = {};
+        bool valid = false, momentsValid = false;
+        rthost::Event ev[5];
         float ms[4] = {};
     } temporal;
     // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
     // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
-    // and the sets change places at its end.  listCap: entries each list holds.  log: triangles per thread, per workgroup, entries of the
-    // last move; ms: device time of its count stage and of its fill stage.
+    // and the sets change places at its end.  log: triangles per thread, per workgroup, entries of the last move; ms: device time of its
+    // count stage and of its fill stage.
     struct CamMove {
-        char *scratch = nullptr;
-        uint64_t scratchBytes = 0;
-        uint32_t *start[2] = {}, *end[2] = {}, *list[2] = {};
-        uint64_t listCap[2] = {};
+        rthost::Dev<> scratch;
+        rthost::Dev<uint32_t> start[2], end[2], list[2];
         int live = -1; // the set in use; -1 while the scene still renders from the lists it was created with
         RtCamMoveArgs args{};
-        hipEvent_t ev[4] = {};
+        rthost::Event ev[4];
         uint64_t log[3] = {};
         double ms[2] = {};
     } cam;
     // geometry updates (rtHipSceneSetGeometry), made by the first update: TWO sets of everything the kernels read of the shape (triangle
     // records, shading rows, planes, cell table, grid starts and list, occupancy words, block table, pair records) -- an update builds into
     // the set the frames do not read and the sets change places at its end; the parts the scene was created with are freed after the
-    // first update.  pairCap: entries the set's list and pair records hold.  The rest is build scratch that stays: the grid build's space,
-    // staging for host arrays, two index arrays (the retained one and the one being checked), the pair order.
+    // first update.  The rest is build scratch that stays: the grid build's space, staging for host arrays, two index arrays (the retained
+    // one and the one being checked), the pair order.
     struct GeoMove {
         struct Set {
-            float *triRec = nullptr, *triShade = nullptr, *boxMin = nullptr, *pairRec = nullptr;
-            uint8_t *cellLut = nullptr;
-            uint32_t *gridStart = nullptr, *gridList = nullptr, *sparse = nullptr;
-            unsigned long long *gridBits = nullptr;
-            uint64_t listCap = 0, pairCap = 0; // in bytes
+            rthost::Dev<float> triRec, triShade, boxMin, pairRec;
+            rthost::Dev<uint8_t> cellLut;
+            rthost::Dev<uint32_t> gridStart, gridList, sparse;
+            rthost::Dev<unsigned long long> gridBits;
         } set[2];
         int live = -1;      // the set in use; -1 while the scene still renders from the parts it was created with
         RtGridSpace space{};
-        char *vertexBuf = nullptr, *normalBuf = nullptr, *index[2] = {}, *material = nullptr, *pairOrder = nullptr, *pairInfo = nullptr, *denseTmp = nullptr;
-        uint64_t vertexCap = 0, normalCap = 0, indexCap[2] = {}, materialCap = 0, orderCap = 0, infoCap = 0, denseCap = 0; // in bytes
+        rthost::Dev<> vertexBuf, normalBuf, index[2], denseTmp;
+        rthost::Dev<int> material;
+        rthost::Dev<uint32_t> pairOrder, pairInfo;
         int retained = -1;  // which index array the last successful update left; -1: none (creation drops the index array)
-        hipEvent_t ev[5] = {};
+        rthost::Event ev[5];
         uint64_t log[6] = {}; // per thread, per workgroup, attempts, pairs, camera entries, allocated
         double ms[4] = {};
     } geo;
+
+    // Only what ordering requires: the device is selected, work on the streams ends, then the parts, the grid build's space, the upload
+    // staging and the pooled query staging go; every member above frees itself afterwards.
+    ~rtHipScene()
+    {
+        if (device >= 0) (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (Group &G : groups)
+            if (G.stream) (void)hipStreamSynchronize(G.stream);
+        for (int part = 0; part < PART_COUNT; ++part) release_part(part);
+        rt_grid_space_free(&geo.space);
+        stager.destroy();
+        if (queryHost) rthost::Stager::pool().give(queryHost, queryDev.size);
+    }
 
     template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
     {
@@ -404,6 +407,18 @@ struct rtHipScene {
 };
 
 namespace rthost {
+
+// Scene scratch of `bytes` bytes, counted in rtHipSceneBytes, and an event: made, or fail() in the name of `who`.
+inline int scene_block(rtHipScene *sc, DevBlock &b, uint64_t bytes, const char *who)
+{
+    const hipError_t e = b.make(bytes, sc->bytes);
+    return e == hipSuccess ? 0 : fail("%s: hipMalloc(%llu) failed: %s", who, (unsigned long long)bytes, hipGetErrorString(e));
+}
+inline int scene_event(Event &ev, unsigned flags, const char *who)
+{
+    const hipError_t e = ev.make(flags);
+    return e == hipSuccess ? 0 : fail("%s: hipEventCreate failed: %s", who, hipGetErrorString(e));
+}
 
 // rt_api.cpp
 RT_INTERNAL int frame_finish(rtHipScene *sc, hipStream_t st, int *redone);
