@@ -318,6 +318,52 @@ int rtHipRenderTiles(rtHipScene *scene, void *stream);
  * the incomplete frame has to be repeated.  RT_WF_BLOCKING=1 makes every frame a watched one.  Returns 0 on success. */
 int rtHipFrameFinish(rtHipScene *scene, int *redone);
 
+/* SAMPLE WINDOWS: successive frames of a resident scene draw different samples.  By default every frame renders samples 1..S of a
+ * sequence of S (S = the sampleCount the scene was created with): sample s of pixel p is seeded p*S + s (raytrace_opencl.c:481), its
+ * addend is trunc(out * (65535.0f / (float)S)), added with saturation in sample order (:726-741) -- so every frame of a still scene is
+ * the same frame.  A window makes the frame a slice of a longer sequence instead:
+ *   total      N: samples per pixel of the whole sequence = the seed stride; sample id i of pixel p is seeded (uint64)p*N + i
+ *   first      f: the frame renders sample ids f+1 .. f+S, in that order (S is unchanged: it is what the path-state buffers are sized for)
+ *   divisor    D: a sample's addend is trunc(out * (65535.0f / (float)D)), saturating, in sample order
+ *   accumulate 1: the frame's first addend follows on what the tile buffer holds, unless f == 0 (the start of a sequence starts from
+ *              zero); 0: every frame starts from zero
+ *   advance    1: every frame issued moves f to (f + S) % N for the next one
+ * The default window is {S, 0, S, 0, 0}; under it every kernel computes exactly what it computed before windows existed.
+ * An N-sample frame of the reference is the ordered saturating sum of its samples' addends, which gives the two uses:
+ *   PROGRESSIVE {N, 0, N, 1, 1}: after N / S frames the tile buffer is bit for bit the N-sample frame, saturation included.  The tile
+ *              buffer may be read after any frame; the caller scales what it reads by N / done for a preview (no device-side preview).
+ *   SEQUENCE   {N, 0, S, 0, 1}: each frame is a full-brightness image of S fresh samples per pixel; the frames repeat after N / S.  This
+ *              is the input the temporal accumulation and the variance-guided filter (their blocks below) need under a still or
+ *              slowly moving camera.
+ * rtHipSampleWindowCheck (host only, no device) and rtHipSceneSetSampleWindow return -1 with the last-error text set for N == 0, D == 0,
+ * f + S > N (compared in 64 bits), accumulate or advance other than 0 or 1, and advance with N % S != 0 or f % S != 0; a refused set
+ * leaves the scene's window and its next frame unchanged.  A set is host-side state the next frame issued picks up: it synchronises
+ * nothing, allocates nothing and keeps the launch plan (other sample ids of the same pixels need statistically the same rounds; a plan
+ * that is too short is caught by rtHipFrameFinish as ever).  NULL sets the default window.
+ * rtHipSceneGetSampleWindow: *next = the window the next frame will use, *last = the one the last issued frame used (all zero before
+ * the first frame); either may be NULL.
+ * Frames and their verification.  `advance` is applied when a frame is issued; an rtHipRenderTiles that returns -1 moves nothing
+ * and leaves *last alone.  A frame rendered again by rtHipFrameFinish, rtHipSync or
+ * rtHipReadback renders the window that frame had (*last) and does not advance again.  A frame that continues from the tile buffer
+ * (accumulate == 1, f > 0) has already added into the planes when it is found incomplete and could not be redone: such frames are issued
+ * with every batch watched, as under RT_WF_BLOCKING=1, after the frames before them are verified.
+ * Both pipelines honour the window and keep producing identical planes.  Render passes (ALPHA, DEPTH, TRIANGLE, NORMAL, ALBEDO)
+ * describe the window's own S samples: "sample 1" is sample id f + 1, means and alpha divide by S; passes never accumulate across
+ * windows.  rtHipSceneDenoise, rtHipSceneTemporal and rtHipSceneTemporalVariance read the tile buffer, whatever window filled it.
+ * rtHipRenderTilesCounted returns -1 while a window other than the default is in effect.  A scene made by RaytraceAll's cache or by
+ * rtHipSceneCreateLike starts with the default window: instances (peers, tile subsets) are set one by one, and disjoint tile deals
+ * under the same window still compose one image. */
+typedef struct rtHipSampleWindow {
+    cl_uint total;      /* N */
+    cl_uint first;      /* f */
+    cl_uint divisor;    /* D */
+    cl_uint accumulate; /* 0 or 1 */
+    cl_uint advance;    /* 0 or 1 */
+} rtHipSampleWindow;
+int rtHipSampleWindowCheck(cl_uint sampleCount, const rtHipSampleWindow *window);
+int rtHipSceneSetSampleWindow(rtHipScene *scene, const rtHipSampleWindow *window);
+int rtHipSceneGetSampleWindow(const rtHipScene *scene, rtHipSampleWindow *next, rtHipSampleWindow *last);
+
 /* Two implementations of the same frame (identical planes):
  *   WAVEFRONT (default) staged pipeline: primary -> rounds of (per-path logic, length sort of the new ray requests, grid
  *                       trace) -> ordered accumulate.  The first frame of a scene watches its ray queue from the host; later frames
@@ -702,9 +748,8 @@ int  rtHipSceneTemporalTimes(const rtHipScene *scene, cl_float ms[4]);
  * launched.  Every bit pattern of the inputs has a defined answer up to the payload of a NaN (an infinite variance next to a zero weight
  * is a NaN by 0 * inf, and spreads), and nothing indexes out of range.
  *
- * One limit: the renderer seeds every frame alike (the reference's seeding), so under a still camera and still geometry successive
- * frames are identical and the temporal variance is 0: the filter then does not smooth at all beyond what the floor allows.  For such
- * sequences set spatialBelow above maxHistory, which forces the spatial estimate in every pixel. */
+ * Fresh samples per frame: under the default sample window every frame of a still scene is the same frame and the temporal variance is
+ * 0.  Give the scene a sequence window (SAMPLE WINDOWS above: {N, 0, S, 0, 1}) and successive frames draw different samples. */
 typedef struct rtHipVarianceParams {
     cl_uint  iterations;      /* K */
     cl_float luminanceSigma2; /* ls: the luminance edge-stop is (dl*dl) / (ls * variance + floor) */

@@ -34,6 +34,12 @@ BAKE") and writes it to PATH like ``--ao``: .pfm (f32) or .pgm (8 bits).  ``--ba
 ``--bake-radius``, ``--bake-seed`` and ``--bake-dilate`` set its parameters; ``--bake-material M`` or ``--bake-triangles FIRST COUNT``
 selects what is baked; ``--bake-atlas`` bakes over a grid atlas (scene.grid_atlas_uv) instead of the scene's own UVs.  For the
 all-GPUs device it runs on device 0.
+
+``--progressive N`` renders N samples per pixel in N / S frames of S (S = ``--samples``) on the one resident scene (include/raytrace_hip.h,
+"SAMPLE WINDOWS"; ResidentScene.progressive): ``--out img.bmp`` is the finished image, equal to the ``--samples N`` image, and after each
+frame but the last a preview img_000.bmp, img_001.bmp .. is written, the tile buffer scaled by N / done on the host.  ``--sequence N``
+(with ``--orbit N``, ``--spin N`` or ``--temporal PATH``) gives the frames the sequence window: frame i draws S fresh samples per pixel of
+a sequence of N, so that the temporal chain has something to average under a still or slowly moving camera.
 """
 import argparse
 import sys
@@ -89,6 +95,13 @@ def parser():
     ap.add_argument("--variance", metavar="PATH",
                     help="with --temporal PATH: also write every frame's variance as .pfm, numbered like --out: V^K of the variance-guided "
                          "filter with --variance-guided, the temporal variance of the luminance without")
+    ap.add_argument("--progressive", type=int, default=0, metavar="N",
+                    help="render N samples per pixel in N / --samples frames of the one resident scene (sample windows): --out is the finished "
+                         "image, the --samples N image bit for bit; the previews after the earlier frames are numbered like --orbit's outputs "
+                         "and scaled by N / done on the host.  One GPU only; not together with --orbit, --spin or the other outputs")
+    ap.add_argument("--sequence", type=int, default=0, metavar="N",
+                    help="with --orbit, --spin or --temporal: frame i renders samples i * S + 1 .. (i + 1) * S (mod N) of a sequence of N per "
+                         "pixel (S = --samples; N a multiple of S) instead of the same S samples every frame")
     ap.add_argument("--orbit", type=int, default=1, metavar="N",
                     help="N views of the one resident scene on a circle about the vertical axis through the look-at point, same height and "
                          "distance, each after the first through ResidentScene.look_at (the camera lists are rebuilt on the device, nothing is "
@@ -129,6 +142,16 @@ def parse_args(argv=None):
         ap.error("--variance-guided does not go with --denoise (one filter runs on the accumulation)")
     if args.variance and not args.variance.lower().endswith(".pfm"):
         ap.error("--variance PATH must end in .pfm")
+    if args.progressive:
+        if args.progressive < args.samples or args.progressive % args.samples:
+            ap.error("--progressive N needs N to be a multiple of --samples (the samples of one frame)")
+        if args.orbit > 1 or args.spin > 1 or args.passes or args.denoise or args.ao or args.bake_ao or args.sequence:
+            ap.error("--progressive does not go with --orbit, --spin, --sequence, --passes, --denoise, --ao or --bake-ao")
+    if args.sequence:
+        if args.orbit < 2 and args.spin < 2:
+            ap.error("--sequence N needs --orbit N or --spin N with N >= 2 (the frames of the sequence)")
+        if args.sequence < args.samples or args.sequence % args.samples:
+            ap.error("--sequence N needs N to be a multiple of --samples (the samples of one frame)")
     if args.surface_passes and not args.passes:
         ap.error("--surface-passes needs --passes PREFIX")
     if args.denoise and not args.denoise.lower().endswith((".bmp", ".ppm", ".pfm")):
@@ -283,6 +306,27 @@ def write_temporal(rs, args, index: int) -> None:
         frontend.write_bmp(path, *res["planes"], low_byte_compat=args.low_byte_compat)
 
 
+def render_progressive(sc, args, device: int):
+    """--progressive: args.progressive samples per pixel in frames of sc.sample_count on one ResidentScene of HIP device `device`.  Writes
+    a preview after every frame but the last (the planes scaled by N / done, saturating) and returns the finished R, G, B planes."""
+    from . import frontend, raytrace
+    rs = raytrace.ResidentScene(sc, device)
+    try:
+        total = args.progressive
+        for done, planes in rs.progressive(total):
+            planes = [p.reshape(sc.height, sc.width) for p in planes]
+            if done < total:
+                preview = [np.minimum(p.astype(np.uint64) * total // done, 65535).astype(np.uint16) for p in planes]
+                path = raytrace.orbit_path(args.out, done // sc.sample_count - 1)
+                if path.lower().endswith(".ppm"):
+                    frontend.write_ppm(path, *preview)
+                else:
+                    frontend.write_bmp(path, *preview, low_byte_compat=args.low_byte_compat)
+        return planes
+    finally:
+        rs.close()
+
+
 def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
     """--orbit: args.orbit views of one ResidentScene on HIP device `device`, the camera moved on the device between them.  Returns
     the seconds the moves, frames and read-backs took."""
@@ -292,6 +336,8 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
         basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
         if basic or surface:
             rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        if args.sequence:
+            rs.set_sample_window(args.sequence, 0, sc.sample_count, advance=True)
         spent = 0.0
         for i, position in enumerate(raytrace.orbit_positions(eye, centre, args.orbit)):
             t = time.perf_counter()
@@ -325,6 +371,8 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
         basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
         if basic or surface:
             rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        if args.sequence:
+            rs.set_sample_window(args.sequence, 0, sc.sample_count, advance=True)
         vertex, index, normal = sc.vertex, sc.tri_index, sc.tri_normal
         spent = 0.0
         for i in range(args.spin):
@@ -393,7 +441,12 @@ def main(argv=None):
         print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel, "
               f"{args.orbit} views -> {raytrace.orbit_path(args.out, 0)} ..\n  moves + frames + read-backs {1e3 * spent:.0f} ms = {args.orbit / spent:.1f} views/s")
         return 0
-    if args.passes or args.denoise:
+    if args.progressive:
+        if args.device == raytrace.lib().rtHipDeviceCount() + 1:
+            sys.exit("--progressive renders on one GPU: choose --device 1..%d" % raytrace.lib().rtHipDeviceCount())
+        r, g, b = render_progressive(sc, args, args.device - 1)
+        ok = True
+    elif args.passes or args.denoise:
         (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount(), surface=args.surface_passes,
                                           basic=bool(args.passes), denoise=bool(args.denoise))
         ok = True
@@ -428,10 +481,10 @@ def main(argv=None):
         frontend.write_ppm(args.out, r, g, b)
     else:
         frontend.write_bmp(args.out, r, g, b, low_byte_compat=args.low_byte_compat)
-    rays = args.width * args.height * args.samples
+    rays = args.width * args.height * (args.progressive or args.samples)
     print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel -> {args.out}\n"
           f"  scene {1e3 * (t1 - t0):.0f} ms, lists on the device {1e3 * (t2 - t1):.0f} ms (kernels {cam_ms:.1f} + {grid_ms:.1f} ms), "
-          f"{'resident render + passes' if args.passes or args.denoise else 'RaytraceAll'} {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
+          f"{'progressive frames + previews' if args.progressive else 'resident render + passes' if args.passes or args.denoise else 'RaytraceAll'} {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
     return 0
 
 

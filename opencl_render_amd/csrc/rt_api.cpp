@@ -352,6 +352,27 @@ int build_lights(rtHipScene *sc, const rtHipSceneDesc *d)
     return 0;
 }
 
+// Sample windows (include/raytrace_hip.h, "SAMPLE WINDOWS").  The default window of a scene of S samples:
+rtHipSampleWindow default_window(uint32_t S) { return rtHipSampleWindow{ S, 0u, S, 0u, 0u }; }
+bool same_window(const rtHipSampleWindow &a, const rtHipSampleWindow &b)
+{
+    return a.total == b.total && a.first == b.first && a.divisor == b.divisor && a.accumulate == b.accumulate && a.advance == b.advance;
+}
+// Does a frame under `w` follow on what the tile buffer holds?  (Such a frame cannot be rendered again: it is issued watched.)
+bool window_continues(const rtHipSampleWindow &w) { return w.accumulate == 1u && w.first > 0u; }
+// `w` becomes the window of the scene's device description and of every tile group's copy of it (RtDevScene travels by value): host
+// words only, picked up by the next launch.
+void apply_window(rtHipScene *sc, const rtHipSampleWindow &w)
+{
+    auto put = [&](RtDevScene &D) {
+        D.seedStride = w.total; D.sampleFirst = w.first; D.sampleDivisor = w.divisor;
+        D.continuesFrame = window_continues(w) ? 1u : 0u;
+        D.directStore = (D.sampleCount == 1u && !D.continuesFrame) ? 1u : 0u;
+    };
+    put(sc->dev);
+    for (auto &G : sc->groups) put(G.dev);
+}
+
 // wavefront pipeline buffers: worst case every pixel of every sample in a batch becomes a path
 int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
 {
@@ -362,6 +383,9 @@ int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
     sc->curPart = PART_WAVEFRONT;
     RtDevScene &D = sc->dev;
     D.sampleCount = sampleCount;
+    sc->window = default_window(sampleCount); // (a scene starts, and a cached scene whose S changed starts again, with the default window)
+    sc->lastWindow = rtHipSampleWindow{};
+    apply_window(sc, sc->window);             // (the groups' views follow in refresh_views)
     sc->planRounds = 0; // the next frame watches its queue again
     sc->unverified = false;
     const Tuning &T = sc->tune;
@@ -800,8 +824,8 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
                 }
             } else anyPlannedBatch = true;
             rounds = std::max<uint64_t>(rounds, G.rounds);
-            if (sampleCount > 1) // a one-sample frame's pixels were written by the kernels that finished them
-                HIP_OK(stage(3, on, [&] { return rtw_launch_accum(&G.dev, &G.wf, base == 0 ? 1 : 0, on); }));
+            if (!G.dev.directStore) // a one-sample frame that starts from zero: its pixels were written by the kernels that finished them
+                HIP_OK(stage(3, on, [&] { return rtw_launch_accum(&G.dev, &G.wf, (base == 0 && !G.dev.continuesFrame) ? 1 : 0, on); }));
         }
         // a watched batch knows here that its rounds are over: tell whoever polls GetProgress (raytrace.c:566-587)
         if (!planned && sc->progress)
@@ -872,6 +896,7 @@ int rthost::frame_finish(rtHipScene *sc, hipStream_t st, int *redone)
         return 0;
     }
     if (redone) *redone = 1;
+    apply_window(sc, sc->lastWindow); // the window that frame had; the scene's next window has moved on already and stays where it is
     if (render_wavefront(sc, st, true) != 0) return -1;
     HIP_OK(hipStreamSynchronize(st));
     return 0;
@@ -1153,20 +1178,68 @@ int rtHipRenderTiles(rtHipScene *sc, void *stream)
     if (!sc) return fail("null scene");
     HIP_OK(hipSetDevice(sc->device));
     hipStream_t st = stream ? (hipStream_t)stream : sc->stream;
+    // The frame's sample window.  A frame that continues from the tile buffer adds into the planes and cannot be rendered again: the
+    // frames before it are verified first (and redone while their own window is still the last one), and it is issued watched.
+    const rtHipSampleWindow w = sc->window;
+    const bool continues = window_continues(w);
+    if (continues && sc->unverified && frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    apply_window(sc, w);
     sc->lastStream = st;
-    if (sc->eventsUsed == sc->events.size()) {
-        Event a, b;
-        HIP_OK(a.make()); HIP_OK(b.make());
-        sc->events.emplace_back(std::move(a), std::move(b));
-    }
-    auto &ev = sc->events[sc->eventsUsed++];
-    HIP_OK(hipEventRecord(ev.first, st));
-    if (sc->pipeline == RT_HIP_PIPELINE_WAVEFRONT) {
-        if (render_wavefront(sc, st, false) != 0) return -1;
-    } else {
-        HIP_OK(rtk_launch_trace(&sc->dev, 0, st));
-    }
-    HIP_OK(hipEventRecord(ev.second, st));
+    auto issue = [&]() -> int {
+        if (sc->eventsUsed == sc->events.size()) {
+            Event a, b;
+            HIP_OK(a.make()); HIP_OK(b.make());
+            sc->events.emplace_back(std::move(a), std::move(b));
+        }
+        auto &ev = sc->events[sc->eventsUsed++];
+        HIP_OK(hipEventRecord(ev.first, st));
+        if (sc->pipeline == RT_HIP_PIPELINE_WAVEFRONT) {
+            if (render_wavefront(sc, st, continues) != 0) return -1;
+        } else {
+            HIP_OK(rtk_launch_trace(&sc->dev, 0, st));
+        }
+        HIP_OK(hipEventRecord(ev.second, st));
+        return 0;
+    };
+    // a frame that could not be issued leaves the windows alone: `last` keeps naming the last frame that was issued, `next` has not moved
+    if (issue() != 0) return -1;
+    sc->lastWindow = w;
+    if (w.advance) sc->window.first = (uint32_t)(((uint64_t)w.first + sc->dev.sampleCount) % w.total);
+    return 0;
+}
+
+int rtHipSampleWindowCheck(cl_uint sampleCount, const rtHipSampleWindow *w)
+{
+    if (!w) return fail("sample window: null argument");
+    const uint64_t S = sampleCount, N = w->total, f = w->first;
+    if (S == 0) return fail("sample window: sampleCount must be >= 1");
+    if (N == 0) return fail("sample window: total must be >= 1");
+    if (w->divisor == 0) return fail("sample window: divisor must be >= 1");
+    if (f + S > N) return fail("sample window: first + sampleCount = %llu + %llu reaches past total = %llu", (unsigned long long)f, (unsigned long long)S, (unsigned long long)N);
+    if (w->accumulate > 1u) return fail("sample window: accumulate must be 0 or 1, not %u", w->accumulate);
+    if (w->advance > 1u) return fail("sample window: advance must be 0 or 1, not %u", w->advance);
+    if (w->advance && N % S != 0) return fail("sample window: advance needs total = %llu to be a multiple of sampleCount = %llu", (unsigned long long)N, (unsigned long long)S);
+    if (w->advance && f % S != 0) return fail("sample window: advance needs first = %llu to be a multiple of sampleCount = %llu", (unsigned long long)f, (unsigned long long)S);
+    return 0;
+}
+
+int rtHipSceneSetSampleWindow(rtHipScene *sc, const rtHipSampleWindow *w)
+{
+    if (!sc) return fail("rtHipSceneSetSampleWindow: null scene");
+    const rtHipSampleWindow def = default_window(sc->dev.sampleCount);
+    if (!w) w = &def;
+    if (rtHipSampleWindowCheck(sc->dev.sampleCount, w) != 0) return -1;
+    // (the launch plan stays: other sample ids of the same pixels need statistically the same rounds, see render_wavefront's batches)
+    sc->window = *w;
+    apply_window(sc, sc->window);
+    return 0;
+}
+
+int rtHipSceneGetSampleWindow(const rtHipScene *sc, rtHipSampleWindow *next, rtHipSampleWindow *last)
+{
+    if (!sc) return fail("rtHipSceneGetSampleWindow: null scene");
+    if (next) *next = sc->window;
+    if (last) *last = sc->lastWindow;
     return 0;
 }
 
@@ -1258,7 +1331,10 @@ int rtHipStageTimes(rtHipScene *sc, double ms[5], uint64_t *rounds)
 int rtHipRenderTilesCounted(rtHipScene *sc, rtHipStats *stats)
 {
     if (!sc || !stats) return fail("null argument");
+    if (!same_window(sc->window, default_window(sc->dev.sampleCount)))
+        return fail("rtHipRenderTilesCounted: a sample window is in effect (the work counters describe the default frame; rtHipSceneSetSampleWindow(scene, NULL) first)");
     HIP_OK(hipSetDevice(sc->device));
+    apply_window(sc, sc->window);
     HIP_OK(hipMemsetAsync(sc->dev.stats, 0, 64, sc->stream));
     HIP_OK(rtk_launch_trace(&sc->dev, 1, sc->stream));
     unsigned long long host[8] = { 0 };

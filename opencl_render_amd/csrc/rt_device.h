@@ -40,7 +40,7 @@ struct RtDevScene {
     // camera (raytrace.h:61-66)
     float eye[3], topLeft[3], lr[3], tb[3];
     float pixelSizeInv;
-    uint32_t width, height, sampleCount;
+    uint32_t width, height, sampleCount; // sampleCount: samples per pixel THIS FRAME renders (S)
     // tiles rendered by this scene instance
     const uint32_t *tileIds;
     uint32_t tileCount, tilesX;
@@ -105,6 +105,15 @@ struct RtDevScene {
     // outputs
     uint16_t *tileBuf;
     unsigned long long *stats; // 7 counters, only touched by the counted kernel variant
+    // the frame's sample window (include/raytrace_hip.h, "SAMPLE WINDOWS"; the default window is {S, 0, S, 0, 0}), behind everything else
+    // so that no other field's kernarg offset depends on it: the frame renders sample ids sampleFirst+1 .. sampleFirst+S of a sequence
+    // of seedStride samples per pixel, sample id i of pixel p is seeded p*seedStride + i (raytrace_opencl.c:481), and a sample's addend
+    // is trunc(out * (65535 / sampleDivisor)) (:728)
+    uint32_t seedStride, sampleFirst, sampleDivisor;
+    uint32_t directStore;   // 1: S == 1 and the frame starts from zero -- the kernel that finishes a pixel stores it (store_single_sample).
+                            // Tested as == 1u, the compare the kernels made against sampleCount: a != 0 test moved the opaque-diffuse logic
+                            // kernel's register allocation (127 -> 128 VGPRs)
+    uint32_t continuesFrame; // 1: the frame's first addend follows on what the tile buffer holds (window.accumulate with first > 0)
 };
 
 // error bits of the device-side input validation (rt_scene_prep.hip)

@@ -242,6 +242,10 @@ struct rtHipScene {
     rthost::Tuning tune;       // the tuning values this scene was built with (rtHipTune)
     bool unverified = false;   // planned frames were issued since the last frame_finish()
     hipStream_t lastStream = nullptr; // where the last frame was issued
+    // sample windows (rtHipSceneSetSampleWindow): the window the next frame issued will use and the one the last issued frame used (all
+    // zero before the first frame; a frame that is rendered again renders this one).  `dev` and the groups' views carry the window of the
+    // frame issued last, or of the last set.
+    rtHipSampleWindow window{}, lastWindow{};
     std::atomic<float> *progress = nullptr; // drop-in layer: where finished sample batches are reported (GetProgress, raytrace.c:566-587)
     float progressBase = 0.f, progressSpan = 0.f;
     // per-stage device time of the frames since the last query: [primary, logic, trace, accum, sort]

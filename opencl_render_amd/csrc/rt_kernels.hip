@@ -30,7 +30,7 @@ __device__ V3 trace_sample(const RtDevScene &S, const Shared &sh, uint32_t pixel
                            uint32_t sampleId, Counters &cn)
 {
     QRay ring[RT_RING];
-    uint64_t rng = (uint64_t)pixel * (uint64_t)S.sampleCount + (uint64_t)sampleId; // :481
+    uint64_t rng = (uint64_t)pixel * (uint64_t)S.seedStride + (uint64_t)sampleId; // :481
     const V3 lr = ld3(S.lr), tb = ld3(S.tb);
     V3 out = mk(0.f, 0.f, 0.f);
 
@@ -262,16 +262,17 @@ __global__ __launch_bounds__(256, RT_TRACE_WAVES) void rt_trace_kernel(const RtD
     if (gx < S.width && gy < S.height) {
         const uint32_t pixel = gy * S.width + gx;
         const uint32_t localPixel = slot * RT_TILE_PIXELS + ly * RT_TILE + lx;
-        const float scale = (float)(0xFFFF) / (float)S.sampleCount; // :728
+        const float scale = (float)(0xFFFF) / (float)S.sampleDivisor; // :728
+        uint16_t *planes = S.tileBuf + (size_t)slot * 3 * RT_TILE_PIXELS + ly * RT_TILE + lx;
         int r = 0, g = 0, b = 0;
-        // samples 1..S in order, each addend truncated on its own, saturating (:726-741; raytrace.c:612-653)
+        if (S.continuesFrame) { r = planes[0]; g = planes[RT_TILE_PIXELS]; b = planes[2 * RT_TILE_PIXELS]; } // (a later window of the sequence)
+        // the window's samples in order, each addend truncated on its own, saturating (:726-741; raytrace.c:612-653)
         for (uint32_t s = 1; s <= S.sampleCount; ++s) {
-            const V3 c = trace_sample<COUNT>(S, sh, pixel, localPixel, (float)gx, (float)gy, s, cn);
+            const V3 c = trace_sample<COUNT>(S, sh, pixel, localPixel, (float)gx, (float)gy, S.sampleFirst + s, cn);
             r = sat_add_u16(r, c.x, scale);
             g = sat_add_u16(g, c.y, scale);
             b = sat_add_u16(b, c.z, scale);
         }
-        uint16_t *planes = S.tileBuf + (size_t)slot * 3 * RT_TILE_PIXELS + ly * RT_TILE + lx;
         planes[0] = (uint16_t)r;
         planes[RT_TILE_PIXELS] = (uint16_t)g;
         planes[2 * RT_TILE_PIXELS] = (uint16_t)b;

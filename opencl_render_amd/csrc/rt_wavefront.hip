@@ -14,7 +14,8 @@
 //   wf_trace    one entry per lane: walks the non-uniform grid (:324-401) in blind phases, tests the occupied cells it
 //               passed wave-cooperatively; a hit is published as (segment, pair) in hitKey and resolved by wf_logic.
 //   wf_accum    frames with several samples: per pixel, samples in order, truncated saturating u16 accumulate into the
-//               tile buffer (:726-741); a one-sample frame's pixels are written by wf_primary / wf_logic directly.
+//               tile buffer (:726-741); a one-sample frame's pixels are written by wf_primary / wf_logic directly (unless the
+//               frame continues a sample window's sequence from the tile buffer: rt_device.h, directStore).
 //
 // Per path everything happens in the reference's order (RNG draws, ring FIFO, light loop), and paths never interact,
 // so the planes are bit-identical to the single-launch kernel (rt_kernels.hip) and to the oracle.
@@ -28,12 +29,13 @@ __device__ __forceinline__ float4 pack4(V3 v, float w) { return make_float4(v.x,
 __device__ __forceinline__ V3 xyz(float4 v) { return mk(v.x, v.y, v.z); }
 
 // A frame with ONE sample per pixel needs no ordered accumulate (raytrace_opencl.c:726-741 adds to zeroed planes once): the
-// kernel that finishes a pixel writes its three u16 values itself, wf_accum_kernel is not launched.
+// kernel that finishes a pixel writes its three u16 values itself, wf_accum_kernel is not launched.  (S.directStore; a one-sample frame
+// that continues a sample window's sequence from the tile buffer goes through sampleOut and wf_accum_kernel like any other.)
 __device__ __forceinline__ void store_single_sample(const RtDevScene &S, uint32_t localPixel, V3 c)
 {
     const uint32_t slot = localPixel / RT_TILE_PIXELS, inTile = localPixel % RT_TILE_PIXELS;
     uint16_t *planes = S.tileBuf + (size_t)slot * 3 * RT_TILE_PIXELS + inTile;
-    uint32_t samples = S.sampleCount; // :728 (1 here).  Opaque, so that the quotient is made where it is used: hoisted to the top of the
+    uint32_t samples = S.sampleDivisor; // :728 (the window's divisor; 1 by default here).  Opaque, so that the quotient is made where it is used: hoisted to the top of the
     asm volatile("" : "+s"(samples)); // logic kernel it lived in a vector register across the state machine and was spilled
     const float scale = (float)(0xFFFF) / (float)samples;
     planes[0] = (uint16_t)sat_add_u16(0, c.x, scale);
@@ -220,7 +222,7 @@ __device__ __forceinline__ void wf_primary_body(const RtDevScene &S, const RtWav
     const uint32_t outSlot = localPixel * W.samplesInBatch + sb;
     if (valid) {
         const uint32_t pixel = gy * S.width + gx;
-        rng = (uint64_t)pixel * (uint64_t)S.sampleCount + (uint64_t)(W.sampleBase + sb + 1); // :481
+        rng = (uint64_t)pixel * (uint64_t)S.seedStride + (uint64_t)(S.sampleFirst + W.sampleBase + sb + 1); // :481
         const V3 lr = ld3(S.lr), tb = ld3(S.tb);
         dir = ld3(S.topLeft);
         float k = (float)gx + rand01(rng); // LR jitter first, then TB (:496-503)
@@ -229,7 +231,7 @@ __device__ __forceinline__ void wf_primary_body(const RtDevScene &S, const RtWav
         dir.x += tb.x * k; dir.y += tb.y * k; dir.z += tb.z * k;
         hit_tri = camera_scan(S, localPixel, ld3(S.eye), dir, 0.f, RT_INF, RT_NONE, hit_t, hit_l1, hit_l2);
         if (hit_tri == RT_NONE) {
-            if (S.sampleCount == 1u) store_single_sample(S, localPixel, mk(0.f, 0.f, 0.f));
+            if (S.directStore == 1u) store_single_sample(S, localPixel, mk(0.f, 0.f, 0.f));
             else W.sampleOut[outSlot] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
@@ -298,7 +300,7 @@ __global__ __launch_bounds__(256) void wf_surface_passes_kernel(const RtDevScene
     const V3 eye = ld3(S.eye), lr = ld3(S.lr), tb = ld3(S.tb), topLeft = ld3(S.topLeft);
     Counters cn; // unused (COUNT=false)
     for (uint32_t sb = 0; sb < W.samplesInBatch; ++sb) {
-        uint64_t rng = (uint64_t)pixel * (uint64_t)S.sampleCount + (uint64_t)(W.sampleBase + sb + 1); // :481
+        uint64_t rng = (uint64_t)pixel * (uint64_t)S.seedStride + (uint64_t)(S.sampleFirst + W.sampleBase + sb + 1); // :481
         V3 dir = topLeft;
         float k = (float)gx + rand01(rng); // LR jitter first, then TB (:496-503)
         dir.x += lr.x * k; dir.y += lr.y * k; dir.z += lr.z * k;
@@ -845,7 +847,7 @@ __global__ __launch_bounds__(256, LEAN ? (FIRST ? RT_WF_LOGIC_WAVES_LEAN_FIRST :
 
             if (finished) {
                 const uint2 where2 = FIRST ? *reinterpret_cast<const uint2 *>(W.meta + a) : make_uint2(meta.x, meta.y); // {output slot, pixel}
-                if (S.sampleCount == 1u) store_single_sample(S, where2.y, out);
+                if (S.directStore == 1u) store_single_sample(S, where2.y, out);
                 else W.sampleOut[where2.x] = pack4(out, 0.f);
             } else {
                 asm volatile("" : "+v"(a));
@@ -1164,7 +1166,7 @@ __global__ __launch_bounds__(256, LEAN ? (FIRST ? RT_WF_LOGIC_WAVES_LEAN_FIRST :
             if (laexcl != 12345u) DG(7);
             if (finished) {
                 const uint2 where2 = FIRST ? *reinterpret_cast<const uint2 *>(W.meta + a) : make_uint2(meta.x, meta.y); // {output slot, pixel}
-                if (S.sampleCount == 1u) store_single_sample(S, where2.y, out);
+                if (S.directStore == 1u) store_single_sample(S, where2.y, out);
                 else W.sampleOut[where2.x] = pack4(out, 0.f);
             } else {
                 // park the path in HBM until the grid has answered.  The index is made opaque here so that the store addresses are
@@ -2015,7 +2017,7 @@ __global__ __launch_bounds__(256) void wf_accum_kernel(const RtDevScene S, const
     uint16_t *planes = S.tileBuf + (size_t)slot * 3 * RT_TILE_PIXELS + inTile;
     int r = 0, g = 0, b = 0;
     if (!first) { r = planes[0]; g = planes[RT_TILE_PIXELS]; b = planes[2 * RT_TILE_PIXELS]; }
-    const float scale = (float)(0xFFFF) / (float)S.sampleCount; // :728
+    const float scale = (float)(0xFFFF) / (float)S.sampleDivisor; // :728
     for (uint32_t sb = 0; sb < W.samplesInBatch; ++sb) {
         const float4 c = W.sampleOut[localPixel * W.samplesInBatch + sb];
         r = sat_add_u16(r, c.x, scale);

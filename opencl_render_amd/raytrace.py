@@ -108,6 +108,13 @@ class Camera(C.Structure):  # rtHipCamera
                 ("pixelSizeInv", C.c_float)]
 
 
+class SampleWindow(C.Structure):  # rtHipSampleWindow
+    _fields_ = [(n, C.c_uint32) for n in ("total", "first", "divisor", "accumulate", "advance")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class GeometryUpdate(C.Structure):  # rtHipGeometryUpdate
     _fields_ = [("vertexCount", C.c_uint32), ("vertex", C.c_void_p), ("triIndex", C.c_void_p), ("triNormal", C.c_void_p), ("arraysOnDevice", C.c_int32)]
 
@@ -127,6 +134,7 @@ DROPIN_SYMBOLS = [
 ]
 RESIDENT_SYMBOLS = [
     "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipSceneGetCamera", "rtHipSceneSetCamera", "rtHipSceneSetGeometry", "rtHipRenderTiles", "rtHipFrameFinish",
+    "rtHipSampleWindowCheck", "rtHipSceneSetSampleWindow", "rtHipSceneGetSampleWindow",
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
     "rtHipScenePasses", "rtHipPassBuffer", "rtHipPassBufferBytes", "rtHipReadbackPasses",
@@ -212,6 +220,9 @@ def lib() -> C.CDLL:
     L.rtHipTestSceneGeometryTimes.argtypes = [vp, C.POINTER(C.c_double * 4)]
     L.rtHipRenderTiles.argtypes = [vp, vp]
     L.rtHipFrameFinish.argtypes = [vp, C.POINTER(C.c_int)]
+    L.rtHipSampleWindowCheck.argtypes = [u32, C.POINTER(SampleWindow)]
+    L.rtHipSceneSetSampleWindow.argtypes = [vp, C.POINTER(SampleWindow)]
+    L.rtHipSceneGetSampleWindow.argtypes = [vp, C.POINTER(SampleWindow), C.POINTER(SampleWindow)]
     L.rtHipRenderTilesCounted.argtypes = [vp, C.POINTER(Stats)]
     L.rtHipDebugCounters.argtypes = [vp, C.POINTER(C.c_uint64 * 8), C.c_int]
     L.rtHipSetPipeline.argtypes = [vp, C.c_int]
@@ -1115,6 +1126,31 @@ class ResidentScene:
         redone = C.c_int(0)
         self._check(lib().rtHipFrameFinish(self.handle, C.byref(redone)), "rtHipFrameFinish")
         return bool(redone.value)
+
+    def set_sample_window(self, total: Optional[int] = None, first: int = 0, divisor: Optional[int] = None, accumulate: bool = False,
+                          advance: bool = False) -> None:
+        """The sample window of the frames to come (rtHipSceneSetSampleWindow; include/raytrace_hip.h, "SAMPLE WINDOWS"): a frame renders
+        sample ids first+1 .. first+S of a sequence of `total` samples per pixel, each scaled by 65535 / divisor.  None means S, so
+        set_sample_window() is the default window."""
+        S = int(self.scene.sample_count)
+        w = SampleWindow(S if total is None else total, first, S if divisor is None else divisor, int(accumulate), int(advance))
+        self._check(lib().rtHipSceneSetSampleWindow(self.handle, C.byref(w)), "rtHipSceneSetSampleWindow")
+
+    def sample_window(self) -> dict:
+        """{"next": the window the next frame will use, "last": the one the last issued frame used (all zero before the first frame)}."""
+        nxt, last = SampleWindow(), SampleWindow()
+        self._check(lib().rtHipSceneGetSampleWindow(self.handle, C.byref(nxt), C.byref(last)), "rtHipSceneGetSampleWindow")
+        return {"next": nxt.as_dict(), "last": last.as_dict()}
+
+    def progressive(self, total: int, stream: int = 0):
+        """Renders a frame of `total` samples per pixel in total / S frames of S: sets the progressive window {total, 0, total, 1, 1} and
+        yields (samples_done, planes) after each frame, planes as readback() returns them.  The last planes are bit for bit the frame of a
+        scene created with `total` samples; an earlier one, scaled by total / samples_done on the host, is a preview."""
+        S = int(self.scene.sample_count)
+        self.set_sample_window(total, 0, total, accumulate=True, advance=True)
+        for done in range(S, int(total) + 1, S):
+            self.render(stream)
+            yield done, self.readback()
 
     def set_pipeline(self, pipeline: int):
         self._check(lib().rtHipSetPipeline(self.handle, pipeline), "rtHipSetPipeline")
