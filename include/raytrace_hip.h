@@ -1041,8 +1041,10 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
  * "state_mb", "groups", "lookahead", "seg0".."seg4", "seg_rays0".."seg_rays3", "fast_quotient", "spin_limit", "append_rays", "ordered_first", "extra_factor",
  * "slice_rays", "small_slices", "group_rays", "blocking", "batch_plan", "pipeline", "timing", "cache", "logic_class" (0: every scene's
  * paths run on the general logic kernel; 1, the default: on the kernel of the scene's path class), "dead_shadow" (0: trace every
- * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), and the test hooks
- * "plan_rounds", "plan_grid_tiny", "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
+ * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), "logic_split" (1, the
+ * default: the later logic rounds of an opaque-diffuse scene with look-ahead on stream the answers and shade the bounce hits densely; 0:
+ * one logic kernel per round), and the test hooks
+ * "plan_rounds", "plan_grid_tiny", "plan_shade_skip" (planned frames launch no shade pass), "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
  * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
  * and most 2^32 - 1; above it they return -3), "query_rays" (rays per staging chunk of rtHipSceneIntersect, default 2^20), and
  * "ao_samples" (pixel samples per chunk of the ambient occlusion calls, default 2^20, at most 2^24), and "bake_texels" (texels per chunk
@@ -1071,6 +1073,13 @@ int rtHipTestPathClass(const rtHipScene *scene);
  * after the frame was synchronised; with several sample batches the figures are the last batch's.  Returns the frame's round count,
  * -1 for invalid arguments. */
 int rtHipTestRoundLog(const rtHipScene *scene, cl_uint *rays, cl_uint n);
+
+/* TEST-ONLY: the split logic rounds ("logic_split") of the scene's last wavefront frame.  listed[r] for r < n: the paths round r listed
+ * for its shade pass, summed over the tile groups, as the last shade pass of that round logged it (a planned frame that skips the launch
+ * because its plan says 0 logs nothing; rounds the frame did not issue read 0).  Call after the frame was synchronised.  Returns the
+ * number of logic rounds the frame issued as answer + shade launches, over its sample batches and tile groups (0: none was split), -1
+ * for invalid arguments. */
+int rtHipTestShadeLog(const rtHipScene *scene, cl_uint *listed, cl_uint n);
 
 /* TEST-ONLY: what the calling thread's last device list builds did (rtHipBuildCameraListDevice, rtHipBuildSceneGridDevice; each
  * clears and fills its own fields), so that tests can prove which paths ran.  out[i] for i < n in the order of RT_BUILD_LOG_*:

@@ -38,9 +38,13 @@ extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefr
 extern "C" hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const RtWavefront *wf, uint32_t *passBuf, hipStream_t stream);
 extern "C" hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const RtWavefront *wf, float *surfBuf, hipStream_t stream);
 extern "C" hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next, hipStream_t stream);
+extern "C" hipError_t rtw_launch_answer(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtShadeList *list,
+                                        uint32_t shadeFollows, hipStream_t stream);
+extern "C" hipError_t rtw_launch_shade(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next,
+                                       const RtShadeList *list, hipStream_t stream);
 extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
 extern "C" hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
-extern "C" hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, hipStream_t stream);
+extern "C" hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, uint32_t *shadeCount, hipStream_t stream);
 extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefront *wf, int first, hipStream_t stream);
 extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
                                        uint32_t fastQuotient, hipStream_t stream);
@@ -449,9 +453,11 @@ int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
             sc->alloc<uint2>(cap, &Wf.pathOf[1]) || sc->alloc<unsigned long long>(qcap, &Wf.hitKey[0]) || sc->alloc<unsigned long long>(qcap, &Wf.hitKey[1]) ||
             sc->alloc<uint4>(cap, &Wf.res) || sc->alloc<float4>(gpix * sb, &Wf.sampleOut) ||
             sc->alloc<uint32_t>(ecap, &Wf.sortRank) || sc->alloc<uint16_t>(ecap, &Wf.sortTag) || sc->alloc<uint32_t>(ecap, &Wf.sortedIdx) ||
-            sc->alloc<uint32_t>((uint64_t)3 * RT_WF_CTL_WORDS, &Wf.ctl))
+            sc->alloc<uint32_t>((uint64_t)3 * RT_WF_CTL_WORDS, &Wf.ctl) ||
+            sc->alloc<uint4>(cap, &G.shade.list) || sc->alloc<uint32_t>((uint64_t)3 * RT_WF_SHARDS, &G.shade.count)) // (split logic rounds: 16 bytes per path)
             return -1;
         HIP_OK(hipMemsetAsync(Wf.ctl, 0, sizeof(uint32_t) * 3 * RT_WF_CTL_WORDS, sc->stream));
+        HIP_OK(hipMemsetAsync(G.shade.count, 0, sizeof(uint32_t) * 3 * RT_WF_SHARDS, sc->stream));
         HIP_OK(G.hostLog.make(sizeof(uint4) * RT_WF_ROUND_LOG, hipHostMallocMapped));
         memset(G.hostLog, 0, sizeof(uint4) * RT_WF_ROUND_LOG);
         HIP_OK(hipHostGetDevicePointer((void **)&Wf.roundLog, G.hostLog, 0));
@@ -719,6 +725,18 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
         const uint64_t want = m.ordered ? ((rays + extra) * 11 / 10 + 255) / 256 + 8 : (rays * 11 / 10 + m.groupRays - 1) / m.groupRays + 2ull * m.slices + 8;
         return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(want, worst), 1);
     };
+    // workgroups of a split round's shade pass (0: not launched).  Its waves stride over their slice's list, so any whole number of waves
+    // per slice is enough; a planned frame launches as many as the list the plan logged fills once -- a tenth more plus a few, like a
+    // round's rays, spread over the slices -- and a watched one the logic kernel's grid.
+    auto shade_blocks = [&](rtHipScene::Group &G, uint32_t r, const RtRoundMode &m) -> uint32_t {
+        if (!planned || r >= RT_WF_ROUND_LOG) return G.logicBlocks;
+        const uint64_t listed = T.planShadeSkip ? 0 : G.plan[r].shade;
+        if (listed == 0) return 0;
+        const uint64_t perSlice = (listed * 11 / 10 + m.slices - 1) / m.slices + 8;
+        const uint64_t waves = (perSlice + 63) / 64 * m.slices, unit = RT_WF_SHARDS / 4;
+        return (uint32_t)std::min<uint64_t>(G.logicBlocks, ((waves + 3) / 4 + unit - 1) / unit * unit);
+    };
+    uint64_t splitRounds = 0;
     auto issue_round = [&](rtHipScene::Group &G, hipStream_t on) -> int {
         const uint32_t r = G.rounds;
         const RtRoundMode mode = r > 0 ? round_mode(G, r) : RtRoundMode{ 0u, 4096u, 64u, (uint32_t)RT_WF_SHARDS };
@@ -727,7 +745,16 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
             HIP_OK(stage(2, on, [&] { return rtw_launch_trace(&G.dev, &G.wf, r, trace_blocks(G, r, mode), &mode, on); }));
         }
         const RtRoundMode next = round_mode(G, r + 1);
-        HIP_OK(stage(1, on, [&] { return rtw_launch_logic(&G.dev, &G.wf, r, G.logicBlocks, mode.slices, &next, on); }));
+        // A later round of the opaque-diffuse class with look-ahead on (Tuning::logicSplit): the answers as a stream (wf_answer_kernel), then the
+        // paths whose bounce hit something shaded by dense waves (wf_shade_kernel).  A planned frame sizes the shade launch from the list the plan
+        // logged and skips it where that was empty; the answer kernel is told, and raises RT_WF_ERR_GRID if it lists a path all the same.
+        if (r > 0 && T.logicSplit && G.wf.lookAhead && G.dev.pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE) {
+            const uint32_t shadeBlocks = shade_blocks(G, r, mode);
+            ++splitRounds;
+            HIP_OK(stage(1, on, [&] { return rtw_launch_answer(&G.dev, &G.wf, r, G.logicBlocks, mode.slices, &G.shade, shadeBlocks ? 1u : 0u, on); }));
+            if (shadeBlocks) HIP_OK(stage(1, on, [&] { return rtw_launch_shade(&G.dev, &G.wf, r, shadeBlocks, mode.slices, &next, &G.shade, on); }));
+        } else
+            HIP_OK(stage(1, on, [&] { return rtw_launch_logic(&G.dev, &G.wf, r, G.logicBlocks, mode.slices, &next, on); }));
         ++G.rounds;
         return 0;
     };
@@ -765,7 +792,10 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
             G.rounds = 0;
             G.modes.clear();
             G.guessRays = (uint64_t)(G.slot1 - G.slot0) * RT_TILE_PIXELS * G.wf.samplesInBatch; // round 1 of a watched batch: as if every pixel were a path
-            if (!G.ctlClean) HIP_OK(hipMemsetAsync(G.wf.ctl, 0, sizeof(uint32_t) * (size_t)3 * RT_WF_CTL_WORDS, on));
+            if (!G.ctlClean) {
+                HIP_OK(hipMemsetAsync(G.wf.ctl, 0, sizeof(uint32_t) * (size_t)3 * RT_WF_CTL_WORDS, on));
+                HIP_OK(hipMemsetAsync(G.shade.count, 0, sizeof(uint32_t) * (size_t)3 * RT_WF_SHARDS, on));
+            }
             G.ctlClean = false;
             if (!planned) memset(G.hostLog, 0, sizeof(uint4) * RT_WF_ROUND_LOG); // (nothing of this group is in flight: the batch before was waited for)
             if (sc->passBuf) {
@@ -789,7 +819,9 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
             if (planned) {
                 while (G.rounds < planRounds)
                     if (issue_round(G, on) != 0) return -1;
-                HIP_OK(rtw_launch_status(&G.wf, G.rounds, on));
+                // (the shade lists' lengths are zeroed with the control words where the batch can have run split rounds)
+                const bool split = T.logicSplit && G.wf.lookAhead && G.dev.pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE;
+                HIP_OK(rtw_launch_status(&G.wf, G.rounds, split ? G.shade.count : nullptr, on));
                 G.ctlClean = true;
             } else if (issue_chunk(G, on) != 0) return -1;
         }
@@ -818,6 +850,7 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
                 for (uint32_t r = 0; r < RT_WF_ROUND_LOG; ++r) {
                     rtHipScene::Group::RoundPlan &N = G.planNext[r]; // the maximum over the watched batches
                     N.rays = std::max(N.rays, log[r].x);
+                    N.shade = std::max(N.shade, log[r].w);
                     const uint32_t seg = r < G.modes.size() ? G.modes[r].segLen : 4096u;
                     if (N.extraSegLen != seg && N.extraSegLen != 0u) N.extraSegLen = 0xffffffffu; // (batches cut differently: no figure)
                     else { N.extraSegLen = seg; N.extra = std::max(N.extra, log[r].z); }
@@ -840,7 +873,7 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
                 need = std::max(need, G.roundsNeeded);
                 for (uint32_t r = 0; r < RT_WF_ROUND_LOG; ++r) {
                     G.plan[r] = G.planNext[r];
-                    G.plan[r].rays += G.plan[r].rays / 10; G.plan[r].extra += G.plan[r].extra / 10;
+                    G.plan[r].rays += G.plan[r].rays / 10; G.plan[r].extra += G.plan[r].extra / 10; G.plan[r].shade += G.plan[r].shade / 10;
                 }
             }
             planRounds = need + 1; // (one spare round: a later batch's deepest path may go one bounce further)
@@ -864,6 +897,7 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
             HIP_OK(hipStreamWaitEvent(st, sc->groups[g].done, 0));
         }
     sc->roundsLast = rounds;
+    sc->splitRoundsLast = splitRounds;
     return 0;
 }
 
@@ -2181,9 +2215,9 @@ int rtHipTune(const char *key, double value)
         { "seg0", &T.segLen[0] }, { "seg1", &T.segLen[1] }, { "seg2", &T.segLen[2] }, { "seg3", &T.segLen[3] }, { "seg4", &T.segLen[4] },
         { "seg_rays0", &T.segRays[0] }, { "seg_rays1", &T.segRays[1] }, { "seg_rays2", &T.segRays[2] }, { "seg_rays3", &T.segRays[3] },
         { "fast_quotient", &T.fastQuotient }, { "spin_limit", &T.spinLimit }, { "append_rays", &T.appendRays }, { "ordered_first", &T.orderedFirst }, { "slice_rays", &T.sliceRays },
-        { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny },
+        { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny }, { "plan_shade_skip", &T.planShadeSkip },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
-        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
+        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "logic_split", &T.logicSplit }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
         { "ao_samples", &T.aoSamples, nullptr, 1u << 22 }, { "bake_texels", &T.bakeTexels, nullptr, 1u << 24 },
         { "state_mb", nullptr, &T.stateMb, HUGE_VAL }, { "build_key_cap", nullptr, &T.buildKeyCap, 1e18 }, { "build_list_limit", nullptr, &T.buildListLimit },
     };
@@ -2243,6 +2277,19 @@ int rtHipTestRoundLog(const rtHipScene *scene, uint32_t *rays, uint32_t n)
         rays[r] = (uint32_t)std::min<uint64_t>(sum, 0xffffffffu);
     }
     return (int)scene->roundsLast;
+}
+
+int rtHipTestShadeLog(const rtHipScene *scene, uint32_t *listed, uint32_t n)
+{
+    if (!scene || (n && !listed)) return -1;
+    const uint32_t rounds = (uint32_t)std::min<uint64_t>(scene->roundsLast, RT_WF_ROUND_LOG);
+    for (uint32_t r = 0; r < n; ++r) {
+        uint64_t sum = 0;
+        if (r < rounds)
+            for (const auto &G : scene->groups) sum += G.hostLog[r].w; // (mapped host memory, written by the shade passes)
+        listed[r] = (uint32_t)std::min<uint64_t>(sum, 0xffffffffu);
+    }
+    return (int)std::min<uint64_t>(scene->splitRoundsLast, 0x7fffffffu);
 }
 
 int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement, uint64_t count, void *out)

@@ -149,7 +149,9 @@ struct RtDevScene {
 #define RT_WF_ROUND_LOG 64     // rounds of a batch that are logged for the launch plan (RtWavefront::roundLog)
 #define RT_WF_ERR_SPIN 1u     // wf_trace_kernel's walk guard tripped: rays were abandoned, the frame is invalid
 #define RT_WF_ERR_GRID 2u     // a planned frame's trace grid was smaller than the round's entries: entries were not traced; the host renders
-                              // the frame again with the worst-case grid (rt_api.cpp, frame_finish)
+                              // the frame again with the worst-case grid (rt_api.cpp, frame_finish).  Also: a planned frame skipped a shade launch
+                              // (the plan said no bounce hit anything in that round) and the round listed a path for it
+#define RT_WF_ERR_SPLIT 4u    // wf_answer_kernel met a path that is not of the shape it knows (opaque-diffuse class, look-ahead on): the frame is invalid
 // per-round control words, three sets used in turn like the queue lengths (round r uses set r % 3): logic(r-1) fills set r,
 // scatter(r) and trace(r) read it, logic(r) zeroes set (r + 2) % 3 for logic(r+1)
 #define RT_WF_CTL_COUNTS 0                                   // [RT_WF_QSHARDS] queue lengths
@@ -181,7 +183,7 @@ struct RtWavefront {
     uint32_t fastQuotient;   // 1: waves whose rays all have tame exponents skip the scaling / fix-up instructions of the quotients
     uint32_t spinLimit;      // walk phases a wave of wf_trace_kernel may run before it gives up and raises RT_WF_ERR_SPIN (default 16384)
     uint32_t *hostStatus;    // pinned HOST words mapped into the device (RT_WF_STATUS_*): written by kernels, read by the host after a sync
-    uint4 *roundLog;         // [RT_WF_ROUND_LOG] per round: x rays, y longest queue slice, z entries in region B
+    uint4 *roundLog;         // [RT_WF_ROUND_LOG] per round: x rays, y longest queue slice, z entries in region B, w shade-list length (split rounds)
     // per-path state, indexed by path id
     unsigned long long *rng; // generator state (raytrace_opencl.c:474-481), already moved past the current hit's light draws
     unsigned long long *rngL; // lightCount > 1 only: where the current hit's NEXT light set-up draws from
@@ -219,6 +221,15 @@ struct RtWavefront {
     uint16_t *sortTag;         // [2*capacity + extraCap] the class: bin | copy << 6 (what wf_scatter_kernel needs of an entry, 6 bytes instead of a 64-byte line)
     uint32_t extraCap;         // capacity of region B (multiple of 256)
     float4 *sampleOut;         // [capacity] finished colour per output slot
+};
+
+// The split logic rounds of the opaque-diffuse class (rt_wavefront.hip, wf_answer_kernel / wf_shade_kernel): the paths of a round whose
+// bounce ray hit something, listed densely for the shade pass.  An argument of its own for the kernels that use it (RtWavefront keeps its
+// layout).  Sliced like the round's main queue: slice s holds list[s*sliceCap, s*sliceCap + count[(round % 3)*RT_WF_SHARDS + s]), sliceCap =
+// capacity / slices; a slice's list is never longer than its queue slice.  The counts are zeroed in-stream two rounds ahead like the control words.
+struct RtShadeList {
+    uint4 *list;     // [capacity] x: path id  y,z: the bounce answer's hitKey (low, high word)
+    uint32_t *count; // [3][RT_WF_SHARDS]
 };
 
 // ---- ambient occlusion (rt_wavefront.hip, rt_ao_*; definition in include/raytrace_hip.h, "AMBIENT OCCLUSION") -----------------------

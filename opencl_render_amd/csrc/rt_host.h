@@ -58,6 +58,7 @@ struct Tuning {
     uint32_t blocking = 0;          // 1: every frame watches its queue (no launch plan)
     uint32_t planRounds = 0;        // test hook: planned frames issue at most this many rounds, so that the too-short-plan path runs
     uint32_t planGridTiny = 0;      // test hook: planned trace grids of one workgroup, so that the too-small-grid path runs
+    uint32_t planShadeSkip = 0;     // test hook: planned frames launch no shade pass (as if the plan's shade lists were empty), so that the listed-but-skipped path runs
     uint32_t pipeline = RT_HIP_PIPELINE_WAVEFRONT;
     uint32_t timing = 0;            // 1: where the time of a scene build / a RaytraceAll call goes (stderr)
     uint32_t virtualDevices = 0;    // test hook: the all-GPUs id deals the tiles over this many instances on the devices that are there
@@ -65,6 +66,7 @@ struct Tuning {
     uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
     uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
     uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
+    uint32_t logicSplit = 1;        // 1: rounds >= 1 of the opaque-diffuse class (look-ahead on) run wf_answer_kernel + wf_shade_kernel; 0: wf_logic_kernel
     uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
     uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
     uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
@@ -216,6 +218,7 @@ struct rtHipScene {
     struct Group {
         RtDevScene dev{};
         RtWavefront wf{};
+        RtShadeList shade{};            // the split logic rounds' list of paths to shade (rt_device.h)
         rthost::Stream stream;          // groups 1.. ; group 0 runs on the caller's stream
         rthost::Event done;
         uint32_t logicBlocks = 1, traceBlocks = 1, queueBlocks = 1;
@@ -228,7 +231,8 @@ struct rtHipScene {
         uint32_t roundsNeeded = 0;
         // per round: rays (entries in region A), the longest queue slice, entries in region B -- the maximum over the watched batches
         // rays of the round, and -- an ordered round -- the further segments of its cut rays under the cut it was logged with
-        struct RoundPlan { uint32_t rays = 0, extra = 0, extraSegLen = 0; };
+        // and -- a split logic round -- the paths it listed for its shade pass
+        struct RoundPlan { uint32_t rays = 0, extra = 0, extraSegLen = 0, shade = 0; };
         rthost::Pinned<uint4> hostLog;  // pinned + mapped: RtWavefront::roundLog, written by the kernels, read by the host after a sync
         RoundPlan plan[RT_WF_ROUND_LOG], planNext[RT_WF_ROUND_LOG];
         std::vector<RtRoundMode> modes; // how the rounds of the batch being issued are laid out (modes[r] is decided when logic(r-1) is launched)
@@ -238,6 +242,7 @@ struct rtHipScene {
     rthost::Event forkEvent;
     uint32_t samplesPerBatch = 1;
     uint32_t planRounds = 0;   // rounds a planned frame issues per batch; 0 = no plan yet (the next frame is a discovery frame)
+    uint64_t splitRoundsLast = 0; // logic rounds the last frame issued as answer + shade launches, over its batches and groups (rtHipTestShadeLog)
     bool blocking = false;     // every frame watches the queue (no plan)
     rthost::Tuning tune;       // the tuning values this scene was built with (rtHipTune)
     bool unverified = false;   // planned frames were issued since the last frame_finish()

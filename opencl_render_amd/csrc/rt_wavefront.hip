@@ -511,6 +511,46 @@ __device__ __forceinline__ bool cut_at(float ta, float te, uint32_t k, uint32_t 
 #else
 #define DG(i)
 #endif
+// PC_LIGHT_ACCUM (:628-636) and PC_SHADE_END (:647-651) of the opaque-diffuse class for wf_answer_kernel: the operations of the class path's
+// light_accum and shade_end (rt_wf_logic_body.h) in their order; lc = the light's colour and half-attenuation distance.  (Those stay written
+// out where they are: calling these from there moved instructions in the round-0 kernels, which this split leaves as they were.)
+__device__ __forceinline__ void class_light_accum(V3 &face, float ndl, bool front, float lmax, float4 lc, V3 atten)
+{
+    const float mag = __builtin_fabsf(ndl);
+    const float x = lmax / lc.w;
+    const float e = mag * half_falloff(x);
+    if ((0.f <= ndl) == front) {
+        face.x += (1.f - face.x) * atten.x * e * lc.x;
+        face.y += (1.f - face.y) * atten.y * e * lc.y;
+        face.z += (1.f - face.z) * atten.z * e * lc.z;
+    }
+}
+__device__ __forceinline__ void class_shade_end(V3 &out, V3 P, V3 face)
+{
+    out.x += P.x * face.x;
+    out.y += P.y * face.y;
+    out.z += P.z * face.z;
+}
+
+// For the launch plan: a round's rays and its longest queue slice, as the logic kernel logs them (rt_wf_logic_body.h), for wf_answer_kernel.
+// One whole workgroup adds up the RT_WF_QSHARDS queue lengths.
+__device__ __forceinline__ void log_round_rays(const RtWavefront &W, const uint32_t *ctlIn, uint32_t round, uint32_t lane, uint32_t wave)
+{
+    __shared__ uint32_t sumWave[4], maxWave[4];
+    static_assert(RT_WF_QSHARDS == 512, "two queue lengths per thread");
+    const uint32_t c0 = ctlIn[RT_WF_CTL_COUNTS + threadIdx.x], c1 = ctlIn[RT_WF_CTL_COUNTS + 256 + threadIdx.x];
+    uint32_t n = c0 + c1, m = max(c0, c1);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { n += __shfl_xor(n, off, 64); m = max(m, (uint32_t)__shfl_xor((int)m, off, 64)); }
+    if (lane == 0) { sumWave[wave] = n; maxWave[wave] = m; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t *log = reinterpret_cast<uint32_t *>(W.roundLog + round);
+        log[0] = sumWave[0] + sumWave[1] + sumWave[2] + sumWave[3];
+        log[1] = max(max(maxWave[0], maxWave[1]), max(maxWave[2], maxWave[3]));
+    }
+}
+
 // What shading a hit reads of its triangle, fetched in one batch: the 24-float shading row (rt_device.h, triShade) and the
 // first vertex (triRec[0]).
 struct TriRow { float v[24]; float4 a; uint32_t tri; };
@@ -531,910 +571,112 @@ __device__ __forceinline__ void load_tri_row(const RtDevScene &S, uint32_t tri, 
 // slicesIn = queue slices per kind of THIS round (what logic(round - 1) was told), next = how the round this launch spawns is laid out.
 // LEAN = the scene is in the opaque-diffuse path class (RtDevScene::pathClass, rt_api.cpp): the path is written out as its fixed shape
 // instead of the general state machine below, in fewer registers.
+// SHADE = the dense shade pass of a split round (class only, rounds >= 1; wf_shade_kernel): one lane per entry of the round's shade list
+// (wf_answer_kernel, below) instead of per queue entry.  An entry is a path whose bounce ray hit something; the answer kernel has folded
+// what came before (the shadow answer) into the stored `out` and left the rest of the state alone, so the lane takes the class path up at
+// "a ray's answer" with the listed key.  The housekeeping is the answer kernel's; this pass logs the list's length.
+// The kernel's body is in rt_wf_logic_body.h: wf_shade_kernel (below) is the same text with SHADE on, and a kernel whose body is a function
+// shared through a call compiled to other instructions than the one that holds it.
 template <bool FIRST, bool ORDERED, bool LEAN>
 __global__ __launch_bounds__(256, LEAN ? (FIRST ? RT_WF_LOGIC_WAVES_LEAN_FIRST : RT_WF_LOGIC_WAVES_LEAN)
                                        : (FIRST ? (ORDERED ? RT_WF_LOGIC_WAVES_FIRST_ORDERED : RT_WF_LOGIC_WAVES_FIRST) : RT_WF_LOGIC_WAVES)) void wf_logic_kernel(const RtDevScene S, const RtWavefront W, const uint32_t round,
                                                                                                              const uint32_t slicesIn, const RtRoundMode next)
 {
-    __shared__ Shared sh; // the texel/255 table and the split planes (for the entries of the rays spawned here)
-    // the first RT_WF_LIGHTS_LDS lights, one LDS read away instead of a chain of small global loads per light and state
-    __shared__ float4 ltPosRadius[RT_WF_LIGHTS_LDS], ltDirSpread[RT_WF_LIGHTS_LDS], ltColHalf[RT_WF_LIGHTS_LDS];
-    __shared__ int ltType[RT_WF_LIGHTS_LDS];
-    // an ordered round's classes, per wave: entries of this wave per walk-length class, then where the class's ranks of this wave start
-    __shared__ uint32_t waveHist[ORDERED ? 4 : 1][RT_WF_SORT_BINS], waveBase[ORDERED ? 4 : 1][RT_WF_SORT_BINS];
-    __shared__ uint8_t cellLut[ORDERED ? 3 * 256 : 4];
-    // per wave: whose ray the i-th further segment belongs to, and its rank in the wave | class << 24
-    __shared__ uint8_t itemOwner[ORDERED ? 4 : 1][2 * 64 * (RT_WF_MAXSEG - 1)];
-    __shared__ uint32_t itemWord[ORDERED ? 4 : 1][ORDERED ? 2 * 64 * (RT_WF_MAXSEG - 1) : 1];
-    __shared__ float lutScale[3];
-    static_assert(RT_WF_SORT_BINS == 64, "one class per lane");
-    sh.unit255[threadIdx.x] = (float)threadIdx.x / 255.f;
-    if (ORDERED) {
-        float *pl = &sh.planes[0][0];
-        for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) pl[i] = S.boxMin[i];
-        waveHist[threadIdx.x >> 6][threadIdx.x & 63] = 0u;
-        if (threadIdx.x < 3 * 256 / 4) reinterpret_cast<uint32_t *>(cellLut)[threadIdx.x] = reinterpret_cast<const uint32_t *>(S.cellLut)[threadIdx.x];
-        if (threadIdx.x < 3) lutScale[threadIdx.x] = 256.f / (S.boxMin[threadIdx.x * (RT_GRID_DIV + 1) + RT_GRID_DIV] - S.boxMin[threadIdx.x * (RT_GRID_DIV + 1)]);
-    }
-    if (threadIdx.x < RT_WF_LIGHTS_LDS && threadIdx.x < S.lightCount) {
-        const uint32_t k = threadIdx.x;
-        ltType[k] = S.lightType[k];
-        ltPosRadius[k] = make_float4(S.lightPos[4 * k], S.lightPos[4 * k + 1], S.lightPos[4 * k + 2], S.lightRadius[k]);
-        ltDirSpread[k] = make_float4(S.lightDir[4 * k], S.lightDir[4 * k + 1], S.lightDir[4 * k + 2], S.lightSpread[k]);
-        ltColHalf[k] = make_float4(S.lightCol[4 * k], S.lightCol[4 * k + 1], S.lightCol[4 * k + 2], S.lightHalfAtt[k]);
-    }
-    __syncthreads();
-    auto light_type = [&](uint32_t k) -> int { return k < RT_WF_LIGHTS_LDS ? ltType[k] : S.lightType[k]; };
-    auto light_pos_radius = [&](uint32_t k) -> float4 {
-        return k < RT_WF_LIGHTS_LDS ? ltPosRadius[k] : make_float4(S.lightPos[4 * k], S.lightPos[4 * k + 1], S.lightPos[4 * k + 2], S.lightRadius[k]);
-    };
-    auto light_dir_spread = [&](uint32_t k) -> float4 {
-        return k < RT_WF_LIGHTS_LDS ? ltDirSpread[k] : make_float4(S.lightDir[4 * k], S.lightDir[4 * k + 1], S.lightDir[4 * k + 2], S.lightSpread[k]);
-    };
-    auto light_col_half = [&](uint32_t k) -> float4 {
-        return k < RT_WF_LIGHTS_LDS ? ltColHalf[k] : make_float4(S.lightCol[4 * k], S.lightCol[4 * k + 1], S.lightCol[4 * k + 2], S.lightHalfAtt[k]);
-    };
+    constexpr bool SHADE = false;
+    const RtShadeList L{ nullptr, nullptr }; // (named in SHADE branches only)
+#include "rt_wf_logic_body.h"
+}
 
-    const uint32_t in = round & 1, outq = in ^ 1;
+// ---- stage 2, split (opaque-diffuse class with look-ahead, rounds >= 1): answers streamed, bounce hits shaded densely ----------------
+// Of such a round's paths one in nine has anything to shade -- its bounce ray hit something.  The others read two answers, fold the
+// shadow answer into `out` and store their pixel: a stream, for which the logic kernel's registers (4 waves per SIMD) and its chain of
+// dependent loads are not needed.  So the round is two launches.  wf_answer_kernel, one lane per main entry in the logic kernel's
+// addressing, does what needs no shading, with the logic kernel's operations in its order:
+//   a shadow answer:  atten = 1, times zero when the ray was answered, light_accum, shade_end; then the next ring entry -- none: the pixel
+//                     is stored; the bounce, whose look-ahead answer is a miss: the ring is empty, the pixel is stored;
+//   a ray's answer (the bounce became the main ray because the camera hit's shadow ray was dead): a miss stores the pixel.
+// A path whose bounce answer is a hit is appended to the round's shade list (RtShadeList) with the winning key; of its state only `out`
+// is rewritten.  wf_shade_kernel (wf_logic_body<.., SHADE>) then runs the class code from the hit on with one lane per listed path.
+// The in-stream housekeeping of the round (control words two rounds ahead, round log) is done here.  shadeFollows = 0: the host's plan
+// says nothing will be listed and no shade pass is launched -- a wave that lists a path all the same raises RT_WF_ERR_GRID.
+#ifndef RT_WF_ANSWER_WAVES
+#define RT_WF_ANSWER_WAVES 8
+#endif
+__global__ __launch_bounds__(256, RT_WF_ANSWER_WAVES) void wf_answer_kernel(const RtDevScene S, const RtWavefront W, const uint32_t round, const uint32_t slicesIn,
+                                                                            const RtShadeList L, const uint32_t shadeFollows)
+{
+    const uint32_t in = round & 1;
     const uint32_t *ctlIn = W.ctl + (round % 3) * RT_WF_CTL_WORDS;
-    uint32_t *ctlOut = W.ctl + ((round + 1) % 3) * RT_WF_CTL_WORDS;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t waveId = (blockIdx.x * 256 + threadIdx.x) >> 6, waves = (gridDim.x * 256) >> 6;
-    Counters cn; // unused (COUNT=false instantiations below)
-    // in-stream housekeeping: the control words two rounds ahead (queue lengths, class histogram, region B's fill)
     {
         const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
         if (gid < RT_WF_CTL_WORDS) W.ctl[((round + 2) % 3) * RT_WF_CTL_WORDS + gid] = 0u;
+        if (gid < RT_WF_SHARDS) L.count[((round + 2) % 3) * RT_WF_SHARDS + gid] = 0u;
     }
-    // for the launch plan: this round's rays and its longest queue slice (one workgroup adds up the RT_WF_QSHARDS queue lengths)
-    if (blockIdx.x == gridDim.x - 1 && round < RT_WF_ROUND_LOG) {
-        __shared__ uint32_t sumWave[4], maxWave[4];
-        static_assert(RT_WF_QSHARDS == 512, "two queue lengths per thread");
-        const uint32_t c0 = ctlIn[RT_WF_CTL_COUNTS + threadIdx.x], c1 = ctlIn[RT_WF_CTL_COUNTS + 256 + threadIdx.x];
-        uint32_t n = c0 + c1, m = max(c0, c1);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { n += __shfl_xor(n, off, 64); m = max(m, (uint32_t)__shfl_xor((int)m, off, 64)); }
-        if (lane == 0) { sumWave[wave] = n; maxWave[wave] = m; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t *log = reinterpret_cast<uint32_t *>(W.roundLog + round);
-            log[0] = sumWave[0] + sumWave[1] + sumWave[2] + sumWave[3];
-            log[1] = max(max(maxWave[0], maxWave[1]), max(maxWave[2], maxWave[3]));
-        }
-    }
-    const bool multiLight = S.lightCount > 1u;
-    const float *planes = &sh.planes[0][0];
-
-    // main entries only (slices [0, slicesIn)): one per waiting path; look-ahead answers are picked up by index.
-    // The grid is a whole number of waves per slice (rtw_launch_logic), so a wave stays in ONE slice and needs its length only:
-    // slice = wave id % slicesIn, chunks of 64 entries dealt to the slice's waves in turn.
-    // (wave-uniform values are told to be so: they live in scalar registers, not in one of the few vector registers left)
+    if (blockIdx.x == gridDim.x - 1 && round < RT_WF_ROUND_LOG) log_round_rays(W, ctlIn, round, lane, wave);
     const uint32_t shard = __builtin_amdgcn_readfirstlane(waveId % slicesIn);
     const uint32_t total = __builtin_amdgcn_readfirstlane(ctlIn[RT_WF_CTL_COUNTS + shard]);
-    const uint32_t sliceCapIn = W.capacity / slicesIn, sliceCapOut = W.capacity / next.slices;
-    const uint32_t outShard = shard % next.slices; // (slices never grow from one round to the next: a slice holds at most the paths of its shards)
+    const uint32_t sliceCapIn = W.capacity / slicesIn;
+    uint32_t *listCount = L.count + (round % 3) * RT_WF_SHARDS + shard;
+    const float4 lc = S.lightCount != 0u ? make_float4(S.lightCol[0], S.lightCol[1], S.lightCol[2], S.lightHalfAtt[0]) : make_float4(0.f, 0.f, 0.f, 0.f);
     for (uint32_t localChunk = __builtin_amdgcn_readfirstlane(waveId / slicesIn); localChunk * 64 < total; localChunk += waves / slicesIn) {
         const uint32_t local = localChunk * 64 + lane;
         const uint32_t q = shard * sliceCapIn + local;
-        const bool live = local < total;
-#ifdef RT_DIAG_LOGIC
-        unsigned long long dg[12];
-        dg[0] = diag_stamp();
-        for (int i = 1; i < 12; ++i) dg[i] = 0;
-#endif
-        bool emit = false, emitLa = false;
-        V3 ro = mk(0, 0, 0), rd = mk(0, 0, 0), lo3 = mk(0, 0, 0), ld3v = mk(0, 0, 0);
-        float rtmin = 0.f, rtmax = 0.f, latmin = 0.f;
-        uint32_t rexcl = RT_NONE, laexcl = RT_NONE, a = 0;
-
-        if (LEAN && live) {
-            // ---- the opaque-diffuse path class (rt_api.cpp, path_class_of): every material's reflection, transparency and luminance are
-            // absent or one black texel, the height map is absent or one texel, and there is at most one light.  Then a path is: the camera
-            // ray's hit, shaded, spawning at most one diffuse bounce (bounces = 0, fromCamera = 0), light 0's shadow ray; the bounce's hit,
-            // shaded with no spawn, light 0's shadow ray.  At most one ring entry after the camera's, no camera-type ray after the primary,
-            // no second light.  Every operation the general machine performs on that path is performed here, in the same order; only
-            // branches that cannot be taken are left out (each says why).  Entry states: round 0's camera hit, a shadow answer, a ray answer.
-            // A hit whose shadow ray is dead (W.deadShadow) goes on at once: the bounce becomes the main ray of round 1, or the path ends.
-            const V3 zero = mk(0.f, 0.f, 0.f); // what the absent / black reflection, transparency and luminance channels read as
-            uint32_t res_tri = RT_NONE;
-            float res_t = 0.f, res_l1 = 0.f, res_l2 = 0.f;
-            unsigned long long key = ~0ull, laKeyEarly = ~0ull;
-            if (FIRST) {
-                a = q;
-                const uint4 r = W.res[q];
-                res_tri = r.x; res_t = __uint_as_float(r.y); res_l1 = __uint_as_float(r.z); res_l2 = __uint_as_float(r.w);
-            } else {
-                const uint2 who = W.pathOf[in][q];
-                a = who.x;
-                key = W.hitKey[in][q];
-                if (who.y != 0xffffffffu) laKeyEarly = W.hitKey[in][who.y];
-            }
-            float4 *ringA = W.ring + (size_t)a * (RT_RING * 3);
-            uint64_t rng = W.rng[a];
-            const uint4 meta = FIRST ? make_uint4(0u, 0u, 0u | (1u << 4) | ((uint32_t)WS_RAY << 8), res_tri) : W.meta[a];
-            V3 out = mk(0.f, 0.f, 0.f);
-            float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0, c2 = c0;
-            TriRow row;
-            row.tri = RT_NONE;
-            if (FIRST) {
-                c0 = pack4(ld3(S.eye), 0.f); c1 = ringA[1]; c2 = make_float4(1.f, 1.f, 1.f, __uint_as_float((12u << 1) | 1u));
-                load_tri_row(S, res_tri, row);
-            } else out = xyz(W.outc[a]);
-            uint32_t hit_tri = meta.w;
-            int head = (int)(meta.z & 15u), tail = (int)((meta.z >> 4) & 15u);
-            const uint32_t stage = (meta.z >> 8) & 1u;
-            uint32_t laState = (meta.z >> 10) & 3u;
-            int laIndex = (int)((meta.z >> 12) & 15u);
-            bool laFetched = false;
+        bool list = false, odd = false;
+        uint32_t a = 0;
+        unsigned long long listKey = ~0ull;
+        if (local < total) {
+            const uint2 who = W.pathOf[in][q];
+            a = who.x;
+            const unsigned long long key = W.hitKey[in][q];
             unsigned long long laKey = ~0ull;
-            if (laState == 1u) { laKey = laKeyEarly; laState = 2u; laFetched = true; }
-            else if (laState == 2u) laKey = W.laKey[a];
-
-            V3 cur_o = mk(0, 0, 0), cur_d = mk(0, 0, 0), cur_w = mk(0, 0, 0);
-            float cur_tmin = 0.f;
-            uint32_t cur_excl = RT_NONE;
-            int cur_bounces = 0;
-            V3 n = mk(0, 0, 0), where = mk(0, 0, 0), P = mk(0, 0, 0), face = mk(0, 0, 0), toL = mk(0, 0, 0);
-            float ndl = 0.f, lmin = 0.f, lmax = 0.f;
-            bool front = false, finished = false, rngDirty = false, outDirty = false, shade = false;
-            uint32_t emitStage = WS_RAY;
-            int firstSpawnSlot = -1;
-            float4 firstSpawn0 = make_float4(0.f, 0.f, 0.f, 0.f), firstSpawn1 = firstSpawn0;
-
-            auto take_ray = [&](float4 e0, float4 e1, float4 e2) {
-                cur_o = xyz(e0); cur_tmin = e0.w; cur_d = xyz(e1); cur_excl = __float_as_uint(e1.w); cur_w = xyz(e2);
-                cur_bounces = (int)(__float_as_uint(e2.w) >> 1); // (fromCamera is set on the camera ray only: see-through rays are never spawned)
-            };
-            // PC_NEXT_RAY (:509): false when the ring is empty (the path is finished)
-            auto next_ray = [&]() -> bool {
-                head = (head + 1) % RT_RING;
-                if (head == tail) { finished = true; return false; }
-                take_ray(ringA[head * 3 + 0], ringA[head * 3 + 1], ringA[head * 3 + 2]);
-                return true;
-            };
-            auto emit_ray = [&]() { emit = true; emitStage = WS_RAY; ro = cur_o; rd = cur_d; rtmin = cur_tmin; rtmax = RT_INF; rexcl = cur_excl; };
-            // PC_LIGHT_ACCUM (:628-636) for light 0
-            auto light_accum = [&](V3 atten) {
-                const float mag = __builtin_fabsf(ndl);
-                const float4 lc = light_col_half(0);
-                const float x = lmax / lc.w;
-                const float e = mag * half_falloff(x);
-                if ((0.f <= ndl) == front) {
-                    face.x += (1.f - face.x) * atten.x * e * lc.x;
-                    face.y += (1.f - face.y) * atten.y * e * lc.y;
-                    face.z += (1.f - face.z) * atten.z * e * lc.z;
-                }
-            };
-            // PC_SHADE_END (:647-651)
-            auto shade_end = [&]() {
-                out.x += P.x * face.x;
-                out.y += P.y * face.y;
-                out.z += P.z * face.z;
-                outDirty = true;
-            };
-
-            bool advance = false; // the hit in hand is done: on to the next ring entry
-            if (FIRST) {
-                take_ray(c0, c1, c2);
-                shade = res_tri != RT_NONE;
-                advance = !shade;
-            } else if (stage == WS_SHADOW) { // PC_SHADOW_RESULT (:612-626) of light 0
+            if (who.y != 0xffffffffu) laKey = W.hitKey[in][who.y];
+            const uint4 meta = W.meta[a];
+            V3 out = xyz(W.outc[a]);
+            int head = (int)(meta.z & 15u);
+            const int tail = (int)((meta.z >> 4) & 15u);
+            const uint32_t stage = (meta.z >> 8) & 1u, laState = (meta.z >> 10) & 3u;
+            const int laIndex = (int)((meta.z >> 12) & 15u);
+            if (laState == 2u) laKey = W.laKey[a]; // (an answer kept from an earlier round)
+            bool finished = false;
+            if (stage == WS_SHADOW) { // PC_SHADOW_RESULT (:612-626) of light 0
                 const float4 sp = W.shP[a], sf = W.shFace[a];
-                P = xyz(sp); ndl = sp.w; face = xyz(sf); front = (sf.w != 0.f);
-                const float4 *e = reinterpret_cast<const float4 *>(W.ent[in]) + 4 * (size_t)q;
-                const float4 e1 = e[1], e2 = e[2], e3 = e[3];
-                where = xyz(e2); lmin = e1.w; toL = xyz(e3); lmax = e2.w;
-                res_tri = resolve_hit(S, key, where, toL, lmin, lmax, hit_tri, res_t, res_l1, res_l2);
-                V3 atten = mk(1.f, 1.f, 1.f);
-                // an occluder's transparency is absent or black in this class: atten becomes 0, so the shadow ray is never sent on (:621-625)
-                if (res_tri != RT_NONE) { atten.x *= zero.x; atten.y *= zero.y; atten.z *= zero.z; }
-                light_accum(atten);
-                shade_end(); // (no light after light 0)
-                advance = true;
-            } else { // a ray's answer: the ray is the ring entry at head
-                take_ray(ringA[head * 3 + 0], ringA[head * 3 + 1], ringA[head * 3 + 2]);
-                res_tri = resolve_hit(S, key, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
-                shade = res_tri != RT_NONE;
-                advance = !shade;
-            }
-            if (advance && next_ray()) {
-                if (laState == 2u && laIndex == head) { // traced ahead of time: the answer is already here
-                    res_tri = resolve_hit(S, laKey, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
-                    laState = 0u;
-                    shade = res_tri != RT_NONE;
-                    if (!shade && next_ray()) emit_ray(); // (the ring holds no further entry: this finishes the path)
-                } else emit_ray();
-            }
-            if (shade) { // SHADE_BEGIN (:532-561), the hit's one spawn, light 0
-                hit_tri = res_tri;
-                const float *shadeRow = FIRST ? row.v : S.triShade + 24 * (size_t)res_tri; // (round 0 shades the camera hit only)
-                const int m = __float_as_int(shadeRow[21]);
-                const float *uv = shadeRow + 15;
-                where = along(cur_o, res_t, cur_d);
-                MatRec mat;
-                mat.desc[0] = mat.desc[1] = mat.desc[2] = mat.desc[3] = mat.desc[4] = 0u; mat.m = m;
-                if (0 <= m) mat = load_mat(S, m);
-                n = shading_normal<false, true>(S, sh, where, cur_o, cur_d, hit_tri, res_l1, res_l2, shadeRow, m, cn, &mat, FIRST ? &row.a : nullptr);
-                V3 tex = mk(0, 0, 0);
-                const V3 transp = zero, refl = zero, lum = zero;
-                if (0 <= m && mat.desc[CH_COLOR]) {
-                    uint32_t raw;
-                    tex = texel_rec<false>(S, sh, mat, CH_COLOR, uv, res_l1, res_l2, raw, cn);
-                }
-                out.x += (1.f - out.x) * lum.x * cur_w.x;
-                out.y += (1.f - out.y) * lum.y * cur_w.y;
-                out.z += (1.f - out.z) * lum.z * cur_w.z;
-                outDirty = true;
-                front = (dot3(n, cur_d) <= 0.f);
-                P.x = (1.f - out.x) * cur_w.x * (1.f - transp.x) * tex.x;
-                P.y = (1.f - out.y) * cur_w.y * (1.f - transp.y) * tex.y;
-                P.z = (1.f - out.z) * cur_w.z * (1.f - transp.z) * tex.z;
-                face = mk(0.1f, 0.1f, 0.1f);
-                // light 0's GetSpherePoint comes before the bounce's draws (:573,:595 then :671)
-                const int type = S.lightCount != 0u ? light_type(0) : 0;
-                SphereRaw raw0;
-                raw0.p = mk(0, 0, 0); raw0.len = 1.f; raw0.sq = 0.f;
-                if (S.lightCount != 0u && type >= 1 && type <= 9) raw0 = sphere_raw(rng);
-                rngDirty = true;
-                if (cur_bounces > 0) {
-                    const int frontI = front ? 1 : 0;
-                    const float total_rt = RT_MAX2(RT_MAX2(refl.x + transp.x, refl.y + transp.y), refl.z + transp.z);
-                    const float dif = (total_rt < 1.f) ? 1.f - total_rt : 0.f;
-                    const V3 w = mk(cur_w.x * tex.x * dif, cur_w.y * tex.y * dif, cur_w.z * tex.z * dif);
-                    if (3.f / 256.f <= w.x + w.y + w.z) { // diffuse bounce (:664-683)
-                        V3 nd = sphere_scaled(sphere_raw(rng), 1.f);
-                        if (frontI != ((0 <= dot3(nd, n)) ? 1 : 0)) { nd.x = -nd.x; nd.y = -nd.y; nd.z = -nd.z; }
-                        const float4 s0 = pack4(where, 0.f), s1 = pack4(nd, __uint_as_float(hit_tri));
-                        ringA[tail * 3 + 0] = s0; ringA[tail * 3 + 1] = s1; ringA[tail * 3 + 2] = pack4(w, __uint_as_float(0u));
-                        if (FIRST) { firstSpawnSlot = tail; firstSpawn0 = s0; firstSpawn1 = s1; }
-                        tail = (tail + 1) % RT_RING;
-                    }
-                    // mirror (:686-705) and see-through (:707-722): their weights are cur_w * tex * 0, i.e. +-0 or NaN, and 3/256 <= a sum of
-                    // those is false -- never spawned
-                }
-                // PC_LIGHT_SETUP (:563-607) of light 0 (the draws above); no light 1
-                if (S.lightCount != 0u) {
-                    toL = mk(0.f, 0.f, 0.f);
-                    lmin = 0.f; lmax = 0.f;
-                    if (type >= 1 && type <= 9) {
-                        if (type >= 3 && type <= 6) {
-                            const float4 ld = light_dir_spread(0);
-                            toL = sphere_scaled(raw0, ld.w);
-                            toL.x -= ld.x; toL.y -= ld.y; toL.z -= ld.z;
-                            const float inv = 1.f / sqrt_rn(dot3(toL, toL));
-                            toL.x *= inv; toL.y *= inv; toL.z *= inv;
-                            lmax = RT_INF;
-                        } else {
-                            const float4 lp = light_pos_radius(0);
-                            const V3 rp = sphere_scaled(raw0, lp.w);
-                            toL.x = rp.x + lp.x - where.x;
-                            toL.y = rp.y + lp.y - where.y;
-                            toL.z = rp.z + lp.z - where.z;
-                            lmax = sqrt_rn(dot3(toL, toL));
-                            const float inv = 1.f / lmax;
-                            toL.x *= inv; toL.y *= inv; toL.z *= inv;
-                        }
-                    }
-                    ndl = dot3(n, toL);
-                    // a dead shadow ray (light on the side whose face entry :647 does not read) is not traced: light_accum is a no-op for it
-                    const bool dead = W.deadShadow && ((0.f <= ndl) != front);
-                    if (lmin < lmax && !dead) { emit = true; emitStage = WS_SHADOW; ro = where; rd = toL; rtmin = lmin; rtmax = lmax; rexcl = hit_tri; }
-                    else light_accum(mk(1.f, 1.f, 1.f));
-                }
-                if (!emit) {
-                    shade_end();
-                    // (a look-ahead answer is only ever outstanding while a shadow ray is: it was taken above)
-                    if (FIRST && firstSpawnSlot >= 0) {
-                        // the camera hit's bounce is the next ring entry and becomes the main ray: from the registers it was spawned from
-                        // (PC_NEXT_RAY + take_ray + emit_ray without reading back the ring slot just stored)
-                        head = firstSpawnSlot;
-                        emit = true; emitStage = WS_RAY; ro = xyz(firstSpawn0); rtmin = firstSpawn0.w; rd = xyz(firstSpawn1); rtmax = RT_INF;
-                        rexcl = __float_as_uint(firstSpawn1.w);
-                    } else if (next_ray()) emit_ray();
-                }
-            }
-
-            // Leaving with a request and no look-ahead outstanding: start the next ring entry's grid walk as well (every entry is a grid ray)
-            if (!finished && laState == 0u && W.lookAhead) {
-                const int nx = (head + 1) % RT_RING;
-                if (nx != tail) {
-                    float4 n0 = firstSpawn0, n1 = firstSpawn1;
-                    if (!FIRST || nx != firstSpawnSlot) { n0 = ringA[nx * 3 + 0]; n1 = ringA[nx * 3 + 1]; }
-                    emitLa = true; lo3 = xyz(n0); latmin = n0.w; ld3v = xyz(n1); laexcl = __float_as_uint(n1.w);
-                    laState = 1u; laIndex = nx;
-                }
-            }
-
+                const float lmax = reinterpret_cast<const float *>(W.ent[in] + 4 * (size_t)q)[11];
+                const V3 zero = mk(0.f, 0.f, 0.f);
+                V3 face = xyz(sf), atten = mk(1.f, 1.f, 1.f);
+                if (key != ~0ull) { atten.x *= zero.x; atten.y *= zero.y; atten.z *= zero.z; }
+                class_light_accum(face, sp.w, sf.w != 0.f, lmax, lc, atten);
+                class_shade_end(out, xyz(sp), face);
+                head = (head + 1) % RT_RING; // PC_NEXT_RAY (:509)
+                if (head == tail) finished = true;
+                else if (laState != 0u && laIndex == head) { // the bounce, traced ahead of time
+                    if (laKey != ~0ull) { list = true; listKey = laKey; W.outc[a] = pack4(out, 0.f); }
+                    else if ((head + 1) % RT_RING == tail) finished = true; // (a bounce spawns nothing: the ring is empty)
+                    else odd = true;
+                } else odd = true;
+            } else if (laState != 0u) odd = true;
+            else if (key != ~0ull) { list = true; listKey = key; } // the bounce as the main ray: `out` is as it was
+            else if ((head + 1) % RT_RING == tail) finished = true;
+            else odd = true;
             if (finished) {
-                const uint2 where2 = FIRST ? *reinterpret_cast<const uint2 *>(W.meta + a) : make_uint2(meta.x, meta.y); // {output slot, pixel}
-                if (S.directStore == 1u) store_single_sample(S, where2.y, out);
-                else W.sampleOut[where2.x] = pack4(out, 0.f);
-            } else {
-                asm volatile("" : "+v"(a));
-                if (rngDirty) W.rng[a] = rng;
-                if (outDirty) W.outc[a] = pack4(out, 0.f);
-                // (a shadow ray leaves with atten = 1, never stored; the next light index is always 0)
-                const uint32_t flags = (uint32_t)head | ((uint32_t)tail << 4) | (emitStage << 8) | (laState << 10) | ((uint32_t)laIndex << 12);
-                if (FIRST) reinterpret_cast<uint2 *>(W.meta + a)[1] = make_uint2(flags, hit_tri);
-                else W.meta[a] = make_uint4(meta.x, meta.y, flags, hit_tri);
-                if (laState == 2u && laFetched) W.laKey[a] = laKey;
-                if (emitStage == WS_SHADOW) {
-                    W.shP[a] = pack4(P, ndl);
-                    W.shFace[a] = pack4(face, front ? 1.f : 0.f);
-                }
-            }
-        } else if (live) {
-            // Round 0 issues its loads in as few dependent batches as the data allows -- a wave runs one chunk and has two
-            // neighbours on its SIMD, so the chunk lasts as long as its chain of memory round trips (measured: ~8 of them at
-            // 2-4 us each before the first shading instruction when every load sat next to its use).  Batch one: the primary hit,
-            // the generator and the camera ray; batch two: the hit triangle's shading row.  Later rounds, whose paths are in
-            // different stages, keep their loads next to the uses (batching them too measured 100 -> 120 us).  Both instantiations
-            // fit 3 waves per SIMD without a spilled register (166 / 164 VGPRs) only because nothing that is wanted at the far end
-            // of the state machine is carried across it: addresses, the sample scale, the output slot are made or read again
-            // where they are used (a spill reload in this kernel is a wait for everything in flight).
-            uint32_t res_tri = RT_NONE;
-            float res_t = 0.f, res_l1 = 0.f, res_l2 = 0.f;
-            unsigned long long key = ~0ull, laKeyEarly = ~0ull;
-            float4 qo = make_float4(0.f, 0.f, 0.f, 0.f), qd = qo;
-            if (FIRST) {
-                a = q; // (a path is born at its own round-0 queue index)
-                const uint4 r = W.res[q];
-                res_tri = r.x; res_t = __uint_as_float(r.y); res_l1 = __uint_as_float(r.z); res_l2 = __uint_as_float(r.w);
-            } else {
-                // {path, queue slot of the look-ahead ray it sent out with this one}: the second answer is asked for right here, one
-                // round trip earlier than through the path's own state (it is only USED if the path's flags say it is outstanding)
-                const uint2 who = W.pathOf[in][q];
-                a = who.x;
-                key = W.hitKey[in][q];
-                if (who.y != 0xffffffffu) laKeyEarly = W.hitKey[in][who.y];
-            }
-            float4 *ringA = W.ring + (size_t)a * (RT_RING * 3);
-            uint64_t rng = W.rng[a];
-            // (round 0 knows the path's flags and its hit triangle; the output slot and the pixel are wanted at the very end only and are
-            // read then, instead of occupying two registers across the state machine)
-            const uint4 meta = FIRST ? make_uint4(0u, 0u, 0u | (1u << 4) | ((uint32_t)WS_RAY << 8), res_tri) : W.meta[a];
-            V3 out = mk(0.f, 0.f, 0.f); // (round 0: nothing collected yet)
-            float4 c0 = qo, c1 = qo, c2 = qo;
-            unsigned long long laKey = ~0ull;
-            TriRow row;
-            row.tri = RT_NONE;
-            if (FIRST) {
-                // slot 0 = the camera ray, of which wf_primary_kernel stores the direction only (:490-508: origin = eye, weight 1, maxBounces 12, fromCamera)
-                c0 = pack4(ld3(S.eye), 0.f); c1 = ringA[1]; c2 = make_float4(1.f, 1.f, 1.f, __uint_as_float((12u << 1) | 1u));
-                load_tri_row(S, res_tri, row);
-            } else out = xyz(W.outc[a]);
-            uint32_t hit_tri = meta.w;
-            int head = (int)(meta.z & 15u), tail = (int)((meta.z >> 4) & 15u);
-            const uint32_t stage = (meta.z >> 8) & 1u;
-            bool attStored = ((meta.z >> 9) & 1u) != 0u;
-            uint32_t laState = (meta.z >> 10) & 3u; // 0 none, 1 requested last round (answer at hitKey[pathOf.y]), 2 answer kept in laKey
-            int laIndex = (int)((meta.z >> 12) & 15u);
-            uint32_t j = meta.z >> 16;
-            DG(1);
-            bool laFetched = false;
-            if (laState == 1u) { laKey = laKeyEarly; laState = 2u; laFetched = true; }
-            else if (laState == 2u) laKey = W.laKey[a];
-
-            // the ray in flight (ring slot `head`), loaded when its answer is here
-            V3 cur_o = mk(0, 0, 0), cur_d = mk(0, 0, 0), cur_w = mk(0, 0, 0);
-            float cur_tmin = 0.f;
-            uint32_t cur_excl = RT_NONE;
-            int cur_bounces = 0, cur_fromCamera = 0;
-            // the hit being lit
-            V3 n = mk(0, 0, 0), where = mk(0, 0, 0), P = mk(0, 0, 0), face = mk(0, 0, 0), atten = mk(1.f, 1.f, 1.f), toL = mk(0, 0, 0);
-            float ndl = 0.f, lmin = 0.f, lmax = 0.f;
-            bool front = false;
-            uint64_t rngL = 0;
-            SphereRaw raw0;
-            raw0.p = mk(0, 0, 0); raw0.len = 1.f; raw0.sq = 0.f;
-
-            enum { PC_RAY_RESULT, PC_SHADOW_RESULT, PC_LIGHT_SETUP, PC_LIGHT_ACCUM, PC_SHADE_END, PC_NEXT_RAY, PC_EXIT };
-            int pc = PC_RAY_RESULT;
-            if (!FIRST && stage == WS_SHADOW) {
-                const float4 sp = W.shP[a], sf = W.shFace[a];
-                P = xyz(sp); ndl = sp.w; face = xyz(sf); front = (sf.w != 0.f);
-                if (attStored) atten = xyz(W.shAtt[a]);
-                // the entry that was answered still holds the hit point and the direction to the light: {..} {.., tmin} {o, tmax} {d, ..}
-                {
-                    const float4 *e = reinterpret_cast<const float4 *>(W.ent[in]) + 4 * (size_t)q;
-                    const float4 e1 = e[1];
-                    qo = e[2]; qd = e[3];
-                    where = xyz(qo); lmin = e1.w; toL = xyz(qd); lmax = qo.w;
-                }
-                if (multiLight) { n = xyz(W.shN[a]); rngL = W.rngL[a]; }
-                res_tri = resolve_hit(S, key, where, toL, lmin, lmax, hit_tri, res_t, res_l1, res_l2);
-                pc = PC_SHADOW_RESULT;
-            } else {
-                if (!FIRST) { c0 = ringA[head * 3 + 0]; c1 = ringA[head * 3 + 1]; c2 = ringA[head * 3 + 2]; }
-                cur_o = xyz(c0); cur_tmin = c0.w; cur_d = xyz(c1); cur_excl = __float_as_uint(c1.w); cur_w = xyz(c2);
-                cur_bounces = (int)(__float_as_uint(c2.w) >> 1);
-                cur_fromCamera = (int)(__float_as_uint(c2.w) & 1u);
-                if (!FIRST) res_tri = resolve_hit(S, key, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
-            }
-            DG(2);
-            bool finished = false, shadedNow = false, rngDirty = false, outDirty = false;
-            uint32_t emitStage = WS_RAY;
-
-            // A spawned ray goes to the ring in HBM; the first one of this invocation also stays in registers, because it is the
-            // ray the look-ahead below will ask for when the ring was empty (reading it back cost a round trip behind the stores).
-            // Round 0 only: later rounds have no registers to spare.
-            int firstSpawnSlot = -1;
-            float4 firstSpawn0 = make_float4(0.f, 0.f, 0.f, 0.f), firstSpawn1 = firstSpawn0;
-            uint32_t firstSpawnFlags = 0u;
-            auto spawn = [&](float4 e0, float4 e1, float4 e2) {
-                ringA[tail * 3 + 0] = e0; ringA[tail * 3 + 1] = e1; ringA[tail * 3 + 2] = e2;
-                if (FIRST && firstSpawnSlot < 0) { firstSpawnSlot = tail; firstSpawn0 = e0; firstSpawn1 = e1; firstSpawnFlags = __float_as_uint(e2.w); }
-                tail = (tail + 1) % RT_RING;
-            };
-            // SHADE_BEGIN (:532-561) and the hit's spawns, on the triangle's shading row
-            auto shade_begin = [&](const float *shade, const float4 *firstVertex) {
-                hit_tri = res_tri;
-                const float hit_t = res_t, hit_l1 = res_l1, hit_l2 = res_l2;
-                const int m = __float_as_int(shade[21]);
-                if (m != 12345678) DG(3);
-                const float *uv = shade + 15;
-                where = along(cur_o, hit_t, cur_d);
-                // the material's whole record in one burst (rt_device.h, matRec): the channel look-ups below are then no chain
-                // of dependent loads, and one-texel channels need no further load at all
-                MatRec mat;
-                mat.desc[0] = mat.desc[1] = mat.desc[2] = mat.desc[3] = mat.desc[4] = 0u; mat.m = m;
-                if (0 <= m) mat = load_mat(S, m);
-                n = shading_normal<false>(S, sh, where, cur_o, cur_d, hit_tri, hit_l1, hit_l2, shade, m, cn, &mat, firstVertex);
-                if (n.x != 12345.f) DG(4);
-                V3 tex = mk(0, 0, 0), transp = mk(0, 0, 0), refl = mk(0, 0, 0), lum = mk(0, 0, 0);
-                if (0 <= m) {
-                    uint32_t raw;
-                    if (mat.desc[CH_COLOR]) tex = texel_rec<false>(S, sh, mat, CH_COLOR, uv, hit_l1, hit_l2, raw, cn);
-                    if (mat.desc[CH_TRANSPARENCY]) transp = texel_rec<false>(S, sh, mat, CH_TRANSPARENCY, uv, hit_l1, hit_l2, raw, cn);
-                    if (mat.desc[CH_REFLECTION]) refl = texel_rec<false>(S, sh, mat, CH_REFLECTION, uv, hit_l1, hit_l2, raw, cn);
-                    if (mat.desc[CH_LUMINANCE]) lum = texel_rec<false>(S, sh, mat, CH_LUMINANCE, uv, hit_l1, hit_l2, raw, cn);
-                }
-                // :642-644 now (the light loop does not touch `out`), then the light-independent factors of :649-651
-                out.x += (1.f - out.x) * lum.x * cur_w.x;
-                out.y += (1.f - out.y) * lum.y * cur_w.y;
-                out.z += (1.f - out.z) * lum.z * cur_w.z;
-                outDirty = true;
-                front = (dot3(n, cur_d) <= 0.f);
-                P.x = (1.f - out.x) * cur_w.x * (1.f - transp.x) * tex.x;
-                P.y = (1.f - out.y) * cur_w.y * (1.f - transp.y) * tex.y;
-                P.z = (1.f - out.z) * cur_w.z * (1.f - transp.z) * tex.z;
-                face = mk(0.1f, 0.1f, 0.1f); // :540
-                // The light loop (:563-637) draws one GetSpherePoint per light of a sampled type (:573,:595).  Make those
-                // draws now: keep light 0's, remember where light 1's start, and leave the generator behind them all.
-                rngL = rng;
-                for (uint32_t k = 0; k < S.lightCount; ++k) {
-                    const int type = light_type(k);
-                    if (type >= 1 && type <= 9) {
-                        const SphereRaw rr = sphere_raw(rng);
-                        if (k == 0) raw0 = rr;
-                    }
-                    if (k == 0) rngL = rng;
-                }
-                rngDirty = true;
-                // the hit's spawns (:656-722), ahead of its light loop: nothing below depends on the face lights
-                if (cur_bounces > 0) {
-                    const int frontI = front ? 1 : 0;
-                    const float total_rt = RT_MAX2(RT_MAX2(refl.x + transp.x, refl.y + transp.y), refl.z + transp.z);
-                    const float dif = (total_rt < 1.f) ? 1.f - total_rt : 0.f;
-                    bool open = true;
-                    V3 w = mk(cur_w.x * tex.x * dif, cur_w.y * tex.y * dif, cur_w.z * tex.z * dif);
-                    if (3.f / 256.f <= w.x + w.y + w.z) { // diffuse bounce (:664-683)
-                        V3 nd = sphere_scaled(sphere_raw(rng), 1.f);
-                        if (frontI != ((0 <= dot3(nd, n)) ? 1 : 0)) { nd.x = -nd.x; nd.y = -nd.y; nd.z = -nd.z; }
-                        spawn(pack4(where, 0.f), pack4(nd, __uint_as_float(hit_tri)), pack4(w, __uint_as_float(0u)));
-                        if ((tail + 1) % RT_RING == head) open = false;
-                    }
-                    if (open) { // mirror (:686-705)
-                        w = mk(cur_w.x * tex.x * refl.x, cur_w.y * tex.y * refl.y, cur_w.z * tex.z * refl.z);
-                        if (3.f / 256.f <= w.x + w.y + w.z) {
-                            const float two = -2.f * dot3(n, cur_d);
-                            const V3 md = mk(cur_d.x + two * n.x, cur_d.y + two * n.y, cur_d.z + two * n.z);
-                            spawn(pack4(where, 0.f), pack4(md, __uint_as_float(hit_tri)), pack4(w, __uint_as_float((uint32_t)(cur_bounces - 1) << 1)));
-                            if ((tail + 1) % RT_RING == head) open = false;
-                        }
-                    }
-                    if (open) { // see-through continuation (:707-722)
-                        w = mk(cur_w.x * tex.x * transp.x, cur_w.y * tex.y * transp.y, cur_w.z * tex.z * transp.z);
-                        if (3.f / 256.f <= w.x + w.y + w.z) {
-                            spawn(pack4(cur_o, hit_t), pack4(cur_d, __uint_as_float(hit_tri)),
-                                  pack4(w, __uint_as_float(((uint32_t)(cur_bounces - 1) << 1) | (uint32_t)cur_fromCamera)));
-                        }
-                    }
-                }
-                DG(5);
-                j = 0;
-                shadedNow = true;
-                pc = PC_LIGHT_SETUP;
-            };
-            if (FIRST) { // the camera ray's hit: its row was requested with the path's state
-                if (res_tri != RT_NONE) shade_begin(row.v, &row.a); else pc = PC_NEXT_RAY;
-            }
-            while (pc != PC_EXIT) {
-                if (pc == PC_RAY_RESULT) {
-                    if (res_tri == RT_NONE) { pc = PC_NEXT_RAY; continue; }
-                    shade_begin(S.triShade + 24 * (size_t)res_tri, nullptr); // (read where it is used: registers, see above)
-                } else if (pc == PC_LIGHT_SETUP) { // :563-607
-                    if (j >= S.lightCount) { pc = PC_SHADE_END; continue; }
-                    toL = mk(0.f, 0.f, 0.f); atten = mk(1.f, 1.f, 1.f); attStored = false;
-                    lmin = 0.f; lmax = 0.f;
-                    const int type = light_type(j);
-                    if (type >= 1 && type <= 9) {
-                        // light 0 is only ever set up in the invocation that shaded the hit, where its draws are at hand
-                        const SphereRaw rr = (j == 0u) ? raw0 : sphere_raw(rngL);
-                        if (type >= 3 && type <= 6) {
-                            const float4 ld = light_dir_spread(j);
-                            toL = sphere_scaled(rr, ld.w);
-                            toL.x -= ld.x; toL.y -= ld.y; toL.z -= ld.z;
-                            const float inv = 1.f / sqrt_rn(dot3(toL, toL));
-                            toL.x *= inv; toL.y *= inv; toL.z *= inv;
-                            lmax = RT_INF;
-                        } else {
-                            const float4 lp = light_pos_radius(j);
-                            const V3 rp = sphere_scaled(rr, lp.w);
-                            toL.x = rp.x + lp.x - where.x;
-                            toL.y = rp.y + lp.y - where.y;
-                            toL.z = rp.z + lp.z - where.z;
-                            lmax = sqrt_rn(dot3(toL, toL));
-                            const float inv = 1.f / lmax;
-                            toL.x *= inv; toL.y *= inv; toL.z *= inv;
-                        }
-                    }
-                    ndl = dot3(n, toL);
-                    // shadow ray (:608-611): leave the machine until the grid has answered -- unless it is dead: a light on the side whose face
-                    // entry :647 will not read (W.deadShadow).  Its answer, any walk through transparent occluders and the attenuation feed only
-                    // that entry, and no draw depends on them; PC_LIGHT_ACCUM is a no-op on `face` for it.
-                    const bool dead = W.deadShadow && ((0.f <= ndl) != front);
-                    if (lmin < lmax && !dead) {
-                        emit = true; emitStage = WS_SHADOW; ro = where; rd = toL; rtmin = lmin; rtmax = lmax; rexcl = hit_tri;
-                        pc = PC_EXIT;
-                    } else pc = PC_LIGHT_ACCUM;
-                } else if (pc == PC_SHADOW_RESULT) { // :612-626
-                    pc = PC_LIGHT_ACCUM;
-                    if (res_tri != RT_NONE) {
-                        const float *oshade = S.triShade + 24 * (size_t)res_tri;
-                        const int om = __float_as_int(oshade[21]);
-                        V3 tr = mk(0.f, 0.f, 0.f);
-                        if (0 <= om) {
-                            const MatRec omat = load_mat(S, om);
-                            uint32_t raw;
-                            if (omat.desc[CH_TRANSPARENCY]) tr = texel_rec<false>(S, sh, omat, CH_TRANSPARENCY, oshade + 15, res_l1, res_l2, raw, cn);
-                        }
-                        atten.x *= tr.x; atten.y *= tr.y; atten.z *= tr.z;
-                        attStored = true;
-                        if (0.f < atten.x && 0.f < atten.y && 0.f < atten.z) {
-                            lmin = res_t;
-                            emit = true; emitStage = WS_SHADOW; ro = where; rd = toL; rtmin = lmin; rtmax = lmax; rexcl = hit_tri;
-                            pc = PC_EXIT;
-                        }
-                    }
-                } else if (pc == PC_LIGHT_ACCUM) { // :628-636
-                    const float mag = __builtin_fabsf(ndl);
-                    const float4 lc = light_col_half(j);
-                    const float x = lmax / lc.w;
-                    const float e = mag * half_falloff(x);
-                    if ((0.f <= ndl) == front) { // face[1] collects the lights in front of the normal, face[0] the others (:632-635)
-                        face.x += (1.f - face.x) * atten.x * e * lc.x;
-                        face.y += (1.f - face.y) * atten.y * e * lc.y;
-                        face.z += (1.f - face.z) * atten.z * e * lc.z;
-                    }
-                    ++j;
-                    pc = PC_LIGHT_SETUP;
-                } else if (pc == PC_SHADE_END) { // :647-651
-                    out.x += P.x * face.x;
-                    out.y += P.y * face.y;
-                    out.z += P.z * face.z;
-                    outDirty = true;
-                    pc = PC_NEXT_RAY;
-                } else { // PC_NEXT_RAY (:509)
-                    head = (head + 1) % RT_RING;
-                    if (head == tail) { finished = true; pc = PC_EXIT; continue; }
-                    const float4 c0 = ringA[head * 3 + 0], c1 = ringA[head * 3 + 1], c2 = ringA[head * 3 + 2];
-                    cur_o = xyz(c0); cur_tmin = c0.w; cur_d = xyz(c1); cur_excl = __float_as_uint(c1.w); cur_w = xyz(c2);
-                    cur_bounces = (int)(__float_as_uint(c2.w) >> 1);
-                    cur_fromCamera = (int)(__float_as_uint(c2.w) & 1u);
-                    if (cur_fromCamera) {
-                        uint32_t localPixel = FIRST ? W.meta[a].y : meta.y; // (opaque: the list addresses are worked out here, not carried from the prologue)
-                        asm volatile("" : "+v"(localPixel));
-                        res_tri = camera_scan_compact(S, localPixel, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
-                        pc = PC_RAY_RESULT;
-                    } else if (laState == 2u && laIndex == head) { // traced ahead of time: the answer is already here
-                        res_tri = resolve_hit(S, laKey, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
-                        laState = 0u;
-                        pc = PC_RAY_RESULT;
-                    } else {
-                        emit = true; emitStage = WS_RAY; ro = cur_o; rd = cur_d; rtmin = cur_tmin; rtmax = RT_INF; rexcl = cur_excl;
-                        pc = PC_EXIT;
-                    }
-                }
-            }
-
-            DG(6);
-            // Leaving with a request and no look-ahead outstanding: start the next ring entry's grid walk as well.
-            if (!finished && laState == 0u && W.lookAhead) {
-                const int nx = (head + 1) % RT_RING;
-                if (nx != tail) {
-                    float4 n0 = firstSpawn0, n1 = firstSpawn1;
-                    uint32_t nflags = firstSpawnFlags;
-                    if (!FIRST || nx != firstSpawnSlot) { n0 = ringA[nx * 3 + 0]; n1 = ringA[nx * 3 + 1]; nflags = __float_as_uint(ringA[nx * 3 + 2].w); }
-                    if ((nflags & 1u) == 0u) { // a grid ray (camera-type rays are answered inline)
-                        emitLa = true; lo3 = xyz(n0); latmin = n0.w; ld3v = xyz(n1); laexcl = __float_as_uint(n1.w);
-                        laState = 1u; laIndex = nx;
-                    }
-                }
-            }
-
-            if (laexcl != 12345u) DG(7);
-            if (finished) {
-                const uint2 where2 = FIRST ? *reinterpret_cast<const uint2 *>(W.meta + a) : make_uint2(meta.x, meta.y); // {output slot, pixel}
-                if (S.directStore == 1u) store_single_sample(S, where2.y, out);
-                else W.sampleOut[where2.x] = pack4(out, 0.f);
-            } else {
-                // park the path in HBM until the grid has answered.  The index is made opaque here so that the store addresses are
-                // worked out again (two instructions each) instead of being the prologue's load addresses kept alive across the
-                // whole state machine: those were spilled, and every reload put an `s_waitcnt vmcnt(0)` -- i.e. "all stores so far
-                // acknowledged" -- between two stores (ten of them in a row: a third of a later round's time).
-                asm volatile("" : "+v"(a));
-                if (rngDirty) W.rng[a] = rng;
-                if (outDirty) W.outc[a] = pack4(out, 0.f);
-                const uint32_t flags = (uint32_t)head | ((uint32_t)tail << 4) | (emitStage << 8) | ((attStored ? 1u : 0u) << 9) | (laState << 10) |
-                                       ((uint32_t)laIndex << 12) | (j << 16);
-                if (FIRST) reinterpret_cast<uint2 *>(W.meta + a)[1] = make_uint2(flags, hit_tri); // (slot and pixel stay as wf_primary_kernel wrote them)
-                else W.meta[a] = make_uint4(meta.x, meta.y, flags, hit_tri);
-                if (laState == 2u && laFetched) W.laKey[a] = laKey;
-                if (emitStage == WS_SHADOW) {
-                    W.shP[a] = pack4(P, ndl);
-                    W.shFace[a] = pack4(face, front ? 1.f : 0.f);
-                    if (attStored) W.shAtt[a] = pack4(atten, 0.f);
-                    if (multiLight) {
-                        W.rngL[a] = rngL;
-                        if (shadedNow) W.shN[a] = pack4(n, 0.f);
-                    }
-                }
+                if (S.directStore == 1u) store_single_sample(S, meta.y, out);
+                else W.sampleOut[meta.x] = pack4(out, 0.f);
             }
         }
-        // Every lane of the wave arrives here: one atomic instruction for the wave's two queue appends.
-        uint32_t slot, slotLa;
-        wave_append2(&ctlOut[RT_WF_CTL_COUNTS + outShard], emit, &ctlOut[RT_WF_CTL_COUNTS + RT_WF_SHARDS + outShard], emitLa, slot, slotLa);
-        slot += outShard * sliceCapOut;
-        slotLa += W.capacity + outShard * sliceCapOut;
-        asm volatile("" : "+v"(a), "+v"(slot), "+v"(slotLa)); // (addresses made here, not carried across the state machine)
-        if (slot != 0xfffffff0u) DG(8);
-        // The rays of the next round go to their queue slots now.  An ORDERED round (most lanes have one): as complete trace entries --
-        // DDA start state, segments, walk-length class -- so that nothing stands between this kernel and the walk but the placing of
-        // the classes.  Any other round: the ray alone; wf_trace_kernel<false> plans and cuts it (stage "trace entries").
-        const uint32_t copy = waveId % RT_WF_SORT_COPIES;
-        if (!ORDERED) {
-#pragma unroll 1
-            for (int which = 0; which < 2; ++which) {
-                const bool has = which ? emitLa : emit;
-                if (!has) continue;
-                const V3 o = which ? lo3 : ro, d = which ? ld3v : rd;
-                const float tmin = which ? latmin : rtmin, tmax = which ? RT_INF : rtmax;
-                const uint32_t excluded = which ? laexcl : rexcl, mine = which ? slotLa : slot;
-                uint4 *e = W.ent[outq] + 4 * (size_t)mine;
-                if (!which) W.pathOf[outq][mine] = make_uint2(a, emitLa ? slotLa : 0xffffffffu); // (only main entries are ever looked up: wf_logic_kernel's prologue)
-                W.hitKey[outq][mine] = ~0ull; // no segment of this ray has a hit yet
-                reinterpret_cast<uint32_t *>(e)[3] = excluded;
-                reinterpret_cast<uint32_t *>(e)[7] = __float_as_uint(tmin);
-                e[2] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(tmax));
-                e[3] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), 0u);
-            }
-        } else {
-            // walk-length class of an entry that will make v cell visits if it hits nothing (scheduling only).  Two scales: segments of a
-            // finely cut round differ by a few visits, uncut rays by hundreds; class 0 = longest
-            auto visit_class = [](uint32_t v) -> uint32_t {
-                if ((int)v < 1) v = 1;
-                if (v > 767u) v = 767u;
-                return (v < 128u) ? 63u - (v >> 2) : 31u - (v - 128u) / 20u;
-            };
-            // Everything that can be known without touching memory comes first -- both rays' plans, their segments, every entry's class and
-            // its rank inside the wave -- so that the one returned atomic every wave needs (where its classes' ranks start) goes out BEFORE
-            // the entries' stores: a returned atomic waits for every store issued ahead of it, and behind 128 bytes of entry per lane the
-            // wave sat out its own stores' round trip to HBM.  Nothing is read back either: a further segment's class and rank wait in LDS
-            // for the lane that makes its entry.
-            EntryPlan planM, planL;
-            planM.visits = planL.visits = 1; planM.endCell = planL.endCell = 0xffffffffu; planM.te = planL.te = RT_INF;
-            planM.start.cell = planL.start.cell = 0; planM.start.dx = planM.start.dy = planM.start.dz = 0.f; planL.start.dx = planL.start.dy = planL.start.dz = 0.f;
-            uint32_t nsegM = 0, nsegL = 0;
-            // (a round that is cut needs the exact far cell: the cut positions follow from the visit count)
-            const uint8_t *lut = next.segLen >= 4096u ? cellLut : nullptr;
-#pragma unroll 1
-            for (int which = 0; which < 2; ++which) { // (one copy of the planning code: two made the kernel a sixth longer)
-                const bool has = which ? emitLa : emit;
-                if (__ballot(has) == 0ull) continue; // wave-uniform
-                const V3 o = which ? lo3 : ro, d = which ? ld3v : rd;
-                const float tmin = which ? latmin : rtmin, tmax = which ? RT_INF : rtmax;
-                // (a hit's look-ahead ray starts where its shadow ray starts: one plane search for the two -- when the start is the origin
-                // itself, tmin = 0, and lies inside the grid's box, so that BindInCube (:265-322) moves it for neither direction)
-                const bool sameStart = which && emit && lo3.x == ro.x && lo3.y == ro.y && lo3.z == ro.z && latmin == 0.f && rtmin == 0.f &&
-                                       planes[0] <= o.x && o.x <= planes[RT_GRID_DIV] && planes[RT_GRID_DIV + 1] <= o.y && o.y <= planes[2 * RT_GRID_DIV + 1] &&
-                                       planes[2 * (RT_GRID_DIV + 1)] <= o.z && o.z <= planes[3 * RT_GRID_DIV + 2];
-                if (has) {
-                    const EntryPlan plan = plan_ray(planes, o, d, tmin, tmax, sameStart, planM.start.cell, lut, lutScale);
-                    const uint32_t n = segments_of(plan, d, tmax, next.segLen);
-                    if (which) { planL = plan; nsegL = n; } else { planM = plan; nsegM = n; }
-                }
-            }
-            // items = further segments of this wave's rays: those of the main rays first (lane L's start at beforeM), then those of the
-            // look-ahead rays (at itemsM + beforeL)
-            const uint32_t extraM = nsegM > 1u ? nsegM - 1u : 0u, extraL = nsegL > 1u ? nsegL - 1u : 0u;
-            uint32_t itemsM = 0, itemsL = 0, beforeM = 0, beforeL = 0;
-            const bool cutting = __ballot((extraM | extraL) != 0u) != 0ull; // wave-uniform
-            if (cutting) {
-                uint32_t inclM = extraM, inclL = extraL;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t upM = __shfl_up(inclM, off, 64), upL = __shfl_up(inclL, off, 64);
-                    if ((int)lane >= off) { inclM += upM; inclL += upL; }
-                }
-                itemsM = (uint32_t)__shfl((int)inclM, 63, 64); itemsL = (uint32_t)__shfl((int)inclL, 63, 64);
-                beforeM = inclM - extraM; beforeL = inclL - extraL;
-            }
-            const uint32_t items = itemsM + itemsL;
-            // room in region B for the wave's further segments (a wave that cuts anything: one atomic).  A reservation is never undone (an
-            // add followed by a subtract is not atomic across waves); a count past extraCap just means "region B is full", every reader
-            // clamps it; the one wave whose range straddles the end owns [at, extraCap) and marks those slots empty.  No room, no
-            // cutting: the wave's rays stay whole -- decided BEFORE the classes are counted, so that every counted entry is placed.
-            uint32_t extraBase = 0;
-            bool room = true;
-            if (items != 0u) { // wave-uniform
-                if (lane == 0u) extraBase = atomicAdd(&ctlOut[RT_WF_CTL_EXTRA], items);
-                extraBase = (uint32_t)__shfl((int)extraBase, 0, 64);
-                if ((uint64_t)extraBase + items > (uint64_t)W.extraCap) {
-                    room = false;
-                    for (uint32_t i = extraBase + lane; i < W.extraCap; i += 64) {
-                        W.ent[outq][4 * (size_t)(2u * W.capacity + i)].x = 0xffffffffu;
-                        W.sortRank[2u * W.capacity + i] = 0xffffffffu;
-                    }
-                    if (nsegM > 1u) nsegM = 1u;
-                    if (nsegL > 1u) nsegL = 1u;
-                }
-            }
-            const uint32_t extraAt = 2u * W.capacity + extraBase; // region B of the entry array starts after the 2*capacity queue slots
-            const float taM = fminf(planM.start.dx, fminf(planM.start.dy, planM.start.dz)), taL = fminf(planL.start.dx, fminf(planL.start.dy, planL.start.dz));
-            const uint32_t perM = nsegM ? (planM.visits + nsegM - 1) / nsegM : 1u, perL = nsegL ? (planL.visits + nsegL - 1) / nsegL : 1u;
-            // classes and ranks inside the wave: segment 0 of both rays, then every further segment (whose class follows from the cut
-            // positions alone: the cuts that exist are a prefix of 1 .. nseg - 1, cut_at)
-            uint32_t binM = 0, rankM = 0, binL = 0, rankL = 0;
-            {
-                float tau;
-                if (emit) { binM = visit_class(nsegM > 1u && cut_at(taM, planM.te, 1u, nsegM, tau) ? perM : planM.visits); rankM = atomicAdd(&waveHist[wave][binM], 1u); }
-                if (emitLa) { binL = visit_class(nsegL > 1u && cut_at(taL, planL.te, 1u, nsegL, tau) ? perL : planL.visits); rankL = atomicAdd(&waveHist[wave][binL], 1u); }
-                if (cutting && room) {
-#pragma unroll 1
-                    for (int which = 0; which < 2; ++which) {
-                        const uint32_t n = which ? nsegL : nsegM, per = which ? perL : perM, visits = which ? planL.visits : planM.visits;
-                        const float ta = which ? taL : taM, te = which ? planL.te : planM.te;
-                        const uint32_t at = which ? itemsM + beforeL : beforeM;
-                        for (uint32_t k = 1; k < n; ++k) {
-                            uint32_t word = 0xffffffffu; // (cut k does not exist: no entry)
-                            if (cut_at(ta, te, k, n, tau)) {
-                                const bool cutNext = k + 1u < n && cut_at(ta, te, k + 1u, n, tau);
-                                const uint32_t bin = visit_class(cutNext ? per : visits - per * k);
-                                word = atomicAdd(&waveHist[wave][bin], 1u) | (bin << 24);
-                            }
-                            itemWord[wave][at + k - 1] = word;
-                            itemOwner[wave][at + k - 1] = (uint8_t)lane;
-                        }
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            // lane b fetches where class b's ranks of this wave start: the one returned atomic that stands between the plans and the stores
-            {
-                uint32_t l2 = lane;
-                asm volatile("" : "+v"(l2)); // (the address is made here: hoisted out of the chunk loop it was spilled)
-                const uint32_t n = waveHist[wave][l2];
-                waveBase[wave][l2] = n ? atomicAdd(&ctlOut[RT_WF_CTL_HIST + copy * RT_WF_SORT_BINS + l2], n) : 0u;
-                waveHist[wave][l2] = 0u; // (for this wave's next chunk)
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            // segment 0 of both rays, at their queue indices; where a cut ray's segment 0 ends is filled in by the lane that makes cut 1
-#pragma unroll 1
-            for (int which = 0; which < 2; ++which) {
-                const bool has = which ? emitLa : emit;
-                if (!has) continue;
-                const V3 o = which ? lo3 : ro, d = which ? ld3v : rd;
-                const float tmin = which ? latmin : rtmin, tmax = which ? RT_INF : rtmax;
-                const uint32_t excluded = which ? laexcl : rexcl, mine = which ? slotLa : slot;
-                const uint32_t bin = which ? binL : binM, rank = which ? rankL : rankM, cell = which ? planL.start.cell : planM.start.cell;
-                const uint32_t endCell = which ? planL.endCell : planM.endCell, nseg = which ? nsegL : nsegM;
-                uint4 *e = W.ent[outq] + 4 * (size_t)mine;
-                if (!which) W.pathOf[outq][mine] = make_uint2(a, emitLa ? slotLa : 0xffffffffu); // (only main entries are ever looked up: wf_logic_kernel's prologue)
-                W.hitKey[outq][mine] = ~0ull; // no segment of this ray has a hit yet
-                if (nseg > 1u) { // (.z comes from another lane: not written here, so that the two stores cannot meet)
-                    *reinterpret_cast<uint2 *>(e) = make_uint2(mine, cell);
-                    reinterpret_cast<uint32_t *>(e)[3] = excluded;
-                } else e[0] = make_uint4(mine, cell, endCell, excluded);
-                e[1] = make_uint4(__float_as_uint(which ? planL.start.dx : planM.start.dx), __float_as_uint(which ? planL.start.dy : planM.start.dy),
-                                  __float_as_uint(which ? planL.start.dz : planM.start.dz), __float_as_uint(tmin));
-                e[2] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(tmax));
-                e[3] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), 0u); // (segment 0)
-                W.sortRank[mine] = waveBase[wave][bin] + rank;
-                W.sortTag[mine] = (uint16_t)(bin | (copy << 6));
-            }
-            // The further segments, one per lane whoever's ray it is (a lane making its ray's up to 11 cuts one after the other while the
-            // wave's other lanes wait was 40 % of a chunk's time).  Segment k goes from the walk's state at tau_k to the start cell of
-            // segment k + 1; every lane can tell from k alone whether cut k and cut k + 1 exist, and writes where the segment BEFORE its
-            // own ends.
-            if (room) {
-#pragma unroll 1
-                for (int which = 0; which < 2; ++which) {
-                    // (what the lanes hand out is picked by `which`, the same for the whole wave, BEFORE the shuffles: a shuffle reads nothing
-                    // from a lane that sits the instruction out, so none of them may stand in a branch of its own)
-                    const V3 so = which ? lo3 : ro, sd = which ? ld3v : rd;
-                    const float stmin = which ? latmin : rtmin, stmax = which ? RT_INF : rtmax, sta = which ? taL : taM, ste = which ? planL.te : planM.te;
-                    const uint32_t sexcl = which ? laexcl : rexcl, smine = which ? slotLa : slot, scell = which ? planL.start.cell : planM.start.cell;
-                    const uint32_t snseg = which ? nsegL : nsegM, send = which ? planL.endCell : planM.endCell, sbefore = which ? beforeL : beforeM;
-                    const uint32_t count = which ? itemsL : itemsM, base = which ? itemsM : 0u;
-                    for (uint32_t i0 = 0; i0 < count; i0 += 64) {
-                        const uint32_t i = i0 + lane;
-                        const bool liveItem = i < count;
-                        const uint32_t owner = liveItem ? itemOwner[wave][base + i] : 0u;
-                        const uint32_t word = liveItem ? itemWord[wave][base + i] : 0xffffffffu;
-                        const uint32_t k = i - (uint32_t)__shfl((int)sbefore, owner, 64) + 1u; // this lane makes cut k of `owner`'s ray
-                        const V3 po = mk(__shfl(so.x, owner, 64), __shfl(so.y, owner, 64), __shfl(so.z, owner, 64));
-                        const V3 pd = mk(__shfl(sd.x, owner, 64), __shfl(sd.y, owner, 64), __shfl(sd.z, owner, 64));
-                        const float ptmin = __shfl(stmin, owner, 64), ptmax = __shfl(stmax, owner, 64), pta = __shfl(sta, owner, 64), pte = __shfl(ste, owner, 64);
-                        const uint32_t pexcl = __shfl(sexcl, owner, 64), pmine = __shfl(smine, owner, 64), pcell = __shfl(scell, owner, 64);
-                        const uint32_t pnseg = __shfl(snseg, owner, 64), pend = __shfl(send, owner, 64);
-                        if (!liveItem) continue;
-                        const uint32_t at = extraAt + base + i; // entry of segment k
-                        uint32_t *prev = reinterpret_cast<uint32_t *>(W.ent[outq] + 4 * (size_t)(k == 1u ? pmine : at - 1u));
-                        uint32_t *self = reinterpret_cast<uint32_t *>(W.ent[outq] + 4 * (size_t)at);
-                        if (word == 0xffffffffu) { // rounding left no room for this cut: the segment before runs to the ray's end, this one does not exist
-                            prev[2] = pend;
-                            self[0] = 0xffffffffu;
-                            W.sortRank[at] = 0xffffffffu;
-                            continue;
-                        }
-                        float tau, tauNext;
-                        (void)cut_at(pta, pte, k, pnseg, tau);
-                        const bool cutNext = k + 1u < pnseg && cut_at(pta, pte, k + 1u, pnseg, tauNext);
-                        DdaState st;
-                        // (counting the crossings with T <= tau from the ray's start cell: the state does not depend on where counting begins)
-                        const uint32_t nx = axis_state_at(planes, pcell & 255u, po.x, pd.x, tau, st.dx, cellLut, lutScale[0]);
-                        const uint32_t ny = axis_state_at(planes + (RT_GRID_DIV + 1), (pcell >> 8) & 255u, po.y, pd.y, tau, st.dy, cellLut + 256, lutScale[1]);
-                        const uint32_t nz = axis_state_at(planes + 2 * (RT_GRID_DIV + 1), pcell >> 16, po.z, pd.z, tau, st.dz, cellLut + 512, lutScale[2]);
-                        st.cell = nx | (ny << 8) | (nz << 16);
-                        prev[2] = st.cell; // the segment before ends where this one starts
-                        *reinterpret_cast<uint2 *>(self) = make_uint2(pmine, st.cell);
-                        self[3] = pexcl;
-                        if (!cutNext) self[2] = pend; // the ray's last segment
-                        uint4 *se = reinterpret_cast<uint4 *>(self);
-                        se[1] = make_uint4(__float_as_uint(st.dx), __float_as_uint(st.dy), __float_as_uint(st.dz), __float_as_uint(ptmin));
-                        se[2] = make_uint4(__float_as_uint(po.x), __float_as_uint(po.y), __float_as_uint(po.z), __float_as_uint(ptmax));
-                        se[3] = make_uint4(__float_as_uint(pd.x), __float_as_uint(pd.y), __float_as_uint(pd.z), k << 24);
-                        const uint32_t bin = word >> 24;
-                        W.sortRank[at] = waveBase[wave][bin] + (word & 0xffffffu);
-                        W.sortTag[at] = (uint16_t)(bin | (copy << 6));
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier(); // (waveBase, itemOwner and itemWord are rewritten by this wave's next chunk)
-        }
-        if (copy != 0xfffffff0u) DG(9);
-        if (copy != 0xfffffff0u) DG(10);
-#ifdef RT_DIAG_LOGIC
-        if (round == RT_DIAG_LOGIC) {
-            dg[11] = diag_stamp();
-            // a stamp taken in a divergent branch belongs to the wave: take the latest any lane saw, and keep the sequence monotone
-            for (int i = 1; i < 12; ++i) {
-                unsigned long long v = dg[i];
-                for (int off = 32; off >= 1; off >>= 1) { const unsigned long long o2 = __shfl_xor((long long)v, off, 64); v = v > o2 ? v : o2; }
-                dg[i] = v > dg[i - 1] ? v : dg[i - 1];
-            }
-            if (lane == 0) { // machine | look-ahead pick | append atomics | entries | classes + ranks | rest | chunks | whole chunk
-                atomicAdd(&S.stats[0], dg[6] - dg[0]); atomicAdd(&S.stats[1], dg[7] - dg[6]); atomicAdd(&S.stats[2], dg[8] - dg[7]);
-                atomicAdd(&S.stats[3], dg[9] - dg[8]); atomicAdd(&S.stats[4], dg[10] - dg[9]); atomicAdd(&S.stats[5], dg[11] - dg[10]);
-                atomicAdd(&S.stats[6], 1ull); atomicAdd(&S.stats[7], dg[11] - dg[0]);
-            }
-        }
-#endif
+        if (__ballot(odd) != 0ull && lane == 0u) atomicOr(W.hostStatus + RT_WF_STATUS_ERROR, RT_WF_ERR_SPLIT);
+        if (!shadeFollows && __ballot(list) != 0ull && lane == 0u) atomicOr(W.hostStatus + RT_WF_STATUS_ERROR, RT_WF_ERR_GRID);
+        const uint32_t at = wave_append(listCount, list);
+        if (list) L.list[shard * sliceCapIn + at] = make_uint4(a, (uint32_t)listKey, (uint32_t)(listKey >> 32), 0u);
     }
+}
+
+template <bool ORDERED>
+__global__ __launch_bounds__(256, RT_WF_LOGIC_WAVES_LEAN) void wf_shade_kernel(const RtDevScene S, const RtWavefront W, const uint32_t round, const uint32_t slicesIn,
+                                                                              const RtRoundMode next, const RtShadeList L)
+{
+    constexpr bool FIRST = false, LEAN = true, SHADE = true;
+#include "rt_wf_logic_body.h"
 }
 
 // ---- stage 2b: an ordered round's entries, longest predicted walk first ------------------------------------------------------
@@ -2033,7 +1275,7 @@ __global__ __launch_bounds__(256) void wf_accum_kernel(const RtDevScene S, const
 // One workgroup.  The main queue slices of round `round` (what logic(round - 1) appended) hold one request per path that is not
 // finished; their sum goes to the mapped host word, so the host can issue a frame's rounds without looking at the queue in
 // between and check afterwards (rt_api.cpp).
-__global__ __launch_bounds__(256) void wf_status_kernel(const RtWavefront W, const uint32_t round)
+__global__ __launch_bounds__(256) void wf_status_kernel(const RtWavefront W, const uint32_t round, uint32_t *shadeCount)
 {
     __shared__ uint32_t part[4];
     uint32_t n = W.ctl[(round % 3) * RT_WF_CTL_WORDS + RT_WF_CTL_COUNTS + threadIdx.x]; // RT_WF_SHARDS == 256 main slices
@@ -2049,6 +1291,8 @@ __global__ __launch_bounds__(256) void wf_status_kernel(const RtWavefront W, con
     // nothing of the batch is in flight any more: leave all three sets of control words zeroed for the next one (the host skips its memset --
     // a launch of the runtime's fill kernel with ~6 us of idle time in front of it -- when the batch before ended here)
     for (uint32_t i = threadIdx.x; i < 3u * RT_WF_CTL_WORDS; i += 256u) W.ctl[i] = 0u;
+    if (shadeCount) // (the split rounds' list lengths, RtShadeList::count, likewise)
+        for (uint32_t i = threadIdx.x; i < 3u * RT_WF_SHARDS; i += 256u) shadeCount[i] = 0u;
 }
 
 // ---- ray queries (rtHipSceneIntersect*): caller-supplied rays against the resident grid -------------------------------------
@@ -2227,6 +1471,29 @@ extern "C" hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefron
     return hipGetLastError();
 }
 
+// A split logic round (opaque-diffuse class, look-ahead on, round >= 1): the answers of every main entry ...
+extern "C" hipError_t rtw_launch_answer(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtShadeList *list,
+                                        uint32_t shadeFollows, hipStream_t stream)
+{
+    if (blocks % (RT_WF_SHARDS / 4) != 0 || blocks * 256ull < RT_WF_CTL_WORDS) return hipErrorInvalidValue; // whole waves per queue slice; the housekeeping's threads
+    if (scene->pathClass != RT_PATH_CLASS_OPAQUE_DIFFUSE || !wf->lookAhead || round == 0u || !list->list || !list->count) return hipErrorInvalidValue;
+    if (slicesIn < 1u || slicesIn > RT_WF_SHARDS || (slicesIn & (slicesIn - 1u)) != 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wf_answer_kernel, dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *list, shadeFollows);
+    return hipGetLastError();
+}
+
+// ... then the listed paths' hits, shaded by dense waves (any whole number of waves per slice will do: they stride over the list)
+extern "C" hipError_t rtw_launch_shade(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next,
+                                       const RtShadeList *list, hipStream_t stream)
+{
+    if (blocks == 0u || blocks % (RT_WF_SHARDS / 4) != 0) return hipErrorInvalidValue;
+    if (!mode_ok(*next) || slicesIn < next->slices || slicesIn > RT_WF_SHARDS || (slicesIn & (slicesIn - 1u)) != 0u) return hipErrorInvalidValue;
+    if (scene->pathClass != RT_PATH_CLASS_OPAQUE_DIFFUSE || !wf->lookAhead || round == 0u || !list->list || !list->count) return hipErrorInvalidValue;
+    if (next->ordered) hipLaunchKernelGGL(wf_shade_kernel<true>, dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next, *list);
+    else hipLaunchKernelGGL(wf_shade_kernel<false>, dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next, *list);
+    return hipGetLastError();
+}
+
 // an ordered round: ranks -> positions (fixed grid, the kernel strides over the blocks that are in use)
 extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream)
 {
@@ -2244,10 +1511,10 @@ extern "C" hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefron
     return hipGetLastError();
 }
 
-extern "C" hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, hipStream_t stream)
+extern "C" hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, uint32_t *shadeCount, hipStream_t stream)
 {
     static_assert(RT_WF_SHARDS == 256, "wf_status_kernel sums one main queue slice per thread");
-    hipLaunchKernelGGL(wf_status_kernel, dim3(1), dim3(256), 0, stream, *wf, round);
+    hipLaunchKernelGGL(wf_status_kernel, dim3(1), dim3(256), 0, stream, *wf, round, shadeCount);
     return hipGetLastError();
 }
 

@@ -148,7 +148,7 @@ RESIDENT_SYMBOLS = [
     "rtHipDenoiseVariance", "rtHipSceneTemporalVariance",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
-    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestBuildLog",
+    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestShadeLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat", "rtHipTestSceneView", "rtHipTestSceneCameraList", "rtHipTestScenePointers", "rtHipTestSceneCameraLog", "rtHipTestSceneCameraTimes",
     "rtHipTestSceneGeometryLog", "rtHipTestSceneGeometryTimes",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm", "rtHipWritePfmRgb",
@@ -304,6 +304,7 @@ def lib() -> C.CDLL:
     L.rtHipScenePathClass.argtypes = [C.POINTER(SceneDesc)]
     L.rtHipTestPathClass.argtypes = [vp]
     L.rtHipTestRoundLog.argtypes = [vp, C.POINTER(u32), u32]
+    L.rtHipTestShadeLog.argtypes = [vp, C.POINTER(u32), u32]
     L.rtHipTestBuildLog.argtypes = [C.POINTER(u64), u32]
     L.rtHipTestShadeKat.argtypes = [vp, C.c_int, u32, vp, vp]
     L.rtHipTestSceneView.argtypes = [vp, C.c_int, u64, u64, vp]
@@ -321,7 +322,7 @@ _ENV_KEYS = {
     "RT_WF_APPEND_RAYS": "append_rays", "RT_WF_ORDERED_FIRST": "ordered_first", "RT_WF_SLICE_RAYS": "slice_rays", "RT_WF_SMALL_SLICES": "small_slices", "RT_WF_GROUP_RAYS": "group_rays",
     "RT_WF_BLOCKING": "blocking", "RT_WF_BATCH_PLAN": "batch_plan", "RT_WF_PLAN_ROUNDS": "plan_rounds", "RT_HIP_PIPELINE": "pipeline",
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
-    "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow",
+    "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow", "RT_WF_LOGIC_SPLIT": "logic_split", "RT_WF_PLAN_SHADE_SKIP": "plan_shade_skip",
     "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit", "RT_HIP_QUERY_RAYS": "query_rays",
 }
 # comma-separated lists: RT_WF_SEG=a,b,.. sets seg0, seg1, .. (at most 5 values), RT_WF_SEG_RAYS sets seg_rays0.. (at most 4)
@@ -1086,6 +1087,15 @@ class ResidentScene:
         if lib().rtHipTestRoundLog(self.handle, rays, n) < 0:
             raise RuntimeError("rtHipTestRoundLog failed")
         return [int(v) for v in rays]
+
+    def shade_log(self, n: int = 8):
+        """(split logic rounds the last frame issued, paths each round listed for its shade pass) -- rtHipTestShadeLog; call after a
+        synchronisation.  0 rounds: the frame ran one logic kernel per round."""
+        listed = (C.c_uint32 * n)()
+        rounds = lib().rtHipTestShadeLog(self.handle, listed, n)
+        if rounds < 0:
+            raise RuntimeError("rtHipTestShadeLog failed")
+        return rounds, [int(v) for v in listed]
 
     def shade_kat(self, op: int, inp: np.ndarray) -> np.ndarray:
         """rtHipTestShadeKat on this scene: `inp` holds one 40-byte (RT_SHADE_KAT_TEXEL) or 48-byte (RT_SHADE_KAT_NORMAL) row per item;
