@@ -1043,8 +1043,10 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
  * paths run on the general logic kernel; 1, the default: on the kernel of the scene's path class), "dead_shadow" (0: trace every
  * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), "logic_split" (1, the
  * default: the later logic rounds of an opaque-diffuse scene with look-ahead on stream the answers and shade the bounce hits densely; 0:
- * one logic kernel per round), and the test hooks
- * "plan_rounds", "plan_grid_tiny", "plan_shade_skip" (planned frames launch no shade pass), "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
+ * one logic kernel per round), "ray_clip" (1, the default: a grid ray without a far end stops where it leaves the convex bound of the
+ * grid's occupied cells; 0: at the grid's wall), and the test hooks
+ * "plan_rounds", "plan_grid_tiny", "plan_shade_skip" (planned frames launch no shade pass), "visit_log" (every frame waits after each round's
+ * trace launch and reads the round back for rtHipTestRoundVisits), "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
  * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
  * and most 2^32 - 1; above it they return -3), "query_rays" (rays per staging chunk of rtHipSceneIntersect, default 2^20), and
  * "ao_samples" (pixel samples per chunk of the ambient occlusion calls, default 2^20, at most 2^24), and "bake_texels" (texels per chunk
@@ -1073,6 +1075,21 @@ int rtHipTestPathClass(const rtHipScene *scene);
  * after the frame was synchronised; with several sample batches the figures are the last batch's.  Returns the frame's round count,
  * -1 for invalid arguments. */
 int rtHipTestRoundLog(const rtHipScene *scene, cl_uint *rays, cl_uint n);
+
+/* TEST-ONLY, for scenes built with the test hook "visit_log" on: what the trace rounds of the scene's last wavefront frame held, summed over
+ * its tile groups and sample batches.  With the hook on, every frame stops after each round's trace launch, and the host reads the round's
+ * queues back before the next logic launch consumes them: the entries as the planning kernels wrote them, the rays' answers, and which main
+ * entry went out with a look-ahead entry.  out[RT_ROUND_VISIT_FIELDS * r + f] for r < rounds (round 0 traces nothing and reads 0):
+ *   RT_ROUND_VISIT_ORDERED   1 when the round was an ordered one: its entries were planned by the kernel that spawned the rays, and the visit
+ *                            fields count them; a round that is not ordered is planned inside the trace kernel and its visit fields read 0
+ *   RT_ROUND_VISIT_ENTRIES   trace entries (a cut ray makes several), RT_ROUND_VISIT_ENDED those of them that carry an end cell
+ *   then, for the three kinds of ray -- a main entry sent out with a look-ahead entry (a hit's shadow ray), a main entry on its own, a
+ *   look-ahead entry (a bounce ray) -- RT_ROUND_VISIT_RAYS + 3 * kind: rays, rays that hit something, planned cell visits.
+ * An entry's planned visits are the cells its walk makes if it hits nothing: the Manhattan distance from its start cell to its end cell + 1;
+ * for an entry without an end cell the host takes the cell where the ray leaves the grid's box (the planner's own arithmetic, exact cell
+ * search).  Returns the frame's round count, -1 for invalid arguments or a scene built without the hook. */
+enum { RT_ROUND_VISIT_ORDERED = 0, RT_ROUND_VISIT_ENTRIES, RT_ROUND_VISIT_ENDED, RT_ROUND_VISIT_RAYS, RT_ROUND_VISIT_FIELDS = 12 };
+int rtHipTestRoundVisits(const rtHipScene *scene, uint64_t *out, cl_uint rounds);
 
 /* TEST-ONLY: the split logic rounds ("logic_split") of the scene's last wavefront frame.  listed[r] for r < n: the paths round r listed
  * for its shade pass, summed over the tile groups, as the last shade pass of that round logged it (a planned frame that skips the launch
@@ -1106,10 +1123,16 @@ int rtHipTestBuildLog(uint64_t *out, cl_uint n);
  *                            (3 * ((63<<16 | 63<<8 | 63) + 1) elements)
  *   RT_SCENE_VIEW_PAIR_REC   16 32-bit words (64 bytes): a (cell, triangle) pair record (pair count elements)
  *   RT_SCENE_VIEW_CELL_LUT   one byte: the cell estimate table [3][256]
+ *   RT_SCENE_VIEW_CLIP_PLANES 4 floats: a plane {n.xyz, off} of the grid's clip bound -- every corner of every occupied cell has n.x <= off (at
+ *                            most 8 elements, none for a scene whose occupied cells fill the grid's box; kept whatever "ray_clip" says),
+ *                            read from behind the split planes on the device, where the planning kernels read them
+ *   RT_SCENE_VIEW_CLIP_APPLIED cl_uint: how many of those planes the planning kernels apply, the word in front of them on the device (1
+ *                            element: the number kept, or 0 for a scene built with "ray_clip" 0)
  * With out == NULL it returns the array's element count (firstElement and count are ignored); otherwise 0, or -1 with a
  * rtHipLastError() text for a NULL scene, an unknown `what`, a range that reaches past the array's end or a HIP failure. */
 enum { RT_SCENE_VIEW_HEADER = 0, RT_SCENE_VIEW_CAM_START, RT_SCENE_VIEW_CAM_END, RT_SCENE_VIEW_TRI_REC, RT_SCENE_VIEW_TRI_SHADE,
-       RT_SCENE_VIEW_GRID_BITS, RT_SCENE_VIEW_BLOCK_SPARSE, RT_SCENE_VIEW_PAIR_REC, RT_SCENE_VIEW_CELL_LUT, RT_SCENE_VIEWS };
+       RT_SCENE_VIEW_GRID_BITS, RT_SCENE_VIEW_BLOCK_SPARSE, RT_SCENE_VIEW_PAIR_REC, RT_SCENE_VIEW_CELL_LUT, RT_SCENE_VIEWS,
+       RT_SCENE_VIEW_CLIP_PLANES = 16, RT_SCENE_VIEW_CLIP_APPLIED /* (parts of the planes' buffer, numbered apart from the arrays 0 .. RT_SCENE_VIEWS - 1) */ };
 int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement, uint64_t count, void *out);
 
 /* TEST-ONLY, for rtHipSceneSetCamera.  rtHipTestSceneCameraList copies entries [first, first + count) of the scene's device camera list

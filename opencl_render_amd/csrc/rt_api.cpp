@@ -28,6 +28,8 @@ extern "C" hipError_t rtp_validate(uint32_t T, uint32_t V, uint32_t M, const voi
                                    hipStream_t stream);
 extern "C" hipError_t rtp_camera_ranges(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount, const uint32_t *camStart,
                                         const uint32_t *camEnd, uint64_t camListSize, uint32_t *outStart, uint32_t *outEnd, uint32_t *err, hipStream_t stream);
+extern "C" hipError_t rtp_clip_support(const unsigned long long *words, const float *planeTable, const float *normals, uint32_t candidates, uint32_t *keys,
+                                       hipStream_t stream);
 extern "C" hipError_t rtp_dense_grid(const uint32_t *gridStart, const uint32_t *gridList, unsigned long long *words, uint32_t *sparse, uint32_t *pairOrder,
                                      uint32_t *pairCount, void *scratch, size_t *scratchBytes, hipStream_t stream);
 
@@ -222,6 +224,45 @@ void grid_tables(const float *planes, uint8_t *lut, uint32_t *tame)
     }
 }
 
+// The planes' buffer as the host makes it (rt_ray_clip.h): the [3][257] planes, no clip plane yet, the candidate normals for the bound kernel.
+void clip_buffer_init(const float *planes, float *buffer)
+{
+    static const std::vector<float> normals = [] { std::vector<float> n(4 * RT_CLIP_CANDIDATES); (void)rt_clip_candidates(reinterpret_cast<float (*)[4]>(n.data())); return n; }();
+    memset(buffer, 0, sizeof(float) * RT_CLIP_FLOATS);
+    memcpy(buffer, planes, sizeof(float) * 3 * (RT_GRID_DIV + 1));
+    memcpy(buffer + RT_CLIP_NORMALS_AT, normals.data(), sizeof(float) * normals.size());
+}
+// The bound's supports over the occupancy words `words`, into the planes' buffer `boxMin` and back to sc->clipKeys (complete after a
+// synchronisation of `st`) ...
+hipError_t clip_bound_issue(rtHipScene *sc, const unsigned long long *words, float *boxMin, hipStream_t st)
+{
+    uint32_t *keys = reinterpret_cast<uint32_t *>(boxMin + RT_CLIP_KEYS_AT);
+    const hipError_t e = rtp_clip_support(words, boxMin, boxMin + RT_CLIP_NORMALS_AT, RT_CLIP_CANDIDATES, keys, st);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(sc->clipKeys, keys, sizeof sc->clipKeys, hipMemcpyDeviceToHost, st);
+}
+// ... and, after that synchronisation, the planes to keep: their number in *count and what the planes' buffer holds from RT_CLIP_AT on in
+// `tail` ([4 + 4 * RT_CLIP_MAX_PLANES]), written behind the planes of `boxMin` on `st`.  The scene's own copy (clipCount, clipTail) is the
+// caller's to set once the grid they belong to is the scene's: a build or a move that fails after this leaves the scene as it was.
+hipError_t clip_bound_commit(const rtHipScene *sc, const float *planes, float *boxMin, hipStream_t st, uint32_t *count, float *tail)
+{
+    float normal[RT_CLIP_CANDIDATES][4], off[RT_CLIP_CANDIDATES];
+    (void)rt_clip_candidates(normal);
+    const float inflate = rt_clip_inflation(planes);
+    for (int c = 0; c < RT_CLIP_CANDIDATES; ++c) off[c] = sc->clipKeys[c] ? rt_clip_unkey(sc->clipKeys[c]) + inflate : std::nanf(""); // (key 0: no cell is occupied)
+    int kept[RT_CLIP_MAX_PLANES];
+    const int n = rt_clip_choose(planes, normal, off, RT_CLIP_CANDIDATES, kept, nullptr);
+    memset(tail, 0, sizeof sc->clipTail);
+    for (int k = 0; k < n; ++k) {
+        float *row = tail + 4 + 4 * k;
+        row[0] = normal[kept[k]][0]; row[1] = normal[kept[k]][1]; row[2] = normal[kept[k]][2]; row[3] = off[kept[k]];
+    }
+    *count = (uint32_t)n;
+    const uint32_t applied = sc->tune.rayClip ? *count : 0u;
+    memcpy(tail, &applied, 4);
+    return hipMemcpyAsync(boxMin + RT_CLIP_AT, tail, sizeof sc->clipTail, hipMemcpyHostToDevice, st);
+}
+
 // the grid as the ABI hands it over, plus its dense view for the wavefront trace kernel, built on the device
 int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
 {
@@ -232,7 +273,9 @@ int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
     std::vector<float> planes(3 * (RT_GRID_DIV + 1));
     for (int w = 0; w < 3; ++w)
         for (int i = 0; i <= RT_GRID_DIV; ++i) planes[w * (RT_GRID_DIV + 1) + i] = d->boxMin[i].s[w];
-    if (sc->upload(planes.data(), planes.size(), &D.boxMin, "boxMin")) return -1;
+    std::vector<float> planeBuffer(RT_CLIP_FLOATS);
+    clip_buffer_init(planes.data(), planeBuffer.data());
+    if (sc->upload(planeBuffer.data(), planeBuffer.size(), &D.boxMin, "boxMin")) return -1;
     std::vector<uint8_t> lut(3 * 256);
     grid_tables(planes.data(), lut.data(), &D.planesTame);
     if (sc->upload(lut.data(), lut.size(), &D.cellLut, "cellLut")) return -1;
@@ -261,6 +304,7 @@ int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
     HIP_OK(scratch.get((void **)&pairOrder, (size_t)listSize * 4)); HIP_OK(scratch.get((void **)&pairCount, (size_t)listSize * 4));
     HIP_OK(scratch.get(&tmp, tmpBytes));
     HIP_OK(rtp_dense_grid(D.gridStart, D.gridList, words, sparse, pairOrder, pairCount, tmp, &tmpBytes, sc->stream));
+    HIP_OK(clip_bound_issue(sc, words, const_cast<float *>(D.boxMin), sc->stream));
     float *pairRec = nullptr;
     if (sc->alloc<float>((uint64_t)listSize * 16, &pairRec)) return -1;
     HIP_OK(rtk_launch_gather_pairs((uint32_t)listSize, pairOrder, pairCount, D.triRec, pairRec, sc->stream));
@@ -268,6 +312,12 @@ int build_grid(rtHipScene *sc, const rtHipSceneDesc *d)
     sc->gridListSize = listSize;
     D.cellCount = 0; // informational; the kernels find a cell's records through the block table
     HIP_OK(hipStreamSynchronize(sc->stream));
+    uint32_t clipCount = 0;
+    float clipTail[4 + 4 * RT_CLIP_MAX_PLANES];
+    HIP_OK(clip_bound_commit(sc, planes.data(), const_cast<float *>(D.boxMin), sc->stream, &clipCount, clipTail));
+    HIP_OK(hipStreamSynchronize(sc->stream));
+    sc->clipCount = clipCount;
+    memcpy(sc->clipTail, clipTail, sizeof sc->clipTail);
     return 0;
 }
 
@@ -495,7 +545,7 @@ void refresh_views(rtHipScene *sc)
 }
 
 // bytes of the fixed-size arrays of a grid (rtHipScene::GeoMove::Set)
-constexpr uint64_t GEO_PLANE_BYTES = 3 * (RT_GRID_DIV + 1) * 4, GEO_LUT_BYTES = 3 * 256, GEO_START_BYTES = ((uint64_t)RT_GRID_DIV * RT_GRID_DIV * RT_GRID_DIV + 1) * 4,
+constexpr uint64_t GEO_PLANE_BYTES = RT_CLIP_FLOATS * 4 /* (the planes and the clip bound behind them, rt_ray_clip.h) */, GEO_LUT_BYTES = 3 * 256, GEO_START_BYTES = ((uint64_t)RT_GRID_DIV * RT_GRID_DIV * RT_GRID_DIV + 1) * 4,
                    GEO_BITS_BYTES = (uint64_t)(RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * 8,
                    GEO_SPARSE_BYTES = (uint64_t)3 * ((63u << 16 | 63u << 8 | 63u) + 1u) * 4;
 
@@ -536,6 +586,12 @@ int clone_part(rtHipScene *dst, const rtHipScene *src, int part)
     if (part == PART_GRID) {
         D.planesTame = S.planesTame; D.cellCount = S.cellCount; dst->gridListSize = src->gridListSize;
         RT_MOVE(boxMin); RT_MOVE(cellLut); RT_MOVE(gridStart); RT_MOVE(gridList); RT_MOVE(gridBits); RT_MOVE(gridBlockSparse); RT_MOVE(pairRec);
+        // the clip bound came with the planes; how many of its planes the kernels apply is this instance's own tuning
+        dst->clipCount = src->clipCount;
+        memcpy(dst->clipTail, src->clipTail, sizeof dst->clipTail);
+        const uint32_t applied = dst->tune.rayClip ? dst->clipCount : 0u;
+        memcpy(dst->clipTail, &applied, 4);
+        HIP_OK(hipMemcpyAsync(const_cast<float *>(D.boxMin) + RT_CLIP_AT, dst->clipTail, 4, hipMemcpyHostToDevice, dst->stream));
     }
     if (part == PART_MATERIALS) {
         D.materialCount = S.materialCount; D.texelCount = S.texelCount; RT_MOVE(matSize); RT_MOVE(matStart); RT_MOVE(textures); RT_MOVE(matRec);
@@ -653,6 +709,75 @@ RtRoundMode mode_for(const Tuning &T, uint32_t round, uint64_t rays, uint32_t sl
     return m;
 }
 
+// TEST ONLY (tuning key visit_log; include/raytrace_hip.h, rtHipTestRoundVisits).  Round r of group G, once its trace launch is issued on
+// `on` and before logic(r) consumes its answers and logic(r + 1) overwrites its entries: wait for the stream, read the round's queues back
+// and add what they hold to sc->visitLog[r].  The entries are the ones the planning kernels wrote (rt_device.h, RtWavefront::ent).
+int log_round_visits(rtHipScene *sc, rtHipScene::Group &G, uint32_t r, const RtRoundMode &mode, hipStream_t on)
+{
+    const RtWavefront &W = G.wf;
+    HIP_OK(hipStreamSynchronize(on));
+    std::vector<uint32_t> ctl(RT_WF_CTL_WORDS);
+    std::vector<float> planes(3 * (RT_GRID_DIV + 1));
+    HIP_OK(hipMemcpy(ctl.data(), W.ctl + (size_t)(r % 3) * RT_WF_CTL_WORDS, sizeof(uint32_t) * RT_WF_CTL_WORDS, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(planes.data(), G.dev.boxMin, sizeof(float) * planes.size(), hipMemcpyDeviceToHost));
+    const uint32_t cap = W.capacity, sliceCap = cap / mode.slices;
+    const uint32_t extra = mode.ordered ? std::min(ctl[RT_WF_CTL_EXTRA], W.extraCap) : 0u;
+    std::vector<uint4> ent((size_t)4 * (2 * (size_t)cap + extra));
+    std::vector<unsigned long long> key(2 * (size_t)cap);
+    std::vector<uint2> pathOf(cap);
+    HIP_OK(hipMemcpy(ent.data(), W.ent[r & 1u], sizeof(uint4) * ent.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(key.data(), W.hitKey[r & 1u], sizeof(unsigned long long) * key.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(pathOf.data(), W.pathOf[r & 1u], sizeof(uint2) * pathOf.size(), hipMemcpyDeviceToHost));
+    auto cell_of = [&](const float p[3]) { // (GetBoxAddress, as rt_wavefront.hip's cell_of)
+        uint32_t c[3] = { 0, 0, 0 };
+        for (int w = 0; w < 3; ++w)
+            for (int div = RT_GRID_DIV / 2; div >= 1; div /= 2)
+                if (planes[(size_t)w * (RT_GRID_DIV + 1) + c[w] + div] < p[w]) c[w] += div;
+        return c[0] | c[1] << 8 | c[2] << 16;
+    };
+    // the cells an entry's walk makes if it hits nothing (plan_ray: one axis by one cell per step)
+    auto visits_of = [&](const uint4 *e) -> uint64_t {
+        const uint32_t start = e[0].y & 0xffffffu;
+        uint32_t last = e[0].z;
+        if (last == 0xffffffffu) { // no end cell: the walk leaves the box, at the smallest of the three wall crossings
+            float o[3], d[3], te = HUGE_VALF;
+            memcpy(o, &e[2], 12); memcpy(d, &e[3], 12);
+            for (int w = 0; w < 3; ++w)
+                if (d[w] != 0.f) { const float t = (planes[(size_t)w * (RT_GRID_DIV + 1) + (0.f <= d[w] ? RT_GRID_DIV : 0)] - o[w]) / d[w]; if (t < te) te = t; }
+            if (!(te < HUGE_VALF)) return 1;
+            const float to[3] = { o[0] + te * d[0], o[1] + te * d[1], o[2] + te * d[2] };
+            last = cell_of(to);
+        }
+        uint64_t v = 1;
+        for (int w = 0; w < 3; ++w) v += (uint64_t)std::abs((int)((last >> 8 * w) & 255u) - (int)((start >> 8 * w) & 255u));
+        return v;
+    };
+    uint64_t *out = sc->visitLog[r].data();
+    out[RT_ROUND_VISIT_ORDERED] = mode.ordered;
+    auto kind_of = [&](uint32_t q) { return q >= cap ? 2u : (pathOf[q].y != 0xffffffffu ? 0u : 1u); }; // q: a ray's queue index
+    for (uint32_t look = 0; look < 2; ++look)
+        for (uint32_t s = 0; s < mode.slices; ++s) {
+            const uint32_t n = std::min(ctl[RT_WF_CTL_COUNTS + look * RT_WF_SHARDS + s], sliceCap), base = look * cap + s * sliceCap;
+            for (uint32_t q = base; q < base + n; ++q) {
+                uint64_t *f = out + RT_ROUND_VISIT_RAYS + 3 * kind_of(q);
+                f[0] += 1;
+                f[1] += key[q] != ~0ull;
+                if (!mode.ordered) continue;
+                f[2] += visits_of(&ent[(size_t)4 * q]);
+                out[RT_ROUND_VISIT_ENTRIES] += 1;
+                out[RT_ROUND_VISIT_ENDED] += ent[(size_t)4 * q].z != 0xffffffffu;
+            }
+        }
+    for (uint32_t i = 0; i < extra; ++i) { // region B: the further segments of cut rays, x = the ray's queue index (all ones: an unused reservation)
+        const uint4 *e = &ent[(size_t)4 * (2 * (size_t)cap + i)];
+        if (e[0].x >= 2 * cap) continue;
+        out[RT_ROUND_VISIT_RAYS + 3 * kind_of(e[0].x) + 2] += visits_of(e);
+        out[RT_ROUND_VISIT_ENTRIES] += 1;
+        out[RT_ROUND_VISIT_ENDED] += e[0].z != 0xffffffffu;
+    }
+    return 0;
+}
+
 // One frame through the staged pipeline: per sample batch and tile group -- primary, then rounds of (scatter,) trace, logic until
 // no path is waiting for the grid, then the ordered accumulate.  The round count is data dependent.
 //
@@ -691,6 +816,7 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
         if (er != hipSuccess) return er;
         return hipEventRecord(e.b, on);
     };
+    if (T.visitLog) sc->visitLog.assign(RT_WF_ROUND_LOG, {});
     const bool serial = sc->stageTiming || sc->groups.size() == 1;
     auto streamOf = [&](size_t g) { return (serial || g == 0) ? st : sc->groups[g].stream; };
     if (!serial) {
@@ -743,6 +869,7 @@ int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
         if (r > 0) { // the entries appended by logic(r-1): order them if the round is an ordered one, then walk the grid
             if (mode.ordered) HIP_OK(stage(4, on, [&] { return rtw_launch_scatter(&G.wf, r, G.queueBlocks, &mode, on); }));
             HIP_OK(stage(2, on, [&] { return rtw_launch_trace(&G.dev, &G.wf, r, trace_blocks(G, r, mode), &mode, on); }));
+            if (T.visitLog && r < RT_WF_ROUND_LOG && log_round_visits(sc, G, r, mode, on) != 0) return -1;
         }
         const RtRoundMode next = round_mode(G, r + 1);
         // A later round of the opaque-diffuse class with look-ahead on (Tuning::logicSplit): the answers as a stream (wf_answer_kernel), then the
@@ -1955,7 +2082,9 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     for (int w = 0; w < 3; ++w)
         for (int i = 0; i <= RT_GRID_DIV; ++i) planes[w * (RT_GRID_DIV + 1) + i] = bm[4 * i + w];
     grid_tables(planes, lut, &tame);
-    GEO_HIP(hipMemcpyAsync(N.boxMin, planes, sizeof planes, hipMemcpyHostToDevice, st));
+    float planeBuffer[RT_CLIP_FLOATS];
+    clip_buffer_init(planes, planeBuffer);
+    GEO_HIP(hipMemcpyAsync(N.boxMin, planeBuffer, sizeof planeBuffer, hipMemcpyHostToDevice, st));
     GEO_HIP(hipMemcpyAsync(N.cellLut, lut, sizeof lut, hipMemcpyHostToDevice, st));
     GEO_HIP(hipEventRecord(G.ev[2], st));
 
@@ -1967,6 +2096,7 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     GEO_HIP(hipMemsetAsync(N.sparse, 0, GEO_SPARSE_BYTES, st));
     GEO_HIP(rtp_dense_grid(N.gridStart, N.gridList, N.gridBits, N.sparse, G.pairOrder, G.pairInfo, G.denseTmp, &denseBytes, st));
     GEO_HIP(rtk_launch_gather_pairs((uint32_t)pairs, G.pairOrder, G.pairInfo, N.triRec, N.pairRec, st));
+    GEO_HIP(clip_bound_issue(sc, N.gridBits, N.boxMin, st)); // (read back by the synchronisation behind the camera lists)
     GEO_HIP(hipEventRecord(G.ev[3], st));
 
     // 6. the camera lists of the camera in effect, over the new records
@@ -1980,6 +2110,10 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     GEO_HIP(hipStreamSynchronize(st));
     float ms[4] = {};
     for (int i = 0; i < 4; ++i) GEO_HIP(hipEventElapsedTime(&ms[i], G.ev[i], G.ev[i + 1]));
+    uint32_t clipCount = 0;
+    float clipTail[4 + 4 * RT_CLIP_MAX_PLANES];
+    GEO_HIP(clip_bound_commit(sc, planes, N.boxMin, st, &clipCount, clipTail));
+    GEO_HIP(hipStreamSynchronize(st));
 #undef GEO_HIP
 #undef GEO_MEM
 
@@ -1987,6 +2121,8 @@ int rtHipSceneSetGeometry(rtHipScene *sc, const rtHipGeometryUpdate *up)
     RtDevScene &D = sc->dev;
     D.triRec = N.triRec; D.triShade = N.triShade;
     D.boxMin = N.boxMin; D.cellLut = N.cellLut; D.planesTame = tame;
+    sc->clipCount = clipCount;
+    memcpy(sc->clipTail, clipTail, sizeof sc->clipTail);
     D.gridStart = N.gridStart; D.gridList = N.gridList; D.gridBits = N.gridBits; D.gridBlockSparse = N.sparse; D.pairRec = N.pairRec;
     sc->gridListSize = pairs;
     G.live = target;
@@ -2215,9 +2351,9 @@ int rtHipTune(const char *key, double value)
         { "seg0", &T.segLen[0] }, { "seg1", &T.segLen[1] }, { "seg2", &T.segLen[2] }, { "seg3", &T.segLen[3] }, { "seg4", &T.segLen[4] },
         { "seg_rays0", &T.segRays[0] }, { "seg_rays1", &T.segRays[1] }, { "seg_rays2", &T.segRays[2] }, { "seg_rays3", &T.segRays[3] },
         { "fast_quotient", &T.fastQuotient }, { "spin_limit", &T.spinLimit }, { "append_rays", &T.appendRays }, { "ordered_first", &T.orderedFirst }, { "slice_rays", &T.sliceRays },
-        { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny }, { "plan_shade_skip", &T.planShadeSkip },
+        { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny }, { "plan_shade_skip", &T.planShadeSkip }, { "visit_log", &T.visitLog },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
-        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "logic_split", &T.logicSplit }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
+        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "ray_clip", &T.rayClip }, { "logic_split", &T.logicSplit }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
         { "ao_samples", &T.aoSamples, nullptr, 1u << 22 }, { "bake_texels", &T.bakeTexels, nullptr, 1u << 24 },
         { "state_mb", nullptr, &T.stateMb, HUGE_VAL }, { "build_key_cap", nullptr, &T.buildKeyCap, 1e18 }, { "build_list_limit", nullptr, &T.buildListLimit },
     };
@@ -2279,6 +2415,15 @@ int rtHipTestRoundLog(const rtHipScene *scene, uint32_t *rays, uint32_t n)
     return (int)scene->roundsLast;
 }
 
+int rtHipTestRoundVisits(const rtHipScene *scene, uint64_t *out, uint32_t rounds)
+{
+    if (!scene || (rounds && !out)) return fail("rtHipTestRoundVisits: null argument");
+    if (!scene->tune.visitLog) return fail("rtHipTestRoundVisits: the scene was built without the test hook visit_log");
+    for (uint32_t r = 0; r < rounds; ++r)
+        for (uint32_t f = 0; f < RT_ROUND_VISIT_FIELDS; ++f) out[(size_t)RT_ROUND_VISIT_FIELDS * r + f] = r < scene->visitLog.size() ? scene->visitLog[r][f] : 0;
+    return (int)std::min<uint64_t>(scene->roundsLast, 0x7fffffffu);
+}
+
 int rtHipTestShadeLog(const rtHipScene *scene, uint32_t *listed, uint32_t n)
 {
     if (!scene || (n && !listed)) return -1;
@@ -2309,6 +2454,9 @@ int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement,
     case RT_SCENE_VIEW_BLOCK_SPARSE: v = { D.gridBlockSparse, (uint64_t)3 * ((63u << 16 | 63u << 8 | 63u) + 1u), 4, false }; break;
     case RT_SCENE_VIEW_PAIR_REC: v = { D.pairRec, scene->gridListSize, 64, false }; break;
     case RT_SCENE_VIEW_CELL_LUT: v = { D.cellLut, 3 * 256, 1, false }; break;
+    // (what the planning kernels read, behind the planes on the device -- not the host's copy)
+    case RT_SCENE_VIEW_CLIP_PLANES: v = { D.boxMin ? D.boxMin + RT_CLIP_AT + 4 : nullptr, scene->clipCount, 16, false }; break;
+    case RT_SCENE_VIEW_CLIP_APPLIED: v = { D.boxMin ? D.boxMin + RT_CLIP_AT : nullptr, 1, 4, false }; break;
     default: return fail("rtHipTestSceneView: unknown array %d", what);
     }
     if (v.elements > 0x7fffffffull) return fail("rtHipTestSceneView: array %d has %llu elements", what, (unsigned long long)v.elements);

@@ -21,6 +21,8 @@
 //                           while a candidate test costs one 64-B gather instead of 16 B index + 3 x 16 B vertices.
 //  triShade [T][24 floats]  what only a shaded hit needs: b.xyz c.xyz | nA nB nC | uvA uvB uvC | materialId | pad
 //  boxMin   [3][257]        split planes, one array per axis (staged into LDS by every workgroup)
+//                           followed, from float RT_CLIP_AT on, by the grid's clip bound (rt_ray_clip.h): how many planes the planning
+//                           kernels apply, the planes {n.xyz, off}, and the bound kernel's keys and candidate normals
 //  camStart/camEnd          per pixel of this scene's tiles, TILE-MAJOR: index = slot*128*128 + ly*128 + lx
 //  tileBuf  [slot][3][128*128] u16 planes R,G,B
 //  passBuf  [slot][RT_PASS_WORDS][128*128] 32-bit words (only when render passes are on; not part of RtDevScene): per pixel the

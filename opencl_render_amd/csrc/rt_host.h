@@ -4,6 +4,7 @@
 #pragma once
 #include "raytrace_hip.h"
 #include "rt_device.h"
+#include "rt_ray_clip.h"
 #include "rt_camera_move.h"
 #include "rt_geometry_move.h"
 #include "rt_owned.h"
@@ -11,6 +12,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstring>
 #include <mutex>
@@ -59,6 +61,7 @@ struct Tuning {
     uint32_t planRounds = 0;        // test hook: planned frames issue at most this many rounds, so that the too-short-plan path runs
     uint32_t planGridTiny = 0;      // test hook: planned trace grids of one workgroup, so that the too-small-grid path runs
     uint32_t planShadeSkip = 0;     // test hook: planned frames launch no shade pass (as if the plan's shade lists were empty), so that the listed-but-skipped path runs
+    uint32_t visitLog = 0;          // test hook: every frame waits after each round's trace launch and the host reads the round back (rtHipTestRoundVisits)
     uint32_t pipeline = RT_HIP_PIPELINE_WAVEFRONT;
     uint32_t timing = 0;            // 1: where the time of a scene build / a RaytraceAll call goes (stderr)
     uint32_t virtualDevices = 0;    // test hook: the all-GPUs id deals the tiles over this many instances on the devices that are there
@@ -66,6 +69,7 @@ struct Tuning {
     uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
     uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
     uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
+    uint32_t rayClip = 1;           // 1: grid rays without a far end stop where they leave the scene's clip bound (rt_ray_clip.h); 0: at the grid's wall
     uint32_t logicSplit = 1;        // 1: rounds >= 1 of the opaque-diffuse class (look-ahead on) run wf_answer_kernel + wf_shade_kernel; 0: wf_logic_kernel
     uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
     uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
@@ -202,6 +206,11 @@ struct rtHipScene {
     uint64_t gridListSize = 0;      // entries of the grid list = pair records of the dense view
     uint32_t gridListSizeHint = 0;  // scene description with device arrays: scenePixelTriangleListStart[256^3], fetched by scene_build
     bool haveGridListSize = false;
+    // the clip bound of the grid in effect (rt_ray_clip.h): the planes kept {n.xyz, off}, and what the planes' buffer holds from RT_CLIP_AT
+    // on (the count the kernels apply -- 0 with tune.rayClip off -- three pad words, the planes); clipKeys: the supports' read-back
+    uint32_t clipCount = 0;
+    float clipTail[4 + 4 * RT_CLIP_MAX_PLANES] = {};
+    uint32_t clipKeys[RT_CLIP_CANDIDATES] = {};
     bool wfMultiLight = false;     // what the path-state buffers were sized for
     bool classMaterials = false, classLights = false; // the materials part / the lights part admit the opaque-diffuse path class
     uint64_t bytes = 0;
@@ -259,6 +268,8 @@ struct rtHipScene {
     size_t stageEventsUsed = 0;
     bool stageTiming = false;
     uint64_t roundsLast = 0;
+    // test hook visit_log: per round of the last frame, the fields of rtHipTestRoundVisits (render_wavefront, log_round_visits)
+    std::vector<std::array<uint64_t, RT_ROUND_VISIT_FIELDS>> visitLog;
     // render passes (rtHipScenePasses): RT_HIP_PASS_* bits, the pass buffer [slot][RT_PASS_WORDS][128*128] (rt_device.h) while ALPHA,
     // DEPTH or TRIANGLE is on, and the surface buffer [slot][RT_SURF_WORDS][128*128] while NORMAL or ALBEDO is on
     uint32_t passMask = 0;

@@ -12,6 +12,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rt_device.h"
+#include "rt_ray_clip.h"
 
 namespace {
 
@@ -115,6 +116,46 @@ __global__ __launch_bounds__(256) void rtp_block_emit(const uint32_t *__restrict
     }
 }
 
+// The clip bound's supports (rt_ray_clip.h): for every candidate normal, the largest n . corner over the boxes of the occupied cells, reduced
+// into keys[] (rt_clip_key; zeroed before).  One thread per 4x4x4 block and RTP_CLIP_NORMALS candidates (blockIdx.y picks which; they sit in
+// scalar registers), one atomic per wave and candidate.
+#define RTP_CLIP_NORMALS 16
+__global__ __launch_bounds__(256) void rtp_clip_support_kernel(const unsigned long long *__restrict__ words, const float *__restrict__ planeTable,
+                                                               const float4 *__restrict__ normals, uint32_t candidates, uint32_t *__restrict__ keys)
+{
+    __shared__ float pl[3 * (RT_GRID_DIV + 1)];
+    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) pl[i] = planeTable[i];
+    __syncthreads();
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x; // BLOCKS threads
+    const uint32_t bx = b & 63u, by = (b >> 6) & 63u, bz = b >> 12;
+    const uint32_t first = blockIdx.y * RTP_CLIP_NORMALS;
+    unsigned long long w = words[b];
+    if (__ballot(w != 0ull) == 0ull) return; // wave-uniform
+    float4 n[RTP_CLIP_NORMALS];
+    float best[RTP_CLIP_NORMALS];
+#pragma unroll
+    for (int j = 0; j < RTP_CLIP_NORMALS; ++j) {
+        n[j] = normals[min(first + j, candidates - 1u)];
+        best[j] = -__builtin_inff();
+    }
+    while (w) {
+        const int bit = __ffsll((long long)w) - 1;
+        w &= w - 1;
+        const uint32_t cx = bx * 4 + (bit & 3), cy = by * 4 + ((bit >> 2) & 3), cz = bz * 4 + (bit >> 4);
+        const float lox = pl[cx], hix = pl[cx + 1], loy = pl[(RT_GRID_DIV + 1) + cy], hiy = pl[(RT_GRID_DIV + 1) + cy + 1];
+        const float loz = pl[2 * (RT_GRID_DIV + 1) + cz], hiz = pl[2 * (RT_GRID_DIV + 1) + cz + 1];
+#pragma unroll
+        for (int j = 0; j < RTP_CLIP_NORMALS; ++j) best[j] = fmaxf(best[j], rt_clip_support(n[j].x, n[j].y, n[j].z, lox, loy, loz, hix, hiy, hiz));
+    }
+#pragma unroll
+    for (int j = 0; j < RTP_CLIP_NORMALS; ++j) {
+        float m = best[j];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        if ((threadIdx.x & 63) == 0 && first + j < candidates && m > -__builtin_inff()) atomicMax(&keys[first + j], rt_clip_key(m));
+    }
+}
+
 } // namespace
 
 extern "C" hipError_t rtp_validate(uint32_t T, uint32_t V, uint32_t M, const void *triIndex, const int *triMaterial, uint64_t camListSize,
@@ -156,5 +197,18 @@ extern "C" hipError_t rtp_dense_grid(const uint32_t *gridStart, const uint32_t *
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rtp_block_emit, dim3(BLOCKS / 256), dim3(256), 0, stream, gridStart, gridList, words, rank, restBase, blockCells, sparse, pairOrder,
                        pairCount);
+    return hipGetLastError();
+}
+
+// The supports of the clip bound over the occupied cells of `words` (rtp_dense_grid's occupancy words): planeTable = the [3][257] planes,
+// normals = `candidates` unit normals {n.xyz, 0}; keys[candidates] receives rt_clip_key(support), 0 where no cell is occupied.
+extern "C" hipError_t rtp_clip_support(const unsigned long long *words, const float *planeTable, const float *normals, uint32_t candidates, uint32_t *keys,
+                                       hipStream_t stream)
+{
+    if (!candidates) return hipSuccess;
+    hipError_t e = hipMemsetAsync(keys, 0, sizeof(uint32_t) * candidates, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rtp_clip_support_kernel, dim3(BLOCKS / 256, (candidates + RTP_CLIP_NORMALS - 1) / RTP_CLIP_NORMALS), dim3(256), 0, stream, words,
+                       planeTable, (const float4 *)normals, candidates, keys);
     return hipGetLastError();
 }

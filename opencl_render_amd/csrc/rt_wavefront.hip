@@ -20,6 +20,7 @@
 // Per path everything happens in the reference's order (RNG draws, ring FIFO, light loop), and paths never interact,
 // so the planes are bit-identical to the single-launch kernel (rt_kernels.hip) and to the oracle.
 #include "rt_devfuncs.h"
+#include "rt_ray_clip.h"
 
 namespace {
 
@@ -415,14 +416,18 @@ struct EntryPlan { DdaState start; uint32_t endCell, visits; float te; };
 // `haveStart`: the caller knows the start cell (a hit's shadow ray and its bounce ray start at the same point).  `lut` (optional; LDS
 // copy of RtDevScene::cellLut followed by the three scales 256 / box width): where a ray WITHOUT an end cell leaves the grid -- which
 // only predicts the length of its walk -- is estimated with one table read per axis instead of a plane search.
+// `clip` (optional; RtDevScene::boxMin + RT_CLIP_AT, the same address in every lane): the scene's clip planes (rt_ray_clip.h), read with scalar
+// loads.  A plain ray's te is lowered to where it leaves their bound, and it ends in the cell of that point like a finite ray.
+typedef const __attribute__((address_space(4))) float *ClipPlanes;
 __device__ __forceinline__ EntryPlan plan_ray(const float *planes, V3 o, V3 d, float tmin, float tmax, bool haveStart = false, uint32_t startCell = 0u,
-                                              const uint8_t *lut = nullptr, const float *lutScale = nullptr)
+                                              const uint8_t *lut = nullptr, const float *lutScale = nullptr, const float *clip = nullptr)
 {
     EntryPlan p;
     const V3 lo = mk(planes[0], planes[RT_GRID_DIV + 1], planes[2 * (RT_GRID_DIV + 1)]);
     const V3 hi = mk(planes[RT_GRID_DIV], planes[2 * RT_GRID_DIV + 1], planes[3 * RT_GRID_DIV + 2]);
     // start / end cells (:351-362)
     V3 from = along(o, tmin, d);
+    const bool startInside = lo.x <= from.x && from.x <= hi.x && lo.y <= from.y && from.y <= hi.y && lo.z <= from.z && from.z <= hi.z;
     bind_in_cube(from, d, lo, hi);
     p.start.cell = startCell;
     if (!haveStart) p.start.cell = cell_of(planes, from);
@@ -438,18 +443,26 @@ __device__ __forceinline__ EntryPlan plan_ray(const float *planes, V3 o, V3 d, f
         if (d.z != 0.f) { const float t = (((0.f <= d.z) ? hi.z : lo.z) - o.z) / d.z; if (t < p.te) p.te = t; }
         to = (p.te < RT_INF) ? along(o, p.te, d) : from;
     }
-    uint32_t last; // (where a ray without an end cell leaves the grid is a scheduling matter only)
-    if (lut && !(tmax < RT_INF)) {
-        const float fx = (to.x - lo.x) * lutScale[0], fy = (to.y - lo.y) * lutScale[1], fz = (to.z - lo.z) * lutScale[2];
-        const int ix = min(255, max(0, (int)fx)), iy = min(255, max(0, (int)fy)), iz = min(255, max(0, (int)fz)); // (a NaN converts to 0)
-        last = (uint32_t)lut[ix] | ((uint32_t)lut[256 + iy] << 8) | ((uint32_t)lut[512 + iz] << 16);
-    } else last = cell_of(planes, to);
-    p.endCell = (tmax < RT_INF) ? last : 0xffffffffu;
     const int cx = (int)(p.start.cell & 255u), cy = (int)((p.start.cell >> 8) & 255u), cz = (int)(p.start.cell >> 16);
     // distances from the ray ORIGIN to the next plane of each axis (:383-385)
     p.start.dx = (planes[cx + ((0 <= d.x) ? 1 : 0)] - o.x) / d.x;
     p.start.dy = (planes[(RT_GRID_DIV + 1) + cy + ((0 <= d.y) ? 1 : 0)] - o.y) / d.y;
     p.start.dz = (planes[2 * (RT_GRID_DIV + 1) + cz + ((0 <= d.z) ? 1 : 0)] - o.z) / d.z;
+    // the clip (rt_ray_clip.h has the argument): the walk ends once it has visited the cell of o + te d, beyond which every cell is empty
+    bool clipped = false;
+    if (clip) {
+        const ClipPlanes cp = (ClipPlanes)(uintptr_t)clip;
+        const uint32_t count = __float_as_uint(cp[0]);
+        clipped = rt_clip_ray(cp, count, tmax < RT_INF, startInside, o.x, o.y, o.z, d.x, d.y, d.z, tmin, p.start.dx, p.start.dy, p.start.dz, p.te);
+        if (clipped) to = along(o, p.te, d);
+    }
+    uint32_t last; // (where a ray without an end cell leaves the grid is a scheduling matter only)
+    if (lut && !(tmax < RT_INF) && !clipped) {
+        const float fx = (to.x - lo.x) * lutScale[0], fy = (to.y - lo.y) * lutScale[1], fz = (to.z - lo.z) * lutScale[2];
+        const int ix = min(255, max(0, (int)fx)), iy = min(255, max(0, (int)fy)), iz = min(255, max(0, (int)fz)); // (a NaN converts to 0)
+        last = (uint32_t)lut[ix] | ((uint32_t)lut[256 + iy] << 8) | ((uint32_t)lut[512 + iz] << 16);
+    } else last = cell_of(planes, to);
+    p.endCell = (tmax < RT_INF || clipped) ? last : 0xffffffffu;
     // every step moves one axis by one cell in a fixed direction: visits = Manhattan distance + 1
     p.visits = (uint32_t)(abs((int)(last & 255u) - cx) + abs((int)((last >> 8) & 255u) - cy) + abs((int)(last >> 16) - cz)) + 1u;
     return p;
@@ -460,10 +473,7 @@ __device__ __forceinline__ EntryPlan plan_ray(const float *planes, V3 o, V3 d, f
 // or NaN and the merge argument is not worth stretching to them); a ray only slightly over the aim is left whole.
 __device__ __forceinline__ uint32_t segments_of(const EntryPlan &p, V3 d, float tmax, uint32_t segLen)
 {
-    const float ta = fminf(p.start.dx, fminf(p.start.dy, p.start.dz));
-    const bool plain = !(tmax < RT_INF) && d.x != 0.f && d.y != 0.f && d.z != 0.f && p.te < RT_INF && -RT_INF < ta && ta < p.te &&
-                       p.start.dx == p.start.dx && p.start.dy == p.start.dy && p.start.dz == p.start.dz && p.start.dx < RT_INF &&
-                       p.start.dy < RT_INF && p.start.dz < RT_INF;
+    const bool plain = rt_clip_plain(tmax < RT_INF, d.x, d.y, d.z, p.te, p.start.dx, p.start.dy, p.start.dz);
     if (!plain || p.visits <= segLen + segLen / 4) return 1u;
     const uint32_t n = (p.visits + segLen - 1) / segLen;
     return n > RT_WF_MAXSEG ? (uint32_t)RT_WF_MAXSEG : n;
@@ -886,7 +896,7 @@ __global__ __launch_bounds__(256, RT_WF_LEAN_WAVES) void wf_trace_kernel(const R
             const uint4 c2 = e[2], c3 = e[3];
             const V3 o = mk(__uint_as_float(c2.x), __uint_as_float(c2.y), __uint_as_float(c2.z)), d = mk(__uint_as_float(c3.x), __uint_as_float(c3.y), __uint_as_float(c3.z));
             const float tmax = __uint_as_float(c2.w);
-            const EntryPlan plan = plan_ray(planes, o, d, tmin, tmax);
+            const EntryPlan plan = plan_ray(planes, o, d, tmin, tmax, false, 0u, nullptr, nullptr, S.boxMin + RT_CLIP_AT);
             n = segments_of(plan, d, tmax, mode.segLen);
             rayO[threadIdx.x] = pack4(o, tmin); rayD[threadIdx.x] = pack4(d, tmax);
             rayX[threadIdx.x] = make_uint4(excl, q, plan.start.cell, plan.endCell);

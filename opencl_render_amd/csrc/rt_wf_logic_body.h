@@ -734,7 +734,7 @@
                                        planes[0] <= o.x && o.x <= planes[RT_GRID_DIV] && planes[RT_GRID_DIV + 1] <= o.y && o.y <= planes[2 * RT_GRID_DIV + 1] &&
                                        planes[2 * (RT_GRID_DIV + 1)] <= o.z && o.z <= planes[3 * RT_GRID_DIV + 2];
                 if (has) {
-                    const EntryPlan plan = plan_ray(planes, o, d, tmin, tmax, sameStart, planM.start.cell, lut, lutScale);
+                    const EntryPlan plan = plan_ray(planes, o, d, tmin, tmax, sameStart, planM.start.cell, lut, lutScale, S.boxMin + RT_CLIP_AT);
                     const uint32_t n = segments_of(plan, d, tmax, next.segLen);
                     if (which) { planL = plan; nsegL = n; } else { planM = plan; nsegM = n; }
                 }

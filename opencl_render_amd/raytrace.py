@@ -148,7 +148,7 @@ RESIDENT_SYMBOLS = [
     "rtHipDenoiseVariance", "rtHipSceneTemporalVariance",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
-    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestShadeLog", "rtHipTestBuildLog",
+    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestRoundVisits", "rtHipTestShadeLog", "rtHipTestBuildLog",
     "rtHipTestShadeKat", "rtHipTestSceneView", "rtHipTestSceneCameraList", "rtHipTestScenePointers", "rtHipTestSceneCameraLog", "rtHipTestSceneCameraTimes",
     "rtHipTestSceneGeometryLog", "rtHipTestSceneGeometryTimes",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm", "rtHipWritePfmRgb",
@@ -304,6 +304,7 @@ def lib() -> C.CDLL:
     L.rtHipScenePathClass.argtypes = [C.POINTER(SceneDesc)]
     L.rtHipTestPathClass.argtypes = [vp]
     L.rtHipTestRoundLog.argtypes = [vp, C.POINTER(u32), u32]
+    L.rtHipTestRoundVisits.argtypes = [vp, C.POINTER(C.c_uint64), u32]
     L.rtHipTestShadeLog.argtypes = [vp, C.POINTER(u32), u32]
     L.rtHipTestBuildLog.argtypes = [C.POINTER(u64), u32]
     L.rtHipTestShadeKat.argtypes = [vp, C.c_int, u32, vp, vp]
@@ -322,7 +323,7 @@ _ENV_KEYS = {
     "RT_WF_APPEND_RAYS": "append_rays", "RT_WF_ORDERED_FIRST": "ordered_first", "RT_WF_SLICE_RAYS": "slice_rays", "RT_WF_SMALL_SLICES": "small_slices", "RT_WF_GROUP_RAYS": "group_rays",
     "RT_WF_BLOCKING": "blocking", "RT_WF_BATCH_PLAN": "batch_plan", "RT_WF_PLAN_ROUNDS": "plan_rounds", "RT_HIP_PIPELINE": "pipeline",
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
-    "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow", "RT_WF_LOGIC_SPLIT": "logic_split", "RT_WF_PLAN_SHADE_SKIP": "plan_shade_skip",
+    "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow", "RT_WF_RAY_CLIP": "ray_clip", "RT_WF_LOGIC_SPLIT": "logic_split", "RT_WF_PLAN_SHADE_SKIP": "plan_shade_skip", "RT_WF_VISIT_LOG": "visit_log",
     "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit", "RT_HIP_QUERY_RAYS": "query_rays",
 }
 # comma-separated lists: RT_WF_SEG=a,b,.. sets seg0, seg1, .. (at most 5 values), RT_WF_SEG_RAYS sets seg_rays0.. (at most 4)
@@ -785,6 +786,9 @@ SCENE_VIEWS = {
     "tri_shade": (4, np.float32, 24), "grid_bits": (5, np.uint64, 1), "block_sparse": (6, np.uint32, 1), "pair_rec": (7, np.uint32, 16),
     "cell_lut": (8, np.uint8, 1),
 }
+SCENE_VIEW_CLIP_PLANES = 16  # (RT_SCENE_VIEW_CLIP_PLANES; read by ResidentScene.clip_planes)
+SCENE_VIEW_CLIP_APPLIED = 17  # (RT_SCENE_VIEW_CLIP_APPLIED; read by ResidentScene.clip_applied)
+ROUND_VISIT_FIELDS = 12  # (RT_ROUND_VISIT_FIELDS)
 SCENE_VIEW_HEADER = ("planes_tame", "tile_count", "tiles_x", "triangle_count", "pair_count")
 
 
@@ -1088,6 +1092,23 @@ class ResidentScene:
             raise RuntimeError("rtHipTestRoundLog failed")
         return [int(v) for v in rays]
 
+    def round_visits(self, n: int = 8) -> list:
+        """What each trace round of the last frame held (rtHipTestRoundVisits; the scene was built with RT_WF_VISIT_LOG=1): per round a
+        dict {ordered, entries, ended, and per kind of ray -- shadow (a main entry sent out with a look-ahead entry), main (a main entry
+        on its own), bounce (a look-ahead entry) -- {rays, hits, visits}}; visits are planned cell visits, counted in ordered rounds."""
+        out = (C.c_uint64 * (ROUND_VISIT_FIELDS * n))()
+        if lib().rtHipTestRoundVisits(self.handle, out, n) < 0:
+            raise RuntimeError("rtHipTestRoundVisits failed: " + last_error())
+        rounds = []
+        for r in range(n):
+            f = [int(v) for v in out[ROUND_VISIT_FIELDS * r:ROUND_VISIT_FIELDS * (r + 1)]]
+            row = dict(ordered=f[0], entries=f[1], ended=f[2])
+            for k, kind in enumerate(("shadow", "main", "bounce")):
+                row[kind] = dict(rays=f[3 + 3 * k], hits=f[4 + 3 * k], visits=f[5 + 3 * k])
+            row["visits"] = sum(row[kind]["visits"] for kind in ("shadow", "main", "bounce"))
+            rounds.append(row)
+        return rounds
+
     def shade_log(self, n: int = 8):
         """(split logic rounds the last frame issued, paths each round listed for its shade pass) -- rtHipTestShadeLog; call after a
         synchronisation.  0 rounds: the frame ran one logic kernel per round."""
@@ -1119,6 +1140,22 @@ class ResidentScene:
         out = np.zeros((count, words) if words > 1 else count, dtype)
         self._check(lib().rtHipTestSceneView(self.handle, what, first, count, _ptr(out)), "rtHipTestSceneView")
         return out
+
+    def clip_planes(self) -> np.ndarray:
+        """The planes [n, 4] f32 {n.xyz, off} of the grid's clip bound (RT_SCENE_VIEW_CLIP_PLANES, read from the device; n <= 8, 0 when none is kept)."""
+        total = lib().rtHipTestSceneView(self.handle, SCENE_VIEW_CLIP_PLANES, 0, 0, None)
+        if total < 0:
+            raise RuntimeError("rtHipTestSceneView failed: " + last_error())
+        out = np.zeros((total, 4), np.float32)
+        if total:
+            self._check(lib().rtHipTestSceneView(self.handle, SCENE_VIEW_CLIP_PLANES, 0, total, _ptr(out)), "rtHipTestSceneView")
+        return out
+
+    def clip_applied(self) -> int:
+        """How many clip planes the planning kernels apply (RT_SCENE_VIEW_CLIP_APPLIED): len(clip_planes()), or 0 with ray_clip = 0."""
+        out = np.zeros(1, np.uint32)
+        self._check(lib().rtHipTestSceneView(self.handle, SCENE_VIEW_CLIP_APPLIED, 0, 1, _ptr(out)), "rtHipTestSceneView")
+        return int(out[0])
 
     def scene_header(self) -> dict:
         return dict(zip(SCENE_VIEW_HEADER, (int(v) for v in self.scene_view("header"))))
