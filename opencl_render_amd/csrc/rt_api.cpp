@@ -5,6 +5,7 @@
 // scene once into HBM, reshapes it on the device (rt_prepare_triangles) and issues ONE launch per frame and GPU.
 // There is no CPU fallback: without a HIP device every entry point that would compute fails with an error text.
 #include "rt_host.h"
+#include "rt_launch.h"
 #include "rt_build_shared.h"
 
 #include <cmath>
@@ -15,52 +16,6 @@
 #include <chrono>
 
 using namespace rthost;
-
-extern "C" hipError_t rtk_launch_trace(const RtDevScene *scene, int counted, hipStream_t stream);
-extern "C" hipError_t rtk_launch_prepare(uint32_t triangleCount, const void *vertex, const void *triIndex, const void *triMaterial,
-                                         const void *triUv, const void *triNormal, float *triRec, float *triShade, hipStream_t stream);
-extern "C" hipError_t rtk_launch_gather_pairs(uint32_t pairCount, const uint32_t *pairTri, const uint32_t *pairInfo, const float *triRec, float *pairRec, hipStream_t stream);
-extern "C" hipError_t rtk_launch_detile(const void *tileBuf, const uint32_t *tileIds, uint32_t tileCount, uint32_t width,
-                                        uint32_t height, uint32_t tilesX, void *planeR, void *planeG, void *planeB, int accumulate, hipStream_t stream);
-
-extern "C" hipError_t rtp_validate(uint32_t T, uint32_t V, uint32_t M, const void *triIndex, const int *triMaterial, uint64_t camListSize,
-                                   const uint32_t *camList, const uint32_t *gridStart, uint64_t gridListSize, const uint32_t *gridList, uint32_t *err,
-                                   hipStream_t stream);
-extern "C" hipError_t rtp_camera_ranges(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount, const uint32_t *camStart,
-                                        const uint32_t *camEnd, uint64_t camListSize, uint32_t *outStart, uint32_t *outEnd, uint32_t *err, hipStream_t stream);
-extern "C" hipError_t rtp_clip_support(const unsigned long long *words, const float *planeTable, const float *normals, uint32_t candidates, uint32_t *keys,
-                                       hipStream_t stream);
-extern "C" hipError_t rtp_dense_grid(const uint32_t *gridStart, const uint32_t *gridList, unsigned long long *words, uint32_t *sparse, uint32_t *pairOrder,
-                                     uint32_t *pairCount, void *scratch, size_t *scratchBytes, hipStream_t stream);
-
-extern "C" hipError_t rtc_scan_bytes(uint32_t n, size_t *bytes);
-extern "C" hipError_t rtc_launch_count(const RtCamMoveArgs *args, hipStream_t stream);
-extern "C" hipError_t rtc_launch_fill(const RtCamMoveArgs *args, hipStream_t stream);
-extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefront *wf, hipStream_t stream);
-extern "C" hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const RtWavefront *wf, uint32_t *passBuf, hipStream_t stream);
-extern "C" hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const RtWavefront *wf, float *surfBuf, hipStream_t stream);
-extern "C" hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next, hipStream_t stream);
-extern "C" hipError_t rtw_launch_answer(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtShadeList *list,
-                                        uint32_t shadeFollows, hipStream_t stream);
-extern "C" hipError_t rtw_launch_shade(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next,
-                                       const RtShadeList *list, hipStream_t stream);
-extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
-extern "C" hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
-extern "C" hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, uint32_t *shadeCount, hipStream_t stream);
-extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefront *wf, int first, hipStream_t stream);
-extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
-                                       uint32_t fastQuotient, hipStream_t stream);
-extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream);
-extern "C" hipError_t rtw_launch_motion_mark(const float *triRec, void *ref, uint32_t triangles, hipStream_t stream);
-extern "C" hipError_t rtw_launch_motion(const RtDevScene *scene, const RtMotionArgs *args, hipStream_t stream);
-extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
-                                           hipStream_t stream);
-extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
-extern "C" hipError_t rtw_launch_bake_points(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
-extern "C" hipError_t rtw_launch_bake_ao(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream);
-extern "C" hipError_t rtw_launch_bake_finish(uint32_t texels, const uint32_t *win, const uint32_t *counter, uint32_t rays, float fill, float *out,
-                                             uint32_t *tri, hipStream_t stream);
-extern "C" hipError_t rtw_launch_bake_dilate(uint32_t W, uint32_t H, const float *src, float *dst, uint32_t last, hipStream_t stream);
 
 namespace {
 thread_local std::string g_error;
@@ -412,20 +367,6 @@ bool same_window(const rtHipSampleWindow &a, const rtHipSampleWindow &b)
 {
     return a.total == b.total && a.first == b.first && a.divisor == b.divisor && a.accumulate == b.accumulate && a.advance == b.advance;
 }
-// Does a frame under `w` follow on what the tile buffer holds?  (Such a frame cannot be rendered again: it is issued watched.)
-bool window_continues(const rtHipSampleWindow &w) { return w.accumulate == 1u && w.first > 0u; }
-// `w` becomes the window of the scene's device description and of every tile group's copy of it (RtDevScene travels by value): host
-// words only, picked up by the next launch.
-void apply_window(rtHipScene *sc, const rtHipSampleWindow &w)
-{
-    auto put = [&](RtDevScene &D) {
-        D.seedStride = w.total; D.sampleFirst = w.first; D.sampleDivisor = w.divisor;
-        D.continuesFrame = window_continues(w) ? 1u : 0u;
-        D.directStore = (D.sampleCount == 1u && !D.continuesFrame) ? 1u : 0u;
-    };
-    put(sc->dev);
-    for (auto &G : sc->groups) put(G.dev);
-}
 
 // wavefront pipeline buffers: worst case every pixel of every sample in a batch becomes a path
 int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
@@ -686,382 +627,7 @@ int scene_build(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds,
     return 0;
 }
 
-// How a round with `rays` rays is laid out (RtRoundMode, rt_device.h): big rounds are ordered by predicted walk length and spread
-// their appends over all queue slices, small ones are cut into segments and keep their entries dense.
-RtRoundMode mode_for(const Tuning &T, uint32_t round, uint64_t rays, uint32_t slicesBefore)
-{
-    RtRoundMode m;
-    // planned where the rays are made (and ordered) when most paths make one: the round behind the primary hits, and any big round
-    m.ordered = (round <= 1u || rays >= T.appendRays) ? 1u : 0u;
-    if (T.orderedFirst == 0u && rays < T.appendRays) m.ordered = 0u;
-    m.segLen = rays >= T.segRays[0] ? T.segLen[0] : (rays >= T.segRays[1] ? T.segLen[1] : (rays >= T.segRays[2] ? T.segLen[2] : (rays >= T.segRays[3] ? T.segLen[3] : T.segLen[4])));
-    if (m.segLen < 1u) m.segLen = 1u;
-    uint32_t small = T.smallSlices;
-    if (small < 1u || small > RT_WF_SHARDS || (small & (small - 1u))) small = 16u;
-    m.slices = rays >= T.sliceRays ? (uint32_t)RT_WF_SHARDS : small;
-    if (m.slices > slicesBefore) m.slices = slicesBefore; // a slice holds at most the paths of its shards: slices only ever merge
-    // rays per workgroup of the trace kernel: about 256 lanes / the segments a ray of this round is expected to be cut into ...
-    // ... and few enough workgroups for all of them to run at once (5 per CU): the round lasts as long as its slowest workgroup
-    // (at most 64: with 128 -- two segments per ray on average fill the 256 lanes -- every second workgroup has to cut coarser, and its
-    // longer segments are the round's duration: 4K, 232 k rays, 403 us against 273)
-    m.groupRays = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(16, ((rays + 1099) / 1100 + 15) / 16 * 16));
-    if (T.groupRays >= 1u && T.groupRays <= 128u) m.groupRays = T.groupRays;
-    return m;
-}
-
-// TEST ONLY (tuning key visit_log; include/raytrace_hip.h, rtHipTestRoundVisits).  Round r of group G, once its trace launch is issued on
-// `on` and before logic(r) consumes its answers and logic(r + 1) overwrites its entries: wait for the stream, read the round's queues back
-// and add what they hold to sc->visitLog[r].  The entries are the ones the planning kernels wrote (rt_device.h, RtWavefront::ent).
-int log_round_visits(rtHipScene *sc, rtHipScene::Group &G, uint32_t r, const RtRoundMode &mode, hipStream_t on)
-{
-    const RtWavefront &W = G.wf;
-    HIP_OK(hipStreamSynchronize(on));
-    std::vector<uint32_t> ctl(RT_WF_CTL_WORDS);
-    std::vector<float> planes(3 * (RT_GRID_DIV + 1));
-    HIP_OK(hipMemcpy(ctl.data(), W.ctl + (size_t)(r % 3) * RT_WF_CTL_WORDS, sizeof(uint32_t) * RT_WF_CTL_WORDS, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(planes.data(), G.dev.boxMin, sizeof(float) * planes.size(), hipMemcpyDeviceToHost));
-    const uint32_t cap = W.capacity, sliceCap = cap / mode.slices;
-    const uint32_t extra = mode.ordered ? std::min(ctl[RT_WF_CTL_EXTRA], W.extraCap) : 0u;
-    std::vector<uint4> ent((size_t)4 * (2 * (size_t)cap + extra));
-    std::vector<unsigned long long> key(2 * (size_t)cap);
-    std::vector<uint2> pathOf(cap);
-    HIP_OK(hipMemcpy(ent.data(), W.ent[r & 1u], sizeof(uint4) * ent.size(), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(key.data(), W.hitKey[r & 1u], sizeof(unsigned long long) * key.size(), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(pathOf.data(), W.pathOf[r & 1u], sizeof(uint2) * pathOf.size(), hipMemcpyDeviceToHost));
-    auto cell_of = [&](const float p[3]) { // (GetBoxAddress, as rt_wavefront.hip's cell_of)
-        uint32_t c[3] = { 0, 0, 0 };
-        for (int w = 0; w < 3; ++w)
-            for (int div = RT_GRID_DIV / 2; div >= 1; div /= 2)
-                if (planes[(size_t)w * (RT_GRID_DIV + 1) + c[w] + div] < p[w]) c[w] += div;
-        return c[0] | c[1] << 8 | c[2] << 16;
-    };
-    // the cells an entry's walk makes if it hits nothing (plan_ray: one axis by one cell per step)
-    auto visits_of = [&](const uint4 *e) -> uint64_t {
-        const uint32_t start = e[0].y & 0xffffffu;
-        uint32_t last = e[0].z;
-        if (last == 0xffffffffu) { // no end cell: the walk leaves the box, at the smallest of the three wall crossings
-            float o[3], d[3], te = HUGE_VALF;
-            memcpy(o, &e[2], 12); memcpy(d, &e[3], 12);
-            for (int w = 0; w < 3; ++w)
-                if (d[w] != 0.f) { const float t = (planes[(size_t)w * (RT_GRID_DIV + 1) + (0.f <= d[w] ? RT_GRID_DIV : 0)] - o[w]) / d[w]; if (t < te) te = t; }
-            if (!(te < HUGE_VALF)) return 1;
-            const float to[3] = { o[0] + te * d[0], o[1] + te * d[1], o[2] + te * d[2] };
-            last = cell_of(to);
-        }
-        uint64_t v = 1;
-        for (int w = 0; w < 3; ++w) v += (uint64_t)std::abs((int)((last >> 8 * w) & 255u) - (int)((start >> 8 * w) & 255u));
-        return v;
-    };
-    uint64_t *out = sc->visitLog[r].data();
-    out[RT_ROUND_VISIT_ORDERED] = mode.ordered;
-    auto kind_of = [&](uint32_t q) { return q >= cap ? 2u : (pathOf[q].y != 0xffffffffu ? 0u : 1u); }; // q: a ray's queue index
-    for (uint32_t look = 0; look < 2; ++look)
-        for (uint32_t s = 0; s < mode.slices; ++s) {
-            const uint32_t n = std::min(ctl[RT_WF_CTL_COUNTS + look * RT_WF_SHARDS + s], sliceCap), base = look * cap + s * sliceCap;
-            for (uint32_t q = base; q < base + n; ++q) {
-                uint64_t *f = out + RT_ROUND_VISIT_RAYS + 3 * kind_of(q);
-                f[0] += 1;
-                f[1] += key[q] != ~0ull;
-                if (!mode.ordered) continue;
-                f[2] += visits_of(&ent[(size_t)4 * q]);
-                out[RT_ROUND_VISIT_ENTRIES] += 1;
-                out[RT_ROUND_VISIT_ENDED] += ent[(size_t)4 * q].z != 0xffffffffu;
-            }
-        }
-    for (uint32_t i = 0; i < extra; ++i) { // region B: the further segments of cut rays, x = the ray's queue index (all ones: an unused reservation)
-        const uint4 *e = &ent[(size_t)4 * (2 * (size_t)cap + i)];
-        if (e[0].x >= 2 * cap) continue;
-        out[RT_ROUND_VISIT_RAYS + 3 * kind_of(e[0].x) + 2] += visits_of(e);
-        out[RT_ROUND_VISIT_ENTRIES] += 1;
-        out[RT_ROUND_VISIT_ENDED] += e[0].z != 0xffffffffu;
-    }
-    return 0;
-}
-
-// One frame through the staged pipeline: per sample batch and tile group -- primary, then rounds of (scatter,) trace, logic until
-// no path is waiting for the grid, then the ordered accumulate.  The round count is data dependent.
-//
-// WATCHED batch (the first batch of a scene's first frame, or Tuning::blocking): rounds are issued in chunks and the queue length
-// is read back after every chunk (one small pinned copy + stream sync per chunk and group).  It leaves a PLAN behind: the number of
-// rounds the batch needed and, per round, its rays, its longest queue slice and its further segments (RtWavefront::roundLog).
-// PLANNED batches (every later frame, and the further batches of a watched frame): the plan's rounds are issued back to back with
-// the layouts and grid sizes the plan implies and NO host synchronisation -- whatever the caller enqueues behind the frame (the tile
-// gather) follows immediately.  The last kernel of a batch (wf_status_kernel) adds the number of paths still waiting to a mapped
-// host word; frame_finish() looks at it after the caller's own synchronisation.  A non-zero count means the plan was too short for
-// this frame (the frames of a scene are deterministic, so that only happens when something about the frame changed, or when a later
-// sample batch needs more than the first one did): the frame is rendered again, every batch watched, and the caller is told, so
-// that work enqueued behind the incomplete frame can be redone.
-// How a round's entries are laid out (ordered or not, cut how finely, how many queue slices) is decided HERE, before the round exists,
-// from the plan -- or, in a watched batch, from a guess: the layout changes when cells are visited, never what is found.
-// Groups run concurrently on their own streams, forked from and joined to `st`; with stage timing on they run one after the
-// other on `st`, so that a kernel's measured duration is its own.
-int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery)
-{
-    const Tuning &T = sc->tune;
-    auto stage = [&](int which, hipStream_t on, auto &&launch) -> hipError_t {
-        if (!sc->stageTiming) return launch();
-        if (sc->stageEventsUsed == sc->stageEvents.size()) {
-            rtHipScene::StageEvent e{};
-            hipError_t er = e.a.make();
-            if (er != hipSuccess) return er;
-            er = e.b.make();
-            if (er != hipSuccess) return er;
-            sc->stageEvents.push_back(std::move(e));
-        }
-        rtHipScene::StageEvent &e = sc->stageEvents[sc->stageEventsUsed++];
-        e.stage = which;
-        hipError_t er = hipEventRecord(e.a, on);
-        if (er != hipSuccess) return er;
-        er = launch();
-        if (er != hipSuccess) return er;
-        return hipEventRecord(e.b, on);
-    };
-    if (T.visitLog) sc->visitLog.assign(RT_WF_ROUND_LOG, {});
-    const bool serial = sc->stageTiming || sc->groups.size() == 1;
-    auto streamOf = [&](size_t g) { return (serial || g == 0) ? st : sc->groups[g].stream; };
-    if (!serial) {
-        HIP_OK(hipEventRecord(sc->forkEvent, st));
-        for (size_t g = 1; g < sc->groups.size(); ++g) HIP_OK(hipStreamWaitEvent(sc->groups[g].stream, sc->forkEvent, 0));
-    }
-    const bool watchedFrame = forceDiscovery || sc->blocking || sc->planRounds == 0;
-    bool planned = !watchedFrame; // per batch: a watched frame's further batches follow its first batch's plan (Tuning::batchPlan)
-    uint32_t planRounds = sc->planRounds;
-    // the layout of round r: from the plan, or (watched batch) from what the round is assumed to hold
-    auto round_mode = [&](rtHipScene::Group &G, uint32_t r) -> RtRoundMode {
-        if (G.modes.size() <= r) {
-            const uint32_t before = G.modes.empty() ? (uint32_t)RT_WF_SHARDS : G.modes.back().slices;
-            uint64_t rays = G.guessRays;
-            if (planned) rays = r < RT_WF_ROUND_LOG ? G.plan[r].rays : 0;
-            else G.guessRays = std::max<uint64_t>(G.guessRays / 4, 1); // (watched: a round is assumed to hold a quarter of the one before)
-            G.modes.resize(r + 1, mode_for(T, r, rays, before));
-        }
-        return G.modes[r];
-    };
-    auto trace_blocks = [&](rtHipScene::Group &G, uint32_t r, const RtRoundMode &m) -> uint32_t {
-        // worst case: every queue slot in use -- an ordered round takes 256 entries per workgroup, any other mode.groupRays rays of
-        // one queue slice (every slice's last piece may be a partial one)
-        const uint64_t worst = m.ordered ? G.traceBlocks : 2ull * G.wf.capacity / m.groupRays + 2ull * m.slices;
-        if (!planned || r >= RT_WF_ROUND_LOG) return (uint32_t)std::min<uint64_t>(worst, 0x7fffffffu);
-        if (T.planGridTiny) return 1;
-        // the same frame gave this many rays last time: a tenth more plus a few, never more than the worst case
-        // (an ordered round's further segments: as many as last time if the cut is the same -- a watched frame guesses the round's size
-        // and with it the cut -- and at most RT_WF_MAXSEG - 1 per ray whatever the cut)
-        const uint64_t rays = G.plan[r].rays;
-        const uint64_t extra = std::min<uint64_t>(G.wf.extraCap, G.plan[r].extraSegLen == m.segLen ? G.plan[r].extra : (m.segLen >= 4096u ? 0 : rays * 11));
-        const uint64_t want = m.ordered ? ((rays + extra) * 11 / 10 + 255) / 256 + 8 : (rays * 11 / 10 + m.groupRays - 1) / m.groupRays + 2ull * m.slices + 8;
-        return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(want, worst), 1);
-    };
-    // workgroups of a split round's shade pass (0: not launched).  Its waves stride over their slice's list, so any whole number of waves
-    // per slice is enough; a planned frame launches as many as the list the plan logged fills once -- a tenth more plus a few, like a
-    // round's rays, spread over the slices -- and a watched one the logic kernel's grid.
-    auto shade_blocks = [&](rtHipScene::Group &G, uint32_t r, const RtRoundMode &m) -> uint32_t {
-        if (!planned || r >= RT_WF_ROUND_LOG) return G.logicBlocks;
-        const uint64_t listed = T.planShadeSkip ? 0 : G.plan[r].shade;
-        if (listed == 0) return 0;
-        const uint64_t perSlice = (listed * 11 / 10 + m.slices - 1) / m.slices + 8;
-        const uint64_t waves = (perSlice + 63) / 64 * m.slices, unit = RT_WF_SHARDS / 4;
-        return (uint32_t)std::min<uint64_t>(G.logicBlocks, ((waves + 3) / 4 + unit - 1) / unit * unit);
-    };
-    uint64_t splitRounds = 0;
-    auto issue_round = [&](rtHipScene::Group &G, hipStream_t on) -> int {
-        const uint32_t r = G.rounds;
-        const RtRoundMode mode = r > 0 ? round_mode(G, r) : RtRoundMode{ 0u, 4096u, 64u, (uint32_t)RT_WF_SHARDS };
-        if (r > 0) { // the entries appended by logic(r-1): order them if the round is an ordered one, then walk the grid
-            if (mode.ordered) HIP_OK(stage(4, on, [&] { return rtw_launch_scatter(&G.wf, r, G.queueBlocks, &mode, on); }));
-            HIP_OK(stage(2, on, [&] { return rtw_launch_trace(&G.dev, &G.wf, r, trace_blocks(G, r, mode), &mode, on); }));
-            if (T.visitLog && r < RT_WF_ROUND_LOG && log_round_visits(sc, G, r, mode, on) != 0) return -1;
-        }
-        const RtRoundMode next = round_mode(G, r + 1);
-        // A later round of the opaque-diffuse class with look-ahead on (Tuning::logicSplit): the answers as a stream (wf_answer_kernel), then the
-        // paths whose bounce hit something shaded by dense waves (wf_shade_kernel).  A planned frame sizes the shade launch from the list the plan
-        // logged and skips it where that was empty; the answer kernel is told, and raises RT_WF_ERR_GRID if it lists a path all the same.
-        if (r > 0 && T.logicSplit && G.wf.lookAhead && G.dev.pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE) {
-            const uint32_t shadeBlocks = shade_blocks(G, r, mode);
-            ++splitRounds;
-            HIP_OK(stage(1, on, [&] { return rtw_launch_answer(&G.dev, &G.wf, r, G.logicBlocks, mode.slices, &G.shade, shadeBlocks ? 1u : 0u, on); }));
-            if (shadeBlocks) HIP_OK(stage(1, on, [&] { return rtw_launch_shade(&G.dev, &G.wf, r, shadeBlocks, mode.slices, &next, &G.shade, on); }));
-        } else
-            HIP_OK(stage(1, on, [&] { return rtw_launch_logic(&G.dev, &G.wf, r, G.logicBlocks, mode.slices, &next, on); }));
-        ++G.rounds;
-        return 0;
-    };
-    // Watched: rounds are issued in chunks without looking at the queue.  A one-bounce scene needs exactly three logic rounds
-    // (shade the primary hits | consume shadow + bounce answers, shade the bounce hits | consume their shadow answers) with a
-    // trace before the last two, so a chunk is 3 rounds.
-    auto issue_chunk = [&](rtHipScene::Group &G, hipStream_t on) -> int {
-        for (uint32_t k = 0; k < 3 && G.rounds < RT_WF_MAX_ROUNDS; ++k)
-            if (issue_round(G, on) != 0) return -1;
-        HIP_OK(hipMemcpyAsync(G.hostCount, G.wf.ctl + (G.rounds % 3) * RT_WF_CTL_WORDS + RT_WF_CTL_COUNTS, sizeof(uint32_t) * RT_WF_SHARDS, hipMemcpyDeviceToHost, on)); // main slices
-        return 0;
-    };
-    auto device_error = [&](rtHipScene::Group &G) -> int {
-        if (const uint32_t err = G.hostStatus[RT_WF_STATUS_ERROR]) {
-            G.hostStatus[RT_WF_STATUS_ERROR] = 0u;
-            return fail("wavefront pipeline: device error 0x%x%s -- the frame is invalid", err,
-                        (err & RT_WF_ERR_SPIN) ? " (wf_trace_kernel's walk guard tripped: rays were abandoned)" : "");
-        }
-        return 0;
-    };
-    // NORMAL / ALBEDO on: the batch's samples are summed per pixel in the primary stage's bracket (the batch with sampleBase 0 starts
-    // the sums from zero, so planned and redone frames need no memset)
-    auto launch_surface = [&](rtHipScene::Group &G, hipStream_t on) {
-        return rtw_launch_surface_passes(&G.dev, &G.wf, sc->surfBuf + (size_t)G.slot0 * RT_SURF_WORDS * RT_TILE_PIXELS, on);
-    };
-    uint64_t rounds = 0;
-    bool anyPlannedBatch = false;
-    const uint32_t sampleCount = sc->dev.sampleCount;
-    for (uint32_t base = 0; base < sampleCount; base += sc->samplesPerBatch) {
-        for (size_t g = 0; g < sc->groups.size(); ++g) {
-            rtHipScene::Group &G = sc->groups[g];
-            const hipStream_t on = streamOf(g);
-            G.wf.sampleBase = base;
-            G.wf.samplesInBatch = std::min<uint32_t>(sc->samplesPerBatch, sampleCount - base);
-            G.rounds = 0;
-            G.modes.clear();
-            G.guessRays = (uint64_t)(G.slot1 - G.slot0) * RT_TILE_PIXELS * G.wf.samplesInBatch; // round 1 of a watched batch: as if every pixel were a path
-            if (!G.ctlClean) {
-                HIP_OK(hipMemsetAsync(G.wf.ctl, 0, sizeof(uint32_t) * (size_t)3 * RT_WF_CTL_WORDS, on));
-                HIP_OK(hipMemsetAsync(G.shade.count, 0, sizeof(uint32_t) * (size_t)3 * RT_WF_SHARDS, on));
-            }
-            G.ctlClean = false;
-            if (!planned) memset(G.hostLog, 0, sizeof(uint4) * RT_WF_ROUND_LOG); // (nothing of this group is in flight: the batch before was waited for)
-            if (sc->passBuf) {
-                // passes on: with several samples per pixel the group's hit counters (one 64 KiB plane per slot) start at zero in every
-                // frame -- in-stream, so planned and redone frames alike; a one-sample frame's kernel stores them, and sample 1 rewrites
-                // every depth and triangle word
-                uint32_t *pass = sc->passBuf + (size_t)G.slot0 * RT_PASS_WORDS * RT_TILE_PIXELS;
-                HIP_OK(stage(0, on, [&] {
-                    if (base == 0 && sampleCount > 1) {
-                        const hipError_t er = hipMemset2DAsync(pass + RT_PASS_HITS * RT_TILE_PIXELS, (size_t)RT_PASS_WORDS * RT_TILE_PIXELS * 4, 0,
-                                                               (size_t)RT_TILE_PIXELS * 4, G.slot1 - G.slot0, on);
-                        if (er != hipSuccess) return er;
-                    }
-                    const hipError_t er = rtw_launch_primary_passes(&G.dev, &G.wf, pass, on);
-                    return (er != hipSuccess || !sc->surfBuf) ? er : launch_surface(G, on);
-                }));
-            } else HIP_OK(stage(0, on, [&] {
-                const hipError_t er = rtw_launch_primary(&G.dev, &G.wf, on);
-                return (er != hipSuccess || !sc->surfBuf) ? er : launch_surface(G, on);
-            }));
-            if (planned) {
-                while (G.rounds < planRounds)
-                    if (issue_round(G, on) != 0) return -1;
-                // (the shade lists' lengths are zeroed with the control words where the batch can have run split rounds)
-                const bool split = T.logicSplit && G.wf.lookAhead && G.dev.pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE;
-                HIP_OK(rtw_launch_status(&G.wf, G.rounds, split ? G.shade.count : nullptr, on));
-                G.ctlClean = true;
-            } else if (issue_chunk(G, on) != 0) return -1;
-        }
-        for (size_t g = 0; g < sc->groups.size(); ++g) {
-            rtHipScene::Group &G = sc->groups[g];
-            const hipStream_t on = streamOf(g);
-            if (!planned) {
-                for (;;) {
-                    HIP_OK(hipStreamSynchronize(on));
-                    if (device_error(G) != 0) return -1;
-                    uint64_t waiting = 0;
-                    for (int i = 0; i < RT_WF_SHARDS; ++i) waiting += G.hostCount[i];
-                    if (waiting == 0) break;
-                    if (G.rounds >= RT_WF_MAX_ROUNDS) return fail("wavefront pipeline: more than %d rounds", RT_WF_MAX_ROUNDS);
-                    G.guessRays = 2 * waiting; // the next round holds at most two rays per waiting path
-                    if (issue_chunk(G, on) != 0) return -1;
-                }
-                // the plan for the batches and frames to come: the rounds that had anything to trace (+ the logic round that consumed
-                // the last answers), and every round's sizes
-                const uint4 *log = G.hostLog; // (mapped host memory; the stream was synchronised in the loop above)
-                uint32_t needed = 1; // logic(0) always runs
-                for (uint32_t r = 1; r < std::min<uint32_t>(G.rounds, RT_WF_ROUND_LOG); ++r)
-                    if (log[r].x) needed = r + 1;
-                if (G.rounds > RT_WF_ROUND_LOG) needed = G.rounds;
-                G.roundsNeeded = std::max(G.roundsNeeded, needed);
-                for (uint32_t r = 0; r < RT_WF_ROUND_LOG; ++r) {
-                    rtHipScene::Group::RoundPlan &N = G.planNext[r]; // the maximum over the watched batches
-                    N.rays = std::max(N.rays, log[r].x);
-                    N.shade = std::max(N.shade, log[r].w);
-                    const uint32_t seg = r < G.modes.size() ? G.modes[r].segLen : 4096u;
-                    if (N.extraSegLen != seg && N.extraSegLen != 0u) N.extraSegLen = 0xffffffffu; // (batches cut differently: no figure)
-                    else { N.extraSegLen = seg; N.extra = std::max(N.extra, log[r].z); }
-                }
-            } else anyPlannedBatch = true;
-            rounds = std::max<uint64_t>(rounds, G.rounds);
-            if (!G.dev.directStore) // a one-sample frame that starts from zero: its pixels were written by the kernels that finished them
-                HIP_OK(stage(3, on, [&] { return rtw_launch_accum(&G.dev, &G.wf, (base == 0 && !G.dev.continuesFrame) ? 1 : 0, on); }));
-        }
-        // a watched batch knows here that its rounds are over: tell whoever polls GetProgress (raytrace.c:566-587)
-        if (!planned && sc->progress)
-            sc->progress->store(sc->progressBase + sc->progressSpan * (float)std::min<uint64_t>(sampleCount, (uint64_t)base + sc->samplesPerBatch) / (float)sampleCount,
-                                std::memory_order_relaxed);
-        // A watched frame's further batches: the same pixels with other sample ids -- statistically the same rounds.  They are issued from
-        // the plan the batches so far left (a fifth more than the largest of them saw, see trace_blocks) and verified like any planned
-        // frame; should one of them need more, frame_finish renders the whole frame again, every batch watched.
-        if (!planned && !forceDiscovery && !sc->blocking && T.batchPlan && base + sc->samplesPerBatch < sampleCount) {
-            uint32_t need = 1;
-            for (auto &G : sc->groups) {
-                need = std::max(need, G.roundsNeeded);
-                for (uint32_t r = 0; r < RT_WF_ROUND_LOG; ++r) {
-                    G.plan[r] = G.planNext[r];
-                    G.plan[r].rays += G.plan[r].rays / 10; G.plan[r].extra += G.plan[r].extra / 10; G.plan[r].shade += G.plan[r].shade / 10;
-                }
-            }
-            planRounds = need + 1; // (one spare round: a later batch's deepest path may go one bounce further)
-            planned = true;
-        }
-    }
-    if (watchedFrame) { // adopt what this frame's watched batches needed (the maximum over batches and groups)
-        uint32_t need = 1;
-        for (auto &G : sc->groups) {
-            need = std::max(need, G.roundsNeeded);
-            for (uint32_t r = 0; r < RT_WF_ROUND_LOG; ++r) { G.plan[r] = G.planNext[r]; G.planNext[r] = rtHipScene::Group::RoundPlan(); }
-            G.roundsNeeded = 0;
-        }
-        if (anyPlannedBatch && sampleCount > sc->samplesPerBatch) need += 1; // (the spare round of the further batches, kept for the frames to come)
-        sc->planRounds = T.planRounds ? std::min(need, T.planRounds) : need;
-    }
-    if (anyPlannedBatch) sc->unverified = true;
-    if (!serial)
-        for (size_t g = 1; g < sc->groups.size(); ++g) {
-            HIP_OK(hipEventRecord(sc->groups[g].done, sc->groups[g].stream));
-            HIP_OK(hipStreamWaitEvent(st, sc->groups[g].done, 0));
-        }
-    sc->roundsLast = rounds;
-    sc->splitRoundsLast = splitRounds;
-    return 0;
-}
-
 } // namespace
-
-// After the caller's synchronisation of `st`: were the planned frames since the last call complete?  If not, the LAST frame
-// is rendered again with the queue watched (earlier incomplete frames were overwritten by it anyway).  *redone (optional)
-// = 1 when that happened: whatever was enqueued behind the incomplete frame saw unfinished tiles.
-int rthost::frame_finish(rtHipScene *sc, hipStream_t st, int *redone)
-{
-    if (redone) *redone = 0;
-    if (!sc->unverified) return 0;
-    HIP_OK(hipStreamSynchronize(st));
-    for (auto &G : sc->groups)
-        if (G.stream) HIP_OK(hipStreamSynchronize(G.stream));
-    sc->unverified = false;
-    uint64_t waiting = 0;
-    for (auto &G : sc->groups) {
-        if (const uint32_t err = G.hostStatus[RT_WF_STATUS_ERROR]) {
-            G.hostStatus[RT_WF_STATUS_ERROR] = 0u;
-            if (err & ~RT_WF_ERR_GRID)
-                return fail("wavefront pipeline: device error 0x%x%s -- the frame is invalid", err,
-                            (err & RT_WF_ERR_SPIN) ? " (wf_trace_kernel's walk guard tripped: rays were abandoned)" : "");
-            waiting += 1; // a planned trace grid was too small: same remedy as a plan with too few rounds
-        }
-        waiting += G.hostStatus[RT_WF_STATUS_WAITING];
-        G.hostStatus[RT_WF_STATUS_WAITING] = 0u;
-    }
-    if (waiting == 0) {
-        return 0;
-    }
-    if (redone) *redone = 1;
-    apply_window(sc, sc->lastWindow); // the window that frame had; the scene's next window has moved on already and stays where it is
-    if (render_wavefront(sc, st, true) != 0) return -1;
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
 
 // A device pointer a kernel may read or write `bytes` from: device memory of `device`, 16-byte aligned where the kernel loads 16 bytes at
 // a time, and inside one allocation.  A host pointer must never reach a kernel: its fault takes the whole GPU down.
@@ -2381,8 +1947,6 @@ int rtHipTestPathClass(const rtHipScene *scene)
     if (!scene) return -1;
     return (int)scene->dev.pathClass;
 }
-
-int rt_shade_kat_run(const RtDevScene *scene, int op, uint32_t count, const void *in, void *out); // rt_kat.hip
 
 int rtHipTestShadeKat(const rtHipScene *scene, int op, uint32_t count, const void *in, void *out)
 {

@@ -22,6 +22,7 @@
 
 #include "rt_build_shared.h"
 #include "rt_camera_move.h"
+#include "rt_launch.h"
 
 using rtbuild::Camera;
 using rtbuild::F2;

@@ -15,6 +15,8 @@
 
 #include <stdint.h>
 
+#include "rt_launch.h"
+
 namespace {
 
 constexpr uint32_t PATCH = 16; // 16x16 pixels per workgroup of the iteration kernels

@@ -151,7 +151,7 @@ struct RtDevScene {
 #define RT_WF_ROUND_LOG 64     // rounds of a batch that are logged for the launch plan (RtWavefront::roundLog)
 #define RT_WF_ERR_SPIN 1u     // wf_trace_kernel's walk guard tripped: rays were abandoned, the frame is invalid
 #define RT_WF_ERR_GRID 2u     // a planned frame's trace grid was smaller than the round's entries: entries were not traced; the host renders
-                              // the frame again with the worst-case grid (rt_api.cpp, frame_finish).  Also: a planned frame skipped a shade launch
+                              // the frame again with the worst-case grid (rt_frame.cpp, frame_finish).  Also: a planned frame skipped a shade launch
                               // (the plan said no bounce hit anything in that round) and the round listed a path for it
 #define RT_WF_ERR_SPLIT 4u    // wf_answer_kernel met a path that is not of the shape it knows (opaque-diffuse class, look-ahead on): the frame is invalid
 // per-round control words, three sets used in turn like the queue lengths (round r uses set r % 3): logic(r-1) fills set r,

@@ -2,40 +2,12 @@
 // "VARIANCE-GUIDED FILTER"): parameter checks, the device and host entry points, and the resident scene's calls with their buffers.
 // The kernels are in rt_denoise.hip, rt_temporal.hip and rt_variance.hip; the scene and what else the host side shares, in rt_host.h.
 #include "rt_host.h"
+#include "rt_launch.h"
 #include "rt_overlap.h"
 
 #include <cmath>
 
 using namespace rthost;
-
-// rt_denoise.hip
-extern "C" hipError_t rtd_launch_guides(uint32_t n, const float *colour, const float *normal, const float *albedo, void *c0, void *g0, void *g1,
-                                        hipStream_t stream);
-extern "C" hipError_t rtd_launch_iteration(uint32_t W, uint32_t H, int h, float ic, float ia, uint32_t E, const void *cin, const void *g0,
-                                           const void *g1, void *cout, hipStream_t stream);
-extern "C" hipError_t rtd_launch_output(uint32_t n, const void *c, float *out, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
-extern "C" hipError_t rtd_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount, const uint16_t *tileBuf,
-                                        const float *surf, float S, float *colour, float *normal, float *albedo, hipStream_t stream);
-// rt_temporal.hip
-extern "C" hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
-                                            const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
-                                            const uint32_t *histTriangle, float *outColour, float *outCount, float maxHistory,
-                                            float depthTolerance, hipStream_t stream);
-extern "C" hipError_t rtt_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount,
-                                        const uint16_t *tileBuf, float *colour, hipStream_t stream);
-extern "C" hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
-// rt_variance.hip
-extern "C" hipError_t rtv_launch_moments(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
-                                         const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
-                                         const uint32_t *histTriangle, const float *histMoments, float *outColour, float *outCount,
-                                         float *outMoments, float *outVariance, float maxHistory, float depthTolerance, hipStream_t stream);
-extern "C" hipError_t rtv_launch_estimate(uint32_t W, uint32_t H, const float *colour, const float *normal, const float *albedo,
-                                          const float *moments, const float *count, float spatialBelow, float ia, uint32_t E, void *s0,
-                                          void *g0, void *g1, hipStream_t stream);
-extern "C" hipError_t rtv_launch_iteration(uint32_t W, uint32_t H, int h, float ls, float floor_, float ia, uint32_t E, const void *sin,
-                                           void *il, const void *g0, const void *g1, void *sout, hipStream_t stream);
-extern "C" hipError_t rtv_launch_output(uint32_t n, const void *s, float *out, float *outVariance, uint16_t *outR, uint16_t *outG,
-                                        uint16_t *outB, hipStream_t stream);
 
 // ---- what the filters share ------------------------------------------------------------------------------------------------------
 // The arrays of a device entry point, in the order its refusals name them: no written array overlaps another, `stream` (or the null

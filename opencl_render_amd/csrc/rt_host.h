@@ -1,9 +1,11 @@
-// rt_host.h -- what the host translation units of libraytrace_hip.so share (rt_api.cpp: scenes, frames, queries; rt_filters.cpp: the
-// image-space filters): the error text, the tuning values, device scratch and staging, and the resident scene itself.  Internal: nothing
-// here is part of the C ABI of include/raytrace_hip.h.
+// rt_host.h -- what the host translation units of libraytrace_hip.so share (rt_api.cpp: scenes, queries; rt_frame.cpp: the frame loop;
+// rt_filters.cpp: the image-space filters): the error text, the tuning values (rt_tuning.h), device scratch and staging, and the resident
+// scene itself.  Internal: nothing here is part of the C ABI of include/raytrace_hip.h.
 #pragma once
 #include "raytrace_hip.h"
 #include "rt_device.h"
+#include "rt_tuning.h"
+#include "rt_frame_plan.h"
 #include "rt_ray_clip.h"
 #include "rt_camera_move.h"
 #include "rt_geometry_move.h"
@@ -36,47 +38,6 @@ RT_INTERNAL int fail(const char *fmt, ...);
         hipError_t e_ = (expr);                                                                        \
         if (e_ != hipSuccess) return rthost::fail("%s failed: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
-
-// Tuning values and test hooks.  The library reads NO environment variables: a plugin host's environment must not be able to
-// make frames slower, redo themselves or fail.  Everything here is set through rtHipTune() (include/raytrace_hip.h, test / tuning
-// entry point; the Python stub maps RT_* variables of ITS process onto it for the sweep scripts) and applies to scenes built
-// afterwards.
-struct Tuning {
-    uint32_t stageMb = 32;          // size of each of the two pinned staging buffers of an upload
-    uint32_t extraFactor = 6;       // region B of the entry arrays (further segments of cut rays), in units of the path capacity
-    uint64_t stateMb = 0;           // path-state budget per sample batch (0 = 24 GB, never more than a third of free memory); tests force several batches
-    uint32_t groups = 1;            // concurrent tile groups per instance (measured: no gain once rays are cut into segments)
-    uint32_t lookAhead = 1;         // 0: one ray in flight per path
-    uint32_t segLen[5] = { 4096u, 384u, 96u, 64u, 16u }; // aimed-at cell visits per segment for rounds with >= segRays[0] | [1] | [2] | [3] | fewer rays
-    uint32_t segRays[4] = { 700000u, 300000u, 100000u, 30000u };
-    uint32_t fastQuotient = 1;
-    uint32_t spinLimit = 16384;     // a ray makes at most 766 cell visits = 154 walk phases; lowered by the test of the guard's error path
-    uint32_t appendRays = 300000;   // later rounds with fewer rays are not ordered: the trace kernel plans and cuts their rays itself (RtRoundMode)
-    uint32_t orderedFirst = 1;      // 0: round 1 follows the same rule (tests: the trace kernel's planning on dense rounds)
-    uint32_t sliceRays = 0;         // rounds with fewer rays use smallSlices queue slices per kind instead of RT_WF_SHARDS (off: a round's appends want
-                                    // many counters -- 16 slices cost the logic kernel of a 58 k-ray round 17 us -- and the trace kernel packs its pieces anyway)
-    uint32_t smallSlices = 16;
-    uint32_t groupRays = 0;         // rays per workgroup of the trace kernel in rounds that are not ordered (0 = by segment length)
-    uint32_t blocking = 0;          // 1: every frame watches its queue (no launch plan)
-    uint32_t planRounds = 0;        // test hook: planned frames issue at most this many rounds, so that the too-short-plan path runs
-    uint32_t planGridTiny = 0;      // test hook: planned trace grids of one workgroup, so that the too-small-grid path runs
-    uint32_t planShadeSkip = 0;     // test hook: planned frames launch no shade pass (as if the plan's shade lists were empty), so that the listed-but-skipped path runs
-    uint32_t visitLog = 0;          // test hook: every frame waits after each round's trace launch and the host reads the round back (rtHipTestRoundVisits)
-    uint32_t pipeline = RT_HIP_PIPELINE_WAVEFRONT;
-    uint32_t timing = 0;            // 1: where the time of a scene build / a RaytraceAll call goes (stderr)
-    uint32_t virtualDevices = 0;    // test hook: the all-GPUs id deals the tiles over this many instances on the devices that are there
-    uint32_t cache = 1;             // 0: RaytraceAll builds and frees per call, like the reference
-    uint32_t batchPlan = 1;         // 1: the sample batches after a watched frame's first are issued from that batch's launch plan
-    uint32_t logicClass = 1;        // 0: every scene's paths run on the general logic kernel; 1: the kernel of the scene's path class (path_class_of)
-    uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
-    uint32_t rayClip = 1;           // 1: grid rays without a far end stop where they leave the scene's clip bound (rt_ray_clip.h); 0: at the grid's wall
-    uint32_t logicSplit = 1;        // 1: rounds >= 1 of the opaque-diffuse class (look-ahead on) run wf_answer_kernel + wf_shade_kernel; 0: wf_logic_kernel
-    uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
-    uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
-    uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
-    uint32_t aoSamples = 1u << 20;  // pixel samples per chunk of the ambient occlusion calls (32 bytes each of scene-owned scratch)
-    uint32_t bakeTexels = 1u << 20; // texels per chunk of the ambient occlusion bake (32 bytes each of scene-owned scratch)
-};
 
 // Device scratch of a scene build: freed when the scope ends, whichever way it ends.
 struct DevScratch {
@@ -238,12 +199,8 @@ struct rtHipScene {
         uint32_t slot0 = 0, slot1 = 0;  // this group's range of the instance's tile slots
         // launch plan (render_wavefront): what the last discovery frame needed
         uint32_t roundsNeeded = 0;
-        // per round: rays (entries in region A), the longest queue slice, entries in region B -- the maximum over the watched batches
-        // rays of the round, and -- an ordered round -- the further segments of its cut rays under the cut it was logged with
-        // and -- a split logic round -- the paths it listed for its shade pass
-        struct RoundPlan { uint32_t rays = 0, extra = 0, extraSegLen = 0, shade = 0; };
         rthost::Pinned<uint4> hostLog;  // pinned + mapped: RtWavefront::roundLog, written by the kernels, read by the host after a sync
-        RoundPlan plan[RT_WF_ROUND_LOG], planNext[RT_WF_ROUND_LOG];
+        rthost::RoundPlan plan[RT_WF_ROUND_LOG], planNext[RT_WF_ROUND_LOG]; // (rt_frame_plan.h)
         std::vector<RtRoundMode> modes; // how the rounds of the batch being issued are laid out (modes[r] is decided when logic(r-1) is launched)
         uint64_t guessRays = 0;         // watched batches: what the next round is assumed to hold
     };
@@ -440,8 +397,26 @@ inline int scene_event(Event &ev, unsigned flags, const char *who)
     return e == hipSuccess ? 0 : fail("%s: hipEventCreate failed: %s", who, hipGetErrorString(e));
 }
 
-// rt_api.cpp
+// Sample windows (include/raytrace_hip.h, "SAMPLE WINDOWS").
+// Does a frame under `w` follow on what the tile buffer holds?  (Such a frame cannot be rendered again: it is issued watched.)
+inline bool window_continues(const rtHipSampleWindow &w) { return w.accumulate == 1u && w.first > 0u; }
+// `w` becomes the window of the scene's device description and of every tile group's copy of it (RtDevScene travels by value): host
+// words only, picked up by the next launch.
+inline void apply_window(rtHipScene *sc, const rtHipSampleWindow &w)
+{
+    auto put = [&](RtDevScene &D) {
+        D.seedStride = w.total; D.sampleFirst = w.first; D.sampleDivisor = w.divisor;
+        D.continuesFrame = window_continues(w) ? 1u : 0u;
+        D.directStore = (D.sampleCount == 1u && !D.continuesFrame) ? 1u : 0u;
+    };
+    put(sc->dev);
+    for (auto &G : sc->groups) put(G.dev);
+}
+
+// rt_frame.cpp
+RT_INTERNAL int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery);
 RT_INTERNAL int frame_finish(rtHipScene *sc, hipStream_t st, int *redone);
+// rt_api.cpp
 RT_INTERNAL int query_pointer_ok(int device, const char *whose, const void *p, uint64_t bytes, uint64_t align, const char *what);
 RT_INTERNAL int motion_run(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, bool rowMajor, hipStream_t st);
 

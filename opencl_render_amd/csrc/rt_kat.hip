@@ -26,6 +26,7 @@
 //                                                                           opaque-diffuse class form; ran = 0 where the material's height
 //                                                                           map is an image), each without and with firstVertex
 #include "rt_devfuncs.h"
+#include "rt_launch.h"
 #include "raytrace_hip.h"
 
 #include <hip/hip_runtime_api.h>

@@ -21,6 +21,7 @@
 //   sin/cos (bump) and the distant-light spread: host-libm tables / per-light constants uploaded with the scene
 //   pow(0.5, x): exp2(-x) in double on the device (exact for the reference's own scenes where x is 0 or NaN)
 #include "rt_devfuncs.h"
+#include "rt_launch.h"
 
 namespace {
 

@@ -12,6 +12,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rt_device.h"
+#include "rt_launch.h"
 #include "rt_ray_clip.h"
 
 namespace {

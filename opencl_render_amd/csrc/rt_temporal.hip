@@ -13,6 +13,7 @@
 
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_temporal_pixel.h"
 
 namespace {

@@ -20,6 +20,7 @@
 
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_variance_pixel.h"
 
 namespace {

@@ -20,6 +20,7 @@
 // Per path everything happens in the reference's order (RNG draws, ring FIFO, light loop), and paths never interact,
 // so the planes are bit-identical to the single-launch kernel (rt_kernels.hip) and to the oracle.
 #include "rt_devfuncs.h"
+#include "rt_launch.h"
 #include "rt_ray_clip.h"
 
 namespace {
