@@ -352,7 +352,12 @@ int rtHipFrameFinish(rtHipScene *scene, int *redone);
  * windows.  rtHipSceneDenoise, rtHipSceneTemporal and rtHipSceneTemporalVariance read the tile buffer, whatever window filled it.
  * rtHipRenderTilesCounted returns -1 while a window other than the default is in effect.  A scene made by RaytraceAll's cache or by
  * rtHipSceneCreateLike starts with the default window: instances (peers, tile subsets) are set one by one, and disjoint tile deals
- * under the same window still compose one image. */
+ * under the same window still compose one image.
+ * What leaves the window alone.  The window (*next, with the f it has advanced to) and *last belong to the scene, not to its camera,
+ * geometry or pipeline: rtHipSceneSetCamera, rtHipSceneSetGeometry, rtHipSetPipeline, rtHipScenePasses, rtHipSceneMotionMark, the
+ * filters, rtHipSceneTemporalReset and every refused call leave both as they are, and none of them touches the tile buffer.  So a frame
+ * that continues after a move or an update adds its window's samples of the NEW state to what the frames of the old state left: a
+ * plain mixture, defined and seldom wanted -- a caller that moves something mid-run sets the window again to start from f = 0. */
 typedef struct rtHipSampleWindow {
     cl_uint total;      /* N */
     cl_uint first;      /* f */

@@ -411,14 +411,17 @@ typedef struct {
 
 #define MAX2(a, b) (((a) > (b)) ? (a) : (b)) /* raytrace.h:30 (NaN in a falls through to b) */
 
-/* One sample of one pixel: raytrace_opencl.c:470-741, seeded as the C path does (:477-482). */
-static void trace_sample(const rt_oracle_scene *sc, uint32_t pixel, uint32_t sample_id, rt_oracle_stats *st, rt_oracle_census *cs)
+/* One sample of one pixel: raytrace_opencl.c:470-741, seeded as the C path does (:477-482): pixel * stride + sample_id, the addend
+ * scaled by 65535 / divisor.  The reference's frame has stride == divisor == sample_count; a window frame (rt_oracle_render_window) has a
+ * sequence's total as its stride, ids past sample_count and a divisor of its own. */
+static void trace_sample(const rt_oracle_scene *sc, uint32_t pixel, uint64_t sample_id, uint32_t stride, uint32_t divisor,
+                         rt_oracle_stats *st, rt_oracle_census *cs)
 {
     queued_ray ring[RING];
     int head = 0, tail;
     const float px = (float)(pixel % sc->width);
     const float py = (float)(pixel / sc->width);
-    uint64_t rng = (uint64_t)pixel * (uint64_t)sc->sample_count + (uint64_t)sample_id;
+    uint64_t rng = (uint64_t)pixel * (uint64_t)stride + sample_id;
     const v3 lr = ld3(sc->left_to_right), tb = ld3(sc->top_to_bottom);
     v3 out = { 0.f, 0.f, 0.f };
     float k;
@@ -628,7 +631,7 @@ static void trace_sample(const rt_oracle_scene *sc, uint32_t pixel, uint32_t sam
     }
 
     { /* saturating u16 accumulate, addend truncated per sample (:726-741) */
-        const float scale = (float)(0xFFFF) / (float)sc->sample_count;
+        const float scale = (float)(0xFFFF) / (float)divisor;
         int v;
         v = (int)sc->out_r[pixel] + trunc_x86(out.x * scale); if (v < 0) v = 0; if (0xFFFF < v) v = 0xFFFF; sc->out_r[pixel] = (uint16_t)v;
         v = (int)sc->out_g[pixel] + trunc_x86(out.y * scale); if (v < 0) v = 0; if (0xFFFF < v) v = 0xFFFF; sc->out_g[pixel] = (uint16_t)v;
@@ -655,9 +658,9 @@ static void add_census(rt_oracle_census *dst, const rt_oracle_census *src)
     for (i = 0; i < sizeof *dst / sizeof(uint64_t); ++i) d[i] += s[i];
 }
 
-/* raytrace.c:612-653: for each pixel, samples 1..S in order */
-static void render_range(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count, int threads, rt_oracle_stats *stats,
-                         rt_oracle_census *census)
+/* raytrace.c:612-653: for each pixel, samples first+1 .. first+S in order (the reference: first = 0, stride = divisor = S) */
+static void render_range(const rt_oracle_scene *sc, uint32_t stride, uint32_t first, uint32_t divisor, uint32_t first_pixel,
+                         uint32_t pixel_count, int threads, rt_oracle_stats *stats, rt_oracle_census *census)
 {
     const int64_t n = (int64_t)pixel_count;
     if (stats) memset(stats, 0, sizeof *stats);
@@ -673,7 +676,8 @@ static void render_range(const rt_oracle_scene *sc, uint32_t first_pixel, uint32
 #pragma omp for schedule(dynamic, 256)
         for (i = 0; i < n; ++i) {
             uint32_t pixel = first_pixel + (uint32_t)i, s;
-            for (s = 1; s <= sc->sample_count; ++s) trace_sample(sc, pixel, s, stats ? &local : 0, census ? &local_census : 0);
+            for (s = 1; s <= sc->sample_count; ++s)
+                trace_sample(sc, pixel, (uint64_t)first + s, stride, divisor, stats ? &local : 0, census ? &local_census : 0);
         }
         if (stats || census) {
 #pragma omp critical
@@ -687,12 +691,20 @@ static void render_range(const rt_oracle_scene *sc, uint32_t first_pixel, uint32
 
 int rt_oracle_render(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count, int threads, rt_oracle_stats *stats)
 {
-    render_range(sc, first_pixel, pixel_count, threads, stats, 0);
+    render_range(sc, sc->sample_count, 0, sc->sample_count, first_pixel, pixel_count, threads, stats, 0);
     return 1;
 }
 
 int rt_oracle_render_census(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count, int threads, rt_oracle_census *census)
 {
-    render_range(sc, first_pixel, pixel_count, threads, 0, census);
+    render_range(sc, sc->sample_count, 0, sc->sample_count, first_pixel, pixel_count, threads, 0, census);
+    return 1;
+}
+
+int rt_oracle_render_window(const rt_oracle_scene *sc, uint32_t total, uint32_t first, uint32_t divisor, uint32_t first_pixel,
+                            uint32_t pixel_count, int threads)
+{
+    if (total == 0 || divisor == 0 || (uint64_t)first + sc->sample_count > total) return 0;
+    render_range(sc, total, first, divisor, first_pixel, pixel_count, threads, 0, 0);
     return 1;
 }

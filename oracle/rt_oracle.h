@@ -96,6 +96,13 @@ int rt_oracle_render(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t p
 int rt_oracle_render_census(const rt_oracle_scene *sc, uint32_t first_pixel, uint32_t pixel_count,
                             int threads, rt_oracle_census *census);
 
+/* A window frame (include/raytrace_hip.h, "SAMPLE WINDOWS"): every pixel's sample ids first+1 .. first+S in order (S = sample_count),
+ * id i of pixel p seeded (uint64)p*total + i, each addend trunc(out * (65535.0f / (float)divisor)) added with saturation to what the
+ * planes already hold (zeros: a frame that starts afresh; the planes of the frame before: one that continues).  {S, 0, S} is
+ * rt_oracle_render.  Returns 0, planes untouched, for total == 0, divisor == 0 or first + S > total. */
+int rt_oracle_render_window(const rt_oracle_scene *sc, uint32_t total, uint32_t first, uint32_t divisor, uint32_t first_pixel,
+                            uint32_t pixel_count, int threads);
+
 /* Function-level entry points for known-answer tests (same maths as the reference helpers). */
 float rt_oracle_randf(uint64_t *state, float lo, float hi);                     /* :12-23  */
 void  rt_oracle_sphere_point(uint64_t *state, float radius, float out[3]);      /* :30-45  */

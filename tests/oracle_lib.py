@@ -77,6 +77,7 @@ def oracle() -> C.CDLL:
         L = C.CDLL(ORACLE_SO)
         L.rt_oracle_render.argtypes = [C.POINTER(OracleScene), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(OracleStats)]
         L.rt_oracle_render_census.argtypes = [C.POINTER(OracleScene), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(OracleCensus)]
+        L.rt_oracle_render_window.argtypes = [C.POINTER(OracleScene)] + [C.c_uint32] * 5 + [C.c_int]
         L.rt_oracle_randf.restype = C.c_float
         L.rt_oracle_randf.argtypes = [C.POINTER(C.c_uint64), C.c_float, C.c_float]
         L.rt_oracle_sphere_point.argtypes = [C.POINTER(C.c_uint64), C.c_float, C.POINTER(C.c_float)]
@@ -207,6 +208,21 @@ def oracle_render(sc, threads: int = 1, with_stats: bool = False, first_pixel: i
     oracle().rt_oracle_render(C.byref(o), first_pixel, n, threads, C.byref(st) if with_stats else None)
     out = [p.reshape(sc.height, sc.width) for p in planes]
     return (out, st.as_dict()) if with_stats else out
+
+
+def oracle_render_window(sc, total: int, first: int, divisor: int, onto=None, threads: int = 1):
+    """A window frame of the C restatement (rt_oracle_render_window): sample ids first+1 .. first+S of a sequence of `total`, addends
+    scaled by 65535 / divisor and added with saturation onto copies of the three [H, W] u16 planes `onto` (None: zeros).  `onto` is
+    never written to.  Returns [H,W] u16 R,G,B."""
+    if onto is None:
+        planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
+    else:
+        planes = [np.array(p, np.uint16).reshape(sc.pixels).copy() for p in onto]
+        assert len(planes) == 3
+    o = oracle_scene(sc, planes)
+    ok = oracle().rt_oracle_render_window(C.byref(o), int(total), int(first), int(divisor), 0, sc.pixels, threads)
+    assert ok == 1, f"rt_oracle_render_window refused the window {{{total}, {first}, {divisor}}} at S = {sc.sample_count}"
+    return [p.reshape(sc.height, sc.width) for p in planes]
 
 
 def oracle_census(sc, threads: int = 1):

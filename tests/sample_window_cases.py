@@ -21,6 +21,24 @@ PROGRESSIVE = [("lambert_distant", 2, 8), ("mixed_materials_textured", 2, 6), ("
 # premises: checked against the fixtures without a GPU)
 DIVISOR_SCENES = {"all_light_types": (0.079, 0.0), "primary_only": (0.107, 0.0001), "odd_size_multi_tile": (0.194, 0.0)}
 
+U32_MAX = 2 ** 32 - 1
+# every refusal of rtHipSampleWindowCheck: what tests/test_sample_window.py asserts one by one and the session sequences draw from
+REFUSALS = [
+    # (S, window, what the error text must say)
+    (2, (0, 0, 2, 0, 0), "total must be >= 1"),
+    (2, (8, 0, 0, 0, 0), "divisor must be >= 1"),
+    (2, (8, 7, 8, 0, 0), "reaches past total"),
+    (3, (U32_MAX, U32_MAX - 2, 1, 0, 0), "reaches past total"),      # f + S = 2^32 - 2 + 3 wraps in 32 bits: compared in 64
+    (U32_MAX, (U32_MAX, 1, 1, 0, 0), "reaches past total"),
+    (2, (8, 0, 8, 2, 0), "accumulate must be 0 or 1"),
+    (2, (8, 0, 8, 0, 2), "advance must be 0 or 1"),
+    (2, (8, 0, 8, U32_MAX, 0), "accumulate must be 0 or 1"),
+    (3, (8, 0, 8, 0, 1), "multiple of sampleCount"),                  # N % S != 0
+    (2, (8, 1, 8, 0, 1), "advance needs first"),                      # f % S != 0
+]
+
+THREADS = min(os.cpu_count() or 1, 16)
+
 _golden = {}
 _oracle = {}
 
@@ -45,6 +63,37 @@ def oracle_frame(name, total):
         for p in planes:
             p.setflags(write=False)
         _oracle[key] = planes
+    return _oracle[key]
+
+
+def _frozen(planes):
+    for p in planes:
+        p.setflags(write=False)
+    return planes
+
+
+def window_frame(name, total, first, divisor, samples=None):
+    """The window oracle's frame {total, first, divisor} of the golden scene `name` (at another sample count where `samples` is given)
+    from zeros: three read-only [H, W] u16 planes, computed once."""
+    key = (name, int(total), int(first), int(divisor), samples)
+    if key not in _oracle:
+        sc = golden(name)[0]
+        sc = sc if samples is None else with_samples(sc, samples)
+        _oracle[key] = _frozen(O.oracle_render_window(sc, total, first, divisor, threads=THREADS))
+    return _oracle[key]
+
+
+def window_chain(name, total):
+    """The tile buffer after each frame of progressive rendering {total, 0, total, 1, 1} of the golden scene `name`, by the window
+    oracle: total / S triples of read-only planes, each frame added onto the one before; computed once."""
+    key = (name, int(total), "chain")
+    if key not in _oracle:
+        sc = golden(name)[0]
+        out, planes = [], None
+        for f in range(0, total, sc.sample_count):
+            planes = _frozen(O.oracle_render_window(sc, total, f, total, onto=planes, threads=THREADS))
+            out.append(planes)
+        _oracle[key] = out
     return _oracle[key]
 
 

@@ -6,16 +6,22 @@ State.  The model (Session) holds the pose (camera_cases.POSES + "shifted") and 
 BASE scene), the pass mask, the pipeline, the last rendered frame (its planes and the pose, shape and mask it was rendered under), the
 motion reference (pose and shape at the mark, or none), the temporal history (temporal_oracle's arrays; None = reset or never made),
 whether an update has succeeded (the scene retains an index array from then on) and the pose ResidentScene.scene describes (the one of
-creation or of the last update: a camera move does not touch that copy).  The 5 x 7 Scenes of a base scene (fewer where a scene's
+creation or of the last update: a camera move does not touch that copy); for the wide seeds (KINDS_WIDE) also the sample window the
+next frame renders and the one the last frame rendered, and the live moments of the history (None: stale or absent).  The 5 x 7 Scenes of a base scene (fewer where a scene's
 shapes are narrowed) are cached in a World with the oracle's grid, camera lists, planes, centre-ray walks and flows.
 
-Checks.  Frames equal oracle_render as integers; lists and device arrays equal the oracle's after every move and update; motion equals
+Checks.  Frames equal oracle_render as integers -- under a window, oracle_render_window of the model's window, onto the model's planes
+where the frame continues from the tile buffer (accumulate, first > 0); the scene's window equals the model's after every step; lists and device arrays equal the oracle's after every move and update; motion equals
 motion_oracle against the model's mark; temporal equals temporal_oracle.accumulate over the model's LAST RENDERED planes, the flow of the
 CURRENT state against the model's mark, and the model's history; refusals return their code and text and change nothing, which every
-later check proves.  Passes, denoise, AO and the bake are compared with a twin: a ResidentScene created fresh from the model's Scene
+later check proves.  temporal_variance equals variance_oracle the same way; a temporal step leaves the moments stale, and the next
+variance step starts the history again (count 1, variance 0, the frame's colour).  Passes, denoise, AO and the bake are compared with a twin: a ResidentScene created fresh from the model's Scene
 (made once per visited state and closed at once, its products cached for the module); a fresh scene's products are pinned to their
 oracles by the feature tests.  The denoiser is also compared with denoise_oracle on the read-backs, and on the small scene AO and the
-bake with ao_oracle and bake_oracle, so that twin and subject cannot be wrong alike.
+bake with ao_oracle and bake_oracle, so that twin and subject cannot be wrong alike.  Under a window the twin is set to the frame's
+(total, first) for the passes, and the filters' colour input is the model's planes; AO, the bake, ray queries and motion keep twins and
+oracles that know nothing of windows.  After every update and in every clone the clip bound equals a fresh scene's and holds every
+occupied cell; a clone starts with the default window and leaves its parent's alone.
 
 What the header leaves open is not checked: read_passes, denoise and temporal(denoise=) read buffers that a frame fills under the mask
 in effect, so where no frame has been rendered yet, or the last one was rendered under another mask, the operation renders one first
@@ -29,7 +35,11 @@ SCENES).  A cut is placed as late as the refusal cap allows: a sequence is the l
 steps and after which the rest of the circuit can still be cut that way.  Each sequence starts from a fresh scene, at the pose and
 shape the one before ended in, and its first step repeats the previous one's last kind, so no pair is lost at a cut.
 Arguments are drawn against a light copy of the state so that camera and shape steps always change something and refusals stay rare;
-a draw that misses one of the caps below is drawn again (attempt 0, 1, ...): generation is a pure function of (scene, seed)."""
+a draw that misses one of the caps below is drawn again (attempt 0, 1, ...): generation is a pure function of (scene, seed).  The wide
+seeds have caps of their own (wide_caps); a window that continues is only ever drawn at first = 0, so no frame continues from a buffer
+the header leaves undefined."""
+import ctypes
+
 import numpy as np
 
 import ao_oracle
@@ -42,7 +52,10 @@ import motion_oracle as MO
 import oracle_lib as O
 import prep_oracle as P
 import query_cases as Q
+import sample_window_cases as WC
 import temporal_oracle as TO
+import variance_oracle as VO
+from clip_checks import assert_bound
 from geometry_checks import assert_device_arrays, prep_of, update_to
 from opencl_render_amd import raytrace as R
 
@@ -51,6 +64,9 @@ NONE = 0xFFFFFFFF
 KINDS = ("frame", "camera", "shape", "passes", "pipeline", "read_passes", "denoise", "ao", "bake", "intersect", "mark", "motion", "temporal",
          "reset_temporal", "refused_update", "refused_camera", "clone")
 K = len(KINDS)
+# The alphabet is a property of the seed: the seeds drawn before sample windows and the moments history existed keep KINDS (their
+# sequences are what they were), the wide seeds of a scene draw from KINDS_WIDE.
+KINDS_WIDE = KINDS + ("window", "variance")
 POSES = CC.POSES + ("shifted",)
 NEAR = ("home", "pan", "shifted")
 SURFACE = R.PASS_NORMAL | R.PASS_ALBEDO
@@ -64,15 +80,32 @@ MAX_REFUSED = 0.2  # of any sequence's steps
 MIN_WARM = 0.35  # of a seed's temporal steps follow another one of their sequence, with no reset and no update between
 # Scenes, with their circuit and walk seeds and the shapes drawn for them.  axis_near_axis_mixed loses "translate": from orbit90 the
 # translated mesh is hidden, and the oracle's planes of translate, reindex and home are the same there.
-SCENES = {"mirror_hall": dict(size=(24, 16), circuits=(1, 2), walks=(101, 102), shapes=GC.SEQUENCE, cut=40),
-          "axis_near_axis_mixed": dict(size=(136, 132), circuits=(3,), walks=(), shapes=tuple(n for n in GC.SEQUENCE if n != "translate"), cut=25,
-                                       shape_steps=2)}
+# wide_circuits / wide_walks: the seeds that draw from KINDS_WIDE (a circuit of 19 * 19 + 1 = 362 steps).  axis_near_axis_mixed has four
+# tiles, so its wide walk exercises the tile groups' copies of the window.  Its path class is the general one (R.path_class), which
+# takes no split logic rounds: playing its sequences once more under RT_WF_LOGIC_SPLIT=0 would run the same kernels, and is left out.
+# Its walk of 60 steps is cut in two (walk_cut, the second starting with the first's last kind): played whole it took 6.6 s on the device.
+# (Seed 106 meets the caps of the draw at its fifth attempt; 104, 105 and 107..109 meet the same caps after 100 to 630.)
+SCENES = {"mirror_hall": dict(size=(24, 16), samples=2, circuits=(1, 2), walks=(101, 102), wide_circuits=(4,), wide_walks=(103,),
+                              shapes=GC.SEQUENCE, cut=40),
+          "axis_near_axis_mixed": dict(size=(136, 132), samples=2, circuits=(3,), walks=(), wide_circuits=(), wide_walks=(106,),
+                                       shapes=tuple(n for n in GC.SEQUENCE if n != "translate"), cut=25, shape_steps=2, walk_cut=31)}
 # Measured on the oracle by tests/test_session.py, which prints them, over the visited states (hit share of the centre rays; share of the
 # oracle's pixels that differ between the two states of a camera or shape step, home <-> reindex excepted as in geometry_cases.py):
-# mirror_hall 31 states visited, hit share 0.596..0.979, changed share 0.602..1.000 over 70
-# distinct moves; axis_near_axis_mixed 17 states, hit share 0.746..1.000, changed share 0.195..1.000 over 32 moves; 21 of 62 temporal steps
-# accept history in at least 0.2 of the pixels.  COUNTS is asserted there, so that a change of the draw cannot leave these figures behind.
+# mirror_hall 33 states visited, hit share 0.596..0.987, changed share 0.591..1.000 over 101
+# distinct moves; axis_near_axis_mixed 19 states, hit share 0.746..1.000, changed share 0.195..1.000 over 37 moves (all seeds); 21 of 62
+# temporal steps of the seeds of COUNTS accept history in at least 0.2 of the pixels.  COUNTS is asserted there, so that a change of the
+# draw cannot leave these figures behind.
 COUNTS = dict(sequences=34, steps=1019)
+# The wide seeds, counted and measured apart (tests/test_session.py prints the figures and asserts the counts): 44 frames (16 under the
+# default window, 10 progressive, 7 over-bright, 7 fixed, 4 of a sequence), 6 of them continue from the tile buffer, 4 of those after a
+# camera, shape or pipeline step; 4 progressive runs complete; 2 over-bright frames saturate a value that their D = N frame does not;
+# of 20 variance steps 8 are warm, 10 start again over stale moments and 1 goes on with live moments.  WINDOW_SHARES: the mean share of
+# the plane values in which a continuing frame differs from the same window rendered from zeros (0.811..0.995 over the 6), and in which
+# two successive windows of a sequence differ (2 pairs); the test asserts half of each, which leaves room for another draw.
+COUNTS_WIDE = dict(sequences=14, steps=493)
+WINDOW_SHARES = dict(continuing=0.950, successive=0.987)
+WINDOW_SIZES = (2, 3, 4)  # N / S of a drawn window
+VARIANCE_FILTER = dict(iterations=2, spatial_below=2.0)
 SMALL = "mirror_hall"  # AO and the bake are also compared with their numpy oracles here
 # Reduced sequences of mismatches found by the circuits: name -> (scene, (start pose, start shape), steps).  None so far.
 REGRESSIONS = {}
@@ -89,7 +122,8 @@ class World:
         self.name, self.size = name, SCENES[name]["size"]
         self.base = MC.base_scene(name, self.size)
         self.width, self.height = self.base.width, self.base.height
-        self._shape, self._state, self._planes, self._trace, self._flow, self._prep = {}, {}, {}, {}, {}, {}
+        self._shape, self._state, self._planes, self._trace, self._flow, self._prep, self._window = {}, {}, {}, {}, {}, {}, {}
+        assert self.base.sample_count == SCENES[name]["samples"]
 
     def shape_scene(self, shape):
         if shape not in self._shape:
@@ -126,6 +160,17 @@ class World:
             self._planes[pose, shape] = [np.asarray(p).reshape(sc.height, sc.width).copy() for p in O.oracle_render(sc, threads=16)]
         return self._planes[pose, shape]
 
+    def window_planes(self, pose, shape, total, first, divisor, onto=None):
+        """oracle_render_window of the state: the frame of the window {total, first, divisor}, from zeros or onto the planes `onto`
+        (the tile buffer a continuing frame finds).  Cached: from zeros per state and window, onto planes also per what they hold."""
+        sc = self.state(pose, shape)
+        if onto is None and (total, first, divisor) == (sc.sample_count, 0, sc.sample_count):
+            return self.planes(pose, shape)
+        key = (pose, shape, total, first, divisor) + (() if onto is None else tuple(hash(np.asarray(p).tobytes()) for p in onto))
+        if key not in self._window:
+            self._window[key] = O.oracle_render_window(sc, total, first, divisor, onto=onto, threads=16)
+        return self._window[key]
+
     def trace(self, pose, shape):
         if (pose, shape) not in self._trace:
             self._trace[pose, shape] = MO.trace(self.state(pose, shape))
@@ -148,26 +193,37 @@ def world(name):
 
 
 # ---- twins ---------------------------------------------------------------------------------------------------------------------------
-_twin, _twin_ao, _twin_bake, _oracle_ao, _oracle_bake = {}, {}, {}, {}, {}
+_twin, _twin_ao, _twin_bake, _twin_clip, _oracle_ao, _oracle_bake = {}, {}, {}, {}, {}, {}
+_bound_held = set()
 
 
-def twin(w, pose, shape, mask):
-    """What a scene created fresh from the state returns under `mask`: {"passes", "denoise" (one per variant, with both surface
-    passes)}; its AO image and bake go to caches of their own (they do not depend on the mask, the bake not on the pose either)."""
-    key = (w.name, pose, shape, mask)
+def twin(w, pose, shape, mask, total=None, first=0):
+    """What a scene created fresh from the state returns under `mask` for a frame of sample ids first+1 .. first+S of a sequence of
+    `total` (None: S, the default window): {"passes", "denoise" (one per variant, with both surface passes)}.  Passes depend on neither
+    the divisor nor on what the frame continued from, so the twin's window is {total, first, S, 0, 0}; its denoised colour is that
+    frame's own.  Its AO image, bake and clip bound go to caches of their own (they do not depend on the mask or the window, the bake
+    and the bound not on the pose either)."""
+    samples = w.base.sample_count
+    total = samples if total is None else total
+    key = (w.name, pose, shape, mask) + (() if (total, first) == (samples, 0) else (total, first))
     if key not in _twin:
         t = R.ResidentScene(w.state(pose, shape), 0)
         try:
             out = {}
             if mask:
                 t.set_passes(**flags(mask))
+            if (total, first) != (samples, 0):
+                t.set_sample_window(total, first, samples)
+            if (w.name, shape) not in _twin_clip:
+                _twin_clip[w.name, shape] = t.clip_planes()
             t.render()
             out["passes"] = t.readback_passes()
             if mask & SURFACE == SURFACE:
                 out["denoise"] = [t.denoise(**v) for v in DENOISE_VARIANTS]
-            if (w.name, pose, shape) not in _twin_ao:
+            plain = (total, first) == (samples, 0)  # (AO and the bake come from twins that never saw a window)
+            if plain and (w.name, pose, shape) not in _twin_ao:
                 _twin_ao[w.name, pose, shape] = t.ambient_occlusion(rays=4)
-            if (w.name, shape) not in _twin_bake:
+            if plain and (w.name, shape) not in _twin_bake:
                 _twin_bake[w.name, shape] = t.bake_ambient_occlusion(16, 16, rays=4, dilate=2)
             _twin[key] = out
         finally:
@@ -185,6 +241,13 @@ def twin_bake(w, shape):
     if (w.name, shape) not in _twin_bake:
         twin(w, "home", shape, 0)
     return _twin_bake[w.name, shape]
+
+
+def twin_clip(w, pose, shape):
+    """The clip bound of a fresh scene of the shape (made at `pose`, where AO is likely to ask for the same twin)."""
+    if (w.name, shape) not in _twin_clip:
+        twin(w, pose, shape, 0)
+    return _twin_clip[w.name, shape]
 
 
 def differs(got, want, what):
@@ -207,14 +270,33 @@ def refusal(call, text, what):
 
 
 # ---- the light state the arguments are drawn against, and every kind's expected refusal ----------------------------------------------------
+def window_kind(win, samples):
+    """What a window {N, f, D, accumulate, advance} is called here."""
+    N, f, D, acc, adv = win
+    if win == (samples, 0, samples, 0, 0):
+        return "default"
+    if acc and adv:
+        return "progressive" if D == N else "overbright"
+    return "sequence" if adv else "fixed"
+
+
 class Lite:
-    def __init__(self, pose="home", shape="home"):
+    def __init__(self, pose="home", shape="home", samples=2):
         self.pose, self.shape, self.mask, self.pipeline = pose, shape, 0, R.PIPELINE_WAVEFRONT
-        self.frame = self.mark = None  # (pose, shape, mask) / (pose, shape)
+        self.frame = self.mark = None  # (pose, shape, mask, total, first) / (pose, shape)
         self.updated = False
+        # sample windows: the window the next frame renders, the one the last frame rendered (None before the first), and what
+        # tests/test_session.py and the caps of the draw ask about every rendered frame (self.frames, one dict per frame)
+        self.samples = samples
+        self.window_next, self.window_last = (samples, 0, samples, 0, 0), None
+        self.frames, self.moved, self.run = [], False, None
 
     def refuses(self, step):
         kind, arg = step
+        if kind == "window":
+            return arg is not None and arg[0] == "refused"
+        if kind == "variance":
+            return arg[0] and self.mask & SURFACE != SURFACE
         if kind == "passes":
             return self.pipeline == R.PIPELINE_MEGAKERNEL and arg != 0
         if kind == "pipeline":
@@ -238,19 +320,44 @@ class Lite:
         if self.refuses(step) and kind != "clone":
             return
         if kind == "camera":
-            self.pose = arg
+            self.pose, self.moved, self.run = arg, True, None
         elif kind == "shape":
-            self.shape, self.updated = arg, True
+            self.shape, self.updated, self.moved, self.run = arg, True, True, None
         elif kind == "passes":
             self.mask = arg
         elif kind == "pipeline":
+            self.moved |= arg != self.pipeline
             self.pipeline = arg
         elif kind == "mark":
             self.mark = (self.pose, self.shape)
-        if kind == "frame" or (kind in ("read_passes", "denoise") and self.renders(True)) or (kind == "temporal" and self.renders(arg[0])):
-            self.frame = (self.pose, self.shape, self.mask)
-        if kind == "temporal":
+        elif kind == "window":
+            self.window_next, self.run = (arg if arg is not None else (self.samples, 0, self.samples, 0, 0)), None
+        if (kind == "frame" or (kind in ("read_passes", "denoise") and self.renders(True))
+                or (kind in ("temporal", "variance") and self.renders(arg[0]))):
+            self.render_frame()
+        if kind in ("temporal", "variance"):
             self.mark = (self.pose, self.shape)
+
+    def render_frame(self):
+        """A frame is issued: it renders window_next, which becomes window_last and moves on if it advances.  Notes in self.frames what
+        the frame was: its window and the kind of it, whether it continued from the tile buffer and whether a camera, shape or pipeline
+        step was made since the frame before, and `complete`: N where this frame ends a progressive run that started at f = 0 and saw
+        no camera, shape or window step since (the tile buffer then holds the N-sample frame of the state), else 0."""
+        S = self.samples
+        N, f, D, acc, adv = win = self.window_next
+        kind = window_kind(win, S)
+        if kind == "progressive" and f == 0:
+            self.run = N
+        elif kind != "progressive":
+            self.run = None
+        complete = N if self.run == N and kind == "progressive" and f == N - S else 0
+        self.frames.append(dict(state=(self.pose, self.shape), window=win, kind=kind, continuing=bool(acc and f > 0), moved=self.moved,
+                                complete=complete))
+        self.frame, self.window_last, self.moved = (self.pose, self.shape, self.mask, N, f), win, False
+        if adv:
+            self.window_next = (N, (f + S) % N, D, acc, adv)
+        if complete:
+            self.run = None
 
 
 def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
@@ -288,10 +395,35 @@ def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
         return pick([p for p in POSES if p != s.pose])
     if kind == "clone":
         return bool(tiles > 1 and dare)
+    if kind == "variance":
+        on = rng.random() < 0.5 if s.mask & SURFACE == SURFACE else dare
+        return (bool(on), int(pick(MAX_HISTORY)))
+    if kind == "window":
+        S = s.samples
+        if dare:  # one of the refusals that apply to a scene of S samples: returns -1 with its text and changes nothing
+            _, win, text = pick([r for r in WC.REFUSALS if r[0] == S])
+            return ("refused", win, text)
+        N = S * int(pick(WINDOW_SIZES))
+        r = rng.random()
+        if r < 0.08:
+            return None  # the default window
+        if r < 0.43:  # (a short progressive run is the likeliest to complete before the next move)
+            return _progressive(rng, S, N)
+        if r < 0.62:
+            return (N, 0, S, 0, 1)  # a sequence
+        if r < 0.85:
+            return (N, 0, S, 1, 1)  # over-bright progressive: every frame at full brightness on top of the frames before
+        return (N, int(rng.integers(1, N - S + 1)), int(pick((1, 3, S, N))), 0, 0)  # fixed, off the grid of S where N allows
     return None
 
 
-def eulerian(rng):
+def _progressive(rng, S, N):
+    """{N, 0, N, 1, 1}; half of them the shortest run, N = 2 S."""
+    N = 2 * S if rng.random() < 0.5 else N
+    return (N, 0, N, 1, 1)
+
+
+def eulerian(rng, K=K):
     """K * K + 1 kind indices: a walk that uses every ordered pair of kinds, loops included, exactly once (Hierholzer, the edges of every
     node in a seeded order)."""
     out = [[int(v) for v in rng.permutation(K)] for _ in range(K)]
@@ -304,13 +436,15 @@ def eulerian(rng):
     return path[::-1]
 
 
-def _piece(rng, kinds, start, tiles, shapes, seen):
+def _piece(rng, kinds, start, tiles, shapes, seen, samples=2):
     """Steps for `kinds` from a fresh scene at `start`, and what the caps ask about them: (steps, refusals after each step, temporal
-    steps on an older frame, motion steps with camera and shape both changed, each as the index of the step)."""
-    s, steps, refused, stale, mixed = Lite(*start), [], [], [], []
+    steps on an older frame, motion steps with camera and shape both changed, temporal steps, the warm ones among them, each as the
+    index of the step; and of the variance steps [(index, warm, stale moments over a live history)])."""
+    s, steps, refused, stale, mixed = Lite(*start, samples=samples), [], [], [], []
     seen, hist, temporal, warm = set(seen), False, [], []
+    moments, variance = False, []
     for i, k in enumerate(kinds):
-        kind = KINDS[k]
+        kind = KINDS_WIDE[k]
         step = (kind, draw(rng, kind, s, (sum(refused[-1:]) + 1) <= MAX_REFUSED * (i + 1), tiles, shapes, seen))
         refused.append((refused[-1] if refused else 0) + bool(s.refuses(step)))
         if kind == "temporal" and not s.refuses(step) and not s.renders(step[1][0]) and s.frame[:2] != (s.pose, s.shape):
@@ -321,13 +455,16 @@ def _piece(rng, kinds, start, tiles, shapes, seen):
             temporal.append(i)
             if hist and s.mark[1] == s.shape:
                 warm.append(i)
-            hist = True
+            hist, moments = True, False
+        if kind == "variance" and not s.refuses(step):  # warm as a temporal step is: a history, reprojected from the same shape
+            variance.append((i, bool(hist and s.mark[1] == s.shape), bool(hist and not moments)))
+            hist = moments = True
         if kind == "reset_temporal":
-            hist = False
+            hist = moments = False
         s.advance(step)
         steps.append(step)
         seen |= {s.pose, s.shape}
-    return steps, refused, stale, mixed, temporal, warm
+    return steps, refused, stale, mixed, temporal, warm, variance
 
 
 def _attempt(name, seed, attempt):
@@ -337,9 +474,12 @@ def _attempt(name, seed, attempt):
     spec = SCENES[name]
     key = [sorted(SCENES).index(name), seed, attempt]
     tiles = R.tile_count(*spec["size"])
-    walk = seed in spec["walks"]
-    kinds = [int(v) for v in np.random.default_rng(key).integers(K, size=WALK)] if walk else eulerian(np.random.default_rng(key))
-    limit = WALK if walk else spec["cut"]
+    walk = seed in spec["walks"] + spec["wide_walks"]
+    wide = seed in spec["wide_circuits"] + spec["wide_walks"]
+    k = len(kinds_of(name, seed))
+    kinds = [int(v) for v in np.random.default_rng(key).integers(k, size=WALK)] if walk else eulerian(np.random.default_rng(key), k)
+    limit = spec.get("walk_cut", WALK) if walk else spec["cut"]
+    whole = walk and limit == WALK  # (a walk is one sequence, unless the scene cuts its walks as it cuts a circuit)
     budget = [400]  # pieces tried: a draw that needs more is given up
 
     def rest(at, start, seen):
@@ -350,31 +490,66 @@ def _attempt(name, seed, attempt):
         if budget[0] < 0:
             return None
         piece = kinds[at:at + limit]
-        steps, refused, st, mx, tp, wm = _piece(np.random.default_rng(key + [at]), piece, start, tiles, spec["shapes"], seen)
+        steps, refused, st, mx, tp, wm, vr = _piece(np.random.default_rng(key + [at]), piece, start, tiles, spec["shapes"], seen,
+                                                    spec["samples"])
         for n in range(len(piece), 1, -1):
-            if refused[n - 1] > MAX_REFUSED * n or (walk and n < len(piece)):
+            if refused[n - 1] > MAX_REFUSED * n or (whole and n < len(piece)):
                 continue
             if sum(k == "shape" for k, _ in steps[:n]) > spec.get("shape_steps", n):
                 continue  # (an update's check of the device arrays takes over a second on the larger scene's 12.6 million pairs)
-            s, now = Lite(*start), set(seen)
+            s, now = Lite(*start, samples=spec["samples"]), set(seen)
             for step in steps[:n]:
                 s.advance(step)
                 now |= {s.pose, s.shape}
             tail = rest(at + n - 1, (s.pose, s.shape), now)
             if tail is not None:
                 return [dict(start=start, steps=steps[:n], stale=sum(i < n for i in st), mixed=sum(i < n for i in mx), seen=now,
-                             temporal=sum(i < n for i in tp), warm=sum(i < n for i in wm))] + tail
+                             temporal=sum(i < n for i in tp), warm=sum(i < n for i in wm), variance=[v for v in vr if v[0] < n],
+                             frames=s.frames)] + tail
         return None
 
     out = rest(0, ("home", "home"), {"home"})
     if out is None:
         return None
     stale, mixed, seen = sum(q.pop("stale") for q in out), sum(q.pop("mixed") for q in out), set().union(*(q.pop("seen") for q in out))
+    variance, frames = [v for q in out for v in q.pop("variance")], [q.pop("frames") for q in out]
     if sum(q.pop("warm") for q in out) < MIN_WARM * sum(q.pop("temporal") for q in out):
         return None  # (too few temporal steps with a history to reproject: the accepting share could not reach a third)
+    if wide and not wide_caps(frames, variance, walk):
+        return None
     if not walk and not (stale and mixed and seen >= set(POSES) | set(spec["shapes"])):
         return None  # (the camera draw favours the near poses: a circuit still visits every pose and every shape)
     return out
+
+
+def successive(frames):
+    """(i, i + 1) of the frames of one sequence that are successive windows of a sample sequence rendered in the same state."""
+    return [(i, i + 1) for i, (a, b) in enumerate(zip(frames, frames[1:])) if a["kind"] == b["kind"] == "sequence"
+            and a["state"] == b["state"] and a["window"][0] == b["window"][0] and a["window"][1] != b["window"][1]]
+
+
+def wide_caps(frames, variance, walk):
+    """What a wide seed's draw must hold, from the frames its sequences render (Lite.frames, one list per sequence) and its variance steps [(index, warm,
+    stale moments over a live history)].  Every seed: a progressive run completes, and a variance step finds stale moments over a live
+    history; a third of the frames under another window than the default, one frame in ten continuing from the tile buffer, half of
+    those after a camera, shape or pipeline step made since the frame they continue, and a third of the variance steps warm (a history,
+    reprojected from the same shape: the sense of MIN_WARM).  A circuit also: an over-bright frame that continues, and two successive
+    frames of a sequence in one state.  tests/test_session.py asserts all of it on the oracle, over the wide seeds together."""
+    pairs = [p for part in frames for p in successive(part)]
+    frames = [f for part in frames for f in part]
+    if not any(f["complete"] for f in frames) or not any(stale for _, _, stale in variance):
+        return False
+    cont = [f for f in frames if f["continuing"]]
+    if not (3 * sum(f["kind"] != "default" for f in frames) >= len(frames) and 10 * len(cont) >= len(frames)
+            and 2 * sum(f["moved"] for f in cont) >= len(cont) and 3 * sum(w for _, w, _ in variance) >= len(variance)):
+        return False
+    return walk or (any(f["kind"] == "overbright" for f in cont) and bool(pairs))
+
+
+def kinds_of(name, seed):
+    """The alphabet of a seed."""
+    spec = SCENES[name]
+    return KINDS_WIDE if seed in spec["wide_circuits"] + spec["wide_walks"] else KINDS
 
 
 _sequences = {}
@@ -393,10 +568,16 @@ def sequences(name, seed):
     return _sequences[name, seed]
 
 
+def seeds_of(name, wide=None):
+    """The scene's seeds: all of them, the wide ones (wide=True) or the others (wide=False)."""
+    spec = SCENES[name]
+    old, new = spec["circuits"] + spec["walks"], spec["wide_circuits"] + spec["wide_walks"]
+    return old + new if wide is None else new if wide else old
+
+
 def all_parts():
     """(scene, seed, part) of every sequence; regressions are (scene, name, 0)."""
-    out = [(name, seed, part) for name, spec in SCENES.items() for seed in spec["circuits"] + spec["walks"]
-           for part in range(len(sequences(name, seed)))]
+    out = [(name, seed, part) for name, spec in SCENES.items() for seed in seeds_of(name) for part in range(len(sequences(name, seed)))]
     return out + [(scene, key, 0) for key, (scene, _, _) in REGRESSIONS.items()]
 
 
@@ -406,12 +587,22 @@ def visited(name):
     for n, seed, part in all_parts():
         if n == name:
             q = part_of(n, seed, part)
-            s = Lite(*q["start"])
+            s = Lite(*q["start"], samples=SCENES[n]["samples"])
             out.append((s.pose, s.shape))
             for step in q["steps"]:
                 s.advance(step)
                 out.append((s.pose, s.shape))
     return list(dict.fromkeys(out))
+
+
+def warm_wide(name):
+    """The model alone over the scene's wide sequences: every window frame, flow and accumulation their checks read is made now (the
+    caches are the World's), as World.warm does for the planes of the visited states."""
+    for seed in seeds_of(name, wide=True):
+        for q in sequences(name, seed):
+            s = Session(world(name), q["start"])
+            for step in q["steps"]:
+                s.apply(step)
 
 
 def part_of(name, seed, part):
@@ -427,10 +618,11 @@ class Session(Lite):
     and checked; without, the model advances alone and notes what tests/test_session.py asserts on (self.notes)."""
 
     def __init__(self, w, start=("home", "home"), rs=None):
-        super().__init__(*start)
+        super().__init__(*start, samples=w.base.sample_count)
         self.w, self.rs = w, rs
         self.described_pose = start[0]
         self.planes = self.history = None
+        self.moments = None  # the live moments [H, W, 2] of the history; None: stale (a temporal step wrote none) or absent
         self.notes = []
 
     def here(self):
@@ -440,21 +632,50 @@ class Session(Lite):
         kind, arg = step
         getattr(self, "do_" + kind)(arg) if arg is not None else getattr(self, "do_" + kind)()
         self.advance(step)
+        if self.rs:
+            self.same_window(f"after {kind}")
 
     # -- frames
     def do_frame(self):
-        want = self.w.planes(*self.here())
+        """The frame of window_next: the window oracle's, onto the model's planes where the frame continues from the tile buffer."""
+        N, f, D, acc, adv = self.window_next
+        onto = self.planes if acc and f > 0 else None
+        assert onto is not None or not (acc and f > 0), "a frame continues before the sequence's first frame: the header leaves the buffer open"
+        want = self.w.window_planes(self.pose, self.shape, N, f, D, onto)
         if self.rs:
             self.rs.render()
             sc = self.w.base
             for ch, g, x in zip("RGB", self.rs.readback(), want):
-                differs(np.asarray(g).reshape(sc.height, sc.width), x, f"plane {ch} of the frame at {self.here()}")
-        self.planes = want
+                differs(np.asarray(g).reshape(sc.height, sc.width), x, f"plane {ch} of the frame at {self.here()} under the window {self.window_next}")
+        self.before, self.planes = self.planes, want
+
+    def render_frame(self):
+        super().render_frame()
+        self.notes.append(("frame", self.frames[-1], (self.before, self.planes)))  # (what the buffer held, what it holds now)
 
     def need_frame(self, uses_passes):
         if self.renders(uses_passes):
             self.do_frame()
-            self.frame = (self.pose, self.shape, self.mask)
+            self.render_frame()
+
+    def same_window(self, what):
+        zero = dict(total=0, first=0, divisor=0, accumulate=0, advance=0)
+        as_dict = lambda v: dict(zip(("total", "first", "divisor", "accumulate", "advance"), v))  # noqa: E731
+        want = {"next": as_dict(self.window_next), "last": zero if self.window_last is None else as_dict(self.window_last)}
+        got = self.rs.sample_window()
+        assert got == want, f"{what}: the scene's sample window is {got}, the model's {want}"
+
+    def do_window(self, arg=None):
+        if not self.rs:
+            return
+        if self.refuses(("window", arg)):
+            _, win, text = arg
+            rc = int(R.lib().rtHipSceneSetSampleWindow(self.rs.handle, ctypes.byref(R.SampleWindow(*win))))
+            assert rc == -1 and text in R.last_error(), f"refused window {win}: returned {rc} with {R.last_error()!r}, expected -1 with {text!r}"
+        elif arg is None:
+            self.rs.set_sample_window()
+        else:
+            self.rs.set_sample_window(*arg)
 
     # -- state changes
     def do_camera(self, pose):
@@ -469,7 +690,19 @@ class Session(Lite):
             update_to(self.rs, want)
             CC.assert_lists_equal(self.rs, want, f"lists after the update to {name}")
             assert_device_arrays(self.rs, want, f"device arrays after the update to {name}", self.w.prep(name))
+            self.same_bound(self.rs, name, f"the clip bound after the update to {name}")
         self.described_pose = self.pose
+
+    def same_bound(self, rs, shape, what):
+        """The kept planes are a fresh scene's, and they hold every corner of every occupied cell."""
+        kept = rs.clip_planes()
+        differs(kept, twin_clip(self.w, self.pose, shape), what + " (against the twin)")
+        # (the corners of a million occupied cells take a second on the larger scene: the same planes over the same block table
+        # have the same verdict, and clones of one shape are many)
+        key = (self.w.name, shape, kept.tobytes(), hash(rs.scene_view("block_sparse").tobytes()))
+        if key not in _bound_held:
+            assert_bound(rs, self.w.shape_scene(shape).box_min, what)
+            _bound_held.add(key)
 
     def do_passes(self, mask):
         if not self.rs:
@@ -504,13 +737,21 @@ class Session(Lite):
             return
         self.need_frame(True)
         if self.rs:
-            got, want = self.rs.denoise(**params), twin(self.w, *self.frame)["denoise"][variant]
-            differs(got["colour"], want["colour"], "denoised colour (against the twin)")
-            for ch, g, x in zip("RGB", got["planes"], want["planes"]):
-                differs(g, x, f"denoised plane {ch} (against the twin)")
+            got, made = self.rs.denoise(**params), twin(self.w, *self.frame)
+            if self.window_last[2:4] == (self.samples, 0):  # the twin's frame is this frame: its divisor is S and neither continued
+                want = made["denoise"][variant]
+                differs(got["colour"], want["colour"], "denoised colour (against the twin)")
+                for ch, g, x in zip("RGB", got["planes"], want["planes"]):
+                    differs(g, x, f"denoised plane {ch} (against the twin)")
+            # the colour input is the tile buffer, whatever window filled it: the read-backs the oracle is fed are the model's planes
+            # and the twin's surface passes
             sc = self.w.base
             planes = [np.asarray(p).reshape(sc.height, sc.width) for p in self.rs.readback()]
             surf = self.rs.readback_passes()
+            for ch, g, x in zip("RGB", planes, self.planes):
+                differs(g, x, f"plane {ch} of the tile buffer the denoiser read")
+            for k in ("normal", "albedo"):
+                differs(surf[k], made["passes"][k], f"pass {k} the denoiser read")
             exp = D.denoise(*D.inputs(planes, surf["normal"], surf["albedo"]), **dict(R.DENOISE_DEFAULTS, **params))
             differs(got["colour"], exp, "denoised colour (against the oracle on the read-backs)")
             for ch, g, x in zip("RGB", got["planes"], D.quantise(exp)):
@@ -596,11 +837,48 @@ class Session(Lite):
                 differs(g, x, f"temporal plane {ch}")
             self.same_mark("temporal (the call owns the mark)")
         self.history = TO.next_history(dict(colour=acc["colour"], count=acc["count"]), flow["t"], flow["triangle"])
+        self.moments = None  # the plain call writes none: they are stale from here on
+
+    def do_variance(self, arg):
+        """rs.temporal_variance: the accumulation with the luminance moments carried along, over the model's planes, the flow against
+        the mark and the model's history; a live history whose moments are stale starts again, as after a reset."""
+        on, cap = arg
+        if self.refuses(("variance", arg)):
+            if self.rs:
+                refusal(lambda: self.rs.temporal_variance(filter=VARIANCE_FILTER, max_history=float(cap)), "normal and the albedo pass",
+                        "temporal_variance(filter=) without both surface passes")
+            return
+        self.need_frame(on)
+        flow = self.w.flow(self.here(), self.mark or self.here())
+        colour = np.stack(self.planes, -1).astype(F32) / F32(65535.0)
+        stale = self.history is not None and self.moments is None
+        live = self.history is not None and not stale
+        hist = dict(self.history, moments=self.moments) if live else VO.empty_history(self.w.height, self.w.width)
+        acc = VO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap))
+        if not live:  # no history, or one that starts again: the frame itself
+            assert (acc["count"] == 1.0).all() and (acc["variance"] == 0.0).all() and TO.same_bits(acc["colour"], colour).all()
+        warm = self.history is not None and self.mark is not None and self.mark[1] == self.shape  # (as _piece counts it)
+        self.notes.append(("variance", dict(stale=stale, warm=warm, live=live), float((acc["count"] > 1.0).mean())))
+        if self.rs:
+            shown = dict(colour=acc["colour"], variance=acc["variance"])
+            if on:
+                surf = twin(self.w, *self.frame)["passes"]
+                shown["colour"], shown["variance"] = VO.denoise(acc["colour"], surf["normal"], surf["albedo"], acc["moments"], acc["count"],
+                                                                **VARIANCE_FILTER)
+            got = self.rs.temporal_variance(filter=VARIANCE_FILTER if on else None, max_history=float(cap))
+            differs(got["count"], acc["count"], "temporal_variance count")
+            differs(got["colour"], shown["colour"], "temporal_variance colour")
+            differs(got["variance"], shown["variance"], "temporal_variance variance")
+            for ch, g, x in zip("RGB", got["planes"], D.quantise(shown["colour"])):
+                differs(g, x, f"temporal_variance plane {ch}")
+            self.same_mark("temporal_variance (the call owns the mark)")
+        self.history = TO.next_history(dict(colour=acc["colour"], count=acc["count"]), flow["t"], flow["triangle"])
+        self.moments = acc["moments"]
 
     def do_reset_temporal(self):
         if self.rs:
             self.rs.reset_temporal()
-        self.history = None
+        self.history = self.moments = None
 
     # -- refusals: one illegal argument each; nothing changes, which every later check proves
     def do_refused_update(self, arg):
@@ -655,6 +933,9 @@ class Session(Lite):
         desc = self.rs.scene if self.w.name == SMALL else self.w.state(self.described_pose, self.shape)
         c = R.ResidentScene(desc, 0, tiles, like=self.rs)
         try:
+            S = self.samples  # a clone starts with the default window, whatever its model has, and renders the default window's frame
+            assert c.sample_window()["next"] == dict(total=S, first=0, divisor=S, accumulate=0, advance=0), c.sample_window()
+            self.same_bound(c, self.shape, "the clone's clip bound")
             c.render()
             got = [np.asarray(p).reshape(sc.height, sc.width) for p in c.readback()]
             mine = np.ones((sc.height, sc.width), bool)
@@ -680,6 +961,7 @@ def play(name, seed, part, last=None, report=None):
     rs = R.ResidentScene(w.state(*seq["start"]), 0)
     try:
         s = Session(w, seq["start"], rs)
+        s.same_window("a fresh scene")
         for i, step in enumerate(steps):
             try:
                 s.apply(step)

@@ -4,13 +4,15 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
 import pytest
 
+import oracle_lib as O
 import sample_window_cases as WC
-from conftest import ROOT
+from conftest import ROOT, golden_names
 from opencl_render_amd import raytrace as R
 
-U32_MAX = 2 ** 32 - 1
+U32_MAX = WC.U32_MAX
 
 
 def check(samples, *window):
@@ -34,19 +36,7 @@ def test_header_python_and_library_agree(hip_lib):
         assert callable(getattr(R.ResidentScene, method))
 
 
-REFUSALS = [
-    # (S, window, what the error text must say)
-    (2, (0, 0, 2, 0, 0), "total must be >= 1"),
-    (2, (8, 0, 0, 0, 0), "divisor must be >= 1"),
-    (2, (8, 7, 8, 0, 0), "reaches past total"),
-    (3, (U32_MAX, U32_MAX - 2, 1, 0, 0), "reaches past total"),      # f + S = 2^32 - 2 + 3 wraps in 32 bits: compared in 64
-    (U32_MAX, (U32_MAX, 1, 1, 0, 0), "reaches past total"),
-    (2, (8, 0, 8, 2, 0), "accumulate must be 0 or 1"),
-    (2, (8, 0, 8, 0, 2), "advance must be 0 or 1"),
-    (2, (8, 0, 8, U32_MAX, 0), "accumulate must be 0 or 1"),
-    (3, (8, 0, 8, 0, 1), "multiple of sampleCount"),                  # N % S != 0
-    (2, (8, 1, 8, 0, 1), "advance needs first"),                      # f % S != 0
-]
+REFUSALS = WC.REFUSALS  # (samples, window, what the error text must say): shared with the session sequences
 
 
 @pytest.mark.parametrize("samples, window, text", REFUSALS)
@@ -106,6 +96,68 @@ def test_progressive_cases_name_goldens_with_the_stated_sample_counts():
     assert abs(WC.shares(planes)[1] - 0.058) < 0.0006 and (sc.light_col[:, :3] < 0).any()
     # the golden of the scene of the off-grid windows shows no saturation
     assert WC.shares(WC.golden("lambert_distant")[1])[1] == 0.0
+
+
+# ---- the window oracle (oracle_lib.oracle_render_window), tied to the goldens and to the oracle's N-sample frames -----------------------
+THREADS = min(os.cpu_count() or 1, 16)
+
+
+@pytest.mark.parametrize("name", golden_names())
+def test_the_window_oracle_under_the_default_window_is_the_golden(name):
+    sc, want = WC.golden(name)
+    S = sc.sample_count
+    got = O.oracle_render_window(sc, S, 0, S, threads=THREADS)
+    assert WC.differing(got, want) == 0
+
+
+@pytest.mark.parametrize("name, samples, total", WC.PROGRESSIVE)
+def test_chained_windows_of_the_oracle_are_its_n_sample_frame(name, samples, total):
+    """degenerate_and_outside (5.8 % saturated, one negative light) proves the order of the saturating adds."""
+    sc, _ = WC.golden(name)
+    chain = WC.window_chain(name, total)
+    assert len(chain) == total // samples
+    assert WC.differing(chain[-1], WC.oracle_frame(name, total)) == 0
+    for a, b in zip(chain, chain[1:]):
+        assert WC.differing(a, b) > 0  # (every window adds something)
+
+
+def test_chained_windows_off_the_sample_grid_are_the_oracles_frame():
+    """lambert_distant, N = 5: S = 2 at f = 0 and f = 2, then a one-sample scene at f = 4."""
+    sc, _ = WC.golden("lambert_distant")
+    assert sc.sample_count == 2
+    planes = O.oracle_render_window(sc, 5, 0, 5, threads=THREADS)
+    planes = O.oracle_render_window(sc, 5, 2, 5, onto=planes, threads=THREADS)
+    planes = O.oracle_render_window(WC.with_samples(sc, 1), 5, 4, 5, onto=planes, threads=THREADS)
+    assert WC.differing(planes, WC.oracle_frame("lambert_distant", 5)) == 0
+
+
+def test_the_window_oracle_copies_what_it_adds_onto():
+    sc, _ = WC.golden("lambert_distant")
+    first = O.oracle_render_window(sc, 8, 0, 8, threads=THREADS)
+    kept = [p.copy() for p in first]
+    second = O.oracle_render_window(sc, 8, 2, 8, onto=first, threads=THREADS)
+    assert WC.differing(first, kept) == 0 and WC.differing(second, first) > 0
+    assert all((b >= a).all() for a, b in zip(first, second))  # (no negative light in this scene: the adds only raise)
+
+
+def test_a_smaller_divisor_saturates_more():
+    name, S, N = "degenerate_and_outside", 3, 12
+    sc, _ = WC.golden(name)
+    assert sc.sample_count == S
+    full = O.oracle_render_window(sc, N, 3, N, threads=THREADS)
+    half = O.oracle_render_window(sc, N, 3, N // 2, threads=THREADS)
+    assert WC.shares(half)[1] > WC.shares(full)[1]
+    assert sum(int((p == WC.SATURATED).sum()) for p in half) > sum(int((p == WC.SATURATED).sum()) for p in full)
+
+
+def test_the_window_oracle_refuses_what_the_library_refuses():
+    sc, _ = WC.golden("lambert_distant")
+    planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
+    osc = O.oracle_scene(sc, planes)
+    for total, first, divisor in ((0, 0, 2), (8, 0, 0), (8, 7, 8), (U32_MAX, U32_MAX - 1, 1)):
+        assert O.oracle().rt_oracle_render_window(C.byref(osc), total, first, divisor, 0, sc.pixels, 1) == 0
+        assert check(sc.sample_count, total, first, divisor, 0, 0)[0] == -1
+    assert not any(p.any() for p in planes)
 
 
 def test_command_line_refusals_and_acceptance():

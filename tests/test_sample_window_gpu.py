@@ -1,21 +1,28 @@
 """Sample windows on the MI355X (run with -m gpu): the default window leaves every frame alone; progressive rendering equals the oracle's
 N-sample frame bit for bit on both pipelines, under pipeline modes, sample batches and tile deals; windows off the S grid; accumulating
 frames are watched, never redone; the divisor; advance under planned and redone frames; the render passes of a window; the temporal
-chain fed with a sequence; refusals on a scene."""
+chain fed with a sequence; refusals on a scene; and single window frames against the window oracle (oracle_lib.oracle_render_window):
+every frame of a progressive run and of a sequence, freely chosen windows (64-bit seeds among them), a progressive run that goes on
+over camera, geometry and pipeline changes, and sequences under split logic rounds and the ray clip."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import camera_cases as CC
+import geometry_cases as GC
 import motion_oracle as MO
+import oracle_lib as O
 import sample_window_cases as WC
 import temporal_oracle as TO
 from conftest import golden_names
-from opencl_render_amd import raytrace as R
+from geometry_checks import update_to
+from opencl_render_amd import raytrace as R, scene as SCN
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
+U32_MAX = 2 ** 32 - 1
 ZERO = dict(total=0, first=0, divisor=0, accumulate=0, advance=0)
 
 
@@ -401,5 +408,190 @@ def test_command_line_progressive_and_sequence(tmp_path):
             F.write_ppm(str(tmp_path / "want.ppm"), *[p.reshape(64, 96) for p in frame(rs)])
             assert open(tmp_path / f"seq_{i:03d}.ppm", "rb").read() == open(tmp_path / "want.ppm", "rb").read(), f"sequence frame {i}"
             assert open(tmp_path / f"seq_{i:03d}.ppm", "rb").read() != open(tmp_path / f"same_{i:03d}.ppm", "rb").read()
+    finally:
+        rs.close()
+
+
+# ---- single window frames against the window oracle ------------------------------------------------------------------------------------------
+# A window frame has an expected value of its own (oracle_lib.oracle_render_window): no sum in which two windows' errors could cancel, no
+# other device frame as the reference.  Modes: the wavefront pipeline with its first frame watched and the later ones planned, every
+# frame watched, every frame planned (a frame of the default window goes first), and the megakernel.
+ORACLE_MODES = ("wavefront", "watched", "planned", "megakernel")
+
+
+def opened(sc, mode, monkeypatch, env=None):
+    """A fresh scene under `mode` (and the RT_* variables in env); under "planned" a frame of the default window has been rendered, so the
+    next frame that does not continue from the tile buffer is issued from the launch plan."""
+    for k, v in dict(env or {}, **({"RT_WF_BLOCKING": "1"} if mode == "watched" else {})).items():
+        monkeypatch.setenv(k, v)
+    rs = R.ResidentScene(sc, 0)
+    try:
+        if mode == "megakernel":
+            rs.set_pipeline(R.PIPELINE_MEGAKERNEL)
+        if mode == "planned":
+            rs.render()
+            rs.sync()
+            assert not rs.finish()
+    except BaseException:
+        rs.close()
+        raise
+    return rs
+
+
+def checked_frame(rs, want, what):
+    """Renders a frame that must not be redone, reads it back and compares it with `want`; returns the read-back."""
+    rs.render()
+    rs.sync()
+    assert not rs.finish(), f"{what}: the frame was rendered again"
+    got = [p.copy() for p in rs.readback()]
+    assert_planes(got, want, what)
+    return got
+
+
+@pytest.mark.parametrize("mode", ["wavefront", "planned", "megakernel"])  # (a continuing frame is watched whatever the mode)
+@pytest.mark.parametrize("name, samples, total", WC.PROGRESSIVE)
+def test_every_frame_of_a_progressive_sequence_equals_the_chained_oracle(name, samples, total, mode, monkeypatch):
+    sc, _ = WC.golden(name)
+    chain = WC.window_chain(name, total)
+    rs = opened(sc, mode, monkeypatch)
+    try:
+        rs.set_sample_window(total, 0, total, accumulate=True, advance=True)
+        for i, want in enumerate(chain + chain[:1]):  # (the frame after the last starts from zero again: f == 0)
+            f = i * samples % total
+            assert rs.sample_window()["next"] == window(total, f, total, 1, 1)
+            checked_frame(rs, want, f"{name}, {mode}: the tile buffer after frame {i} (f = {f})")
+    finally:
+        rs.close()
+
+
+@pytest.mark.parametrize("mode", ORACLE_MODES)
+@pytest.mark.parametrize("name, samples, total", WC.PROGRESSIVE)
+def test_every_frame_of_a_sequence_equals_the_window_oracle(name, samples, total, mode, monkeypatch):
+    sc, _ = WC.golden(name)
+    rs = opened(sc, mode, monkeypatch)
+    try:
+        rs.set_sample_window(total, 0, samples, advance=True)
+        for i in range(total // samples + 1):
+            f = i * samples % total
+            checked_frame(rs, WC.window_frame(name, total, f, samples), f"{name}, {mode}: frame {i}, window {{{total}, {f}, {samples}}}")
+            assert rs.sample_window() == {"next": window(total, (f + samples) % total, samples, 0, 1), "last": window(total, f, samples, 0, 1)}
+    finally:
+        rs.close()
+
+
+# {7, 3, 3} on an S = 2 scene: neither N nor f a multiple of S, D neither N nor S (1.5 times over-bright).  {2^32 - 1, 2^32 - 2, 1} on an
+# S = 1 scene: pixel * N passes 2^32 from pixel 2 on, and f + 1 = 2^32 - 1 is the largest sample id there is, so the seed is right only
+# where product and sum are formed in 64 bits.  D = 1 = S is full brightness; primary_only casts no secondary rays, which keeps the
+# frame from saturating: the oracle's frame has 9.8 % of its plane values non-zero and 0.038 % saturated.
+FREE_WINDOWS = [("lambert_distant", 2, (7, 3, 3)), ("mirror_hall", 2, (7, 3, 3)), ("primary_only", 1, (U32_MAX, U32_MAX - 1, 1))]
+
+
+@pytest.mark.parametrize("mode", ORACLE_MODES)
+@pytest.mark.parametrize("name, samples, win", FREE_WINDOWS, ids=lambda v: v if isinstance(v, str) else None)
+def test_a_freely_chosen_window_equals_the_window_oracle(name, samples, win, mode, monkeypatch):
+    sc, golden = WC.golden(name)
+    assert sc.sample_count == samples
+    want = WC.window_frame(name, *win)
+    nonzero, saturated = WC.shares(want)
+    assert nonzero > 0.05 and saturated < 0.01, (nonzero, saturated)
+    assert WC.differing(want, golden) > 0  # (other samples than the default window's)
+    rs = opened(sc, mode, monkeypatch)
+    try:
+        rs.set_sample_window(*win)
+        checked_frame(rs, want, f"{name}, {mode}: window {win}")
+        assert rs.sample_window() == {"next": window(*win), "last": window(*win)}
+        checked_frame(rs, want, f"{name}, {mode}: window {win} again")  # (no advance, no accumulate: the same frame, now planned)
+    finally:
+        rs.close()
+
+
+# ---- a progressive run goes on after the scene changed ---------------------------------------------------------------------------------------
+MOVED = [("lambert_distant", "pan", "twist"), ("mirror_hall", "orbit90", "scale")]
+_moved = {}
+
+
+def moved_states(name, pose, shape):
+    """The golden scene, the scene seen from `pose`, and `shape` of it seen from `pose`: Scenes with the oracle's grid and lists."""
+    if name not in _moved:
+        base, _ = WC.golden(name)
+        bent = GC.with_arrays(base, *GC.arrays(base, shape), lists=False)
+        bent.box_min, bent.grid_start, bent.grid_list = O.oracle_scene_grid(bent)
+        _moved[name] = (base, CC.posed(base, pose), CC.posed(bent, pose))
+    return _moved[name]
+
+
+@pytest.mark.parametrize("start", [R.PIPELINE_WAVEFRONT, R.PIPELINE_MEGAKERNEL], ids=["wavefront_first", "megakernel_first"])
+@pytest.mark.parametrize("name, pose, shape", MOVED)
+def test_a_progressive_run_continues_over_camera_geometry_and_pipeline_changes(name, pose, shape, start):
+    """The header defines a frame that continues as its addends on top of what the tile buffer holds, whatever filled it: a camera move, a
+    geometry update and a change of pipeline leave the tile buffer and the window alone, so each frame is the window oracle of the state
+    it is rendered in, onto the read-back of the frame before."""
+    base, turned, bent = moved_states(name, pose, shape)
+    S, N = base.sample_count, 8
+    assert N % S == 0 and N // S >= 4
+    other = R.PIPELINE_MEGAKERNEL if start == R.PIPELINE_WAVEFRONT else R.PIPELINE_WAVEFRONT
+
+    def nothing(rs):
+        pass
+
+    def move_camera(rs):
+        rs.set_camera(turned.eye, turned.eye_to_top_left, turned.left_to_right, turned.top_to_bottom, turned.pixel_size_inv)
+
+    def move_vertices(rs):
+        update_to(rs, bent)
+
+    steps = [("the first frame", base, nothing), (f"after the camera move to {pose}", turned, move_camera),
+             (f"after the update to {shape}", bent, move_vertices), ("after the change of pipeline", bent, lambda rs: rs.set_pipeline(other))]
+    rs = R.ResidentScene(base, 0)
+    try:
+        rs.set_pipeline(start)
+        rs.set_sample_window(N, 0, N, accumulate=True, advance=True)
+        held = None
+        for i, (what, state, change) in enumerate(steps):
+            change(rs)
+            f = i * S
+            assert rs.sample_window()["next"] == window(N, f, N, 1, 1), what
+            want = O.oracle_render_window(state, N, f, N, onto=held, threads=WC.THREADS)
+            fresh = O.oracle_render_window(state, N, f, N, threads=WC.THREADS)
+            if held is not None:  # the inputs: the frame adds something, and it shows that it started from the buffer
+                assert WC.differing(want, held) > 0 and WC.differing(want, fresh) > 0, what
+                stale = O.oracle_render_window(steps[i - 1][1], N, f, N, onto=held, threads=WC.THREADS)
+                assert i == 3 or WC.differing(want, stale) > 0, f"{what}: the change does not show in the oracle's frame"
+            held = checked_frame(rs, want, f"{name}, {what} (f = {f})")
+            assert rs.sample_window()["last"] == window(N, f, N, 1, 1), what
+    finally:
+        rs.close()
+
+
+# ---- split logic rounds and the ray clip -----------------------------------------------------------------------------------------------------
+_soup = {}
+
+
+def clip_soup():
+    """The frustum soup of tests/test_ray_clip_gpu.py (128 x 128, 10 000 triangles, opaque and diffuse: the class that takes split rounds)
+    at S = 2, with the window oracle's frames of the sequence {6, f, 2}."""
+    if not _soup:
+        sc = SCN.make_soup(128, 128, 10_000, 0.02, seed=91, samples=2)
+        R.build_lists(sc)
+        _soup["scene"] = sc
+        _soup["frames"] = {f: O.oracle_render_window(sc, 6, f, 2, threads=WC.THREADS) for f in (0, 2, 4)}
+    return _soup["scene"], _soup["frames"]
+
+
+@pytest.mark.parametrize("clip", ["0", "1"])
+@pytest.mark.parametrize("split", ["0", "1"])
+def test_sequence_frames_equal_the_window_oracle_under_split_rounds_and_the_ray_clip(split, clip, monkeypatch):
+    sc, frames = clip_soup()
+    assert R.path_class(sc) == R.PATH_CLASS_OPAQUE_DIFFUSE
+    assert len({tuple(p.tobytes() for p in v) for v in frames.values()}) == 3  # (three different frames)
+    rs = opened(sc, "wavefront", monkeypatch, {"RT_WF_LOGIC_SPLIT": split, "RT_WF_RAY_CLIP": clip})
+    try:
+        assert len(rs.clip_planes()) >= 1
+        rs.set_sample_window(6, 0, 2, advance=True)
+        for i in range(4):  # (the first frame watched, the others planned)
+            f = 2 * i % 6
+            checked_frame(rs, frames[f], f"logic_split {split}, ray_clip {clip}: frame {i}, window {{6, {f}, 2}}")
+            assert (rs.shade_log(4)[0] > 0) == (split == "1"), f"frame {i}: split rounds issued {rs.shade_log(4)[0]}"
+        assert rs.clip_applied() == (len(rs.clip_planes()) if clip == "1" else 0)
     finally:
         rs.close()

@@ -2,13 +2,17 @@
 Eulerian circuits over the operation kinds, cut into sequences of at most 40 steps, the random walks and the named regressions -- is
 played on a fresh scene, and after every step the device's answer is compared with the oracle's answer for the model's state (frames as
 integers, lists and device arrays, motion and temporal accumulation as float bits, passes, denoise, AO and the bake against a twin
-created fresh from the model's Scene, refusals by code and text).  A test stops at the first mismatch and names the scene, the seed,
+created fresh from the model's Scene, refusals by code and text).  The wide seeds add the sample window and the moments history to
+the state: every frame is the window oracle's frame of the model's window, onto the model's planes where it continues; the scene's
+window is compared with the model's after every step; temporal_variance equals variance_oracle over the model's planes and history;
+the clip bound is compared after every update and in every clone.  A test stops at the first mismatch and names the scene, the seed,
 the step, every step so far and the array that differed; nothing is tried again.  tests/test_session.py shows without a GPU that the
 sequences are not vacuous and that the model is right; tests/session_replay.py plays one sequence by hand.
 
 Sizing, measured on the MI355X in one run of this file with tests/test_temporal_gpu.py: the temporal suite's slowest test (the camera
-chain on axis_class_sun) takes 1.85 s, so a sequence may take 5.55 s.  The slowest sequence takes 3.19 s (axis_near_axis_mixed, 25
-steps); every mirror_hall sequence of 40 steps and both walks of 60 stay below 1.3 s.  The module's fixture takes 61 s: it makes the
+chain on axis_class_sun) takes 1.85 s, so a sequence may take 5.55 s.  The slowest sequence takes 4.4 s (axis_near_axis_mixed, 25
+steps, with the clip bound checked after its update and in its clones); every mirror_hall sequence of 40 steps and its walks of 60
+stay below 1.8 s, and the two halves of the larger scene's wide walk below 2 s.  The module's fixture takes 63 s: it makes the
 oracles' products once -- the grids of the larger scene's six shapes at 7 s each, prep_oracle's records and dense views, and the planes
 and walks of every visited state -- so that a sequence's time is the device's and the comparisons'.  On the larger scene (12.6 million
 grid pairs) the check of the device arrays after an update takes 1.2 s; a sequence there holds at most two updates and 25 steps."""
@@ -31,6 +35,7 @@ def need_gpu(hip_lib):
         for shape in spec["shapes"]:
             SC.world(name).shape_scene(shape)
         SC.world(name).warm(SC.visited(name))
+        SC.warm_wide(name)
     yield
     MC.use_grid_builder(R.build_scene_grid)
     R.tune("build_list_limit", 0xFFFFFFFF)
