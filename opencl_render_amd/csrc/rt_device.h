@@ -153,7 +153,8 @@ struct RtDevScene {
 #define RT_WF_ERR_GRID 2u     // a planned frame's trace grid was smaller than the round's entries: entries were not traced; the host renders
                               // the frame again with the worst-case grid (rt_frame.cpp, frame_finish).  Also: a planned frame skipped a shade launch
                               // (the plan said no bounce hit anything in that round) and the round listed a path for it
-#define RT_WF_ERR_SPLIT 4u    // wf_answer_kernel met a path that is not of the shape it knows (opaque-diffuse class, look-ahead on): the frame is invalid
+#define RT_WF_ERR_SPLIT 4u    // wf_answer_kernel met a path that is not of the shape it knows (opaque-diffuse class, look-ahead on), or a class kernel
+                              // a path that asked for a ring slot other than the class layout's one bounce slot: the frame is invalid
 // per-round control words, three sets used in turn like the queue lengths (round r uses set r % 3): logic(r-1) fills set r,
 // scatter(r) and trace(r) read it, logic(r) zeroes set (r + 2) % 3 for logic(r+1)
 #define RT_WF_CTL_COUNTS 0                                   // [RT_WF_QSHARDS] queue lengths
@@ -192,9 +193,14 @@ struct RtWavefront {
     uint4 *meta;             // x: output slot (localPixel*samplesInBatch + sb)  y: localPixel  w: hit triangle
                              // z: head | tail<<4 | stage<<8 | attenuation stored<<9 | look-ahead state<<10 | look-ahead ring index<<12 | light<<16
     unsigned long long *laKey; // answer (hitKey) of the path's look-ahead ray while it waits to be consumed
-    float4 *outc;            // accumulated colour xyz
-    float4 *ring;            // [capacity][12][3] the pixel's ray queue (:459-468): o.xyz,tmin | d.xyz,excluded | weight.xyz, bounces<<1|fromCamera;
-                             // slot `head` is the ray in flight
+    float4 *outc;            // accumulated colour xyz.  Opaque-diffuse class: w = the far end (tmax) of the ray the path is parked on -- lmax of
+                             // its shadow ray, which is all the answer's reader wants of the entry (wf_answer_kernel and the class kernel read
+                             // it here instead of fetching the 64-byte entry); the general machine leaves w = 0 and reads its entry
+    float4 *ring;            // the pixel's ray queue (:459-468), 36 quads per path, addressed through rt_path_state.h.  General class:
+                             // [capacity][12][3], o.xyz,tmin | d.xyz,excluded | weight.xyz, bounces<<1|fromCamera; slot `head` is the ray in
+                             // flight.  Opaque-diffuse class (RtDevScene::pathClass): the same allocation as [capacity] camera directions (slot 0,
+                             // quad 1) followed by [capacity] bounce records of 64-byte pitch (slot 1, quads 0..2, the fourth spare); the rest
+                             // of the allocation is not touched.  A frame uses one layout from its primary stage to its last round
     // what a hit still needs once its spawns are made and a shadow ray is in flight (everything else was folded at shading time):
     float4 *shP;             // P.xyz = (1-out)*weight*(1-transparency)*texture, the factors of :649-651 in the reference's order; w: N.L of this light
     float4 *shFace;          // xyz: the face[] entry that :647 will select (the other one is dead); w: 1 if front facing

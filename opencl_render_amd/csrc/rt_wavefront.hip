@@ -21,11 +21,13 @@
 // so the planes are bit-identical to the single-launch kernel (rt_kernels.hip) and to the oracle.
 #include "rt_devfuncs.h"
 #include "rt_launch.h"
+#include "rt_path_state.h"
 #include "rt_ray_clip.h"
 
 namespace {
 
 enum { WS_RAY = 0, WS_SHADOW = 1 };
+static_assert(RT_PATH_RING_SLOTS == RT_RING, "rt_path_state.h addresses the ring allocation");
 
 __device__ __forceinline__ float4 pack4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 __device__ __forceinline__ V3 xyz(float4 v) { return mk(v.x, v.y, v.z); }
@@ -247,7 +249,10 @@ __device__ __forceinline__ void wf_primary_body(const RtDevScene &S, const RtWav
         W.meta[a] = make_uint4(outSlot, localPixel, 0u | (1u << 4) | ((uint32_t)WS_RAY << 8), hit_tri);
         // ring slot 0 = the camera ray (:490-508).  Only its direction is stored: round 0 of wf_logic_kernel, the slot's one
         // reader, knows the rest (origin = eye, weight 1, maxBounces 12, fromCamera), as it knows that nothing is collected yet.
-        W.ring[(size_t)a * (RT_RING * 3) + 1] = pack4(dir, __uint_as_float(RT_NONE));
+        // Where the slot lives depends on the scene's path class (rt_path_state.h; the same choice in every lane): in the opaque-diffuse
+        // class the directions are a dense plane, a wave's store is whole lines.
+        const size_t dirAt = S.pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE ? rt_path_class_quad(W.capacity, a, 0u, 1u) : rt_path_ring_quad(a, 0u, 1u);
+        W.ring[dirAt] = pack4(dir, __uint_as_float(RT_NONE));
         W.res[a] = make_uint4(hit_tri, __float_as_uint(hit_t), __float_as_uint(hit_l1), __float_as_uint(hit_l2));
     }
     if (PASSES && valid) {
@@ -644,7 +649,8 @@ __global__ __launch_bounds__(256, RT_WF_ANSWER_WAVES) void wf_answer_kernel(cons
             unsigned long long laKey = ~0ull;
             if (who.y != 0xffffffffu) laKey = W.hitKey[in][who.y];
             const uint4 meta = W.meta[a];
-            V3 out = xyz(W.outc[a]);
+            const float4 oc = W.outc[a]; // xyz: the colour so far; w: the far end of the shadow ray the path is parked on (rt_wf_logic_body.h)
+            V3 out = xyz(oc);
             int head = (int)(meta.z & 15u);
             const int tail = (int)((meta.z >> 4) & 15u);
             const uint32_t stage = (meta.z >> 8) & 1u, laState = (meta.z >> 10) & 3u;
@@ -653,7 +659,7 @@ __global__ __launch_bounds__(256, RT_WF_ANSWER_WAVES) void wf_answer_kernel(cons
             bool finished = false;
             if (stage == WS_SHADOW) { // PC_SHADOW_RESULT (:612-626) of light 0
                 const float4 sp = W.shP[a], sf = W.shFace[a];
-                const float lmax = reinterpret_cast<const float *>(W.ent[in] + 4 * (size_t)q)[11];
+                const float lmax = oc.w;
                 const V3 zero = mk(0.f, 0.f, 0.f);
                 V3 face = xyz(sf), atten = mk(1.f, 1.f, 1.f);
                 if (key != ~0ull) { atten.x *= zero.x; atten.y *= zero.y; atten.z *= zero.z; }

@@ -98,6 +98,7 @@
         for (int i = 1; i < 12; ++i) dg[i] = 0;
 #endif
         bool emit = false, emitLa = false;
+        bool odd = false; // (class only) the path asked for a ring slot its layout does not have: RT_WF_ERR_SPLIT below
         V3 ro = mk(0, 0, 0), rd = mk(0, 0, 0), lo3 = mk(0, 0, 0), ld3v = mk(0, 0, 0);
         float rtmin = 0.f, rtmax = 0.f, latmin = 0.f;
         uint32_t rexcl = RT_NONE, laexcl = RT_NONE, a = 0;
@@ -128,17 +129,29 @@
                 key = W.hitKey[in][q];
                 if (who.y != 0xffffffffu) laKeyEarly = W.hitKey[in][who.y];
             }
-            float4 *ringA = W.ring + (size_t)a * (RT_RING * 3);
+            // The class layout of the ring allocation (rt_path_state.h): the camera directions are a dense plane, and behind it each path has
+            // ONE bounce record, ring slot 1 -- round 0 spawns it at tail == 1, later rounds take it at head == 1.  The head / tail arithmetic
+            // is the general machine's; a slot other than 1 is never indexed, the lane sets `odd` instead.
+            // (the record's address is made where it is used, not carried across the state machine)
+            auto bounce_of = [&]() -> float4 * {
+                uint32_t path = a;
+                asm volatile("" : "+v"(path));
+                return W.ring + rt_path_class_quad(W.capacity, path, RT_PATH_CLASS_BOUNCE_SLOT, 0u);
+            };
             uint64_t rng = W.rng[a];
             const uint4 meta = FIRST ? make_uint4(0u, 0u, 0u | (1u << 4) | ((uint32_t)WS_RAY << 8), res_tri) : W.meta[a];
             V3 out = mk(0.f, 0.f, 0.f);
+            float parkedLmax = 0.f; // the far end of the shadow ray the path is parked on: it travels in outc.w
             float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0, c2 = c0;
             TriRow row;
             row.tri = RT_NONE;
             if (FIRST) {
-                c0 = pack4(ld3(S.eye), 0.f); c1 = ringA[1]; c2 = make_float4(1.f, 1.f, 1.f, __uint_as_float((12u << 1) | 1u));
+                c0 = pack4(ld3(S.eye), 0.f); c1 = W.ring[rt_path_class_quad(W.capacity, a, 0u, 1u)]; c2 = make_float4(1.f, 1.f, 1.f, __uint_as_float((12u << 1) | 1u));
                 load_tri_row(S, res_tri, row);
-            } else out = xyz(W.outc[a]);
+            } else {
+                const float4 oc = W.outc[a];
+                out = xyz(oc); parkedLmax = oc.w;
+            }
             uint32_t hit_tri = meta.w;
             int head = (int)(meta.z & 15u), tail = (int)((meta.z >> 4) & 15u);
             const uint32_t stage = (meta.z >> 8) & 1u;
@@ -161,7 +174,7 @@
             int cur_bounces = 0;
             V3 n = mk(0, 0, 0), where = mk(0, 0, 0), P = mk(0, 0, 0), face = mk(0, 0, 0), toL = mk(0, 0, 0);
             float ndl = 0.f, lmin = 0.f, lmax = 0.f;
-            bool front = false, finished = false, rngDirty = false, outDirty = false, shade = false;
+            bool front = false, finished = false, rngDirty = false, shade = false;
             uint32_t emitStage = WS_RAY;
             int firstSpawnSlot = -1;
             float4 firstSpawn0 = make_float4(0.f, 0.f, 0.f, 0.f), firstSpawn1 = firstSpawn0;
@@ -174,7 +187,9 @@
             auto next_ray = [&]() -> bool {
                 head = (head + 1) % RT_RING;
                 if (head == tail) { finished = true; return false; }
-                take_ray(ringA[head * 3 + 0], ringA[head * 3 + 1], ringA[head * 3 + 2]);
+                odd |= head != (int)RT_PATH_CLASS_BOUNCE_SLOT;
+                const float4 *bounce = bounce_of();
+                take_ray(bounce[0], bounce[1], bounce[2]);
                 return true;
             };
             auto emit_ray = [&]() { emit = true; emitStage = WS_RAY; ro = cur_o; rd = cur_d; rtmin = cur_tmin; rtmax = RT_INF; rexcl = cur_excl; };
@@ -195,7 +210,6 @@
                 out.x += P.x * face.x;
                 out.y += P.y * face.y;
                 out.z += P.z * face.z;
-                outDirty = true;
             };
 
             bool advance = false; // the hit in hand is done: on to the next ring entry
@@ -206,9 +220,9 @@
             } else if (!SHADE && stage == WS_SHADOW) { // PC_SHADOW_RESULT (:612-626) of light 0
                 const float4 sp = W.shP[a], sf = W.shFace[a];
                 P = xyz(sp); ndl = sp.w; face = xyz(sf); front = (sf.w != 0.f);
-                // of the answered entry only the ray's far end is read, of the answer only whether there is one: which occluder, and where
+                // of the answered ray only its far end is wanted, of the answer only whether there is one: which occluder, and where
                 // along the ray, feeds nothing in this class (no transparency look-up)
-                lmax = reinterpret_cast<const float *>(W.ent[in] + 4 * (size_t)q)[11];
+                lmax = parkedLmax; // (as stored when the shadow ray was emitted; the entry itself is not touched)
                 V3 atten = mk(1.f, 1.f, 1.f);
                 // an occluder's transparency is absent or black in this class: atten becomes 0, so the shadow ray is never sent on (:621-625)
                 if (key != ~0ull) { atten.x *= zero.x; atten.y *= zero.y; atten.z *= zero.z; }
@@ -216,7 +230,9 @@
                 shade_end(); // (no light after light 0)
                 advance = true;
             } else { // a ray's answer: the ray is the ring entry at head
-                take_ray(ringA[head * 3 + 0], ringA[head * 3 + 1], ringA[head * 3 + 2]);
+                odd |= head != (int)RT_PATH_CLASS_BOUNCE_SLOT;
+                const float4 *bounce = bounce_of();
+                take_ray(bounce[0], bounce[1], bounce[2]);
                 res_tri = resolve_hit(S, key, cur_o, cur_d, cur_tmin, RT_INF, cur_excl, res_t, res_l1, res_l2);
                 shade = res_tri != RT_NONE;
                 advance = !shade;
@@ -248,7 +264,6 @@
                 out.x += (1.f - out.x) * lum.x * cur_w.x;
                 out.y += (1.f - out.y) * lum.y * cur_w.y;
                 out.z += (1.f - out.z) * lum.z * cur_w.z;
-                outDirty = true;
                 front = (dot3(n, cur_d) <= 0.f);
                 P.x = (1.f - out.x) * cur_w.x * (1.f - transp.x) * tex.x;
                 P.y = (1.f - out.y) * cur_w.y * (1.f - transp.y) * tex.y;
@@ -269,7 +284,9 @@
                         V3 nd = sphere_scaled(sphere_raw(rng), 1.f);
                         if (frontI != ((0 <= dot3(nd, n)) ? 1 : 0)) { nd.x = -nd.x; nd.y = -nd.y; nd.z = -nd.z; }
                         const float4 s0 = pack4(where, 0.f), s1 = pack4(nd, __uint_as_float(hit_tri));
-                        ringA[tail * 3 + 0] = s0; ringA[tail * 3 + 1] = s1; ringA[tail * 3 + 2] = pack4(w, __uint_as_float(0u));
+                        odd |= tail != (int)RT_PATH_CLASS_BOUNCE_SLOT;
+                        float4 *bounce = bounce_of();
+                        bounce[0] = s0; bounce[1] = s1; bounce[2] = pack4(w, __uint_as_float(0u));
                         if (FIRST) { firstSpawnSlot = tail; firstSpawn0 = s0; firstSpawn1 = s1; }
                         tail = (tail + 1) % RT_RING;
                     }
@@ -323,7 +340,11 @@
                 const int nx = (head + 1) % RT_RING;
                 if (nx != tail) {
                     float4 n0 = firstSpawn0, n1 = firstSpawn1;
-                    if (!FIRST || nx != firstSpawnSlot) { n0 = ringA[nx * 3 + 0]; n1 = ringA[nx * 3 + 1]; }
+                    if (!FIRST || nx != firstSpawnSlot) {
+                        odd |= nx != (int)RT_PATH_CLASS_BOUNCE_SLOT;
+                        const float4 *bounce = bounce_of();
+                        n0 = bounce[0]; n1 = bounce[1];
+                    }
                     emitLa = true; lo3 = xyz(n0); latmin = n0.w; ld3v = xyz(n1); laexcl = __float_as_uint(n1.w);
                     laState = 1u; laIndex = nx;
                 }
@@ -336,7 +357,10 @@
             } else {
                 asm volatile("" : "+v"(a));
                 if (rngDirty) W.rng[a] = rng;
-                if (outDirty) W.outc[a] = pack4(out, 0.f);
+                // A class path parks only behind a hit it shaded (round 0: the camera hit; later: the shadow answer's shade_end or the bounce
+                // hit), so `out` is always dirty here.  Its spare word carries the far end of the ray that goes out -- lmax for a shadow ray
+                // (rtmax == lmax then), which is all the answer's reader wants of the entry; for a ring ray the word is not read.
+                W.outc[a] = pack4(out, rtmax);
                 // (a shadow ray leaves with atten = 1, never stored; the next light index is always 0)
                 const uint32_t flags = (uint32_t)head | ((uint32_t)tail << 4) | (emitStage << 8) | (laState << 10) | ((uint32_t)laIndex << 12);
                 if (FIRST) reinterpret_cast<uint2 *>(W.meta + a)[1] = make_uint2(flags, hit_tri);
@@ -679,6 +703,7 @@
         // Every lane of the wave arrives here: one atomic instruction for the wave's two queue appends.
         uint32_t slot, slotLa;
         wave_append2(&ctlOut[RT_WF_CTL_COUNTS + outShard], emit, &ctlOut[RT_WF_CTL_COUNTS + RT_WF_SHARDS + outShard], emitLa, slot, slotLa);
+        if (LEAN && __ballot(odd) != 0ull && lane == 0u) atomicOr(W.hostStatus + RT_WF_STATUS_ERROR, RT_WF_ERR_SPLIT); // (the frame is invalid)
         slot += outShard * sliceCapOut;
         slotLa += W.capacity + outShard * sliceCapOut;
         asm volatile("" : "+v"(a), "+v"(slot), "+v"(slotLa)); // (addresses made here, not carried across the state machine)
