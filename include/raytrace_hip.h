@@ -305,6 +305,68 @@ typedef struct rtHipGeometryUpdate {
 } rtHipGeometryUpdate;
 int rtHipSceneSetGeometry(rtHipScene *scene, const rtHipGeometryUpdate *update);
 
+/* SCENE EDITS: LIGHTS AND MATERIALS.  The lights, the material tables and atlas, and the triangles' material ids of a resident scene,
+ * replaced in place: rtHipSceneSetLights takes six new light arrays; rtHipSceneSetMaterials takes new tables and atlas
+ * (replaceMaterials = 1), new material ids (triMaterial != NULL), or both.  A light is a few hundred bytes; none of these needs a new scene.
+ *   Equivalence.  After a call returns 0 the scene is, for everything the public API shows, the scene rtHipSceneCreate would have made
+ *   from the same description with the light arrays, the material tables / atlas and / or triMaterial replaced, the camera and the shape
+ *   in effect (after any rtHipSceneSetCamera / rtHipSceneSetGeometry) staying as they are: every later frame on both pipelines, pass,
+ *   surface pass (albedo and bump-mapped normals change with the materials), denoise, AO image, AO bake (its `material` filter reads the
+ *   id word), ray query and motion output is bit-identical to that scene's, and rtHipTestPathClass equals rtHipScenePathClass of that
+ *   description: a second light, or a reflective, transparent or luminous channel, moves the scene from the opaque-diffuse class to the
+ *   general one, and taking them away moves it back.
+ *   What a call leaves alone.  Geometry, grid, camera lists, tile set, pipeline, pass mask and stage-timing switch; the sample window,
+ *   both what rtHipSceneGetSampleWindow reports as `next` and as `last`; the contents of the tile, pass and surface buffers (an
+ *   accumulating window is not wiped); the motion reference and the temporal / moments history.  Whether a re-lit frame may blend with
+ *   older ones is the CALLER's decision: call rtHipSceneTemporalReset where it may not.
+ *   Light count.  Path state that only scenes of several lights use (16 + 8 bytes per path) is made by the first edit that brings a
+ *   second light and kept from then on; no other path state is touched, whichever way the count crosses the one / several boundary.
+ *   Ordering.  Synchronous on the scene's own stream like rtHipSceneSetCamera: the call waits for what was issued there, planned frames
+ *   are verified first, and on return the edit is in effect for everything issued afterwards; the launch plan is dropped, the next frame
+ *   is a watched one.  With triMaterialOnDevice == 1 the CALLER has synchronised the stream that produced the ids before the call.
+ *   Transactional.  New tables, atlas and light arrays are built into storage the frames do not read and take the old ones' place at
+ *   the very end; the old ones are freed after that.  Material ids are checked completely, on the device, before the first one is
+ *   stored.  On any failure the scene renders what it rendered before and holds its tables and light arrays at their old addresses.
+ *   Returns -1 for a NULL argument, lightCount >= 65536, a NULL light array with lightCount > 0, a NULL table with materialCount > 0, a
+ *   channel of w > 0 texels a row whose matStart is negative or whose start + w * h exceeds texturesSize (w and h are full 32-bit values:
+ *   the sum is formed without wrapping), a triMaterial that is not device memory of the scene's device, 4-byte aligned and T ids long
+ *   when triMaterialOnDevice == 1 (checked like rtHipSceneIntersectDevice's pointers), or an update that brings neither tables nor ids;
+ *   -5 with the text "scene rejected (0x..): ..." for an id >= materialCount among the ids that will be in effect -- the new triMaterial,
+ *   or, with triMaterial == NULL and a smaller materialCount, the RESIDENT ids; every negative id is legal ("no material") --; -4 when
+ *   device memory could not be had; -2 for any other HIP failure; each with a text in rtHipLastError().  rtHipLightsCheck and
+ *   rtHipMaterialsCheck decide everything that needs neither a scene nor a GPU (0, or -1 with the text); the Set calls run them first.
+ *   Values.  No light or texel value is refused: NaN, infinities, negative colours render as they would in a scene created with them.
+ *   Ids.  The material id lives in one word of a triangle's 96-byte shading row; new ids are written into the rows in use, and a later
+ *   rtHipSceneSetGeometry carries them over.  Host ids are staged to the device; device ids are read in place.
+ *   Peers.  Instances made with rtHipSceneCreateLike and instances over tile subsets are edited one by one by the caller.  An edited
+ *   scene can be the `like` of a new instance whose description describes the edited state.
+ *   Memory.  New tables and arrays replace the old ones; host ids are staged in 4 bytes per triangle made by the first call that brings
+ *   some.  Everything is counted in rtHipSceneBytes and freed with the scene; repeating an edit of the same sizes leaves rtHipSceneBytes
+ *   unchanged from the second repetition on.
+ *   rtHipSceneEditTimes gives the device time of the last successful edit's stages, from events on the scene's stream, in ms: [0] the
+ *   light arrays, [1] the material tables and atlas, [2] the id check and the id store (0 for a stage the edit did not have). */
+typedef struct rtHipLights {            /* host arrays, as in rtHipSceneDesc */
+    cl_uint lightCount;
+    const cl_int *lightType;
+    const cl_float3 *lightPos, *lightDir, *lightCol;
+    const cl_float *lightRadius, *lightHalfAtt;
+} rtHipLights;
+typedef struct rtHipMaterialUpdate {
+    cl_int  replaceMaterials;           /* 0: keep the resident tables and atlas; the five fields below are ignored */
+    cl_uint materialCount;
+    const cl_uint2 *matSize;            /* 5 per material */
+    const cl_int   *matStart;           /* 5 per material */
+    cl_uint texturesSize;
+    const cl_uchar3 *textures;
+    const cl_int *triMaterial;          /* T ids (T = the scene's triangle count), or NULL = keep the resident ids */
+    cl_int  triMaterialOnDevice;        /* 1: triMaterial is device memory of the scene's device, 4-byte aligned */
+} rtHipMaterialUpdate;
+int rtHipLightsCheck(const rtHipLights *lights);
+int rtHipMaterialsCheck(const rtHipMaterialUpdate *update);
+int rtHipSceneSetLights(rtHipScene *scene, const rtHipLights *lights);
+int rtHipSceneSetMaterials(rtHipScene *scene, const rtHipMaterialUpdate *update);
+int rtHipSceneEditTimes(const rtHipScene *scene, double ms[3]);
+
 /* Renders all samples of the scene's tiles into its device-resident tile buffer
  * ([tile][plane R,G,B][128*128] u16, tiles in the order given at creation).  Asynchronous on `stream`
  * (a hipStream_t passed as void*; NULL = the scene's own stream).  Returns 0 on success. */

@@ -29,6 +29,10 @@ the accumulation before it is written.  ``--variance-guided`` (beside ``--tempor
 runs the variance-guided filter (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER"; ResidentScene.temporal_variance) on the accumulation
 in the denoiser's place; ``--variance PATH`` also writes each frame's variance (V^K with the filter) as .pfm, numbered the same way.
 
+``--relight N`` renders N frames of the one resident scene with its first light turned about the vertical axis between them
+(include/raytrace_hip.h, "SCENE EDITS: LIGHTS AND MATERIALS"; ResidentScene.set_lights): img_000 .. img_{N-1}, with ``--passes`` /
+``--denoise`` / ``--ao`` numbered alike.
+
 ``--bake-ao PATH`` also bakes ambient occlusion into a texture over the scene's UVs (include/raytrace_hip.h, "AMBIENT OCCLUSION
 BAKE") and writes it to PATH like ``--ao``: .pfm (f32) or .pgm (8 bits).  ``--bake-size W H`` (default 512 512), ``--bake-rays``,
 ``--bake-radius``, ``--bake-seed`` and ``--bake-dilate`` set its parameters; ``--bake-material M`` or ``--bake-triangles FIRST COUNT``
@@ -116,12 +120,21 @@ def parser():
                          "ResidentScene.set_vertices (grid and camera lists are rebuilt on the device); outputs are numbered like --orbit's.  "
                          "For the built-in scenes the camera is set through --eye / --look-at / --fov as for --orbit (defaults: the origin "
                          "and (0, 0, 3)).  One GPU only; not together with --orbit or --bake-ao")
+    ap.add_argument("--relight", type=int, default=1, metavar="N",
+                    help="N frames of the one resident scene with the first light's position and direction turned by i * 360 / N degrees "
+                         "about the vertical axis (raytrace.relight), each after the first through ResidentScene.set_lights (six small arrays "
+                         "are uploaded, nothing is rebuilt); outputs are numbered like --orbit's.  One GPU only; not together with --orbit "
+                         "or --spin")
     return ap
 
 
 def parse_args(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
+    if args.relight < 1:
+        ap.error("--relight N needs N >= 1")
+    if args.relight > 1 and (args.orbit > 1 or args.spin > 1 or args.progressive or args.bake_ao):
+        ap.error("--relight does not go with --orbit, --spin, --progressive or --bake-ao")
     if args.orbit < 1:
         ap.error("--orbit N needs N >= 1")
     if args.orbit > 1 and args.bake_ao:
@@ -396,6 +409,35 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
     return spent
 
 
+def render_relight(sc, args, device: int) -> float:
+    """--relight: args.relight frames of one ResidentScene on HIP device `device`, its first light turned through set_lights between
+    them.  Returns the seconds the edits, frames and read-backs took."""
+    from . import raytrace
+    rs = raytrace.ResidentScene(sc, device)
+    try:
+        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise)
+        if basic or surface:
+            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        lights = raytrace.scene_lights(sc)
+        spent = 0.0
+        for i in range(args.relight):
+            t = time.perf_counter()
+            if i:
+                rs.set_lights(raytrace.relight(lights, i, args.relight))
+            rs.render()
+            planes = [p.reshape(sc.height, sc.width) for p in rs.readback()]
+            spent += time.perf_counter() - t
+            passes = rs.readback_passes() if basic or surface else None
+            if passes is not None and "triangle" in passes and "mesh" not in passes:
+                passes["mesh"] = np.where(passes["triangle"] != 0xFFFFFFFF, 0, -1).astype(np.int32)
+            denoised = rs.denoise() if args.denoise else None
+            ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
+            write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+    finally:
+        rs.close()
+    return spent
+
+
 def main(argv=None):
     args = parse_args(argv)
 
@@ -422,6 +464,13 @@ def main(argv=None):
     cam_ms = raytrace.build_camera_list_device(sc, 0)
     grid_ms = raytrace.build_scene_grid_device(sc, 0)
     t2 = time.perf_counter()
+    if args.relight > 1:
+        if args.device == raytrace.lib().rtHipDeviceCount() + 1:
+            sys.exit("--relight renders on one GPU: choose --device 1..%d" % raytrace.lib().rtHipDeviceCount())
+        spent = render_relight(sc, args, args.device - 1)
+        print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel, "
+              f"{args.relight} lightings -> {raytrace.orbit_path(args.out, 0)} ..\n  edits + frames + read-backs {1e3 * spent:.0f} ms = {args.relight / spent:.1f} frames/s")
+        return 0
     if args.spin > 1:
         if args.device == raytrace.lib().rtHipDeviceCount() + 1:
             sys.exit("--spin renders on one GPU: choose --device 1..%d" % raytrace.lib().rtHipDeviceCount())

@@ -7,6 +7,7 @@
 #include "rt_host.h"
 #include "rt_launch.h"
 #include "rt_build_shared.h"
+#include "rt_scene_edit.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -297,6 +298,32 @@ void derive_path_class(rtHipScene *sc)
     sc->dev.pathClass = (sc->tune.logicClass && sc->classMaterials && sc->classLights) ? RT_PATH_CLASS_OPAQUE_DIFFUSE : RT_PATH_CLASS_GENERAL;
 }
 
+// the per-material channel descriptors of rt_device.h (the channel starts have been checked against the atlas): one arithmetic for a
+// scene build and a materials edit
+std::vector<uint32_t> material_records(const rtHipSceneDesc *d)
+{
+    std::vector<uint32_t> rec((size_t)d->materialCount * 8, 0u);
+    for (uint32_t m = 0; m < d->materialCount; ++m)
+        for (int c = 0; c < 5; ++c) {
+            const uint32_t w = d->matSize[5 * m + c].s[0], h = d->matSize[5 * m + c].s[1];
+            uint32_t desc = 0u;
+            if (w == 1u && h == 1u) {
+                const cl_uchar *px = d->textures[d->matStart[5 * m + c]].s;
+                desc = 0x80000000u | (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
+            } else if (w) desc = 0x40000000u; // (w > 0, h == 0: an image without rows -- the general path indexes it as the reference would)
+            rec[8 * (size_t)m + c] = desc;
+        }
+    return rec;
+}
+
+// a light's spread per light (rt_scene_edit.h); one element at least
+std::vector<float> light_spreads(uint32_t count, const cl_float3 *dir, const cl_float *radius)
+{
+    std::vector<float> spread(count ? count : 1, 0.f);
+    for (uint32_t j = 0; j < count; ++j) spread[j] = rtedit::light_spread(radius[j], dir[j].s);
+    return spread;
+}
+
 int build_materials(rtHipScene *sc, const rtHipSceneDesc *d)
 {
     sc->release_part(PART_MATERIALS);
@@ -312,18 +339,8 @@ int build_materials(rtHipScene *sc, const rtHipSceneDesc *d)
         if (w && ((int64_t)d->matStart[m] < 0 || (uint64_t)d->matStart[m] + w * h > d->texturesSize))
             return fail("material channel %u: %llux%llu texels at %d exceed the %u-texel atlas", m, (unsigned long long)w, (unsigned long long)h, d->matStart[m], d->texturesSize);
     }
-    { // the per-material channel descriptors of rt_device.h
-        std::vector<uint32_t> rec((size_t)d->materialCount * 8, 0u);
-        for (uint32_t m = 0; m < d->materialCount; ++m)
-            for (int c = 0; c < 5; ++c) {
-                const uint32_t w = d->matSize[5 * m + c].s[0], h = d->matSize[5 * m + c].s[1];
-                uint32_t desc = 0u;
-                if (w == 1u && h == 1u) {
-                    const cl_uchar *px = d->textures[d->matStart[5 * m + c]].s; // (start was checked above)
-                    desc = 0x80000000u | (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
-                } else if (w) desc = 0x40000000u; // (w > 0, h == 0: an image without rows -- the general path indexes it as the reference would)
-                rec[8 * (size_t)m + c] = desc;
-            }
+    {
+        const std::vector<uint32_t> rec = material_records(d);
         if (sc->upload(rec.data(), rec.size(), &D.matRec, "matRec")) return -1;
     }
     sc->classMaterials = materials_admit_opaque_diffuse(d); // (the channel starts were checked above)
@@ -341,13 +358,7 @@ int build_lights(rtHipScene *sc, const rtHipSceneDesc *d)
     D.lightCount = d->lightCount;
     if (d->lightCount && (!d->lightType || !d->lightPos || !d->lightDir || !d->lightCol || !d->lightRadius || !d->lightHalfAtt))
         return fail("null light array with lightCount %u", d->lightCount); // (the spread below reads two of them before upload() would notice)
-    std::vector<float> spread(d->lightCount ? d->lightCount : 1, 0.f);
-    for (uint32_t j = 0; j < d->lightCount; ++j) {
-        const float *ld = d->lightDir[j].s;
-        const float dd = ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2];
-        // raytrace_opencl.c:594 (double sin * double sqrt, then one rounding to float)
-        spread[j] = (float)(std::sin((double)((d->lightRadius[j] / 2.f) * 3.14159265f / 180.f)) * std::sqrt((double)dd));
-    }
+    const std::vector<float> spread = light_spreads(d->lightCount, d->lightDir, d->lightRadius);
     if (sc->upload(d->lightType, d->lightCount, &D.lightType, "lightType")) return -1;
     if (sc->upload((const float *)d->lightPos, (uint64_t)d->lightCount * 4, &D.lightPos, "lightPosition")) return -1;
     if (sc->upload((const float *)d->lightDir, (uint64_t)d->lightCount * 4, &D.lightDir, "lightDirection")) return -1;
@@ -626,6 +637,46 @@ int scene_build(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds,
     mark("path state buffers");
     return 0;
 }
+
+// Scene edits (rtHipSceneSetLights, rtHipSceneSetMaterials below).
+// A part (PART_LIGHTS, PART_MATERIALS) built beside the one in use: its blocks are freed when the edit fails and take the old part's
+// place, in the scene's own lists (clone_part reads them), when it succeeds.
+struct FreshPart {
+    std::vector<void *> allocs;
+    std::vector<uint64_t> sizes;
+    uint64_t bytes = 0;
+    FreshPart() = default;
+    FreshPart(const FreshPart &) = delete;
+    FreshPart &operator=(const FreshPart &) = delete;
+    ~FreshPart() { for (void *p : allocs) (void)hipFree(p); }
+    // `count` elements (one at least) on the device, filled from the host array `src` through the scene's stager: 0, -4 or -2
+    template <class T> int put(rtHipScene *sc, const T *src, uint64_t count, const T **dst, const char *who, const char *what)
+    {
+        void *p = nullptr;
+        const uint64_t n = (count ? count : 1) * sizeof(T);
+        if (const hipError_t e = hipMalloc(&p, n); e != hipSuccess) {
+            (void)hipGetLastError();
+            fail("%s: no device memory for %s (%llu bytes): %s", who, what, (unsigned long long)n, hipGetErrorString(e));
+            return -4;
+        }
+        allocs.push_back(p); sizes.push_back(n); bytes += n;
+        if (count)
+            if (const hipError_t e = sc->stager.copy(p, src, count * sizeof(T)); e != hipSuccess) {
+                fail("%s: copying %s to the device failed: %s", who, what, hipGetErrorString(e));
+                return -2;
+            }
+        *dst = (const T *)p;
+        return 0;
+    }
+    // (the scene's stream is idle; the caller has pointed the scene's description at the new blocks)
+    void commit(rtHipScene *sc, int part)
+    {
+        sc->release_part(part);
+        sc->partAllocs[part] = std::move(allocs); sc->partSizes[part] = std::move(sizes);
+        sc->partBytes[part] = bytes; sc->bytes += bytes;
+        allocs.clear(); sizes.clear(); bytes = 0;
+    }
+};
 
 } // namespace
 
@@ -1718,6 +1769,187 @@ int rtHipTestSceneGeometryTimes(const rtHipScene *sc, double ms[4])
 {
     if (!sc || !ms) return fail("rtHipTestSceneGeometryTimes: null argument");
     for (int i = 0; i < 4; ++i) ms[i] = sc->geo.ms[i];
+    return 0;
+}
+
+// ---- scene edits: lights and materials (include/raytrace_hip.h, "SCENE EDITS: LIGHTS AND MATERIALS") ------------------------------------
+
+#define EDIT_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); return -2; } } while (0)
+
+// What every edit starts with: work already issued reads the old tables -- planned frames are verified while they are still in effect,
+// then the stream is idle.
+static int edit_begin(rtHipScene *sc, const char *who)
+{
+    EDIT_HIP(hipSetDevice(sc->device));
+    if (sc->unverified && frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -2;
+    EDIT_HIP(hipStreamSynchronize(sc->stream));
+    for (Event &e : sc->edit.ev) EDIT_HIP(e.make());
+    return 0;
+}
+
+// What every edit ends with: other rays, so the next frame watches its queue again; the groups' views follow the description.
+static void edit_end(rtHipScene *sc, double lights, double tables, double ids)
+{
+    derive_path_class(sc);
+    sc->planRounds = 0;
+    refresh_views(sc);
+    sc->edit.ms[0] = lights; sc->edit.ms[1] = tables; sc->edit.ms[2] = ids;
+}
+
+int rtHipLightsCheck(const rtHipLights *lights)
+{
+    char text[256];
+    return rtedit::lights_check(lights, text, sizeof text) == 0 ? 0 : fail("lights: %s", text);
+}
+
+int rtHipMaterialsCheck(const rtHipMaterialUpdate *update)
+{
+    char text[256];
+    return rtedit::materials_check(update, text, sizeof text) == 0 ? 0 : fail("materials: %s", text);
+}
+
+int rtHipSceneSetLights(rtHipScene *sc, const rtHipLights *l)
+{
+    static const char who[] = "rtHipSceneSetLights";
+    if (!sc || !l) return fail("%s: null argument", who);
+    if (rtHipLightsCheck(l) != 0) return -1;
+    if (const int rc = edit_begin(sc, who)) return rc;
+    hipStream_t st = sc->stream;
+    rtHipScene::Edit &E = sc->edit;
+    const uint32_t L = l->lightCount;
+    FreshPart part;
+    RtDevScene N = sc->dev; // (its light fields are filled here and copied over at the end)
+    EDIT_HIP(hipEventRecord(E.ev[0], st));
+    const std::vector<float> spread = light_spreads(L, l->lightDir, l->lightRadius);
+    int rc = 0;
+    if ((rc = part.put(sc, l->lightType, L, &N.lightType, who, "lightType")) != 0 ||
+        (rc = part.put(sc, (const float *)l->lightPos, (uint64_t)L * 4, &N.lightPos, who, "lightPosition")) != 0 ||
+        (rc = part.put(sc, (const float *)l->lightDir, (uint64_t)L * 4, &N.lightDir, who, "lightDirection")) != 0 ||
+        (rc = part.put(sc, (const float *)l->lightCol, (uint64_t)L * 4, &N.lightCol, who, "lightColour")) != 0 ||
+        (rc = part.put(sc, l->lightRadius, L, &N.lightRadius, who, "lightRadius")) != 0 ||
+        (rc = part.put(sc, l->lightHalfAtt, L, &N.lightHalfAtt, who, "lightHalfAttenuationDistance")) != 0 ||
+        (rc = part.put(sc, spread.data(), L, &N.lightSpread, who, "lightSpread")) != 0)
+        return rc;
+    EDIT_HIP(sc->stager.drain());
+    EDIT_HIP(hipEventRecord(E.ev[1], st));
+    // The path state only scenes of several lights use (build_wavefront: shN, rngL), made by the first edit that brings a second light
+    // and kept from then on: nothing else of the path state depends on the light count, so the sample window, the launch plan's storage
+    // and the groups stay as they are.
+    const bool grow = L > 1u && !sc->wfMultiLight;
+    std::vector<Dev<float4>> shN(grow ? sc->groups.size() : 0);
+    std::vector<Dev<unsigned long long>> rngL(shN.size());
+    uint64_t uncounted = 0;
+    for (size_t g = 0; g < shN.size(); ++g) {
+        const uint64_t cap = sc->groups[g].wf.capacity ? sc->groups[g].wf.capacity : 1;
+        if (shN[g].make(cap * sizeof(float4), uncounted) != hipSuccess || rngL[g].make(cap * 8, uncounted) != hipSuccess) {
+            fail("%s: no device memory for the path state of a scene of several lights", who);
+            return -4;
+        }
+    }
+    EDIT_HIP(hipStreamSynchronize(st));
+    float ms = 0.f;
+    EDIT_HIP(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
+    // everything is complete: the new lights take the old ones' place
+    RtDevScene &D = sc->dev;
+    D.lightCount = L;
+    D.lightType = N.lightType; D.lightPos = N.lightPos; D.lightDir = N.lightDir; D.lightCol = N.lightCol;
+    D.lightRadius = N.lightRadius; D.lightHalfAtt = N.lightHalfAtt; D.lightSpread = N.lightSpread;
+    part.commit(sc, PART_LIGHTS);
+    for (size_t g = 0; g < shN.size(); ++g) { // (the one-element stand-ins stay in the part's list until the scene goes)
+        for (DevBlock *b : { (DevBlock *)&shN[g], (DevBlock *)&rngL[g] }) {
+            sc->partAllocs[PART_WAVEFRONT].push_back(b->p); sc->partSizes[PART_WAVEFRONT].push_back(b->size);
+            sc->partBytes[PART_WAVEFRONT] += b->size; sc->bytes += b->size;
+        }
+        sc->groups[g].wf.shN = shN[g]; sc->groups[g].wf.rngL = rngL[g];
+        shN[g].p = nullptr; shN[g].size = 0; rngL[g].p = nullptr; rngL[g].size = 0; // (the part owns them now)
+    }
+    if (grow) sc->wfMultiLight = true;
+    sc->classLights = L <= 1u;
+    edit_end(sc, ms, 0.0, 0.0);
+    return 0;
+}
+
+int rtHipSceneSetMaterials(rtHipScene *sc, const rtHipMaterialUpdate *u)
+{
+    static const char who[] = "rtHipSceneSetMaterials";
+    if (!sc || !u) return fail("%s: null argument", who);
+    if (rtHipMaterialsCheck(u) != 0) return -1;
+    const uint64_t T = sc->dev.triangleCount;
+    EDIT_HIP(hipSetDevice(sc->device));
+    if (u->triMaterial && u->triMaterialOnDevice && T && query_pointer_ok(sc->device, "the scene", u->triMaterial, T * 4, 4, "triMaterial") != 0) return -1;
+    if (const int rc = edit_begin(sc, who)) return rc;
+    hipStream_t st = sc->stream;
+    rtHipScene::Edit &E = sc->edit;
+
+    // 1. the ids that will be in effect, checked completely before anything is stored: the new array, or -- tables that shrink under
+    // ids that stay -- the resident rows
+    const uint32_t M = u->replaceMaterials ? u->materialCount : sc->dev.materialCount;
+    const int *ids = nullptr;
+    if (u->triMaterial && T) {
+        if (u->triMaterialOnDevice) ids = u->triMaterial;
+        else {
+            if (E.ids.fit(T * 4, T * 4, sc->bytes) != hipSuccess) { fail("%s: no device memory for the ids' staging", who); return -4; }
+            EDIT_HIP(sc->stager.copy(E.ids, u->triMaterial, T * 4));
+            ids = E.ids;
+        }
+    }
+    const bool check = ids || (!u->triMaterial && M < sc->dev.materialCount);
+    EDIT_HIP(hipEventRecord(E.ev[2], st));
+    if (check) EDIT_HIP(rte_launch_check_ids((uint32_t)T, M, ids, sc->dev.triShade, sc->prepErr, st));
+    EDIT_HIP(hipEventRecord(E.ev[3], st));
+    EDIT_HIP(hipStreamSynchronize(st));
+    if (check && sc->check_prep() != 0) return strncmp(rtHipLastError(), "scene rejected", 14) == 0 ? -5 : -2;
+
+    // 2. tables and atlas, beside the ones in use
+    FreshPart part;
+    RtDevScene N = sc->dev;
+    bool classMaterials = sc->classMaterials;
+    EDIT_HIP(hipEventRecord(E.ev[0], st));
+    if (u->replaceMaterials) {
+        rtHipSceneDesc d;
+        memset(&d, 0, sizeof d);
+        d.materialCount = u->materialCount; d.matSize = u->matSize; d.matStart = u->matStart; d.texturesSize = u->texturesSize; d.textures = u->textures;
+        const std::vector<uint32_t> rec = material_records(&d); // (rtHipMaterialsCheck has checked the channel starts)
+        int rc = 0;
+        if ((rc = part.put(sc, (const uint32_t *)u->matSize, (uint64_t)u->materialCount * 10, &N.matSize, who, "materialImageSize")) != 0 ||
+            (rc = part.put(sc, (const int32_t *)u->matStart, (uint64_t)u->materialCount * 5, &N.matStart, who, "materialImageStart")) != 0 ||
+            (rc = part.put(sc, (const uint8_t *)u->textures, (uint64_t)u->texturesSize * 4, &N.textures, who, "textures")) != 0 ||
+            (rc = part.put(sc, rec.data(), rec.size(), &N.matRec, who, "matRec")) != 0)
+            return rc;
+        N.materialCount = u->materialCount;
+        N.texelCount = u->texturesSize ? u->texturesSize : 1;
+        classMaterials = materials_admit_opaque_diffuse(&d);
+    }
+    EDIT_HIP(sc->stager.drain());
+    EDIT_HIP(hipEventRecord(E.ev[1], st));
+
+    // 3. the ids into the rows in use: the last thing issued, after everything that can be refused
+    EDIT_HIP(hipEventRecord(E.ev[4], st));
+    if (ids) EDIT_HIP(rte_launch_store_ids((uint32_t)T, ids, const_cast<float *>(sc->dev.triShade), st));
+    EDIT_HIP(hipEventRecord(E.ev[5], st));
+    EDIT_HIP(hipStreamSynchronize(st));
+    float ms[3] = {};
+    EDIT_HIP(hipEventElapsedTime(&ms[0], E.ev[0], E.ev[1]));
+    EDIT_HIP(hipEventElapsedTime(&ms[1], E.ev[2], E.ev[3]));
+    EDIT_HIP(hipEventElapsedTime(&ms[2], E.ev[4], E.ev[5]));
+
+    // 4. the new tables take the old ones' place
+    if (u->replaceMaterials) {
+        RtDevScene &D = sc->dev;
+        D.materialCount = N.materialCount; D.texelCount = N.texelCount;
+        D.matSize = N.matSize; D.matStart = N.matStart; D.textures = N.textures; D.matRec = N.matRec;
+        part.commit(sc, PART_MATERIALS);
+        sc->classMaterials = classMaterials;
+    }
+    edit_end(sc, 0.0, u->replaceMaterials ? ms[0] : 0.0, check ? (double)ms[1] + ms[2] : 0.0);
+    return 0;
+}
+#undef EDIT_HIP
+
+int rtHipSceneEditTimes(const rtHipScene *sc, double ms[3])
+{
+    if (!sc || !ms) return fail("rtHipSceneEditTimes: null argument");
+    for (int i = 0; i < 3; ++i) ms[i] = sc->edit.ms[i];
     return 0;
 }
 

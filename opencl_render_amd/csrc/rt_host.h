@@ -313,6 +313,14 @@ struct rtHipScene {
         uint64_t log[6] = {}; // per thread, per workgroup, attempts, pairs, camera entries, allocated
         double ms[4] = {};
     } geo;
+    // scene edits (rtHipSceneSetLights, rtHipSceneSetMaterials): staging for material ids that come from the host, made by the first
+    // call that brings some; the events around the last edit's stages (light arrays | tables and atlas | id check | id store) and ms:
+    // device time of the last successful edit's light arrays, tables and atlas, id check + id store
+    struct Edit {
+        rthost::Dev<int> ids;
+        rthost::Event ev[6];
+        double ms[3] = {};
+    } edit;
 
     // Only what ordering requires: the device is selected, work on the streams ends, then the parts, the grid build's space, the upload
     // staging and the pooled query staging go; every member above frees itself afterwards.

@@ -38,6 +38,10 @@ hipError_t rtc_scan_bytes(uint32_t n, size_t *bytes);
 hipError_t rtc_launch_count(const RtCamMoveArgs *args, hipStream_t stream);
 hipError_t rtc_launch_fill(const RtCamMoveArgs *args, hipStream_t stream);
 
+// ---- rt_scene_edit.hip (ids == NULL: the check reads word 21 of the triShade rows)
+hipError_t rte_launch_check_ids(uint32_t T, uint32_t M, const int *ids, const float *triShade, uint32_t *err, hipStream_t stream);
+hipError_t rte_launch_store_ids(uint32_t T, const int *ids, float *triShade, hipStream_t stream);
+
 // ---- rt_wavefront.hip
 hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
                             uint32_t fastQuotient, hipStream_t stream);

@@ -119,6 +119,16 @@ class GeometryUpdate(C.Structure):  # rtHipGeometryUpdate
     _fields_ = [("vertexCount", C.c_uint32), ("vertex", C.c_void_p), ("triIndex", C.c_void_p), ("triNormal", C.c_void_p), ("arraysOnDevice", C.c_int32)]
 
 
+class Lights(C.Structure):  # rtHipLights
+    _fields_ = [("lightCount", C.c_uint32), ("lightType", C.c_void_p), ("lightPos", C.c_void_p), ("lightDir", C.c_void_p), ("lightCol", C.c_void_p),
+                ("lightRadius", C.c_void_p), ("lightHalfAtt", C.c_void_p)]
+
+
+class MaterialUpdate(C.Structure):  # rtHipMaterialUpdate
+    _fields_ = [("replaceMaterials", C.c_int32), ("materialCount", C.c_uint32), ("matSize", C.c_void_p), ("matStart", C.c_void_p),
+                ("texturesSize", C.c_uint32), ("textures", C.c_void_p), ("triMaterial", C.c_void_p), ("triMaterialOnDevice", C.c_int32)]
+
+
 class Stats(C.Structure):  # rtHipStats
     _fields_ = [(n, C.c_uint64) for n in ("primarySamples", "primaryCandidates", "gridRays", "gridCells", "gridCandidates", "shadedHits", "texelFetches")]
 
@@ -133,7 +143,8 @@ DROPIN_SYMBOLS = [
     "dot", "cross", "normalize", "vector", "bindf", "GetPointToLineSqLen", "RayIntersectsTriangle", "GetBoxAddress",
 ]
 RESIDENT_SYMBOLS = [
-    "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipSceneGetCamera", "rtHipSceneSetCamera", "rtHipSceneSetGeometry", "rtHipRenderTiles", "rtHipFrameFinish",
+    "rtHipCacheClear", "rtHipDeviceCount", "rtHipLastError", "rtHipSceneCreate", "rtHipSceneCreateLike", "rtHipSceneDestroy", "rtHipSceneBytes", "rtHipSceneGetCamera", "rtHipSceneSetCamera", "rtHipSceneSetGeometry",
+    "rtHipLightsCheck", "rtHipMaterialsCheck", "rtHipSceneSetLights", "rtHipSceneSetMaterials", "rtHipSceneEditTimes", "rtHipRenderTiles", "rtHipFrameFinish",
     "rtHipSampleWindowCheck", "rtHipSceneSetSampleWindow", "rtHipSceneGetSampleWindow",
     "rtHipSetPipeline", "rtHipStageTiming", "rtHipStageTimes", "rtHipDebugCounters",
     "rtHipRenderTilesCounted", "rtHipTileBuffer", "rtHipTileBufferBytes", "rtHipDetile", "rtHipDetileStore", "rtHipDeviceAlloc", "rtHipDeviceFree", "rtHipDeviceCopy", "rtHipReadback", "rtHipSync",
@@ -218,6 +229,11 @@ def lib() -> C.CDLL:
     L.rtHipSceneSetGeometry.argtypes = [vp, C.POINTER(GeometryUpdate)]
     L.rtHipTestSceneGeometryLog.argtypes = [vp, C.POINTER(u64 * 6), u32]
     L.rtHipTestSceneGeometryTimes.argtypes = [vp, C.POINTER(C.c_double * 4)]
+    L.rtHipLightsCheck.argtypes = [C.POINTER(Lights)]
+    L.rtHipMaterialsCheck.argtypes = [C.POINTER(MaterialUpdate)]
+    L.rtHipSceneSetLights.argtypes = [vp, C.POINTER(Lights)]
+    L.rtHipSceneSetMaterials.argtypes = [vp, C.POINTER(MaterialUpdate)]
+    L.rtHipSceneEditTimes.argtypes = [vp, C.POINTER(C.c_double * 3)]
     L.rtHipRenderTiles.argtypes = [vp, vp]
     L.rtHipFrameFinish.argtypes = [vp, C.POINTER(C.c_int)]
     L.rtHipSampleWindowCheck.argtypes = [u32, C.POINTER(SampleWindow)]
@@ -859,6 +875,51 @@ def spin_directions(normals, index: int, count: int) -> np.ndarray:
     return spin_vertices(normals, (0.0, 0.0, 0.0), index, count)
 
 
+LIGHT_FIELDS = ("light_type", "light_pos", "light_dir", "light_col", "light_radius", "light_half_att")
+
+
+def scene_lights(sc) -> dict:
+    """The six light arrays of a Scene under Scene's field names (what set_lights and relight take)."""
+    return {k: getattr(sc, k) for k in LIGHT_FIELDS}
+
+
+def _light_arrays(lights) -> dict:
+    """`lights` -- a sequence of dicts as scene.pack_lights takes, or a dict of the six arrays under Scene's field names -- as contiguous
+    arrays in the library's layouts: light_type [L] int32, light_pos / light_dir / light_col [L, 4] float32 (lane 3 zero where it is
+    added), light_radius / light_half_att [L] float32."""
+    from .scene import pack_lights
+    if not isinstance(lights, dict):
+        lights = dict(zip(LIGHT_FIELDS, pack_lights(list(lights))))
+    missing = [k for k in LIGHT_FIELDS if k not in lights]
+    if missing:
+        raise ValueError(f"lights: missing {missing}")
+    out = {"light_type": np.ascontiguousarray(lights["light_type"], np.int32).reshape(-1)}
+    n = out["light_type"].shape[0]
+    for k in ("light_pos", "light_dir", "light_col"):
+        out[k] = _padded_rows(k, np.asarray(lights[k], np.float32).reshape(n, -1), np.float32, n)[0] if n else np.zeros((0, 4), np.float32)
+    for k in ("light_radius", "light_half_att"):
+        out[k] = np.ascontiguousarray(lights[k], np.float32).reshape(-1)
+        if out[k].shape[0] != n:
+            raise ValueError(f"{k}: {out[k].shape[0]} values for {n} lights")
+    return out
+
+
+def relight(lights, index: int, count: int) -> dict:
+    """The light arrays (a dict under Scene's field names, scene_lights) with light 0's position and direction turned by index * 360 /
+    count degrees about the vertical axis through the origin, in float32 arithmetic; heights, lane 3, the other four arrays and lights
+    1.. are copied.  Pose 0 is the input, bit for bit."""
+    out = {k: np.array(lights[k], copy=True) for k in LIGHT_FIELDS}
+    if index % count == 0 or out["light_type"].shape[0] == 0:
+        return out
+    a = np.float32(2.0 * np.pi * index / count)
+    c, s = np.float32(np.cos(a)), np.float32(np.sin(a))
+    for k in ("light_pos", "light_dir"):
+        x, z = np.float32(lights[k][0, 0]), np.float32(lights[k][0, 2])
+        out[k][0, 0] = np.float32(x * c) + np.float32(z * s)
+        out[k][0, 2] = np.float32(z * c) - np.float32(x * s)
+    return out
+
+
 def _padded_rows(name: str, a, dtype, rows: Optional[int] = None):
     """A [n, 3] or [n, 4] array (numpy, or a torch tensor on a GPU) as contiguous [n, 4] rows of `dtype`, lane 3 zero where it is added:
     the library's 16-byte cl_float3 / cl_int3.  Returns (array, on_device)."""
@@ -914,7 +975,7 @@ def _resident_view_class(base):
         def put(self, value):
             self.__dict__[name] = value
         return property(get, put)
-    members = {n: array(n) for n in ("vertex", "tri_index", "tri_normal")}
+    members = {n: array(n) for n in ("vertex", "tri_index", "tri_normal", "tri_material")}
     members.update({n: built(n, "grid") for n in ("box_min", "grid_start", "grid_list")})
     members.update({n: built(n, "camera") for n in ("cam_start", "cam_end", "cam_list")})
     members["triangle_count"] = property(lambda self: int(self.__dict__["tri_index"].shape[0]))  # (the counts do not download anything)
@@ -1036,6 +1097,95 @@ class ResidentScene:
         rc = self.try_set_vertices(vertex, tri_index, tri_normal)
         if rc != 0:
             raise RuntimeError(f"rtHipSceneSetGeometry failed ({rc}): {last_error()}")
+
+    def try_set_lights(self, lights) -> int:
+        """rtHipSceneSetLights' return code (0, or a negative code with last_error() set): the scene's lights become `lights`, a sequence of
+        dicts as scene.pack_lights takes or a dict of the six arrays under Scene's field names.  Sample window, tile buffer and temporal
+        history are kept (reset_temporal is the caller's decision).  On success self.scene is replaced by a copy that describes what is
+        resident; on failure nothing changes."""
+        a = _light_arrays(lights)
+        arg = Lights(int(a["light_type"].shape[0]), *[_ptr(a[k]) for k in LIGHT_FIELDS])
+        rc = int(lib().rtHipSceneSetLights(self.handle, C.byref(arg)))
+        if rc == 0:
+            self._describe_edit(**a)
+        return rc
+
+    def set_lights(self, lights) -> None:
+        """Replaces the resident scene's lights (rtHipSceneSetLights); raises RuntimeError when the edit is refused."""
+        rc = self.try_set_lights(lights)
+        if rc != 0:
+            raise RuntimeError(f"rtHipSceneSetLights failed ({rc}): {last_error()}")
+
+    def try_set_materials(self, materials=None, tri_material=None) -> int:
+        """rtHipSceneSetMaterials' return code (0, or a negative code with last_error() set).  materials: a sequence of dicts as
+        scene.pack_materials takes, or a dict with mat_size, mat_start and textures; None keeps the resident tables and atlas.
+        tri_material: [T] int32 ids, a numpy array or a torch tensor on the scene's GPU (handed over as a device pointer once torch's
+        current stream has been synchronised); None keeps the resident ids.  On success self.scene is replaced by a copy that describes
+        what is resident (a tensor is kept and comes to the host when the copy's tri_material is first read); on failure nothing changes."""
+        from .scene import pack_materials
+        up, fields, keep = MaterialUpdate(), {}, []
+        if materials is not None:
+            if not isinstance(materials, dict):
+                materials = dict(zip(("mat_size", "mat_start", "textures"), pack_materials(list(materials))))
+            size = np.ascontiguousarray(materials["mat_size"], np.uint32).reshape(-1, 2)
+            start = np.ascontiguousarray(materials["mat_start"], np.int32).reshape(-1)
+            tex = np.ascontiguousarray(materials["textures"], np.uint8).reshape(-1, 4)
+            if size.shape[0] % 5 or start.shape[0] < size.shape[0]:
+                raise ValueError(f"materials: {size.shape[0]} sizes and {start.shape[0]} starts (five channels per material)")
+            up.replaceMaterials, up.materialCount, up.matSize, up.matStart = 1, size.shape[0] // 5, _ptr(size), _ptr(start)
+            up.texturesSize, up.textures = tex.shape[0], _ptr(tex)
+            fields.update(mat_size=size, mat_start=start, textures=tex)
+            keep += [size, start, tex]
+        if tri_material is not None:
+            T = self.scene.triangle_count
+            if hasattr(tri_material, "data_ptr"):
+                import torch
+
+                if tri_material.dtype != torch.int32 or tuple(tri_material.shape) != (T,):
+                    raise ValueError(f"tri_material: {tri_material.dtype} {tuple(tri_material.shape)}, expected int32 [{T}]")
+                if not tri_material.is_cuda or tri_material.device.index != self.device:
+                    raise ValueError(f"tri_material: a torch tensor must live on the scene's GPU {self.device} (pass a numpy array for host memory)")
+                ids = tri_material.contiguous()
+                torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()  # the call has no stream argument
+                up.triMaterialOnDevice = 1
+            else:
+                ids = np.asarray(tri_material)
+                if ids.dtype != np.int32 or ids.shape != (T,):
+                    raise ValueError(f"tri_material: {ids.dtype} {ids.shape}, expected int32 [{T}]")
+                ids = np.ascontiguousarray(ids)
+            up.triMaterial = _ptr(ids)
+            fields["tri_material"] = ids
+            keep.append(ids)
+        rc = int(lib().rtHipSceneSetMaterials(self.handle, C.byref(up)))
+        if rc == 0:
+            self._describe_edit(**fields)
+        return rc
+
+    def set_materials(self, materials=None, tri_material=None) -> None:
+        """Replaces the resident scene's materials and / or material ids (rtHipSceneSetMaterials); raises RuntimeError when the edit is
+        refused."""
+        rc = self.try_set_materials(materials, tri_material)
+        if rc != 0:
+            raise RuntimeError(f"rtHipSceneSetMaterials failed ({rc}): {last_error()}")
+
+    def _describe_edit(self, **fields) -> None:
+        """self.scene becomes a copy with `fields` replaced: what readback_passes' material ids, scene_desc for a later like= and a
+        fresh twin read."""
+        import copy
+
+        sc = copy.copy(self.scene)
+        if any(hasattr(v, "data_ptr") for v in fields.values()) and not isinstance(sc, _ResidentView):
+            sc.__class__ = _resident_view_class(type(sc))
+        for name, v in fields.items():
+            setattr(sc, name, v)
+        self.scene = sc
+
+    def edit_times_ms(self) -> dict:
+        """Device time of the last successful edit's stages (rtHipSceneEditTimes): the light arrays, the material tables and atlas, the id
+        check and store."""
+        out = (C.c_double * 3)()
+        self._check(lib().rtHipSceneEditTimes(self.handle, C.byref(out)), "rtHipSceneEditTimes")
+        return dict(lights=out[0], materials=out[1], ids=out[2])
 
     def geometry_log(self) -> dict:
         """The last update: triangles filled by one thread, by workgroups, fill attempts, pairs, camera list entries, and whether it
