@@ -31,7 +31,7 @@ static int checked_device_arrays(const char *who, int device, void *stream, cons
 // The device side of a host entry point's arrays, freed when the scope ends: up() gives a device copy of a host array (null for a null
 // one), out() a device array to copy back from.  After a failure both give null and `status` says what failed.
 struct HostStage {
-    DevScratch mem;
+    DevPart mem;
     hipError_t status = hipSuccess;
     int failed() const { return fail("device staging failed: %s", hipGetErrorString(status)); }
     template <class T> T *out(size_t bytes)

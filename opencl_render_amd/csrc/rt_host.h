@@ -1,6 +1,6 @@
-// rt_host.h -- what the host translation units of libraytrace_hip.so share (rt_api.cpp: scenes, queries; rt_frame.cpp: the frame loop;
-// rt_filters.cpp: the image-space filters): the error text, the tuning values (rt_tuning.h), device scratch and staging, and the resident
-// scene itself.  Internal: nothing here is part of the C ABI of include/raytrace_hip.h.
+// rt_host.h -- what the host translation units of libraytrace_hip.so share (rt_api.cpp: scenes, queries; rt_scene_parts.cpp: the builders
+// of a scene's parts; rt_frame.cpp: the frame loop; rt_filters.cpp: the image-space filters): the error text, the tuning values
+// (rt_tuning.h), upload staging, and the resident scene itself.  Internal: nothing here is part of the C ABI of include/raytrace_hip.h.
 #pragma once
 #include "raytrace_hip.h"
 #include "rt_device.h"
@@ -38,18 +38,6 @@ RT_INTERNAL int fail(const char *fmt, ...);
         hipError_t e_ = (expr);                                                                        \
         if (e_ != hipSuccess) return rthost::fail("%s failed: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
-
-// Device scratch of a scene build: freed when the scope ends, whichever way it ends.
-struct DevScratch {
-    std::vector<void *> blocks;
-    ~DevScratch() { for (void *p : blocks) (void)hipFree(p); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) blocks.push_back(*out);
-        return e;
-    }
-};
 
 // Host-to-device copies go through two pinned buffers (hipHostMalloc once per scene, RT_HIP_STAGE_MB each, default 32): the
 // caller's arrays are pageable (new[] in render.cpp:1089-1123), and a pageable hipMemcpy is a synchronous bounce through the
@@ -156,11 +144,9 @@ struct rtHipScene {
     rthost::Stream stream; // (declared before everything issued on it: destroyed last)
     RtDevScene dev{};
     // Device allocations by PART (tiles + outputs | camera lists | geometry | grid | materials | lights | path state): the drop-in
-    // layer's cache replaces the parts whose inputs changed between two RaytraceAll calls and keeps the others in HBM.
-    std::vector<void *> partAllocs[PART_COUNT];
-    std::vector<uint64_t> partSizes[PART_COUNT]; // bytes of every allocation (a peer instance copies the shared parts device to device)
-    uint64_t partBytes[PART_COUNT] = { 0 };
-    int curPart = PART_FIXED;
+    // layer's cache replaces the parts whose inputs changed between two RaytraceAll calls and keeps the others in HBM.  A part's bytes
+    // are counted in `bytes` by install and drop_part below, nowhere else (a peer instance copies the shared parts block by block).
+    rthost::DevPart parts[PART_COUNT];
     rthost::Stager stager;
     uint32_t *prepErr = nullptr;   // device word: RT_PREP_ERR_* bits raised by the validation kernels
     uint64_t camListSize = 0;
@@ -322,57 +308,53 @@ struct rtHipScene {
         double ms[3] = {};
     } edit;
 
-    // Only what ordering requires: the device is selected, work on the streams ends, then the parts, the grid build's space, the upload
-    // staging and the pooled query staging go; every member above frees itself afterwards.
+    // Only what ordering requires: the device is selected, work on the streams ends, then the grid build's space, the upload staging and
+    // the pooled query staging go; every member above, the parts among them, frees itself afterwards.
     ~rtHipScene()
     {
         if (device >= 0) (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (Group &G : groups)
             if (G.stream) (void)hipStreamSynchronize(G.stream);
-        for (int part = 0; part < PART_COUNT; ++part) release_part(part);
         rt_grid_space_free(&geo.space);
         stager.destroy();
         if (queryHost) rthost::Stager::pool().give(queryHost, queryDev.size);
     }
 
-    template <class T> int upload(const T *src, uint64_t count, const T **dst, const char *what)
+    // `count` elements (one at least) as a new block of `part`, a part being built: not the scene's, and not counted, before install
+    template <class T> int alloc(rthost::DevPart &part, uint64_t count, T **dst)
     {
         void *p = nullptr;
-        const uint64_t n = count ? count : 1;
-        HIP_OK(hipMalloc(&p, n * sizeof(T)));
-        partAllocs[curPart].push_back(p);
-        partSizes[curPart].push_back(n * sizeof(T));
-        partBytes[curPart] += n * sizeof(T);
-        bytes += n * sizeof(T);
+        const hipError_t e = part.get(&p, (count ? count : 1) * sizeof(T));
+        if (e != hipSuccess) return rthost::fail("hipMalloc(&p, n * sizeof(T)) failed: %s", hipGetErrorString(e));
+        *dst = (T *)p;
+        return 0;
+    }
+    // ... filled from `src` (host or device memory) through the stager
+    template <class T> int upload(rthost::DevPart &part, const T *src, uint64_t count, const T **dst, const char *what)
+    {
+        T *p = nullptr;
+        if (alloc(part, count, &p)) return -1;
         if (count) {
             if (!src) return rthost::fail("%s: null pointer with %llu elements", what, (unsigned long long)count);
             HIP_OK(stager.copy(p, src, count * sizeof(T)));
         }
-        *dst = (const T *)p;
+        *dst = p;
         return 0;
     }
-    template <class T> int alloc(uint64_t count, T **dst)
+    // The two places a part's bytes enter and leave rtHipSceneBytes.  Work on the scene's stream may still read a part that goes.
+    void drop_part(int part)
     {
-        void *p = nullptr;
-        const uint64_t n = count ? count : 1;
-        HIP_OK(hipMalloc(&p, n * sizeof(T)));
-        partAllocs[curPart].push_back(p);
-        partSizes[curPart].push_back(n * sizeof(T));
-        partBytes[curPart] += n * sizeof(T);
-        bytes += n * sizeof(T);
-        *dst = (T *)p;
-        return 0;
-    }
-    void release_part(int part)
-    {
-        if (partAllocs[part].empty()) return;
+        if (parts[part].empty()) return;
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void *p : partAllocs[part]) (void)hipFree(p);
-        partAllocs[part].clear();
-        partSizes[part].clear();
-        bytes -= partBytes[part];
-        partBytes[part] = 0;
+        bytes -= parts[part].bytes;
+        parts[part].clear();
+    }
+    void install(int part, rthost::DevPart &&fresh)
+    {
+        drop_part(part);
+        bytes += fresh.bytes;
+        parts[part] = std::move(fresh);
     }
     // looks at the device-side validation word (after the caller's stream synchronisation)
     int check_prep()
@@ -405,7 +387,12 @@ inline int scene_event(Event &ev, unsigned flags, const char *who)
     return e == hipSuccess ? 0 : fail("%s: hipEventCreate failed: %s", who, hipGetErrorString(e));
 }
 
-// Sample windows (include/raytrace_hip.h, "SAMPLE WINDOWS").
+// Sample windows (include/raytrace_hip.h, "SAMPLE WINDOWS").  The default window of a scene of S samples:
+inline rtHipSampleWindow default_window(uint32_t S) { return rtHipSampleWindow{ S, 0u, S, 0u, 0u }; }
+inline bool same_window(const rtHipSampleWindow &a, const rtHipSampleWindow &b)
+{
+    return a.total == b.total && a.first == b.first && a.divisor == b.divisor && a.accumulate == b.accumulate && a.advance == b.advance;
+}
 // Does a frame under `w` follow on what the tile buffer holds?  (Such a frame cannot be rendered again: it is issued watched.)
 inline bool window_continues(const rtHipSampleWindow &w) { return w.accumulate == 1u && w.first > 0u; }
 // `w` becomes the window of the scene's device description and of every tile group's copy of it (RtDevScene travels by value): host
@@ -421,6 +408,32 @@ inline void apply_window(rtHipScene *sc, const rtHipSampleWindow &w)
     for (auto &G : sc->groups) put(G.dev);
 }
 
+// bytes of the fixed-size arrays of a grid (rtHipScene::GeoMove::Set)
+constexpr uint64_t GEO_PLANE_BYTES = RT_CLIP_FLOATS * 4 /* (the planes and the clip bound behind them, rt_ray_clip.h) */, GEO_LUT_BYTES = 3 * 256, GEO_START_BYTES = ((uint64_t)RT_GRID_DIV * RT_GRID_DIV * RT_GRID_DIV + 1) * 4,
+                   GEO_BITS_BYTES = (uint64_t)(RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * 8,
+                   GEO_SPARSE_BYTES = (uint64_t)3 * ((63u << 16 | 63u << 8 | 63u) + 1u) * 4;
+
+// rt_scene_parts.cpp: the part builders (0, or -1 with the error text set: the caller destroys the scene), what follows a rebuilt
+// part, and the arithmetic a scene build shares with the moves and edits of rt_api.cpp
+RT_INTERNAL int build_fixed(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds, cl_uint tileCount);
+RT_INTERNAL int build_camera(rtHipScene *sc, const rtHipSceneDesc *d);
+RT_INTERNAL int build_geometry(rtHipScene *sc, const rtHipSceneDesc *d);
+RT_INTERNAL int build_grid(rtHipScene *sc, const rtHipSceneDesc *d);
+RT_INTERNAL int build_materials(rtHipScene *sc, const rtHipSceneDesc *d);
+RT_INTERNAL int build_lights(rtHipScene *sc, const rtHipSceneDesc *d);
+RT_INTERNAL int build_wavefront(rtHipScene *sc, uint32_t sampleCount);
+RT_INTERNAL int clone_part(rtHipScene *dst, const rtHipScene *src, int part);
+RT_INTERNAL int scene_build(rtHipScene *sc, const rtHipSceneDesc *d, const cl_uint *tileIds, cl_uint tileCount, const rtHipScene *like, const Tuning &tune);
+RT_INTERNAL void refresh_views(rtHipScene *sc);
+RT_INTERNAL void derive_path_class(rtHipScene *sc);
+RT_INTERNAL bool materials_admit_opaque_diffuse(const rtHipSceneDesc *d);
+RT_INTERNAL bool lights_admit_opaque_diffuse(const rtHipSceneDesc *d);
+RT_INTERNAL std::vector<uint32_t> material_records(const rtHipSceneDesc *d);
+RT_INTERNAL std::vector<float> light_spreads(uint32_t count, const cl_float3 *dir, const cl_float *radius);
+RT_INTERNAL void grid_tables(const float *planes, uint8_t *lut, uint32_t *tame);
+RT_INTERNAL void clip_buffer_init(const float *planes, float *buffer);
+RT_INTERNAL hipError_t clip_bound_issue(rtHipScene *sc, const unsigned long long *words, float *boxMin, hipStream_t st);
+RT_INTERNAL hipError_t clip_bound_commit(const rtHipScene *sc, const float *planes, float *boxMin, hipStream_t st, uint32_t *count, float *tail);
 // rt_frame.cpp
 RT_INTERNAL int render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery);
 RT_INTERNAL int frame_finish(rtHipScene *sc, hipStream_t st, int *redone);

@@ -6,6 +6,8 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 namespace rthost {
 
@@ -88,6 +90,37 @@ private:
 // the same, read as an array of T
 template <class T = char> struct Dev : DevBlock {
     operator T *() const { return (T *)p; }
+};
+
+// Device blocks in the order they were made and the sum of their bytes: one PART of a scene (rt_host.h), or scratch that goes when the
+// scope ends.  A part counts into its own sum only; rtHipScene::install and drop_part count that sum into the scene's total.
+struct DevPart {
+    std::vector<DevBlock> blocks;
+    uint64_t bytes = 0;
+    DevPart() = default;
+    DevPart(DevPart &&o) noexcept : blocks(std::move(o.blocks)), bytes(o.bytes) { o.clear(); }
+    DevPart &operator=(DevPart &&o) noexcept
+    {
+        if (this != &o) { blocks = std::move(o.blocks); bytes = o.bytes; o.clear(); }
+        return *this;
+    }
+    bool empty() const { return blocks.empty(); }
+    // a new last block of `n` bytes (one at least), its start in *out; a failure leaves the part as it was
+    hipError_t get(void **out, uint64_t n)
+    {
+        blocks.emplace_back();
+        const hipError_t e = blocks.back().make(n ? n : 1, bytes);
+        if (e != hipSuccess) blocks.pop_back();
+        else *out = blocks.back().p;
+        return e;
+    }
+    // a block made elsewhere (and not counted there) becomes the last one
+    void adopt(DevBlock &&b)
+    {
+        blocks.emplace_back();
+        blocks.back().adopt(std::move(b), bytes);
+    }
+    void clear() { blocks.clear(); bytes = 0; }
 };
 
 } // namespace rthost

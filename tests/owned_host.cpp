@@ -162,6 +162,127 @@ int owned_compound(uint64_t out[3])
     return 0;
 }
 
+// ---- DevPart: a list of blocks and their byte sum ---------------------------------------------------------------------------------
+// block i of a test part has PART_BLOCK(i) bytes
+#define PART_BLOCK(i) (uint64_t)(16 * ((i) + 1))
+
+// `k` blocks are added to a part (the stand-in may have been told to fail one of the adds), then the part goes out of scope.
+// out: blocks held when the adding stopped | the part's sum then | device blocks alive then | the earlier blocks kept pointer and size |
+// *out was left alone by the failed add.  Returns the first failure.
+int owned_part_fill(int k, uint64_t out[5])
+{
+    DevPart part;
+    void *got[16] = {};
+    hipError_t e = hipSuccess;
+    void *sentinel = &part, *p = sentinel;
+    for (int i = 0; i < k && i < 16 && e == hipSuccess; ++i) {
+        p = sentinel;
+        e = part.get(&p, PART_BLOCK(i));
+        if (e == hipSuccess) got[i] = p;
+    }
+    out[0] = part.blocks.size(); out[1] = part.bytes; out[2] = F.live.size(); out[3] = 1;
+    for (size_t i = 0; i < part.blocks.size(); ++i) out[3] = out[3] && part.blocks[i].p == got[i] && part.blocks[i].size == PART_BLOCK(i);
+    out[4] = (e == hipSuccess) || p == sentinel;
+    return (int)e;
+}
+
+// a (3 blocks) -> b by move construction, then b over a held c (1 block) by move assignment.  out: a empty with sum 0 | b's sum | blocks
+// freed when the assignment returns (c's own) | c's sum | b empty with sum 0 | c's first block is a's first
+void owned_part_move(uint64_t out[6])
+{
+    DevPart a, c;
+    void *p = nullptr, *first = nullptr;
+    for (int i = 0; i < 3; ++i) { (void)a.get(&p, PART_BLOCK(i)); if (!i) first = p; }
+    (void)c.get(&p, 1000);
+    DevPart b(std::move(a));
+    out[0] = a.empty() && a.bytes == 0; out[1] = b.bytes;
+    const uint64_t before = F.gone[K_DEVICE];
+    c = std::move(b);
+    out[2] = F.gone[K_DEVICE] - before; out[3] = c.bytes; out[4] = b.empty() && b.bytes == 0;
+    out[5] = c.blocks.size() == 3 && c.blocks[0].p == first;
+}
+
+// A block of `bytes` made elsewhere is adopted by a part that holds one block.
+// out: sum before | sum after | the part's last block is that block, pointer and size | the source is empty | what the maker counted
+void owned_part_adopt(uint64_t bytes, uint64_t out[5])
+{
+    DevPart part;
+    void *p = nullptr;
+    (void)part.get(&p, PART_BLOCK(0));
+    Dev<float> made;
+    uint64_t uncounted = 0;
+    (void)made.make(bytes, uncounted);
+    const void *at = made.p;
+    out[0] = part.bytes;
+    part.adopt(std::move(made));
+    out[1] = part.bytes; out[2] = part.blocks.size() == 2 && part.blocks[1].p == at && part.blocks[1].size == bytes;
+    out[3] = !made.p && !made.size; out[4] = uncounted;
+}
+
+namespace {
+// what rtHipScene (rt_host.h) does with its parts, without its stream
+struct PartScene {
+    DevPart parts[2];
+    uint64_t bytes = 0;
+    void drop_part(int part) { bytes -= parts[part].bytes; parts[part].clear(); }
+    void install(int part, DevPart &&fresh) { drop_part(part); bytes += fresh.bytes; parts[part] = std::move(fresh); }
+};
+bool part_of(DevPart &part, int first, int count)
+{
+    void *p = nullptr;
+    for (int i = first; i < first + count; ++i)
+        if (part.get(&p, PART_BLOCK(i)) != hipSuccess) return false;
+    return true;
+}
+} // namespace
+
+// A scene holds part 0 (blocks 0, 1) and part 1 (block 2).  A part of blocks 3, 4, 5 is built beside part 0 and installed over it --
+// unless one of its adds fails (the stand-in is told by the caller; the scene's three are made before the count starts at `failAt`),
+// in which case the build returns before install.  Then part 1 is dropped.
+// out: total before | total after the install or the refusal | blocks freed by install | part 0 kept its first block's pointer |
+// blocks alive after the install or the refusal | total after the drop | blocks freed by the drop | installed (1) or refused (0)
+void owned_scene_handover(uint64_t failAt, uint64_t out[8])
+{
+    PartScene scene;
+    DevPart a, b;
+    (void)part_of(a, 0, 2); (void)part_of(b, 2, 1);
+    scene.install(0, std::move(a)); scene.install(1, std::move(b));
+    const void *held = scene.parts[0].blocks[0].p;
+    out[0] = scene.bytes;
+    owned_fail(K_DEVICE, failAt);
+    uint64_t before = F.gone[K_DEVICE];
+    out[7] = [&] {
+        DevPart fresh;
+        if (!part_of(fresh, 3, 3)) return 0;
+        scene.install(0, std::move(fresh));
+        out[2] = F.gone[K_DEVICE] - before; // (when install returns: before `fresh` goes out of scope)
+        return 1;
+    }();
+    if (!out[7]) out[2] = 0;
+    out[1] = scene.bytes; out[3] = scene.parts[0].blocks[0].p == held; out[4] = F.live.size();
+    before = F.gone[K_DEVICE];
+    scene.drop_part(1);
+    out[5] = scene.bytes; out[6] = F.gone[K_DEVICE] - before;
+}
+
+// The lights edit's growth: two blocks made locally, counted nowhere, are adopted by the installed part 1 and their bytes counted.
+// out: total before | total after | part 1's sum after | blocks of part 1 | both sources empty
+void owned_scene_grow(uint64_t first, uint64_t second, uint64_t out[5])
+{
+    PartScene scene;
+    DevPart a, b;
+    (void)part_of(a, 0, 2); (void)part_of(b, 2, 1);
+    scene.install(0, std::move(a)); scene.install(1, std::move(b));
+    out[0] = scene.bytes;
+    Dev<float> x;
+    Dev<unsigned long long> y;
+    uint64_t uncounted = 0;
+    (void)x.make(first, uncounted); (void)y.make(second, uncounted);
+    scene.parts[1].adopt(std::move(x)); scene.parts[1].adopt(std::move(y));
+    scene.bytes += uncounted;
+    out[1] = scene.bytes; out[2] = scene.parts[1].bytes; out[3] = scene.parts[1].blocks.size(); out[4] = !x.p && !x.size && !y.p && !y.size;
+}
+
 } // extern "C"
 
 #ifdef OWNED_HOST_MAIN
@@ -206,6 +327,32 @@ int main()
             CHECK(nth ? (rc != 0 && o[0] == 0 && o[1] == 0 && o[2] == 0) : (rc == 0 && o[0] == 4096 + 4 * 256 && o[1] == 5 && o[2] == 4));
             CHECK(settled());
         }
+    // DevPart
+    uint64_t q[8];
+    const auto sum = [](int n) { uint64_t s = 0; for (int i = 0; i < n; ++i) s += PART_BLOCK(i); return s; };
+    for (int k : { 0, 1, 4 }) {
+        owned_reset();
+        CHECK(owned_part_fill(k, q) == 0 && q[0] == (uint64_t)k && q[1] == sum(k) && q[2] == (uint64_t)k && q[3]);
+        CHECK(F.made[K_DEVICE] == (uint64_t)k && settled());
+    }
+    for (int n = 1; n <= 4; ++n) {
+        owned_reset(); owned_fail(K_DEVICE, n);
+        CHECK(owned_part_fill(4, q) != 0 && q[0] == (uint64_t)n - 1 && q[1] == sum(n - 1) && q[2] == (uint64_t)n - 1 && q[3] && q[4]);
+        CHECK(F.made[K_DEVICE] == (uint64_t)n - 1 && settled());
+    }
+    owned_reset(); owned_part_move(q);
+    CHECK(q[0] && q[1] == sum(3) && q[2] == 1 && q[3] == sum(3) && q[4] && q[5] && F.made[K_DEVICE] == 4 && settled());
+    owned_reset(); owned_part_adopt(4000, q);
+    CHECK(q[0] == 16 && q[1] == 4016 && q[2] && q[3] && q[4] == 4000 && F.made[K_DEVICE] == 2 && settled());
+    for (uint64_t failAt = 0; failAt <= 3; ++failAt) {
+        owned_reset(); owned_scene_handover(failAt, q);
+        CHECK(q[0] == 96 && q[5] == q[1] - 48 && q[6] == 1);
+        if (failAt) CHECK(!q[7] && q[1] == 96 && q[2] == 0 && q[3] && q[4] == 3 && F.made[K_DEVICE] == 3 + failAt - 1);
+        else CHECK(q[7] && q[1] == 96 - 48 + 240 && q[2] == 2 && !q[3] && q[4] == 4 && F.made[K_DEVICE] == 6);
+        CHECK(settled());
+    }
+    owned_reset(); owned_scene_grow(4096, 2048, q);
+    CHECK(q[0] == 96 && q[1] == 96 + 6144 && q[2] == 48 + 6144 && q[3] == 3 && q[4] && F.made[K_DEVICE] == 5 && settled());
     printf(g_bad ? "owned_host: %d checks FAILED\n" : "owned_host: all checks passed\n", g_bad);
     return g_bad ? 1 : 0;
 }

@@ -435,6 +435,34 @@ def test_tile_subsets_and_peers():
                 rs.close()
 
 
+def test_a_clone_of_a_scene_grown_to_two_lights_outlives_its_source():
+    """6b: class_degenerate_outside (one light) gets a second light by an edit -- a lights part built beside the old one and installed,
+    and path state for several lights handed to the path-state part -- and is then the `like` of a new instance.  The source is destroyed
+    before the clone renders: the clone's blocks are its own, and its frame and its bytes are those of a scene created fresh with the
+    two lights."""
+    sc = base("class_degenerate_outside")
+    L = lights_of(ONE_SUN + [SPOT])
+    fr = R.ResidentScene(twin_of(sc, lights=L), 0)
+    try:
+        want, want_bytes = frame(fr), fr.bytes()
+    finally:
+        fr.close()
+    src, clone = R.ResidentScene(sc, 0), None
+    try:
+        assert src.path_class() == R.PATH_CLASS_OPAQUE_DIFFUSE
+        before = src.bytes()
+        src.set_lights(L)
+        assert src.path_class() == R.PATH_CLASS_GENERAL and src.bytes() > before
+        clone = R.ResidentScene(src.scene, 0, like=src)
+    finally:
+        src.close()
+    try:
+        assert_planes(frame(clone), want, "a clone of a grown scene, after its source went")
+        assert clone.bytes() == want_bytes
+    finally:
+        clone.close()
+
+
 def test_history_is_the_callers():
     """7: an edit keeps the temporal history: the accumulation after a re-lit frame still holds the old lighting; after reset_temporal it
     is, bit for bit, a fresh twin's first accumulation."""
