@@ -695,6 +695,84 @@ int  rtHipSceneMotion(rtHipScene *scene, cl_float *motion, cl_float *t, cl_float
  * later mark after it, by events. */
 int  rtHipSceneMotionDevice(rtHipScene *scene, void *motion, void *t, void *prevT, void *triangle, void *stream);
 
+/* MATTES: anti-aliased id coverage over a pixel's samples -- the object buffer of a compositor.  Per pixel, the fraction of its samples
+ * whose primary hit carries a given id (SELECTED MATTES, up to 16 ids the caller names), and the K ids that cover the pixel most with
+ * their fractions (RANKED LAYERS, K <= 8: any matte can be pulled afterwards without knowing the ids in advance -- the idea of
+ * Cryptomatte, with raw ids instead of hashed names).  Both come from one pass over the samples and both are exact: integer counts,
+ * one fp32 division each.  The samples are the beauty's, so a matte's edge is anti-aliased exactly like the frame it cuts.  The pass
+ * reads the camera, the camera lists, the triangle records, the shading rows' material word and the group table: no frame has to be
+ * rendered, it works on either pipeline and with passes on or off, and a call changes nothing a later frame, read-back, pass, denoise,
+ * AO, bake, query or motion call produces; it leaves the sample window and the tile buffer alone.  (The TRIANGLE pass of rtHipScenePasses
+ * stays what it is: sample 1's id, one per pixel.)  tests/matte_oracle.py restates the definition in numpy and the device output equals
+ * it bit for bit.
+ *
+ * Samples: pixel p = y*W + x of the scene's own tiles; sample j = 0..C-1 has sample id i = f + 1 + j; its generator is seeded
+ * (uint64)p*N + i; its direction is (topLeft + lr*((float)x + r1)) + tb*((float)y + r2) per component, r1 and r2 the next two rand01
+ * draws (LR first); the pixel's camera list is scanned in order from the eye with tmin = 0, tmax = +inf and a running closest hit, ties
+ * keep the earlier candidate.  This is a frame's primary ray under the sample window {N, f, ...} (SAMPLE WINDOWS above), bit for bit:
+ * with N = C = S, f = 0 the samples are the default frame's, with {N, 0, N} those of a whole progressive sequence.  C need not equal
+ * the scene's S: no path state is involved.
+ * The sample's id g_j: 0xffffffff (NONE) on a miss; on a hit of triangle tri,
+ *   RT_HIP_MATTE_TRIANGLE (0)  tri;
+ *   RT_HIP_MATTE_MATERIAL (1)  the resident material id (what rtHipSceneSetMaterials edits); every negative id reads as NONE;
+ *   RT_HIP_MATTE_GROUP    (2)  groups[tri] of the scene's group table (rtHipSceneSetMatteGroups): any u32, 0xffffffff = "in no group".
+ * Selected mattes: count_m = the number of j with g_j == select[m], m < M <= 16.  A repeated id gives equal planes; NONE is refused.
+ * Layers: a table of K <= 8 slots, empty at j = 0.  The samples are taken in order j = 0..C-1; one with g_j == NONE is skipped; if g_j
+ * is in the table its slot's count goes up by one; otherwise, if a slot is free, the first free slot takes (g_j, 1); otherwise `rest`
+ * goes up by one.  After the last sample the used slots are ordered by count descending, equal counts by id ascending; unused slots
+ * follow with id NONE and count 0.  So with K >= the number of distinct ids in the pixel the layers are exact and rest = 0; with a
+ * smaller K the FIRST K distinct ids in sample order are the ones kept (not the K largest), and rest counts every sample of the others.
+ * Always: the layer counts + rest + the NONE samples = C.
+ * Outputs, each row-major W x H and plane-major where there are several planes:
+ *   select        f32 [M][H][W] = (float)count_m / (float)C
+ *   layerId       u32 [K][H][W]
+ *   layerCoverage f32 [K][H][W] = (float)count / (float)C
+ *   rest          f32 [H][W]    = (float)rest / (float)C
+ * Each may be NULL; not all of them, not select with M = 0, not a layer output with K = 0.  Only the pixels of the scene's own tiles are
+ * written; every other pixel keeps its value, so instances over a tile deal compose one image.  Every bit pattern of camera, vertices
+ * and table has a defined answer, and nothing indexes out of range.
+ * Parameters: rtHipMatteCheck (host only, no device) returns -1 with the last-error text set for a kind outside 0..2, N == 0, C == 0 or
+ * C > 65536, f + C > N (compared in 64 bits), M > 16, K > 8, M == 0 && K == 0, a selected id of NONE; 0 otherwise.
+ * The scratch (M + 2K + 1 words per pixel of the scene's tiles: the state between the launches of a call, each of which walks at most
+ * "matte_chunk" samples, rtHipTune) belongs to the scene: made on first use, grown when M + 2K + 1 grows, counted in rtHipSceneBytes,
+ * freed with the scene; a scene that never asks holds none of it.  Calls on different streams are ordered by an event.
+ * Both rtHipSceneMattes calls refuse, with -1, the last-error text set and nothing launched: a NULL scene or params, a failed check,
+ * the output rules above, kind GROUP without a table, an image of 2^32 pixels or more, a bad device pointer. */
+#define RT_HIP_MATTE_TRIANGLE 0
+#define RT_HIP_MATTE_MATERIAL 1
+#define RT_HIP_MATTE_GROUP 2
+#define RT_HIP_MATTE_NONE 0xffffffffu
+#define RT_HIP_MATTE_MAX_SELECT 16
+#define RT_HIP_MATTE_MAX_LAYERS 8
+typedef struct rtHipMatteParams {
+    cl_uint kind;        /* RT_HIP_MATTE_* */
+    cl_uint total;       /* N */
+    cl_uint first;       /* f */
+    cl_uint samples;     /* C */
+    cl_uint selectCount; /* M */
+    cl_uint select[RT_HIP_MATTE_MAX_SELECT];
+    cl_uint layers;      /* K */
+} rtHipMatteParams;
+int  rtHipMatteCheck(const rtHipMatteParams *params);
+/* kind TRIANGLE, M = 0, K = 4 and {N, f, C} = {total, first, S} of the window the scene's last issued frame used (*last of
+ * rtHipSceneGetSampleWindow), {S, 0, S} before the first frame.  Returns 0, or -1 for a NULL argument. */
+int  rtHipMatteDefaults(const rtHipScene *scene, rtHipMatteParams *params);
+/* The group table of kind GROUP: T ids (T = the scene's triangle count, which never changes), from host memory or -- onDevice -- from
+ * memory of the scene's device, checked like rtHipSceneIntersectDevice's pointers.  The ids are copied into storage the scene owns
+ * (counted in rtHipSceneBytes, freed with the scene), so the table survives rtHipSceneSetCamera, rtHipSceneSetGeometry,
+ * rtHipSceneSetLights and rtHipSceneSetMaterials.  NULL frees the table.  Synchronous, on the scene's stream.  Returns 0, -1 on failure. */
+int  rtHipSceneSetMatteGroups(rtHipScene *scene, const cl_uint *groups, cl_int onDevice);
+/* HOST arrays; synchronous, on the scene's stream. */
+int  rtHipSceneMattes(rtHipScene *scene, const rtHipMatteParams *params, cl_float *select, cl_uint *layerId, cl_float *layerCoverage,
+                      cl_float *rest);
+/* DEVICE arrays of the scene's device (4-byte aligned), asynchronous on `stream` (a hipStream_t as void*; NULL = the scene's stream): no
+ * synchronisation, and no allocation when the scratch already fits.  The pointers are checked like rtHipSceneAmbientOcclusionDevice's. */
+int  rtHipSceneMattesDevice(rtHipScene *scene, const rtHipMatteParams *params, void *select, void *layerId, void *layerCoverage, void *rest,
+                            void *stream);
+/* Device time in milliseconds of the scene's last matte call, from HIP events on its stream: ms[0] the count launches, ms[1] the finish
+ * kernel.  Waits for that call to end.  Both 0 before the first call.  Returns 0, or -1 for a NULL argument. */
+int  rtHipSceneMatteTimes(rtHipScene *scene, double ms[2]);
+
 /* TEMPORAL ACCUMULATION: the consumer of the motion vectors.  The previous call's output (the history) is fetched bilinearly where the
  * flow says each pixel's surface point was, every tap validated against the triangle id and prevT, and blended with the new frame as a
  * running mean of at most maxHistory frames; a pixel without valid history starts again from the frame itself.  The arithmetic is IEEE
@@ -1117,7 +1195,9 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
  * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
  * and most 2^32 - 1; above it they return -3), "query_rays" (rays per staging chunk of rtHipSceneIntersect, default 2^20), and
  * "ao_samples" (pixel samples per chunk of the ambient occlusion calls, default 2^20, at most 2^24), and "bake_texels" (texels per chunk
- * of the ambient occlusion bake, default 2^20, at most 2^24; a call uses at most 2^31 / R).  Returns 0, -1 for an unknown key. */
+ * of the ambient occlusion bake, default 2^20, at most 2^24; a call uses at most 2^31 / R).  "matte_chunk" (samples per launch of the
+ * matte count kernel, default 64) is read at the entry of every matte call, not at scene creation, and is refused outside 1..65536.
+ * Returns 0, -1 for an unknown key. */
 int rtHipTune(const char *key, double value);
 
 /* TEST-ONLY: device addresses held by the first scene of RaytraceAll's cache -- triangle records, shading rows, the grid's pair

@@ -44,12 +44,28 @@ all-GPUs device it runs on device 0.
 frame but the last a preview img_000.bmp, img_001.bmp .. is written, the tile buffer scaled by N / done on the host.  ``--sequence N``
 (with ``--orbit N``, ``--spin N`` or ``--temporal PATH``) gives the frames the sequence window: frame i draws S fresh samples per pixel of
 a sequence of N, so that the temporal chain has something to average under a still or slowly moving camera.
+
+``--mattes PREFIX`` also writes anti-aliased id mattes over the frame's own samples (include/raytrace_hip.h, "MATTES";
+ResidentScene.mattes): one PREFIX_matte_<id>.pgm per ``--matte-select`` id (u16 = trunc(coverage * 65535)) and PREFIX_layers.npz with the
+``--matte-layers K`` ranked layers.  ``--matte-kind`` says what the ids are: mesh (the default; a scene not made of front-end meshes
+counts as mesh 0), material or triangle.  Single views only; for the all-GPUs device it runs on device 0.
 """
 import argparse
 import sys
 import time
 
 import numpy as np
+
+
+def matte_ids(text: str) -> tuple:
+    """--matte-select: ID[,ID..] -> a tuple of u32 ids."""
+    try:
+        ids = tuple(int(v, 0) for v in text.split(",") if v.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a comma-separated list of ids")
+    if len(ids) > 16 or any(not 0 <= v < 0xFFFFFFFF for v in ids):
+        raise argparse.ArgumentTypeError("at most 16 ids, each in 0 .. 2^32 - 2")
+    return ids
 
 
 def parser():
@@ -75,6 +91,13 @@ def parser():
     ap.add_argument("--ao-radius", type=float, default=float("inf"), help="--ao: how far an occluder counts (scene units; default: any distance)")
     ap.add_argument("--ao-samples", type=int, default=1, help="--ao: jittered primary samples per pixel (1..64)")
     ap.add_argument("--ao-seed", type=int, default=0, help="--ao: seed of the ray directions (u32)")
+    ap.add_argument("--mattes", metavar="PREFIX",
+                    help="also write anti-aliased id mattes over the frame's samples (include/raytrace_hip.h, \"MATTES\"): "
+                         "PREFIX_matte_<id>.pgm per --matte-select id (u16 = trunc(coverage * 65535)) and PREFIX_layers.npz with layer_id, "
+                         "layer_coverage [K, H, W] and rest [H, W].  Single views only")
+    ap.add_argument("--matte-kind", choices=("mesh", "material", "triangle"), default="mesh", help="--mattes: what the ids are")
+    ap.add_argument("--matte-select", type=matte_ids, default=(), metavar="ID[,ID..]", help="--mattes: up to 16 ids, one matte each")
+    ap.add_argument("--matte-layers", type=int, default=4, metavar="K", help="--mattes: ranked layers per pixel (0..8)")
     ap.add_argument("--bake-ao", metavar="PATH", help="also bake ambient occlusion over the UVs into PATH (.pfm or .pgm)")
     ap.add_argument("--bake-size", type=int, nargs=2, metavar=("W", "H"), default=(512, 512), help="--bake-ao: texture size")
     ap.add_argument("--bake-rays", type=int, default=16, help="--bake-ao: hemisphere rays per texel (1..256)")
@@ -173,7 +196,35 @@ def parse_args(argv=None):
         ap.error("--ao PATH must end in .pfm or .pgm")
     if args.bake_ao and not args.bake_ao.lower().endswith((".pfm", ".pgm")):
         ap.error("--bake-ao PATH must end in .pfm or .pgm")
+    if args.mattes:
+        if args.orbit > 1 or args.spin > 1 or args.relight > 1 or args.progressive:
+            ap.error("--mattes PREFIX writes a single view: it does not go with --orbit, --spin, --relight or --progressive")
+        if not 0 <= args.matte_layers <= 8:
+            ap.error("--matte-layers K needs K in 0..8")
+        if not args.matte_select and args.matte_layers == 0:
+            ap.error("--mattes PREFIX needs --matte-select ids or --matte-layers K >= 1")
+    elif args.matte_select or args.matte_kind != "mesh" or args.matte_layers != 4:
+        ap.error("--matte-kind, --matte-select and --matte-layers need --mattes PREFIX")
     return args
+
+
+def write_mattes(sc, prefix: str, device: int, kind: str, select, layers: int) -> dict:
+    """ResidentScene.mattes over the frame's own samples on HIP device `device` -> PREFIX_matte_<id>.pgm per selected id and
+    PREFIX_layers.npz.  Returns what mattes() returned."""
+    from . import frontend, raytrace
+    rs = raytrace.ResidentScene(sc, device)
+    try:
+        if kind == "mesh" and getattr(sc, "tri_mesh", None) is None:  # a scene not made of front-end meshes: all of it counts as mesh 0
+            rs.set_matte_groups(np.zeros(sc.triangle_count, np.uint32))
+            kind = "group"
+        res = rs.mattes(kind=kind, select=select, layers=layers)
+    finally:
+        rs.close()
+    for m, i in enumerate(select):
+        frontend.write_pgm(f"{prefix}_matte_{i}.pgm", (res["select"][m] * np.float32(65535.0)).astype(np.uint16))
+    if layers:
+        np.savez(prefix + "_layers.npz", layer_id=res["layer_id"], layer_coverage=res["layer_coverage"], rest=res["rest"])
+    return res
 
 
 def write_ao(sc, path: str, device: int, rays: int, radius: float, samples: int, seed: int) -> np.ndarray:
@@ -522,6 +573,9 @@ def main(argv=None):
     if args.ao:
         gpus = raytrace.lib().rtHipDeviceCount()
         write_ao(sc, args.ao, 0 if args.device == gpus + 1 else args.device - 1, args.ao_rays, args.ao_radius, args.ao_samples, args.ao_seed)
+    if args.mattes:
+        gpus = raytrace.lib().rtHipDeviceCount()
+        write_mattes(sc, args.mattes, 0 if args.device == gpus + 1 else args.device - 1, args.matte_kind, args.matte_select, args.matte_layers)
     if args.bake_ao:
         gpus = raytrace.lib().rtHipDeviceCount()
         write_bake_ao(sc, args.bake_ao, 0 if args.device == gpus + 1 else args.device - 1, args.bake_size, args.bake_rays, args.bake_radius,

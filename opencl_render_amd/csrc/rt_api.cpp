@@ -43,6 +43,7 @@ Tuning tuning() { std::lock_guard<std::mutex> lock(g_tuneMutex); return g_tune; 
 
 } // namespace
 
+Tuning rthost::tuning_now() { return tuning(); }
 rtbuild::DeviceBuildTuning rtbuild::device_build_tuning() { const Tuning t = tuning(); return { t.buildKeyCap, t.buildListLimit }; }
 
 namespace {
@@ -1528,6 +1529,11 @@ int rtHipTune(const char *key, double value)
     Tuning &T = g_tune;
     const std::string k = key;
     if (k == "reset") { T = Tuning(); return 0; }
+    if (k == "matte_chunk") { // (the one key with a smallest legal value: a chunk of no samples would never end)
+        if (!(value >= 1.0 && value <= 65536.0)) return fail("rtHipTune: matte_chunk %g is not in 1..65536", value);
+        T.matteChunk = (uint32_t)value;
+        return 0;
+    }
     // every key's field, 32 or 64 bits wide, and the most it takes: negative values become 0, larger ones saturate at `most`
     struct Key { const char *name; uint32_t *f32; uint64_t *f64 = nullptr; double most = 4294967295.0; } table[] = {
         { "stage_mb", &T.stageMb }, { "extra_factor", &T.extraFactor }, { "groups", &T.groups }, { "lookahead", &T.lookAhead },

@@ -289,4 +289,30 @@ struct RtMotionArgs {
     uint32_t rowMajor, fastQuotient;
 };
 
+// ---- mattes (rt_wavefront.hip, rt_matte_*; definition in include/raytrace_hip.h, "MATTES") -------------------------------------------
+// The per-pixel state between the chunks of a call, laid out like the pass buffer: state[slot][word][128*128] u32 with `words` =
+// M + 2K + 1 words per pixel -- M selected counts, K layer ids, K layer counts (0 = the slot is free; used slots are a prefix), rest.
+// The count kernel walks samples sampleFirst+1+j, j = 0..samples-1, of a sequence of seedStride per pixel; the chunk with `first` set
+// starts from zero instead of reading the state.  The finish kernel orders the layers and stores the quotients by `den`: row-major into
+// the four arrays (a null one is skipped), or -- rowMajor 0, the host entry point -- over the pixel's own state words, in the same order
+// (select | layer ids | layer coverages | rest).
+#define RT_MATTE_MAX_SELECT 16
+#define RT_MATTE_MAX_LAYERS 8
+enum { RT_MATTE_TRIANGLE = 0, RT_MATTE_MATERIAL = 1, RT_MATTE_GROUP = 2 };
+struct RtMatteArgs {
+    uint32_t kind;                        // RT_MATTE_*: the same in every lane
+    uint32_t seedStride, sampleFirst, samples, first;
+    uint32_t selectCount, layers, words;  // M, K, M + 2K + 1
+    uint32_t select[RT_MATTE_MAX_SELECT]; // entries from M on are 0xffffffff: no sample's id equals them
+    const uint32_t *groups;               // [triangleCount], kind GROUP only
+    uint32_t *state;
+    // the finish kernel's
+    float den;                            // (float)C
+    uint32_t rowMajor;
+    float *outSelect;                     // [M][H][W]
+    uint32_t *outLayerId;                 // [K][H][W]
+    float *outLayerCoverage;              // [K][H][W]
+    float *outRest;                       // [H][W]
+};
+
 #endif

@@ -1,5 +1,5 @@
 // rt_host.h -- what the host translation units of libraytrace_hip.so share (rt_api.cpp: scenes, queries; rt_scene_parts.cpp: the builders
-// of a scene's parts; rt_frame.cpp: the frame loop; rt_filters.cpp: the image-space filters): the error text, the tuning values
+// of a scene's parts; rt_frame.cpp: the frame loop; rt_filters.cpp: the image-space filters; rt_matte.cpp: the mattes): the error text, the tuning values
 // (rt_tuning.h), upload staging, and the resident scene itself.  Internal: nothing here is part of the C ABI of include/raytrace_hip.h.
 #pragma once
 #include "raytrace_hip.h"
@@ -307,6 +307,16 @@ struct rtHipScene {
         rthost::Event ev[6];
         double ms[3] = {};
     } edit;
+    // mattes (rtHipSceneMattes*, rt_matte.cpp): the group table of rtHipSceneSetMatteGroups (one id per triangle, storage of the scene's
+    // own) and the per-pixel state [slot][words][128*128] u32, made by the first call and grown when a call needs more words per pixel.
+    // ev: before the last call's first count launch, after its last one, after its finish kernel -- the last one also marks the end of
+    // the last call that used the state or read the table, on whatever stream it ran.  issued: the events have been recorded.
+    struct Matte {
+        rthost::Dev<uint32_t> groups, state;
+        uint32_t words = 0;
+        rthost::Event ev[3];
+        bool issued = false;
+    } matte;
 
     // Only what ordering requires: the device is selected, work on the streams ends, then the grid build's space, the upload staging and
     // the pooled query staging go; every member above, the parts among them, frees itself afterwards.
@@ -440,5 +450,6 @@ RT_INTERNAL int frame_finish(rtHipScene *sc, hipStream_t st, int *redone);
 // rt_api.cpp
 RT_INTERNAL int query_pointer_ok(int device, const char *whose, const void *p, uint64_t bytes, uint64_t align, const char *what);
 RT_INTERNAL int motion_run(rtHipScene *sc, void *motion, void *t, void *prevT, void *triangle, bool rowMajor, hipStream_t st);
+RT_INTERNAL Tuning tuning_now(); // a snapshot of the tuning values as rtHipTune left them: an entry point's one look at them
 
 } // namespace rthost

@@ -46,6 +46,7 @@ struct Tuning {
     uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
     uint32_t aoSamples = 1u << 20;  // pixel samples per chunk of the ambient occlusion calls (32 bytes each of scene-owned scratch)
     uint32_t bakeTexels = 1u << 20; // texels per chunk of the ambient occlusion bake (32 bytes each of scene-owned scratch)
+    uint32_t matteChunk = 64;       // samples per launch of the matte count kernel (1..65536), read at the entry of every matte call
 };
 
 } // namespace rthost

@@ -334,6 +334,147 @@ __global__ __launch_bounds__(256) void wf_surface_passes_kernel(const RtDevScene
     for (int k = 0; k < RT_SURF_WORDS; ++k) sums[k * RT_TILE_PIXELS] = acc[k];
 }
 
+// ---- mattes: id coverage over a pixel's samples (rtHipSceneMattes*; include/raytrace_hip.h, "MATTES"; rt_device.h, RtMatteArgs) -------
+// The mapping of wf_surface_passes_kernel (ONE thread per pixel, a wave an 8x8 quadrant whose lanes scan overlapping camera lists), and
+// its way of deriving each sample's primary hit again; what is summed is an indicator.  The M selected counts, the K layer slots and
+// rest stay in registers across the chunk's samples: every loop below runs to a compile-time bound and indexes its array with the loop
+// variable, so the arrays are registers, and the bounds that are the call's (M, K) and the id's kind are uniform kernel arguments.
+// Chunks of one call follow one another on one stream: the table is built in sample order without atomics.
+__global__ __launch_bounds__(256) void rt_matte_count_kernel(const RtDevScene S, const RtMatteArgs A)
+{
+    const uint32_t slot = blockIdx.x >> 6, patch = blockIdx.x & 63;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lx = (patch & 7) * RT_PATCH + (wave & 1) * 8 + (lane & 7);
+    const uint32_t ly = (patch >> 3) * RT_PATCH + (wave >> 1) * 8 + (lane >> 3);
+    const uint32_t tile = S.tileIds[slot];
+    const uint32_t gx = (tile % S.tilesX) * RT_TILE + lx;
+    const uint32_t gy = (tile / S.tilesX) * RT_TILE + ly;
+    if (gx >= S.width || gy >= S.height) return;
+
+    const uint32_t localPixel = slot * RT_TILE_PIXELS + ly * RT_TILE + lx;
+    uint32_t *state = A.state + (size_t)slot * A.words * RT_TILE_PIXELS + ly * RT_TILE + lx;
+    const uint32_t M = A.selectCount, K = A.layers;
+    uint32_t sel[RT_MATTE_MAX_SELECT], id[RT_MATTE_MAX_LAYERS], cnt[RT_MATTE_MAX_LAYERS], rest = 0u;
+#pragma unroll
+    for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m) sel[m] = 0u;
+#pragma unroll
+    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k) { id[k] = RT_NONE; cnt[k] = 0u; }
+    if (!A.first) {
+#pragma unroll
+        for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m)
+            if ((uint32_t)m < M) sel[m] = state[(size_t)m * RT_TILE_PIXELS];
+#pragma unroll
+        for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k)
+            if ((uint32_t)k < K) {
+                id[k] = state[(size_t)(M + k) * RT_TILE_PIXELS];
+                cnt[k] = state[(size_t)(M + K + k) * RT_TILE_PIXELS];
+            }
+        rest = state[(size_t)(M + 2u * K) * RT_TILE_PIXELS];
+    }
+    const uint32_t pixel = gy * S.width + gx;
+    const V3 eye = ld3(S.eye), lr = ld3(S.lr), tb = ld3(S.tb), topLeft = ld3(S.topLeft);
+    for (uint32_t j = 0; j < A.samples; ++j) {
+        uint64_t rng = (uint64_t)pixel * (uint64_t)A.seedStride + ((uint64_t)A.sampleFirst + j + 1u); // :481
+        V3 dir = topLeft;
+        float k = (float)gx + rand01(rng); // LR jitter first, then TB (:496-503)
+        dir.x += lr.x * k; dir.y += lr.y * k; dir.z += lr.z * k;
+        k = (float)gy + rand01(rng);
+        dir.x += tb.x * k; dir.y += tb.y * k; dir.z += tb.z * k;
+        float hit_t = 0.f, hit_l1 = 0.f, hit_l2 = 0.f;
+        const uint32_t tri = camera_scan(S, localPixel, eye, dir, 0.f, RT_INF, RT_NONE, hit_t, hit_l1, hit_l2);
+        uint32_t g = tri;
+        if (tri != RT_NONE) {
+            if (A.kind == RT_MATTE_MATERIAL) {
+                const int m = __float_as_int(S.triShade[24 * (size_t)tri + 21]);
+                g = m < 0 ? RT_NONE : (uint32_t)m;
+            } else if (A.kind == RT_MATTE_GROUP) g = A.groups[tri];
+        }
+        if (g == RT_NONE) continue;
+#pragma unroll
+        for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m) sel[m] += (g == A.select[m]) ? 1u : 0u; // (entries from M on are NONE)
+        // find or insert: the used slots are a prefix, so whether g was found is settled before the first free slot is reached
+        bool settled = false;
+#pragma unroll
+        for (int s = 0; s < RT_MATTE_MAX_LAYERS; ++s) {
+            const bool open = (uint32_t)s < K && !settled;
+            const bool used = cnt[s] != 0u;
+            const bool match = open && used && id[s] == g, take = open && !used;
+            id[s] = take ? g : id[s];
+            cnt[s] += (match || take) ? 1u : 0u;
+            settled = settled || match || take;
+        }
+        rest += settled ? 0u : 1u;
+    }
+#pragma unroll
+    for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m)
+        if ((uint32_t)m < M) state[(size_t)m * RT_TILE_PIXELS] = sel[m];
+#pragma unroll
+    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k)
+        if ((uint32_t)k < K) {
+            state[(size_t)(M + k) * RT_TILE_PIXELS] = id[k];
+            state[(size_t)(M + K + k) * RT_TILE_PIXELS] = cnt[k];
+        }
+    state[(size_t)(M + 2u * K) * RT_TILE_PIXELS] = rest;
+}
+
+// One compare-exchange of the finish kernel's network.  A slot's key is ~count << 32 | id: ascending keys are counts descending, equal
+// counts by id ascending, and a free slot (count 0, id NONE) is the largest key there is.
+__device__ __forceinline__ void matte_exchange(unsigned long long &a, unsigned long long &b)
+{
+    const unsigned long long lo = a < b ? a : b, hi = a < b ? b : a;
+    a = lo; b = hi;
+}
+
+// One thread per pixel of the scene's tiles, row by row of its tile (the state is read, and the caller's arrays are written, in whole
+// lines): the K slots ordered by Batcher's odd-even merge network for 8 keys (19 exchanges, fixed indices: registers), the quotients,
+// and the stores -- row-major into the caller's arrays, or over the pixel's own state words for the host entry point.
+__global__ __launch_bounds__(256) void rt_matte_finish_kernel(const RtDevScene S, const RtMatteArgs A)
+{
+    const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
+    if (lp >= S.tileCount * RT_TILE_PIXELS) return;
+    const uint32_t slot = lp >> 14, q = lp & (RT_TILE_PIXELS - 1u), tile = S.tileIds[slot];
+    const uint32_t gx = (tile % S.tilesX) * RT_TILE + (q & (RT_TILE - 1u)), gy = (tile / S.tilesX) * RT_TILE + (q >> 7);
+    if (gx >= S.width || gy >= S.height) return;
+    uint32_t *state = A.state + (size_t)slot * A.words * RT_TILE_PIXELS + q;
+    const uint32_t M = A.selectCount, K = A.layers;
+    uint32_t sel[RT_MATTE_MAX_SELECT];
+    unsigned long long key[RT_MATTE_MAX_LAYERS];
+#pragma unroll
+    for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m) sel[m] = (uint32_t)m < M ? state[(size_t)m * RT_TILE_PIXELS] : 0u;
+#pragma unroll
+    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k) {
+        const uint32_t c = (uint32_t)k < K ? state[(size_t)(M + K + k) * RT_TILE_PIXELS] : 0u;
+        const uint32_t i = c != 0u ? state[(size_t)(M + k) * RT_TILE_PIXELS] : RT_NONE;
+        key[k] = (unsigned long long)~c << 32 | i;
+    }
+    const uint32_t rest = state[(size_t)(M + 2u * K) * RT_TILE_PIXELS];
+    matte_exchange(key[0], key[1]); matte_exchange(key[2], key[3]); matte_exchange(key[4], key[5]); matte_exchange(key[6], key[7]);
+    matte_exchange(key[0], key[2]); matte_exchange(key[1], key[3]); matte_exchange(key[4], key[6]); matte_exchange(key[5], key[7]);
+    matte_exchange(key[1], key[2]); matte_exchange(key[5], key[6]);
+    matte_exchange(key[0], key[4]); matte_exchange(key[1], key[5]); matte_exchange(key[2], key[6]); matte_exchange(key[3], key[7]);
+    matte_exchange(key[2], key[4]); matte_exchange(key[3], key[5]);
+    matte_exchange(key[1], key[2]); matte_exchange(key[3], key[4]); matte_exchange(key[5], key[6]);
+    const size_t plane = A.rowMajor ? (size_t)S.width * S.height : (size_t)RT_TILE_PIXELS;
+    const size_t at = A.rowMajor ? (size_t)gy * S.width + gx : 0;
+    // (every store is a 32-bit word store, the quotients as their bits: over the state they follow this thread's own loads of the same type)
+    uint32_t *outSelect = A.rowMajor ? reinterpret_cast<uint32_t *>(A.outSelect) : state;
+    uint32_t *outId = A.rowMajor ? A.outLayerId : state + (size_t)M * RT_TILE_PIXELS;
+    uint32_t *outCov = A.rowMajor ? reinterpret_cast<uint32_t *>(A.outLayerCoverage) : state + (size_t)(M + K) * RT_TILE_PIXELS;
+    uint32_t *outRest = A.rowMajor ? reinterpret_cast<uint32_t *>(A.outRest) : state + (size_t)(M + 2u * K) * RT_TILE_PIXELS;
+    if (outSelect) {
+#pragma unroll
+        for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m)
+            if ((uint32_t)m < M) outSelect[(size_t)m * plane + at] = __float_as_uint((float)sel[m] / A.den);
+    }
+#pragma unroll
+    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k)
+        if ((uint32_t)k < K) {
+            if (outId) outId[(size_t)k * plane + at] = (uint32_t)key[k];
+            if (outCov) outCov[(size_t)k * plane + at] = __float_as_uint((float)~(uint32_t)(key[k] >> 32) / A.den);
+        }
+    if (outRest) outRest[at] = __float_as_uint((float)rest / A.den);
+}
+
 // ---- trace entries: the DDA start state of a ray, and exact segments ------------------------------------------------
 // A round lasts as long as its longest dependent chain: a ray that crosses the whole grid makes 766 cell visits one after
 // the other, and measured round times are ~0.4 ms + 0.32 ms per million rays -- the constant is that chain.  The walk is a
@@ -1461,6 +1602,29 @@ extern "C" hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const R
 {
     if (scene->tileCount == 0) return hipSuccess;
     hipLaunchKernelGGL(wf_surface_passes_kernel, dim3(scene->tileCount * 64), dim3(256), 0, stream, *scene, *wf, surfBuf);
+    return hipGetLastError();
+}
+
+// mattes: one chunk of samples counted into the state ...
+extern "C" hipError_t rtw_launch_matte_count(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream)
+{
+    if (scene->tileCount == 0 || args->samples == 0) return hipSuccess;
+    if (args->kind > RT_MATTE_GROUP || args->selectCount > RT_MATTE_MAX_SELECT || args->layers > RT_MATTE_MAX_LAYERS || !args->state ||
+        args->words != args->selectCount + 2u * args->layers + 1u || (args->kind == RT_MATTE_GROUP && !args->groups))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_matte_count_kernel, dim3(scene->tileCount * 64), dim3(256), 0, stream, *scene, *args);
+    return hipGetLastError();
+}
+
+// ... and the finished values stored
+extern "C" hipError_t rtw_launch_matte_finish(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream)
+{
+    const uint32_t n = scene->tileCount * RT_TILE_PIXELS;
+    if (n == 0) return hipSuccess;
+    if (args->selectCount > RT_MATTE_MAX_SELECT || args->layers > RT_MATTE_MAX_LAYERS || !args->state ||
+        args->words != args->selectCount + 2u * args->layers + 1u)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_matte_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
     return hipGetLastError();
 }
 

@@ -92,6 +92,17 @@ class AoParams(C.Structure):  # rtHipAoParams
 AO_DEFAULTS = dict(rays=16, radius=float("inf"), pixel_samples=1, seed=0)
 
 
+class MatteParams(C.Structure):  # rtHipMatteParams
+    _fields_ = [("kind", C.c_uint32), ("total", C.c_uint32), ("first", C.c_uint32), ("samples", C.c_uint32), ("selectCount", C.c_uint32),
+                ("select", C.c_uint32 * 16), ("layers", C.c_uint32)]
+
+
+# RT_HIP_MATTE_* (include/raytrace_hip.h, "MATTES"); "mesh" is kind GROUP with scene.tri_mesh as the table
+MATTE_KINDS = dict(triangle=0, material=1, group=2)
+MATTE_NONE = 0xFFFFFFFF
+MATTE_MAX_SELECT, MATTE_MAX_LAYERS = 16, 8
+
+
 class BakeParams(C.Structure):  # rtHipBakeParams
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("raysPerTexel", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32),
                 ("dilate", C.c_uint32), ("firstTriangle", C.c_uint32), ("triangleCount", C.c_uint32), ("material", C.c_int32),
@@ -154,6 +165,7 @@ RESIDENT_SYMBOLS = [
     "rtHipDenoiseDefaults", "rtHipDenoiseScratchBytes", "rtHipDenoiseDevice", "rtHipDenoise", "rtHipSceneDenoise", "rtHipSceneDenoiseTimes",
     "rtHipAoDefaults", "rtHipSceneAmbientOcclusion", "rtHipSceneAmbientOcclusionDevice",
     "rtHipSceneMotionMark", "rtHipSceneMotionReferenceCamera", "rtHipSceneMotion", "rtHipSceneMotionDevice",
+    "rtHipMatteCheck", "rtHipMatteDefaults", "rtHipSceneSetMatteGroups", "rtHipSceneMattes", "rtHipSceneMattesDevice", "rtHipSceneMatteTimes",
     "rtHipTemporalDefaults", "rtHipTemporalDevice", "rtHipTemporal", "rtHipSceneTemporal", "rtHipSceneTemporalReset", "rtHipSceneTemporalTimes",
     "rtHipVarianceDefaults", "rtHipTemporalMomentsDevice", "rtHipTemporalMoments", "rtHipVarianceScratchBytes", "rtHipDenoiseVarianceDevice",
     "rtHipDenoiseVariance", "rtHipSceneTemporalVariance",
@@ -286,6 +298,12 @@ def lib() -> C.CDLL:
     L.rtHipSceneMotionReferenceCamera.argtypes = [vp, C.POINTER(Camera)]
     L.rtHipSceneMotion.argtypes = [vp, vp, vp, vp, vp]
     L.rtHipSceneMotionDevice.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rtHipMatteCheck.argtypes = [C.POINTER(MatteParams)]
+    L.rtHipMatteDefaults.argtypes = [vp, C.POINTER(MatteParams)]
+    L.rtHipSceneSetMatteGroups.argtypes = [vp, vp, i32]
+    L.rtHipSceneMattes.argtypes = [vp, C.POINTER(MatteParams), vp, vp, vp, vp]
+    L.rtHipSceneMattesDevice.argtypes = [vp, C.POINTER(MatteParams), vp, vp, vp, vp, vp]
+    L.rtHipSceneMatteTimes.argtypes = [vp, C.POINTER(C.c_double * 2)]
     L.rtHipTemporalDefaults.restype = None
     L.rtHipTemporalDefaults.argtypes = [C.POINTER(TemporalParams)]
     L.rtHipTemporalDevice.argtypes = [C.c_int, u32, u32] + [vp] * 10 + [C.POINTER(TemporalParams), vp]
@@ -341,6 +359,7 @@ _ENV_KEYS = {
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
     "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow", "RT_WF_RAY_CLIP": "ray_clip", "RT_WF_LOGIC_SPLIT": "logic_split", "RT_WF_PLAN_SHADE_SKIP": "plan_shade_skip", "RT_WF_VISIT_LOG": "visit_log",
     "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit", "RT_HIP_QUERY_RAYS": "query_rays",
+    "RT_MATTE_CHUNK": "matte_chunk",
 }
 # comma-separated lists: RT_WF_SEG=a,b,.. sets seg0, seg1, .. (at most 5 values), RT_WF_SEG_RAYS sets seg_rays0.. (at most 4)
 _ENV_LISTS = (("RT_WF_SEG", "seg", 5), ("RT_WF_SEG_RAYS", "seg_rays", 4))
@@ -1581,6 +1600,114 @@ class ResidentScene:
                 raise ValueError(f"motion: out[{k!r}] must be a C-contiguous {np.dtype(kind).name} {shapes[k]} array")
         self._check(lib().rtHipSceneMotion(self.handle, *[_ptr(out.get(k)) for k in keys]), "rtHipSceneMotion")
         return out
+
+    def set_matte_groups(self, groups) -> None:
+        """The group table of mattes(kind="group") (rtHipSceneSetMatteGroups): one u32 id per triangle, 0xffffffff = in no group; a numpy
+        array (any integer type whose values fit u32), or a torch tensor (uint32 or int32, the ids' bits) on the scene's GPU, handed over
+        as a device pointer once torch's current stream has been synchronised.  The scene keeps a copy of its own.  None frees the table."""
+        self._mesh_groups = False
+        if groups is None:
+            self._check(lib().rtHipSceneSetMatteGroups(self.handle, None, 0), "rtHipSceneSetMatteGroups")
+            return
+        T = self.scene.triangle_count
+        if hasattr(groups, "data_ptr"):
+            import torch
+
+            if groups.dtype not in (torch.uint32, torch.int32) or tuple(groups.shape) != (T,):
+                raise ValueError(f"set_matte_groups: {groups.dtype} {tuple(groups.shape)}, expected uint32 or int32 [{T}]")
+            if not groups.is_cuda or groups.device.index != self.device:
+                raise ValueError(f"set_matte_groups: a torch tensor must live on the scene's GPU {self.device} (pass a numpy array for host memory)")
+            ids = groups.contiguous()
+            torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()  # the call has no stream argument
+            on_device = 1
+        else:
+            g = np.asarray(groups)
+            if g.shape != (T,) or g.dtype.kind not in "iu":
+                raise ValueError(f"set_matte_groups: {g.dtype} {g.shape}, expected integers [{T}]")
+            if g.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)):
+                if g.size and (int(g.min()) < 0 or int(g.max()) > MATTE_NONE):
+                    raise ValueError("set_matte_groups: an id does not fit 32 bits")
+                g = g.astype(np.uint32)
+            ids = np.ascontiguousarray(g).view(np.uint32)
+            on_device = 0
+        self._check(lib().rtHipSceneSetMatteGroups(self.handle, _ptr(ids), on_device), "rtHipSceneSetMatteGroups")
+
+    def matte_defaults(self) -> dict:
+        """rtHipMatteDefaults: kind triangle, no selected id, 4 layers, and {total, first, samples} of the last issued frame's window."""
+        p = MatteParams()
+        self._check(lib().rtHipMatteDefaults(self.handle, C.byref(p)), "rtHipMatteDefaults")
+        kind = [k for k, v in MATTE_KINDS.items() if v == p.kind][0]
+        return dict(kind=kind, select=tuple(p.select[:p.selectCount]), layers=int(p.layers), total=int(p.total), first=int(p.first),
+                    samples=int(p.samples))
+
+    def mattes(self, kind: str = "triangle", select=(), layers: int = 4, total: Optional[int] = None, first: Optional[int] = None,
+               samples: Optional[int] = None, out: Optional[dict] = None, stream: int = 0) -> dict:
+        """Anti-aliased id coverage over each pixel's samples (include/raytrace_hip.h, "MATTES").  kind: "triangle", "material", "group"
+        (the table of set_matte_groups) or "mesh" (scene.tri_mesh, installed as the group table once).  select: up to 16 ids, one coverage
+        plane each; layers: K <= 8 ranked (id, coverage) layers per pixel.  total, first, samples: the sample window {N, f} and the number
+        of samples C; None takes rtHipMatteDefaults' value (the last issued frame's window and the scene's sample count).
+        Returns {"select": [M, H, W] f32, "layer_id": [K, H, W] u32 (0xffffffff: an unused slot), "layer_coverage": [K, H, W] f32,
+        "rest": [H, W] f32} as numpy arrays (rtHipSceneMattes; zeros where this instance's tiles do not reach; "select" is left out for
+        M = 0, the layer arrays for K = 0).  `out`: a dict with any subset of the keys; numpy arrays of those shapes are filled and
+        returned with the missing keys left out, and torch tensors on this scene's device (float32; layer_id uint32 or int32, the ids'
+        bits) are filled by rtHipSceneMattesDevice on torch's current stream (or `stream`) and returned as they are."""
+        if kind == "mesh":
+            if getattr(self.scene, "tri_mesh", None) is None:
+                raise ValueError("mattes: kind 'mesh' needs a scene with tri_mesh (frontend.scene_from_meshes)")
+            if not getattr(self, "_mesh_groups", False):
+                self.set_matte_groups(np.asarray(self.scene.tri_mesh, np.int32))
+                self._mesh_groups = True
+        elif kind not in MATTE_KINDS:
+            raise ValueError(f"mattes: kind {kind!r} is not one of {sorted(MATTE_KINDS) + ['mesh']}")
+        select = [int(v) for v in select]
+        if len(select) > MATTE_MAX_SELECT or any(not 0 <= v <= MATTE_NONE for v in select):
+            raise ValueError(f"mattes: select takes at most {MATTE_MAX_SELECT} u32 ids")
+        p = MatteParams()
+        self._check(lib().rtHipMatteDefaults(self.handle, C.byref(p)), "rtHipMatteDefaults")
+        p.kind = MATTE_KINDS["group" if kind == "mesh" else kind]
+        for name, v in (("total", total), ("first", first), ("samples", samples), ("layers", layers)):
+            if v is not None:
+                if not 0 <= int(v) <= MATTE_NONE:
+                    raise ValueError(f"mattes: {name} = {v} does not fit 32 bits")
+                setattr(p, name, int(v))
+        p.selectCount = len(select)
+        for m, v in enumerate(select):
+            p.select[m] = v
+        if lib().rtHipMatteCheck(C.byref(p)) != 0:
+            raise ValueError(last_error())
+        sc = self.scene
+        M, K, H, W = len(select), int(p.layers), sc.height, sc.width
+        keys = ("select", "layer_id", "layer_coverage", "rest")
+        shapes = dict(select=(M, H, W), layer_id=(K, H, W), layer_coverage=(K, H, W), rest=(H, W))
+        if out is None:
+            out = {k: np.zeros(shapes[k], np.uint32 if k == "layer_id" else np.float32) for k in keys if shapes[k][0]}
+        unknown = [k for k in out if k not in keys]
+        if unknown or not out:
+            raise ValueError(f"mattes: out takes a non-empty subset of {keys} (got {sorted(out)})")
+        if any(hasattr(v, "data_ptr") for v in out.values()):
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            for k, v in out.items():
+                kinds = (torch.uint32, torch.int32) if k == "layer_id" else (torch.float32,)
+                if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype not in kinds or tuple(v.shape) != shapes[k] or not v.is_contiguous():
+                    raise ValueError(f"mattes: out[{k!r}] must be a contiguous {kinds[0]} {shapes[k]} tensor on {dev}")
+            ptrs = [C.c_void_p(out[k].data_ptr()) if k in out else None for k in keys]
+            self._on_torch_stream(stream, list(out.values()), lambda run: self._check(lib().rtHipSceneMattesDevice(
+                self.handle, C.byref(p), *ptrs, C.c_void_p(run)), "rtHipSceneMattesDevice"))
+            return out
+        for k, v in out.items():
+            want = np.uint32 if k == "layer_id" else np.float32
+            if not (isinstance(v, np.ndarray) and v.dtype == want and v.shape == shapes[k] and v.flags.c_contiguous):
+                raise ValueError(f"mattes: out[{k!r}] must be a C-contiguous {np.dtype(want).name} {shapes[k]} array")
+        self._check(lib().rtHipSceneMattes(self.handle, C.byref(p), *[_ptr(out.get(k)) for k in keys]), "rtHipSceneMattes")
+        return out
+
+    def matte_times_ms(self) -> dict:
+        """Device time of the last mattes() (rtHipSceneMatteTimes): the count launches and the finish kernel; waits for that call."""
+        ms = (C.c_double * 2)()
+        self._check(lib().rtHipSceneMatteTimes(self.handle, C.byref(ms)), "rtHipSceneMatteTimes")
+        return dict(count=ms[0], finish=ms[1])
 
     def _on_torch_stream(self, stream, tensors, call):
         """call(hipStream_t as int) on torch's current stream of this scene's device, or on `stream`, ordered after the current stream's
