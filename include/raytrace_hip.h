@@ -284,7 +284,7 @@ int rtHipSceneSetCamera(rtHipScene *scene, const rtHipCamera *camera);
  *   (zero area, repeated corners) are handled like everywhere else.
  *   Peers.  Instances made with rtHipSceneCreateLike and instances over tile subsets are updated one by one by the caller; each builds
  *   its own grid.  A scene that was updated can be the `like` of a new instance.
- *   Memory.  The first update makes a SECOND set of everything the kernels read of the shape (64 + 96 bytes per triangle, 64 MB of grid
+ *   Memory.  The first update makes a SECOND set of everything the kernels read of the shape (64 + 128 bytes per triangle, 64 MB of grid
  *   starts, 50 MB of block table, 2 MB of occupancy words, 4 + 64 bytes per pair) -- updates build into the set that is not in use, and
  *   the parts the scene was created with are freed after the first one -- and the build scratch, which stays: the grid build's storage
  *   (two key buffers of max(32 T, 2^22) x 8 bytes, 24 bytes per vertex, 64 MB of cell counts, sort temporaries; when a triangle is too
@@ -336,7 +336,7 @@ int rtHipSceneSetGeometry(rtHipScene *scene, const rtHipGeometryUpdate *update);
  *   device memory could not be had; -2 for any other HIP failure; each with a text in rtHipLastError().  rtHipLightsCheck and
  *   rtHipMaterialsCheck decide everything that needs neither a scene nor a GPU (0, or -1 with the text); the Set calls run them first.
  *   Values.  No light or texel value is refused: NaN, infinities, negative colours render as they would in a scene created with them.
- *   Ids.  The material id lives in one word of a triangle's 96-byte shading row; new ids are written into the rows in use, and a later
+ *   Ids.  The material id lives in one word of a triangle's 128-byte shading row; new ids are written into the rows in use, and a later
  *   rtHipSceneSetGeometry carries them over.  Host ids are staged to the device; device ids are read in place.
  *   Peers.  Instances made with rtHipSceneCreateLike and instances over tile subsets are edited one by one by the caller.  An edited
  *   scene can be the `like` of a new instance whose description describes the edited state.
@@ -1264,7 +1264,10 @@ int rtHipTestBuildLog(uint64_t *out, cl_uint n);
  *   RT_SCENE_VIEW_CAM_START  cl_uint: tile-major range starts, index slot*128*128 + ly*128 + lx (tileCount*128*128 elements)
  *   RT_SCENE_VIEW_CAM_END    cl_uint: the range ends, same index
  *   RT_SCENE_VIEW_TRI_REC    16 floats (64 bytes): a triangle's intersection record (triangleCount elements)
- *   RT_SCENE_VIEW_TRI_SHADE  24 floats (96 bytes): a triangle's shading row
+ *   RT_SCENE_VIEW_TRI_SHADE  24 floats (96 bytes): the packed words of a triangle's shading row -- b c | nA nB nC | uvA uvB uvC | material
+ *                            id | two zero words -- gathered from the device's 128-byte rows
+ *   RT_SCENE_VIEW_TRI_SHADE_ROW 32 floats (128 bytes): the shading row as the device stores it, one line per triangle: the 24 words above,
+ *                            then the first four floats of the triangle's RT_SCENE_VIEW_TRI_REC record (vertex a, ab.x), then four zero words
  *   RT_SCENE_VIEW_GRID_BITS  uint64_t: the occupancy word of a 4x4x4 block, block (cx>>2) + 64*(cy>>2) + 4096*(cz>>2) (64^3 elements)
  *   RT_SCENE_VIEW_BLOCK_SPARSE cl_uint: the block table {word lo, word hi, rank}, entry 3*((cx>>2) | (cy>>2)<<8 | (cz>>2)<<16)
  *                            (3 * ((63<<16 | 63<<8 | 63) + 1) elements)
@@ -1279,7 +1282,8 @@ int rtHipTestBuildLog(uint64_t *out, cl_uint n);
  * rtHipLastError() text for a NULL scene, an unknown `what`, a range that reaches past the array's end or a HIP failure. */
 enum { RT_SCENE_VIEW_HEADER = 0, RT_SCENE_VIEW_CAM_START, RT_SCENE_VIEW_CAM_END, RT_SCENE_VIEW_TRI_REC, RT_SCENE_VIEW_TRI_SHADE,
        RT_SCENE_VIEW_GRID_BITS, RT_SCENE_VIEW_BLOCK_SPARSE, RT_SCENE_VIEW_PAIR_REC, RT_SCENE_VIEW_CELL_LUT, RT_SCENE_VIEWS,
-       RT_SCENE_VIEW_CLIP_PLANES = 16, RT_SCENE_VIEW_CLIP_APPLIED /* (parts of the planes' buffer, numbered apart from the arrays 0 .. RT_SCENE_VIEWS - 1) */ };
+       RT_SCENE_VIEW_CLIP_PLANES = 16, RT_SCENE_VIEW_CLIP_APPLIED /* (parts of the planes' buffer, numbered apart from the arrays 0 .. RT_SCENE_VIEWS - 1) */,
+       RT_SCENE_VIEW_TRI_SHADE_ROW /* (18: another view of array RT_SCENE_VIEW_TRI_SHADE) */ };
 int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement, uint64_t count, void *out);
 
 /* TEST-ONLY, for rtHipSceneSetCamera.  rtHipTestSceneCameraList copies entries [first, first + count) of the scene's device camera list

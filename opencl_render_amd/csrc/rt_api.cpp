@@ -1001,7 +1001,7 @@ static bool geo_set_fit(rtHipScene *sc, int i, bool lists, uint64_t listBytes, u
 {
     rtHipScene::GeoMove::Set &L = sc->geo.set[i];
     const uint64_t T = sc->dev.triangleCount;
-    return geo_fit(sc, L.triRec, T * 64, true, allocated) && geo_fit(sc, L.triShade, T * 96, true, allocated) &&
+    return geo_fit(sc, L.triRec, T * 64, true, allocated) && geo_fit(sc, L.triShade, T * RT_TRI_SHADE_WORDS * 4, true, allocated) &&
            geo_fit(sc, L.boxMin, GEO_PLANE_BYTES, true, allocated) && geo_fit(sc, L.cellLut, GEO_LUT_BYTES, true, allocated) &&
            geo_fit(sc, L.gridStart, GEO_START_BYTES, true, allocated) && geo_fit(sc, L.gridBits, GEO_BITS_BYTES, true, allocated) &&
            geo_fit(sc, L.sparse, GEO_SPARSE_BYTES, true, allocated) &&
@@ -1631,12 +1631,14 @@ int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement,
     const uint32_t header[5] = { D.planesTame, D.tileCount, D.tilesX, D.triangleCount, (uint32_t)scene->gridListSize };
     const uint64_t tilePixels = (uint64_t)D.tileCount * RT_TILE_PIXELS, blocks = (uint64_t)(RT_GRID_DIV / 4) * (RT_GRID_DIV / 4) * (RT_GRID_DIV / 4);
     struct View { const void *ptr; uint64_t elements, elementBytes; bool host; } v;
+    uint64_t pitch = 0; // bytes from one element to the next on the device, where that is more than the view's elementBytes
     switch (what) {
     case RT_SCENE_VIEW_HEADER: v = { header, 5, 4, true }; break;
     case RT_SCENE_VIEW_CAM_START: v = { D.camStart, tilePixels, 4, false }; break;
     case RT_SCENE_VIEW_CAM_END: v = { D.camEnd, tilePixels, 4, false }; break;
     case RT_SCENE_VIEW_TRI_REC: v = { D.triRec, D.triangleCount, 64, false }; break;
-    case RT_SCENE_VIEW_TRI_SHADE: v = { D.triShade, D.triangleCount, 96, false }; break;
+    case RT_SCENE_VIEW_TRI_SHADE: v = { D.triShade, D.triangleCount, 96, false }; pitch = RT_TRI_SHADE_WORDS * 4; break; // the packed words of each row
+    case RT_SCENE_VIEW_TRI_SHADE_ROW: v = { D.triShade, D.triangleCount, RT_TRI_SHADE_WORDS * 4, false }; break;
     case RT_SCENE_VIEW_GRID_BITS: v = { D.gridBits, blocks, 8, false }; break;
     case RT_SCENE_VIEW_BLOCK_SPARSE: v = { D.gridBlockSparse, (uint64_t)3 * ((63u << 16 | 63u << 8 | 63u) + 1u), 4, false }; break;
     case RT_SCENE_VIEW_PAIR_REC: v = { D.pairRec, scene->gridListSize, 64, false }; break;
@@ -1656,7 +1658,8 @@ int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement,
     if (!v.ptr) return fail("rtHipTestSceneView: the scene does not hold array %d", what);
     HIP_OK(hipSetDevice(scene->device));
     HIP_OK(hipStreamSynchronize(scene->stream));
-    HIP_OK(hipMemcpy(out, (const char *)v.ptr + firstElement * v.elementBytes, count * v.elementBytes, hipMemcpyDeviceToHost));
+    if (pitch) { HIP_OK(hipMemcpy2D(out, v.elementBytes, (const char *)v.ptr + firstElement * pitch, pitch, v.elementBytes, count, hipMemcpyDeviceToHost)); }
+    else { HIP_OK(hipMemcpy(out, (const char *)v.ptr + firstElement * v.elementBytes, count * v.elementBytes, hipMemcpyDeviceToHost)); }
     return 0;
 }
 

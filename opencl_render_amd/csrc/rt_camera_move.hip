@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void rtc_project(const Camera cam, uint32_t T,
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= T) return;
     const float4 a = triRec[4 * (size_t)t]; // {a.xyz, ab.x}
-    const float2 *sh = reinterpret_cast<const float2 *>(triShade + 24 * (size_t)t); // {b.xyz, c.xyz} (96-byte rows: 8-byte aligned)
+    const float2 *sh = reinterpret_cast<const float2 *>(triShade + RT_TRI_SHADE_WORDS * (size_t)t); // {b.xyz, c.xyz}
     const float2 s0 = sh[0], s1 = sh[1], s2 = sh[2];
     pos[3 * (size_t)t] = rtbuild::camera_position(cam, F3{ a.x, a.y, a.z });
     pos[3 * (size_t)t + 1] = rtbuild::camera_position(cam, F3{ s0.x, s0.y, s1.x });

@@ -33,9 +33,11 @@ __global__ __launch_bounds__(256) void rtg_records(uint32_t triangleCount, const
     rec[1] = make_float4(ab.y, ab.z, ac.x, ac.y);
     rec[2] = make_float4(ac.z, n.x, n.y, n.z);
     rec[3] = make_float4(abab, abac, acac, inv);
-    // the 96-byte rows are 8-byte aligned: twelve float2 each
-    float2 *sh = reinterpret_cast<float2 *>(triShade + 24 * (size_t)t);
-    const float2 *old = reinterpret_cast<const float2 *>(oldShade + 24 * (size_t)t);
+    // a row is one 128-byte line (rt_device.h): twelve float2 of packed words, then the copy of the record's quad 0 and a zero quad
+    float2 *sh = reinterpret_cast<float2 *>(triShade + RT_TRI_SHADE_WORDS * (size_t)t);
+    const float2 *old = reinterpret_cast<const float2 *>(oldShade + RT_TRI_SHADE_WORDS * (size_t)t);
+    reinterpret_cast<float4 *>(sh)[6] = make_float4(a.x, a.y, a.z, ab.x);
+    reinterpret_cast<float4 *>(sh)[7] = make_float4(0.f, 0.f, 0.f, 0.f);
     sh[0] = make_float2(b.x, b.y); sh[1] = make_float2(b.z, c.x); sh[2] = make_float2(c.y, c.z);
     if (NORMALS) {
         const float4 na = triNormal[3 * (size_t)t], nb = triNormal[3 * (size_t)t + 1], nc = triNormal[3 * (size_t)t + 2];

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void rt_shade_kat_kernel(const RtDevScene S, i
     const uint32_t tri = reinterpret_cast<const uint32_t *>(fi)[0];
     const V3 where = ld3(fi + 1), o = ld3(fi + 4), d = ld3(fi + 7);
     const float l1 = fi[10], l2 = fi[11];
-    const float *shade = S.triShade + 24 * (size_t)tri;
+    const float *shade = S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri;
     const int m = __float_as_int(shade[21]);
     const float4 first = reinterpret_cast<const float4 *>(S.triRec)[4 * (size_t)tri]; // the round-0 row's copy (rt_wavefront.hip, TriRow)
     MatRec mat;

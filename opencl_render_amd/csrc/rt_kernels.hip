@@ -75,7 +75,7 @@ __device__ V3 trace_sample(const RtDevScene &S, const Shared &sh, uint32_t pixel
         }
 
         if (hit_tri != RT_NONE) {
-            const float *shade = S.triShade + 24 * (size_t)hit_tri;
+            const float *shade = S.triShade + RT_TRI_SHADE_WORDS * (size_t)hit_tri;
             const int m = __float_as_int(shade[21]);
             const float *uv = shade + 15;
             V3 tex = mk(0, 0, 0), transp = mk(0, 0, 0), refl = mk(0, 0, 0), lum = mk(0, 0, 0);
@@ -125,7 +125,9 @@ __device__ V3 trace_sample(const RtDevScene &S, const Shared &sh, uint32_t pixel
                         float t, l1, l2;
                         const uint32_t occ = grid_trace<COUNT>(S, sh, where, toL, lmin, lmax, hit_tri, t, l1, l2, cn);
                         if (occ == RT_NONE) break;
-                        const float *oshade = S.triShade + 24 * (size_t)occ;
+                        uint32_t occRow = occ; // (the row's address from an index made opaque: folded into the walk's arithmetic, the 128-byte
+                        asm volatile("" : "+v"(occRow)); // pitch cost <false> 32 bytes of scratch more than the 96-byte one; so it is 64 fewer)
+                        const float *oshade = S.triShade + RT_TRI_SHADE_WORDS * (size_t)occRow;
                         const int om = __float_as_int(oshade[21]);
                         V3 tr = mk(0.f, 0.f, 0.f);
                         if (0 <= om) {
@@ -309,7 +311,7 @@ __global__ __launch_bounds__(256) void rt_prepare_triangles(uint32_t triangleCou
     rec[1] = make_float4(ab.y, ab.z, ac.x, ac.y);
     rec[2] = make_float4(ac.z, n.x, n.y, n.z);
     rec[3] = make_float4(abab, abac, acac, inv);
-    float *sh = triShade + 24 * (size_t)t;
+    float *sh = triShade + RT_TRI_SHADE_WORDS * (size_t)t;
     const float4 na = triNormal[3 * (size_t)t], nb = triNormal[3 * (size_t)t + 1], nc = triNormal[3 * (size_t)t + 2];
     const float2 ua = triUv[3 * (size_t)t], ub = triUv[3 * (size_t)t + 1], uc = triUv[3 * (size_t)t + 2];
     sh[0] = b.x; sh[1] = b.y; sh[2] = b.z; sh[3] = c.x; sh[4] = c.y; sh[5] = c.z;
@@ -317,6 +319,9 @@ __global__ __launch_bounds__(256) void rt_prepare_triangles(uint32_t triangleCou
     sh[15] = ua.x; sh[16] = ua.y; sh[17] = ub.x; sh[18] = ub.y; sh[19] = uc.x; sh[20] = uc.y;
     sh[21] = __int_as_float(triMaterial[t]);
     sh[22] = 0.f; sh[23] = 0.f;
+    // the row's copy of the record's quad 0 (vertex a for a shaded hit), and the rest of the line
+    reinterpret_cast<float4 *>(sh)[6] = make_float4(a.x, a.y, a.z, ab.x);
+    reinterpret_cast<float4 *>(sh)[7] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // De-tiles [slot][3][128*128] tile buffers into three row-major planes.  ACCUMULATE: saturating add into what is there (the ABI

@@ -1,13 +1,13 @@
 // rt_scene_edit.hip -- the device side of a material id edit of a RESIDENT scene (rtHipSceneSetMaterials).
 //
 // Lights, material tables and the atlas are tables the host fills and the frame kernels read: replacing them needs no kernel.  The
-// material ID of a triangle lives in one place only, word 21 of its 96-byte triShade row (rt_prepare_triangles, rt_kernels.hip), beside
-// corner and UV words an edit must not touch.  Two kernels, one thread per triangle:
+// material ID of a triangle lives in one place only, word 21 of its triShade row (RT_TRI_SHADE_WORDS floats, rt_device.h; rt_prepare_triangles,
+// rt_kernels.hip), beside corner and UV words an edit must not touch.  Two kernels, one thread per triangle:
 //   rte_check_ids   reads the ids that will be in effect -- an array of T ids (coalesced), or word 21 of the resident rows when the
 //                   tables shrink under ids that stay -- and raises RT_PREP_ERR_TRI_MATERIAL in the scene's validation word for an
 //                   id >= M: one ballot per wave, at most one atomic per wave.  Negative ids are legal ("no material").
 //   rte_store_ids   launched only after the host has read a clean validation word: word 21 of every row of the set in use, one 4-byte
-//                   store per row; the other 23 words are neither read nor written.
+//                   store per row; the row's other words are neither read nor written.
 #include <hip/hip_runtime.h>
 
 #include "rt_device.h"
@@ -15,7 +15,7 @@
 
 namespace {
 
-constexpr uint32_t ROW_WORDS = 24, ID_WORD = 21;
+constexpr uint32_t ROW_WORDS = RT_TRI_SHADE_WORDS, ID_WORD = 21;
 
 __global__ __launch_bounds__(256) void rte_check_ids(uint32_t T, uint32_t M, const int *__restrict__ ids, const int *__restrict__ rows, uint32_t *err)
 {

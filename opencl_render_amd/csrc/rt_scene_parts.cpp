@@ -113,7 +113,7 @@ int build_geometry(rtHipScene *sc, const rtHipSceneDesc *d)
     HIP_OK(sc->stager.copy(du, d->triUv, T * 24));
     HIP_OK(sc->stager.copy(dn, d->triNormal, T * 48));
     float *rec = nullptr, *shade = nullptr;
-    if (sc->alloc<float>(part, T * 16, &rec) || sc->alloc<float>(part, T * 24, &shade)) return -1;
+    if (sc->alloc<float>(part, T * 16, &rec) || sc->alloc<float>(part, T * RT_TRI_SHADE_WORDS, &shade)) return -1; // (hipMalloc: each row is one line)
     // ids are checked on the device before anything gathers through them; a scene with a bad id fails at the end of the build
     HIP_OK(rtp_validate(d->triangleCount, d->vertexCount, d->materialCount, di, (const int *)dm, 0, nullptr, nullptr, 0, nullptr, sc->prepErr, sc->stream));
     HIP_OK(hipStreamSynchronize(sc->stream));
@@ -473,7 +473,7 @@ int clone_part(rtHipScene *dst, const rtHipScene *src, int part)
     if (src->geo.live >= 0 && (part == PART_GEOMETRY || part == PART_GRID)) { // a source whose shape was updated holds it in a set of its own
         const rtHipScene::GeoMove::Set &L = src->geo.set[src->geo.live];
         const uint64_t T = src->dev.triangleCount ? src->dev.triangleCount : 1, n = src->gridListSize ? src->gridListSize : 1;
-        if (part == PART_GEOMETRY) { blocks = { L.triRec, L.triShade }; sizes = { T * 64, T * 96 }; }
+        if (part == PART_GEOMETRY) { blocks = { L.triRec, L.triShade }; sizes = { T * 64, T * RT_TRI_SHADE_WORDS * 4 }; }
         else {
             blocks = { L.boxMin, L.cellLut, L.gridStart, L.gridList, L.gridBits, L.sparse, L.pairRec };
             sizes = { GEO_PLANE_BYTES, GEO_LUT_BYTES, GEO_START_BYTES, n * 4, GEO_BITS_BYTES, GEO_SPARSE_BYTES, n * 64 };

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void wf_surface_passes_kernel(const RtDevScene
         const uint32_t hit_tri = camera_scan(S, localPixel, eye, dir, 0.f, RT_INF, RT_NONE, hit_t, hit_l1, hit_l2);
         V3 n = mk(0.f, 0.f, 0.f), albedo = mk(0.f, 0.f, 0.f);
         if (hit_tri != RT_NONE) {
-            const float *shade = S.triShade + 24 * (size_t)hit_tri;
+            const float *shade = S.triShade + RT_TRI_SHADE_WORDS * (size_t)hit_tri;
             const int m = __float_as_int(shade[21]);
             const V3 where = along(eye, hit_t, dir);
             MatRec mat;
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(256) void rt_matte_count_kernel(const RtDevScene S,
         uint32_t g = tri;
         if (tri != RT_NONE) {
             if (A.kind == RT_MATTE_MATERIAL) {
-                const int m = __float_as_int(S.triShade[24 * (size_t)tri + 21]);
+                const int m = __float_as_int(S.triShade[RT_TRI_SHADE_WORDS * (size_t)tri + 21]);
                 g = m < 0 ? RT_NONE : (uint32_t)m;
             } else if (A.kind == RT_MATTE_GROUP) g = A.groups[tri];
         }
@@ -708,18 +708,26 @@ __device__ __forceinline__ void log_round_rays(const RtWavefront &W, const uint3
     }
 }
 
-// What shading a hit reads of its triangle, fetched in one batch: the 24-float shading row (rt_device.h, triShade) and the
-// first vertex (triRec[0]).
+// What shading a hit reads of its triangle, fetched in one batch from ONE 128-byte line: the shading row's 24 packed floats and its copy
+// of the first vertex (rt_device.h, triShade: quad 6 = triRec quad 0).
 struct TriRow { float v[24]; float4 a; uint32_t tri; };
 __device__ __forceinline__ void load_tri_row(const RtDevScene &S, uint32_t tri, TriRow &row)
 {
-    const float4 *sp = reinterpret_cast<const float4 *>(S.triShade + 24 * (size_t)tri);
+    const float4 *sp = reinterpret_cast<const float4 *>(S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri);
     const float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3], s4 = sp[4], s5 = sp[5];
-    row.a = reinterpret_cast<const float4 *>(S.triRec)[4 * (size_t)tri];
+    row.a = sp[6];
     row.v[0] = s0.x; row.v[1] = s0.y; row.v[2] = s0.z; row.v[3] = s0.w; row.v[4] = s1.x; row.v[5] = s1.y; row.v[6] = s1.z; row.v[7] = s1.w;
     row.v[8] = s2.x; row.v[9] = s2.y; row.v[10] = s2.z; row.v[11] = s2.w; row.v[12] = s3.x; row.v[13] = s3.y; row.v[14] = s3.z; row.v[15] = s3.w;
     row.v[16] = s4.x; row.v[17] = s4.y; row.v[18] = s4.z; row.v[19] = s4.w; row.v[20] = s5.x; row.v[21] = s5.y; row.v[22] = s5.z; row.v[23] = s5.w;
     row.tri = tri;
+}
+// Where a later round's hit reads vertex a: quad 6 of the triangle's own row (the line its other shading words come from, not triRec).  The
+// address is made from the triangle on its own, as the record's address was: derived from the row pointer, the load joined the row's other
+// loads and the ordered later-round kernels spilled more registers.
+__device__ __forceinline__ const float4 *tri_row_a(const RtDevScene &S, uint32_t tri)
+{
+    asm volatile("" : "+v"(tri));
+    return reinterpret_cast<const float4 *>(S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri) + 6;
 }
 
 // FIRST = round 0: every entry is a primary hit (stage, ring positions and the colour so far are known), a path's id is its queue index.
@@ -799,12 +807,13 @@ __global__ __launch_bounds__(256, RT_WF_ANSWER_WAVES) void wf_answer_kernel(cons
             if (laState == 2u) laKey = W.laKey[a]; // (an answer kept from an earlier round)
             bool finished = false;
             if (stage == WS_SHADOW) { // PC_SHADOW_RESULT (:612-626) of light 0
-                const float4 sp = W.shP[a], sf = W.shFace[a];
+                const float4 sp = W.shP[a];
                 const float lmax = oc.w;
                 const V3 zero = mk(0.f, 0.f, 0.f);
-                V3 face = xyz(sf), atten = mk(1.f, 1.f, 1.f);
+                // (the parked face entry is always SHADE_BEGIN's 0.1, and `front` is a bit of the flags word: rt_wf_logic_body.h)
+                V3 face = mk(0.1f, 0.1f, 0.1f), atten = mk(1.f, 1.f, 1.f);
                 if (key != ~0ull) { atten.x *= zero.x; atten.y *= zero.y; atten.z *= zero.z; }
-                class_light_accum(face, sp.w, sf.w != 0.f, lmax, lc, atten);
+                class_light_accum(face, sp.w, (meta.z & RT_WF_META_CLASS_FRONT) != 0u, lmax, lc, atten);
                 class_shade_end(out, xyz(sp), face);
                 head = (head + 1) % RT_RING; // PC_NEXT_RAY (:509)
                 if (head == tail) finished = true;
@@ -2004,7 +2013,7 @@ __global__ __launch_bounds__(256) void rt_bake_raster_kernel(const RtDevScene S,
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= A.count) return;
     const uint32_t tri = A.first + i;
-    const float *sh = S.triShade + 24 * (size_t)tri;
+    const float *sh = S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri;
     if (A.matchMaterial && __float_as_int(sh[21]) != A.material) return;
     float uv[6];
     for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
@@ -2026,7 +2035,7 @@ __global__ __launch_bounds__(256) void rt_bake_raster_big_kernel(const RtDevScen
     const uint32_t stride = gridDim.x * 256u;
     for (uint32_t b = 0; b < n; ++b) {
         const uint32_t tri = A.bigList[b];
-        const float *sh = S.triShade + 24 * (size_t)tri;
+        const float *sh = S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri;
         float uv[6];
         for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
         uint32_t x0, x1, y0, y1;
@@ -2050,7 +2059,7 @@ __global__ __launch_bounds__(256) void rt_bake_points_kernel(const RtDevScene S,
     bool trace = false;
     uint32_t open = 0;
     if (tri != RT_NONE) {
-        const float *sh = S.triShade + 24 * (size_t)tri;
+        const float *sh = S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri;
         float uv[6];
         for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
         const uint32_t y = t / A.width, x = t - y * A.width;

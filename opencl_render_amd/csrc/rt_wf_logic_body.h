@@ -218,8 +218,11 @@
                 shade = res_tri != RT_NONE;
                 advance = !shade;
             } else if (!SHADE && stage == WS_SHADOW) { // PC_SHADOW_RESULT (:612-626) of light 0
-                const float4 sp = W.shP[a], sf = W.shFace[a];
-                P = xyz(sp); ndl = sp.w; face = xyz(sf); front = (sf.w != 0.f);
+                // A class path parks behind a shadow ray only straight after SHADE_BEGIN set face = 0.1 (no light_accum comes before light 0's
+                // shadow ray), so the face entry it would have parked is that literal: W.shFace is neither stored nor loaded by the class
+                // kernels, and `front` rides in bit 16 of the flags word (RT_WF_META_CLASS_FRONT)
+                const float4 sp = W.shP[a];
+                P = xyz(sp); ndl = sp.w; face = mk(0.1f, 0.1f, 0.1f); front = (meta.z & RT_WF_META_CLASS_FRONT) != 0u;
                 // of the answered ray only its far end is wanted, of the answer only whether there is one: which occluder, and where
                 // along the ray, feeds nothing in this class (no transparency look-up)
                 lmax = parkedLmax; // (as stored when the shadow ray was emitted; the entry itself is not touched)
@@ -247,14 +250,14 @@
             }
             if (shade) { // SHADE_BEGIN (:532-561), the hit's one spawn, light 0
                 hit_tri = res_tri;
-                const float *shadeRow = FIRST ? row.v : S.triShade + 24 * (size_t)res_tri; // (round 0 shades the camera hit only)
+                const float *shadeRow = FIRST ? row.v : S.triShade + RT_TRI_SHADE_WORDS * (size_t)res_tri; // (round 0 shades the camera hit only)
                 const int m = __float_as_int(shadeRow[21]);
                 const float *uv = shadeRow + 15;
                 where = along(cur_o, res_t, cur_d);
                 MatRec mat;
                 mat.desc[0] = mat.desc[1] = mat.desc[2] = mat.desc[3] = mat.desc[4] = 0u; mat.m = m;
                 if (0 <= m) mat = load_mat(S, m);
-                n = shading_normal<false, true>(S, sh, where, cur_o, cur_d, hit_tri, res_l1, res_l2, shadeRow, m, cn, &mat, FIRST ? &row.a : nullptr);
+                n = shading_normal<false, true>(S, sh, where, cur_o, cur_d, hit_tri, res_l1, res_l2, shadeRow, m, cn, &mat, FIRST ? &row.a : tri_row_a(S, res_tri));
                 V3 tex = mk(0, 0, 0);
                 const V3 transp = zero, refl = zero, lum = zero;
                 if (0 <= m && mat.desc[CH_COLOR]) {
@@ -362,14 +365,13 @@
                 // (rtmax == lmax then), which is all the answer's reader wants of the entry; for a ring ray the word is not read.
                 W.outc[a] = pack4(out, rtmax);
                 // (a shadow ray leaves with atten = 1, never stored; the next light index is always 0)
-                const uint32_t flags = (uint32_t)head | ((uint32_t)tail << 4) | (emitStage << 8) | (laState << 10) | ((uint32_t)laIndex << 12);
+                // (`front` is read back only when the path is parked on a shadow ray; the face entry that goes with it is the literal 0.1)
+                const uint32_t flags = (uint32_t)head | ((uint32_t)tail << 4) | (emitStage << 8) | (laState << 10) | ((uint32_t)laIndex << 12) |
+                                       (front ? RT_WF_META_CLASS_FRONT : 0u);
                 if (FIRST) reinterpret_cast<uint2 *>(W.meta + a)[1] = make_uint2(flags, hit_tri);
                 else W.meta[a] = make_uint4(meta.x, meta.y, flags, hit_tri);
                 if (laState == 2u && laFetched) W.laKey[a] = laKey;
-                if (emitStage == WS_SHADOW) {
-                    W.shP[a] = pack4(P, ndl);
-                    W.shFace[a] = pack4(face, front ? 1.f : 0.f);
-                }
+                if (emitStage == WS_SHADOW) W.shP[a] = pack4(P, ndl);
             }
         } else if (live) {
             // Round 0 issues its loads in as few dependent batches as the data allows -- a wave runs one chunk and has two
@@ -560,7 +562,10 @@
             while (pc != PC_EXIT) {
                 if (pc == PC_RAY_RESULT) {
                     if (res_tri == RT_NONE) { pc = PC_NEXT_RAY; continue; }
-                    shade_begin(S.triShade + 24 * (size_t)res_tri, nullptr); // (read where it is used: registers, see above)
+                    // (read where it is used: registers, see above.  Vertex a still comes from triRec here: taken from the row's quad 6 -- through
+                    // the row pointer, through tri_row_a or through an opaque pointer -- the ORDERED instantiations of this machine spilled
+                    // 8 to 16 bytes more per lane, and they have none to give)
+                    shade_begin(S.triShade + RT_TRI_SHADE_WORDS * (size_t)res_tri, nullptr);
                 } else if (pc == PC_LIGHT_SETUP) { // :563-607
                     if (j >= S.lightCount) { pc = PC_SHADE_END; continue; }
                     toL = mk(0.f, 0.f, 0.f); atten = mk(1.f, 1.f, 1.f); attStored = false;
@@ -599,7 +604,7 @@
                 } else if (pc == PC_SHADOW_RESULT) { // :612-626
                     pc = PC_LIGHT_ACCUM;
                     if (res_tri != RT_NONE) {
-                        const float *oshade = S.triShade + 24 * (size_t)res_tri;
+                        const float *oshade = S.triShade + RT_TRI_SHADE_WORDS * (size_t)res_tri;
                         const int om = __float_as_int(oshade[21]);
                         V3 tr = mk(0.f, 0.f, 0.f);
                         if (0 <= om) {

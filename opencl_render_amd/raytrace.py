@@ -821,6 +821,9 @@ SCENE_VIEWS = {
     "tri_shade": (4, np.float32, 24), "grid_bits": (5, np.uint64, 1), "block_sparse": (6, np.uint32, 1), "pair_rec": (7, np.uint32, 16),
     "cell_lut": (8, np.uint8, 1),
 }
+# further views of those arrays, numbered apart from 0 .. RT_SCENE_VIEWS - 1 (scene_view takes either table's names):
+# tri_shade_row = RT_SCENE_VIEW_TRI_SHADE_ROW, the shading rows as stored (128 bytes each; tri_shade is their first 24 words, packed)
+SCENE_VIEWS_EXTRA = {"tri_shade_row": (18, np.float32, 32)}
 SCENE_VIEW_CLIP_PLANES = 16  # (RT_SCENE_VIEW_CLIP_PLANES; read by ResidentScene.clip_planes)
 SCENE_VIEW_CLIP_APPLIED = 17  # (RT_SCENE_VIEW_CLIP_APPLIED; read by ResidentScene.clip_applied)
 ROUND_VISIT_FIELDS = 12  # (RT_ROUND_VISIT_FIELDS)
@@ -1299,8 +1302,9 @@ class ResidentScene:
     def scene_view(self, name: str, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """Elements [first, first + count) (default: to the end) of one of the scene's device arrays (rtHipTestSceneView; names in
         SCENE_VIEWS): cam_start / cam_end tile-major u32, tri_rec [n, 16] f32, tri_shade [n, 24] f32, grid_bits u64, block_sparse u32
-        words, pair_rec [n, 16] u32 words (floats as their bits), cell_lut u8, header u32 (SCENE_VIEW_HEADER)."""
-        what, dtype, words = SCENE_VIEWS[name]
+        words, pair_rec [n, 16] u32 words (floats as their bits), cell_lut u8, header u32 (SCENE_VIEW_HEADER); SCENE_VIEWS_EXTRA:
+        tri_shade_row [n, 32] f32, the shading rows as the device stores them."""
+        what, dtype, words = SCENE_VIEWS[name] if name in SCENE_VIEWS else SCENE_VIEWS_EXTRA[name]
         total = lib().rtHipTestSceneView(self.handle, what, 0, 0, None)
         if total < 0:
             raise RuntimeError("rtHipTestSceneView failed: " + last_error())
