@@ -1191,8 +1191,8 @@ class ResidentScene:
             raise RuntimeError(f"rtHipSceneSetMaterials failed ({rc}): {last_error()}")
 
     def _describe_edit(self, **fields) -> None:
-        """self.scene becomes a copy with `fields` replaced: what readback_passes' material ids, scene_desc for a later like= and a
-        fresh twin read."""
+        """self.scene becomes a copy with `fields` replaced: what scene_desc for a later like=, a fresh twin and -- from the next frame
+        on -- readback_passes' material ids read."""
         import copy
 
         sc = copy.copy(self.scene)
@@ -1339,12 +1339,15 @@ class ResidentScene:
 
     def render(self, stream: int = 0):
         self._check(lib().rtHipRenderTiles(self.handle, stream or None), "rtHipRenderTiles")
+        self._frame_scene = self.scene  # (the description the frame was issued under: readback_passes' material ids are that frame's)
 
     def finish(self) -> bool:
         """After the caller's own synchronisation: checks that the frames issued since the last check were complete
         (rtHipFrameFinish).  Returns True when the last frame had to be rendered again (its launch plan was too short)."""
         redone = C.c_int(0)
         self._check(lib().rtHipFrameFinish(self.handle, C.byref(redone)), "rtHipFrameFinish")
+        if redone.value:
+            self._frame_scene = self.scene  # (rendered again, under the description in effect now)
         return bool(redone.value)
 
     def set_sample_window(self, total: Optional[int] = None, first: int = 0, divisor: Optional[int] = None, accumulate: bool = False,
@@ -1432,7 +1435,9 @@ class ResidentScene:
     def readback_passes(self, out: Optional[dict] = None) -> dict:
         """The passes that are on, as [H, W] arrays: alpha u16, depth f32, triangle u32, and with triangle also material i32
         (-1 on a miss) and -- for a scene made by frontend.scene_from_meshes -- mesh i32 (-1 on a miss); normal and albedo as [H, W, 3]
-        f32, the means over the pixel's samples.  `out`: arrays of an earlier
+        f32, the means over the pixel's samples.  The material ids are those of the frame that filled the pass buffers, like every
+        other pass: the last frame of render() (or that frame rendered again by finish()).  A later set_materials shows in them once
+        render() has issued a frame under it; render_counted() runs the megakernel, which writes no pass, so it leaves them alone.  `out`: arrays of an earlier
         call (another instance's tiles) to store this instance's tiles into; pixels of other tiles keep their values."""
         sc = self.scene
         mask = getattr(self, "passes", 0)
@@ -1462,7 +1467,7 @@ class ResidentScene:
             tri = out["triangle"]
             hit = tri != 0xFFFFFFFF
             idx = np.where(hit, tri, 0).astype(np.int64)
-            mat = np.asarray(sc.tri_material, np.int32)
+            mat = np.asarray(getattr(self, "_frame_scene", sc).tri_material, np.int32)
             out["material"] = np.where(hit, mat[idx] if len(mat) else -1, -1).astype(np.int32)
             tri_mesh = getattr(sc, "tri_mesh", None)
             if tri_mesh is not None:

@@ -37,7 +37,21 @@ shape the one before ended in, and its first step repeats the previous one's las
 Arguments are drawn against a light copy of the state so that camera and shape steps always change something and refusals stay rare;
 a draw that misses one of the caps below is drawn again (attempt 0, 1, ...): generation is a pure function of (scene, seed).  The wide
 seeds have caps of their own (wide_caps); a window that continues is only ever drawn at first = 0, so no frame continues from a buffer
-the header leaves undefined."""
+the header leaves undefined.
+
+Looks.  The edit seeds (KINDS_EDIT, on class_textured_bumped, the base scene of the opaque-diffuse class) add the look to the state:
+(light set, material set, (id variant, modulus)) from the small tables of look_parts, the model's Scene being the base scene's with
+those fields replaced (edit_cases.twin_of).  A World per look keeps what depends on shading and shares the rest with the World of the
+scene's own look.  The last rendered frame records its look: read_passes, denoise, temporal(denoise=) and the variance filter read
+that frame's buffers and are that look's products, stale like a stale pose; what traces anew follows the look in effect; a continuing
+frame is rendered onto the model's planes whatever look they came from, and the history arrays are carried across edits.  lights,
+materials and ids check the path class (R.path_class of the model's Scene), the scene's description and word 21 of the shading rows;
+refused_edit one illegal argument of EDIT_REFUSALS by code and text, with addresses and byte count unchanged -- except that the first
+call that brings host ids, refused or not, makes their staging of 4 bytes per triangle (the header's Memory paragraph: ids are
+checked on the device); matte_groups installs or frees the group table, which is state; mattes compares rtHipMatteDefaults with the
+model's last window and the four outputs with matte_oracle, bit for bit, over the sample ids of the current pose and shape and the
+table of the kind.  Whether a clone inherits the group table is left open by the header and is not checked.  Every sequence starts
+from a fresh scene under the scene's own look.  The caps of these seeds: edit_caps, shows_its_edits and histories_cross."""
 import ctypes
 
 import numpy as np
@@ -46,13 +60,16 @@ import ao_oracle
 import bake_oracle
 import camera_cases as CC
 import denoise_oracle as D
+import edit_cases as EC
 import geometry_cases as GC
+import matte_oracle as MA
 import motion_cases as MC
 import motion_oracle as MO
 import oracle_lib as O
 import prep_oracle as P
 import query_cases as Q
 import sample_window_cases as WC
+import scenarios
 import temporal_oracle as TO
 import variance_oracle as VO
 from clip_checks import assert_bound
@@ -67,6 +84,8 @@ K = len(KINDS)
 # The alphabet is a property of the seed: the seeds drawn before sample windows and the moments history existed keep KINDS (their
 # sequences are what they were), the wide seeds of a scene draw from KINDS_WIDE.
 KINDS_WIDE = KINDS + ("window", "variance")
+# The edit seeds of a scene draw from KINDS_EDIT: scene edits and mattes beside everything else (a circuit of 25 * 25 + 1 = 626 steps).
+KINDS_EDIT = KINDS_WIDE + ("lights", "materials", "ids", "refused_edit", "matte_groups", "mattes")
 POSES = CC.POSES + ("shifted",)
 NEAR = ("home", "pan", "shifted")
 SURFACE = R.PASS_NORMAL | R.PASS_ALBEDO
@@ -88,7 +107,17 @@ MIN_WARM = 0.35  # of a seed's temporal steps follow another one of their sequen
 SCENES = {"mirror_hall": dict(size=(24, 16), samples=2, circuits=(1, 2), walks=(101, 102), wide_circuits=(4,), wide_walks=(103,),
                               shapes=GC.SEQUENCE, cut=40),
           "axis_near_axis_mixed": dict(size=(136, 132), samples=2, circuits=(3,), walks=(), wide_circuits=(), wide_walks=(106,),
-                                       shapes=tuple(n for n in GC.SEQUENCE if n != "translate"), cut=25, shape_steps=2, walk_cut=31)}
+                                       shapes=tuple(n for n in GC.SEQUENCE if n != "translate"), cut=25, shape_steps=2, walk_cut=31),
+          # class_textured_bumped is the one base scene of the opaque-diffuse class (six materials with one-texel height maps, a fifth
+          # of the triangles without a material, one tube light, smooth normals); its seeds draw from KINDS_EDIT, and an edit walks
+          # it into the general class and back (LIGHT_SETS, MATERIAL_SETS).  Cropped as mirror_hall is.  It keeps every pose and shape:
+          # no state is empty.  min_hit: the soup is sparse (0.35..0.54 of the centre rays hit from the four poses outside it) and from
+          # `inside` more than half of it lies behind the eye, where 0.11..0.21 hit -- 42 pixels and more of the 384, which temporal,
+          # motion and matte steps still have answers for; motion_cases.MIN_HIT (0.2) was sized for rooms and halls.
+          "class_textured_bumped": dict(size=(24, 16), samples=2, circuits=(), walks=(), wide_circuits=(), wide_walks=(),
+                                        edit_circuits=(21,), edit_walks=(110,), shapes=GC.SEQUENCE, cut=40, min_hit=0.1)}
+# A scene's number in the generators' keys (the order the scenes were added in: a new scene leaves the older ones' draws alone).
+SCENE_KEY = {"axis_near_axis_mixed": 0, "mirror_hall": 1, "class_textured_bumped": 2}
 # Measured on the oracle by tests/test_session.py, which prints them, over the visited states (hit share of the centre rays; share of the
 # oracle's pixels that differ between the two states of a camera or shape step, home <-> reindex excepted as in geometry_cases.py):
 # mirror_hall 33 states visited, hit share 0.596..0.987, changed share 0.591..1.000 over 101
@@ -104,11 +133,28 @@ COUNTS = dict(sequences=34, steps=1019)
 # two successive windows of a sequence differ (2 pairs); the test asserts half of each, which leaves room for another draw.
 COUNTS_WIDE = dict(sequences=14, steps=493)
 WINDOW_SHARES = dict(continuing=0.950, successive=0.987)
+# The edit seeds (tests/test_session.py prints the figures and asserts the counts): 82 edits, every one changing the look; class
+# crossings: 9 by lights to the general class and 6 back, 17 by materials to the general class and 8 back; frames directly after a
+# camera / a shape step: 1 / 1 in the general class, 2 / 1 in the opaque-diffuse one; 9 clones in another class than the one of
+# creation; 1 frame continues another look's buffer; 2 temporal steps and 1 variance step find a live history across a class change
+# under max_history 32, 32 and 4: they blend it in in 1.000, 0.953 and 0.339 of the pixels and differ there from the answer over an
+# empty history;
+# 26 mattes (6 triangle, 13 material, 7 group; 1 more refused for want of a table), 10 with defaults, 9 of those under another
+# window_last than the default; 4 before any frame, 2 group mattes after a shape step and 6 after an edit made since the table was
+# installed, 9 material mattes after an ids step; 2 overflow into rest, 24 hold a pixel of two layers, 13 take another sample count
+# than S.  The 24 edits that a frame shows change 0.094..0.578 of the oracle's pixels (floor: MIN_EDIT_CHANGED); all 11 pairs of
+# consecutive mattes under different states or tables differ.  27 states visited, hit share 0.107..0.539, changed share 0.034..0.688
+# over 53 moves.
+COUNTS_EDIT = dict(sequences=19, steps=703)
 WINDOW_SIZES = (2, 3, 4)  # N / S of a drawn window
 VARIANCE_FILTER = dict(iterations=2, spatial_below=2.0)
 SMALL = "mirror_hall"  # AO and the bake are also compared with their numpy oracles here
-# Reduced sequences of mismatches found by the circuits: name -> (scene, (start pose, start shape), steps).  None so far.
-REGRESSIONS = {}
+# Reduced sequences of mismatches found by the circuits: name -> (scene, (start pose, start shape), steps).
+# material_pass_after_ids (reduced from class_textured_bumped seed 21 part 14, step 35): read_passes after an ids edit, with no frame between, gave the
+# NEW ids in the material pass beside the old frame's albedo -- ResidentScene.readback_passes looked the frame's triangles up in the
+# description in effect.  It reads the description the frame was issued under now.
+REGRESSIONS = {"material_pass_after_ids": ("class_textured_bumped", ("home", "home"),
+                                           (("passes", 31), ("frame", None), ("ids", ((1, 6), "numpy")), ("read_passes", None)))}
 
 
 def flags(mask):
@@ -116,17 +162,110 @@ def flags(mask):
                 normal=bool(mask & R.PASS_NORMAL), albedo=bool(mask & R.PASS_ALBEDO))
 
 
+# ---- looks: what the edits of a resident scene replace ------------------------------------------------------------------------------
+# A look is (light set, material set, (id variant, modulus)): the ids in effect are the variant's folded into 0 .. modulus - 1 with every
+# -1 kept (edit_cases.fold).  The modulus is the material count of the set the ids were handed over for: tables that come alone leave
+# the resident ids as they are, so it may be smaller than the count of the set in effect.  The tables are small and fixed, so that the
+# oracle's products and the twins of a look are shared between steps.
+LIGHT_SETS = ("own", "none", "sun", "sun_spot", "many65")  # sun_spot and many65 (past the logic kernel's 64-light split): general class
+MATERIAL_SETS = ("own", "hall", "lambert2")  # hall: mirror_hall's four, reflective and transparent: general class
+ID_VARIANTS = (0, 1)  # the scene's own ids; a permutation of them with more -1 mixed in
+EDIT_REFUSALS = ("shrink", "bad_first", "bad_last", "host_pointer", "neither", "past_atlas", "65536_lights", "null_light_array")
+REJECTED = "a triangle uses a material >= materialCount"
+MATTE_KINDS = ("triangle", "material", "group")
+MATTE_LAYERS = (2, 4, 8)
+MATTE_SELECT = (0, 2, 5)  # ids selected: the most frequent of the answer, one that nothing hits and the most frequent again
+GROUP_SEEDS = (5, 6, 7)
+_look_parts = {}
+
+
+def default_look(name):
+    return ("own", "own", (0, look_parts(name)["counts"]["own"]))
+
+
+def look_parts(name):
+    """The tables of scene `name`: {"lights": set -> six arrays, "materials": set -> tables and atlas, "counts": set -> material count,
+    "ids": variant -> [T] int32 before folding}."""
+    if name not in _look_parts:
+        base = getattr(scenarios, name)()
+        T = base.triangle_count
+        rng = np.random.default_rng(77)
+        own = np.asarray(base.tri_material, np.int32)
+        mixed = np.where(rng.random(T) < 0.15, -1, own[rng.permutation(T)]).astype(np.int32)
+        lights = dict(own=EC.lights_of(base), none=EC.lights_of([]), sun=EC.lights_of(EC.ONE_SUN), sun_spot=EC.lights_of(EC.ONE_SUN + [EC.SPOT]),
+                      many65=EC.lights_of(EC.many_lights(65, 2)))
+        mats = dict(own=EC.materials_of(base), hall=EC.materials_of(scenarios.mirror_hall()),
+                    lambert2=EC.materials_of([scenarios._lambert(), scenarios._lambert(color=(220, 40, 30))]))
+        counts = {k: int(np.asarray(v["mat_size"]).reshape(-1, 2).shape[0] // 5) for k, v in mats.items()}
+        _look_parts[name] = dict(lights=lights, materials=mats, counts=counts, ids={0: own, 1: mixed})
+    return _look_parts[name]
+
+
+def look_ids(name, ids):
+    """The [T] int32 material ids of a look's id part (variant, modulus)."""
+    return EC.fold(look_parts(name)["ids"][ids[0]], ids[1])
+
+
+_look_class = {}
+
+
+def look_class(name, look):
+    """R.path_class of the scene under the look (decided on the host from the tables alone)."""
+    if (name, look[:2]) not in _look_class:
+        parts = look_parts(name)
+        sc = EC.twin_of(getattr(scenarios, name)(), lights=parts["lights"][look[0]], materials=parts["materials"][look[1]])
+        _look_class[name, look[:2]] = R.path_class(sc)
+    return _look_class[name, look[:2]]
+
+
+def group_table(T, seed):
+    """Many triangles in few groups, some in none, some group ids above T (the table of tests/test_mattes_gpu.py)."""
+    rng = np.random.default_rng(seed)
+    table = rng.integers(0, 5, T).astype(np.uint32)
+    table[rng.random(T) < 0.15] = NONE
+    big = rng.random(T) < 0.2
+    table[big] = rng.choice(np.array([T + 1, 1_000_000, 0xFFFFFFFE], np.uint32), int(big.sum()))
+    return table
+
+
+def selection(g, n):
+    """n ids to select from the samples' ids g: the most frequent ones, then an id nothing hits, then the most frequent again."""
+    if not n:
+        return []
+    hit = g[g != NONE]
+    values, counts = np.unique(hit, return_counts=True)
+    ranked = [int(v) for v in values[np.argsort(-counts, kind="stable")]]
+    unhit = next(t for t in range(1 << 20) if t not in set(ranked))
+    return (ranked[:max(n - 2, 1)] + [unhit] + ranked[:1])[:n]
+
+
 # ---- the oracle's view of a base scene's 5 x 7 states -------------------------------------------------------------------------------
 class World:
-    def __init__(self, name):
-        self.name, self.size = name, SCENES[name]["size"]
-        self.base = MC.base_scene(name, self.size)
+    """The states of a base scene under one look (None: the scene as scenarios.py makes it).  The World of another look shares what
+    depends on geometry and camera alone -- grids, lists, walks, flows, sample ids and all of prep_oracle's records but the id word --
+    with the World of the scene's own look, and keeps what depends on shading: the Scenes, the planes and the window frames."""
+
+    def __init__(self, name, look=None):
+        self.name, self.size, self.look = name, SCENES[name]["size"], look
+        self.key = name if look is None else (name, look)  # (what a twin of this World's Scenes is cached under)
+        self.geo = self if look is None else world(name)
+        self.base = MC.base_scene(name, self.size) if look is None else self.dressed(self.geo.base)
         self.width, self.height = self.base.width, self.base.height
         self._shape, self._state, self._planes, self._trace, self._flow, self._prep, self._window = {}, {}, {}, {}, {}, {}, {}
+        self._ids = {}
         assert self.base.sample_count == SCENES[name]["samples"]
+
+    def dressed(self, sc):
+        """The Scene with this World's lights, materials and ids in place of its own."""
+        parts = look_parts(self.name)
+        return EC.twin_of(sc, lights=parts["lights"][self.look[0]], materials=parts["materials"][self.look[1]],
+                          ids=look_ids(self.name, self.look[2]))
 
     def shape_scene(self, shape):
         if shape not in self._shape:
+            if self.look is not None:
+                self._shape[shape] = self.dressed(self.geo.shape_scene(shape))
+                return self._shape[shape]
             sc = GC.with_arrays(self.base, *GC.arrays(self.base, shape), lists=False)
             sc.box_min, sc.grid_start, sc.grid_list = O.oracle_scene_grid(sc)
             self._shape[shape] = sc
@@ -134,10 +273,25 @@ class World:
 
     def prep(self, shape):
         """prep_oracle's records and dense view of the shape (seconds on the larger scene's grid, and a circuit updates to the same
-        few shapes many times)."""
+        few shapes many times).  Under a look: the shape's, with word 21 of the shading rows -- the material id -- the look's."""
         if shape not in self._prep:
+            if self.look is not None:
+                rec, shade, view = self.geo.prep(shape)
+                shade = np.array(shade, copy=True)
+                shade.view(np.int32)[:, 21] = look_ids(self.name, self.look[2])
+                self._prep[shape] = (rec, shade, view)
+                return self._prep[shape]
             self._prep[shape] = prep_of(self.shape_scene(shape))
         return self._prep[shape]
+
+    def sample_ids(self, pose, shape, N, f, C_):
+        """matte_oracle.sample_ids of the state under the window {N, f} with C samples: the primary hit of every sample."""
+        if self.look is not None:
+            return self.geo.sample_ids(pose, shape, N, f, C_)
+        if (pose, shape, N, f, C_) not in self._ids:
+            self._ids[pose, shape, N, f, C_] = MA.sample_ids(self.state(pose, shape), N, f, C_)
+            self._ids[pose, shape, N, f, C_].setflags(write=False)
+        return self._ids[pose, shape, N, f, C_]
 
     def warm(self, states):
         """Everything the checks read of the given (pose, shape) states, made now: a test module's fixture calls this once, so that a
@@ -150,7 +304,8 @@ class World:
     def state(self, pose, shape):
         """The Scene of (pose, shape) with the oracle's grid and camera lists."""
         if (pose, shape) not in self._state:
-            self._state[pose, shape] = CC.posed(self.shape_scene(shape), pose)
+            self._state[pose, shape] = (CC.posed(self.shape_scene(shape), pose) if self.look is None
+                                        else self.dressed(self.geo.state(pose, shape)))
         return self._state[pose, shape]
 
     def planes(self, pose, shape):
@@ -172,12 +327,16 @@ class World:
         return self._window[key]
 
     def trace(self, pose, shape):
+        if self.look is not None:
+            return self.geo.trace(pose, shape)
         if (pose, shape) not in self._trace:
             self._trace[pose, shape] = MO.trace(self.state(pose, shape))
         return self._trace[pose, shape]
 
     def flow(self, cur, ref):
         """motion_oracle.motion of state `cur` against the reference state `ref` ((pose, shape) each)."""
+        if self.look is not None:
+            return self.geo.flow(cur, ref)
         if (cur, ref) not in self._flow:
             self._flow[cur, ref] = MO.project(self.state(*cur), self.state(*ref), self.trace(*cur))
         return self._flow[cur, ref]
@@ -186,10 +345,14 @@ class World:
 _worlds = {}
 
 
-def world(name):
-    if name not in _worlds:
-        _worlds[name] = World(name)
-    return _worlds[name]
+def world(name, look=None):
+    """The World of the scene under `look`; the scene's own look is the World of no look."""
+    if look is not None and look == default_look(name):
+        look = None
+    key = name if look is None else (name, look)
+    if key not in _worlds:
+        _worlds[key] = World(name, look)
+    return _worlds[key]
 
 
 # ---- twins ---------------------------------------------------------------------------------------------------------------------------
@@ -205,7 +368,7 @@ def twin(w, pose, shape, mask, total=None, first=0):
     and the bound not on the pose either)."""
     samples = w.base.sample_count
     total = samples if total is None else total
-    key = (w.name, pose, shape, mask) + (() if (total, first) == (samples, 0) else (total, first))
+    key = (w.key, pose, shape, mask) + (() if (total, first) == (samples, 0) else (total, first))
     if key not in _twin:
         t = R.ResidentScene(w.state(pose, shape), 0)
         try:
@@ -280,9 +443,30 @@ def window_kind(win, samples):
     return "sequence" if adv else "fixed"
 
 
+class CapLog:
+    """What the caps of the edit seeds ask about a sequence, kept beside the light state: nothing but the caps and the draw's
+    steering towards them reads it."""
+
+    def __init__(self):
+        # ("edit", kind, class before, class after, look before, look after), ("mattes", facts), ("clone", whether in another class
+        # than the one of creation), ("temporal" | "variance", Lite.across)
+        self.events = []
+        self.prev = None  # the kind of the step before
+        self.pending = None  # (look before, look after) of the last edit, until a frame shows it or another edit follows
+        self.hist_classes = None  # the classes of the frames the live history holds; None: no history
+        self.moments_live = False  # the history's moments are live: the last of its steps was a variance step
+        self.table_shape = self.table_edit = False  # a shape step / an edit was made since the group table was installed
+        self.ids_step = False  # an ids step was made in this sequence
+
+
 class Lite:
-    def __init__(self, pose="home", shape="home", samples=2):
+    def __init__(self, pose="home", shape="home", samples=2, name=None):
         self.pose, self.shape, self.mask, self.pipeline = pose, shape, 0, R.PIPELINE_WAVEFRONT
+        # the edit seeds (name: the scene whose look tables the steps index): the look in effect and the one the last frame was
+        # rendered under, the group table (the seed of group_table, or None), and what the caps of the draw ask (self.log)
+        self.name = name
+        self.look = self.look0 = default_look(name) if name else None
+        self.frame_look, self.groups, self.log = None, None, CapLog()
         self.frame = self.mark = None  # (pose, shape, mask, total, first) / (pose, shape)
         self.updated = False
         # sample windows: the window the next frame renders, the one the last frame rendered (None before the first), and what
@@ -309,16 +493,62 @@ class Lite:
             return arg[0] and self.mask & SURFACE != SURFACE
         if kind == "clone":
             return bool(arg)  # the subset's temporal() is refused
-        return kind in ("refused_update", "refused_camera")
+        if kind == "mattes":
+            return arg[0] == "group" and self.groups is None
+        return kind in ("refused_update", "refused_camera", "refused_edit")
 
     def renders(self, uses_passes):
         return self.frame is None or (uses_passes and self.frame[2] != self.mask)
 
+    def cls(self, look=None):
+        return look_class(self.name, look or self.look)
+
+    def max_id(self):
+        """The largest material id in effect."""
+        return int(look_ids(self.name, self.look[2]).max())
+
+    def after(self, step):
+        """The look a successful edit step leaves."""
+        kind, arg = step
+        L, M, ids = self.look
+        if kind == "lights":
+            return (arg, M, ids)
+        if kind == "materials":
+            return (L, arg[0], arg[1] or ids)
+        return (L, M, arg[0])
+
     def advance(self, step):
-        """The step's effect on (pose, shape, mask, pipeline, frame, mark, updated); a refused step has none."""
+        """The step's effect on (pose, shape, mask, pipeline, frame, mark, updated) and, for the edit seeds, on the look and the group
+        table; a refused step has none."""
+        self._advance(step)
+        self.log.prev = step[0]
+
+    def _advance(self, step):
         kind, arg = step
         if self.refuses(step) and kind != "clone":
+            if kind == "mattes":
+                self.log.events.append(("mattes", dict(kind=arg[0], refused=True)))
             return
+        if kind in ("lights", "materials", "ids"):
+            new = self.after(step)
+            self.log.events.append(("edit", kind, self.cls(), self.cls(new), self.look, new))
+            self.log.pending = (self.look, new)  # until the next frame or the next edit
+            self.look, self.log.table_edit, self.log.ids_step = new, self.groups is not None, self.log.ids_step or kind == "ids"
+        elif kind == "matte_groups":
+            self.groups, self.log.table_shape, self.log.table_edit = arg, False, False
+        elif kind == "mattes":
+            S, last = self.samples, self.window_last
+            table = None if arg[0] == "triangle" else self.look[2] if arg[0] == "material" else self.groups
+            self.log.events.append(("mattes", dict(kind=arg[0], refused=False, defaults=arg[3] is None, before_frames=self.frame is None,
+                                               state=(self.pose, self.shape), table=table,
+                                               other_window=last is not None and last[:2] != (S, 0),
+                                               group_after_shape=arg[0] == "group" and self.log.table_shape,
+                                               group_after_edit=arg[0] == "group" and self.log.table_edit,
+                                               material_after_ids=arg[0] == "material" and self.log.ids_step)))
+        elif kind == "clone" and self.name:
+            self.log.events.append(("clone", self.cls() != self.cls(self.look0)))
+        if kind == "shape":
+            self.log.table_shape = self.groups is not None
         if kind == "camera":
             self.pose, self.moved, self.run = arg, True, None
         elif kind == "shape":
@@ -337,6 +567,23 @@ class Lite:
             self.render_frame()
         if kind in ("temporal", "variance"):
             self.mark = (self.pose, self.shape)
+        if kind == "reset_temporal":
+            self.log.hist_classes, self.log.moments_live = None, False
+        if kind in ("temporal", "variance") and self.name:
+            self.log.events.append((kind, self.across(kind, arg[1])))
+            self.log.hist_classes = (self.log.hist_classes if self.blends(kind, arg[1]) else set()) | {self.cls(self.frame_look)}
+            self.log.moments_live = kind == "variance"
+
+    def blends(self, kind, cap):
+        """Whether a temporal or variance step made now can blend the history into its frame: there is one, a variance step finds its
+        moments live (over stale ones it starts the history again), and max_history is above 1 -- at 1 every pixel's count is capped to
+        1 and the output is the frame itself, as over an empty history, so what the step leaves holds that frame alone."""
+        return self.log.hist_classes is not None and (kind == "temporal" or self.log.moments_live) and cap > 1
+
+    def across(self, kind, cap):
+        """Whether such a step, its frame rendered, runs with a live history across a class change: it can blend (blends) a history that
+        holds a frame of another class than the frame's.  Whether a tap is accepted only the oracle knows (histories_cross)."""
+        return bool(self.blends(kind, cap) and self.log.hist_classes - {self.cls(self.frame_look)})
 
     def render_frame(self):
         """A frame is issued: it renders window_next, which becomes window_last and moves on if it advances.  Notes in self.frames what
@@ -353,6 +600,10 @@ class Lite:
         complete = N if self.run == N and kind == "progressive" and f == N - S else 0
         self.frames.append(dict(state=(self.pose, self.shape), window=win, kind=kind, continuing=bool(acc and f > 0), moved=self.moved,
                                 complete=complete))
+        if self.name:  # the class the frame runs in and the step it follows; whether it continues another look's buffer; the edit it shows
+            self.frames[-1].update(cls=self.cls(), follows=self.log.prev, look=self.look,
+                                   other_look=bool(acc and f > 0 and self.frame_look not in (None, self.look)), edit=self.log.pending)
+            self.frame_look, self.log.pending = self.look, None
         self.frame, self.window_last, self.moved = (self.pose, self.shape, self.mask, N, f), win, False
         if adv:
             self.window_next = (N, (f + S) % N, D, acc, adv)
@@ -397,7 +648,8 @@ def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
         return bool(tiles > 1 and dare)
     if kind == "variance":
         on = rng.random() < 0.5 if s.mask & SURFACE == SURFACE else dare
-        return (bool(on), int(pick(MAX_HISTORY)))
+        # (the edit seeds: over live moments of another class than the look's, a cap that lets the history show)
+        return (bool(on), int(pick(MAX_HISTORY[1:] if s.name and s.log.moments_live and s.log.hist_classes - {s.cls()} else MAX_HISTORY)))
     if kind == "window":
         S = s.samples
         if dare:  # one of the refusals that apply to a scene of S samples: returns -1 with its text and changes nothing
@@ -414,6 +666,54 @@ def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
         if r < 0.85:
             return (N, 0, S, 1, 1)  # over-bright progressive: every frame at full brightness on top of the frames before
         return (N, int(rng.integers(1, N - S + 1)), int(pick((1, 3, S, N))), 0, 0)  # fixed, off the grid of S where N allows
+    if s.name:
+        return draw_edit(rng, pick, kind, s, dare)
+    return None
+
+
+def draw_edit(rng, pick, kind, s, dare):
+    """The argument of a step of one of the kinds the edit seeds add, and of a bake there (a `material` filter in half of the steps).
+    An edit always changes the look; about half of the lights and materials steps cross the class boundary where a set does."""
+    counts = look_parts(s.name)["counts"]
+    L, M, ids = s.look
+    if kind == "bake":
+        return int(rng.integers(counts[M])) if rng.random() < 0.5 else None
+    if kind in ("lights", "materials"):
+        at, sets = (0, LIGHT_SETS) if kind == "lights" else (1, MATERIAL_SETS)
+        others = [v for v in sets if v != s.look[at]]
+        cross = [v for v in others if s.cls(s.look[:at] + (v,) + s.look[at + 1:]) != s.cls()]
+        # (a crossing is likelier out of the opaque-diffuse class, which most sets lead back to, and certain under a live history,
+        # so that temporal and variance steps find frames of both classes in it)
+        new = pick(cross) if cross and (s.log.hist_classes is not None or rng.random() < (0.7 if s.cls() else 0.4)) else pick(others)
+        if kind == "lights":
+            return new
+        # ids come exactly where a resident id would be out of range for the new tables, and in four draws of ten otherwise
+        brings = s.max_id() >= counts[new] or rng.random() < 0.4
+        return (new, (int(pick(ID_VARIANTS)), counts[new]) if brings else None)
+    if kind == "ids":
+        return (pick([(i, counts[M]) for i in ID_VARIANTS if (i, counts[M]) != ids]), "numpy" if rng.random() < 0.5 else "torch")
+    if kind == "refused_edit":
+        while True:  # a variant that is legal in the current look is drawn again: tables of max_id materials need a material
+            variant = pick(EDIT_REFUSALS)
+            if variant != "shrink" or s.max_id() >= 1:
+                return variant
+    if kind == "matte_groups":
+        if s.groups is not None and rng.random() < 0.25:
+            return None
+        return int(pick([g for g in GROUP_SEEDS if g != s.groups]))
+    if kind == "mattes":
+        if s.groups is None:
+            what = "group" if dare else pick(MATTE_KINDS[:2])
+        else:
+            what = pick(MATTE_KINDS + ("group",))
+        S, last = s.samples, s.window_last
+        moved = last is not None and last[:2] != (S, 0)
+        window = None
+        if rng.random() >= (0.85 if moved else 0.25):  # explicit {N, f, C}, C unequal to S in three draws of four
+            C_ = int(pick((1, S, 4, 8)))  # (with four and eight samples a pixel holds more ids than two layers take)
+            N = C_ + int(rng.integers(0, 6))
+            window = (N, int(rng.integers(0, N - C_ + 1)), C_)
+        return (what, int(pick(MATTE_SELECT)), int(pick(MATTE_LAYERS)), window)
     return None
 
 
@@ -436,15 +736,15 @@ def eulerian(rng, K=K):
     return path[::-1]
 
 
-def _piece(rng, kinds, start, tiles, shapes, seen, samples=2):
+def _piece(rng, kinds, start, tiles, shapes, seen, samples=2, name=None):
     """Steps for `kinds` from a fresh scene at `start`, and what the caps ask about them: (steps, refusals after each step, temporal
     steps on an older frame, motion steps with camera and shape both changed, temporal steps, the warm ones among them, each as the
     index of the step; and of the variance steps [(index, warm, stale moments over a live history)])."""
-    s, steps, refused, stale, mixed = Lite(*start, samples=samples), [], [], [], []
+    s, steps, refused, stale, mixed = Lite(*start, samples=samples, name=name), [], [], [], []
     seen, hist, temporal, warm = set(seen), False, [], []
     moments, variance = False, []
     for i, k in enumerate(kinds):
-        kind = KINDS_WIDE[k]
+        kind = KINDS_EDIT[k]
         step = (kind, draw(rng, kind, s, (sum(refused[-1:]) + 1) <= MAX_REFUSED * (i + 1), tiles, shapes, seen))
         refused.append((refused[-1] if refused else 0) + bool(s.refuses(step)))
         if kind == "temporal" and not s.refuses(step) and not s.renders(step[1][0]) and s.frame[:2] != (s.pose, s.shape):
@@ -472,11 +772,13 @@ def _attempt(name, seed, attempt):
     longest run of at most the scene's cut whose refusals are at most MAX_REFUSED of its steps, drawn with a generator of its own, and
     the next piece starts with its last kind."""
     spec = SCENES[name]
-    key = [sorted(SCENES).index(name), seed, attempt]
+    key = [SCENE_KEY[name], seed, attempt]
     tiles = R.tile_count(*spec["size"])
-    walk = seed in spec["walks"] + spec["wide_walks"]
-    wide = seed in spec["wide_circuits"] + spec["wide_walks"]
-    k = len(kinds_of(name, seed))
+    alphabet = kinds_of(name, seed)
+    edit, wide = alphabet is KINDS_EDIT, alphabet is KINDS_WIDE
+    walk = seed in spec["walks"] + spec["wide_walks"] + spec.get("edit_walks", ())
+    lite = dict(samples=spec["samples"], name=name if edit else None)
+    k = len(alphabet)
     kinds = [int(v) for v in np.random.default_rng(key).integers(k, size=WALK)] if walk else eulerian(np.random.default_rng(key), k)
     limit = spec.get("walk_cut", WALK) if walk else spec["cut"]
     whole = walk and limit == WALK  # (a walk is one sequence, unless the scene cuts its walks as it cuts a circuit)
@@ -491,13 +793,13 @@ def _attempt(name, seed, attempt):
             return None
         piece = kinds[at:at + limit]
         steps, refused, st, mx, tp, wm, vr = _piece(np.random.default_rng(key + [at]), piece, start, tiles, spec["shapes"], seen,
-                                                    spec["samples"])
+                                                    **lite)
         for n in range(len(piece), 1, -1):
             if refused[n - 1] > MAX_REFUSED * n or (whole and n < len(piece)):
                 continue
             if sum(k == "shape" for k, _ in steps[:n]) > spec.get("shape_steps", n):
                 continue  # (an update's check of the device arrays takes over a second on the larger scene's 12.6 million pairs)
-            s, now = Lite(*start, samples=spec["samples"]), set(seen)
+            s, now = Lite(*start, **lite), set(seen)
             for step in steps[:n]:
                 s.advance(step)
                 now |= {s.pose, s.shape}
@@ -505,7 +807,7 @@ def _attempt(name, seed, attempt):
             if tail is not None:
                 return [dict(start=start, steps=steps[:n], stale=sum(i < n for i in st), mixed=sum(i < n for i in mx), seen=now,
                              temporal=sum(i < n for i in tp), warm=sum(i < n for i in wm), variance=[v for v in vr if v[0] < n],
-                             frames=s.frames)] + tail
+                             frames=s.frames, events=s.log.events)] + tail
         return None
 
     out = rest(0, ("home", "home"), {"home"})
@@ -513,10 +815,14 @@ def _attempt(name, seed, attempt):
         return None
     stale, mixed, seen = sum(q.pop("stale") for q in out), sum(q.pop("mixed") for q in out), set().union(*(q.pop("seen") for q in out))
     variance, frames = [v for q in out for v in q.pop("variance")], [q.pop("frames") for q in out]
+    events = [q.pop("events") for q in out]
     if sum(q.pop("warm") for q in out) < MIN_WARM * sum(q.pop("temporal") for q in out):
         return None  # (too few temporal steps with a history to reproject: the accepting share could not reach a third)
     if wide and not wide_caps(frames, variance, walk):
         return None
+    if edit and not (walk or (edit_caps(edit_facts(frames, events)) and shows_its_edits(name, frames, events)
+                              and histories_cross(across_notes(name, out)))):
+        return None  # (the caps of the edit seeds are the circuit's to meet: the walk adds to them)
     if not walk and not (stale and mixed and seen >= set(POSES) | set(spec["shapes"])):
         return None  # (the camera draw favours the near poses: a circuit still visits every pose and every shape)
     return out
@@ -546,10 +852,125 @@ def wide_caps(frames, variance, walk):
     return walk or (any(f["kind"] == "overbright" for f in cont) and bool(pairs))
 
 
+def edit_facts(frames, events):
+    """What the caps of the edit seeds ask, counted from Lite.frames and Lite.log.events (one list per sequence each)."""
+    frames = [f for part in frames for f in part]
+    events = [e for part in events for e in part]
+    edits = [e for e in events if e[0] == "edit"]
+    mattes = [e[1] for e in events if e[0] == "mattes" and not e[1]["refused"]]
+    defaults = [m for m in mattes if m["defaults"]]
+    general = {R.PATH_CLASS_GENERAL: "to_general", R.PATH_CLASS_OPAQUE_DIFFUSE: "to_opaque_diffuse"}
+    out = dict(edits=len(edits), same_look=sum(e[4] == e[5] for e in edits), clones_in_another_class=sum(e[1] for e in events if e[0] == "clone"),
+               frames_on_another_look=sum(f["other_look"] for f in frames), temporal_across=sum(e[1] for e in events if e[0] == "temporal"),
+               variance_across=sum(e[1] for e in events if e[0] == "variance"), mattes=len(mattes), mattes_defaults=len(defaults),
+               mattes_defaults_other_window=sum(m["other_window"] for m in defaults),
+               mattes_refused=sum(e[1]["refused"] for e in events if e[0] == "mattes"))
+    for kind in ("lights", "materials"):
+        for cls, word in general.items():
+            out[f"{kind}_{word}"] = sum(e[1] == kind and e[2] != e[3] == cls for e in edits)
+    for cls, word in ((R.PATH_CLASS_GENERAL, "general"), (R.PATH_CLASS_OPAQUE_DIFFUSE, "opaque_diffuse")):
+        for prev in ("camera", "shape"):
+            out[f"frames_{word}_after_{prev}"] = sum(f["cls"] == cls and f["follows"] == prev for f in frames)
+    for k in MATTE_KINDS:
+        out[f"mattes_{k}"] = sum(m["kind"] == k for m in mattes)
+    for k in ("before_frames", "group_after_shape", "group_after_edit", "material_after_ids"):
+        out[f"mattes_{k}"] = sum(m[k] for m in mattes)
+    return out
+
+
+def edit_caps(facts):
+    """What the edit seeds' draw must hold (tests/test_session.py asserts it on the oracle, over the edit seeds together): every edit
+    changes the look; each of the four class crossings -- by lights or by materials, to the general class or back -- at least twice; in
+    each class a frame directly after a camera step and directly after a shape step; a clone made while the class is not the class of
+    creation; a frame that continues from a buffer another look's frame filled; a temporal and a variance step with a live history
+    across a class change (Lite.across: max_history above 1; histories_cross asks the oracle whether it shows); a matte of every
+    kind, a group matte after a shape step and one after an edit made since the table was installed, a material matte after an ids step, a matte before any frame of its sequence, a group matte refused for want of a
+    table, and a third of the mattes with defaults under another window_last than the default window's."""
+    need = [k for k in facts if k.startswith("frames_") or k.startswith("mattes_") and k not in ("mattes_defaults", "mattes_defaults_other_window",
+                                                                                                "mattes_refused")]
+    need += ["clones_in_another_class", "temporal_across", "variance_across", "mattes_refused"]
+    crossings = [k for k in facts if k.startswith("lights_") or k.startswith("materials_")]
+    return (facts["same_look"] == 0 and all(facts[k] >= 1 for k in need) and all(facts[k] >= 2 for k in crossings)
+            and 3 * facts["mattes_defaults_other_window"] >= facts["mattes_defaults"] > 0)
+
+
+MIN_EDIT_CHANGED = 0.05  # of the pixels: the oracle's planes of the looks before and after an edit that a frame shows
+_canon = {}
+
+
+def matte_canon(name, state, kind, table):
+    """The layers (K = 8, the default window) of the state's matte of `kind` under `table` (material: the id part of a look; group:
+    the seed of group_table): what two consecutive matte steps are told apart by."""
+    if (name, state, kind, table) not in _canon:
+        w = world(name)
+        S = w.base.sample_count
+        tab = None if kind == "triangle" else MA.material_table(look_ids(name, table)) if kind == "material" else \
+            group_table(w.base.triangle_count, table)
+        m = MA.mattes(w.sample_ids(*state, S, 0, S), tab, [], 8, S)
+        _canon[name, state, kind, table] = (m["layer_id"], m["layer_coverage"])
+    return _canon[name, state, kind, table]
+
+
+def edit_shares(name, frames):
+    """For every frame that is the first after an edit: the share of the pixels in which the oracle's planes of the looks before and
+    after the edit differ at the frame's state."""
+    return [GC.changed_share(world(name, f["edit"][0]).planes(*f["state"]), world(name, f["edit"][1]).planes(*f["state"]))
+            for part in frames for f in part if f.get("edit")]
+
+
+def matte_pairs(name, events):
+    """(consecutive matte steps of one sequence taken under different states or tables, those of them whose answers differ)."""
+    pairs = same = 0
+    for part in events:
+        keys = [(e[1]["state"], e[1]["kind"], e[1]["table"]) for e in part if e[0] == "mattes" and not e[1]["refused"]]
+        for a, b in zip(keys, keys[1:]):
+            if a != b:
+                pairs += 1
+                same += all(np.array_equal(x, y) for x, y in zip(matte_canon(name, *a), matte_canon(name, *b)))
+    return pairs, pairs - same
+
+
+def shows_its_edits(name, frames, events):
+    """Not vacuous, on the oracle: every edit that a frame shows changes MIN_EDIT_CHANGED of the pixels, and consecutive matte steps
+    under different states or tables differ."""
+    pairs, differing = matte_pairs(name, events)
+    return all(v >= MIN_EDIT_CHANGED for v in edit_shares(name, frames)) and pairs == differing > 0
+
+
+def across_notes(name, parts):
+    """The model alone over the sequences `parts` of an edit seed: (kind, figures) of every temporal and variance step that runs with a
+    live history across a class change (Session.note_across)."""
+    out = []
+    for q in parts:
+        s = Session(world(name), q["start"], edit=True)
+        for step in q["steps"]:
+            s.apply(step)
+        out += [n[1:] for n in s.notes if n[0] == "across"]
+    return out
+
+
+def histories_cross(notes):
+    """Not vacuous, on the oracle: of the steps of across_notes one temporal and one variance step blend the history in in some pixels
+    (used; count > 1) and give another answer than over an empty history, so a history wiped by an edit or a crossing shows."""
+    return all(any(k == kind and f["blended"] > 0 and f["differs"] > 0 for k, f in notes) for kind in ("temporal", "variance"))
+
+
+def lite_of(name, seed, start):
+    """The light state a sequence of the seed starts from."""
+    return Lite(*start, samples=SCENES[name]["samples"], name=name if is_edit(name, seed) else None)
+
+
 def kinds_of(name, seed):
-    """The alphabet of a seed."""
-    spec = SCENES[name]
-    return KINDS_WIDE if seed in spec["wide_circuits"] + spec["wide_walks"] else KINDS
+    """The alphabet of a seed: the one of the list its scene names it in; a regression plays the newest alphabet its scene has seeds
+    of, so on a scene with edit seeds its steps index the look tables."""
+    if seed in REGRESSIONS:
+        return KINDS_EDIT if edit_seeds(name) else KINDS
+    return KINDS_EDIT if seed in edit_seeds(name) else KINDS_WIDE if seed in seeds_of(name, wide=True) else KINDS
+
+
+def is_edit(name, seed):
+    """Whether the seed's steps index the scene's look tables."""
+    return kinds_of(name, seed) is KINDS_EDIT
 
 
 _sequences = {}
@@ -569,10 +990,15 @@ def sequences(name, seed):
 
 
 def seeds_of(name, wide=None):
-    """The scene's seeds: all of them, the wide ones (wide=True) or the others (wide=False)."""
+    """The scene's seeds: all of them, the wide ones (wide=True) or the oldest (wide=False); the edit seeds are edit_seeds'."""
     spec = SCENES[name]
     old, new = spec["circuits"] + spec["walks"], spec["wide_circuits"] + spec["wide_walks"]
-    return old + new if wide is None else new if wide else old
+    return old + new + edit_seeds(name) if wide is None else new if wide else old
+
+
+def edit_seeds(name):
+    """The scene's seeds that draw from KINDS_EDIT."""
+    return SCENES[name].get("edit_circuits", ()) + SCENES[name].get("edit_walks", ())
 
 
 def all_parts():
@@ -587,7 +1013,7 @@ def visited(name):
     for n, seed, part in all_parts():
         if n == name:
             q = part_of(n, seed, part)
-            s = Lite(*q["start"], samples=SCENES[n]["samples"])
+            s = lite_of(n, seed, q["start"])
             out.append((s.pose, s.shape))
             for step in q["steps"]:
                 s.advance(step)
@@ -598,9 +1024,9 @@ def visited(name):
 def warm_wide(name):
     """The model alone over the scene's wide sequences: every window frame, flow and accumulation their checks read is made now (the
     caches are the World's), as World.warm does for the planes of the visited states."""
-    for seed in seeds_of(name, wide=True):
+    for seed in seeds_of(name, wide=True) + edit_seeds(name):
         for q in sequences(name, seed):
-            s = Session(world(name), q["start"])
+            s = Session(world(name), q["start"], edit=is_edit(name, seed))
             for step in q["steps"]:
                 s.apply(step)
 
@@ -617,16 +1043,27 @@ class Session(Lite):
     """The model of one resident scene.  With rs (a ResidentScene created from world.state(*start)) every step is also made on the device
     and checked; without, the model advances alone and notes what tests/test_session.py asserts on (self.notes)."""
 
-    def __init__(self, w, start=("home", "home"), rs=None):
-        super().__init__(*start, samples=w.base.sample_count)
-        self.w, self.rs = w, rs
+    def __init__(self, w, start=("home", "home"), rs=None, edit=False):
+        super().__init__(*start, samples=w.base.sample_count, name=w.name if edit else None)
+        self.w, self.rs = w, rs  # (w: the World of the scene's own look, which holds what depends on geometry and camera alone)
         self.described_pose = start[0]
         self.planes = self.history = None
         self.moments = None  # the live moments [H, W, 2] of the history; None: stale (a temporal step wrote none) or absent
+        self.staged = False  # a call has brought host ids: the scene holds their staging (4 bytes per triangle) from then on
         self.notes = []
 
     def here(self):
         return (self.pose, self.shape)
+
+    @property
+    def lw(self):
+        """The World of the look in effect: what traces anew follows it."""
+        return world(self.w.name, self.look) if self.name else self.w
+
+    @property
+    def fw(self):
+        """The World of the look the last frame was rendered under: what reads the frame's buffers is that look's, stale or not."""
+        return world(self.w.name, self.frame_look) if self.name else self.w
 
     def apply(self, step):
         kind, arg = step
@@ -641,7 +1078,7 @@ class Session(Lite):
         N, f, D, acc, adv = self.window_next
         onto = self.planes if acc and f > 0 else None
         assert onto is not None or not (acc and f > 0), "a frame continues before the sequence's first frame: the header leaves the buffer open"
-        want = self.w.window_planes(self.pose, self.shape, N, f, D, onto)
+        want = self.lw.window_planes(self.pose, self.shape, N, f, D, onto)  # (onto the model's planes, whatever look they came from)
         if self.rs:
             self.rs.render()
             sc = self.w.base
@@ -689,7 +1126,7 @@ class Session(Lite):
         if self.rs:
             update_to(self.rs, want)
             CC.assert_lists_equal(self.rs, want, f"lists after the update to {name}")
-            assert_device_arrays(self.rs, want, f"device arrays after the update to {name}", self.w.prep(name))
+            assert_device_arrays(self.rs, want, f"device arrays after the update to {name}", self.lw.prep(name))
             self.same_bound(self.rs, name, f"the clip bound after the update to {name}")
         self.described_pose = self.pose
 
@@ -724,7 +1161,7 @@ class Session(Lite):
     def do_read_passes(self):
         self.need_frame(True)
         if self.rs:
-            got, want = self.rs.readback_passes(), twin(self.w, *self.frame)["passes"]
+            got, want = self.rs.readback_passes(), twin(self.fw, *self.frame)["passes"]
             assert sorted(got) == sorted(want), f"passes {sorted(got)}, the twin's {sorted(want)}"
             for k in want:
                 differs(got[k], want[k], f"pass {k} of the frame at {self.frame}")
@@ -737,7 +1174,7 @@ class Session(Lite):
             return
         self.need_frame(True)
         if self.rs:
-            got, made = self.rs.denoise(**params), twin(self.w, *self.frame)
+            got, made = self.rs.denoise(**params), twin(self.fw, *self.frame)
             if self.window_last[2:4] == (self.samples, 0):  # the twin's frame is this frame: its divisor is S and neither continued
                 want = made["denoise"][variant]
                 differs(got["colour"], want["colour"], "denoised colour (against the twin)")
@@ -767,8 +1204,23 @@ class Session(Lite):
                     _oracle_ao[key] = ao_oracle.ambient_occlusion(self.w.state(*self.here()), rays=4)
                 differs(got, _oracle_ao[key], "AO image (against the oracle)")
 
-    def do_bake(self):
-        if self.rs:
+    def do_bake(self, material=None):
+        """The bake, in some steps of the edit seeds with a `material` filter, which reads the id word: the twin of the filter is
+        keyed by the shape, the ids and the filter."""
+        if self.rs and material is not None:
+            key = (self.w.name, self.shape, self.look[2], material)
+            if key not in _twin_bake:
+                t = R.ResidentScene(self.lw.state("home", self.shape), 0)
+                try:
+                    _twin_bake[key] = t.bake_ambient_occlusion(16, 16, rays=4, dilate=2, material=material)
+                finally:
+                    t.close()
+            got = self.rs.bake_ambient_occlusion(16, 16, rays=4, dilate=2, material=material)
+            for k in ("ao", "triangle"):
+                differs(got[k], _twin_bake[key][k], f"bake {k} of material {material} (against the twin)")
+            covered = got["triangle"][got["triangle"] != NONE]
+            assert (look_ids(self.name, self.look[2])[covered] == material).all(), f"the bake of material {material} covers another material's triangle"
+        elif self.rs:
             got, want = self.rs.bake_ambient_occlusion(16, 16, rays=4, dilate=2), twin_bake(self.w, self.shape)
             for k in ("ao", "triangle"):
                 differs(got[k], want[k], f"bake {k} (against the twin)")
@@ -825,10 +1277,14 @@ class Session(Lite):
         hist = self.history if self.history is not None else TO.empty_history(self.w.height, self.w.width)
         acc = TO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap), with_taps=True)
         self.notes.append(("temporal", self.frame[:2] != self.here(), float(acc["used"].mean())))
+        if self.name and self.across("temporal", cap):
+            fresh = TO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], TO.empty_history(self.w.height, self.w.width),
+                                  max_history=float(cap))
+            self.note_across("temporal", cap, acc["used"], acc, fresh, ("colour", "count"))
         if self.rs:
             shown = acc["colour"]
             if on:
-                surf = twin(self.w, *self.frame)["passes"]
+                surf = twin(self.fw, *self.frame)["passes"]
                 shown = D.denoise(acc["colour"], surf["normal"], surf["albedo"], **dict(R.DENOISE_DEFAULTS, **TEMPORAL_DENOISE))
             got = self.rs.temporal(denoise=TEMPORAL_DENOISE if on else None, max_history=float(cap))
             differs(got["count"], acc["count"], "temporal count")
@@ -859,10 +1315,15 @@ class Session(Lite):
             assert (acc["count"] == 1.0).all() and (acc["variance"] == 0.0).all() and TO.same_bits(acc["colour"], colour).all()
         warm = self.history is not None and self.mark is not None and self.mark[1] == self.shape  # (as _piece counts it)
         self.notes.append(("variance", dict(stale=stale, warm=warm, live=live), float((acc["count"] > 1.0).mean())))
+        if self.name and self.across("variance", cap):
+            assert live
+            fresh = VO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], VO.empty_history(self.w.height, self.w.width),
+                                  max_history=float(cap))
+            self.note_across("variance", cap, acc["count"] > 1.0, acc, fresh, ("colour", "count", "moments", "variance"))
         if self.rs:
             shown = dict(colour=acc["colour"], variance=acc["variance"])
             if on:
-                surf = twin(self.w, *self.frame)["passes"]
+                surf = twin(self.fw, *self.frame)["passes"]
                 shown["colour"], shown["variance"] = VO.denoise(acc["colour"], surf["normal"], surf["albedo"], acc["moments"], acc["count"],
                                                                 **VARIANCE_FILTER)
             got = self.rs.temporal_variance(filter=VARIANCE_FILTER if on else None, max_history=float(cap))
@@ -874,6 +1335,15 @@ class Session(Lite):
             self.same_mark("temporal_variance (the call owns the mark)")
         self.history = TO.next_history(dict(colour=acc["colour"], count=acc["count"]), flow["t"], flow["triangle"])
         self.moments = acc["moments"]
+
+    def note_across(self, kind, cap, blended, acc, fresh, outputs):
+        """A step with a live history across a class change (Lite.across): the share of the pixels that blend the history in, and the
+        share in which an expected output differs from the one over an empty history -- what the step would give had an edit or a class
+        crossing wiped the history."""
+        same = np.ones(blended.shape, bool)
+        for k in outputs:
+            same &= TO.same_bits(acc[k], fresh[k]).reshape(blended.shape + (-1,)).all(-1)
+        self.notes.append(("across", kind, dict(cap=cap, blended=float(np.mean(blended)), differs=float(1.0 - same.mean()))))
 
     def do_reset_temporal(self):
         if self.rs:
@@ -930,9 +1400,11 @@ class Session(Lite):
         tiles = np.arange(R.tile_count(sc.width, sc.height), dtype=np.uint32)[1:] if subset else None
         # (the scene's own description rebuilds its lists with the host builders when read, which takes seconds on the larger scene's
         # rooms: there the clone is described by the model's Scene of the same pose and shape)
-        desc = self.rs.scene if self.w.name == SMALL else self.w.state(self.described_pose, self.shape)
+        desc = self.rs.scene if self.w.name == SMALL or self.name else self.w.state(self.described_pose, self.shape)
         c = R.ResidentScene(desc, 0, tiles, like=self.rs)
         try:
+            if self.name:  # the clone of an edited scene runs the class of a scene created with the look
+                assert c.path_class() == R.path_class(self.lw.base), f"the clone's path class is {c.path_class()}, the look's {R.path_class(self.lw.base)}"
             S = self.samples  # a clone starts with the default window, whatever its model has, and renders the default window's frame
             assert c.sample_window()["next"] == dict(total=S, first=0, divisor=S, accumulate=0, advance=0), c.sample_window()
             self.same_bound(c, self.shape, "the clone's clip bound")
@@ -942,10 +1414,142 @@ class Session(Lite):
             if subset:
                 mine[:R.TILE, :R.TILE] = False  # tile 0 is not the clone's
                 refusal(c.temporal, "every tile of the image", "temporal on a tile subset")
-            for ch, g, x in zip("RGB", got, self.w.planes(self.described_pose, self.shape)):
+            for ch, g, x in zip("RGB", got, self.lw.planes(self.described_pose, self.shape)):
                 differs(g, np.where(mine, x, 0).astype(np.uint16), f"plane {ch} of the clone's frame")
         finally:
             c.close()
+
+
+    # -- scene edits: the look changes in place; buffers, window, history, mark and group table stay, which the later steps prove
+    def rows(self):
+        return np.asarray(self.rs.scene_view("tri_shade")).reshape(-1, 24).view(np.int32).copy()
+
+    def same_class(self, look, what):
+        want = R.path_class(world(self.w.name, look).base)
+        assert want == look_class(self.name, look)
+        assert self.rs.path_class() == want, f"{what}: the scene's path class is {self.rs.path_class()}, the model's {want}"
+
+    def do_lights(self, name):
+        if self.rs:
+            new = self.after(("lights", name))
+            arrays = look_parts(self.name)["lights"][name]
+            self.rs.set_lights(arrays)
+            self.same_class(new, f"after set_lights({name})")
+            for k in R.LIGHT_FIELDS:
+                assert np.asarray(getattr(self.rs.scene, k)).tobytes() == np.ascontiguousarray(arrays[k]).tobytes(), \
+                    f"after set_lights({name}): the scene's description differs in {k}"
+
+    def do_materials(self, arg):
+        if self.rs:
+            name, ids = arg
+            new = self.after(("materials", arg))
+            self.rs.set_materials(look_parts(self.name)["materials"][name], None if ids is None else look_ids(self.name, ids))
+            self.staged |= ids is not None
+            self.same_class(new, f"after set_materials({name}, {ids})")
+            count = look_parts(self.name)["counts"][name]
+            assert self.rs.scene.material_count == count, f"after set_materials({name}): {self.rs.scene.material_count} materials, the model has {count}"
+            differs(self.rows()[:, 21], look_ids(self.name, new[2]), f"word 21 of the shading rows after set_materials({name}, {ids})")
+
+    def do_ids(self, arg):
+        if self.rs:
+            ids, form = arg
+            want = look_ids(self.name, ids)
+            before = self.rows()
+            if form == "torch":
+                import torch
+                self.rs.set_materials(tri_material=torch.from_numpy(want).to(torch.device("cuda", 0)))
+            else:
+                self.rs.set_materials(tri_material=want)
+                self.staged = True
+            self.same_class(self.after(("ids", arg)), f"after the ids {ids}")
+            now = self.rows()
+            differs(now[:, 21], want, f"word 21 of the shading rows after the ids {ids} ({form})")
+            differs(np.delete(now, 21, axis=1), np.delete(before, 21, axis=1), f"the other 23 words of the shading rows after the ids {ids}")
+            row = np.asarray(self.rs.scene_view("tri_shade_row")).reshape(-1, 32).view(np.uint32)
+            rec = np.asarray(self.rs.scene_view("tri_rec")).reshape(-1, 16).view(np.uint32)
+            differs(row[:, 24:28], rec[:, 0:4], f"words 24..27 of the shading rows (vertex a) after the ids {ids}")
+
+    def do_refused_edit(self, variant):
+        """One illegal argument: the code and the text, and addresses and byte count as they were -- but for the staging of host
+        ids, which the header gives to the first call that brings some, refused or not: ids are checked on the device."""
+        if not self.rs:
+            return
+        rs, lib, parts = self.rs, R.lib(), look_parts(self.name)
+        pointers, held = rs.pointers(), rs.bytes()
+        ids = look_ids(self.name, self.look[2])
+        mats = {k: np.ascontiguousarray(v) for k, v in parts["materials"][self.look[1]].items()}
+        count, T = parts["counts"][self.look[1]], ids.shape[0]
+        L = {k: np.ascontiguousarray(v) for k, v in parts["lights"]["sun_spot"].items()}
+        p = {k: R._ptr(v) for k, v in L.items()}
+        size, start, tex = mats["mat_size"].reshape(-1, 2), mats["mat_start"].reshape(-1), mats["textures"].reshape(-1, 4)
+        code, grown = -1, 0
+        if variant == "shrink":  # tables of max_id materials, without ids: the resident max_id is out of range
+            m = self.max_id()
+            assert 1 <= m < count
+            rc, code, text = rs.try_set_materials(dict(mat_size=size[:5 * m].copy(), mat_start=start[:5 * m + 1].copy(), textures=tex)), -5, REJECTED
+        elif variant in ("bad_first", "bad_last"):
+            bad = ids.copy()
+            bad[0 if variant == "bad_first" else T - 1] = count
+            rc, code, text = rs.try_set_materials(tri_material=bad), -5, REJECTED
+            grown, self.staged = (0 if self.staged else 4 * T), True
+        elif variant == "host_pointer":
+            rc = lib.rtHipSceneSetMaterials(rs.handle, ctypes.byref(R.MaterialUpdate(0, 0, None, None, 0, None, R._ptr(ids), 1)))
+            text = "not device memory"
+        elif variant == "neither":
+            rc, text = lib.rtHipSceneSetMaterials(rs.handle, ctypes.byref(R.MaterialUpdate())), "neither"
+        elif variant == "past_atlas":
+            past = start.copy()
+            ch = int(np.flatnonzero(size[:, 0] > 0)[0])  # the first channel that holds texels, moved one texel past the atlas
+            past[ch] = len(tex) - int(size[ch, 0]) * int(size[ch, 1]) + 1
+            rc = lib.rtHipSceneSetMaterials(rs.handle, ctypes.byref(R.MaterialUpdate(1, count, R._ptr(size), R._ptr(past), len(tex), R._ptr(tex), None, 0)))
+            text = "exceed"
+        elif variant == "65536_lights":
+            rc, text = lib.rtHipSceneSetLights(rs.handle, ctypes.byref(R.Lights(65536, *[p[k] for k in R.LIGHT_FIELDS]))), "too large"
+        else:
+            rc = lib.rtHipSceneSetLights(rs.handle, ctypes.byref(R.Lights(2, p["light_type"], None, p["light_dir"], p["light_col"], p["light_radius"],
+                                                                          p["light_half_att"])))
+            text = "null light array"
+        assert int(rc) == code and text in R.last_error(), f"refused edit ({variant}): returned {rc} with {R.last_error()!r}, expected {code} with {text!r}"
+        if code == -5:
+            assert "scene rejected" in R.last_error(), R.last_error()
+        assert rs.pointers() == pointers, f"refused edit ({variant}): the scene's addresses changed"
+        assert rs.bytes() - held == grown, \
+            f"refused edit ({variant}): the scene holds {rs.bytes()} bytes, {held} before it (staging expected: exactly {grown})"
+
+    # -- mattes: the group table is state; a call reads the last frame's window for its defaults and leaves window and buffers alone
+    def do_matte_groups(self, seed=None):
+        if self.rs:
+            self.rs.set_matte_groups(None if seed is None else group_table(self.w.base.triangle_count, seed))
+
+    def matte_table(self, kind):
+        if kind == "triangle":
+            return None
+        return MA.material_table(look_ids(self.name, self.look[2])) if kind == "material" else group_table(self.w.base.triangle_count, self.groups)
+
+    def do_mattes(self, arg):
+        kind, n, layers, window = arg
+        S = self.samples
+        last = (S, 0) if self.window_last is None else self.window_last[:2]
+        defaults = dict(kind="triangle", select=(), layers=4, total=last[0], first=last[1], samples=S)
+        if self.rs:
+            got = self.rs.matte_defaults()
+            assert got == defaults, f"the matte defaults are {got}, the model's last frame gives {defaults}"
+        if self.refuses(("mattes", arg)):
+            if self.rs:
+                refusal(lambda: self.rs.mattes(kind="group", layers=layers), "group table", "kind GROUP without a table")
+            return
+        N, f, C_ = window or (last[0], last[1], S)
+        ids = self.w.sample_ids(self.pose, self.shape, N, f, C_)
+        table = self.matte_table(kind)
+        select = selection(MA.table_ids(ids, table), n)
+        want = MA.mattes(ids, table, select, layers, C_, shape=(self.w.height, self.w.width))
+        self.notes.append(("mattes", dict(kind=kind, window=(N, f, C_), layers=layers, select=select), want))
+        if self.rs:
+            kw = {} if window is None else dict(total=N, first=f, samples=C_)
+            got = self.rs.mattes(kind=kind, select=select, layers=layers, **kw)
+            assert sorted(got) == sorted(k for k in ("select", "layer_id", "layer_coverage", "rest") if k != "select" or select), sorted(got)
+            for k in got:
+                differs(got[k], want[k], f"matte output {k} ({kind}, select {select}, K = {layers}, window {(N, f, C_)}) at {self.here()}")
 
 
 def describe(steps):
@@ -960,7 +1564,7 @@ def play(name, seed, part, last=None, report=None):
     w = world(name)
     rs = R.ResidentScene(w.state(*seq["start"]), 0)
     try:
-        s = Session(w, seq["start"], rs)
+        s = Session(w, seq["start"], rs, edit=is_edit(name, seed))
         s.same_window("a fresh scene")
         for i, step in enumerate(steps):
             try:

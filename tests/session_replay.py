@@ -2,8 +2,8 @@
 the tool for reducing a failure of tests/test_session_gpu.py (find the shortest failing prefix with LAST_STEP, then drop steps in a
 copy of the sequence under session_cases.REGRESSIONS).  One pass; nothing is tried again.
 usage: python tests/session_replay.py SCENE SEED [PART] [LAST_STEP]
-SEED: a circuit or walk seed of the scene (the wide seeds, which also draw window and variance steps, included: session_cases.SCENES),
-or the name of a regression; PART: one sequence of the seed (default: all of them)."""
+SEED: a circuit or walk seed of the scene (the wide seeds, which also draw window and variance steps, and the edit seeds, which also
+draw lights, materials, ids, refused_edit, matte_groups and mattes steps, included: session_cases.SCENES), or the name of a regression; PART: one sequence of the seed (default: all of them)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

@@ -5,7 +5,6 @@ The yardstick is always a FRESH ResidentScene of the edited description (the "tw
 scene.pack_lights / scene.pack_materials) -- a path the rest of the suite pins to the oracle.  Every test needs the entry points of this
 feature, so all of them fail without it.  Where a test could pass on nothing (an edit that changes no pixel), it asserts that the twins of
 consecutive steps differ."""
-import copy
 import ctypes as C
 
 import torch  # (before the library loads its HIP runtime: the order bench.py uses)
@@ -14,6 +13,7 @@ import pytest
 
 import camera_cases as CC
 import scenarios
+from edit_cases import ONE_SUN, SPOT, fold, lights_of, many_lights, materials_of, twin_of
 from opencl_render_amd import raytrace as R, scene as S
 
 pytestmark = pytest.mark.gpu
@@ -39,29 +39,6 @@ def base(name):
         R.build_lists(sc)
         _bases[name] = sc
     return _bases[name]
-
-
-def lights_of(spec):
-    """The six arrays (a dict under Scene's field names) of a list of light dicts, or of a Scene."""
-    return R.scene_lights(spec) if isinstance(spec, S.Scene) else dict(zip(R.LIGHT_FIELDS, S.pack_lights(spec)))
-
-
-def materials_of(spec):
-    if isinstance(spec, S.Scene):
-        return dict(mat_size=spec.mat_size, mat_start=spec.mat_start, textures=spec.textures)
-    return dict(zip(("mat_size", "mat_start", "textures"), S.pack_materials(spec)))
-
-
-def twin_of(sc, lights=None, materials=None, ids=None, **fields):
-    out = copy.copy(sc)
-    for part in (lights, materials):
-        for k, v in (part or {}).items():
-            setattr(out, k, v)
-    if ids is not None:
-        out.tri_material = np.ascontiguousarray(ids, np.int32)
-    for k, v in fields.items():
-        setattr(out, k, v)
-    return out
 
 
 def frame(rs):
@@ -93,18 +70,6 @@ def differ(a, b):
 
 def rows(rs):
     return np.asarray(rs.scene_view("tri_shade")).reshape(-1, 24).view(np.int32).copy()
-
-
-def many_lights(n, seed):
-    """n dim lights of types 0..9 inside and around the soup (dim: their sum stays below saturation)."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    return [dict(type=int(rng.integers(0, 10)), pos=tuple(rng.uniform(-1, 1, 3) + [0, 0, 2]), dir=tuple(rng.uniform(-1, 1, 3)),
-                 col=tuple(rng.uniform(0.004, 0.03, 3)), radius=float(rng.uniform(0.05, 0.6)), half_att=float(rng.choice([np.inf, 2.0])))
-            for _ in range(n)]
-
-
-ONE_SUN = [dict(type=S.LIGHT_DISTANT, dir=(0.3, -0.8, 0.5), col=(0.9, 0.9, 0.8))]
-SPOT = dict(type=S.LIGHT_SPOT, pos=(0.4, 0.6, 1.5), col=(0.5, 0.4, 0.3), radius=0.2, half_att=2.0)
 
 
 LIGHT_STEPS = [("none", lambda: []), ("one_distant", lambda: ONE_SUN), ("spot_finite_range", scenarios.spot_finite_range),
@@ -181,11 +146,6 @@ def test_lights_class_transitions_keep_the_sample_window():
             before = want
     finally:
         rs.close()
-
-
-def fold(ids, m):
-    ids = np.asarray(ids, np.int32)
-    return np.where(ids < 0, ids, ids % m).astype(np.int32)
 
 
 def test_materials_class_transitions():

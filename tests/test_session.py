@@ -2,7 +2,10 @@
 deterministic, every circuit holds every ordered pair of kinds exactly once and cutting loses none, camera and shape steps change the
 state; on the oracles alone the visited states are not vacuous (hit shares, changed shares), the caps hold (refusals, accepting
 temporal steps, a temporal step on an older frame and a motion step with camera and shape both changed in every circuit), and the
-model, driven through the chains of motion_cases.py and temporal_cases.py, gives exactly their states, references and histories."""
+model, driven through the chains of motion_cases.py and temporal_cases.py, gives exactly their states, references and histories.
+The edit seeds: their caps (class crossings by direction and cause, frames, clones, histories and mattes around them), the shares by
+which an edit changes the oracle's planes and mattes differ, and that planes and mattes of an edited look are those of a scene built
+with the look's fields from the start."""
 import collections
 
 import numpy as np
@@ -24,7 +27,7 @@ F32 = np.float32
 
 
 def circuits():
-    return [(name, seed) for name, spec in SC.SCENES.items() for seed in spec["circuits"] + spec["wide_circuits"]]
+    return [(name, seed) for name, spec in SC.SCENES.items() for seed in spec["circuits"] + spec["wide_circuits"] + spec.get("edit_circuits", ())]
 
 
 def every_sequence():
@@ -40,6 +43,8 @@ def test_generation_is_deterministic():
     for wide, counts in ((False, SC.COUNTS), (True, SC.COUNTS_WIDE)):  # the seeds drawn before the wide alphabet existed are what they were
         mine = [q for (n, s, p), q in first.items() if s in SC.seeds_of(n, wide)]
         assert dict(sequences=len(mine), steps=sum(len(q["steps"]) for q in mine)) == counts, f"the draw changed (wide: {wide}): measure again"
+    mine = [q for (n, s, p), q in first.items() if s in SC.edit_seeds(n)]
+    assert dict(sequences=len(mine), steps=sum(len(q["steps"]) for q in mine)) == SC.COUNTS_EDIT, "the draw of the edit seeds changed: measure again"
 
 
 @pytest.mark.parametrize("name, seed", circuits())
@@ -53,13 +58,13 @@ def test_a_circuit_holds_every_ordered_pair_once_and_cutting_loses_none(name, se
             assert ks[0] == kinds[-1], "a sequence does not start with the kind the one before ended in"
             ks = ks[1:]
         kinds += ks
-        s = SC.Lite(*q["start"], samples=SC.SCENES[name]["samples"])
+        s = SC.lite_of(name, seed, q["start"])
         for step in q["steps"]:
             s.advance(step)
         end = (s.pose, s.shape)
     alphabet = SC.kinds_of(name, seed)
     K = len(alphabet)
-    assert K == (19 if seed in SC.SCENES[name]["wide_circuits"] else 17)
+    assert K == (25 if seed in SC.SCENES[name].get("edit_circuits", ()) else 19 if seed in SC.SCENES[name]["wide_circuits"] else 17)
     assert len(kinds) == K * K + 1 and kinds[0] == kinds[-1]
     pairs = collections.Counter(zip(kinds, kinds[1:]))
     assert len(pairs) == K * K and set(pairs.values()) == {1} and set(k for k, _ in pairs) == set(alphabet)
@@ -70,9 +75,24 @@ def test_a_circuit_holds_every_ordered_pair_once_and_cutting_loses_none(name, se
 def test_camera_and_shape_steps_change_the_state_and_refusals_stay_rare():
     for name, seed, part, q in every_sequence():
         S = SC.SCENES[name]["samples"]
-        s, refused = SC.Lite(*q["start"], samples=S), 0
+        s, refused = SC.lite_of(name, seed, q["start"]), 0
         for kind, arg in q["steps"]:
             assert kind in SC.kinds_of(name, seed)
+            if kind in ("lights", "materials", "ids"):  # an edit names a set of the tables and always changes the look
+                assert s.after((kind, arg)) != s.look, (name, seed, part, kind, arg)
+                L, M, (variant, modulus) = s.after((kind, arg))
+                assert L in SC.LIGHT_SETS and M in SC.MATERIAL_SETS and variant in SC.ID_VARIANTS
+                assert int(SC.look_ids(name, (variant, modulus)).max()) < SC.look_parts(name)["counts"][M], "an id of the look is out of range"
+            if kind == "materials":  # ids come exactly where the resident ones would be out of range, and in some draws otherwise
+                assert arg[1] is not None or s.max_id() < SC.look_parts(name)["counts"][arg[0]]
+            if kind == "refused_edit":
+                assert arg in SC.EDIT_REFUSALS and (arg != "shrink" or s.max_id() >= 1)
+            if kind == "mattes":
+                what, n, layers, window = arg
+                assert what in SC.MATTE_KINDS and n in SC.MATTE_SELECT and layers in SC.MATTE_LAYERS
+                if window is not None:
+                    p = R.MatteParams(kind=0, total=window[0], first=window[1], samples=window[2], selectCount=0, layers=layers)
+                    assert R.lib().rtHipMatteCheck(C.byref(p)) == 0, (window, R.last_error())
             if kind == "window" and arg is not None:
                 win = arg[1] if s.refuses((kind, arg)) else arg
                 rc = R.lib().rtHipSampleWindowCheck(S, C.byref(R.SampleWindow(*win)))
@@ -91,7 +111,7 @@ def test_camera_and_shape_steps_change_the_state_and_refusals_stay_rare():
             s.advance((kind, arg))
         assert refused * 5 <= len(q["steps"]), f"{name} seed {seed} part {part}: {refused} of {len(q['steps'])} steps are refusals"
     for name, spec in SC.SCENES.items():
-        for seed in spec["walks"] + spec["wide_walks"]:
+        for seed in spec["walks"] + spec["wide_walks"] + spec.get("edit_walks", ()):
             parts = SC.sequences(name, seed)
             assert sum(len(q["steps"]) for q in parts) == SC.WALK + len(parts) - 1  # (a cut walk repeats the kind it was cut at)
             assert all(len(q["steps"]) <= spec.get("walk_cut", SC.WALK) for q in parts) and ("walk_cut" in spec or len(parts) == 1)
@@ -111,7 +131,7 @@ def played(name):
         for n, seed, part, q in every_sequence():
             if n != name:
                 continue
-            s = SC.Session(w, q["start"])
+            s = SC.Session(w, q["start"], edit=SC.is_edit(name, seed))
             states.append(s.here())
             for step in q["steps"]:
                 before = s.here()
@@ -131,7 +151,8 @@ def test_visited_states_hit_and_consecutive_states_differ(name):
     hits = []
     for st in states:
         hits.append(float((w.trace(*st)[1] != SC.NONE).mean()))
-        assert hits[-1] >= MC.MIN_HIT, f"{name}/{st}: only {hits[-1]:.3f} of the centre rays hit"
+        floor = SC.SCENES[name].get("min_hit", MC.MIN_HIT)
+        assert hits[-1] >= floor, f"{name}/{st}: only {hits[-1]:.3f} of the centre rays hit"
     changed = []
     for a, b in moves:
         share = GC.changed_share(w.planes(*a), w.planes(*b))
@@ -233,9 +254,125 @@ def test_the_wide_seeds_variance_steps_find_stale_and_live_moments():
 
 def test_the_scenes_of_the_wide_seeds_take_no_split_logic_rounds():
     """Why no sequence is played a second time under RT_WF_LOGIC_SPLIT=0 (session_cases.SCENES): split rounds exist in the
-    opaque-diffuse class only, and both scenes are of the general class."""
-    for name in SC.SCENES:
+    opaque-diffuse class only, and both scenes that have wide seeds are of the general class (class_textured_bumped, which has the
+    edit seeds, is the scene of the opaque-diffuse class)."""
+    wide = [name for name in SC.SCENES if SC.seeds_of(name, wide=True)]
+    assert wide == ["mirror_hall", "axis_near_axis_mixed"]
+    for name in wide:
         assert R.path_class(SC.world(name).base) == R.PATH_CLASS_GENERAL, name
+
+
+# ---- the edit seeds: looks, class crossings and mattes ---------------------------------------------------------------------------------------------
+EDITED = "class_textured_bumped"
+
+
+def edit_logs():
+    """(frames, events) of the edit seeds' sequences, one list per sequence each, from the light state alone."""
+    frames, events = [], []
+    for seed in SC.edit_seeds(EDITED):
+        for q in SC.sequences(EDITED, seed):
+            s = SC.lite_of(EDITED, seed, q["start"])
+            for step in q["steps"]:
+                s.advance(step)
+            frames.append(s.frames)
+            events.append(s.log.events)
+    return frames, events
+
+
+def test_the_edit_seeds_cross_the_class_boundary_between_all_other_operations():
+    frames, events = edit_logs()
+    facts = SC.edit_facts(frames, events)
+    print(f"edit seeds: {facts}")
+    assert R.path_class(SC.world(EDITED).base) == R.PATH_CLASS_OPAQUE_DIFFUSE
+    assert {SC.look_class(EDITED, (L, M, None)) for L in SC.LIGHT_SETS for M in SC.MATERIAL_SETS} == {R.PATH_CLASS_GENERAL, R.PATH_CLASS_OPAQUE_DIFFUSE}
+    assert int(SC.look_parts(EDITED)["lights"]["many65"]["light_type"].shape[0]) == 65  # past the logic kernel's 64-light split
+    assert facts["edits"] >= 60 and facts["same_look"] == 0, "an edit leaves the look as it was"
+    for k in ("lights_to_general", "lights_to_opaque_diffuse", "materials_to_general", "materials_to_opaque_diffuse"):
+        assert facts[k] >= 2, k
+    for k in ("frames_general_after_camera", "frames_general_after_shape", "frames_opaque_diffuse_after_camera", "frames_opaque_diffuse_after_shape",
+              "clones_in_another_class", "frames_on_another_look", "temporal_across", "variance_across", "mattes_triangle", "mattes_material",
+              "mattes_group", "mattes_group_after_shape", "mattes_group_after_edit", "mattes_material_after_ids", "mattes_before_frames",
+              "mattes_refused"):
+        assert facts[k] >= 1, k
+    assert 3 * facts["mattes_defaults_other_window"] >= facts["mattes_defaults"] > 0
+    assert SC.edit_caps(facts)
+
+
+def test_the_edit_seeds_histories_cross_the_class_boundary_and_show_it():
+    """A temporal and a variance step whose live history holds a frame of another class are counted only under max_history > 1 (at 1
+    the answer is the frame itself), and at least one of each blends the history in and gives another answer than over an empty
+    history: a history that an edit or a class crossing wiped would fail these steps."""
+    _, events = edit_logs()
+    logged = collections.Counter(e[0] for part in events for e in part if e[0] in ("temporal", "variance") and e[1])
+    notes = [n[1:] for seed in SC.edit_seeds(EDITED) for part in range(len(SC.sequences(EDITED, seed)))
+             for n in played(EDITED)[0][seed, part] if n[0] == "across"]
+    print(f"edit seeds: steps with a live history across a class change (kind, max_history, share of the pixels that blend the history in, "
+          f"share that differs from the answer over an empty history): {[(k, f['cap'], round(f['blended'], 3), round(f['differs'], 3)) for k, f in notes]}")
+    assert collections.Counter(k for k, _ in notes) == logged, "the model and the light state disagree on which steps cross"
+    assert all(f["cap"] > 1 for _, f in notes)
+    for kind in ("temporal", "variance"):
+        shown = [f for k, f in notes if k == kind and f["blended"] > 0 and f["differs"] > 0]
+        assert shown, f"no {kind} step blends a history across a class change into another answer than over an empty history"
+    assert SC.histories_cross(notes)
+
+
+def test_the_edit_seeds_edits_and_mattes_are_not_vacuous():
+    frames, events = edit_logs()
+    shares = SC.edit_shares(EDITED, frames)
+    pairs, differing = SC.matte_pairs(EDITED, events)
+    notes = [n for seed in SC.edit_seeds(EDITED) for part in range(len(SC.sequences(EDITED, seed)))
+             for n in played(EDITED)[0][seed, part] if n[0] == "mattes"]
+    rest = sum(bool(w["rest_count"].any()) for _, _, w in notes)
+    two = sum(bool((w["layer_count"] > 0).sum(0).max() >= 2) for _, _, w in notes)
+    selected = sum(bool(info["select"]) and bool(w["select"][0].any()) for _, info, w in notes)
+    other = sum(info["window"][2] != SC.SCENES[EDITED]["samples"] for _, info, _ in notes)
+    print(f"edit seeds: {len(shares)} edits shown by a frame change {min(shares):.3f}..{max(shares):.3f} of the pixels; {pairs} consecutive matte "
+          f"steps under different states or tables, {differing} differ; of {len(notes)} mattes {rest} overflow into rest, {two} hold a pixel of two "
+          f"layers, {selected} select an id that is hit, {other} take another sample count than the scene's")
+    assert len(shares) >= 20 and min(shares) >= SC.MIN_EDIT_CHANGED
+    assert pairs == differing >= 10
+    assert rest >= 1 and two >= 1 and selected >= 1 and other >= 1  # (each figure says that a branch of the definition is taken at all)
+    assert SC.shows_its_edits(EDITED, frames, events)
+
+
+def test_the_model_is_right_about_looks():
+    """Planes and mattes of an edited look are those of a scene built with the look's fields from the start: the scenario with the
+    arrays in place, gridded, cropped, deformed and posed by the helpers of the motion tests, not by the model's Worlds."""
+    import copy
+    import matte_oracle as MA
+    import scenarios
+    parts = SC.look_parts(EDITED)
+    looks = [("sun_spot", "own", (1, 6)), ("many65", "lambert2", (0, 2)), ("none", "hall", (1, 4)), ("own", "hall", (0, 2)), ("sun", "own", (1, 2))]
+    states = [("home", "home"), ("pan", "twist"), ("orbit90", "collapse"), ("shifted", "normals"), ("inside", "scale")]
+    for look, (pose, shape) in zip(looks, states):
+        sc = getattr(scenarios, EDITED)()
+        for k, v in {**parts["lights"][look[0]], **parts["materials"][look[1]]}.items():
+            setattr(sc, k, v)
+        own = parts["ids"][look[2][0]]
+        sc.tri_material = np.where(own < 0, own, own % look[2][1]).astype(np.int32)
+        O_ = copy.copy(sc)
+        O_.box_min, O_.grid_start, O_.grid_list = O.oracle_scene_grid(O_)
+        cropped = MC.crop(O_, *SC.SCENES[EDITED]["size"])
+        bent = GC.with_arrays(cropped, *GC.arrays(cropped, shape), lists=False)
+        bent.box_min, bent.grid_start, bent.grid_list = O.oracle_scene_grid(bent)
+        import camera_cases as CC
+        posed = CC.posed(bent, pose)
+        want = [np.asarray(p).reshape(posed.height, posed.width) for p in O.oracle_render(posed, threads=16)]
+        w = SC.world(EDITED, look)
+        assert w.state(pose, shape).material_count == parts["counts"][look[1]] and w.state(pose, shape).light_count == posed.light_count
+        for ch, g, x in zip("RGB", w.planes(pose, shape), want):
+            assert np.array_equal(g, x), (look, pose, shape, ch)
+        assert GC.changed_share(want, SC.world(EDITED).planes(pose, shape)) >= SC.MIN_EDIT_CHANGED, (look, pose, shape)
+        s = SC.Session(SC.world(EDITED), (pose, shape), edit=True)
+        s.look = look
+        s.apply(("mattes", ("material", 2, 8, (4, 1, 3))))
+        ids = MA.sample_ids(posed, 4, 1, 3)
+        table = MA.material_table(sc.tri_material)
+        _, info, got = s.notes[-1]
+        ref = MA.mattes(ids, table, info["select"], 8, 3, shape=(posed.height, posed.width))
+        for k in ("select", "layer_id", "layer_coverage", "rest"):
+            assert np.array_equal(got[k].view(np.uint32), ref[k].view(np.uint32)), (look, k)
+        assert (ref["layer_count"] > 0).any()
 
 
 # ---- the model against the chains of the motion and temporal tests ---------------------------------------------------------------------------

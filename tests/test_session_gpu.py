@@ -5,17 +5,23 @@ integers, lists and device arrays, motion and temporal accumulation as float bit
 created fresh from the model's Scene, refusals by code and text).  The wide seeds add the sample window and the moments history to
 the state: every frame is the window oracle's frame of the model's window, onto the model's planes where it continues; the scene's
 window is compared with the model's after every step; temporal_variance equals variance_oracle over the model's planes and history;
-the clip bound is compared after every update and in every clone.  A test stops at the first mismatch and names the scene, the seed,
-the step, every step so far and the array that differed; nothing is tried again.  tests/test_session.py shows without a GPU that the
-sequences are not vacuous and that the model is right; tests/session_replay.py plays one sequence by hand.
+the clip bound is compared after every update and in every clone.  The edit seeds (class_textured_bumped, the base scene of the
+opaque-diffuse class) add the look: lights, materials and ids are edited in place, across the path-class boundary and back, frames and
+every product follow the look they belong to, refused edits change nothing, and mattes equal matte_oracle under the model's window,
+ids and group table.  A test stops at the first mismatch and names the scene, the seed, the step, every step so far and the array that
+differed; nothing is tried again.  tests/test_session.py shows without a GPU that the sequences are not vacuous and that the model is
+right; tests/session_replay.py plays one sequence by hand.
 
 Sizing, measured on the MI355X in one run of this file with tests/test_temporal_gpu.py: the temporal suite's slowest test (the camera
-chain on axis_class_sun) takes 1.85 s, so a sequence may take 5.55 s.  The slowest sequence takes 4.4 s (axis_near_axis_mixed, 25
+chain on axis_class_sun) takes 1.90 s, so a sequence may take 5.70 s.  The slowest sequence takes 4.3 s (axis_near_axis_mixed, 25
 steps, with the clip bound checked after its update and in its clones); every mirror_hall sequence of 40 steps and its walks of 60
-stay below 1.8 s, and the two halves of the larger scene's wide walk below 2 s.  The module's fixture takes 63 s: it makes the
-oracles' products once -- the grids of the larger scene's six shapes at 7 s each, prep_oracle's records and dense views, and the planes
-and walks of every visited state -- so that a sequence's time is the device's and the comparisons'.  On the larger scene (12.6 million
-grid pairs) the check of the device arrays after an update takes 1.2 s; a sequence there holds at most two updates and 25 steps."""
+stay below 1.8 s, and the two halves of the larger scene's wide walk below 2.2 s.  Of the 19 sequences of class_textured_bumped's edit
+seeds the slowest takes 1.2 s (seed 21, part 14), the walk of 60 steps 0.7 s.  The module's fixture, measured again with the edit
+seeds' model played in it, takes 65 s in that run (63 s before them).  It makes the oracles' products once -- the grids of the larger
+scene's six shapes at 7 s each, prep_oracle's records and dense views, the planes and walks of every visited state, and the window
+frames, accumulations and sample ids that the wide and the edit sequences read -- so that a sequence's time is the device's and the
+comparisons'.  On the larger scene (12.6 million grid pairs) the check of the device arrays after an update takes 1.2 s; a sequence
+there holds at most two updates and 25 steps."""
 import pytest
 import torch  # noqa: F401  (before the library loads its HIP runtime: the order bench.py uses)
 
