@@ -949,6 +949,76 @@ int  rtHipDenoiseVariance(int device, cl_uint width, cl_uint height, const cl_fl
 int  rtHipSceneTemporalVariance(rtHipScene *scene, const rtHipTemporalParams *params, const rtHipVarianceParams *variance, cl_float *outRgb,
                                 cl_ushort *outR, cl_ushort *outG, cl_ushort *outB, cl_float *outCount, cl_float *outVariance);
 
+/* TEMPORAL CLAMP: neighbourhood clamping of the reprojected history.  TEMPORAL ACCUMULATION accepts a history tap on geometry alone
+ * (triangle id and prevT), so history that no longer agrees with the frame -- after rtHipSceneSetLights or rtHipSceneSetMaterials every
+ * pixel's geometry is unchanged and every tap is accepted -- drags through up to maxHistory frames.  Here the history colour is pulled
+ * into the colour box of the current frame's 3x3 neighbourhood before the blend: the box is the neighbourhood's min / max, or
+ * mean +- gamma * sigma (Salvi's variance clipping), or the intersection of the two.  History that lies inside the box is untouched.  The
+ * arithmetic is IEEE fp32 + - * /, sqrtf and compares in a fixed order (no FMA, division and square root correctly rounded):
+ * tests/temporal_clamp_oracle.py restates it in numpy and the device output equals it bit for bit (up to the payload of a NaN).
+ *
+ * Parameters: mode in {1, 2, 3}, gamma finite and >= 0; anything else returns -1 before anything is launched.
+ * Per pixel p = (x, y) and channel c of the current frame's colour: the taps dy = -1..1 (rows, outer), dx = -1..1 (columns, inner),
+ * q = (x + dx, y + dy); taps outside the image are skipped.
+ *   cnt = the number of taps inside the image as a float (1, 2, 3, 4, 6 or 9; it follows from x, y, W and H alone)
+ *   s1 = s2 = +0.0f, mn = +inf, mx = -inf;  per tap, v = colour_q[c]:  s1 = s1 + v;  s2 = s2 + v*v;  if (v < mn) mn = v;  if (v > mx) mx = v
+ *   mu = s1/cnt, ex2 = s2/cnt, var = ex2 - mu*mu, var = (var > 0 ? var : 0), e = gamma * sqrtf(var)
+ *   mode 1: lo = mn, hi = mx;   mode 2: lo = mu - e, hi = mu + e;
+ *   mode 3: lo = (mu - e > mn ? mu - e : mn), hi = (mu + e < mx ? mu + e : mx)
+ * The rest of the pixel is TEMPORAL ACCUMULATION's, word for word -- gx, gy, ok, the four taps, sw, hc = s/sw, hn, n, a -- with one
+ * insertion: when ok && sw > 0 && n != 1.0f, per channel, before the blend:
+ *   h = hc[c];  if (h < lo) h = lo;  if (h > hi) h = hi
+ * and the blend uses h in place of hc[c]: outColour[c] = h + (colour[c] - h) * a.  outCount is not changed by the clamp.  A constant
+ * neighbourhood makes the box a point, so the output is then the frame itself.  Every bit pattern of the inputs has a defined answer up
+ * to the payload of a NaN -- the compares above define it, in this order: a NaN history colour passes both and stays a NaN; a NaN in
+ * the neighbourhood is skipped by mn and mx and makes mu a NaN (and var 0), so that mode 2's edges are NaN and compare false (no clamp)
+ * and mode 3's are mn and mx.
+ * With moments (the *MomentsClamp* calls and rtHipSceneTemporalVariance under a clamp): the two luminance moments accumulate exactly as
+ * in VARIANCE-GUIDED FILTER (a), from the unclamped taps.  They are NOT clamped: a pixel whose colour was pulled shows a large temporal
+ * variance for a few frames, which is what the variance-guided filter should see there (it widens the luminance edge-stop and the pixel
+ * is filtered spatially while its history is wrong).
+ * Out of scope: clamping the moments, shortening the count on a clamp, larger neighbourhoods, YCoCg. */
+#define RT_HIP_CLAMP_MINMAX   1u
+#define RT_HIP_CLAMP_VARIANCE 2u /* both bits: the intersection */
+typedef struct rtHipTemporalClampParams {
+    cl_uint  mode;  /* RT_HIP_CLAMP_MINMAX, RT_HIP_CLAMP_VARIANCE or both */
+    cl_float gamma; /* the half-width of the variance box, in standard deviations */
+} rtHipTemporalClampParams;
+/* mode = 3, gamma = 1.0f: a parameter's default, not a measurement. */
+void rtHipTemporalClampDefaults(rtHipTemporalClampParams *params);
+/* 0 for legal parameters, -1 (the last-error text set) for NULL, a mode outside {1, 2, 3}, a gamma that is NaN, infinite or negative.
+ * Needs no device. */
+int  rtHipTemporalClampCheck(const rtHipTemporalClampParams *params);
+/* rtHipTemporalDevice / rtHipTemporal with the clamp: the same arrays, the same pointer, overlap, stream and size checks, one launch;
+ * a refusal launches nothing.  clamp NULL is a refusal: the unclamped call exists for that. */
+int  rtHipTemporalClampDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                              const void *triangle, const void *histColour, const void *histCount, const void *histT,
+                              const void *histTriangle, void *outColour, void *outCount, const rtHipTemporalParams *params,
+                              const rtHipTemporalClampParams *clamp, void *stream);
+int  rtHipTemporalClamp(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                        const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                        const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params,
+                        const rtHipTemporalClampParams *clamp);
+/* rtHipTemporalMomentsDevice / rtHipTemporalMoments with the clamp, likewise. */
+int  rtHipTemporalMomentsClampDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                                     const void *triangle, const void *histColour, const void *histCount, const void *histT,
+                                     const void *histTriangle, const void *histMoments, void *outColour, void *outCount, void *outMoments,
+                                     void *outVariance, const rtHipTemporalParams *params, const rtHipTemporalClampParams *clamp,
+                                     void *stream);
+int  rtHipTemporalMomentsClamp(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion,
+                               const cl_float *prevT, const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount,
+                               const cl_float *histT, const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour,
+                               cl_float *outCount, cl_float *outMoments, cl_float *outVariance, const rtHipTemporalParams *params,
+                               const rtHipTemporalClampParams *clamp);
+/* The scene's clamp: clamp non-NULL turns it on with these parameters, NULL turns it off (the default).  While it is on, the
+ * accumulation step of rtHipSceneTemporal and of rtHipSceneTemporalVariance runs the clamped kernel on the gathered colour (ms[2] of
+ * rtHipSceneTemporalTimes stays "the accumulation"); while it is off both calls issue exactly the launches they issue without this
+ * block.  The setting is per scene and touches neither the history, the mark nor any buffer, and needs no storage.  Returns 0, or -1
+ * for a NULL scene or parameters rtHipTemporalClampCheck refuses (the setting then stays what it was). */
+int  rtHipSceneSetTemporalClamp(rtHipScene *scene, const rtHipTemporalClampParams *clamp);
+/* 1 and *out = the parameters if the scene's clamp is on, 0 and *out zeroed if it is off, -1 for a NULL argument. */
+int  rtHipSceneGetTemporalClamp(const rtHipScene *scene, rtHipTemporalClampParams *out);
+
 /* AMBIENT OCCLUSION BAKE: a W x H texture of ambient occlusion over the scene's UV layout.  Each texel centre is mapped to the surface
  * point of the triangle whose UV triangle covers it, and the AO rays of the block above are traced from there with the same walk.  It
  * needs geometry, UVs, corner normals and the grid only: it works on every instance (whatever its tiles, passes or pipeline), ignores

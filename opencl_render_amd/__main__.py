@@ -23,11 +23,16 @@ scene's camera, to PATH: .pfm (f32) or .pgm (u16 quantised like the denoiser's o
 ``--motion PREFIX`` (with ``--orbit N`` or ``--spin N``) also writes every frame's motion vectors (include/raytrace_hip.h, "MOTION
 VECTORS") against the frame before it to PREFIX_000.npz .. PREFIX_{N-1}.npz.
 
-``--temporal PATH`` (with ``--orbit N`` or ``--spin N``) also writes every frame accumulated over the frames before it (include/raytrace_hip.h,
+``--temporal PATH`` (with ``--orbit N``, ``--spin N`` or ``--relight N``) also writes every frame accumulated over the frames before it (include/raytrace_hip.h,
 "TEMPORAL ACCUMULATION"; ResidentScene.temporal) to PATH_000 .. PATH_{N-1}: .bmp, .ppm or .pfm.  With ``--denoise`` the denoiser runs on
 the accumulation before it is written.  ``--variance-guided`` (beside ``--temporal PATH``) carries the luminance moments along and
 runs the variance-guided filter (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER"; ResidentScene.temporal_variance) on the accumulation
 in the denoiser's place; ``--variance PATH`` also writes each frame's variance (V^K with the filter) as .pfm, numbered the same way.
+``--temporal-clamp [GAMMA]`` (beside ``--temporal PATH``) turns the scene's temporal clamp on (include/raytrace_hip.h, "TEMPORAL CLAMP";
+ResidentScene.set_temporal_clamp): the reprojected history is pulled into the frame's 3x3 colour box before the blend, GAMMA (default 1)
+standard deviations wide; ``--temporal-clamp-mode minmax|variance|both`` (default both) chooses the box.  ``--relight N --temporal PATH``
+shows what it is for: without the clamp the old lighting fades out over the history's length, with it the accumulation follows the
+light at once.
 
 ``--relight N`` renders N frames of the one resident scene with its first light turned about the vertical axis between them
 (include/raytrace_hip.h, "SCENE EDITS: LIGHTS AND MATERIALS"; ResidentScene.set_lights): img_000 .. img_{N-1}, with ``--passes`` /
@@ -116,6 +121,12 @@ def parser():
                     help="with --orbit N or --spin N: also write every frame accumulated over the frames before it (ResidentScene.temporal: "
                          "the history reprojected along the motion vectors, default parameters) to PATH numbered like --out: .bmp, .ppm or "
                          ".pfm.  With --denoise the denoiser runs on the accumulation before it is written (the history stays unfiltered)")
+    ap.add_argument("--temporal-clamp", type=float, nargs="?", const=1.0, default=None, metavar="GAMMA",
+                    help="with --temporal PATH: clamp the reprojected history to the colour box of the frame's 3x3 neighbourhood before the "
+                         "blend (ResidentScene.set_temporal_clamp); GAMMA (default 1) is the variance box's half-width in standard deviations")
+    ap.add_argument("--temporal-clamp-mode", choices=("minmax", "variance", "both"), default=None,
+                    help="with --temporal-clamp: the box is the neighbourhood's min / max, its mean +- GAMMA sigma, or (the default) the "
+                         "intersection of both")
     ap.add_argument("--variance-guided", action="store_true",
                     help="with --temporal PATH: accumulate the luminance moments too and run the variance-guided filter (default parameters) "
                          "on the accumulation before it is written (ResidentScene.temporal_variance); not together with --denoise")
@@ -168,8 +179,14 @@ def parse_args(argv=None):
         ap.error("--spin does not go with --orbit or --bake-ao")
     if args.motion and args.orbit < 2 and args.spin < 2:
         ap.error("--motion PREFIX needs --orbit N or --spin N with N >= 2 (the frames it is measured between)")
-    if args.temporal and args.orbit < 2 and args.spin < 2:
-        ap.error("--temporal PATH needs --orbit N or --spin N with N >= 2 (the frames it accumulates)")
+    if args.temporal and args.orbit < 2 and args.spin < 2 and args.relight < 2:
+        ap.error("--temporal PATH needs --orbit N, --spin N or --relight N with N >= 2 (the frames it accumulates)")
+    if args.temporal_clamp is not None and not args.temporal:
+        ap.error("--temporal-clamp needs --temporal PATH")
+    if args.temporal_clamp is not None and not (np.isfinite(args.temporal_clamp) and args.temporal_clamp >= 0):
+        ap.error("--temporal-clamp GAMMA needs a finite GAMMA >= 0")
+    if args.temporal_clamp_mode and args.temporal_clamp is None:
+        ap.error("--temporal-clamp-mode needs --temporal-clamp")
     if args.temporal and not args.temporal.lower().endswith((".bmp", ".ppm", ".pfm")):
         ap.error("--temporal PATH must end in .bmp, .ppm or .pfm")
     if (args.variance_guided or args.variance) and not args.temporal:
@@ -351,10 +368,12 @@ def write_motion(rs, args, index: int) -> None:
 
 def write_temporal(rs, args, index: int) -> None:
     """--temporal: frame `index` accumulated over the frames before it -> PATH numbered like --out; with --denoise or --variance-guided,
-    filtered; --variance: its variance too."""
+    filtered; --variance: its variance too.  --temporal-clamp: under the scene's clamp, set before frame 0."""
     if not args.temporal:
         return
     from . import frontend, raytrace
+    if index == 0 and args.temporal_clamp is not None:
+        rs.set_temporal_clamp(args.temporal_clamp_mode or "both", args.temporal_clamp)
     if args.variance_guided or args.variance:
         res = rs.temporal_variance(filter={} if args.variance_guided else None)
         if args.variance:
@@ -466,7 +485,7 @@ def render_relight(sc, args, device: int) -> float:
     from . import raytrace
     rs = raytrace.ResidentScene(sc, device)
     try:
-        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise)
+        basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
         if basic or surface:
             rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
         lights = raytrace.scene_lights(sc)
@@ -484,6 +503,7 @@ def render_relight(sc, args, device: int) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_temporal(rs, args, i)
     finally:
         rs.close()
     return spent

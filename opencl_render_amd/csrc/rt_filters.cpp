@@ -1,5 +1,5 @@
 // rt_filters.cpp -- the image-space filters of libraytrace_hip.so (include/raytrace_hip.h: "DENOISER", "TEMPORAL ACCUMULATION",
-// "VARIANCE-GUIDED FILTER"): parameter checks, the device and host entry points, and the resident scene's calls with their buffers.
+// "VARIANCE-GUIDED FILTER", "TEMPORAL CLAMP"): parameter checks, the device and host entry points, and the resident scene's calls with their buffers.
 // The kernels are in rt_denoise.hip, rt_temporal.hip and rt_variance.hip; the scene and what else the host side shares, in rt_host.h.
 #include "rt_host.h"
 #include "rt_launch.h"
@@ -250,9 +250,47 @@ static int temporal_size_ok(uint32_t W, uint32_t H)
     return 0;
 }
 
-int rtHipTemporalDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
-                        const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
-                        void *outColour, void *outCount, const rtHipTemporalParams *params, void *stream)
+// ---- temporal clamp (include/raytrace_hip.h, "TEMPORAL CLAMP"; rtt_clamp_kernel in rt_temporal.hip) ------------------------------
+void rtHipTemporalClampDefaults(rtHipTemporalClampParams *p)
+{
+    if (!p) return;
+    p->mode = RT_HIP_CLAMP_MINMAX | RT_HIP_CLAMP_VARIANCE;
+    p->gamma = 1.0f;
+}
+
+int rtHipTemporalClampCheck(const rtHipTemporalClampParams *p)
+{
+    if (!p) return fail("temporal clamp: null parameters");
+    if (p->mode < 1 || p->mode > 3) return fail("temporal clamp: mode %u is not 1 (min/max), 2 (variance) or 3 (both)", p->mode);
+    if (!(std::isfinite(p->gamma) && p->gamma >= 0.f)) return fail("temporal clamp: gamma %g is not finite and >= 0", (double)p->gamma);
+    return 0;
+}
+
+// The accumulation on checked device arrays: with `clamp` (checked) the clamped kernel, with or without moments; without, the kernel
+// each call has always issued.
+static int accumulate_issue(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT, const uint32_t *triangle,
+                            const float *histColour, const float *histCount, const float *histT, const uint32_t *histTriangle,
+                            const float *histMoments, float *outColour, float *outCount, float *outMoments, float *outVariance,
+                            const rtHipTemporalParams *p, const rtHipTemporalClampParams *clamp, hipStream_t st)
+{
+    if (clamp)
+        HIP_OK(rtt_launch_accumulate_clamp(W, H, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, histMoments,
+                                           outColour, outCount, outMoments, outVariance, p->maxHistory, p->depthTolerance, clamp->mode,
+                                           clamp->gamma, st));
+    else if (histMoments)
+        HIP_OK(rtv_launch_moments(W, H, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, histMoments, outColour,
+                                  outCount, outMoments, outVariance, p->maxHistory, p->depthTolerance, st));
+    else
+        HIP_OK(rtt_launch_accumulate(W, H, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, outColour, outCount,
+                                     p->maxHistory, p->depthTolerance, st));
+    return 0;
+}
+
+// rtHipTemporalDevice (clamp null) and rtHipTemporalClampDevice (clamp checked by the caller)
+static int temporal_device(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                           const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
+                           void *outColour, void *outCount, const rtHipTemporalParams *params, const rtHipTemporalClampParams *clamp,
+                           void *stream)
 {
     if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
     if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !outColour)
@@ -263,15 +301,34 @@ int rtHipTemporalDevice(int device, cl_uint width, cl_uint height, const void *c
         { histColour, n * 12, 4, "histColour" }, { histCount, n * 4, 4, "histCount" }, { histT, n * 4, 4, "histT" },
         { histTriangle, n * 4, 4, "histTriangle" }, { outColour, n * 12, 4, "outColour", true }, { outCount, n * 4, 4, "outCount", true } };
     if (checked_device_arrays("temporal", device, stream, arr, 10) != 0) return -1;
-    HIP_OK(rtt_launch_accumulate(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
-                                 (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle,
-                                 (float *)outColour, (float *)outCount, params->maxHistory, params->depthTolerance, (hipStream_t)stream));
-    return 0;
+    return accumulate_issue(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
+                            (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle, nullptr,
+                            (float *)outColour, (float *)outCount, nullptr, nullptr, params, clamp, (hipStream_t)stream);
 }
 
-int rtHipTemporal(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
-                  const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
-                  const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params)
+int rtHipTemporalDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                        const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
+                        void *outColour, void *outCount, const rtHipTemporalParams *params, void *stream)
+{
+    return temporal_device(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, outColour,
+                           outCount, params, nullptr, stream);
+}
+
+int rtHipTemporalClampDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                             const void *triangle, const void *histColour, const void *histCount, const void *histT,
+                             const void *histTriangle, void *outColour, void *outCount, const rtHipTemporalParams *params,
+                             const rtHipTemporalClampParams *clamp, void *stream)
+{
+    if (rtHipTemporalClampCheck(clamp) != 0) return -1;
+    return temporal_device(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, outColour,
+                           outCount, params, clamp, stream);
+}
+
+// rtHipTemporal (clamp null) and rtHipTemporalClamp (clamp checked by the caller)
+static int temporal_host(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                         const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                         const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params,
+                         const rtHipTemporalClampParams *clamp)
 {
     if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
     if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !outColour)
@@ -285,12 +342,30 @@ int rtHipTemporal(int device, cl_uint width, cl_uint height, const cl_float *col
     const cl_uint *htri = dev.up(histTriangle, n * 4);
     float *dColour = dev.out<float>(n * 12), *dCount = outCount ? dev.out<float>(n * 4) : nullptr;
     if (dev.status != hipSuccess) return dev.failed();
-    HIP_OK(rtt_launch_accumulate(width, height, c, m, pt, tri, hc, hn, ht, htri, dColour, dCount, params->maxHistory, params->depthTolerance,
-                                 nullptr));
+    if (accumulate_issue(width, height, c, m, pt, tri, hc, hn, ht, htri, nullptr, dColour, dCount, nullptr, nullptr, params, clamp, nullptr) != 0)
+        return -1;
     HIP_OK(hipMemcpy(outColour, dColour, n * 12, hipMemcpyDeviceToHost));
     if (outCount) HIP_OK(hipMemcpy(outCount, dCount, n * 4, hipMemcpyDeviceToHost));
     HIP_OK(hipDeviceSynchronize());
     return 0;
+}
+
+int rtHipTemporal(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                  const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                  const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params)
+{
+    return temporal_host(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, outColour, outCount,
+                         params, nullptr);
+}
+
+int rtHipTemporalClamp(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                       const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                       const cl_uint *histTriangle, cl_float *outColour, cl_float *outCount, const rtHipTemporalParams *params,
+                       const rtHipTemporalClampParams *clamp)
+{
+    if (rtHipTemporalClampCheck(clamp) != 0) return -1;
+    return temporal_host(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, outColour, outCount,
+                         params, clamp);
 }
 
 // ---- variance-guided filter (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER"; kernels in rt_variance.hip) ------------------------
@@ -388,10 +463,11 @@ int rtHipDenoiseVariance(int device, cl_uint width, cl_uint height, const cl_flo
     return 0;
 }
 
-int rtHipTemporalMomentsDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
-                               const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
-                               const void *histMoments, void *outColour, void *outCount, void *outMoments, void *outVariance,
-                               const rtHipTemporalParams *params, void *stream)
+// rtHipTemporalMomentsDevice (clamp null) and rtHipTemporalMomentsClampDevice (clamp checked by the caller)
+static int moments_device(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                          const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
+                          const void *histMoments, void *outColour, void *outCount, void *outMoments, void *outVariance,
+                          const rtHipTemporalParams *params, const rtHipTemporalClampParams *clamp, void *stream)
 {
     if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
     if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !histMoments || !outColour ||
@@ -404,17 +480,36 @@ int rtHipTemporalMomentsDevice(int device, cl_uint width, cl_uint height, const 
         { histTriangle, n * 4, 4, "histTriangle" }, { histMoments, n * 8, 4, "histMoments" }, { outColour, n * 12, 4, "outColour", true },
         { outMoments, n * 8, 4, "outMoments", true }, { outCount, n * 4, 4, "outCount", true }, { outVariance, n * 4, 4, "outVariance", true } };
     if (checked_device_arrays("temporal", device, stream, arr, 13) != 0) return -1;
-    HIP_OK(rtv_launch_moments(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
-                              (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle,
-                              (const float *)histMoments, (float *)outColour, (float *)outCount, (float *)outMoments, (float *)outVariance,
-                              params->maxHistory, params->depthTolerance, (hipStream_t)stream));
-    return 0;
+    return accumulate_issue(width, height, (const float *)colour, (const float *)motion, (const float *)prevT, (const uint32_t *)triangle,
+                            (const float *)histColour, (const float *)histCount, (const float *)histT, (const uint32_t *)histTriangle,
+                            (const float *)histMoments, (float *)outColour, (float *)outCount, (float *)outMoments, (float *)outVariance, params,
+                            clamp, (hipStream_t)stream);
 }
 
-int rtHipTemporalMoments(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
-                         const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
-                         const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour, cl_float *outCount, cl_float *outMoments,
-                         cl_float *outVariance, const rtHipTemporalParams *params)
+int rtHipTemporalMomentsDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                               const void *triangle, const void *histColour, const void *histCount, const void *histT, const void *histTriangle,
+                               const void *histMoments, void *outColour, void *outCount, void *outMoments, void *outVariance,
+                               const rtHipTemporalParams *params, void *stream)
+{
+    return moments_device(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, histMoments,
+                          outColour, outCount, outMoments, outVariance, params, nullptr, stream);
+}
+
+int rtHipTemporalMomentsClampDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *prevT,
+                                    const void *triangle, const void *histColour, const void *histCount, const void *histT,
+                                    const void *histTriangle, const void *histMoments, void *outColour, void *outCount, void *outMoments,
+                                    void *outVariance, const rtHipTemporalParams *params, const rtHipTemporalClampParams *clamp, void *stream)
+{
+    if (rtHipTemporalClampCheck(clamp) != 0) return -1;
+    return moments_device(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, histMoments,
+                          outColour, outCount, outMoments, outVariance, params, clamp, stream);
+}
+
+// rtHipTemporalMoments (clamp null) and rtHipTemporalMomentsClamp (clamp checked by the caller)
+static int moments_host(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                        const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                        const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour, cl_float *outCount, cl_float *outMoments,
+                        cl_float *outVariance, const rtHipTemporalParams *params, const rtHipTemporalClampParams *clamp)
 {
     if (temporal_params_ok(params) != 0 || temporal_size_ok(width, height) != 0) return -1;
     if (!colour || !motion || !prevT || !triangle || !histColour || !histCount || !histT || !histTriangle || !histMoments || !outColour ||
@@ -431,14 +526,34 @@ int rtHipTemporalMoments(int device, cl_uint width, cl_uint height, const cl_flo
     float *dColour = dev.out<float>(n * 12), *dMoments = dev.out<float>(n * 8);
     float *dCount = outCount ? dev.out<float>(n * 4) : nullptr, *dVariance = outVariance ? dev.out<float>(n * 4) : nullptr;
     if (dev.status != hipSuccess) return dev.failed();
-    HIP_OK(rtv_launch_moments(width, height, c, m, pt, tri, hc, hn, ht, htri, hm, dColour, dCount, dMoments, dVariance, params->maxHistory,
-                              params->depthTolerance, nullptr));
+    if (accumulate_issue(width, height, c, m, pt, tri, hc, hn, ht, htri, hm, dColour, dCount, dMoments, dVariance, params, clamp, nullptr) != 0)
+        return -1;
     HIP_OK(hipMemcpy(outColour, dColour, n * 12, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(outMoments, dMoments, n * 8, hipMemcpyDeviceToHost));
     if (outCount) HIP_OK(hipMemcpy(outCount, dCount, n * 4, hipMemcpyDeviceToHost));
     if (outVariance) HIP_OK(hipMemcpy(outVariance, dVariance, n * 4, hipMemcpyDeviceToHost));
     HIP_OK(hipDeviceSynchronize());
     return 0;
+}
+
+int rtHipTemporalMoments(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                         const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                         const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour, cl_float *outCount, cl_float *outMoments,
+                         cl_float *outVariance, const rtHipTemporalParams *params)
+{
+    return moments_host(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, histMoments,
+                        outColour, outCount, outMoments, outVariance, params, nullptr);
+}
+
+int rtHipTemporalMomentsClamp(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *prevT,
+                              const cl_uint *triangle, const cl_float *histColour, const cl_float *histCount, const cl_float *histT,
+                              const cl_uint *histTriangle, const cl_float *histMoments, cl_float *outColour, cl_float *outCount,
+                              cl_float *outMoments, cl_float *outVariance, const rtHipTemporalParams *params,
+                              const rtHipTemporalClampParams *clamp)
+{
+    if (rtHipTemporalClampCheck(clamp) != 0) return -1;
+    return moments_host(device, width, height, colour, motion, prevT, triangle, histColour, histCount, histT, histTriangle, histMoments,
+                        outColour, outCount, outMoments, outVariance, params, clamp);
 }
 
 // ---- the resident scene's temporal calls -------------------------------------------------------------------------------------------
@@ -518,13 +633,10 @@ static int scene_temporal(rtHipScene *sc, const rtHipTemporalParams *params, con
         HIP_OK(rtt_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, colour, st));
     }
     HIP_OK(hipEventRecord(T.ev[2], st));
-    if (withMoments)
-        HIP_OK(rtv_launch_moments(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle,
-                                  moments[T.cur], next.colour, next.count, moments[T.cur ^ 1], variance ? nullptr : varianceOut,
-                                  params->maxHistory, params->depthTolerance, st));
-    else
-        HIP_OK(rtt_launch_accumulate(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle, next.colour,
-                                     next.count, params->maxHistory, params->depthTolerance, st));
+    if (accumulate_issue(W, H, colour, motion, prevT, next.triangle, hist.colour, hist.count, hist.t, hist.triangle,
+                         withMoments ? moments[T.cur] : nullptr, next.colour, next.count, withMoments ? moments[T.cur ^ 1] : nullptr,
+                         withMoments && !variance ? varianceOut : nullptr, params, T.clampOn ? &T.clamp : nullptr, st) != 0)
+        return -1;
     HIP_OK(hipEventRecord(T.ev[3], st));
     // From here until the new mark stands, a failure leaves the scene without history: set `next` is half a step ahead of the reference.
     T.valid = false;
@@ -577,6 +689,22 @@ int rtHipSceneTemporalReset(rtHipScene *sc)
     if (!sc) return fail("temporal: null scene");
     sc->temporal.valid = false;
     return 0;
+}
+
+int rtHipSceneSetTemporalClamp(rtHipScene *sc, const rtHipTemporalClampParams *clamp)
+{
+    if (!sc) return fail("temporal clamp: null scene");
+    if (clamp && rtHipTemporalClampCheck(clamp) != 0) return -1;
+    sc->temporal.clampOn = clamp != nullptr;
+    sc->temporal.clamp = clamp ? *clamp : rtHipTemporalClampParams{};
+    return 0;
+}
+
+int rtHipSceneGetTemporalClamp(const rtHipScene *sc, rtHipTemporalClampParams *out)
+{
+    if (!sc || !out) return fail("null argument");
+    *out = sc->temporal.clamp; // (zeroed while off)
+    return sc->temporal.clampOn ? 1 : 0;
 }
 
 int rtHipSceneTemporalTimes(const rtHipScene *sc, cl_float *ms)

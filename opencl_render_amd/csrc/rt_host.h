@@ -263,6 +263,8 @@ struct rtHipScene {
         bool valid = false, momentsValid = false;
         rthost::Event ev[5];
         float ms[4] = {};
+        bool clampOn = false; // rtHipSceneSetTemporalClamp: the accumulation step runs the clamped kernel with `clamp`
+        rtHipTemporalClampParams clamp = {};
     } temporal;
     // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
     // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read

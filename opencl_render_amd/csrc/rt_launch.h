@@ -88,6 +88,11 @@ hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float *colour, co
                                  const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
                                  const uint32_t *histTriangle, float *outColour, float *outCount, float maxHistory,
                                  float depthTolerance, hipStream_t stream);
+hipError_t rtt_launch_accumulate_clamp(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
+                                       const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,
+                                       const uint32_t *histTriangle, const float *histMoments, float *outColour, float *outCount,
+                                       float *outMoments, float *outVariance, float maxHistory, float depthTolerance, uint32_t mode,
+                                       float gamma, hipStream_t stream);
 hipError_t rtt_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount,
                              const uint16_t *tileBuf, float *colour, hipStream_t stream);
 hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);

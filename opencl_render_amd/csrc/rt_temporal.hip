@@ -7,6 +7,9 @@
 //                          rtd_gather_kernel without the surface sums, for scenes that have no surface passes on
 //   rtt_accumulate_kernel  one lane per pixel, a wave is one 8x8 block of the screen (a workgroup is four of them side by side), so under
 //                          a smooth flow the four taps of neighbouring lanes fall into the same cache lines; no LDS: the flow is arbitrary
+//   rtt_clamp_kernel       "TEMPORAL CLAMP": the same mapping with the frame's 3x3 colour boxes taken from a 34 x 10 tile in LDS, with or
+//                          without the luminance moments (rt_temporal_clamp_pixel.h); issued in place of rtt_accumulate_kernel or
+//                          rtv_moments_kernel when a clamp is asked for
 //   rtt_quantise_kernel    scene path only: W x H x 3 f32 -> the quantised u16 planes, as rtd_output_kernel writes them
 // Nothing here may change a bit: no fast math, no reciprocal-multiply, no contraction (the Makefile's exactness flags apply).
 #include <hip/hip_runtime.h>
@@ -14,6 +17,7 @@
 #include <stdint.h>
 
 #include "rt_launch.h"
+#include "rt_temporal_clamp_pixel.h"
 #include "rt_temporal_pixel.h"
 
 namespace {
@@ -25,6 +29,36 @@ __global__ __launch_bounds__(256) void rtt_accumulate_kernel(const RttArgs A)
     const uint32_t x = bx * 32u + wave * 8u + (in & 7u), y = by * 8u + (in >> 3);
     if (x >= A.W || y >= A.H) return;
     rtt_pixel(A, x, y);
+}
+
+// The clamped accumulation ("TEMPORAL CLAMP"): rtt_accumulate_kernel's mapping, and the frame's colour of the 34 x 10 texels the
+// workgroup's 3x3 boxes reach staged in LDS, planar per channel.  The load walks the tile's rows as the 102 consecutive floats they
+// are in memory; a texel outside the image is not loaded and never read (rtc_box skips its tap by the same coordinate test).  Row stride
+// 40 floats: a ds_read_b32 is served per 32-lane half, which is 4 rows x 8 columns of a wave's 8x8 block -- words 40 r + c + const, banks
+// 8 r + c + const, all 32 distinct for every (dx, dy).  Plane stride 405 = 21 mod 32: the 32 consecutive floats a half-wave stores are
+// 10 or 11 texels x 3 channels and land on banks t, t + 21, t + 10.  4860 bytes, so the LDS does not limit the occupancy.
+// Lanes past the image's edge help to load and reach the barrier; only the pixel's own work is skipped.  History taps stay global loads.
+constexpr int RTC_TILE_W = 34, RTC_TILE_H = 10, RTC_ROW = 40, RTC_PLANE = RTC_TILE_H * RTC_ROW + 5;
+
+template <bool Moments>
+__global__ __launch_bounds__(256) void rtt_clamp_kernel(const RtcArgs A)
+{
+    __shared__ float tile[3 * RTC_PLANE];
+    const uint32_t bx = blockIdx.x % A.blocksX, by = blockIdx.x / A.blocksX;
+    const int tx0 = (int)(bx * 32u) - 1, ty0 = (int)(by * 8u) - 1; // the tile's top-left texel
+    for (int i = threadIdx.x; i < RTC_TILE_H * RTC_TILE_W * 3; i += 256) {
+        const int r = i / (RTC_TILE_W * 3), e = i % (RTC_TILE_W * 3), t = e / 3, ch = e % 3;
+        const int qx = tx0 + t, qy = ty0 + r;
+        if (qx >= 0 && qx < (int)A.W && qy >= 0 && qy < (int)A.H)
+            tile[ch * RTC_PLANE + r * RTC_ROW + t] = A.colour[((size_t)qy * A.W + (size_t)qx) * 3 + ch];
+    }
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6, in = threadIdx.x & 63u;
+    const uint32_t lx = wave * 8u + (in & 7u), ly = in >> 3;
+    const uint32_t x = bx * 32u + lx, y = by * 8u + ly;
+    if (x >= A.W || y >= A.H) return; // (after the barrier)
+    const float *centre = tile + (ly + 1u) * RTC_ROW + lx + 1u;
+    rtc_pixel<Moments>(A, x, y, [&](int dx, int dy, int ch) { return centre[ch * RTC_PLANE + dy * RTC_ROW + dx]; });
 }
 
 // One thread per pixel slot of the instance's tiles (tile-major, like tileBuf); slots past the image's edge write nothing.  tileIds were
@@ -73,6 +107,29 @@ extern "C" hipError_t rtt_launch_accumulate(uint32_t W, uint32_t H, const float 
     A.histColour = histColour; A.histCount = histCount; A.histT = histT; A.histTriangle = histTriangle;
     A.outColour = outColour; A.outCount = outCount;
     hipLaunchKernelGGL(rtt_accumulate_kernel, dim3(A.blocksX * ((H + 7u) / 8u)), dim3(256), 0, stream, A);
+    return hipGetLastError();
+}
+
+// The clamped accumulation; mode and gamma were checked too.  histMoments null: colour and count alone (outMoments and outVariance are
+// not written); given: the moments ride along, outMoments is needed and outVariance may be null.
+extern "C" hipError_t rtt_launch_accumulate_clamp(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
+                                                  const uint32_t *triangle, const float *histColour, const float *histCount,
+                                                  const float *histT, const uint32_t *histTriangle, const float *histMoments,
+                                                  float *outColour, float *outCount, float *outMoments, float *outVariance, float maxHistory,
+                                                  float depthTolerance, uint32_t mode, float gamma, hipStream_t stream)
+{
+    RtcArgs A;
+    A.W = W; A.H = H; A.blocksX = (W + 31u) / 32u;
+    A.mode = mode; A.gamma = gamma;
+    A.maxHistory = maxHistory; A.depthTolerance = depthTolerance;
+    A.colour = colour; A.motion = motion; A.prevT = prevT; A.triangle = triangle;
+    A.histColour = histColour; A.histCount = histCount; A.histT = histT; A.histTriangle = histTriangle; A.histMoments = histMoments;
+    A.outColour = outColour; A.outCount = outCount; A.outMoments = outMoments; A.outVariance = outVariance;
+    const dim3 grid(A.blocksX * ((H + 7u) / 8u));
+    if (histMoments)
+        hipLaunchKernelGGL(rtt_clamp_kernel<true>, grid, dim3(256), 0, stream, A);
+    else
+        hipLaunchKernelGGL(rtt_clamp_kernel<false>, grid, dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 

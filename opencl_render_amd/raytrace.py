@@ -84,6 +84,15 @@ VARIANCE_DEFAULTS = dict(iterations=4, luminance_sigma2=4.0, variance_floor=1e-8
                          spatial_below=4.0)
 
 
+class TemporalClampParams(C.Structure):  # rtHipTemporalClampParams
+    _fields_ = [("mode", C.c_uint32), ("gamma", C.c_float)]
+
+
+# rtHipTemporalClampDefaults (include/raytrace_hip.h, "TEMPORAL CLAMP"); the modes by name, as the command line takes them
+TEMPORAL_CLAMP_DEFAULTS = dict(mode=3, gamma=1.0)
+TEMPORAL_CLAMP_MODES = dict(minmax=1, variance=2, both=3)
+
+
 class AoParams(C.Structure):  # rtHipAoParams
     _fields_ = [("raysPerHit", C.c_uint32), ("pixelSamples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -169,6 +178,8 @@ RESIDENT_SYMBOLS = [
     "rtHipTemporalDefaults", "rtHipTemporalDevice", "rtHipTemporal", "rtHipSceneTemporal", "rtHipSceneTemporalReset", "rtHipSceneTemporalTimes",
     "rtHipVarianceDefaults", "rtHipTemporalMomentsDevice", "rtHipTemporalMoments", "rtHipVarianceScratchBytes", "rtHipDenoiseVarianceDevice",
     "rtHipDenoiseVariance", "rtHipSceneTemporalVariance",
+    "rtHipTemporalClampDefaults", "rtHipTemporalClampCheck", "rtHipTemporalClampDevice", "rtHipTemporalClamp", "rtHipTemporalMomentsClampDevice",
+    "rtHipTemporalMomentsClamp", "rtHipSceneSetTemporalClamp", "rtHipSceneGetTemporalClamp",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestRoundVisits", "rtHipTestShadeLog", "rtHipTestBuildLog",
@@ -320,6 +331,16 @@ def lib() -> C.CDLL:
     L.rtHipDenoiseVarianceDevice.argtypes = [C.c_int, u32, u32] + [vp] * 8 + [C.c_uint64, C.POINTER(VarianceParams), vp]
     L.rtHipDenoiseVariance.argtypes = [C.c_int, u32, u32] + [vp] * 7 + [C.POINTER(VarianceParams)]
     L.rtHipSceneTemporalVariance.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(VarianceParams), vp, vp, vp, vp, vp, vp]
+    clamp = C.POINTER(TemporalClampParams)
+    L.rtHipTemporalClampDefaults.restype = None
+    L.rtHipTemporalClampDefaults.argtypes = [clamp]
+    L.rtHipTemporalClampCheck.argtypes = [clamp]
+    L.rtHipTemporalClampDevice.argtypes = [C.c_int, u32, u32] + [vp] * 10 + [C.POINTER(TemporalParams), clamp, vp]
+    L.rtHipTemporalClamp.argtypes = [C.c_int, u32, u32] + [vp] * 10 + [C.POINTER(TemporalParams), clamp]
+    L.rtHipTemporalMomentsClampDevice.argtypes = [C.c_int, u32, u32] + [vp] * 13 + [C.POINTER(TemporalParams), clamp, vp]
+    L.rtHipTemporalMomentsClamp.argtypes = [C.c_int, u32, u32] + [vp] * 13 + [C.POINTER(TemporalParams), clamp]
+    L.rtHipSceneSetTemporalClamp.argtypes = [vp, clamp]
+    L.rtHipSceneGetTemporalClamp.argtypes = [vp, clamp]
     L.rtHipBakeDefaults.restype = None
     L.rtHipBakeDefaults.argtypes = [C.POINTER(BakeParams)]
     L.rtHipSceneBakeAmbientOcclusion.argtypes = [vp, C.POINTER(BakeParams), vp, vp]
@@ -604,20 +625,34 @@ def temporal_params(max_history=TEMPORAL_DEFAULTS["max_history"], depth_toleranc
     return TemporalParams(float(max_history), float(depth_tolerance))
 
 
+def temporal_clamp_params(mode=TEMPORAL_CLAMP_DEFAULTS["mode"], gamma=TEMPORAL_CLAMP_DEFAULTS["gamma"]) -> TemporalClampParams:
+    """rtHipTemporalClampParams from the Python keywords; mode 1, 2, 3 or a name of TEMPORAL_CLAMP_MODES (the library checks the values)."""
+    mode = TEMPORAL_CLAMP_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(mode, str) or not 0 <= int(mode) <= 0xFFFFFFFF:  # (ctypes would wrap it into the uint32 field)
+        raise ValueError(f"temporal clamp: mode must be 1, 2, 3 or one of {sorted(TEMPORAL_CLAMP_MODES)} (got {mode!r})")
+    return TemporalClampParams(int(mode), float(gamma))
+
+
 _TEMPORAL_INPUTS = (("colour", 3, False), ("motion", 2, False), ("prev_t", 1, False), ("triangle", 1, True))
 _TEMPORAL_HISTORY = (("colour", 3, False), ("count", 1, False), ("t", 1, False), ("triangle", 1, True))
 
 
 def temporal(colour, motion, prev_t, triangle, history, max_history=TEMPORAL_DEFAULTS["max_history"],
-             depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"], out: Optional[dict] = None, device: int = 0, stream: int = 0) -> dict:
+             depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"], out: Optional[dict] = None, device: int = 0, stream: int = 0,
+             clamp: Optional[dict] = None) -> dict:
     """The temporal accumulation of include/raytrace_hip.h ("TEMPORAL ACCUMULATION"): the frame `colour` [H, W, 3] f32 with its flow --
     `motion` [H, W, 2] f32, `prev_t` [H, W] f32, `triangle` [H, W] u32, what ResidentScene.motion() gives -- against `history`, a dict
     with "colour" [H, W, 3] f32, "count" [H, W] f32 (0: none), "t" [H, W] f32 and "triangle" [H, W] u32: the previous call's outputs and
     the previous frame's t and triangle maps.  Returns {"colour": [H, W, 3] f32, "count": [H, W] f32}.  numpy arrays go through
     rtHipTemporal (host arrays, synchronous); torch tensors on cuda:`device` (triangle ids uint32 or int32, their bits) stay there and go
     through rtHipTemporalDevice on torch's current stream (or `stream`).  `out`: a dict with "colour" and, optionally, "count" to fill
-    instead of new arrays (they must not overlap an input); without "count" the counts are not written."""
+    instead of new arrays (they must not overlap an input); without "count" the counts are not written.  `clamp`: a dict with "mode"
+    and "gamma" ({} for the defaults) pulls the history colour into the frame's 3x3 colour box before the blend (include/raytrace_hip.h,
+    "TEMPORAL CLAMP"; rtHipTemporalClamp / rtHipTemporalClampDevice); None: no clamp."""
     p = temporal_params(max_history, depth_tolerance)
+    cp = temporal_clamp_params(**clamp) if clamp is not None else None
+    tail = (C.byref(p),) if cp is None else (C.byref(p), C.byref(cp))
+    host, dev = ("rtHipTemporal", "rtHipTemporalDevice") if cp is None else ("rtHipTemporalClamp", "rtHipTemporalClampDevice")
     missing = [k for k, _, _ in _TEMPORAL_HISTORY if k not in history]
     if missing:
         raise ValueError(f"temporal: history lacks {missing}")
@@ -636,11 +671,11 @@ def temporal(colour, motion, prev_t, triangle, history, max_history=TEMPORAL_DEF
         A.check(f"out[{name!r}]", v, shape + (3,) if name == "colour" else shape)
     ptrs = [A.address(v) for _, v, _, _ in given] + [A.address(res["colour"]), A.address(res.get("count"))]
     if not A.on_gpu:
-        if lib().rtHipTemporal(device, shape[1], shape[0], *ptrs, C.byref(p)) != 0:
-            raise RuntimeError("rtHipTemporal failed: " + last_error())
+        if getattr(lib(), host)(device, shape[1], shape[0], *ptrs, *tail) != 0:
+            raise RuntimeError(host + " failed: " + last_error())
         return res
-    if lib().rtHipTemporalDevice(device, shape[1], shape[0], *ptrs, C.byref(p), A.stream_arg()) != 0:
-        raise RuntimeError("rtHipTemporalDevice failed: " + last_error())
+    if getattr(lib(), dev)(device, shape[1], shape[0], *ptrs, *tail, A.stream_arg()) != 0:
+        raise RuntimeError(dev + " failed: " + last_error())
     A.done([v for _, v, _, _ in given] + list(res.values()))
     return res
 
@@ -706,12 +741,18 @@ _MOMENTS_HISTORY = _TEMPORAL_HISTORY + (("moments", 2, False),)
 
 
 def temporal_moments(colour, motion, prev_t, triangle, history, max_history=TEMPORAL_DEFAULTS["max_history"],
-                     depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"], device: int = 0, stream: int = 0) -> dict:
+                     depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"], device: int = 0, stream: int = 0,
+                     clamp: Optional[dict] = None) -> dict:
     """raytrace.temporal with the luminance moments carried along (include/raytrace_hip.h, "VARIANCE-GUIDED FILTER", (a)): `history` also
     holds "moments" [H, W, 2] f32.  Returns {"colour", "count", "moments" [H, W, 2] f32, "variance" [H, W] f32}; colour and count equal
     raytrace.temporal's.  numpy arrays go through rtHipTemporalMoments; torch tensors on cuda:`device` stay there and go through
-    rtHipTemporalMomentsDevice on torch's current stream (or `stream`)."""
+    rtHipTemporalMomentsDevice on torch's current stream (or `stream`).  `clamp`: as raytrace.temporal's (rtHipTemporalMomentsClamp /
+    rtHipTemporalMomentsClampDevice); the moments are not clamped."""
     p = temporal_params(max_history, depth_tolerance)
+    cp = temporal_clamp_params(**clamp) if clamp is not None else None
+    tail = (C.byref(p),) if cp is None else (C.byref(p), C.byref(cp))
+    host, dev = (("rtHipTemporalMoments", "rtHipTemporalMomentsDevice") if cp is None else
+                 ("rtHipTemporalMomentsClamp", "rtHipTemporalMomentsClampDevice"))
     missing = [k for k, _, _ in _MOMENTS_HISTORY if k not in history]
     if missing:
         raise ValueError(f"temporal_moments: history lacks {missing}")
@@ -726,11 +767,11 @@ def temporal_moments(colour, motion, prev_t, triangle, history, max_history=TEMP
     res = {"colour": A.new(shape + (3,)), "count": A.new(shape), "moments": A.new(shape + (2,)), "variance": A.new(shape)}
     ptrs = [A.address(v) for _, v, _, _ in given] + [A.address(res[k]) for k in ("colour", "count", "moments", "variance")]
     if not A.on_gpu:
-        if lib().rtHipTemporalMoments(device, shape[1], shape[0], *ptrs, C.byref(p)) != 0:
-            raise RuntimeError("rtHipTemporalMoments failed: " + last_error())
+        if getattr(lib(), host)(device, shape[1], shape[0], *ptrs, *tail) != 0:
+            raise RuntimeError(host + " failed: " + last_error())
         return res
-    if lib().rtHipTemporalMomentsDevice(device, shape[1], shape[0], *ptrs, C.byref(p), A.stream_arg()) != 0:
-        raise RuntimeError("rtHipTemporalMomentsDevice failed: " + last_error())
+    if getattr(lib(), dev)(device, shape[1], shape[0], *ptrs, *tail, A.stream_arg()) != 0:
+        raise RuntimeError(dev + " failed: " + last_error())
     A.done([v for _, v, _, _ in given] + list(res.values()))
     return res
 
@@ -1525,6 +1566,22 @@ class ResidentScene:
                                                      _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), _ptr(count), _ptr(variance)),
                     "rtHipSceneTemporalVariance")
         return {"colour": colour, "planes": planes, "count": count, "variance": variance}
+
+    def set_temporal_clamp(self, mode=TEMPORAL_CLAMP_DEFAULTS["mode"], gamma=TEMPORAL_CLAMP_DEFAULTS["gamma"]) -> None:
+        """Turns the scene's temporal clamp on (rtHipSceneSetTemporalClamp; include/raytrace_hip.h, "TEMPORAL CLAMP"): from now on
+        temporal() and temporal_variance() pull the reprojected history into the frame's 3x3 colour box before the blend, so that a
+        set_lights or set_materials shows in one frame instead of fading in over max_history frames.  mode 1 / "minmax", 2 / "variance" or
+        3 / "both"; set_temporal_clamp(None) turns it off (the default).  History, mark and buffers are not touched."""
+        cp = temporal_clamp_params(mode, gamma) if mode is not None else None
+        self._check(lib().rtHipSceneSetTemporalClamp(self.handle, C.byref(cp) if cp is not None else None), "rtHipSceneSetTemporalClamp")
+
+    def temporal_clamp(self) -> Optional[dict]:
+        """The scene's temporal clamp (rtHipSceneGetTemporalClamp): {"mode", "gamma"}, or None while it is off."""
+        cp = TemporalClampParams()
+        on = lib().rtHipSceneGetTemporalClamp(self.handle, C.byref(cp))
+        if on < 0:
+            self._check(on, "rtHipSceneGetTemporalClamp")
+        return dict(mode=int(cp.mode), gamma=float(cp.gamma)) if on else None
 
     def reset_temporal(self) -> None:
         """Forgets the history of temporal() (rtHipSceneTemporalReset): the next call returns the frame itself with count 1."""
