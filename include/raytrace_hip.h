@@ -1019,6 +1019,92 @@ int  rtHipSceneSetTemporalClamp(rtHipScene *scene, const rtHipTemporalClampParam
 /* 1 and *out = the parameters if the scene's clamp is on, 0 and *out zeroed if it is off, -1 for a NULL argument. */
 int  rtHipSceneGetTemporalClamp(const rtHipScene *scene, rtHipTemporalClampParams *out);
 
+/* MOTION BLUR: the other consumer of the motion vectors, the "vector motion blur" post effect.  A frame is blurred along its flow after
+ * it was rendered: every pixel gathers `taps` samples along the dominant velocity of its neighbourhood, weighted by whether the sampled
+ * pixel's own streak, or this pixel's, reaches the other and by which of the two is in front (McGuire, Hennessy, Bukowski and Osman
+ * 2012, "A Reconstruction Filter for Plausible Motion Blur": the per-tile dominant velocity, its neighbourhood maximum, a depth-aware
+ * gather).  The frame kernels are not involved: the camera's candidate lists belong to one instant.  The arithmetic is IEEE fp32
+ * + - * /, sqrtf, fabsf and compares in the order written (no FMA, division and square root correctly rounded):
+ * tests/motion_blur_oracle.py restates it in numpy and the device output equals it bit for bit (up to the payload of a NaN).  Every bit
+ * pattern of the inputs has a defined answer up to the payload of a NaN, and no index is formed before its range test.
+ *
+ * All arrays are W x H, row-major; W, H and W*H limited as in TEMPORAL ACCUMULATION.  Inputs: colour 3 x f32; motion 2 x f32, exactly
+ * what rtHipSceneMotion writes (from the pixel to its previous position, in pixels); depth f32, the motion pass's t (+inf on a miss).
+ * Output: out 3 x f32; it must overlap no input (the taps belong to neighbours).
+ * Parameters: shutter finite in [0, 4] (the share of the frame interval the exposure covers, centred on the frame); maxBlur finite in
+ * [1, 32] pixels (the cap of a streak's half-extent); taps in [1, 64]; depthSoftness finite and >= 0 (relative).  Anything else returns
+ * -1 before anything is launched.
+ *   clamp01(r) = !(r > 0) ? 0 : (r > 1 ? 1 : r)                                                              (a NaN gives 0)
+ * (a) Velocity of pixel q:
+ *   s = shutter * 0.5f;  vx = motion.x * s;  vy = motion.y * s;  l2 = vx*vx + vy*vy
+ *   if (!(l2 < +inf)) { vx = vy = 0; l = 0; } else l = sqrtf(l2)
+ *   if (l > maxBlur) { k = maxBlur / l;  vx = vx * k;  vy = vy * k;  l = maxBlur; }
+ * (b) Tile maximum.  Tiles are 32 x 32 pixels, tile(x, y) = (x >> 5, y >> 5).  tileMax[T] starts as (0, 0, 0) and is replaced by a pixel's
+ *   (vx, vy, l) only when that pixel's l is strictly greater, the tile's pixels visited in row-major order: the greatest l, and among
+ *   equals the smallest index (which is how a parallel reduction states it, so that the answer does not depend on its order).
+ * (c) Neighbourhood maximum.  nbMax[T] likewise over the tiles (Tx + dx, Ty + dy) that exist, dy = -1..1 outer, dx = -1..1 inner, from
+ *   (0, 0, 0), a candidate replacing only when strictly greater.
+ * (d) Gather at p = (x, y), with (nx, ny, nl) = nbMax[tile(p)]:
+ *   if (!(nl >= 0.5f)): out = colour_p, a copy, bit for bit.  Otherwise:
+ *   lp = l_p < 0.5f ? 0.5f : l_p;  zp = depth_p;  wsum = 1.0f / lp;  sum = colour_p * wsum (per channel)
+ *   j = ((x & 1) * 2 + (y & 1) * 3) & 3;  jit = ((float)j - 1.5f) * 0.25f                (a fixed 2 x 2 dither: no random state)
+ *   for i = 0 .. taps-1:
+ *     u = (((float)i + 0.5f) + jit) / (float)taps;  sg = u * 2.0f - 1.0f
+ *     X = ((float)x + 0.5f) + nx * sg;  Y likewise with y and ny
+ *     the tap is skipped unless X >= 0 && X < (float)W && Y >= 0 && Y < (float)H; then q = ((int)X, (int)Y)
+ *     d = fabsf(sg) * nl;  lq = l_q < 0.5f ? 0.5f : l_q;  zq = depth_q;  e = depthSoftness * (zp < zq ? zp : zq)
+ *     sdc(a, b) = (a == b) ? 1.0f : clamp01(1.0f - (a - b) / e);   f = sdc(zq, zp)  (q lies in front of p);   bk = sdc(zp, zq)
+ *     cone(l) = clamp01(1.0f - d / l)
+ *     cyl(l) = 1.0f - sm(clamp01((d - 0.95f*l) / (1.05f*l - 0.95f*l))),  sm(r) = (r*r) * (3.0f - 2.0f*r)
+ *     w = (f * cone(lq) + bk * cone(lp)) + (cyl(lq) * cyl(lp)) * 2.0f
+ *     wsum += w;  sum += colour_q * w (per channel: a multiply, an add)
+ *   out = sum / wsum per channel
+ * The == arm lets two missed pixels (both at +inf) count as one layer, as TEMPORAL ACCUMULATION's == arm does.  A tap that lands on p
+ * itself is not special.  wsum starts positive and no weight is negative or a NaN, so out is a NaN only where a colour it sums is.
+ * Not done: samples distributed over the shutter inside the frame kernels, sub-pixel reprojection, tile-dealt instances (their taps
+ * cross tile borders: the array entry points take a composed image). */
+typedef struct rtHipMotionBlurParams {
+    cl_float shutter;       /* the exposure's share of the frame interval, centred on the frame */
+    cl_float maxBlur;       /* pixels: the longest half-extent of a streak */
+    cl_uint  taps;          /* samples along the streak */
+    cl_float depthSoftness; /* relative: the depth extent over which "in front" falls from 1 to 0 */
+} rtHipMotionBlurParams;
+/* shutter = 0.5, maxBlur = 16, taps = 15, depthSoftness = 0.05: defaults of a parameter, not measurements. */
+void rtHipMotionBlurDefaults(rtHipMotionBlurParams *params);
+/* 0 for legal parameters, -1 (the last-error text set) for NULL or a value outside the ranges above.  Needs no device. */
+int  rtHipMotionBlurCheck(const rtHipMotionBlurParams *params);
+/* Bytes of scratch rtHipMotionBlurDevice needs for a width x height image: (l, depth) per pixel, 8 bytes, rounded up to 16, then tileMax
+ * and nbMax at 16 bytes per 32 x 32 tile each.  0 for a size the filter refuses. */
+uint64_t rtHipMotionBlurScratchBytes(cl_uint width, cl_uint height);
+/* DEVICE arrays of `device`, asynchronous on `stream` (a hipStream_t of `device` as void*; NULL = the null stream): four launches, no
+ * allocation, no synchronisation.  scratch: at least rtHipMotionBlurScratchBytes(width, height) bytes, 16-byte aligned, contents
+ * irrelevant.  Pointer, overlap and stream checks are rtHipTemporalDevice's: out and scratch must overlap nothing.  Anything else returns
+ * -1 with the last-error text set and launches nothing. */
+int  rtHipMotionBlurDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *depth, void *out,
+                           void *scratch, uint64_t scratchBytes, const rtHipMotionBlurParams *params, void *stream);
+/* HOST arrays, synchronous; device memory is allocated and freed per call.  Same results as rtHipMotionBlurDevice. */
+int  rtHipMotionBlur(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *depth,
+                     cl_float *out, const rtHipMotionBlurParams *params);
+/* The scene's last frame, blurred on its device along the flow to the scene's motion reference.  The caller's loop is:
+ * rtHipSceneMotionMark, rtHipSceneSetCamera and / or rtHipSceneSetGeometry, render, rtHipSceneMotionBlur.  The call needs a tile set
+ * that holds every tile of the image once and a motion reference (without one: -1, "no motion reference"); it synchronises and finishes
+ * the frame like rtHipReadback, and then, on the scene's stream: runs the motion pass (motion and t) into storage of its own; gathers
+ * the colour ((float)u16 / 65535.0f of the beauty planes, what rtHipReadback gives); blurs; and quantises the planes as
+ * rtHipSceneDenoise's.  THE CALL DOES NOT MARK: the reference stays the caller's.  rtHipSceneTemporal marks again, so a caller who wants
+ * both on one frame blurs first and accumulates second (the accumulation then sees the unblurred frame and the same flow); or takes
+ * rtHipSceneMotion before the temporal call and feeds its outColour to rtHipMotionBlur / rtHipMotionBlurDevice.
+ * Outputs (each may be NULL, host arrays): outRgb W x H x 3 f32 and the u16 planes R, G, B.
+ * Storage, made on first use in one block, counted in rtHipSceneBytes from then on and freed with the scene (a scene that never calls
+ * holds none of it), with n = W*H and every part rounded up to 256 bytes: motion 8n, t 4n, the gathered colour 12n, the blurred image
+ * 12n, the planes 3 x 2n and rtHipMotionBlurScratchBytes.
+ * Refused with -1, the last-error text set and nothing launched: a NULL scene or params, parameters out of range, an image wider or
+ * higher than 16384 or of more than 2^27 pixels, a tile subset, no motion reference, a reference made for another triangle count. */
+int  rtHipSceneMotionBlur(rtHipScene *scene, const rtHipMotionBlurParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG,
+                          cl_ushort *outB);
+/* Device time in milliseconds of the scene's last rtHipSceneMotionBlur call, from HIP events on the scene's stream: ms[0] the motion pass,
+ * ms[1] the colour gather, ms[2] the blur and the output kernel.  All 0 before the first call.  Returns 0, or -1 for a NULL argument. */
+int  rtHipSceneMotionBlurTimes(const rtHipScene *scene, cl_float ms[3]);
+
 /* AMBIENT OCCLUSION BAKE: a W x H texture of ambient occlusion over the scene's UV layout.  Each texel centre is mapped to the surface
  * point of the triangle whose UV triangle covers it, and the AO rays of the block above are traced from there with the same walk.  It
  * needs geometry, UVs, corner normals and the grid only: it works on every instance (whatever its tiles, passes or pipeline), ignores

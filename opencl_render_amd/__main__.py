@@ -34,6 +34,11 @@ standard deviations wide; ``--temporal-clamp-mode minmax|variance|both`` (defaul
 shows what it is for: without the clamp the old lighting fades out over the history's length, with it the accumulation follows the
 light at once.
 
+``--motion-blur PATH`` (with ``--orbit N`` or ``--spin N``) also writes every frame blurred along its motion vectors to the frame before
+it (include/raytrace_hip.h, "MOTION BLUR"; ResidentScene.motion_blur) to PATH_000 .. PATH_{N-1}: .bmp, .ppm or .pfm; frame 0 is written
+unblurred.  ``--shutter S``, ``--max-blur PX`` and ``--blur-taps N`` set its parameters.  Beside ``--temporal`` the blur runs first:
+the accumulation marks the scene again.
+
 ``--relight N`` renders N frames of the one resident scene with its first light turned about the vertical axis between them
 (include/raytrace_hip.h, "SCENE EDITS: LIGHTS AND MATERIALS"; ResidentScene.set_lights): img_000 .. img_{N-1}, with ``--passes`` /
 ``--denoise`` / ``--ao`` numbered alike.
@@ -121,6 +126,15 @@ def parser():
                     help="with --orbit N or --spin N: also write every frame accumulated over the frames before it (ResidentScene.temporal: "
                          "the history reprojected along the motion vectors, default parameters) to PATH numbered like --out: .bmp, .ppm or "
                          ".pfm.  With --denoise the denoiser runs on the accumulation before it is written (the history stays unfiltered)")
+    ap.add_argument("--motion-blur", metavar="PATH",
+                    help="with --orbit N or --spin N: also write every frame blurred along its motion vectors to the frame before it "
+                         "(ResidentScene.motion_blur) to PATH numbered like --out: .bmp, .ppm or .pfm.  Frame 0 has no frame before it and is "
+                         "written unblurred")
+    ap.add_argument("--shutter", type=float, default=None, metavar="S",
+                    help="with --motion-blur: the share of the frame interval the exposure covers, 0..4 (default 0.5)")
+    ap.add_argument("--max-blur", type=float, default=None, metavar="PX",
+                    help="with --motion-blur: the longest half-extent of a streak in pixels, 1..32 (default 16)")
+    ap.add_argument("--blur-taps", type=int, default=None, metavar="N", help="with --motion-blur: samples along a streak, 1..64 (default 15)")
     ap.add_argument("--temporal-clamp", type=float, nargs="?", const=1.0, default=None, metavar="GAMMA",
                     help="with --temporal PATH: clamp the reprojected history to the colour box of the frame's 3x3 neighbourhood before the "
                          "blend (ResidentScene.set_temporal_clamp); GAMMA (default 1) is the variance box's half-width in standard deviations")
@@ -181,6 +195,18 @@ def parse_args(argv=None):
         ap.error("--motion PREFIX needs --orbit N or --spin N with N >= 2 (the frames it is measured between)")
     if args.temporal and args.orbit < 2 and args.spin < 2 and args.relight < 2:
         ap.error("--temporal PATH needs --orbit N, --spin N or --relight N with N >= 2 (the frames it accumulates)")
+    if args.motion_blur and args.orbit < 2 and args.spin < 2:
+        ap.error("--motion-blur PATH needs --orbit N or --spin N with N >= 2 (the frames whose flow it blurs along)")
+    if args.motion_blur and not args.motion_blur.lower().endswith((".bmp", ".ppm", ".pfm")):
+        ap.error("--motion-blur PATH must end in .bmp, .ppm or .pfm")
+    if (args.shutter is not None or args.max_blur is not None or args.blur_taps is not None) and not args.motion_blur:
+        ap.error("--shutter, --max-blur and --blur-taps need --motion-blur PATH")
+    if args.shutter is not None and not 0 <= args.shutter <= 4:
+        ap.error("--shutter S needs S in 0..4")
+    if args.max_blur is not None and not 1 <= args.max_blur <= 32:
+        ap.error("--max-blur PX needs PX in 1..32")
+    if args.blur_taps is not None and not 1 <= args.blur_taps <= 64:
+        ap.error("--blur-taps N needs N in 1..64")
     if args.temporal_clamp is not None and not args.temporal:
         ap.error("--temporal-clamp needs --temporal PATH")
     if args.temporal_clamp is not None and not (np.isfinite(args.temporal_clamp) and args.temporal_clamp >= 0):
@@ -366,6 +392,30 @@ def write_motion(rs, args, index: int) -> None:
         rs.mark_motion()
 
 
+def write_motion_blur(rs, args, index: int, planes) -> None:
+    """--motion-blur: frame `index` blurred along its flow to the marked state (the frame before it) -> PATH numbered like --out.  Frame
+    0 has no frame before it: it is written as it is (`planes`, the read-back).  Called before write_motion and write_temporal, which
+    mark the scene for the next frame; without them the mark is made here (ResidentScene.motion_blur does not mark)."""
+    if not args.motion_blur:
+        return
+    from . import frontend, raytrace
+    if index == 0:
+        rs.mark_motion()
+        res = dict(rgb=np.stack(planes, -1).astype(np.float32) / np.float32(65535.0), planes=planes)
+    else:
+        params = dict(shutter=args.shutter, max_blur=args.max_blur, taps=args.blur_taps)
+        res = rs.motion_blur(**{k: v for k, v in params.items() if v is not None})
+    if index and not (args.motion or args.temporal):
+        rs.mark_motion()
+    path = raytrace.orbit_path(args.motion_blur, index)
+    if path.lower().endswith(".pfm"):
+        frontend.write_pfm_rgb(path, res["rgb"])
+    elif path.lower().endswith(".ppm"):
+        frontend.write_ppm(path, *res["planes"])
+    else:
+        frontend.write_bmp(path, *res["planes"], low_byte_compat=args.low_byte_compat)
+
+
 def write_temporal(rs, args, index: int) -> None:
     """--temporal: frame `index` accumulated over the frames before it -> PATH numbered like --out; with --denoise or --variance-guided,
     filtered; --variance: its variance too.  --temporal-clamp: under the scene's clamp, set before frame 0."""
@@ -435,6 +485,7 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_motion_blur(rs, args, i, planes)
             write_motion(rs, args, i)
             write_temporal(rs, args, i)
     finally:
@@ -472,6 +523,7 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_motion_blur(rs, args, i, planes)
             write_motion(rs, args, i)
             write_temporal(rs, args, i)
     finally:

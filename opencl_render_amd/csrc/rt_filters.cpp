@@ -1,6 +1,6 @@
 // rt_filters.cpp -- the image-space filters of libraytrace_hip.so (include/raytrace_hip.h: "DENOISER", "TEMPORAL ACCUMULATION",
-// "VARIANCE-GUIDED FILTER", "TEMPORAL CLAMP"): parameter checks, the device and host entry points, and the resident scene's calls with their buffers.
-// The kernels are in rt_denoise.hip, rt_temporal.hip and rt_variance.hip; the scene and what else the host side shares, in rt_host.h.
+// "VARIANCE-GUIDED FILTER", "TEMPORAL CLAMP", "MOTION BLUR"): parameter checks, the device and host entry points, and the resident scene's calls with their buffers.
+// The kernels are in rt_denoise.hip, rt_temporal.hip, rt_variance.hip and rt_motion_blur.hip; the scene and what else the host side shares, in rt_host.h.
 #include "rt_host.h"
 #include "rt_launch.h"
 #include "rt_overlap.h"
@@ -711,5 +711,142 @@ int rtHipSceneTemporalTimes(const rtHipScene *sc, cl_float *ms)
 {
     if (!sc || !ms) return fail("null argument");
     for (int i = 0; i < 4; ++i) ms[i] = sc->temporal.ms[i];
+    return 0;
+}
+
+// ---- motion blur (include/raytrace_hip.h, "MOTION BLUR"; kernels in rt_motion_blur.hip) ---------------------------------------------
+// Filter scratch of a W x H image: lz = (l, depth) per pixel as 2 f32, rounded up to 16 bytes, then tileMax and nbMax as float4 per
+// 32 x 32 tile.
+void rtHipMotionBlurDefaults(rtHipMotionBlurParams *p)
+{
+    if (!p) return;
+    p->shutter = 0.5f;
+    p->maxBlur = 16.0f;
+    p->taps = 15;
+    p->depthSoftness = 0.05f;
+}
+
+int rtHipMotionBlurCheck(const rtHipMotionBlurParams *p)
+{
+    if (!p) return fail("motion blur: null parameters");
+    if (!(std::isfinite(p->shutter) && p->shutter >= 0.f && p->shutter <= 4.0f))
+        return fail("motion blur: shutter %g is not finite and in 0..4", (double)p->shutter);
+    if (!(std::isfinite(p->maxBlur) && p->maxBlur >= 1.0f && p->maxBlur <= 32.0f))
+        return fail("motion blur: maxBlur %g is not finite and in 1..32", (double)p->maxBlur);
+    if (p->taps < 1 || p->taps > 64) return fail("motion blur: taps %u is not in 1..64", p->taps);
+    if (!(std::isfinite(p->depthSoftness) && p->depthSoftness >= 0.f))
+        return fail("motion blur: depthSoftness %g is not finite and >= 0", (double)p->depthSoftness);
+    return 0;
+}
+
+static bool motion_blur_size_legal(uint32_t W, uint32_t H)
+{
+    return W != 0 && H != 0 && W <= RT_TEMPORAL_MAX_SIDE && H <= RT_TEMPORAL_MAX_SIDE && (uint64_t)W * H <= RT_DENOISE_MAX_PIXELS;
+}
+
+static int motion_blur_size_ok(uint32_t W, uint32_t H)
+{
+    if (!motion_blur_size_legal(W, H))
+        return fail("motion blur: a %u x %u image is not 1..16384 pixels wide and high and 1..2^27 pixels", W, H);
+    return 0;
+}
+
+static uint64_t motion_blur_tiles(uint32_t W, uint32_t H) { return (uint64_t)((W + 31u) / 32u) * ((H + 31u) / 32u); }
+static uint64_t motion_blur_lz_bytes(uint32_t W, uint32_t H) { return ((uint64_t)W * H * 8 + 15) & ~15ull; }
+
+uint64_t rtHipMotionBlurScratchBytes(cl_uint width, cl_uint height)
+{
+    if (!motion_blur_size_legal(width, height)) return 0;
+    return motion_blur_lz_bytes(width, height) + 2 * motion_blur_tiles(width, height) * 16;
+}
+
+// Issues the filter on `st`; arguments were checked by the caller.
+static int motion_blur_issue(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *depth, float *out, char *scratch,
+                             const rtHipMotionBlurParams *p, hipStream_t st)
+{
+    char *tileMax = scratch + motion_blur_lz_bytes(W, H), *nbMax = tileMax + motion_blur_tiles(W, H) * 16;
+    HIP_OK(rmb_launch(W, H, colour, motion, depth, out, (float *)scratch, (float *)tileMax, (float *)nbMax, p->shutter, p->maxBlur, p->taps,
+                      p->depthSoftness, st));
+    return 0;
+}
+
+int rtHipMotionBlurDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *motion, const void *depth, void *out,
+                          void *scratch, uint64_t scratchBytes, const rtHipMotionBlurParams *params, void *stream)
+{
+    if (rtHipMotionBlurCheck(params) != 0 || motion_blur_size_ok(width, height) != 0) return -1;
+    if (!colour || !motion || !depth || !out || !scratch) return fail("motion blur: null array");
+    const uint64_t n = (uint64_t)width * height, need = rtHipMotionBlurScratchBytes(width, height);
+    if (scratchBytes < need)
+        return fail("motion blur: scratch of %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)need);
+    const RtArray arr[5] = { { colour, n * 12, 4, "colour" }, { motion, n * 8, 4, "motion" }, { depth, n * 4, 4, "depth" },
+                             { out, n * 12, 4, "out", true }, { scratch, need, 16, "scratch", true } };
+    if (checked_device_arrays("motion blur", device, stream, arr, 5) != 0) return -1;
+    return motion_blur_issue(width, height, (const float *)colour, (const float *)motion, (const float *)depth, (float *)out, (char *)scratch,
+                             params, (hipStream_t)stream);
+}
+
+int rtHipMotionBlur(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *motion, const cl_float *depth,
+                    cl_float *out, const rtHipMotionBlurParams *params)
+{
+    if (rtHipMotionBlurCheck(params) != 0 || motion_blur_size_ok(width, height) != 0) return -1;
+    if (!colour || !motion || !depth || !out) return fail("motion blur: null array");
+    HIP_OK(hipSetDevice(device));
+    const size_t n = (size_t)width * height;
+    HostStage dev;
+    const float *c = dev.up(colour, n * 12), *m = dev.up(motion, n * 8), *z = dev.up(depth, n * 4);
+    float *dout = dev.out<float>(n * 12);
+    char *scratch = dev.out<char>(rtHipMotionBlurScratchBytes(width, height));
+    if (dev.status != hipSuccess) return dev.failed();
+    if (motion_blur_issue(width, height, c, m, z, dout, scratch, params, nullptr) != 0) return -1;
+    HIP_OK(hipMemcpy(out, dout, n * 12, hipMemcpyDeviceToHost));
+    HIP_OK(hipDeviceSynchronize());
+    return 0;
+}
+
+int rtHipSceneMotionBlur(rtHipScene *sc, const rtHipMotionBlurParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG,
+                         cl_ushort *outB)
+{
+    if (!sc) return fail("motion blur: null scene");
+    if (rtHipMotionBlurCheck(params) != 0 || motion_blur_size_ok(sc->width, sc->height) != 0) return -1;
+    if (whole_image_tiles(sc, "motion blur") != 0) return -1;
+    if (!sc->motion.have) return fail("motion blur: no motion reference (rtHipSceneMotionMark)");
+    if (sc->dev.triangleCount != sc->motion.triangles)
+        return fail("motion blur: the scene has %u triangles, the motion reference was made for %u", sc->dev.triangleCount, sc->motion.triangles);
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    rtHipScene::MotionBlur &B = sc->motionBlur;
+    const uint32_t W = sc->width, H = sc->height;
+    const size_t n = (size_t)W * H;
+    const auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    if (!B.buf) { // motion | t | colour | out | R | G | B | scratch
+        const uint64_t bytes = part(n * 8) + part(n * 4) + 2 * part(n * 12) + 3 * part(n * 2) + part(rtHipMotionBlurScratchBytes(W, H));
+        if (scene_block(sc, B.buf, bytes, "motion blur") != 0) return -1;
+    }
+    for (Event &e : B.ev) HIP_OK(e.make());
+    char *b = B.buf;
+    float *motion = (float *)b, *t = (float *)(b + part(n * 8)), *colour = (float *)(b + part(n * 8) + part(n * 4));
+    float *out = (float *)((char *)colour + part(n * 12));
+    char *plane = (char *)out + part(n * 12);
+    const Planes planes = { (uint16_t *)plane, (uint16_t *)(plane + part(n * 2)), (uint16_t *)(plane + 2 * part(n * 2)) };
+    char *scratch = plane + 3 * part(n * 2);
+    hipStream_t st = sc->stream;
+    HIP_OK(hipEventRecord(B.ev[0], st));
+    if (motion_run(sc, motion, t, nullptr, nullptr, true, st) != 0) return -1;
+    HIP_OK(hipEventRecord(B.ev[1], st));
+    HIP_OK(rtt_launch_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, colour, st));
+    HIP_OK(hipEventRecord(B.ev[2], st));
+    if (motion_blur_issue(W, H, colour, motion, t, out, scratch, params, st) != 0) return -1;
+    if (outR || outG || outB) HIP_OK(rtt_launch_quantise((uint32_t)n, out, planes.r, planes.g, planes.b, st));
+    HIP_OK(hipEventRecord(B.ev[3], st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(&B.ms[i], B.ev[i], B.ev[i + 1]));
+    return scene_outputs_to_host(n, out, planes, outRgb, outR, outG, outB);
+}
+
+int rtHipSceneMotionBlurTimes(const rtHipScene *sc, cl_float *ms)
+{
+    if (!sc || !ms) return fail("null argument");
+    for (int i = 0; i < 3; ++i) ms[i] = sc->motionBlur.ms[i];
     return 0;
 }

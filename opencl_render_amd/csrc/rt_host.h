@@ -266,6 +266,14 @@ struct rtHipScene {
         bool clampOn = false; // rtHipSceneSetTemporalClamp: the accumulation step runs the clamped kernel with `clamp`
         rtHipTemporalClampParams clamp = {};
     } temporal;
+    // motion blur (rtHipSceneMotionBlur), made on its first call in one block: this frame's motion and t, the gathered colour, the blurred
+    // image, the u16 output planes and the filter's scratch.  ev: before the motion pass, after it, after the gather, after the blur
+    // and the output kernel; ms: the three spans of the last call.
+    struct MotionBlur {
+        rthost::Dev<> buf;
+        rthost::Event ev[4];
+        float ms[3] = {};
+    } motionBlur;
     // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
     // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
     // and the sets change places at its end.  log: triangles per thread, per workgroup, entries of the last move; ms: device time of its

@@ -97,6 +97,10 @@ hipError_t rtt_launch_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint
                              const uint16_t *tileBuf, float *colour, hipStream_t stream);
 hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, uint16_t *outG, uint16_t *outB, hipStream_t stream);
 
+// ---- rt_motion_blur.hip (lz: 2 f32 per pixel; tileMax, nbMax: 4 f32 per 32 x 32 tile)
+hipError_t rmb_launch(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *depth, float *out, float *lz,
+                      float *tileMax, float *nbMax, float shutter, float maxBlur, uint32_t taps, float depthSoftness, hipStream_t stream);
+
 // ---- rt_variance.hip
 hipError_t rtv_launch_moments(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
                               const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,

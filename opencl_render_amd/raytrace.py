@@ -93,6 +93,14 @@ TEMPORAL_CLAMP_DEFAULTS = dict(mode=3, gamma=1.0)
 TEMPORAL_CLAMP_MODES = dict(minmax=1, variance=2, both=3)
 
 
+class MotionBlurParams(C.Structure):  # rtHipMotionBlurParams
+    _fields_ = [("shutter", C.c_float), ("maxBlur", C.c_float), ("taps", C.c_uint32), ("depthSoftness", C.c_float)]
+
+
+# rtHipMotionBlurDefaults (include/raytrace_hip.h, "MOTION BLUR")
+MOTION_BLUR_DEFAULTS = dict(shutter=0.5, max_blur=16.0, taps=15, depth_softness=0.05)
+
+
 class AoParams(C.Structure):  # rtHipAoParams
     _fields_ = [("raysPerHit", C.c_uint32), ("pixelSamples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -180,6 +188,8 @@ RESIDENT_SYMBOLS = [
     "rtHipDenoiseVariance", "rtHipSceneTemporalVariance",
     "rtHipTemporalClampDefaults", "rtHipTemporalClampCheck", "rtHipTemporalClampDevice", "rtHipTemporalClamp", "rtHipTemporalMomentsClampDevice",
     "rtHipTemporalMomentsClamp", "rtHipSceneSetTemporalClamp", "rtHipSceneGetTemporalClamp",
+    "rtHipMotionBlurDefaults", "rtHipMotionBlurCheck", "rtHipMotionBlurScratchBytes", "rtHipMotionBlurDevice", "rtHipMotionBlur",
+    "rtHipSceneMotionBlur", "rtHipSceneMotionBlurTimes",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestRoundVisits", "rtHipTestShadeLog", "rtHipTestBuildLog",
@@ -341,6 +351,16 @@ def lib() -> C.CDLL:
     L.rtHipTemporalMomentsClamp.argtypes = [C.c_int, u32, u32] + [vp] * 13 + [C.POINTER(TemporalParams), clamp]
     L.rtHipSceneSetTemporalClamp.argtypes = [vp, clamp]
     L.rtHipSceneGetTemporalClamp.argtypes = [vp, clamp]
+    blur = C.POINTER(MotionBlurParams)
+    L.rtHipMotionBlurDefaults.restype = None
+    L.rtHipMotionBlurDefaults.argtypes = [blur]
+    L.rtHipMotionBlurCheck.argtypes = [blur]
+    L.rtHipMotionBlurScratchBytes.restype = C.c_uint64
+    L.rtHipMotionBlurScratchBytes.argtypes = [u32, u32]
+    L.rtHipMotionBlurDevice.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, vp, u64, blur, vp]
+    L.rtHipMotionBlur.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, blur]
+    L.rtHipSceneMotionBlur.argtypes = [vp, blur, vp, vp, vp, vp]
+    L.rtHipSceneMotionBlurTimes.argtypes = [vp, C.POINTER(C.c_float)]
     L.rtHipBakeDefaults.restype = None
     L.rtHipBakeDefaults.argtypes = [C.POINTER(BakeParams)]
     L.rtHipSceneBakeAmbientOcclusion.argtypes = [vp, C.POINTER(BakeParams), vp, vp]
@@ -691,7 +711,7 @@ def variance_params(iterations=VARIANCE_DEFAULTS["iterations"], luminance_sigma2
 
 
 class _Arrays:
-    """What denoise, temporal, temporal_moments and denoise_variance need of their arrays, for numpy (host entry point) or torch on
+    """What denoise, temporal, temporal_moments, denoise_variance and motion_blur need of their arrays, for numpy (host entry point) or torch on
     cuda:`device` (device entry point on torch's current stream or `stream`)."""
 
     def __init__(self, who, on_gpu, device, stream):
@@ -735,6 +755,47 @@ class _Arrays:
             for buf in buffers:
                 if buf is not None:
                     buf.record_stream(self.run)
+
+
+def motion_blur_params(shutter=MOTION_BLUR_DEFAULTS["shutter"], max_blur=MOTION_BLUR_DEFAULTS["max_blur"], taps=MOTION_BLUR_DEFAULTS["taps"],
+                       depth_softness=MOTION_BLUR_DEFAULTS["depth_softness"]) -> MotionBlurParams:
+    """rtHipMotionBlurParams from the Python keywords (the library checks the ranges)."""
+    if not 0 <= int(taps) <= 0xFFFFFFFF:  # (ctypes would wrap it into the uint32 field)
+        raise ValueError(f"motion blur: taps must be in 0..2^32-1 (got {taps})")
+    return MotionBlurParams(float(shutter), float(max_blur), int(taps), float(depth_softness))
+
+
+def motion_blur(colour, motion, depth, shutter=MOTION_BLUR_DEFAULTS["shutter"], max_blur=MOTION_BLUR_DEFAULTS["max_blur"],
+                taps=MOTION_BLUR_DEFAULTS["taps"], depth_softness=MOTION_BLUR_DEFAULTS["depth_softness"], device: int = 0, stream: int = 0,
+                out=None):
+    """The vector motion blur of include/raytrace_hip.h ("MOTION BLUR"): the frame `colour` [H, W, 3] f32 blurred along `motion`
+    [H, W, 2] f32 with `depth` [H, W] f32 deciding what lies in front -- "motion" and "t" of ResidentScene.motion().  Returns the
+    blurred image [H, W, 3] f32: `out` if given (it must not overlap an input), else a new array.  numpy arrays go through rtHipMotionBlur
+    (host arrays, synchronous); torch tensors on cuda:`device` stay there and go through rtHipMotionBlurDevice on torch's current stream
+    (or `stream`) with a torch scratch tensor."""
+    p = motion_blur_params(shutter, max_blur, taps, depth_softness)
+    if len(colour.shape) != 3 or colour.shape[2] != 3:
+        raise ValueError(f"motion_blur: colour must be [H, W, 3] (got {tuple(colour.shape)})")
+    shape = (int(colour.shape[0]), int(colour.shape[1]))
+    given = [("colour", colour, shape + (3,)), ("motion", motion, shape + (2,)), ("depth", depth, shape)]
+    A = _Arrays("motion_blur", any(hasattr(v, "data_ptr") for _, v, _ in given), device, stream)
+    for name, v, sh in given:
+        A.check(name, v, sh)
+    res = A.check("out", out, shape + (3,)) if out is not None else A.new(shape + (3,))
+    ptrs = [A.address(v) for v in (colour, motion, depth, res)]
+    H, W = shape
+    if not A.on_gpu:
+        if lib().rtHipMotionBlur(device, W, H, *ptrs, C.byref(p)) != 0:
+            raise RuntimeError("rtHipMotionBlur failed: " + last_error())
+        return res
+    nbytes = lib().rtHipMotionBlurScratchBytes(W, H)
+    if nbytes == 0:
+        raise ValueError(f"motion_blur: a {W} x {H} image is not 1..16384 pixels wide and high and 1..2^27 pixels")
+    scratch = A.new(nbytes, np.uint8)
+    if lib().rtHipMotionBlurDevice(device, W, H, *ptrs, A.address(scratch), nbytes, C.byref(p), A.stream_arg()) != 0:
+        raise RuntimeError("rtHipMotionBlurDevice failed: " + last_error())
+    A.done([colour, motion, depth, res, scratch])
+    return res
 
 
 _MOMENTS_HISTORY = _TEMPORAL_HISTORY + (("moments", 2, False),)
@@ -1593,6 +1654,25 @@ class ResidentScene:
         ms = (C.c_float * 4)()
         self._check(lib().rtHipSceneTemporalTimes(self.handle, ms), "rtHipSceneTemporalTimes")
         return dict(motion=ms[0], gather=ms[1], accumulate=ms[2], filter=ms[3])
+
+    def motion_blur(self, **params) -> dict:
+        """The last frame blurred along its motion vectors on the device (rtHipSceneMotionBlur; keywords shutter, max_blur, taps and
+        depth_softness as for raytrace.motion_blur): {"rgb": [H, W, 3] f32, "planes": [r, g, b] [H, W] u16}.  The loop is mark_motion(),
+        set_camera / set_vertices, render(), motion_blur(): the call needs a reference and does NOT mark, the reference stays the
+        caller's.  temporal() marks again, so with both on one frame blur first.  Needs every tile of the image in this instance."""
+        p = motion_blur_params(**params)
+        sc = self.scene
+        rgb = np.empty((sc.height, sc.width, 3), np.float32)
+        planes = [np.empty((sc.height, sc.width), np.uint16) for _ in range(3)]
+        self._check(lib().rtHipSceneMotionBlur(self.handle, C.byref(p), _ptr(rgb), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2])),
+                    "rtHipSceneMotionBlur")
+        return {"rgb": rgb, "planes": planes}
+
+    def motion_blur_times_ms(self) -> dict:
+        """Device time of the last motion_blur() (rtHipSceneMotionBlurTimes): motion pass, gather, blur (the filter and the output)."""
+        ms = (C.c_float * 3)()
+        self._check(lib().rtHipSceneMotionBlurTimes(self.handle, ms), "rtHipSceneMotionBlurTimes")
+        return dict(motion=ms[0], gather=ms[1], blur=ms[2])
 
     def ambient_occlusion(self, rays=AO_DEFAULTS["rays"], radius=AO_DEFAULTS["radius"], pixel_samples=AO_DEFAULTS["pixel_samples"],
                           seed=AO_DEFAULTS["seed"], out=None, stream: int = 0):

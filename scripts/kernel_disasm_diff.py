@@ -16,7 +16,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = ("rt_kernels", "rt_wavefront", "rt_build_device", "rt_kat", "rt_scene_prep", "rt_denoise", "rt_temporal", "rt_variance",
-           "rt_camera_move", "rt_geometry_move")
+           "rt_camera_move", "rt_geometry_move", "rt_scene_edit", "rt_motion_blur")
 
 
 def devflags(tree):
@@ -29,6 +29,9 @@ def disassemble(tree, out, rocm):
     csrc = os.path.join(tree, "opencl_render_amd", "csrc")
     kernels = {}
     for name in SOURCES:
+        if not os.path.exists(os.path.join(csrc, name + ".hip")):  # a file one tree does not have yet: every symbol of it is added or gone
+            kernels[name] = {}
+            continue
         co = os.path.join(out, name + ".co")
         subprocess.run([os.path.join(rocm, "bin", "hipcc")] + devflags(tree) + ["-I" + os.path.join(tree, "include"), "-I" + csrc,
                        "--cuda-device-only", "--no-gpu-bundle-output", "-c", os.path.join(csrc, name + ".hip"), "-o", co], check=True)
