@@ -1105,6 +1105,116 @@ int  rtHipSceneMotionBlur(rtHipScene *scene, const rtHipMotionBlurParams *params
  * ms[1] the colour gather, ms[2] the blur and the output kernel.  All 0 before the first call.  Returns 0, or -1 for a NULL argument. */
 int  rtHipSceneMotionBlurTimes(const rtHipScene *scene, cl_float ms[3]);
 
+/* DEPTH OF FIELD: the lens as a post effect.  A frame is blurred by the circle of confusion its DEPTH pass gives every pixel: "scatter as
+ * gather" -- a pixel q counts at p if q's own disc reaches p, spread over that disc's area --, with the gather's extent taken from a
+ * per-tile maximum of the radius and its 3 x 3 neighbourhood maximum (the tile machinery of MOTION BLUR, after McGuire et al. 2012).
+ * The frame kernels are not involved, and cannot be: every pixel's primary rays are tested against a candidate list built for ONE eye
+ * point (rtHipBuildCameraList, rtHipSceneSetCamera), and a lens that moves the ray origin over an aperture would need other lists per
+ * sample.  The arithmetic is IEEE fp32 + - * /, sqrtf, fabsf and compares in the order written (no FMA, no reciprocal-multiply, no
+ * trigonometry; division and square root correctly rounded): tests/dof_oracle.py restates it in numpy and the device output equals it
+ * bit for bit.  Every bit pattern of the inputs has a defined answer up to the payload of a NaN, and no index is formed before its
+ * range test.
+ *
+ * All arrays are W x H, row-major; W, H and W*H limited as in TEMPORAL ACCUMULATION.  Inputs: colour 3 x f32; depth f32, exactly what
+ * rtHipReadbackPasses writes for DEPTH: sample 1's distance from the eye to its hit ALONG THE RAY, +inf on a miss.  Output: out 3 x f32;
+ * it must overlap no input (the taps belong to neighbours).
+ * Parameters: focus finite and > 0, the distance in focus in the DEPTH pass's measure -- along the ray, so the surface in focus is a
+ * sphere around the eye, not a plane --; cocScale finite in [0, 4096], pixels: the radius of the circle of confusion of a point
+ * infinitely far away; maxCoc finite in [1, 32] pixels, the cap of a radius; rings in [1, 6]; depthSoftness finite and >= 0 (relative).
+ * Anything else returns -1 before anything is launched.
+ *   clamp01(r) = !(r > 0) ? 0 : (r > 1 ? 1 : r)                                                              (a NaN gives 0)
+ *   sdc(a, b, e) = (a == b) ? 1.0f : clamp01(1.0f - (a - b) / e)            (is a in front of b, softly; as in MOTION BLUR)
+ * (a) Radius of pixel q, z = depth_q:
+ *   if (z == +inf) a = 1.0f;  else if (!(z > 0)) a = 0.0f  (a NaN, zero, negative, -inf);  else a = fabsf(z - focus) / z
+ *   r = a * cocScale;  if (!(r < maxCoc)) r = cocScale > 0 ? maxCoc : 0.0f                       (also catches inf * 0, a NaN)
+ *   So r is never negative and never a NaN, and cocScale == 0 gives r = 0 everywhere.
+ * (b) Tile maximum.  Tiles are 32 x 32 pixels, tile(x, y) = (x >> 5, y >> 5).  tileMax[T] is the greatest r of the tile's pixels (a
+ *   maximum of numbers that are not NaN: it does not depend on the order).
+ * (c) Neighbourhood maximum.  nbMax[T] is the greatest tileMax over the tiles (Tx + dx, Ty + dy), dx, dy = -1..1, that exist.  Because
+ *   maxCoc <= 32 = the tile's side, a pixel q whose disc reaches p (|q - p| <= r_q <= 32) lies in p's tile or in one of its eight
+ *   neighbours, so r_q <= nbMax[tile(p)]: a gather of radius nbMax[tile(p)] around p visits the whole neighbourhood from which anything
+ *   can reach p.  That makes the gather complete, and a neighbourhood whose maximum is below half a pixel a copy.
+ * (d) Gather at p = (x, y), with R = nbMax[tile(p)]:
+ *   if (!(R >= 0.5f)): out = colour_p, a copy, bit for bit.  Otherwise:
+ *   rp = r_p < 0.5f ? 0.5f : r_p;  zp = depth_p
+ *   j = ((x & 1) * 2 + (y & 1) * 3) & 3;  jit = ((float)j - 1.5f) * 0.25f                (a fixed 2 x 2 dither: no random state)
+ *   wsum = 1.0f / (rp * rp);  sum = colour_p * wsum (per channel)                                              (the centre tap)
+ *   The other taps lie on `rings` octagonal rings (no sine, no cosine).  V[0..8] = (1,0), (c,c), (0,1), (-c,c), (-1,0), (-c,-c), (0,-1),
+ *   (c,-c), (1,0) with the one literal c = 0.70710678f.  Ring k = 1..rings has 8k taps s = 0..8k-1 (1 + 4*rings*(rings+1) taps in all,
+ *   the centre included); for k ascending, and s ascending within k:
+ *     v = s / k;  m = s % k  (integers);  f = (float)m / (float)k
+ *     ux = V[v].x + (V[v+1].x - V[v].x) * f;  uy = V[v].y + (V[v+1].y - V[v].y) * f
+ *     rad = (((float)k + jit) / (float)rings) * R;  ox = ux * rad;  oy = uy * rad
+ *     X = ((float)x + 0.5f) + ox;  Y = ((float)y + 0.5f) + oy
+ *     the tap is skipped unless X >= 0 && X < (float)W && Y >= 0 && Y < (float)H; then q = ((int)X, (int)Y)
+ *     d = sqrtf(ox*ox + oy*oy);  rq = r_q < 0.5f ? 0.5f : r_q;  zq = depth_q;  e = depthSoftness * (zp < zq ? zp : zq)
+ *     fr = sdc(zq, zp, e)        (1 when q lies in front of p or at p's depth, both at +inf included; 0 when it lies well behind)
+ *     m2 = rq < rp ? rq : rp;  reff = rq * fr + m2 * (1.0f - fr)
+ *     w = clamp01((reff - d) + 0.5f) / (reff * reff)
+ *     wsum += w;  sum += colour_q * w (per channel: a multiply, an add)
+ *   out = sum / wsum per channel
+ * The (1 - fr) term keeps a sharp pixel sharp in front of a blurred background: a pixel behind p spreads no further over p than p's
+ * own disc.  reff lies in [0.5, maxCoc], wsum starts positive and no weight is negative or a NaN, so out is a NaN only where a colour
+ * it sums is.  The outermost ring of a pixel whose dither is positive lies up to R * 0.375 / rings outside R: such taps weigh little
+ * or nothing and are read like any other.
+ * Not done: lens sampling inside the frame kernels (the candidate lists belong to one eye point, above); axial depth (focus and depth
+ * are distances along the ray: the surface in focus is a sphere); an anti-aliased depth (DEPTH is sample 1's: silhouettes are
+ * classified per pixel); separate near and far layers with in-painting behind a blurred foreground (a blurred near object shows the
+ * sharp background's own pixels through it, not what it hides); bokeh highlights (the weights are energy-preserving discs, nothing is
+ * boosted); tile-dealt instances (their taps cross tile borders: the array entry points take a composed image). */
+typedef struct rtHipDepthOfFieldParams {
+    cl_float focus;         /* the distance in focus, along the ray (the DEPTH pass's measure) */
+    cl_float cocScale;      /* pixels: the circle-of-confusion radius of a point infinitely far away */
+    cl_float maxCoc;        /* pixels: the cap of a radius */
+    cl_uint  rings;         /* octagonal rings of taps: 1 + 4*rings*(rings+1) taps */
+    cl_float depthSoftness; /* relative: the depth extent over which "in front" falls from 1 to 0 */
+} rtHipDepthOfFieldParams;
+/* focus = 1, cocScale = 8, maxCoc = 16, rings = 3, depthSoftness = 0.05: defaults of a parameter, not measurements. */
+void rtHipDepthOfFieldDefaults(rtHipDepthOfFieldParams *params);
+/* 0 for legal parameters, -1 (the last-error text set) for NULL or a value outside the ranges above.  Needs no device. */
+int  rtHipDepthOfFieldCheck(const rtHipDepthOfFieldParams *params);
+/* Bytes of scratch rtHipDepthOfFieldDevice needs for a width x height image of n pixels and T = ceil(width/32) * ceil(height/32) tiles:
+ * (r, depth) per pixel, 8n bytes rounded up to 16, then tileMax and nbMax, 4T bytes each rounded up to 16.  0 for a size the filter
+ * refuses. */
+uint64_t rtHipDepthOfFieldScratchBytes(cl_uint width, cl_uint height);
+/* DEVICE arrays of `device`, asynchronous on `stream` (a hipStream_t of `device` as void*; NULL = the null stream): four launches, no
+ * allocation, no synchronisation.  scratch: at least rtHipDepthOfFieldScratchBytes(width, height) bytes, 16-byte aligned, contents
+ * irrelevant.  Pointer, overlap and stream checks are rtHipTemporalDevice's: out and scratch must overlap nothing.  Anything else returns
+ * -1 with the last-error text set and launches nothing. */
+int  rtHipDepthOfFieldDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *depth, void *out, void *scratch,
+                             uint64_t scratchBytes, const rtHipDepthOfFieldParams *params, void *stream);
+/* HOST arrays, synchronous; device memory is allocated and freed per call.  Same results as rtHipDepthOfFieldDevice. */
+int  rtHipDepthOfField(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *depth, cl_float *out,
+                       const rtHipDepthOfFieldParams *params);
+/* The scene's last frame, blurred on its device by its own DEPTH pass.  The call needs RT_HIP_PASS_DEPTH on (rtHipScenePasses, before
+ * the frame) and a tile set that holds every tile of the image once; it synchronises and finishes the frame like rtHipReadback, and
+ * then, on the scene's stream: gathers the colour ((float)u16 / 65535.0f of the beauty planes, what rtHipReadback gives) and the depth
+ * (the pass buffer's words, what rtHipReadbackPasses gives) into row-major storage of its own; blurs; and quantises the planes as
+ * rtHipSceneDenoise's.  It changes neither the tile buffer, the pass buffer, the temporal history nor the motion reference.
+ * Outputs (each may be NULL, host arrays): outRgb W x H x 3 f32 and the u16 planes R, G, B.
+ * Storage, made on first use in one block, counted in rtHipSceneBytes from then on and freed with the scene (a scene that never calls
+ * holds none of it), with n = W*H and every part rounded up to 256 bytes: the gathered colour 12n, the depth 4n, the blurred image 12n,
+ * the planes 3 x 2n and rtHipDepthOfFieldScratchBytes.
+ * Refused with -1, the last-error text set and nothing launched: a NULL scene or params, parameters out of range, an image wider or
+ * higher than 16384 or of more than 2^27 pixels, the depth pass off, a tile subset. */
+int  rtHipSceneDepthOfField(rtHipScene *scene, const rtHipDepthOfFieldParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG,
+                            cl_ushort *outB);
+/* Device time in milliseconds of the scene's last rtHipSceneDepthOfField call, from HIP events on the scene's stream: ms[0] the gather of
+ * colour and depth, ms[1] the blur, ms[2] the output kernel.  All 0 before the first call.  Returns 0, or -1 for a NULL argument. */
+int  rtHipSceneDepthOfFieldTimes(const rtHipScene *scene, cl_float ms[3]);
+/* A thin lens into the parameters: fills inout->focus = focus and inout->cocScale = apertureRadius * focalPixels / focus, the radius in
+ * pixels of the circle of confusion of a point infinitely far away for a lens of radius apertureRadius (scene units) focused at `focus`
+ * (scene units, along the ray).  focalPixels is the distance from the eye to the image plane over the pixel pitch, from the camera's
+ * vectors, in double with + - * / and sqrt only (lane 3 not read):
+ *   n = leftToRight x topToBottom  (n.x = lr.y*tb.z - lr.z*tb.y, n.y = lr.z*tb.x - lr.x*tb.z, n.z = lr.x*tb.y - lr.y*tb.x)
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;  h = dot(eyeToTopLeft, n);  if (h < 0) h = -h
+ *   plane = h / sqrt(dot(n, n));  pitch = sqrt(dot(leftToRight, leftToRight));  focalPixels = plane / pitch
+ *   cocScale = (float)(((double)apertureRadius * focalPixels) / (double)focus)                                 (rounded once)
+ * The other fields of *inout are kept.  Returns 0; -1 (the last-error text set, *inout unchanged) for a NULL argument, a camera whose
+ * pitch or plane distance is zero or not finite, or a focus or cocScale outside the ranges rtHipDepthOfFieldCheck allows (the other fields are not looked
+ * at).  Needs no device. */
+int  rtHipDepthOfFieldLens(const rtHipCamera *camera, cl_float apertureRadius, cl_float focus, rtHipDepthOfFieldParams *inout);
+
 /* AMBIENT OCCLUSION BAKE: a W x H texture of ambient occlusion over the scene's UV layout.  Each texel centre is mapped to the surface
  * point of the triangle whose UV triangle covers it, and the AO rays of the block above are traced from there with the same walk.  It
  * needs geometry, UVs, corner normals and the grid only: it works on every instance (whatever its tiles, passes or pipeline), ignores

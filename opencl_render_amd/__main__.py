@@ -39,6 +39,11 @@ it (include/raytrace_hip.h, "MOTION BLUR"; ResidentScene.motion_blur) to PATH_00
 unblurred.  ``--shutter S``, ``--max-blur PX`` and ``--blur-taps N`` set its parameters.  Beside ``--temporal`` the blur runs first:
 the accumulation marks the scene again.
 
+``--dof PATH`` also writes the frame blurred by its depth pass's circle of confusion (include/raytrace_hip.h, "DEPTH OF FIELD";
+ResidentScene.depth_of_field) to PATH: .bmp, .ppm or .pfm, numbered like --out under ``--orbit`` / ``--spin`` / ``--relight``.  ``--aperture A``
+is the lens radius in scene units; the distance in focus is ``--focus D`` (along the ray) or the depth of pixel ``--focus-pixel X Y`` of
+every frame; ``--dof-rings N`` and ``--max-coc PX`` set the tap rings and the cap of the blur radius.  The depth pass is turned on by itself.
+
 ``--relight N`` renders N frames of the one resident scene with its first light turned about the vertical axis between them
 (include/raytrace_hip.h, "SCENE EDITS: LIGHTS AND MATERIALS"; ResidentScene.set_lights): img_000 .. img_{N-1}, with ``--passes`` /
 ``--denoise`` / ``--ao`` numbered alike.
@@ -135,6 +140,15 @@ def parser():
     ap.add_argument("--max-blur", type=float, default=None, metavar="PX",
                     help="with --motion-blur: the longest half-extent of a streak in pixels, 1..32 (default 16)")
     ap.add_argument("--blur-taps", type=int, default=None, metavar="N", help="with --motion-blur: samples along a streak, 1..64 (default 15)")
+    ap.add_argument("--dof", metavar="PATH",
+                    help="also write the frame blurred by its depth pass's circle of confusion (ResidentScene.depth_of_field) to PATH: .bmp, "
+                         ".ppm or .pfm, numbered like --out under --orbit / --spin / --relight.  Needs --aperture and --focus or --focus-pixel")
+    ap.add_argument("--aperture", type=float, default=None, metavar="A", help="with --dof: the lens radius in scene units, >= 0")
+    ap.add_argument("--focus", type=float, default=None, metavar="D", help="with --dof: the distance in focus, along the ray, > 0")
+    ap.add_argument("--focus-pixel", type=int, nargs=2, default=None, metavar=("X", "Y"),
+                    help="with --dof: focus on what pixel (X, Y) shows (its value in the depth pass); an error where its ray hits nothing")
+    ap.add_argument("--dof-rings", type=int, default=None, metavar="N", help="with --dof: octagonal rings of taps, 1..6 (default 3)")
+    ap.add_argument("--max-coc", type=float, default=None, metavar="PX", help="with --dof: the cap of the blur radius in pixels, 1..32 (default 16)")
     ap.add_argument("--temporal-clamp", type=float, nargs="?", const=1.0, default=None, metavar="GAMMA",
                     help="with --temporal PATH: clamp the reprojected history to the colour box of the frame's 3x3 neighbourhood before the "
                          "blend (ResidentScene.set_temporal_clamp); GAMMA (default 1) is the variance box's half-width in standard deviations")
@@ -207,6 +221,25 @@ def parse_args(argv=None):
         ap.error("--max-blur PX needs PX in 1..32")
     if args.blur_taps is not None and not 1 <= args.blur_taps <= 64:
         ap.error("--blur-taps N needs N in 1..64")
+    if args.dof:
+        if not args.dof.lower().endswith((".bmp", ".ppm", ".pfm")):
+            ap.error("--dof PATH must end in .bmp, .ppm or .pfm")
+        if args.aperture is None or not (np.isfinite(args.aperture) and args.aperture >= 0):
+            ap.error("--dof PATH needs --aperture A with a finite A >= 0")
+        if (args.focus is None) == (args.focus_pixel is None):
+            ap.error("--dof PATH needs --focus D or --focus-pixel X Y (one of them)")
+        if args.focus is not None and not (np.isfinite(args.focus) and args.focus > 0):
+            ap.error("--focus D needs a finite D > 0")
+        if args.focus_pixel is not None and not (0 <= args.focus_pixel[0] < args.width and 0 <= args.focus_pixel[1] < args.height):
+            ap.error("--focus-pixel X Y needs a pixel of the image")
+        if args.dof_rings is not None and not 1 <= args.dof_rings <= 6:
+            ap.error("--dof-rings N needs N in 1..6")
+        if args.max_coc is not None and not 1 <= args.max_coc <= 32:
+            ap.error("--max-coc PX needs PX in 1..32")
+        if args.progressive:
+            ap.error("--dof does not go with --progressive")
+    elif any(v is not None for v in (args.aperture, args.focus, args.focus_pixel, args.dof_rings, args.max_coc)):
+        ap.error("--aperture, --focus, --focus-pixel, --dof-rings and --max-coc need --dof PATH")
     if args.temporal_clamp is not None and not args.temporal:
         ap.error("--temporal-clamp needs --temporal PATH")
     if args.temporal_clamp is not None and not (np.isfinite(args.temporal_clamp) and args.temporal_clamp >= 0):
@@ -308,12 +341,37 @@ def write_bake_ao(sc, path: str, device: int, size, rays: int, radius: float, se
     return res
 
 
-def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool = True, denoise: bool = False):
+def dof_keywords(args) -> dict:
+    """--dof's options as the keywords of ResidentScene.depth_of_field."""
+    kw = dict(aperture=args.aperture, focus=args.focus, focus_pixel=tuple(args.focus_pixel) if args.focus_pixel else None,
+              rings=args.dof_rings, max_coc=args.max_coc)
+    return {k: v for k, v in kw.items() if v is not None}
+
+
+def write_dof_image(args, path: str, res: dict) -> None:
+    from . import frontend
+    if path.lower().endswith(".pfm"):
+        frontend.write_pfm_rgb(path, res["rgb"])
+    elif path.lower().endswith(".ppm"):
+        frontend.write_ppm(path, *res["planes"])
+    else:
+        frontend.write_bmp(path, *res["planes"], low_byte_compat=args.low_byte_compat)
+
+
+def write_dof(rs, args, index: int) -> None:
+    """--dof under --orbit / --spin / --relight: frame `index` blurred by its depth pass -> PATH numbered like --out."""
+    if args.dof:
+        from . import raytrace
+        write_dof_image(args, raytrace.orbit_path(args.dof, index), rs.depth_of_field(**dof_keywords(args)))
+
+
+def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool = True, denoise: bool = False, dof=None):
     """The frame through ResidentScene with the alpha, depth and triangle passes on (with `basic`) and normal and albedo (with `surface`
     or `denoise`): computation type `device` (1..gpus = one GPU, gpus + 1 = all of them, one instance per GPU over
     raytrace.tiles_of_rank).  Returns the R, G, B planes and readback_passes' dict; with `denoise` the dict also holds "denoised", what
     ResidentScene.denoise returns (default parameters) -- for several instances their read-backs composed and run through
-    raytrace.denoise on device 0."""
+    raytrace.denoise on device 0.  `dof`: the keywords of ResidentScene.depth_of_field; the dict then holds "dof", what it returns --
+    for several instances their read-backs composed and run through raytrace.dof_lens and raytrace.depth_of_field on device 0."""
     from . import raytrace
     world = gpus if device == gpus + 1 else 1
     instances = []
@@ -322,7 +380,7 @@ def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool
             tiles = raytrace.tiles_of_rank(sc.width, sc.height, rank, world) if world > 1 else None
             rs = raytrace.ResidentScene(sc, rank if world > 1 else device - 1, tiles, like=instances[0] if instances else None)
             instances.append(rs)
-            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface or denoise, albedo=surface or denoise)
+            rs.set_passes(alpha=basic, depth=basic or dof is not None, triangle=basic, normal=surface or denoise, albedo=surface or denoise)
         for rs in instances:
             rs.render()
         planes = [np.zeros(sc.pixels, np.uint16) for _ in range(3)]
@@ -332,6 +390,9 @@ def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool
             passes = rs.readback_passes(passes)
         if denoise and world == 1:
             passes["denoised"] = instances[0].denoise()
+        if dof is not None and world == 1:
+            passes["dof"] = instances[0].depth_of_field(**dof)
+        camera = instances[0].camera()
     finally:
         for rs in instances:
             rs.close()
@@ -339,6 +400,18 @@ def render_passes(sc, device: int, gpus: int, surface: bool = False, basic: bool
         colour = np.stack(planes, -1).reshape(sc.height, sc.width, 3).astype(np.float32) / np.float32(65535.0)
         out = raytrace.denoise(colour, passes["normal"], passes["albedo"], device=0)
         passes["denoised"] = {"colour": out, "planes": raytrace.quantise(out)}
+    if dof is not None and world > 1:
+        kw = dict(dof)
+        aperture, focus, pixel = kw.pop("aperture"), kw.pop("focus", None), kw.pop("focus_pixel", None)
+        if pixel is not None:
+            focus = float(passes["depth"][pixel[1], pixel[0]])
+            if not (np.isfinite(focus) and focus > 0):
+                raise ValueError(f"--focus-pixel {pixel}: the ray of that pixel hit nothing")
+        p = raytrace.dof_lens(camera, aperture, focus, **kw)
+        colour = np.stack(planes, -1).reshape(sc.height, sc.width, 3).astype(np.float32) / np.float32(65535.0)
+        out = raytrace.depth_of_field(colour, passes["depth"], focus=p.focus, coc_scale=p.cocScale, max_coc=p.maxCoc, rings=p.rings,
+                                      depth_softness=p.depthSoftness, device=0)
+        passes["dof"] = {"rgb": out, "planes": raytrace.quantise(out)}
     if "triangle" in passes and "mesh" not in passes:  # a scene not made of front-end meshes: all of it counts as mesh 0
         passes["mesh"] = np.where(passes["triangle"] != 0xFFFFFFFF, 0, -1).astype(np.int32)
     return [p.reshape(sc.height, sc.width) for p in planes], passes
@@ -467,8 +540,8 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
     rs = raytrace.ResidentScene(sc, device)
     try:
         basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
-        if basic or surface:
-            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        if basic or surface or args.dof:
+            rs.set_passes(alpha=basic, depth=basic or bool(args.dof), triangle=basic, normal=surface, albedo=surface)
         if args.sequence:
             rs.set_sample_window(args.sequence, 0, sc.sample_count, advance=True)
         spent = 0.0
@@ -485,6 +558,7 @@ def render_orbit(sc, args, device: int, eye, centre, move_first: bool) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_dof(rs, args, i)
             write_motion_blur(rs, args, i, planes)
             write_motion(rs, args, i)
             write_temporal(rs, args, i)
@@ -503,8 +577,8 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
         if eye is not None:
             rs.look_at(eye, centre, (0, 1, 0), np.radians(args.fov))
         basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
-        if basic or surface:
-            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        if basic or surface or args.dof:
+            rs.set_passes(alpha=basic, depth=basic or bool(args.dof), triangle=basic, normal=surface, albedo=surface)
         if args.sequence:
             rs.set_sample_window(args.sequence, 0, sc.sample_count, advance=True)
         vertex, index, normal = sc.vertex, sc.tri_index, sc.tri_normal
@@ -523,6 +597,7 @@ def render_spin(sc, args, device: int, centre, eye=None) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_dof(rs, args, i)
             write_motion_blur(rs, args, i, planes)
             write_motion(rs, args, i)
             write_temporal(rs, args, i)
@@ -538,8 +613,8 @@ def render_relight(sc, args, device: int) -> float:
     rs = raytrace.ResidentScene(sc, device)
     try:
         basic, surface = bool(args.passes), bool(args.surface_passes or args.denoise or args.variance_guided)
-        if basic or surface:
-            rs.set_passes(alpha=basic, depth=basic, triangle=basic, normal=surface, albedo=surface)
+        if basic or surface or args.dof:
+            rs.set_passes(alpha=basic, depth=basic or bool(args.dof), triangle=basic, normal=surface, albedo=surface)
         lights = raytrace.scene_lights(sc)
         spent = 0.0
         for i in range(args.relight):
@@ -555,6 +630,7 @@ def render_relight(sc, args, device: int) -> float:
             denoised = rs.denoise() if args.denoise else None
             ao = rs.ambient_occlusion(rays=args.ao_rays, radius=args.ao_radius, pixel_samples=args.ao_samples, seed=args.ao_seed) if args.ao else None
             write_view(args, orbit_outputs(args, i), planes, passes, denoised, ao)
+            write_dof(rs, args, i)
             write_temporal(rs, args, i)
     finally:
         rs.close()
@@ -618,9 +694,9 @@ def main(argv=None):
             sys.exit("--progressive renders on one GPU: choose --device 1..%d" % raytrace.lib().rtHipDeviceCount())
         r, g, b = render_progressive(sc, args, args.device - 1)
         ok = True
-    elif args.passes or args.denoise:
+    elif args.passes or args.denoise or args.dof:
         (r, g, b), passes = render_passes(sc, args.device, raytrace.lib().rtHipDeviceCount(), surface=args.surface_passes,
-                                          basic=bool(args.passes), denoise=bool(args.denoise))
+                                          basic=bool(args.passes), denoise=bool(args.denoise), dof=dof_keywords(args) if args.dof else None)
         ok = True
     else:
         ok, r, g, b = raytrace.raytrace_all(args.device, sc)
@@ -642,6 +718,8 @@ def main(argv=None):
             frontend.write_ppm(args.denoise, *den["planes"])
         else:
             frontend.write_bmp(args.denoise, *den["planes"], low_byte_compat=args.low_byte_compat)
+    if args.dof:
+        write_dof_image(args, args.dof, passes["dof"])
     if args.ao:
         gpus = raytrace.lib().rtHipDeviceCount()
         write_ao(sc, args.ao, 0 if args.device == gpus + 1 else args.device - 1, args.ao_rays, args.ao_radius, args.ao_samples, args.ao_seed)
@@ -659,7 +737,7 @@ def main(argv=None):
     rays = args.width * args.height * (args.progressive or args.samples)
     print(f"{names[args.device]}: {sc.name}, {sc.triangle_count} triangles, {args.width}x{args.height}, {args.samples} samples/pixel -> {args.out}\n"
           f"  scene {1e3 * (t1 - t0):.0f} ms, lists on the device {1e3 * (t2 - t1):.0f} ms (kernels {cam_ms:.1f} + {grid_ms:.1f} ms), "
-          f"{'progressive frames + previews' if args.progressive else 'resident render + passes' if args.passes or args.denoise else 'RaytraceAll'} {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
+          f"{'progressive frames + previews' if args.progressive else 'resident render + passes' if args.passes or args.denoise or args.dof else 'RaytraceAll'} {1e3 * (t3 - t2):.0f} ms = {rays / (t3 - t2) / 1e6:.0f} M primary rays/s, lit pixels {float((np.asarray(r) > 0).mean()):.2f}")
     return 0
 
 

@@ -1,6 +1,6 @@
 // rt_filters.cpp -- the image-space filters of libraytrace_hip.so (include/raytrace_hip.h: "DENOISER", "TEMPORAL ACCUMULATION",
-// "VARIANCE-GUIDED FILTER", "TEMPORAL CLAMP", "MOTION BLUR"): parameter checks, the device and host entry points, and the resident scene's calls with their buffers.
-// The kernels are in rt_denoise.hip, rt_temporal.hip, rt_variance.hip and rt_motion_blur.hip; the scene and what else the host side shares, in rt_host.h.
+// "VARIANCE-GUIDED FILTER", "TEMPORAL CLAMP", "MOTION BLUR", "DEPTH OF FIELD"): parameter checks, the device and host entry points, and the resident scene's calls with their buffers.
+// The kernels are in rt_denoise.hip, rt_temporal.hip, rt_variance.hip, rt_motion_blur.hip and rt_dof.hip; the scene and what else the host side shares, in rt_host.h.
 #include "rt_host.h"
 #include "rt_launch.h"
 #include "rt_overlap.h"
@@ -848,5 +848,174 @@ int rtHipSceneMotionBlurTimes(const rtHipScene *sc, cl_float *ms)
 {
     if (!sc || !ms) return fail("null argument");
     for (int i = 0; i < 3; ++i) ms[i] = sc->motionBlur.ms[i];
+    return 0;
+}
+
+// ---- depth of field (include/raytrace_hip.h, "DEPTH OF FIELD"; kernels in rt_dof.hip) ------------------------------------------------
+// Filter scratch of a W x H image: rz = (r, depth) per pixel as 2 f32, rounded up to 16 bytes, then tileMax and nbMax as one float per
+// 32 x 32 tile, each rounded up to 16 bytes.
+void rtHipDepthOfFieldDefaults(rtHipDepthOfFieldParams *p)
+{
+    if (!p) return;
+    p->focus = 1.0f;
+    p->cocScale = 8.0f;
+    p->maxCoc = 16.0f;
+    p->rings = 3;
+    p->depthSoftness = 0.05f;
+}
+
+static int dof_focus_ok(float focus)
+{
+    if (!(std::isfinite(focus) && focus > 0.f)) return fail("depth of field: focus %g is not finite and > 0", (double)focus);
+    return 0;
+}
+
+static int dof_coc_scale_ok(float cocScale)
+{
+    if (!(std::isfinite(cocScale) && cocScale >= 0.f && cocScale <= 4096.0f))
+        return fail("depth of field: cocScale %g is not finite and in 0..4096", (double)cocScale);
+    return 0;
+}
+
+int rtHipDepthOfFieldCheck(const rtHipDepthOfFieldParams *p)
+{
+    if (!p) return fail("depth of field: null parameters");
+    if (dof_focus_ok(p->focus) != 0 || dof_coc_scale_ok(p->cocScale) != 0) return -1;
+    if (!(std::isfinite(p->maxCoc) && p->maxCoc >= 1.0f && p->maxCoc <= 32.0f))
+        return fail("depth of field: maxCoc %g is not finite and in 1..32", (double)p->maxCoc);
+    if (p->rings < 1 || p->rings > 6) return fail("depth of field: rings %u is not in 1..6", p->rings);
+    if (!(std::isfinite(p->depthSoftness) && p->depthSoftness >= 0.f))
+        return fail("depth of field: depthSoftness %g is not finite and >= 0", (double)p->depthSoftness);
+    return 0;
+}
+
+static bool dof_size_legal(uint32_t W, uint32_t H)
+{
+    return W != 0 && H != 0 && W <= RT_TEMPORAL_MAX_SIDE && H <= RT_TEMPORAL_MAX_SIDE && (uint64_t)W * H <= RT_DENOISE_MAX_PIXELS;
+}
+
+static int dof_size_ok(uint32_t W, uint32_t H)
+{
+    if (!dof_size_legal(W, H))
+        return fail("depth of field: a %u x %u image is not 1..16384 pixels wide and high and 1..2^27 pixels", W, H);
+    return 0;
+}
+
+static uint64_t dof_rz_bytes(uint32_t W, uint32_t H) { return ((uint64_t)W * H * 8 + 15) & ~15ull; }
+static uint64_t dof_tile_bytes(uint32_t W, uint32_t H) { return ((uint64_t)((W + 31u) / 32u) * ((H + 31u) / 32u) * 4 + 15) & ~15ull; }
+
+uint64_t rtHipDepthOfFieldScratchBytes(cl_uint width, cl_uint height)
+{
+    if (!dof_size_legal(width, height)) return 0;
+    return dof_rz_bytes(width, height) + 2 * dof_tile_bytes(width, height);
+}
+
+// Issues the filter on `st`; arguments were checked by the caller.
+static int dof_issue(uint32_t W, uint32_t H, const float *colour, const float *depth, float *out, char *scratch,
+                     const rtHipDepthOfFieldParams *p, hipStream_t st)
+{
+    char *tileMax = scratch + dof_rz_bytes(W, H), *nbMax = tileMax + dof_tile_bytes(W, H);
+    HIP_OK(rdf_launch(W, H, colour, depth, out, (float *)scratch, (float *)tileMax, (float *)nbMax, p->focus, p->cocScale, p->maxCoc, p->rings,
+                      p->depthSoftness, st));
+    return 0;
+}
+
+int rtHipDepthOfFieldDevice(int device, cl_uint width, cl_uint height, const void *colour, const void *depth, void *out, void *scratch,
+                            uint64_t scratchBytes, const rtHipDepthOfFieldParams *params, void *stream)
+{
+    if (rtHipDepthOfFieldCheck(params) != 0 || dof_size_ok(width, height) != 0) return -1;
+    if (!colour || !depth || !out || !scratch) return fail("depth of field: null array");
+    const uint64_t n = (uint64_t)width * height, need = rtHipDepthOfFieldScratchBytes(width, height);
+    if (scratchBytes < need)
+        return fail("depth of field: scratch of %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)need);
+    const RtArray arr[4] = { { colour, n * 12, 4, "colour" }, { depth, n * 4, 4, "depth" }, { out, n * 12, 4, "out", true },
+                             { scratch, need, 16, "scratch", true } };
+    if (checked_device_arrays("depth of field", device, stream, arr, 4) != 0) return -1;
+    return dof_issue(width, height, (const float *)colour, (const float *)depth, (float *)out, (char *)scratch, params, (hipStream_t)stream);
+}
+
+int rtHipDepthOfField(int device, cl_uint width, cl_uint height, const cl_float *colour, const cl_float *depth, cl_float *out,
+                      const rtHipDepthOfFieldParams *params)
+{
+    if (rtHipDepthOfFieldCheck(params) != 0 || dof_size_ok(width, height) != 0) return -1;
+    if (!colour || !depth || !out) return fail("depth of field: null array");
+    HIP_OK(hipSetDevice(device));
+    const size_t n = (size_t)width * height;
+    HostStage dev;
+    const float *c = dev.up(colour, n * 12), *z = dev.up(depth, n * 4);
+    float *dout = dev.out<float>(n * 12);
+    char *scratch = dev.out<char>(rtHipDepthOfFieldScratchBytes(width, height));
+    if (dev.status != hipSuccess) return dev.failed();
+    if (dof_issue(width, height, c, z, dout, scratch, params, nullptr) != 0) return -1;
+    HIP_OK(hipMemcpy(out, dout, n * 12, hipMemcpyDeviceToHost));
+    HIP_OK(hipDeviceSynchronize());
+    return 0;
+}
+
+int rtHipSceneDepthOfField(rtHipScene *sc, const rtHipDepthOfFieldParams *params, cl_float *outRgb, cl_ushort *outR, cl_ushort *outG,
+                           cl_ushort *outB)
+{
+    if (!sc) return fail("depth of field: null scene");
+    if (rtHipDepthOfFieldCheck(params) != 0 || dof_size_ok(sc->width, sc->height) != 0) return -1;
+    if (!(sc->passMask & RT_HIP_PASS_DEPTH) || !sc->passBuf)
+        return fail("depth of field needs the depth pass on for this scene (rtHipScenePasses)");
+    if (whole_image_tiles(sc, "depth of field") != 0) return -1;
+    HIP_OK(hipSetDevice(sc->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (frame_finish(sc, sc->lastStream ? sc->lastStream : sc->stream, nullptr) != 0) return -1;
+    rtHipScene::DepthOfField &D = sc->dof;
+    const uint32_t W = sc->width, H = sc->height;
+    const size_t n = (size_t)W * H;
+    const auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    if (!D.buf) { // colour | depth | out | R | G | B | scratch
+        const uint64_t bytes = 2 * part(n * 12) + part(n * 4) + 3 * part(n * 2) + part(rtHipDepthOfFieldScratchBytes(W, H));
+        if (scene_block(sc, D.buf, bytes, "depth of field") != 0) return -1;
+    }
+    for (Event &e : D.ev) HIP_OK(e.make());
+    char *b = D.buf;
+    float *colour = (float *)b, *depth = (float *)(b + part(n * 12)), *out = (float *)(b + part(n * 12) + part(n * 4));
+    char *plane = (char *)out + part(n * 12);
+    const Planes planes = { (uint16_t *)plane, (uint16_t *)(plane + part(n * 2)), (uint16_t *)(plane + 2 * part(n * 2)) };
+    char *scratch = plane + 3 * part(n * 2);
+    hipStream_t st = sc->stream;
+    HIP_OK(hipEventRecord(D.ev[0], st));
+    HIP_OK(rdf_launch_scene_gather(W, H, sc->tilesX, sc->dev.tileIds, (uint32_t)sc->tileIds.size(), sc->dev.tileBuf, sc->passBuf, colour, depth,
+                                   st));
+    HIP_OK(hipEventRecord(D.ev[1], st));
+    if (dof_issue(W, H, colour, depth, out, scratch, params, st) != 0) return -1;
+    HIP_OK(hipEventRecord(D.ev[2], st));
+    if (outR || outG || outB) HIP_OK(rtt_launch_quantise((uint32_t)n, out, planes.r, planes.g, planes.b, st));
+    HIP_OK(hipEventRecord(D.ev[3], st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(&D.ms[i], D.ev[i], D.ev[i + 1]));
+    return scene_outputs_to_host(n, out, planes, outRgb, outR, outG, outB);
+}
+
+int rtHipSceneDepthOfFieldTimes(const rtHipScene *sc, cl_float *ms)
+{
+    if (!sc || !ms) return fail("null argument");
+    for (int i = 0; i < 3; ++i) ms[i] = sc->dof.ms[i];
+    return 0;
+}
+
+// The thin lens of the header, in double with + - * / and sqrt, each result rounded once to float (tests/dof_oracle.py: lens).
+int rtHipDepthOfFieldLens(const rtHipCamera *cam, cl_float apertureRadius, cl_float focus, rtHipDepthOfFieldParams *inout)
+{
+    if (!cam || !inout) return fail("depth of field: null argument");
+    const double tl[3] = { cam->eyeToTopLeft[0], cam->eyeToTopLeft[1], cam->eyeToTopLeft[2] };
+    const double lr[3] = { cam->leftToRight[0], cam->leftToRight[1], cam->leftToRight[2] };
+    const double tb[3] = { cam->topToBottom[0], cam->topToBottom[1], cam->topToBottom[2] };
+    const double nv[3] = { lr[1] * tb[2] - lr[2] * tb[1], lr[2] * tb[0] - lr[0] * tb[2], lr[0] * tb[1] - lr[1] * tb[0] };
+    const auto dot = [](const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    double h = dot(tl, nv);
+    if (h < 0) h = -h;
+    const double plane = h / std::sqrt(dot(nv, nv)), pitch = std::sqrt(dot(lr, lr));
+    if (!(std::isfinite(plane) && plane > 0 && std::isfinite(pitch) && pitch > 0))
+        return fail("depth of field: the camera's plane distance %g or pixel pitch %g is zero or not finite", plane, pitch);
+    const double focalPixels = plane / pitch;
+    const float cocScale = (float)(((double)apertureRadius * focalPixels) / (double)focus);
+    if (dof_focus_ok(focus) != 0 || dof_coc_scale_ok(cocScale) != 0) return -1;
+    inout->focus = focus;
+    inout->cocScale = cocScale;
     return 0;
 }

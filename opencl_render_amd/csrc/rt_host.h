@@ -274,6 +274,14 @@ struct rtHipScene {
         rthost::Event ev[4];
         float ms[3] = {};
     } motionBlur;
+    // depth of field (rtHipSceneDepthOfField), made on its first call in one block: the gathered colour and depth, the blurred image, the
+    // u16 output planes and the filter's scratch.  ev: before the gather, after it, after the blur, after the output kernel; ms: the three
+    // spans of the last call.
+    struct DepthOfField {
+        rthost::Dev<> buf;
+        rthost::Event ev[4];
+        float ms[3] = {};
+    } dof;
     // camera moves (rtHipSceneSetCamera), made on the first move: the build scratch (slot tables, projected vertices, counts, big list,
     // control words, scan temporaries) in one block, and TWO sets of ranges + list -- a move builds into the set the frames do not read
     // and the sets change places at its end.  log: triangles per thread, per workgroup, entries of the last move; ms: device time of its

@@ -101,6 +101,12 @@ hipError_t rtt_launch_quantise(uint32_t n, const float *colour, uint16_t *outR, 
 hipError_t rmb_launch(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *depth, float *out, float *lz,
                       float *tileMax, float *nbMax, float shutter, float maxBlur, uint32_t taps, float depthSoftness, hipStream_t stream);
 
+// ---- rt_dof.hip (rz: 2 f32 per pixel; tileMax, nbMax: 1 f32 per 32 x 32 tile)
+hipError_t rdf_launch(uint32_t W, uint32_t H, const float *colour, const float *depth, float *out, float *rz, float *tileMax, float *nbMax,
+                      float focus, float cocScale, float maxCoc, uint32_t rings, float depthSoftness, hipStream_t stream);
+hipError_t rdf_launch_scene_gather(uint32_t W, uint32_t H, uint32_t tilesX, const uint32_t *tileIds, uint32_t tileCount,
+                                   const uint16_t *tileBuf, const uint32_t *passBuf, float *colour, float *depth, hipStream_t stream);
+
 // ---- rt_variance.hip
 hipError_t rtv_launch_moments(uint32_t W, uint32_t H, const float *colour, const float *motion, const float *prevT,
                               const uint32_t *triangle, const float *histColour, const float *histCount, const float *histT,

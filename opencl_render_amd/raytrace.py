@@ -101,6 +101,14 @@ class MotionBlurParams(C.Structure):  # rtHipMotionBlurParams
 MOTION_BLUR_DEFAULTS = dict(shutter=0.5, max_blur=16.0, taps=15, depth_softness=0.05)
 
 
+class DofParams(C.Structure):  # rtHipDepthOfFieldParams
+    _fields_ = [("focus", C.c_float), ("cocScale", C.c_float), ("maxCoc", C.c_float), ("rings", C.c_uint32), ("depthSoftness", C.c_float)]
+
+
+# rtHipDepthOfFieldDefaults (include/raytrace_hip.h, "DEPTH OF FIELD")
+DEPTH_OF_FIELD_DEFAULTS = dict(focus=1.0, coc_scale=8.0, max_coc=16.0, rings=3, depth_softness=0.05)
+
+
 class AoParams(C.Structure):  # rtHipAoParams
     _fields_ = [("raysPerHit", C.c_uint32), ("pixelSamples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -190,6 +198,8 @@ RESIDENT_SYMBOLS = [
     "rtHipTemporalMomentsClamp", "rtHipSceneSetTemporalClamp", "rtHipSceneGetTemporalClamp",
     "rtHipMotionBlurDefaults", "rtHipMotionBlurCheck", "rtHipMotionBlurScratchBytes", "rtHipMotionBlurDevice", "rtHipMotionBlur",
     "rtHipSceneMotionBlur", "rtHipSceneMotionBlurTimes",
+    "rtHipDepthOfFieldDefaults", "rtHipDepthOfFieldCheck", "rtHipDepthOfFieldScratchBytes", "rtHipDepthOfFieldDevice", "rtHipDepthOfField",
+    "rtHipSceneDepthOfField", "rtHipSceneDepthOfFieldTimes", "rtHipDepthOfFieldLens",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
     "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestRoundVisits", "rtHipTestShadeLog", "rtHipTestBuildLog",
@@ -361,6 +371,17 @@ def lib() -> C.CDLL:
     L.rtHipMotionBlur.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, blur]
     L.rtHipSceneMotionBlur.argtypes = [vp, blur, vp, vp, vp, vp]
     L.rtHipSceneMotionBlurTimes.argtypes = [vp, C.POINTER(C.c_float)]
+    dof = C.POINTER(DofParams)
+    L.rtHipDepthOfFieldDefaults.restype = None
+    L.rtHipDepthOfFieldDefaults.argtypes = [dof]
+    L.rtHipDepthOfFieldCheck.argtypes = [dof]
+    L.rtHipDepthOfFieldScratchBytes.restype = C.c_uint64
+    L.rtHipDepthOfFieldScratchBytes.argtypes = [u32, u32]
+    L.rtHipDepthOfFieldDevice.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, u64, dof, vp]
+    L.rtHipDepthOfField.argtypes = [C.c_int, u32, u32, vp, vp, vp, dof]
+    L.rtHipSceneDepthOfField.argtypes = [vp, dof, vp, vp, vp, vp]
+    L.rtHipSceneDepthOfFieldTimes.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rtHipDepthOfFieldLens.argtypes = [C.POINTER(Camera), C.c_float, C.c_float, dof]
     L.rtHipBakeDefaults.restype = None
     L.rtHipBakeDefaults.argtypes = [C.POINTER(BakeParams)]
     L.rtHipSceneBakeAmbientOcclusion.argtypes = [vp, C.POINTER(BakeParams), vp, vp]
@@ -711,7 +732,7 @@ def variance_params(iterations=VARIANCE_DEFAULTS["iterations"], luminance_sigma2
 
 
 class _Arrays:
-    """What denoise, temporal, temporal_moments, denoise_variance and motion_blur need of their arrays, for numpy (host entry point) or torch on
+    """What denoise, temporal, temporal_moments, denoise_variance, motion_blur and depth_of_field need of their arrays, for numpy (host entry point) or torch on
     cuda:`device` (device entry point on torch's current stream or `stream`)."""
 
     def __init__(self, who, on_gpu, device, stream):
@@ -795,6 +816,62 @@ def motion_blur(colour, motion, depth, shutter=MOTION_BLUR_DEFAULTS["shutter"], 
     if lib().rtHipMotionBlurDevice(device, W, H, *ptrs, A.address(scratch), nbytes, C.byref(p), A.stream_arg()) != 0:
         raise RuntimeError("rtHipMotionBlurDevice failed: " + last_error())
     A.done([colour, motion, depth, res, scratch])
+    return res
+
+
+def dof_params(focus=DEPTH_OF_FIELD_DEFAULTS["focus"], coc_scale=DEPTH_OF_FIELD_DEFAULTS["coc_scale"], max_coc=DEPTH_OF_FIELD_DEFAULTS["max_coc"],
+               rings=DEPTH_OF_FIELD_DEFAULTS["rings"], depth_softness=DEPTH_OF_FIELD_DEFAULTS["depth_softness"]) -> DofParams:
+    """rtHipDepthOfFieldParams from the Python keywords (the library checks the ranges)."""
+    if not 0 <= int(rings) <= 0xFFFFFFFF:  # (ctypes would wrap it into the uint32 field)
+        raise ValueError(f"depth of field: rings must be in 0..2^32-1 (got {rings})")
+    return DofParams(float(focus), float(coc_scale), float(max_coc), int(rings), float(depth_softness))
+
+
+def dof_lens(camera: dict, aperture: float, focus: float, **params) -> DofParams:
+    """rtHipDepthOfFieldLens: the parameters of a thin lens of radius `aperture` (scene units) focused at `focus` (scene units, along the
+    ray) for `camera` (the dict ResidentScene.camera() gives); the other parameters from the keywords of dof_params."""
+    cam = Camera()
+    for dst, key in ((cam.eye, "eye"), (cam.eyeToTopLeft, "eye_to_top_left"), (cam.leftToRight, "left_to_right"), (cam.topToBottom, "top_to_bottom")):
+        v = np.asarray(camera[key], np.float32).reshape(-1)
+        for i in range(3):
+            dst[i] = v[i]
+    cam.pixelSizeInv = np.float32(camera["pixel_size_inv"])
+    p = dof_params(**params)
+    if lib().rtHipDepthOfFieldLens(C.byref(cam), float(aperture), float(focus), C.byref(p)) != 0:
+        raise ValueError("rtHipDepthOfFieldLens failed: " + last_error())
+    return p
+
+
+def depth_of_field(colour, depth, focus=DEPTH_OF_FIELD_DEFAULTS["focus"], coc_scale=DEPTH_OF_FIELD_DEFAULTS["coc_scale"],
+                   max_coc=DEPTH_OF_FIELD_DEFAULTS["max_coc"], rings=DEPTH_OF_FIELD_DEFAULTS["rings"],
+                   depth_softness=DEPTH_OF_FIELD_DEFAULTS["depth_softness"], device: int = 0, stream: int = 0, out=None):
+    """The depth of field of include/raytrace_hip.h ("DEPTH OF FIELD"): the frame `colour` [H, W, 3] f32 blurred by the circle of
+    confusion `depth` [H, W] f32 gives every pixel -- "depth" of ResidentScene.readback_passes(), the distance along the ray, +inf on a
+    miss.  Returns the blurred image [H, W, 3] f32: `out` if given (it must not overlap an input), else a new array.  numpy arrays go
+    through rtHipDepthOfField (host arrays, synchronous); torch tensors on cuda:`device` stay there and go through
+    rtHipDepthOfFieldDevice on torch's current stream (or `stream`) with a torch scratch tensor."""
+    p = dof_params(focus, coc_scale, max_coc, rings, depth_softness)
+    if len(colour.shape) != 3 or colour.shape[2] != 3:
+        raise ValueError(f"depth_of_field: colour must be [H, W, 3] (got {tuple(colour.shape)})")
+    shape = (int(colour.shape[0]), int(colour.shape[1]))
+    given = [("colour", colour, shape + (3,)), ("depth", depth, shape)]
+    A = _Arrays("depth_of_field", any(hasattr(v, "data_ptr") for _, v, _ in given), device, stream)
+    for name, v, sh in given:
+        A.check(name, v, sh)
+    res = A.check("out", out, shape + (3,)) if out is not None else A.new(shape + (3,))
+    ptrs = [A.address(v) for v in (colour, depth, res)]
+    H, W = shape
+    if not A.on_gpu:
+        if lib().rtHipDepthOfField(device, W, H, *ptrs, C.byref(p)) != 0:
+            raise RuntimeError("rtHipDepthOfField failed: " + last_error())
+        return res
+    nbytes = lib().rtHipDepthOfFieldScratchBytes(W, H)
+    if nbytes == 0:
+        raise ValueError(f"depth_of_field: a {W} x {H} image is not 1..16384 pixels wide and high and 1..2^27 pixels")
+    scratch = A.new(nbytes, np.uint8)
+    if lib().rtHipDepthOfFieldDevice(device, W, H, *ptrs, A.address(scratch), nbytes, C.byref(p), A.stream_arg()) != 0:
+        raise RuntimeError("rtHipDepthOfFieldDevice failed: " + last_error())
+    A.done([colour, depth, res, scratch])
     return res
 
 
@@ -1673,6 +1750,48 @@ class ResidentScene:
         ms = (C.c_float * 3)()
         self._check(lib().rtHipSceneMotionBlurTimes(self.handle, ms), "rtHipSceneMotionBlurTimes")
         return dict(motion=ms[0], gather=ms[1], blur=ms[2])
+
+    def depth_of_field(self, aperture=None, focus=None, focus_pixel=None, **params) -> dict:
+        """The last frame blurred by its depth pass's circle of confusion on the device (rtHipSceneDepthOfField; keywords coc_scale,
+        max_coc, rings and depth_softness as for raytrace.depth_of_field): {"rgb": [H, W, 3] f32, "planes": [r, g, b] [H, W] u16,
+        "params": the keywords in effect}.  `focus`: the distance in focus along the ray; `focus_pixel` = (x, y): that pixel's depth
+        instead (a ValueError where its ray missed).  `aperture`: a thin lens of that radius in scene units through
+        rtHipDepthOfFieldLens and the scene's camera, which sets coc_scale.  Needs set_passes(depth=True) before the frame and every
+        tile of the image in this instance."""
+        sc = self.scene
+        if focus_pixel is not None:
+            if focus is not None:
+                raise ValueError("depth_of_field: focus and focus_pixel exclude each other")
+            if not getattr(self, "passes", 0) & PASS_DEPTH:
+                raise RuntimeError("depth_of_field: focus_pixel needs the depth pass (set_passes(depth=True))")
+            x, y = (int(v) for v in focus_pixel)
+            if not (0 <= x < sc.width and 0 <= y < sc.height):
+                raise ValueError(f"depth_of_field: focus_pixel {(x, y)} is not inside the {sc.width} x {sc.height} image")
+            depth = np.full((sc.height, sc.width), np.inf, np.float32)
+            self._check(lib().rtHipReadbackPasses(self.handle, None, _ptr(depth), None), "rtHipReadbackPasses")
+            focus = float(depth[y, x])
+            if not (np.isfinite(focus) and focus > 0):
+                raise ValueError(f"depth_of_field: the ray of focus_pixel {(x, y)} hit nothing (depth {focus})")
+        if focus is not None:
+            params["focus"] = focus
+        if aperture is not None:
+            if "coc_scale" in params:
+                raise ValueError("depth_of_field: aperture and coc_scale exclude each other")
+            p = dof_lens(self.camera(), aperture, params.pop("focus", DEPTH_OF_FIELD_DEFAULTS["focus"]), **params)
+        else:
+            p = dof_params(**params)
+        rgb = np.empty((sc.height, sc.width, 3), np.float32)
+        planes = [np.empty((sc.height, sc.width), np.uint16) for _ in range(3)]
+        self._check(lib().rtHipSceneDepthOfField(self.handle, C.byref(p), _ptr(rgb), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2])),
+                    "rtHipSceneDepthOfField")
+        used = dict(focus=p.focus, coc_scale=p.cocScale, max_coc=p.maxCoc, rings=p.rings, depth_softness=p.depthSoftness)
+        return {"rgb": rgb, "planes": planes, "params": used}
+
+    def depth_of_field_times_ms(self) -> dict:
+        """Device time of the last depth_of_field() (rtHipSceneDepthOfFieldTimes): gather of colour and depth, blur, output kernel."""
+        ms = (C.c_float * 3)()
+        self._check(lib().rtHipSceneDepthOfFieldTimes(self.handle, ms), "rtHipSceneDepthOfFieldTimes")
+        return dict(gather=ms[0], blur=ms[1], output=ms[2])
 
     def ambient_occlusion(self, rays=AO_DEFAULTS["rays"], radius=AO_DEFAULTS["radius"], pixel_samples=AO_DEFAULTS["pixel_samples"],
                           seed=AO_DEFAULTS["seed"], out=None, stream: int = 0):

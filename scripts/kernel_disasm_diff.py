@@ -16,7 +16,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = ("rt_kernels", "rt_wavefront", "rt_build_device", "rt_kat", "rt_scene_prep", "rt_denoise", "rt_temporal", "rt_variance",
-           "rt_camera_move", "rt_geometry_move", "rt_scene_edit", "rt_motion_blur")
+           "rt_camera_move", "rt_geometry_move", "rt_scene_edit", "rt_motion_blur", "rt_dof")
 
 
 def devflags(tree):
