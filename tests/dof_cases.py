@@ -16,11 +16,17 @@ SHAPES = ((1, 1), (1, 7), (7, 1), (31, 9), (33, 33), (64, 40))
 # seven tile columns: wide enough for tiles whose whole neighbourhood is in focus beside tiles that are not, so that `split` runs the copy
 # arm and the gather arm in ONE launch
 WIDE = (200, 40)
+# 4 x 3 tiles: tiles (1, 1) and (2, 1) have all eight neighbours, so (c) takes a maximum over a full 3 x 3 and a tile has one above AND below
+INTERIOR = (97, 70)
+# 1 x 257 tiles: the second workgroup of (c) (one lane per tile, 256 lanes) and block indices of (d) far past the first tile row.  W = 2,
+# so the numpy oracle stays cheap (16 400 pixels); it runs the ORDINARY settings only (grid_of)
+TALL = (2, 8200)
 FOCUS = 4.0  # what the fields call "in focus"
 FIELDS = ("focus", "constant", "near_sharp", "near_blurred", "ramp", "misses", "specials", "bright", "layers", "split")
 CASES = (tuple(("ramp", W, H) for W, H in SHAPES + (WIDE,)) + tuple(("layers", W, H) for W, H in ((31, 9), (33, 33), (64, 40), WIDE))
          + tuple((f, W, H) for f in ("focus", "near_sharp", "misses", "specials", "bright") for W, H in ((33, 33), (64, 40)))
-         + tuple((f, W, H) for f in ("constant", "near_blurred") for W, H in ((31, 9), (64, 40))) + (("split",) + WIDE,))
+         + tuple((f, W, H) for f in ("constant", "near_blurred") for W, H in ((31, 9), (64, 40))) + (("split",) + WIDE,)
+         + tuple((f,) + INTERIOR for f in ("layers", "near_sharp")) + tuple((f,) + TALL for f in ("ramp", "layers")))
 
 # The grid: the issue's extremes as a full product, and ordinary settings (every ring count; a cap of one pixel; a wide cap with a hard
 # depth test; an odd cap).  cocScale 0 and the smallest denormal copy the frame except where a depth makes `a` infinite.
@@ -32,6 +38,16 @@ ORDINARY = (tuple(dict(rings=r, max_coc=16.0, coc_scale=8.0, focus=FOCUS, depth_
                dict(rings=4, max_coc=7.5, coc_scale=12.0, focus=2.5, depth_softness=0.5)))
 GRID = ORDINARY + EXTREMES
 DEFAULT_LIKE = ORDINARY[2]  # rings 3, maxCoc 16, cocScale 8, focus FOCUS, depthSoftness 0.05
+
+
+def grid_of(W, H):
+    """The settings a case of W x H runs: the whole GRID, the ORDINARY ones alone at the tall shape."""
+    return ORDINARY if (W, H) == TALL else GRID
+
+
+# Scene path (tests/test_dof_gpu.py, and the dof steps of tests/session_cases.py): a moderate blur, and the widest one with a hard depth
+# test; the focus is the median depth of the frame's hits
+SCENE_PARAMS = (dict(coc_scale=12.0, max_coc=8.0, rings=3), dict(coc_scale=40.0, max_coc=32.0, rings=6, depth_softness=0.0))
 
 # Non-vacuity (test_dof.py asserts it on the oracle's intermediate results): `split` at 200 x 40 puts at least this share of its pixels
 # into each arm under DEFAULT_LIKE.  Measured: copy 0.320 (tile columns 0 and 1: column 2 neighbours column 3, which the boundary

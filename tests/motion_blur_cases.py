@@ -20,7 +20,19 @@ FIELDS = ("uniform", "split", "random", "ties")
 SPECIALS_SHAPE = (65, 34)
 TAPS, SHUTTERS, MAX_BLURS, SOFTNESS = (1, 2, 15, 64), (0.0, 0.5, 4.0), (1.0, 7.5, 32.0), (0.0, 0.05)
 GRID = tuple(dict(taps=t, shutter=s, max_blur=m, depth_softness=d) for t, s, m, d in itertools.product(TAPS, SHUTTERS, MAX_BLURS, SOFTNESS))
-CASES = tuple((f, W, H) for W, H in SHAPES for f in FIELDS) + (("specials",) + SPECIALS_SHAPE, ("split",) + WIDE, ("random",) + WIDE)
+# 1 x 257 tiles: the second workgroup of (c) (one lane per tile, 256 lanes) and block indices of (d) far past the first tile row.  W = 2
+# keeps the numpy oracle cheap (16 400 pixels); it runs TALL_GRID, every tap count once with the other settings varied (grid_of)
+TALL = (2, 8200)
+TALL_GRID = tuple(dict(taps=t, shutter=s, max_blur=m, depth_softness=d)
+                  for t, s, m, d in ((1, 0.5, 7.5, 0.05), (2, 4.0, 32.0, 0.0), (15, 0.5, 32.0, 0.05), (64, 4.0, 7.5, 0.0)))
+CASES = (tuple((f, W, H) for W, H in SHAPES for f in FIELDS) + (("specials",) + SPECIALS_SHAPE, ("split",) + WIDE, ("random",) + WIDE)
+         + (("random",) + TALL, ("ties",) + TALL))
+
+
+def grid_of(W, H):
+    """The settings a case of W x H runs: the whole GRID, TALL_GRID at the tall shape."""
+    return TALL_GRID if (W, H) == TALL else GRID
+
 
 # Non-vacuity conditions (test_motion_blur.py asserts them on the oracle's intermediate results): `split` and `random` each put this
 # share of the pixels of some tested case into the copy arm and into the gather arm, and `random` clamps this share.
@@ -76,9 +88,12 @@ def fields(name, W, H, seed=11):
         depth = np.where(right, F32(5.0), F32(1.0))
     elif name == "random":  # lengths 0..80 px in every direction: the cap, and ties among capped pixels (l == maxBlur exactly)
         length, angle = rng.random((H, W), dtype=F32) * F32(80.0), rng.random((H, W), dtype=F32) * F32(2 * np.pi)
+        if (W, H) == TALL:  # two pixels wide: only a velocity within a degree of the vertical keeps its taps inside the image, up or down
+            angle = (F32(np.pi / 2) + np.floor(angle / F32(np.pi)) * F32(np.pi) + (angle % F32(0.04) - F32(0.02))).astype(F32)
         motion[..., 0], motion[..., 1] = length * np.cos(angle), length * np.sin(angle)
     elif name == "ties":  # one length everywhere, signs that differ from pixel to pixel and from tile origin to tile origin
-        motion[..., 0] = np.where((x * 7 + y * 3) % 5 < 2, F32(6.0), F32(-6.0))
+        across = F32(0.25) if (W, H) == TALL else F32(6.0)  # (two pixels wide: nearly vertical, so that taps stay inside the image)
+        motion[..., 0] = np.where((x * 7 + y * 3) % 5 < 2, across, -across)
         motion[..., 1] = np.where((x + y * 11) % 3 == 0, F32(6.0), F32(-6.0))
     elif name == "specials":
         length, angle = rng.random((H, W), dtype=F32) * F32(24.0), rng.random((H, W), dtype=F32) * F32(2 * np.pi)

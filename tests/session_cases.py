@@ -51,7 +51,26 @@ call that brings host ids, refused or not, makes their staging of 4 bytes per tr
 checked on the device); matte_groups installs or frees the group table, which is state; mattes compares rtHipMatteDefaults with the
 model's last window and the four outputs with matte_oracle, bit for bit, over the sample ids of the current pose and shape and the
 table of the kind.  Whether a clone inherits the group table is left open by the header and is not checked.  Every sequence starts
-from a fresh scene under the scene's own look.  The caps of these seeds: edit_caps, shows_its_edits and histories_cross."""
+from a fresh scene under the scene's own look.  The caps of these seeds: edit_caps, shows_its_edits and histories_cross.
+
+Clamp and blurs.  The post seeds (KINDS_POST, on mirror_hall and, as a walk, on the four-tile axis_near_axis_mixed) add the temporal clamp
+to the state -- None or (mode, gamma), off in a fresh scene and in every clone, whatever its parent's -- and two products of the last
+frame that promise to change nothing.  clamp sets, changes or turns off the scene's clamp from CLAMP_SETTINGS, or hands over one
+setting of CLAMP_REFUSALS, which returns -1 with its text and leaves the setting as it was; after every step of a post sequence the
+scene's clamp (rs.temporal_clamp()) equals the model's.  While the clamp is on, temporal and temporal_variance equal
+temporal_clamp_oracle.accumulate over the same inputs as before (the variance step with the history's moments, which are not clamped:
+the model asserts on the oracles that count, moments and variance are the unclamped ones'); denoise= and filter= are applied after.
+motion_blur (one of motion_blur_cases.SCENE_PARAMS) equals motion_blur_oracle.blur of the LAST RENDERED planes / 65535 along the flow of
+the CURRENT state against the model's mark -- a stale frame keeps its colour under the new flow --, rgb bit for bit and the planes
+quantised; it is refused without a mark, renders a frame first where the scene has none, and leaves the mark where it was
+(same_mark against the mark's state), the history and the moments alone, which the later steps prove.  dof (one of
+dof_cases.SCENE_PARAMS) equals dof_oracle.blur of the model's planes / 65535 by the depth pass of the frame's twin, under the frame's
+window, the focus being the median of the depths that hit, handed to both sides as one number; it is refused without the depth pass
+in the mask, renders a frame first where there is none under the mask in effect (as read_passes does), gives the old frame's product
+for a stale pose or shape, and changes nothing.  Without a device the model takes the depth pass from its definition (oracle_depth),
+so that tests/test_session.py can measure the blurs and compare the model with the feature tests' own chains.  The draw of a passes
+step favours masks with the depth pass (MASKS_POST), the draw of a clamp step looks one kind ahead (Lite.upcoming) so that a temporal
+step directly follows the clamp being turned off over a history made under it; the caps: POST_FACTS and post_caps."""
 import ctypes
 
 import numpy as np
@@ -60,9 +79,13 @@ import ao_oracle
 import bake_oracle
 import camera_cases as CC
 import denoise_oracle as D
+import dof_cases as DC
+import dof_oracle as DO
 import edit_cases as EC
 import geometry_cases as GC
 import matte_oracle as MA
+import motion_blur_cases as BC
+import motion_blur_oracle as BO
 import motion_cases as MC
 import motion_oracle as MO
 import oracle_lib as O
@@ -70,6 +93,8 @@ import prep_oracle as P
 import query_cases as Q
 import sample_window_cases as WC
 import scenarios
+import temporal_clamp_cases as TCC
+import temporal_clamp_oracle as CO
 import temporal_oracle as TO
 import variance_oracle as VO
 from clip_checks import assert_bound
@@ -86,6 +111,9 @@ K = len(KINDS)
 KINDS_WIDE = KINDS + ("window", "variance")
 # The edit seeds of a scene draw from KINDS_EDIT: scene edits and mattes beside everything else (a circuit of 25 * 25 + 1 = 626 steps).
 KINDS_EDIT = KINDS_WIDE + ("lights", "materials", "ids", "refused_edit", "matte_groups", "mattes")
+# The post seeds of a scene draw from KINDS_POST: the temporal clamp, which is state, and the two blurs of the last frame, which promise to
+# change none (a circuit of 22 * 22 + 1 = 485 steps).
+KINDS_POST = KINDS_WIDE + ("clamp", "motion_blur", "dof")
 POSES = CC.POSES + ("shifted",)
 NEAR = ("home", "pan", "shifted")
 SURFACE = R.PASS_NORMAL | R.PASS_ALBEDO
@@ -104,9 +132,13 @@ MIN_WARM = 0.35  # of a seed's temporal steps follow another one of their sequen
 # takes no split logic rounds: playing its sequences once more under RT_WF_LOGIC_SPLIT=0 would run the same kernels, and is left out.
 # Its walk of 60 steps is cut in two (walk_cut, the second starting with the first's last kind): played whole it took 6.6 s on the device.
 # (Seed 106 meets the caps of the draw at its fifth attempt; 104, 105 and 107..109 meet the same caps after 100 to 630.)
+# post_circuits / post_walks: the seeds that draw from KINDS_POST.  axis_near_axis_mixed is 5 x 5 blur tiles of 32 pixels over its four scene
+# tiles, so its post walk runs the blurs' neighbourhood maxima on interior tiles and their scene gathers with slot > 0 and tilesX > 1;
+# post_walk_cut: that walk is cut shorter than the wide walk (see COUNTS_POST).
 SCENES = {"mirror_hall": dict(size=(24, 16), samples=2, circuits=(1, 2), walks=(101, 102), wide_circuits=(4,), wide_walks=(103,),
-                              shapes=GC.SEQUENCE, cut=40),
+                              post_circuits=(36,), post_walks=(118,), shapes=GC.SEQUENCE, cut=40),
           "axis_near_axis_mixed": dict(size=(136, 132), samples=2, circuits=(3,), walks=(), wide_circuits=(), wide_walks=(106,),
+                                       post_walks=(118,), post_walk_cut=16,
                                        shapes=tuple(n for n in GC.SEQUENCE if n != "translate"), cut=25, shape_steps=2, walk_cut=31),
           # class_textured_bumped is the one base scene of the opaque-diffuse class (six materials with one-texel height maps, a fifth
           # of the triangles without a material, one tube light, smooth normals); its seeds draw from KINDS_EDIT, and an edit walks
@@ -146,6 +178,31 @@ WINDOW_SHARES = dict(continuing=0.950, successive=0.987)
 # consecutive mattes under different states or tables differ.  27 states visited, hit share 0.107..0.539, changed share 0.034..0.688
 # over 53 moves.
 COUNTS_EDIT = dict(sequences=19, steps=703)
+# The post seeds (tests/test_session.py prints the figures and asserts the counts; every figure is the oracles', none the device's):
+# over the three seeds (mirror_hall's circuit 36 in 14 sequences and its walk 118; axis_near_axis_mixed's walk 118 in 5 sequences of at
+# most 16 steps -- cut as its wide walk is, at 31, its first half took 4.9 s on the device, above the sizing rule of
+# tests/test_session_gpu.py) 8 temporal steps run under the clamp with a live history and max_history above 1 (5 + 2 + 1) and 3
+# variance steps with live moments (2 + 1 + 0); 2 temporal steps with max_history above 1 directly follow the step that turned the
+# clamp off over a history made under it (the circuit's and the small walk's); of 23 motion blurs 9 have a mark that differs from the
+# current state (7 + 1 + 1), 9 blur a stale frame and 3 stand between two temporal steps with no reset and no variance step between,
+# the second under max_history above 1; of 15 depths of field 3 follow a mask change with no frame between, 4 blur a frame of another
+# window than the default and 5 a stale frame.  POST_SHARES: of the 22 accumulation steps under the clamp 11 find a live history
+# under max_history above 1, and there the clamped oracle's colour differs from the unclamped oracle's in 0.265 of the pixels on
+# average (0.000..0.607; in some pixel in 10 of the 11), while counts, moments and variance are the unclamped ones' bit for bit; the
+# motion blurs gather in 0.391 of their pixels on average -- in all pixels of the 9 whose mark differs from the state, which change
+# their frame, in none of the 14 whose mark is the state, which return it (a circuit holds the pairs (mark, motion_blur), (temporal,
+# motion_blur) and (variance, motion_blur), and which steps lie between a mark and a blur is the circuit's order, not the draw's; every
+# walk must hold a blur that gathers) --; every depth of field gathers in all pixels (the focus is the median depth, so every
+# 32-pixel tile neighbours one out of focus) and changes its frame.  The test asserts half of each share.
+COUNTS_POST = dict(sequences=20, steps=622)
+POST_SHARES = dict(clamped=0.265, motion_blur_gathered=0.391, dof_gathered=1.000)
+# The clamp's settings (None: off; every mode, gammas from 0, where the variance box is the mean itself) and the settings that
+# rtHipTemporalClampCheck refuses, with a word of its text: a refused step returns -1 and leaves the setting as it was.
+CLAMP_SETTINGS = (None,) + tuple((mode, gamma) for mode in TCC.MODES for gamma in (0.0, 0.5, 1.0, 2.5))
+CLAMP_REFUSALS = (((4, 1.0), "mode 4"), ((0, 0.5), "mode 0"), ((3, -1.0), "gamma"), ((2, -0.25), "gamma"))
+# The masks a post seed's passes step draws from: mostly with the depth pass, which the depth of field needs, and with both surface
+# passes, which the denoisers need.
+MASKS_POST = (31, SURFACE | R.PASS_DEPTH, 30, 7, 31, R.PASS_DEPTH, SURFACE, 0, SURFACE | R.PASS_DEPTH)
 WINDOW_SIZES = (2, 3, 4)  # N / S of a drawn window
 VARIANCE_FILTER = dict(iterations=2, spatial_below=2.0)
 SMALL = "mirror_hall"  # AO and the bake are also compared with their numpy oracles here
@@ -252,7 +309,7 @@ class World:
         self.base = MC.base_scene(name, self.size) if look is None else self.dressed(self.geo.base)
         self.width, self.height = self.base.width, self.base.height
         self._shape, self._state, self._planes, self._trace, self._flow, self._prep, self._window = {}, {}, {}, {}, {}, {}, {}
-        self._ids = {}
+        self._ids, self._depth, self._blurred = {}, {}, {}
         assert self.base.sample_count == SCENES[name]["samples"]
 
     def dressed(self, sc):
@@ -340,6 +397,62 @@ class World:
         if (cur, ref) not in self._flow:
             self._flow[cur, ref] = MO.project(self.state(*cur), self.state(*ref), self.trace(*cur))
         return self._flow[cur, ref]
+
+    def depth(self, pose, shape, total, first):
+        """The depth pass of a frame of the state that renders sample ids first+1 .. of a sequence of `total`, by its definition
+        (oracle_depth): what the model without a device blurs by; on the device the twin's pass is read instead."""
+        if self.look is not None:
+            return self.geo.depth(pose, shape, total, first)
+        if (pose, shape, total, first) not in self._depth:
+            self._depth[pose, shape, total, first] = oracle_depth(self.state(pose, shape), total, first)
+            self._depth[pose, shape, total, first].setflags(write=False)
+        return self._depth[pose, shape, total, first]
+
+    def motion_blurred(self, planes, cur, ref, variant):
+        """motion_blur_oracle.blur (with its parts) of the planes / 65535 along the flow of `cur` against `ref` under
+        motion_blur_cases.SCENE_PARAMS[variant]; cached per what the planes hold, so that a module's fixture can make it beforehand."""
+        key = (cur, ref, variant) + tuple(np.asarray(p).tobytes() for p in planes)  # (the bytes themselves: the planes are small)
+        if key not in self._blurred:
+            flow = self.flow(cur, ref)
+            colour = np.stack(planes, -1).astype(F32) / F32(65535.0)
+            self._blurred[key] = BO.blur(colour, flow["motion"], flow["t"], **BC.SCENE_PARAMS[variant], with_parts=True)
+        return self._blurred[key]
+
+
+def oracle_depth(sc, total, first):
+    """[H, W] f32: the DEPTH pass as include/raytrace_hip.h defines it, for a frame whose first sample has id first + 1 in a sequence
+    of `total`: that sample's ray (seed p * total + first + 1, LR jitter, then TB) against the pixel's camera list in order with a
+    running closest hit, t * |d|; +inf on a miss.  (sample_window_cases.window_passes restates every pass; this is its depth alone.)"""
+    C = ctypes
+    L = O.oracle()
+    f3 = C.c_float * 3
+    W, H = sc.width, sc.height
+    eye = f3(*[float(v) for v in np.asarray(sc.eye, F32)[:3]])
+    tl, lr, tb = (np.asarray(v, F32)[:3] for v in (sc.eye_to_top_left, sc.left_to_right, sc.top_to_bottom))
+    corners = np.asarray(sc.vertex, F32)[np.asarray(sc.tri_index)[:, :3], :3]
+    verts = {}
+    depth = np.full(H * W, np.inf, F32)
+    t, l1, l2 = C.c_float(), C.c_float(), C.c_float()
+    start, end, cam = np.asarray(sc.cam_start), np.asarray(sc.cam_end), np.asarray(sc.cam_list)
+    for p in range(H * W):
+        state = C.c_uint64(p * total + first + 1)
+        kx = F32(p % W) + F32(L.rt_oracle_randf(C.byref(state), 0.0, 1.0))
+        ky = F32(p // W) + F32(L.rt_oracle_randf(C.byref(state), 0.0, 1.0))
+        d = tl.copy()
+        d = d + lr * kx
+        d = d + tb * ky
+        dc = f3(*[float(v) for v in d])
+        best_t = None
+        for c in cam[int(start[p]):int(end[p])]:
+            c = int(c)
+            if c not in verts:
+                verts[c] = [f3(*[float(v) for v in corner]) for corner in corners[c]]
+            a, b, cc = verts[c]
+            if L.rt_oracle_ray_triangle(eye, dc, 0.0, float(np.inf if best_t is None else best_t), a, b, cc, C.byref(t), C.byref(l1), C.byref(l2)):
+                best_t = F32(t.value)
+        if best_t is not None:
+            depth[p] = best_t * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    return depth.reshape(H, W)
 
 
 _worlds = {}
@@ -460,8 +573,15 @@ class CapLog:
 
 
 class Lite:
-    def __init__(self, pose="home", shape="home", samples=2, name=None):
+    def __init__(self, pose="home", shape="home", samples=2, name=None, post=False):
         self.pose, self.shape, self.mask, self.pipeline = pose, shape, 0, R.PIPELINE_WAVEFRONT
+        # the post seeds (post: the steps may be of KINDS_POST): the temporal clamp, None or (mode, gamma), and what the caps of their draw
+        # ask, as ("post", fact) events of self.log -- the history the accumulation keeps (None, or whether its last step ran under the
+        # clamp and which kind it was), whether its moments are live, whether the step before turned the clamp off over a history made
+        # under it, and whether a motion blur has been made since the last temporal step with no reset between
+        self.post, self.clamp = post, None
+        self.p_hist, self.p_moments, self.p_just_off, self.p_blurred = None, False, False, False
+        self.upcoming = None  # (while a post seed is drawn: the kind of the step after the one being drawn, or None)
         # the edit seeds (name: the scene whose look tables the steps index): the look in effect and the one the last frame was
         # rendered under, the group table (the seed of group_table, or None), and what the caps of the draw ask (self.log)
         self.name = name
@@ -495,6 +615,12 @@ class Lite:
             return bool(arg)  # the subset's temporal() is refused
         if kind == "mattes":
             return arg[0] == "group" and self.groups is None
+        if kind == "clamp":
+            return arg is not None and arg[0] == "refused"
+        if kind == "motion_blur":  # (no shape of geometry_cases.SEQUENCE changes the triangle count, so the header's "reference made
+            return self.mark is None  # for another triangle count" cannot occur: tests/test_session.py asserts it)
+        if kind == "dof":
+            return not self.mask & R.PASS_DEPTH
         return kind in ("refused_update", "refused_camera", "refused_edit")
 
     def renders(self, uses_passes):
@@ -525,10 +651,13 @@ class Lite:
 
     def _advance(self, step):
         kind, arg = step
+        just_off, self.p_just_off = self.p_just_off, False
         if self.refuses(step) and kind != "clone":
             if kind == "mattes":
                 self.log.events.append(("mattes", dict(kind=arg[0], refused=True)))
             return
+        if self.post:
+            self.post_facts(kind, arg, just_off)
         if kind in ("lights", "materials", "ids"):
             new = self.after(step)
             self.log.events.append(("edit", kind, self.cls(), self.cls(new), self.look, new))
@@ -562,8 +691,10 @@ class Lite:
             self.mark = (self.pose, self.shape)
         elif kind == "window":
             self.window_next, self.run = (arg if arg is not None else (self.samples, 0, self.samples, 0, 0)), None
-        if (kind == "frame" or (kind in ("read_passes", "denoise") and self.renders(True))
-                or (kind in ("temporal", "variance") and self.renders(arg[0]))):
+        elif kind == "clamp":
+            self.clamp = arg
+        if (kind == "frame" or (kind in ("read_passes", "denoise", "dof") and self.renders(True))
+                or (kind in ("temporal", "variance") and self.renders(arg[0])) or (kind == "motion_blur" and self.renders(False))):
             self.render_frame()
         if kind in ("temporal", "variance"):
             self.mark = (self.pose, self.shape)
@@ -573,6 +704,39 @@ class Lite:
             self.log.events.append((kind, self.across(kind, arg[1])))
             self.log.hist_classes = (self.log.hist_classes if self.blends(kind, arg[1]) else set()) | {self.cls(self.frame_look)}
             self.log.moments_live = kind == "variance"
+
+    def post_facts(self, kind, arg, just_off):
+        """What the caps of the post seeds ask about a step that is not refused, noted before it takes effect (POST_FACTS), and the
+        light state they are counted from."""
+        fact = lambda name: self.log.events.append(("post", name))  # noqa: E731
+        if kind in ("temporal", "variance"):
+            if self.clamp is not None and self.p_hist is not None and (kind == "temporal" or self.p_moments) and arg[1] > 1:
+                fact(f"{kind}_clamped_live")  # under the clamp with a live history (a variance step: with live moments)
+            # (max_history above 1 in all three: at 1 the history is not blended in, and neither clamp, mark nor history could show)
+            if kind == "temporal" and just_off and self.log.prev == "clamp" and arg[1] > 1:
+                fact("temporal_after_off")  # directly after the clamp was turned off, over a history made under it
+            if kind == "temporal" and self.p_blurred and arg[1] > 1:
+                fact("blur_between_temporal")  # a motion blur since the temporal step that made the history, no reset or variance step between
+            self.p_hist, self.p_moments, self.p_blurred = (self.clamp is not None, kind), kind == "variance", False
+        elif kind == "reset_temporal":
+            self.p_hist, self.p_moments, self.p_blurred = None, False, False
+        elif kind == "clamp":
+            self.p_just_off = arg is None and self.clamp is not None and self.p_hist is not None and self.p_hist[0]
+        elif kind == "motion_blur":
+            fact("motion_blur")
+            if self.mark != (self.pose, self.shape):
+                fact("blur_mark_differs")  # the mark differs from the current state in pose or shape
+            if self.frame is not None and self.frame[:2] != (self.pose, self.shape):
+                fact("blur_stale")  # the colour of the old pose under the flow of the current one
+            self.p_blurred = self.p_hist is not None and self.p_hist[1] == "temporal"
+        elif kind == "dof":
+            fact("dof")
+            if self.frame is not None and self.frame[2] != self.mask:
+                fact("dof_after_mask_change")  # the mask changed with no frame between: the step renders one first
+            elif self.frame is not None and self.frame[:2] != (self.pose, self.shape):
+                fact("dof_stale")  # the old frame's colour and depth
+            if window_kind(self.window_next if self.renders(True) else self.window_last, self.samples) != "default":
+                fact("dof_window")  # the frame it blurs was rendered under another window than the default
 
     def blends(self, kind, cap):
         """Whether a temporal or variance step made now can blend the history into its frame: there is one, a variance step finds its
@@ -624,9 +788,10 @@ def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
     if kind == "shape":
         return pick([n for n in shapes if n != s.shape])
     if kind == "passes":
+        masks = MASKS_POST if s.post else MASKS
         if s.pipeline == R.PIPELINE_MEGAKERNEL:
-            return pick([m for m in MASKS if m]) if dare else 0
-        return pick(MASKS)
+            return pick([m for m in masks if m]) if dare else 0
+        return pick(masks)
     if kind == "pipeline":
         if s.mask:
             return R.PIPELINE_MEGAKERNEL if dare else R.PIPELINE_WAVEFRONT
@@ -639,7 +804,10 @@ def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
         return int(rng.integers(1 << 20))
     if kind == "temporal":
         on = rng.random() < 0.5 if s.mask & SURFACE == SURFACE else dare
-        return (bool(on), int(pick(MAX_HISTORY)))
+        # (the post seeds: over a live history under the clamp, directly after it was turned off, or after a motion blur, a cap that
+        # lets the history show, and with it the clamp, the setting turned off, or a mark or history that the blur moved)
+        shows = s.post and s.p_hist is not None and (s.clamp is not None or s.p_blurred or s.p_just_off)
+        return (bool(on), int(pick(MAX_HISTORY[1:] if shows else MAX_HISTORY)))
     if kind == "refused_update":
         return (pick(UPDATE_REFUSALS), pick([n for n in shapes if n != s.shape]))
     if kind == "refused_camera":
@@ -649,7 +817,9 @@ def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
     if kind == "variance":
         on = rng.random() < 0.5 if s.mask & SURFACE == SURFACE else dare
         # (the edit seeds: over live moments of another class than the look's, a cap that lets the history show)
-        return (bool(on), int(pick(MAX_HISTORY[1:] if s.name and s.log.moments_live and s.log.hist_classes - {s.cls()} else MAX_HISTORY)))
+        # (the post seeds: likewise under the clamp over live moments)
+        return (bool(on), int(pick(MAX_HISTORY[1:] if (s.name and s.log.moments_live and s.log.hist_classes - {s.cls()})
+                                   or (s.post and s.clamp is not None and s.p_moments) else MAX_HISTORY)))
     if kind == "window":
         S = s.samples
         if dare:  # one of the refusals that apply to a scene of S samples: returns -1 with its text and changes nothing
@@ -666,6 +836,19 @@ def draw(rng, kind, s, may_refuse, tiles, shapes, seen=()):
         if r < 0.85:
             return (N, 0, S, 1, 1)  # over-bright progressive: every frame at full brightness on top of the frames before
         return (N, int(rng.integers(1, N - S + 1)), int(pick((1, 3, S, N))), 0, 0)  # fixed, off the grid of S where N allows
+    if kind == "clamp":
+        if dare:  # one setting that rtHipTemporalClampCheck refuses: returns -1 with its text and changes nothing
+            setting, text = pick(CLAMP_REFUSALS)
+            return ("refused", setting, text)
+        # off again where a temporal step follows over a history made under the clamp, so that the step shows whether "off" took effect
+        # (s.upcoming: the draw looks one kind ahead), and in some draws otherwise; else another setting than the one in effect
+        if s.clamp is not None and ((s.upcoming == "temporal" and s.p_hist is not None and s.p_hist[0]) or rng.random() < 0.15):
+            return None
+        return pick([c for c in CLAMP_SETTINGS[1:] if c != s.clamp])
+    if kind == "motion_blur":
+        return int(rng.integers(len(BC.SCENE_PARAMS)))
+    if kind == "dof":
+        return int(rng.integers(len(DC.SCENE_PARAMS)))
     if s.name:
         return draw_edit(rng, pick, kind, s, dare)
     return None
@@ -736,15 +919,17 @@ def eulerian(rng, K=K):
     return path[::-1]
 
 
-def _piece(rng, kinds, start, tiles, shapes, seen, samples=2, name=None):
+def _piece(rng, kinds, start, tiles, shapes, seen, samples=2, name=None, post=False):
     """Steps for `kinds` from a fresh scene at `start`, and what the caps ask about them: (steps, refusals after each step, temporal
     steps on an older frame, motion steps with camera and shape both changed, temporal steps, the warm ones among them, each as the
     index of the step; and of the variance steps [(index, warm, stale moments over a live history)])."""
-    s, steps, refused, stale, mixed = Lite(*start, samples=samples, name=name), [], [], [], []
+    s, steps, refused, stale, mixed = Lite(*start, samples=samples, name=name, post=post), [], [], [], []
+    alphabet = KINDS_POST if post else KINDS_EDIT  # (KINDS and KINDS_WIDE are the beginning of both)
     seen, hist, temporal, warm = set(seen), False, [], []
     moments, variance = False, []
     for i, k in enumerate(kinds):
-        kind = KINDS_EDIT[k]
+        kind = alphabet[k]
+        s.upcoming = alphabet[kinds[i + 1]] if post and i + 1 < len(kinds) else None
         step = (kind, draw(rng, kind, s, (sum(refused[-1:]) + 1) <= MAX_REFUSED * (i + 1), tiles, shapes, seen))
         refused.append((refused[-1] if refused else 0) + bool(s.refuses(step)))
         if kind == "temporal" and not s.refuses(step) and not s.renders(step[1][0]) and s.frame[:2] != (s.pose, s.shape):
@@ -775,12 +960,12 @@ def _attempt(name, seed, attempt):
     key = [SCENE_KEY[name], seed, attempt]
     tiles = R.tile_count(*spec["size"])
     alphabet = kinds_of(name, seed)
-    edit, wide = alphabet is KINDS_EDIT, alphabet is KINDS_WIDE
-    walk = seed in spec["walks"] + spec["wide_walks"] + spec.get("edit_walks", ())
-    lite = dict(samples=spec["samples"], name=name if edit else None)
+    edit, wide, post = alphabet is KINDS_EDIT, alphabet is KINDS_WIDE, alphabet is KINDS_POST
+    walk = seed in spec["walks"] + spec["wide_walks"] + spec.get("edit_walks", ()) + spec.get("post_walks", ())
+    lite = dict(samples=spec["samples"], name=name if edit else None, post=post)
     k = len(alphabet)
     kinds = [int(v) for v in np.random.default_rng(key).integers(k, size=WALK)] if walk else eulerian(np.random.default_rng(key), k)
-    limit = spec.get("walk_cut", WALK) if walk else spec["cut"]
+    limit = walk_limit(name, seed) if walk else spec["cut"]
     whole = walk and limit == WALK  # (a walk is one sequence, unless the scene cuts its walks as it cuts a circuit)
     budget = [400]  # pieces tried: a draw that needs more is given up
 
@@ -823,6 +1008,8 @@ def _attempt(name, seed, attempt):
     if edit and not (walk or (edit_caps(edit_facts(frames, events)) and shows_its_edits(name, frames, events)
                               and histories_cross(across_notes(name, out)))):
         return None  # (the caps of the edit seeds are the circuit's to meet: the walk adds to them)
+    if post and not post_caps(post_counts(events), walk, tiles):
+        return None
     if not walk and not (stale and mixed and seen >= set(POSES) | set(spec["shapes"])):
         return None  # (the camera draw favours the near poses: a circuit still visits every pose and every shape)
     return out
@@ -850,6 +1037,39 @@ def wide_caps(frames, variance, walk):
             and 2 * sum(f["moved"] for f in cont) >= len(cont) and 3 * sum(w for _, w, _ in variance) >= len(variance)):
         return False
     return walk or (any(f["kind"] == "overbright" for f in cont) and bool(pairs))
+
+
+# What the caps of the post seeds count (Lite.post_facts notes each as it occurs, refused steps never): a temporal step under the clamp
+# with a live history and max_history above 1; a variance step under the clamp with live moments and max_history above 1; a temporal
+# step with max_history above 1 directly after the clamp was turned off, over a history whose last step ran under it; the blurs that
+# are not refused; a motion blur whose mark differs from the current state in pose or shape; one of a stale frame; one between two
+# temporal steps with no reset and no variance step between, the second with max_history above 1 (counted at that step); a depth of
+# field after the mask changed with no frame between; one of a frame rendered under another window than the default; one of a stale
+# frame.
+POST_FACTS = ("temporal_clamped_live", "variance_clamped_live", "temporal_after_off", "motion_blur", "blur_mark_differs", "blur_stale",
+              "blur_between_temporal", "dof", "dof_after_mask_change", "dof_window", "dof_stale")
+
+
+def post_counts(events):
+    """How often each of POST_FACTS occurs in Lite.log.events (one list per sequence)."""
+    return {k: sum(e == ("post", k) for part in events for e in part) for k in POST_FACTS}
+
+
+def post_caps(counts, walk, tiles):
+    """What a post seed's draw must hold, so that over the post seeds together every one of POST_FACTS occurs at least twice
+    (tests/test_session.py asserts that).  The circuit: each twice, but the temporal step directly after the clamp was turned off
+    once -- a circuit holds the pair (clamp, temporal) once (the draw of a clamp step looks one kind ahead for it); the small scene's
+    walk brings the second.  Every walk: a motion blur whose mark differs from the current state (one that gathers: with the mark at
+    the state the blur returns its frame) and a depth of field that is not refused.  The larger scene's walk, where the blurs run on
+    several tiles and the sequences are short: a temporal or variance step under the clamp with a live history, and a depth of field
+    of a stale frame or under another window."""
+    if not walk:
+        return all(counts[k] >= (1 if k == "temporal_after_off" else 2) for k in POST_FACTS)
+    if not (counts["blur_mark_differs"] >= 1 and counts["dof"] >= 1):
+        return False
+    if tiles == 1:
+        return counts["temporal_after_off"] >= 1
+    return counts["temporal_clamped_live"] + counts["variance_clamped_live"] >= 1 and counts["dof_stale"] + counts["dof_window"] >= 1
 
 
 def edit_facts(frames, events):
@@ -955,9 +1175,16 @@ def histories_cross(notes):
     return all(any(k == kind and f["blended"] > 0 and f["differs"] > 0 for k, f in notes) for kind in ("temporal", "variance"))
 
 
+def walk_limit(name, seed):
+    """The most steps a sequence of the walk seed may have: WALK (the walk is one sequence) unless the scene cuts its walks (walk_cut),
+    its post walk shorter still where it says so (post_walk_cut)."""
+    spec = SCENES[name]
+    return spec.get("post_walk_cut" if seed in spec.get("post_walks", ()) and "post_walk_cut" in spec else "walk_cut", WALK)
+
+
 def lite_of(name, seed, start):
     """The light state a sequence of the seed starts from."""
-    return Lite(*start, samples=SCENES[name]["samples"], name=name if is_edit(name, seed) else None)
+    return Lite(*start, samples=SCENES[name]["samples"], name=name if is_edit(name, seed) else None, post=is_post(name, seed))
 
 
 def kinds_of(name, seed):
@@ -965,12 +1192,18 @@ def kinds_of(name, seed):
     of, so on a scene with edit seeds its steps index the look tables."""
     if seed in REGRESSIONS:
         return KINDS_EDIT if edit_seeds(name) else KINDS
-    return KINDS_EDIT if seed in edit_seeds(name) else KINDS_WIDE if seed in seeds_of(name, wide=True) else KINDS
+    return (KINDS_EDIT if seed in edit_seeds(name) else KINDS_POST if seed in post_seeds(name)
+            else KINDS_WIDE if seed in seeds_of(name, wide=True) else KINDS)
 
 
 def is_edit(name, seed):
     """Whether the seed's steps index the scene's look tables."""
     return kinds_of(name, seed) is KINDS_EDIT
+
+
+def is_post(name, seed):
+    """Whether the seed's steps may be of KINDS_POST: the clamp is compared after every step."""
+    return kinds_of(name, seed) is KINDS_POST
 
 
 _sequences = {}
@@ -993,12 +1226,17 @@ def seeds_of(name, wide=None):
     """The scene's seeds: all of them, the wide ones (wide=True) or the oldest (wide=False); the edit seeds are edit_seeds'."""
     spec = SCENES[name]
     old, new = spec["circuits"] + spec["walks"], spec["wide_circuits"] + spec["wide_walks"]
-    return old + new + edit_seeds(name) if wide is None else new if wide else old
+    return old + new + edit_seeds(name) + post_seeds(name) if wide is None else new if wide else old
 
 
 def edit_seeds(name):
     """The scene's seeds that draw from KINDS_EDIT."""
     return SCENES[name].get("edit_circuits", ()) + SCENES[name].get("edit_walks", ())
+
+
+def post_seeds(name):
+    """The scene's seeds that draw from KINDS_POST."""
+    return SCENES[name].get("post_circuits", ()) + SCENES[name].get("post_walks", ())
 
 
 def all_parts():
@@ -1024,9 +1262,9 @@ def visited(name):
 def warm_wide(name):
     """The model alone over the scene's wide sequences: every window frame, flow and accumulation their checks read is made now (the
     caches are the World's), as World.warm does for the planes of the visited states."""
-    for seed in seeds_of(name, wide=True) + edit_seeds(name):
+    for seed in seeds_of(name, wide=True) + edit_seeds(name) + post_seeds(name):
         for q in sequences(name, seed):
-            s = Session(world(name), q["start"], edit=is_edit(name, seed))
+            s = Session(world(name), q["start"], edit=is_edit(name, seed), post=is_post(name, seed), warming=True)
             for step in q["steps"]:
                 s.apply(step)
 
@@ -1043,8 +1281,9 @@ class Session(Lite):
     """The model of one resident scene.  With rs (a ResidentScene created from world.state(*start)) every step is also made on the device
     and checked; without, the model advances alone and notes what tests/test_session.py asserts on (self.notes)."""
 
-    def __init__(self, w, start=("home", "home"), rs=None, edit=False):
-        super().__init__(*start, samples=w.base.sample_count, name=w.name if edit else None)
+    def __init__(self, w, start=("home", "home"), rs=None, edit=False, post=False, warming=False):
+        super().__init__(*start, samples=w.base.sample_count, name=w.name if edit else None, post=post)
+        self.warming = warming  # played to fill the World's caches only: what is not cached (the depth of field's oracle) is left out
         self.w, self.rs = w, rs  # (w: the World of the scene's own look, which holds what depends on geometry and camera alone)
         self.described_pose = start[0]
         self.planes = self.history = None
@@ -1071,6 +1310,8 @@ class Session(Lite):
         self.advance(step)
         if self.rs:
             self.same_window(f"after {kind}")
+            if self.post:
+                self.same_clamp(self.rs, self.clamp, f"after {kind}")
 
     # -- frames
     def do_frame(self):
@@ -1242,8 +1483,9 @@ class Session(Lite):
             assert bad.size == 0, f"ray query answers differ in {bad.size} of 256 rays"
 
     # -- motion and temporal accumulation
-    def same_mark(self, what):
-        cam, sc = self.rs.motion_reference_camera(), self.w.state(*self.here())
+    def same_mark(self, what, state=None):
+        """The reference camera is the camera of `state` (the current state: what a call that marks leaves)."""
+        cam, sc = self.rs.motion_reference_camera(), self.w.state(*(state or self.here()))
         for k in ("eye", "eye_to_top_left", "left_to_right", "top_to_bottom"):
             differs(cam[k][:3], np.asarray(getattr(sc, k), F32)[:3], f"{what}: the reference camera's {k}")
 
@@ -1275,7 +1517,10 @@ class Session(Lite):
         flow = self.w.flow(self.here(), self.mark or self.here())  # no mark yet: the call marks the current state first
         colour = np.stack(self.planes, -1).astype(F32) / F32(65535.0)
         hist = self.history if self.history is not None else TO.empty_history(self.w.height, self.w.width)
-        acc = TO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap), with_taps=True)
+        if self.clamp is None:
+            acc = TO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap), with_taps=True)
+        else:  # the scene's clamp is on: the clamped accumulation's colour and count
+            acc = self.clamped("temporal", colour, flow, hist, cap)
         self.notes.append(("temporal", self.frame[:2] != self.here(), float(acc["used"].mean())))
         if self.name and self.across("temporal", cap):
             fresh = TO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], TO.empty_history(self.w.height, self.w.width),
@@ -1310,7 +1555,10 @@ class Session(Lite):
         stale = self.history is not None and self.moments is None
         live = self.history is not None and not stale
         hist = dict(self.history, moments=self.moments) if live else VO.empty_history(self.w.height, self.w.width)
-        acc = VO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap))
+        if self.clamp is None:
+            acc = VO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap))
+        else:  # the scene's clamp is on: the colour is clamped, the moments (taken with the history's) are not
+            acc = self.clamped("variance", colour, flow, hist, cap)
         if not live:  # no history, or one that starts again: the frame itself
             assert (acc["count"] == 1.0).all() and (acc["variance"] == 0.0).all() and TO.same_bits(acc["colour"], colour).all()
         warm = self.history is not None and self.mark is not None and self.mark[1] == self.shape  # (as _piece counts it)
@@ -1336,6 +1584,21 @@ class Session(Lite):
         self.history = TO.next_history(dict(colour=acc["colour"], count=acc["count"]), flow["t"], flow["triangle"])
         self.moments = acc["moments"]
 
+    def clamped(self, kind, colour, flow, hist, cap):
+        """temporal_clamp_oracle.accumulate under the model's clamp (with the moments where `hist` has some); notes the share of the
+        pixels in which any output differs from the unclamped oracle's and, for a variance step, that the moments are the unclamped
+        ones' bit for bit (the header: "the moments are not clamped")."""
+        mode, gamma = self.clamp
+        acc = CO.accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap), mode=mode, gamma=gamma)
+        plain = (VO if kind == "variance" else TO).accumulate(colour, flow["motion"], flow["prev_t"], flow["triangle"], hist, max_history=float(cap))
+        assert TO.same_bits(acc["count"], plain["count"]).all(), "the clamp changed a history length"
+        if kind == "variance":
+            assert TO.same_bits(acc["moments"], plain["moments"]).all() and TO.same_bits(acc["variance"], plain["variance"]).all()
+        live = self.history is not None and (kind == "temporal" or self.moments is not None)
+        differs_in = float(1.0 - TO.same_bits(acc["colour"], plain["colour"]).all(-1).mean())
+        self.notes.append(("clamped", dict(kind=kind, live=live, cap=cap, clamp=self.clamp), differs_in))
+        return acc
+
     def note_across(self, kind, cap, blended, acc, fresh, outputs):
         """A step with a live history across a class change (Lite.across): the share of the pixels that blend the history in, and the
         share in which an expected output differs from the one over an empty history -- what the step would give had an edit or a class
@@ -1349,6 +1612,74 @@ class Session(Lite):
         if self.rs:
             self.rs.reset_temporal()
         self.history = self.moments = None
+
+    # -- the temporal clamp: state of the scene; the accumulation steps above follow it
+    @staticmethod
+    def same_clamp(rs, clamp, what):
+        want = None if clamp is None else dict(mode=clamp[0], gamma=clamp[1])
+        got = rs.temporal_clamp()
+        assert got == want, f"{what}: the scene's temporal clamp is {got}, the model's {want}"
+
+    def do_clamp(self, arg=None):
+        if not self.rs:
+            return
+        if self.refuses(("clamp", arg)):
+            _, (mode, gamma), text = arg
+            rc = int(R.lib().rtHipSceneSetTemporalClamp(self.rs.handle, ctypes.byref(R.temporal_clamp_params(mode, gamma))))
+            assert rc == -1 and text in R.last_error(), f"refused clamp {(mode, gamma)}: returned {rc} with {R.last_error()!r}, expected -1 with {text!r}"
+        elif arg is None:
+            self.rs.set_temporal_clamp(None)
+        else:
+            self.rs.set_temporal_clamp(*arg)
+
+    # -- the blurs of the last frame: they read the tile buffer (and the flow, or the depth word of the pass buffer) and change nothing,
+    # which the later steps prove
+    def do_motion_blur(self, variant):
+        """rs.motion_blur: the LAST rendered frame's colour along the flow of the CURRENT state against the mark; the mark stays."""
+        params = BC.SCENE_PARAMS[variant]
+        if self.refuses(("motion_blur", variant)):
+            if self.rs:
+                refusal(lambda: self.rs.motion_blur(**params), "no motion reference", "motion_blur without a mark")
+            return
+        self.need_frame(False)
+        parts = self.w.motion_blurred(self.planes, self.here(), self.mark, variant)
+        colour = np.stack(self.planes, -1).astype(F32) / F32(65535.0)
+        self.notes.append(("motion_blur", dict(stale=self.frame[:2] != self.here(), mark_differs=self.mark != self.here(),
+                                               gathered=float(parts["gathered"].mean()),
+                                               changed=not BO.same_bits(parts["out"], colour).all()), parts["out"]))
+        if self.rs:
+            got = self.rs.motion_blur(**params)
+            differs(got["rgb"], parts["out"], f"motion_blur rgb {params} at {self.here()} against the mark at {self.mark}, frame of {self.frame[:2]}")
+            for ch, g, x in zip("RGB", got["planes"], R.quantise(parts["out"])):
+                differs(g, x, f"motion_blur plane {ch}")
+            self.same_mark("motion_blur (the call does not mark)", self.mark)
+
+    def do_dof(self, variant):
+        """rs.depth_of_field: the last frame's colour by the depth pass of that frame, rendered first where there is none under the
+        mask in effect (as read_passes); the focus is the median of the depths that hit, handed over as the number both sides use."""
+        params = DC.SCENE_PARAMS[variant]
+        if self.refuses(("dof", variant)):
+            if self.rs:
+                refusal(lambda: self.rs.depth_of_field(focus=1.0, **params), "depth pass", "depth_of_field without the depth pass")
+            return
+        self.need_frame(True)
+        if self.warming:
+            return
+        pose, shape, mask, total, first = self.frame
+        depth = twin(self.fw, *self.frame)["passes"]["depth"] if self.rs else self.w.depth(pose, shape, total, first)
+        hit = depth[np.isfinite(depth) & (depth > 0)]
+        assert hit.size, f"the frame at {self.frame[:2]} hit nothing"
+        focus = float(np.median(hit))
+        colour = np.stack(self.planes, -1).astype(F32) / F32(65535.0)
+        parts = DO.blur(colour, depth, focus=focus, **params, with_parts=True)
+        self.notes.append(("dof", dict(stale=self.frame[:2] != self.here(), window=window_kind(self.window_last, self.samples), focus=focus,
+                                       gathered=float(parts["gathered"].mean()), changed=not DO.same_bits(parts["out"], colour).all()),
+                           parts["out"]))
+        if self.rs:
+            got = self.rs.depth_of_field(focus=focus, **params)
+            differs(got["rgb"], parts["out"], f"depth_of_field rgb {params}, focus {focus}, of the frame at {self.frame}")
+            for ch, g, x in zip("RGB", got["planes"], R.quantise(parts["out"])):
+                differs(g, x, f"depth_of_field plane {ch}")
 
     # -- refusals: one illegal argument each; nothing changes, which every later check proves
     def do_refused_update(self, arg):
@@ -1407,6 +1738,7 @@ class Session(Lite):
                 assert c.path_class() == R.path_class(self.lw.base), f"the clone's path class is {c.path_class()}, the look's {R.path_class(self.lw.base)}"
             S = self.samples  # a clone starts with the default window, whatever its model has, and renders the default window's frame
             assert c.sample_window()["next"] == dict(total=S, first=0, divisor=S, accumulate=0, advance=0), c.sample_window()
+            self.same_clamp(c, None, "a clone")  # the clamp is per scene and off by default, whatever the parent's (which apply() compares)
             self.same_bound(c, self.shape, "the clone's clip bound")
             c.render()
             got = [np.asarray(p).reshape(sc.height, sc.width) for p in c.readback()]
@@ -1564,8 +1896,9 @@ def play(name, seed, part, last=None, report=None):
     w = world(name)
     rs = R.ResidentScene(w.state(*seq["start"]), 0)
     try:
-        s = Session(w, seq["start"], rs, edit=is_edit(name, seed))
+        s = Session(w, seq["start"], rs, edit=is_edit(name, seed), post=is_post(name, seed))
         s.same_window("a fresh scene")
+        s.same_clamp(rs, None, "a fresh scene")
         for i, step in enumerate(steps):
             try:
                 s.apply(step)

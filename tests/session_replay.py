@@ -3,7 +3,9 @@ the tool for reducing a failure of tests/test_session_gpu.py (find the shortest 
 copy of the sequence under session_cases.REGRESSIONS).  One pass; nothing is tried again.
 usage: python tests/session_replay.py SCENE SEED [PART] [LAST_STEP]
 SEED: a circuit or walk seed of the scene (the wide seeds, which also draw window and variance steps, and the edit seeds, which also
-draw lights, materials, ids, refused_edit, matte_groups and mattes steps, included: session_cases.SCENES), or the name of a regression; PART: one sequence of the seed (default: all of them)."""
+draw lights, materials, ids, refused_edit, matte_groups and mattes steps, and the post seeds, which also draw clamp, motion_blur and dof
+steps and compare the scene's temporal clamp after every step, included: session_cases.SCENES), or the name of a regression; PART: one
+sequence of the seed (default: all of them)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

@@ -104,7 +104,7 @@ def test_the_scratch_formula(hip_lib):
     assert L.rtHipDepthOfFieldScratchBytes(0, 3) == 0 and L.rtHipDepthOfFieldScratchBytes(16385, 1) == 0
     assert L.rtHipDepthOfFieldScratchBytes(16384, 16384) == 0
     up16 = lambda b: (b + 15) // 16 * 16  # noqa: E731
-    for W, H in DC.SHAPES + (DC.WIDE, (1920, 1080), (16384, 8192)):
+    for W, H in DC.SHAPES + (DC.WIDE, DC.INTERIOR, DC.TALL, (1920, 1080), (16384, 8192)):
         tiles = ((W + 31) // 32) * ((H + 31) // 32)
         assert L.rtHipDepthOfFieldScratchBytes(W, H) == up16(W * H * 8) + 2 * up16(tiles * 4), (W, H)
     assert L.rtHipDepthOfFieldScratchBytes(33, 33) == 8720 + 2 * 16
@@ -136,15 +136,18 @@ def host_blur(tmp_path_factory):
 @pytest.mark.parametrize("name, W, H", DC.CASES)
 def test_the_kernels_pixel_code_on_the_host_equals_the_oracle_bit_for_bit(host_blur, name, W, H):
     fields = DC.fields(name, W, H)
-    for params in DC.GRID:
+    for params in DC.grid_of(W, H):
         want, got = DC.reference(name, W, H, params), host_blur(*fields, **params)
         bad = np.flatnonzero(~DO.same_bits(got, want).reshape(-1))
         assert bad.size == 0, f"{name} {W}x{H} {params}: differs in {bad.size} values, first {bad[:4]}"
 
 
 def test_every_shape_field_and_grid_value_is_among_the_cases():
-    assert {(W, H) for _, W, H in DC.CASES} == set(DC.SHAPES) | {DC.WIDE}
+    assert {(W, H) for _, W, H in DC.CASES} == set(DC.SHAPES) | {DC.WIDE, DC.INTERIOR, DC.TALL}
     assert {name for name, _, _ in DC.CASES} == set(DC.FIELDS)
+    assert all(DC.grid_of(W, H) is (DC.ORDINARY if (W, H) == DC.TALL else DC.GRID) for _, W, H in DC.CASES)
+    assert {n for n, W, H in DC.CASES if (W, H) == DC.INTERIOR} == {"layers", "near_sharp"}
+    assert {n for n, W, H in DC.CASES if (W, H) == DC.TALL} == {"ramp", "layers"}
     for key, values in (("rings", range(1, 7)), ("max_coc", (1.0, 32.0)), ("coc_scale", (0.0, DC.DENORMAL, 4096.0)),
                         ("focus", (DC.DENORMAL, 3e38)), ("depth_softness", (0.0, 3e38))):
         assert set(values) <= {p[key] for p in DC.GRID}, key
@@ -294,6 +297,24 @@ def test_the_synthetic_fields_take_both_arms_and_skip_taps_at_the_border():
     for name in ("near_sharp", "near_blurred", "ramp", "misses", "layers"):
         r = DO.blur(*DC.fields(name, 64, 40), **DC.DEFAULT_LIKE, with_parts=True)["r"]
         assert (r < 0.5).any() and (r > 2.0).any(), name  # sharp and blurred pixels side by side
+    # INTERIOR: three tile rows, so tiles with a neighbour above AND below and two with all eight; under `near_sharp` the disc in focus
+    # lies inside the middle row, whose tiles take their radius from the 3 x 3 maximum
+    for name in ("layers", "near_sharp"):
+        parts = DO.blur(*DC.fields(name, *DC.INTERIOR), **DC.DEFAULT_LIKE, with_parts=True)
+        assert parts["tile_max"].shape == (3, 4) and parts["gathered"].mean() >= DC.MIN_GATHER, name
+        assert not DO.same_bits(parts["out"], DC.fields(name, *DC.INTERIOR)[0]).all(), name
+    # TALL: 257 tiles in one column, the last past the first 256; along the ramp both arms are taken, the radius differs from tile to
+    # tile, and the last tiles take their maximum from the neighbour below, across the boundary between tiles 255 and 256
+    for name in ("ramp", "layers"):
+        parts = DO.blur(*DC.fields(name, *DC.TALL), **DC.DEFAULT_LIKE, with_parts=True)
+        assert parts["tile_max"].shape == (257, 1), name
+        assert parts["gathered"][8192:].all() and parts["taps"][8192:].max() > 0, name  # tile 256 gathers
+    ramp = DO.blur(*DC.fields("ramp", *DC.TALL), **DC.DEFAULT_LIKE, with_parts=True)
+    copy, gather = DC.shares(ramp)
+    print(f"ramp {DC.TALL}: copy {copy:.3f}, gather {gather:.3f}")
+    assert copy > 0 and gather >= DC.MIN_GATHER
+    assert not DO.same_bits(ramp["out"][8192:], DC.fields("ramp", *DC.TALL)[0][8192:]).all()  # (tile 256 is blurred: r = 6 there)
+    assert ramp["nb_max"][255, 0] == ramp["tile_max"][256, 0] > ramp["tile_max"][255, 0] and len(np.unique(ramp["nb_max"])) > 100
     tiny = next(p for p in DC.EXTREMES if p["coc_scale"] == DC.DENORMAL and p["focus"] == 3e38 and p["max_coc"] == 32.0)
     r = DO.blur(*DC.fields("specials", 64, 40), **tiny, with_parts=True)["r"]  # cocScale the smallest denormal
     assert 0 < (r >= 0.5).sum() < 40 and set(np.unique(r[r >= 0.5])) == {F32(32.0)}  # only where a depth makes `a` infinite

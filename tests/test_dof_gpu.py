@@ -2,8 +2,9 @@
 counts as equal), the output of the numpy restatement (dof_oracle.py) over the shapes, fields and the parameter grid of dof_cases.py;
 the device entry writes nothing outside W x H, takes a scratch full of garbage, and refuses overlaps, bad pointers, a short scratch and
 foreign streams and launches nothing; ResidentScene.depth_of_field equals the oracle on the scene's own read-back and depth pass, also
-after set_camera and set_vertices, needs the depth pass and every tile, makes its storage once and leaves the scene as a twin that never
-calls it; --dof writes what the API returns.  Every test needs the entry points of this feature, so all of them fail without it."""
+after set_camera and set_vertices, and on a scene of four scene tiles (the gather's slot > 0 and tilesX > 1), needs the depth pass
+and every tile, makes its storage once and leaves the scene as a twin that never calls it; --dof writes what the API returns.  Every
+test needs the entry points of this feature, so all of them fail without it."""
 import ctypes as C
 
 import numpy as np
@@ -45,7 +46,7 @@ def on_gpu(a):
 def test_host_and_device_entry_points_equal_the_oracle_bit_for_bit(name, W, H):
     fields = DC.fields(name, W, H)
     dev = [on_gpu(a) for a in fields]
-    for params in DC.GRID:
+    for params in DC.grid_of(W, H):
         want = DC.reference(name, W, H, params)
         assert_same(R.depth_of_field(*fields, **params), want, f"{name} {W}x{H} {params}: numpy")
         got = R.depth_of_field(*dev, **params)
@@ -144,7 +145,7 @@ def test_the_device_entry_refuses_overlaps_bad_pointers_a_short_scratch_and_fore
 
 # ---- the scene path -------------------------------------------------------------------------------------------------------------------
 SCENE, SIZE = "mirror_hall", (24, 16)  # the smallest scene the other scene tests use
-SCENE_PARAMS = (dict(coc_scale=12.0, max_coc=8.0, rings=3), dict(coc_scale=40.0, max_coc=32.0, rings=6, depth_softness=0.0))
+SCENE_PARAMS = DC.SCENE_PARAMS
 
 
 def move(rs, sc):
@@ -212,6 +213,31 @@ def test_the_scene_path_equals_the_oracle_also_after_set_camera_and_set_vertices
                 rs.depth_of_field(aperture=0.05, focus_pixel=(int(xs[0]), int(ys[0])))
         with pytest.raises(ValueError):
             rs.depth_of_field(aperture=0.05, focus_pixel=(sc.width, 0))
+    finally:
+        rs.close()
+
+
+def test_the_scene_path_on_four_scene_tiles_equals_the_oracle():
+    """axis_near_axis_mixed at 136 x 132: 2 x 2 scene tiles of 128 pixels, the right-hand and the lower ones partly filled, so the scene
+    gather runs with slot > 0 and tilesX > 1; 5 x 5 blur tiles, so interior ones exist."""
+    name = "axis_near_axis_mixed"
+    sc = MC.base_scene(name, MC.CAMERA_SCENES[name])
+    assert R.tile_count(sc.width, sc.height) == 4 and sc.width > 128 and sc.height > 128
+    rs = R.ResidentScene(sc, 0)
+    try:
+        rs.set_passes(depth=True)
+        for pose in ("home", "pan"):
+            if pose != "home":
+                move(rs, MC.posed(sc, pose))
+            share = dof_step(rs, f"{name}/{pose}")
+            assert share >= DC.MIN_GATHER, (pose, share)
+            # the blur reaches more than one scene tile: pixels of several 128 x 128 tiles differ from the frame
+            colour, depth = frame_colour(rs), rs.readback_passes()["depth"]
+            for params in SCENE_PARAMS:
+                out = DO.blur(colour, depth, focus=focus_of(depth), **params)
+                changed = ~DO.same_bits(out, colour).all(-1)
+                tiles = {(int(y) // 128, int(x) // 128) for y, x in zip(*np.nonzero(changed))}
+                assert len(tiles) > 1, (pose, params, tiles)
     finally:
         rs.close()
 

@@ -120,7 +120,7 @@ def host_blur(tmp_path_factory):
 @pytest.mark.parametrize("name, W, H", BC.CASES)
 def test_the_kernels_pixel_code_on_the_host_equals_the_oracle_bit_for_bit(host_blur, name, W, H):
     fields = BC.fields(name, W, H)
-    for params in BC.GRID:
+    for params in BC.grid_of(W, H):
         want, got = BC.reference(name, W, H, params), host_blur(*fields, **params)
         bad = np.flatnonzero(~BO.same_bits(got, want).reshape(-1))
         assert bad.size == 0, f"{name} {W}x{H} {params}: differs in {bad.size} values, first {bad[:4]}"
@@ -204,6 +204,31 @@ def test_the_synthetic_fields_take_both_arms_and_the_cap():
     assert parts["gathered"].all() and (parts["taps"] < 15).any() and (parts["taps"] == 15).any()  # taps leave the image at its border
     parts = BO.blur(*BC.fields("random", 97, 70), shutter=4.0, max_blur=7.5, with_parts=True)
     assert (parts["l"] == F32(7.5)).mean() > 0.9  # ties among capped pixels: l == maxBlur exactly
+
+
+def test_the_tall_shape_reaches_the_tiles_past_the_first_256():
+    """1 x 257 tiles.  Every setting of TALL_GRID is one of GRID and every tap count occurs once; under each open shutter the last tile
+    (rows 8192..8199) gathers, sums taps that stay inside the two columns and changes its pixels; under `random` the tiles' dominant
+    velocities differ, so (c) has to pick among three tiles, also across the boundary between tiles 255 and 256."""
+    assert all(p in BC.GRID for p in BC.TALL_GRID) and sorted(p["taps"] for p in BC.TALL_GRID) == sorted(BC.TAPS)
+    assert all(BC.grid_of(W, H) is (BC.TALL_GRID if (W, H) == BC.TALL else BC.GRID) for _, W, H in BC.CASES)
+    assert {n for n, W, H in BC.CASES if (W, H) == BC.TALL} == {"random", "ties"}
+    for name in ("random", "ties"):
+        colour = BC.fields(name, *BC.TALL)[0]
+        for params in BC.TALL_GRID:
+            parts = BO.blur(*BC.fields(name, *BC.TALL), **params, with_parts=True)
+            assert parts["tile_max"].shape == (257, 1, 3)
+            last = parts["taps"][8192:]
+            print(f"{name} {BC.TALL} {params}: gather share {parts['gathered'].mean():.3f}, taps summed per pixel of the last tile "
+                  f"{last.min()}..{last.max()}")
+            assert parts["gathered"][8192:].all() and last.max() > 0, (name, params)
+            assert not BO.same_bits(parts["out"][8192:], colour[8192:]).all(), (name, params)
+    parts = BO.blur(*BC.fields("random", *BC.TALL), **BC.TALL_GRID[2], with_parts=True)
+    tm, nb = parts["tile_max"][:, 0], parts["nb_max"][:, 0]
+    assert len(np.unique(tm[:, 2])) > 100 and abs(tm[:, 1]).min() > 20 * abs(tm[:, 0]).max()  # different lengths, all of them vertical
+    took = [int(np.flatnonzero((tm[max(t - 1, 0):t + 2] == nb[t]).all(-1))[0]) + max(t - 1, 0) - t for t in range(257)]
+    assert {-1, 0, 1} == set(took) and (took[255] == 1 or took[256] == -1), "no tile takes its velocity across tiles 255 | 256"
+    assert (parts["taps"] == 15).mean() > 0.5  # (vertical: most taps stay inside the image)
 
 
 def test_ties_are_won_by_the_first_index():

@@ -5,7 +5,10 @@ temporal steps, a temporal step on an older frame and a motion step with camera 
 model, driven through the chains of motion_cases.py and temporal_cases.py, gives exactly their states, references and histories.
 The edit seeds: their caps (class crossings by direction and cause, frames, clones, histories and mattes around them), the shares by
 which an edit changes the oracle's planes and mattes differ, and that planes and mattes of an edited look are those of a scene built
-with the look's fields from the start."""
+with the look's fields from the start.
+The post seeds: how often each situation of session_cases.POST_FACTS occurs, the share of the pixels in which the clamped oracle differs
+from the unclamped one where a history is live, the gather shares of the blurs and that they change their frames, and that the model
+gives what the three features' own GPU tests compute from their oracles for their hand-written chains."""
 import collections
 
 import numpy as np
@@ -27,7 +30,8 @@ F32 = np.float32
 
 
 def circuits():
-    return [(name, seed) for name, spec in SC.SCENES.items() for seed in spec["circuits"] + spec["wide_circuits"] + spec.get("edit_circuits", ())]
+    return [(name, seed) for name, spec in SC.SCENES.items() for seed in spec["circuits"] + spec["wide_circuits"] + spec.get("edit_circuits", ())
+            + spec.get("post_circuits", ())]
 
 
 def every_sequence():
@@ -45,6 +49,8 @@ def test_generation_is_deterministic():
         assert dict(sequences=len(mine), steps=sum(len(q["steps"]) for q in mine)) == counts, f"the draw changed (wide: {wide}): measure again"
     mine = [q for (n, s, p), q in first.items() if s in SC.edit_seeds(n)]
     assert dict(sequences=len(mine), steps=sum(len(q["steps"]) for q in mine)) == SC.COUNTS_EDIT, "the draw of the edit seeds changed: measure again"
+    mine = [q for (n, s, p), q in first.items() if s in SC.post_seeds(n)]
+    assert dict(sequences=len(mine), steps=sum(len(q["steps"]) for q in mine)) == SC.COUNTS_POST, "the draw of the post seeds changed: measure again"
 
 
 @pytest.mark.parametrize("name, seed", circuits())
@@ -64,7 +70,8 @@ def test_a_circuit_holds_every_ordered_pair_once_and_cutting_loses_none(name, se
         end = (s.pose, s.shape)
     alphabet = SC.kinds_of(name, seed)
     K = len(alphabet)
-    assert K == (25 if seed in SC.SCENES[name].get("edit_circuits", ()) else 19 if seed in SC.SCENES[name]["wide_circuits"] else 17)
+    assert K == (25 if seed in SC.SCENES[name].get("edit_circuits", ()) else 22 if seed in SC.SCENES[name].get("post_circuits", ())
+                 else 19 if seed in SC.SCENES[name]["wide_circuits"] else 17)
     assert len(kinds) == K * K + 1 and kinds[0] == kinds[-1]
     pairs = collections.Counter(zip(kinds, kinds[1:]))
     assert len(pairs) == K * K and set(pairs.values()) == {1} and set(k for k, _ in pairs) == set(alphabet)
@@ -101,6 +108,19 @@ def test_camera_and_shape_steps_change_the_state_and_refusals_stay_rare():
                 else:
                     assert rc == 0 and win[0] in [S * n for n in SC.WINDOW_SIZES], (name, seed, part, arg, R.last_error())
                     assert not (win[3] and win[1] > 0), "a window that continues is drawn at f = 0 only: it never starts on an undefined buffer"
+            if kind == "clamp" and arg is not None:  # a setting of the table, or one that the library's check refuses with the text
+                mode, gamma = arg[1] if s.refuses((kind, arg)) else arg
+                rc = R.lib().rtHipTemporalClampCheck(C.byref(R.temporal_clamp_params(mode, gamma)))
+                if s.refuses((kind, arg)):
+                    assert rc == -1 and arg[2] in R.last_error() and (arg[1], arg[2]) in SC.CLAMP_REFUSALS, (name, seed, part, arg, R.last_error())
+                else:
+                    assert rc == 0 and arg in SC.CLAMP_SETTINGS and arg != s.clamp, (name, seed, part, arg, R.last_error())
+            if kind == "clamp" and arg is None:
+                assert s.clamp is not None, "the clamp is turned off while it is off"
+            if kind == "motion_blur":
+                assert R.lib().rtHipMotionBlurCheck(C.byref(R.motion_blur_params(**SC.BC.SCENE_PARAMS[arg]))) == 0, arg
+            if kind == "dof":
+                assert R.lib().rtHipDepthOfFieldCheck(C.byref(R.dof_params(**SC.DC.SCENE_PARAMS[arg]))) == 0, arg
             if kind in ("camera", "refused_camera"):
                 assert arg in SC.POSES and arg != s.pose, (name, seed, part, kind, arg)
             if kind == "shape":
@@ -111,10 +131,10 @@ def test_camera_and_shape_steps_change_the_state_and_refusals_stay_rare():
             s.advance((kind, arg))
         assert refused * 5 <= len(q["steps"]), f"{name} seed {seed} part {part}: {refused} of {len(q['steps'])} steps are refusals"
     for name, spec in SC.SCENES.items():
-        for seed in spec["walks"] + spec["wide_walks"] + spec.get("edit_walks", ()):
+        for seed in spec["walks"] + spec["wide_walks"] + spec.get("edit_walks", ()) + spec.get("post_walks", ()):
             parts = SC.sequences(name, seed)
             assert sum(len(q["steps"]) for q in parts) == SC.WALK + len(parts) - 1  # (a cut walk repeats the kind it was cut at)
-            assert all(len(q["steps"]) <= spec.get("walk_cut", SC.WALK) for q in parts) and ("walk_cut" in spec or len(parts) == 1)
+            assert all(len(q["steps"]) <= SC.walk_limit(name, seed) for q in parts) and ("walk_cut" in spec or len(parts) == 1)
             assert all(sum(k == "shape" for k, _ in q["steps"]) <= spec.get("shape_steps", SC.WALK) for q in parts)
 
 
@@ -131,7 +151,7 @@ def played(name):
         for n, seed, part, q in every_sequence():
             if n != name:
                 continue
-            s = SC.Session(w, q["start"], edit=SC.is_edit(name, seed))
+            s = SC.Session(w, q["start"], edit=SC.is_edit(name, seed), post=SC.is_post(name, seed))
             states.append(s.here())
             for step in q["steps"]:
                 before = s.here()
@@ -373,6 +393,146 @@ def test_the_model_is_right_about_looks():
         for k in ("select", "layer_id", "layer_coverage", "rest"):
             assert np.array_equal(got[k].view(np.uint32), ref[k].view(np.uint32)), (look, k)
         assert (ref["layer_count"] > 0).any()
+
+
+# ---- the post seeds: the temporal clamp, motion blur and depth of field ------------------------------------------------------------------------
+def post_notes():
+    """[(scene, seed, part, notes)] of the post seeds' sequences, the model alone."""
+    return [(name, seed, part, played(name)[0][seed, part]) for name in SC.SCENES for seed in SC.post_seeds(name)
+            for part in range(len(SC.sequences(name, seed)))]
+
+
+def test_no_shape_changes_the_triangle_count():
+    """Why "a reference made for another triangle count" is not among the motion blur's refusals in session_cases.Lite.refuses."""
+    for name, spec in SC.SCENES.items():
+        base = SC.world(name).base
+        for shape in spec["shapes"]:
+            _, index, _ = GC.arrays(base, shape)
+            assert index is None or np.asarray(index).shape[0] == base.triangle_count, (name, shape)
+
+
+def test_the_post_seeds_play_the_clamp_and_the_blurs_between_all_other_operations():
+    events, per_seed = [], {}
+    for name in SC.SCENES:
+        for seed in SC.post_seeds(name):
+            mine = []
+            for q in SC.sequences(name, seed):
+                s = SC.lite_of(name, seed, q["start"])
+                for step in q["steps"]:
+                    s.advance(step)
+                mine.append(s.log.events)
+            per_seed[name, seed] = SC.post_counts(mine)
+            events += mine
+    counts = SC.post_counts(events)
+    print(f"post seeds: {counts}; per seed {per_seed}")
+    assert sorted(per_seed) == [("axis_near_axis_mixed", 118), ("mirror_hall", 36), ("mirror_hall", 118)]
+    for k in SC.POST_FACTS:
+        assert counts[k] >= 2, f"{k} occurs {counts[k]} times over the post seeds"
+    for (name, seed), mine in per_seed.items():
+        walk = seed in SC.SCENES[name]["post_walks"]
+        assert SC.post_caps(mine, walk, R.tile_count(*SC.SCENES[name]["size"])), (name, seed)
+    steps = [(k, a) for name in SC.SCENES for seed in SC.post_seeds(name) for q in SC.sequences(name, seed) for k, a in q["steps"]]
+    clamps = [a for k, a in steps if k == "clamp"]
+    assert any(a is None for a in clamps) and any(a is not None and a[0] == "refused" for a in clamps)
+    assert {a[0] for a in clamps if a is not None and a[0] != "refused"} == set(SC.TCC.MODES), "a mode of the clamp is never set"
+    assert any(a is not None and a[0] != "refused" and a[1] == 0.0 for a in clamps), "gamma 0 is never set"
+    for kind, table in (("motion_blur", SC.BC.SCENE_PARAMS), ("dof", SC.DC.SCENE_PARAMS)):
+        assert {a for k, a in steps if k == kind} == set(range(len(table))), kind
+
+
+def test_the_post_seeds_clamp_and_blurs_are_not_vacuous():
+    """On the oracles alone: the clamp changes the accumulation where a history is live, the blurs gather and change their frames.  Each
+    measured share is asserted at half of session_cases.POST_SHARES, which leaves room for another draw."""
+    clamped, blurs, dofs = [], [], []
+    for name, seed, part, notes in post_notes():
+        clamped += [(info, share) for k, info, share in notes if k == "clamped"]
+        blurs += [info for k, info, _ in notes if k == "motion_blur"]
+        dofs += [info for k, info, _ in notes if k == "dof"]
+    live = [share for info, share in clamped if info["live"] and info["cap"] > 1]
+    moved = [info for info in blurs if info["mark_differs"]]
+    print(f"post seeds: {len(clamped)} accumulation steps under the clamp, {len(live)} with a live history and max_history above 1: the clamped "
+          f"oracle's colour differs from the unclamped one's in {np.mean(live):.3f} of the pixels ({min(live):.3f}..{max(live):.3f}), in some pixel "
+          f"in {sum(s > 0 for s in live)} of them; {len(blurs)} motion blurs, {len(moved)} with a mark that differs from the state, "
+          f"{sum(i['stale'] for i in blurs)} of a stale frame: gather share {np.mean([i['gathered'] for i in blurs]):.3f} over all, "
+          f"{np.mean([i['gathered'] for i in moved]):.3f} over the moved ones, {sum(i['changed'] for i in blurs)} change their frame; "
+          f"{len(dofs)} depths of field, {sum(i['stale'] for i in dofs)} of a stale frame, {sum(i['window'] != 'default' for i in dofs)} under "
+          f"another window: gather share {np.mean([i['gathered'] for i in dofs]):.3f} ({min(i['gathered'] for i in dofs):.3f}.."
+          f"{max(i['gathered'] for i in dofs):.3f}), {sum(i['changed'] for i in dofs)} change their frame")
+    assert len(live) >= 4 and np.mean(live) >= 0.5 * SC.POST_SHARES["clamped"] > 0
+    assert np.mean([i["gathered"] for i in blurs]) >= 0.5 * SC.POST_SHARES["motion_blur_gathered"] > 0
+    assert np.mean([i["gathered"] for i in dofs]) >= 0.5 * SC.POST_SHARES["dof_gathered"] > 0
+    assert all(i["changed"] for i in dofs), "a depth of field returns its frame"
+    assert all(i["changed"] == (i["gathered"] > 0) for i in blurs), "a motion blur that gathers returns its frame, or one that only copies changes it"
+    assert all(i["gathered"] > 0 for i in moved), "a motion blur against another state than the mark's gathers nothing"
+    off = [share for info, share in clamped if not info["live"]]
+    assert all(s == 0.0 for s in off)  # (without a live history the clamp has nothing to pull: the frame itself)
+
+
+def test_the_model_gives_what_the_clamp_and_blur_tests_compute_from_their_oracles():
+    """Played without a device, the model's expected arrays for the hand-written chains of the three features' own GPU tests are what
+    those tests compute directly from their oracles: a relight under the clamp (tests/test_temporal_clamp_gpu.py; here on the scene
+    whose looks the model can edit, under a still camera), the camera moves of tests/test_motion_blur_gpu.py, and home / pan / twist of
+    tests/test_dof_gpu.py with the depth pass restated by sample_window_cases.window_passes."""
+    import motion_blur_oracle as BO
+    import dof_oracle as DO
+    import temporal_clamp_oracle as CO
+    import variance_oracle as VO
+    # the relight under the clamp, with and without moments
+    w = SC.world(EDITED)
+    sc = w.base
+    flow = MO.motion(sc, sc)
+    looks = [("sun", "own", SC.default_look(EDITED)[2]), ("many65", "own", SC.default_look(EDITED)[2])]
+    frames = [np.stack(SC.world(EDITED, look).planes("home", "home"), -1).astype(F32) / F32(65535.0) for look in looks]
+    assert not np.array_equal(frames[0], frames[1])
+    for clamp in ((3, 1.0), (1, 1.0), (2, 0.5)):
+        for kind, empty in (("temporal", TO.empty_history), ("variance", VO.empty_history)):
+            s = SC.Session(w, edit=True, post=True)
+            s.apply(("clamp", clamp))
+            hist, outs = empty(w.height, w.width), []
+            for look, frame in zip(looks, frames):
+                s.apply(("lights", look[0]))
+                s.apply(("frame", None))
+                s.apply((kind, (False, 32)))
+                want = CO.accumulate(frame, flow["motion"], flow["prev_t"], flow["triangle"], hist, mode=clamp[0], gamma=clamp[1])
+                hist = CO.next_history(want, flow["t"], flow["triangle"])
+                outs.append(want)
+                for k in ("colour", "count"):
+                    assert TO.same_bits(s.history[k], want[k]).all(), (clamp, kind, look, k)
+                if kind == "variance":
+                    assert TO.same_bits(s.moments, want["moments"]).all(), (clamp, look)
+            assert s.clamp == clamp and (outs[1]["count"] == 2.0).mean() > 0.1 and (outs[1]["moved"] != 0).any(), "the relight pulled no history in"
+    # the camera moves under the motion blur
+    w = SC.world("mirror_hall")
+    s = SC.Session(w, post=True)
+    s.apply(("mark", None))
+    for pose, cur, ref, mark, _ in MC.camera_steps(w.base):
+        if mark:
+            s.apply(("mark", None))
+        s.apply(("camera", pose))
+        s.apply(("frame", None))
+        moved = MO.motion(cur, ref)
+        colour = np.stack(w.planes(pose, "home"), -1).astype(F32) / F32(65535.0)
+        for variant, params in enumerate(SC.BC.SCENE_PARAMS):
+            s.apply(("motion_blur", variant))
+            assert BO.same_bits(s.notes[-1][2], BO.blur(colour, moved["motion"], moved["t"], **params)).all(), (pose, params)
+    # home / pan / twist under the depth of field
+    s = SC.Session(w, post=True)
+    s.apply(("passes", R.PASS_DEPTH))
+    blurred = 0
+    for kind, arg in ((None, None), ("camera", "pan"), ("shape", "twist")):
+        if kind:
+            s.apply((kind, arg))
+        s.apply(("frame", None))
+        state = w.state(*s.here())
+        depth = WC.window_passes(state, state.sample_count, 0)["depth"]
+        colour = np.stack(w.planes(*s.here()), -1).astype(F32) / F32(65535.0)
+        focus = float(np.median(depth[np.isfinite(depth) & (depth > 0)]))
+        for variant, params in enumerate(SC.DC.SCENE_PARAMS):
+            s.apply(("dof", variant))
+            _, info, out = s.notes[-1]
+            assert info["focus"] == focus and DO.same_bits(out, DO.blur(colour, depth, focus=focus, **params)).all(), (s.here(), params)
+            blurred += info["changed"]
+    assert blurred == 6 and s.mark is None and s.history is None and s.clamp is None  # (the blurs left the model alone)
 
 
 # ---- the model against the chains of the motion and temporal tests ---------------------------------------------------------------------------
