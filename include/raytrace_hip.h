@@ -1371,8 +1371,35 @@ int rtHipBakeMaterials(const rtHipMaterialSpec *materials, cl_uint materialCount
  * any face carries them -- 4 corner normals / 4 corner UVs per polygon (zero where a face has none), one material id per polygon
  * (-1 before the first usemtl).  The materials its MTL libraries define (paths relative to the OBJ) come back as rtHipObjMaterial:
  * Kd = material colour, d / Tr = opacity, Ke = emission, refl = reflectance, and the channel image paths map_Kd (colour), map_refl
- * (reflection), map_d (transparency), map_bump / bump (bump), map_Ke (luminance).  Arrays are malloc'ed: rtHipObjFree.
- * Returns 0, -1 null argument, -2 malformed file, -3 out of memory, -4 cannot open. */
+ * (reflection), map_d (transparency), map_bump / map_Bump / bump (bump), map_Ke (luminance).  Arrays are malloc'ed: rtHipObjFree.
+ * Returns 0, -1 null argument, -2 malformed file, -3 out of memory, -4 cannot open; on any failure *out is zeroed.
+ *
+ * The rules the readers keep (tests/fileio_oracle.py is an independent reader written from them; tests/test_fileio.py holds both to them):
+ *
+ * OBJ / MTL
+ *  - A line ends at LF; carriage returns are dropped, so CR LF files read alike; the last line needs no newline.  Blanks and tabs
+ *    separate tokens.  Every read stays inside the line.
+ *  - The keyword is the line's first token.  v, vt, vn, f, usemtl and mtllib are recognised only as whole tokens: "vtx ..",
+ *    "vnormal ..", "vp .." and every other keyword (o, g, s, l, ...) are ignored, as are lines whose first token starts with '#'.
+ *  - v and vn need three numbers, vt one or two (a missing second is 0); fewer gives -2, and so does a recognised keyword with
+ *    nothing behind it.  Tokens behind the numbers are ignored ("v x y z w").
+ *  - A number is a whole token that strtof reads in decimal form: [+-] digits [. digits] [e [+-] digits] with at least one digit
+ *    before the exponent, or [+-] inf / infinity / nan in any letter case.  Anything else where a number is due ("1.5abc", "0x1p3",
+ *    "nan(1)", a second vt token that is no number) gives -2.
+ *  - A face needs at least 3 corners; 3 or 4 make one polygon, more are fanned into triangles (0, k, k + 1).
+ *  - A corner token is v, v/vt, v//vn or v/vt/vn; an index is an optional '-' and decimal digits.  An empty vt or vn field ("1/",
+ *    "1//", "1/2/") means "absent".  The whole token must be consumed: "1x" and "1/2/3/4" give -2.  An index of 0 gives -2; so does
+ *    an index outside what has been defined so far, counted from the start (positive) or from the end (negative), and an index that
+ *    does not fit 32 bits ("4294967297", "-4294967297", 20 digits).
+ *  - The name after usemtl / newmtl and the file name after mtllib / map_* run to the end of the line with leading and trailing blanks
+ *    and tabs removed; they may contain blanks.  A path that starts with '/' is taken as given, any other is relative to the OBJ's
+ *    directory.  Names are cut to 63 bytes in the record, paths to 255.
+ *  - Materials are numbered in the order of first use (usemtl) and then of first definition (newmtl), the libraries read in the order
+ *    of their mtllib lines after the whole OBJ.  A missing library leaves its materials at their defaults.
+ *  - In a library the keywords newmtl, Kd, Ke, d, Tr, refl and the seven map_* spellings are whole tokens too; what stands before
+ *    the first newmtl and every other statement (Ns, illum, ...) is ignored.  Kd and Ke need three numbers, d, Tr and refl one
+ *    (dissolve = 1 - Tr in float); a statement of a material with fewer, or a newmtl or map_* without a name, gives -2.  The last
+ *    statement of a kind wins. */
 typedef struct rtHipObjMaterial {
     char name[64];
     cl_float kd[3];            /* Kd (default 1 1 1) */
@@ -1391,7 +1418,26 @@ void rtHipObjFree(rtHipObjData *data);
 
 /* An image file as rtHipChannelSpec::pixels: binary or plain PPM (P6 / P3, maxval <= 255, scaled to 255) or an uncompressed 24 / 32-bit
  * BMP -> width*height texels of 4 bytes (r, g, b, 0), top row first, malloc'ed (rtHipFree).  Returns 0, -1 null argument, -2 not
- * such a file, -3 out of memory, -4 cannot open. */
+ * such a file, -3 out of memory, -4 cannot open; on any failure *pixels is NULL and *width = *height = 0.
+ *
+ * PPM
+ *  - "P6" or "P3", one white-space byte (C's isspace), then width, height and maxval as decimal digits, each after any run of white
+ *    space and comments ('#' to the end of its line).  Width and height must be at least 1 (and at most 10^9), maxval 1..255.
+ *  - In P6 exactly one white-space byte follows maxval, then 3wh sample bytes; anything else there gives -2.  Bytes behind the
+ *    samples are ignored.  In P3 the samples are decimal numbers separated like the header's (comments allowed); what follows the
+ *    last one is ignored.
+ *  - A sample above maxval gives -2, in P6 as in P3.  A sample s becomes s * 255 / maxval, rounded down.
+ *  - A file may end anywhere: if it ends before the last sample the result is -2, and no byte outside the file is read.
+ *  - The header's size is checked against the bytes that are there before anything proportional to it is allocated: P6 needs 3wh
+ *    bytes behind maxval's white-space byte, P3 at least 6wh - 1 bytes behind maxval (a digit per sample, a separator between two).
+ * BMP
+ *  - "BM", a 14-byte file header and an info header of at least 40 bytes (a V4 / V5 header is fine; what lies past the first 40 bytes
+ *    of it is not read).  Refused with -2: a file shorter than 54 bytes; an info header smaller than 40 bytes; a pixel offset below
+ *    14 + that header's size; a pixel offset or a row range past the end of the file; width < 1; height 0 or INT32_MIN; depths other
+ *    than 24 / 32; compression other than 0 (or 3 at 32 bits, read as BGRA like 0).
+ *  - Rows are padded to 4 bytes.  A positive height means bottom row first, a negative one top row first; both are read.  The fourth
+ *    byte of a 32-bit texel is dropped.
+ *  - The size is checked before anything is allocated. */
 int rtHipImageRead(const char *path, cl_uint *width, cl_uint *height, cl_uchar3 **pixels);
 
 /* ShdProjectPoint (render.cpp:495-673): the UV a point gets from a texture tag's projection when its polygon has no UVW tag

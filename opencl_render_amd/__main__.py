@@ -648,7 +648,12 @@ def main(argv=None):
         sys.exit(f"--device {args.device}: choose 1..{len(names) - 1} ({names[1:]})")
     t0 = time.perf_counter()
     if args.obj:
-        mesh, materials = frontend.read_obj(args.obj)
+        try:
+            mesh, materials = frontend.read_obj(args.obj)
+        except OSError as e:  # (malformed or unreadable: the OBJ, one of its libraries or one of their images)
+            sys.exit(f"--obj {args.obj}: {e}")
+        if not len(mesh.polygons):
+            sys.exit(f"--obj {args.obj}: the file holds no faces")
         lo, hi = mesh.points.min(axis=0), mesh.points.max(axis=0)
         centre, size = (lo + hi) / 2, float(np.linalg.norm(hi - lo)) or 1.0
         look_at = np.asarray(args.look_at, np.float32) if args.look_at else centre

@@ -11,6 +11,7 @@
 
 #include <cctype>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,25 +44,90 @@ bool read_line(FILE *f, std::string &line)
 
 struct ObjCorner { int v, vt, vn; };
 
-// "7", "7/2", "7//3", "7/2/3"; negative indices count from the end (OBJ); returns false on a malformed token
+inline bool blank(char c) { return c == ' ' || c == '\t'; }
+
+// the next token of a line (blanks and tabs separate); false when only blanks are left.  Nothing behind the terminator is read.
+bool next_token(const char *&p, std::string &tok)
+{
+    while (blank(*p)) ++p;
+    if (!*p) return false;
+    const char *q = p;
+    while (*q && !blank(*q)) ++q;
+    tok.assign(p, q);
+    p = q;
+    return true;
+}
+
+// a decimal number as strtof reads it: [+-] digits [. digits] [e [+-] digits], or [+-] inf / infinity / nan in any case; the whole
+// token, no hexadecimal form, no nan(...)
+bool parse_number(const std::string &tok, float &out)
+{
+    const char *s = tok.c_str();
+    if (*s == '+' || *s == '-') ++s;
+    auto word = [&](const char *w) { size_t k = 0; for (; w[k]; ++k) if (tolower((unsigned char)s[k]) != w[k]) return false; return s[k] == 0; };
+    if (!(word("inf") || word("infinity") || word("nan"))) {
+        int digits = 0;
+        while (isdigit((unsigned char)*s)) { ++s; ++digits; }
+        if (*s == '.') { ++s; while (isdigit((unsigned char)*s)) { ++s; ++digits; } }
+        if (digits == 0) return false;
+        if (*s == 'e' || *s == 'E') {
+            ++s;
+            if (*s == '+' || *s == '-') ++s;
+            if (!isdigit((unsigned char)*s)) return false;
+            while (isdigit((unsigned char)*s)) ++s;
+        }
+        if (*s) return false;
+    }
+    out = strtof(tok.c_str(), nullptr);
+    return true;
+}
+
+// `want` numbers from the line's next tokens; `need` of them must be there (the others stay as they are), a token that is there must be
+// a number; what follows them is ignored
+bool parse_numbers(const char *p, int need, int want, float *out)
+{
+    std::string tok;
+    for (int k = 0; k < want; ++k) {
+        if (!next_token(p, tok)) return k >= need;
+        if (!parse_number(tok, out[k])) return false;
+    }
+    return true;
+}
+
+// the rest of a line as a name: leading and trailing blanks and tabs removed, inner ones kept
+std::string rest_of_line(const char *p)
+{
+    while (blank(*p)) ++p;
+    size_t n = strlen(p);
+    while (n > 0 && blank(p[n - 1])) --n;
+    return std::string(p, n);
+}
+
+// "7", "7/2", "7//3", "7/2/3", an empty vt / vn field meaning "absent"; negative indices count from the end (OBJ).  The whole token
+// must be consumed; an index of 0, one that does not fit 32 bits or one outside what is defined so far makes the token malformed.
 bool parse_corner(const char *tok, size_t nv, size_t nvt, size_t nvn, ObjCorner &out)
 {
-    long idx[3] = { 0, 0, 0 };
+    const size_t count[3] = { nv, nvt, nvn };
+    int res[3] = { -1, -1, -1 };
     const char *p = tok;
     for (int k = 0; k < 3; ++k) {
-        if (*p == '/' || *p == 0) { if (k == 0) return false; }
+        if (*p == '/' || *p == 0) { if (k == 0) return false; } // (an empty field)
         else {
-            char *endp = nullptr;
-            idx[k] = strtol(p, &endp, 10);
-            if (endp == p) return false;
-            p = endp;
+            const bool neg = *p == '-';
+            if (neg) ++p;
+            if (!isdigit((unsigned char)*p)) return false;
+            int64_t i = 0;
+            for (; isdigit((unsigned char)*p); ++p) { i = i * 10 + (*p - '0'); if (i > 0x7fffffffLL) return false; }
+            if (i == 0) return false;
+            const int64_t at = neg ? (int64_t)count[k] - i : i - 1;
+            if (at < 0 || at >= (int64_t)count[k]) return false;
+            res[k] = (int)at;
         }
-        if (*p == '/') ++p; else break;
+        if (k < 2 && *p == '/') ++p; else break;
     }
-    auto resolve = [](long i, size_t n) -> int { return i > 0 ? (int)(i - 1) : (i < 0 ? (int)((long)n + i) : -1); };
-    out.v = resolve(idx[0], nv); out.vt = resolve(idx[1], nvt); out.vn = resolve(idx[2], nvn);
-    return out.v >= 0 && (size_t)out.v < nv && (out.vt < 0 || (size_t)out.vt < nvt) && (out.vn < 0 || (size_t)out.vn < nvn) &&
-           (idx[1] == 0 || out.vt >= 0) && (idx[2] == 0 || out.vn >= 0);
+    if (*p) return false;
+    out.v = res[0]; out.vt = res[1]; out.vn = res[2];
+    return true;
 }
 
 template <class T> T *take(const std::vector<T> &v)
@@ -108,34 +174,28 @@ int rtHipObjRead(const char *path, rtHipObjData *out)
         mats.push_back(m);
         return matId[name] = (int)mats.size() - 1;
     };
+    std::string key, tok;
     while (rc == 0 && read_line(f, line)) {
         const char *s = line.c_str();
-        while (*s == ' ' || *s == '\t') ++s;
-        if (*s == 0 || *s == '#') continue;
-        if (s[0] == 'v' && (s[1] == ' ' || s[1] == '\t')) {
-            float x = 0, y = 0, z = 0;
-            if (sscanf(s + 2, "%f %f %f", &x, &y, &z) != 3) rc = -2;
-            v.insert(v.end(), { x, y, z });
-        } else if (s[0] == 'v' && s[1] == 't') {
-            float a = 0, b = 0;
-            if (sscanf(s + 3, "%f %f", &a, &b) < 1) rc = -2;
-            vt.insert(vt.end(), { a, b });
-        } else if (s[0] == 'v' && s[1] == 'n') {
-            float x = 0, y = 0, z = 0;
-            if (sscanf(s + 3, "%f %f %f", &x, &y, &z) != 3) rc = -2;
-            vn.insert(vn.end(), { x, y, z });
-        } else if (s[0] == 'f' && (s[1] == ' ' || s[1] == '\t')) {
+        if (!next_token(s, key) || key[0] == '#') continue; // (s now stands behind the keyword, the line's first token)
+        if (key == "v") {
+            float x[3] = { 0, 0, 0 };
+            if (!parse_numbers(s, 3, 3, x)) { rc = -2; break; }
+            v.insert(v.end(), { x[0], x[1], x[2] });
+        } else if (key == "vt") {
+            float x[2] = { 0, 0 };
+            if (!parse_numbers(s, 1, 2, x)) { rc = -2; break; }
+            vt.insert(vt.end(), { x[0], x[1] });
+        } else if (key == "vn") {
+            float x[3] = { 0, 0, 0 };
+            if (!parse_numbers(s, 3, 3, x)) { rc = -2; break; }
+            vn.insert(vn.end(), { x[0], x[1], x[2] });
+        } else if (key == "f") {
             std::vector<ObjCorner> cs;
-            const char *p = s + 2;
-            while (*p) {
-                while (*p == ' ' || *p == '\t') ++p;
-                if (!*p) break;
-                const char *q = p;
-                while (*q && *q != ' ' && *q != '\t') ++q;
+            while (next_token(s, tok)) {
                 ObjCorner c;
-                if (!parse_corner(std::string(p, q).c_str(), v.size() / 3, vt.size() / 2, vn.size() / 3, c)) { rc = -2; break; }
+                if (!parse_corner(tok.c_str(), v.size() / 3, vt.size() / 2, vn.size() / 3, c)) { rc = -2; break; }
                 cs.push_back(c);
-                p = q;
             }
             if (rc != 0) break;
             if (cs.size() < 3) { rc = -2; break; }
@@ -154,46 +214,52 @@ int rtHipObjRead(const char *path, rtHipObjData *out)
             if (cs.size() <= 4) emit(cs.data(), (int)cs.size());
             else
                 for (size_t k = 1; k + 1 < cs.size(); ++k) { const ObjCorner tri[3] = { cs[0], cs[k], cs[k + 1] }; emit(tri, 3); }
-        } else if (strncmp(s, "usemtl", 6) == 0) {
-            const char *p = s + 6;
-            while (*p == ' ' || *p == '\t') ++p;
-            current = material(p);
-        } else if (strncmp(s, "mtllib", 6) == 0) {
-            const char *p = s + 6;
-            while (*p == ' ' || *p == '\t') ++p;
-            mtlFiles.push_back(p);
-        } // (o, g, s, l and the rest: ignored)
+        } else if (key == "usemtl") {
+            const std::string name = rest_of_line(s);
+            if (name.empty()) { rc = -2; break; }
+            current = material(name);
+        } else if (key == "mtllib") {
+            const std::string name = rest_of_line(s);
+            if (name.empty()) { rc = -2; break; }
+            mtlFiles.push_back(name);
+        } // (o, g, s, l, vp and the rest: ignored)
     }
     fclose(f);
     if (rc != 0) return rc;
-    // MTL: Kd -> material colour, d / Tr -> transparency, Ke -> luminance, map_* -> channel images (paths relative to the OBJ)
+    // a file name of an OBJ or MTL line: as given when it starts with '/', else relative to the OBJ's directory
+    auto resolve = [&](const std::string &name) { return name[0] == '/' ? name : dir_of(path) + name; };
+    // MTL: Kd -> material colour, d / Tr -> transparency, Ke -> luminance, map_* -> channel images.  Keywords are whole tokens as in the
+    // OBJ; what stands before the first newmtl is ignored; a statement of a material with too few numbers or no name is malformed.
     for (const std::string &mf : mtlFiles) {
-        FILE *m = fopen((dir_of(path) + mf).c_str(), "rb");
+        FILE *m = fopen(resolve(mf).c_str(), "rb");
         if (!m) continue; // (a missing library leaves its materials at their defaults)
         int at = -1;
-        while (read_line(m, line)) {
+        while (rc == 0 && read_line(m, line)) {
             const char *s = line.c_str();
-            while (*s == ' ' || *s == '\t') ++s;
-            auto arg = [&](size_t skip) -> const char * { const char *p = s + skip; while (*p == ' ' || *p == '\t') ++p; return p; };
-            if (strncmp(s, "newmtl", 6) == 0) at = material(arg(6));
-            else if (at < 0) continue;
-            else if (strncmp(s, "Kd", 2) == 0 && isspace((unsigned char)s[2])) sscanf(s + 3, "%f %f %f", &mats[at].kd[0], &mats[at].kd[1], &mats[at].kd[2]);
-            else if (strncmp(s, "Ke", 2) == 0 && isspace((unsigned char)s[2])) { sscanf(s + 3, "%f %f %f", &mats[at].ke[0], &mats[at].ke[1], &mats[at].ke[2]); mats[at].hasKe = 1; }
-            else if (s[0] == 'd' && isspace((unsigned char)s[1])) sscanf(s + 2, "%f", &mats[at].dissolve);
-            else if (strncmp(s, "Tr", 2) == 0 && isspace((unsigned char)s[2])) { float tr = 0.f; if (sscanf(s + 3, "%f", &tr) == 1) mats[at].dissolve = 1.f - tr; }
-            else if (strncmp(s, "refl", 4) == 0 && isspace((unsigned char)s[4])) { sscanf(s + 5, "%f", &mats[at].reflect); mats[at].hasReflect = 1; }
+            if (!next_token(s, key) || key[0] == '#') continue;
+            float x[3] = { 0, 0, 0 };
+            if (key == "newmtl") {
+                const std::string name = rest_of_line(s);
+                if (name.empty()) rc = -2; else at = material(name);
+            } else if (at < 0) continue;
+            else if (key == "Kd") { if (parse_numbers(s, 3, 3, x)) memcpy(mats[at].kd, x, sizeof x); else rc = -2; }
+            else if (key == "Ke") { if (parse_numbers(s, 3, 3, x)) { memcpy(mats[at].ke, x, sizeof x); mats[at].hasKe = 1; } else rc = -2; }
+            else if (key == "d") { if (parse_numbers(s, 1, 1, x)) mats[at].dissolve = x[0]; else rc = -2; }
+            else if (key == "Tr") { if (parse_numbers(s, 1, 1, x)) mats[at].dissolve = 1.f - x[0]; else rc = -2; }
+            else if (key == "refl") { if (parse_numbers(s, 1, 1, x)) { mats[at].reflect = x[0]; mats[at].hasReflect = 1; } else rc = -2; }
             else {
                 static const struct { const char *key; int channel; } maps[] = { { "map_Kd", 0 }, { "map_refl", 1 }, { "map_d", 2 }, { "map_bump", 3 }, { "map_Bump", 3 }, { "bump", 3 }, { "map_Ke", 4 } };
-                for (const auto &mp : maps) {
-                    const size_t n = strlen(mp.key);
-                    if (strncmp(s, mp.key, n) == 0 && isspace((unsigned char)s[n])) {
-                        const std::string file = dir_of(path) + arg(n);
-                        snprintf(mats[at].map[mp.channel], sizeof mats[at].map[mp.channel], "%s", file.c_str());
+                for (const auto &mp : maps)
+                    if (key == mp.key) {
+                        const std::string name = rest_of_line(s);
+                        if (name.empty()) { rc = -2; break; }
+                        memset(mats[at].map[mp.channel], 0, sizeof mats[at].map[mp.channel]); // (nothing of an earlier, longer path stays behind)
+                        snprintf(mats[at].map[mp.channel], sizeof mats[at].map[mp.channel], "%s", resolve(name).c_str());
                     }
-                }
             }
         }
         fclose(m);
+        if (rc != 0) return rc;
     }
     out->pointCount = (cl_uint)(v.size() / 3);
     std::vector<float> pts(4 * (size_t)out->pointCount, 0.f);
@@ -226,44 +292,56 @@ int rtHipImageRead(const char *path, cl_uint *width, cl_uint *height, cl_uchar3 
     size_t n;
     while ((n = fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + n);
     fclose(f);
-    if (data.size() < 8) return -2;
+    if (data.size() < 3) return -2;
     std::vector<unsigned char> px;
     cl_uint w = 0, h = 0;
     if (data[0] == 'P' && (data[1] == '6' || data[1] == '3')) {
         size_t at = 2;
-        auto number = [&](long &outv) -> bool {
+        if (!isspace(data[at])) return -2; // (white space ends the magic number)
+        auto number = [&](uint64_t &outv) -> bool {
             for (;;) { // white space and comments
                 while (at < data.size() && isspace(data[at])) ++at;
                 if (at < data.size() && data[at] == '#') { while (at < data.size() && data[at] != '\n') ++at; } else break;
             }
             if (at >= data.size() || !isdigit(data[at])) return false;
             outv = 0;
-            while (at < data.size() && isdigit(data[at])) { outv = outv * 10 + (data[at] - '0'); if (outv > 1000000000L) return false; ++at; }
+            while (at < data.size() && isdigit(data[at])) { outv = outv * 10 + (data[at] - '0'); if (outv > 1000000000u) return false; ++at; }
             return true;
         };
-        long lw, lh, maxv;
-        if (!number(lw) || !number(lh) || !number(maxv) || lw < 1 || lh < 1 || maxv < 1 || maxv > 255 || (double)lw * lh > 1e9) return -2;
-        w = (cl_uint)lw; h = (cl_uint)lh;
-        px.assign((size_t)w * h * 4, 0);
+        uint64_t lw, lh, maxv;
+        if (!number(lw) || !number(lh) || !number(maxv) || lw < 1 || lh < 1 || maxv < 1 || maxv > 255) return -2;
+        const uint64_t texels = lw * lh; // (each at most 1e9: no wrap, and 6 * texels fits too)
         if (data[1] == '6') {
-            ++at; // the single white-space byte behind maxval
-            if (data.size() - at < (size_t)w * h * 3) return -2;
-            for (size_t i = 0; i < (size_t)w * h; ++i)
-                for (int c = 0; c < 3; ++c) px[4 * i + c] = (unsigned char)((unsigned)data[at + 3 * i + c] * 255u / (unsigned)maxv);
-        } else
-            for (size_t i = 0; i < (size_t)w * h * 3; ++i) {
-                long vch;
+            if (at >= data.size() || !isspace(data[at])) return -2; // the single white-space byte behind maxval
+            ++at;
+            if (data.size() - at < 3 * texels) return -2;           // (at <= size; checked before anything is allocated)
+            px.assign((size_t)texels * 4, 0);
+            for (size_t i = 0; i < (size_t)texels; ++i)
+                for (int c = 0; c < 3; ++c) {
+                    const unsigned sample = data[at + 3 * i + c];
+                    if (sample > maxv) return -2;
+                    px[4 * i + c] = (unsigned char)(sample * 255u / (unsigned)maxv);
+                }
+        } else {
+            if (data.size() - at < 6 * texels - 1) return -2;       // a digit per sample and a separator between two
+            px.assign((size_t)texels * 4, 0);
+            for (size_t i = 0; i < (size_t)texels * 3; ++i) {
+                uint64_t vch;
                 if (!number(vch) || vch > maxv) return -2;
                 px[4 * (i / 3) + i % 3] = (unsigned char)(vch * 255 / maxv);
             }
-    } else if (data[0] == 'B' && data[1] == 'M' && data.size() >= 54) {
+        }
+        w = (cl_uint)lw; h = (cl_uint)lh;
+    } else if (data[0] == 'B' && data[1] == 'M') {
+        if (data.size() < 54) return -2; // (the file header and the smallest info header)
         auto u32 = [&](size_t o) { return (uint32_t)data[o] | ((uint32_t)data[o + 1] << 8) | ((uint32_t)data[o + 2] << 16) | ((uint32_t)data[o + 3] << 24); };
-        const uint32_t offset = u32(10), bpp = data[28] | (data[29] << 8), compression = u32(30);
+        const uint32_t offset = u32(10), header = u32(14), bpp = data[28] | (data[29] << 8), compression = u32(30);
         const int32_t bw = (int32_t)u32(18), bh = (int32_t)u32(22);
-        if (bw < 1 || bh == 0 || (bpp != 24 && bpp != 32) || (compression != 0 && compression != 3) || (double)bw * std::abs((double)bh) > 1e9) return -2;
-        w = (cl_uint)bw; h = (cl_uint)std::abs(bh);
-        const size_t row = ((size_t)w * (bpp / 8) + 3) & ~(size_t)3;
-        if (data.size() < offset + row * h) return -2;
+        if (header < 40 || (uint64_t)offset < 14 + (uint64_t)header || offset > data.size()) return -2;
+        if (bw < 1 || bh == 0 || bh == INT32_MIN || (bpp != 24 && bpp != 32) || (compression != 0 && !(compression == 3 && bpp == 32))) return -2;
+        w = (cl_uint)bw; h = (cl_uint)(bh < 0 ? -bh : bh);
+        const uint64_t row = ((uint64_t)w * (bpp / 8) + 3) & ~(uint64_t)3;
+        if ((data.size() - offset) / row < h) return -2; // (the rows lie inside the file; checked before anything is allocated)
         px.assign((size_t)w * h * 4, 0);
         for (cl_uint y = 0; y < h; ++y) {
             const unsigned char *src = data.data() + offset + row * (bh > 0 ? h - 1 - y : y); // (positive height: bottom row first)
