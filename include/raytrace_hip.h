@@ -1501,7 +1501,10 @@ int rtHipTestShadeKat(const rtHipScene *scene, int op, cl_uint count, const void
  * shadow ray; 1, the default: none for a light whose answer would only feed the face that is never read), "logic_split" (1, the
  * default: the later logic rounds of an opaque-diffuse scene with look-ahead on stream the answers and shade the bounce hits densely; 0:
  * one logic kernel per round), "ray_clip" (1, the default: a grid ray without a far end stops where it leaves the convex bound of the
- * grid's occupied cells; 0: at the grid's wall), and the test hooks
+ * grid's occupied cells; 0: at the grid's wall), "place_direct" (1, the default: a planned frame's uncut ordered rounds of an
+ * opaque-diffuse scene are written in sorted place from the placement table the round's last scatter launch recorded, and run no scatter
+ * launch; 0: every ordered round is scattered), and the test hooks "place_skew" (once per scene, the first table a round is about to be
+ * placed by is skewed by one entry between two cells: that frame is flagged and rendered again),
  * "plan_rounds", "plan_grid_tiny", "plan_shade_skip" (planned frames launch no shade pass), "visit_log" (every frame waits after each round's
  * trace launch and reads the round back for rtHipTestRoundVisits), "virtual_devices", and of the device list builders "build_key_cap" (first key capacity of
  * rtHipBuildSceneGridDevice, 0 = max(32 T, 2^22)) and "build_list_limit" (most entries either device builder may return, default
@@ -1556,6 +1559,18 @@ int rtHipTestRoundVisits(const rtHipScene *scene, uint64_t *out, cl_uint rounds)
  * number of logic rounds the frame issued as answer + shade launches, over its sample batches and tile groups (0: none was split), -1
  * for invalid arguments. */
 int rtHipTestShadeLog(const rtHipScene *scene, cl_uint *listed, cl_uint n);
+
+/* TEST-ONLY: direct placement ("place_direct") in the scene's last wavefront frame, over its sample batches and tile groups: out[0] = the
+ * ordered rounds whose entries the logic kernel wrote at their sorted positions from the round's placement table, out[1] = the scatter
+ * launches the frame issued (a frame rendered again reports the watched frame that replaced it).  Returns 0, -1 for NULL.
+ * rtHipTestPlaceView: of the scene's first tile group after a synchronisation -- table (may be NULL): the RT_PLACE_TABLE_WORDS words of
+ * round `round`'s placement table as the last scatter launch of that round recorded it, 64 classes x 32 copies cells {first sorted position,
+ * entries}, class-major, then the total, the slices and the segment length of the round's layout and a spare word; entries (may be NULL):
+ * the first `positions` 64-byte trace entries of the entry array of the round's parity, 16 words each, word 0 = the entry's queue slot.
+ * round is in 1 .. RT_PLACE_TABLE_ROUNDS.  Returns 0, -1 for invalid arguments. */
+enum { RT_PLACE_TABLE_ROUNDS = 8, RT_PLACE_TABLE_WORDS = 2 * 64 * 32 + 4 };
+int rtHipTestPlaceLog(const rtHipScene *scene, cl_uint out[2]);
+int rtHipTestPlaceView(const rtHipScene *scene, cl_uint round, cl_uint *table, cl_uint *entries, cl_uint positions);
 
 /* TEST-ONLY: what the calling thread's last device list builds did (rtHipBuildCameraListDevice, rtHipBuildSceneGridDevice; each
  * clears and fills its own fields), so that tests can prove which paths ran.  out[i] for i < n in the order of RT_BUILD_LOG_*:

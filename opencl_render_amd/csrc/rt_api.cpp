@@ -1542,7 +1542,7 @@ int rtHipTune(const char *key, double value)
         { "fast_quotient", &T.fastQuotient }, { "spin_limit", &T.spinLimit }, { "append_rays", &T.appendRays }, { "ordered_first", &T.orderedFirst }, { "slice_rays", &T.sliceRays },
         { "small_slices", &T.smallSlices }, { "group_rays", &T.groupRays }, { "blocking", &T.blocking }, { "plan_rounds", &T.planRounds }, { "plan_grid_tiny", &T.planGridTiny }, { "plan_shade_skip", &T.planShadeSkip }, { "visit_log", &T.visitLog },
         { "pipeline", &T.pipeline }, { "timing", &T.timing }, { "virtual_devices", &T.virtualDevices }, { "cache", &T.cache }, { "batch_plan", &T.batchPlan },
-        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "ray_clip", &T.rayClip }, { "logic_split", &T.logicSplit }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
+        { "logic_class", &T.logicClass }, { "dead_shadow", &T.deadShadow }, { "ray_clip", &T.rayClip }, { "logic_split", &T.logicSplit }, { "place_direct", &T.placeDirect }, { "place_skew", &T.placeSkew }, { "query_rays", &T.queryRays, nullptr, 1u << 26 },
         { "ao_samples", &T.aoSamples, nullptr, 1u << 22 }, { "bake_texels", &T.bakeTexels, nullptr, 1u << 24 },
         { "state_mb", nullptr, &T.stateMb, HUGE_VAL }, { "build_key_cap", nullptr, &T.buildKeyCap, 1e18 }, { "build_list_limit", nullptr, &T.buildListLimit },
     };
@@ -1622,6 +1622,27 @@ int rtHipTestShadeLog(const rtHipScene *scene, uint32_t *listed, uint32_t n)
         listed[r] = (uint32_t)std::min<uint64_t>(sum, 0xffffffffu);
     }
     return (int)std::min<uint64_t>(scene->splitRoundsLast, 0x7fffffffu);
+}
+
+int rtHipTestPlaceLog(const rtHipScene *scene, uint32_t out[2])
+{
+    if (!scene || !out) return -1;
+    out[0] = scene->directRoundsLast;
+    out[1] = scene->scatterLaunchesLast;
+    return 0;
+}
+
+int rtHipTestPlaceView(const rtHipScene *scene, uint32_t round, uint32_t *table, uint32_t *entries, uint32_t positions)
+{
+    static_assert(RT_PLACE_TABLE_ROUNDS == RT_WF_PLACE_ROUNDS && RT_PLACE_TABLE_WORDS == RT_WF_PLACE_WORDS, "the header's figures are the device's");
+    if (!scene || scene->groups.empty() || round < 1u || round > RT_WF_PLACE_ROUNDS) return fail("rtHipTestPlaceView: invalid argument");
+    const RtWavefront &W = scene->groups[0].wf;
+    if ((uint64_t)positions > 2ull * W.capacity + W.extraCap) return fail("rtHipTestPlaceView: %u positions reach past the entry array", positions);
+    HIP_OK(hipSetDevice(scene->device));
+    HIP_OK(hipStreamSynchronize(scene->stream));
+    if (table) HIP_OK(hipMemcpy(table, W.ctl + RT_WF_PLACE_AT(round), sizeof(uint32_t) * RT_WF_PLACE_WORDS, hipMemcpyDeviceToHost));
+    if (entries && positions) HIP_OK(hipMemcpy(entries, W.ent[round & 1u], (size_t)64 * positions, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int rtHipTestSceneView(const rtHipScene *scene, int what, uint64_t firstElement, uint64_t count, void *out)

@@ -157,7 +157,9 @@ struct RtDevScene {
 #define RT_WF_ERR_SPIN 1u     // wf_trace_kernel's walk guard tripped: rays were abandoned, the frame is invalid
 #define RT_WF_ERR_GRID 2u     // a planned frame's trace grid was smaller than the round's entries: entries were not traced; the host renders
                               // the frame again with the worst-case grid (rt_frame.cpp, frame_finish).  Also: a planned frame skipped a shade launch
-                              // (the plan said no bounce hit anything in that round) and the round listed a path for it
+                              // (the plan said no bounce hit anything in that round) and the round listed a path for it.  Also: a round placed
+                              // directly (RT_ROUND_DIRECT) did not fill its placement table's cells exactly -- a cell got more entries than
+                              // the table holds room for (they were not stored), or the round fewer than the table's total
 #define RT_WF_ERR_SPLIT 4u    // wf_answer_kernel met a path that is not of the shape it knows (opaque-diffuse class, look-ahead on), or a class kernel
                               // a path that asked for a ring slot other than the class layout's one bounce slot: the frame is invalid
 // per-round control words, three sets used in turn like the queue lengths (round r uses set r % 3): logic(r-1) fills set r,
@@ -167,16 +169,33 @@ struct RtDevScene {
 #define RT_WF_CTL_EXTRA (RT_WF_CTL_HIST + RT_WF_SORT_COPIES * RT_WF_SORT_BINS) // ordered round: entries in region B (further segments of cut rays)
 #define RT_WF_CTL_TOTAL (RT_WF_CTL_EXTRA + 1)                // ordered round: entries in sortedIdx (written by wf_scatter_kernel)
 #define RT_WF_CTL_WORDS (RT_WF_CTL_TOTAL + 3)                // (multiple of 4)
+// PLACEMENT TABLES, behind the three sets of control words in the same allocation (so that no kernel takes a further argument): one per
+// ordered round 1 .. RT_WF_PLACE_ROUNDS, what wf_scatter_kernel worked out the last time it ran for that round.  The frames of an
+// unchanged scene put the same rays into every (class, copy) cell ("Round 11"), so a planned frame's logic kernel
+// can write each entry at its sorted position at once (RT_ROUND_DIRECT) and the round needs no scatter launch.
+//   [RT_WF_SORT_BINS][RT_WF_SORT_COPIES] uint2 {first sorted position, entries} per cell, bin-major like the scatter kernel's base[]
+//   then RT_WF_PLACE_TAIL words: the total, the slices and segLen of the RtRoundMode it was recorded under, one spare
+#define RT_WF_PLACE_ROUNDS 8
+#define RT_WF_PLACE_CELLS (RT_WF_SORT_BINS * RT_WF_SORT_COPIES)
+#define RT_WF_PLACE_TOTAL (2 * RT_WF_PLACE_CELLS)
+#define RT_WF_PLACE_SLICES (RT_WF_PLACE_TOTAL + 1)
+#define RT_WF_PLACE_SEGLEN (RT_WF_PLACE_TOTAL + 2)
+#define RT_WF_PLACE_WORDS (RT_WF_PLACE_TOTAL + 4)
+#define RT_WF_PLACE_AT(round) (3 * RT_WF_CTL_WORDS + ((round) - 1u) * RT_WF_PLACE_WORDS) // word offset from RtWavefront::ctl, round in 1 .. RT_WF_PLACE_ROUNDS
 
 // How a round's entries are laid out and handed to the trace kernel.  Decided by the HOST before the round exists (from the launch
 // plan the same frame left behind, or from a guess in a watched frame) and passed to the kernels as an argument: a wrong guess
 // costs time, never correctness.
+#define RT_ROUND_DIRECT 2u
 struct RtRoundMode {
     uint32_t ordered;   // 1: a round most paths spawn a ray for (the first one, or any big one) -- the logic kernel writes complete trace entries,
                         // cuts long rays into segments and counts the entries' walk-length classes, wf_scatter_kernel places them longest
                         // first; 0: a round few paths spawn a ray for -- the logic kernel writes the rays, the trace kernel's workgroups plan
                         // them, cut them into segments and trace those, in queue order
-    uint32_t segLen;    // aimed-at cell visits per segment (>= 4096: rays are never cut)
+                        // 1 | RT_ROUND_DIRECT: an ordered round whose entries the logic kernel writes at their sorted positions, from the
+                        // round's placement table (RT_WF_PLACE_*): no wf_scatter_kernel, the trace kernel reads block i of the entries.
+                        // Decided by rt_frame_plan.h, round_goes_direct; the kernels never read the low bit (it is their template argument)
+    uint32_t segLen;   // aimed-at cell visits per segment (>= 4096: rays are never cut)
     uint32_t groupRays; // round that is not ordered: rays per workgroup of the trace kernel (1..64; about 256 / expected segments per ray)
     uint32_t slices;    // queue slices in use per kind (power of two <= RT_WF_SHARDS, never more than the round before): a big round
                         // spreads its appends over 256 counters, a small one keeps its entries in a few dense stretches

@@ -18,6 +18,7 @@ struct FrameState {
     uint32_t planRounds;     // rounds a planned batch issues
     uint64_t splitRounds = 0; // logic rounds issued as answer + shade launches, over the batches and groups
     bool anyPlannedBatch = false;
+    uint32_t directRounds = 0, scatterLaunches = 0; // ordered rounds placed directly / scatter launches issued, over the batches and groups
 };
 
 // Stage timing on: `launch` between two events of its own on `on`, counted under stage `which` (rtHipStageTimes).
@@ -125,7 +126,13 @@ RtRoundMode round_mode(const rtHipScene *sc, const FrameState &S, Group &G, uint
         uint64_t rays = G.guessRays;
         if (S.planned) rays = r < RT_WF_ROUND_LOG ? G.plan[r].rays : 0;
         else G.guessRays = std::max<uint64_t>(G.guessRays / 4, 1); // (watched: a round is assumed to hold a quarter of the one before)
-        G.modes.resize(r + 1, mode_for(sc->tune, r, rays, before));
+        RtRoundMode m = mode_for(sc->tune, r, rays, before);
+        // (decided once, here: logic(r - 1) places the entries and trace(r) reads them by the same flag)
+        const uint32_t batches = (sc->dev.sampleCount + sc->samplesPerBatch - 1u) / sc->samplesPerBatch;
+        if (round_goes_direct(S.planned, r, m, G.dev.pathClass, sc->tune.placeDirect, sc->tune.visitLog, batches, r <= RT_WF_PLACE_ROUNDS ? G.place[r] : PlaceStamp(),
+                              G.dev.seedStride, G.dev.sampleFirst))
+            m.ordered |= RT_ROUND_DIRECT;
+        G.modes.resize(r + 1, m);
     }
     return G.modes[r];
 }
@@ -140,12 +147,22 @@ int issue_round(rtHipScene *sc, FrameState &S, Group &G, hipStream_t on)
     const RoundPlan plan = r < RT_WF_ROUND_LOG ? G.plan[r] : RoundPlan();
     const RtRoundMode mode = r > 0 ? round_mode(sc, S, G, r) : RtRoundMode{ 0u, 4096u, 64u, (uint32_t)RT_WF_SHARDS };
     if (r > 0) { // the entries appended by logic(r-1): order them if the round is an ordered one, then walk the grid
-        if (mode.ordered) HIP_OK(stage(sc, 4, on, [&] { return rtw_launch_scatter(&G.wf, r, G.queueBlocks, &mode, on); }));
+        if (mode.ordered & RT_ROUND_DIRECT) ++S.directRounds; // (logic(r - 1) wrote the entries in sorted place: nothing to scatter)
+        else if (mode.ordered) {
+            HIP_OK(stage(sc, 4, on, [&] { return rtw_launch_scatter(&G.wf, r, G.queueBlocks, &mode, on); }));
+            ++S.scatterLaunches;
+            // the launch records the round's placement table under this layout; a frame of several batches leaves its last batch's, which no frame may use
+            if (r <= RT_WF_PLACE_ROUNDS) G.place[r] = PlaceStamp{ mode.slices, mode.segLen, G.dev.seedStride, G.dev.sampleFirst, sc->dev.sampleCount <= sc->samplesPerBatch };
+        }
         const uint32_t traceBlocks = trace_blocks(S.planned, r, mode, plan, G.traceBlocks, G.wf.capacity, G.wf.extraCap, T.planGridTiny != 0);
         HIP_OK(stage(sc, 2, on, [&] { return rtw_launch_trace(&G.dev, &G.wf, r, traceBlocks, &mode, on); }));
         if (T.visitLog && r < RT_WF_ROUND_LOG && log_round_visits(sc, G, r, mode, on) != 0) return -1;
     }
     const RtRoundMode next = round_mode(sc, S, G, r + 1);
+    if ((next.ordered & RT_ROUND_DIRECT) && T.placeSkew && !sc->placeSkewed) { // TEST ONLY: the table the entries are about to be placed by, skewed once
+        HIP_OK(rtw_launch_place_skew(&G.wf, r + 1, on));
+        sc->placeSkewed = true;
+    }
     // A split round (round_runs_split).  A planned frame sizes the shade launch from the list the plan
     // logged and skips it where that was empty; the answer kernel is told, and raises RT_WF_ERR_GRID if it lists a path all the same.
     if (runs_split(sc, G, r)) {
@@ -280,6 +297,12 @@ int rthost::render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery
     }
     const bool watchedFrame = forceDiscovery || sc->blocking || sc->planRounds == 0;
     FrameState S{ !watchedFrame, sc->planRounds };
+    // A watched frame is what everything that changes a frame's rays forces (planRounds = 0: camera, geometry, scene edit, sample window, pass
+    // switches) and what redoes a flagged frame: the placement tables recorded before it are not this scene state's.  Its own scatter
+    // launches record fresh ones.
+    if (watchedFrame)
+        for (auto &G : sc->groups)
+            for (PlaceStamp &p : G.place) p = PlaceStamp();
     uint64_t rounds = 0;
     const uint32_t sampleCount = sc->dev.sampleCount;
     for (uint32_t base = 0; base < sampleCount; base += sc->samplesPerBatch) {
@@ -320,6 +343,8 @@ int rthost::render_wavefront(rtHipScene *sc, hipStream_t st, bool forceDiscovery
         }
     sc->roundsLast = rounds;
     sc->splitRoundsLast = S.splitRounds;
+    sc->directRoundsLast = S.directRounds;
+    sc->scatterLaunchesLast = S.scatterLaunches;
     return 0;
 }
 

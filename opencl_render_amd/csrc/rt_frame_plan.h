@@ -79,6 +79,46 @@ inline bool round_runs_split(uint32_t r, uint32_t logicSplit, uint32_t lookAhead
     return r > 0 && logicSplit && lookAhead && pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE;
 }
 
+// What the host knows of a round's placement table (rt_device.h, RT_WF_PLACE_*) without reading it: the layout wf_scatter_kernel last
+// recorded it under, and whether that launch belongs to the scene state, sample window and plan in force -- a watched frame, which
+// everything that changes a frame's rays forces, forgets every stamp before its own scatter launches make new ones.
+// windowTotal, windowFirst: the sample window of the frame that recorded it (rtHipSampleWindow: N and f name the frame's sample ids, and
+// with them its rays).  A set window keeps the launch plan, so the next frame is a planned one: it scatters, and records anew.
+struct PlaceStamp { uint32_t slices = 0, segLen = 0, windowTotal = 0, windowFirst = 0; bool valid = false; };
+
+// Round r's entries are written at their sorted positions by the logic kernel that makes them, from the round's placement table, and the
+// round runs no scatter launch (RT_ROUND_DIRECT).  Only where the table is known to be this frame's and nothing reads entries by queue slot:
+//   planned, ordered, one of the rounds that have a table;
+//   uncut (region B is empty, no segment patches another's entry by position);
+//   slices >= 32: the histogram copy, wave id % RT_WF_SORT_COPIES, is then a function of the path's shard (the wave serves slice
+//     wave id % slicesIn, slicesIn >= slices a power of two), so a cell holds the same rays whatever the scheduling;
+//   the opaque-diffuse class (the general machine reads an answered entry back by its slot), visit_log off (that hook does too);
+//   one sample batch per frame (the table is one batch's);
+//   a valid stamp that equals the round's mode and the frame's sample window.
+inline bool round_goes_direct(bool planned, uint32_t r, const RtRoundMode &m, uint32_t pathClass, uint32_t placeDirect, uint32_t visitLog, uint32_t batches,
+                              const PlaceStamp &stamp, uint32_t windowTotal, uint32_t windowFirst)
+{
+    return placeDirect && planned && r >= 1u && r <= RT_WF_PLACE_ROUNDS && m.ordered && m.segLen >= 4096u && m.slices >= 32u &&
+           pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE && !visitLog && batches == 1u && stamp.valid && stamp.slices == m.slices && stamp.segLen == m.segLen &&
+           stamp.windowTotal == windowTotal && stamp.windowFirst == windowFirst;
+}
+
+// The table wf_scatter_kernel records from a round's histogram hist[copy][bin]: cell (bin, copy), stored at bin * RT_WF_SORT_COPIES + copy,
+// gets {first sorted position, entries} -- the cells in that order, class 0 (the longest walks) first, each starting where the one before
+// ends.  Returns the total.  The host's statement of the kernel's arithmetic (tests/place_plan_host.cpp, test_place_direct_gpu.py).
+inline uint32_t place_table(const uint32_t *hist, uint32_t *cells)
+{
+    uint32_t at = 0;
+    for (uint32_t b = 0; b < RT_WF_SORT_BINS; ++b)
+        for (uint32_t c = 0; c < RT_WF_SORT_COPIES; ++c) {
+            const uint32_t n = hist[c * RT_WF_SORT_BINS + b];
+            cells[2 * (b * RT_WF_SORT_COPIES + c)] = at;
+            cells[2 * (b * RT_WF_SORT_COPIES + c) + 1] = n;
+            at += n;
+        }
+    return at;
+}
+
 // A watched batch that took `rounds` rounds, laid out as modes[0 .. modeCount), has ended and left `log` (RtWavefront::roundLog):
 // the plan for the batches and frames to come: the rounds that had anything to trace (+ the logic round that consumed
 // the last answers), and every round's sizes

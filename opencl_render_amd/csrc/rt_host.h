@@ -189,12 +189,15 @@ struct rtHipScene {
         rthost::RoundPlan plan[RT_WF_ROUND_LOG], planNext[RT_WF_ROUND_LOG]; // (rt_frame_plan.h)
         std::vector<RtRoundMode> modes; // how the rounds of the batch being issued are laid out (modes[r] is decided when logic(r-1) is launched)
         uint64_t guessRays = 0;         // watched batches: what the next round is assumed to hold
+        rthost::PlaceStamp place[RT_WF_PLACE_ROUNDS + 1]; // per round: what its placement table on the device was recorded under (rt_frame_plan.h)
     };
     std::vector<Group> groups;
     rthost::Event forkEvent;
     uint32_t samplesPerBatch = 1;
     uint32_t planRounds = 0;   // rounds a planned frame issues per batch; 0 = no plan yet (the next frame is a discovery frame)
     uint64_t splitRoundsLast = 0; // logic rounds the last frame issued as answer + shade launches, over its batches and groups (rtHipTestShadeLog)
+    uint32_t directRoundsLast = 0, scatterLaunchesLast = 0; // ordered rounds the last frame placed directly / scatter launches it issued, over its batches and groups (rtHipTestPlaceLog)
+    bool placeSkewed = false;  // test hook place_skew: the one skew has been applied
     bool blocking = false;     // every frame watches the queue (no plan)
     rthost::Tuning tune;       // the tuning values this scene was built with (rtHipTune)
     bool unverified = false;   // planned frames were issued since the last frame_finish()

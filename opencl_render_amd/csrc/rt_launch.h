@@ -56,6 +56,7 @@ hipError_t rtw_launch_answer(const RtDevScene *scene, const RtWavefront *wf, uin
 hipError_t rtw_launch_shade(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next,
                             const RtShadeList *list, hipStream_t stream);
 hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
+hipError_t rtw_launch_place_skew(const RtWavefront *wf, uint32_t round, hipStream_t stream); // (test hook place_skew)
 hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
 hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, uint32_t *shadeCount, hipStream_t stream);
 hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefront *wf, int first, hipStream_t stream);

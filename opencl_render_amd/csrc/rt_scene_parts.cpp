@@ -417,10 +417,10 @@ int build_wavefront(rtHipScene *sc, uint32_t sampleCount)
             sc->alloc<uint2>(part, cap, &Wf.pathOf[1]) || sc->alloc<unsigned long long>(part, qcap, &Wf.hitKey[0]) || sc->alloc<unsigned long long>(part, qcap, &Wf.hitKey[1]) ||
             sc->alloc<uint4>(part, cap, &Wf.res) || sc->alloc<float4>(part, gpix * sb, &Wf.sampleOut) ||
             sc->alloc<uint32_t>(part, ecap, &Wf.sortRank) || sc->alloc<uint16_t>(part, ecap, &Wf.sortTag) || sc->alloc<uint32_t>(part, ecap, &Wf.sortedIdx) ||
-            sc->alloc<uint32_t>(part, (uint64_t)3 * RT_WF_CTL_WORDS, &Wf.ctl) ||
+            sc->alloc<uint32_t>(part, (uint64_t)3 * RT_WF_CTL_WORDS + (uint64_t)RT_WF_PLACE_ROUNDS * RT_WF_PLACE_WORDS, &Wf.ctl) || // (control words, then the placement tables)
             sc->alloc<uint4>(part, cap, &G.shade.list) || sc->alloc<uint32_t>(part, (uint64_t)3 * RT_WF_SHARDS, &G.shade.count)) // (split logic rounds: 16 bytes per path)
             return -1;
-        HIP_OK(hipMemsetAsync(Wf.ctl, 0, sizeof(uint32_t) * 3 * RT_WF_CTL_WORDS, sc->stream));
+        HIP_OK(hipMemsetAsync(Wf.ctl, 0, sizeof(uint32_t) * (3 * RT_WF_CTL_WORDS + RT_WF_PLACE_ROUNDS * RT_WF_PLACE_WORDS), sc->stream));
         HIP_OK(hipMemsetAsync(G.shade.count, 0, sizeof(uint32_t) * 3 * RT_WF_SHARDS, sc->stream));
         HIP_OK(G.hostLog.make(sizeof(uint4) * RT_WF_ROUND_LOG, hipHostMallocMapped));
         memset(G.hostLog, 0, sizeof(uint4) * RT_WF_ROUND_LOG);

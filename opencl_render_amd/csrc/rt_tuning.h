@@ -41,7 +41,11 @@ struct Tuning {
     uint32_t deadShadow = 1;        // 0: trace every shadow ray, also those whose answer only feeds the face[] entry that is never read
     uint32_t rayClip = 1;           // 1: grid rays without a far end stop where they leave the scene's clip bound (rt_ray_clip.h); 0: at the grid's wall
     uint32_t logicSplit = 1;        // 1: rounds >= 1 of the opaque-diffuse class (look-ahead on) run wf_answer_kernel + wf_shade_kernel; 0: wf_logic_kernel
-    uint64_t buildKeyCap = 0;       // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
+    uint32_t placeDirect = 1;       // 1: a planned frame's ordered rounds that qualify (rt_frame_plan.h, round_goes_direct) are placed by the logic kernel
+                                    // from the round's placement table and run no wf_scatter_kernel; 0: every ordered round is scattered
+    uint32_t placeSkew = 0;         // test hook: once per scene, the first placement table a round is about to be placed by is skewed by one entry
+                                    // between two cells (wf_place_skew_kernel), so that the guard, the flagged frame and its remedy run
+    uint64_t buildKeyCap = 0;      // test hook: first key capacity of the device grid build (0 = max(32 T, 2^22)), so that its grow and refill paths run
     uint64_t buildListLimit = 0xffffffffull; // test hook: most entries a device-built list may hold, so that the refusal above it runs
     uint32_t queryRays = 1u << 20;  // rays per staging chunk of rtHipSceneIntersect (52 bytes each, on the device and pinned on the host)
     uint32_t aoSamples = 1u << 20;  // pixel samples per chunk of the ambient occlusion calls (32 bytes each of scene-owned scratch)

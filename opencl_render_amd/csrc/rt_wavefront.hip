@@ -862,7 +862,10 @@ __device__ __forceinline__ uint32_t slice_count(const uint32_t *ctl, uint32_t sl
 // Work items: the used 256-entry blocks of the queue slices (region A: segment 0 of every ray, in queue order), then the blocks of
 // region B (further segments, densely packed); a fixed grid takes them in turn.  The logic kernel left a rank inside its (class,
 // copy) and the class itself per entry; the classes' sizes are in the round's histogram.
-__global__ __launch_bounds__(256) void wf_scatter_kernel(const RtWavefront W, const uint32_t round, const uint32_t slices)
+// The launch also RECORDS what it worked out -- every cell's first position and size, the total, the round's layout -- in the round's
+// placement table (rt_device.h, RT_WF_PLACE_*; rounds 1 .. RT_WF_PLACE_ROUNDS): the frames of an unchanged scene fill the cells alike, so a
+// later planned frame's logic kernel places the entries itself (RT_ROUND_DIRECT) and this kernel is not launched for the round.
+__global__ __launch_bounds__(256) void wf_scatter_kernel(const RtWavefront W, const uint32_t round, const uint32_t slices, const uint32_t segLen)
 {
     __shared__ uint32_t base[RT_WF_SORT_BINS * RT_WF_SORT_COPIES];
     __shared__ uint32_t longWave[4];
@@ -886,9 +889,18 @@ __global__ __launch_bounds__(256) void wf_scatter_kernel(const RtWavefront W, co
         }
         uint32_t at = incl - sum;
         for (int c = 0; c < RT_WF_SORT_COPIES; ++c) { base[threadIdx.x * RT_WF_SORT_COPIES + c] = at; at += ctl[RT_WF_CTL_HIST + c * RT_WF_SORT_BINS + threadIdx.x]; }
-        if (blockIdx.x == 0 && threadIdx.x == RT_WF_SORT_BINS - 1) ctl[RT_WF_CTL_TOTAL] = incl; // all entries are in [0, total)
+        if (blockIdx.x == 0 && threadIdx.x == RT_WF_SORT_BINS - 1) {
+            ctl[RT_WF_CTL_TOTAL] = incl; // all entries are in [0, total)
+            if (round >= 1u && round <= RT_WF_PLACE_ROUNDS) W.ctl[RT_WF_PLACE_AT(round) + RT_WF_PLACE_TOTAL] = incl;
+        }
     }
     __syncthreads();
+    if (blockIdx.x == 0 && round >= 1u && round <= RT_WF_PLACE_ROUNDS) {
+        uint32_t *place = W.ctl + RT_WF_PLACE_AT(round);
+        for (uint32_t i = threadIdx.x; i < RT_WF_PLACE_CELLS; i += 256) // i = bin * copies + copy
+            reinterpret_cast<uint2 *>(place)[i] = make_uint2(base[i], ctl[RT_WF_CTL_HIST + (i % RT_WF_SORT_COPIES) * RT_WF_SORT_BINS + i / RT_WF_SORT_COPIES]);
+        if (threadIdx.x == 0) { place[RT_WF_PLACE_SLICES] = slices; place[RT_WF_PLACE_SEGLEN] = segLen; }
+    }
     const uint32_t usedBlocks = (max(max(longWave[0], longWave[1]), max(longWave[2], longWave[3])) + 255u) >> 8;
     const uint32_t itemsA = 2u * slices * usedBlocks;
     const uint32_t extra = min(ctl[RT_WF_CTL_EXTRA], W.extraCap); // the count runs past the capacity when region B filled up (wf_logic_kernel)
@@ -915,6 +927,14 @@ __global__ __launch_bounds__(256) void wf_scatter_kernel(const RtWavefront W, co
             }
         }
     }
+}
+
+__global__ void wf_place_skew_kernel(const RtWavefront W, const uint32_t round)
+{
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    uint2 *cell = reinterpret_cast<uint2 *>(W.ctl + RT_WF_PLACE_AT(round));
+    for (uint32_t i = 0; i + 1u < RT_WF_PLACE_CELLS; ++i)
+        if (cell[i].y != 0u) { cell[i].y -= 1u; cell[i + 1].x -= 1u; cell[i + 1].y += 1u; return; }
 }
 
 // ---- stage 3: grid traversal (raytrace_opencl.c:324-401) ------------------------------------------------------------------
@@ -984,8 +1004,21 @@ __global__ __launch_bounds__(256, RT_WF_LEAN_WAVES) void wf_trace_kernel(const R
     uint32_t mine = 0, segments = 0;
     bool active = false;
     if (ORDERED) {
-        const uint32_t total = ctl[RT_WF_CTL_TOTAL];
+        // (a round placed directly, RT_ROUND_DIRECT: no scatter launch wrote the total or an order -- the total is the placement table's and
+        // the entries stand in sorted order, so the workgroup's 256 are one 16 KB block and nothing is looked up on the way to them)
+        const bool direct = (mode.ordered & RT_ROUND_DIRECT) != 0u;
+        const uint32_t total = direct ? W.ctl[RT_WF_PLACE_AT(round) + RT_WF_PLACE_TOTAL] : ctl[RT_WF_CTL_TOTAL];
         const uint32_t blocksUsed = (total + 255u) >> 8;
+        if (direct && blockIdx.x + 1u == blocksUsed && wave == 0u) {
+            // No cell took more than its run (the logic kernel's guard), so the cells are exactly full if the round made as many entries as
+            // the table places; fewer, and some position still holds an entry of an earlier frame: the frame is invalid
+            uint32_t n = 0;
+#pragma unroll
+            for (int i = 0; i < RT_WF_QSHARDS / 64; ++i) n += ctl[RT_WF_CTL_COUNTS + i * 64 + lane];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off, 64);
+            if (lane == 0u && n != total) atomicOr(W.hostStatus + RT_WF_STATUS_ERROR, RT_WF_ERR_GRID);
+        }
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             if (round < RT_WF_ROUND_LOG) reinterpret_cast<uint32_t *>(W.roundLog + round)[2] = min(ctl[RT_WF_CTL_EXTRA], W.extraCap);
             if (blocksUsed > gridDim.x) atomicOr(W.hostStatus + RT_WF_STATUS_ERROR, RT_WF_ERR_GRID);
@@ -993,7 +1026,7 @@ __global__ __launch_bounds__(256, RT_WF_LEAN_WAVES) void wf_trace_kernel(const R
         if (blockIdx.x >= blocksUsed) return; // whole workgroup beyond the entries
         const uint32_t at = blockIdx.x * 256 + threadIdx.x;
         active = at < total;
-        if (active) mine = W.sortedIdx[at];
+        if (active) mine = direct ? at : W.sortedIdx[at];
         for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
         __syncthreads();
     } else {
@@ -1108,6 +1141,9 @@ __global__ __launch_bounds__(256, RT_WF_LEAN_WAVES) void wf_trace_kernel(const R
             o = mk(__uint_as_float(c2.x), __uint_as_float(c2.y), __uint_as_float(c2.z)); tmax = __uint_as_float(c2.w);
             d = mk(__uint_as_float(c3.x), __uint_as_float(c3.y), __uint_as_float(c3.z));
             seg = c3.w >> 24;
+            // (a position that this frame did not fill -- a round placed directly whose table was not the frame's, flagged where it is found
+            // out -- holds whatever was there: the answer goes to hitKey[q], so a q that is no queue slot is not walked)
+            active = q < 2u * W.capacity;
         }
     } else {
         const uint32_t i = threadIdx.x;
@@ -1647,6 +1683,7 @@ extern "C" hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefron
 {
     if (blocks % (RT_WF_SHARDS / 4) != 0) return hipErrorInvalidValue; // a whole number of waves per queue slice (wf_logic_kernel)
     if (!mode_ok(*next) || slicesIn < next->slices || slicesIn > RT_WF_SHARDS || (slicesIn & (slicesIn - 1u)) != 0u) return hipErrorInvalidValue;
+    if ((next->ordered & RT_ROUND_DIRECT) && (round >= RT_WF_PLACE_ROUNDS || scene->pathClass != RT_PATH_CLASS_OPAQUE_DIFFUSE)) return hipErrorInvalidValue;
     if (scene->pathClass == RT_PATH_CLASS_OPAQUE_DIFFUSE) {
         if (round == 0u && next->ordered) hipLaunchKernelGGL((wf_logic_kernel<true, true, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
         else if (round == 0u) hipLaunchKernelGGL((wf_logic_kernel<true, false, true>), dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next);
@@ -1679,6 +1716,7 @@ extern "C" hipError_t rtw_launch_shade(const RtDevScene *scene, const RtWavefron
     if (blocks == 0u || blocks % (RT_WF_SHARDS / 4) != 0) return hipErrorInvalidValue;
     if (!mode_ok(*next) || slicesIn < next->slices || slicesIn > RT_WF_SHARDS || (slicesIn & (slicesIn - 1u)) != 0u) return hipErrorInvalidValue;
     if (scene->pathClass != RT_PATH_CLASS_OPAQUE_DIFFUSE || !wf->lookAhead || round == 0u || !list->list || !list->count) return hipErrorInvalidValue;
+    if ((next->ordered & RT_ROUND_DIRECT) && round >= RT_WF_PLACE_ROUNDS) return hipErrorInvalidValue;
     if (next->ordered) hipLaunchKernelGGL(wf_shade_kernel<true>, dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next, *list);
     else hipLaunchKernelGGL(wf_shade_kernel<false>, dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, slicesIn, *next, *list);
     return hipGetLastError();
@@ -1688,7 +1726,17 @@ extern "C" hipError_t rtw_launch_shade(const RtDevScene *scene, const RtWavefron
 extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream)
 {
     if (!mode_ok(*mode)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(wf_scatter_kernel, dim3(blocks), dim3(256), 0, stream, *wf, round, mode->slices);
+    hipLaunchKernelGGL(wf_scatter_kernel, dim3(blocks), dim3(256), 0, stream, *wf, round, mode->slices, mode->segLen);
+    return hipGetLastError();
+}
+
+// TEST ONLY (tuning key place_skew): the round's recorded placement table with one entry moved from its first cell that holds any to the
+// cell behind it -- still a partition of [0, total), but not the one the frame's entries want: a frame placed by it runs one cell over
+// (the guard's path) and leaves the other a stale entry.
+extern "C" hipError_t rtw_launch_place_skew(const RtWavefront *wf, uint32_t round, hipStream_t stream)
+{
+    if (round < 1u || round > RT_WF_PLACE_ROUNDS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wf_place_skew_kernel, dim3(1), dim3(64), 0, stream, *wf, round);
     return hipGetLastError();
 }
 
@@ -1696,6 +1744,7 @@ extern "C" hipError_t rtw_launch_scatter(const RtWavefront *wf, uint32_t round, 
 extern "C" hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream)
 {
     if (!mode_ok(*mode)) return hipErrorInvalidValue;
+    if ((mode->ordered & RT_ROUND_DIRECT) && (round < 1u || round > RT_WF_PLACE_ROUNDS)) return hipErrorInvalidValue;
     if (mode->ordered) hipLaunchKernelGGL(wf_trace_kernel<true>, dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, *mode);
     else hipLaunchKernelGGL(wf_trace_kernel<false>, dim3(blocks), dim3(256), 0, stream, *scene, *wf, round, *mode);
     return hipGetLastError();

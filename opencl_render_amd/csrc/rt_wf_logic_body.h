@@ -717,6 +717,8 @@
         // DDA start state, segments, walk-length class -- so that nothing stands between this kernel and the walk but the placing of
         // the classes.  Any other round: the ray alone; wf_trace_kernel<false> plans and cuts it (stage "trace entries").
         const uint32_t copy = waveId % RT_WF_SORT_COPIES;
+        // (class kernels only: the general machine reads an answered entry back by its queue slot, so its entries stay where they are)
+        const bool direct = LEAN && ORDERED && (next.ordered & RT_ROUND_DIRECT) != 0u; // wave-uniform: the host's decision
         if (!ORDERED) {
 #pragma unroll 1
             for (int which = 0; which < 2; ++which) {
@@ -840,7 +842,17 @@
                 uint32_t l2 = lane;
                 asm volatile("" : "+v"(l2)); // (the address is made here: hoisted out of the chunk loop it was spilled)
                 const uint32_t n = waveHist[wave][l2];
-                waveBase[wave][l2] = n ? atomicAdd(&ctlOut[RT_WF_CTL_HIST + copy * RT_WF_SORT_BINS + l2], n) : 0u;
+                uint32_t first = n ? atomicAdd(&ctlOut[RT_WF_CTL_HIST + copy * RT_WF_SORT_BINS + l2], n) : 0u;
+                if (direct) {
+                    // the rank in the cell becomes the sorted position: the cell's run starts where the placement table says.  A cell that
+                    // would run over (the table is not this frame's: RT_WF_ERR_GRID) gets none of this wave's entries -- no store ever
+                    // lands outside its cell's run, whatever the counters do
+                    const uint2 cell = reinterpret_cast<const uint2 *>(W.ctl + RT_WF_PLACE_AT(round + 1u))[l2 * RT_WF_SORT_COPIES + copy];
+                    const bool over = n != 0u && (first > cell.y || n > cell.y - first);
+                    first = over ? 0xffffffffu : first + cell.x;
+                    if (over) atomicOr(W.hostStatus + RT_WF_STATUS_ERROR, RT_WF_ERR_GRID);
+                }
+                waveBase[wave][l2] = first;
                 waveHist[wave][l2] = 0u; // (for this wave's next chunk)
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -855,19 +867,32 @@
                 const uint32_t excluded = which ? laexcl : rexcl, mine = which ? slotLa : slot;
                 const uint32_t bin = which ? binL : binM, rank = which ? rankL : rankM, cell = which ? planL.start.cell : planM.start.cell;
                 const uint32_t endCell = which ? planL.endCell : planM.endCell, nseg = which ? nsegL : nsegM;
-                uint4 *e = W.ent[outq] + 4 * (size_t)mine;
+                // (a round placed directly: the entry goes to its sorted position and only the path's links and the answer stay at the queue
+                // slot -- the entry names its slot, which is all the trace kernel wants of it; a cell the table has no room for stores nothing)
+                uint32_t at = mine;
+                bool placed = true;
+                if (direct) {
+                    const uint32_t first = waveBase[wave][bin];
+                    placed = first != 0xffffffffu;
+                    at = first + rank;
+                }
+                uint4 *e = W.ent[outq] + 4 * (size_t)at;
                 if (!which) W.pathOf[outq][mine] = make_uint2(a, emitLa ? slotLa : 0xffffffffu); // (only main entries are ever looked up: wf_logic_kernel's prologue)
                 W.hitKey[outq][mine] = ~0ull; // no segment of this ray has a hit yet
-                if (nseg > 1u) { // (.z comes from another lane: not written here, so that the two stores cannot meet)
-                    *reinterpret_cast<uint2 *>(e) = make_uint2(mine, cell);
-                    reinterpret_cast<uint32_t *>(e)[3] = excluded;
-                } else e[0] = make_uint4(mine, cell, endCell, excluded);
-                e[1] = make_uint4(__float_as_uint(which ? planL.start.dx : planM.start.dx), __float_as_uint(which ? planL.start.dy : planM.start.dy),
-                                  __float_as_uint(which ? planL.start.dz : planM.start.dz), __float_as_uint(tmin));
-                e[2] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(tmax));
-                e[3] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), 0u); // (segment 0)
-                W.sortRank[mine] = waveBase[wave][bin] + rank;
-                W.sortTag[mine] = (uint16_t)(bin | (copy << 6));
+                if (placed) {
+                    if (nseg > 1u) { // (.z comes from another lane: not written here, so that the two stores cannot meet)
+                        *reinterpret_cast<uint2 *>(e) = make_uint2(mine, cell);
+                        reinterpret_cast<uint32_t *>(e)[3] = excluded;
+                    } else e[0] = make_uint4(mine, cell, endCell, excluded);
+                    e[1] = make_uint4(__float_as_uint(which ? planL.start.dx : planM.start.dx), __float_as_uint(which ? planL.start.dy : planM.start.dy),
+                                      __float_as_uint(which ? planL.start.dz : planM.start.dz), __float_as_uint(tmin));
+                    e[2] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(tmax));
+                    e[3] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), 0u); // (segment 0)
+                }
+                if (!direct) {
+                    W.sortRank[mine] = waveBase[wave][bin] + rank;
+                    W.sortTag[mine] = (uint16_t)(bin | (copy << 6));
+                }
             }
             // The further segments, one per lane whoever's ray it is (a lane making its ray's up to 11 cuts one after the other while the
             // wave's other lanes wait was 40 % of a chunk's time).  Segment k goes from the walk's state at tau_k to the start cell of

@@ -202,7 +202,7 @@ RESIDENT_SYMBOLS = [
     "rtHipSceneDepthOfField", "rtHipSceneDepthOfFieldTimes", "rtHipDepthOfFieldLens",
     "rtHipBakeDefaults", "rtHipSceneBakeAmbientOcclusion", "rtHipSceneBakeAmbientOcclusionDevice",
     "rtHipKernelTime", "rtHipBuildCameraList", "rtHipBuildCameraListDevice", "rtHipBuildSceneGrid", "rtHipBuildSceneGridDevice", "rtHipFree",
-    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestRoundVisits", "rtHipTestShadeLog", "rtHipTestBuildLog",
+    "rtHipDeviceKat", "rtHipTune", "rtHipTestCachePointers", "rtHipTestHashBytes", "rtHipScenePathClass", "rtHipTestPathClass", "rtHipTestRoundLog", "rtHipTestRoundVisits", "rtHipTestShadeLog", "rtHipTestPlaceLog", "rtHipTestPlaceView", "rtHipTestBuildLog",
     "rtHipTestShadeKat", "rtHipTestSceneView", "rtHipTestSceneCameraList", "rtHipTestScenePointers", "rtHipTestSceneCameraLog", "rtHipTestSceneCameraTimes",
     "rtHipTestSceneGeometryLog", "rtHipTestSceneGeometryTimes",
     "rtHipSetCamera", "rtHipMeshCount", "rtHipMeshFill", "rtHipLightFill", "rtHipBakeMaterials", "rtHipPlanesToRgb8", "rtHipWriteBmp", "rtHipWritePpm", "rtHipWritePgm", "rtHipWritePfm", "rtHipWritePfmRgb",
@@ -402,6 +402,8 @@ def lib() -> C.CDLL:
     L.rtHipTestRoundLog.argtypes = [vp, C.POINTER(u32), u32]
     L.rtHipTestRoundVisits.argtypes = [vp, C.POINTER(C.c_uint64), u32]
     L.rtHipTestShadeLog.argtypes = [vp, C.POINTER(u32), u32]
+    L.rtHipTestPlaceLog.argtypes = [vp, C.POINTER(u32)]
+    L.rtHipTestPlaceView.argtypes = [vp, u32, vp, vp, u32]
     L.rtHipTestBuildLog.argtypes = [C.POINTER(u64), u32]
     L.rtHipTestShadeKat.argtypes = [vp, C.c_int, u32, vp, vp]
     L.rtHipTestSceneView.argtypes = [vp, C.c_int, u64, u64, vp]
@@ -419,7 +421,7 @@ _ENV_KEYS = {
     "RT_WF_APPEND_RAYS": "append_rays", "RT_WF_ORDERED_FIRST": "ordered_first", "RT_WF_SLICE_RAYS": "slice_rays", "RT_WF_SMALL_SLICES": "small_slices", "RT_WF_GROUP_RAYS": "group_rays",
     "RT_WF_BLOCKING": "blocking", "RT_WF_BATCH_PLAN": "batch_plan", "RT_WF_PLAN_ROUNDS": "plan_rounds", "RT_HIP_PIPELINE": "pipeline",
     "RT_HIP_TIMING": "timing", "RT_HIP_VIRTUAL_DEVICES": "virtual_devices", "RT_HIP_CACHE": "cache",
-    "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow", "RT_WF_RAY_CLIP": "ray_clip", "RT_WF_LOGIC_SPLIT": "logic_split", "RT_WF_PLAN_SHADE_SKIP": "plan_shade_skip", "RT_WF_VISIT_LOG": "visit_log",
+    "RT_WF_LOGIC_CLASS": "logic_class", "RT_WF_DEAD_SHADOW": "dead_shadow", "RT_WF_RAY_CLIP": "ray_clip", "RT_WF_LOGIC_SPLIT": "logic_split", "RT_WF_PLACE_DIRECT": "place_direct", "RT_WF_PLACE_SKEW": "place_skew", "RT_WF_PLAN_SHADE_SKIP": "plan_shade_skip", "RT_WF_VISIT_LOG": "visit_log",
     "RT_BUILD_KEY_CAP": "build_key_cap", "RT_BUILD_LIST_LIMIT": "build_list_limit", "RT_HIP_QUERY_RAYS": "query_rays",
     "RT_MATTE_CHUNK": "matte_chunk",
 }
@@ -1006,6 +1008,7 @@ SCENE_VIEWS_EXTRA = {"tri_shade_row": (18, np.float32, 32)}
 SCENE_VIEW_CLIP_PLANES = 16  # (RT_SCENE_VIEW_CLIP_PLANES; read by ResidentScene.clip_planes)
 SCENE_VIEW_CLIP_APPLIED = 17  # (RT_SCENE_VIEW_CLIP_APPLIED; read by ResidentScene.clip_applied)
 ROUND_VISIT_FIELDS = 12  # (RT_ROUND_VISIT_FIELDS)
+PLACE_TABLE_WORDS = 2 * 64 * 32 + 4  # (RT_PLACE_TABLE_WORDS)
 SCENE_VIEW_HEADER = ("planes_tame", "tile_count", "tiles_x", "triangle_count", "pair_count")
 
 
@@ -1468,6 +1471,25 @@ class ResidentScene:
         if rounds < 0:
             raise RuntimeError("rtHipTestShadeLog failed")
         return rounds, [int(v) for v in listed]
+
+    def place_log(self):
+        """(ordered rounds the last frame placed directly, scatter launches it issued) -- rtHipTestPlaceLog."""
+        out = (C.c_uint32 * 2)()
+        if lib().rtHipTestPlaceLog(self.handle, out) != 0:
+            raise RuntimeError("rtHipTestPlaceLog failed")
+        return int(out[0]), int(out[1])
+
+    def place_view(self, round_: int, positions: Optional[int] = None):
+        """rtHipTestPlaceView of the first tile group: (cells [64 classes, 32 copies, 2] u32 {first sorted position, entries}, total,
+        (slices, segment length) of the recorded layout, entries [positions, 16] u32 -- by default the table's total of them)."""
+        table = np.zeros(PLACE_TABLE_WORDS, np.uint32)
+        self._check(lib().rtHipTestPlaceView(self.handle, round_, _ptr(table), None, 0), "rtHipTestPlaceView")
+        total = int(table[PLACE_TABLE_WORDS - 4])
+        n = total if positions is None else positions
+        entries = np.zeros((n, 16), np.uint32)
+        if n:
+            self._check(lib().rtHipTestPlaceView(self.handle, round_, None, _ptr(entries), n), "rtHipTestPlaceView")
+        return table[:PLACE_TABLE_WORDS - 4].reshape(64, 32, 2), total, (int(table[PLACE_TABLE_WORDS - 3]), int(table[PLACE_TABLE_WORDS - 2])), entries
 
     def shade_kat(self, op: int, inp: np.ndarray) -> np.ndarray:
         """rtHipTestShadeKat on this scene: `inp` holds one 40-byte (RT_SHADE_KAT_TEXEL) or 48-byte (RT_SHADE_KAT_NORMAL) row per item;
