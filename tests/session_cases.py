@@ -70,8 +70,27 @@ in the mask, renders a frame first where there is none under the mask in effect 
 for a stale pose or shape, and changes nothing.  Without a device the model takes the depth pass from its definition (oracle_depth),
 so that tests/test_session.py can measure the blurs and compare the model with the feature tests' own chains.  The draw of a passes
 step favours masks with the depth pass (MASKS_POST), the draw of a clamp step looks one kind ahead (Lite.upcoming) so that a temporal
-step directly follows the clamp being turned off over a history made under it; the caps: POST_FACTS and post_caps."""
+step directly follows the clamp being turned off over a history made under it; the caps: POST_FACTS and post_caps.
+
+Layouts.  Under default tuning the small images render round 1 ordered and cut and every later round appended, and almost every frame
+of a sequence is the first after some change: what the product keeps between the frames of an unchanged scene -- the launch plan
+(Group::plan, planRounds), the placement tables and their stamps (rt_frame_plan.h, round_goes_direct), control words left clean by a
+planned batch, the tile groups' copies, several sample batches -- is never live while the operations run.  So 58 sequences of
+existing seeds (LAYOUT_SEEDS) are played once more under a layout (LAYOUTS: RT_* variables set in os.environ while the scene, its
+clones and twins are created), and there every frame whose repetition is idempotent in the model (settles: the window neither
+advances nor continues, wavefront pipeline) is rendered three times, a clone's too: each read-back equals the planes the model has
+for the step, the second and third are not rendered again, and the last reports the placement the layout promises (Session.placed:
+under direct and direct_unsplit every trace round of a frame in the opaque-diffuse class placed directly and none scattered, in the
+general class all scattered; under cut all scattered; under groups nothing direct and round 1 scattered once per tile group and
+sample batch, which is how the batch count is asserted).  The model is untouched by the repeats -- window_last, history, mark and
+tile buffer are what one frame leaves --, so every later step checks what the step after a settled frame left behind.  Other frames
+(advancing and continuing windows, the megakernel) are single frames between the settled ones.  COUNTS_LAYOUT holds what that
+exercises.  Kinds that a layout's sequences never put between a settled frame and a later frame (LAYOUT_UNCOVERED): clamp,
+motion_blur and dof under every layout (no post seed is played under one); under direct_unsplit also mark, window and lights; under
+cut also lights; under groups also denoise, lights, materials, ids, refused_edit, matte_groups and mattes."""
+import collections
 import ctypes
+import os
 
 import numpy as np
 
@@ -212,6 +231,74 @@ SMALL = "mirror_hall"  # AO and the bake are also compared with their numpy orac
 # description in effect.  It reads the description the frame was issued under now.
 REGRESSIONS = {"material_pass_after_ids": ("class_textured_bumped", ("home", "home"),
                                            (("passes", 31), ("frame", None), ("ids", ((1, 6), "numpy")), ("read_passes", None)))}
+# Layouts: the RT_* variables a sequence is played under once more (play(layout=); the Python stub turns them into rtHipTune calls
+# when a scene is created), so that the state the product keeps between the frames of an unchanged scene -- the launch plan, the
+# placement tables and their stamps, clean control words, the tile groups' copies -- is live while the operations run.
+# direct: every trace round is ordered and uncut (test_place_direct_gpu.BASE_ENV); in the opaque-diffuse class planned frames place
+# their rounds directly.  direct_unsplit: the class ORDERED logic kernel places round 2, not wf_shade_kernel<true>.  cut: every round
+# ordered and cut, region B sized from the plan, the slices merge mid-frame (the entry of pipeline_modes.MODES); nothing may go direct.
+# groups: three tile groups on the four-tile scene and one sample per batch, so a frame of S = 2 renders in two batches: by
+# build_wavefront (rt_scene_parts.cpp) a path takes 1860 bytes under the default extra_factor, 116.25 MiB for the 65536 pixels of four
+# tiles and 87.2 MiB for the three of a tile subset, so a budget of 100 MiB holds one sample of either and not two.
+LAYOUTS = {"direct": {"RT_WF_SEG_RAYS": "1", "RT_WF_APPEND_RAYS": "0"},
+           "direct_unsplit": {"RT_WF_SEG_RAYS": "1", "RT_WF_APPEND_RAYS": "0", "RT_WF_LOGIC_SPLIT": "0"},
+           "cut": {"RT_WF_APPEND_RAYS": "0", "RT_WF_SEG": "24,24,24,24,24", "RT_WF_SEG_RAYS": "1,1,1,1", "RT_WF_SLICE_RAYS": "20000",
+                   "RT_WF_SMALL_SLICES": "4"},
+           "groups": {"RT_WF_GROUPS": "3", "RT_WF_STATE_MB": "100"}}
+# (layout, scene, seed): the sequences played under a layout, all of existing seeds -- 18 + 1 + 8, 1, 11 + 1 and 16 + 2 sequences.
+LAYOUT_SEEDS = (("direct", "class_textured_bumped", 21), ("direct", "class_textured_bumped", 110), ("direct", "mirror_hall", 1),
+                ("direct_unsplit", "class_textured_bumped", 110), ("cut", "mirror_hall", 4), ("cut", "class_textured_bumped", 110),
+                ("groups", "axis_near_axis_mixed", 3), ("groups", "axis_near_axis_mixed", 106))
+SETTLED_FRAMES = 3  # under a layout a frame that can be rendered again is: the first may be watched, the others run from what it left
+# What the sequences under a layout exercise, by the light model alone (layout_facts; tests/test_session.py prints the figures and asserts
+# them per seed, and per layout what they add up to): the frames of the sequences' own scenes, settled (rendered SETTLED_FRAMES times)
+# and single, the settled ones by path class; the clones, whose frames are settled as well; and per kind of step -- one that the
+# state refuses apart -- how often it lies between a settled frame and a later frame of its sequence.  Over the 58 sequences the
+# device renders 28 + 4 + 23 = 55 settled frames under direct, 26 of them in the opaque-diffuse class, 4 under direct_unsplit,
+# 18 + 4 under cut and 33 + 3 under groups, and as many clone frames as there are clones.
+COUNTS_LAYOUT = {
+    ("class_textured_bumped", 21): dict(
+        sequences=18, steps=643, settled=28, single=18, settled_class=22, settled_general=6, clones=25,
+        between={'ao': 5, 'bake': 4, 'camera': 7, 'clone': 6, 'denoise': 3, 'denoise (refused)': 6, 'frame': 9, 'ids': 6, 'intersect': 5,
+                 'lights': 10, 'mark': 6, 'materials': 13, 'matte_groups': 9, 'mattes': 6, 'mattes (refused)': 1, 'motion': 8,
+                 'motion (refused)': 4, 'passes': 9, 'pipeline': 1, 'read_passes': 8, 'refused_camera': 9, 'refused_edit': 12,
+                 'refused_update': 7, 'reset_temporal': 5, 'shape': 8, 'temporal': 8, 'temporal (refused)': 0, 'variance': 9, 'window': 12,
+                 'window (refused)': 1}),
+    ("class_textured_bumped", 110): dict(
+        sequences=1, steps=60, settled=4, single=0, settled_class=4, settled_general=0, clones=1,
+        between={'ao': 2, 'bake': 2, 'camera': 2, 'clone': 1, 'denoise': 2, 'denoise (refused)': 1, 'frame': 1, 'ids': 2, 'intersect': 2,
+                 'materials': 2, 'matte_groups': 1, 'mattes': 2, 'motion': 1, 'motion (refused)': 0, 'passes': 3, 'pipeline': 1,
+                 'pipeline (refused)': 1, 'read_passes': 2, 'refused_camera': 3, 'refused_edit': 2, 'refused_update': 1, 'reset_temporal': 3,
+                 'shape': 2, 'temporal': 3, 'variance': 6}),
+    ("mirror_hall", 1): dict(
+        sequences=8, steps=297, settled=23, single=3, settled_class=0, settled_general=23, clones=17,
+        between={'ao': 10, 'bake': 9, 'camera': 9, 'clone': 13, 'denoise': 3, 'denoise (refused)': 8, 'frame': 9, 'intersect': 12, 'mark': 11,
+                 'motion': 9, 'motion (refused)': 3, 'passes': 10, 'pipeline': 16, 'read_passes': 10, 'refused_camera': 9,
+                 'refused_update': 12, 'reset_temporal': 13, 'shape': 9, 'temporal': 10, 'temporal (refused)': 0}),
+    ("mirror_hall", 4): dict(
+        sequences=11, steps=372, settled=18, single=15, settled_class=0, settled_general=18, clones=19,
+        between={'ao': 3, 'bake': 9, 'camera': 4, 'clone': 6, 'denoise': 4, 'denoise (refused)': 3, 'frame': 7, 'intersect': 5, 'mark': 7,
+                 'motion': 4, 'motion (refused)': 0, 'passes': 4, 'passes (refused)': 0, 'pipeline': 3, 'pipeline (refused)': 1,
+                 'read_passes': 9, 'refused_camera': 4, 'refused_update': 7, 'reset_temporal': 4, 'shape': 6, 'temporal': 5,
+                 'temporal (refused)': 1, 'variance': 4, 'variance (refused)': 0, 'window': 4, 'window (refused)': 0}),
+    ("axis_near_axis_mixed", 3): dict(
+        sequences=16, steps=305, settled=33, single=2, settled_class=0, settled_general=33, clones=18,
+        between={'ao': 10, 'bake': 8, 'camera': 10, 'clone': 9, 'denoise': 0, 'denoise (refused)': 8, 'frame': 4, 'intersect': 6, 'mark': 10,
+                 'motion': 12, 'motion (refused)': 2, 'passes': 10, 'pipeline': 8, 'read_passes': 5, 'refused_camera': 7,
+                 'refused_update': 9, 'reset_temporal': 10, 'shape': 8, 'temporal': 8, 'temporal (refused)': 0}),
+    ("axis_near_axis_mixed", 106): dict(
+        sequences=2, steps=61, settled=3, single=3, settled_class=0, settled_general=3, clones=3,
+        between={'ao': 1, 'bake': 1, 'camera': 1, 'clone': 0, 'frame': 2, 'intersect': 1, 'mark': 1, 'motion': 0, 'passes': 0, 'pipeline': 1,
+                 'read_passes': 2, 'refused_camera': 1, 'refused_update': 0, 'reset_temporal': 2, 'shape': 1, 'temporal': 4,
+                 'temporal (refused)': 0, 'variance': 2, 'variance (refused)': 0, 'window': 2})}
+# The kinds that no step of a layout's sequences puts between a settled frame and a later frame (refused steps not counted; the module
+# docstring lists them): no post seed is played under a layout, direct covers everything else (circuit 21 alone does), the walk 110
+# draws no lights, mark or window step, and the larger scene has no edit seed and its circuit 3 no denoise step in that position.
+KINDS_ALL = KINDS_EDIT + KINDS_POST[len(KINDS_WIDE):]
+LAYOUT_UNCOVERED = {"direct": ("clamp", "motion_blur", "dof"),
+                    "direct_unsplit": ("mark", "window", "lights", "clamp", "motion_blur", "dof"),
+                    "cut": ("lights", "clamp", "motion_blur", "dof"),
+                    "groups": ("denoise", "lights", "materials", "ids", "refused_edit", "matte_groups", "mattes", "clamp", "motion_blur", "dof")}
 
 
 def flags(mask):
@@ -556,6 +643,15 @@ def window_kind(win, samples):
     return "sequence" if adv else "fixed"
 
 
+def settles(window, pipeline):
+    """Whether rendering the frame of `window` again is idempotent in the model, so that under a layout the device renders it
+    SETTLED_FRAMES times: the window does not advance and the frame does not continue from the tile buffer (every frame of it is the
+    same frame), on the wavefront pipeline (the megakernel keeps no plan and no table).  The one rule of the model's count
+    (Lite.render_frame, tests/test_session.py) and of the device (Session.on_device)."""
+    N, f, D, acc, adv = window
+    return pipeline == R.PIPELINE_WAVEFRONT and not adv and not (acc and f > 0)
+
+
 class CapLog:
     """What the caps of the edit seeds ask about a sequence, kept beside the light state: nothing but the caps and the draw's
     steering towards them reads it."""
@@ -763,7 +859,7 @@ class Lite:
             self.run = None
         complete = N if self.run == N and kind == "progressive" and f == N - S else 0
         self.frames.append(dict(state=(self.pose, self.shape), window=win, kind=kind, continuing=bool(acc and f > 0), moved=self.moved,
-                                complete=complete))
+                                complete=complete, settled=settles(win, self.pipeline)))
         if self.name:  # the class the frame runs in and the step it follows; whether it continues another look's buffer; the edit it shows
             self.frames[-1].update(cls=self.cls(), follows=self.log.prev, look=self.look,
                                    other_look=bool(acc and f > 0 and self.frame_look not in (None, self.look)), edit=self.log.pending)
@@ -1259,6 +1355,49 @@ def visited(name):
     return list(dict.fromkeys(out))
 
 
+def layout_parts():
+    """(scene, seed, part, layout) of every sequence that is played under a layout (LAYOUT_SEEDS)."""
+    return [(name, seed, part, layout) for layout, name, seed in LAYOUT_SEEDS for part in range(len(sequences(name, seed)))]
+
+
+def step_key(s, step):
+    """What a step counts as in layout_facts: its kind, a step that the state refuses apart ("temporal (refused)"); the kinds that are
+    refusals themselves and a clone, whose subset only has its temporal() refused, under their own name."""
+    kind = step[0]
+    return kind + (" (refused)" if s.refuses(step) and kind != "clone" and not kind.startswith("refused_") else "")
+
+
+def layout_facts(name, seed):
+    """What playing the seed's sequences under a layout exercises, from the light model alone: sequences and steps; the frames of the
+    sequences' own scenes (a clone's apart: it is settled too, but shows nothing of its parent's state) that are settled (settles)
+    and single, the settled ones by path class; and per step_key how often a step lies between a settled frame and a later frame of
+    its sequence -- the last frame of the steps before it is a settled one, so the step finds plan, tables and buffers live, and a
+    later step renders a frame, which shows what the step left stale.  Every key that occurs is listed, also with 0."""
+    out = dict(sequences=0, steps=0, settled=0, single=0, settled_class=0, settled_general=0, clones=0, between={})
+    own = R.path_class(world(name).base)
+    for q in sequences(name, seed):
+        s, marks = lite_of(name, seed, q["start"]), []
+        for step in q["steps"]:
+            key, n = step_key(s, step), len(s.frames)
+            s.advance(step)
+            marks.append((key, s.frames[n:]))
+        out["sequences"] += 1
+        out["steps"] += len(marks)
+        out["clones"] += sum(key == "clone" for key, _ in marks)
+        for f in s.frames:
+            out["settled" if f["settled"] else "single"] += 1
+            if f["settled"]:
+                out["settled_class" if f.get("cls", own) == R.PATH_CLASS_OPAQUE_DIFFUSE else "settled_general"] += 1
+        frame_at = [i for i, (_, fs) in enumerate(marks) if fs]
+        last = None  # the last frame of the steps before: what it left is what the step finds
+        for i, (key, fs) in enumerate(marks):
+            out["between"].setdefault(key, 0)
+            out["between"][key] += bool(last is not None and last["settled"] and i < frame_at[-1])
+            last = fs[-1] if fs else last
+    out["between"] = dict(sorted(out["between"].items()))
+    return out
+
+
 def warm_wide(name):
     """The model alone over the scene's wide sequences: every window frame, flow and accumulation their checks read is made now (the
     caches are the World's), as World.warm does for the planes of the visited states."""
@@ -1281,9 +1420,12 @@ class Session(Lite):
     """The model of one resident scene.  With rs (a ResidentScene created from world.state(*start)) every step is also made on the device
     and checked; without, the model advances alone and notes what tests/test_session.py asserts on (self.notes)."""
 
-    def __init__(self, w, start=("home", "home"), rs=None, edit=False, post=False, warming=False):
+    def __init__(self, w, start=("home", "home"), rs=None, edit=False, post=False, warming=False, layout=None, tally=None):
         super().__init__(*start, samples=w.base.sample_count, name=w.name if edit else None, post=post)
         self.warming = warming  # played to fill the World's caches only: what is not cached (the depth of field's oracle) is left out
+        # the layout the scene was created under (a key of LAYOUTS, or None): frames that settle are rendered SETTLED_FRAMES times
+        # (on_device); tally (a Counter, optional) takes what they reported, for the figures of tests/test_session_gpu.py
+        self.layout, self.tally = layout, tally
         self.w, self.rs = w, rs  # (w: the World of the scene's own look, which holds what depends on geometry and camera alone)
         self.described_pose = start[0]
         self.planes = self.history = None
@@ -1321,11 +1463,54 @@ class Session(Lite):
         assert onto is not None or not (acc and f > 0), "a frame continues before the sequence's first frame: the header leaves the buffer open"
         want = self.lw.window_planes(self.pose, self.shape, N, f, D, onto)  # (onto the model's planes, whatever look they came from)
         if self.rs:
-            self.rs.render()
-            sc = self.w.base
-            for ch, g, x in zip("RGB", self.rs.readback(), want):
-                differs(np.asarray(g).reshape(sc.height, sc.width), x, f"plane {ch} of the frame at {self.here()} under the window {self.window_next}")
+            self.on_device(self.rs, want, settles(self.window_next, self.pipeline),
+                           f"of the frame at {self.here()} under the window {self.window_next}")
         self.before, self.planes = self.planes, want
+
+    def on_device(self, rs, want, settled, what, tiles=None):
+        """Scene rs (the session's, or a clone) renders the frame whose planes the model has as `want`.  Without a layout, or where
+        rendering it again is not idempotent (settles), once.  Under a layout SETTLED_FRAMES times, each a render / finish / readback
+        compared with the same planes: the first may be watched or redone (a kept plan can be too short for a new window), the
+        others are planned frames of an unchanged scene, which are deterministic and must not be redone; what the last one reports
+        of its ordered rounds is what the layout says (placed).  tiles: how many rs holds (None: the image's)."""
+        sc = self.w.base
+        frames = SETTLED_FRAMES if self.layout and settled else 1
+        for n in range(1, frames + 1):
+            rs.render()
+            redone = frames > 1 and rs.finish()
+            which = f" (frame {n} of {frames} under the layout {self.layout})" if frames > 1 else ""
+            for ch, g, x in zip("RGB", rs.readback(), want):
+                differs(np.asarray(g).reshape(sc.height, sc.width), x, f"plane {ch} {what}{which}")
+            assert n == 1 or not redone, f"the frame {what}{which} was rendered again: its plan was too short, and nothing had changed"
+        if frames > 1:
+            self.placed(rs, what, R.tile_count(sc.width, sc.height) if tiles is None else tiles)
+
+    def placed(self, rs, what, tiles):
+        """After a settled frame's last repeat: (ordered rounds placed directly, scatter launches) of rtHipTestPlaceLog against the
+        trace rounds the frame issued (rtHipTestRoundLog's round count less the logic round that consumes the last answers), by
+        round_goes_direct and issue_round (rt_frame_plan.h, rt_frame.cpp).
+        direct, direct_unsplit: every trace round is ordered and uncut over 256 slices; in the opaque-diffuse class the frame before
+        left a valid stamp of this window for each (a watched frame forgets all stamps and its scatter launches make new ones, a
+        planned one scatters where a stamp does not match and records it), so all are placed and none is scattered; the general class
+        scatters every one.  cut: every trace round is ordered and cut, so none is placed and each is scattered.  groups: round 1 alone
+        is ordered (the later ones hold fewer rays than append_rays), and every tile group scatters it once per sample batch -- the
+        scene has min(3, tiles) groups and one sample per batch (LAYOUTS), so a frame with a trace round reports 3 S launches: the
+        batch count, as the library reports it; several batches never go direct (a stamp of theirs is not valid)."""
+        traced = int(R.lib().rtHipTestRoundLog(rs.handle, None, 0)) - 1
+        log, cls = rs.place_log(), rs.path_class()
+        in_class = cls == R.PATH_CLASS_OPAQUE_DIFFUSE
+        assert traced >= 0, f"the frame {what} reports {traced + 1} rounds"
+        if self.layout in ("direct", "direct_unsplit"):
+            want = (traced, 0) if in_class else (0, traced)
+        elif self.layout == "cut":
+            want = (0, traced)
+        else:
+            want = (0, min(3, tiles) * self.samples * min(traced, 1))
+        if self.tally is not None:
+            self.tally[self.layout, "class" if in_class else "general", "traced" if traced else "untraced",
+                       "direct" if log[0] else "scattered" if log[1] else "neither"] += 1
+        assert log == want, \
+            f"the settled frame {what} under the layout {self.layout}: the place log is {log} with {traced} trace rounds in path class {cls}, expected {want}"
 
     def render_frame(self):
         super().render_frame()
@@ -1740,14 +1925,15 @@ class Session(Lite):
             assert c.sample_window()["next"] == dict(total=S, first=0, divisor=S, accumulate=0, advance=0), c.sample_window()
             self.same_clamp(c, None, "a clone")  # the clamp is per scene and off by default, whatever the parent's (which apply() compares)
             self.same_bound(c, self.shape, "the clone's clip bound")
-            c.render()
-            got = [np.asarray(p).reshape(sc.height, sc.width) for p in c.readback()]
             mine = np.ones((sc.height, sc.width), bool)
             if subset:
                 mine[:R.TILE, :R.TILE] = False  # tile 0 is not the clone's
+            # (the default window on the wavefront pipeline: under a layout the clone's frame is settled like the scene's own)
+            self.on_device(c, [np.where(mine, x, 0).astype(np.uint16) for x in self.lw.planes(self.described_pose, self.shape)],
+                           settles((S, 0, S, 0, 0), R.PIPELINE_WAVEFRONT), "of the clone's frame",
+                           tiles=len(tiles) if subset else None)
+            if subset:
                 refusal(c.temporal, "every tile of the image", "temporal on a tile subset")
-            for ch, g, x in zip("RGB", got, self.lw.planes(self.described_pose, self.shape)):
-                differs(g, np.where(mine, x, 0).astype(np.uint16), f"plane {ch} of the clone's frame")
         finally:
             c.close()
 
@@ -1888,27 +2074,44 @@ def describe(steps):
     return "; ".join(f"{i}: {k}" + ("" if a is None else f"({a})") for i, (k, a) in enumerate(steps))
 
 
-def play(name, seed, part, last=None, report=None):
+def play(name, seed, part, last=None, report=None, layout=None, tally=None):
     """Plays one sequence on the device and stops at the first mismatch: one pass, nothing is tried again.  The scene is always closed
-    (twins and clones close themselves).  report(step number, step, verdict) is called after every step."""
+    (twins and clones close themselves).  report(step number, step, verdict) is called after every step.
+    layout (a key of LAYOUTS): its variables stand in os.environ from before the scene is created -- so the clones and twins made on
+    the way are laid out like it -- until the sequence is over, when the values of before are put back and the library's tuning
+    values are set from them, so the next scene anyone creates is on the defaults again; frames that settle are rendered
+    SETTLED_FRAMES times (Session.on_device), and `tally` (a Counter) takes what their last repeats reported."""
     seq = part_of(name, seed, part)
     steps = seq["steps"] if last is None else seq["steps"][:last + 1]
     w = world(name)
-    rs = R.ResidentScene(w.state(*seq["start"]), 0)
+    under = f" under the layout {layout}" if layout else ""
+    env = LAYOUTS[layout] if layout else {}
+    before = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
     try:
-        s = Session(w, seq["start"], rs, edit=is_edit(name, seed), post=is_post(name, seed))
-        s.same_window("a fresh scene")
-        s.same_clamp(rs, None, "a fresh scene")
-        for i, step in enumerate(steps):
-            try:
-                s.apply(step)
-            except (AssertionError, RuntimeError) as e:
+        rs = R.ResidentScene(w.state(*seq["start"]), 0)
+        try:
+            s = Session(w, seq["start"], rs, edit=is_edit(name, seed), post=is_post(name, seed), layout=layout, tally=tally)
+            s.same_window("a fresh scene")
+            s.same_clamp(rs, None, "a fresh scene")
+            for i, step in enumerate(steps):
+                try:
+                    s.apply(step)
+                except (AssertionError, RuntimeError) as e:
+                    if report:
+                        report(i, step, f"MISMATCH: {e}")
+                    raise AssertionError(f"{name} seed {seed} part {part}{under}, step {i} {step}: {e}\nstarted at {seq['start']}; steps so far: "
+                                         f"{describe(steps[:i + 1])}") from e
                 if report:
-                    report(i, step, f"MISMATCH: {e}")
-                raise AssertionError(f"{name} seed {seed} part {part}, step {i} {step}: {e}\nstarted at {seq['start']}; steps so far: "
-                                     f"{describe(steps[:i + 1])}") from e
-            if report:
-                report(i, step, "ok")
+                    report(i, step, "ok")
+        finally:
+            rs.close()
     finally:
-        rs.close()
+        for k, v in before.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        if env:
+            R.apply_env_tuning()
     return len(steps)

@@ -468,6 +468,55 @@ def test_the_post_seeds_clamp_and_blurs_are_not_vacuous():
     assert all(s == 0.0 for s in off)  # (without a live history the clamp has nothing to pull: the frame itself)
 
 
+# ---- the sequences played under a layout ----------------------------------------------------------------------------------------------
+def test_the_layouts_put_every_operation_between_a_settled_frame_and_a_later_frame():
+    """The 58 sequences that tests/test_session_gpu.py plays once more under a layout (session_cases.LAYOUT_SEEDS), on the light model
+    alone: how many frames settle (are rendered three times, so that launch plan, placement tables and clean control words are live),
+    in which path class, and how often each kind of step stands where it can leave that state stale and have a frame show it."""
+    facts = {(name, seed): SC.layout_facts(name, seed) for name, seed in dict.fromkeys((n, s) for _, n, s in SC.LAYOUT_SEEDS)}
+    for key, f in facts.items():
+        print(f"under a layout, {key}: {f}")
+    assert facts == SC.COUNTS_LAYOUT, "the draw or the model changed: measure again"
+    assert len(SC.layout_parts()) == 58 and set(SC.LAYOUT_SEEDS) <= {(lay, n, s) for lay in SC.LAYOUTS for n in SC.SCENES for s in SC.seeds_of(n)}
+    assert [p[:3] for p in SC.layout_parts()] == [p for _, n, s in SC.LAYOUT_SEEDS for p in SC.all_parts() if p[:2] == (n, s)]
+    for name, seed, part, layout in SC.layout_parts():  # a settled frame is one of the default or of a fixed window: every repeat is the same frame
+        q = SC.part_of(name, seed, part)
+        s = SC.lite_of(name, seed, q["start"])
+        for step in q["steps"]:
+            s.advance(step)
+        for f in s.frames:
+            assert not f["settled"] or (f["kind"] in ("default", "fixed") and not f["continuing"] and not f["window"][4]), f
+    per_layout = {}
+    for layout in SC.LAYOUTS:
+        mine = [facts[n, s] for lay, n, s in SC.LAYOUT_SEEDS if lay == layout]
+        between = collections.Counter()
+        for f in mine:
+            between.update(f["between"])
+        per_layout[layout] = dict({k: sum(f[k] for f in mine) for k in ("sequences", "steps", "settled", "single", "settled_class", "settled_general", "clones")},
+                                  between=dict(between))
+        print(f"layout {layout}: {per_layout[layout]}")
+        uncovered = tuple(k for k in SC.KINDS_ALL if not between.get(k, 0))
+        assert uncovered == SC.LAYOUT_UNCOVERED[layout], f"layout {layout} leaves uncovered: {uncovered}"
+        for k in SC.LAYOUT_UNCOVERED[layout]:
+            assert k in SC.__doc__.split("Layouts.")[1], f"{k}: not named in session_cases' docstring"
+    assert sum(v["sequences"] for v in per_layout.values()) == 58
+    # direct: the class's edit circuit and walk alone hold every kind of their alphabet that is not refused, with 20 settled frames in the class
+    both = collections.Counter()
+    for seed in (21, 110):
+        both.update(facts["class_textured_bumped", seed]["between"])
+    assert all(both[k] >= 1 for k in SC.KINDS_EDIT), [k for k in SC.KINDS_EDIT if not both[k]]
+    assert sum(facts["class_textured_bumped", seed]["settled_class"] for seed in (21, 110)) >= 20
+    assert per_layout["direct"]["settled_general"] >= 20  # (and as many that must scatter every ordered round and stay right)
+    for layout in ("cut", "groups"):
+        for k in ("camera", "shape", "passes", "pipeline", "window"):
+            assert per_layout[layout]["between"][k] >= 1, (layout, k)
+    assert facts["axis_near_axis_mixed", 3]["between"].get("window", 0) == 0 < facts["axis_near_axis_mixed", 106]["between"]["window"]
+    assert per_layout["direct_unsplit"]["settled_class"] >= 4 and per_layout["cut"]["settled_class"] >= 4
+    # the four tiles of the groups layout's scene: three groups, and clones of a tile subset among its steps
+    assert R.tile_count(*SC.SCENES["axis_near_axis_mixed"]["size"]) == 4
+    assert any(k == "clone" and a for s in (3, 106) for q in SC.sequences("axis_near_axis_mixed", s) for k, a in q["steps"])
+
+
 def test_the_model_gives_what_the_clamp_and_blur_tests_compute_from_their_oracles():
     """Played without a device, the model's expected arrays for the hand-written chains of the three features' own GPU tests are what
     those tests compute directly from their oracles: a relight under the clamp (tests/test_temporal_clamp_gpu.py; here on the scene

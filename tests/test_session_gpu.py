@@ -38,7 +38,31 @@ sequences are what they were, and their times move with the machine's host side,
 scene is spent (comparisons of lists and device arrays): in the run of the 1.16 s the slowest of them took 4.31 s (seed 3, part 1;
 the 4.3 s of the first paragraph, whose yardstick of 1.90 s that run did not reproduce), in the run of the 1.33 s 9.8 s (seed 3,
 part 0).  By the yardstick of one run alone seed 3's parts 0, 1, 2 and 9 lie above the rule; they are older than this measurement
-and are left as they are."""
+and are left as they are.
+
+Layouts (test_sequence_under_layout; session_cases.LAYOUTS, LAYOUT_SEEDS): 58 sequences of existing seeds are played once more with
+the scene, its clones and twins created under direct, direct_unsplit, cut or groups, so that launch plans, placement tables and their
+stamps, clean control words, three tile groups and two sample batches are live while the operations run.  Every frame whose repetition
+is idempotent in the model (session_cases.settles), a clone's included, is rendered three times, each a render / finish / readback
+compared with the planes the model has for the step; the second and third must not be rendered again, and after the third
+rtHipTestPlaceLog must report what the layout and the path class promise (session_cases.Session.placed).  Measured on the MI355X,
+over the settled frames of the sequences' own scenes and of their clones, every one with at least one trace round: under direct 43
+frames in the opaque-diffuse class (26 + 17 of clones) placed every trace round directly and scattered none -- all in-class ones, as
+the model says -- and 55 in the general class (29 + 26) scattered every round; under direct_unsplit all 5 (4 + 1) went direct; under
+cut none of 42 (37 general, 5 in the class) went direct and each scattered every round; under groups none of 57 (36 + 21) went direct
+and each reported 3 groups x 2 batches = 6 scatter launches of round 1, which is the batch count as the library reports it.  A failure
+names the layout and which of the three frames differed.
+Sizing of these, in one run of this file with tests/test_temporal_gpu.py whose temporal yardstick was 1.89 s (the camera chain on
+axis_class_sun; 5.67 s allowed): each layout's slowest sequence against the same sequence under default tuning in that run -- groups
+3.26 s (seed 3, part 9; 3.75 s), then 3.25 s (part 0; 4.11 s) and 3.24 s (part 12; 3.43 s); direct 1.50 s (mirror_hall seed 1,
+part 2; 1.75 s) and 1.09 s on class_textured_bumped (seed 21, part 14; 1.15 s); cut 1.16 s (mirror_hall seed 4, part 1; 0.98 s);
+direct_unsplit 0.64 s (class_textured_bumped's walk 110; 0.66 s).  The two extra frames cost little next to the host-side comparisons,
+and a sequence played second finds its twins made.  No sequence of circuit 3 under groups lies above the rule, so none is cut; the
+slowest sequence of that run was the default seed 3, part 1, at 4.32 s.  The module took 216 s with the temporal suite, 67 s of it the
+fixture."""
+import collections
+import os
+
 import pytest
 import torch  # noqa: F401  (before the library loads its HIP runtime: the order bench.py uses)
 
@@ -67,3 +91,17 @@ def need_gpu(hip_lib):
 @pytest.mark.parametrize("name, seed, part", SC.all_parts())
 def test_sequence(name, seed, part):
     assert SC.play(name, seed, part) >= 2
+
+
+TALLY = collections.Counter()  # what the settled frames played so far reported: (layout, class, traced or not, direct / scattered / neither)
+
+
+@pytest.mark.parametrize("name, seed, part, layout", SC.layout_parts())
+def test_sequence_under_layout(name, seed, part, layout):
+    """The sequence once more with the scene, its clones and twins created under the layout: every frame that settles three times,
+    each equal to the model's planes, the second and third not rendered again, the last with the placement the layout promises
+    (session_cases.Session.on_device and placed)."""
+    before, env = collections.Counter(TALLY), {k: os.environ.get(k) for k in SC.LAYOUTS[layout]}
+    assert SC.play(name, seed, part, layout=layout, tally=TALLY) >= 2
+    assert {k: os.environ.get(k) for k in SC.LAYOUTS[layout]} == env, "the layout's variables were left behind"
+    print(f"settled frames of {name} seed {seed} part {part} under {layout}: {dict(TALLY - before)}; so far: {dict(TALLY)}")
