@@ -9,6 +9,7 @@
 #include "rt_launch.h"
 #include "rt_build_shared.h"
 #include "rt_scene_edit.h"
+#include "rt_tile_order.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -589,21 +590,16 @@ int rtHipReadback(rtHipScene *sc, cl_ushort *outR, cl_ushort *outG, cl_ushort *o
     std::vector<uint16_t> host(nt * 3 * RT_TILE_PIXELS);
     HIP_OK(hipMemcpy(host.data(), sc->dev.tileBuf, host.size() * 2, hipMemcpyDeviceToHost));
     cl_ushort *planes[3] = { outR, outG, outB };
-    for (size_t s = 0; s < nt; ++s) {
-        const uint32_t tx = sc->tileIds[s] % sc->tilesX, ty = sc->tileIds[s] / sc->tilesX;
-        for (int c = 0; c < 3; ++c)
-            for (uint32_t ly = 0; ly < RT_TILE; ++ly) {
-                const uint32_t gy = ty * RT_TILE + ly;
-                if (gy >= sc->height) break;
-                const uint16_t *src = host.data() + (s * 3 + c) * RT_TILE_PIXELS + ly * RT_TILE;
-                cl_ushort *dst = planes[c] + (size_t)gy * sc->width + tx * RT_TILE;
-                const uint32_t n = std::min<uint32_t>(RT_TILE, sc->width - tx * RT_TILE);
-                for (uint32_t i = 0; i < n; ++i) {
-                    const uint32_t v = (uint32_t)dst[i] + src[i]; // saturating accumulate (raytrace_opencl.c:729-740)
-                    dst[i] = (cl_ushort)(v > 0xFFFFu ? 0xFFFFu : v);
-                }
+    rt_tile_walk_rows(sc->tileIds.data(), nt, sc->tilesX, sc->width, sc->height, [&](size_t s, uint32_t ly, size_t at, uint32_t n) {
+        for (int c = 0; c < 3; ++c) {
+            const uint16_t *src = host.data() + (s * 3 + c) * RT_TILE_PIXELS + ly * RT_TILE;
+            cl_ushort *dst = planes[c] + at;
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint32_t v = (uint32_t)dst[i] + src[i]; // saturating accumulate (raytrace_opencl.c:729-740)
+                dst[i] = (cl_ushort)(v > 0xFFFFu ? 0xFFFFu : v);
             }
-    }
+        }
+    });
     return 0;
 }
 
@@ -622,21 +618,14 @@ int rtHipReadbackPasses(rtHipScene *sc, cl_ushort *alpha, cl_float *depth, cl_ui
     std::vector<uint32_t> host(nt * RT_PASS_WORDS * RT_TILE_PIXELS);
     HIP_OK(hipMemcpy(host.data(), sc->passBuf, host.size() * 4, hipMemcpyDeviceToHost));
     const uint64_t S = sc->dev.sampleCount;
-    for (size_t s = 0; s < nt; ++s) {
-        const uint32_t tx = sc->tileIds[s] % sc->tilesX, ty = sc->tileIds[s] / sc->tilesX;
-        const uint32_t n = std::min<uint32_t>(RT_TILE, sc->width - tx * RT_TILE);
-        for (uint32_t ly = 0; ly < RT_TILE; ++ly) {
-            const uint32_t gy = ty * RT_TILE + ly;
-            if (gy >= sc->height) break;
-            const uint32_t *src = host.data() + s * RT_PASS_WORDS * RT_TILE_PIXELS + ly * RT_TILE;
-            const size_t at = (size_t)gy * sc->width + tx * RT_TILE;
-            for (uint32_t i = 0; i < n; ++i) {
-                if (alpha) alpha[at + i] = (cl_ushort)((uint64_t)src[RT_PASS_HITS * RT_TILE_PIXELS + i] * 65535u / S);
-                if (depth) memcpy(&depth[at + i], &src[RT_PASS_DEPTH * RT_TILE_PIXELS + i], 4);
-                if (triangle) triangle[at + i] = src[RT_PASS_TRIANGLE * RT_TILE_PIXELS + i];
-            }
+    rt_tile_walk_rows(sc->tileIds.data(), nt, sc->tilesX, sc->width, sc->height, [&](size_t s, uint32_t ly, size_t at, uint32_t n) {
+        const uint32_t *src = host.data() + s * RT_PASS_WORDS * RT_TILE_PIXELS + ly * RT_TILE;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (alpha) alpha[at + i] = (cl_ushort)((uint64_t)src[RT_PASS_HITS * RT_TILE_PIXELS + i] * 65535u / S);
+            if (depth) memcpy(&depth[at + i], &src[RT_PASS_DEPTH * RT_TILE_PIXELS + i], 4);
+            if (triangle) triangle[at + i] = src[RT_PASS_TRIANGLE * RT_TILE_PIXELS + i];
         }
-    }
+    });
     return 0;
 }
 
@@ -653,21 +642,14 @@ int rtHipReadbackSurfacePasses(rtHipScene *sc, cl_float *normal, cl_float *albed
     std::vector<float> host(nt * RT_SURF_WORDS * RT_TILE_PIXELS);
     HIP_OK(hipMemcpy(host.data(), sc->surfBuf, host.size() * 4, hipMemcpyDeviceToHost));
     const float S = (float)sc->dev.sampleCount; // the buffer holds sums in sample order; the means are taken here, in fp32
-    for (size_t s = 0; s < nt; ++s) {
-        const uint32_t tx = sc->tileIds[s] % sc->tilesX, ty = sc->tileIds[s] / sc->tilesX;
-        const uint32_t n = std::min<uint32_t>(RT_TILE, sc->width - tx * RT_TILE);
-        for (uint32_t ly = 0; ly < RT_TILE; ++ly) {
-            const uint32_t gy = ty * RT_TILE + ly;
-            if (gy >= sc->height) break;
-            const float *src = host.data() + s * RT_SURF_WORDS * RT_TILE_PIXELS + ly * RT_TILE;
-            const size_t at = (size_t)gy * sc->width + tx * RT_TILE;
-            for (uint32_t i = 0; i < n; ++i)
-                for (int c = 0; c < 3; ++c) {
-                    if (normal) normal[3 * (at + i) + c] = src[(RT_SURF_NORMAL + c) * RT_TILE_PIXELS + i] / S;
-                    if (albedo) albedo[3 * (at + i) + c] = src[(RT_SURF_ALBEDO + c) * RT_TILE_PIXELS + i] / S;
-                }
-        }
-    }
+    rt_tile_walk_rows(sc->tileIds.data(), nt, sc->tilesX, sc->width, sc->height, [&](size_t s, uint32_t ly, size_t at, uint32_t n) {
+        const float *src = host.data() + s * RT_SURF_WORDS * RT_TILE_PIXELS + ly * RT_TILE;
+        for (uint32_t i = 0; i < n; ++i)
+            for (int c = 0; c < 3; ++c) {
+                if (normal) normal[3 * (at + i) + c] = src[(RT_SURF_NORMAL + c) * RT_TILE_PIXELS + i] / S;
+                if (albedo) albedo[3 * (at + i) + c] = src[(RT_SURF_ALBEDO + c) * RT_TILE_PIXELS + i] / S;
+            }
+    });
     return 0;
 }
 
@@ -719,7 +701,7 @@ int rtHipSceneIntersect(rtHipScene *sc, const rtHipRay *rays, const cl_uint *exc
     return 0;
 }
 
-// ---- ambient occlusion (include/raytrace_hip.h, "AMBIENT OCCLUSION"; kernels in rt_wavefront.hip, rt_ao_*) ------------------------
+// ---- ambient occlusion (include/raytrace_hip.h, "AMBIENT OCCLUSION"; kernels in rt_scene_passes.hip, rt_ao_*) ------------------------
 void rtHipAoDefaults(rtHipAoParams *p)
 {
     if (!p) return;
@@ -786,15 +768,11 @@ int rtHipSceneAmbientOcclusion(rtHipScene *sc, const rtHipAoParams *p, cl_float 
     std::vector<float> host(n);
     HIP_OK(hipMemcpyAsync(host.data(), sc->aoBuf, n * 4, hipMemcpyDeviceToHost, sc->stream));
     HIP_OK(hipStreamSynchronize(sc->stream));
-    for (size_t lp = 0; lp < n; ++lp) {
-        const uint32_t tile = sc->tileIds[lp >> 14], q = (uint32_t)(lp & (RT_TILE_PIXELS - 1)), blk = q >> 6, in = q & 63u;
-        const uint32_t gx = (tile % sc->tilesX) * RT_TILE + (blk & 15u) * 8u + (in & 7u), gy = (tile / sc->tilesX) * RT_TILE + (blk >> 4) * 8u + (in >> 3);
-        if (gx < sc->width && gy < sc->height) out[(size_t)gy * sc->width + gx] = host[lp];
-    }
+    rt_tile_walk_block_pixels(sc->tileIds.data(), sc->tileIds.size(), sc->tilesX, sc->width, sc->height, [&](size_t lp, size_t at) { out[at] = host[lp]; });
     return 0;
 }
 
-// ---- motion vectors (include/raytrace_hip.h, "MOTION VECTORS"; kernels in rt_wavefront.hip, rt_motion_*) ---------------------------
+// ---- motion vectors (include/raytrace_hip.h, "MOTION VECTORS"; kernels in rt_scene_passes.hip, rt_motion_*) ---------------------------
 int rtHipSceneMotionMark(rtHipScene *sc)
 {
     if (!sc) return fail("rtHipSceneMotionMark: null scene");
@@ -869,20 +847,16 @@ int rtHipSceneMotion(rtHipScene *sc, cl_float *motion, cl_float *t, cl_float *pr
     if (prevT) HIP_OK(hipMemcpyAsync(hPrev, dPrev, n * 4, hipMemcpyDeviceToHost, sc->stream));
     if (triangle) HIP_OK(hipMemcpyAsync(hTri, dTri, n * 4, hipMemcpyDeviceToHost, sc->stream));
     HIP_OK(hipStreamSynchronize(sc->stream));
-    for (size_t lp = 0; lp < n; ++lp) {
-        const uint32_t tile = sc->tileIds[lp >> 14], q = (uint32_t)(lp & (RT_TILE_PIXELS - 1)), blk = q >> 6, in = q & 63u;
-        const uint32_t gx = (tile % sc->tilesX) * RT_TILE + (blk & 15u) * 8u + (in & 7u), gy = (tile / sc->tilesX) * RT_TILE + (blk >> 4) * 8u + (in >> 3);
-        if (gx >= sc->width || gy >= sc->height) continue;
-        const size_t at = (size_t)gy * sc->width + gx;
+    rt_tile_walk_block_pixels(sc->tileIds.data(), sc->tileIds.size(), sc->tilesX, sc->width, sc->height, [&](size_t lp, size_t at) {
         if (motion) memcpy(motion + 2 * at, hMotion + 2 * lp, 8);
         if (t) memcpy(t + at, hT + lp, 4);
         if (prevT) memcpy(prevT + at, hPrev + lp, 4);
         if (triangle) triangle[at] = hTri[lp];
-    }
+    });
     return 0;
 }
 
-// ---- ambient occlusion bake (include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE"; kernels in rt_wavefront.hip, rt_bake_*) -------------
+// ---- ambient occlusion bake (include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE"; kernels in rt_scene_passes.hip, rt_bake_*) -------------
 void rtHipBakeDefaults(rtHipBakeParams *p)
 {
     if (!p) return;

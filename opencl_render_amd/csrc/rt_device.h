@@ -268,7 +268,7 @@ struct RtShadeList {
     uint32_t *count; // [3][RT_WF_SHARDS]
 };
 
-// ---- ambient occlusion (rt_wavefront.hip, rt_ao_*; definition in include/raytrace_hip.h, "AMBIENT OCCLUSION") -----------------------
+// ---- ambient occlusion (rt_scene_passes.hip, rt_ao_*; definition in include/raytrace_hip.h, "AMBIENT OCCLUSION") -----------------------
 // Pixel samples are numbered g = lp*Sp + j over the scene's pixels in AO order: lp = slot*128*128 + q, q walking its tile in 8x8 blocks,
 // 16 blocks per block row (a wave of 64 samples at Sp = 1 is one 8x8 block of the screen).  One launch pair per chunk of `count` samples
 // from g = base: the primary kernel adds R to counter[lp] for a miss or a normal of length 0 and appends every other sample to the hit
@@ -284,7 +284,7 @@ struct RtAoArgs {
     uint32_t *counter; // [tileCount * 128*128], zeroed before the first chunk
 };
 
-// ---- ambient occlusion bake (rt_wavefront.hip, rt_bake_*; definition in include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE") -----------
+// ---- ambient occlusion bake (rt_scene_passes.hip, rt_bake_*; definition in include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE") -----------
 // Texels t = y*W + x.  The rasterise kernels atomicMin the selected triangles into win[t] (all ones before).  Then per chunk of `count`
 // texels from t = base: the points kernel settles uncovered and zero-normal texels in counter[t] and appends the others to the hit list,
 // rec[*hits++] = {P.xyz, tri} {n^.xyz, t - base}; the AO kernel traces R rays per listed texel and adds its open rays into counter[t].
@@ -303,7 +303,7 @@ struct RtBakeArgs {
     uint32_t *hits;     // its length, zeroed before the chunk's points launch
 };
 
-// ---- motion vectors (rt_wavefront.hip, rt_motion_*; definition in include/raytrace_hip.h, "MOTION VECTORS") -------------------------
+// ---- motion vectors (rt_scene_passes.hip, rt_motion_*; definition in include/raytrace_hip.h, "MOTION VECTORS") -------------------------
 // The reference record of triangle i is three float4: {a.xyz, ab.x} {ab.yz, ac.xy} {ac.z, 0, 0, 0}, the first 9 floats of its triRec row at
 // the mark (48 B per triangle).  The motion kernel runs one lane per pixel of the scene's tiles in AO order (lp, see RtAoArgs) and stores
 // the wanted outputs (a null array is skipped) at the pixel's row-major index (rowMajor) or at lp (the host entry point's staging).
@@ -317,7 +317,7 @@ struct RtMotionArgs {
     uint32_t rowMajor, fastQuotient;
 };
 
-// ---- mattes (rt_wavefront.hip, rt_matte_*; definition in include/raytrace_hip.h, "MATTES") -------------------------------------------
+// ---- mattes (rt_scene_passes.hip, rt_matte_*; definition in include/raytrace_hip.h, "MATTES") -------------------------------------------
 // The per-pixel state between the chunks of a call, laid out like the pass buffer: state[slot][word][128*128] u32 with `words` =
 // M + 2K + 1 words per pixel -- M selected counts, K layer ids, K layer counts (0 = the slot is free; used slots are a prefix), rest.
 // The count kernel walks samples sampleFirst+1+j, j = 0..samples-1, of a sequence of seedStride per pixel; the chunk with `first` set

@@ -68,7 +68,7 @@ int log_round_visits(rtHipScene *sc, Group &G, uint32_t r, const RtRoundMode &mo
     HIP_OK(hipMemcpy(ent.data(), W.ent[r & 1u], sizeof(uint4) * ent.size(), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(key.data(), W.hitKey[r & 1u], sizeof(unsigned long long) * key.size(), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(pathOf.data(), W.pathOf[r & 1u], sizeof(uint2) * pathOf.size(), hipMemcpyDeviceToHost));
-    auto cell_of = [&](const float p[3]) { // (GetBoxAddress, as rt_wavefront.hip's cell_of)
+    auto cell_of = [&](const float p[3]) { // (GetBoxAddress, as rt_wf_shared.h's cell_of)
         uint32_t c[3] = { 0, 0, 0 };
         for (int w = 0; w < 3; ++w)
             for (int div = RT_GRID_DIV / 2; div >= 1; div /= 2)

@@ -42,14 +42,10 @@ hipError_t rtc_launch_fill(const RtCamMoveArgs *args, hipStream_t stream);
 hipError_t rte_launch_check_ids(uint32_t T, uint32_t M, const int *ids, const float *triShade, uint32_t *err, hipStream_t stream);
 hipError_t rte_launch_store_ids(uint32_t T, const int *ids, float *triShade, hipStream_t stream);
 
-// ---- rt_wavefront.hip
-hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
-                            uint32_t fastQuotient, hipStream_t stream);
+// ---- rt_wavefront.hip (the frame's kernels)
 hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefront *wf, hipStream_t stream);
 hipError_t rtw_launch_primary_passes(const RtDevScene *scene, const RtWavefront *wf, uint32_t *passBuf, hipStream_t stream);
 hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const RtWavefront *wf, float *surfBuf, hipStream_t stream);
-hipError_t rtw_launch_matte_count(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream);
-hipError_t rtw_launch_matte_finish(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream);
 hipError_t rtw_launch_logic(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtRoundMode *next, hipStream_t stream);
 hipError_t rtw_launch_answer(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, uint32_t slicesIn, const RtShadeList *list,
                              uint32_t shadeFollows, hipStream_t stream);
@@ -60,6 +56,12 @@ hipError_t rtw_launch_place_skew(const RtWavefront *wf, uint32_t round, hipStrea
 hipError_t rtw_launch_trace(const RtDevScene *scene, const RtWavefront *wf, uint32_t round, uint32_t blocks, const RtRoundMode *mode, hipStream_t stream);
 hipError_t rtw_launch_status(const RtWavefront *wf, uint32_t round, uint32_t *shadeCount, hipStream_t stream);
 hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefront *wf, int first, hipStream_t stream);
+
+// ---- rt_scene_passes.hip (what is traced against a resident scene outside the frame)
+hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
+                            uint32_t fastQuotient, hipStream_t stream);
+hipError_t rtw_launch_matte_count(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream);
+hipError_t rtw_launch_matte_finish(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream);
 hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream);
 hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
                                 hipStream_t stream);

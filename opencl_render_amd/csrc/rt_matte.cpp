@@ -1,8 +1,9 @@
 // rt_matte.cpp -- the mattes of libraytrace_hip.so (include/raytrace_hip.h, "MATTES"): the parameter check and defaults, the scene's group
 // table, the device and host entry points with the scene-owned state between a call's launches, and the last call's device times.  The
-// kernels are in rt_wavefront.hip (rt_matte_*), where the frame's camera scan is; the scene and what else the host side shares, in rt_host.h.
+// kernels are in rt_scene_passes.hip (rt_matte_*); the scene and what else the host side shares, in rt_host.h.
 #include "rt_host.h"
 #include "rt_launch.h"
+#include "rt_tile_order.h"
 
 using namespace rthost;
 
@@ -140,24 +141,16 @@ int rtHipSceneMattes(rtHipScene *sc, const rtHipMatteParams *p, cl_float *select
     if (!host.empty()) HIP_OK(hipMemcpyAsync(host.data(), sc->matte.state, host.size() * 4, hipMemcpyDeviceToHost, sc->stream));
     HIP_OK(hipStreamSynchronize(sc->stream));
     const size_t plane = (size_t)sc->width * sc->height;
-    // word w of the state is plane `k` of the caller's array `dst` (32-bit words either way)
-    auto rows = [&](size_t s, uint32_t w, void *dst, uint32_t k) {
-        const uint32_t tx = sc->tileIds[s] % sc->tilesX, ty = sc->tileIds[s] / sc->tilesX;
-        if (tx * RT_TILE >= sc->width) return;
-        const uint32_t n = std::min<uint32_t>(RT_TILE, sc->width - tx * RT_TILE);
-        for (uint32_t ly = 0; ly < RT_TILE; ++ly) {
-            const uint32_t gy = ty * RT_TILE + ly;
-            if (gy >= sc->height) break;
-            memcpy((uint32_t *)dst + k * plane + (size_t)gy * sc->width + tx * RT_TILE,
-                   host.data() + (s * words + w) * RT_TILE_PIXELS + (size_t)ly * RT_TILE, (size_t)n * 4);
-        }
-    };
-    for (size_t s = 0; s < nt; ++s) {
-        for (uint32_t m = 0; select && m < M; ++m) rows(s, m, select, m);
-        for (uint32_t k = 0; layerId && k < K; ++k) rows(s, M + k, layerId, k);
-        for (uint32_t k = 0; layerCoverage && k < K; ++k) rows(s, M + K + k, layerCoverage, k);
-        if (rest) rows(s, M + 2u * K, rest, 0);
-    }
+    rt_tile_walk_rows(sc->tileIds.data(), nt, sc->tilesX, sc->width, sc->height, [&](size_t s, uint32_t ly, size_t at, uint32_t n) {
+        // word w of the state is plane `k` of the caller's array `dst` (32-bit words either way)
+        auto row = [&](uint32_t w, void *dst, uint32_t k) {
+            memcpy((uint32_t *)dst + k * plane + at, host.data() + (s * words + w) * RT_TILE_PIXELS + (size_t)ly * RT_TILE, (size_t)n * 4);
+        };
+        for (uint32_t m = 0; select && m < M; ++m) row(m, select, m);
+        for (uint32_t k = 0; layerId && k < K; ++k) row(M + k, layerId, k);
+        for (uint32_t k = 0; layerCoverage && k < K; ++k) row(M + K + k, layerCoverage, k);
+        if (rest) row(M + 2u * K, rest, 0);
+    });
     return 0;
 }
 

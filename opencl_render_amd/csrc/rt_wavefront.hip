@@ -19,184 +19,20 @@
 //
 // Per path everything happens in the reference's order (RNG draws, ring FIFO, light loop), and paths never interact,
 // so the planes are bit-identical to the single-launch kernel (rt_kernels.hip) and to the oracle.
+//
+// This file holds the kernels a frame launches and their launch wrappers, nothing else.  The helpers it shares with the passes traced
+// against a resident scene outside the frame (rt_scene_passes.hip: mattes, ray queries, ambient occlusion, motion vectors, the bake) are
+// in rt_wf_shared.h, the trace entries among them.
 #include "rt_devfuncs.h"
 #include "rt_launch.h"
 #include "rt_path_state.h"
 #include "rt_ray_clip.h"
+#include "rt_wf_shared.h"
 
 namespace {
 
 enum { WS_RAY = 0, WS_SHADOW = 1 };
 static_assert(RT_PATH_RING_SLOTS == RT_RING, "rt_path_state.h addresses the ring allocation");
-
-__device__ __forceinline__ float4 pack4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
-__device__ __forceinline__ V3 xyz(float4 v) { return mk(v.x, v.y, v.z); }
-
-// A frame with ONE sample per pixel needs no ordered accumulate (raytrace_opencl.c:726-741 adds to zeroed planes once): the
-// kernel that finishes a pixel writes its three u16 values itself, wf_accum_kernel is not launched.  (S.directStore; a one-sample frame
-// that continues a sample window's sequence from the tile buffer goes through sampleOut and wf_accum_kernel like any other.)
-__device__ __forceinline__ void store_single_sample(const RtDevScene &S, uint32_t localPixel, V3 c)
-{
-    const uint32_t slot = localPixel / RT_TILE_PIXELS, inTile = localPixel % RT_TILE_PIXELS;
-    uint16_t *planes = S.tileBuf + (size_t)slot * 3 * RT_TILE_PIXELS + inTile;
-    uint32_t samples = S.sampleDivisor; // :728 (the window's divisor; 1 by default here).  Opaque, so that the quotient is made where it is used: hoisted to the top of the
-    asm volatile("" : "+s"(samples)); // logic kernel it lived in a vector register across the state machine and was spilled
-    const float scale = (float)(0xFFFF) / (float)samples;
-    planes[0] = (uint16_t)sat_add_u16(0, c.x, scale);
-    planes[RT_TILE_PIXELS] = (uint16_t)sat_add_u16(0, c.y, scale);
-    planes[2 * RT_TILE_PIXELS] = (uint16_t)sat_add_u16(0, c.z, scale);
-}
-
-// Wave-aggregated queue append: one atomic per wave for all lanes that `want` a slot.  Must be reached by the lanes
-// together (it ballots over the lanes that execute it).
-__device__ __forceinline__ uint32_t wave_append(uint32_t *counter, bool want)
-{
-    const unsigned long long mask = __ballot(want);
-    if (mask == 0) return 0;
-    const uint32_t lane = __lane_id();
-    const int leader = __ffsll((long long)mask) - 1;
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(mask));
-    base = __shfl(base, leader, 64);
-    return base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
-// Two appends in one round trip: lanes 0 and 1 carry the two atomics of the wave in the same instruction.
-__device__ __forceinline__ void wave_append2(uint32_t *counterA, bool wantA, uint32_t *counterB, bool wantB, uint32_t &posA, uint32_t &posB)
-{
-    const unsigned long long maskA = __ballot(wantA), maskB = __ballot(wantB);
-    const uint32_t lane = __lane_id();
-    uint32_t base = 0;
-    const uint32_t n = (lane == 0u) ? (uint32_t)__popcll(maskA) : (uint32_t)__popcll(maskB);
-    if (lane < 2u && n != 0u) base = atomicAdd(lane == 0u ? counterA : counterB, n);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    posA = (uint32_t)__shfl((int)base, 0, 64) + (uint32_t)__popcll(maskA & below);
-    posB = (uint32_t)__shfl((int)base, 1, 64) + (uint32_t)__popcll(maskB & below);
-}
-
-// Triangle test on a per-triangle record that is already in registers (rt_device.h: a | ab | ac | n | abab abac acac inv),
-// branch-free like pair_test_flat below: same operations and operands as tri_test for every lane whose plane distance is in
-// range, the others discard the second half.
-__device__ __forceinline__ bool tri_rec_test_flat(const float4 r0, const float4 r1, const float4 r2, const float4 r3, V3 o, V3 d, float tmin,
-                                                  float tmax, float &t, float &l1, float &l2)
-{
-    const V3 a = mk(r0.x, r0.y, r0.z), ab = mk(r0.w, r1.x, r1.y), ac = mk(r1.z, r1.w, r2.x), n = mk(r2.y, r2.z, r2.w);
-    const V3 ao = sub3(o, a);
-    t = -dot3(n, ao) / dot3(n, d);
-    const V3 ap = sub3(along(o, t, d), a);
-    const float ap_ab = dot3(ap, ab);
-    const float ap_ac = dot3(ap, ac);
-    l1 = (r3.y * ap_ac - r3.z * ap_ab) * r3.w;
-    l2 = (r3.y * ap_ab - r3.x * ap_ac) * r3.w;
-    return (tmin < t) & (t < tmax) & (0 <= l1) & (0 <= l2) & (l1 + l2 <= 1.f);
-}
-
-// Nearest hit among the pixel's candidate list (raytrace_opencl.c:514-528): running maximum, ties keep the earliest.
-// Two candidates per step: their list entries were requested a step ahead, their records are requested together, so a
-// pixel with one or two candidates (the common case) costs three dependent round trips: range, list, records.
-__device__ __forceinline__ uint32_t camera_scan(const RtDevScene &S, uint32_t localPixel, V3 o, V3 d, float tmin, float tmax,
-                                                uint32_t excluded, float &hit_t, float &hit_l1, float &hit_l2)
-{
-    uint32_t hit_tri = RT_NONE;
-    hit_t = tmax;
-    const uint32_t first = S.camStart[localPixel], last = S.camEnd[localPixel];
-    const float4 *recs = reinterpret_cast<const float4 *>(S.triRec);
-    uint32_t t0 = (first < last) ? S.camList[first] : RT_NONE;
-    uint32_t t1 = (first + 1 < last) ? S.camList[first + 1] : RT_NONE;
-    for (uint32_t i = first; i < last; i += 2) {
-        const bool two = i + 1 < last;
-        const float4 *ra = recs + 4 * (size_t)t0, *rb = recs + 4 * (size_t)(two ? t1 : t0);
-        const float4 a0 = ra[0], a1 = ra[1], a2 = ra[2], a3 = ra[3];
-        const float4 b0 = rb[0], b1 = rb[1], b2 = rb[2], b3 = rb[3];
-        const uint32_t n0 = (i + 2 < last) ? S.camList[i + 2] : RT_NONE;
-        const uint32_t n1 = (i + 3 < last) ? S.camList[i + 3] : RT_NONE;
-        float t, l1, l2;
-        if (tri_rec_test_flat(a0, a1, a2, a3, o, d, tmin, hit_t, t, l1, l2) & (excluded != t0)) {
-            hit_t = t; hit_tri = t0; hit_l1 = l1; hit_l2 = l2;
-        }
-        if (tri_rec_test_flat(b0, b1, b2, b3, o, d, tmin, hit_t, t, l1, l2) & (excluded != t1) & two) {
-            hit_t = t; hit_tri = t1; hit_l1 = l1; hit_l2 = l2;
-        }
-        t0 = n0; t1 = n1;
-    }
-    return hit_tri;
-}
-
-// The same scan without the pipelining, for the logic kernel's rare camera-type continuation rays (:707-722), where
-// registers matter more than round trips.
-__device__ __forceinline__ uint32_t camera_scan_compact(const RtDevScene &S, uint32_t localPixel, V3 o, V3 d, float tmin, float tmax,
-                                                     uint32_t excluded, float &hit_t, float &hit_l1, float &hit_l2)
-{
-    uint32_t hit_tri = RT_NONE;
-    hit_t = tmax;
-    const uint32_t first = S.camStart[localPixel], last = S.camEnd[localPixel];
-    for (uint32_t i = first; i < last; ++i) {
-        const uint32_t tri = S.camList[i];
-        if (excluded != tri) {
-            float t, l1, l2;
-            if (tri_test(S.triRec, tri, o, d, tmin, hit_t, t, l1, l2)) {
-                hit_t = t; hit_tri = tri; hit_l1 = l1; hit_l2 = l2;
-            }
-        }
-    }
-    return hit_tri;
-}
-
-// Triangle test against a (cell, triangle) pair record (rt_device.h: {a,id}{n,-}{ab,abab}{ac,acac}), the arithmetic of
-// tri_test / the reference (raytrace_opencl.c:124-172).
-// The record is already in registers and the test is BRANCH-FREE: every lane computes both halves, and whether the
-// plane distance was in range only enters the final predicate.  Lanes for which the reference would not have computed the
-// second half (raytrace_opencl.c:143) discard it; for the others every operation and operand is the same, so t, l1, l2
-// are bit-identical.  With no branch between the four 16-byte loads and their uses the compiler issues them together
-// (one round trip per candidate instead of three dependent ones).
-__device__ __forceinline__ bool pair_test_flat(const float4 r0, const float4 r1, const float4 r2, const float4 r3, V3 o, V3 d, float tmin,
-                                               float tmax, uint32_t excluded, float &t, float &l1, float &l2)
-{
-    const uint32_t tri = __float_as_uint(r0.w);
-    const V3 a = mk(r0.x, r0.y, r0.z), n = mk(r1.x, r1.y, r1.z);
-    const V3 ao = sub3(o, a);
-    t = -dot3(n, ao) / dot3(n, d);
-    const V3 ab = mk(r2.x, r2.y, r2.z), ac = mk(r3.x, r3.y, r3.z);
-    // The record's two spare words carry dot(ab,ac) and 1/(abac^2 - abab*acac) as rt_prepare_triangles worked them out (:147-149, the same
-    // correctly rounded division); the two squared lengths are worked out here from the same operands.  (The other way round -- lengths
-    // stored, the quotient taken here -- was a second full division per candidate: ~13 issue slots against 10 plain ones.)
-    const float abab = dot3(ab, ab), abac = r2.w, acac = dot3(ac, ac);
-    const float inv = r3.w;
-    const V3 ap = sub3(along(o, t, d), a);
-    const float ap_ab = dot3(ap, ab);
-    const float ap_ac = dot3(ap, ac);
-    l1 = (abac * ap_ac - acac * ap_ab) * inv;
-    l2 = (abac * ap_ab - abab * ap_ac) * inv;
-    return (tri != excluded) & (tmin < t) & (t < tmax) & (0 <= l1) & (0 <= l2) & (l1 + l2 <= 1.f);
-}
-
-// The answer of a traced ray from its hitKey: the winning (cell, triangle) pair is evaluated once more with the ray's own
-// limits, which reproduces t, l1, l2 bit for bit (the running maximum of :366-379 only ever rejected other candidates).
-__device__ __forceinline__ uint32_t resolve_hit(const RtDevScene &S, unsigned long long key, V3 o, V3 d, float tmin, float tmax,
-                                                uint32_t excluded, float &t, float &l1, float &l2)
-{
-    if (key == ~0ull) return RT_NONE;
-    const float4 *rec = reinterpret_cast<const float4 *>(S.pairRec) + 4 * (size_t)(uint32_t)key;
-    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-    pair_test_flat(r0, r1, r2, r3, o, d, tmin, tmax, excluded, t, l1, l2);
-    return __float_as_uint(r0.w);
-}
-
-// Order of the hits of one ray inside a test phase: earlier recorded cell, then smaller t, then earlier candidate.
-__device__ __forceinline__ unsigned long long hit_key(uint32_t cellOrder, float t, uint32_t pair)
-{
-    return ((unsigned long long)cellOrder << 60) | ((unsigned long long)__float_as_uint(t) << 29) | (unsigned long long)pair;
-}
-
-#if defined(RT_DIAG_STAMPS) || defined(RT_DIAG_LOGIC)
-// Diagnostic build only (never shipped, outputs untouched): shader-clock stamps, summed per wave into S.stats.
-__device__ __forceinline__ unsigned long long diag_stamp()
-{
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-#endif
 
 } // namespace
 
@@ -332,306 +168,6 @@ __global__ __launch_bounds__(256) void wf_surface_passes_kernel(const RtDevScene
     }
 #pragma unroll
     for (int k = 0; k < RT_SURF_WORDS; ++k) sums[k * RT_TILE_PIXELS] = acc[k];
-}
-
-// ---- mattes: id coverage over a pixel's samples (rtHipSceneMattes*; include/raytrace_hip.h, "MATTES"; rt_device.h, RtMatteArgs) -------
-// The mapping of wf_surface_passes_kernel (ONE thread per pixel, a wave an 8x8 quadrant whose lanes scan overlapping camera lists), and
-// its way of deriving each sample's primary hit again; what is summed is an indicator.  The M selected counts, the K layer slots and
-// rest stay in registers across the chunk's samples: every loop below runs to a compile-time bound and indexes its array with the loop
-// variable, so the arrays are registers, and the bounds that are the call's (M, K) and the id's kind are uniform kernel arguments.
-// Chunks of one call follow one another on one stream: the table is built in sample order without atomics.
-__global__ __launch_bounds__(256) void rt_matte_count_kernel(const RtDevScene S, const RtMatteArgs A)
-{
-    const uint32_t slot = blockIdx.x >> 6, patch = blockIdx.x & 63;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t lx = (patch & 7) * RT_PATCH + (wave & 1) * 8 + (lane & 7);
-    const uint32_t ly = (patch >> 3) * RT_PATCH + (wave >> 1) * 8 + (lane >> 3);
-    const uint32_t tile = S.tileIds[slot];
-    const uint32_t gx = (tile % S.tilesX) * RT_TILE + lx;
-    const uint32_t gy = (tile / S.tilesX) * RT_TILE + ly;
-    if (gx >= S.width || gy >= S.height) return;
-
-    const uint32_t localPixel = slot * RT_TILE_PIXELS + ly * RT_TILE + lx;
-    uint32_t *state = A.state + (size_t)slot * A.words * RT_TILE_PIXELS + ly * RT_TILE + lx;
-    const uint32_t M = A.selectCount, K = A.layers;
-    uint32_t sel[RT_MATTE_MAX_SELECT], id[RT_MATTE_MAX_LAYERS], cnt[RT_MATTE_MAX_LAYERS], rest = 0u;
-#pragma unroll
-    for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m) sel[m] = 0u;
-#pragma unroll
-    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k) { id[k] = RT_NONE; cnt[k] = 0u; }
-    if (!A.first) {
-#pragma unroll
-        for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m)
-            if ((uint32_t)m < M) sel[m] = state[(size_t)m * RT_TILE_PIXELS];
-#pragma unroll
-        for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k)
-            if ((uint32_t)k < K) {
-                id[k] = state[(size_t)(M + k) * RT_TILE_PIXELS];
-                cnt[k] = state[(size_t)(M + K + k) * RT_TILE_PIXELS];
-            }
-        rest = state[(size_t)(M + 2u * K) * RT_TILE_PIXELS];
-    }
-    const uint32_t pixel = gy * S.width + gx;
-    const V3 eye = ld3(S.eye), lr = ld3(S.lr), tb = ld3(S.tb), topLeft = ld3(S.topLeft);
-    for (uint32_t j = 0; j < A.samples; ++j) {
-        uint64_t rng = (uint64_t)pixel * (uint64_t)A.seedStride + ((uint64_t)A.sampleFirst + j + 1u); // :481
-        V3 dir = topLeft;
-        float k = (float)gx + rand01(rng); // LR jitter first, then TB (:496-503)
-        dir.x += lr.x * k; dir.y += lr.y * k; dir.z += lr.z * k;
-        k = (float)gy + rand01(rng);
-        dir.x += tb.x * k; dir.y += tb.y * k; dir.z += tb.z * k;
-        float hit_t = 0.f, hit_l1 = 0.f, hit_l2 = 0.f;
-        const uint32_t tri = camera_scan(S, localPixel, eye, dir, 0.f, RT_INF, RT_NONE, hit_t, hit_l1, hit_l2);
-        uint32_t g = tri;
-        if (tri != RT_NONE) {
-            if (A.kind == RT_MATTE_MATERIAL) {
-                const int m = __float_as_int(S.triShade[RT_TRI_SHADE_WORDS * (size_t)tri + 21]);
-                g = m < 0 ? RT_NONE : (uint32_t)m;
-            } else if (A.kind == RT_MATTE_GROUP) g = A.groups[tri];
-        }
-        if (g == RT_NONE) continue;
-#pragma unroll
-        for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m) sel[m] += (g == A.select[m]) ? 1u : 0u; // (entries from M on are NONE)
-        // find or insert: the used slots are a prefix, so whether g was found is settled before the first free slot is reached
-        bool settled = false;
-#pragma unroll
-        for (int s = 0; s < RT_MATTE_MAX_LAYERS; ++s) {
-            const bool open = (uint32_t)s < K && !settled;
-            const bool used = cnt[s] != 0u;
-            const bool match = open && used && id[s] == g, take = open && !used;
-            id[s] = take ? g : id[s];
-            cnt[s] += (match || take) ? 1u : 0u;
-            settled = settled || match || take;
-        }
-        rest += settled ? 0u : 1u;
-    }
-#pragma unroll
-    for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m)
-        if ((uint32_t)m < M) state[(size_t)m * RT_TILE_PIXELS] = sel[m];
-#pragma unroll
-    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k)
-        if ((uint32_t)k < K) {
-            state[(size_t)(M + k) * RT_TILE_PIXELS] = id[k];
-            state[(size_t)(M + K + k) * RT_TILE_PIXELS] = cnt[k];
-        }
-    state[(size_t)(M + 2u * K) * RT_TILE_PIXELS] = rest;
-}
-
-// One compare-exchange of the finish kernel's network.  A slot's key is ~count << 32 | id: ascending keys are counts descending, equal
-// counts by id ascending, and a free slot (count 0, id NONE) is the largest key there is.
-__device__ __forceinline__ void matte_exchange(unsigned long long &a, unsigned long long &b)
-{
-    const unsigned long long lo = a < b ? a : b, hi = a < b ? b : a;
-    a = lo; b = hi;
-}
-
-// One thread per pixel of the scene's tiles, row by row of its tile (the state is read, and the caller's arrays are written, in whole
-// lines): the K slots ordered by Batcher's odd-even merge network for 8 keys (19 exchanges, fixed indices: registers), the quotients,
-// and the stores -- row-major into the caller's arrays, or over the pixel's own state words for the host entry point.
-__global__ __launch_bounds__(256) void rt_matte_finish_kernel(const RtDevScene S, const RtMatteArgs A)
-{
-    const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
-    if (lp >= S.tileCount * RT_TILE_PIXELS) return;
-    const uint32_t slot = lp >> 14, q = lp & (RT_TILE_PIXELS - 1u), tile = S.tileIds[slot];
-    const uint32_t gx = (tile % S.tilesX) * RT_TILE + (q & (RT_TILE - 1u)), gy = (tile / S.tilesX) * RT_TILE + (q >> 7);
-    if (gx >= S.width || gy >= S.height) return;
-    uint32_t *state = A.state + (size_t)slot * A.words * RT_TILE_PIXELS + q;
-    const uint32_t M = A.selectCount, K = A.layers;
-    uint32_t sel[RT_MATTE_MAX_SELECT];
-    unsigned long long key[RT_MATTE_MAX_LAYERS];
-#pragma unroll
-    for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m) sel[m] = (uint32_t)m < M ? state[(size_t)m * RT_TILE_PIXELS] : 0u;
-#pragma unroll
-    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k) {
-        const uint32_t c = (uint32_t)k < K ? state[(size_t)(M + K + k) * RT_TILE_PIXELS] : 0u;
-        const uint32_t i = c != 0u ? state[(size_t)(M + k) * RT_TILE_PIXELS] : RT_NONE;
-        key[k] = (unsigned long long)~c << 32 | i;
-    }
-    const uint32_t rest = state[(size_t)(M + 2u * K) * RT_TILE_PIXELS];
-    matte_exchange(key[0], key[1]); matte_exchange(key[2], key[3]); matte_exchange(key[4], key[5]); matte_exchange(key[6], key[7]);
-    matte_exchange(key[0], key[2]); matte_exchange(key[1], key[3]); matte_exchange(key[4], key[6]); matte_exchange(key[5], key[7]);
-    matte_exchange(key[1], key[2]); matte_exchange(key[5], key[6]);
-    matte_exchange(key[0], key[4]); matte_exchange(key[1], key[5]); matte_exchange(key[2], key[6]); matte_exchange(key[3], key[7]);
-    matte_exchange(key[2], key[4]); matte_exchange(key[3], key[5]);
-    matte_exchange(key[1], key[2]); matte_exchange(key[3], key[4]); matte_exchange(key[5], key[6]);
-    const size_t plane = A.rowMajor ? (size_t)S.width * S.height : (size_t)RT_TILE_PIXELS;
-    const size_t at = A.rowMajor ? (size_t)gy * S.width + gx : 0;
-    // (every store is a 32-bit word store, the quotients as their bits: over the state they follow this thread's own loads of the same type)
-    uint32_t *outSelect = A.rowMajor ? reinterpret_cast<uint32_t *>(A.outSelect) : state;
-    uint32_t *outId = A.rowMajor ? A.outLayerId : state + (size_t)M * RT_TILE_PIXELS;
-    uint32_t *outCov = A.rowMajor ? reinterpret_cast<uint32_t *>(A.outLayerCoverage) : state + (size_t)(M + K) * RT_TILE_PIXELS;
-    uint32_t *outRest = A.rowMajor ? reinterpret_cast<uint32_t *>(A.outRest) : state + (size_t)(M + 2u * K) * RT_TILE_PIXELS;
-    if (outSelect) {
-#pragma unroll
-        for (int m = 0; m < RT_MATTE_MAX_SELECT; ++m)
-            if ((uint32_t)m < M) outSelect[(size_t)m * plane + at] = __float_as_uint((float)sel[m] / A.den);
-    }
-#pragma unroll
-    for (int k = 0; k < RT_MATTE_MAX_LAYERS; ++k)
-        if ((uint32_t)k < K) {
-            if (outId) outId[(size_t)k * plane + at] = (uint32_t)key[k];
-            if (outCov) outCov[(size_t)k * plane + at] = __float_as_uint((float)~(uint32_t)(key[k] >> 32) / A.den);
-        }
-    if (outRest) outRest[at] = __float_as_uint((float)rest / A.den);
-}
-
-// ---- trace entries: the DDA start state of a ray, and exact segments ------------------------------------------------
-// A round lasts as long as its longest dependent chain: a ray that crosses the whole grid makes 766 cell visits one after
-// the other, and measured round times are ~0.4 ms + 0.32 ms per million rays -- the constant is that chain.  The walk is a
-// 3-way merge: per axis, the parameters T_a(i) = (plane_a[i] - o_a) / d_a at which the ray crosses successive planes form a
-// non-decreasing sequence (the same rounded quotients the reference computes, :383-385), and every step takes the smallest
-// head (:387-398).  So the state of the walk after all crossings with T <= tau is, per axis, simply the NUMBER of such
-// crossings -- it can be computed without walking (a plane search plus two exact divides per axis), for any tau.  A long
-// ray is therefore cut into up to RT_WF_MAXSEG SEGMENTS at parameters tau_k: segment k starts in the state at tau_k and ends
-// when it has visited the start cell of segment k+1 (the existing end-cell rule, :380).  Segments are traced by different
-// lanes; the ray's answer is the hit of its lowest segment that has one (atomicMin on hitKey), exactly the first cell
-// with a hit in path order.  Segments after a hit are wasted work; the chain per lane is ~8x shorter.
-//
-// Who makes the DDA start state of a ray (no kernel of its own: a set-up kernel between logic and trace cost a launch, a second
-// round trip of every ray through HBM and 30-50 us per round of a frame whose rounds are 60-600 us):
-//   * an ORDERED round (many rays: bound by total work, never cut) -- wf_logic_kernel, where the ray is in registers and nearly
-//     every lane spawns one; the entry carries the start state, and its walk-length class (predicted cell visits, exact for a
-//     ray that hits nothing) is counted on the way (per wave in LDS, one global atomic instruction per wave); wf_scatter_kernel
-//     turns ranks into positions, longest class first;
-//   * any other round (few rays: bound by its longest chain, cut finely enough to occupy every SIMD) -- wf_trace_kernel<false>,
-//     whose workgroups take a few rays each, plan them with every lane busy, and deal the segments to their lanes.  In a late
-//     round only every tenth path spawns a ray: planning those in the logic kernel ran its whole tail at a tenth of the lanes
-//     (measured: logic round 1 84 -> 167 us).
-// Only the ORDER and GROUPING in which cells are visited changes.  Cutting costs work (every segment has a start-up and a test
-// batch of its own, segments behind a hit are wasted), so the aimed-at cell visits per segment depend on how many rays the
-// round has (RtRoundMode::segLen, chosen by the host from the launch plan).
-#ifndef RT_WF_MAXSEG
-#define RT_WF_MAXSEG 12
-#endif
-struct DdaState { uint32_t cell; float dx, dy, dz; };
-
-// One axis of the state at parameter tau: c0 = cell coordinate of the walk's start, returns the coordinate after all
-// crossings with T <= tau and, in `head`, the parameter of the next crossing.  `limit` = crossings that stay inside the grid.
-// `lut` / `lutScale` (optional): this axis' 256 cell estimates and 256 / box width (RtDevScene::cellLut) -- the guess then costs one
-// table read instead of the eight dependent reads of a plane search, unless the table is coarse where the point lies.
-__device__ __forceinline__ uint32_t axis_state_at(const float *planes, uint32_t c0, float oa, float da, float tau, float &head,
-                                                  const uint8_t *lut = nullptr, float lutScale = 0.f)
-{
-    const bool pos = (0.f <= da);
-    const int limit = pos ? (int)(RT_GRID_DIV - 1 - c0) : (int)c0; // the crossing after these leaves the grid (tau is before it)
-    // guess from the position (the plane search of GetBoxAddress), then settle it with the exact quotients
-    const float p = oa + tau * da;
-    int g = 0;
-    bool search = true;
-    if (lut) {
-        const int i = min(255, max(0, (int)((p - planes[0]) * lutScale)));
-        const int a = lut[max(i - 1, 0)], b = lut[min(i + 1, 255)];
-        g = lut[i];
-        search = b - a > 4; // (more than a few cells in three table steps: the settling loops below would walk them one by one)
-    }
-    if (search) {
-        g = 0;
-#pragma unroll
-        for (int div = RT_GRID_DIV / 2; div >= 1; div /= 2)
-            if (planes[g + div] < p) g += div;
-    }
-    int m = pos ? g - (int)c0 : (int)c0 - g;
-    m = m < 0 ? 0 : (m > limit ? limit : m);
-    // crossing number k (1-based) is plane c0+k going up, c0-k+1 going down
-    while (m >= 1 && !((planes[pos ? (int)c0 + m : (int)c0 - m + 1] - oa) / da <= tau)) --m;
-    float next = (planes[pos ? (int)c0 + m + 1 : (int)c0 - m] - oa) / da;
-    while (m < limit && next <= tau) {
-        ++m;
-        next = (planes[pos ? (int)c0 + m + 1 : (int)c0 - m] - oa) / da;
-    }
-    head = next;
-    return pos ? c0 + (uint32_t)m : c0 - (uint32_t)m;
-}
-
-// GetBoxAddress (:174-193) on the LDS planes: strict '<'; packed cx | cy << 8 | cz << 16
-__device__ __forceinline__ uint32_t cell_of(const float *planes, V3 p)
-{
-    int cx = 0, cy = 0, cz = 0;
-#pragma unroll
-    for (int div = RT_GRID_DIV / 2; div >= 1; div /= 2) {
-        if (planes[cx + div] < p.x) cx += div;
-        if (planes[(RT_GRID_DIV + 1) + cy + div] < p.y) cy += div;
-        if (planes[2 * (RT_GRID_DIV + 1) + cz + div] < p.z) cz += div;
-    }
-    return (uint32_t)cx | ((uint32_t)cy << 8) | ((uint32_t)cz << 16);
-}
-
-// What a ray's walk is made from: its DDA start state (:351-362, :383-385), where it ends (a ray with a finite range: the cell of
-// its far end, :356-362), how many cells it will visit if it hits nothing, and where it leaves the grid (te).
-struct EntryPlan { DdaState start; uint32_t endCell, visits; float te; };
-
-// `haveStart`: the caller knows the start cell (a hit's shadow ray and its bounce ray start at the same point).  `lut` (optional; LDS
-// copy of RtDevScene::cellLut followed by the three scales 256 / box width): where a ray WITHOUT an end cell leaves the grid -- which
-// only predicts the length of its walk -- is estimated with one table read per axis instead of a plane search.
-// `clip` (optional; RtDevScene::boxMin + RT_CLIP_AT, the same address in every lane): the scene's clip planes (rt_ray_clip.h), read with scalar
-// loads.  A plain ray's te is lowered to where it leaves their bound, and it ends in the cell of that point like a finite ray.
-typedef const __attribute__((address_space(4))) float *ClipPlanes;
-__device__ __forceinline__ EntryPlan plan_ray(const float *planes, V3 o, V3 d, float tmin, float tmax, bool haveStart = false, uint32_t startCell = 0u,
-                                              const uint8_t *lut = nullptr, const float *lutScale = nullptr, const float *clip = nullptr)
-{
-    EntryPlan p;
-    const V3 lo = mk(planes[0], planes[RT_GRID_DIV + 1], planes[2 * (RT_GRID_DIV + 1)]);
-    const V3 hi = mk(planes[RT_GRID_DIV], planes[2 * RT_GRID_DIV + 1], planes[3 * RT_GRID_DIV + 2]);
-    // start / end cells (:351-362)
-    V3 from = along(o, tmin, d);
-    const bool startInside = lo.x <= from.x && from.x <= hi.x && lo.y <= from.y && from.y <= hi.y && lo.z <= from.z && from.z <= hi.z;
-    bind_in_cube(from, d, lo, hi);
-    p.start.cell = startCell;
-    if (!haveStart) p.start.cell = cell_of(planes, from);
-    p.te = RT_INF;
-    V3 to;
-    if (tmax < RT_INF) {
-        to = along(o, tmax, d);
-        bind_in_cube(to, d, lo, hi);
-    } else {
-        // where the ray leaves the grid: the smallest of the three boundary crossings (same quotients as the walk's)
-        if (d.x != 0.f) { const float t = (((0.f <= d.x) ? hi.x : lo.x) - o.x) / d.x; if (t < p.te) p.te = t; }
-        if (d.y != 0.f) { const float t = (((0.f <= d.y) ? hi.y : lo.y) - o.y) / d.y; if (t < p.te) p.te = t; }
-        if (d.z != 0.f) { const float t = (((0.f <= d.z) ? hi.z : lo.z) - o.z) / d.z; if (t < p.te) p.te = t; }
-        to = (p.te < RT_INF) ? along(o, p.te, d) : from;
-    }
-    const int cx = (int)(p.start.cell & 255u), cy = (int)((p.start.cell >> 8) & 255u), cz = (int)(p.start.cell >> 16);
-    // distances from the ray ORIGIN to the next plane of each axis (:383-385)
-    p.start.dx = (planes[cx + ((0 <= d.x) ? 1 : 0)] - o.x) / d.x;
-    p.start.dy = (planes[(RT_GRID_DIV + 1) + cy + ((0 <= d.y) ? 1 : 0)] - o.y) / d.y;
-    p.start.dz = (planes[2 * (RT_GRID_DIV + 1) + cz + ((0 <= d.z) ? 1 : 0)] - o.z) / d.z;
-    // the clip (rt_ray_clip.h has the argument): the walk ends once it has visited the cell of o + te d, beyond which every cell is empty
-    bool clipped = false;
-    if (clip) {
-        const ClipPlanes cp = (ClipPlanes)(uintptr_t)clip;
-        const uint32_t count = __float_as_uint(cp[0]);
-        clipped = rt_clip_ray(cp, count, tmax < RT_INF, startInside, o.x, o.y, o.z, d.x, d.y, d.z, tmin, p.start.dx, p.start.dy, p.start.dz, p.te);
-        if (clipped) to = along(o, p.te, d);
-    }
-    uint32_t last; // (where a ray without an end cell leaves the grid is a scheduling matter only)
-    if (lut && !(tmax < RT_INF) && !clipped) {
-        const float fx = (to.x - lo.x) * lutScale[0], fy = (to.y - lo.y) * lutScale[1], fz = (to.z - lo.z) * lutScale[2];
-        const int ix = min(255, max(0, (int)fx)), iy = min(255, max(0, (int)fy)), iz = min(255, max(0, (int)fz)); // (a NaN converts to 0)
-        last = (uint32_t)lut[ix] | ((uint32_t)lut[256 + iy] << 8) | ((uint32_t)lut[512 + iz] << 16);
-    } else last = cell_of(planes, to);
-    p.endCell = (tmax < RT_INF || clipped) ? last : 0xffffffffu;
-    // every step moves one axis by one cell in a fixed direction: visits = Manhattan distance + 1
-    p.visits = (uint32_t)(abs((int)(last & 255u) - cx) + abs((int)((last >> 8) & 255u) - cy) + abs((int)(last >> 16) - cz)) + 1u;
-    return p;
-}
-
-// Into how many segments a planned ray is cut when a segment should make about segLen cell visits.  Only rays without an end
-// cell are cut, and only where every quotient involved is an ordinary number (a zero direction component makes heads infinite
-// or NaN and the merge argument is not worth stretching to them); a ray only slightly over the aim is left whole.
-__device__ __forceinline__ uint32_t segments_of(const EntryPlan &p, V3 d, float tmax, uint32_t segLen)
-{
-    const bool plain = rt_clip_plain(tmax < RT_INF, d.x, d.y, d.z, p.te, p.start.dx, p.start.dy, p.start.dz);
-    if (!plain || p.visits <= segLen + segLen / 4) return 1u;
-    const uint32_t n = (p.visits + segLen - 1) / segLen;
-    return n > RT_WF_MAXSEG ? (uint32_t)RT_WF_MAXSEG : n;
-}
-
-// Cut k (1 <= k < n) of a ray: tau_k = ta + (te - ta) * k / n is non-decreasing in k, and a cut only exists where ta <= tau_k < te,
-// so the cuts that exist are a prefix of 1 .. n - 1: whether cut k and cut k + 1 exist can be told from k alone.
-__device__ __forceinline__ bool cut_at(float ta, float te, uint32_t k, uint32_t n, float &tau)
-{
-    tau = ta + (te - ta) * ((float)k / (float)n);
-    return ta <= tau && tau < te;
 }
 
 // ---- stage 2: per-path state machine ---------------------------------------------------------------------------------
@@ -1477,7 +1013,7 @@ __global__ __launch_bounds__(256) void wf_accum_kernel(const RtDevScene S, const
 // ---- end of a batch's issued rounds: tell the host whether anybody is still waiting ------------------------------------------
 // One workgroup.  The main queue slices of round `round` (what logic(round - 1) appended) hold one request per path that is not
 // finished; their sum goes to the mapped host word, so the host can issue a frame's rounds without looking at the queue in
-// between and check afterwards (rt_api.cpp).
+// between and check afterwards (rt_frame.cpp).
 __global__ __launch_bounds__(256) void wf_status_kernel(const RtWavefront W, const uint32_t round, uint32_t *shadeCount)
 {
     __shared__ uint32_t part[4];
@@ -1498,135 +1034,7 @@ __global__ __launch_bounds__(256) void wf_status_kernel(const RtWavefront W, con
         for (uint32_t i = threadIdx.x; i < 3u * RT_WF_SHARDS; i += 256u) shadeCount[i] = 0u;
 }
 
-// ---- ray queries (rtHipSceneIntersect*): caller-supplied rays against the resident grid -------------------------------------
-// One lane per ray: RayIntersectsTriangles (raytrace_opencl.c:324-401) over the dense view wf_trace_kernel reads (rt_device.h,
-// gridBlockSparse / pairRec): one block-table look-up per 4x4x4 block the walk enters, one 64-byte gather per occupied cell (its
-// first candidate and its count), the further candidates at `rest` in list order.  The running maximum is reset per cell (:366), a
-// candidate replaces it only with a strictly smaller t (ties keep the earlier candidate), and the walk ends at the first cell with a
-// hit, at the end cell, or where a step would leave the grid (:380-398).  Rays are {o.xyz, tmin} {d.xyz, tmax}; hits {t, triangle,
-// abL, acL}, abL = acL = 0 and t = tmax on a miss.  Every input has a bounded walk that reads inside the grid arrays: cell_of is a
-// binary search (coordinates in [0, 255] whatever the point, NaN included), and each step moves one axis one cell in the direction
-// fixed by the sign of d, so a walk leaves the grid after at most 3 x 255 steps -- the loop bound only states that.
-template <bool FAST>
-__device__ __forceinline__ uint32_t query_walk(const RtDevScene &S, const float *planes, V3 o, V3 d, float tmin, float tmax, uint32_t excluded,
-                                               float &hitT, float &hitL1, float &hitL2)
-{
-    const V3 lo = mk(planes[0], planes[RT_GRID_DIV + 1], planes[2 * (RT_GRID_DIV + 1)]);
-    const V3 hi = mk(planes[RT_GRID_DIV], planes[2 * RT_GRID_DIV + 1], planes[3 * RT_GRID_DIV + 2]);
-    V3 from = along(o, tmin, d);
-    bind_in_cube(from, d, lo, hi);
-    uint32_t cell = cell_of(planes, from), endCell = 0xffffffffu;
-    if (tmax < RT_INF) {
-        V3 to = along(o, tmax, d);
-        bind_in_cube(to, d, lo, hi);
-        endCell = cell_of(planes, to);
-    }
-    const bool px = (0.f <= d.x), py = (0.f <= d.y), pz = (0.f <= d.z);
-    const float *planesY = planes + (RT_GRID_DIV + 1), *planesZ = planes + 2 * (RT_GRID_DIV + 1);
-    uint32_t cx = cell & 255u, cy = (cell >> 8) & 255u, cz = cell >> 16;
-    // distances from the ray ORIGIN to the next plane of each axis (:383-385); a step re-divides only the axis it moved
-    float dx = (planes[cx + (px ? 1 : 0)] - o.x) / d.x;
-    float dy = (planesY[cy + (py ? 1 : 0)] - o.y) / d.y;
-    float dz = (planesZ[cz + (pz ? 1 : 0)] - o.z) / d.z;
-    const float rx = FAST ? refined_rcp(d.x) : 0.f, ry = FAST ? refined_rcp(d.y) : 0.f, rz = FAST ? refined_rcp(d.z) : 0.f;
-    const char *__restrict__ blockTable = reinterpret_cast<const char *>(S.gridBlockSparse);
-    const float4 *__restrict__ recs = reinterpret_cast<const float4 *>(S.pairRec);
-    uint32_t wordKey = 0xffffffffu, wordLo = 0, wordHi = 0, wordRank = 0;
-    uint32_t best = RT_NONE;
-    hitT = tmax;
-#pragma unroll 1
-    for (uint32_t visit = 0; visit < 3u * RT_GRID_DIV; ++visit) {
-        cell = cx | (cy << 8) | (cz << 16);
-        const uint32_t key = cell & 0xFCFCFCu;
-        if (key != wordKey) {
-            const uint3 w = *reinterpret_cast<const uint3 *>(blockTable + (size_t)key * 3u);
-            wordKey = key; wordLo = w.x; wordHi = w.y; wordRank = w.z;
-        }
-        const uint32_t bit = (cx & 3u) | ((cy & 3u) << 2) | ((cz & 3u) << 4);
-        const uint32_t below = (1u << (bit & 31u)) - 1u;
-        const uint32_t half = (bit & 32u) ? wordHi : wordLo;
-        if ((half >> (bit & 31u)) & 1u) {
-            const uint32_t dense = wordRank + ((bit & 32u) ? __popc(wordLo) + __popc(wordHi & below) : __popc(wordLo & below));
-            float tbest = tmax; // reset per cell (:366)
-            const float4 *rec = recs + 4 * (size_t)dense;
-            float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-            const uint32_t info = __float_as_uint(r1.w);
-            float t, l1, l2;
-            if (pair_test_flat(r0, r1, r2, r3, o, d, tmin, tbest, excluded, t, l1, l2)) {
-                best = __float_as_uint(r0.w); tbest = t; hitL1 = l1; hitL2 = l2;
-            }
-            uint32_t n = info & 15u;
-            if (n > 1u) {
-                rec = recs + 4 * (size_t)(info >> 4);
-                r0 = rec[0]; r1 = rec[1]; r2 = rec[2]; r3 = rec[3];
-                if (n == RT_PAIR_MANY) n = __float_as_uint(r1.w); // (the first further record has the exact count)
-#pragma unroll 1
-                for (uint32_t i = 1;;) {
-                    if (pair_test_flat(r0, r1, r2, r3, o, d, tmin, tbest, excluded, t, l1, l2)) {
-                        best = __float_as_uint(r0.w); tbest = t; hitL1 = l1; hitL2 = l2;
-                    }
-                    if (++i >= n) break;
-                    rec += 4;
-                    r0 = rec[0]; r1 = rec[1]; r2 = rec[2]; r3 = rec[3];
-                }
-            }
-            hitT = tbest;
-            if (best != RT_NONE) break;
-        }
-        if (cell == endCell) break;
-        // axis choice (:387-398): x only if strictly smallest, else y if smaller than z, else z; a step off the grid ends the walk
-        if ((dx < dy) & (dx < dz)) {
-            if (cx == (px ? 255u : 0u)) break;
-            cx = px ? cx + 1u : cx - 1u;
-            const float num = planes[cx + (px ? 1 : 0)] - o.x;
-            dx = FAST ? tame_quotient(num, d.x, rx) : num / d.x;
-        } else if (dy < dz) {
-            if (cy == (py ? 255u : 0u)) break;
-            cy = py ? cy + 1u : cy - 1u;
-            const float num = planesY[cy + (py ? 1 : 0)] - o.y;
-            dy = FAST ? tame_quotient(num, d.y, ry) : num / d.y;
-        } else {
-            if (cz == (pz ? 255u : 0u)) break;
-            cz = pz ? cz + 1u : cz - 1u;
-            const float num = planesZ[cz + (pz ? 1 : 0)] - o.z;
-            dz = FAST ? tame_quotient(num, d.z, rz) : num / d.z;
-        }
-    }
-    return best;
-}
-
-// rays [count][2] float4, excluded [count] (nullptr: none), hits [count] float4.  fastQuotient: the walk's quotient without scaling
-// and fix-up for waves whose rays are all tame, under the same guard as wf_trace_kernel.
-__global__ __launch_bounds__(256) void rt_query_kernel(const RtDevScene S, const float4 *__restrict__ rays, const uint32_t *__restrict__ excludedIds,
-                                                       const uint32_t count, float4 *__restrict__ hits, const uint32_t fastQuotient)
-{
-    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
-    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
-    __syncthreads();
-    const size_t at = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (at >= count) return;
-    const float4 a = rays[2 * at], b = rays[2 * at + 1];
-    const uint32_t excluded = excludedIds ? excludedIds[at] : RT_NONE;
-    const V3 o = xyz(a), d = xyz(b);
-    float t, l1 = 0.f, l2 = 0.f;
-    uint32_t tri;
-    const bool tame = tame_origin(o.x) && tame_origin(o.y) && tame_origin(o.z) && tame_direction(d.x) && tame_direction(d.y) && tame_direction(d.z);
-    if (S.planesTame && fastQuotient && __ballot(!tame) == 0ull) tri = query_walk<true>(S, planes, o, d, a.w, b.w, excluded, t, l1, l2);
-    else tri = query_walk<false>(S, planes, o, d, a.w, b.w, excluded, t, l1, l2);
-    if (tri == RT_NONE) { l1 = 0.f; l2 = 0.f; }
-    hits[at] = make_float4(t, __uint_as_float(tri), l1, l2);
-}
-
-// ---- launch wrappers ------------------------------------------------------------------------------------------------
-extern "C" hipError_t rtw_launch_query(const RtDevScene *scene, const void *rays, const uint32_t *excluded, uint32_t count, void *hits,
-                                       uint32_t fastQuotient, hipStream_t stream)
-{
-    if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_query_kernel, dim3((uint32_t)(((uint64_t)count + 255u) / 256u)), dim3(256), 0, stream, *scene,
-                       reinterpret_cast<const float4 *>(rays), excluded, count, reinterpret_cast<float4 *>(hits), fastQuotient);
-    return hipGetLastError();
-}
-
+// ---- launch wrappers of the frame's kernels (rt_launch.h; those of the scene passes are in rt_scene_passes.hip) -------------------
 extern "C" hipError_t rtw_launch_primary(const RtDevScene *scene, const RtWavefront *wf, hipStream_t stream)
 {
     if (scene->tileCount == 0) return hipSuccess;
@@ -1647,29 +1055,6 @@ extern "C" hipError_t rtw_launch_surface_passes(const RtDevScene *scene, const R
 {
     if (scene->tileCount == 0) return hipSuccess;
     hipLaunchKernelGGL(wf_surface_passes_kernel, dim3(scene->tileCount * 64), dim3(256), 0, stream, *scene, *wf, surfBuf);
-    return hipGetLastError();
-}
-
-// mattes: one chunk of samples counted into the state ...
-extern "C" hipError_t rtw_launch_matte_count(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream)
-{
-    if (scene->tileCount == 0 || args->samples == 0) return hipSuccess;
-    if (args->kind > RT_MATTE_GROUP || args->selectCount > RT_MATTE_MAX_SELECT || args->layers > RT_MATTE_MAX_LAYERS || !args->state ||
-        args->words != args->selectCount + 2u * args->layers + 1u || (args->kind == RT_MATTE_GROUP && !args->groups))
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rt_matte_count_kernel, dim3(scene->tileCount * 64), dim3(256), 0, stream, *scene, *args);
-    return hipGetLastError();
-}
-
-// ... and the finished values stored
-extern "C" hipError_t rtw_launch_matte_finish(const RtDevScene *scene, const RtMatteArgs *args, hipStream_t stream)
-{
-    const uint32_t n = scene->tileCount * RT_TILE_PIXELS;
-    if (n == 0) return hipSuccess;
-    if (args->selectCount > RT_MATTE_MAX_SELECT || args->layers > RT_MATTE_MAX_LAYERS || !args->state ||
-        args->words != args->selectCount + 2u * args->layers + 1u)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rt_matte_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
     return hipGetLastError();
 }
 
@@ -1762,492 +1147,5 @@ extern "C" hipError_t rtw_launch_accum(const RtDevScene *scene, const RtWavefron
     const uint32_t n = scene->tileCount * RT_TILE_PIXELS;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(wf_accum_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *scene, *wf, first);
-    return hipGetLastError();
-}
-
-// ---- ambient occlusion (rtHipSceneAmbientOcclusion*; include/raytrace_hip.h, "AMBIENT OCCLUSION"; buffers in rt_device.h, RtAoArgs) -------
-// Both walks are query_walk, under rt_query_kernel's tame guard: each ray gets exactly the answer rtHipSceneIntersect gives it.
-__device__ __forceinline__ uint64_t ao_mix(uint64_t z)
-{
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// U(c) for base state s0 = mix(seed): the top 24 bits of h(c), exact in fp32
-__device__ __forceinline__ float ao_uniform(uint64_t s0, uint64_t c)
-{
-    return (float)(uint32_t)(ao_mix(s0 + (c + 1ull) * 0x9E3779B97F4A7C15ull) >> 40) * 0x1p-24f;
-}
-// the image pixel of AO-order index lp (may lie outside the image in a tile at its right or bottom edge)
-__device__ __forceinline__ void ao_pixel(const RtDevScene &S, uint32_t lp, uint32_t &gx, uint32_t &gy)
-{
-    const uint32_t tile = S.tileIds[lp >> 14], q = lp & (RT_TILE_PIXELS - 1u), blk = q >> 6, in = q & 63u;
-    gx = (tile % S.tilesX) * RT_TILE + (blk & 15u) * 8u + (in & 7u);
-    gy = (tile / S.tilesX) * RT_TILE + (blk >> 4) * 8u + (in >> 3);
-}
-__device__ __forceinline__ uint32_t ao_walk(const RtDevScene &S, const float *planes, uint32_t fastQuotient, V3 o, V3 d, float tmax, uint32_t excluded,
-                                            float &t)
-{
-    float l1, l2;
-    const bool tame = tame_origin(o.x) && tame_origin(o.y) && tame_origin(o.z) && tame_direction(d.x) && tame_direction(d.y) && tame_direction(d.z);
-    if (S.planesTame && fastQuotient && __ballot(!tame) == 0ull) return query_walk<true>(S, planes, o, d, 0.f, tmax, excluded, t, l1, l2);
-    return query_walk<false>(S, planes, o, d, 0.f, tmax, excluded, t, l1, l2);
-}
-
-// One lane per pixel sample: the primary ray, its walk, the hit point and the oriented unit normal.  A sample with something to trace is
-// appended to the chunk's hit list (one atomic per wave); a miss or a normal of length 0 adds its R open rays to the pixel at once, so the
-// AO kernel's waves hold only rays that are traced.
-__global__ __launch_bounds__(256) void rt_ao_primary_kernel(const RtDevScene S, const RtAoArgs A)
-{
-    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
-    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
-    __syncthreads();
-    const uint32_t at = blockIdx.x * 256u + threadIdx.x;
-    if (at >= A.count) return;
-    const uint64_t g = A.base + at;
-    const uint32_t Sp = A.pixelSamples, lp = (uint32_t)(g / Sp), j = (uint32_t)(g - (uint64_t)lp * Sp);
-    uint32_t gx, gy;
-    ao_pixel(S, lp, gx, gy);
-    if (gx >= S.width || gy >= S.height) return; // (its counter is never read)
-    const uint32_t p = gy * S.width + gx;
-    float u = 0.5f, v = 0.5f;
-    if (Sp > 1u) {
-        const uint64_t s0 = ao_mix(A.seed), c = ((uint64_t)p * Sp + j) * (A.raysPerHit + 1u) * 32ull;
-        u = ao_uniform(s0, c);
-        v = ao_uniform(s0, c + 1u);
-    }
-    const float fx = (float)gx + u, fy = (float)gy + v;
-    const V3 o = mk(S.eye[0], S.eye[1], S.eye[2]);
-    const V3 d = mk((S.topLeft[0] + S.lr[0] * fx) + S.tb[0] * fy, (S.topLeft[1] + S.lr[1] * fx) + S.tb[1] * fy,
-                    (S.topLeft[2] + S.lr[2] * fx) + S.tb[2] * fy);
-    float t;
-    const uint32_t tri = ao_walk(S, planes, A.fastQuotient, o, d, RT_INF, RT_NONE, t);
-    V3 P = mk(0.f, 0.f, 0.f), n = P;
-    bool trace = false;
-    if (tri != RT_NONE) {
-        P = along(o, t, d);
-        const float4 r2 = reinterpret_cast<const float4 *>(S.triRec)[4 * (size_t)tri + 2]; // {ac.z, n = cross(ac, ab)}
-        n = mk(r2.y, r2.z, r2.w);
-        if (dot3(n, d) > 0.f) n = mk(-n.x, -n.y, -n.z);
-        const float m = dot3(n, n);
-        if (m > 0.f) {
-            const float r = sqrt_rn(m);
-            n = mk(n.x / r, n.y / r, n.z / r);
-            trace = true;
-        }
-    }
-    const uint32_t slot = wave_append(A.hits, trace);
-    if (trace) {
-        A.rec[2 * (size_t)slot] = make_float4(P.x, P.y, P.z, __uint_as_float(tri));
-        A.rec[2 * (size_t)slot + 1] = make_float4(n.x, n.y, n.z, __uint_as_float(at));
-    } else atomicAdd(A.counter + lp, A.raysPerHit);
-}
-
-// One lane per AO ray of the chunk's hit list, the R rays of a pixel sample on consecutive lanes (the grid is sized for every sample of
-// the chunk hitting; workgroups past the list exit at once).  The unoccluded rays of a wave are counted per pixel with a ballot: each
-// pixel's lanes are one run of the wave, its first lane adds the run's popcount to the pixel's counter (integer sums: the result does
-// not depend on the order of the atomics, nor on the order of the hit list).
-__global__ __launch_bounds__(256) void rt_ao_kernel(const RtDevScene S, const RtAoArgs A)
-{
-    const uint32_t R = A.raysPerHit, Sp = A.pixelSamples, listed = *A.hits;
-    if ((uint64_t)blockIdx.x * 256u >= (uint64_t)listed * R) return;
-    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
-    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
-    __syncthreads();
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x, s = k / R, r = k - s * R;
-    const bool live = s < listed;
-    bool open = false;
-    uint32_t lp = 0xffffffffu;
-    if (live) {
-        const float4 a = A.rec[2 * (size_t)s], b = A.rec[2 * (size_t)s + 1];
-        const uint64_t g = A.base + __float_as_uint(b.w);
-        lp = (uint32_t)(g / Sp);
-        const uint32_t j = (uint32_t)(g - (uint64_t)lp * Sp), tri = __float_as_uint(a.w);
-        uint32_t gx, gy;
-        ao_pixel(S, lp, gx, gy);
-        const V3 n = xyz(b);
-        const float sg = (n.z >= 0.f) ? 1.f : -1.f, fa = -1.f / (sg + n.z), fb = (n.x * n.y) * fa;
-        const V3 t1 = mk(1.f + ((sg * n.x) * n.x) * fa, sg * fb, -(sg * n.x));
-        const V3 t2 = mk(fb, sg + (n.y * n.y) * fa, -n.y);
-        const uint64_t s0 = ao_mix(A.seed), c = (((uint64_t)(gy * S.width + gx) * Sp + j) * (R + 1u) + 1u + r) * 32ull;
-        float xd = 0.f, yd = 0.f, r2 = 0.f;
-#pragma unroll 1
-        for (uint32_t att = 0; att < 16u; ++att) {
-            const float x = 2.f * ao_uniform(s0, c + 2u * att) - 1.f, y = 2.f * ao_uniform(s0, c + 2u * att + 1u) - 1.f;
-            const float q = x * x + y * y;
-            if (q < 1.f) { xd = x; yd = y; r2 = q; break; }
-        }
-        const float z = sqrt_rn(1.f - r2);
-        const V3 d = mk((xd * t1.x + yd * t2.x) + z * n.x, (xd * t1.y + yd * t2.y) + z * n.y, (xd * t1.z + yd * t2.z) + z * n.z);
-        float t;
-        open = ao_walk(S, planes, A.fastQuotient, xyz(a), d, A.radius, tri, t) == RT_NONE;
-    }
-    const uint64_t openMask = __ballot(open);
-    const uint32_t lane = __lane_id();
-    const uint32_t before = __shfl_up(lp, 1, 64);
-    const bool first = live && (lane == 0u || before != lp);
-    const uint64_t firsts = __ballot(first);
-    if (first) {
-        const uint64_t later = firsts & ~((2ull << lane) - 1ull);           // first lanes of the runs after this one
-        const uint64_t run = (later ? (later & (0ull - later)) - 1ull : ~0ull) & ~((1ull << lane) - 1ull);
-        const uint32_t n = (uint32_t)__popcll(openMask & run);
-        if (n) atomicAdd(A.counter + lp, n);
-    }
-}
-
-// One lane per pixel of the scene's tiles: value = (float)U / (float)(Sp*R) into row-major W x H `out` (rowMajor) or at index lp
-// (the host entry point's staging, de-tiled on the host; `out` may then be `counter` itself).
-__global__ __launch_bounds__(256) void rt_ao_finish_kernel(const RtDevScene S, const uint32_t *counter, float den, float *out, uint32_t rowMajor)
-{
-    const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
-    if (lp >= S.tileCount * RT_TILE_PIXELS) return;
-    uint32_t gx, gy;
-    ao_pixel(S, lp, gx, gy);
-    if (gx >= S.width || gy >= S.height) return;
-    const float v = (float)counter[lp] / den;
-    if (rowMajor) out[(size_t)gy * S.width + gx] = v;
-    else out[lp] = v;
-}
-
-extern "C" hipError_t rtw_launch_ao(const RtDevScene *scene, const RtAoArgs *args, hipStream_t stream)
-{
-    if (args->count == 0) return hipSuccess;
-    const uint64_t rays = (uint64_t)args->count * args->raysPerHit;
-    if (rays > (1ull << 31)) return hipErrorInvalidValue; // (the AO kernel's lane index is 32-bit)
-    hipLaunchKernelGGL(rt_ao_primary_kernel, dim3((args->count + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
-    hipLaunchKernelGGL(rt_ao_kernel, dim3((uint32_t)((rays + 255u) / 256u)), dim3(256), 0, stream, *scene, *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t rtw_launch_ao_finish(const RtDevScene *scene, const uint32_t *counter, uint32_t samplesTimesRays, float *out, uint32_t rowMajor,
-                                           hipStream_t stream)
-{
-    const uint32_t n = scene->tileCount * RT_TILE_PIXELS;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_ao_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, *scene, counter, (float)samplesTimesRays, out, rowMajor);
-    return hipGetLastError();
-}
-
-// ---- motion vectors (rtHipSceneMotion*; include/raytrace_hip.h, "MOTION VECTORS"; buffers in rt_device.h, RtMotionArgs) -------------------
-// One lane per triangle: the rows of its triRec line that hold a, ab, ac become its reference record (16-byte loads and stores).
-__global__ __launch_bounds__(256) void rt_motion_mark_kernel(const float4 *__restrict__ triRec, float4 *__restrict__ ref, const uint32_t triangles)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= triangles) return;
-    const float4 *src = triRec + 4 * (size_t)i;
-    const float4 r0 = src[0], r1 = src[1], r2 = src[2];
-    float4 *dst = ref + RT_MOTION_REF_ROWS * (size_t)i;
-    dst[0] = r0;
-    dst[1] = r1;
-    dst[2] = make_float4(r2.x, 0.f, 0.f, 0.f); // (the rest of the row is the normal)
-}
-
-// One lane per pixel of the scene's tiles in AO order (a wave is one 8x8 block of the screen): the centre ray, its walk -- query_walk
-// under rt_query_kernel's tame guard, the answer rtHipSceneIntersect gives --, one gather of the hit triangle's reference record, the
-// projection through the reference camera and up to four stores.
-__global__ __launch_bounds__(256) void rt_motion_kernel(const RtDevScene S, const RtMotionArgs A)
-{
-    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
-    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
-    __syncthreads();
-    const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
-    if (lp >= S.tileCount * RT_TILE_PIXELS) return;
-    uint32_t gx, gy;
-    ao_pixel(S, lp, gx, gy);
-    if (gx >= S.width || gy >= S.height) return;
-    const float fx = (float)gx + 0.5f, fy = (float)gy + 0.5f;
-    const V3 o = mk(S.eye[0], S.eye[1], S.eye[2]);
-    const V3 d = mk((S.topLeft[0] + S.lr[0] * fx) + S.tb[0] * fy, (S.topLeft[1] + S.lr[1] * fx) + S.tb[1] * fy,
-                    (S.topLeft[2] + S.lr[2] * fx) + S.tb[2] * fy);
-    float t, l1 = 0.f, l2 = 0.f;
-    uint32_t tri;
-    const bool tame = tame_origin(o.x) && tame_origin(o.y) && tame_origin(o.z) && tame_direction(d.x) && tame_direction(d.y) && tame_direction(d.z);
-    if (S.planesTame && A.fastQuotient && __ballot(!tame) == 0ull) tri = query_walk<true>(S, planes, o, d, 0.f, RT_INF, RT_NONE, t, l1, l2);
-    else tri = query_walk<false>(S, planes, o, d, 0.f, RT_INF, RT_NONE, t, l1, l2);
-    const bool hit = tri != RT_NONE;
-    const V3 E = mk(A.eye[0], A.eye[1], A.eye[2]), TL = mk(A.topLeft[0], A.topLeft[1], A.topLeft[2]);
-    const V3 lr = mk(A.lr[0], A.lr[1], A.lr[2]), tb = mk(A.tb[0], A.tb[1], A.tb[2]);
-    V3 w = d; // a miss: the background is a point at infinity
-    if (hit) {
-        const float4 *rec = A.ref + RT_MOTION_REF_ROWS * (size_t)tri;
-        const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-        const V3 P = mk((r0.x + l1 * r0.w) + l2 * r1.z, (r0.y + l1 * r1.x) + l2 * r1.w, (r0.z + l1 * r1.y) + l2 * r2.x);
-        w = sub3(P, E);
-    }
-    const V3 n = cross3(lr, tb);
-    const float den = dot3(w, n);
-    const size_t at = A.rowMajor ? (size_t)gy * S.width + gx : (size_t)lp;
-    if (A.motion) {
-        const float px = dot3(TL, cross3(w, tb)) / den, py = dot3(TL, cross3(lr, w)) / den;
-        A.motion[2 * at] = px - fx; // (two 4-byte stores: the caller's array need not be 8-byte aligned)
-        A.motion[2 * at + 1] = py - fy;
-    }
-    if (A.t) A.t[at] = hit ? t : RT_INF;
-    if (A.prevT) A.prevT[at] = hit ? den / dot3(TL, n) : RT_INF;
-    if (A.triangle) A.triangle[at] = tri;
-}
-
-extern "C" hipError_t rtw_launch_motion_mark(const float *triRec, void *ref, uint32_t triangles, hipStream_t stream)
-{
-    if (triangles == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_motion_mark_kernel, dim3((triangles + 255u) / 256u), dim3(256), 0, stream, reinterpret_cast<const float4 *>(triRec),
-                       reinterpret_cast<float4 *>(ref), triangles);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t rtw_launch_motion(const RtDevScene *scene, const RtMotionArgs *args, hipStream_t stream)
-{
-    const uint32_t n = scene->tileCount * RT_TILE_PIXELS;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_motion_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
-    return hipGetLastError();
-}
-
-// ---- ambient occlusion bake (rtHipSceneBakeAmbientOcclusion*; include/raytrace_hip.h, "AMBIENT OCCLUSION BAKE"; buffers in rt_device.h,
-// RtBakeArgs) ------------------------------------------------------------------------------------------------------------------------
-// The AO rays are the AO block's (ao_mix, ao_uniform, ao_walk): each gets exactly the answer rtHipSceneIntersect gives it.
-#define RT_BAKE_BIG_RECT 1024u // texel rectangles larger than this are rasterised by every workgroup of rt_bake_raster_big_kernel
-#define RT_BAKE_BIG_BLOCKS 1024u
-
-// The coverage test of texel centre (cu, cv) against UV corners uv[0..5] = uvA, uvB, uvC, and its barycentrics (l1 weighs b, l2 c).
-__device__ __forceinline__ bool bake_cover(const float *uv, float cu, float cv, float &l1, float &l2)
-{
-    const float e1x = uv[2] - uv[0], e1y = uv[3] - uv[1], e2x = uv[4] - uv[0], e2y = uv[5] - uv[1], qx = cu - uv[0], qy = cv - uv[1];
-    const float den = e1x * e2y - e1y * e2x;
-    l1 = (qx * e2y - qy * e2x) / den;
-    l2 = (e1x * qy - e1y * qx) / den;
-    return l1 >= 0.f && l2 >= 0.f && l1 + l2 <= 1.f;
-}
-__device__ __forceinline__ float bake_centre(uint32_t i, uint32_t n) { return ((float)i + 0.5f) / (float)n; }
-
-// The texel rectangle outside which bake_cover provably fails for UV corners uv[0..5]; false if no texel can pass.  A den that is 0 or
-// NaN (a NaN UV gives one) covers nothing.  Otherwise the UV bounding box is grown by a bound on the test's rounding (in double):
-// with E the largest |e| component, Q = 1 + max|uvA|, u = 2^-24, the computed den is within 8uE^2 of the exact D of the rounded edges,
-// and a texel that passes has exact barycentrics within delta = 4(u + 8u(QE + 2E^2)/D) of [0, 1], so its centre lies within 6 delta E
-// (+ 4uQ for the centre's own rounding) of the box, plus one texel.  An infinite UV, or D <= 32uE^2 (den may be rounding noise), gets
-// the whole map.
-__device__ __forceinline__ bool bake_rect(const float *uv, uint32_t W, uint32_t H, uint32_t &x0, uint32_t &x1, uint32_t &y0, uint32_t &y1)
-{
-    const float e1x = uv[2] - uv[0], e1y = uv[3] - uv[1], e2x = uv[4] - uv[0], e2y = uv[5] - uv[1];
-    const float den = e1x * e2y - e1y * e2x;
-    if (den == 0.f || den != den) return false;
-    x0 = 0; x1 = W - 1; y0 = 0; y1 = H - 1;
-    bool finite = fabsf(den) < RT_INF;
-    for (int k = 0; k < 6; ++k) finite = finite && fabsf(uv[k]) < RT_INF;
-    if (!finite) return true;
-    const double u = 0x1p-24, E = fmax(fmax(fabs((double)e1x), fabs((double)e1y)), fmax(fabs((double)e2x), fabs((double)e2y)));
-    const double D = fabs((double)e1x * (double)e2y - (double)e1y * (double)e2x);
-    if (!(D > 32.0 * u * E * E)) return true;
-    const double Q = 1.0 + fmax(fabs((double)uv[0]), fabs((double)uv[1]));
-    const double delta = 4.0 * (u + 8.0 * u * (Q * E + 2.0 * E * E) / D), m = 6.0 * delta * E + 4.0 * u * Q;
-    const double umin = fmin(fmin((double)uv[0], (double)uv[2]), (double)uv[4]) - m, umax = fmax(fmax((double)uv[0], (double)uv[2]), (double)uv[4]) + m;
-    const double vmin = fmin(fmin((double)uv[1], (double)uv[3]), (double)uv[5]) - m, vmax = fmax(fmax((double)uv[1], (double)uv[3]), (double)uv[5]) + m;
-    const double lx = floor(umin * W - 0.5) - 1.0, hx = ceil(umax * W - 0.5) + 1.0, ly = floor(vmin * H - 0.5) - 1.0, hy = ceil(vmax * H - 0.5) + 1.0;
-    if (hx < 0.0 || hy < 0.0 || lx > (double)(W - 1) || ly > (double)(H - 1)) return false;
-    x0 = lx > 0.0 ? (uint32_t)lx : 0u; y0 = ly > 0.0 ? (uint32_t)ly : 0u;
-    x1 = hx < (double)(W - 1) ? (uint32_t)hx : W - 1; y1 = hy < (double)(H - 1) ? (uint32_t)hy : H - 1;
-    return true;
-}
-__device__ __forceinline__ void bake_texel(const float *uv, uint32_t W, uint32_t H, uint32_t x, uint32_t y, uint32_t tri, uint32_t *win)
-{
-    float l1, l2;
-    if (bake_cover(uv, bake_centre(x, W), bake_centre(y, H), l1, l2)) atomicMin(win + (size_t)y * W + x, tri);
-}
-
-// One thread per triangle of the range A.first .. A.first + A.count - 1 that passes the material filter: the texels of its rectangle,
-// or -- a rectangle of more than RT_BAKE_BIG_RECT texels -- an entry of the big list.  atomicMin: the smallest covering id wins
-// whatever the order.
-__global__ __launch_bounds__(256) void rt_bake_raster_kernel(const RtDevScene S, const RtBakeArgs A)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= A.count) return;
-    const uint32_t tri = A.first + i;
-    const float *sh = S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri;
-    if (A.matchMaterial && __float_as_int(sh[21]) != A.material) return;
-    float uv[6];
-    for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
-    uint32_t x0, x1, y0, y1;
-    if (!bake_rect(uv, A.width, A.height, x0, x1, y0, y1)) return;
-    if ((uint64_t)(x1 - x0 + 1) * (uint64_t)(y1 - y0 + 1) > RT_BAKE_BIG_RECT) {
-        A.bigList[atomicAdd(A.bigCount, 1u)] = tri;
-        return;
-    }
-    for (uint32_t y = y0; y <= y1; ++y)
-        for (uint32_t x = x0; x <= x1; ++x) bake_texel(uv, A.width, A.height, x, y, tri, A.win);
-}
-
-// The big list's triangles in turn, the texels of each one's rectangle dealt over every thread of the launch (one quad can cover the
-// whole map: a workgroup per triangle would leave the chip idle).
-__global__ __launch_bounds__(256) void rt_bake_raster_big_kernel(const RtDevScene S, const RtBakeArgs A)
-{
-    const uint32_t n = *A.bigCount;
-    const uint32_t stride = gridDim.x * 256u;
-    for (uint32_t b = 0; b < n; ++b) {
-        const uint32_t tri = A.bigList[b];
-        const float *sh = S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri;
-        float uv[6];
-        for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
-        uint32_t x0, x1, y0, y1;
-        bake_rect(uv, A.width, A.height, x0, x1, y0, y1); // (true: it was listed)
-        const uint32_t w = x1 - x0 + 1, area = w * (y1 - y0 + 1); // (at most W*H <= 2^26)
-        for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < area; k += stride) {
-            const uint32_t ky = k / w;
-            bake_texel(uv, A.width, A.height, x0 + (k - ky * w), y0 + ky, tri, A.win);
-        }
-    }
-}
-
-// One lane per texel of the chunk: its winner, the surface point and the oriented unit normal.  An uncovered texel's counter is set to
-// 0 and a zero-normal texel's to R here; the others' to 0, and they are appended to the hit list (one atomic per wave).
-__global__ __launch_bounds__(256) void rt_bake_points_kernel(const RtDevScene S, const RtBakeArgs A)
-{
-    const uint32_t at = blockIdx.x * 256u + threadIdx.x;
-    if (at >= A.count) return;
-    const uint32_t t = (uint32_t)(A.base + at), tri = A.win[t];
-    V3 P = mk(0.f, 0.f, 0.f), n = P;
-    bool trace = false;
-    uint32_t open = 0;
-    if (tri != RT_NONE) {
-        const float *sh = S.triShade + RT_TRI_SHADE_WORDS * (size_t)tri;
-        float uv[6];
-        for (int k = 0; k < 6; ++k) uv[k] = sh[15 + k];
-        const uint32_t y = t / A.width, x = t - y * A.width;
-        float l1, l2;
-        bake_cover(uv, bake_centre(x, A.width), bake_centre(y, A.height), l1, l2); // (true: it won)
-        const float4 *rec = reinterpret_cast<const float4 *>(S.triRec) + 4 * (size_t)tri;
-        const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2]; // a.xyz ab.x | ab.yz ac.xy | ac.z n.xyz
-        P = mk((r0.x + l1 * r0.w) + l2 * r1.z, (r0.y + l1 * r1.x) + l2 * r1.w, (r0.z + l1 * r1.y) + l2 * r2.x);
-        n = mk(r2.y, r2.z, r2.w);
-        const V3 s = mk((sh[6] + sh[9]) + sh[12], (sh[7] + sh[10]) + sh[13], (sh[8] + sh[11]) + sh[14]);
-        if (dot3(n, s) < 0.f) n = mk(-n.x, -n.y, -n.z);
-        const float m = dot3(n, n);
-        if (m > 0.f) {
-            const float r = sqrt_rn(m);
-            n = mk(n.x / r, n.y / r, n.z / r);
-            trace = true;
-        } else open = A.raysPerTexel;
-    }
-    A.counter[t] = open;
-    const uint32_t slot = wave_append(A.hits, trace);
-    if (trace) {
-        A.rec[2 * (size_t)slot] = make_float4(P.x, P.y, P.z, __uint_as_float(tri));
-        A.rec[2 * (size_t)slot + 1] = make_float4(n.x, n.y, n.z, __uint_as_float(at));
-    }
-}
-
-// One lane per AO ray of the chunk's hit list, a texel's R rays on consecutive lanes; open rays are counted per texel with
-// rt_ao_kernel's ballot and one atomic per run of a wave.
-__global__ __launch_bounds__(256) void rt_bake_ao_kernel(const RtDevScene S, const RtBakeArgs A)
-{
-    const uint32_t R = A.raysPerTexel, listed = *A.hits;
-    if ((uint64_t)blockIdx.x * 256u >= (uint64_t)listed * R) return;
-    __shared__ float planes[3 * (RT_GRID_DIV + 1)];
-    for (int i = threadIdx.x; i < 3 * (RT_GRID_DIV + 1); i += 256) planes[i] = S.boxMin[i];
-    __syncthreads();
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x, s = k / R, r = k - s * R;
-    const bool live = s < listed;
-    bool open = false;
-    uint32_t t = 0xffffffffu;
-    if (live) {
-        const float4 a = A.rec[2 * (size_t)s], b = A.rec[2 * (size_t)s + 1];
-        t = (uint32_t)(A.base + __float_as_uint(b.w));
-        const uint32_t tri = __float_as_uint(a.w);
-        const V3 n = xyz(b);
-        const float sg = (n.z >= 0.f) ? 1.f : -1.f, fa = -1.f / (sg + n.z), fb = (n.x * n.y) * fa;
-        const V3 t1 = mk(1.f + ((sg * n.x) * n.x) * fa, sg * fb, -(sg * n.x));
-        const V3 t2 = mk(fb, sg + (n.y * n.y) * fa, -n.y);
-        const uint64_t s0 = ao_mix(A.seed), c = ((uint64_t)t * (R + 1u) + 1u + r) * 32ull;
-        float xd = 0.f, yd = 0.f, r2 = 0.f;
-#pragma unroll 1
-        for (uint32_t att = 0; att < 16u; ++att) {
-            const float x = 2.f * ao_uniform(s0, c + 2u * att) - 1.f, y = 2.f * ao_uniform(s0, c + 2u * att + 1u) - 1.f;
-            const float q = x * x + y * y;
-            if (q < 1.f) { xd = x; yd = y; r2 = q; break; }
-        }
-        const float z = sqrt_rn(1.f - r2);
-        const V3 d = mk((xd * t1.x + yd * t2.x) + z * n.x, (xd * t1.y + yd * t2.y) + z * n.y, (xd * t1.z + yd * t2.z) + z * n.z);
-        float th;
-        open = ao_walk(S, planes, A.fastQuotient, xyz(a), d, A.radius, tri, th) == RT_NONE;
-    }
-    const uint64_t openMask = __ballot(open);
-    const uint32_t lane = __lane_id();
-    const uint32_t before = __shfl_up(t, 1, 64);
-    const bool first = live && (lane == 0u || before != t);
-    const uint64_t firsts = __ballot(first);
-    if (first) {
-        const uint64_t later = firsts & ~((2ull << lane) - 1ull);
-        const uint64_t run = (later ? (later & (0ull - later)) - 1ull : ~0ull) & ~((1ull << lane) - 1ull);
-        const uint32_t cnt = (uint32_t)__popcll(openMask & run);
-        if (cnt) atomicAdd(A.counter + t, cnt);
-    }
-}
-
-// One lane per texel: the value (float)U / (float)R, or `fill` where nothing covers the texel (0, or -1 = invalid when dilation
-// follows), into `out` (which may be `counter` itself), and the winner into `tri` (if not null).
-__global__ __launch_bounds__(256) void rt_bake_finish_kernel(uint32_t texels, const uint32_t *win, const uint32_t *counter, float rays, float fill,
-                                                             float *out, uint32_t *tri)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= texels) return;
-    const uint32_t w = win[t];
-    const float v = (w == RT_NONE) ? fill : (float)counter[t] / rays;
-    out[t] = v;
-    if (tri) tri[t] = w;
-}
-
-// One dilation pass (Jacobi): values >= 0 are valid, -1 is not.  `last`: a texel still invalid is written as 0.
-__global__ __launch_bounds__(256) void rt_bake_dilate_kernel(uint32_t W, uint32_t H, const float *src, float *dst, uint32_t last)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= W * H) return;
-    const float v = src[t];
-    if (v >= 0.f) { dst[t] = v; return; }
-    const int y = (int)(t / W), x = (int)(t - (uint32_t)y * W);
-    float sum = 0.f;
-    uint32_t k = 0;
-    for (int dy = -1; dy <= 1; ++dy)
-        for (int dx = -1; dx <= 1; ++dx) {
-            const int nx = x + dx, ny = y + dy;
-            if ((dx == 0 && dy == 0) || nx < 0 || ny < 0 || nx >= (int)W || ny >= (int)H) continue;
-            const float w = src[(size_t)ny * W + nx];
-            if (w >= 0.f) { sum += w; ++k; }
-        }
-    dst[t] = k ? sum / (float)k : (last ? 0.f : -1.f);
-}
-
-extern "C" hipError_t rtw_launch_bake_raster(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream)
-{
-    if (args->count == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_bake_raster_kernel, dim3((args->count + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
-    hipLaunchKernelGGL(rt_bake_raster_big_kernel, dim3(RT_BAKE_BIG_BLOCKS), dim3(256), 0, stream, *scene, *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t rtw_launch_bake_points(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream)
-{
-    if (args->count == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_bake_points_kernel, dim3((args->count + 255u) / 256u), dim3(256), 0, stream, *scene, *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t rtw_launch_bake_ao(const RtDevScene *scene, const RtBakeArgs *args, hipStream_t stream)
-{
-    if (args->count == 0) return hipSuccess;
-    const uint64_t rays = (uint64_t)args->count * args->raysPerTexel;
-    if (rays > (1ull << 31)) return hipErrorInvalidValue; // (the AO kernel's lane index is 32-bit)
-    hipLaunchKernelGGL(rt_bake_ao_kernel, dim3((uint32_t)((rays + 255u) / 256u)), dim3(256), 0, stream, *scene, *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t rtw_launch_bake_finish(uint32_t texels, const uint32_t *win, const uint32_t *counter, uint32_t rays, float fill, float *out,
-                                             uint32_t *tri, hipStream_t stream)
-{
-    hipLaunchKernelGGL(rt_bake_finish_kernel, dim3((texels + 255u) / 256u), dim3(256), 0, stream, texels, win, counter, (float)rays, fill, out, tri);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t rtw_launch_bake_dilate(uint32_t W, uint32_t H, const float *src, float *dst, uint32_t last, hipStream_t stream)
-{
-    hipLaunchKernelGGL(rt_bake_dilate_kernel, dim3((W * H + 255u) / 256u), dim3(256), 0, stream, W, H, src, dst, last);
     return hipGetLastError();
 }

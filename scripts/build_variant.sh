@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage: bash scripts/build_variant.sh <tag> [extra hipcc -D flags...]  ->  opencl_render_amd/variants/lib_<tag>.so
-# Same sources and exactness flags as csrc/Makefile; only rt_wavefront.hip is recompiled with the extra defines.
+# Same sources and exactness flags as csrc/Makefile; only rt_wavefront.hip (the frame's kernels) is recompiled with the extra defines;
+# the scene passes of rt_scene_passes.hip are linked as the Makefile built them.
 set -e
 tag=$1; shift
 cd "$(dirname "$0")/../opencl_render_amd/csrc"

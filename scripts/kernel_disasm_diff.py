@@ -5,7 +5,9 @@ starts); the instruction text, relative branch offsets included, is compared.  N
 
     python scripts/kernel_disasm_diff.py --base /path/to/parent/checkout [--new .] [--keep DIR]
 
-Prints per source file the symbols that are identical, changed, removed and added, and exits 1 if any existing symbol changed or went.
+Prints per source file the symbols that are identical, changed, moved, removed and added, and exits 1 if any existing symbol changed or
+went.  Symbols are matched over all files together: one that left its file and is new in another has moved, and passes if its instructions
+are the same.  The last line printed is the verdict.
 """
 import argparse
 import os
@@ -15,7 +17,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("rt_kernels", "rt_wavefront", "rt_build_device", "rt_kat", "rt_scene_prep", "rt_denoise", "rt_temporal", "rt_variance",
+SOURCES = ("rt_kernels", "rt_wavefront", "rt_scene_passes", "rt_build_device", "rt_kat", "rt_scene_prep", "rt_denoise", "rt_temporal", "rt_variance",
            "rt_camera_move", "rt_geometry_move", "rt_scene_edit", "rt_motion_blur", "rt_dof")
 
 
@@ -65,22 +67,38 @@ def main():
         os.makedirs(os.path.join(keep, "new"), exist_ok=True)
         a = disassemble(args.base, os.path.join(keep, "base"), args.rocm)
         b = disassemble(args.new, os.path.join(keep, "new"), args.rocm)
+    # A symbol that left its file and is new in another one is the same symbol, moved.  home[(file, symbol)]: the file it went to.
+    home = {}
+    for name in SOURCES:
+        for k in a[name]:
+            if k not in b[name]:
+                for other in SOURCES:
+                    if other != name and k in b[other] and k not in a[other]:
+                        home[(name, k)] = other
+                        break
+    arrived = {name: [k for (_, k), to in home.items() if to == name] for name in SOURCES}
     bad = False
     for name in SOURCES:
         ka, kb = a[name], b[name]
-        same = [k for k in ka if k in kb and ka[k] == kb[k]]
-        changed = [k for k in ka if k in kb and ka[k] != kb[k]]
-        gone = [k for k in ka if k not in kb]
-        added = [k for k in kb if k not in ka]
-        print(f"{name}.hip: {len(ka)} symbols before, {len(kb)} after: {len(same)} identical, {len(changed)} changed, {len(gone)} removed, "
-              f"{len(added)} added")
+        after = {k: b[home.get((name, k), name)].get(k) for k in ka}  # each old symbol's instructions now, wherever it lives; None: gone
+        same = [k for k in ka if k in kb and after[k] == ka[k]]
+        moved = [k for k in ka if k not in kb and after[k] == ka[k]]
+        changed = [k for k in ka if after[k] is not None and after[k] != ka[k]]
+        gone = [k for k in ka if after[k] is None]
+        added = [k for k in kb if k not in ka and k not in arrived[name]]
+        print(f"{name}.hip: {len(ka)} symbols before, {len(kb)} after: {len(same)} identical, {len(changed)} changed, "
+              f"{len(moved)} moved, {len(gone)} removed, {len(added)} added, {len(arrived[name])} moved in")
         for k in changed:
-            print(f"  changed  {k} ({len(ka[k])} -> {len(kb[k])} instructions)")
+            where = f", now in {home[(name, k)]}.hip" if (name, k) in home else ""
+            print(f"  changed  {k}{where} ({len(ka[k])} -> {len(after[k])} instructions)")
+        for k in moved:
+            print(f"  moved    {k} to {home[(name, k)]}.hip, identical ({len(ka[k])} instructions)")
         for k in gone:
             print(f"  removed  {k}")
         for k in added:
             print(f"  added    {k} ({len(kb[k])} instructions)")
         bad = bad or bool(changed or gone)
+    print("FAIL: an existing symbol changed or went" if bad else "OK: every existing symbol is identical, in its file or moved")
     return 1 if bad else 0
 
 

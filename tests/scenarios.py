@@ -644,3 +644,22 @@ def shade_normal_scene(zoom=1):
 # light directions
 SPREAD_RADII = (0.0, 0.5, 90.0, 360.0)
 SPREAD_DIRS = ((0.3, -0.8, 0.5), (0.0, 0.0, 2.0))
+
+
+# ---- slots out of image order over partial tiles: what every read-back of a tile buffer has to place right ----------------------------
+SHUFFLED_TILES = (3, 0)  # of the 2 x 2 tiles of shuffled_tiles(): the ragged corner tile (32 x 16 pixels of it in the image) first, then a whole one
+
+
+def shuffled_tiles():
+    """160 x 144: two tiles across and two down, ragged on both edges; 300 triangles, two samples per pixel.  Rendered as the tiles
+    SHUFFLED_TILES, slot order and image order differ and one slot is mostly outside the image."""
+    return R.build_lists(S.make_soup(160, 144, 300, 0.3, seed=41, samples=2, name="shuffled_tiles"))
+
+
+def tiles_mask(sc, tiles):
+    """[H, W] bool: the pixels of `tiles`."""
+    mine = np.zeros((sc.height, sc.width), bool)
+    for t in tiles:
+        ty, tx = divmod(int(t), (sc.width + R.TILE - 1) // R.TILE)
+        mine[ty * R.TILE:(ty + 1) * R.TILE, tx * R.TILE:(tx + 1) * R.TILE] = True
+    return mine

@@ -180,6 +180,25 @@ def test_instances_over_a_tile_deal_compose():
     assert_bits(devout.cpu().numpy(), full, "two instances composed (device)")
 
 
+def test_host_and_device_entries_agree_on_shuffled_partial_tiles():
+    """Slot order that is not image order, one slot mostly outside the image: the host entry point's image is the device entry point's,
+    bit for bit, other tiles' pixels left alone by both."""
+    sc, tiles = scenarios.shuffled_tiles(), scenarios.SHUFFLED_TILES
+    kw = dict(rays=3, pixel_samples=2, seed=6)
+    host = np.full((sc.height, sc.width), -7.0, F32)
+    devout = torch.full((sc.height, sc.width), -7.0, device=torch.device("cuda", 0))
+    rs = R.ResidentScene(sc, 0, tiles)
+    try:
+        rs.ambient_occlusion(out=host, **kw)
+        rs.ambient_occlusion(out=devout, **kw)
+        torch.cuda.synchronize()
+    finally:
+        rs.close()
+    mine = scenarios.tiles_mask(sc, tiles)
+    assert_bits(host, devout.cpu().numpy(), "tiles 3, 0")
+    assert (host[~mine] == -7.0).all() and ((host[mine] >= 0) & (host[mine] <= 1)).all() and (host[mine] < 1).any()
+
+
 def test_frames_around_an_ao_call_are_unchanged():
     sc = load_golden_scene("lambert_distant")[0]
     rs = R.ResidentScene(sc)

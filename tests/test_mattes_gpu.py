@@ -322,6 +322,27 @@ def test_disjoint_tile_deals_compose_one_image():
     assert_same({k: v.cpu().numpy().view(host[k].dtype) for k, v in dev.items()}, w, "two instances composed (device)")
 
 
+def test_host_and_device_entries_agree_on_shuffled_partial_tiles():
+    """Slot order that is not image order, one slot mostly outside the image: the host entry point's arrays are the device entry
+    point's, bit for bit, other tiles' pixels left alone by both."""
+    sc, tiles = SC.shuffled_tiles(), SC.SHUFFLED_TILES
+    H, W = sc.height, sc.width
+    host = dict(select=np.full((2, H, W), -7.0, F32), layer_id=np.full((3, H, W), 12345, np.uint32),
+                layer_coverage=np.full((3, H, W), -7.0, F32), rest=np.full((H, W), -7.0, F32))
+    dev = {k: torch.as_tensor(v.view(np.int32) if k == "layer_id" else v, device="cuda:0").clone() for k, v in host.items()}
+    rs = R.ResidentScene(sc, 0, tiles)
+    try:
+        rs.mattes(select=(5, 17), layers=3, out=host)
+        rs.mattes(select=(5, 17), layers=3, out=dev)
+        torch.cuda.synchronize()
+    finally:
+        rs.close()
+    mine = SC.tiles_mask(sc, tiles)
+    assert_same(host, {k: v.cpu().numpy().view(host[k].dtype) for k, v in dev.items()}, "tiles 3, 0")
+    assert (host["rest"][~mine] == -7.0).all() and (host["layer_id"][:, ~mine] == 12345).all() and (host["rest"][mine] >= 0).all()
+    assert (host["layer_coverage"][0][128:, 128:] > 0).any() and (host["layer_coverage"][0][:128, :128] > 0).any()
+
+
 def test_device_arrays_equal_host_arrays():
     sc = scene("B")[0]
     sel = selection(ids_of("B"), 3, sc.triangle_count)

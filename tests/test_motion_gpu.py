@@ -13,6 +13,7 @@ import torch  # (before the library loads its HIP runtime: the order bench.py us
 
 import motion_cases as MC
 import motion_oracle as MO
+import scenarios
 from opencl_render_amd import raytrace as R, scene as S
 
 pytestmark = pytest.mark.gpu
@@ -188,6 +189,30 @@ def test_instances_over_a_tile_deal_compose_and_a_peer_marks_for_itself(pair):
             p.close()
     assert_same(host, want, "two instances composed (host)")
     assert_same(to_numpy(devout), want, "two instances composed (device)")
+
+
+def test_host_and_device_entries_agree_on_shuffled_partial_tiles():
+    """Slot order that is not image order, one slot mostly outside the image: the host entry point's arrays are the device entry
+    point's, bit for bit, other tiles' pixels left alone by both."""
+    sc, tiles = scenarios.shuffled_tiles(), scenarios.SHUFFLED_TILES
+    host, devout = sentinels(sc), device_sentinels(sc)
+    rs = R.ResidentScene(sc, 0, tiles)
+    try:
+        rs.mark_motion()
+        cam = rs.camera()
+        cam["eye"] = cam["eye"] + np.asarray(cam["left_to_right"], F32) * F32(3.0)  # a small pan after the mark
+        rs.set_camera(**cam)
+        rs.motion(out=host)
+        rs.motion(out=devout)
+        torch.cuda.synchronize()
+    finally:
+        rs.close()
+    mine, keep = scenarios.tiles_mask(sc, tiles), sentinels(sc)
+    assert_same(host, to_numpy(devout), "tiles 3, 0")
+    for k in KEYS:
+        assert MO.same_bits(host[k][~mine], keep[k][~mine]).all(), k
+    seen = host["triangle"] != 0xFFFFFFFF
+    assert seen[128:, 128:].any() and seen[:128, :128].any()  # both tiles show something
 
 
 def test_nothing_else_changes():

@@ -11,6 +11,7 @@ import pytest
 
 import oracle_lib as O
 import pipeline_modes as PM
+import scenarios
 from conftest import golden_names, load_golden_scene
 from opencl_render_amd import raytrace as R, scene as S
 
@@ -576,6 +577,38 @@ def test_device_detile_store_and_accumulate(name):
         rs.close()
         L.rtHipDeviceFree(0, planes)
         L.rtHipDeviceFree(0, ids)
+
+
+def test_readback_of_shuffled_partial_tiles_equals_the_device_detile():
+    """rtHipReadback against rtHipDetile, bit for bit, where slot order is not image order and a slot is mostly outside the image: both
+    add the tiles' pixels with saturation into planes that hold 60000 already, and leave the pixels of other tiles alone."""
+    import ctypes as C
+    sc, tiles = scenarios.shuffled_tiles(), scenarios.SHUFFLED_TILES
+    L = R.lib()
+    rs = R.ResidentScene(sc, 0, tiles)
+    P = sc.pixels
+    planes = L.rtHipDeviceAlloc(0, 6 * P)
+    ids_host = np.asarray(tiles, np.uint32)
+    ids = L.rtHipDeviceAlloc(0, ids_host.nbytes)
+    assert planes and ids
+    try:
+        rs.render()
+        host = rs.readback([np.full(P, 60000, np.uint16) for _ in range(3)])
+        ptr, _ = rs.tile_buffer()
+        fill = np.full(3 * P, 60000, np.uint16)
+        assert L.rtHipDeviceCopy(0, planes, fill.ctypes.data_as(C.c_void_p), 6 * P, 1) == 0
+        assert L.rtHipDeviceCopy(0, ids, ids_host.ctypes.data_as(C.c_void_p), ids_host.nbytes, 1) == 0
+        assert L.rtHipDetile(0, ptr, ids, len(ids_host), sc.width, sc.height, planes, planes + 2 * P, planes + 4 * P, None) == 0
+        dev = np.zeros(3 * P, np.uint16)
+        assert L.rtHipDeviceCopy(0, dev.ctypes.data_as(C.c_void_p), planes, 6 * P, 0) == 0
+    finally:
+        rs.close()
+        L.rtHipDeviceFree(0, planes)
+        L.rtHipDeviceFree(0, ids)
+    mine = scenarios.tiles_mask(sc, tiles).reshape(-1)
+    for ch, h, d in zip("RGB", host, dev.reshape(3, P)):
+        assert np.array_equal(h, d), f"plane {ch}: host read-back and device de-tile differ in {int((h != d).sum())} pixels"
+        assert (h[~mine] == 60000).all() and (h[mine] > 60000).any() and (h.reshape(sc.height, sc.width)[128:, 128:] > 60000).any()
 
 
 def test_planned_frames_with_several_sample_batches(monkeypatch):

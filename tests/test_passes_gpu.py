@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import scenarios
 from conftest import ROOT, golden_names, load_golden_scene
 from opencl_render_amd import frontend as F, raytrace as R
 
@@ -146,6 +147,17 @@ def test_disjoint_tile_sets_compose():
             rs.close()
     assert_passes(parts, whole, "two instances")
     assert_passes(whole, expected("odd_size_multi_tile"), "one instance")
+
+
+def test_shuffled_partial_tiles_land_where_they_belong():
+    """Slot order that is not image order, one slot mostly outside the image: the instance's pixels are the whole image's, bit for bit,
+    and the pixels of other tiles keep what the arrays held."""
+    sc, tiles = scenarios.shuffled_tiles(), scenarios.SHUFFLED_TILES
+    whole, part = render_passes(sc)[1], render_passes(sc, tiles)[1]
+    mine = scenarios.tiles_mask(sc, tiles)
+    assert (whole["alpha"][128:, 128:] != 0).any() and (whole["alpha"][:128, :128] != 0).any()  # both tiles show something
+    assert_passes({k: v[mine] for k, v in part.items()}, {k: v[mine] for k, v in whole.items()}, "tiles 3, 0")
+    assert (part["alpha"][~mine] == 0).all() and np.isinf(part["depth"][~mine]).all() and (part["triangle"][~mine] == 0xFFFFFFFF).all()
 
 
 def test_megakernel_is_refused_and_passes_off_frees_the_buffer():

@@ -1,4 +1,4 @@
-"""CPU restatement of the property the trace kernel's ray SEGMENTATION rests on (rt_wavefront.hip: plan_ray, segments_of, cut_at, axis_state_at):
+"""CPU restatement of the property the trace kernel's ray SEGMENTATION rests on (rt_wf_shared.h: plan_ray, segments_of, cut_at, axis_state_at):
 
 The reference's grid walk (raytrace_opencl.c:383-398) is a 3-way merge of per-axis plane-crossing parameters
 T_a(i) = (plane_a[i] - o_a) / d_a, evaluated in float32 exactly as the reference does.  Per axis the sequence is

@@ -224,6 +224,17 @@ def test_disjoint_tile_sets_compose():
     assert_surface(whole, expected("odd_size_multi_tile")[0], "one instance")
 
 
+def test_shuffled_partial_tiles_land_where_they_belong():
+    """Slot order that is not image order, one slot mostly outside the image: the instance's pixels are the whole image's, bit for bit,
+    and the pixels of other tiles keep what the arrays held."""
+    sc, tiles = SC.shuffled_tiles(), SC.SHUFFLED_TILES
+    whole, part = render(sc, **ALL)[1], render(sc, tiles, **ALL)[1]
+    mine = SC.tiles_mask(sc, tiles)
+    assert whole["normal"][128:, 128:].any() and whole["normal"][:128, :128].any()  # both tiles show something
+    assert_surface(part, whole, "tiles 3, 0", pixels=np.flatnonzero(mine.reshape(-1)))
+    assert not part["normal"][~mine].any() and not part["albedo"][~mine].any()
+
+
 def test_buffers_live_while_their_passes_are_on_and_the_guards_hold():
     sc, _ = load_golden_scene("primary_only")
     rs = R.ResidentScene(sc, 0)
